@@ -25,6 +25,11 @@ names the launches that were really timed.
 latency is off the clock; HIP events on the launch stream around every launch.
 `cpu_baseline` is the C oracle (a port of the reference algorithm) on this host's cores.
 Rank 0 prints ONE JSON line.
+
+`--dump-outputs DIR` writes, after the timed region, what its LAST step returned to the caller (rank 0's envs):
+obs[B,N,12], reward[B,N], terms[3,B,N], covered[B], done[B], ep_sums[B,5] (and actions[B,N] under an in-kernel policy)
+as DIR/<name>.npy, float32.  Inputs depend only on the arguments (seeded reset and actions), so two builds can be compared
+file for file.  Beyond DUMP_MAX_BYTES a fixed, seeded sample of envs is written, with their indices in DIR/env_index.npy.
 """
 import argparse
 import json
@@ -48,6 +53,8 @@ ROOFLINE_LAUNCHES = 10         # timed launches of a roofline leg (median / min 
 # 0.51 flat right after sustained load, whatever the buffers): the power state ramps.  Every measured leg is therefore
 # preceded, without an idle gap, by this much untimed work of the same kind.
 DEVICE_WARM_MS = 60.0
+DUMP_MAX_BYTES = 64 << 20      # --dump-outputs: at most this much in all
+DUMP_KEYS = ("obs", "reward", "terms", "covered", "done", "ep_sums", "actions")
 BF16_MFMA_PEAK_TFLOPS = 2500.0
 FP32_MFMA_PEAK_TFLOPS = 157.3
 
@@ -88,6 +95,8 @@ def parse(argv=None):
     ap.add_argument("--box", type=float, default=2000.0,
                     help="side of the square field in metres (reference: 2000; 500 = the dense MAAC-R worst case of SURVEY 8d)")
     ap.add_argument("--seed", type=int, default=42)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the arrays the last timed step returned as DIR/<name>.npy (float32, rank 0, at most 64 MB)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-extras", action="store_true", help="skip per-step-launch, saturating-batch and closed-loop legs")
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
@@ -315,9 +324,43 @@ def bind_plan(env, actions, plan, ep_steps, out, device):
     return dict(launch=launches, reset=env.bind_reset(42, obs), episode=1 << 20)
 
 
-def time_config(uavtrack, args, B, steps, warmup, rollout, device, dist=None, env_offset=0, total_envs=None):
+def last_step_outputs(res):
+    """The arrays of the last step of a rollout result (a step_many / run_greedy / run_actor dict of [T, ...] outputs),
+    on the host in float32, env axis first except terms [3, B, N]; ep_sums [B, 5] is the rollout's, already per env."""
+    import numpy as np
+    out = {}
+    for k in DUMP_KEYS:
+        v = res.get(k)
+        if v is None:
+            continue
+        v = v if k == "ep_sums" else v[-1]
+        out[k] = v.detach().cpu().numpy().astype(np.float32)
+    return out
+
+
+def dump_outputs(path, arrays, max_bytes=DUMP_MAX_BYTES, seed=0):
+    """Write `arrays` (name -> float32 array whose env axis is 0, or 1 for terms) as path/<name>.npy.  If they exceed
+    `max_bytes`, a fixed seeded sample of envs (the same for every array, sorted) is written instead and its indices go to
+    path/env_index.npy.  Returns the names written."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    axis = {k: 1 if k == "terms" else 0 for k in arrays}
+    B = arrays["reward"].shape[0]
+    per_env = sum(a.nbytes for a in arrays.values()) / B
+    if per_env * B > max_bytes:
+        keep = max(1, int((max_bytes - 4096) // (per_env + 8)))     # (+ the index column; 4 KB for the .npy headers)
+        idx = np.sort(np.random.RandomState(seed).choice(B, keep, replace=False))
+        arrays = {k: np.take(a, idx, axis=axis[k]) for k, a in arrays.items()}
+        arrays["env_index"] = idx.astype(np.float64)
+    for k, a in arrays.items():
+        np.save(os.path.join(path, k + ".npy"), np.ascontiguousarray(a))
+    return sorted(arrays)
+
+
+def time_config(uavtrack, args, B, steps, warmup, rollout, device, dist=None, env_offset=0, total_envs=None, keep_outputs=False):
     """The contract's timed region: `warmup` untimed steps, then exactly `steps` steps between
-    barrier + synchronize.  Returns wall time, the plan that was timed and per-launch HIP-event times."""
+    barrier + synchronize.  Returns wall time, the plan that was timed and per-launch HIP-event times; with keep_outputs,
+    `outputs` is the host copy of what the last timed step returned (last_step_outputs), taken after the clock stopped."""
     import torch
     total_envs = total_envs or B
     env = make_env(uavtrack, args, B, device, env_offset)
@@ -375,6 +418,7 @@ def time_config(uavtrack, args, B, steps, warmup, rollout, device, dist=None, en
         dist.barrier()                    # closing bracket: no rank leaves the region before the slowest has stopped its clock
     in_region = gathers[0] - g0
     assert in_region == len(gather_points(timed_plan, pos, horizon)) >= 1
+    outputs = last_step_outputs(out[timed_plan[-1]]) if keep_outputs else None     # out[T]: the last T-step launch issued
     info = env.kernel_info()
     env.close()
     if warm is not None:
@@ -403,7 +447,8 @@ def time_config(uavtrack, args, B, steps, warmup, rollout, device, dist=None, en
             gather_info["transitions_bytes_per_rank"] = smp["actions"].shape[0] * 28 * 4
             gather_info["transitions_per_rank"] = int(smp["actions"].shape[0])
     return dict(wall_s=wall, launches=launches, steps=steps, geometry=info,
-                timed_plan=timed_plan, warm_plan=warm_plan, device_warmup=warm, gather=gather_info)
+                timed_plan=timed_plan, warm_plan=warm_plan, device_warmup=warm, gather=gather_info,
+                outputs=outputs)
 
 
 def device_warmup(uavtrack, args, B, device, warm_ms=DEVICE_WARM_MS):
@@ -933,7 +978,8 @@ def worker(args):
 
     B, N, M = args.envs, args.n_uav, args.m_targets
     res = time_config(uavtrack, args, B, args.steps, args.warmup, args.rollout, device,
-                      dist=dist if world > 1 else None, env_offset=rank * B, total_envs=world * B)
+                      dist=dist if world > 1 else None, env_offset=rank * B, total_envs=world * B,
+                      keep_outputs=bool(args.dump_outputs) and rank == 0)
     wall = torch.tensor([res["wall_s"]], dtype=torch.float64, device=device if args.backend == "nccl" else "cpu")
     rank_walls = [float(wall.item())]
     if world > 1:
@@ -1030,6 +1076,9 @@ def worker(args):
             line["cpu_baseline"] = cb
             if "value" in cb:
                 cb["gpu_over_cpu"] = value / cb["value"]
+        if args.dump_outputs:
+            names = dump_outputs(args.dump_outputs, res["outputs"])
+            line["dumped_outputs"] = {"dir": args.dump_outputs, "arrays": names, "step": "last timed step, rank 0"}
         line["configs"] = configs_summary(line, B, N, M, args)       # LAST key: the tail of stdout is what the driver's record keeps
         print(json.dumps(line), flush=True)
 
@@ -1043,6 +1092,8 @@ def main(argv=None):
     args = parse(argv)
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1:
+        raise SystemExit("--steps must be >= 1")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(spawn_ranks(args, argv))        # the parent makes no GPU call, before or after
     worker(args)

@@ -1089,6 +1089,35 @@ def test_bench_contract_line(uavtrack):
     assert [c["bound"] for c in cs] == ["hbm", "mfma", "mfma", "hbm", "mfma"]
 
 
+def test_bench_dump_outputs_reproducible(uavtrack, tmp_path):
+    """bench.py --dump-outputs: the last timed step's arrays as float32 .npy files; the same arguments give the same files
+    bit for bit, and --steps really moves the step that is dumped."""
+    import json
+    import subprocess
+    import sys
+    from conftest import ROOT
+    B, N, M = 256, 20, 10
+
+    def run(steps, d):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", str(steps), "--warmup", "5",
+                            "--envs", str(B), "--no-extras", "--no-cpu-baseline", "--no-other-configs",
+                            "--dump-outputs", str(tmp_path / d)], capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-2000:]
+        line = json.loads([ln for ln in r.stdout.splitlines() if ln.strip()][-1])
+        assert line["steps"] == steps and line["ms_per_step"] > 0.0
+        return line["dumped_outputs"]["arrays"], {k: np.load(tmp_path / d / f"{k}.npy") for k in line["dumped_outputs"]["arrays"]}
+    names, a = run(20, "a")
+    _, b = run(20, "b")
+    _, c = run(21, "c")
+    assert names == ["covered", "done", "ep_sums", "obs", "reward", "terms"]
+    shapes = dict(obs=(B, N, 12), reward=(B, N), terms=(3, B, N), covered=(B,), done=(B,), ep_sums=(B, 5))
+    for k in names:
+        assert a[k].dtype == np.float32 and a[k].shape == shapes[k], k
+        assert np.array_equal(a[k], b[k]), k
+    assert np.isfinite(a["obs"]).all() and np.all((a["done"] == 0) | (a["done"] == 1))
+    assert not np.array_equal(a["obs"], c["obs"])
+
+
 def test_example_training_loop_runs(uavtrack):
     """examples/train_maac.py: fused rollouts -> device replay -> PyTorch TD actor-critic update -> weight upload,
     a few iterations end to end; returns stay finite."""

@@ -403,6 +403,36 @@ def test_bench_launch_plan_and_cores():
     assert bench.gather_points([], 0, 200) == []
 
 
+def test_bench_dump_outputs_budget_and_sample(tmp_path):
+    """bench.dump_outputs: every array as <name>.npy, float32 as given; past the byte budget a fixed seeded sample of
+    envs, the same envs in every array (terms on its axis 1) and their indices in env_index.npy, within the budget."""
+    bench = _load_bench()
+    B, N = 500, 20
+    r = np.random.RandomState(3)
+    arrays = dict(obs=r.rand(B, N, 12).astype(np.float32), reward=r.rand(B, N).astype(np.float32),
+                  terms=r.rand(3, B, N).astype(np.float32), covered=r.randint(0, 10, B).astype(np.float32),
+                  done=np.zeros(B, np.float32), ep_sums=r.rand(B, 5).astype(np.float32))
+    names = bench.dump_outputs(str(tmp_path / "all"), arrays)
+    assert names == sorted(arrays)
+    for k, a in arrays.items():
+        got = np.load(tmp_path / "all" / f"{k}.npy")
+        assert got.dtype == np.float32 and np.array_equal(got, a)
+    budget = 100_000
+    for d in ("s1", "s2"):
+        names = bench.dump_outputs(str(tmp_path / d), arrays, max_bytes=budget)
+        assert "env_index" in names
+    total = sum(os.path.getsize(tmp_path / "s1" / f"{k}.npy") for k in names)
+    assert total <= budget
+    idx = np.load(tmp_path / "s1" / "env_index.npy")
+    assert idx.dtype == np.float64 and np.array_equal(idx, np.load(tmp_path / "s2" / "env_index.npy"))
+    i = idx.astype(np.int64)
+    assert len(i) > 1 and np.all(np.diff(i) > 0) and i[-1] < B
+    assert np.array_equal(np.load(tmp_path / "s1" / "obs.npy"), arrays["obs"][i])
+    assert np.array_equal(np.load(tmp_path / "s1" / "terms.npy"), arrays["terms"][:, i])
+    with pytest.raises(SystemExit):
+        bench.main(["--steps", "0"])
+
+
 def test_bench_gpus_n_starts_n_ranks_or_fails():
     """`python bench.py --gpus N` (no torchrun) starts N ranks itself: the launcher self-test (no GPU: gloo
     rendezvous + all-reduce) reports n_gpus == rccl_world_size == 2 on ONE line; without enough GPUs, or with a
