@@ -73,6 +73,12 @@ def main(argv=None):
     ap.add_argument("--pmi-b2", type=int, default=3000)      # PMINetwork b2_size (PMINet.py:21)
     ap.add_argument("--pmi-batch", type=int, default=500)
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--learner", choices=["torch", "device"], default="torch",
+                    help="torch: the PyTorch update below (per-sample actor loss); device: uavtrack.DeviceActorCritic, "
+                         "the whole update in one library call")
+    ap.add_argument("--actor-loss", choices=["reference", "per_sample"], default="reference",
+                    help="--learner device only: the reference's broadcast loss mean(-log p) * mean(delta), or "
+                         "mean(-log p * delta) (what the torch learner trains with)")
     args = ap.parse_args(argv)
 
     dev = "cuda:0"
@@ -91,6 +97,11 @@ def main(argv=None):
     critic = ValueNet(hidden_dim=args.hidden).to(dev)
     opt_a = torch.optim.Adam(actor.parameters(), lr=args.actor_lr)
     opt_c = torch.optim.Adam(critic.parameters(), lr=args.critic_lr)
+    learner = None
+    if args.learner == "device":
+        learner = uavtrack.DeviceActorCritic(12, args.hidden, cfg.na_total, args.actor_lr, args.critic_lr, args.gamma,
+                                             dev, loss=args.actor_loss, max_batch=args.batch)
+        actor.load_state_dict(learner.actor_state_dict())
     rollout = uavtrack.BatchedRollout(env, actor, device_actor=True, seed=args.seed)
     per_iter = args.envs * args.n_uav * args.steps
     replay = uavtrack.DeviceReplayBuffer(capacity=2 * per_iter, device=dev)
@@ -106,8 +117,14 @@ def main(argv=None):
         replay.add(uavtrack.transitions_from_rollout(obs_in, res))
         torch.cuda.synchronize()
         t_roll = time.perf_counter() - t0
-        for _ in range(args.updates):
-            la, lc = update(actor, critic, opt_a, opt_c, replay.sample(args.batch), args.gamma)
+        if learner is None:
+            for _ in range(args.updates):
+                la, lc = update(actor, critic, opt_a, opt_c, replay.sample(args.batch), args.gamma)
+        else:
+            for _ in range(args.updates):
+                la_t, lc_t, _ = learner.update_from(replay, args.batch)
+            la, lc = float(la_t), float(lc_t)
+            actor.load_state_dict(learner.actor_state_dict())     # the rollout's actor: host pack, as sync_actor
         lp = float("nan")
         if pmi is not None:                                           # PMINetwork.train_pmi on this rollout's observations
             pmi.train()

@@ -331,6 +331,79 @@ int uavtrack_kernel_info(uavtrack_env *env, int64_t out[5]);
  * All zero before the first launch. */
 int uavtrack_launch_info(uavtrack_env *env, int64_t out[4]);
 
+/* ---- the learner: ActorCritic.update + both Adam steps on the device ----
+ * A handle of its own, independent of any environment (one learner may serve sharded environments).  It holds the
+ * shared actor FnnPolicyNet (actor_critic.py:85-98: Linear(12,H) - ReLU - Linear(H,A) - softmax), the critic
+ * FnnValueNet (actor_critic.py:101-112: Linear(12,H) - ReLU - Linear(H,1)) and one torch.optim.Adam state per
+ * network (actor_critic.py:128-131: defaults betas (0.9, 0.999), eps 1e-8, no weight decay, no amsgrad).
+ * Parameter blobs are fp32 in torch order: actor fc1.weight [H][12], fc1.bias [H], fc2.weight [A][H], fc2.bias [A],
+ * then critic fc1.weight [H][12], fc1.bias [H], fc2.weight [1][H], fc2.bias [1] -- uavtrack_learner_num_params floats. */
+enum uavtrack_actor_loss {
+    UAVTRACK_LOSS_REFERENCE  = 0,   /* actor_critic.py:171: log_probs [n,1] * td_delta [n] broadcasts to [n,n]:
+                                       actor_loss = mean_i(-log p_i) * mean_j(delta_j) */
+    UAVTRACK_LOSS_PER_SAMPLE = 1    /* actor_loss = mean_i(-log p_i * delta_i) */
+};
+
+typedef struct uavtrack_learner_config {
+    uint32_t struct_size;       /* = sizeof(uavtrack_learner_config), ABI check */
+    int32_t  device_id;         /* HIP device ordinal */
+    int32_t  hidden;            /* H in [1, 256]             (actor_critic.py:120 hidden_dim) */
+    int32_t  n_actions;         /* A = na * nc in [1, 48]    (actor_critic.py:120 action_dim) */
+    int32_t  loss;              /* enum uavtrack_actor_loss */
+    int32_t  pad_;              /* 0 */
+    int64_t  max_batch;         /* scratch for batches up to this many rows; 0 = 65536 (see uavtrack_learner_reserve) */
+    double   gamma;             /* actor_critic.py:133 */
+    double   actor_lr;          /* actor_critic.py:128-129 */
+    double   critic_lr;         /* actor_critic.py:130-131 */
+} uavtrack_learner_config;
+
+typedef struct uavtrack_learner uavtrack_learner;   /* opaque handle */
+
+/* Replaces ActorCritic.__init__ (actor_critic.py:118-134).  Parameters and Adam moments start at zero, step counts
+ * at 0: upload the initial weights with uavtrack_learner_set_params.  Allocates everything an update needs. */
+int uavtrack_learner_create(const uavtrack_learner_config *cfg, uavtrack_learner **out);
+int uavtrack_learner_destroy(uavtrack_learner *learner);
+
+/* Floats in a parameter blob (= in each Adam moment blob). */
+int uavtrack_learner_num_params(uavtrack_learner *learner, int64_t *out);
+
+/* Grows the update scratch to batches of max_batch rows (allocates; synchronises the device).  Never shrinks. */
+int uavtrack_learner_reserve(uavtrack_learner *learner, int64_t max_batch);
+
+/* actor.load_state_dict + critic.load_state_dict (actor_critic.py:198, 203) / state_dict (actor_critic.py:183-190):
+ * HOST blobs of n_floats = uavtrack_learner_num_params floats in the order above.  Synchronise `stream`.  A failing
+ * set leaves the previous parameters in place. */
+int uavtrack_learner_set_params(uavtrack_learner *learner, const float *params, int64_t n_floats, void *stream);
+int uavtrack_learner_get_params(uavtrack_learner *learner, float *params, int64_t n_floats, void *stream);
+
+/* actor_optimizer / critic_optimizer .load_state_dict (actor_critic.py:199, 204) / state_dict (actor_critic.py:185,
+ * 189): exp_avg and exp_avg_sq as HOST blobs in parameter order, step [8] = the Adam step count of each parameter
+ * tensor (same order; int64, >= 0).  Synchronise `stream`.  A failing set leaves the previous state in place. */
+int uavtrack_learner_set_optimizer_state(uavtrack_learner *learner, const float *exp_avg, const float *exp_avg_sq,
+                                         const int64_t *step, int64_t n_floats, void *stream);
+int uavtrack_learner_get_optimizer_state(uavtrack_learner *learner, float *exp_avg, float *exp_avg_sq, int64_t *step,
+                                         int64_t n_floats, void *stream);
+
+/* Replaces ActorCritic.update (actor_critic.py:150-179) and the PrioritizedReplayBuffer.update_priorities call behind
+ * it (train.py:262 -> train.py:136-138), stream-ordered: no synchronisation, no allocation, capturable into a graph.
+ * Rows are gathered in the kernel from a replay ring's stores (DEVICE pointers): states / next_states [capacity][12],
+ * actions [capacity] int32, rewards [capacity]; row i of the batch is slot indices[i] (int64 [n], what the buffers'
+ * sample draws), or slot i when indices == NULL (then n <= capacity).  Outputs (DEVICE): actor_loss and critic_loss
+ * (fp32 scalars), td_delta [n] (nullable), priorities [capacity] (nullable): |td_delta| written at the sampled slots,
+ * the last occurrence of a repeated slot winning, as the reference's loop.  Both Adam steps advance their device step
+ * counts, so a replayed graph keeps counting.  Returns an error, enqueuing nothing, for a null required pointer,
+ * n < 1, or n above the reserved batch.  An action outside [0, A) or an index outside [0, capacity) is found on the
+ * device: that update then changes nothing (parameters, moments, steps, priorities), its losses are NaN, and the next
+ * uavtrack_learner_check reports it. */
+int uavtrack_learner_update(uavtrack_learner *learner, int64_t n,
+                            const float *states, const int32_t *actions, const float *rewards,
+                            const float *next_states, int64_t capacity, const int64_t *indices,
+                            float *actor_loss, float *critic_loss, float *td_delta, float *priorities, void *stream);
+
+/* Synchronises `stream`; fails if any update since the previous check was refused on the device (bad action or
+ * index).  refused (nullable) receives their number; the count restarts at 0. */
+int uavtrack_learner_check(uavtrack_learner *learner, int64_t *refused, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

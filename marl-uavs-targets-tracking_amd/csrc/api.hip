@@ -1033,3 +1033,256 @@ int uavtrack_kernel_info(uavtrack_env *env, int64_t out[5])
 }
 
 }  // extern "C"
+
+// ---- the device learner -------------------------------------------------------------------------------------------
+
+struct uavtrack_learner {
+    uavtrack_learner_config cfg;
+    LearnerDevice d;
+};
+
+namespace {
+
+void free_learner_scratch(LearnerDevice &d)
+{
+    if (d.td) (void)hipFree(d.td);
+    if (d.last) (void)hipFree(d.last);
+    d.td = nullptr; d.last = nullptr; d.max_n = 0;
+}
+
+void free_learner(uavtrack_learner *l)
+{
+    LearnerDevice &d = l->d;
+    free_learner_scratch(d);
+    for (void *p : {(void *)d.params, (void *)d.m, (void *)d.v, (void *)d.steps, (void *)d.partials, (void *)d.scal,
+                    (void *)d.status, (void *)d.errors})
+        if (p) (void)hipFree(p);
+}
+
+constexpr int64_t kLearnerDefaultBatch = 65536;
+constexpr int64_t kLearnerMaxBatch = ((int64_t)1 << 31) - 1;   // row numbers are int32 in the priority write
+
+hipError_t learner_scratch(LearnerDevice &d, int64_t max_n)
+{
+    float *td = nullptr;
+    uint8_t *last = nullptr;
+    hipError_t e = dmalloc(&td, (size_t)max_n);
+    if (e == hipSuccess) e = dmalloc(&last, (size_t)max_n);
+    if (e != hipSuccess) {
+        if (td) (void)hipFree(td);
+        return e;
+    }
+    free_learner_scratch(d);
+    d.td = td; d.last = last; d.max_n = max_n;
+    return hipSuccess;
+}
+
+}  // namespace
+
+extern "C" {
+
+int uavtrack_learner_create(const uavtrack_learner_config *cfg, uavtrack_learner **out)
+{
+    if (!cfg || !out) return fail("uavtrack_learner_create: null argument");
+    *out = nullptr;
+    if (cfg->struct_size != sizeof(uavtrack_learner_config))
+        return fail("uavtrack_learner_create: struct_size %u != %zu (header / library mismatch)", cfg->struct_size,
+                    sizeof(uavtrack_learner_config));
+    if (cfg->hidden < 1 || cfg->hidden > kLearnerMaxHidden)
+        return fail("uavtrack_learner_create: hidden %d out of range [1, %d]", cfg->hidden, kLearnerMaxHidden);
+    if (cfg->n_actions < 1 || cfg->n_actions > kLearnerMaxActions)
+        return fail("uavtrack_learner_create: n_actions %d out of range [1, %d]", cfg->n_actions, kLearnerMaxActions);
+    if (cfg->loss != UAVTRACK_LOSS_REFERENCE && cfg->loss != UAVTRACK_LOSS_PER_SAMPLE)
+        return fail("uavtrack_learner_create: unknown loss form %d", cfg->loss);
+    if (cfg->max_batch < 0 || cfg->max_batch > kLearnerMaxBatch)
+        return fail("uavtrack_learner_create: max_batch %lld out of range [0, %lld]", (long long)cfg->max_batch,
+                    (long long)kLearnerMaxBatch);
+    if (!std::isfinite(cfg->gamma) || !std::isfinite(cfg->actor_lr) || !std::isfinite(cfg->critic_lr) ||
+        cfg->actor_lr < 0 || cfg->critic_lr < 0)
+        return fail("uavtrack_learner_create: gamma and the learning rates must be finite, the rates >= 0");
+
+    int ndev = 0;
+    hipError_t e = hipGetDeviceCount(&ndev);
+    if (e != hipSuccess || ndev < 1)
+        return fail("uavtrack_learner_create: no HIP device visible (%s); libuavtrack has no CPU fallback",
+                    e != hipSuccess ? hipGetErrorString(e) : "device count 0");
+    if (cfg->device_id < 0 || cfg->device_id >= ndev)
+        return fail("uavtrack_learner_create: device_id %d out of range [0, %d)", cfg->device_id, ndev);
+    ON_DEVICE(cfg->device_id);
+    hipDeviceProp_t prop;
+    HIP_TRY(hipGetDeviceProperties(&prop, cfg->device_id));
+    if (strncmp(prop.gcnArchName, "gfx950", 6) != 0)
+        return fail("uavtrack_learner_create: device %d is %s; this library is built for gfx950 only", cfg->device_id,
+                    prop.gcnArchName);
+
+    uavtrack_learner *l = new (std::nothrow) uavtrack_learner();
+    if (!l) return fail("uavtrack_learner_create: out of host memory");
+    l->cfg = *cfg;
+    LearnerDevice &d = l->d;
+    d.L = LearnerLayout::make(cfg->hidden, cfg->n_actions);
+    d.gamma = (float)cfg->gamma;
+    d.actor_lr = (float)cfg->actor_lr;
+    d.critic_lr = (float)cfg->critic_lr;
+    d.per_sample = cfg->loss == UAVTRACK_LOSS_PER_SAMPLE;
+    const size_t P = (size_t)d.L.P;
+    hipError_t he = hipSuccess;
+    if (he == hipSuccess) he = dmalloc(&d.params, P);
+    if (he == hipSuccess) he = dmalloc(&d.m, P);
+    if (he == hipSuccess) he = dmalloc(&d.v, P);
+    if (he == hipSuccess) he = dmalloc(&d.steps, (size_t)kLearnerTensors);
+    if (he == hipSuccess) he = dmalloc(&d.partials, (size_t)kLearnerMaxGroups * (P + 4));
+    if (he == hipSuccess) he = dmalloc(&d.scal, (size_t)2);
+    if (he == hipSuccess) he = dmalloc(&d.status, (size_t)1);
+    if (he == hipSuccess) he = dmalloc(&d.errors, (size_t)1);
+    if (he == hipSuccess) he = learner_scratch(d, cfg->max_batch ? cfg->max_batch : kLearnerDefaultBatch);
+    if (he == hipSuccess) he = hipMemset(d.params, 0, P * 4);
+    if (he == hipSuccess) he = hipMemset(d.m, 0, P * 4);
+    if (he == hipSuccess) he = hipMemset(d.v, 0, P * 4);
+    if (he == hipSuccess) he = hipMemset(d.steps, 0, kLearnerTensors * 8);
+    if (he == hipSuccess) he = hipMemset(d.errors, 0, 4);
+    if (he == hipSuccess) he = hipMemset(d.status, 0, 4);
+    if (he == hipSuccess) he = learner_prepare_kernels(d.L);
+    if (he == hipSuccess) he = hipDeviceSynchronize();
+    if (he != hipSuccess) {
+        free_learner(l);
+        delete l;
+        return fail("uavtrack_learner_create: %s", hipGetErrorString(he));
+    }
+    *out = l;
+    return 0;
+}
+
+int uavtrack_learner_destroy(uavtrack_learner *learner)
+{
+    if (!learner) return 0;
+    DeviceGuard guard(learner->cfg.device_id);
+    (void)hipDeviceSynchronize();
+    free_learner(learner);
+    delete learner;
+    return 0;
+}
+
+int uavtrack_learner_num_params(uavtrack_learner *learner, int64_t *out)
+{
+    if (!learner || !out) return fail("uavtrack_learner_num_params: null argument");
+    *out = learner->d.L.P;
+    return 0;
+}
+
+int uavtrack_learner_reserve(uavtrack_learner *learner, int64_t max_batch)
+{
+    if (!learner) return fail("uavtrack_learner_reserve: null handle");
+    if (max_batch < 1 || max_batch > kLearnerMaxBatch)
+        return fail("uavtrack_learner_reserve: max_batch %lld out of range [1, %lld]", (long long)max_batch,
+                    (long long)kLearnerMaxBatch);
+    if (max_batch <= learner->d.max_n) return 0;
+    ON_DEVICE(learner->cfg.device_id);
+    HIP_TRY(hipDeviceSynchronize());          // in-flight updates may still read the old scratch
+    HIP_TRY(learner_scratch(learner->d, max_batch));
+    return 0;
+}
+
+int uavtrack_learner_set_params(uavtrack_learner *learner, const float *params, int64_t n_floats, void *stream)
+{
+    if (!learner || !params) return fail("uavtrack_learner_set_params: null argument");
+    if (n_floats != learner->d.L.P)
+        return fail("uavtrack_learner_set_params: %lld floats, the networks have %d", (long long)n_floats, learner->d.L.P);
+    ON_DEVICE(learner->cfg.device_id);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    HIP_TRY(hipStreamSynchronize(st));
+    HIP_TRY(hipMemcpyAsync(learner->d.params, params, (size_t)n_floats * 4, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return 0;
+}
+
+int uavtrack_learner_get_params(uavtrack_learner *learner, float *params, int64_t n_floats, void *stream)
+{
+    if (!learner || !params) return fail("uavtrack_learner_get_params: null argument");
+    if (n_floats != learner->d.L.P)
+        return fail("uavtrack_learner_get_params: %lld floats, the networks have %d", (long long)n_floats, learner->d.L.P);
+    ON_DEVICE(learner->cfg.device_id);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    HIP_TRY(hipMemcpyAsync(params, learner->d.params, (size_t)n_floats * 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return 0;
+}
+
+int uavtrack_learner_set_optimizer_state(uavtrack_learner *learner, const float *exp_avg, const float *exp_avg_sq,
+                                         const int64_t *step, int64_t n_floats, void *stream)
+{
+    if (!learner || !exp_avg || !exp_avg_sq || !step) return fail("uavtrack_learner_set_optimizer_state: null argument");
+    LearnerDevice &d = learner->d;
+    if (n_floats != d.L.P)
+        return fail("uavtrack_learner_set_optimizer_state: %lld floats, the networks have %d", (long long)n_floats, d.L.P);
+    for (int t = 0; t < kLearnerTensors; ++t)
+        if (step[t] < 0) return fail("uavtrack_learner_set_optimizer_state: step[%d] = %lld < 0", t, (long long)step[t]);
+    for (int64_t p = 0; p < n_floats; ++p)
+        if (!(exp_avg_sq[p] >= 0.0f)) return fail("uavtrack_learner_set_optimizer_state: exp_avg_sq[%lld] is not >= 0", (long long)p);
+    ON_DEVICE(learner->cfg.device_id);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    HIP_TRY(hipStreamSynchronize(st));
+    HIP_TRY(hipMemcpyAsync(d.m, exp_avg, (size_t)n_floats * 4, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(d.v, exp_avg_sq, (size_t)n_floats * 4, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(d.steps, step, kLearnerTensors * 8, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return 0;
+}
+
+int uavtrack_learner_get_optimizer_state(uavtrack_learner *learner, float *exp_avg, float *exp_avg_sq, int64_t *step,
+                                         int64_t n_floats, void *stream)
+{
+    if (!learner || !exp_avg || !exp_avg_sq || !step) return fail("uavtrack_learner_get_optimizer_state: null argument");
+    LearnerDevice &d = learner->d;
+    if (n_floats != d.L.P)
+        return fail("uavtrack_learner_get_optimizer_state: %lld floats, the networks have %d", (long long)n_floats, d.L.P);
+    ON_DEVICE(learner->cfg.device_id);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    HIP_TRY(hipMemcpyAsync(exp_avg, d.m, (size_t)n_floats * 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(exp_avg_sq, d.v, (size_t)n_floats * 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(step, d.steps, kLearnerTensors * 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return 0;
+}
+
+int uavtrack_learner_update(uavtrack_learner *learner, int64_t n, const float *states, const int32_t *actions,
+                            const float *rewards, const float *next_states, int64_t capacity, const int64_t *indices,
+                            float *actor_loss, float *critic_loss, float *td_delta, float *priorities, void *stream)
+{
+    if (!learner) return fail("uavtrack_learner_update: null handle");
+    if (!states || !actions || !rewards || !next_states)
+        return fail("uavtrack_learner_update: states, actions, rewards and next_states must not be null");
+    if (!actor_loss || !critic_loss) return fail("uavtrack_learner_update: actor_loss and critic_loss must not be null");
+    if (n < 1) return fail("uavtrack_learner_update: n = %lld < 1", (long long)n);
+    if (n > learner->d.max_n)
+        return fail("uavtrack_learner_update: n = %lld rows, scratch is reserved for %lld (uavtrack_learner_reserve)",
+                    (long long)n, (long long)learner->d.max_n);
+    if (capacity < 1) return fail("uavtrack_learner_update: capacity = %lld < 1", (long long)capacity);
+    if (!indices && n > capacity)
+        return fail("uavtrack_learner_update: n = %lld rows without indices from a store of %lld", (long long)n,
+                    (long long)capacity);
+    ON_DEVICE(learner->cfg.device_id);
+    LearnerLaunch q;
+    q.n = n; q.capacity = capacity;
+    q.states = states; q.rewards = rewards; q.next_states = next_states; q.actions = actions; q.idx = indices;
+    q.actor_loss = actor_loss; q.critic_loss = critic_loss; q.td_delta = td_delta; q.priorities = priorities;
+    HIP_TRY(launch_learner_update(learner->d, q, static_cast<hipStream_t>(stream)));
+    return 0;
+}
+
+int uavtrack_learner_check(uavtrack_learner *learner, int64_t *refused, void *stream)
+{
+    if (!learner) return fail("uavtrack_learner_check: null handle");
+    ON_DEVICE(learner->cfg.device_id);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    int count = 0;
+    HIP_TRY(hipMemcpyAsync(&count, learner->d.errors, 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemsetAsync(learner->d.errors, 0, 4, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (refused) *refused = count;
+    if (count)
+        return fail("uavtrack_learner_check: %d update(s) refused: an action outside [0, %d) or an index outside "
+                    "[0, capacity); they changed nothing", count, learner->d.L.A);
+    return 0;
+}
+
+}  // extern "C"

@@ -230,4 +230,63 @@ hipError_t launch_actor(const uavtrack_env *env, const float *obs, uint64_t seed
 hipError_t launch_reset(const uavtrack_env *env, uint64_t seed, uint32_t episode, float *obs,
                         hipStream_t stream);
 
+// learner_kernel.hip -- the device learner (uavtrack_learner_*).  Both networks' parameters live in one fp32 array in
+// torch order: actor fc1.weight [H][12], fc1.bias [H], fc2.weight [A][H], fc2.bias [A], then critic fc1.weight [H][12],
+// fc1.bias [H], fc2.weight [1][H], fc2.bias [1]; the Adam moments use the same order.
+constexpr int kLearnerTensors = 8;
+constexpr int kLearnerMaxHidden = 256;
+constexpr int kLearnerMaxActions = 48;
+constexpr int kLearnerMaxGroups = 256;        // workgroups of the gradient kernel (= gradient partial rows)
+struct LearnerLayout {
+    int H, A, P;
+    int a_w1, a_b1, a_w2, a_b2, c_w1, c_b1, c_w2, c_b2;
+    static LearnerLayout make(int H, int A)
+    {
+        LearnerLayout L;
+        L.H = H; L.A = A;
+        L.a_w1 = 0; L.a_b1 = 12 * H; L.a_w2 = 13 * H; L.a_b2 = 13 * H + A * H;
+        L.c_w1 = L.a_b2 + A; L.c_b1 = L.c_w1 + 12 * H; L.c_w2 = L.c_b1 + H; L.c_b2 = L.c_w2 + H;
+        L.P = L.c_b2 + 1;
+        return L;
+    }
+    __host__ __device__ int offset(int t) const
+    {
+        const int o[kLearnerTensors] = {a_w1, a_b1, a_w2, a_b2, c_w1, c_b1, c_w2, c_b2};
+        return o[t];
+    }
+    __host__ __device__ int tensor_of(int p) const
+    {
+        int t = 0;
+        while (t + 1 < kLearnerTensors && p >= offset(t + 1)) ++t;
+        return t;
+    }
+};
+// the device state of one learner handle
+struct LearnerDevice {
+    LearnerLayout L;
+    float gamma, actor_lr, critic_lr;
+    int per_sample;
+    float *params, *m, *v;          // [P]
+    int64_t *steps;                 // [kLearnerTensors] Adam step per parameter tensor
+    float *partials;                // [kLearnerMaxGroups][P + 4]
+    float *scal;                    // [2] gradient scales of the current update
+    float *td;                      // [max_n] td_delta when the caller passes none
+    uint8_t *last;                  // [max_n] last-occurrence marks of the priority write
+    int *status;                    // [1] this update's input errors
+    int *errors;                    // [1] updates refused since the last uavtrack_learner_check
+    int64_t max_n;
+};
+struct LearnerLaunch {
+    int64_t n, capacity;
+    const float *states, *rewards, *next_states;
+    const int32_t *actions;
+    const int64_t *idx;
+    float *actor_loss, *critic_loss, *td_delta, *priorities;
+};
+int learner_rows_per_tile(int hidden);
+size_t learner_lds_bytes(const LearnerLayout &L, int rows);
+int learner_groups(const LearnerLayout &L, int64_t n);
+hipError_t learner_prepare_kernels(const LearnerLayout &L);
+hipError_t launch_learner_update(const LearnerDevice &d, const LearnerLaunch &q, hipStream_t stream);
+
 }  // namespace uavtrack

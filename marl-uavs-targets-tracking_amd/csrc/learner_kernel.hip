@@ -1,0 +1,377 @@
+// learner_kernel.hip -- ActorCritic.update (actor_critic.py:150-179) and both torch.optim.Adam steps on the device,
+// plus the PrioritizedReplayBuffer.update_priorities write of train.py:262 (train.py:136-138).
+//
+// One update is a chain of stream-ordered launches (a one-thread kernel clears the status word first), none of which synchronises or allocates:
+//   learner_grad_kernel      rows gathered through the index vector, tiled R rows at a time per workgroup: both
+//                            forwards (critic on s and s', actor on s), softmax, TD error, both backwards; every
+//                            gradient sum of the tile is added into the workgroup's LDS accumulators (each
+//                            parameter owned by one thread, so the order of the adds is fixed), and the workgroup
+//                            writes one partial row [P + 4] (gradients, then the four loss sums) at the end;
+//   learner_finalize_kernel  the loss partials summed in workgroup order -> losses, mean(delta), step counters;
+//   learner_adam_kernel      per parameter: the gradient partials summed in workgroup order, scaled, Adam;
+//   learner_prio_*           |delta| into the priorities at the sampled slots, the last occurrence of a slot in the
+//                            batch winning (a claim / max-row / mark / write chain: no float atomics anywhere).
+// Nothing depends on timing, so two identical calls give bitwise identical results.
+//
+// The sums are arranged so the reference's broadcast actor loss costs nothing extra: with
+// actor_loss = mean_i(-log p_i) * mean_j(delta_j), dL/dz_i = -mean(delta) (onehot(a_i) - p_i) / n, so the grad kernel
+// accumulates (onehot - p) and the Adam kernel multiplies by -mean(delta) / n once.  Per-sample: delta_i (onehot - p)
+// is accumulated and scaled by -1 / n.  The critic accumulates (V - target) and is scaled by 2 / n.
+
+#include "internal.h"
+
+#include <hip/hip_runtime.h>
+#include <cmath>
+#include <cstdint>
+
+namespace uavtrack {
+
+namespace {
+
+constexpr int kLW = 256;   // threads per workgroup of the grad kernel
+
+// the launch's shape, folded on the host
+struct GradArgs {
+    const float *params;            // [P] both networks, LearnerLayout order
+    const float *states, *rewards, *next_states;
+    const int32_t *actions;
+    const int64_t *idx;             // nullable: rows 0..n-1
+    int64_t n, capacity;
+    float *partials;                // [groups][P + 4]
+    float *td_delta;                // nullable [n]
+    int *status;                    // bit 0: action out of range, bit 1: index out of range
+    LearnerLayout L;
+    int rows;                       // R rows per tile
+    float gamma;
+    int per_sample;
+};
+
+__global__ void __launch_bounds__(kLW) learner_grad_kernel(GradArgs a)
+{
+    extern __shared__ float lds[];
+    const LearnerLayout &L = a.L;
+    const int H = L.H, A = L.A, R = a.rows, P = L.P;
+    float *acc = lds;                       // [P]
+    float *s   = acc + P;                   // [R][12]
+    float *s2  = s + R * 12;                // [R][12]
+    float *ha  = s2 + R * 12;               // [R][H]  actor hidden (post-ReLU)
+    float *hc  = ha + R * H;                // [R][H]  critic hidden on s
+    float *hx  = hc + R * H;                // [R][H]  critic hidden on s', then the actor's dL/dh
+    float *gz  = hx + R * H;                // [R][A]  logits, then the accumulated logit weights
+    float *gv  = gz + R * A;                // [R]     V, then (V - target)
+    float *vn  = gv + R;                    // [R]     V'
+    float *lt  = vn + R;                    // [R][4]  per-row loss terms
+    int *act   = reinterpret_cast<int *>(lt + R * 4);   // [R] action, -1 = row not used
+
+    const int tid = threadIdx.x;
+    const float *W1a = a.params + L.a_w1, *b1a = a.params + L.a_b1, *W2a = a.params + L.a_w2, *b2a = a.params + L.a_b2;
+    const float *W1c = a.params + L.c_w1, *b1c = a.params + L.c_b1, *W2c = a.params + L.c_w2, *b2c = a.params + L.c_b2;
+
+    for (int p = tid; p < P; p += kLW) acc[p] = 0.0f;
+    float loss_run[4] = {0.0f, 0.0f, 0.0f, 0.0f};   // thread 0's running sums, tile after tile
+
+    const int64_t tiles = (a.n + R - 1) / R;
+    for (int64_t t = blockIdx.x; t < tiles; t += gridDim.x) {
+        const int64_t row0 = t * R;
+        // ---- gather the tile: states, next states, action, reward
+        for (int r = tid; r < R; r += kLW) {
+            const int64_t i = row0 + r;
+            int av = -1;
+            if (i < a.n) {
+                const int64_t src = a.idx ? a.idx[i] : i;
+                if (src < 0 || src >= a.capacity) {
+                    atomicOr(a.status, 2);
+                } else {
+                    av = a.actions[src];
+                    if (av < 0 || av >= A) { atomicOr(a.status, 1); av = -1; }
+                    vn[r] = a.rewards[src];               // the reward waits in vn until V' overwrites it
+                }
+                for (int k = 0; k < 12; ++k) {
+                    s[r * 12 + k]  = av >= 0 ? a.states[src * 12 + k] : 0.0f;
+                    s2[r * 12 + k] = av >= 0 ? a.next_states[src * 12 + k] : 0.0f;
+                }
+            } else {
+                for (int k = 0; k < 12; ++k) { s[r * 12 + k] = 0.0f; s2[r * 12 + k] = 0.0f; }
+            }
+            if (av < 0) vn[r] = 0.0f;
+            act[r] = av;
+        }
+        __syncthreads();
+        // ---- layer 1 of the three forwards
+        for (int e = tid; e < R * H; e += kLW) {
+            const int r = e / H, j = e - r * H;
+            float pa = b1a[j], pc = b1c[j], pn = b1c[j];
+            for (int k = 0; k < 12; ++k) {
+                pa = fmaf(W1a[j * 12 + k], s[r * 12 + k], pa);
+                pc = fmaf(W1c[j * 12 + k], s[r * 12 + k], pc);
+                pn = fmaf(W1c[j * 12 + k], s2[r * 12 + k], pn);
+            }
+            ha[e] = fmaxf(pa, 0.0f);
+            hc[e] = fmaxf(pc, 0.0f);
+            hx[e] = fmaxf(pn, 0.0f);
+        }
+        __syncthreads();
+        // ---- layer 2: A logits, V, V' per row (the reward moves from vn to lt[.][0] first)
+        for (int r = tid; r < R; r += kLW) lt[r * 4] = vn[r];
+        __syncthreads();
+        const int O = A + 2;
+        for (int e = tid; e < R * O; e += kLW) {
+            const int r = e / O, o = e - r * O;
+            const float *h = o < A ? ha + r * H : (o == A ? hc + r * H : hx + r * H);
+            const float *w = o < A ? W2a + o * H : W2c;
+            float z = o < A ? b2a[o] : b2c[0];
+            for (int j = 0; j < H; ++j) z = fmaf(w[j], h[j], z);
+            if (o < A) gz[r * A + o] = z;
+            else if (o == A) gv[r] = z;
+            else vn[r] = z;
+        }
+        __syncthreads();
+        // ---- per row: softmax, log p_a, TD error, the logit and value weights of the backward pass
+        for (int r = tid; r < R; r += kLW) {
+            const int av = act[r];
+            const float rew = lt[r * 4];
+            float *z = gz + r * A;
+            if (av < 0) {
+                for (int o = 0; o < A; ++o) z[o] = 0.0f;
+                gv[r] = 0.0f;
+                lt[r * 4 + 0] = lt[r * 4 + 1] = lt[r * 4 + 2] = lt[r * 4 + 3] = 0.0f;
+                continue;
+            }
+            float m = z[0];
+            for (int o = 1; o < A; ++o) m = fmaxf(m, z[o]);
+            float sum = 0.0f;
+            for (int o = 0; o < A; ++o) { z[o] = expf(z[o] - m); sum += z[o]; }
+            const float inv = 1.0f / sum;
+            const float target = rew + a.gamma * vn[r];
+            const float v = gv[r];
+            const float delta = target - v;
+            const float nlp = -logf(z[av] * inv);
+            const float w = a.per_sample ? delta : 1.0f;
+            for (int o = 0; o < A; ++o) z[o] = w * ((o == av ? 1.0f : 0.0f) - z[o] * inv);
+            gv[r] = v - target;
+            lt[r * 4 + 0] = nlp;
+            lt[r * 4 + 1] = delta;
+            lt[r * 4 + 2] = nlp * delta;
+            lt[r * 4 + 3] = (v - target) * (v - target);
+            if (a.td_delta) a.td_delta[row0 + r] = delta;
+        }
+        __syncthreads();
+        if (tid == 0)
+            for (int r = 0; r < R; ++r)
+                for (int q = 0; q < 4; ++q) loss_run[q] += lt[r * 4 + q];
+        // ---- the actor's dL/dh (up to the -scale / n of the Adam kernel), masked by its ReLU; over hx
+        for (int e = tid; e < R * H; e += kLW) {
+            const int r = e / H, j = e - r * H;
+            float d = 0.0f;
+            if (ha[e] > 0.0f)
+                for (int o = 0; o < A; ++o) d = fmaf(W2a[o * H + j], gz[r * A + o], d);
+            hx[e] = d;
+        }
+        __syncthreads();
+        // ---- the tile's gradient sums into the accumulators, one owner thread per parameter, rows in order
+        for (int p = tid; p < 12 * H; p += kLW) {           // actor fc1.weight [H][12]
+            const int j = p / 12, k = p - j * 12;
+            float g = acc[L.a_w1 + p];
+            for (int r = 0; r < R; ++r) g = fmaf(hx[r * H + j], s[r * 12 + k], g);
+            acc[L.a_w1 + p] = g;
+        }
+        for (int j = tid; j < H; j += kLW) {                // actor fc1.bias, critic fc1.bias, critic fc2.weight
+            float ga = acc[L.a_b1 + j], gb = acc[L.c_b1 + j], gw = acc[L.c_w2 + j];
+            const float w2 = W2c[j];
+            for (int r = 0; r < R; ++r) {
+                ga += hx[r * H + j];
+                gb += hc[r * H + j] > 0.0f ? gv[r] * w2 : 0.0f;
+                gw = fmaf(gv[r], hc[r * H + j], gw);
+            }
+            acc[L.a_b1 + j] = ga; acc[L.c_b1 + j] = gb; acc[L.c_w2 + j] = gw;
+        }
+        for (int p = tid; p < A * H; p += kLW) {            // actor fc2.weight [A][H]
+            const int o = p / H, j = p - o * H;
+            float g = acc[L.a_w2 + p];
+            for (int r = 0; r < R; ++r) g = fmaf(gz[r * A + o], ha[r * H + j], g);
+            acc[L.a_w2 + p] = g;
+        }
+        for (int o = tid; o < A; o += kLW) {                // actor fc2.bias
+            float g = acc[L.a_b2 + o];
+            for (int r = 0; r < R; ++r) g += gz[r * A + o];
+            acc[L.a_b2 + o] = g;
+        }
+        for (int p = tid; p < 12 * H; p += kLW) {           // critic fc1.weight [H][12]
+            const int j = p / 12, k = p - j * 12;
+            float g = acc[L.c_w1 + p];
+            const float w2 = W2c[j];
+            for (int r = 0; r < R; ++r)
+                if (hc[r * H + j] > 0.0f) g = fmaf(gv[r] * w2, s[r * 12 + k], g);
+            acc[L.c_w1 + p] = g;
+        }
+        if (tid == 0) {                                     // critic fc2.bias
+            float g = acc[L.c_b2];
+            for (int r = 0; r < R; ++r) g += gv[r];
+            acc[L.c_b2] = g;
+        }
+        __syncthreads();
+    }
+    float *out = a.partials + (size_t)blockIdx.x * (P + 4);
+    for (int p = tid; p < P; p += kLW) out[p] = acc[p];
+    if (tid == 0)
+        for (int q = 0; q < 4; ++q) out[P + q] = loss_run[q];
+}
+
+// Clears the update's status word (a kernel node rather than a memset node, so a captured update is a chain of kernels)
+__global__ void learner_begin_kernel(int *status)
+{
+    if (threadIdx.x == 0 && blockIdx.x == 0) *status = 0;
+}
+
+// One thread: losses, mean(delta), the per-call status into the sticky error count, the step counters.
+__global__ void learner_finalize_kernel(const float *partials, int groups, LearnerLayout L, int64_t n, int per_sample,
+                                        const int *status, int *errors, int64_t *steps, float *scal,
+                                        float *actor_loss, float *critic_loss)
+{
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    float sum[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+    for (int g = 0; g < groups; ++g)
+        for (int q = 0; q < 4; ++q) sum[q] += partials[(size_t)g * (L.P + 4) + L.P + q];
+    const float inv_n = 1.0f / (float)n;
+    const float mean_nlp = sum[0] * inv_n, mean_delta = sum[1] * inv_n;
+    const float al = per_sample ? sum[2] * inv_n : mean_nlp * mean_delta;
+    const float cl = sum[3] * inv_n;
+    const int bad = *status;
+    if (actor_loss) *actor_loss = bad ? NAN : al;
+    if (critic_loss) *critic_loss = bad ? NAN : cl;
+    // gradient scales of the Adam kernel: actor, critic
+    scal[0] = per_sample ? -inv_n : -mean_delta * inv_n;
+    scal[1] = 2.0f * inv_n;
+    if (bad) { *errors += 1; return; }
+    for (int q = 0; q < kLearnerTensors; ++q) steps[q] += 1;
+}
+
+// torch.optim.Adam (defaults: betas (0.9, 0.999), eps 1e-8, no weight decay, no amsgrad), the single-tensor and
+// foreach forms' arithmetic: m.lerp_(g, 1 - b1); v = v * b2 + (1 - b2) g^2; p -= (lr / bc1) * m / (sqrt(v) / sqrt(bc2) + eps)
+// with bc = 1 - b^step in double precision on the host side of torch (here: on the device, from the device step count).
+__global__ void learner_adam_kernel(float *params, float *m, float *v, const float *partials, int groups, LearnerLayout L,
+                                    const int *status, const int64_t *steps, const float *scal, float actor_lr, float critic_lr)
+{
+    const int p = blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= L.P || *status) return;
+    float g = 0.0f;
+    for (int w = 0; w < groups; ++w) g += partials[(size_t)w * (L.P + 4) + p];
+    const bool actor = p < L.c_w1;
+    g *= actor ? scal[0] : scal[1];
+    const int tensor = L.tensor_of(p);
+    const double step = (double)steps[tensor];
+    const double bc1 = 1.0 - pow(0.9, step), bc2 = 1.0 - pow(0.999, step);
+    const float step_size = (float)((actor ? (double)actor_lr : (double)critic_lr) / bc1);
+    const float bc2_sqrt = (float)sqrt(bc2);
+    float mi = m[p];
+    mi = mi + 0.1f * (g - mi);                              // lerp with weight 1 - 0.9 < 0.5
+    const float vi = v[p] * 0.999f + 0.001f * g * g;
+    const float denom = sqrtf(vi) / bc2_sqrt + 1e-8f;
+    params[p] = params[p] - step_size * (mi / denom);
+    m[p] = mi;
+    v[p] = vi;
+}
+
+// the priorities: claim every sampled slot, keep the largest batch row per slot, mark it, write |delta| from it
+__global__ void learner_prio_claim_kernel(const int64_t *idx, int64_t n, int64_t capacity, float *prio, const int *status)
+{
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n || *status) return;
+    const int64_t slot = idx ? idx[i] : i;
+    if (slot >= 0 && slot < capacity) reinterpret_cast<int *>(prio)[slot] = -1;
+}
+
+__global__ void learner_prio_max_kernel(const int64_t *idx, int64_t n, int64_t capacity, float *prio, const int *status)
+{
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n || *status) return;
+    const int64_t slot = idx ? idx[i] : i;
+    if (slot >= 0 && slot < capacity) atomicMax(reinterpret_cast<int *>(prio) + slot, (int)i);
+}
+
+__global__ void learner_prio_mark_kernel(const int64_t *idx, int64_t n, int64_t capacity, const float *prio,
+                                         uint8_t *last, const int *status)
+{
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n || *status) return;
+    const int64_t slot = idx ? idx[i] : i;
+    last[i] = (slot >= 0 && slot < capacity && reinterpret_cast<const int *>(prio)[slot] == (int)i) ? 1 : 0;
+}
+
+__global__ void learner_prio_write_kernel(const int64_t *idx, int64_t n, const float *td, float *prio,
+                                          const uint8_t *last, const int *status)
+{
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n || *status) return;
+    if (last[i]) prio[idx ? idx[i] : i] = fabsf(td[i]);
+}
+
+}  // namespace
+
+int learner_rows_per_tile(int hidden)
+{
+    const int r = 4096 / (hidden < 16 ? 16 : hidden);
+    return r > 256 ? 256 : r;
+}
+
+size_t learner_lds_bytes(const LearnerLayout &L, int rows)
+{
+    return sizeof(float) * ((size_t)L.P + (size_t)rows * (24 + 3 * L.H + L.A + 2 + 4)) + sizeof(int) * (size_t)rows;
+}
+
+int learner_groups(const LearnerLayout &L, int64_t n)
+{
+    const int64_t R = learner_rows_per_tile(L.H);
+    const int64_t tiles = (n + R - 1) / R;
+    return (int)(tiles < kLearnerMaxGroups ? tiles : kLearnerMaxGroups);
+}
+
+hipError_t learner_prepare_kernels(const LearnerLayout &L)
+{
+    const size_t lds = learner_lds_bytes(L, learner_rows_per_tile(L.H));
+    return hipFuncSetAttribute(reinterpret_cast<const void *>(learner_grad_kernel),
+                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+}
+
+hipError_t launch_learner_update(const LearnerDevice &d, const LearnerLaunch &q, hipStream_t st)
+{
+    const LearnerLayout &L = d.L;
+    const int R = learner_rows_per_tile(L.H);
+    const int groups = learner_groups(L, q.n);
+    hipLaunchKernelGGL(learner_begin_kernel, dim3(1), dim3(64), 0, st, d.status);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+
+    GradArgs a;
+    a.params = d.params; a.states = q.states; a.rewards = q.rewards; a.next_states = q.next_states;
+    a.actions = q.actions; a.idx = q.idx; a.n = q.n; a.capacity = q.capacity;
+    a.partials = d.partials; a.td_delta = q.td_delta ? q.td_delta : d.td; a.status = d.status;
+    a.L = L; a.rows = R; a.gamma = d.gamma; a.per_sample = d.per_sample;
+    hipLaunchKernelGGL(learner_grad_kernel, dim3(groups), dim3(kLW), learner_lds_bytes(L, R), st, a);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+
+    hipLaunchKernelGGL(learner_finalize_kernel, dim3(1), dim3(64), 0, st, d.partials, groups, L, q.n, d.per_sample,
+                       d.status, d.errors, d.steps, d.scal, q.actor_loss, q.critic_loss);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+
+    hipLaunchKernelGGL(learner_adam_kernel, dim3((L.P + 255) / 256), dim3(256), 0, st, d.params, d.m, d.v, d.partials,
+                       groups, L, d.status, d.steps, d.scal, d.actor_lr, d.critic_lr);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+
+    if (q.priorities) {
+        const dim3 grid((unsigned)((q.n + 255) / 256)), blk(256);
+        const float *td = q.td_delta ? q.td_delta : d.td;
+        hipLaunchKernelGGL(learner_prio_claim_kernel, grid, blk, 0, st, q.idx, q.n, q.capacity, q.priorities, d.status);
+        if ((e = hipGetLastError()) != hipSuccess) return e;
+        hipLaunchKernelGGL(learner_prio_max_kernel, grid, blk, 0, st, q.idx, q.n, q.capacity, q.priorities, d.status);
+        if ((e = hipGetLastError()) != hipSuccess) return e;
+        hipLaunchKernelGGL(learner_prio_mark_kernel, grid, blk, 0, st, q.idx, q.n, q.capacity, q.priorities, d.last,
+                           d.status);
+        if ((e = hipGetLastError()) != hipSuccess) return e;
+        hipLaunchKernelGGL(learner_prio_write_kernel, grid, blk, 0, st, q.idx, q.n, td, q.priorities, d.last, d.status);
+        if ((e = hipGetLastError()) != hipSuccess) return e;
+    }
+    return hipSuccess;
+}
+
+}  // namespace uavtrack

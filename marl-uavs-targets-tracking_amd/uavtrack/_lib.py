@@ -41,6 +41,17 @@ class HostStep(C.Structure):
                                           "ux", "uy", "uz", "uh", "ua", "tx", "ty", "tz", "th", "step_count")]
 
 
+class LearnerConfig(C.Structure):
+    """Mirror of `struct uavtrack_learner_config` (include/uavtrack.h)."""
+    _fields_ = [
+        ("struct_size", C.c_uint32), ("device_id", C.c_int32), ("hidden", C.c_int32), ("n_actions", C.c_int32),
+        ("loss", C.c_int32), ("pad_", C.c_int32), ("max_batch", C.c_int64),
+        ("gamma", C.c_double), ("actor_lr", C.c_double), ("critic_lr", C.c_double),
+    ]
+
+
+LOSS_FORMS = ("reference", "per_sample")                  # enum uavtrack_actor_loss
+LEARNER_TENSORS = 8                                       # parameter tensors: actor fc1.w fc1.b fc2.w fc2.b, critic likewise
 ACTOR_SAMPLE, ACTOR_ARGMAX = 0, 1   # enum in include/uavtrack.h
 PROF_CLASSES = ("rollout", "scorer", "mix", "ep_sums")   # UAVTRACK_PROF_* in include/uavtrack.h
 PMI_SCHEMES = ("auto", "f16x3", "bf16x6", "fp32")         # enum uavtrack_pmi_scheme
@@ -77,6 +88,16 @@ SIGNATURES = {
     "uavtrack_get_profile": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int64), C.c_void_p]),
     "uavtrack_kernel_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]),
     "uavtrack_launch_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]),
+    "uavtrack_learner_create": (C.c_int, [C.POINTER(LearnerConfig), C.POINTER(C.c_void_p)]),
+    "uavtrack_learner_destroy": (C.c_int, [C.c_void_p]),
+    "uavtrack_learner_num_params": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]),
+    "uavtrack_learner_reserve": (C.c_int, [C.c_void_p, C.c_int64]),
+    "uavtrack_learner_set_params": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
+    "uavtrack_learner_get_params": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
+    "uavtrack_learner_set_optimizer_state": (C.c_int, [C.c_void_p] + [C.c_void_p] * 3 + [C.c_int64, C.c_void_p]),
+    "uavtrack_learner_get_optimizer_state": (C.c_int, [C.c_void_p] + [C.c_void_p] * 3 + [C.c_int64, C.c_void_p]),
+    "uavtrack_learner_update": (C.c_int, [C.c_void_p, C.c_int64] + [C.c_void_p] * 4 + [C.c_int64] + [C.c_void_p] * 6),
+    "uavtrack_learner_check": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64), C.c_void_p]),
 }
 
 _lib = None

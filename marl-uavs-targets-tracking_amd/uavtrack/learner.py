@@ -1,0 +1,278 @@
+"""The reference's learner `ActorCritic` (src/models/actor_critic.py:115-205) on the device: one `update` is ONE
+library call (uavtrack_learner_update) -- both forwards, both backwards and both torch.optim.Adam steps, with the
+batch gathered in the kernel from a device replay ring and, for a prioritised ring, the |td_delta| priorities of
+train.py:262 written back -- stream-ordered, with no synchronisation and no allocation inside the library.
+
+The actor loss of the reference broadcasts: log_probs is [n, 1], td_delta is [n], so `-log_probs * td_delta` is
+[n, n] and actor_loss = mean_i(-log p_i) * mean_j(delta_j).  That is the default here (loss="reference");
+loss="per_sample" is mean_i(-log p_i * delta_i), the form examples/train_maac.py's PyTorch learner trains with.
+"""
+from __future__ import annotations
+
+import ctypes as C
+import os
+from collections import OrderedDict
+from typing import Dict, Optional
+
+import numpy as np
+import torch
+
+from . import _lib
+from .replay import DeviceReplayBuffer, PrioritizedDeviceReplayBuffer
+from .rollout import ActorMLP
+
+
+class ValueMLP(torch.nn.Module):
+    """Same shape as the reference's critic `FnnValueNet` (actor_critic.py:101-112): Linear(12, H) - ReLU -
+    Linear(H, 1), squeezed to [b].  Weights load from its state_dict."""
+
+    def __init__(self, state_dim: int = 12, hidden_dim: int = 128):
+        super().__init__()
+        self.fc1 = torch.nn.Linear(state_dim, hidden_dim)
+        self.fc2 = torch.nn.Linear(hidden_dim, 1)
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        return self.fc2(torch.relu(self.fc1(x))).squeeze(1)
+
+
+def _ptr(t: Optional[torch.Tensor]):
+    return None if t is None else C.c_void_p(t.data_ptr())
+
+
+class DeviceActorCritic:
+    """ActorCritic(state_dim, hidden_dim, action_dim, actor_lr, critic_lr, gamma, device) with the update on the GPU.
+    Initial weights are torch.nn.Linear's defaults drawn from torch's global generator, like the reference's."""
+
+    def __init__(self, state_dim: int = 12, hidden_dim: int = 128, action_dim: int = 12, actor_lr: float = 1e-4,
+                 critic_lr: float = 5e-4, gamma: float = 0.95, device="cuda:0", loss: str = "reference",
+                 max_batch: int = 0):
+        if state_dim != _lib.OBS_DIM:
+            raise ValueError(f"state_dim must be {_lib.OBS_DIM} (the environment's observation), got {state_dim}")
+        if loss not in _lib.LOSS_FORMS:
+            raise ValueError(f"loss must be one of {_lib.LOSS_FORMS}, got {loss!r}")
+        self.device = torch.device(device)
+        if self.device.index is None:
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        self.hidden_dim, self.action_dim, self.gamma, self.loss = int(hidden_dim), int(action_dim), float(gamma), loss
+        self.actor_lr, self.critic_lr = float(actor_lr), float(critic_lr)
+        # host-side modules: the reference's layouts, default initialisation, and the format of state dicts
+        self._actor = ActorMLP(state_dim, self.hidden_dim, self.action_dim)
+        self._critic = ValueMLP(state_dim, self.hidden_dim)
+        self._lib = _lib.load()
+        cfg = _lib.LearnerConfig(struct_size=C.sizeof(_lib.LearnerConfig), device_id=self.device.index,
+                                 hidden=self.hidden_dim, n_actions=self.action_dim, loss=_lib.LOSS_FORMS.index(loss),
+                                 pad_=0, max_batch=int(max_batch), gamma=self.gamma, actor_lr=self.actor_lr,
+                                 critic_lr=self.critic_lr)
+        h = C.c_void_p()
+        _lib.check(self._lib.uavtrack_learner_create(C.byref(cfg), C.byref(h)), "uavtrack_learner_create")
+        self._h = h
+        n = C.c_int64()
+        _lib.check(self._lib.uavtrack_learner_num_params(self._h, C.byref(n)), "uavtrack_learner_num_params")
+        self.num_params = n.value
+        self._sizes = [p.numel() for p in self._params()]
+        self._set_params(self._flat([p.detach() for p in self._params()]))
+
+    # ---- handle plumbing
+    def close(self) -> None:
+        if getattr(self, "_h", None):
+            self._lib.uavtrack_learner_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _stream(self):
+        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+
+    def _params(self):
+        return list(self._actor.parameters()) + list(self._critic.parameters())
+
+    @staticmethod
+    def _flat(tensors) -> np.ndarray:
+        return np.ascontiguousarray(np.concatenate([t.detach().cpu().float().numpy().ravel() for t in tensors]),
+                                    dtype=np.float32)
+
+    def _split(self, flat: np.ndarray):
+        out, o = [], 0
+        for p, k in zip(self._params(), self._sizes):
+            out.append(torch.from_numpy(flat[o:o + k].copy()).view_as(p))
+            o += k
+        return out
+
+    def _set_params(self, flat: np.ndarray) -> None:
+        _lib.check(self._lib.uavtrack_learner_set_params(self._h, flat.ctypes.data_as(C.c_void_p), flat.size,
+                                                         self._stream()), "uavtrack_learner_set_params")
+
+    def _get_params(self) -> np.ndarray:
+        flat = np.empty(self.num_params, np.float32)
+        _lib.check(self._lib.uavtrack_learner_get_params(self._h, flat.ctypes.data_as(C.c_void_p), flat.size,
+                                                         self._stream()), "uavtrack_learner_get_params")
+        return flat
+
+    def reserve(self, max_batch: int) -> None:
+        """Scratch for batches of up to max_batch rows (an update beyond the reserved size is an error)."""
+        _lib.check(self._lib.uavtrack_learner_reserve(self._h, int(max_batch)), "uavtrack_learner_reserve")
+
+    def check(self) -> None:
+        """Synchronises; raises if an update since the last check was refused on the device (an action outside
+        [0, action_dim) or an index outside the ring), which then changed nothing."""
+        _lib.check(self._lib.uavtrack_learner_check(self._h, None, self._stream()), "uavtrack_learner_check")
+
+    # ---- the update
+    def _run(self, n: int, store: Dict[str, torch.Tensor], capacity: int, idx: Optional[torch.Tensor],
+             priorities: Optional[torch.Tensor]):
+        dev = self.device
+        losses = torch.empty(2, device=dev)
+        td = torch.empty(n, device=dev)
+        _lib.check(self._lib.uavtrack_learner_update(
+            self._h, n, _ptr(store["states"]), _ptr(store["actions"]), _ptr(store["rewards"]),
+            _ptr(store["next_states"]), capacity, _ptr(idx), _ptr(losses[0:1]), _ptr(losses[1:2]), _ptr(td),
+            _ptr(priorities), self._stream()), "uavtrack_learner_update")
+        return losses[0], losses[1], td
+
+    def update(self, transition_dict: Dict[str, torch.Tensor]):
+        """ActorCritic.update (actor_critic.py:150-179) on a batch {states [n,12], actions [n], rewards [n],
+        next_states [n,12]}: returns (actor_loss, critic_loss, td_delta) as device tensors, without synchronising."""
+        dev = self.device
+        s = torch.as_tensor(transition_dict["states"], device=dev, dtype=torch.float32).reshape(-1, _lib.OBS_DIM).contiguous()
+        n = s.shape[0]
+        store = {"states": s,
+                 "actions": torch.as_tensor(transition_dict["actions"], device=dev).reshape(n).to(torch.int32).contiguous(),
+                 "rewards": torch.as_tensor(transition_dict["rewards"], device=dev, dtype=torch.float32).reshape(n).contiguous(),
+                 "next_states": torch.as_tensor(transition_dict["next_states"], device=dev,
+                                                dtype=torch.float32).reshape(n, _lib.OBS_DIM).contiguous()}
+        return self._run(n, store, n, None, None)
+
+    def update_from(self, buffer: DeviceReplayBuffer, batch_size: int, beta: float = 0.4,
+                    generator: Optional[torch.Generator] = None):
+        """buffer.sample(batch_size) + update + (prioritised buffer) update_priorities(indices, |td_delta|)
+        (train.py:253-262), the gather and the priority write inside the library call.  The indices are drawn as
+        the buffer's own sample() draws them.  beta only weights the importance weights, which the reference's
+        update does not use."""
+        k = min(int(batch_size), buffer.count)
+        if k < 1:
+            raise ValueError("update_from: the buffer is empty")
+        if isinstance(buffer, PrioritizedDeviceReplayBuffer):
+            prob = buffer.priorities[:buffer.count] ** buffer.alpha
+            prob = prob / prob.sum()
+            idx = torch.multinomial(prob, k, replacement=True, generator=generator)
+            prio = buffer.priorities
+        else:
+            idx = torch.randperm(buffer.count, device=buffer.device, generator=generator)[:k]
+            prio = None
+        return self._run(k, buffer.store, buffer.capacity, idx, prio)
+
+    # ---- weights and optimizer state
+    def _module_state(self, module: torch.nn.Module, offset: int) -> "OrderedDict[str, torch.Tensor]":
+        flat = self._get_params()
+        sd, o = OrderedDict(), offset
+        for name, p in module.named_parameters():
+            sd[name] = torch.from_numpy(flat[o:o + p.numel()].copy()).view_as(p)
+            o += p.numel()
+        return sd
+
+    def actor_state_dict(self) -> "OrderedDict[str, torch.Tensor]":
+        """FnnPolicyNet's state_dict (fc1.weight, fc1.bias, fc2.weight, fc2.bias; CPU fp32): loads into ActorMLP,
+        the reference's FnnPolicyNet and BatchedUavEnv.set_actor."""
+        return self._module_state(self._actor, 0)
+
+    def critic_state_dict(self) -> "OrderedDict[str, torch.Tensor]":
+        """FnnValueNet's state_dict (CPU fp32)."""
+        return self._module_state(self._critic, sum(p.numel() for p in self._actor.parameters()))
+
+    def _optim_state(self):
+        P = self.num_params
+        m, v = np.empty(P, np.float32), np.empty(P, np.float32)
+        steps = np.empty(_lib.LEARNER_TENSORS, np.int64)
+        _lib.check(self._lib.uavtrack_learner_get_optimizer_state(
+            self._h, m.ctypes.data_as(C.c_void_p), v.ctypes.data_as(C.c_void_p), steps.ctypes.data_as(C.c_void_p),
+            P, self._stream()), "uavtrack_learner_get_optimizer_state")
+        return m, v, steps
+
+    def _adam_state_dicts(self):
+        """(actor, critic) torch.optim.Adam state dicts, built by torch itself so Adam.load_state_dict accepts them."""
+        m, v, steps = self._optim_state()
+        ms, vs = self._split(m), self._split(v)
+        out, t = [], 0
+        for module, lr in ((self._actor, self.actor_lr), (self._critic, self.critic_lr)):
+            params = list(module.parameters())
+            opt = torch.optim.Adam(params, lr=lr)
+            for p in params:
+                if steps[t] > 0:
+                    opt.state[p] = {"step": torch.tensor(float(steps[t])), "exp_avg": ms[t].clone(),
+                                    "exp_avg_sq": vs[t].clone()}
+                t += 1
+            out.append(opt.state_dict())
+        return out
+
+    def _load_adam(self, actor_sd: Optional[dict], critic_sd: Optional[dict]) -> None:
+        m, v, steps = self._optim_state()
+        ms, vs = self._split(m), self._split(v)
+        t0 = 0
+        for module, lr, sd in ((self._actor, self.actor_lr, actor_sd), (self._critic, self.critic_lr, critic_sd)):
+            params = list(module.parameters())
+            if sd is not None:
+                opt = torch.optim.Adam(params, lr=lr)
+                opt.load_state_dict(sd)               # torch validates the dict
+                for i, p in enumerate(params):
+                    st = opt.state.get(p, {})
+                    if st:
+                        steps[t0 + i] = int(float(st["step"]))
+                        ms[t0 + i] = st["exp_avg"].detach().float().cpu().reshape(p.shape)
+                        vs[t0 + i] = st["exp_avg_sq"].detach().float().cpu().reshape(p.shape)
+                    else:
+                        steps[t0 + i] = 0
+                        ms[t0 + i] = torch.zeros_like(p)
+                        vs[t0 + i] = torch.zeros_like(p)
+            t0 += len(params)
+        mf, vf = self._flat(ms), self._flat(vs)
+        steps = np.ascontiguousarray(steps, dtype=np.int64)
+        _lib.check(self._lib.uavtrack_learner_set_optimizer_state(
+            self._h, mf.ctypes.data_as(C.c_void_p), vf.ctypes.data_as(C.c_void_p), steps.ctypes.data_as(C.c_void_p),
+            self.num_params, self._stream()), "uavtrack_learner_set_optimizer_state")
+
+    def _load_module(self, actor_sd: Optional[dict], critic_sd: Optional[dict]) -> None:
+        cur = self._split(self._get_params())
+        t0 = 0
+        for module, sd in ((self._actor, actor_sd), (self._critic, critic_sd)):
+            names = [k for k, _ in module.named_parameters()]
+            if sd is not None:
+                probe = type(module)(_lib.OBS_DIM, self.hidden_dim, *((self.action_dim,) if module is self._actor else ()))
+                probe.load_state_dict(sd)             # torch checks keys and shapes
+                for i, k in enumerate(names):
+                    cur[t0 + i] = probe.state_dict()[k]
+            t0 += len(names)
+        self._set_params(self._flat(cur))
+
+    def state_dict(self) -> dict:
+        a_opt, c_opt = self._adam_state_dicts()
+        return {"actor": self.actor_state_dict(), "critic": self.critic_state_dict(),
+                "actor_optimizer": a_opt, "critic_optimizer": c_opt}
+
+    def load_state_dict(self, sd: dict) -> None:
+        self._load_module(sd.get("actor"), sd.get("critic"))
+        self._load_adam(sd.get("actor_optimizer"), sd.get("critic_optimizer"))
+
+    def save(self, save_dir: str, epoch_i) -> None:
+        """ActorCritic.save (actor_critic.py:181-190): <save_dir>/actor/actor_weights_<epoch>.pth and
+        <save_dir>/critic/critic_weights_<epoch>.pth, each {'model_state_dict', 'optimizer_state_dict'}."""
+        a_opt, c_opt = self._adam_state_dicts()
+        for sub, model, opt in (("actor", self.actor_state_dict(), a_opt), ("critic", self.critic_state_dict(), c_opt)):
+            os.makedirs(os.path.join(save_dir, sub), exist_ok=True)
+            torch.save({"model_state_dict": model, "optimizer_state_dict": opt},
+                       os.path.join(save_dir, sub, f"{sub}_weights_{epoch_i}.pth"))
+
+    def load(self, actor_path: Optional[str], critic_path: Optional[str]) -> None:
+        """ActorCritic.load (actor_critic.py:192-205): each checkpoint that exists replaces that network's weights
+        and Adam state.  (The learning rates stay the ones this learner was built with.)"""
+        ck = {}
+        for key, path in (("actor", actor_path), ("critic", critic_path)):
+            if path and os.path.exists(path):
+                ck[key] = torch.load(path, map_location="cpu")
+        self._load_module(ck["actor"]["model_state_dict"] if "actor" in ck else None,
+                          ck["critic"]["model_state_dict"] if "critic" in ck else None)
+        self._load_adam(ck["actor"]["optimizer_state_dict"] if "actor" in ck else None,
+                        ck["critic"]["optimizer_state_dict"] if "critic" in ck else None)

@@ -1,0 +1,96 @@
+#!/usr/bin/env python3
+"""Learner rate: examples/train_maac.py's PyTorch `update` against DeviceActorCritic.update (one library call) at
+n in {4096, 65536, 262144} x H in {64, 128, 256}, A = 12.  Per configuration: warm-up, then HIP events around 100
+back-to-back updates on resident batches, median of 5 runs; prints us per update, the speed-up and the fraction of
+the 157 TF fp32 peak for the exact FLOP count below.
+
+FLOPs of one update (multiply-add = 2): forwards 2n(12H) x 3 (actor, critic on s and s') + 2n(H A) + 2n(H) x 2;
+backwards: actor fc2 weight + input gradients 2 x 2n(H A), fc1 weight gradient 2n(12H); critic fc2 2n H, fc1 2n(12H);
+softmax, losses and Adam are not counted.
+
+    python tools/learner_rate.py [--quick]
+"""
+import argparse
+import json
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path[:0] = [ROOT, os.path.join(ROOT, "marl-uavs-targets-tracking_amd"), os.path.join(ROOT, "examples")]
+
+import torch  # noqa: E402
+import uavtrack  # noqa: E402
+from train_maac import ValueNet, update as torch_update  # noqa: E402
+
+PEAK_TF = 157.3
+
+
+def flops(n, H, A=12):
+    fwd = 3 * 2 * n * 12 * H + 2 * n * H * A + 2 * 2 * n * H
+    bwd = 2 * 2 * n * H * A + 2 * n * 12 * H + 2 * n * H + 2 * n * 12 * H
+    return fwd + bwd
+
+
+def timed(fn, reps, runs):
+    ts = []
+    for _ in range(runs):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        for _ in range(reps):
+            fn()
+        b.record()
+        b.synchronize()
+        ts.append(a.elapsed_time(b) * 1e3 / reps)
+    ts.sort()
+    return ts[len(ts) // 2], ts
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--quick", action="store_true", help="n 65536, H 128 only")
+    ap.add_argument("--reps", type=int, default=100)
+    ap.add_argument("--runs", type=int, default=5)
+    args = ap.parse_args()
+    dev = "cuda:0"
+    A = 12
+    grid = [(65536, 128)] if args.quick else [(n, H) for H in (64, 128, 256) for n in (4096, 65536, 262144)]
+    for n, H in grid:
+        g = torch.Generator(device=dev); g.manual_seed(0)
+        batch = {"states": torch.rand(n, 12, device=dev, generator=g) * 2 - 1,
+                 "actions": torch.randint(0, A, (n,), device=dev, generator=g, dtype=torch.int32),
+                 "rewards": torch.rand(n, device=dev, generator=g) * 4 - 2,
+                 "next_states": torch.rand(n, 12, device=dev, generator=g) * 2 - 1}
+        actor, critic = uavtrack.ActorMLP(12, H, A).to(dev), ValueNet(12, H).to(dev)
+        oa, oc = torch.optim.Adam(actor.parameters(), lr=1e-4), torch.optim.Adam(critic.parameters(), lr=5e-4)
+
+        def tstep():   # the example's update without its two host reads of the losses
+            s, a, r, s2 = batch["states"], batch["actions"].long().unsqueeze(1), batch["rewards"], batch["next_states"]
+            td_target = r + 0.95 * critic(s2)
+            td_delta = td_target - critic(s)
+            lp = torch.log(actor(s).gather(1, a).squeeze(1).clamp_min(1e-12))
+            al = torch.mean(-lp * td_delta.detach())
+            cl = torch.nn.functional.mse_loss(critic(s), td_target.detach())
+            oa.zero_grad(); oc.zero_grad(); al.backward(); cl.backward(); oa.step(); oc.step()
+        L = uavtrack.DeviceActorCritic(12, H, A, 1e-4, 5e-4, 0.95, dev, max_batch=n)
+        store = {k: v.contiguous() for k, v in batch.items()}
+
+        def dstep():
+            L._run(n, store, n, None, None)
+        for f in (tstep, dstep):
+            for _ in range(10):
+                f()
+        torch.cuda.synchronize()
+        t_torch, _ = timed(tstep, args.reps, args.runs)
+        t_dev, runs = timed(dstep, args.reps, args.runs)
+        L.check()
+        fl = flops(n, H, A)
+        print(json.dumps({"n": n, "H": H, "A": A, "torch_us": round(t_torch, 1), "device_us": round(t_dev, 1),
+                          "speedup": round(t_torch / t_dev, 2), "gflop": round(fl / 1e9, 3),
+                          "device_tflops": round(fl / t_dev / 1e6, 2),
+                          "frac_of_157TF": round(fl / t_dev / 1e6 / PEAK_TF, 4),
+                          "device_runs_us": [round(x, 1) for x in runs]}), flush=True)
+        L.close()
+
+
+if __name__ == "__main__":
+    main()
