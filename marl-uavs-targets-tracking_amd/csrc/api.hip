@@ -670,14 +670,15 @@ int uavtrack_pmi_info(uavtrack_env *env, int64_t out[4], void *stream)
     return 0;
 }
 
-// Where a rollout's actions come from: the caller's tensor, or the in-kernel actor (uavtrack_run_actor).
+// Where a rollout's actions come from: the caller's tensor, the in-kernel greedy baseline (uavtrack_run_greedy) or the
+// in-kernel actor (uavtrack_run_actor).
 struct PolicyArgs {
     bool auto_reset = false;           // uavtrack_step_many_autoreset: reset seed
     uint64_t reset_seed = 0;
     int policy = kPolicyGiven;
     const float *obs_in = nullptr;     // actor: observation seen at the first step
-    int32_t *actions_out = nullptr;    // actor: chosen actions [T][B][N], nullable
-    uint64_t seed = 0;
+    int32_t *actions_out = nullptr;    // greedy / actor: chosen actions [T][B][N], nullable
+    uint64_t seed = 0;                 // greedy / actor: policy seed
     int32_t mode = 0;
 };
 
@@ -708,8 +709,8 @@ static int run_steps(uavtrack_env *env, int32_t T, const int32_t *actions, float
     p.env_offset = env->cfg.env_offset;
     p.auto_reset = pol.auto_reset ? 1 : 0;
     p.reset_k0 = (uint32_t)pol.reset_seed; p.reset_k1 = (uint32_t)(pol.reset_seed >> 32);
+    p.greedy_k0 = (uint32_t)pol.seed; p.greedy_k1 = (uint32_t)(pol.seed >> 32);
     if (pol.policy == kPolicyActor) {
-        p.greedy_k0 = (uint32_t)pol.seed; p.greedy_k1 = (uint32_t)(pol.seed >> 32);
         p.obs_in = pol.obs_in; p.actor_w = env->actor_w; p.actor_hblocks = actor_blocks(env->actor_hidden);
         p.actor_mode = pol.mode;
     }
@@ -749,9 +750,7 @@ static int run_steps(uavtrack_env *env, int32_t T, const int32_t *actions, float
         p.done = done ? done + (size_t)t0 * c.n_envs : nullptr;
         p.tpos = env->tpos ? env->tpos + (size_t)t0 * c.n_envs * c.m_targets : nullptr;
         p.raw = env->raw_out ? env->raw_out + (size_t)t0 * BN : nullptr;
-        // (short launches: 4-wave groups; long ones: the handle's geometry where its kernel variant exists -- launch_rollout)
-        const Geometry *geo = n < kPmiShortLaunch ? &env->geo_short : nullptr;
-        HIP_TRY(timed_launch(env, UAVTRACK_PROF_ROLLOUT, st, [&] { return launch_rollout(env, p, st, pol.policy, geo); }));
+        HIP_TRY(timed_launch(env, UAVTRACK_PROF_ROLLOUT, st, [&] { return launch_rollout(env, p, st, pol.policy); }));
         // the actor of the next chunk starts from this chunk's last observation (a lane reads its own row
         // once, at launch start, before it writes anything: the scratch buffer may be reused in place)
         p.obs_in = obs_t + (size_t)(n - 1) * BN * UAVTRACK_OBS_DIM;
@@ -798,29 +797,12 @@ int uavtrack_run_greedy(uavtrack_env *env, int32_t T, uint64_t seed, int32_t *ac
                         float *terms, int32_t *covered, uint8_t *done, float *ep_sums, void *stream)
 {
     if (!env) return fail("uavtrack_run_greedy: null handle");
-    if (T < 1) return fail("uavtrack_run_greedy: T must be >= 1 (got %d)", T);
-    if (!reward) return fail("uavtrack_run_greedy: reward is null");
     if (env->cfg.dim != 2) return fail("uavtrack_run_greedy: the reference baseline is planar (dim must be 2)");
     if (env->cfg.reward_mode == UAVTRACK_REWARD_PMI)
         return fail("uavtrack_run_greedy: the C-METHOD baseline runs with the MAAC / MAAC-G rewards (C-METHOD.yaml: cooperative 0)");
-    ON_DEVICE(env->cfg.device_id);
-    if (env->tpos && T > env->tpos_steps)
-        return fail("uavtrack_run_greedy: T = %d exceeds the %d steps the target-trace buffer holds", T, env->tpos_steps);
-    if (env->raw_out && T > env->raw_steps)
-        return fail("uavtrack_run_greedy: T = %d exceeds the %d steps the raw-reward buffer holds", T, env->raw_steps);
-    StepParams p = env->base;
-    p.T = T;
-    p.tpos = env->tpos;
-    p.raw = env->raw_out;
-    p.actions = nullptr; p.actions_out = actions_out;
-    p.obs = obs; p.reward = reward; p.terms = terms; p.nbrec = nullptr;
-    p.covered = covered; p.done = done; p.ep_sums = ep_sums;
-    p.pairs = nullptr; p.pair_count = nullptr; p.ep_accumulate = 0;
-    p.env_offset = env->cfg.env_offset;
-    p.greedy_k0 = (uint32_t)seed; p.greedy_k1 = (uint32_t)(seed >> 32);
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    HIP_TRY(timed_launch(env, UAVTRACK_PROF_ROLLOUT, st, [&] { return launch_rollout(env, p, st, kPolicyGreedy); }));
-    return 0;
+    PolicyArgs pol;
+    pol.policy = kPolicyGreedy; pol.actions_out = actions_out; pol.seed = seed;
+    return run_steps(env, T, nullptr, obs, reward, terms, covered, done, ep_sums, stream, "uavtrack_run_greedy", false, pol);
 }
 
 int uavtrack_greedy_actions(uavtrack_env *env, uint64_t seed, int32_t *actions, void *stream)

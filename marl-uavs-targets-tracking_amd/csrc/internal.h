@@ -145,9 +145,9 @@ struct uavtrack_env {
     float *slab = nullptr;       // the one device allocation behind `state`
     uavtrack::StateBlock state;  // pointers into the slab (host-side view)
     uavtrack::Geometry geo;
-    // MAAC-R launches of fewer than kPmiShortLaunch steps: the 4-wave geometry (one pair-list reservation per workgroup-step
-    // on a quarter of the workgroups; the single-wavefront variant's block reservations pay off over many steps, and a
-    // launch that starts with an empty pool waits for its first one)
+    // MAAC-R launches of fewer than kPmiShortLaunch steps, or without a single-wavefront variant (select_rollout): the 4-wave
+    // geometry (one pair-list reservation per workgroup-step on a quarter of the workgroups; the single-wavefront variant's
+    // block reservations pay off over many steps, and a launch that starts with an empty pool waits for its first one)
     uavtrack::Geometry geo_short;
     uavtrack::Geometry last_launch;   // geometry of the most recent rollout launch (uavtrack_launch_info)
     uavtrack::PmiWeights pmi;
@@ -192,10 +192,9 @@ namespace uavtrack {
 // step_kernel.hip
 Geometry plan_geometry(const uavtrack_config &cfg, int n_simd, bool allow_small_grid = true);
 enum { kPolicyGiven = 0, kPolicyGreedy = 1, kPolicyActor = 2 };   // where a rollout's actions come from
-// (geo: the launch geometry, default the handle's own; MAAC-R launches of a few steps use env->geo_short)
-hipError_t launch_rollout(uavtrack_env *env, const StepParams &p, hipStream_t stream, int policy = kPolicyGiven,
-                          const Geometry *geo = nullptr);
-size_t rollout_lds_bytes(const Geometry &g, int policy);   // dynamic LDS of a rollout launch with that policy
+// one rollout launch of p.T steps: the kernel variant and the geometry (env->geo or env->geo_short) are chosen by
+// select_rollout; the choice is kept in env->last_launch
+hipError_t launch_rollout(uavtrack_env *env, const StepParams &p, hipStream_t stream, int policy = kPolicyGiven);
 
 // pmi_kernel.hip
 constexpr int kPmiShortLaunch = 16;

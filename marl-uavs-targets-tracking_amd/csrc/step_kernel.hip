@@ -863,7 +863,7 @@ __global__ void __launch_bounds__(kMaxWorkgroup) rollout_kernel(const StepParams
         //      observation, still in registers -- no table, no barrier
         if (ACTOR) {     // whole wavefronts: the two layers run on the matrix cores (actor.h)
             // (the single-wavefront variant -- the closed loop at the reference shape -- carries the two-tiles-per-trip layout of
-            //  the tile loop, for the reference's hidden width ONLY: 128 = kLoneActorTiles tiles; launch_rollout sends other
+            //  the tile loop, for the reference's hidden width ONLY: 128 = kLoneActorTiles tiles; select_rollout sends other
             //  widths to the general variants -- both layouts in one kernel spilled)
             if constexpr (LONE)
                 act = actor_pick<false, actor_tiles(Z3), kLoneActorTiles>(o, p.actor_w, kLoneActorTiles, p.na_total, (uint64_t)(p.env_offset + b),
@@ -1517,64 +1517,71 @@ size_t lds_bytes_for(int E, int N, int M, bool z3, int reward_mode)
 
 using KernelFn = void (*)(const StepParams);
 
-template <int N_, int M_, int POLICY, bool ALLOUT, bool EXTRAS, bool LONE = false>
-KernelFn pick_reward(int mode, bool z3)
+// The specialised (N, M) shapes: sweeps unrolled for that swarm and target count; every other shape runs the generic
+// kernel (N_ = M_ = 0).  `lone`: the shape also has the single-wavefront (LONE) variants -- swarms of up to 20 x 10, what
+// sweep_fast's prefetch is written for.  Adding or removing a shape is one edit here.
+struct SpecShape { int N, M; bool lone; };
+constexpr SpecShape kSpecShapes[] = {{20, 10, true}, {50, 25, false}, {10, 10, true}, {5, 3, true}};
+constexpr int kSpecShapeCount = sizeof kSpecShapes / sizeof kSpecShapes[0];
+
+const SpecShape *spec_shape(int N, int M)
 {
-    constexpr bool PLANAR_ONLY = POLICY == kPolicyGreedy;      // the baseline policy is planar and runs with MAAC / MAAC-G
-    if (z3 && !PLANAR_ONLY) {
-        switch (mode) {
-        case UAVTRACK_REWARD_MEAN: return rollout_kernel<N_, M_, UAVTRACK_REWARD_MEAN, !PLANAR_ONLY, POLICY, ALLOUT, EXTRAS, LONE>;
-        case UAVTRACK_REWARD_PMI:  return rollout_kernel<N_, M_, PLANAR_ONLY ? UAVTRACK_REWARD_RAW : UAVTRACK_REWARD_PMI, !PLANAR_ONLY, POLICY, ALLOUT, EXTRAS, LONE>;
-        default:                   return rollout_kernel<N_, M_, UAVTRACK_REWARD_RAW, !PLANAR_ONLY, POLICY, ALLOUT, EXTRAS, LONE>;
-        }
-    }
+    for (const SpecShape &s : kSpecShapes)
+        if (s.N == N && s.M == M) return &s;
+    return nullptr;
+}
+
+// What selects a launch's template arguments beyond its shape (select_rollout): MODE, Z3, POLICY, ALLOUT, EXTRAS, LONE
+struct Variant { int mode; bool z3; int policy; bool allout, extras, lone; };
+
+template <int N_, int M_, bool Z3, int POLICY, bool ALLOUT, bool EXTRAS, bool LONE = false>
+KernelFn pick_reward(int mode)
+{
+    // (the greedy baseline never runs MAAC-R -- uavtrack_run_greedy refuses it -- so its PMI slot is the RAW kernel)
+    constexpr int kPmi = POLICY == kPolicyGreedy ? UAVTRACK_REWARD_RAW : UAVTRACK_REWARD_PMI;
     switch (mode) {
-    case UAVTRACK_REWARD_MEAN: return rollout_kernel<N_, M_, UAVTRACK_REWARD_MEAN, false, POLICY, ALLOUT, EXTRAS, LONE>;
-    case UAVTRACK_REWARD_PMI:  return rollout_kernel<N_, M_, PLANAR_ONLY ? UAVTRACK_REWARD_RAW : UAVTRACK_REWARD_PMI, false, POLICY, ALLOUT, EXTRAS, LONE>;
-    default:                   return rollout_kernel<N_, M_, UAVTRACK_REWARD_RAW, false, POLICY, ALLOUT, EXTRAS, LONE>;
+    case UAVTRACK_REWARD_MEAN: return rollout_kernel<N_, M_, UAVTRACK_REWARD_MEAN, Z3, POLICY, ALLOUT, EXTRAS, LONE>;
+    case UAVTRACK_REWARD_PMI:  return rollout_kernel<N_, M_, kPmi, Z3, POLICY, ALLOUT, EXTRAS, LONE>;
+    default:                   return rollout_kernel<N_, M_, UAVTRACK_REWARD_RAW, Z3, POLICY, ALLOUT, EXTRAS, LONE>;
     }
 }
 
-// The launches a single-wavefront (LONE) kernel variant exists for: pre-sampled actions with every output, or the fused
-// actor rollout; no extras, planar, a specialised shape up to 20 x 10 (what sweep_fast's prefetch is written for).
-constexpr bool lone_shape(int n_spec, int m_spec) { return n_spec > 0 && n_spec <= 20 && m_spec <= 10; }
-bool lone_variant_exists(int N, int M, bool z3, int policy, bool allout, bool extras, int actor_hblocks)
+template <int N_, int M_, int POLICY, bool ALLOUT, bool EXTRAS>
+KernelFn pick_dim(const Variant &v)
 {
-    const bool shape = (N == 20 && M == 10) || (N == 10 && M == 10) || (N == 5 && M == 3);      // the specialised shapes that pass lone_shape()
-    return shape && !z3 && !extras && ((policy == kPolicyGiven && allout) || (policy == kPolicyActor && actor_hblocks == kLoneActorTiles));
+    return v.z3 ? pick_reward<N_, M_, true, POLICY, ALLOUT, EXTRAS>(v.mode) : pick_reward<N_, M_, false, POLICY, ALLOUT, EXTRAS>(v.mode);
 }
 
-// Instantiations: pre-sampled actions with every output and no extras (the learner's rollout, the benchmark);
-// any policy without extras; any policy with them.
-template <int N_, int M_>
-KernelFn pick_mode(int mode, bool z3, int policy, bool allout, bool extras, bool lone)
+// Instantiations: the single-wavefront variants (planar: pre-sampled actions with every output and no extras -- the
+// learner's rollout, the benchmark -- or the fused actor rollout: wave fences for barriers and, under MAAC-R, pair-list
+// slots from the pool); the planar greedy baseline with and without extras; any other policy without extras, with them.
+template <int N_, int M_, bool LONE_SHAPE>
+KernelFn pick_policy(const Variant &v)
 {
-    if constexpr (lone_shape(N_, M_)) {
-        if (policy == kPolicyGiven && allout && !extras && lone && !z3)
-            return pick_reward<N_, M_, kPolicyGiven, true, false, true>(mode, false);
-        // the fused actor rollout on single-wavefront groups: wave fences for barriers and, under MAAC-R, pair-list slots
-        // from the pool (the 4-wave emission path would make one reservation per workgroup-step on four times the groups)
-        if (policy == kPolicyActor && !extras && lone && !z3)
-            return pick_reward<N_, M_, kPolicyActor, false, false, true>(mode, false);
+    if constexpr (LONE_SHAPE) {
+        if (v.lone)
+            return v.policy == kPolicyActor ? pick_reward<N_, M_, false, kPolicyActor, false, false, true>(v.mode)
+                                            : pick_reward<N_, M_, false, kPolicyGiven, true, false, true>(v.mode);
     }
-    if (policy == kPolicyGreedy)
-        return extras ? pick_reward<N_, M_, kPolicyGreedy, false, true>(mode, z3) : pick_reward<N_, M_, kPolicyGreedy, false, false>(mode, z3);
-    if (policy == kPolicyActor)
-        return extras ? pick_reward<N_, M_, kPolicyActor, false, true>(mode, z3) : pick_reward<N_, M_, kPolicyActor, false, false>(mode, z3);
-    if (extras) return pick_reward<N_, M_, kPolicyGiven, false, true>(mode, z3);
-    return allout ? pick_reward<N_, M_, kPolicyGiven, true, false>(mode, z3) : pick_reward<N_, M_, kPolicyGiven, false, false>(mode, z3);
+    if (v.policy == kPolicyGreedy)
+        return v.extras ? pick_reward<N_, M_, false, kPolicyGreedy, false, true>(v.mode) : pick_reward<N_, M_, false, kPolicyGreedy, false, false>(v.mode);
+    if (v.policy == kPolicyActor)
+        return v.extras ? pick_dim<N_, M_, kPolicyActor, false, true>(v) : pick_dim<N_, M_, kPolicyActor, false, false>(v);
+    if (v.extras) return pick_dim<N_, M_, kPolicyGiven, false, true>(v);
+    return v.allout ? pick_dim<N_, M_, kPolicyGiven, true, false>(v) : pick_dim<N_, M_, kPolicyGiven, false, false>(v);
 }
 
-KernelFn pick_kernel(int N, int M, int mode, bool z3, int *specialised, int policy = kPolicyGiven, bool allout = false,
-                     bool extras = false, bool lone = false)
+// kSpecShapes[I..] in order, then the generic kernel
+template <int I = 0>
+KernelFn pick_kernel(int N, int M, const Variant &v)
 {
-    *specialised = 1;
-    if (N == 20 && M == 10) return pick_mode<20, 10>(mode, z3, policy, allout, extras, lone);
-    if (N == 50 && M == 25) return pick_mode<50, 25>(mode, z3, policy, allout, extras, lone);
-    if (N == 10 && M == 10) return pick_mode<10, 10>(mode, z3, policy, allout, extras, lone);
-    if (N == 5 && M == 3) return pick_mode<5, 3>(mode, z3, policy, allout, extras, lone);
-    *specialised = 0;
-    return pick_mode<0, 0>(mode, z3, policy, allout, extras, lone);
+    if constexpr (I == kSpecShapeCount) {
+        return pick_policy<0, 0, false>(v);
+    } else {
+        constexpr SpecShape s = kSpecShapes[I];
+        if (N == s.N && M == s.M) return pick_policy<s.N, s.M, s.lone>(v);
+        return pick_kernel<I + 1>(N, M, v);
+    }
 }
 
 }  // namespace
@@ -1583,6 +1590,7 @@ Geometry plan_geometry(const uavtrack_config &cfg, int n_simd, bool allow_small_
 {
     Geometry g;
     const int N = cfg.n_uav;
+    const SpecShape *shape = spec_shape(N, cfg.m_targets);
     int best = 0;
     int forced = 0;
     if (const char *s = getenv("UAVTRACK_WGS")) forced = atoi(s);
@@ -1596,21 +1604,18 @@ Geometry plan_geometry(const uavtrack_config &cfg, int n_simd, bool allow_small_
     static const int kSmall[] = {64, 128, 256, 512};
     // whole environments per workgroup: as many as there are lanes for, fewer when their tables would not fit
     // the 64 KB of LDS a workgroup has by default (few UAVs, many targets: N = 1, M = 70 fits 58 environments, not 64).
-    auto lds_need = [&](int wgs, int E) {
-        (void)wgs;
-        return lds_bytes_for(E, N, cfg.m_targets, cfg.dim == 3, cfg.reward_mode);
-    };
+    auto lds_need = [&](int E) { return lds_bytes_for(E, N, cfg.m_targets, cfg.dim == 3, cfg.reward_mode); };
     // (kLdsSoft = the 64 KiB a launch gets without asking: several environments per workgroup stay inside it, so two or more
     //  workgroups share a CU; a SINGLE environment whose tables need more -- hundreds of UAVs with thousands of targets --
     //  may take up to the CU's whole 160 KiB, which launch_rollout requests per kernel, hipFuncSetAttribute)
     auto envs_of = [&](int wgs) {
         int E = wgs / N;
-        while (E > 1 && lds_need(wgs, E) > kLdsSoft) --E;
+        while (E > 1 && lds_need(E) > kLdsSoft) --E;
         return E;
     };
     auto feasible = [&](int wgs) {
         const int E = envs_of(wgs);
-        return E >= 1 && lds_need(wgs, E) <= kLdsMax;
+        return E >= 1 && lds_need(E) <= kLdsMax;
     };
     auto util_of = [&](int wgs) {
         const int E = envs_of(wgs);
@@ -1626,15 +1631,11 @@ Geometry plan_geometry(const uavtrack_config &cfg, int n_simd, bool allow_small_
             if (feasible(wgs) && util_of(wgs) > best_util) best_util = util_of(wgs);
         bool small_grid = false;
         long waves64 = 0;
-        // (MAAC-R keeps the larger groups: its pair emission costs one global atomic per workgroup-step, and
-        // four times the workgroups measured 15.8 instead of 5.2 us per step at 4096 envs)
-        // (MAAC-R used to keep the larger groups -- one pair-list reservation per workgroup-step on ONE counter; the
-        // single-wavefront variant now reserves per block, see kPoolEmit -- so it follows the same rule, for the swarm
-        // sizes that variant is built for)
-        int spec_shape = 0;
-        pick_kernel(N, cfg.m_targets, cfg.reward_mode, cfg.dim == 3, &spec_shape);
+        // (MAAC-R follows the same rule only where its single-wavefront variant exists, which reserves pair-list slots per
+        // block (kPoolEmit); elsewhere it keeps the larger groups: the 4-wave emission path makes one reservation per
+        // workgroup-step on ONE counter, and four times the workgroups measured 15.8 instead of 5.2 us per step at 4096 envs)
         if (allow_small_grid && feasible(64) &&
-            (cfg.reward_mode != UAVTRACK_REWARD_PMI || (spec_shape && N <= 20 && cfg.m_targets <= 10 && cfg.dim == 2))) {
+            (cfg.reward_mode != UAVTRACK_REWARD_PMI || (shape && shape->lone && cfg.dim == 2))) {
             const long waves = (cfg.n_envs + envs_of(64) - 1) / envs_of(64);
             small_grid = waves <= 3L * (n_simd > 0 ? n_simd : 1024);
             waves64 = waves;
@@ -1651,42 +1652,51 @@ Geometry plan_geometry(const uavtrack_config &cfg, int n_simd, bool allow_small_
     g.envs_per_wg = envs_of(best);
     g.groups = (cfg.n_envs + g.envs_per_wg - 1) / g.envs_per_wg;
     g.lds_bytes = lds_bytes_for(g.envs_per_wg, N, cfg.m_targets, cfg.dim == 3, cfg.reward_mode);
-    pick_kernel(N, cfg.m_targets, cfg.reward_mode, cfg.dim == 3, &g.specialised);
+    g.specialised = shape != nullptr;
     return g;
 }
 
-size_t rollout_lds_bytes(const Geometry &g, int policy)
-{
-    (void)policy;               // (the in-kernel actor needs no LDS since round 4: its operands move by lane swaps)
-    return g.lds_bytes;
-}
+// The one place that decides what a rollout launch runs: the kernel and its geometry (geo.lone: the LONE variant runs)
+struct RolloutChoice { KernelFn fn; Geometry geo; };
 
-hipError_t launch_rollout(uavtrack_env *env, const StepParams &p, hipStream_t stream, int policy, const Geometry *geo)
+static RolloutChoice select_rollout(const uavtrack_env *env, const StepParams &p, int policy)
 {
-    int spec = 0;
-    const bool allout = p.obs && p.reward && p.terms && p.covered && p.done;
-    const bool extras = p.auto_reset || p.tpos || p.raw || p.state_copy;
+    Variant v;
+    v.mode = env->cfg.reward_mode;
+    v.z3 = env->cfg.dim == 3;
+    v.policy = policy;
+    v.allout = p.obs && p.reward && p.terms && p.covered && p.done;
+    v.extras = p.auto_reset || p.tpos || p.raw || p.state_copy;
+    // the LONE variants: pre-sampled actions with every output, or the fused actor at the width its layout is written for
+    // (an actor of another width runs the general variant on the same geometry)
+    const SpecShape *shape = spec_shape(p.N, p.M);
+    const bool lone_exists = shape && shape->lone && !v.z3 && !v.extras &&
+                             ((policy == kPolicyGiven && v.allout) || (policy == kPolicyActor && p.actor_hblocks == kLoneActorTiles));
     // MAAC-R: the single-wavefront geometry only pays with the kernel variant written for it (pair-list slots from a pool).
     // Every other launch -- an output not requested, the target trace, the automatic reset -- would run the 4-wave emission
     // path (one pair-list reservation per workgroup-step on ONE counter) on four times the workgroups: measured 15.8
-    // against 5.2 us per step at 4096 envs.  Those launches keep the 256-thread geometry.
-    const bool lone_ok = lone_variant_exists(p.N, p.M, env->cfg.dim == 3, policy, allout, extras, p.actor_hblocks);
-    if (!geo && env->cfg.reward_mode == UAVTRACK_REWARD_PMI && env->geo.lone && !lone_ok)
-        geo = &env->geo_short;
-    const Geometry &g = geo ? *geo : env->geo;
-    env->last_launch = g;
-    env->last_launch.lone = g.lone && lone_ok;
-    // (an actor of another width than the single-wavefront variant is laid out for runs the general variant on the same geometry)
-    const bool lone_kernel = g.lone != 0 && !(policy == kPolicyActor && p.actor_hblocks != kLoneActorTiles);
-    KernelFn fn = pick_kernel(p.N, p.M, env->cfg.reward_mode, env->cfg.dim == 3, &spec, policy, allout, extras, lone_kernel);
+    // against 5.2 us per step at 4096 envs.  Those launches, and those of fewer than kPmiShortLaunch steps, take geo_short.
+    const bool short_geo = v.mode == UAVTRACK_REWARD_PMI && (p.T < kPmiShortLaunch || (env->geo.lone && !lone_exists));
+    RolloutChoice r;
+    r.geo = short_geo ? env->geo_short : env->geo;
+    r.geo.lone = r.geo.lone && lone_exists;
+    v.lone = r.geo.lone;
+    r.fn = pick_kernel(p.N, p.M, v);
+    return r;
+}
+
+hipError_t launch_rollout(uavtrack_env *env, const StepParams &p, hipStream_t stream, int policy)
+{
+    const RolloutChoice r = select_rollout(env, p, policy);
+    env->last_launch = r.geo;
     StepParams q = p;
-    q.E = g.envs_per_wg;
-    const size_t lds = rollout_lds_bytes(g, policy);
+    q.E = r.geo.envs_per_wg;
+    const size_t lds = r.geo.lds_bytes;   // (the in-kernel actor needs no LDS: its operands move by lane swaps)
     if (lds > kLdsSoft) {      // beyond the default limit of a launch: raise this kernel's (a host-side attribute, no stream work)
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(r.fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (e != hipSuccess) return e;
     }
-    hipLaunchKernelGGL(fn, dim3(g.groups), dim3(g.wgs), lds, stream, q);
+    hipLaunchKernelGGL(r.fn, dim3(r.geo.groups), dim3(r.geo.wgs), lds, stream, q);
     return hipGetLastError();
 }
 

@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Experiment aid (build container): compile ONE rollout_kernel instantiation to assembly in seconds instead of the whole
 step_kernel.hip in minutes.  usage: one_variant.py "20, 10, 0, false, 2, false, false, true" [out.s ["old=>new" ...]]
-Works on a patched COPY of csrc/step_kernel.hip whose pick_kernel() names only that variant; prints registers / scratch."""
+Works on a patched COPY of csrc/step_kernel.hip whose pick_kernel() names only that variant; prints registers / scratch.
+(The template arguments: N, M, MODE, Z3, POLICY, ALLOUT, EXTRAS, LONE -- see pick_policy() for the ones that exist.)"""
 import os, re, subprocess, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 src = os.path.join(ROOT, "marl-uavs-targets-tracking_amd", "csrc")
@@ -13,10 +14,9 @@ s = open(os.path.join(src, "step_kernel.hip")).read()
 for old, new in subs:
     assert s.count(old) >= 1, old
     s = s.replace(old, new)
-a = s.index("KernelFn pick_kernel(int N, int M, int mode, bool z3, int *specialised")
+a = s.index("template <int I = 0>\nKernelFn pick_kernel(int N, int M, const Variant &v)")
 b = s.index("}  // namespace\n\nGeometry plan_geometry")
-s = s[:a] + ("KernelFn pick_kernel(int N, int M, int mode, bool z3, int *specialised, int policy = kPolicyGiven, bool allout = false,\n"
-             "                     bool extras = false, bool lone = false)\n{\n    *specialised = 1;\n    return rollout_kernel<%s>;\n}\n\n" % args) + s[b:]
+s = s[:a] + ("template <int I = 0>\nKernelFn pick_kernel(int, int, const Variant &)\n{\n    return rollout_kernel<%s>;\n}\n\n" % args) + s[b:]
 tmp = os.path.join(os.path.dirname(out), "one_variant.hip")
 open(tmp, "w").write(s)
 flags = ("--offload-arch=gfx950 -O3 -std=c++17 -fPIC -fno-gpu-rdc -ffp-contract=off -I%s/include -I%s -Wno-unused-function -Wno-pass-failed "
