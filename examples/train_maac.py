@@ -79,6 +79,9 @@ def main(argv=None):
     ap.add_argument("--actor-loss", choices=["reference", "per_sample"], default="reference",
                     help="--learner device only: the reference's broadcast loss mean(-log p) * mean(delta), or "
                          "mean(-log p * delta) (what the torch learner trains with)")
+    ap.add_argument("--pmi-trainer", choices=["torch", "device"], default="torch",
+                    help="--method maac-r only: torch: the PyTorch PMINetwork.train_pmi loop below; device: "
+                         "uavtrack.DevicePMINetwork, the whole train_pmi call in one library call")
     args = ap.parse_args(argv)
 
     dev = "cuda:0"
@@ -88,8 +91,11 @@ def main(argv=None):
     cfg = uavtrack.EnvConfig(n_envs=args.envs, n_uav=args.n_uav, m_targets=args.m_targets, cooperative=coop,
                              reward_mode=mode, horizon=args.steps)
     env = uavtrack.BatchedUavEnv(cfg, dev)
-    pmi = opt_p = None
-    if args.method == "maac-r":
+    pmi = opt_p = pmi_dev = None
+    if args.method == "maac-r" and args.pmi_trainer == "device":
+        pmi_dev = uavtrack.DevicePMINetwork(args.pmi_hidden, args.pmi_b2, dev, max_batch=max(args.pmi_batch, 4096))
+        env.set_pmi(pmi_dev)
+    elif args.method == "maac-r":
         pmi = uavtrack.make_pmi_net(args.pmi_hidden).to(dev)
         opt_p = torch.optim.Adam(pmi.parameters(), lr=1e-3)          # PMINet.py:39
         env.set_pmi(pmi.state_dict())
@@ -134,6 +140,9 @@ def main(argv=None):
                 opt_p.zero_grad(); loss.backward(); opt_p.step()
                 lp = float(loss.detach())
             env.set_pmi(pmi.state_dict())                             # eval-mode (running-stat) BatchNorm is what gets folded
+        elif pmi_dev is not None:                                     # the same call, one library call on the device
+            lp = pmi_dev.train_pmi({"pmi": {"batch_size": args.pmi_batch}}, res["obs"], args.n_uav)
+            env.set_pmi(pmi_dev)
         rollout.sync_actor()                                          # new weights for the next rollout
         ep = res["ep_sums"]                                           # [B, 5]: sum_t mean_i reward, 3 terms, covered
         ret, cov = float(ep[:, 0].mean()), float(ep[:, 4].mean()) / args.steps

@@ -404,6 +404,73 @@ int uavtrack_learner_update(uavtrack_learner *learner, int64_t n,
  * index).  refused (nullable) receives their number; the count restarts at 0. */
 int uavtrack_learner_check(uavtrack_learner *learner, int64_t *refused, void *stream);
 
+/* ---- the PMI trainer: PMINetwork.train_pmi + its Adam steps on the device ----
+ * A handle of its own, independent of any environment.  It holds one reference PMINetwork (PMINet.py:20-62: three
+ * branch Linear(5|4|3, H) + BatchNorm1d + ReLU blocks, concat, Linear(3H, H) + BatchNorm1d + ReLU, Linear(H, 1)) and
+ * its torch.optim.Adam state (PMINet.py:39: lr, betas (0.9, 0.999), eps 1e-8).
+ * State blob (uavtrack_pmi_trainer_num_params: n_state floats): the float entries of PMINetwork.state_dict() in its
+ * order, H = hidden -- for each block (fc_comm/bn_comm, fc_obs/bn_obs, fc_boundary_state/bn_boundary_state, fc1/bn1):
+ *   Linear.weight [H][in] (in = 5, 4, 3, 3H), Linear.bias [H], bn.weight [H], bn.bias [H], bn.running_mean [H],
+ *   bn.running_var [H]
+ * then fc2.weight [1][H], fc2.bias [1].  The four bn.num_batches_tracked entries travel as a separate int64 [4].
+ * Adam blobs (n_train floats) hold the 18 trainable tensors in PMINetwork.parameters() order: per block Linear.weight,
+ * Linear.bias, bn.weight, bn.bias, then fc2.weight, fc2.bias; step [18] is each tensor's Adam step count. */
+typedef struct uavtrack_pmi_trainer_config {
+    uint32_t struct_size;       /* = sizeof(uavtrack_pmi_trainer_config), ABI check */
+    int32_t  device_id;         /* HIP device ordinal */
+    int32_t  hidden;            /* H in [1, 256] (PMINet.py:21 hidden_dim; the scorer's limit) */
+    int32_t  pad_;              /* 0 */
+    int64_t  max_batch;         /* scratch for mini-batches up to this many rows; 0 = 4096 (uavtrack_pmi_trainer_reserve) */
+    double   lr;                /* Adam learning rate (PMINet.py:39: 1e-3) */
+} uavtrack_pmi_trainer_config;
+
+typedef struct uavtrack_pmi_trainer uavtrack_pmi_trainer;   /* opaque handle */
+
+/* Replaces PMINetwork.__init__ (PMINet.py:21-39).  Every state entry, moment and count starts at zero: upload the
+ * initial state with uavtrack_pmi_trainer_set_params.  Allocates everything a train call needs. */
+int uavtrack_pmi_trainer_create(const uavtrack_pmi_trainer_config *cfg, uavtrack_pmi_trainer **out);
+int uavtrack_pmi_trainer_destroy(uavtrack_pmi_trainer *trainer);
+
+/* Floats in the state blob (n_state) and in each Adam moment blob (n_train). */
+int uavtrack_pmi_trainer_num_params(uavtrack_pmi_trainer *trainer, int64_t *n_state, int64_t *n_train);
+
+/* Grows the scratch to mini-batches of max_batch rows (allocates; synchronises the device).  Never shrinks. */
+int uavtrack_pmi_trainer_reserve(uavtrack_pmi_trainer *trainer, int64_t max_batch);
+
+/* load_state_dict / state_dict: HOST blobs, state [n_state] in the order above and num_batches_tracked [4] (>= 0).
+ * Synchronise `stream`.  A failing set leaves the previous state in place. */
+int uavtrack_pmi_trainer_set_params(uavtrack_pmi_trainer *trainer, const float *state, const int64_t *num_batches_tracked,
+                                    int64_t n_state, void *stream);
+int uavtrack_pmi_trainer_get_params(uavtrack_pmi_trainer *trainer, float *state, int64_t *num_batches_tracked,
+                                    int64_t n_state, void *stream);
+
+/* optimizer.load_state_dict / state_dict: exp_avg, exp_avg_sq [n_train] and step [18] (int64, >= 0) as HOST blobs in
+ * parameters() order.  Synchronise `stream`.  A failing set leaves the previous state in place. */
+int uavtrack_pmi_trainer_set_optimizer_state(uavtrack_pmi_trainer *trainer, const float *exp_avg, const float *exp_avg_sq,
+                                             const int64_t *step, int64_t n_train, void *stream);
+int uavtrack_pmi_trainer_get_optimizer_state(uavtrack_pmi_trainer *trainer, float *exp_avg, float *exp_avg_sq,
+                                             int64_t *step, int64_t n_train, void *stream);
+
+/* Replaces PMINetwork.train_pmi (PMINet.py:74-100) after its index draw, stream-ordered: no synchronisation, no
+ * allocation, capturable into a graph.  rows [n_rows][12] (DEVICE) is the observation history, timestep-major
+ * (n_rows = T * n_uav); t_idx [b2] and u_idx [b2][2] (DEVICE, int64) are the drawn triples.  Mini-batch b of
+ * batch_size rows takes input_1_2 row i = rows[t_idx[g] * n_uav + u_idx[g][0]], input_1_3 = rows[t_idx[g] * n_uav +
+ * u_idx[g][1]], g = b * batch_size + i; each of the b2 / batch_size steps is zero_grad, two train-mode forwards,
+ * CustomLoss, backward and one Adam step, the running statistics and step counts advancing on the device.
+ * Outputs (DEVICE): avg_loss (fp32 scalar: the mean of |loss| over the steps); losses [b2 / batch_size] (nullable:
+ * |loss| of each step); outputs [b2 / batch_size][2][batch_size] (nullable: output_1_2 and output_1_3 of each step).
+ * Returns an error, enqueuing nothing, for a null required pointer, n_uav < 1, n_rows not a positive multiple of
+ * n_uav, batch_size < 2, b2 < batch_size, or batch_size above the reserve.  A t_idx outside [0, T) or a u_idx outside
+ * [0, n_uav) is found on the device: the call then changes nothing (state, moments, counts), its losses are NaN, and
+ * the next uavtrack_pmi_trainer_check reports it. */
+int uavtrack_pmi_trainer_train(uavtrack_pmi_trainer *trainer, const float *rows, int64_t n_rows, int64_t n_uav,
+                               const int64_t *t_idx, const int64_t *u_idx, int64_t b2, int64_t batch_size,
+                               float *avg_loss, float *losses, float *outputs, void *stream);
+
+/* Synchronises `stream`; fails if any train call since the previous check was refused on the device (an index out
+ * of range).  refused (nullable) receives their number; the count restarts at 0. */
+int uavtrack_pmi_trainer_check(uavtrack_pmi_trainer *trainer, int64_t *refused, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

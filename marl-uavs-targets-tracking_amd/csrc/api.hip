@@ -1268,3 +1268,272 @@ int uavtrack_learner_check(uavtrack_learner *learner, int64_t *refused, void *st
 }
 
 }  // extern "C"
+
+// ---- the device PMI trainer ---------------------------------------------------------------------------------------
+
+struct uavtrack_pmi_trainer {
+    uavtrack_pmi_trainer_config cfg;
+    PmiTrainDevice d;
+};
+
+namespace {
+
+constexpr int64_t kPmiTrainDefaultBatch = 4096;
+
+void free_pmi_scratch(PmiTrainDevice &d)
+{
+    for (void *p : {(void *)d.xh0, (void *)d.a0, (void *)d.da0, (void *)d.xh1, (void *)d.a1, (void *)d.dz1, (void *)d.go})
+        if (p) (void)hipFree(p);
+    d.xh0 = d.a0 = d.da0 = d.xh1 = d.a1 = d.dz1 = d.go = nullptr;
+    d.max_b = 0;
+}
+
+void free_pmi_trainer(uavtrack_pmi_trainer *t)
+{
+    PmiTrainDevice &d = t->d;
+    free_pmi_scratch(d);
+    for (void *p : {(void *)d.state, (void *)d.nbt, (void *)d.grad, (void *)d.m, (void *)d.v, (void *)d.steps,
+                    (void *)d.inv0, (void *)d.inv1, (void *)d.acc, (void *)d.status, (void *)d.errors})
+        if (p) (void)hipFree(p);
+}
+
+hipError_t pmi_scratch(PmiTrainDevice &d, int64_t max_b)
+{
+    const size_t H = (size_t)d.L.H, nb = (size_t)max_b;
+    float *p[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    const size_t n[7] = {2 * 3 * H * nb, 2 * 3 * H * nb, 2 * 3 * H * nb, 2 * H * nb, 2 * H * nb, 2 * H * nb, 2 * nb};
+    hipError_t e = hipSuccess;
+    for (int i = 0; i < 7 && e == hipSuccess; ++i) e = dmalloc(&p[i], n[i]);
+    if (e != hipSuccess) {
+        for (float *q : p)
+            if (q) (void)hipFree(q);
+        return e;
+    }
+    free_pmi_scratch(d);
+    d.xh0 = p[0]; d.a0 = p[1]; d.da0 = p[2]; d.xh1 = p[3]; d.a1 = p[4]; d.dz1 = p[5]; d.go = p[6];
+    d.max_b = max_b;
+    return hipSuccess;
+}
+
+}  // namespace
+
+extern "C" {
+
+int uavtrack_pmi_trainer_create(const uavtrack_pmi_trainer_config *cfg, uavtrack_pmi_trainer **out)
+{
+    if (!cfg || !out) return fail("uavtrack_pmi_trainer_create: null argument");
+    *out = nullptr;
+    if (cfg->struct_size != sizeof(uavtrack_pmi_trainer_config))
+        return fail("uavtrack_pmi_trainer_create: struct_size %u != %zu (header / library mismatch)", cfg->struct_size,
+                    sizeof(uavtrack_pmi_trainer_config));
+    if (cfg->hidden < 1 || cfg->hidden > kPmiMaxHidden)
+        return fail("uavtrack_pmi_trainer_create: hidden %d out of range [1, %d]", cfg->hidden, kPmiMaxHidden);
+    if (cfg->max_batch < 0 || cfg->max_batch > kPmiTrainMaxBatch)
+        return fail("uavtrack_pmi_trainer_create: max_batch %lld out of range [0, %lld]", (long long)cfg->max_batch,
+                    (long long)kPmiTrainMaxBatch);
+    if (!std::isfinite(cfg->lr) || cfg->lr < 0) return fail("uavtrack_pmi_trainer_create: lr must be finite and >= 0");
+
+    int ndev = 0;
+    hipError_t e = hipGetDeviceCount(&ndev);
+    if (e != hipSuccess || ndev < 1)
+        return fail("uavtrack_pmi_trainer_create: no HIP device visible (%s); libuavtrack has no CPU fallback",
+                    e != hipSuccess ? hipGetErrorString(e) : "device count 0");
+    if (cfg->device_id < 0 || cfg->device_id >= ndev)
+        return fail("uavtrack_pmi_trainer_create: device_id %d out of range [0, %d)", cfg->device_id, ndev);
+    ON_DEVICE(cfg->device_id);
+    hipDeviceProp_t prop;
+    HIP_TRY(hipGetDeviceProperties(&prop, cfg->device_id));
+    if (strncmp(prop.gcnArchName, "gfx950", 6) != 0)
+        return fail("uavtrack_pmi_trainer_create: device %d is %s; this library is built for gfx950 only", cfg->device_id,
+                    prop.gcnArchName);
+
+    uavtrack_pmi_trainer *t = new (std::nothrow) uavtrack_pmi_trainer();
+    if (!t) return fail("uavtrack_pmi_trainer_create: out of host memory");
+    t->cfg = *cfg;
+    PmiTrainDevice &d = t->d;
+    d.L = PmiTrainLayout::make(cfg->hidden);
+    d.lr = (float)cfg->lr;
+    const size_t S = (size_t)d.L.S, P = (size_t)d.L.P, H = (size_t)cfg->hidden;
+    hipError_t he = hipSuccess;
+    if (he == hipSuccess) he = dmalloc(&d.state, S);
+    if (he == hipSuccess) he = dmalloc(&d.nbt, (size_t)kPmiBlocks);
+    if (he == hipSuccess) he = dmalloc(&d.grad, P);
+    if (he == hipSuccess) he = dmalloc(&d.m, P);
+    if (he == hipSuccess) he = dmalloc(&d.v, P);
+    if (he == hipSuccess) he = dmalloc(&d.steps, (size_t)kPmiTrainTensors);
+    if (he == hipSuccess) he = dmalloc(&d.inv0, 2 * 3 * H);
+    if (he == hipSuccess) he = dmalloc(&d.inv1, 2 * H);
+    if (he == hipSuccess) he = dmalloc(&d.acc, (size_t)1);
+    if (he == hipSuccess) he = dmalloc(&d.status, (size_t)1);
+    if (he == hipSuccess) he = dmalloc(&d.errors, (size_t)1);
+    if (he == hipSuccess) he = pmi_scratch(d, cfg->max_batch ? cfg->max_batch : kPmiTrainDefaultBatch);
+    if (he == hipSuccess) he = hipMemset(d.state, 0, S * 4);
+    if (he == hipSuccess) he = hipMemset(d.nbt, 0, kPmiBlocks * 8);
+    if (he == hipSuccess) he = hipMemset(d.grad, 0, P * 4);
+    if (he == hipSuccess) he = hipMemset(d.m, 0, P * 4);
+    if (he == hipSuccess) he = hipMemset(d.v, 0, P * 4);
+    if (he == hipSuccess) he = hipMemset(d.steps, 0, kPmiTrainTensors * 8);
+    if (he == hipSuccess) he = hipMemset(d.status, 0, 4);
+    if (he == hipSuccess) he = hipMemset(d.errors, 0, 4);
+    if (he == hipSuccess) he = hipDeviceSynchronize();
+    if (he != hipSuccess) {
+        free_pmi_trainer(t);
+        delete t;
+        return fail("uavtrack_pmi_trainer_create: %s", hipGetErrorString(he));
+    }
+    *out = t;
+    return 0;
+}
+
+int uavtrack_pmi_trainer_destroy(uavtrack_pmi_trainer *trainer)
+{
+    if (!trainer) return 0;
+    DeviceGuard guard(trainer->cfg.device_id);
+    (void)hipDeviceSynchronize();
+    free_pmi_trainer(trainer);
+    delete trainer;
+    return 0;
+}
+
+int uavtrack_pmi_trainer_num_params(uavtrack_pmi_trainer *trainer, int64_t *n_state, int64_t *n_train)
+{
+    if (!trainer || !n_state || !n_train) return fail("uavtrack_pmi_trainer_num_params: null argument");
+    *n_state = trainer->d.L.S;
+    *n_train = trainer->d.L.P;
+    return 0;
+}
+
+int uavtrack_pmi_trainer_reserve(uavtrack_pmi_trainer *trainer, int64_t max_batch)
+{
+    if (!trainer) return fail("uavtrack_pmi_trainer_reserve: null handle");
+    if (max_batch < 1 || max_batch > kPmiTrainMaxBatch)
+        return fail("uavtrack_pmi_trainer_reserve: max_batch %lld out of range [1, %lld]", (long long)max_batch,
+                    (long long)kPmiTrainMaxBatch);
+    if (max_batch <= trainer->d.max_b) return 0;
+    ON_DEVICE(trainer->cfg.device_id);
+    HIP_TRY(hipDeviceSynchronize());          // in-flight calls may still use the old scratch
+    HIP_TRY(pmi_scratch(trainer->d, max_batch));
+    return 0;
+}
+
+int uavtrack_pmi_trainer_set_params(uavtrack_pmi_trainer *trainer, const float *state, const int64_t *num_batches_tracked,
+                                    int64_t n_state, void *stream)
+{
+    if (!trainer || !state || !num_batches_tracked) return fail("uavtrack_pmi_trainer_set_params: null argument");
+    PmiTrainDevice &d = trainer->d;
+    if (n_state != d.L.S)
+        return fail("uavtrack_pmi_trainer_set_params: %lld floats, the network's state has %d", (long long)n_state, d.L.S);
+    for (int b = 0; b < kPmiBlocks; ++b)
+        if (num_batches_tracked[b] < 0)
+            return fail("uavtrack_pmi_trainer_set_params: num_batches_tracked[%d] = %lld < 0", b,
+                        (long long)num_batches_tracked[b]);
+    ON_DEVICE(trainer->cfg.device_id);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    HIP_TRY(hipStreamSynchronize(st));
+    HIP_TRY(hipMemcpyAsync(d.state, state, (size_t)n_state * 4, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(d.nbt, num_batches_tracked, kPmiBlocks * 8, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return 0;
+}
+
+int uavtrack_pmi_trainer_get_params(uavtrack_pmi_trainer *trainer, float *state, int64_t *num_batches_tracked,
+                                    int64_t n_state, void *stream)
+{
+    if (!trainer || !state || !num_batches_tracked) return fail("uavtrack_pmi_trainer_get_params: null argument");
+    PmiTrainDevice &d = trainer->d;
+    if (n_state != d.L.S)
+        return fail("uavtrack_pmi_trainer_get_params: %lld floats, the network's state has %d", (long long)n_state, d.L.S);
+    ON_DEVICE(trainer->cfg.device_id);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    HIP_TRY(hipMemcpyAsync(state, d.state, (size_t)n_state * 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(num_batches_tracked, d.nbt, kPmiBlocks * 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return 0;
+}
+
+int uavtrack_pmi_trainer_set_optimizer_state(uavtrack_pmi_trainer *trainer, const float *exp_avg, const float *exp_avg_sq,
+                                             const int64_t *step, int64_t n_train, void *stream)
+{
+    if (!trainer || !exp_avg || !exp_avg_sq || !step) return fail("uavtrack_pmi_trainer_set_optimizer_state: null argument");
+    PmiTrainDevice &d = trainer->d;
+    if (n_train != d.L.P)
+        return fail("uavtrack_pmi_trainer_set_optimizer_state: %lld floats, the network has %d trainable", (long long)n_train,
+                    d.L.P);
+    for (int t = 0; t < kPmiTrainTensors; ++t)
+        if (step[t] < 0) return fail("uavtrack_pmi_trainer_set_optimizer_state: step[%d] = %lld < 0", t, (long long)step[t]);
+    for (int64_t p = 0; p < n_train; ++p)
+        if (!(exp_avg_sq[p] >= 0.0f))
+            return fail("uavtrack_pmi_trainer_set_optimizer_state: exp_avg_sq[%lld] is not >= 0", (long long)p);
+    ON_DEVICE(trainer->cfg.device_id);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    HIP_TRY(hipStreamSynchronize(st));
+    HIP_TRY(hipMemcpyAsync(d.m, exp_avg, (size_t)n_train * 4, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(d.v, exp_avg_sq, (size_t)n_train * 4, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(d.steps, step, kPmiTrainTensors * 8, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return 0;
+}
+
+int uavtrack_pmi_trainer_get_optimizer_state(uavtrack_pmi_trainer *trainer, float *exp_avg, float *exp_avg_sq,
+                                             int64_t *step, int64_t n_train, void *stream)
+{
+    if (!trainer || !exp_avg || !exp_avg_sq || !step) return fail("uavtrack_pmi_trainer_get_optimizer_state: null argument");
+    PmiTrainDevice &d = trainer->d;
+    if (n_train != d.L.P)
+        return fail("uavtrack_pmi_trainer_get_optimizer_state: %lld floats, the network has %d trainable", (long long)n_train,
+                    d.L.P);
+    ON_DEVICE(trainer->cfg.device_id);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    HIP_TRY(hipMemcpyAsync(exp_avg, d.m, (size_t)n_train * 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(exp_avg_sq, d.v, (size_t)n_train * 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(step, d.steps, kPmiTrainTensors * 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return 0;
+}
+
+int uavtrack_pmi_trainer_train(uavtrack_pmi_trainer *trainer, const float *rows, int64_t n_rows, int64_t n_uav,
+                               const int64_t *t_idx, const int64_t *u_idx, int64_t b2, int64_t batch_size,
+                               float *avg_loss, float *losses, float *outputs, void *stream)
+{
+    if (!trainer) return fail("uavtrack_pmi_trainer_train: null handle");
+    if (!rows || !t_idx || !u_idx || !avg_loss)
+        return fail("uavtrack_pmi_trainer_train: rows, t_idx, u_idx and avg_loss must not be null");
+    if (n_uav < 1) return fail("uavtrack_pmi_trainer_train: n_uav = %lld < 1", (long long)n_uav);
+    if (n_rows < n_uav || n_rows % n_uav != 0)
+        return fail("uavtrack_pmi_trainer_train: n_rows = %lld is not a positive multiple of n_uav = %lld", (long long)n_rows,
+                    (long long)n_uav);
+    if (batch_size < 2)
+        return fail("uavtrack_pmi_trainer_train: batch_size = %lld < 2 (train-mode BatchNorm1d needs two rows)",
+                    (long long)batch_size);
+    if (batch_size > trainer->d.max_b)
+        return fail("uavtrack_pmi_trainer_train: batch_size = %lld, scratch is reserved for %lld (uavtrack_pmi_trainer_reserve)",
+                    (long long)batch_size, (long long)trainer->d.max_b);
+    if (b2 < batch_size)
+        return fail("uavtrack_pmi_trainer_train: b2 = %lld < batch_size = %lld (no mini-batch)", (long long)b2,
+                    (long long)batch_size);
+    if (b2 / batch_size > (int64_t)1 << 30) return fail("uavtrack_pmi_trainer_train: b2 = %lld too large", (long long)b2);
+    ON_DEVICE(trainer->cfg.device_id);
+    PmiTrainLaunch q;
+    q.rows = rows; q.n_rows = n_rows; q.n_uav = n_uav; q.b2 = b2; q.batch = batch_size;
+    q.t_idx = t_idx; q.u_idx = u_idx; q.avg_loss = avg_loss; q.losses = losses; q.outputs = outputs;
+    HIP_TRY(launch_pmi_train(trainer->d, q, static_cast<hipStream_t>(stream)));
+    return 0;
+}
+
+int uavtrack_pmi_trainer_check(uavtrack_pmi_trainer *trainer, int64_t *refused, void *stream)
+{
+    if (!trainer) return fail("uavtrack_pmi_trainer_check: null handle");
+    ON_DEVICE(trainer->cfg.device_id);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    int count = 0;
+    HIP_TRY(hipMemcpyAsync(&count, trainer->d.errors, 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemsetAsync(trainer->d.errors, 0, 4, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (refused) *refused = count;
+    if (count)
+        return fail("uavtrack_pmi_trainer_check: %d train call(s) refused: a timestep index outside [0, T) or a uav index "
+                    "outside [0, n_uav); they changed nothing", count);
+    return 0;
+}
+
+}  // extern "C"

@@ -288,4 +288,64 @@ int learner_groups(const LearnerLayout &L, int64_t n);
 hipError_t learner_prepare_kernels(const LearnerLayout &L);
 hipError_t launch_learner_update(const LearnerDevice &d, const LearnerLaunch &q, hipStream_t stream);
 
+// pmi_train_kernel.hip -- the device PMI trainer (uavtrack_pmi_trainer_*).  `state` holds the float entries of the
+// reference PMINetwork's state_dict in its order (26 tensors: per Linear+BatchNorm1d block weight, bias, bn weight, bn
+// bias, running_mean, running_var; then fc2.weight, fc2.bias); the gradients and Adam moments hold the 18 trainable
+// tensors in PMINetwork.parameters() order (per block weight, bias, bn weight, bn bias; then fc2).
+constexpr int kPmiTrainTensors = 18;
+constexpr int kPmiStateTensors = 26;
+constexpr int kPmiBlocks = 4;                 // fc_comm, fc_obs, fc_boundary_state, fc1 (each with a BatchNorm1d)
+constexpr int64_t kPmiTrainMaxBatch = (int64_t)1 << 20;
+struct PmiTrainLayout {
+    int H, S, P;
+    int soff[kPmiStateTensors + 1];           // state tensor offsets (soff[26] = S)
+    int poff[kPmiTrainTensors + 1];           // trainable tensor offsets (poff[18] = P)
+    __host__ __device__ static int state_of(int t) { return t < 16 ? (t / 4) * 6 + t % 4 : t + 8; }
+    static PmiTrainLayout make(int H)
+    {
+        PmiTrainLayout L;
+        L.H = H;
+        const int in[kPmiBlocks] = {5, 4, 3, 3 * H};
+        int ssz[kPmiStateTensors], k = 0;
+        for (int b = 0; b < kPmiBlocks; ++b) {
+            ssz[k++] = H * in[b];
+            for (int q = 0; q < 5; ++q) ssz[k++] = H;
+        }
+        ssz[k++] = H;
+        ssz[k++] = 1;
+        L.soff[0] = 0;
+        for (int t = 0; t < kPmiStateTensors; ++t) L.soff[t + 1] = L.soff[t] + ssz[t];
+        L.poff[0] = 0;
+        for (int t = 0; t < kPmiTrainTensors; ++t) L.poff[t + 1] = L.poff[t] + ssz[state_of(t)];
+        L.S = L.soff[kPmiStateTensors];
+        L.P = L.poff[kPmiTrainTensors];
+        return L;
+    }
+};
+// the device state of one trainer handle
+struct PmiTrainDevice {
+    PmiTrainLayout L;
+    float lr;
+    float *state;                   // [S] state_dict floats
+    int64_t *nbt;                   // [4] num_batches_tracked per BatchNorm1d
+    float *grad, *m, *v;            // [P]
+    int64_t *steps;                 // [18] Adam step per trainable tensor
+    // per-step scratch, feature-major ([side][feature][row]) for batches up to max_b rows
+    float *xh0, *a0, *da0;          // [2][3H][max_b] branch BN: normalised input, post-ReLU output, dL/d(output)
+    float *xh1, *a1, *dz1;          // [2][H][max_b]  bn1: normalised input, post-ReLU output; dL/d(fc1 output)
+    float *inv0, *inv1;             // [2][3H], [2][H] 1 / sqrt(var + eps) of the current step
+    float *go;                      // [2][max_b] dL/d(output_1_2), dL/d(output_1_3)
+    float *acc;                     // [1] sum of |loss| over the call
+    int *status;                    // [1] this call's input errors
+    int *errors;                    // [1] calls refused since the last uavtrack_pmi_trainer_check
+    int64_t max_b;
+};
+struct PmiTrainLaunch {
+    const float *rows;
+    int64_t n_rows, n_uav, b2, batch;
+    const int64_t *t_idx, *u_idx;
+    float *avg_loss, *losses, *outputs;
+};
+hipError_t launch_pmi_train(const PmiTrainDevice &d, const PmiTrainLaunch &q, hipStream_t stream);
+
 }  // namespace uavtrack

@@ -16,6 +16,7 @@ from .export import (uav_tracks_from_obs, save_uav_positions, save_covered_num, 
                      save_target_positions, save_rollout)
 from .replay import DeviceReplayBuffer, PrioritizedDeviceReplayBuffer, transitions_from_rollout  # noqa: F401
 from .learner import DeviceActorCritic, ValueMLP  # noqa: F401
+from .pmi_trainer import DevicePMINetwork  # noqa: F401
 from .pmi_data import sample_pmi_pairs, pmi_contrastive_loss, pmi_batches, train_pmi_epoch  # noqa: F401
 from . import _lib  # noqa: F401
 
@@ -23,4 +24,5 @@ __all__ = ["EnvConfig", "RewardMode", "BatchedUavEnv", "Environment", "fold_pmi_
            "shard_range", "gather_rollout_summary", "gather_rollout_summary_async", "sample_local_transitions", "gather_transitions",
            "gather_transitions_async", "ActorMLP", "BatchedRollout", "sample_actions",
            "DeviceReplayBuffer", "PrioritizedDeviceReplayBuffer", "transitions_from_rollout", "DeviceActorCritic", "ValueMLP",
+           "DevicePMINetwork",
            "sample_pmi_pairs", "pmi_contrastive_loss", "pmi_batches", "train_pmi_epoch", "make_pmi_net"]

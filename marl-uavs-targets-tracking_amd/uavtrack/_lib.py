@@ -50,6 +50,16 @@ class LearnerConfig(C.Structure):
     ]
 
 
+class PmiTrainerConfig(C.Structure):
+    """Mirror of `struct uavtrack_pmi_trainer_config` (include/uavtrack.h)."""
+    _fields_ = [
+        ("struct_size", C.c_uint32), ("device_id", C.c_int32), ("hidden", C.c_int32), ("pad_", C.c_int32),
+        ("max_batch", C.c_int64), ("lr", C.c_double),
+    ]
+
+
+PMI_TRAIN_TENSORS = 18                                    # PMINetwork.parameters()
+PMI_BN_LAYERS = 4                                         # BatchNorm1d layers (num_batches_tracked entries)
 LOSS_FORMS = ("reference", "per_sample")                  # enum uavtrack_actor_loss
 LEARNER_TENSORS = 8                                       # parameter tensors: actor fc1.w fc1.b fc2.w fc2.b, critic likewise
 ACTOR_SAMPLE, ACTOR_ARGMAX = 0, 1   # enum in include/uavtrack.h
@@ -98,6 +108,17 @@ SIGNATURES = {
     "uavtrack_learner_get_optimizer_state": (C.c_int, [C.c_void_p] + [C.c_void_p] * 3 + [C.c_int64, C.c_void_p]),
     "uavtrack_learner_update": (C.c_int, [C.c_void_p, C.c_int64] + [C.c_void_p] * 4 + [C.c_int64] + [C.c_void_p] * 6),
     "uavtrack_learner_check": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64), C.c_void_p]),
+    "uavtrack_pmi_trainer_create": (C.c_int, [C.POINTER(PmiTrainerConfig), C.POINTER(C.c_void_p)]),
+    "uavtrack_pmi_trainer_destroy": (C.c_int, [C.c_void_p]),
+    "uavtrack_pmi_trainer_num_params": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "uavtrack_pmi_trainer_reserve": (C.c_int, [C.c_void_p, C.c_int64]),
+    "uavtrack_pmi_trainer_set_params": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
+    "uavtrack_pmi_trainer_get_params": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
+    "uavtrack_pmi_trainer_set_optimizer_state": (C.c_int, [C.c_void_p] + [C.c_void_p] * 3 + [C.c_int64, C.c_void_p]),
+    "uavtrack_pmi_trainer_get_optimizer_state": (C.c_int, [C.c_void_p] + [C.c_void_p] * 3 + [C.c_int64, C.c_void_p]),
+    "uavtrack_pmi_trainer_train": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p,
+                                              C.c_int64, C.c_int64] + [C.c_void_p] * 4),
+    "uavtrack_pmi_trainer_check": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64), C.c_void_p]),
 }
 
 _lib = None

@@ -12,6 +12,7 @@ import torch
 from . import _lib
 from .config import EnvConfig, RewardMode
 from .pmi import fold_pmi_state_dict
+from .pmi_trainer import DevicePMINetwork
 
 _STATE_KEYS = ("ux", "uy", "uz", "uh", "ua", "tx", "ty", "tz", "th")
 
@@ -348,11 +349,12 @@ class BatchedUavEnv:
         torch.cuda.current_stream(self.device).synchronize()
 
     def set_pmi(self, state_dict) -> None:
-        """state_dict of a reference PMINetwork (or None to disable)."""
+        """state_dict of a reference PMINetwork, a uavtrack.DevicePMINetwork (its current weights, through the same host
+        blob), or None to disable."""
         if state_dict is None:
             _lib.check(self._lib.uavtrack_set_pmi_weights(self._h, None, 0, 0, self._stream()), "set_pmi")
             return
-        blob, hidden = fold_pmi_state_dict(state_dict)
+        blob, hidden = state_dict.folded() if isinstance(state_dict, DevicePMINetwork) else fold_pmi_state_dict(state_dict)
         _lib.check(self._lib.uavtrack_set_pmi_weights(self._h, C.c_void_p(blob.ctypes.data), blob.size, hidden,
                                                       self._stream()), "uavtrack_set_pmi_weights")
 

@@ -49,7 +49,8 @@ def make_pmi_net(hidden_dim: int = 128):
     """A trainable network with the reference PMINetwork's architecture and parameter names (PMINet.py:20-62:
     three branch Linear+BatchNorm1d+ReLU over x[0:5] / x[5:9] / x[9:12], concat, Linear(3H,H)+BN+ReLU, Linear(H,1)),
     so state_dicts move freely between the two and `BatchedUavEnv.set_pmi(net.state_dict())` folds and uploads
-    it.  Training stays plain PyTorch (learner side); see examples/train_maac.py --method maac-r."""
+    it.  It trains in plain PyTorch (examples/train_maac.py --method maac-r); uavtrack.DevicePMINetwork trains the same
+    network on the device."""
     import torch
 
     class PmiNet(torch.nn.Module):

@@ -1,0 +1,230 @@
+"""The reference's PMINetwork training surface (src/models/PMINet.py:20-109) on the device: one `train_pmi` is ONE
+library call (uavtrack_pmi_trainer_train) -- every mini-batch step's gather, both train-mode forwards, CustomLoss,
+the backward pass and the torch.optim.Adam step -- stream-ordered, with no synchronisation and no allocation inside
+the library.  The (timestep, uav-pair) triples are drawn as `sample_pmi_pairs` draws them, so under the same
+torch.manual_seed the trainer selects the reference's rows; the rows themselves are gathered in the kernels.
+
+state_dict / save / load speak the reference's formats (30 state_dict keys; {'model_state_dict',
+'optimizer_state_dict'} checkpoints under <save_dir>/pmi/), and `BatchedUavEnv.set_pmi(trainer)` folds and uploads
+the trained network to the MAAC-R scorer."""
+from __future__ import annotations
+
+import ctypes as C
+import os
+from collections import OrderedDict
+from typing import Optional
+
+import numpy as np
+import torch
+
+from . import _lib
+from .pmi import fold_pmi_state_dict, make_pmi_net
+
+_BN = ("bn_comm", "bn_obs", "bn_boundary_state", "bn1")
+
+
+def _ptr(t: Optional[torch.Tensor]):
+    return None if t is None else C.c_void_p(t.data_ptr())
+
+
+def _vp(a: np.ndarray):
+    return a.ctypes.data_as(C.c_void_p)
+
+
+class DevicePMINetwork:
+    """PMINetwork(hidden_dim=hidden_dim, b2_size=b2_size) with train_pmi on the GPU.  Initial weights are
+    torch.nn.Linear's defaults drawn from torch's global generator in the reference's layer order, so under the same
+    seed they are the reference's; the learning rate defaults to the reference's Adam(lr=0.001) (PMINet.py:39)."""
+
+    def __init__(self, hidden_dim: int = 64, b2_size: int = 3000, device="cuda:0", lr: float = 1e-3,
+                 max_batch: int = 0):
+        self.device = torch.device(device)
+        if self.device.index is None:
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        self.hidden_dim, self.b2_size, self.lr = int(hidden_dim), int(b2_size), float(lr)
+        if not 1 <= self.hidden_dim <= 256:
+            raise ValueError(f"hidden_dim must be in [1, 256], got {hidden_dim}")
+        self._net = make_pmi_net(self.hidden_dim)      # host-side module: layout, initialisation, state_dict format
+        self._lib = _lib.load()
+        cfg = _lib.PmiTrainerConfig(struct_size=C.sizeof(_lib.PmiTrainerConfig), device_id=self.device.index,
+                                    hidden=self.hidden_dim, pad_=0, max_batch=int(max_batch), lr=self.lr)
+        h = C.c_void_p()
+        _lib.check(self._lib.uavtrack_pmi_trainer_create(C.byref(cfg), C.byref(h)), "uavtrack_pmi_trainer_create")
+        self._h = h
+        ns, nt = C.c_int64(), C.c_int64()
+        _lib.check(self._lib.uavtrack_pmi_trainer_num_params(self._h, C.byref(ns), C.byref(nt)),
+                   "uavtrack_pmi_trainer_num_params")
+        self.num_state, self.num_params = ns.value, nt.value
+        self.load_state_dict(self._net.state_dict())
+
+    # ---- handle plumbing
+    def close(self) -> None:
+        if getattr(self, "_h", None):
+            self._lib.uavtrack_pmi_trainer_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _stream(self):
+        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+
+    def reserve(self, max_batch: int) -> None:
+        """Scratch for mini-batches of up to max_batch rows (a larger batch_size is an error; the default is 4096)."""
+        _lib.check(self._lib.uavtrack_pmi_trainer_reserve(self._h, int(max_batch)), "uavtrack_pmi_trainer_reserve")
+
+    def check(self) -> None:
+        """Synchronises; raises if a train call since the last check was refused on the device (an index out of
+        range), which then changed nothing."""
+        _lib.check(self._lib.uavtrack_pmi_trainer_check(self._h, None, self._stream()), "uavtrack_pmi_trainer_check")
+
+    # ---- training
+    def train_indices(self, rows: torch.Tensor, n_uav: int, t_idx: torch.Tensor, u_idx: torch.Tensor,
+                      batch_size: int, avg_loss: Optional[torch.Tensor] = None, losses: Optional[torch.Tensor] = None,
+                      outputs: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """train_pmi after its index draw: rows [T * n_uav, 12] fp32, t_idx [b2] and u_idx [b2, 2] int64, all
+        contiguous on this trainer's device.  Optional outputs (device, fp32): losses [b2 // batch_size] (|loss| per
+        step), outputs [b2 // batch_size, 2, batch_size] (output_1_2, output_1_3).  Returns avg_loss, a device
+        scalar, without synchronising.  Fixed shapes and no allocation when avg_loss is given: capturable."""
+        b2 = int(t_idx.numel())
+        for name, t, dt in (("rows", rows, torch.float32), ("t_idx", t_idx, torch.int64), ("u_idx", u_idx, torch.int64)):
+            if t.device != self.device or t.dtype != dt or not t.is_contiguous():
+                raise ValueError(f"{name} must be a contiguous {dt} tensor on {self.device}")
+        if rows.dim() != 2 or rows.shape[1] != _lib.OBS_DIM:
+            raise ValueError(f"rows must be [T * n_uav, {_lib.OBS_DIM}], got {tuple(rows.shape)}")
+        if tuple(u_idx.shape) != (b2, 2):
+            raise ValueError(f"u_idx must be [{b2}, 2], got {tuple(u_idx.shape)}")
+        nb = b2 // int(batch_size) if batch_size > 0 else 0
+        for name, t, shape in (("losses", losses, (nb,)), ("outputs", outputs, (nb, 2, int(batch_size)))):
+            if t is not None and (t.device != self.device or t.dtype != torch.float32 or not t.is_contiguous()
+                                  or tuple(t.shape) != shape):
+                raise ValueError(f"{name} must be a contiguous float32 {list(shape)} tensor on {self.device}")
+        if avg_loss is None:
+            avg_loss = torch.empty((), device=self.device)
+        _lib.check(self._lib.uavtrack_pmi_trainer_train(
+            self._h, _ptr(rows), int(rows.shape[0]), int(n_uav), _ptr(t_idx), _ptr(u_idx), b2, int(batch_size),
+            _ptr(avg_loss), _ptr(losses), _ptr(outputs), self._stream()), "uavtrack_pmi_trainer_train")
+        return avg_loss
+
+    def train_pmi(self, config, train_data: torch.Tensor, n_uav: int, generator: Optional[torch.Generator] = None,
+                  sync: bool = True):
+        """PMINetwork.train_pmi (PMINet.py:74-100): train_data [T * n_uav, 12] or [T, (B,) n_uav, 12] observations on
+        the device; config["pmi"]["batch_size"].  The index triples come from torch's CPU generator (the global one
+        unless `generator` is given; a device generator keeps the draw on the device) in the reference's order.
+        Returns avg_loss as a float (sync=True) or a device scalar."""
+        bs = int(config["pmi"]["batch_size"])
+        rows = train_data.reshape(-1, _lib.OBS_DIM)
+        if rows.device != self.device:
+            raise ValueError(f"train_data must be on {self.device}")
+        rows = rows.to(torch.float32).contiguous()
+        if rows.shape[0] % int(n_uav) != 0:
+            raise ValueError(f"train_data has {rows.shape[0]} rows, not a multiple of n_uav = {n_uav}")
+        T = rows.shape[0] // int(n_uav)
+        draw_dev = generator.device if generator is not None else torch.device("cpu")
+        t_idx = torch.randint(low=0, high=T, size=(self.b2_size,), device=draw_dev, generator=generator)
+        u_idx = torch.randint(low=0, high=int(n_uav), size=(self.b2_size, 2), device=draw_dev, generator=generator)
+        avg = self.train_indices(rows, int(n_uav), t_idx.to(self.device).contiguous(), u_idx.to(self.device).contiguous(),
+                                 bs)
+        return float(avg) if sync else avg
+
+    # ---- state
+    def _get(self):
+        st = np.empty(self.num_state, np.float32)
+        nbt = np.empty(_lib.PMI_BN_LAYERS, np.int64)
+        _lib.check(self._lib.uavtrack_pmi_trainer_get_params(self._h, _vp(st), _vp(nbt), st.size, self._stream()),
+                   "uavtrack_pmi_trainer_get_params")
+        return st, nbt
+
+    def state_dict(self) -> "OrderedDict[str, torch.Tensor]":
+        """The reference PMINetwork's state_dict (30 keys, its order; CPU tensors)."""
+        st, nbt = self._get()
+        sd, o = OrderedDict(), 0
+        for k, v in self._net.state_dict().items():
+            if k.endswith("num_batches_tracked"):
+                sd[k] = torch.tensor(int(nbt[_BN.index(k.split(".")[0])]), dtype=torch.int64)
+            else:
+                sd[k] = torch.from_numpy(st[o:o + v.numel()].copy()).view_as(v)
+                o += v.numel()
+        return sd
+
+    def load_state_dict(self, sd) -> None:
+        """PMINetwork.load_state_dict: torch checks keys and shapes first; the Adam state stays as it is."""
+        probe = make_pmi_net(self.hidden_dim)
+        probe.load_state_dict(sd)
+        items = probe.state_dict()
+        st = np.ascontiguousarray(np.concatenate([v.detach().float().numpy().ravel() for k, v in items.items()
+                                                  if not k.endswith("num_batches_tracked")]), np.float32)
+        nbt = np.array([int(items[b + ".num_batches_tracked"]) for b in _BN], np.int64)
+        _lib.check(self._lib.uavtrack_pmi_trainer_set_params(self._h, _vp(st), _vp(nbt), st.size, self._stream()),
+                   "uavtrack_pmi_trainer_set_params")
+
+    def optimizer_state(self):
+        """(exp_avg [P], exp_avg_sq [P], step [18]) as numpy arrays, parameters() order."""
+        P = self.num_params
+        m, v = np.empty(P, np.float32), np.empty(P, np.float32)
+        steps = np.empty(_lib.PMI_TRAIN_TENSORS, np.int64)
+        _lib.check(self._lib.uavtrack_pmi_trainer_get_optimizer_state(self._h, _vp(m), _vp(v), _vp(steps), P,
+                                                                      self._stream()),
+                   "uavtrack_pmi_trainer_get_optimizer_state")
+        return m, v, steps
+
+    def _split(self, flat: np.ndarray):
+        out, o = [], 0
+        for p in self._net.parameters():
+            out.append(torch.from_numpy(flat[o:o + p.numel()].copy()).view_as(p))
+            o += p.numel()
+        return out
+
+    def optimizer_state_dict(self) -> dict:
+        """torch.optim.Adam(PMINetwork.parameters(), lr).state_dict() of this trainer, built by torch itself."""
+        m, v, steps = self.optimizer_state()
+        ms, vs = self._split(m), self._split(v)
+        params = list(self._net.parameters())
+        opt = torch.optim.Adam(params, lr=self.lr)
+        for i, p in enumerate(params):
+            if steps[i] > 0:
+                opt.state[p] = {"step": torch.tensor(float(steps[i])), "exp_avg": ms[i].clone(), "exp_avg_sq": vs[i].clone()}
+        return opt.state_dict()
+
+    def load_optimizer_state_dict(self, sd: dict) -> None:
+        """optimizer.load_state_dict: a torch.optim.Adam state_dict over PMINetwork.parameters().  (The learning rate
+        stays the one this trainer was built with.)"""
+        params = list(make_pmi_net(self.hidden_dim).parameters())
+        opt = torch.optim.Adam(params, lr=self.lr)
+        opt.load_state_dict(sd)                           # torch validates the dict
+        ms, vs, steps = [], [], np.zeros(_lib.PMI_TRAIN_TENSORS, np.int64)
+        for i, p in enumerate(params):
+            st = opt.state.get(p, {})
+            if st:
+                steps[i] = int(float(st["step"]))
+                ms.append(st["exp_avg"].detach().float().cpu().reshape(p.shape))
+                vs.append(st["exp_avg_sq"].detach().float().cpu().reshape(p.shape))
+            else:
+                ms.append(torch.zeros_like(p))
+                vs.append(torch.zeros_like(p))
+        flat = lambda ts: np.ascontiguousarray(np.concatenate([t.detach().numpy().ravel() for t in ts]), np.float32)
+        mf, vf = flat(ms), flat(vs)
+        _lib.check(self._lib.uavtrack_pmi_trainer_set_optimizer_state(self._h, _vp(mf), _vp(vf), _vp(steps),
+                                                                      self.num_params, self._stream()),
+                   "uavtrack_pmi_trainer_set_optimizer_state")
+
+    def save(self, save_dir: str, epoch_i) -> None:
+        """PMINetwork.save (PMINet.py:102-106): <save_dir>/pmi/pmi_weights_<epoch>.pth holding
+        {'model_state_dict', 'optimizer_state_dict'}."""
+        os.makedirs(os.path.join(save_dir, "pmi"), exist_ok=True)
+        torch.save({"model_state_dict": self.state_dict(), "optimizer_state_dict": self.optimizer_state_dict()},
+                   os.path.join(save_dir, "pmi", f"pmi_weights_{epoch_i}.pth"))
+
+    def load(self, path: Optional[str]) -> None:
+        """PMINetwork.load (PMINet.py:108-112): a checkpoint that exists replaces the weights and the Adam state."""
+        if path and os.path.exists(path):
+            ck = torch.load(path, map_location="cpu")
+            self.load_state_dict(ck["model_state_dict"])
+            self.load_optimizer_state_dict(ck["optimizer_state_dict"])
+
+    def folded(self):
+        """(blob, hidden): the BatchNorm-folded eval-mode network uavtrack_set_pmi_weights takes."""
+        return fold_pmi_state_dict(self.state_dict())
