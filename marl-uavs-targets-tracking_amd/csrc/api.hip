@@ -69,6 +69,21 @@ hipError_t dmalloc(T **p, size_t n)
     return hipMalloc(reinterpret_cast<void **>(p), (n ? n : 1) * sizeof(T));
 }
 
+// The device a handle is created on (`fn` names the creating ABI function in the error): visible, and a gfx950.
+int accept_device(const char *fn, int device_id, hipDeviceProp_t *prop)
+{
+    int ndev = 0;
+    hipError_t e = hipGetDeviceCount(&ndev);
+    if (e != hipSuccess || ndev < 1)
+        return fail("%s: no HIP device visible (%s); libuavtrack has no CPU fallback", fn,
+                    e != hipSuccess ? hipGetErrorString(e) : "device count 0");
+    if (device_id < 0 || device_id >= ndev) return fail("%s: device_id %d out of range [0, %d)", fn, device_id, ndev);
+    HIP_TRY(hipGetDeviceProperties(prop, device_id));
+    if (strncmp(prop->gcnArchName, "gfx950", 6) != 0)
+        return fail("%s: device %d is %s; this library is built for gfx950 only", fn, device_id, prop->gcnArchName);
+    return 0;
+}
+
 void drop_profile(uavtrack_env *env)
 {
     for (auto &r : env->prof) { (void)hipEventDestroy(r.a); (void)hipEventDestroy(r.b); }
@@ -294,20 +309,9 @@ int uavtrack_create(const uavtrack_config *cfg, uavtrack_env **out)
     if (!cfg || !out) return fail("uavtrack_create: null argument");
     *out = nullptr;
     if (validate(*cfg)) return 1;
-
-    int ndev = 0;
-    hipError_t e = hipGetDeviceCount(&ndev);
-    if (e != hipSuccess || ndev < 1)
-        return fail("uavtrack_create: no HIP device visible (%s); libuavtrack has no CPU fallback",
-                    e != hipSuccess ? hipGetErrorString(e) : "device count 0");
-    if (cfg->device_id < 0 || cfg->device_id >= ndev)
-        return fail("uavtrack_create: device_id %d out of range [0, %d)", cfg->device_id, ndev);
-    ON_DEVICE(cfg->device_id);
     hipDeviceProp_t prop;
-    HIP_TRY(hipGetDeviceProperties(&prop, cfg->device_id));
-    if (strncmp(prop.gcnArchName, "gfx950", 6) != 0)
-        return fail("uavtrack_create: device %d is %s; this library is built for gfx950 only", cfg->device_id,
-                    prop.gcnArchName);
+    if (accept_device("uavtrack_create", cfg->device_id, &prop)) return 1;
+    ON_DEVICE(cfg->device_id);
 
     uavtrack_env *env = new (std::nothrow) uavtrack_env();
     if (!env) return fail("uavtrack_create: out of host memory");
@@ -1016,6 +1020,79 @@ int uavtrack_kernel_info(uavtrack_env *env, int64_t out[5])
 
 }  // extern "C"
 
+// ---- shared by the two device trainers: their Adam state and refusal words (AdamState, internal.h) -----------------
+
+namespace {
+
+void adam_free(AdamState &o)
+{
+    for (void *p : {(void *)o.m, (void *)o.v, (void *)o.steps, (void *)o.status, (void *)o.errors})
+        if (p) (void)hipFree(p);
+    o = AdamState();
+}
+
+// All or nothing: zeroed moments, steps and refusal words for `tensors` tensors of P floats in all, or nothing
+// allocated and the error returned.
+hipError_t adam_alloc(AdamState &o, int tensors, int P)
+{
+    AdamState n;
+    n.tensors = tensors;
+    n.P = P;
+    hipError_t e = dmalloc(&n.m, (size_t)P);
+    if (e == hipSuccess) e = dmalloc(&n.v, (size_t)P);
+    if (e == hipSuccess) e = dmalloc(&n.steps, (size_t)tensors);
+    if (e == hipSuccess) e = dmalloc(&n.status, (size_t)1);
+    if (e == hipSuccess) e = dmalloc(&n.errors, (size_t)1);
+    if (e == hipSuccess) e = hipMemset(n.m, 0, (size_t)P * 4);
+    if (e == hipSuccess) e = hipMemset(n.v, 0, (size_t)P * 4);
+    if (e == hipSuccess) e = hipMemset(n.steps, 0, (size_t)tensors * 8);
+    if (e == hipSuccess) e = hipMemset(n.status, 0, 4);
+    if (e == hipSuccess) e = hipMemset(n.errors, 0, 4);
+    if (e != hipSuccess) {
+        adam_free(n);
+        return e;
+    }
+    o = n;
+    return hipSuccess;
+}
+
+// Loads exp_avg, exp_avg_sq [o.P] and step [o.tensors] from the host (the caller has checked the size).  Everything is
+// validated before the first copy, so a refused load leaves the previous state in place.
+int adam_set(const AdamState &o, const char *fn, const float *exp_avg, const float *exp_avg_sq, const int64_t *step,
+             hipStream_t st)
+{
+    for (int t = 0; t < o.tensors; ++t)
+        if (step[t] < 0) return fail("%s: step[%d] = %lld < 0", fn, t, (long long)step[t]);
+    for (int64_t p = 0; p < o.P; ++p)
+        if (!(exp_avg_sq[p] >= 0.0f)) return fail("%s: exp_avg_sq[%lld] is not >= 0", fn, (long long)p);
+    HIP_TRY(hipStreamSynchronize(st));
+    HIP_TRY(hipMemcpyAsync(o.m, exp_avg, (size_t)o.P * 4, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(o.v, exp_avg_sq, (size_t)o.P * 4, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(o.steps, step, (size_t)o.tensors * 8, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return 0;
+}
+
+int adam_get(const AdamState &o, float *exp_avg, float *exp_avg_sq, int64_t *step, hipStream_t st)
+{
+    HIP_TRY(hipMemcpyAsync(exp_avg, o.m, (size_t)o.P * 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(exp_avg_sq, o.v, (size_t)o.P * 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(step, o.steps, (size_t)o.tensors * 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return 0;
+}
+
+// The calls refused on the device since the last check, and the count cleared; synchronises the stream.
+int take_refusals(const AdamState &o, int *count, hipStream_t st)
+{
+    HIP_TRY(hipMemcpyAsync(count, o.errors, 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemsetAsync(o.errors, 0, 4, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return 0;
+}
+
+}  // namespace
+
 // ---- the device learner -------------------------------------------------------------------------------------------
 
 struct uavtrack_learner {
@@ -1036,8 +1113,8 @@ void free_learner(uavtrack_learner *l)
 {
     LearnerDevice &d = l->d;
     free_learner_scratch(d);
-    for (void *p : {(void *)d.params, (void *)d.m, (void *)d.v, (void *)d.steps, (void *)d.partials, (void *)d.scal,
-                    (void *)d.status, (void *)d.errors})
+    adam_free(d.opt);
+    for (void *p : {(void *)d.params, (void *)d.partials, (void *)d.scal})
         if (p) (void)hipFree(p);
 }
 
@@ -1083,19 +1160,9 @@ int uavtrack_learner_create(const uavtrack_learner_config *cfg, uavtrack_learner
         cfg->actor_lr < 0 || cfg->critic_lr < 0)
         return fail("uavtrack_learner_create: gamma and the learning rates must be finite, the rates >= 0");
 
-    int ndev = 0;
-    hipError_t e = hipGetDeviceCount(&ndev);
-    if (e != hipSuccess || ndev < 1)
-        return fail("uavtrack_learner_create: no HIP device visible (%s); libuavtrack has no CPU fallback",
-                    e != hipSuccess ? hipGetErrorString(e) : "device count 0");
-    if (cfg->device_id < 0 || cfg->device_id >= ndev)
-        return fail("uavtrack_learner_create: device_id %d out of range [0, %d)", cfg->device_id, ndev);
-    ON_DEVICE(cfg->device_id);
     hipDeviceProp_t prop;
-    HIP_TRY(hipGetDeviceProperties(&prop, cfg->device_id));
-    if (strncmp(prop.gcnArchName, "gfx950", 6) != 0)
-        return fail("uavtrack_learner_create: device %d is %s; this library is built for gfx950 only", cfg->device_id,
-                    prop.gcnArchName);
+    if (accept_device("uavtrack_learner_create", cfg->device_id, &prop)) return 1;
+    ON_DEVICE(cfg->device_id);
 
     uavtrack_learner *l = new (std::nothrow) uavtrack_learner();
     if (!l) return fail("uavtrack_learner_create: out of host memory");
@@ -1107,22 +1174,12 @@ int uavtrack_learner_create(const uavtrack_learner_config *cfg, uavtrack_learner
     d.critic_lr = (float)cfg->critic_lr;
     d.per_sample = cfg->loss == UAVTRACK_LOSS_PER_SAMPLE;
     const size_t P = (size_t)d.L.P;
-    hipError_t he = hipSuccess;
+    hipError_t he = adam_alloc(d.opt, kLearnerTensors, d.L.P);
     if (he == hipSuccess) he = dmalloc(&d.params, P);
-    if (he == hipSuccess) he = dmalloc(&d.m, P);
-    if (he == hipSuccess) he = dmalloc(&d.v, P);
-    if (he == hipSuccess) he = dmalloc(&d.steps, (size_t)kLearnerTensors);
     if (he == hipSuccess) he = dmalloc(&d.partials, (size_t)kLearnerMaxGroups * (P + 4));
     if (he == hipSuccess) he = dmalloc(&d.scal, (size_t)2);
-    if (he == hipSuccess) he = dmalloc(&d.status, (size_t)1);
-    if (he == hipSuccess) he = dmalloc(&d.errors, (size_t)1);
     if (he == hipSuccess) he = learner_scratch(d, cfg->max_batch ? cfg->max_batch : kLearnerDefaultBatch);
     if (he == hipSuccess) he = hipMemset(d.params, 0, P * 4);
-    if (he == hipSuccess) he = hipMemset(d.m, 0, P * 4);
-    if (he == hipSuccess) he = hipMemset(d.v, 0, P * 4);
-    if (he == hipSuccess) he = hipMemset(d.steps, 0, kLearnerTensors * 8);
-    if (he == hipSuccess) he = hipMemset(d.errors, 0, 4);
-    if (he == hipSuccess) he = hipMemset(d.status, 0, 4);
     if (he == hipSuccess) he = learner_prepare_kernels(d.L);
     if (he == hipSuccess) he = hipDeviceSynchronize();
     if (he != hipSuccess) {
@@ -1193,37 +1250,23 @@ int uavtrack_learner_set_optimizer_state(uavtrack_learner *learner, const float 
                                          const int64_t *step, int64_t n_floats, void *stream)
 {
     if (!learner || !exp_avg || !exp_avg_sq || !step) return fail("uavtrack_learner_set_optimizer_state: null argument");
-    LearnerDevice &d = learner->d;
-    if (n_floats != d.L.P)
-        return fail("uavtrack_learner_set_optimizer_state: %lld floats, the networks have %d", (long long)n_floats, d.L.P);
-    for (int t = 0; t < kLearnerTensors; ++t)
-        if (step[t] < 0) return fail("uavtrack_learner_set_optimizer_state: step[%d] = %lld < 0", t, (long long)step[t]);
-    for (int64_t p = 0; p < n_floats; ++p)
-        if (!(exp_avg_sq[p] >= 0.0f)) return fail("uavtrack_learner_set_optimizer_state: exp_avg_sq[%lld] is not >= 0", (long long)p);
+    if (n_floats != learner->d.L.P)
+        return fail("uavtrack_learner_set_optimizer_state: %lld floats, the networks have %d", (long long)n_floats,
+                    learner->d.L.P);
     ON_DEVICE(learner->cfg.device_id);
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    HIP_TRY(hipStreamSynchronize(st));
-    HIP_TRY(hipMemcpyAsync(d.m, exp_avg, (size_t)n_floats * 4, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(d.v, exp_avg_sq, (size_t)n_floats * 4, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(d.steps, step, kLearnerTensors * 8, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    return 0;
+    return adam_set(learner->d.opt, "uavtrack_learner_set_optimizer_state", exp_avg, exp_avg_sq, step,
+                    static_cast<hipStream_t>(stream));
 }
 
 int uavtrack_learner_get_optimizer_state(uavtrack_learner *learner, float *exp_avg, float *exp_avg_sq, int64_t *step,
                                          int64_t n_floats, void *stream)
 {
     if (!learner || !exp_avg || !exp_avg_sq || !step) return fail("uavtrack_learner_get_optimizer_state: null argument");
-    LearnerDevice &d = learner->d;
-    if (n_floats != d.L.P)
-        return fail("uavtrack_learner_get_optimizer_state: %lld floats, the networks have %d", (long long)n_floats, d.L.P);
+    if (n_floats != learner->d.L.P)
+        return fail("uavtrack_learner_get_optimizer_state: %lld floats, the networks have %d", (long long)n_floats,
+                    learner->d.L.P);
     ON_DEVICE(learner->cfg.device_id);
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    HIP_TRY(hipMemcpyAsync(exp_avg, d.m, (size_t)n_floats * 4, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(exp_avg_sq, d.v, (size_t)n_floats * 4, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(step, d.steps, kLearnerTensors * 8, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    return 0;
+    return adam_get(learner->d.opt, exp_avg, exp_avg_sq, step, static_cast<hipStream_t>(stream));
 }
 
 int uavtrack_learner_update(uavtrack_learner *learner, int64_t n, const float *states, const int32_t *actions,
@@ -1255,11 +1298,8 @@ int uavtrack_learner_check(uavtrack_learner *learner, int64_t *refused, void *st
 {
     if (!learner) return fail("uavtrack_learner_check: null handle");
     ON_DEVICE(learner->cfg.device_id);
-    hipStream_t st = static_cast<hipStream_t>(stream);
     int count = 0;
-    HIP_TRY(hipMemcpyAsync(&count, learner->d.errors, 4, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemsetAsync(learner->d.errors, 0, 4, st));
-    HIP_TRY(hipStreamSynchronize(st));
+    if (take_refusals(learner->d.opt, &count, static_cast<hipStream_t>(stream))) return 1;
     if (refused) *refused = count;
     if (count)
         return fail("uavtrack_learner_check: %d update(s) refused: an action outside [0, %d) or an index outside "
@@ -1292,8 +1332,8 @@ void free_pmi_trainer(uavtrack_pmi_trainer *t)
 {
     PmiTrainDevice &d = t->d;
     free_pmi_scratch(d);
-    for (void *p : {(void *)d.state, (void *)d.nbt, (void *)d.grad, (void *)d.m, (void *)d.v, (void *)d.steps,
-                    (void *)d.inv0, (void *)d.inv1, (void *)d.acc, (void *)d.status, (void *)d.errors})
+    adam_free(d.opt);
+    for (void *p : {(void *)d.state, (void *)d.nbt, (void *)d.grad, (void *)d.inv0, (void *)d.inv1, (void *)d.acc})
         if (p) (void)hipFree(p);
 }
 
@@ -1333,19 +1373,9 @@ int uavtrack_pmi_trainer_create(const uavtrack_pmi_trainer_config *cfg, uavtrack
                     (long long)kPmiTrainMaxBatch);
     if (!std::isfinite(cfg->lr) || cfg->lr < 0) return fail("uavtrack_pmi_trainer_create: lr must be finite and >= 0");
 
-    int ndev = 0;
-    hipError_t e = hipGetDeviceCount(&ndev);
-    if (e != hipSuccess || ndev < 1)
-        return fail("uavtrack_pmi_trainer_create: no HIP device visible (%s); libuavtrack has no CPU fallback",
-                    e != hipSuccess ? hipGetErrorString(e) : "device count 0");
-    if (cfg->device_id < 0 || cfg->device_id >= ndev)
-        return fail("uavtrack_pmi_trainer_create: device_id %d out of range [0, %d)", cfg->device_id, ndev);
-    ON_DEVICE(cfg->device_id);
     hipDeviceProp_t prop;
-    HIP_TRY(hipGetDeviceProperties(&prop, cfg->device_id));
-    if (strncmp(prop.gcnArchName, "gfx950", 6) != 0)
-        return fail("uavtrack_pmi_trainer_create: device %d is %s; this library is built for gfx950 only", cfg->device_id,
-                    prop.gcnArchName);
+    if (accept_device("uavtrack_pmi_trainer_create", cfg->device_id, &prop)) return 1;
+    ON_DEVICE(cfg->device_id);
 
     uavtrack_pmi_trainer *t = new (std::nothrow) uavtrack_pmi_trainer();
     if (!t) return fail("uavtrack_pmi_trainer_create: out of host memory");
@@ -1354,27 +1384,17 @@ int uavtrack_pmi_trainer_create(const uavtrack_pmi_trainer_config *cfg, uavtrack
     d.L = PmiTrainLayout::make(cfg->hidden);
     d.lr = (float)cfg->lr;
     const size_t S = (size_t)d.L.S, P = (size_t)d.L.P, H = (size_t)cfg->hidden;
-    hipError_t he = hipSuccess;
+    hipError_t he = adam_alloc(d.opt, kPmiTrainTensors, d.L.P);
     if (he == hipSuccess) he = dmalloc(&d.state, S);
     if (he == hipSuccess) he = dmalloc(&d.nbt, (size_t)kPmiBlocks);
     if (he == hipSuccess) he = dmalloc(&d.grad, P);
-    if (he == hipSuccess) he = dmalloc(&d.m, P);
-    if (he == hipSuccess) he = dmalloc(&d.v, P);
-    if (he == hipSuccess) he = dmalloc(&d.steps, (size_t)kPmiTrainTensors);
     if (he == hipSuccess) he = dmalloc(&d.inv0, 2 * 3 * H);
     if (he == hipSuccess) he = dmalloc(&d.inv1, 2 * H);
     if (he == hipSuccess) he = dmalloc(&d.acc, (size_t)1);
-    if (he == hipSuccess) he = dmalloc(&d.status, (size_t)1);
-    if (he == hipSuccess) he = dmalloc(&d.errors, (size_t)1);
     if (he == hipSuccess) he = pmi_scratch(d, cfg->max_batch ? cfg->max_batch : kPmiTrainDefaultBatch);
     if (he == hipSuccess) he = hipMemset(d.state, 0, S * 4);
     if (he == hipSuccess) he = hipMemset(d.nbt, 0, kPmiBlocks * 8);
     if (he == hipSuccess) he = hipMemset(d.grad, 0, P * 4);
-    if (he == hipSuccess) he = hipMemset(d.m, 0, P * 4);
-    if (he == hipSuccess) he = hipMemset(d.v, 0, P * 4);
-    if (he == hipSuccess) he = hipMemset(d.steps, 0, kPmiTrainTensors * 8);
-    if (he == hipSuccess) he = hipMemset(d.status, 0, 4);
-    if (he == hipSuccess) he = hipMemset(d.errors, 0, 4);
     if (he == hipSuccess) he = hipDeviceSynchronize();
     if (he != hipSuccess) {
         free_pmi_trainer(t);
@@ -1455,40 +1475,23 @@ int uavtrack_pmi_trainer_set_optimizer_state(uavtrack_pmi_trainer *trainer, cons
                                              const int64_t *step, int64_t n_train, void *stream)
 {
     if (!trainer || !exp_avg || !exp_avg_sq || !step) return fail("uavtrack_pmi_trainer_set_optimizer_state: null argument");
-    PmiTrainDevice &d = trainer->d;
-    if (n_train != d.L.P)
+    if (n_train != trainer->d.L.P)
         return fail("uavtrack_pmi_trainer_set_optimizer_state: %lld floats, the network has %d trainable", (long long)n_train,
-                    d.L.P);
-    for (int t = 0; t < kPmiTrainTensors; ++t)
-        if (step[t] < 0) return fail("uavtrack_pmi_trainer_set_optimizer_state: step[%d] = %lld < 0", t, (long long)step[t]);
-    for (int64_t p = 0; p < n_train; ++p)
-        if (!(exp_avg_sq[p] >= 0.0f))
-            return fail("uavtrack_pmi_trainer_set_optimizer_state: exp_avg_sq[%lld] is not >= 0", (long long)p);
+                    trainer->d.L.P);
     ON_DEVICE(trainer->cfg.device_id);
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    HIP_TRY(hipStreamSynchronize(st));
-    HIP_TRY(hipMemcpyAsync(d.m, exp_avg, (size_t)n_train * 4, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(d.v, exp_avg_sq, (size_t)n_train * 4, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(d.steps, step, kPmiTrainTensors * 8, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    return 0;
+    return adam_set(trainer->d.opt, "uavtrack_pmi_trainer_set_optimizer_state", exp_avg, exp_avg_sq, step,
+                    static_cast<hipStream_t>(stream));
 }
 
 int uavtrack_pmi_trainer_get_optimizer_state(uavtrack_pmi_trainer *trainer, float *exp_avg, float *exp_avg_sq,
                                              int64_t *step, int64_t n_train, void *stream)
 {
     if (!trainer || !exp_avg || !exp_avg_sq || !step) return fail("uavtrack_pmi_trainer_get_optimizer_state: null argument");
-    PmiTrainDevice &d = trainer->d;
-    if (n_train != d.L.P)
+    if (n_train != trainer->d.L.P)
         return fail("uavtrack_pmi_trainer_get_optimizer_state: %lld floats, the network has %d trainable", (long long)n_train,
-                    d.L.P);
+                    trainer->d.L.P);
     ON_DEVICE(trainer->cfg.device_id);
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    HIP_TRY(hipMemcpyAsync(exp_avg, d.m, (size_t)n_train * 4, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(exp_avg_sq, d.v, (size_t)n_train * 4, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(step, d.steps, kPmiTrainTensors * 8, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    return 0;
+    return adam_get(trainer->d.opt, exp_avg, exp_avg_sq, step, static_cast<hipStream_t>(stream));
 }
 
 int uavtrack_pmi_trainer_train(uavtrack_pmi_trainer *trainer, const float *rows, int64_t n_rows, int64_t n_uav,
@@ -1524,11 +1527,8 @@ int uavtrack_pmi_trainer_check(uavtrack_pmi_trainer *trainer, int64_t *refused, 
 {
     if (!trainer) return fail("uavtrack_pmi_trainer_check: null handle");
     ON_DEVICE(trainer->cfg.device_id);
-    hipStream_t st = static_cast<hipStream_t>(stream);
     int count = 0;
-    HIP_TRY(hipMemcpyAsync(&count, trainer->d.errors, 4, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemsetAsync(trainer->d.errors, 0, 4, st));
-    HIP_TRY(hipStreamSynchronize(st));
+    if (take_refusals(trainer->d.opt, &count, static_cast<hipStream_t>(stream))) return 1;
     if (refused) *refused = count;
     if (count)
         return fail("uavtrack_pmi_trainer_check: %d train call(s) refused: a timestep index outside [0, T) or a uav index "

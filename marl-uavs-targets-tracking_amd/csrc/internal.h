@@ -229,6 +229,36 @@ hipError_t launch_actor(const uavtrack_env *env, const float *obs, uint64_t seed
 hipError_t launch_reset(const uavtrack_env *env, uint64_t seed, uint32_t episode, float *obs,
                         hipStream_t stream);
 
+// What both device trainers (uavtrack_learner_*, uavtrack_pmi_trainer_*) keep the same way: the torch.optim.Adam state
+// of their trainable tensors and the words through which a call is refused on the device.  api.hip allocates, loads,
+// reads and frees it (adam_alloc / adam_set / adam_get / adam_free / take_refusals).
+struct AdamState {
+    int tensors = 0, P = 0;         // trainable tensors, their floats
+    float *m = nullptr, *v = nullptr;   // [P] exp_avg, exp_avg_sq
+    int64_t *steps = nullptr;       // [tensors] Adam step per trainable tensor
+    int *status = nullptr;          // [1] this call's input errors
+    int *errors = nullptr;          // [1] calls refused since the last *_check
+};
+
+// torch.optim.Adam (defaults: betas (0.9, 0.999), eps 1e-8, no weight decay, no amsgrad), the single-tensor and
+// foreach forms' arithmetic: m.lerp_(g, 1 - b1); v = v * b2 + (1 - b2) g^2; p -= (lr / bc1) * m / (sqrt(v) / sqrt(bc2) + eps)
+// with bc = 1 - b^step in double precision on the host side of torch (here: on the device, from the device step count).
+// One element: w, m, v are updated in place from the gradient g at Adam step `step` (already advanced for this step).
+__device__ __forceinline__ void adam_element(float &w, float &m, float &v, float g, int64_t step, float lr)
+{
+    const double s = (double)step;
+    const double bc1 = 1.0 - pow(0.9, s), bc2 = 1.0 - pow(0.999, s);
+    const float step_size = (float)((double)lr / bc1);
+    const float bc2_sqrt = (float)sqrt(bc2);
+    float mi = m;
+    mi = mi + 0.1f * (g - mi);                              // lerp with weight 1 - 0.9 < 0.5
+    const float vi = v * 0.999f + 0.001f * g * g;
+    const float denom = sqrtf(vi) / bc2_sqrt + 1e-8f;
+    w = w - step_size * (mi / denom);
+    m = mi;
+    v = vi;
+}
+
 // learner_kernel.hip -- the device learner (uavtrack_learner_*).  Both networks' parameters live in one fp32 array in
 // torch order: actor fc1.weight [H][12], fc1.bias [H], fc2.weight [A][H], fc2.bias [A], then critic fc1.weight [H][12],
 // fc1.bias [H], fc2.weight [1][H], fc2.bias [1]; the Adam moments use the same order.
@@ -265,14 +295,12 @@ struct LearnerDevice {
     LearnerLayout L;
     float gamma, actor_lr, critic_lr;
     int per_sample;
-    float *params, *m, *v;          // [P]
-    int64_t *steps;                 // [kLearnerTensors] Adam step per parameter tensor
+    float *params;                  // [P]
+    AdamState opt;                  // kLearnerTensors tensors over [P]
     float *partials;                // [kLearnerMaxGroups][P + 4]
     float *scal;                    // [2] gradient scales of the current update
     float *td;                      // [max_n] td_delta when the caller passes none
     uint8_t *last;                  // [max_n] last-occurrence marks of the priority write
-    int *status;                    // [1] this update's input errors
-    int *errors;                    // [1] updates refused since the last uavtrack_learner_check
     int64_t max_n;
 };
 struct LearnerLaunch {
@@ -328,16 +356,14 @@ struct PmiTrainDevice {
     float lr;
     float *state;                   // [S] state_dict floats
     int64_t *nbt;                   // [4] num_batches_tracked per BatchNorm1d
-    float *grad, *m, *v;            // [P]
-    int64_t *steps;                 // [18] Adam step per trainable tensor
+    float *grad;                    // [P]
+    AdamState opt;                  // kPmiTrainTensors tensors over [P]
     // per-step scratch, feature-major ([side][feature][row]) for batches up to max_b rows
     float *xh0, *a0, *da0;          // [2][3H][max_b] branch BN: normalised input, post-ReLU output, dL/d(output)
     float *xh1, *a1, *dz1;          // [2][H][max_b]  bn1: normalised input, post-ReLU output; dL/d(fc1 output)
     float *inv0, *inv1;             // [2][3H], [2][H] 1 / sqrt(var + eps) of the current step
     float *go;                      // [2][max_b] dL/d(output_1_2), dL/d(output_1_3)
     float *acc;                     // [1] sum of |loss| over the call
-    int *status;                    // [1] this call's input errors
-    int *errors;                    // [1] calls refused since the last uavtrack_pmi_trainer_check
     int64_t max_b;
 };
 struct PmiTrainLaunch {

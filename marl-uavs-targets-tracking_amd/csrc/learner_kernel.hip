@@ -246,9 +246,7 @@ __global__ void learner_finalize_kernel(const float *partials, int groups, Learn
     for (int q = 0; q < kLearnerTensors; ++q) steps[q] += 1;
 }
 
-// torch.optim.Adam (defaults: betas (0.9, 0.999), eps 1e-8, no weight decay, no amsgrad), the single-tensor and
-// foreach forms' arithmetic: m.lerp_(g, 1 - b1); v = v * b2 + (1 - b2) g^2; p -= (lr / bc1) * m / (sqrt(v) / sqrt(bc2) + eps)
-// with bc = 1 - b^step in double precision on the host side of torch (here: on the device, from the device step count).
+// Both torch.optim.Adam steps (adam_element, internal.h) on the summed and scaled gradient partials.
 __global__ void learner_adam_kernel(float *params, float *m, float *v, const float *partials, int groups, LearnerLayout L,
                                     const int *status, const int64_t *steps, const float *scal, float actor_lr, float critic_lr)
 {
@@ -258,18 +256,7 @@ __global__ void learner_adam_kernel(float *params, float *m, float *v, const flo
     for (int w = 0; w < groups; ++w) g += partials[(size_t)w * (L.P + 4) + p];
     const bool actor = p < L.c_w1;
     g *= actor ? scal[0] : scal[1];
-    const int tensor = L.tensor_of(p);
-    const double step = (double)steps[tensor];
-    const double bc1 = 1.0 - pow(0.9, step), bc2 = 1.0 - pow(0.999, step);
-    const float step_size = (float)((actor ? (double)actor_lr : (double)critic_lr) / bc1);
-    const float bc2_sqrt = (float)sqrt(bc2);
-    float mi = m[p];
-    mi = mi + 0.1f * (g - mi);                              // lerp with weight 1 - 0.9 < 0.5
-    const float vi = v[p] * 0.999f + 0.001f * g * g;
-    const float denom = sqrtf(vi) / bc2_sqrt + 1e-8f;
-    params[p] = params[p] - step_size * (mi / denom);
-    m[p] = mi;
-    v[p] = vi;
+    adam_element(params[p], m[p], v[p], g, steps[L.tensor_of(p)], actor ? actor_lr : critic_lr);
 }
 
 // the priorities: claim every sampled slot, keep the largest batch row per slot, mark it, write |delta| from it
@@ -338,37 +325,37 @@ hipError_t launch_learner_update(const LearnerDevice &d, const LearnerLaunch &q,
     const LearnerLayout &L = d.L;
     const int R = learner_rows_per_tile(L.H);
     const int groups = learner_groups(L, q.n);
-    hipLaunchKernelGGL(learner_begin_kernel, dim3(1), dim3(64), 0, st, d.status);
+    hipLaunchKernelGGL(learner_begin_kernel, dim3(1), dim3(64), 0, st, d.opt.status);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
 
     GradArgs a;
     a.params = d.params; a.states = q.states; a.rewards = q.rewards; a.next_states = q.next_states;
     a.actions = q.actions; a.idx = q.idx; a.n = q.n; a.capacity = q.capacity;
-    a.partials = d.partials; a.td_delta = q.td_delta ? q.td_delta : d.td; a.status = d.status;
+    a.partials = d.partials; a.td_delta = q.td_delta ? q.td_delta : d.td; a.status = d.opt.status;
     a.L = L; a.rows = R; a.gamma = d.gamma; a.per_sample = d.per_sample;
     hipLaunchKernelGGL(learner_grad_kernel, dim3(groups), dim3(kLW), learner_lds_bytes(L, R), st, a);
     if ((e = hipGetLastError()) != hipSuccess) return e;
 
     hipLaunchKernelGGL(learner_finalize_kernel, dim3(1), dim3(64), 0, st, d.partials, groups, L, q.n, d.per_sample,
-                       d.status, d.errors, d.steps, d.scal, q.actor_loss, q.critic_loss);
+                       d.opt.status, d.opt.errors, d.opt.steps, d.scal, q.actor_loss, q.critic_loss);
     if ((e = hipGetLastError()) != hipSuccess) return e;
 
-    hipLaunchKernelGGL(learner_adam_kernel, dim3((L.P + 255) / 256), dim3(256), 0, st, d.params, d.m, d.v, d.partials,
-                       groups, L, d.status, d.steps, d.scal, d.actor_lr, d.critic_lr);
+    hipLaunchKernelGGL(learner_adam_kernel, dim3((L.P + 255) / 256), dim3(256), 0, st, d.params, d.opt.m, d.opt.v,
+                       d.partials, groups, L, d.opt.status, d.opt.steps, d.scal, d.actor_lr, d.critic_lr);
     if ((e = hipGetLastError()) != hipSuccess) return e;
 
     if (q.priorities) {
         const dim3 grid((unsigned)((q.n + 255) / 256)), blk(256);
         const float *td = q.td_delta ? q.td_delta : d.td;
-        hipLaunchKernelGGL(learner_prio_claim_kernel, grid, blk, 0, st, q.idx, q.n, q.capacity, q.priorities, d.status);
+        hipLaunchKernelGGL(learner_prio_claim_kernel, grid, blk, 0, st, q.idx, q.n, q.capacity, q.priorities, d.opt.status);
         if ((e = hipGetLastError()) != hipSuccess) return e;
-        hipLaunchKernelGGL(learner_prio_max_kernel, grid, blk, 0, st, q.idx, q.n, q.capacity, q.priorities, d.status);
+        hipLaunchKernelGGL(learner_prio_max_kernel, grid, blk, 0, st, q.idx, q.n, q.capacity, q.priorities, d.opt.status);
         if ((e = hipGetLastError()) != hipSuccess) return e;
         hipLaunchKernelGGL(learner_prio_mark_kernel, grid, blk, 0, st, q.idx, q.n, q.capacity, q.priorities, d.last,
-                           d.status);
+                           d.opt.status);
         if ((e = hipGetLastError()) != hipSuccess) return e;
-        hipLaunchKernelGGL(learner_prio_write_kernel, grid, blk, 0, st, q.idx, q.n, td, q.priorities, d.last, d.status);
+        hipLaunchKernelGGL(learner_prio_write_kernel, grid, blk, 0, st, q.idx, q.n, td, q.priorities, d.last, d.opt.status);
         if ((e = hipGetLastError()) != hipSuccess) return e;
     }
     return hipSuccess;

@@ -433,8 +433,8 @@ __global__ void __launch_bounds__(kWG) pmi_branch_bwd_kernel(StepArgs a)
     }
 }
 
-// torch.optim.Adam (defaults: betas (0.9, 0.999), eps 1e-8, no weight decay, no amsgrad), single-tensor arithmetic
-// as in learner_kernel.hip; the step counts were advanced by this step's pmi_head_kernel
+// The torch.optim.Adam step (adam_element, internal.h) of every trainable element, in place in the state; the step
+// counts were advanced by this step's pmi_head_kernel
 __global__ void pmi_adam_kernel(PmiTrainLayout L, float *state, float *m, float *v, const float *grad,
                                 const int64_t *steps, const int *status, float lr)
 {
@@ -442,19 +442,7 @@ __global__ void pmi_adam_kernel(PmiTrainLayout L, float *state, float *m, float 
     if (p >= L.P || *status) return;
     int t = 0;
     while (t + 1 < kPmiTrainTensors && p >= L.poff[t + 1]) ++t;
-    const float g = grad[p];
-    const double step = (double)steps[t];
-    const double bc1 = 1.0 - pow(0.9, step), bc2 = 1.0 - pow(0.999, step);
-    const float step_size = (float)((double)lr / bc1);
-    const float bc2_sqrt = (float)sqrt(bc2);
-    float mi = m[p];
-    mi = mi + 0.1f * (g - mi);
-    const float vi = v[p] * 0.999f + 0.001f * g * g;
-    const float denom = sqrtf(vi) / bc2_sqrt + 1e-8f;
-    float *w = state + L.soff[PmiTrainLayout::state_of(t)] + (p - L.poff[t]);
-    *w = *w - step_size * (mi / denom);
-    m[p] = mi;
-    v[p] = vi;
+    adam_element(state[L.soff[PmiTrainLayout::state_of(t)] + (p - L.poff[t])], m[p], v[p], grad[p], steps[t], lr);
 }
 
 __global__ void pmi_finalize_kernel(const int *status, int *errors, const float *acc, int64_t nb, float *avg_loss)
@@ -472,16 +460,16 @@ hipError_t launch_pmi_train(const PmiTrainDevice &d, const PmiTrainLaunch &q, hi
     const int H = L.H, B = (int)q.batch;
     const int64_t nb = q.b2 / q.batch;
     hipLaunchKernelGGL(pmi_begin_kernel, dim3(1), dim3(kWG), 0, st, q.t_idx, q.u_idx, q.b2, q.n_rows / q.n_uav, q.n_uav,
-                       d.status, d.acc);
+                       d.opt.status, d.acc);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
 
     StepArgs a;
     a.L = L; a.rows = q.rows; a.t_idx = q.t_idx; a.u_idx = q.u_idx; a.n_uav = q.n_uav; a.B = B;
-    a.state = d.state; a.grad = d.grad; a.nbt = d.nbt; a.steps = d.steps;
+    a.state = d.state; a.grad = d.grad; a.nbt = d.nbt; a.steps = d.opt.steps;
     a.xh0 = d.xh0; a.a0 = d.a0; a.da0 = d.da0; a.xh1 = d.xh1; a.a1 = d.a1; a.dz1 = d.dz1;
     a.inv0 = d.inv0; a.inv1 = d.inv1; a.go = d.go; a.acc = d.acc;
-    a.losses = q.losses; a.outputs = q.outputs; a.status = d.status;
+    a.losses = q.losses; a.outputs = q.outputs; a.status = d.opt.status;
     const dim3 blk(kWG);
     const dim3 g_branch((3 * H + kWavesPerWG - 1) / kWavesPerWG), g_fc1((H + kWavesPerWG - 1) / kWavesPerWG);
     const dim3 g_adam((L.P + kWG - 1) / kWG);
@@ -508,19 +496,20 @@ hipError_t launch_pmi_train(const PmiTrainDevice &d, const PmiTrainLaunch &q, hi
         a.step = (int)b;
         hipLaunchKernelGGL(pmi_branch_fwd_kernel, g_branch, blk, 0, st, a);
         hipLaunchKernelGGL(pmi_gemm_kernel, tiles(H, N2), blk, 0, st, f_a, f_b, f_c, H, N2, K, (int)kAddBias,
-                           d.state + L.soff[19], none, d.status);
+                           d.state + L.soff[19], none, d.opt.status);
         hipLaunchKernelGGL(pmi_bn1_fwd_kernel, g_fc1, blk, 0, st, a);
         hipLaunchKernelGGL(pmi_head_kernel, dim3(1), dim3(kHeadThreads), 0, st, a);
         hipLaunchKernelGGL(pmi_bn1_bwd_kernel, g_fc1, blk, 0, st, a);
         hipLaunchKernelGGL(pmi_gemm_kernel, tiles(H, K), blk, 0, st, w_a, w_b, w_c, H, K, N2, (int)kStore, nullptr,
-                           none, d.status);
+                           none, d.opt.status);
         hipLaunchKernelGGL(pmi_gemm_kernel, tiles(K, N2), blk, 0, st, x_a, x_b, x_c, K, N2, H, (int)kReluMask, nullptr,
-                           x_m, d.status);
+                           x_m, d.opt.status);
         hipLaunchKernelGGL(pmi_branch_bwd_kernel, g_branch, blk, 0, st, a);
-        hipLaunchKernelGGL(pmi_adam_kernel, g_adam, blk, 0, st, L, d.state, d.m, d.v, d.grad, d.steps, d.status, d.lr);
+        hipLaunchKernelGGL(pmi_adam_kernel, g_adam, blk, 0, st, L, d.state, d.opt.m, d.opt.v, d.grad, d.opt.steps,
+                           d.opt.status, d.lr);
         if ((e = hipGetLastError()) != hipSuccess) return e;
     }
-    hipLaunchKernelGGL(pmi_finalize_kernel, dim3(1), dim3(64), 0, st, d.status, d.errors, d.acc, nb, q.avg_loss);
+    hipLaunchKernelGGL(pmi_finalize_kernel, dim3(1), dim3(64), 0, st, d.opt.status, d.opt.errors, d.acc, nb, q.avg_loss);
     return hipGetLastError();
 }
 

@@ -149,3 +149,8 @@ def check(rc: int, what: str = "") -> None:
     if rc != 0:
         msg = load().uavtrack_last_error().decode("utf-8", "replace")
         raise RuntimeError(f"{what or 'uavtrack'} failed: {msg}")
+
+
+def ptr(t):
+    """A tensor's device address as a void * argument (None for NULL)."""
+    return None if t is None else C.c_void_p(t.data_ptr())

@@ -12,13 +12,10 @@ import torch
 from . import _lib
 from .config import EnvConfig, RewardMode
 from .pmi import fold_pmi_state_dict
+from ._lib import ptr as _ptr
 from .pmi_trainer import DevicePMINetwork
 
 _STATE_KEYS = ("ux", "uy", "uz", "uh", "ua", "tx", "ty", "tz", "th")
-
-
-def _ptr(t: Optional[torch.Tensor]):
-    return None if t is None else C.c_void_p(t.data_ptr())
 
 
 class BatchedUavEnv:

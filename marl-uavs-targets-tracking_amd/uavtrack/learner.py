@@ -18,6 +18,8 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._lib import ptr as _ptr
+from .adam import flat, from_state_dict, split, to_state_dict
 from .replay import DeviceReplayBuffer, PrioritizedDeviceReplayBuffer
 from .rollout import ActorMLP
 
@@ -33,10 +35,6 @@ class ValueMLP(torch.nn.Module):
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         return self.fc2(torch.relu(self.fc1(x))).squeeze(1)
-
-
-def _ptr(t: Optional[torch.Tensor]):
-    return None if t is None else C.c_void_p(t.data_ptr())
 
 
 class DeviceActorCritic:
@@ -69,8 +67,7 @@ class DeviceActorCritic:
         n = C.c_int64()
         _lib.check(self._lib.uavtrack_learner_num_params(self._h, C.byref(n)), "uavtrack_learner_num_params")
         self.num_params = n.value
-        self._sizes = [p.numel() for p in self._params()]
-        self._set_params(self._flat([p.detach() for p in self._params()]))
+        self._set_params(flat(self._params()))
 
     # ---- handle plumbing
     def close(self) -> None:
@@ -89,18 +86,6 @@ class DeviceActorCritic:
 
     def _params(self):
         return list(self._actor.parameters()) + list(self._critic.parameters())
-
-    @staticmethod
-    def _flat(tensors) -> np.ndarray:
-        return np.ascontiguousarray(np.concatenate([t.detach().cpu().float().numpy().ravel() for t in tensors]),
-                                    dtype=np.float32)
-
-    def _split(self, flat: np.ndarray):
-        out, o = [], 0
-        for p, k in zip(self._params(), self._sizes):
-            out.append(torch.from_numpy(flat[o:o + k].copy()).view_as(p))
-            o += k
-        return out
 
     def _set_params(self, flat: np.ndarray) -> None:
         _lib.check(self._lib.uavtrack_learner_set_params(self._h, flat.ctypes.data_as(C.c_void_p), flat.size,
@@ -167,12 +152,8 @@ class DeviceActorCritic:
 
     # ---- weights and optimizer state
     def _module_state(self, module: torch.nn.Module, offset: int) -> "OrderedDict[str, torch.Tensor]":
-        flat = self._get_params()
-        sd, o = OrderedDict(), offset
-        for name, p in module.named_parameters():
-            sd[name] = torch.from_numpy(flat[o:o + p.numel()].copy()).view_as(p)
-            o += p.numel()
-        return sd
+        names, params = zip(*module.named_parameters())
+        return OrderedDict(zip(names, split(self._get_params()[offset:], params)))
 
     def actor_state_dict(self) -> "OrderedDict[str, torch.Tensor]":
         """FnnPolicyNet's state_dict (fc1.weight, fc1.bias, fc2.weight, fc2.bias; CPU fp32): loads into ActorMLP,
@@ -184,6 +165,7 @@ class DeviceActorCritic:
         return self._module_state(self._critic, sum(p.numel() for p in self._actor.parameters()))
 
     def _optim_state(self):
+        """(exp_avg [P], exp_avg_sq [P], step [8]) as numpy arrays: the actor's parameters, then the critic's."""
         P = self.num_params
         m, v = np.empty(P, np.float32), np.empty(P, np.float32)
         steps = np.empty(_lib.LEARNER_TENSORS, np.int64)
@@ -192,50 +174,29 @@ class DeviceActorCritic:
             P, self._stream()), "uavtrack_learner_get_optimizer_state")
         return m, v, steps
 
+    def _optimizers(self):
+        """(parameters, lr, float span, tensor span) of the actor's and the critic's Adam in the flat state."""
+        a = list(self._actor.parameters())
+        na, ta = sum(p.numel() for p in a), len(a)
+        return ((a, self.actor_lr, slice(0, na), slice(0, ta)),
+                (list(self._critic.parameters()), self.critic_lr, slice(na, None), slice(ta, None)))
+
     def _adam_state_dicts(self):
         """(actor, critic) torch.optim.Adam state dicts, built by torch itself so Adam.load_state_dict accepts them."""
         m, v, steps = self._optim_state()
-        ms, vs = self._split(m), self._split(v)
-        out, t = [], 0
-        for module, lr in ((self._actor, self.actor_lr), (self._critic, self.critic_lr)):
-            params = list(module.parameters())
-            opt = torch.optim.Adam(params, lr=lr)
-            for p in params:
-                if steps[t] > 0:
-                    opt.state[p] = {"step": torch.tensor(float(steps[t])), "exp_avg": ms[t].clone(),
-                                    "exp_avg_sq": vs[t].clone()}
-                t += 1
-            out.append(opt.state_dict())
-        return out
+        return [to_state_dict(params, lr, m[f], v[f], steps[t]) for params, lr, f, t in self._optimizers()]
 
     def _load_adam(self, actor_sd: Optional[dict], critic_sd: Optional[dict]) -> None:
         m, v, steps = self._optim_state()
-        ms, vs = self._split(m), self._split(v)
-        t0 = 0
-        for module, lr, sd in ((self._actor, self.actor_lr, actor_sd), (self._critic, self.critic_lr, critic_sd)):
-            params = list(module.parameters())
+        for (params, lr, f, t), sd in zip(self._optimizers(), (actor_sd, critic_sd)):
             if sd is not None:
-                opt = torch.optim.Adam(params, lr=lr)
-                opt.load_state_dict(sd)               # torch validates the dict
-                for i, p in enumerate(params):
-                    st = opt.state.get(p, {})
-                    if st:
-                        steps[t0 + i] = int(float(st["step"]))
-                        ms[t0 + i] = st["exp_avg"].detach().float().cpu().reshape(p.shape)
-                        vs[t0 + i] = st["exp_avg_sq"].detach().float().cpu().reshape(p.shape)
-                    else:
-                        steps[t0 + i] = 0
-                        ms[t0 + i] = torch.zeros_like(p)
-                        vs[t0 + i] = torch.zeros_like(p)
-            t0 += len(params)
-        mf, vf = self._flat(ms), self._flat(vs)
-        steps = np.ascontiguousarray(steps, dtype=np.int64)
+                m[f], v[f], steps[t] = from_state_dict(params, lr, sd)
         _lib.check(self._lib.uavtrack_learner_set_optimizer_state(
-            self._h, mf.ctypes.data_as(C.c_void_p), vf.ctypes.data_as(C.c_void_p), steps.ctypes.data_as(C.c_void_p),
+            self._h, m.ctypes.data_as(C.c_void_p), v.ctypes.data_as(C.c_void_p), steps.ctypes.data_as(C.c_void_p),
             self.num_params, self._stream()), "uavtrack_learner_set_optimizer_state")
 
     def _load_module(self, actor_sd: Optional[dict], critic_sd: Optional[dict]) -> None:
-        cur = self._split(self._get_params())
+        cur = split(self._get_params(), self._params())
         t0 = 0
         for module, sd in ((self._actor, actor_sd), (self._critic, critic_sd)):
             names = [k for k, _ in module.named_parameters()]
@@ -245,7 +206,7 @@ class DeviceActorCritic:
                 for i, k in enumerate(names):
                     cur[t0 + i] = probe.state_dict()[k]
             t0 += len(names)
-        self._set_params(self._flat(cur))
+        self._set_params(flat(cur))
 
     def state_dict(self) -> dict:
         a_opt, c_opt = self._adam_state_dicts()

@@ -18,13 +18,11 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._lib import ptr as _ptr
+from .adam import flat, from_state_dict, to_state_dict
 from .pmi import fold_pmi_state_dict, make_pmi_net
 
 _BN = ("bn_comm", "bn_obs", "bn_boundary_state", "bn1")
-
-
-def _ptr(t: Optional[torch.Tensor]):
-    return None if t is None else C.c_void_p(t.data_ptr())
 
 
 def _vp(a: np.ndarray):
@@ -155,8 +153,7 @@ class DevicePMINetwork:
         probe = make_pmi_net(self.hidden_dim)
         probe.load_state_dict(sd)
         items = probe.state_dict()
-        st = np.ascontiguousarray(np.concatenate([v.detach().float().numpy().ravel() for k, v in items.items()
-                                                  if not k.endswith("num_batches_tracked")]), np.float32)
+        st = flat(v for k, v in items.items() if not k.endswith("num_batches_tracked"))
         nbt = np.array([int(items[b + ".num_batches_tracked"]) for b in _BN], np.int64)
         _lib.check(self._lib.uavtrack_pmi_trainer_set_params(self._h, _vp(st), _vp(nbt), st.size, self._stream()),
                    "uavtrack_pmi_trainer_set_params")
@@ -171,42 +168,14 @@ class DevicePMINetwork:
                    "uavtrack_pmi_trainer_get_optimizer_state")
         return m, v, steps
 
-    def _split(self, flat: np.ndarray):
-        out, o = [], 0
-        for p in self._net.parameters():
-            out.append(torch.from_numpy(flat[o:o + p.numel()].copy()).view_as(p))
-            o += p.numel()
-        return out
-
     def optimizer_state_dict(self) -> dict:
         """torch.optim.Adam(PMINetwork.parameters(), lr).state_dict() of this trainer, built by torch itself."""
-        m, v, steps = self.optimizer_state()
-        ms, vs = self._split(m), self._split(v)
-        params = list(self._net.parameters())
-        opt = torch.optim.Adam(params, lr=self.lr)
-        for i, p in enumerate(params):
-            if steps[i] > 0:
-                opt.state[p] = {"step": torch.tensor(float(steps[i])), "exp_avg": ms[i].clone(), "exp_avg_sq": vs[i].clone()}
-        return opt.state_dict()
+        return to_state_dict(self._net.parameters(), self.lr, *self.optimizer_state())
 
     def load_optimizer_state_dict(self, sd: dict) -> None:
         """optimizer.load_state_dict: a torch.optim.Adam state_dict over PMINetwork.parameters().  (The learning rate
         stays the one this trainer was built with.)"""
-        params = list(make_pmi_net(self.hidden_dim).parameters())
-        opt = torch.optim.Adam(params, lr=self.lr)
-        opt.load_state_dict(sd)                           # torch validates the dict
-        ms, vs, steps = [], [], np.zeros(_lib.PMI_TRAIN_TENSORS, np.int64)
-        for i, p in enumerate(params):
-            st = opt.state.get(p, {})
-            if st:
-                steps[i] = int(float(st["step"]))
-                ms.append(st["exp_avg"].detach().float().cpu().reshape(p.shape))
-                vs.append(st["exp_avg_sq"].detach().float().cpu().reshape(p.shape))
-            else:
-                ms.append(torch.zeros_like(p))
-                vs.append(torch.zeros_like(p))
-        flat = lambda ts: np.ascontiguousarray(np.concatenate([t.detach().numpy().ravel() for t in ts]), np.float32)
-        mf, vf = flat(ms), flat(vs)
+        mf, vf, steps = from_state_dict(make_pmi_net(self.hidden_dim).parameters(), self.lr, sd)
         _lib.check(self._lib.uavtrack_pmi_trainer_set_optimizer_state(self._h, _vp(mf), _vp(vf), _vp(steps),
                                                                       self.num_params, self._stream()),
                    "uavtrack_pmi_trainer_set_optimizer_state")

@@ -313,6 +313,23 @@ def test_refused_inputs_leave_the_learner_unchanged():
     with pytest.raises(RuntimeError):
         L._set_params(np.zeros(5, np.float32))
     assert np.array_equal(L._get_params(), before[0])
+    # a refused optimizer-state load: the wrong size, a negative step, a negative or NaN exp_avg_sq; the arrays differ
+    # from the current state everywhere, so a partial copy would show
+    m0, v0, st0 = before[1]
+    P = L.num_params
+    for n, bad in ((P - 1, None), (P, ("st", 3, -1)), (P, ("v", 7, -1e-3)), (P, ("v", P - 1, np.nan))):
+        arr = {"m": m0 + 1.0, "v": v0 + 1.0, "st": st0 + 1}
+        if bad:
+            arr[bad[0]][bad[1]] = bad[2]
+        with pytest.raises(RuntimeError, match="uavtrack_learner_set_optimizer_state: "):
+            _lib.check(lib.uavtrack_learner_set_optimizer_state(L._h, *(C.c_void_p(arr[q].ctypes.data) for q in
+                                                                        ("m", "v", "st")), n, None))
+        assert np.array_equal(L._get_params(), before[0])
+        for a, b in zip(before[1], _opt(L)):
+            assert np.array_equal(a, b)
+    # a device that does not exist: create refuses
+    with pytest.raises(RuntimeError, match=r"uavtrack_learner_create: device_id \d+ out of range"):
+        _uav().DeviceActorCritic(12, 64, 12, device=f"cuda:{torch.cuda.device_count()}")
 
 
 def test_update_from_prioritized_buffer_writes_priorities():

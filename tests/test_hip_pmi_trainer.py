@@ -340,8 +340,26 @@ def test_refusals_change_nothing():
     for H in (0, 257):
         with pytest.raises((RuntimeError, ValueError)):
             _uav().DevicePMINetwork(H, 1000, DEV)
+    with pytest.raises(RuntimeError, match=r"uavtrack_pmi_trainer_create: device_id \d+ out of range"):
+        _uav().DevicePMINetwork(64, 1000, f"cuda:{torch.cuda.device_count()}")
     for x, y in zip(before, _full_state(tr)):
         assert np.array_equal(x, y)
+    # a refused optimizer-state load: the wrong size, a negative step, a negative or NaN exp_avg_sq; the arrays differ
+    # from the current state everywhere, so a partial copy would show
+    import ctypes as C
+    from uavtrack import _lib
+    lib = _lib.load()
+    _, _, m0, v0, st0 = before
+    P = tr.num_params
+    for n, bad in ((P - 1, None), (P, ("st", 5, -1)), (P, ("v", 9, -1e-3)), (P, ("v", P - 1, np.nan))):
+        arr = {"m": m0 + 1.0, "v": v0 + 1.0, "st": st0 + 1}
+        if bad:
+            arr[bad[0]][bad[1]] = bad[2]
+        with pytest.raises(RuntimeError, match="uavtrack_pmi_trainer_set_optimizer_state: "):
+            _lib.check(lib.uavtrack_pmi_trainer_set_optimizer_state(tr._h, *(C.c_void_p(arr[q].ctypes.data) for q in
+                                                                             ("m", "v", "st")), n, None))
+        for a, b in zip(before, _full_state(tr)):
+            assert np.array_equal(a, b)
     tr.reserve(512)
     tr.train_indices(rows, n_uav, t, u, 512)                    # fits after the reserve
     tr.check()

@@ -1,7 +1,9 @@
 """The fp64 mirror of the device learner (tests/learner_mirror.py) against the reference's own fp32 updates
-recorded in tests/golden/f5_actor_critic_update.npz (tools/gen_learner_golden.py).  No GPU."""
+recorded in tests/golden/f5_actor_critic_update.npz (tools/gen_learner_golden.py); the conversion between both device
+trainers' flat Adam state and torch.optim.Adam state_dicts (uavtrack/adam.py).  No GPU."""
 import numpy as np
 import pytest
+import torch
 
 from conftest import load_golden
 import learner_mirror as mirror
@@ -67,3 +69,81 @@ def test_priority_write_last_occurrence_wins():
     assert len(set(idx.tolist())) < len(idx)
     got = mirror.last_wins(z["prio_before"], idx, np.abs(z["h128_td"][0]))
     np.testing.assert_array_equal(got.astype(np.float32), z["prio_after"])
+
+
+# ---- the flat Adam state <-> torch.optim.Adam.state_dict() (uavtrack.adam), shared by both device trainers
+
+def _torch_adam(params, lr, steps, seed):
+    """A torch.optim.Adam over params after max(steps) steps, tensor i stepped steps[i] times (a tensor without a
+    gradient is skipped by torch and has no state)."""
+    g = torch.Generator().manual_seed(seed)
+    opt = torch.optim.Adam(params, lr=lr)
+    for k in range(max(steps)):
+        for p, n in zip(params, steps):
+            p.grad = torch.randn(p.shape, generator=g) if k < n else None
+        opt.step()
+    return opt.state_dict()
+
+
+def _assert_same_adam_dict(a, b):
+    assert a["param_groups"] == b["param_groups"]
+    assert sorted(a["state"]) == sorted(b["state"])
+    for i, st in a["state"].items():
+        assert sorted(st) == sorted(b["state"][i])
+        for k, t in st.items():
+            assert t.dtype == b["state"][i][k].dtype and torch.equal(t, b["state"][i][k]), (i, k)
+
+
+def _check_round_trip(params, lr, steps, seed):
+    """torch's own dict -> flat arrays -> dict: equal to torch's, absent tensors load as zeros, and Adam takes it."""
+    from uavtrack.adam import flat, from_state_dict, split, to_state_dict
+    sd = _torch_adam(params, lr, steps, seed)
+    m, v, st = from_state_dict(params, lr, sd)
+    P = sum(p.numel() for p in params)
+    assert m.dtype == v.dtype == np.float32 and m.shape == v.shape == (P,) and st.dtype == np.int64
+    np.testing.assert_array_equal(st, steps)
+    for i, (mi, vi) in enumerate(zip(split(m, params), split(v, params))):
+        if steps[i] == 0:
+            assert i not in sd["state"] and not mi.any() and not vi.any()
+        else:
+            assert torch.equal(mi, sd["state"][i]["exp_avg"]) and torch.equal(vi, sd["state"][i]["exp_avg_sq"])
+    back = to_state_dict(params, lr, m, v, st)
+    _assert_same_adam_dict(back, sd)
+    fresh = [torch.nn.Parameter(torch.zeros_like(p)) for p in params]
+    opt = torch.optim.Adam(fresh, lr=lr)
+    opt.load_state_dict(back)
+    assert len(opt.state) == sum(1 for n in steps if n > 0)
+    # a tensor at step 0 has no state, whatever its moments hold
+    m2 = m.copy(); m2[:] = 1.0
+    zero = [i for i, n in enumerate(steps) if n == 0]
+    assert set(to_state_dict(params, lr, m2, v, st)["state"]) == set(range(len(params))) - set(zero)
+    assert np.array_equal(flat(split(m, params)), m)
+    return m, v, st
+
+
+def test_adam_state_round_trip_pmi_parameters():
+    import uavtrack
+    torch.manual_seed(0)
+    params = list(uavtrack.make_pmi_net(16).parameters())
+    assert len(params) == 18
+    steps = [3, 0, 3, 1, 2, 0, 3, 3, 1, 1, 0, 2, 3, 3, 2, 2, 0, 3]
+    _check_round_trip(params, 1e-3, steps, seed=1)
+
+
+def test_adam_state_round_trip_learner_actor_critic_split():
+    """Two optimizers (actor, critic) over consecutive spans of one flat state, as DeviceActorCritic keeps them."""
+    import uavtrack
+    from uavtrack.adam import from_state_dict, to_state_dict
+    torch.manual_seed(0)
+    actor = list(uavtrack.ActorMLP(12, 24, 7).parameters())
+    critic = list(uavtrack.ValueMLP(12, 24).parameters())
+    (ma, va, sa), (mc, vc, sc) = (_check_round_trip(actor, 1e-4, [2, 2, 0, 1], seed=2),
+                                  _check_round_trip(critic, 5e-4, [0, 4, 4, 3], seed=3))
+    m, v, steps = np.concatenate([ma, mc]), np.concatenate([va, vc]), np.concatenate([sa, sc])
+    na = sum(p.numel() for p in actor)
+    assert m.size == na + sum(p.numel() for p in critic) and steps.size == 8
+    for params, lr, f, t, ref in ((actor, 1e-4, slice(0, na), slice(0, 4), (ma, va, sa)),
+                                  (critic, 5e-4, slice(na, None), slice(4, None), (mc, vc, sc))):
+        sd = to_state_dict(params, lr, m[f], v[f], steps[t])
+        for x, y in zip(from_state_dict(params, lr, sd), ref):
+            assert np.array_equal(x, y)
