@@ -10,6 +10,7 @@ update is the same rule on a sampled batch, and the new actor weights are re-upl
 
     python examples/train_maac.py --envs 1024 --iters 40
     python examples/train_maac.py --method maac-r --envs 1024 --iters 40     # reciprocal (PMI) reward, PMI net trained too
+    python examples/train_maac.py --replay prioritized --learner device --envs 4096 --n-uav 20   # prioritised ring, 32.8 M slots
 
 --method maac-r is the paper's method (configs/MAAC-R.yaml): the reward of every step is mixed in-kernel with the
 neighbours' rewards, weighted by the PMI network's scores (uav.py:262-291); that network is trained alongside on
@@ -82,6 +83,12 @@ def main(argv=None):
     ap.add_argument("--pmi-trainer", choices=["torch", "device"], default="torch",
                     help="--method maac-r only: torch: the PyTorch PMINetwork.train_pmi loop below; device: "
                          "uavtrack.DevicePMINetwork, the whole train_pmi call in one library call")
+    ap.add_argument("--replay", choices=["uniform", "prioritized"], default="uniform",
+                    help="uniform: DeviceReplayBuffer (random.sample, train.py:57); prioritized: uavtrack."
+                         "PrioritizedReplayRing (the reference's PrioritizedReplayBuffer, train.py:73-139), added to "
+                         "from the rollout and drawn from in HIP, |td_delta| written back as the new priorities")
+    ap.add_argument("--alpha", type=float, default=0.6, help="--replay prioritized: priority exponent (train.py:74)")
+    ap.add_argument("--beta", type=float, default=0.4, help="--replay prioritized: importance exponent (train.py:100)")
     args = ap.parse_args(argv)
 
     dev = "cuda:0"
@@ -110,7 +117,11 @@ def main(argv=None):
         actor.load_state_dict(learner.actor_state_dict())
     rollout = uavtrack.BatchedRollout(env, actor, device_actor=True, seed=args.seed)
     per_iter = args.envs * args.n_uav * args.steps
-    replay = uavtrack.DeviceReplayBuffer(capacity=2 * per_iter, device=dev)
+    if args.replay == "prioritized":
+        replay = uavtrack.PrioritizedReplayRing(2 * per_iter, dev, alpha=args.alpha, seed=args.seed,
+                                                max_batch=args.batch)
+    else:
+        replay = uavtrack.DeviceReplayBuffer(capacity=2 * per_iter, device=dev)
     history = []
     out = None
     for it in range(args.iters):
@@ -120,10 +131,20 @@ def main(argv=None):
         obs_in = rollout.obs.clone()
         res = rollout.run_fused(args.steps, out=out)                  # B episodes, one launch
         out = {k: v for k, v in res.items() if k != "ep_sums"}        # reuse the output buffers next time
-        replay.add(uavtrack.transitions_from_rollout(obs_in, res))
+        if args.replay == "prioritized":
+            replay.add_rollout(obs_in, res)                           # one library call, straight from the outputs
+        else:
+            replay.add(uavtrack.transitions_from_rollout(obs_in, res))
         torch.cuda.synchronize()
         t_roll = time.perf_counter() - t0
-        if learner is None:
+        if learner is None and args.replay == "prioritized":          # train.py:250-262
+            for _ in range(args.updates):
+                batch, idx, _w = replay.sample(args.batch, args.beta)
+                la, lc = update(actor, critic, opt_a, opt_c, batch, args.gamma)
+                with torch.no_grad():
+                    s, r, s2 = batch["states"], batch["rewards"], batch["next_states"]
+                    replay.update_priorities(idx, (r + args.gamma * critic(s2) - critic(s)).abs())
+        elif learner is None:
             for _ in range(args.updates):
                 la, lc = update(actor, critic, opt_a, opt_c, replay.sample(args.batch), args.gamma)
         else:
@@ -151,6 +172,8 @@ def main(argv=None):
         print(f"iter {it:3d}  episode return {ret:8.3f}  covered targets/step {cov:5.2f}  actor loss {la:+.4f}  "
               f"critic loss {lc:.4f}  pmi loss {lp:.4f}  rollout {t_roll * 1e3:6.1f} ms ({per_iter / t_roll / 1e9:.2f} G agent-steps/s)  "
               f"iteration {(time.perf_counter() - t0) * 1e3:6.1f} ms", flush=True)
+    if args.replay == "prioritized":
+        replay.check()                                                # no draw was refused on the device
     env.close()
     return history
 

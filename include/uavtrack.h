@@ -471,6 +471,84 @@ int uavtrack_pmi_trainer_train(uavtrack_pmi_trainer *trainer, const float *rows,
  * of range).  refused (nullable) receives their number; the count restarts at 0. */
 int uavtrack_pmi_trainer_check(uavtrack_pmi_trainer *trainer, int64_t *refused, void *stream);
 
+/* ---- the prioritised replay ring: PrioritizedReplayBuffer.add / sample on the device ----
+ * The reference's PrioritizedReplayBuffer (train.py:73-139) as a ring of caller-owned DEVICE tensors: states and
+ * next_states [capacity][12] fp32, actions [capacity] int32, rewards and priorities [capacity] fp32.  pos (next slot to
+ * write) and count (valid slots) are host state: they follow from the number of transitions added alone, so the caller
+ * advances them after each add (pos = (pos + n) % capacity, count = min(capacity, count + n)).  The handle owns only
+ * scratch (tile sums, the draw counter, the status words, per-draw probabilities), all allocated at create.
+ *
+ * The draw stream.  Draw j (0 <= j < n) of the c-th sample call on a handle (c = 0, 1, ...; the counter lives on the
+ * device and advances inside each call, so every replay of a captured graph draws afresh) takes
+ *     (r0, r1, r2, r3) = Philox4x32-10(counter = (j, c mod 2^32, c >> 32, 0x52504C59 "RPLY"),
+ *                                      key = (seed mod 2^32, seed >> 32))
+ *     u = ((r0 << 21) | (r1 >> 11)) * 2^-53          (53 bits: u in [0, 1 - 2^-53])
+ * Word 3 of the reset (0x55415631 "UAV1") and actor (0x4143544F "ACTO") streams differs, so no draw shares a counter with
+ * them.  The slot is searchsorted(cdf, u * total, side='right') with w_i = p_i^alpha in fp32 (the reference's float32
+ * `priorities ** alpha`), cdf its fp64 running sum over [0, count) and total = cdf[count - 1], as np.random.choice
+ * (train.py:106); where u * total rounds up to total, the draw takes the last slot with w > 0.  Sums are exact for
+ * integer weights below 2^53; otherwise a draw within rounding of a CDF boundary may fall on either side of it, but never
+ * on a slot >= count or one with w = 0. */
+typedef struct uavtrack_replay_config {
+    uint32_t struct_size;       /* = sizeof(uavtrack_replay_config), ABI check */
+    int32_t  device_id;         /* HIP device ordinal */
+    int64_t  max_capacity;      /* largest ring capacity this handle serves, >= 1 */
+    int64_t  max_batch;         /* largest sample (draws per call), in [1, 2^31) */
+    uint64_t seed;              /* Philox key of the draw stream */
+} uavtrack_replay_config;
+
+typedef struct uavtrack_replay uavtrack_replay;   /* opaque handle */
+
+/* One ring: DEVICE pointers to the caller's stores and priorities, the capacity and the host-side pos and count. */
+typedef struct uavtrack_replay_ring {
+    float   *states;            /* [capacity][12] */
+    int32_t *actions;           /* [capacity] */
+    float   *rewards;           /* [capacity] */
+    float   *next_states;       /* [capacity][12] */
+    float   *priorities;        /* [capacity] */
+    int64_t  capacity;          /* in [1, max_capacity] */
+    int64_t  pos;               /* in [0, capacity) */
+    int64_t  count;             /* in [0, capacity] */
+} uavtrack_replay_ring;
+
+/* Replaces PrioritizedReplayBuffer.__init__'s state (train.py:74-81) beyond the caller's tensors.  Allocates all the
+ * scratch the other calls use; synchronises the device. */
+int uavtrack_replay_create(const uavtrack_replay_config *cfg, uavtrack_replay **out);
+int uavtrack_replay_destroy(uavtrack_replay *replay);
+
+/* PrioritizedReplayBuffer.add (train.py:87-96) for n transitions: states / next_states [n][12], actions [n] int32,
+ * rewards [n] (DEVICE).  Only the last min(n, capacity) are written, from slot (pos + max(0, n - capacity)) % capacity
+ * on, wrapping; each gets the maximum of the whole priorities array as it stood before the call (1.0 when count == 0),
+ * taken on the device.  Stream-ordered, no synchronisation, no allocation.  Returns an error, enqueuing nothing, for a
+ * null pointer, n < 1, a ring outside the limits above, or a row array not 16-byte aligned. */
+int uavtrack_replay_add(uavtrack_replay *replay, const uavtrack_replay_ring *ring, int64_t n, const float *states,
+                        const int32_t *actions, const float *rewards, const float *next_states, void *stream);
+
+/* The same add straight from one rollout (uavtrack_run_actor's outputs, train.py:176-180): obs_in [agents][12] is what
+ * the policy saw first, obs [steps][agents][12], actions and reward [steps][agents] (agents = n_envs * n_uav).
+ * Transition f = t * agents + i (t < steps) is (state = t ? obs[t - 1][i] : obs_in[i], actions[t][i], reward[t][i],
+ * next_state = obs[t][i]), the [t][b][i] order of uavtrack.transitions_from_rollout; n = steps * agents.  Each obs row
+ * is read once.  Errors as uavtrack_replay_add. */
+int uavtrack_replay_add_rollout(uavtrack_replay *replay, const uavtrack_replay_ring *ring, int64_t steps, int64_t agents,
+                                const float *obs_in, const float *obs, const int32_t *actions, const float *reward,
+                                void *stream);
+
+/* PrioritizedReplayBuffer.sample's draw (train.py:98-112) without the gather: n slots with replacement from
+ * P(i) = p_i^alpha / sum_j p_j^alpha over [0, count) (the draw stream above) into indices [n] (DEVICE int64), and,
+ * if weights (DEVICE fp32 [n]) is not NULL, the importance weights (count * P(i))^-beta / max over the batch, computed
+ * in fp64.  Only ring->priorities and ring->count are used.  Stream-ordered, no synchronisation, no allocation,
+ * capturable; indices and weights are bitwise reproducible for the same seed and call number.  Returns an error,
+ * enqueuing nothing, for a null pointer, n < 1 or n > max_batch, count < 1 or count > capacity or capacity >
+ * max_capacity, alpha not finite and > 0, or beta not finite and >= 0.  A priority in [0, count) that is NaN,
+ * infinite or negative, or an all-zero [0, count), is found on the device: the call then writes slot 0 to every index
+ * and NaN weights, and the next uavtrack_replay_check reports it. */
+int uavtrack_replay_sample(uavtrack_replay *replay, const uavtrack_replay_ring *ring, int64_t n, double alpha,
+                           double beta, int64_t *indices, float *weights, void *stream);
+
+/* Synchronises `stream`; fails if any sample call since the previous check was refused on the device (bad or all-zero
+ * priorities).  refused (nullable) receives their number; the count restarts at 0. */
+int uavtrack_replay_check(uavtrack_replay *replay, int64_t *refused, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

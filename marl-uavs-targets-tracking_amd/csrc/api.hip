@@ -1537,3 +1537,185 @@ int uavtrack_pmi_trainer_check(uavtrack_pmi_trainer *trainer, int64_t *refused, 
 }
 
 }  // extern "C"
+
+// ---- the prioritised replay ring ----------------------------------------------------------------------------------
+
+struct uavtrack_replay {
+    uavtrack_replay_config cfg;
+    ReplayDevice d;
+};
+
+namespace {
+
+void free_replay(ReplayDevice &d)
+{
+    for (void *p : {(void *)d.prefix, (void *)d.tile_last, (void *)d.counter, (void *)d.pmin, (void *)d.pdraw,
+                    (void *)d.parts, (void *)d.status, (void *)d.errors})
+        if (p) (void)hipFree(p);
+    d = ReplayDevice();
+}
+
+constexpr int64_t kReplayMaxBatch = ((int64_t)1 << 31) - 1;   // draw numbers are Philox counter word 0
+constexpr int64_t kReplayMaxCapacity = (int64_t)kReplayTile * ((int64_t)1 << 30);   // tile numbers are int32
+
+bool aligned16(const void *p) { return ((uintptr_t)p & 15) == 0; }
+
+// The ring's pointers and host state against the handle's limits (`fn` names the ABI function in the message).
+int accept_ring(const uavtrack_replay *r, const char *fn, const uavtrack_replay_ring *ring, bool stores)
+{
+    if (!ring) return fail("%s: ring is null", fn);
+    if (!ring->priorities) return fail("%s: ring->priorities is null", fn);
+    if (stores && (!ring->states || !ring->actions || !ring->rewards || !ring->next_states))
+        return fail("%s: the ring's states, actions, rewards and next_states must not be null", fn);
+    if (stores && (!aligned16(ring->states) || !aligned16(ring->next_states)))
+        return fail("%s: the ring's states and next_states must be 16-byte aligned", fn);
+    if (ring->capacity < 1 || ring->capacity > r->cfg.max_capacity)
+        return fail("%s: capacity %lld outside [1, max_capacity = %lld]", fn, (long long)ring->capacity,
+                    (long long)r->cfg.max_capacity);
+    if (ring->count < 0 || ring->count > ring->capacity)
+        return fail("%s: count %lld outside [0, capacity = %lld]", fn, (long long)ring->count, (long long)ring->capacity);
+    if (ring->pos < 0 || ring->pos >= ring->capacity)
+        return fail("%s: pos %lld outside [0, capacity = %lld)", fn, (long long)ring->pos, (long long)ring->capacity);
+    return 0;
+}
+
+ReplayRingView ring_view(const uavtrack_replay_ring *ring)
+{
+    ReplayRingView v;
+    v.states = ring->states; v.actions = ring->actions; v.rewards = ring->rewards; v.next_states = ring->next_states;
+    v.priorities = ring->priorities; v.capacity = ring->capacity; v.pos = ring->pos; v.count = ring->count;
+    return v;
+}
+
+}  // namespace
+
+extern "C" {
+
+int uavtrack_replay_create(const uavtrack_replay_config *cfg, uavtrack_replay **out)
+{
+    if (!cfg || !out) return fail("uavtrack_replay_create: null argument");
+    *out = nullptr;
+    if (cfg->struct_size != sizeof(uavtrack_replay_config))
+        return fail("uavtrack_replay_create: struct_size %u != %zu (header / library mismatch)", cfg->struct_size,
+                    sizeof(uavtrack_replay_config));
+    if (cfg->max_capacity < 1 || cfg->max_capacity > kReplayMaxCapacity)
+        return fail("uavtrack_replay_create: max_capacity %lld out of range [1, %lld]", (long long)cfg->max_capacity,
+                    (long long)kReplayMaxCapacity);
+    if (cfg->max_batch < 1 || cfg->max_batch > kReplayMaxBatch)
+        return fail("uavtrack_replay_create: max_batch %lld out of range [1, %lld]", (long long)cfg->max_batch,
+                    (long long)kReplayMaxBatch);
+
+    hipDeviceProp_t prop;
+    if (accept_device("uavtrack_replay_create", cfg->device_id, &prop)) return 1;
+    ON_DEVICE(cfg->device_id);
+
+    uavtrack_replay *r = new (std::nothrow) uavtrack_replay();
+    if (!r) return fail("uavtrack_replay_create: out of host memory");
+    r->cfg = *cfg;
+    ReplayDevice &d = r->d;
+    d.max_capacity = cfg->max_capacity;
+    d.max_batch = cfg->max_batch;
+    d.k0 = (uint32_t)cfg->seed;
+    d.k1 = (uint32_t)(cfg->seed >> 32);
+    const size_t tiles = (size_t)((cfg->max_capacity + kReplayTile - 1) / kReplayTile);
+    hipError_t he = dmalloc(&d.prefix, tiles);
+    if (he == hipSuccess) he = dmalloc(&d.tile_last, tiles);
+    if (he == hipSuccess) he = dmalloc(&d.counter, (size_t)2);
+    if (he == hipSuccess) he = dmalloc(&d.pmin, (size_t)1);
+    if (he == hipSuccess) he = dmalloc(&d.pdraw, (size_t)cfg->max_batch);
+    if (he == hipSuccess) he = dmalloc(&d.parts, (size_t)kReplayMaxParts + 1);
+    if (he == hipSuccess) he = dmalloc(&d.status, (size_t)1);
+    if (he == hipSuccess) he = dmalloc(&d.errors, (size_t)1);
+    if (he == hipSuccess) he = hipMemset(d.counter, 0, 16);
+    if (he == hipSuccess) he = hipMemset(d.status, 0, 4);
+    if (he == hipSuccess) he = hipMemset(d.errors, 0, 4);
+    if (he == hipSuccess) he = hipDeviceSynchronize();
+    if (he != hipSuccess) {
+        free_replay(d);
+        delete r;
+        return fail("uavtrack_replay_create: %s", hipGetErrorString(he));
+    }
+    *out = r;
+    return 0;
+}
+
+int uavtrack_replay_destroy(uavtrack_replay *replay)
+{
+    if (!replay) return 0;
+    DeviceGuard guard(replay->cfg.device_id);
+    (void)hipDeviceSynchronize();
+    free_replay(replay->d);
+    delete replay;
+    return 0;
+}
+
+int uavtrack_replay_add(uavtrack_replay *replay, const uavtrack_replay_ring *ring, int64_t n, const float *states,
+                        const int32_t *actions, const float *rewards, const float *next_states, void *stream)
+{
+    if (!replay) return fail("uavtrack_replay_add: null handle");
+    if (accept_ring(replay, "uavtrack_replay_add", ring, true)) return 1;
+    if (!states || !actions || !rewards || !next_states)
+        return fail("uavtrack_replay_add: states, actions, rewards and next_states must not be null");
+    if (!aligned16(states) || !aligned16(next_states))
+        return fail("uavtrack_replay_add: states and next_states must be 16-byte aligned");
+    if (n < 1) return fail("uavtrack_replay_add: n = %lld < 1", (long long)n);
+    ON_DEVICE(replay->cfg.device_id);
+    HIP_TRY(launch_replay_add(replay->d, ring_view(ring), n, 0, nullptr, states, next_states, actions, rewards,
+                              static_cast<hipStream_t>(stream)));
+    return 0;
+}
+
+int uavtrack_replay_add_rollout(uavtrack_replay *replay, const uavtrack_replay_ring *ring, int64_t steps, int64_t agents,
+                                const float *obs_in, const float *obs, const int32_t *actions, const float *reward,
+                                void *stream)
+{
+    if (!replay) return fail("uavtrack_replay_add_rollout: null handle");
+    if (accept_ring(replay, "uavtrack_replay_add_rollout", ring, true)) return 1;
+    if (!obs_in || !obs || !actions || !reward)
+        return fail("uavtrack_replay_add_rollout: obs_in, obs, actions and reward must not be null");
+    if (!aligned16(obs_in) || !aligned16(obs))
+        return fail("uavtrack_replay_add_rollout: obs_in and obs must be 16-byte aligned");
+    if (steps < 1 || agents < 1) return fail("uavtrack_replay_add_rollout: steps and agents must be >= 1");
+    if (steps > INT64_MAX / agents / 12) return fail("uavtrack_replay_add_rollout: steps * agents overflows");
+    ON_DEVICE(replay->cfg.device_id);
+    HIP_TRY(launch_replay_add(replay->d, ring_view(ring), steps * agents, agents, obs_in, nullptr, obs, actions, reward,
+                              static_cast<hipStream_t>(stream)));
+    return 0;
+}
+
+int uavtrack_replay_sample(uavtrack_replay *replay, const uavtrack_replay_ring *ring, int64_t n, double alpha,
+                           double beta, int64_t *indices, float *weights, void *stream)
+{
+    if (!replay) return fail("uavtrack_replay_sample: null handle");
+    if (accept_ring(replay, "uavtrack_replay_sample", ring, false)) return 1;
+    if (!indices) return fail("uavtrack_replay_sample: indices must not be null");
+    if (n < 1 || n > replay->cfg.max_batch)
+        return fail("uavtrack_replay_sample: n = %lld outside [1, max_batch = %lld]", (long long)n,
+                    (long long)replay->cfg.max_batch);
+    if (ring->count < 1) return fail("uavtrack_replay_sample: the ring is empty (count = 0)");
+    if (!std::isfinite(alpha) || !(alpha > 0) || (float)alpha <= 0.0f)
+        return fail("uavtrack_replay_sample: alpha = %g must be finite and > 0", alpha);
+    if (!std::isfinite(beta) || !(beta >= 0)) return fail("uavtrack_replay_sample: beta = %g must be finite and >= 0", beta);
+    ON_DEVICE(replay->cfg.device_id);
+    HIP_TRY(launch_replay_sample(replay->d, ring->priorities, ring->count, n, (float)alpha, beta, indices, weights,
+                                 static_cast<hipStream_t>(stream)));
+    return 0;
+}
+
+int uavtrack_replay_check(uavtrack_replay *replay, int64_t *refused, void *stream)
+{
+    if (!replay) return fail("uavtrack_replay_check: null handle");
+    ON_DEVICE(replay->cfg.device_id);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    int count = 0;
+    HIP_TRY(hipMemcpyAsync(&count, replay->d.errors, 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemsetAsync(replay->d.errors, 0, 4, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (refused) *refused = count;
+    if (count)
+        return fail("uavtrack_replay_check: %d sample call(s) refused: a priority in [0, count) is NaN, infinite or "
+                    "negative, or all of them are zero; their indices are slot 0", count);
+    return 0;
+}
+
+}  // extern "C"

@@ -374,4 +374,36 @@ struct PmiTrainLaunch {
 };
 hipError_t launch_pmi_train(const PmiTrainDevice &d, const PmiTrainLaunch &q, hipStream_t stream);
 
+// replay_kernel.hip -- the prioritised replay ring (uavtrack_replay_*).  The ring's stores and priorities belong to the
+// caller; the handle owns the scratch below.  Sampling works on tiles of kReplayTile slots: per-tile fp64 sums, one
+// inclusive scan of them, then one wavefront per draw (binary search over the tile prefix, rescan of one tile).
+constexpr int kReplayTile = 2048;
+constexpr int kReplayMaxParts = 1024;         // workgroups of the priority-maximum reduction
+constexpr uint32_t kReplayDomain = 0x52504C59u;   // "RPLY": Philox counter word 3 of the draw stream
+struct ReplayDevice {
+    int64_t max_capacity, max_batch;
+    uint32_t k0, k1;                // Philox key: the ring's seed
+    double *prefix;                 // [ceil(max_capacity / kReplayTile)] tile sums, then their inclusive prefix
+    int64_t *tile_last;             // [same] last slot of a tile with a non-zero weight, -1 if none
+    uint64_t *counter;              // [2] call counter (advanced on the device), this call's value
+    unsigned long long *pmin;       // [1] smallest sampled P(i) of this call (fp64 bits)
+    double *pdraw;                  // [max_batch] P(i) of each draw
+    float *parts;                   // [kReplayMaxParts] per-workgroup priority maxima; [kReplayMaxParts] = the maximum
+    int *status;                    // [1] this call's refusal bits
+    int *errors;                    // [1] draws refused since the last check
+};
+struct ReplayRingView {
+    float *states, *rewards, *next_states, *priorities;
+    int32_t *actions;
+    int64_t capacity, pos, count;
+};
+hipError_t launch_replay_sample(const ReplayDevice &d, const float *priorities, int64_t count, int64_t k, float alpha,
+                                double beta, int64_t *indices, float *weights, hipStream_t stream);
+// n transitions: flat (obs_in == nullptr: states / next_states [n][12], actions / rewards [n]) or one rollout
+// (obs_in [agents][12], obs [n / agents][agents][12], actions / rewards [n / agents][agents]); only the last
+// min(n, capacity) land in the ring, from ring.pos on
+hipError_t launch_replay_add(const ReplayDevice &d, const ReplayRingView &ring, int64_t n, int64_t agents,
+                             const float *obs_in, const float *states, const float *next_states, const int32_t *actions,
+                             const float *rewards, hipStream_t stream);
+
 }  // namespace uavtrack

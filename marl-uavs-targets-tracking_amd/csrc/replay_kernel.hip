@@ -1,0 +1,379 @@
+// replay_kernel.hip -- the reference's PrioritizedReplayBuffer (train.py:73-139) on the device: add (train.py:87-96)
+// straight from a rollout's outputs, and sample (train.py:98-112) with replacement from P(i) = p_i^alpha / sum_j p_j^alpha.
+//
+// Sampling is a chain of stream-ordered launches, none of which synchronises or allocates:
+//   replay_begin_kernel     one thread: this call's Philox counter (the device call counter, then advanced), status and
+//                           the batch minimum of P cleared;
+//   replay_tile_kernel      one workgroup per tile of kReplayTile slots: w_i = p_i^alpha in fp32 (the reference's
+//                           float32 `priorities ** alpha`), their fp64 sum in a fixed order, the tile's last slot with
+//                           w > 0, and a refusal bit for a NaN, infinite or negative priority;
+//   replay_scan_kernel      one workgroup: the tile sums -> their inclusive fp64 prefix (the coarse CDF); an all-zero
+//                           ring is refused here;
+//   replay_draw_kernel      one wavefront per draw: u in [0, 1) from 53 Philox bits, x = u * total, the first tile whose
+//                           prefix exceeds x (binary search), then the wavefront rescans that tile (32 slots per lane,
+//                           a wave prefix sum of the lane sums, a serial search in the lane) for the first slot whose
+//                           running sum exceeds x: searchsorted(cdf, x, side='right'), as np.random.choice;
+//   replay_min_kernel,      (only when weights are asked for) (count * P(i))^-beta / max over the batch, the maximum
+//   replay_weight_kernel    taken from the smallest P(i) of the batch (a workgroup reduction, then one order-independent
+//                           atomic min per workgroup).
+// Where the rescan and the coarse prefix disagree in the last bit, the draw falls on the last slot with w > 0 of the lane
+// or tile it was sent to; x >= total (u * total rounded up) falls on the last slot with w > 0 of the ring.  So a draw
+// never lands on a slot >= count or a slot whose weight is 0.  A refused call writes slot 0 and NaN weights.
+//
+// Adding is two reductions (the maximum of the whole priorities array, train.py:87-88) and one write kernel: each thread
+// owns one source transition f, reads obs[f] once and writes it as the next state of f and the state of f + agents.
+
+#include "internal.h"
+#include "philox.h"
+
+#include <hip/hip_runtime.h>
+#include <cmath>
+#include <cstdint>
+
+namespace uavtrack {
+
+namespace {
+
+constexpr int kSW = 256;                       // threads per workgroup of the tile and write kernels
+constexpr int kPerThread = kReplayTile / kSW;  // slots per thread in the tile kernel
+constexpr int kPerLane = kReplayTile / 64;     // slots per lane in the draw kernel's rescan
+constexpr int kScanW = 1024;                   // threads of the scan kernel
+static_assert(kReplayTile % kSW == 0 && kReplayTile % 64 == 0, "tile geometry");
+
+// p^alpha of slot i as the reference's float32 array power; 0 beyond count.  bad: a NaN, infinite or negative priority.
+__device__ __forceinline__ float slot_weight(const float *prio, int64_t i, int64_t count, float alpha, bool &bad)
+{
+    if (i >= count) return 0.0f;
+    const float p = prio[i];
+    if (!(p >= 0.0f) || isinf(p)) { bad = true; return 0.0f; }
+    return alpha == 1.0f ? p : powf(p, alpha);
+}
+
+__device__ __forceinline__ double wave_sum(double v)
+{
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
+    return v;
+}
+
+__device__ __forceinline__ double wave_inclusive_scan(double v, int lane)
+{
+    for (int o = 1; o < 64; o <<= 1) {
+        const double t = __shfl_up(v, o, 64);
+        if (lane >= o) v += t;
+    }
+    return v;
+}
+
+// max that keeps a NaN once seen (torch.max propagates NaN)
+__device__ __forceinline__ float nan_max(float m, float v) { return (v > m || v != v) ? v : m; }
+
+__global__ void replay_begin_kernel(uint64_t *counter, int *status, unsigned long long *pmin)
+{
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    counter[1] = counter[0];
+    counter[0] += 1;
+    *status = 0;
+    *pmin = 0x7FF0000000000000ull;             // +inf
+}
+
+__global__ void __launch_bounds__(kSW) replay_tile_kernel(const float *prio, int64_t count, float alpha, double *tile_sum,
+                                                          int64_t *tile_last, int *status)
+{
+    __shared__ double wsum[kSW / 64];
+    __shared__ unsigned long long last;        // 1 + the last slot with w > 0 (0: none)
+    __shared__ int bad_any;
+    const int tid = threadIdx.x, lane = tid & 63;
+    if (tid == 0) { last = 0; bad_any = 0; }
+    __syncthreads();
+    const int64_t base = (int64_t)blockIdx.x * kReplayTile + (int64_t)tid * kPerThread;
+    bool bad = false;
+    double s = 0.0;
+    int64_t mylast = -1;
+#pragma unroll
+    for (int q = 0; q < kPerThread; ++q) {
+        const float w = slot_weight(prio, base + q, count, alpha, bad);
+        s += (double)w;
+        if (w > 0.0f) mylast = base + q;
+    }
+    if (mylast >= 0) atomicMax(&last, (unsigned long long)(mylast + 1));
+    if (bad) bad_any = 1;
+    s = wave_sum(s);
+    if (lane == 0) wsum[tid >> 6] = s;
+    __syncthreads();
+    if (tid == 0) {
+        double t = 0.0;
+        for (int w = 0; w < kSW / 64; ++w) t += wsum[w];
+        tile_sum[blockIdx.x] = t;
+        tile_last[blockIdx.x] = (int64_t)last - 1;
+        if (bad_any) atomicOr(status, 1);
+    }
+}
+
+// One workgroup: tile sums -> inclusive prefix in place.  Thread c owns a contiguous chunk of tiles.
+__global__ void __launch_bounds__(kScanW) replay_scan_kernel(double *prefix, int ntiles, int *status, int *errors)
+{
+    __shared__ double wtot[kScanW / 64];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int chunk = (ntiles + kScanW - 1) / kScanW;
+    const int b = tid * chunk, e = min(ntiles, b + chunk);
+    double s = 0.0;
+    for (int t = b; t < e; ++t) s += prefix[t];
+    const double incl = wave_inclusive_scan(s, lane);
+    if (lane == 63) wtot[wave] = incl;
+    __syncthreads();
+    double off = 0.0;
+    for (int w = 0; w < wave; ++w) off += wtot[w];
+    double excl = __shfl_up(incl, 1, 64);
+    if (lane == 0) excl = 0.0;
+    double run = off + excl;
+    for (int t = b; t < e; ++t) { run += prefix[t]; prefix[t] = run; }
+    __syncthreads();
+    if (tid == 0) {
+        const double total = prefix[ntiles - 1];
+        int st = *status;
+        if (!(total > 0.0)) st |= 2;
+        *status = st;
+        if (st) *errors += 1;
+    }
+}
+
+struct DrawArgs {
+    const float *prio;
+    const double *prefix;
+    const int64_t *tile_last;
+    const uint64_t *counter;
+    const int *status;
+    double *pdraw;
+    int64_t *indices;
+    int64_t count, k;
+    int ntiles;
+    float alpha;
+    uint32_t k0, k1;
+};
+
+__global__ void __launch_bounds__(kSW) replay_draw_kernel(DrawArgs a)
+{
+    const int lane = threadIdx.x & 63;
+    const int64_t j = (int64_t)blockIdx.x * (kSW / 64) + (threadIdx.x >> 6);
+    if (j >= a.k) return;                      // (whole wavefronts)
+    if (*a.status) {
+        if (lane == 0) { a.indices[j] = 0; a.pdraw[j] = NAN; }
+        return;
+    }
+    const uint64_t call = a.counter[1];
+    const Philox4 r = philox4x32_10((uint32_t)j, (uint32_t)call, (uint32_t)(call >> 32), kReplayDomain, a.k0, a.k1);
+    const uint64_t bits = ((uint64_t)r.v[0] << 21) | (uint64_t)(r.v[1] >> 11);
+    const double u = (double)bits * 0x1p-53;
+    const double total = a.prefix[a.ntiles - 1];
+    const double x = u * total;
+
+    // the first tile whose inclusive prefix exceeds x
+    int lo = 0, hi = a.ntiles;
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (a.prefix[mid] > x) hi = mid; else lo = mid + 1;
+    }
+    int64_t slot;
+    if (lo == a.ntiles) {
+        // x rounded up to total: the last slot with w > 0, in the first tile whose prefix reaches total
+        lo = 0; hi = a.ntiles - 1;
+        while (lo < hi) {
+            const int mid = (lo + hi) >> 1;
+            if (a.prefix[mid] >= total) hi = mid; else lo = mid + 1;
+        }
+        slot = a.tile_last[lo];
+    } else {
+        const int t = lo;
+        const double rem = x - (t > 0 ? a.prefix[t - 1] : 0.0);     // >= 0: prefix[t - 1] <= x
+        const int64_t base = (int64_t)t * kReplayTile + (int64_t)lane * kPerLane;
+        bool bad = false;
+        double s = 0.0;
+        for (int q = 0; q < kPerLane; ++q) s += (double)slot_weight(a.prio, base + q, a.count, a.alpha, bad);
+        const double incl = wave_inclusive_scan(s, lane);
+        double excl = __shfl_up(incl, 1, 64);
+        if (lane == 0) excl = 0.0;
+        const unsigned long long hit = __ballot(incl > rem);
+        if (hit == 0) {
+            slot = a.tile_last[t];              // the rescan's total fell short of the tile sum in the last bit
+        } else {
+            const int L = __ffsll(hit) - 1;
+            int64_t mine = -1;
+            if (lane == L) {
+                const double want = rem - excl;
+                double c = 0.0;
+                int64_t lastnz = -1;
+                for (int q = 0; q < kPerLane && mine < 0; ++q) {      // the same weights, summed in the same order
+                    const float w = slot_weight(a.prio, base + q, a.count, a.alpha, bad);
+                    if (w > 0.0f) lastnz = base + q;
+                    c += (double)w;
+                    if (c > want) mine = base + q;
+                }
+                if (mine < 0) mine = lastnz;    // (rem - excl) rounded past the lane's own sum
+            }
+            slot = __shfl(mine, L, 64);
+        }
+    }
+    if (slot < 0 || slot >= a.count) slot = 0;  // unreachable while total > 0; kept so no index ever leaves the ring
+    if (lane == 0) {
+        bool bad = false;
+        const double p = (double)slot_weight(a.prio, slot, a.count, a.alpha, bad) / total;
+        a.indices[j] = slot;
+        a.pdraw[j] = p;
+    }
+}
+
+// the batch minimum of P(i): one atomic min per workgroup (positive doubles order as their bits, so the result does not
+// depend on the order of the atomics)
+__global__ void __launch_bounds__(kSW) replay_min_kernel(const double *pdraw, int64_t k, unsigned long long *pmin)
+{
+    __shared__ double wm[kSW / 64];
+    double m = INFINITY;
+    for (int64_t i = (int64_t)blockIdx.x * kSW + threadIdx.x; i < k; i += (int64_t)gridDim.x * kSW) m = fmin(m, pdraw[i]);
+    for (int o = 32; o > 0; o >>= 1) m = fmin(m, __shfl_down(m, o, 64));
+    if ((threadIdx.x & 63) == 0) wm[threadIdx.x >> 6] = m;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int w = 1; w < kSW / 64; ++w) m = fmin(m, wm[w]);
+        atomicMin(pmin, (unsigned long long)__double_as_longlong(m));
+    }
+}
+
+__global__ void replay_weight_kernel(const double *pdraw, int64_t k, int64_t count, double beta,
+                                     const unsigned long long *pmin, const int *status, float *weights)
+{
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= k) return;
+    if (*status) { weights[i] = NAN; return; }
+    const double n = (double)count;
+    const double wmax = pow(n * __longlong_as_double((long long)*pmin), -beta);
+    weights[i] = (float)(pow(n * pdraw[i], -beta) / wmax);
+}
+
+// ---- add
+
+__global__ void __launch_bounds__(kSW) replay_max_kernel(const float *prio, int64_t capacity, float *parts)
+{
+    __shared__ float wm[kSW / 64];
+    float m = -INFINITY;
+    for (int64_t i = (int64_t)blockIdx.x * kSW + threadIdx.x; i < capacity; i += (int64_t)gridDim.x * kSW)
+        m = nan_max(m, prio[i]);
+    for (int o = 32; o > 0; o >>= 1) m = nan_max(m, __shfl_down(m, o, 64));
+    if ((threadIdx.x & 63) == 0) wm[threadIdx.x >> 6] = m;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int w = 1; w < kSW / 64; ++w) m = nan_max(m, wm[w]);
+        parts[blockIdx.x] = m;
+    }
+}
+
+// parts[kReplayMaxParts] = the maximum of parts[0, groups), or 1.0 for an empty ring (train.py:87-88)
+__global__ void replay_top_kernel(float *parts, int groups, int empty)
+{
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    float m = -INFINITY;
+    for (int g = 0; g < groups; ++g) m = nan_max(m, parts[g]);
+    parts[kReplayMaxParts] = empty ? 1.0f : m;
+}
+
+struct AddArgs {
+    ReplayRingView ring;
+    const float *obs_in;                       // rollout form: [agents][12]; nullptr: flat form
+    const float *src_states, *src_next;        // flat: states [n][12]; both forms: next states [n][12]
+    const int32_t *src_actions;
+    const float *src_rewards;
+    const float *top;
+    int64_t n, agents, skip, start;
+};
+
+__device__ __forceinline__ void copy_row(float *dst, const float *src)
+{
+    const float4 *s = reinterpret_cast<const float4 *>(src);
+    float4 *d = reinterpret_cast<float4 *>(dst);
+    const float4 a = s[0], b = s[1], c = s[2];
+    d[0] = a; d[1] = b; d[2] = c;
+}
+
+__global__ void __launch_bounds__(kSW) replay_write_kernel(AddArgs a)
+{
+    const int64_t cap = a.ring.capacity;
+    const float top = *a.top;
+    for (int64_t f = a.skip + (int64_t)blockIdx.x * kSW + threadIdx.x; f < a.n; f += (int64_t)gridDim.x * kSW) {
+        int64_t slot = a.start + (f - a.skip);
+        if (slot >= cap) slot -= cap;
+        const float *row = a.src_next + f * 12;
+        copy_row(a.ring.next_states + slot * 12, row);
+        if (a.obs_in) {
+            const int64_t M = a.agents;
+            if (f + M < a.n) {                   // obs[f] is also the state of transition f + M
+                const int64_t s2 = (a.start + (f + M - a.skip)) % cap;
+                copy_row(a.ring.states + s2 * 12, row);
+            }
+            if (f < M) copy_row(a.ring.states + slot * 12, a.obs_in + f * 12);
+            else if (f - M < a.skip) copy_row(a.ring.states + slot * 12, a.src_next + (f - M) * 12);
+        } else {
+            copy_row(a.ring.states + slot * 12, a.src_states + f * 12);
+        }
+        a.ring.actions[slot] = a.src_actions[f];
+        a.ring.rewards[slot] = a.src_rewards[f];
+        a.ring.priorities[slot] = top;
+    }
+}
+
+}  // namespace
+
+hipError_t launch_replay_sample(const ReplayDevice &d, const float *priorities, int64_t count, int64_t k, float alpha,
+                                double beta, int64_t *indices, float *weights, hipStream_t st)
+{
+    const int ntiles = (int)((count + kReplayTile - 1) / kReplayTile);
+    hipLaunchKernelGGL(replay_begin_kernel, dim3(1), dim3(64), 0, st, d.counter, d.status, d.pmin);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(replay_tile_kernel, dim3(ntiles), dim3(kSW), 0, st, priorities, count, alpha, d.prefix,
+                       d.tile_last, d.status);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    hipLaunchKernelGGL(replay_scan_kernel, dim3(1), dim3(kScanW), 0, st, d.prefix, ntiles, d.status, d.errors);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    DrawArgs a;
+    a.prio = priorities; a.prefix = d.prefix; a.tile_last = d.tile_last; a.counter = d.counter; a.status = d.status;
+    a.pdraw = d.pdraw; a.indices = indices; a.count = count; a.k = k; a.ntiles = ntiles;
+    a.alpha = alpha; a.k0 = d.k0; a.k1 = d.k1;
+    const int64_t per = kSW / 64;
+    hipLaunchKernelGGL(replay_draw_kernel, dim3((unsigned)((k + per - 1) / per)), dim3(kSW), 0, st, a);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    if (weights) {
+        int64_t mg = (k + (int64_t)kSW * 16 - 1) / ((int64_t)kSW * 16);
+        if (mg > 1024) mg = 1024;
+        hipLaunchKernelGGL(replay_min_kernel, dim3((unsigned)mg), dim3(kSW), 0, st, d.pdraw, k, d.pmin);
+        if ((e = hipGetLastError()) != hipSuccess) return e;
+        hipLaunchKernelGGL(replay_weight_kernel, dim3((unsigned)((k + 255) / 256)), dim3(256), 0, st, d.pdraw, k, count,
+                           beta, d.pmin, d.status, weights);
+        if ((e = hipGetLastError()) != hipSuccess) return e;
+    }
+    return hipSuccess;
+}
+
+hipError_t launch_replay_add(const ReplayDevice &d, const ReplayRingView &ring, int64_t n, int64_t agents,
+                             const float *obs_in, const float *states, const float *next_states, const int32_t *actions,
+                             const float *rewards, hipStream_t st)
+{
+    const int64_t cap = ring.capacity;
+    int64_t groups = (cap + (int64_t)kSW * 16 - 1) / ((int64_t)kSW * 16);
+    if (groups > kReplayMaxParts) groups = kReplayMaxParts;
+    hipLaunchKernelGGL(replay_max_kernel, dim3((unsigned)groups), dim3(kSW), 0, st, ring.priorities, cap, d.parts);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(replay_top_kernel, dim3(1), dim3(64), 0, st, d.parts, (int)groups, ring.count == 0 ? 1 : 0);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    AddArgs a;
+    a.ring = ring; a.obs_in = obs_in; a.src_states = states; a.src_next = next_states; a.src_actions = actions;
+    a.src_rewards = rewards; a.top = d.parts + kReplayMaxParts; a.n = n; a.agents = agents;
+    a.skip = n > cap ? n - cap : 0;
+    a.start = (ring.pos + a.skip) % cap;
+    const int64_t m = n - a.skip;
+    int64_t blocks = (m + kSW - 1) / kSW;
+    if (blocks > 65536) blocks = 65536;
+    hipLaunchKernelGGL(replay_write_kernel, dim3((unsigned)blocks), dim3(kSW), 0, st, a);
+    return hipGetLastError();
+}
+
+}  // namespace uavtrack

@@ -58,6 +58,20 @@ class PmiTrainerConfig(C.Structure):
     ]
 
 
+class ReplayConfig(C.Structure):
+    """Mirror of `struct uavtrack_replay_config` (include/uavtrack.h)."""
+    _fields_ = [
+        ("struct_size", C.c_uint32), ("device_id", C.c_int32), ("max_capacity", C.c_int64), ("max_batch", C.c_int64),
+        ("seed", C.c_uint64),
+    ]
+
+
+class ReplayRing(C.Structure):
+    """Mirror of `struct uavtrack_replay_ring` (include/uavtrack.h)."""
+    _fields_ = [(k, C.c_void_p) for k in ("states", "actions", "rewards", "next_states", "priorities")] + [
+        ("capacity", C.c_int64), ("pos", C.c_int64), ("count", C.c_int64)]
+
+
 PMI_TRAIN_TENSORS = 18                                    # PMINetwork.parameters()
 PMI_BN_LAYERS = 4                                         # BatchNorm1d layers (num_batches_tracked entries)
 LOSS_FORMS = ("reference", "per_sample")                  # enum uavtrack_actor_loss
@@ -119,6 +133,13 @@ SIGNATURES = {
     "uavtrack_pmi_trainer_train": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p,
                                               C.c_int64, C.c_int64] + [C.c_void_p] * 4),
     "uavtrack_pmi_trainer_check": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64), C.c_void_p]),
+    "uavtrack_replay_create": (C.c_int, [C.POINTER(ReplayConfig), C.POINTER(C.c_void_p)]),
+    "uavtrack_replay_destroy": (C.c_int, [C.c_void_p]),
+    "uavtrack_replay_add": (C.c_int, [C.c_void_p, C.POINTER(ReplayRing), C.c_int64] + [C.c_void_p] * 5),
+    "uavtrack_replay_add_rollout": (C.c_int, [C.c_void_p, C.POINTER(ReplayRing), C.c_int64, C.c_int64] + [C.c_void_p] * 5),
+    "uavtrack_replay_sample": (C.c_int, [C.c_void_p, C.POINTER(ReplayRing), C.c_int64, C.c_double, C.c_double,
+                                         C.c_void_p, C.c_void_p, C.c_void_p]),
+    "uavtrack_replay_check": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64), C.c_void_p]),
 }
 
 _lib = None

@@ -21,6 +21,7 @@ from . import _lib
 from ._lib import ptr as _ptr
 from .adam import flat, from_state_dict, split, to_state_dict
 from .replay import DeviceReplayBuffer, PrioritizedDeviceReplayBuffer
+from .replay_ring import PrioritizedReplayRing
 from .rollout import ActorMLP
 
 
@@ -131,15 +132,19 @@ class DeviceActorCritic:
                                                 dtype=torch.float32).reshape(n, _lib.OBS_DIM).contiguous()}
         return self._run(n, store, n, None, None)
 
-    def update_from(self, buffer: DeviceReplayBuffer, batch_size: int, beta: float = 0.4,
+    def update_from(self, buffer, batch_size: int, beta: float = 0.4,
                     generator: Optional[torch.Generator] = None):
         """buffer.sample(batch_size) + update + (prioritised buffer) update_priorities(indices, |td_delta|)
         (train.py:253-262), the gather and the priority write inside the library call.  The indices are drawn as
         the buffer's own sample() draws them.  beta only weights the importance weights, which the reference's
-        update does not use."""
+        update does not use.  For a PrioritizedReplayRing the draw is one library call of its own (the ring's seed
+        and device call counter; `generator` does not apply), so the whole update is two library calls with no torch
+        kernel between them, and can be captured into a graph."""
         k = min(int(batch_size), buffer.count)
         if k < 1:
             raise ValueError("update_from: the buffer is empty")
+        if isinstance(buffer, PrioritizedReplayRing):
+            return self._run(k, buffer.store, buffer.capacity, buffer._draw_into(k), buffer.priorities)
         if isinstance(buffer, PrioritizedDeviceReplayBuffer):
             prob = buffer.priorities[:buffer.count] ** buffer.alpha
             prob = prob / prob.sum()

@@ -1,0 +1,164 @@
+"""The reference's `PrioritizedReplayBuffer` (src/train.py:73-139) with its add and its draw in HIP (uavtrack_replay_*):
+the ring's stores and priorities are device tensors laid out as in DeviceReplayBuffer, owned here and passed to the
+library as pointers; the library handle keeps only scratch and the device-side draw counter.
+
+Against PrioritizedDeviceReplayBuffer (uavtrack/replay.py, which stays the plain-PyTorch reference):
+  - add_rollout writes a rollout's outputs straight into the ring (no [T*B*N, 12] concatenation, only the last
+    `capacity` transitions written), new transitions entering at the device-side maximum priority;
+  - the draw has no 2^24-slot limit (torch.multinomial's), keeps its CDF in fp64 as np.random.choice does, and is
+    keyed by (seed, device call counter), so every replay of a captured graph draws afresh.  The stream is documented
+    in include/uavtrack.h.
+"""
+from __future__ import annotations
+
+import ctypes as C
+from typing import Dict, Optional, Tuple
+
+import torch
+
+from . import _lib
+from ._lib import ptr as _ptr
+from .replay import KEYS
+
+
+class PrioritizedReplayRing:
+    """PrioritizedReplayBuffer(capacity, alpha) (train.py:73-139) as a device ring with HIP add and sampling."""
+
+    def __init__(self, capacity: int, device, alpha: float = 0.6, seed: int = 0, max_batch: int = 65536,
+                 obs_dim: int = _lib.OBS_DIM):
+        if obs_dim != _lib.OBS_DIM:
+            raise ValueError(f"obs_dim must be {_lib.OBS_DIM}, got {obs_dim}")
+        if not alpha > 0:
+            raise ValueError(f"alpha must be > 0, got {alpha}")
+        self.capacity = int(capacity)
+        self.device = torch.device(device)
+        if self.device.index is None:
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        self.alpha, self.seed, self.max_batch = float(alpha), int(seed), int(max_batch)
+        self.store = {"states": torch.empty(self.capacity, obs_dim, device=self.device),
+                      "actions": torch.empty(self.capacity, dtype=torch.int32, device=self.device),
+                      "rewards": torch.empty(self.capacity, device=self.device),
+                      "next_states": torch.empty(self.capacity, obs_dim, device=self.device)}
+        self.priorities = torch.zeros(self.capacity, device=self.device)
+        self.pos = 0          # next slot to write
+        self.count = 0        # valid transitions
+        self._lib = _lib.load()
+        cfg = _lib.ReplayConfig(struct_size=C.sizeof(_lib.ReplayConfig), device_id=self.device.index,
+                                max_capacity=self.capacity, max_batch=self.max_batch, seed=self.seed & (2**64 - 1))
+        h = C.c_void_p()
+        _lib.check(self._lib.uavtrack_replay_create(C.byref(cfg), C.byref(h)), "uavtrack_replay_create")
+        self._h = h
+        self._idx = torch.empty(self.max_batch, dtype=torch.int64, device=self.device)   # update_from's draws
+
+    # ---- handle plumbing
+    def close(self) -> None:
+        if getattr(self, "_h", None):
+            self._lib.uavtrack_replay_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _stream(self):
+        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+
+    def _ring(self) -> _lib.ReplayRing:
+        s = self.store
+        return _lib.ReplayRing(states=s["states"].data_ptr(), actions=s["actions"].data_ptr(),
+                               rewards=s["rewards"].data_ptr(), next_states=s["next_states"].data_ptr(),
+                               priorities=self.priorities.data_ptr(), capacity=self.capacity, pos=self.pos,
+                               count=self.count)
+
+    def _advance(self, n: int) -> None:
+        self.pos = (self.pos + n) % self.capacity
+        self.count = min(self.capacity, self.count + n)
+
+    def size(self) -> int:
+        return self.count
+
+    def check(self) -> None:
+        """Synchronises; raises if a draw since the last check was refused on the device (a NaN, infinite or negative
+        priority in [0, count), or all of them zero).  A refused draw returned slot 0 and NaN weights."""
+        _lib.check(self._lib.uavtrack_replay_check(self._h, None, self._stream()), "uavtrack_replay_check")
+
+    # ---- add (train.py:87-96)
+    def add(self, transition_dict: Dict[str, torch.Tensor]) -> None:
+        """transition_dict: states [n,12], actions [n], rewards [n], next_states [n,12] (any leading shape is
+        flattened).  One library call writes the last min(n, capacity) of them at the current maximum priority."""
+        n = transition_dict["actions"].numel()
+        if n < 1:
+            return
+        dev, D = self.device, _lib.OBS_DIM
+        s = transition_dict["states"].to(dev, torch.float32).reshape(n, D).contiguous()
+        a = transition_dict["actions"].to(dev, torch.int32).reshape(n).contiguous()
+        r = transition_dict["rewards"].to(dev, torch.float32).reshape(n).contiguous()
+        s2 = transition_dict["next_states"].to(dev, torch.float32).reshape(n, D).contiguous()
+        ring = self._ring()
+        _lib.check(self._lib.uavtrack_replay_add(self._h, C.byref(ring), n, _ptr(s), _ptr(a), _ptr(r), _ptr(s2),
+                                                 self._stream()), "uavtrack_replay_add")
+        self._advance(n)
+
+    def add_rollout(self, obs_in: torch.Tensor, out: Dict[str, torch.Tensor]) -> None:
+        """add(transitions_from_rollout(obs_in, out)) in one library call: obs_in [B,N,12] is what the policy saw
+        first, out = {obs [T,B,N,12], actions [T,B,N] int32, reward [T,B,N]} (BatchedRollout.run_fused's outputs)."""
+        obs, act, rew = out["obs"], out["actions"], out["reward"]
+        T = obs.shape[0]
+        M = obs_in.numel() // _lib.OBS_DIM
+        if obs.numel() != T * M * _lib.OBS_DIM or act.numel() != T * M or rew.numel() != T * M:
+            raise ValueError(f"add_rollout: obs {tuple(obs.shape)}, actions {tuple(act.shape)}, reward "
+                             f"{tuple(rew.shape)} do not match obs_in {tuple(obs_in.shape)}")
+        if obs.dtype != torch.float32 or obs_in.dtype != torch.float32 or act.dtype != torch.int32 \
+                or rew.dtype != torch.float32:
+            raise TypeError("add_rollout: obs_in, obs and reward must be float32, actions int32")
+        for t in (obs_in, obs, act, rew):
+            if t.device != self.device or not t.is_contiguous():
+                raise ValueError("add_rollout: every input must be contiguous on the ring's device")
+        ring = self._ring()
+        _lib.check(self._lib.uavtrack_replay_add_rollout(self._h, C.byref(ring), T, M, _ptr(obs_in), _ptr(obs),
+                                                         _ptr(act), _ptr(rew), self._stream()),
+                   "uavtrack_replay_add_rollout")
+        self._advance(T * M)
+
+    # ---- sample (train.py:98-112)
+    def _draw(self, k: int, beta: float, idx: torch.Tensor, weights: Optional[torch.Tensor]) -> None:
+        ring = self._ring()
+        _lib.check(self._lib.uavtrack_replay_sample(self._h, C.byref(ring), k, self.alpha, float(beta), _ptr(idx),
+                                                    _ptr(weights), self._stream()), "uavtrack_replay_sample")
+
+    def _draw_into(self, k: int) -> torch.Tensor:
+        """k indices into the preallocated index tensor (no weights): what DeviceActorCritic.update_from uses."""
+        idx = self._idx[:k]
+        self._draw(k, 0.0, idx, None)
+        return idx
+
+    def draw(self, batch_size: int, beta: float = 0.4) -> Tuple[Optional[torch.Tensor], Optional[torch.Tensor]]:
+        """(indices int64 [k], importance weights fp32 [k]) with k = min(batch_size, count), drawn with replacement
+        from P(i) = p_i^alpha / sum_j p_j^alpha; (None, None) for an empty ring.  No synchronisation."""
+        if self.count == 0:
+            return None, None
+        k = min(int(batch_size), self.count)
+        idx = torch.empty(k, dtype=torch.int64, device=self.device)
+        w = torch.empty(k, dtype=torch.float32, device=self.device)
+        self._draw(k, beta, idx, w)
+        return idx, w
+
+    def sample(self, batch_size: int, beta: float = 0.4):
+        """PrioritizedReplayBuffer.sample: (transitions dict, indices int64, weights), or (empty dict, None, None)
+        for an empty ring."""
+        if self.count == 0:
+            return {k: self.store[k][:0] for k in KEYS}, None, None
+        idx, w = self.draw(batch_size, beta)
+        return {key: self.store[key][idx] for key in KEYS}, idx, w
+
+    def update_priorities(self, batch_indices: torch.Tensor, batch_priorities: torch.Tensor) -> None:
+        """PrioritizedReplayBuffer.update_priorities (train.py:136-138): a repeated index keeps its last value, as the
+        reference's sequential loop."""
+        idx = batch_indices.to(self.device, torch.int64).reshape(-1)
+        val = batch_priorities.to(self.device, torch.float32).reshape(-1)
+        srt, perm = torch.sort(idx, stable=True)
+        last = torch.ones_like(srt, dtype=torch.bool)
+        last[:-1] = srt[1:] != srt[:-1]
+        self.priorities.index_copy_(0, srt[last], val[perm[last]])
