@@ -486,9 +486,10 @@ int uavtrack_pmi_trainer_check(uavtrack_pmi_trainer *trainer, int64_t *refused, 
  * Word 3 of the reset (0x55415631 "UAV1") and actor (0x4143544F "ACTO") streams differs, so no draw shares a counter with
  * them.  The slot is searchsorted(cdf, u * total, side='right') with w_i = p_i^alpha in fp32 (the reference's float32
  * `priorities ** alpha`), cdf its fp64 running sum over [0, count) and total = cdf[count - 1], as np.random.choice
- * (train.py:106); where u * total rounds up to total, the draw takes the last slot with w > 0.  Sums are exact for
- * integer weights below 2^53; otherwise a draw within rounding of a CDF boundary may fall on either side of it, but never
- * on a slot >= count or one with w = 0. */
+ * (train.py:106).  Sums are exact for integer weights below 2^53; otherwise a draw within rounding of a CDF boundary
+ * may fall on either side of it.  The rule there: a draw that rounding sends to a lane (32 slots) or a tile (2048
+ * slots) holding no w > 0, or past the last w > 0 of the lane or tile it was sent to, takes the last slot with w > 0
+ * at or before that lane or tile.  So a draw never lands on a slot >= count or one with w = 0. */
 typedef struct uavtrack_replay_config {
     uint32_t struct_size;       /* = sizeof(uavtrack_replay_config), ABI check */
     int32_t  device_id;         /* HIP device ordinal */

@@ -16,9 +16,12 @@
 //   replay_min_kernel,      (only when weights are asked for) (count * P(i))^-beta / max over the batch, the maximum
 //   replay_weight_kernel    taken from the smallest P(i) of the batch (a workgroup reduction, then one order-independent
 //                           atomic min per workgroup).
-// Where the rescan and the coarse prefix disagree in the last bit, the draw falls on the last slot with w > 0 of the lane
-// or tile it was sent to; x >= total (u * total rounded up) falls on the last slot with w > 0 of the ring.  So a draw
-// never lands on a slot >= count or a slot whose weight is 0.  A refused call writes slot 0 and NaN weights.
+// The sums are fp64 in a fixed order, but not one order: the scans associate a prefix differently from its predecessor,
+// so where the rescan and the coarse prefix disagree in the last bit, or a lane or tile holding no w > 0 gets a prefix
+// an ulp above its predecessor's and x falls in between, the rule is: the draw takes the last slot with w > 0 at or
+// before the lane (tile) it was sent to.  One exists: a prefix over nothing but zeros is exactly 0, and never exceeds
+// x >= 0.  x >= total cannot happen: u <= 1 - 2^-53 and total >= 2^-149 is a normal double, so u * total rounds below
+// total.  So a draw lands only on a slot in [0, count) with w > 0.  A refused call writes slot 0 and NaN weights.
 //
 // Adding is two reductions (the maximum of the whole priorities array, train.py:87-88) and one write kernel: each thread
 // owns one source transition f, reads obs[f] once and writes it as the next state of f and the state of f + agents.
@@ -62,6 +65,19 @@ __device__ __forceinline__ double wave_inclusive_scan(double v, int lane)
         if (lane >= o) v += t;
     }
     return v;
+}
+
+// The last slot with w > 0 in tiles <= t, for a whole wavefront: the wave walks tile_last back from t, 64 tiles a step
+// (-1 if there is none).  Past the first step only for a draw that rounding sent into a tile holding no w > 0.
+__device__ __forceinline__ int64_t last_positive_upto(const int64_t *tile_last, int t, int lane)
+{
+    for (int top = t; top >= 0; top -= 64) {
+        const int i = top - lane;
+        const int64_t v = i >= 0 ? tile_last[i] : -1;
+        const unsigned long long has = __ballot(v >= 0);
+        if (has) return __shfl(v, __ffsll(has) - 1, 64);          // the lowest lane holds the highest tile
+    }
+    return -1;
 }
 
 // max that keeps a NaN once seen (torch.max propagates NaN)
@@ -175,13 +191,7 @@ __global__ void __launch_bounds__(kSW) replay_draw_kernel(DrawArgs a)
     }
     int64_t slot;
     if (lo == a.ntiles) {
-        // x rounded up to total: the last slot with w > 0, in the first tile whose prefix reaches total
-        lo = 0; hi = a.ntiles - 1;
-        while (lo < hi) {
-            const int mid = (lo + hi) >> 1;
-            if (a.prefix[mid] >= total) hi = mid; else lo = mid + 1;
-        }
-        slot = a.tile_last[lo];
+        slot = last_positive_upto(a.tile_last, a.ntiles - 1, lane);   // x >= total: unreachable (see the top)
     } else {
         const int t = lo;
         const double rem = x - (t > 0 ? a.prefix[t - 1] : 0.0);     // >= 0: prefix[t - 1] <= x
@@ -189,12 +199,17 @@ __global__ void __launch_bounds__(kSW) replay_draw_kernel(DrawArgs a)
         bool bad = false;
         double s = 0.0;
         for (int q = 0; q < kPerLane; ++q) s += (double)slot_weight(a.prio, base + q, a.count, a.alpha, bad);
+        const unsigned long long nzl = __ballot(s > 0.0);             // the lanes holding a w > 0
         const double incl = wave_inclusive_scan(s, lane);
         double excl = __shfl_up(incl, 1, 64);
         if (lane == 0) excl = 0.0;
         const unsigned long long hit = __ballot(incl > rem);
         if (hit == 0) {
-            slot = a.tile_last[t];              // the rescan's total fell short of the tile sum in the last bit
+            // the rescan's total fell short of the tile sum in the last bit (the tile's last slot with w > 0), or
+            // tile t holds no w > 0 (its prefix rounded an ulp above its predecessor's): the last slot with w > 0
+            // before it.  There is one: a prefix over nothing but zero tiles is exactly 0 <= x.
+            slot = a.tile_last[t];
+            if (slot < 0) slot = last_positive_upto(a.tile_last, t - 1, lane);
         } else {
             const int L = __ffsll(hit) - 1;
             int64_t mine = -1;
@@ -211,9 +226,20 @@ __global__ void __launch_bounds__(kSW) replay_draw_kernel(DrawArgs a)
                 if (mine < 0) mine = lastnz;    // (rem - excl) rounded past the lane's own sum
             }
             slot = __shfl(mine, L, 64);
+            if (slot < 0) {
+                // lane L holds no w > 0 (its scan rounded an ulp above its predecessor's): the last slot with w > 0 of
+                // the lanes before it.  There is one: lanes 0..L all zero would scan to exactly 0 <= rem.
+                const unsigned long long below = nzl & ((1ull << L) - 1);
+                const int P = 63 - __clzll(below);
+                int64_t pl = -1;
+                if (lane == P)
+                    for (int q = 0; q < kPerLane; ++q)
+                        if (slot_weight(a.prio, base + q, a.count, a.alpha, bad) > 0.0f) pl = base + q;
+                slot = __shfl(pl, P & 63, 64);
+            }
         }
     }
-    if (slot < 0 || slot >= a.count) slot = 0;  // unreachable while total > 0; kept so no index ever leaves the ring
+    if (slot < 0 || slot >= a.count) slot = 0;  // unreachable (see the top); kept so no index ever leaves the ring
     if (lane == 0) {
         bool bad = false;
         const double p = (double)slot_weight(a.prio, slot, a.count, a.alpha, bad) / total;

@@ -1,5 +1,7 @@
 """The prioritised replay mirror (tests/replay_mirror.py) on the CPU: its selection against np.random.choice's rule
-given the same uniforms, the tiled search of the device against the flat one, its u mapping, and the ring add."""
+given the same uniforms, the tiled search of the device against the flat one, its u mapping, and the ring add; the
+order-exact mirror of the kernels (draw_device) against kernel code transcribed line by line and against the flat rule,
+the rounding gaps it builds on purpose, and the rule that no draw lands on a slot >= count or with w = 0."""
 import ctypes as C
 
 import numpy as np
@@ -150,3 +152,238 @@ def test_replay_abi_refuses_without_a_gpu_handle():
     assert lib.uavtrack_replay_sample(None, C.byref(ring), 1, 0.6, 0.4, None, None, None) != 0
     assert b"null handle" in lib.uavtrack_last_error()
     assert lib.uavtrack_replay_destroy(None) == 0
+
+
+# ---- the order-exact mirror (draw_device) ---------------------------------------------------------------------------
+
+def _literal_tile_sum(w):
+    """replay_tile_kernel for one tile, transcribed line by line in Python floats (IEEE doubles)."""
+    s = []
+    for tid in range(256):
+        v = 0.0
+        for q in range(8):
+            v += float(w[tid * 8 + q])
+        s.append(v)
+    wsum = []
+    for wave in range(4):
+        v = s[wave * 64:(wave + 1) * 64]
+        o = 32
+        while o:                                           # __shfl_down: lanes past the wave keep their own value
+            v = [v[l] + (v[l + o] if l + o < 64 else v[l]) for l in range(64)]
+            o >>= 1
+        wsum.append(v[0])
+    t = 0.0
+    for x in wsum:
+        t += x
+    return t
+
+
+def _literal_scan(sums):
+    """replay_scan_kernel, transcribed line by line."""
+    n = len(sums)
+    chunk = (n + 1023) // 1024
+    s = []
+    for tid in range(1024):
+        b, e = tid * chunk, min(n, tid * chunk + chunk)
+        v = 0.0
+        for t in range(b, e):
+            v += sums[t]
+        s.append(v)
+    incl = []
+    for wave in range(16):
+        v = s[wave * 64:(wave + 1) * 64]
+        o = 1
+        while o < 64:
+            v = [v[l] + v[l - o] if l >= o else v[l] for l in range(64)]
+            o <<= 1
+        incl.extend(v)
+    out = [0.0] * n
+    for tid in range(1024):
+        wave, lane = tid >> 6, tid & 63
+        off = 0.0
+        for w in range(wave):
+            off += incl[w * 64 + 63]
+        run = off + (incl[tid - 1] if lane else 0.0)
+        for t in range(tid * chunk, min(n, tid * chunk + chunk)):
+            run += sums[t]
+            out[t] = run
+    return out
+
+
+def _wide_weights(rng, n, zero_frac=0.3):
+    """Non-integer fp32 weights over 2^-40 .. 2^40, some zero."""
+    w = (2.0 ** rng.uniform(-40, 40, n)).astype(np.float32)
+    w[rng.rand(n) < zero_frac] = 0
+    return w
+
+
+def test_philox_np_equals_the_oracle():
+    seed, call = 0x123456789ABCDEF0, (7 << 32) | 3
+    assert np.array_equal(mirror.uniforms_np(seed, call, 300), mirror.uniforms(seed, call, 300))
+    assert np.array_equal(mirror.uniforms_np(5, 0, 64), mirror.uniforms(5, 0, 64))
+
+
+@pytest.mark.parametrize("nt", [1, 3, 1024, 1025, 2051])
+def test_tile_sums_and_scan_follow_the_kernels_order(nt):
+    rng = np.random.RandomState(nt)
+    w = np.zeros(nt * mirror.TILE)
+    probe = min(nt, 3)                                     # the literal tile kernel is slow: a few tiles suffice
+    w[:probe * mirror.TILE] = _wide_weights(rng, probe * mirror.TILE)
+    sums, last = mirror.tile_sums(w)
+    for t in range(probe):
+        assert sums[t] == _literal_tile_sum(w[t * mirror.TILE:(t + 1) * mirror.TILE])
+    assert last[0] == np.flatnonzero(w[:mirror.TILE])[-1]
+    ts = (2.0 ** rng.uniform(-30, 30, nt)) * (rng.rand(nt) > 0.3)
+    assert np.array_equal(mirror.scan(ts), np.array(_literal_scan(list(ts))))
+    # the mirror's sums are not np.sum's or np.cumsum's: the association is the kernels'
+    if nt >= 1024:
+        assert not np.array_equal(mirror.scan(ts), np.cumsum(ts))
+
+
+@pytest.mark.parametrize("count", [1, 63, 2047, 2048, 2049, 1024 * 2048, 1024 * 2048 + 1, 3000 * 2048 + 17])
+def test_draw_device_equals_flat_rule_when_sums_are_exact(count):
+    rng = np.random.RandomState(count % 100003)
+    w = rng.randint(0, 1000, size=count).astype(np.float32)          # every fp64 partial sum is an exact integer
+    w[rng.rand(count) < 0.3] = 0
+    w[-1] = 1
+    if count > 4 * 2048:
+        w[2048:2 * 2048] = 0                                           # a whole zero tile
+    w[64:96] = 0                                                       # a whole zero lane
+    u = mirror.uniforms_np(0x1_0000_0005, 0, 4000)
+    cdf = np.cumsum(w, dtype=np.float64)
+    ub = cdf[rng.choice(count, min(count, 500), replace=False)] / cdf[-1]
+    u = np.concatenate([u, ub[ub < 1.0], [0.0, 1.0 - 2.0 ** -53]])
+    d = mirror.draw_device(w, count, 1.0, 0.4, 0, 0, 0, u=u)
+    flat, _ = mirror.select(w, u)
+    assert np.array_equal(d.indices, flat)
+    assert (d.branch == mirror.HIT).all()
+    assert (w[d.indices] > 0).all() and (d.indices < count).all()
+    np.testing.assert_allclose(d.weights, mirror.importance(w, flat, cdf[-1], count, 0.4), rtol=1e-6)
+
+
+def test_draw_device_literal_draw_kernel():
+    """The vectorised draw against the draw kernel transcribed for one draw at a time (binary search, lane sums,
+    Hillis-Steele lane scan, serial search, fallbacks) on wide-range weights."""
+    rng = np.random.RandomState(11)
+    count = 5 * 2048 + 77
+    w = _wide_weights(rng, count, 0.5)
+    w[3 * 2048 + 5 * 32:3 * 2048 + 9 * 32] = 0
+    u = np.concatenate([rng.rand(300), [0.0, 1.0 - 2.0 ** -53]])
+    d = mirror.draw_device(w, count, 1.0, 0.0, 0, 0, 0, u=u)
+    wp = np.zeros(6 * 2048)
+    wp[:count] = w
+    sums, last = mirror.tile_sums(wp)
+    prefix = _literal_scan(list(sums))
+    assert list(mirror.scan(sums)) == prefix
+    total = prefix[-1]
+    assert d.total == total
+    for j, uj in enumerate(u):
+        x = uj * total
+        lo, hi = 0, 6
+        while lo < hi:
+            mid = (lo + hi) >> 1
+            if prefix[mid] > x:
+                hi = mid
+            else:
+                lo = mid + 1
+        rem = x - (prefix[lo - 1] if lo > 0 else 0.0)
+        lanes = []
+        for lane in range(64):
+            s = 0.0
+            for q in range(32):
+                s += float(wp[lo * 2048 + lane * 32 + q])
+            lanes.append(s)
+        incl = lanes
+        o = 1
+        while o < 64:
+            incl = [incl[l] + incl[l - o] if l >= o else incl[l] for l in range(64)]
+            o <<= 1
+        hits = [l for l in range(64) if incl[l] > rem]
+        if not hits:
+            slot = int(np.maximum.accumulate(last)[lo])
+        else:
+            L = hits[0]
+            want = rem - (incl[L - 1] if L else 0.0)
+            c, slot, lastnz = 0.0, -1, -1
+            for q in range(32):
+                i = lo * 2048 + L * 32 + q
+                if wp[i] > 0:
+                    lastnz = i
+                c += float(wp[i])
+                if c > want:
+                    slot = i
+                    break
+            if slot < 0:
+                slot = lastnz if lastnz >= 0 else int(np.flatnonzero(wp[lo * 2048:lo * 2048 + L * 32])[-1]) + lo * 2048
+        assert d.indices[j] == slot, j
+
+
+# kind, ntiles: a lane-level gap; tile-level gaps with a one-tile-per-thread scan and with the chunked scan (> 1024 tiles)
+GAPS = [("lane", 4), ("tile", 600), ("tile", 1100)]
+
+
+@pytest.mark.parametrize("kind,nt", GAPS, ids=["lane-fallback", "tile-fallback", "tile-fallback-chunked"])
+def test_constructed_gap_takes_the_fallback(kind, nt):
+    seed = 0x1_2345_6789
+    p, count, j = mirror.gap_ring(kind, seed, ntiles=nt)
+    assert count == (nt - 1) * mirror.TILE + 1 and p[0] == 0
+    fixed = mirror.draw_device(p, count, 1.0, 0.4, seed, 0, 256)
+    want = mirror.LANE_GAP if kind == "lane" else mirror.TILE_GAP
+    assert fixed.branch[j] == want
+    s = fixed.indices[j]
+    # the documented rule: the last slot with w > 0 before the zero lane / tile the draw was sent to
+    x = fixed.u[j] * fixed.total
+    cdf = np.cumsum(p, dtype=np.float64)
+    assert 0 < s < count and p[s] > 0
+    g = mirror.PER_LANE if kind == "lane" else mirror.TILE
+    assert not p[s + 1:(s // g + 1) * g].any()                      # the last slot with w > 0 of its lane / tile
+    assert abs(cdf[s] - x) <= 1e-12 * fixed.total                   # the draw sits on the CDF boundary after s
+    assert np.isfinite(fixed.weights).all() and fixed.weights.max() == 1.0
+    # the parent library's kernels: the draw falls through to slot 0, whose weight is 0, and the weights break
+    parent = mirror.draw_device(p, count, 1.0, 0.4, seed, 0, 256, parent=True)
+    assert parent.indices[j] == 0 and p[0] == 0
+    assert np.isnan(parent.weights[j]) and (np.nan_to_num(parent.weights) == 0).all()
+    others = np.arange(256) != j
+    assert np.array_equal(parent.indices[others], fixed.indices[others])
+
+
+def test_draw_device_never_a_bad_slot_under_wide_range_weights():
+    rng = np.random.RandomState(17)
+    count = 40 * 2048 + 999
+    # tile t's scale is 4^t * 2^-40 (so each tile outweighs the prefix before it, and x is fine-grained wherever it
+    # lands), the last tile's FLT_MAX / count; within a tile the weights span 2^24
+    scale = (2.0 ** (-40 + 2.0 * np.arange(count // 2048 + 1))).repeat(2048)[:count]
+    scale[40 * 2048:] = np.float32(3.4e38) / count
+    w = (scale * 2.0 ** rng.uniform(-24, 0, count)).astype(np.float32)
+    w[rng.rand(count) < 0.2] = 0
+    w[7 * 2048:9 * 2048] = 0                                          # whole zero tiles
+    for L in rng.choice(count // 32, 200, replace=False):             # whole zero lanes
+        w[L * 32:(L + 1) * 32] = 0
+    w[11 * 2048:12 * 2048] = np.float32(2.0 ** -149) * rng.randint(0, 8, 2048)    # fp32 subnormals
+    w[0] = 0
+    # u at random, and u within a few ulps of every tile and lane boundary as the kernels sum them
+    wp = np.zeros(-(-count // 2048) * 2048)
+    wp[:count] = w
+    prefix = mirror.scan(mirror.tile_sums(wp)[0])
+    lanes = mirror._hillis_steele(mirror._serial(wp.reshape(-1, 64, 32)))
+    b = np.concatenate([prefix, (np.concatenate([[0.0], prefix[:-1]])[:, None] + lanes).reshape(-1)]) / prefix[-1]
+    u = [rng.rand(20000), [0.0, 1.0 - 2.0 ** -53]]
+    for _ in range(3):
+        u += [b]
+        b = np.nextafter(b, 0)
+    u = np.concatenate(u)
+    u = u[(u >= 0) & (u < 1)]
+    d = mirror.draw_device(w, count, 1.0, 0.4, 0, 0, 0, u=u)
+    assert (d.indices >= 0).all() and (d.indices < count).all() and (w[d.indices] > 0).all()
+    seen = np.bincount(d.branch, minlength=6)
+    assert seen[mirror.LANE_FALLBACK] > 0 and seen[mirror.TILE_FALLBACK] > 0 and seen[mirror.OVER] == 0, seen
+    assert np.isfinite(d.weights).all() and d.weights.max() == 1.0
+    # and on the constructed gaps
+    for kind, nt in GAPS:
+        p, n, j = mirror.gap_ring(kind, 77 << 32, ntiles=nt)
+        for parent in (False, True):
+            g = mirror.draw_device(p, n, 1.0, 0.4, 77 << 32, 0, 256, parent=parent)
+            if parent:
+                assert g.indices[j] == 0 and p[0] == 0                     # the defect, modelled
+            else:
+                assert (g.indices < n).all() and (p[g.indices] > 0).all()
