@@ -12,6 +12,7 @@
 #include <cstring>
 #include <new>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 using namespace uavtrack;
@@ -63,10 +64,52 @@ struct DeviceGuard {
     DeviceGuard guard__(dev);     \
     HIP_TRY(guard__.err)
 
+// ---- device buffers: each one is named once, in the list of the set it belongs to, for allocation and release alike
+struct Buf {
+    void **slot;     // the pointer that owns it
+    size_t bytes;    // (read by replace() only: release() takes the same lists)
+    bool zero;       // starts zeroed
+};
+using Bufs = std::vector<Buf>;
+
 template <typename T>
-hipError_t dmalloc(T **p, size_t n)
+Buf buf(T *&p, size_t n = 0, bool zero = false)
 {
-    return hipMalloc(reinterpret_cast<void **>(p), (n ? n : 1) * sizeof(T));
+    return {reinterpret_cast<void **>(&p), (n ? n : 1) * sizeof(T), zero};
+}
+
+Bufs operator+(Bufs a, const Bufs &b)
+{
+    a.insert(a.end(), b.begin(), b.end());
+    return a;
+}
+
+void release(const Bufs &set)
+{
+    for (const Buf &b : set) {
+        if (*b.slot) (void)hipFree(*b.slot);
+        *b.slot = nullptr;
+    }
+}
+
+// All or nothing: a new buffer for every slot of `set`, zeroed on `st` where marked, before any slot changes; only then
+// are the old buffers freed.  On failure the new ones are freed, every slot keeps what it held, and the error comes back
+// (grown scratch: the handle stays good at its old size).
+hipError_t replace(const Bufs &set, hipStream_t st = nullptr)
+{
+    std::vector<void *> fresh(set.size(), nullptr);
+    hipError_t e = hipSuccess;
+    for (size_t i = 0; i < set.size() && e == hipSuccess; ++i) e = hipMalloc(&fresh[i], set[i].bytes);
+    for (size_t i = 0; i < set.size() && e == hipSuccess; ++i)
+        if (set[i].zero) e = hipMemsetAsync(fresh[i], 0, set[i].bytes, st);
+    if (e != hipSuccess) {
+        for (void *p : fresh)
+            if (p) (void)hipFree(p);
+        return e;
+    }
+    release(set);
+    for (size_t i = 0; i < set.size(); ++i) *set[i].slot = fresh[i];
+    return hipSuccess;
 }
 
 // The device a handle is created on (`fn` names the creating ABI function in the error): visible, and a gfx950.
@@ -111,13 +154,50 @@ hipError_t timed_launch(uavtrack_env *env, int cls, hipStream_t st, F &&launch)
     return e;
 }
 
+// ---- the environment's device buffers, by set (the arguments size the sets that are replaced later) -----------------
+Bufs slab_bufs(uavtrack_env *env)
+{
+    const uavtrack_config &c = env->cfg;
+    return {buf(env->slab, state_slab_floats(c.n_envs, c.n_uav, c.m_targets, c.dim == 3), true)};
+}
+
+Bufs counter_bufs(uavtrack_env *env)
+{
+    return {buf(env->pair_count, 2, true), buf(env->pair_total, 1, true), buf(env->pmi_flags, 2, true)};
+}
+
+// MAAC-R pair-list slots per step: every pair within dp at worst -- twice that, because the single-wavefront rollout
+// variant hands out pair-list slots in blocks and what a block has left when a step does not fit goes to dummies (less
+// than that step's pairs each time: never more than one dummy per real pair), plus a block per workgroup for the end of
+// the launch (only the pooled geometry pays the doubling: the 4-wave one reserves exactly what a step emits)
+size_t pair_slots_per_step(const uavtrack_env *env)
+{
+    const size_t BN = (size_t)env->cfg.n_envs * env->cfg.n_uav, N = (size_t)env->cfg.n_uav;
+    return env->geo.lone ? BN * (N - 1) + (size_t)env->geo.groups * 64 + 1 : BN * (N - 1) / 2 + 1;
+}
+
+Bufs maacr_bufs(uavtrack_env *env, size_t steps = 0)
+{
+    const uavtrack_config &c = env->cfg;
+    const size_t BN = (size_t)c.n_envs * c.n_uav, pairs = steps * pair_slots_per_step(env);
+    return {buf(env->pairs, pairs), buf(env->scores, pairs), buf(env->nbrec, steps * BN * nbrec_words(c.n_uav)),
+            buf(env->obs_tmp, steps * BN * UAVTRACK_OBS_DIM), buf(env->rsum, steps * (size_t)c.n_envs)};
+}
+
+Bufs inference_bufs(uavtrack_env *env, size_t n = 0)
+{
+    return {buf(env->inf_obs, n * 2 * UAVTRACK_OBS_DIM), buf(env->inf_pairs, n)};
+}
+
+Bufs actor_bufs(uavtrack_env *env, size_t floats = 0) { return {buf(env->actor_w, floats)}; }
+
+Bufs weight_bufs(PmiWeights &w, size_t floats = 0) { return {buf(w.blob, floats)}; }
+
 void free_state(uavtrack_env *env)
 {
     drop_profile(env);
-    void *ptrs[] = {env->slab, env->pmi.blob, env->actor_w, env->pairs, env->pair_count, env->pair_total, env->scores, env->nbrec,
-                    env->obs_tmp, env->rsum, env->inf_obs, env->inf_pairs, env->pmi_flags};
-    for (void *p : ptrs)
-        if (p) (void)hipFree(p);
+    release(slab_bufs(env) + counter_bufs(env) + maacr_bufs(env) + inference_bufs(env) + actor_bufs(env) +
+            weight_bufs(env->pmi));
     if (env->host_blk) (void)hipHostFree(env->host_blk);
     env->host_blk = env->host_blk_dev = nullptr;
 }
@@ -155,11 +235,7 @@ int ensure_pmi_scratch(uavtrack_env *env, int32_t steps, hipStream_t st)
 {
     const uavtrack_config &c = env->cfg;
     const size_t BN = (size_t)c.n_envs * c.n_uav;
-    // slots per step: every pair within dp at worst -- twice that, because the single-wavefront rollout variant hands out
-    // pair-list slots in blocks and what a block has left when a step does not fit goes to dummies (less than that step's
-    // pairs each time: never more than one dummy per real pair), plus a block per workgroup for the end of the launch
-    // (only the pooled geometry pays the doubling: the 4-wave one reserves exactly what a step emits)
-    const size_t pairs_step = env->geo.lone ? BN * (c.n_uav - 1) + (size_t)env->geo.groups * 64 + 1 : BN * (c.n_uav - 1) / 2 + 1;
+    const size_t pairs_step = pair_slots_per_step(env);
     const size_t rec_bytes = (size_t)nbrec_words(c.n_uav) * 4;
     const size_t per_step = pairs_step * (sizeof(uint2) + 4) + BN * rec_bytes + BN * UAVTRACK_OBS_DIM * 4 + (size_t)c.n_envs * 4;
     size_t budget = (size_t)8192 << 20;        // (of 288 GB: a 200-step rollout of the reference shape stays one chunk)
@@ -169,8 +245,8 @@ int ensure_pmi_scratch(uavtrack_env *env, int32_t steps, hipStream_t st)
     if (cap > idx_cap) cap = idx_cap;
     if (cap < 1) cap = 1;
     if (cap > steps) cap = steps;
-    // the counters first, each guarded on its own: a failure between two of them must not leave a later call with a null one
-    const bool fresh_counters = !env->pair_count || !env->pair_total || !env->pmi_flags;
+    // the counters first, as one set: a later call never finds one of them null
+    const bool fresh_counters = !env->pair_count;
     if (cap <= env->pmi_steps_cap && !fresh_counters) return 0;
     {   // Growing means a host synchronisation and device allocations: neither may happen while `st` is being captured into a
         // HIP graph.  uavtrack_set_pmi_weights sizes the scratch for cfg.horizon steps, so only a call longer than an
@@ -182,32 +258,16 @@ int ensure_pmi_scratch(uavtrack_env *env, int32_t steps, hipStream_t st)
                         "uavtrack_set_pmi_weights)", (long long)cap, env->pmi_steps_cap);
         (void)hipGetLastError();
     }
-    if (!env->pair_count) { HIP_TRY(dmalloc(&env->pair_count, 2)); HIP_TRY(hipMemsetAsync(env->pair_count, 0, 2 * sizeof(unsigned), st)); }
-    if (!env->pair_total) { HIP_TRY(dmalloc(&env->pair_total, 1)); HIP_TRY(hipMemsetAsync(env->pair_total, 0, sizeof(unsigned long long), st)); }
-    if (!env->pmi_flags) { HIP_TRY(dmalloc(&env->pmi_flags, 2)); HIP_TRY(hipMemsetAsync(env->pmi_flags, 0, 2 * sizeof(unsigned), st)); }
+    if (fresh_counters) HIP_TRY(replace(counter_bufs(env), st));
     if (cap <= env->pmi_steps_cap) return 0;
     HIP_TRY(hipStreamSynchronize(st));
-    // the larger buffers first, the old ones released only once all of them exist: a failed allocation leaves the handle
-    // as it was (still good for chunks of the old size)
-    const size_t S = (size_t)cap;
-    uint2 *n_pairs = nullptr; float *n_scores = nullptr, *n_obs = nullptr, *n_rsum = nullptr; uint32_t *n_rec = nullptr;
-    hipError_t e = dmalloc(&n_pairs, S * pairs_step);
-    if (e == hipSuccess) e = dmalloc(&n_scores, S * pairs_step);
-    if (e == hipSuccess) e = dmalloc(&n_rec, S * BN * nbrec_words(c.n_uav));
-    if (e == hipSuccess) e = dmalloc(&n_obs, S * BN * UAVTRACK_OBS_DIM);
-    if (e == hipSuccess) e = dmalloc(&n_rsum, S * (size_t)c.n_envs);
+    // a failed allocation leaves the handle as it was (still good for chunks of the old size)
+    const hipError_t e = replace(maacr_bufs(env, (size_t)cap));
     if (e != hipSuccess) {
-        void *fresh[] = {n_pairs, n_scores, n_rec, n_obs, n_rsum};
-        for (void *q : fresh)
-            if (q) (void)hipFree(q);
         (void)hipGetLastError();
         return fail("MAAC-R scratch for %lld steps per chunk (%.1f MiB) could not be allocated: %s; lower UAVTRACK_PMI_SCRATCH_MB",
-                    (long long)cap, (double)(S * per_step) / 1048576.0, hipGetErrorString(e));
+                    (long long)cap, (double)((size_t)cap * per_step) / 1048576.0, hipGetErrorString(e));
     }
-    void *old[] = {env->pairs, env->scores, env->nbrec, env->obs_tmp, env->rsum};
-    for (void *q : old)
-        if (q) (void)hipFree(q);
-    env->pairs = n_pairs; env->scores = n_scores; env->nbrec = n_rec; env->obs_tmp = n_obs; env->rsum = n_rsum;
     env->pmi_steps_cap = (int32_t)cap;
     return 0;
 }
@@ -347,9 +407,7 @@ int uavtrack_create(const uavtrack_config *cfg, uavtrack_env **out)
                     kLdsMax, cfg->n_uav, cfg->m_targets);
     }
 
-    const size_t nfl = state_slab_floats(cfg->n_envs, cfg->n_uav, cfg->m_targets, cfg->dim == 3);
-    hipError_t err = dmalloc(&env->slab, nfl);
-    if (err == hipSuccess) err = hipMemset(env->slab, 0, nfl * sizeof(float));
+    hipError_t err = replace(slab_bufs(env));
     if (err == hipSuccess) {
         env->state = state_view(env->slab, cfg->n_envs, cfg->n_uav, cfg->m_targets, cfg->dim == 3);
         err = hipMemcpy(env->state.climb_c, climb, sizeof climb, hipMemcpyHostToDevice);
@@ -468,7 +526,7 @@ int uavtrack_set_pmi_weights(uavtrack_env *env, const float *folded, size_t n_fl
     hipStream_t st = static_cast<hipStream_t>(stream);
     if (!folded) {
         HIP_TRY(hipStreamSynchronize(st));
-        if (env->pmi.blob) (void)hipFree(env->pmi.blob);
+        release(weight_bufs(env->pmi));
         env->pmi = PmiWeights();
         return 0;
     }
@@ -583,25 +641,23 @@ int uavtrack_set_pmi_weights(uavtrack_env *env, const float *folded, size_t n_fl
 
     // ---- device side: a blob of another size is allocated BEFORE the old one goes; the uploads are complete before the
     //      host vectors die and before the new weights are published in the handle
-    float *blob = env->pmi.blob;
-    const bool fresh = env->pmi.n_floats != n_dev || !blob;
+    const bool fresh = env->pmi.n_floats != n_dev || !env->pmi.blob;
+    PmiWeights next;
     HIP_TRY(hipStreamSynchronize(st));          // (launches that still read the current weights)
-    if (fresh) {
-        blob = nullptr;
-        HIP_TRY(dmalloc(&blob, t3_off + t3_len));
-    }
+    if (fresh) HIP_TRY(replace(weight_bufs(next, t3_off + t3_len)));
+    float *blob = fresh ? next.blob : env->pmi.blob;
     hipError_t e = hipMemcpyAsync(blob, packed.data(), n_dev * 4, hipMemcpyHostToDevice, st);
     if (e == hipSuccess && x6_len) e = hipMemcpyAsync(blob + x6_off, planes.data(), x6_len * 4, hipMemcpyHostToDevice, st);
     if (e == hipSuccess && h3_ok) e = hipMemcpyAsync(blob + l1_off, planes1.data(), l1_len * 4, hipMemcpyHostToDevice, st);
     if (e == hipSuccess && h3_ok) e = hipMemcpyAsync(blob + t3_off, planes3t.data(), t3_len * 4, hipMemcpyHostToDevice, st);
     if (e == hipSuccess) e = hipStreamSynchronize(st);
     if (e != hipSuccess) {
-        if (fresh) (void)hipFree(blob);          // (an in-place upload that failed half way cannot be undone: the handle loses its weights)
-        else { (void)hipFree(env->pmi.blob); env->pmi = PmiWeights(); }
+        release(weight_bufs(fresh ? next : env->pmi));    // (an in-place upload that failed half way cannot be undone: the handle loses its weights)
+        if (!fresh) env->pmi = PmiWeights();
         (void)hipGetLastError();
         return fail("uavtrack_set_pmi_weights: upload failed: %s", hipGetErrorString(e));
     }
-    if (fresh && env->pmi.blob) (void)hipFree(env->pmi.blob);
+    if (fresh) release(weight_bufs(env->pmi));
     env->pmi.blob = blob;
     env->pmi.x6 = x6_len ? blob + x6_off : nullptr;
     env->pmi.l1 = h3_ok ? blob + l1_off : nullptr;
@@ -628,11 +684,7 @@ int uavtrack_pmi_inference(uavtrack_env *env, const float *x, int64_t n, float *
     hipStream_t st = static_cast<hipStream_t>(stream);
     if ((size_t)n > env->inf_cap) {
         HIP_TRY(hipStreamSynchronize(st));
-        if (env->inf_obs) (void)hipFree(env->inf_obs);
-        if (env->inf_pairs) (void)hipFree(env->inf_pairs);
-        env->inf_obs = nullptr; env->inf_pairs = nullptr; env->inf_cap = 0;
-        HIP_TRY(dmalloc(&env->inf_obs, (size_t)n * 2 * UAVTRACK_OBS_DIM));
-        HIP_TRY(dmalloc(&env->inf_pairs, (size_t)n));
+        HIP_TRY(replace(inference_bufs(env, (size_t)n)));
         env->inf_cap = (size_t)n;
     }
     // the scorer reads its pair count from the device counter the rollout kernel normally fills (zero between calls)
@@ -827,8 +879,8 @@ int uavtrack_set_actor_weights(uavtrack_env *env, const float *w1, const float *
     hipStream_t st = static_cast<hipStream_t>(stream);
     HIP_TRY(hipStreamSynchronize(st));
     if (!w1) {
-        if (env->actor_w) (void)hipFree(env->actor_w);
-        env->actor_w = nullptr; env->actor_hidden = 0;
+        release(actor_bufs(env));
+        env->actor_hidden = 0;
         return 0;
     }
     if (!b1 || !w2 || !b2) return fail("uavtrack_set_actor_weights: b1, w2 and b2 must not be null");
@@ -848,9 +900,9 @@ int uavtrack_set_actor_weights(uavtrack_env *env, const float *w1, const float *
     const double xb[12] = {1, 1, 2, 2, 1, 1, 1, vr, vr, pos, pos, 1};
     pack_actor_blob(w1, b1, w2, b2, hidden, A, mt, xb, blob.data());
     if (env->actor_hidden != hidden) {
-        if (env->actor_w) (void)hipFree(env->actor_w);
-        env->actor_w = nullptr; env->actor_hidden = 0;
-        HIP_TRY(dmalloc(&env->actor_w, n));
+        release(actor_bufs(env));
+        env->actor_hidden = 0;
+        HIP_TRY(replace(actor_bufs(env, n)));
     }
     HIP_TRY(hipMemcpyAsync(env->actor_w, blob.data(), n * 4, hipMemcpyHostToDevice, st));
     HIP_TRY(hipStreamSynchronize(st));
@@ -1020,74 +1072,177 @@ int uavtrack_kernel_info(uavtrack_env *env, int64_t out[5])
 
 }  // extern "C"
 
-// ---- shared by the two device trainers: their Adam state and refusal words (AdamState, internal.h) -----------------
+// ---- the device-side handles: learner, PMI trainer, replay ring ---------------------------------------------------
+
+struct uavtrack_learner {
+    uavtrack_learner_config cfg;
+    LearnerDevice d;
+};
+
+struct uavtrack_pmi_trainer {
+    uavtrack_pmi_trainer_config cfg;
+    PmiTrainDevice d;
+};
+
+struct uavtrack_replay {
+    uavtrack_replay_config cfg;
+    ReplayDevice d;
+};
 
 namespace {
 
-void adam_free(AdamState &o)
+constexpr int64_t kLearnerDefaultBatch = 65536;
+constexpr int64_t kLearnerMaxBatch = ((int64_t)1 << 31) - 1;   // row numbers are int32 in the priority write
+constexpr int64_t kPmiTrainDefaultBatch = 4096;
+constexpr int64_t kReplayMaxBatch = ((int64_t)1 << 31) - 1;   // draw numbers are Philox counter word 0
+constexpr int64_t kReplayMaxCapacity = (int64_t)kReplayTile * ((int64_t)1 << 30);   // tile numbers are int32
+
+// Each handle's device buffers (device_bufs: all of them, sized from the handle's fields) and the word through which
+// its calls are refused on the device.  The two trainers share the torch.optim.Adam state (AdamState, internal.h).
+Bufs adam_bufs(AdamState &o)
 {
-    for (void *p : {(void *)o.m, (void *)o.v, (void *)o.steps, (void *)o.status, (void *)o.errors})
-        if (p) (void)hipFree(p);
-    o = AdamState();
+    return {buf(o.m, o.P, true), buf(o.v, o.P, true), buf(o.steps, o.tensors, true), buf(o.status, 1, true),
+            buf(o.errors, 1, true)};
 }
 
-// All or nothing: zeroed moments, steps and refusal words for `tensors` tensors of P floats in all, or nothing
-// allocated and the error returned.
-hipError_t adam_alloc(AdamState &o, int tensors, int P)
+Bufs scratch_bufs(LearnerDevice &d, int64_t max_n) { return {buf(d.td, max_n), buf(d.last, max_n)}; }
+
+Bufs device_bufs(LearnerDevice &d)
 {
-    AdamState n;
-    n.tensors = tensors;
-    n.P = P;
-    hipError_t e = dmalloc(&n.m, (size_t)P);
-    if (e == hipSuccess) e = dmalloc(&n.v, (size_t)P);
-    if (e == hipSuccess) e = dmalloc(&n.steps, (size_t)tensors);
-    if (e == hipSuccess) e = dmalloc(&n.status, (size_t)1);
-    if (e == hipSuccess) e = dmalloc(&n.errors, (size_t)1);
-    if (e == hipSuccess) e = hipMemset(n.m, 0, (size_t)P * 4);
-    if (e == hipSuccess) e = hipMemset(n.v, 0, (size_t)P * 4);
-    if (e == hipSuccess) e = hipMemset(n.steps, 0, (size_t)tensors * 8);
-    if (e == hipSuccess) e = hipMemset(n.status, 0, 4);
-    if (e == hipSuccess) e = hipMemset(n.errors, 0, 4);
+    const size_t P = (size_t)d.L.P;
+    return adam_bufs(d.opt) + Bufs{buf(d.params, P, true), buf(d.partials, kLearnerMaxGroups * (P + 4)), buf(d.scal, 2)} +
+           scratch_bufs(d, d.max_n);
+}
+
+Bufs scratch_bufs(PmiTrainDevice &d, int64_t max_b)
+{
+    const size_t H = (size_t)d.L.H, nb = (size_t)max_b;
+    return {buf(d.xh0, 2 * 3 * H * nb), buf(d.a0, 2 * 3 * H * nb), buf(d.da0, 2 * 3 * H * nb), buf(d.xh1, 2 * H * nb),
+            buf(d.a1, 2 * H * nb), buf(d.dz1, 2 * H * nb), buf(d.go, 2 * nb)};
+}
+
+Bufs device_bufs(PmiTrainDevice &d)
+{
+    const size_t S = (size_t)d.L.S, P = (size_t)d.L.P, H = (size_t)d.L.H;
+    return adam_bufs(d.opt) + Bufs{buf(d.state, S, true), buf(d.nbt, kPmiBlocks, true), buf(d.grad, P, true),
+                                   buf(d.inv0, 2 * 3 * H), buf(d.inv1, 2 * H), buf(d.acc, 1)} +
+           scratch_bufs(d, d.max_b);
+}
+
+Bufs device_bufs(ReplayDevice &d)
+{
+    const size_t tiles = (size_t)((d.max_capacity + kReplayTile - 1) / kReplayTile);
+    return {buf(d.prefix, tiles), buf(d.tile_last, tiles), buf(d.counter, 2, true), buf(d.pmin, 1),
+            buf(d.pdraw, (size_t)d.max_batch), buf(d.parts, kReplayMaxParts + 1), buf(d.status, 1, true),
+            buf(d.errors, 1, true)};
+}
+
+int *refusal_word(const LearnerDevice &d) { return d.opt.errors; }
+int *refusal_word(const PmiTrainDevice &d) { return d.opt.errors; }
+int *refusal_word(const ReplayDevice &d) { return d.errors; }
+
+// *_create: the null and struct_size tests, the config's ranges (`check`), the device, then the handle with the fields
+// `init` derives from the config (it may return an error of its own), every buffer of device_bufs() at once, and a
+// device synchronisation.  A failure leaves nothing behind.
+template <typename H, typename Cfg, typename Check, typename Init>
+int create_handle(const char *fn, const Cfg *cfg, H **out, Check check, Init init)
+{
+    if (!cfg || !out) return fail("%s: null argument", fn);
+    *out = nullptr;
+    if (cfg->struct_size != sizeof(Cfg))
+        return fail("%s: struct_size %u != %zu (header / library mismatch)", fn, cfg->struct_size, sizeof(Cfg));
+    if (check(fn, *cfg)) return 1;
+    hipDeviceProp_t prop;
+    if (accept_device(fn, cfg->device_id, &prop)) return 1;
+    ON_DEVICE(cfg->device_id);
+    H *h = new (std::nothrow) H();
+    if (!h) return fail("%s: out of host memory", fn);
+    h->cfg = *cfg;
+    hipError_t e = init(h->d, *cfg);
+    if (e == hipSuccess) e = replace(device_bufs(h->d));
+    if (e == hipSuccess) e = hipDeviceSynchronize();
     if (e != hipSuccess) {
-        adam_free(n);
-        return e;
+        release(device_bufs(h->d));
+        delete h;
+        return fail("%s: %s", fn, hipGetErrorString(e));
     }
-    o = n;
-    return hipSuccess;
+    *out = h;
+    return 0;
 }
 
-// Loads exp_avg, exp_avg_sq [o.P] and step [o.tensors] from the host (the caller has checked the size).  Everything is
-// validated before the first copy, so a refused load leaves the previous state in place.
-int adam_set(const AdamState &o, const char *fn, const float *exp_avg, const float *exp_avg_sq, const int64_t *step,
-             hipStream_t st)
+template <typename H>
+int destroy_handle(H *h)
 {
-    for (int t = 0; t < o.tensors; ++t)
-        if (step[t] < 0) return fail("%s: step[%d] = %lld < 0", fn, t, (long long)step[t]);
-    for (int64_t p = 0; p < o.P; ++p)
-        if (!(exp_avg_sq[p] >= 0.0f)) return fail("%s: exp_avg_sq[%lld] is not >= 0", fn, (long long)p);
-    HIP_TRY(hipStreamSynchronize(st));
-    HIP_TRY(hipMemcpyAsync(o.m, exp_avg, (size_t)o.P * 4, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(o.v, exp_avg_sq, (size_t)o.P * 4, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(o.steps, step, (size_t)o.tensors * 8, hipMemcpyHostToDevice, st));
+    if (!h) return 0;
+    DeviceGuard guard(h->cfg.device_id);
+    (void)hipDeviceSynchronize();
+    release(device_bufs(h->d));
+    delete h;
+    return 0;
+}
+
+// *_reserve: scratch for `max_batch` rows (grow-only; `rows` holds what is reserved), the new set allocated before the
+// old one goes.
+template <typename H, typename D>
+int reserve_scratch(const char *fn, H *h, int64_t max_batch, int64_t limit, int64_t D::*rows)
+{
+    if (!h) return fail("%s: null handle", fn);
+    if (max_batch < 1 || max_batch > limit)
+        return fail("%s: max_batch %lld out of range [1, %lld]", fn, (long long)max_batch, (long long)limit);
+    if (max_batch <= h->d.*rows) return 0;
+    ON_DEVICE(h->cfg.device_id);
+    HIP_TRY(hipDeviceSynchronize());          // in-flight calls may still use the old scratch
+    HIP_TRY(replace(scratch_bufs(h->d, max_batch)));
+    h->d.*rows = max_batch;
+    return 0;
+}
+
+// *_set/get_optimizer_state of a trainer: exp_avg, exp_avg_sq [P] and step [tensors] in from the host (const
+// pointers; everything is validated before the first copy, so a refused load leaves the previous state in place) or
+// out to it.  `has` completes the size message: "<n> floats, <has % P>".
+template <typename H, typename F, typename S>
+int optimizer_state(const char *fn, H *h, F *exp_avg, F *exp_avg_sq, S *step, int64_t n_floats, void *stream,
+                    const char *has)
+{
+    if (!h || !exp_avg || !exp_avg_sq || !step) return fail("%s: null argument", fn);
+    const AdamState &o = h->d.opt;
+    if (n_floats != h->d.L.P) {
+        char what[96];
+        snprintf(what, sizeof what, has, h->d.L.P);
+        return fail("%s: %lld floats, %s", fn, (long long)n_floats, what);
+    }
+    ON_DEVICE(h->cfg.device_id);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if constexpr (std::is_const<F>::value) {
+        for (int t = 0; t < o.tensors; ++t)
+            if (step[t] < 0) return fail("%s: step[%d] = %lld < 0", fn, t, (long long)step[t]);
+        for (int64_t p = 0; p < o.P; ++p)
+            if (!(exp_avg_sq[p] >= 0.0f)) return fail("%s: exp_avg_sq[%lld] is not >= 0", fn, (long long)p);
+        HIP_TRY(hipStreamSynchronize(st));
+        HIP_TRY(hipMemcpyAsync(o.m, exp_avg, (size_t)o.P * 4, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(o.v, exp_avg_sq, (size_t)o.P * 4, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(o.steps, step, (size_t)o.tensors * 8, hipMemcpyHostToDevice, st));
+    } else {
+        HIP_TRY(hipMemcpyAsync(exp_avg, o.m, (size_t)o.P * 4, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(exp_avg_sq, o.v, (size_t)o.P * 4, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(step, o.steps, (size_t)o.tensors * 8, hipMemcpyDeviceToHost, st));
+    }
     HIP_TRY(hipStreamSynchronize(st));
     return 0;
 }
 
-int adam_get(const AdamState &o, float *exp_avg, float *exp_avg_sq, int64_t *step, hipStream_t st)
+// *_check: the calls refused on the device since the last check (`count`, and `refused` when given), the count
+// cleared; synchronises the stream.
+template <typename H>
+int take_refusals(const char *fn, H *h, int64_t *refused, void *stream, int *count)
 {
-    HIP_TRY(hipMemcpyAsync(exp_avg, o.m, (size_t)o.P * 4, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(exp_avg_sq, o.v, (size_t)o.P * 4, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(step, o.steps, (size_t)o.tensors * 8, hipMemcpyDeviceToHost, st));
+    if (!h) return fail("%s: null handle", fn);
+    ON_DEVICE(h->cfg.device_id);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    HIP_TRY(hipMemcpyAsync(count, refusal_word(h->d), 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemsetAsync(refusal_word(h->d), 0, 4, st));
     HIP_TRY(hipStreamSynchronize(st));
-    return 0;
-}
-
-// The calls refused on the device since the last check, and the count cleared; synchronises the stream.
-int take_refusals(const AdamState &o, int *count, hipStream_t st)
-{
-    HIP_TRY(hipMemcpyAsync(count, o.errors, 4, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemsetAsync(o.errors, 0, 4, st));
-    HIP_TRY(hipStreamSynchronize(st));
+    if (refused) *refused = *count;
     return 0;
 }
 
@@ -1095,111 +1250,39 @@ int take_refusals(const AdamState &o, int *count, hipStream_t st)
 
 // ---- the device learner -------------------------------------------------------------------------------------------
 
-struct uavtrack_learner {
-    uavtrack_learner_config cfg;
-    LearnerDevice d;
-};
-
-namespace {
-
-void free_learner_scratch(LearnerDevice &d)
-{
-    if (d.td) (void)hipFree(d.td);
-    if (d.last) (void)hipFree(d.last);
-    d.td = nullptr; d.last = nullptr; d.max_n = 0;
-}
-
-void free_learner(uavtrack_learner *l)
-{
-    LearnerDevice &d = l->d;
-    free_learner_scratch(d);
-    adam_free(d.opt);
-    for (void *p : {(void *)d.params, (void *)d.partials, (void *)d.scal})
-        if (p) (void)hipFree(p);
-}
-
-constexpr int64_t kLearnerDefaultBatch = 65536;
-constexpr int64_t kLearnerMaxBatch = ((int64_t)1 << 31) - 1;   // row numbers are int32 in the priority write
-
-hipError_t learner_scratch(LearnerDevice &d, int64_t max_n)
-{
-    float *td = nullptr;
-    uint8_t *last = nullptr;
-    hipError_t e = dmalloc(&td, (size_t)max_n);
-    if (e == hipSuccess) e = dmalloc(&last, (size_t)max_n);
-    if (e != hipSuccess) {
-        if (td) (void)hipFree(td);
-        return e;
-    }
-    free_learner_scratch(d);
-    d.td = td; d.last = last; d.max_n = max_n;
-    return hipSuccess;
-}
-
-}  // namespace
-
 extern "C" {
 
 int uavtrack_learner_create(const uavtrack_learner_config *cfg, uavtrack_learner **out)
 {
-    if (!cfg || !out) return fail("uavtrack_learner_create: null argument");
-    *out = nullptr;
-    if (cfg->struct_size != sizeof(uavtrack_learner_config))
-        return fail("uavtrack_learner_create: struct_size %u != %zu (header / library mismatch)", cfg->struct_size,
-                    sizeof(uavtrack_learner_config));
-    if (cfg->hidden < 1 || cfg->hidden > kLearnerMaxHidden)
-        return fail("uavtrack_learner_create: hidden %d out of range [1, %d]", cfg->hidden, kLearnerMaxHidden);
-    if (cfg->n_actions < 1 || cfg->n_actions > kLearnerMaxActions)
-        return fail("uavtrack_learner_create: n_actions %d out of range [1, %d]", cfg->n_actions, kLearnerMaxActions);
-    if (cfg->loss != UAVTRACK_LOSS_REFERENCE && cfg->loss != UAVTRACK_LOSS_PER_SAMPLE)
-        return fail("uavtrack_learner_create: unknown loss form %d", cfg->loss);
-    if (cfg->max_batch < 0 || cfg->max_batch > kLearnerMaxBatch)
-        return fail("uavtrack_learner_create: max_batch %lld out of range [0, %lld]", (long long)cfg->max_batch,
-                    (long long)kLearnerMaxBatch);
-    if (!std::isfinite(cfg->gamma) || !std::isfinite(cfg->actor_lr) || !std::isfinite(cfg->critic_lr) ||
-        cfg->actor_lr < 0 || cfg->critic_lr < 0)
-        return fail("uavtrack_learner_create: gamma and the learning rates must be finite, the rates >= 0");
-
-    hipDeviceProp_t prop;
-    if (accept_device("uavtrack_learner_create", cfg->device_id, &prop)) return 1;
-    ON_DEVICE(cfg->device_id);
-
-    uavtrack_learner *l = new (std::nothrow) uavtrack_learner();
-    if (!l) return fail("uavtrack_learner_create: out of host memory");
-    l->cfg = *cfg;
-    LearnerDevice &d = l->d;
-    d.L = LearnerLayout::make(cfg->hidden, cfg->n_actions);
-    d.gamma = (float)cfg->gamma;
-    d.actor_lr = (float)cfg->actor_lr;
-    d.critic_lr = (float)cfg->critic_lr;
-    d.per_sample = cfg->loss == UAVTRACK_LOSS_PER_SAMPLE;
-    const size_t P = (size_t)d.L.P;
-    hipError_t he = adam_alloc(d.opt, kLearnerTensors, d.L.P);
-    if (he == hipSuccess) he = dmalloc(&d.params, P);
-    if (he == hipSuccess) he = dmalloc(&d.partials, (size_t)kLearnerMaxGroups * (P + 4));
-    if (he == hipSuccess) he = dmalloc(&d.scal, (size_t)2);
-    if (he == hipSuccess) he = learner_scratch(d, cfg->max_batch ? cfg->max_batch : kLearnerDefaultBatch);
-    if (he == hipSuccess) he = hipMemset(d.params, 0, P * 4);
-    if (he == hipSuccess) he = learner_prepare_kernels(d.L);
-    if (he == hipSuccess) he = hipDeviceSynchronize();
-    if (he != hipSuccess) {
-        free_learner(l);
-        delete l;
-        return fail("uavtrack_learner_create: %s", hipGetErrorString(he));
-    }
-    *out = l;
-    return 0;
+    auto check = [](const char *fn, const uavtrack_learner_config &c) {
+        if (c.hidden < 1 || c.hidden > kLearnerMaxHidden)
+            return fail("%s: hidden %d out of range [1, %d]", fn, c.hidden, kLearnerMaxHidden);
+        if (c.n_actions < 1 || c.n_actions > kLearnerMaxActions)
+            return fail("%s: n_actions %d out of range [1, %d]", fn, c.n_actions, kLearnerMaxActions);
+        if (c.loss != UAVTRACK_LOSS_REFERENCE && c.loss != UAVTRACK_LOSS_PER_SAMPLE)
+            return fail("%s: unknown loss form %d", fn, c.loss);
+        if (c.max_batch < 0 || c.max_batch > kLearnerMaxBatch)
+            return fail("%s: max_batch %lld out of range [0, %lld]", fn, (long long)c.max_batch, (long long)kLearnerMaxBatch);
+        if (!std::isfinite(c.gamma) || !std::isfinite(c.actor_lr) || !std::isfinite(c.critic_lr) || c.actor_lr < 0 ||
+            c.critic_lr < 0)
+            return fail("%s: gamma and the learning rates must be finite, the rates >= 0", fn);
+        return 0;
+    };
+    auto init = [](LearnerDevice &d, const uavtrack_learner_config &c) {
+        d.L = LearnerLayout::make(c.hidden, c.n_actions);
+        d.gamma = (float)c.gamma;
+        d.actor_lr = (float)c.actor_lr;
+        d.critic_lr = (float)c.critic_lr;
+        d.per_sample = c.loss == UAVTRACK_LOSS_PER_SAMPLE;
+        d.opt.tensors = kLearnerTensors;
+        d.opt.P = d.L.P;
+        d.max_n = c.max_batch ? c.max_batch : kLearnerDefaultBatch;
+        return learner_prepare_kernels(d.L);
+    };
+    return create_handle(__func__, cfg, out, check, init);
 }
 
-int uavtrack_learner_destroy(uavtrack_learner *learner)
-{
-    if (!learner) return 0;
-    DeviceGuard guard(learner->cfg.device_id);
-    (void)hipDeviceSynchronize();
-    free_learner(learner);
-    delete learner;
-    return 0;
-}
+int uavtrack_learner_destroy(uavtrack_learner *learner) { return destroy_handle(learner); }
 
 int uavtrack_learner_num_params(uavtrack_learner *learner, int64_t *out)
 {
@@ -1210,15 +1293,7 @@ int uavtrack_learner_num_params(uavtrack_learner *learner, int64_t *out)
 
 int uavtrack_learner_reserve(uavtrack_learner *learner, int64_t max_batch)
 {
-    if (!learner) return fail("uavtrack_learner_reserve: null handle");
-    if (max_batch < 1 || max_batch > kLearnerMaxBatch)
-        return fail("uavtrack_learner_reserve: max_batch %lld out of range [1, %lld]", (long long)max_batch,
-                    (long long)kLearnerMaxBatch);
-    if (max_batch <= learner->d.max_n) return 0;
-    ON_DEVICE(learner->cfg.device_id);
-    HIP_TRY(hipDeviceSynchronize());          // in-flight updates may still read the old scratch
-    HIP_TRY(learner_scratch(learner->d, max_batch));
-    return 0;
+    return reserve_scratch(__func__, learner, max_batch, kLearnerMaxBatch, &LearnerDevice::max_n);
 }
 
 int uavtrack_learner_set_params(uavtrack_learner *learner, const float *params, int64_t n_floats, void *stream)
@@ -1249,24 +1324,13 @@ int uavtrack_learner_get_params(uavtrack_learner *learner, float *params, int64_
 int uavtrack_learner_set_optimizer_state(uavtrack_learner *learner, const float *exp_avg, const float *exp_avg_sq,
                                          const int64_t *step, int64_t n_floats, void *stream)
 {
-    if (!learner || !exp_avg || !exp_avg_sq || !step) return fail("uavtrack_learner_set_optimizer_state: null argument");
-    if (n_floats != learner->d.L.P)
-        return fail("uavtrack_learner_set_optimizer_state: %lld floats, the networks have %d", (long long)n_floats,
-                    learner->d.L.P);
-    ON_DEVICE(learner->cfg.device_id);
-    return adam_set(learner->d.opt, "uavtrack_learner_set_optimizer_state", exp_avg, exp_avg_sq, step,
-                    static_cast<hipStream_t>(stream));
+    return optimizer_state(__func__, learner, exp_avg, exp_avg_sq, step, n_floats, stream, "the networks have %d");
 }
 
 int uavtrack_learner_get_optimizer_state(uavtrack_learner *learner, float *exp_avg, float *exp_avg_sq, int64_t *step,
                                          int64_t n_floats, void *stream)
 {
-    if (!learner || !exp_avg || !exp_avg_sq || !step) return fail("uavtrack_learner_get_optimizer_state: null argument");
-    if (n_floats != learner->d.L.P)
-        return fail("uavtrack_learner_get_optimizer_state: %lld floats, the networks have %d", (long long)n_floats,
-                    learner->d.L.P);
-    ON_DEVICE(learner->cfg.device_id);
-    return adam_get(learner->d.opt, exp_avg, exp_avg_sq, step, static_cast<hipStream_t>(stream));
+    return optimizer_state(__func__, learner, exp_avg, exp_avg_sq, step, n_floats, stream, "the networks have %d");
 }
 
 int uavtrack_learner_update(uavtrack_learner *learner, int64_t n, const float *states, const int32_t *actions,
@@ -1296,124 +1360,38 @@ int uavtrack_learner_update(uavtrack_learner *learner, int64_t n, const float *s
 
 int uavtrack_learner_check(uavtrack_learner *learner, int64_t *refused, void *stream)
 {
-    if (!learner) return fail("uavtrack_learner_check: null handle");
-    ON_DEVICE(learner->cfg.device_id);
     int count = 0;
-    if (take_refusals(learner->d.opt, &count, static_cast<hipStream_t>(stream))) return 1;
-    if (refused) *refused = count;
+    if (take_refusals(__func__, learner, refused, stream, &count)) return 1;
     if (count)
         return fail("uavtrack_learner_check: %d update(s) refused: an action outside [0, %d) or an index outside "
                     "[0, capacity); they changed nothing", count, learner->d.L.A);
     return 0;
 }
 
-}  // extern "C"
-
 // ---- the device PMI trainer ---------------------------------------------------------------------------------------
-
-struct uavtrack_pmi_trainer {
-    uavtrack_pmi_trainer_config cfg;
-    PmiTrainDevice d;
-};
-
-namespace {
-
-constexpr int64_t kPmiTrainDefaultBatch = 4096;
-
-void free_pmi_scratch(PmiTrainDevice &d)
-{
-    for (void *p : {(void *)d.xh0, (void *)d.a0, (void *)d.da0, (void *)d.xh1, (void *)d.a1, (void *)d.dz1, (void *)d.go})
-        if (p) (void)hipFree(p);
-    d.xh0 = d.a0 = d.da0 = d.xh1 = d.a1 = d.dz1 = d.go = nullptr;
-    d.max_b = 0;
-}
-
-void free_pmi_trainer(uavtrack_pmi_trainer *t)
-{
-    PmiTrainDevice &d = t->d;
-    free_pmi_scratch(d);
-    adam_free(d.opt);
-    for (void *p : {(void *)d.state, (void *)d.nbt, (void *)d.grad, (void *)d.inv0, (void *)d.inv1, (void *)d.acc})
-        if (p) (void)hipFree(p);
-}
-
-hipError_t pmi_scratch(PmiTrainDevice &d, int64_t max_b)
-{
-    const size_t H = (size_t)d.L.H, nb = (size_t)max_b;
-    float *p[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    const size_t n[7] = {2 * 3 * H * nb, 2 * 3 * H * nb, 2 * 3 * H * nb, 2 * H * nb, 2 * H * nb, 2 * H * nb, 2 * nb};
-    hipError_t e = hipSuccess;
-    for (int i = 0; i < 7 && e == hipSuccess; ++i) e = dmalloc(&p[i], n[i]);
-    if (e != hipSuccess) {
-        for (float *q : p)
-            if (q) (void)hipFree(q);
-        return e;
-    }
-    free_pmi_scratch(d);
-    d.xh0 = p[0]; d.a0 = p[1]; d.da0 = p[2]; d.xh1 = p[3]; d.a1 = p[4]; d.dz1 = p[5]; d.go = p[6];
-    d.max_b = max_b;
-    return hipSuccess;
-}
-
-}  // namespace
-
-extern "C" {
 
 int uavtrack_pmi_trainer_create(const uavtrack_pmi_trainer_config *cfg, uavtrack_pmi_trainer **out)
 {
-    if (!cfg || !out) return fail("uavtrack_pmi_trainer_create: null argument");
-    *out = nullptr;
-    if (cfg->struct_size != sizeof(uavtrack_pmi_trainer_config))
-        return fail("uavtrack_pmi_trainer_create: struct_size %u != %zu (header / library mismatch)", cfg->struct_size,
-                    sizeof(uavtrack_pmi_trainer_config));
-    if (cfg->hidden < 1 || cfg->hidden > kPmiMaxHidden)
-        return fail("uavtrack_pmi_trainer_create: hidden %d out of range [1, %d]", cfg->hidden, kPmiMaxHidden);
-    if (cfg->max_batch < 0 || cfg->max_batch > kPmiTrainMaxBatch)
-        return fail("uavtrack_pmi_trainer_create: max_batch %lld out of range [0, %lld]", (long long)cfg->max_batch,
-                    (long long)kPmiTrainMaxBatch);
-    if (!std::isfinite(cfg->lr) || cfg->lr < 0) return fail("uavtrack_pmi_trainer_create: lr must be finite and >= 0");
-
-    hipDeviceProp_t prop;
-    if (accept_device("uavtrack_pmi_trainer_create", cfg->device_id, &prop)) return 1;
-    ON_DEVICE(cfg->device_id);
-
-    uavtrack_pmi_trainer *t = new (std::nothrow) uavtrack_pmi_trainer();
-    if (!t) return fail("uavtrack_pmi_trainer_create: out of host memory");
-    t->cfg = *cfg;
-    PmiTrainDevice &d = t->d;
-    d.L = PmiTrainLayout::make(cfg->hidden);
-    d.lr = (float)cfg->lr;
-    const size_t S = (size_t)d.L.S, P = (size_t)d.L.P, H = (size_t)cfg->hidden;
-    hipError_t he = adam_alloc(d.opt, kPmiTrainTensors, d.L.P);
-    if (he == hipSuccess) he = dmalloc(&d.state, S);
-    if (he == hipSuccess) he = dmalloc(&d.nbt, (size_t)kPmiBlocks);
-    if (he == hipSuccess) he = dmalloc(&d.grad, P);
-    if (he == hipSuccess) he = dmalloc(&d.inv0, 2 * 3 * H);
-    if (he == hipSuccess) he = dmalloc(&d.inv1, 2 * H);
-    if (he == hipSuccess) he = dmalloc(&d.acc, (size_t)1);
-    if (he == hipSuccess) he = pmi_scratch(d, cfg->max_batch ? cfg->max_batch : kPmiTrainDefaultBatch);
-    if (he == hipSuccess) he = hipMemset(d.state, 0, S * 4);
-    if (he == hipSuccess) he = hipMemset(d.nbt, 0, kPmiBlocks * 8);
-    if (he == hipSuccess) he = hipMemset(d.grad, 0, P * 4);
-    if (he == hipSuccess) he = hipDeviceSynchronize();
-    if (he != hipSuccess) {
-        free_pmi_trainer(t);
-        delete t;
-        return fail("uavtrack_pmi_trainer_create: %s", hipGetErrorString(he));
-    }
-    *out = t;
-    return 0;
+    auto check = [](const char *fn, const uavtrack_pmi_trainer_config &c) {
+        if (c.hidden < 1 || c.hidden > kPmiMaxHidden)
+            return fail("%s: hidden %d out of range [1, %d]", fn, c.hidden, kPmiMaxHidden);
+        if (c.max_batch < 0 || c.max_batch > kPmiTrainMaxBatch)
+            return fail("%s: max_batch %lld out of range [0, %lld]", fn, (long long)c.max_batch, (long long)kPmiTrainMaxBatch);
+        if (!std::isfinite(c.lr) || c.lr < 0) return fail("%s: lr must be finite and >= 0", fn);
+        return 0;
+    };
+    auto init = [](PmiTrainDevice &d, const uavtrack_pmi_trainer_config &c) {
+        d.L = PmiTrainLayout::make(c.hidden);
+        d.lr = (float)c.lr;
+        d.opt.tensors = kPmiTrainTensors;
+        d.opt.P = d.L.P;
+        d.max_b = c.max_batch ? c.max_batch : kPmiTrainDefaultBatch;
+        return hipSuccess;
+    };
+    return create_handle(__func__, cfg, out, check, init);
 }
 
-int uavtrack_pmi_trainer_destroy(uavtrack_pmi_trainer *trainer)
-{
-    if (!trainer) return 0;
-    DeviceGuard guard(trainer->cfg.device_id);
-    (void)hipDeviceSynchronize();
-    free_pmi_trainer(trainer);
-    delete trainer;
-    return 0;
-}
+int uavtrack_pmi_trainer_destroy(uavtrack_pmi_trainer *trainer) { return destroy_handle(trainer); }
 
 int uavtrack_pmi_trainer_num_params(uavtrack_pmi_trainer *trainer, int64_t *n_state, int64_t *n_train)
 {
@@ -1425,15 +1403,7 @@ int uavtrack_pmi_trainer_num_params(uavtrack_pmi_trainer *trainer, int64_t *n_st
 
 int uavtrack_pmi_trainer_reserve(uavtrack_pmi_trainer *trainer, int64_t max_batch)
 {
-    if (!trainer) return fail("uavtrack_pmi_trainer_reserve: null handle");
-    if (max_batch < 1 || max_batch > kPmiTrainMaxBatch)
-        return fail("uavtrack_pmi_trainer_reserve: max_batch %lld out of range [1, %lld]", (long long)max_batch,
-                    (long long)kPmiTrainMaxBatch);
-    if (max_batch <= trainer->d.max_b) return 0;
-    ON_DEVICE(trainer->cfg.device_id);
-    HIP_TRY(hipDeviceSynchronize());          // in-flight calls may still use the old scratch
-    HIP_TRY(pmi_scratch(trainer->d, max_batch));
-    return 0;
+    return reserve_scratch(__func__, trainer, max_batch, kPmiTrainMaxBatch, &PmiTrainDevice::max_b);
 }
 
 int uavtrack_pmi_trainer_set_params(uavtrack_pmi_trainer *trainer, const float *state, const int64_t *num_batches_tracked,
@@ -1474,24 +1444,13 @@ int uavtrack_pmi_trainer_get_params(uavtrack_pmi_trainer *trainer, float *state,
 int uavtrack_pmi_trainer_set_optimizer_state(uavtrack_pmi_trainer *trainer, const float *exp_avg, const float *exp_avg_sq,
                                              const int64_t *step, int64_t n_train, void *stream)
 {
-    if (!trainer || !exp_avg || !exp_avg_sq || !step) return fail("uavtrack_pmi_trainer_set_optimizer_state: null argument");
-    if (n_train != trainer->d.L.P)
-        return fail("uavtrack_pmi_trainer_set_optimizer_state: %lld floats, the network has %d trainable", (long long)n_train,
-                    trainer->d.L.P);
-    ON_DEVICE(trainer->cfg.device_id);
-    return adam_set(trainer->d.opt, "uavtrack_pmi_trainer_set_optimizer_state", exp_avg, exp_avg_sq, step,
-                    static_cast<hipStream_t>(stream));
+    return optimizer_state(__func__, trainer, exp_avg, exp_avg_sq, step, n_train, stream, "the network has %d trainable");
 }
 
 int uavtrack_pmi_trainer_get_optimizer_state(uavtrack_pmi_trainer *trainer, float *exp_avg, float *exp_avg_sq,
                                              int64_t *step, int64_t n_train, void *stream)
 {
-    if (!trainer || !exp_avg || !exp_avg_sq || !step) return fail("uavtrack_pmi_trainer_get_optimizer_state: null argument");
-    if (n_train != trainer->d.L.P)
-        return fail("uavtrack_pmi_trainer_get_optimizer_state: %lld floats, the network has %d trainable", (long long)n_train,
-                    trainer->d.L.P);
-    ON_DEVICE(trainer->cfg.device_id);
-    return adam_get(trainer->d.opt, exp_avg, exp_avg_sq, step, static_cast<hipStream_t>(stream));
+    return optimizer_state(__func__, trainer, exp_avg, exp_avg_sq, step, n_train, stream, "the network has %d trainable");
 }
 
 int uavtrack_pmi_trainer_train(uavtrack_pmi_trainer *trainer, const float *rows, int64_t n_rows, int64_t n_uav,
@@ -1525,11 +1484,8 @@ int uavtrack_pmi_trainer_train(uavtrack_pmi_trainer *trainer, const float *rows,
 
 int uavtrack_pmi_trainer_check(uavtrack_pmi_trainer *trainer, int64_t *refused, void *stream)
 {
-    if (!trainer) return fail("uavtrack_pmi_trainer_check: null handle");
-    ON_DEVICE(trainer->cfg.device_id);
     int count = 0;
-    if (take_refusals(trainer->d.opt, &count, static_cast<hipStream_t>(stream))) return 1;
-    if (refused) *refused = count;
+    if (take_refusals(__func__, trainer, refused, stream, &count)) return 1;
     if (count)
         return fail("uavtrack_pmi_trainer_check: %d train call(s) refused: a timestep index outside [0, T) or a uav index "
                     "outside [0, n_uav); they changed nothing", count);
@@ -1540,23 +1496,7 @@ int uavtrack_pmi_trainer_check(uavtrack_pmi_trainer *trainer, int64_t *refused, 
 
 // ---- the prioritised replay ring ----------------------------------------------------------------------------------
 
-struct uavtrack_replay {
-    uavtrack_replay_config cfg;
-    ReplayDevice d;
-};
-
 namespace {
-
-void free_replay(ReplayDevice &d)
-{
-    for (void *p : {(void *)d.prefix, (void *)d.tile_last, (void *)d.counter, (void *)d.pmin, (void *)d.pdraw,
-                    (void *)d.parts, (void *)d.status, (void *)d.errors})
-        if (p) (void)hipFree(p);
-    d = ReplayDevice();
-}
-
-constexpr int64_t kReplayMaxBatch = ((int64_t)1 << 31) - 1;   // draw numbers are Philox counter word 0
-constexpr int64_t kReplayMaxCapacity = (int64_t)kReplayTile * ((int64_t)1 << 30);   // tile numbers are int32
 
 bool aligned16(const void *p) { return ((uintptr_t)p & 15) == 0; }
 
@@ -1593,61 +1533,25 @@ extern "C" {
 
 int uavtrack_replay_create(const uavtrack_replay_config *cfg, uavtrack_replay **out)
 {
-    if (!cfg || !out) return fail("uavtrack_replay_create: null argument");
-    *out = nullptr;
-    if (cfg->struct_size != sizeof(uavtrack_replay_config))
-        return fail("uavtrack_replay_create: struct_size %u != %zu (header / library mismatch)", cfg->struct_size,
-                    sizeof(uavtrack_replay_config));
-    if (cfg->max_capacity < 1 || cfg->max_capacity > kReplayMaxCapacity)
-        return fail("uavtrack_replay_create: max_capacity %lld out of range [1, %lld]", (long long)cfg->max_capacity,
-                    (long long)kReplayMaxCapacity);
-    if (cfg->max_batch < 1 || cfg->max_batch > kReplayMaxBatch)
-        return fail("uavtrack_replay_create: max_batch %lld out of range [1, %lld]", (long long)cfg->max_batch,
-                    (long long)kReplayMaxBatch);
-
-    hipDeviceProp_t prop;
-    if (accept_device("uavtrack_replay_create", cfg->device_id, &prop)) return 1;
-    ON_DEVICE(cfg->device_id);
-
-    uavtrack_replay *r = new (std::nothrow) uavtrack_replay();
-    if (!r) return fail("uavtrack_replay_create: out of host memory");
-    r->cfg = *cfg;
-    ReplayDevice &d = r->d;
-    d.max_capacity = cfg->max_capacity;
-    d.max_batch = cfg->max_batch;
-    d.k0 = (uint32_t)cfg->seed;
-    d.k1 = (uint32_t)(cfg->seed >> 32);
-    const size_t tiles = (size_t)((cfg->max_capacity + kReplayTile - 1) / kReplayTile);
-    hipError_t he = dmalloc(&d.prefix, tiles);
-    if (he == hipSuccess) he = dmalloc(&d.tile_last, tiles);
-    if (he == hipSuccess) he = dmalloc(&d.counter, (size_t)2);
-    if (he == hipSuccess) he = dmalloc(&d.pmin, (size_t)1);
-    if (he == hipSuccess) he = dmalloc(&d.pdraw, (size_t)cfg->max_batch);
-    if (he == hipSuccess) he = dmalloc(&d.parts, (size_t)kReplayMaxParts + 1);
-    if (he == hipSuccess) he = dmalloc(&d.status, (size_t)1);
-    if (he == hipSuccess) he = dmalloc(&d.errors, (size_t)1);
-    if (he == hipSuccess) he = hipMemset(d.counter, 0, 16);
-    if (he == hipSuccess) he = hipMemset(d.status, 0, 4);
-    if (he == hipSuccess) he = hipMemset(d.errors, 0, 4);
-    if (he == hipSuccess) he = hipDeviceSynchronize();
-    if (he != hipSuccess) {
-        free_replay(d);
-        delete r;
-        return fail("uavtrack_replay_create: %s", hipGetErrorString(he));
-    }
-    *out = r;
-    return 0;
+    auto check = [](const char *fn, const uavtrack_replay_config &c) {
+        if (c.max_capacity < 1 || c.max_capacity > kReplayMaxCapacity)
+            return fail("%s: max_capacity %lld out of range [1, %lld]", fn, (long long)c.max_capacity,
+                        (long long)kReplayMaxCapacity);
+        if (c.max_batch < 1 || c.max_batch > kReplayMaxBatch)
+            return fail("%s: max_batch %lld out of range [1, %lld]", fn, (long long)c.max_batch, (long long)kReplayMaxBatch);
+        return 0;
+    };
+    auto init = [](ReplayDevice &d, const uavtrack_replay_config &c) {
+        d.max_capacity = c.max_capacity;
+        d.max_batch = c.max_batch;
+        d.k0 = (uint32_t)c.seed;
+        d.k1 = (uint32_t)(c.seed >> 32);
+        return hipSuccess;
+    };
+    return create_handle(__func__, cfg, out, check, init);
 }
 
-int uavtrack_replay_destroy(uavtrack_replay *replay)
-{
-    if (!replay) return 0;
-    DeviceGuard guard(replay->cfg.device_id);
-    (void)hipDeviceSynchronize();
-    free_replay(replay->d);
-    delete replay;
-    return 0;
-}
+int uavtrack_replay_destroy(uavtrack_replay *replay) { return destroy_handle(replay); }
 
 int uavtrack_replay_add(uavtrack_replay *replay, const uavtrack_replay_ring *ring, int64_t n, const float *states,
                         const int32_t *actions, const float *rewards, const float *next_states, void *stream)
@@ -1704,14 +1608,8 @@ int uavtrack_replay_sample(uavtrack_replay *replay, const uavtrack_replay_ring *
 
 int uavtrack_replay_check(uavtrack_replay *replay, int64_t *refused, void *stream)
 {
-    if (!replay) return fail("uavtrack_replay_check: null handle");
-    ON_DEVICE(replay->cfg.device_id);
-    hipStream_t st = static_cast<hipStream_t>(stream);
     int count = 0;
-    HIP_TRY(hipMemcpyAsync(&count, replay->d.errors, 4, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemsetAsync(replay->d.errors, 0, 4, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    if (refused) *refused = count;
+    if (take_refusals(__func__, replay, refused, stream, &count)) return 1;
     if (count)
         return fail("uavtrack_replay_check: %d sample call(s) refused: a priority in [0, count) is NaN, infinite or "
                     "negative, or all of them are zero; their indices are slot 0", count);

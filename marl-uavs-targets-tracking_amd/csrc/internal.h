@@ -230,8 +230,8 @@ hipError_t launch_reset(const uavtrack_env *env, uint64_t seed, uint32_t episode
                         hipStream_t stream);
 
 // What both device trainers (uavtrack_learner_*, uavtrack_pmi_trainer_*) keep the same way: the torch.optim.Adam state
-// of their trainable tensors and the words through which a call is refused on the device.  api.hip allocates, loads,
-// reads and frees it (adam_alloc / adam_set / adam_get / adam_free / take_refusals).
+// of their trainable tensors and the words through which a call is refused on the device.  api.hip owns its buffers
+// (adam_bufs), loads and reads it (optimizer_state) and takes the refusals (take_refusals).
 struct AdamState {
     int tensors = 0, P = 0;         // trainable tensors, their floats
     float *m = nullptr, *v = nullptr;   // [P] exp_avg, exp_avg_sq

@@ -175,3 +175,8 @@ def check(rc: int, what: str = "") -> None:
 def ptr(t):
     """A tensor's device address as a void * argument (None for NULL)."""
     return None if t is None else C.c_void_p(t.data_ptr())
+
+
+def host_ptr(a):
+    """A numpy array's address as a void * argument."""
+    return a.ctypes.data_as(C.c_void_p)

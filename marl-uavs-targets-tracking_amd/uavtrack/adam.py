@@ -9,6 +9,9 @@ from typing import List, Sequence, Tuple
 import numpy as np
 import torch
 
+from . import _lib
+from ._lib import host_ptr
+
 
 def flat(tensors) -> np.ndarray:
     """The tensors' values concatenated in order: one contiguous float32 array."""
@@ -54,3 +57,17 @@ def from_state_dict(params: Sequence[torch.Tensor], lr: float, sd: dict) -> Tupl
             ms.append(torch.zeros_like(p))
             vs.append(torch.zeros_like(p))
     return flat(ms), flat(vs), steps
+
+
+def read(get, h, n_floats: int, tensors: int, stream) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """(exp_avg [n_floats], exp_avg_sq [n_floats], step [tensors]) as numpy arrays, through `get`, a
+    uavtrack_*_get_optimizer_state symbol of handle `h`."""
+    m, v, steps = np.empty(n_floats, np.float32), np.empty(n_floats, np.float32), np.empty(tensors, np.int64)
+    _lib.check(get(h, host_ptr(m), host_ptr(v), host_ptr(steps), n_floats, stream), get.__name__)
+    return m, v, steps
+
+
+def write(set_, h, exp_avg: np.ndarray, exp_avg_sq: np.ndarray, step: np.ndarray, stream) -> None:
+    """read's inverse through `set_`, a uavtrack_*_set_optimizer_state symbol: contiguous float32 moments and int64
+    steps."""
+    _lib.check(set_(h, host_ptr(exp_avg), host_ptr(exp_avg_sq), host_ptr(step), exp_avg.size, stream), set_.__name__)

@@ -12,13 +12,14 @@ import torch
 from . import _lib
 from .config import EnvConfig, RewardMode
 from .pmi import fold_pmi_state_dict
+from ._handle import Handle
 from ._lib import ptr as _ptr
 from .pmi_trainer import DevicePMINetwork
 
 _STATE_KEYS = ("ux", "uy", "uz", "uh", "ua", "tx", "ty", "tz", "th")
 
 
-class BatchedUavEnv:
+class BatchedUavEnv(Handle):
     """B independent copies of the reference `Environment` (src/environment.py:12) on one GPU.
 
     reset(seed)            -> obs [B, N, 12]                           (environment.py:87-118)
@@ -32,13 +33,9 @@ class BatchedUavEnv:
         self.device = torch.device(device)
         if self.device.type != "cuda":
             raise RuntimeError("uavtrack runs on an MI355X only (device must be cuda:N); there is no CPU path")
-        self._lib = _lib.load()
         idx = self.device.index if self.device.index is not None else 0
         self._device_index = idx
-        cstruct = cfg.c_struct(idx)
-        handle = C.c_void_p()
-        _lib.check(self._lib.uavtrack_create(C.byref(cstruct), C.byref(handle)), "uavtrack_create")
-        self._h = handle
+        self._create(cfg.c_struct(idx))
         self.info: Dict[str, torch.Tensor] = {}
         self._episode = 0
         self._trace: Optional[torch.Tensor] = None    # the installed target-trace buffer (kept alive: the library holds its raw pointer)
@@ -53,9 +50,6 @@ class BatchedUavEnv:
     def N(self) -> int: return self.cfg.n_uav
     @property
     def M(self) -> int: return self.cfg.m_targets
-
-    def _stream(self):
-        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
 
     def _empty(self, shape, dtype):
         return torch.empty(shape, dtype=dtype, device=self.device)
@@ -88,16 +82,6 @@ class BatchedUavEnv:
             raise ValueError(f"actions shape {tuple(a.shape)} != {tuple(shape)}")
         return a.contiguous()
 
-    def close(self):
-        if getattr(self, "_h", None) is not None and self._h.value:
-            self._lib.uavtrack_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def kernel_info(self) -> Dict[str, int]:
         out = (C.c_int64 * 5)()

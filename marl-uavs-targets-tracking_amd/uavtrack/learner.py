@@ -18,7 +18,9 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import ptr as _ptr
+from . import adam
+from ._handle import Handle, current_device
+from ._lib import host_ptr, ptr as _ptr
 from .adam import flat, from_state_dict, split, to_state_dict
 from .replay import DeviceReplayBuffer, PrioritizedDeviceReplayBuffer
 from .replay_ring import PrioritizedReplayRing
@@ -38,9 +40,10 @@ class ValueMLP(torch.nn.Module):
         return self.fc2(torch.relu(self.fc1(x))).squeeze(1)
 
 
-class DeviceActorCritic:
+class DeviceActorCritic(Handle):
     """ActorCritic(state_dim, hidden_dim, action_dim, actor_lr, critic_lr, gamma, device) with the update on the GPU.
     Initial weights are torch.nn.Linear's defaults drawn from torch's global generator, like the reference's."""
+    _prefix = "uavtrack_learner_"
 
     def __init__(self, state_dim: int = 12, hidden_dim: int = 128, action_dim: int = 12, actor_lr: float = 1e-4,
                  critic_lr: float = 5e-4, gamma: float = 0.95, device="cuda:0", loss: str = "reference",
@@ -49,52 +52,30 @@ class DeviceActorCritic:
             raise ValueError(f"state_dim must be {_lib.OBS_DIM} (the environment's observation), got {state_dim}")
         if loss not in _lib.LOSS_FORMS:
             raise ValueError(f"loss must be one of {_lib.LOSS_FORMS}, got {loss!r}")
-        self.device = torch.device(device)
-        if self.device.index is None:
-            self.device = torch.device("cuda", torch.cuda.current_device())
+        self.device = current_device(device)
         self.hidden_dim, self.action_dim, self.gamma, self.loss = int(hidden_dim), int(action_dim), float(gamma), loss
         self.actor_lr, self.critic_lr = float(actor_lr), float(critic_lr)
         # host-side modules: the reference's layouts, default initialisation, and the format of state dicts
         self._actor = ActorMLP(state_dim, self.hidden_dim, self.action_dim)
         self._critic = ValueMLP(state_dim, self.hidden_dim)
-        self._lib = _lib.load()
-        cfg = _lib.LearnerConfig(struct_size=C.sizeof(_lib.LearnerConfig), device_id=self.device.index,
-                                 hidden=self.hidden_dim, n_actions=self.action_dim, loss=_lib.LOSS_FORMS.index(loss),
-                                 pad_=0, max_batch=int(max_batch), gamma=self.gamma, actor_lr=self.actor_lr,
-                                 critic_lr=self.critic_lr)
-        h = C.c_void_p()
-        _lib.check(self._lib.uavtrack_learner_create(C.byref(cfg), C.byref(h)), "uavtrack_learner_create")
-        self._h = h
+        self._create(_lib.LearnerConfig(device_id=self.device.index, hidden=self.hidden_dim, n_actions=self.action_dim,
+                                        loss=_lib.LOSS_FORMS.index(loss), pad_=0, max_batch=int(max_batch),
+                                        gamma=self.gamma, actor_lr=self.actor_lr, critic_lr=self.critic_lr))
         n = C.c_int64()
         _lib.check(self._lib.uavtrack_learner_num_params(self._h, C.byref(n)), "uavtrack_learner_num_params")
         self.num_params = n.value
         self._set_params(flat(self._params()))
 
-    # ---- handle plumbing
-    def close(self) -> None:
-        if getattr(self, "_h", None):
-            self._lib.uavtrack_learner_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def _stream(self):
-        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-
     def _params(self):
         return list(self._actor.parameters()) + list(self._critic.parameters())
 
     def _set_params(self, flat: np.ndarray) -> None:
-        _lib.check(self._lib.uavtrack_learner_set_params(self._h, flat.ctypes.data_as(C.c_void_p), flat.size,
+        _lib.check(self._lib.uavtrack_learner_set_params(self._h, host_ptr(flat), flat.size,
                                                          self._stream()), "uavtrack_learner_set_params")
 
     def _get_params(self) -> np.ndarray:
         flat = np.empty(self.num_params, np.float32)
-        _lib.check(self._lib.uavtrack_learner_get_params(self._h, flat.ctypes.data_as(C.c_void_p), flat.size,
+        _lib.check(self._lib.uavtrack_learner_get_params(self._h, host_ptr(flat), flat.size,
                                                          self._stream()), "uavtrack_learner_get_params")
         return flat
 
@@ -105,7 +86,7 @@ class DeviceActorCritic:
     def check(self) -> None:
         """Synchronises; raises if an update since the last check was refused on the device (an action outside
         [0, action_dim) or an index outside the ring), which then changed nothing."""
-        _lib.check(self._lib.uavtrack_learner_check(self._h, None, self._stream()), "uavtrack_learner_check")
+        self._check()
 
     # ---- the update
     def _run(self, n: int, store: Dict[str, torch.Tensor], capacity: int, idx: Optional[torch.Tensor],
@@ -171,13 +152,8 @@ class DeviceActorCritic:
 
     def _optim_state(self):
         """(exp_avg [P], exp_avg_sq [P], step [8]) as numpy arrays: the actor's parameters, then the critic's."""
-        P = self.num_params
-        m, v = np.empty(P, np.float32), np.empty(P, np.float32)
-        steps = np.empty(_lib.LEARNER_TENSORS, np.int64)
-        _lib.check(self._lib.uavtrack_learner_get_optimizer_state(
-            self._h, m.ctypes.data_as(C.c_void_p), v.ctypes.data_as(C.c_void_p), steps.ctypes.data_as(C.c_void_p),
-            P, self._stream()), "uavtrack_learner_get_optimizer_state")
-        return m, v, steps
+        return adam.read(self._lib.uavtrack_learner_get_optimizer_state, self._h, self.num_params,
+                         _lib.LEARNER_TENSORS, self._stream())
 
     def _optimizers(self):
         """(parameters, lr, float span, tensor span) of the actor's and the critic's Adam in the flat state."""
@@ -196,9 +172,7 @@ class DeviceActorCritic:
         for (params, lr, f, t), sd in zip(self._optimizers(), (actor_sd, critic_sd)):
             if sd is not None:
                 m[f], v[f], steps[t] = from_state_dict(params, lr, sd)
-        _lib.check(self._lib.uavtrack_learner_set_optimizer_state(
-            self._h, m.ctypes.data_as(C.c_void_p), v.ctypes.data_as(C.c_void_p), steps.ctypes.data_as(C.c_void_p),
-            self.num_params, self._stream()), "uavtrack_learner_set_optimizer_state")
+        adam.write(self._lib.uavtrack_learner_set_optimizer_state, self._h, m, v, steps, self._stream())
 
     def _load_module(self, actor_sd: Optional[dict], critic_sd: Optional[dict]) -> None:
         cur = split(self._get_params(), self._params())

@@ -18,57 +18,35 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import ptr as _ptr
+from . import adam
+from ._handle import Handle, current_device
+from ._lib import host_ptr, ptr as _ptr
 from .adam import flat, from_state_dict, to_state_dict
 from .pmi import fold_pmi_state_dict, make_pmi_net
 
 _BN = ("bn_comm", "bn_obs", "bn_boundary_state", "bn1")
 
 
-def _vp(a: np.ndarray):
-    return a.ctypes.data_as(C.c_void_p)
-
-
-class DevicePMINetwork:
+class DevicePMINetwork(Handle):
     """PMINetwork(hidden_dim=hidden_dim, b2_size=b2_size) with train_pmi on the GPU.  Initial weights are
     torch.nn.Linear's defaults drawn from torch's global generator in the reference's layer order, so under the same
     seed they are the reference's; the learning rate defaults to the reference's Adam(lr=0.001) (PMINet.py:39)."""
+    _prefix = "uavtrack_pmi_trainer_"
 
     def __init__(self, hidden_dim: int = 64, b2_size: int = 3000, device="cuda:0", lr: float = 1e-3,
                  max_batch: int = 0):
-        self.device = torch.device(device)
-        if self.device.index is None:
-            self.device = torch.device("cuda", torch.cuda.current_device())
+        self.device = current_device(device)
         self.hidden_dim, self.b2_size, self.lr = int(hidden_dim), int(b2_size), float(lr)
         if not 1 <= self.hidden_dim <= 256:
             raise ValueError(f"hidden_dim must be in [1, 256], got {hidden_dim}")
         self._net = make_pmi_net(self.hidden_dim)      # host-side module: layout, initialisation, state_dict format
-        self._lib = _lib.load()
-        cfg = _lib.PmiTrainerConfig(struct_size=C.sizeof(_lib.PmiTrainerConfig), device_id=self.device.index,
-                                    hidden=self.hidden_dim, pad_=0, max_batch=int(max_batch), lr=self.lr)
-        h = C.c_void_p()
-        _lib.check(self._lib.uavtrack_pmi_trainer_create(C.byref(cfg), C.byref(h)), "uavtrack_pmi_trainer_create")
-        self._h = h
+        self._create(_lib.PmiTrainerConfig(device_id=self.device.index, hidden=self.hidden_dim, pad_=0,
+                                           max_batch=int(max_batch), lr=self.lr))
         ns, nt = C.c_int64(), C.c_int64()
         _lib.check(self._lib.uavtrack_pmi_trainer_num_params(self._h, C.byref(ns), C.byref(nt)),
                    "uavtrack_pmi_trainer_num_params")
         self.num_state, self.num_params = ns.value, nt.value
         self.load_state_dict(self._net.state_dict())
-
-    # ---- handle plumbing
-    def close(self) -> None:
-        if getattr(self, "_h", None):
-            self._lib.uavtrack_pmi_trainer_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def _stream(self):
-        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
 
     def reserve(self, max_batch: int) -> None:
         """Scratch for mini-batches of up to max_batch rows (a larger batch_size is an error; the default is 4096)."""
@@ -77,7 +55,7 @@ class DevicePMINetwork:
     def check(self) -> None:
         """Synchronises; raises if a train call since the last check was refused on the device (an index out of
         range), which then changed nothing."""
-        _lib.check(self._lib.uavtrack_pmi_trainer_check(self._h, None, self._stream()), "uavtrack_pmi_trainer_check")
+        self._check()
 
     # ---- training
     def train_indices(self, rows: torch.Tensor, n_uav: int, t_idx: torch.Tensor, u_idx: torch.Tensor,
@@ -132,7 +110,7 @@ class DevicePMINetwork:
     def _get(self):
         st = np.empty(self.num_state, np.float32)
         nbt = np.empty(_lib.PMI_BN_LAYERS, np.int64)
-        _lib.check(self._lib.uavtrack_pmi_trainer_get_params(self._h, _vp(st), _vp(nbt), st.size, self._stream()),
+        _lib.check(self._lib.uavtrack_pmi_trainer_get_params(self._h, host_ptr(st), host_ptr(nbt), st.size, self._stream()),
                    "uavtrack_pmi_trainer_get_params")
         return st, nbt
 
@@ -155,18 +133,13 @@ class DevicePMINetwork:
         items = probe.state_dict()
         st = flat(v for k, v in items.items() if not k.endswith("num_batches_tracked"))
         nbt = np.array([int(items[b + ".num_batches_tracked"]) for b in _BN], np.int64)
-        _lib.check(self._lib.uavtrack_pmi_trainer_set_params(self._h, _vp(st), _vp(nbt), st.size, self._stream()),
+        _lib.check(self._lib.uavtrack_pmi_trainer_set_params(self._h, host_ptr(st), host_ptr(nbt), st.size, self._stream()),
                    "uavtrack_pmi_trainer_set_params")
 
     def optimizer_state(self):
         """(exp_avg [P], exp_avg_sq [P], step [18]) as numpy arrays, parameters() order."""
-        P = self.num_params
-        m, v = np.empty(P, np.float32), np.empty(P, np.float32)
-        steps = np.empty(_lib.PMI_TRAIN_TENSORS, np.int64)
-        _lib.check(self._lib.uavtrack_pmi_trainer_get_optimizer_state(self._h, _vp(m), _vp(v), _vp(steps), P,
-                                                                      self._stream()),
-                   "uavtrack_pmi_trainer_get_optimizer_state")
-        return m, v, steps
+        return adam.read(self._lib.uavtrack_pmi_trainer_get_optimizer_state, self._h, self.num_params,
+                         _lib.PMI_TRAIN_TENSORS, self._stream())
 
     def optimizer_state_dict(self) -> dict:
         """torch.optim.Adam(PMINetwork.parameters(), lr).state_dict() of this trainer, built by torch itself."""
@@ -176,9 +149,7 @@ class DevicePMINetwork:
         """optimizer.load_state_dict: a torch.optim.Adam state_dict over PMINetwork.parameters().  (The learning rate
         stays the one this trainer was built with.)"""
         mf, vf, steps = from_state_dict(make_pmi_net(self.hidden_dim).parameters(), self.lr, sd)
-        _lib.check(self._lib.uavtrack_pmi_trainer_set_optimizer_state(self._h, _vp(mf), _vp(vf), _vp(steps),
-                                                                      self.num_params, self._stream()),
-                   "uavtrack_pmi_trainer_set_optimizer_state")
+        adam.write(self._lib.uavtrack_pmi_trainer_set_optimizer_state, self._h, mf, vf, steps, self._stream())
 
     def save(self, save_dir: str, epoch_i) -> None:
         """PMINetwork.save (PMINet.py:102-106): <save_dir>/pmi/pmi_weights_<epoch>.pth holding

@@ -17,12 +17,14 @@ from typing import Dict, Optional, Tuple
 import torch
 
 from . import _lib
+from ._handle import Handle, current_device
 from ._lib import ptr as _ptr
 from .replay import KEYS
 
 
-class PrioritizedReplayRing:
+class PrioritizedReplayRing(Handle):
     """PrioritizedReplayBuffer(capacity, alpha) (train.py:73-139) as a device ring with HIP add and sampling."""
+    _prefix = "uavtrack_replay_"
 
     def __init__(self, capacity: int, device, alpha: float = 0.6, seed: int = 0, max_batch: int = 65536,
                  obs_dim: int = _lib.OBS_DIM):
@@ -31,9 +33,7 @@ class PrioritizedReplayRing:
         if not alpha > 0:
             raise ValueError(f"alpha must be > 0, got {alpha}")
         self.capacity = int(capacity)
-        self.device = torch.device(device)
-        if self.device.index is None:
-            self.device = torch.device("cuda", torch.cuda.current_device())
+        self.device = current_device(device)
         self.alpha, self.seed, self.max_batch = float(alpha), int(seed), int(max_batch)
         self.store = {"states": torch.empty(self.capacity, obs_dim, device=self.device),
                       "actions": torch.empty(self.capacity, dtype=torch.int32, device=self.device),
@@ -42,28 +42,9 @@ class PrioritizedReplayRing:
         self.priorities = torch.zeros(self.capacity, device=self.device)
         self.pos = 0          # next slot to write
         self.count = 0        # valid transitions
-        self._lib = _lib.load()
-        cfg = _lib.ReplayConfig(struct_size=C.sizeof(_lib.ReplayConfig), device_id=self.device.index,
-                                max_capacity=self.capacity, max_batch=self.max_batch, seed=self.seed & (2**64 - 1))
-        h = C.c_void_p()
-        _lib.check(self._lib.uavtrack_replay_create(C.byref(cfg), C.byref(h)), "uavtrack_replay_create")
-        self._h = h
+        self._create(_lib.ReplayConfig(device_id=self.device.index, max_capacity=self.capacity, max_batch=self.max_batch,
+                                       seed=self.seed & (2**64 - 1)))
         self._idx = torch.empty(self.max_batch, dtype=torch.int64, device=self.device)   # update_from's draws
-
-    # ---- handle plumbing
-    def close(self) -> None:
-        if getattr(self, "_h", None):
-            self._lib.uavtrack_replay_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def _stream(self):
-        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
 
     def _ring(self) -> _lib.ReplayRing:
         s = self.store
@@ -82,7 +63,7 @@ class PrioritizedReplayRing:
     def check(self) -> None:
         """Synchronises; raises if a draw since the last check was refused on the device (a NaN, infinite or negative
         priority in [0, count), or all of them zero).  A refused draw returned slot 0 and NaN weights."""
-        _lib.check(self._lib.uavtrack_replay_check(self._h, None, self._stream()), "uavtrack_replay_check")
+        self._check()
 
     # ---- add (train.py:87-96)
     def add(self, transition_dict: Dict[str, torch.Tensor]) -> None:

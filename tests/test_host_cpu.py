@@ -73,6 +73,20 @@ def test_null_handle_calls_return_errors():
     assert lib.uavtrack_step(None, None, None, None, None, None, None, None) != 0
     assert b"null handle" in lib.uavtrack_last_error()
     assert lib.uavtrack_destroy(None) == 0
+    # every handle-taking symbol: NULL handle, NULL / zero arguments -> an error naming the symbol (destroy: a no-op)
+    walked = 0
+    for name, (_, args) in _lib.SIGNATURES.items():
+        if not args or args[0] is not C.c_void_p:
+            continue
+        rc = getattr(lib, name)(*[0 if a in (C.c_int32, C.c_int64, C.c_uint64, C.c_uint32, C.c_size_t, C.c_double)
+                                  else None for a in args])
+        if name.endswith("_destroy"):
+            assert rc == 0, name
+        else:
+            assert rc != 0, name
+            assert lib.uavtrack_last_error().decode().startswith(name + ": "), (name, lib.uavtrack_last_error())
+        walked += 1
+    assert walked == sum(1 for _, a in _lib.SIGNATURES.values() if a and a[0] is C.c_void_p) >= 50
 
 
 def test_reference_dict_adapter():
