@@ -30,7 +30,8 @@
 // ReLU is the v_med3_f32 that also caps a value at the f16 range (an observation next to the origin can be arbitrarily
 // large, uav.py:165; saturation instead of inf/NaN), so remainders are non-negative and need no clamp of their own.
 //
-// Device weight blob (uavtrack_set_actor_weights packs it): 128 header floats { [0] 1 / (T1 T2), [16 .. 16 + 32 AT) b2 },
+// Device weight blob (uavtrack_set_actor_weights packs it): 128 header floats { [0] 1 / (T1 T2), [1] softmax guard on,
+// [16 .. 16 + 32 AT) b2 },
 // then per tile a of 32 hidden units 2 + 4 AT fragments of 64 lanes x 8 f16 (16 B per lane, lane-major):
 //   W1 hi, W1 lo        lane l, element j: T1 * W1[32 a + l % 32][k = 8 (l >> 5) + j]   (k = 12: b1, k > 12: 0)
 //   per action tile t (AT = 1: the reference's 12 actions; AT = 2: the 3-D action space, up to 48) and half h = 0, 1:
@@ -59,6 +60,9 @@ constexpr int actor_tiles(bool z3) { return z3 ? 2 : 1; }
 constexpr int actor_slots(int at) { return at == 1 ? 12 : 48; }
 constexpr int actor_frags_per_tile(int at) { return 2 + 4 * at; }      // W1 hi, lo; per action tile W2 (half 0, 1) x (hi, lo)
 
+constexpr float kActorCap = 60000.0f;       // inside f16's 65504 with room for the toward-zero conversion
+constexpr int kActorScaleExp = 60;     // block scales T1, T2 in [2^-60, 2^60] (pack_actor_blob)
+
 inline int actor_blocks(int hidden) { return (hidden + 31) / 32; }     // 32-unit tiles of the hidden layer
 inline size_t actor_blob_floats(int hidden, int at)
 {
@@ -85,15 +89,26 @@ inline void pack_actor_blob(const float *w1, const float *b1, const float *w2, c
         act = std::fmax(act, a);
     }
     for (size_t k = 0; k < (size_t)A * H; ++k) w2max = std::fmax(w2max, std::fabs((double)w2[k]));
-    auto pow2_below = [](double bound, double target) {         // largest 2^e with 2^e * bound <= target, e in [-24, 24]
+    // largest 2^e with 2^e * bound <= target, e in [-kActorScaleExp, kActorScaleExp]: wide enough that a network whose
+    // layers are rescaled against each other (W1, b1 x 2^j, W2 x 2^-j: the same policy) keeps both scales unclamped --
+    // with 2^+-24, T1 T2 ~ 2^20 left W1 x 2^-40 clamped at 2^24 and subnormal in f16 -- while 1 / (T1 T2) stays a normal float
+    auto pow2_below = [](double bound, double target) {
         int e = 24;
         if (bound > 0.0 && std::isfinite(bound)) e = (int)std::floor(std::log2(target / bound));
-        return std::ldexp(1.0, e < -24 ? -24 : (e > 24 ? 24 : e));
+        return std::ldexp(1.0, e < -kActorScaleExp ? -kActorScaleExp : (e > kActorScaleExp ? kActorScaleExp : e));
     };
     const double T1 = std::fmin(pow2_below(act, 512.0), pow2_below(w1max, 16384.0));
     const double T2 = pow2_below(w2max, 16384.0);
     memset(blob, 0, actor_blob_floats(H, at) * sizeof(float));
     blob[0] = (float)(1.0 / (T1 * T2));
+    // [1] != 0: a logit may reach 2^28 (hidden values saturate at 60000 / T1), where the softmax needs its guard (actor_pick)
+    double lmax = 0.0;
+    for (int q = 0; q < A; ++q) {
+        double l = std::fabs((double)b2[q]);
+        for (int u = 0; u < H; ++u) l += std::fabs((double)w2[(size_t)q * H + u]) * (kActorCap / T1);
+        lmax = std::fmax(lmax, l);
+    }
+    blob[1] = !(lmax < 268435456.0) ? 1.0f : 0.0f;
     for (int q = 0; q < A; ++q) blob[kActorB2Offset + q] = b2[q];
     uint16_t *frag = reinterpret_cast<uint16_t *>(blob + kActorHeaderFloats);
     auto put = [&](int a, int f, int lane, int j, double v) {                  // hi into fragment f, lo into f + 1
@@ -171,7 +186,6 @@ __device__ __forceinline__ void actor_static_for_impl(std::integer_sequence<int,
 template <int N, class F>
 __device__ __forceinline__ void actor_static_for(F &&f) { actor_static_for_impl(std::make_integer_sequence<int, N>{}, f); }
 
-constexpr float kActorCap = 60000.0f;       // inside f16's 65504 with room for the toward-zero conversion
 
 // EVERY lane of the wavefront must reach this call together (MFMA and the lane swaps ignore EXEC); lanes without a UAV
 // pass zeros and ignore the result.  weights: the blob; HT = actor_blocks(hidden).
@@ -365,6 +379,20 @@ __device__ __forceinline__ int actor_pick(const float (&o)[kActorObs], const flo
     for (int q = 0; q < SLOTS; ++q) {
         ex[q] = __builtin_amdgcn_exp2f(fmaf(lg[q], 1.44269504088896340736f, mneg));   // masked slots: exp2(-inf) = 0
         S += ex[q];
+    }
+    // The max slot's exponent is the rounding residue of m log2 e, up to half its ulp either way: past |m| ~ 2^30 exp2 of it
+    // overflows or underflows (S = inf or 0: NaN probabilities, every draw the last action).  Such a row is redone with the
+    // exponents shifted by their own maximum; no other row takes the branch or changes a bit.
+    if (weights[1] != 0.0f && !(S > 0.0f && S < INFINITY)) {        // (uniform: only weights that can get there test S)
+        float am = -INFINITY;
+#pragma unroll
+        for (int q = 0; q < SLOTS; ++q) am = fmaxf(am, fmaf(lg[q], 1.44269504088896340736f, mneg));
+        S = 0.0f;
+#pragma unroll
+        for (int q = 0; q < SLOTS; ++q) {
+            ex[q] = __builtin_amdgcn_exp2f(fmaf(lg[q], 1.44269504088896340736f, mneg) - am);
+            S += ex[q];
+        }
     }
     if (WANT_PROBS && probs) {
         const float inv = __builtin_amdgcn_rcpf(S);

@@ -70,6 +70,8 @@ class BatchedRollout:
         self._ep_ring: Optional[torch.Tensor] = None                   # fuse_chunks: one row of episode sums per chunk of a run()
         self._ep_used = 0
         self._bound: Dict[int, Callable] = {}
+        self._bound_key = None                                         # (stream handle, seed) the bound calls were built under
+        self._graph_seed = None
         self._chunk_ready = False
 
     # one closed-loop step on the current stream; everything stays on the device
@@ -116,6 +118,11 @@ class BatchedRollout:
         """Advance `steps` closed-loop steps; returns the episode accumulators so far."""
         done = 0
         if self.fuse_chunks:
+            # a bound call froze the stream current when it was built and the seed: another stream or seed rebuilds them
+            key = (self.env._stream().value, self.seed)
+            if key != self._bound_key:
+                self._bound.clear()
+                self._bound_key = key
             self._ep_used = 0
             while steps - done >= self.k:
                 self._fused_chunk(self.k)
@@ -127,8 +134,9 @@ class BatchedRollout:
                 self._ep_used = 0
             return {"ep_sums": self.ep, "obs": self.obs, "reward": self.last_reward}
         if self.use_graph and steps >= self.k:
-            if self._graph is None:
+            if self._graph is None or self._graph_seed != self.seed:      # (the captured launches hold the seed)
                 self._capture()
+                self._graph_seed = self.seed
             while steps - done >= self.k:
                 self._graph.replay()
                 done += self.k
