@@ -6,11 +6,13 @@ Environment.step, push the N*200 transitions into the replay buffer, sample, one
 (src/models/actor_critic.py:150-178: TD(0) target r + gamma*V(s'), actor loss -log pi(a|s) * delta, critic MSE).
 Here one iteration = B episodes at once: the whole rollout (actor + environment, B x N x T agent-steps) is ONE
 launch of the library (uavtrack_run_actor), its [T,B,N] outputs go straight into a device replay ring, the
-update is the same rule on a sampled batch, and the new actor weights are re-uploaded (sync_actor).
+update is the same rule on a sampled batch, and the new actor weights are re-uploaded (sync_actor), or, with
+--publish device, packed into the rollout's actor on the device with no host copy and no synchronisation.
 
     python examples/train_maac.py --envs 1024 --iters 40
     python examples/train_maac.py --method maac-r --envs 1024 --iters 40     # reciprocal (PMI) reward, PMI net trained too
     python examples/train_maac.py --replay prioritized --learner device --envs 4096 --n-uav 20   # prioritised ring, 32.8 M slots
+    python examples/train_maac.py --replay prioritized --learner device --publish device --log-every 10   # no host sync per iteration
 
 --method maac-r is the paper's method (configs/MAAC-R.yaml): the reward of every step is mixed in-kernel with the
 neighbours' rewards, weighted by the PMI network's scores (uav.py:262-291); that network is trained alongside on
@@ -55,7 +57,9 @@ def update(actor, critic, opt_a, opt_c, batch, gamma):
     return float(actor_loss.detach()), float(critic_loss.detach())
 
 
-def main(argv=None):
+def main(argv=None, timings=None):
+    """Returns the episode return of every iteration.  timings (a list, optional) receives (iterations done, perf_counter)
+    at every printed line, each taken after a synchronisation."""
     ap = argparse.ArgumentParser()
     ap.add_argument("--envs", type=int, default=1024)
     ap.add_argument("--n-uav", type=int, default=10)        # configs/MAAC.yaml: 10 UAVs, 10 targets
@@ -89,7 +93,16 @@ def main(argv=None):
                          "from the rollout and drawn from in HIP, |td_delta| written back as the new priorities")
     ap.add_argument("--alpha", type=float, default=0.6, help="--replay prioritized: priority exponent (train.py:74)")
     ap.add_argument("--beta", type=float, default=0.4, help="--replay prioritized: importance exponent (train.py:100)")
+    ap.add_argument("--publish", choices=["host", "device"], default="host",
+                    help="host: the learner's actor weights reach the rollout through the host pack (sync_actor); device: "
+                         "packed on the device from the learner's parameters (publish_actor), no copy, no synchronisation")
+    ap.add_argument("--log-every", type=int, default=1,
+                    help="print (and so synchronise) every N iterations and after the last; the iteration time printed is "
+                         "the mean over the iterations since the previous line, and with N > 1 the rollout time of a "
+                         "line includes the work still queued from the iterations before it")
     args = ap.parse_args(argv)
+    if args.log_every < 1:
+        ap.error("--log-every must be >= 1")
 
     dev = "cuda:0"
     torch.manual_seed(args.seed)
@@ -124,7 +137,10 @@ def main(argv=None):
         replay = uavtrack.DeviceReplayBuffer(capacity=2 * per_iter, device=dev)
     history = []
     out = None
+    t_log = time.perf_counter()
+    stamps = []
     for it in range(args.iters):
+        log = (it + 1) % args.log_every == 0 or it == args.iters - 1
         t0 = time.perf_counter()
         rollout.seed = args.seed + it
         rollout.reset(seed=1000 + it)
@@ -135,7 +151,8 @@ def main(argv=None):
             replay.add_rollout(obs_in, res)                           # one library call, straight from the outputs
         else:
             replay.add(uavtrack.transitions_from_rollout(obs_in, res))
-        torch.cuda.synchronize()
+        if log:
+            torch.cuda.synchronize()
         t_roll = time.perf_counter() - t0
         if learner is None and args.replay == "prioritized":          # train.py:250-262
             for _ in range(args.updates):
@@ -150,8 +167,9 @@ def main(argv=None):
         else:
             for _ in range(args.updates):
                 la_t, lc_t, _ = learner.update_from(replay, args.batch)
-            la, lc = float(la_t), float(lc_t)
-            actor.load_state_dict(learner.actor_state_dict())     # the rollout's actor: host pack, as sync_actor
+            la, lc = (float(la_t), float(lc_t)) if log else (la_t, lc_t)
+            if args.publish == "host":
+                actor.load_state_dict(learner.actor_state_dict())     # the rollout's actor: host pack, as sync_actor
         lp = float("nan")
         if pmi is not None:                                           # PMINetwork.train_pmi on this rollout's observations
             pmi.train()
@@ -164,17 +182,31 @@ def main(argv=None):
         elif pmi_dev is not None:                                     # the same call, one library call on the device
             lp = pmi_dev.train_pmi({"pmi": {"batch_size": args.pmi_batch}}, res["obs"], args.n_uav)
             env.set_pmi(pmi_dev)
-        rollout.sync_actor()                                          # new weights for the next rollout
+        if args.publish == "host":
+            rollout.sync_actor()                                      # new weights for the next rollout
+        elif learner is not None:
+            learner.publish_actor(env)                                # packed on the device: no copy, no synchronisation
+        else:
+            rollout.publish_actor()                                   # the CUDA ActorMLP, packed on the device
         ep = res["ep_sums"]                                           # [B, 5]: sum_t mean_i reward, 3 terms, covered
+        history.append(ep[:, 0].mean())                               # (a device scalar: read once, at the end)
+        if not log:
+            continue
         ret, cov = float(ep[:, 0].mean()), float(ep[:, 4].mean()) / args.steps
-        history.append(ret)
         torch.cuda.synchronize()
+        now = time.perf_counter()
+        n_iter = it + 1 - (stamps[-1][0] if stamps else 0)           # iterations since the previous line
+        stamps.append((it + 1, now))
         print(f"iter {it:3d}  episode return {ret:8.3f}  covered targets/step {cov:5.2f}  actor loss {la:+.4f}  "
               f"critic loss {lc:.4f}  pmi loss {lp:.4f}  rollout {t_roll * 1e3:6.1f} ms ({per_iter / t_roll / 1e9:.2f} G agent-steps/s)  "
-              f"iteration {(time.perf_counter() - t0) * 1e3:6.1f} ms", flush=True)
+              f"iteration {((now - t0) if args.log_every == 1 else (now - t_log) / n_iter) * 1e3:6.1f} ms", flush=True)
+        t_log = now
     if args.replay == "prioritized":
         replay.check()                                                # no draw was refused on the device
     env.close()
+    history = [float(r) for r in history]
+    if timings is not None:
+        timings.extend(stamps)
     return history
 
 

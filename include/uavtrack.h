@@ -241,6 +241,22 @@ enum { UAVTRACK_ACTOR_SAMPLE = 0,   /* Categorical(probs).sample(): inverse CDF 
 int uavtrack_set_actor_weights(uavtrack_env *env, const float *w1, const float *b1,
                                const float *w2, const float *b2, int32_t hidden, void *stream);
 
+/* The same upload from DEVICE pointers (fp32, the torch layouts above), without the host: the blob is packed on the
+ * device, bitwise identical to what uavtrack_set_actor_weights packs from the same weights (up to the one case named
+ * in csrc/actor_pack_kernel.hip: a scale ratio within an ulp or two of a power of two, where the host's and the
+ * device's log2 may floor apart).  Stream-ordered: no synchronisation, no allocation, capturable into a graph; the
+ * weights are read when the launches execute on `stream`, not when this is called.  The handle must already hold an
+ * actor of the same `hidden` (uavtrack_set_actor_weights sizes the blob).  Returns an error, enqueuing nothing and
+ * leaving the installed weights in place, for a null pointer, no actor installed, `hidden` other than the installed
+ * width, or na*nc beyond what the device actor holds. */
+int uavtrack_publish_actor_weights(uavtrack_env *env, const float *w1, const float *b1,
+                                   const float *w2, const float *b2, int32_t hidden, void *stream);
+
+/* Inspection aid: copies the installed actor blob (csrc/actor.h layout) to a HOST buffer of n_floats floats, which
+ * must equal the blob's size (128 + ceil(hidden / 32) * (2 + 4 AT) * 256, AT = 1 in 2-D, 2 in 3-D).  Synchronises
+ * `stream`.  Fails if no actor is installed. */
+int uavtrack_get_actor_blob(uavtrack_env *env, float *host, int64_t n_floats, void *stream);
+
 /* take_action for every UAV: obs [B][N][12] (what get_local_state returned, i.e. the obs output of the
  * previous step / reset) -> actions [B][N] int32, and, if probs != NULL, the policy's probabilities
  * probs [B][N][na*nc].  Draws: Philox4x32-10 keyed by seed, counter (env_offset + b, step_count[b] >> 2,
@@ -375,6 +391,13 @@ int uavtrack_learner_reserve(uavtrack_learner *learner, int64_t max_batch);
  * set leaves the previous parameters in place. */
 int uavtrack_learner_set_params(uavtrack_learner *learner, const float *params, int64_t n_floats, void *stream);
 int uavtrack_learner_get_params(uavtrack_learner *learner, float *params, int64_t n_floats, void *stream);
+
+/* uavtrack_publish_actor_weights from the learner's own parameters (the actor's four tensors at the head of the blob
+ * above) into `env`'s rollout actor: stream-ordered, no synchronisation, no allocation, capturable; the parameters are
+ * read when the launches execute, so a graph replayed after updates publishes the weights of that moment.  Refused,
+ * with nothing enqueued, if the two handles sit on different devices, or if hidden or n_actions differ from the
+ * installed actor's width or from env's na*nc. */
+int uavtrack_learner_publish_actor(uavtrack_learner *learner, uavtrack_env *env, void *stream);
 
 /* actor_optimizer / critic_optimizer .load_state_dict (actor_critic.py:199, 204) / state_dict (actor_critic.py:185,
  * 189): exp_avg and exp_avg_sq as HOST blobs in parameter order, step [8] = the Adam step count of each parameter

@@ -70,7 +70,20 @@ inline size_t actor_blob_floats(int hidden, int at)
 }
 
 // hidden unit held by accumulator register r of a lane in half-wavefront kh (32x32 MFMA C/D layout)
-inline int actor_unit_of(int r, int kh) { return (r & 3) + 8 * (r >> 2) + 4 * kh; }
+__host__ __device__ inline int actor_unit_of(int r, int kh) { return (r & 3) + 8 * (r >> 2) + 4 * kh; }
+
+// largest 2^e with 2^e * bound <= target, e in [-kActorScaleExp, kActorScaleExp]: wide enough that a network whose
+// layers are rescaled against each other (W1, b1 x 2^j, W2 x 2^-j: the same policy) keeps both scales unclamped --
+// with 2^+-24, T1 T2 ~ 2^20 left W1 x 2^-40 clamped at 2^24 and subnormal in f16 -- while 1 / (T1 T2) stays a normal float.
+// A bound that is 0 or not finite gives 2^24.  Shared by pack_actor_blob and its device restatement
+// (actor_pack_kernel.hip): the formula is one text, but log2 is the host's libm there and the device's math library here,
+// so at a ratio within an ulp or two of a power of two the two may floor to neighbouring exponents.
+__host__ __device__ inline double actor_pow2_below(double bound, double target)
+{
+    int e = 24;
+    if (bound > 0.0 && __builtin_isfinite(bound)) e = (int)floor(log2(target / bound));
+    return ldexp(1.0, e < -kActorScaleExp ? -kActorScaleExp : (e > kActorScaleExp ? kActorScaleExp : e));
+}
 
 // Host side: torch layouts (w1 [H][12], b1 [H], w2 [A][H], b2 [A]) -> the blob above.  xb[12]: nominal bounds of |obs_k|
 // (they size T1; a value beyond them saturates at 60000 / T1 inside the kernel instead of overflowing).
@@ -89,16 +102,9 @@ inline void pack_actor_blob(const float *w1, const float *b1, const float *w2, c
         act = std::fmax(act, a);
     }
     for (size_t k = 0; k < (size_t)A * H; ++k) w2max = std::fmax(w2max, std::fabs((double)w2[k]));
-    // largest 2^e with 2^e * bound <= target, e in [-kActorScaleExp, kActorScaleExp]: wide enough that a network whose
-    // layers are rescaled against each other (W1, b1 x 2^j, W2 x 2^-j: the same policy) keeps both scales unclamped --
-    // with 2^+-24, T1 T2 ~ 2^20 left W1 x 2^-40 clamped at 2^24 and subnormal in f16 -- while 1 / (T1 T2) stays a normal float
-    auto pow2_below = [](double bound, double target) {
-        int e = 24;
-        if (bound > 0.0 && std::isfinite(bound)) e = (int)std::floor(std::log2(target / bound));
-        return std::ldexp(1.0, e < -kActorScaleExp ? -kActorScaleExp : (e > kActorScaleExp ? kActorScaleExp : e));
-    };
-    const double T1 = std::fmin(pow2_below(act, 512.0), pow2_below(w1max, 16384.0));
-    const double T2 = pow2_below(w2max, 16384.0);
+    // block scales (actor_pow2_below)
+    const double T1 = std::fmin(actor_pow2_below(act, 512.0), actor_pow2_below(w1max, 16384.0));
+    const double T2 = actor_pow2_below(w2max, 16384.0);
     memset(blob, 0, actor_blob_floats(H, at) * sizeof(float));
     blob[0] = (float)(1.0 / (T1 * T2));
     // [1] != 0: a logit may reach 2^28 (hidden values saturate at 60000 / T1), where the softmax needs its guard (actor_pick)
@@ -139,6 +145,26 @@ inline void pack_actor_blob(const float *w1, const float *b1, const float *w2, c
                     }
             }
         }
+}
+
+// put()'s two halves of one fragment entry as one word (hi in the low half, lo in the high half), for the device restatement
+// of pack_actor_blob (actor_pack_kernel.hip): s = (float)(T w), hi = f16(s), lo = f16(s - hi), each rounded to nearest.
+// IEEE arithmetic fixes every finite and infinite result bit for bit; which NaN comes out it leaves to the machine, so the
+// host's (x86-64) are spelled out here: a NaN weight passes every conversion and the subtraction as itself, quieted (f16:
+// its sign, 0x7E00 and the top payload bits), and the inf - inf of an infinite s is x86's default NaN, negative (0xFE00).
+__host__ __device__ inline uint32_t actor_split_word(double T, float w)
+{
+    if (__builtin_isnan(w)) {
+        const uint32_t b = __builtin_bit_cast(uint32_t, w);
+        const uint32_t h = ((b >> 16) & 0x8000u) | 0x7E00u | ((b >> 13) & 0x3FFu);
+        return h | (h << 16);
+    }
+    const float s = (float)(T * (double)w);
+    const _Float16 hi = (_Float16)s;
+    const uint32_t bh = __builtin_bit_cast(uint16_t, hi);
+    if (__builtin_isinf(s)) return bh | (0xFE00u << 16);
+    const _Float16 lo = (_Float16)(s - (float)hi);
+    return bh | ((uint32_t)__builtin_bit_cast(uint16_t, lo) << 16);
 }
 
 struct ActorRng {          // Philox block cache of one UAV (see the draw below)

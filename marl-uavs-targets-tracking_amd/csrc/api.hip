@@ -189,7 +189,18 @@ Bufs inference_bufs(uavtrack_env *env, size_t n = 0)
     return {buf(env->inf_obs, n * 2 * UAVTRACK_OBS_DIM), buf(env->inf_pairs, n)};
 }
 
-Bufs actor_bufs(uavtrack_env *env, size_t floats = 0) { return {buf(env->actor_w, floats)}; }
+// the blob, and the fp64 scratch of a device publish (uavtrack_publish_actor_weights) next to it
+Bufs actor_bufs(uavtrack_env *env, size_t floats = 0) { return {buf(env->actor_w, floats), buf(env->actor_scales, 2)}; }
+
+// nominal bounds of the observation entries (uav.py:156-197: normalised offsets and action differences within [-1, 1],
+// heading terms within +-2 / +-(1 + v_t / v_u), positions / dc taken up to four field lengths): they size the block
+// scale of the hidden layer, which keeps a factor 128 of headroom above them and saturates beyond that
+void actor_obs_bounds(const uavtrack_config &c, double xb[UAVTRACK_OBS_DIM])
+{
+    const double vr = 1.0 + c.t_v_max / c.u_v_max, pos = 4.0 * std::fmax(c.x_max, c.y_max) / c.dc;
+    const double b[UAVTRACK_OBS_DIM] = {1, 1, 2, 2, 1, 1, 1, vr, vr, pos, pos, 1};
+    for (int k = 0; k < UAVTRACK_OBS_DIM; ++k) xb[k] = b[k];
+}
 
 Bufs weight_bufs(PmiWeights &w, size_t floats = 0) { return {buf(w.blob, floats)}; }
 
@@ -892,12 +903,8 @@ int uavtrack_set_actor_weights(uavtrack_env *env, const float *w1, const float *
     if (hidden < 1 || hidden > 4096) return fail("uavtrack_set_actor_weights: hidden %d out of range [1, 4096]", hidden);
     const size_t n = actor_blob_floats(hidden, mt);
     std::vector<float> blob(n, 0.0f);
-    // nominal bounds of the observation entries (uav.py:156-197: normalised offsets and action differences within [-1, 1],
-    // heading terms within +-2 / +-(1 + v_t / v_u), positions / dc taken up to four field lengths): they size the block
-    // scale of the hidden layer, which keeps a factor 128 of headroom above them and saturates beyond that
-    const uavtrack_config &c = env->cfg;
-    const double vr = 1.0 + c.t_v_max / c.u_v_max, pos = 4.0 * std::fmax(c.x_max, c.y_max) / c.dc;
-    const double xb[12] = {1, 1, 2, 2, 1, 1, 1, vr, vr, pos, pos, 1};
+    double xb[UAVTRACK_OBS_DIM];
+    actor_obs_bounds(env->cfg, xb);
     pack_actor_blob(w1, b1, w2, b2, hidden, A, mt, xb, blob.data());
     if (env->actor_hidden != hidden) {
         release(actor_bufs(env));
@@ -907,6 +914,52 @@ int uavtrack_set_actor_weights(uavtrack_env *env, const float *w1, const float *
     HIP_TRY(hipMemcpyAsync(env->actor_w, blob.data(), n * 4, hipMemcpyHostToDevice, st));
     HIP_TRY(hipStreamSynchronize(st));
     env->actor_hidden = hidden;
+    return 0;
+}
+
+// The device pack behind uavtrack_publish_actor_weights and uavtrack_learner_publish_actor (the caller has tested the
+// handle and the pointers): refused, with nothing enqueued, unless an actor of the same width is installed.
+static int publish_actor(const char *fn, uavtrack_env *env, const float *w1, const float *b1, const float *w2,
+                         const float *b2, int32_t hidden, int32_t n_actions, void *stream)
+{
+    if (!env->actor_w) return fail("%s: no actor installed: uavtrack_set_actor_weights sizes the blob first", fn);
+    if (hidden != env->actor_hidden)
+        return fail("%s: hidden %d, the installed actor has %d (only uavtrack_set_actor_weights changes the width)", fn,
+                    hidden, env->actor_hidden);
+    const int A = env->cfg.na * env->cfg.nc, at = actor_tiles(env->cfg.dim == 3);
+    if (n_actions != A) return fail("%s: %d actions, the environment has na*nc = %d", fn, n_actions, A);
+    if (A > actor_slots(at)) return fail("%s: na*nc = %d actions; the device actor holds up to %d", fn, A, actor_slots(at));
+    ON_DEVICE(env->cfg.device_id);
+    ActorPackArgs a;
+    a.w1 = w1; a.b1 = b1; a.w2 = w2; a.b2 = b2;
+    a.H = hidden; a.A = A; a.at = at;
+    actor_obs_bounds(env->cfg, a.xb);
+    a.blob = env->actor_w;
+    a.scales = env->actor_scales;
+    HIP_TRY(launch_actor_pack(a, static_cast<hipStream_t>(stream)));
+    return 0;
+}
+
+int uavtrack_publish_actor_weights(uavtrack_env *env, const float *w1, const float *b1, const float *w2, const float *b2,
+                                   int32_t hidden, void *stream)
+{
+    if (!env) return fail("uavtrack_publish_actor_weights: null handle");
+    if (!w1 || !b1 || !w2 || !b2) return fail("uavtrack_publish_actor_weights: w1, b1, w2 and b2 must not be null");
+    return publish_actor(__func__, env, w1, b1, w2, b2, hidden, env->cfg.na * env->cfg.nc, stream);
+}
+
+int uavtrack_get_actor_blob(uavtrack_env *env, float *host, int64_t n_floats, void *stream)
+{
+    if (!env) return fail("uavtrack_get_actor_blob: null handle");
+    if (!host) return fail("uavtrack_get_actor_blob: host is null");
+    if (!env->actor_w) return fail("uavtrack_get_actor_blob: no actor installed (uavtrack_set_actor_weights)");
+    const size_t n = actor_blob_floats(env->actor_hidden, actor_tiles(env->cfg.dim == 3));
+    if (n_floats != (int64_t)n)
+        return fail("uavtrack_get_actor_blob: %lld floats, the installed blob has %zu", (long long)n_floats, n);
+    ON_DEVICE(env->cfg.device_id);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    HIP_TRY(hipMemcpyAsync(host, env->actor_w, n * 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
     return 0;
 }
 
@@ -1319,6 +1372,17 @@ int uavtrack_learner_get_params(uavtrack_learner *learner, float *params, int64_
     HIP_TRY(hipMemcpyAsync(params, learner->d.params, (size_t)n_floats * 4, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     return 0;
+}
+
+int uavtrack_learner_publish_actor(uavtrack_learner *learner, uavtrack_env *env, void *stream)
+{
+    if (!learner || !env) return fail("uavtrack_learner_publish_actor: null handle");
+    if (learner->cfg.device_id != env->cfg.device_id)
+        return fail("uavtrack_learner_publish_actor: the learner is on device %d, the environment on device %d",
+                    learner->cfg.device_id, env->cfg.device_id);
+    const LearnerLayout &L = learner->d.L;
+    const float *p = learner->d.params;
+    return publish_actor(__func__, env, p + L.a_w1, p + L.a_b1, p + L.a_w2, p + L.a_b2, L.H, L.A, stream);
 }
 
 int uavtrack_learner_set_optimizer_state(uavtrack_learner *learner, const float *exp_avg, const float *exp_avg_sq,

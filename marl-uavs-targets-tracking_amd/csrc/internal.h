@@ -155,6 +155,7 @@ struct uavtrack_env {
     int32_t pmi_scheme = 0;      // uavtrack_set_pmi_scheme: UAVTRACK_PMI_AUTO or a pinned scorer
     unsigned *pmi_flags = nullptr;   // device [2]: the f16 scorer's range flag, chunks re-scored by the wide-range kernel
     float *actor_w = nullptr;    // device blob of uavtrack_set_actor_weights (actor.h layout)
+    double *actor_scales = nullptr;   // device [2]: T1, T2 between the two launches of a device publish (actor_pack_kernel.hip)
     int32_t actor_hidden = 0;
     // MAAC-R scratch for `pmi_steps_cap` steps of deferred scoring (rewards never feed back into the
     // dynamics, so a chunk of steps is simulated first and all its pairs are scored in one launch):
@@ -224,6 +225,17 @@ hipError_t launch_ep_reward(const uavtrack_env *env, int steps, const float *rsu
 hipError_t launch_greedy(const uavtrack_env *env, uint64_t seed, int32_t *actions, hipStream_t stream);
 hipError_t launch_actor(const uavtrack_env *env, const float *obs, uint64_t seed, int mode, int32_t *actions,
                         float *probs, hipStream_t stream);
+
+// actor_pack_kernel.hip -- pack_actor_blob (actor.h) restated on the device: fp32 DEVICE weights in torch layouts -> the
+// actor blob, two stream-ordered launches.  `scales` holds the block scales T1, T2 (fp64) between the two.
+struct ActorPackArgs {
+    const float *w1, *b1, *w2, *b2;    // [H][12], [H], [A][H], [A]
+    int H, A, at;                      // hidden units, actions, action tiles of the blob
+    double xb[UAVTRACK_OBS_DIM];       // nominal bounds of |obs_k| (actor_obs_bounds)
+    float *blob;                       // actor_blob_floats(H, at) floats
+    double *scales;                    // [2]
+};
+hipError_t launch_actor_pack(const ActorPackArgs &a, hipStream_t stream);
 
 // reset_kernel.hip
 hipError_t launch_reset(const uavtrack_env *env, uint64_t seed, uint32_t episode, float *obs,

@@ -102,6 +102,8 @@ SIGNATURES = {
     "uavtrack_run_greedy": (C.c_int, [C.c_void_p, C.c_int32, C.c_uint64] + [C.c_void_p] * 7 + [C.c_void_p]),
     "uavtrack_greedy_actions": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]),
     "uavtrack_set_actor_weights": (C.c_int, [C.c_void_p] + [C.c_void_p] * 4 + [C.c_int32, C.c_void_p]),
+    "uavtrack_publish_actor_weights": (C.c_int, [C.c_void_p] + [C.c_void_p] * 4 + [C.c_int32, C.c_void_p]),
+    "uavtrack_get_actor_blob": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     "uavtrack_actor_actions": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "uavtrack_run_actor": (C.c_int, [C.c_void_p, C.c_int32, C.c_uint64, C.c_int32] + [C.c_void_p] * 8 + [C.c_void_p]),
     "uavtrack_set_target_trace": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32]),
@@ -118,6 +120,7 @@ SIGNATURES = {
     "uavtrack_learner_reserve": (C.c_int, [C.c_void_p, C.c_int64]),
     "uavtrack_learner_set_params": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     "uavtrack_learner_get_params": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
+    "uavtrack_learner_publish_actor": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "uavtrack_learner_set_optimizer_state": (C.c_int, [C.c_void_p] + [C.c_void_p] * 3 + [C.c_int64, C.c_void_p]),
     "uavtrack_learner_get_optimizer_state": (C.c_int, [C.c_void_p] + [C.c_void_p] * 3 + [C.c_int64, C.c_void_p]),
     "uavtrack_learner_update": (C.c_int, [C.c_void_p, C.c_int64] + [C.c_void_p] * 4 + [C.c_int64] + [C.c_void_p] * 6),

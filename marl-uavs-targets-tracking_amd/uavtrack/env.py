@@ -411,6 +411,7 @@ class BatchedUavEnv(Handle):
         if actor is None:
             _lib.check(self._lib.uavtrack_set_actor_weights(self._h, None, None, None, None, C.c_int32(0),
                                                             self._stream()), "uavtrack_set_actor_weights")
+            self._actor_hidden = 0
             return
         sd = actor.state_dict() if hasattr(actor, "state_dict") else actor
         host = [sd[k].detach().to("cpu", torch.float32).contiguous()
@@ -422,6 +423,45 @@ class BatchedUavEnv(Handle):
         _lib.check(self._lib.uavtrack_set_actor_weights(self._h, *[C.c_void_p(t.data_ptr()) for t in host],
                                                         C.c_int32(w1.shape[0]), self._stream()),
                    "uavtrack_set_actor_weights")
+        self._actor_hidden = w1.shape[0]
+
+    def publish_actor(self, source) -> None:
+        """set_actor without the host: the blob is packed on the device from device tensors, stream-ordered (no copy to
+        the host, no synchronisation; capturable).  source: a DeviceActorCritic (its own parameters), an ActorMLP or a
+        state dict of fp32 tensors on this device (fc1.weight [H, 12], fc1.bias, fc2.weight [na*nc, H], fc2.bias).  The
+        installed actor must have the same H (set_actor sizes it).  A non-contiguous tensor is made contiguous on the
+        device; a wrong device, dtype or shape raises ValueError before anything is enqueued."""
+        from .learner import DeviceActorCritic
+        if isinstance(source, DeviceActorCritic):
+            source.publish_actor(self)
+            return
+        sd = source.state_dict() if isinstance(source, torch.nn.Module) else source
+        keys = ("fc1.weight", "fc1.bias", "fc2.weight", "fc2.bias")
+        if not all(k in sd for k in keys):
+            raise ValueError(f"publish_actor: the source needs the tensors {keys}")
+        ts = [sd[k] for k in keys]
+        for k, t in zip(keys, ts):
+            if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.device.type != "cuda" \
+                    or t.device.index != self._device_index:
+                raise ValueError(f"publish_actor: {k} must be a float32 tensor on cuda:{self._device_index}")
+        w1, b1, w2, b2 = ts
+        H, A = (w1.shape[0] if w1.dim() == 2 else -1), self.cfg.na_total
+        if w1.shape != (H, _lib.OBS_DIM) or b1.shape != (H,) or w2.shape != (A, H) or b2.shape != (A,):
+            raise ValueError(f"publish_actor: shapes fc1 {tuple(w1.shape)} / {tuple(b1.shape)}, fc2 {tuple(w2.shape)} / "
+                             f"{tuple(b2.shape)} do not match Linear({_lib.OBS_DIM}, H) / Linear(H, {A})")
+        ts = [t.detach().contiguous() for t in ts]
+        _lib.check(self._lib.uavtrack_publish_actor_weights(self._h, *[_ptr(t) for t in ts], C.c_int32(H),
+                                                            self._stream()), "uavtrack_publish_actor_weights")
+
+    def actor_blob(self) -> np.ndarray:
+        """The installed actor blob (csrc/actor.h layout) as float32, read back to the host (synchronises): an
+        inspection aid, e.g. to compare set_actor and publish_actor bit for bit."""
+        H = getattr(self, "_actor_hidden", 0)
+        at = 2 if self.cfg.dim == 3 else 1
+        out = np.empty(128 + (H + 31) // 32 * (2 + 4 * at) * 256, np.float32)
+        _lib.check(self._lib.uavtrack_get_actor_blob(self._h, _lib.host_ptr(out), out.size, self._stream()),
+                   "uavtrack_get_actor_blob")
+        return out
 
     def actor_actions(self, obs: torch.Tensor, seed: int = 0, mode: int = _lib.ACTOR_SAMPLE,
                       want_probs: bool = False, out: Optional[torch.Tensor] = None):

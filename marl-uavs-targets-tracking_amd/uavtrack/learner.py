@@ -136,6 +136,14 @@ class DeviceActorCritic(Handle):
             prio = None
         return self._run(k, buffer.store, buffer.capacity, idx, prio)
 
+    def publish_actor(self, env) -> None:
+        """The actor's current parameters into env's rollout actor, packed on the device (uavtrack_learner_publish_actor):
+        stream-ordered, no host copy, no synchronisation, capturable -- the sync-free form of
+        env.set_actor(self.actor_state_dict()), with the same bits.  env's actor must already be installed at this
+        hidden_dim (set_actor)."""
+        _lib.check(self._lib.uavtrack_learner_publish_actor(self._h, env._h, env._stream()),
+                   "uavtrack_learner_publish_actor")
+
     # ---- weights and optimizer state
     def _module_state(self, module: torch.nn.Module, offset: int) -> "OrderedDict[str, torch.Tensor]":
         names, params = zip(*module.named_parameters())

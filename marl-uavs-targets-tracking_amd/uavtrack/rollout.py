@@ -44,7 +44,8 @@ class BatchedRollout:
     device_actor=True (policy must then have FnnPolicyNet's parameters, e.g. ActorMLP or the reference's own
     actor): the policy runs inside the library -- per step as uavtrack_actor_actions, or, with `run_fused`,
     actor and environment together in ONE launch for the whole rollout (uavtrack_run_actor); call
-    `sync_actor()` after every learner update to upload the new weights."""
+    `sync_actor()` (host pack) or `publish_actor()` (device pack, no synchronisation) after every learner update to
+    upload the new weights."""
 
     def __init__(self, env: BatchedUavEnv, policy, select: Callable[[torch.Tensor], torch.Tensor] = sample_actions,
                  steps_per_graph: int = 8, use_graph: bool = True, seed: int = 0, device_actor: bool = False,
@@ -186,6 +187,12 @@ class BatchedRollout:
     def sync_actor(self):
         """Upload the policy's current parameters to the library (device_actor mode; after a learner update)."""
         self.env.set_actor(self.policy)
+
+    def publish_actor(self, source=None):
+        """sync_actor without the host: `source` (default: the rollout's own policy module, on the GPU) is packed into the
+        library's actor on the device, stream-ordered, with no synchronisation (BatchedUavEnv.publish_actor).  source may
+        also be a DeviceActorCritic or a state dict of device tensors."""
+        self.env.publish_actor(self.policy if source is None else source)
 
     def run_fused(self, steps: int, want_terms: bool = False, out: Optional[Dict[str, torch.Tensor]] = None
                   ) -> Dict[str, torch.Tensor]:
