@@ -13,11 +13,14 @@ update is the same rule on a sampled batch, and the new actor weights are re-upl
     python examples/train_maac.py --method maac-r --envs 1024 --iters 40     # reciprocal (PMI) reward, PMI net trained too
     python examples/train_maac.py --replay prioritized --learner device --envs 4096 --n-uav 20   # prioritised ring, 32.8 M slots
     python examples/train_maac.py --replay prioritized --learner device --publish device --log-every 10   # no host sync per iteration
+    python examples/train_maac.py --method maac-r --pmi-trainer device --learner device --replay prioritized --publish device --log-every 10
 
 --method maac-r is the paper's method (configs/MAAC-R.yaml): the reward of every step is mixed in-kernel with the
 neighbours' rewards, weighted by the PMI network's scores (uav.py:262-291); that network is trained alongside on
 (timestep, uav-pair) samples of the rollout's observations (PMINet.py:74-100, here uavtrack.sample_pmi_pairs +
-pmi_contrastive_loss on the device history) and its BatchNorm-folded weights are re-uploaded every iteration.
+pmi_contrastive_loss on the device history) and its BatchNorm-folded weights are re-uploaded every iteration -- or, with
+--publish device, folded and packed into the scorer on the device (publish_pmi), the index draw of train_pmi on a device
+generator and the PMI loss read on printed lines only, so that a MAAC-R iteration too issues no host synchronisation.
 """
 import argparse
 import os
@@ -95,7 +98,12 @@ def main(argv=None, timings=None):
     ap.add_argument("--beta", type=float, default=0.4, help="--replay prioritized: importance exponent (train.py:100)")
     ap.add_argument("--publish", choices=["host", "device"], default="host",
                     help="host: the learner's actor weights reach the rollout through the host pack (sync_actor); device: "
-                         "packed on the device from the learner's parameters (publish_actor), no copy, no synchronisation")
+                         "packed on the device from the learner's parameters (publish_actor), no copy, no synchronisation; "
+                         "with --method maac-r the PMI network reaches the scorer the same way (publish_pmi)")
+    ap.add_argument("--pmi-draw", choices=["auto", "cpu", "device"], default="auto",
+                    help="--pmi-trainer device only: where train_pmi draws its index triples: torch's CPU generator (the "
+                         "reference's stream; copies them to the device) or a device generator seeded with --seed (no "
+                         "host work); auto: cpu with --publish host, device with --publish device")
     ap.add_argument("--log-every", type=int, default=1,
                     help="print (and so synchronise) every N iterations and after the last; the iteration time printed is "
                          "the mean over the iterations since the previous line, and with N > 1 the rollout time of a "
@@ -119,6 +127,10 @@ def main(argv=None, timings=None):
         pmi = uavtrack.make_pmi_net(args.pmi_hidden).to(dev)
         opt_p = torch.optim.Adam(pmi.parameters(), lr=1e-3)          # PMINet.py:39
         env.set_pmi(pmi.state_dict())
+    pmi_gen = None
+    if pmi_dev is not None and (args.pmi_draw == "device" or (args.pmi_draw == "auto" and args.publish == "device")):
+        pmi_gen = torch.Generator(device=dev)
+        pmi_gen.manual_seed(args.seed)
     actor = uavtrack.ActorMLP(hidden_dim=args.hidden, action_dim=cfg.na_total).to(dev)
     critic = ValueNet(hidden_dim=args.hidden).to(dev)
     opt_a = torch.optim.Adam(actor.parameters(), lr=args.actor_lr)
@@ -177,11 +189,20 @@ def main(argv=None, timings=None):
             for x12, x13 in uavtrack.pmi_batches(sel, args.pmi_batch):
                 loss = uavtrack.pmi_contrastive_loss(pmi(x12), pmi(x13))
                 opt_p.zero_grad(); loss.backward(); opt_p.step()
-                lp = float(loss.detach())
-            env.set_pmi(pmi.state_dict())                             # eval-mode (running-stat) BatchNorm is what gets folded
+                lp = loss.detach()
+            lp = float(lp) if log else lp
+            if args.publish == "device":
+                env.publish_pmi(pmi)                                  # folded and packed on the device, same bits
+            else:
+                env.set_pmi(pmi.state_dict())                         # eval-mode (running-stat) BatchNorm is what gets folded
         elif pmi_dev is not None:                                     # the same call, one library call on the device
-            lp = pmi_dev.train_pmi({"pmi": {"batch_size": args.pmi_batch}}, res["obs"], args.n_uav)
-            env.set_pmi(pmi_dev)
+            lp = pmi_dev.train_pmi({"pmi": {"batch_size": args.pmi_batch}}, res["obs"], args.n_uav, generator=pmi_gen,
+                                   sync=False)
+            lp = float(lp) if log else lp
+            if args.publish == "device":
+                pmi_dev.publish_pmi(env)                              # no copy to the host, no synchronisation
+            else:
+                env.set_pmi(pmi_dev)
         if args.publish == "host":
             rollout.sync_actor()                                      # new weights for the next rollout
         elif learner is not None:

@@ -159,6 +159,43 @@ int uavtrack_set_pmi_scheme(uavtrack_env *env, int32_t scheme);
  * operand left f16's range at run time.  Synchronises `stream`. */
 int uavtrack_pmi_info(uavtrack_env *env, int64_t out[4], void *stream);
 
+/* The 26 fp32 tensors of a PMINetwork (PMINet.py:20-62) as DEVICE pointers in torch layouts: the four Linear +
+ * BatchNorm1d blocks in the order fc_comm / bn_comm (in = 5), fc_obs / bn_obs (4), fc_boundary_state /
+ * bn_boundary_state (3), fc1 / bn1 (3 hidden) -- weight [hidden][in], bias, BatchNorm weight, bias, running_mean,
+ * running_var [hidden] each -- then fc2.weight [1][hidden] and fc2.bias [1]. */
+typedef struct uavtrack_pmi_tensors {
+    struct {
+        const float *weight, *bias, *bn_weight, *bn_bias, *running_mean, *running_var;
+    } block[4];
+    const float *fc2_weight, *fc2_bias;
+} uavtrack_pmi_tensors;
+
+/* uavtrack_set_pmi_weights without the host: BatchNorm fold (fp64, each result rounded once to fp32, as
+ * uavtrack/pmi.py folds), padding, bounds, block scales, range-watch limits, the f16 verdict and all packed layouts
+ * are computed on the device from the tensors of `t`, bitwise identical to what the host path writes from the same
+ * numbers (csrc/pmi_pack.h states every rounding once, for both).  Stream-ordered: no synchronisation, no allocation,
+ * capturable into a graph; the tensors are read when the launches execute on `stream`, not when this is called.  The
+ * handle must already hold weights of the same `hidden` (uavtrack_set_pmi_weights sizes the allocation and the
+ * scratch).  Returns an error, enqueuing nothing and leaving the installed weights in place, for a null pointer, no
+ * weights installed, or `hidden` other than the installed width.
+ * At widths 64 / 96 / 128 the verdict "fits f16's range" is then known to the device only: from this call until the
+ * next uavtrack_set_pmi_weights the handle launches F16X3 with its gated BF16X6 stand-by under AUTO and F16X3 alike;
+ * weights that do not fit are scored by the stand-by -- the BF16X6 scores of the host path, bit for bit -- and such
+ * chunks are counted in uavtrack_pmi_publish_info, not in uavtrack_pmi_info's out[3].  A scheme pinned to F16X3 can
+ * therefore not be refused by a device publish; uavtrack_pmi_info reports BF16X6 while the verdict is "unfit". */
+int uavtrack_publish_pmi_weights(uavtrack_env *env, const uavtrack_pmi_tensors *t, int32_t hidden, void *stream);
+
+/* out[0] = 1 if the installed weights come from a device publish (0 after uavtrack_set_pmi_weights), out[1] = chunks
+ * the wide-range kernel has scored since the handle was created because device-published weights did not fit f16's
+ * range (the run-time range watch keeps its own count, uavtrack_pmi_info out[3]).  Synchronises `stream`. */
+int uavtrack_pmi_publish_info(uavtrack_env *env, int64_t out[2], void *stream);
+
+/* Inspection aid: the size in floats of the installed weights allocation (0 without weights), and a copy of all of it
+ * -- the fp32 blob in scorer order, the bf16 / f16 planes of widths 64 / 96 / 128, the 8-word scalar block
+ * (csrc/pmi_pack.h) -- to a HOST buffer of exactly that many floats.  The copy synchronises `stream`. */
+int uavtrack_pmi_blob_floats(uavtrack_env *env, int64_t *out);
+int uavtrack_get_pmi_blob(uavtrack_env *env, float *host, int64_t n_floats, void *stream);
+
 /* Replaces PMINetwork.inference (PMINet.py:64-72: eval mode, no grad) on a batch: x [n][12] (device; row k is what
  * uav.py:281 builds, la_i * la_j) -> scores [n] (device), with the weights of uavtrack_set_pmi_weights and on the very
  * kernels that score the neighbour pairs of a MAAC-R step (f16 x 3 on block-scaled planes, bf16 x 6 or fp32 MFMA by width and weight range) -- the network alone, for
@@ -493,6 +530,12 @@ int uavtrack_pmi_trainer_train(uavtrack_pmi_trainer *trainer, const float *rows,
 /* Synchronises `stream`; fails if any train call since the previous check was refused on the device (an index out
  * of range).  refused (nullable) receives their number; the count restarts at 0. */
 int uavtrack_pmi_trainer_check(uavtrack_pmi_trainer *trainer, int64_t *refused, void *stream);
+
+/* uavtrack_publish_pmi_weights from the trainer's own state into `env`'s scorer: stream-ordered, no synchronisation,
+ * no allocation, capturable; the state is read when the launches execute, so a graph replayed after training
+ * publishes the weights of that moment.  Refused, with nothing enqueued, if the two handles sit on different devices
+ * or the trainer's hidden differs from the installed width. */
+int uavtrack_pmi_trainer_publish(uavtrack_pmi_trainer *trainer, uavtrack_env *env, void *stream);
 
 /* ---- the prioritised replay ring: PrioritizedReplayBuffer.add / sample on the device ----
  * The reference's PrioritizedReplayBuffer (train.py:73-139) as a ring of caller-owned DEVICE tensors: states and

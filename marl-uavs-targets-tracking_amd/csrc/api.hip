@@ -4,6 +4,7 @@
 
 #include "internal.h"
 #include "actor.h"
+#include "pmi_pack.h"
 
 #include <cmath>
 #include <cstdarg>
@@ -163,7 +164,7 @@ Bufs slab_bufs(uavtrack_env *env)
 
 Bufs counter_bufs(uavtrack_env *env)
 {
-    return {buf(env->pair_count, 2, true), buf(env->pair_total, 1, true), buf(env->pmi_flags, 2, true)};
+    return {buf(env->pair_count, 2, true), buf(env->pair_total, 1, true), buf(env->pmi_flags, 3, true)};
 }
 
 // MAAC-R pair-list slots per step: every pair within dp at worst -- twice that, because the single-wavefront rollout
@@ -202,7 +203,19 @@ void actor_obs_bounds(const uavtrack_config &c, double xb[UAVTRACK_OBS_DIM])
     for (int k = 0; k < UAVTRACK_OBS_DIM; ++k) xb[k] = b[k];
 }
 
-Bufs weight_bufs(PmiWeights &w, size_t floats = 0) { return {buf(w.blob, floats)}; }
+// the weights allocation (PmiBlobLayout) and the scratch of a device publish (the folded network) next to it
+Bufs weight_bufs(PmiWeights &w, size_t floats = 0, size_t fold_floats = 0) { return {buf(w.blob, floats), buf(w.fold, fold_floats)}; }
+
+// nominal bounds of the pair inputs x = la_i * la_j (uav.py:156-197: normalised offsets and action differences within
+// [-1, 1], heading terms within +-(1 + v_t/v_u), positions / dc taken up to three field lengths outside the box);
+// returns the largest, pos^2
+double pmi_input_bounds(const uavtrack_config &c, double xb[UAVTRACK_OBS_DIM])
+{
+    const double vr = 1.0 + c.t_v_max / c.u_v_max, pos = 4.0 * std::fmax(c.x_max, c.y_max) / c.dc;
+    const double b[UAVTRACK_OBS_DIM] = {1, 1, 4, 4, 1, 1, 1, vr * vr, vr * vr, pos * pos, pos * pos, 1};
+    for (int k = 0; k < UAVTRACK_OBS_DIM; ++k) xb[k] = b[k];
+    return pos * pos;
+}
 
 void free_state(uavtrack_env *env)
 {
@@ -552,15 +565,14 @@ int uavtrack_set_pmi_weights(uavtrack_env *env, const float *folded, size_t n_fl
     // and biases are zero (relu(0) = 0 adds nothing to any sum), so every hidden_dim runs on the same kernels.
     const int hp = pmi_padded_hidden(hidden);
     const size_t HP = (size_t)hp, n_dev = 12 * HP + 3 * HP + 3 * HP * HP + HP + HP + 1;
-    const size_t x6_off = (n_dev + 3) & ~(size_t)3, x6_len = pmi_x6_floats(hp);     // the bf16 planes, 16-B aligned
-    const size_t l1_off = x6_off + x6_len, l1_len = pmi_l1_floats(hp);               // the branch layers' f16 planes behind them
-    const size_t t3_off = l1_off + l1_len, t3_len = pmi_t3_floats(hp);               // ... and fc1 block-scaled (pmi_score_t3_kernel)
+    const PmiBlobLayout lay = PmiBlobLayout::make(hp);      // the fp32 blob, the bf16 / f16 planes behind it, the scalar block
+    const size_t x6_len = lay.x6_len, t3_len = lay.t3_len;
 
     // ---- everything the host can decide comes FIRST: a call that fails leaves the handle's previous weights in place
     bool h3_ok = t3_len != 0;
     float s1 = 1.0f, tw = 1.0f;
     float rng_inv[3] = {0.0f, 0.0f, 0.0f};
-    std::vector<float> padded(n_dev, 0.0f), packed(n_dev);
+    std::vector<float> padded(n_dev, 0.0f);
     {
         const float *src = folded;
         float *dst = padded.data();
@@ -585,10 +597,10 @@ int uavtrack_set_pmi_weights(uavtrack_env *env, const float *folded, size_t n_fl
     // (uav.py:156-197: normalised offsets and action differences within [-1, 1], heading terms within +-(1 + v_t/v_u),
     // positions / dc taken up to three field lengths outside the box).  A network beyond half that range keeps the
     // bf16 x 6 kernel (bf16 has fp32's exponent).
+    // (the bounds, scales and limits below are restated on the device, in this order, by pmi_pack_kernel.hip)
     if (h3_ok) {
-        const uavtrack_config &c = env->cfg;
-        const double vr = 1.0 + c.t_v_max / c.u_v_max, pos = 4.0 * std::fmax(c.x_max, c.y_max) / c.dc;
-        const double xb[12] = {1, 1, 4, 4, 1, 1, 1, vr * vr, vr * vr, pos * pos, pos * pos, 1};
+        double xb[UAVTRACK_OBS_DIM];
+        const double pos2 = pmi_input_bounds(env->cfg, xb);
         const float *pw = padded.data();
         double act_max = 0.0, w_max = 0.0, w1_max = 0.0;
         double gain[3] = {0.0, 0.0, 0.0}, bias[3] = {0.0, 0.0, 0.0};      // per branch: max_u sum_k |w_uk|, max_u |b_u|
@@ -611,56 +623,57 @@ int uavtrack_set_pmi_weights(uavtrack_env *env, const float *folded, size_t n_fl
         for (size_t k = 0; k < 3 * HP * HP; ++k) w1_max = std::fmax(w1_max, std::fabs(pw[k]));
         w_max = w1_max;
         for (size_t k = 0; k < 15 * HP; ++k) w_max = std::fmax(w_max, std::fabs(padded[k]));      // the branch layers (MFMA operands of pmi_score_t3_kernel)
-        w_max = std::fmax(w_max, pos * pos);                                                         // ... and their inputs
-        h3_ok = std::isfinite(act_max) && act_max < 32000.0 && w_max < 32000.0;
+        w_max = std::fmax(w_max, pos2);                                                              // ... and their inputs
+        h3_ok = pmi_f16_fit(act_max, w_max);
         // Block scales of the t3 planes, powers of two: T * max |fc1 weight| just below 32000 (the weights are known
         // exactly); S1 * (activation bound) below 512 -- the bound comes from nominal observation ranges, and the
         // uav.py:165 weight lets a UAV next to the origin exceed them, so the activations keep a factor 128 of
         // headroom to f16's 65504 (the unscaled h3 planes have 65504 / bound).  Remainders x - f16(x) of values within
         // 2^-12 (activations) / 2^-18 (weights) of those sizes are normal f16 numbers.
-        auto scale_for = [](double bound, double target) {
-            int e = 15;
-            if (bound > 0.0) e = (int)std::floor(std::log2(target / bound));
-            return std::ldexp(1.0f, e < -6 ? -6 : (e > 15 ? 15 : e));
-        };
-        s1 = scale_for(act_max, 512.0);
-        tw = scale_for(w1_max, 32000.0);
+        s1 = pmi_scale_for(act_max, 512.0);
+        tw = pmi_scale_for(w1_max, 32000.0);
         // The run-time watch of the f16 kernel (pmi_kernel.hip, PmiParams::rng_inv).  The bounds above come from NOMINAL
         // observation ranges; the uav.py:165 weight 1 / min(d, 1) lets a UAV next to the origin exceed them without
         // limit.  An activation of branch br stays below 60000 / S1 while |x| <= (60000 / S1 - max|b|) / max_u sum_k|w_uk|
         // over the branch's inputs, and an input splits into normal f16 planes below 30000 (its remainder is scaled by 2^11):
         // the kernel compares the largest |x| of a tile with the smaller of the two and has the chunk re-scored by the
         // bf16 kernel when it is exceeded.
-        for (int br = 0; br < 3; ++br) {
-            double lim = 30000.0;
-            if (gain[br] > 0.0) lim = std::fmin(lim, (60000.0 / (double)s1 - bias[br]) / gain[br]);
-            rng_inv[br] = lim > 0.0 ? (float)(1.0 / lim) : INFINITY;
-        }
+        for (int br = 0; br < 3; ++br) rng_inv[br] = pmi_rng_inv(gain[br], bias[br], s1);
     }
     // a pinned scorer (uavtrack_set_pmi_scheme) that cannot take these weights: refused before anything is replaced
     if (!pmi_scheme_fits(hp, h3_ok, env->pmi_scheme))
         return fail("uavtrack_set_pmi_weights: these weights (hidden %d%s) cannot run on the pinned scorer scheme %d "
                     "(uavtrack_set_pmi_scheme); pin UAVTRACK_PMI_AUTO or a scheme that takes them; the previous weights stay loaded",
                     hidden, h3_ok ? "" : ", beyond f16's range", env->pmi_scheme);
-    pack_pmi_blob(padded.data(), packed.data(), hp);
-    std::vector<uint16_t> planes(x6_len * 2), planes1(h3_ok ? l1_len * 2 : 0), planes3t(h3_ok ? t3_len * 2 : 0);
-    if (x6_len) pack_pmi_x6(padded.data(), planes.data(), hp);
-    if (h3_ok) {
-        pack_pmi_l1(padded.data(), planes1.data(), hp, s1);
-        pack_pmi_t3(padded.data(), planes3t.data(), hp, tw);
+    // One host image of the whole allocation.  The l1 / t3 planes are packed for every width that has them, whatever the
+    // verdict (their scales are defined either way), so that the allocation is word for word what a device publish of the
+    // same numbers writes; what is launched still follows the verdict (the handle's l1 / t3 pointers below).
+    std::vector<float> image(lay.total, 0.0f);
+    pack_pmi_blob(padded.data(), image.data(), hp);
+    if (x6_len) pack_pmi_x6(padded.data(), reinterpret_cast<uint16_t *>(image.data() + lay.x6_off), hp);
+    if (t3_len) {
+        pack_pmi_l1(padded.data(), reinterpret_cast<uint16_t *>(image.data() + lay.l1_off), hp, s1);
+        pack_pmi_t3(padded.data(), reinterpret_cast<uint16_t *>(image.data() + lay.t3_off), hp, tw);
+    }
+    {
+        float *scal = image.data() + lay.scal_off;
+        scal[kPmiScalScale] = s1 * tw;
+        scal[kPmiScalInvScale] = 1.0f / (s1 * tw);
+        for (int k = 0; k < 3; ++k) scal[kPmiScalRng + k] = rng_inv[k];
+        scal[kPmiScalFit] = pmi_float(h3_ok ? 1u : 0u);
+        scal[kPmiScalS1] = s1;
+        scal[kPmiScalT] = tw;
     }
 
-    // ---- device side: a blob of another size is allocated BEFORE the old one goes; the uploads are complete before the
-    //      host vectors die and before the new weights are published in the handle
+    // ---- device side: a blob of another size is allocated BEFORE the old one goes; the upload is complete before the
+    //      host vector dies and before the new weights are published in the handle
     const bool fresh = env->pmi.n_floats != n_dev || !env->pmi.blob;
     PmiWeights next;
     HIP_TRY(hipStreamSynchronize(st));          // (launches that still read the current weights)
-    if (fresh) HIP_TRY(replace(weight_bufs(next, t3_off + t3_len)));
+    if (fresh) HIP_TRY(replace(weight_bufs(next, lay.total, n_dev)));
     float *blob = fresh ? next.blob : env->pmi.blob;
-    hipError_t e = hipMemcpyAsync(blob, packed.data(), n_dev * 4, hipMemcpyHostToDevice, st);
-    if (e == hipSuccess && x6_len) e = hipMemcpyAsync(blob + x6_off, planes.data(), x6_len * 4, hipMemcpyHostToDevice, st);
-    if (e == hipSuccess && h3_ok) e = hipMemcpyAsync(blob + l1_off, planes1.data(), l1_len * 4, hipMemcpyHostToDevice, st);
-    if (e == hipSuccess && h3_ok) e = hipMemcpyAsync(blob + t3_off, planes3t.data(), t3_len * 4, hipMemcpyHostToDevice, st);
+    float *fold = fresh ? next.fold : env->pmi.fold;
+    hipError_t e = hipMemcpyAsync(blob, image.data(), lay.total * 4, hipMemcpyHostToDevice, st);
     if (e == hipSuccess) e = hipStreamSynchronize(st);
     if (e != hipSuccess) {
         release(weight_bufs(fresh ? next : env->pmi));    // (an in-place upload that failed half way cannot be undone: the handle loses its weights)
@@ -670,13 +683,14 @@ int uavtrack_set_pmi_weights(uavtrack_env *env, const float *folded, size_t n_fl
     }
     if (fresh) release(weight_bufs(env->pmi));
     env->pmi.blob = blob;
-    env->pmi.x6 = x6_len ? blob + x6_off : nullptr;
-    env->pmi.l1 = h3_ok ? blob + l1_off : nullptr;
-    env->pmi.t3 = h3_ok ? blob + t3_off : nullptr;
-    env->pmi.t3_s1 = s1;
-    env->pmi.t3_t = tw;
-    for (int k = 0; k < 3; ++k) env->pmi.rng_inv[k] = rng_inv[k];
+    env->pmi.fold = fold;
+    env->pmi.x6 = x6_len ? blob + lay.x6_off : nullptr;
+    env->pmi.l1 = h3_ok ? blob + lay.l1_off : nullptr;
+    env->pmi.t3 = h3_ok ? blob + lay.t3_off : nullptr;
+    env->pmi.scal = blob + lay.scal_off;
+    env->pmi.dev_published = false;
     env->pmi.hidden = hp;
+    env->pmi.hidden_raw = hidden;
     env->pmi.n_floats = n_dev;
     // scratch for an episode's worth of deferred scoring (bounded by UAVTRACK_PMI_SCRATCH_MB): the stepping calls then never
     // allocate or synchronise, whatever their length up to cfg.horizon -- which also makes them capturable into a HIP graph
@@ -726,6 +740,16 @@ int uavtrack_pmi_info(uavtrack_env *env, int64_t out[4], void *stream)
     out[0] = pmi_effective_scheme(env);
     out[1] = env->pmi.hidden;
     out[2] = env->pmi.t3 ? 1 : 0;
+    if (env->pmi.dev_published && pmi_t3_floats(env->pmi.hidden)) {
+        // the verdict of the last device publish is the device's: read it (this call synchronises anyway)
+        ON_DEVICE(env->cfg.device_id);
+        hipStream_t st = static_cast<hipStream_t>(stream);
+        uint32_t fit = 0;
+        HIP_TRY(hipMemcpyAsync(&fit, env->pmi.scal + kPmiScalFit, sizeof fit, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        out[2] = fit ? 1 : 0;
+        if (!fit && (env->pmi_scheme == UAVTRACK_PMI_AUTO || env->pmi_scheme == UAVTRACK_PMI_F16X3)) out[0] = UAVTRACK_PMI_BF16X6;   // (the stand-by scores)
+    }
     if (env->pmi_flags) {
         ON_DEVICE(env->cfg.device_id);
         hipStream_t st = static_cast<hipStream_t>(stream);
@@ -734,6 +758,88 @@ int uavtrack_pmi_info(uavtrack_env *env, int64_t out[4], void *stream)
         HIP_TRY(hipStreamSynchronize(st));
         out[3] = v[1];
     }
+    return 0;
+}
+
+int uavtrack_pmi_publish_info(uavtrack_env *env, int64_t out[2], void *stream)
+{
+    if (!env || !out) return fail("uavtrack_pmi_publish_info: null argument");
+    out[0] = env->pmi.blob && env->pmi.dev_published ? 1 : 0;
+    out[1] = 0;
+    if (env->pmi_flags) {
+        ON_DEVICE(env->cfg.device_id);
+        hipStream_t st = static_cast<hipStream_t>(stream);
+        unsigned v = 0;
+        HIP_TRY(hipMemcpyAsync(&v, env->pmi_flags + 2, sizeof v, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        out[1] = v;
+    }
+    return 0;
+}
+
+// The device pack behind uavtrack_publish_pmi_weights and uavtrack_pmi_trainer_publish (the caller has tested the handle
+// and the pointers): refused, with nothing enqueued, unless weights of the same width are installed.
+static int publish_pmi(const char *fn, uavtrack_env *env, const float *const tensors[kPmiStateTensors], int32_t hidden,
+                       void *stream)
+{
+    if (!env->pmi.blob) return fail("%s: no weights installed: uavtrack_set_pmi_weights sizes the allocation first", fn);
+    if (hidden != env->pmi.hidden_raw)
+        return fail("%s: hidden %d, the installed weights have %d (only uavtrack_set_pmi_weights changes the width)", fn,
+                    hidden, env->pmi.hidden_raw);
+    ON_DEVICE(env->cfg.device_id);
+    PmiPackArgs a;
+    for (int k = 0; k < kPmiStateTensors; ++k) a.t[k] = tensors[k];
+    a.H = hidden;
+    a.HP = env->pmi.hidden;
+    a.pos2 = pmi_input_bounds(env->cfg, a.xb);
+    a.fold = env->pmi.fold;
+    a.blob = env->pmi.blob;
+    HIP_TRY(launch_pmi_pack(a, static_cast<hipStream_t>(stream)));
+    // from here on only the device knows whether the weights fit f16: the planes are there either way, and the t3 kernel
+    // honours the verdict in the scalar block (pmi_kernel.hip)
+    const PmiBlobLayout lay = PmiBlobLayout::make(env->pmi.hidden);
+    env->pmi.l1 = lay.t3_len ? env->pmi.blob + lay.l1_off : nullptr;
+    env->pmi.t3 = lay.t3_len ? env->pmi.blob + lay.t3_off : nullptr;
+    env->pmi.dev_published = true;
+    return 0;
+}
+
+int uavtrack_publish_pmi_weights(uavtrack_env *env, const uavtrack_pmi_tensors *t, int32_t hidden, void *stream)
+{
+    if (!env) return fail("uavtrack_publish_pmi_weights: null handle");
+    if (!t) return fail("uavtrack_publish_pmi_weights: the tensor list is null");
+    const float *p[kPmiStateTensors];
+    for (int b = 0; b < kPmiBlocks; ++b) {
+        const float *q[6] = {t->block[b].weight, t->block[b].bias, t->block[b].bn_weight, t->block[b].bn_bias,
+                             t->block[b].running_mean, t->block[b].running_var};
+        for (int k = 0; k < 6; ++k) p[b * 6 + k] = q[k];
+    }
+    p[24] = t->fc2_weight;
+    p[25] = t->fc2_bias;
+    for (int k = 0; k < kPmiStateTensors; ++k)
+        if (!p[k]) return fail("uavtrack_publish_pmi_weights: tensor %d of the 26 is null", k);
+    return publish_pmi(__func__, env, p, hidden, stream);
+}
+
+int uavtrack_pmi_blob_floats(uavtrack_env *env, int64_t *out)
+{
+    if (!env || !out) return fail("uavtrack_pmi_blob_floats: null argument");
+    *out = env->pmi.blob ? (int64_t)PmiBlobLayout::make(env->pmi.hidden).total : 0;
+    return 0;
+}
+
+int uavtrack_get_pmi_blob(uavtrack_env *env, float *host, int64_t n_floats, void *stream)
+{
+    if (!env) return fail("uavtrack_get_pmi_blob: null handle");
+    if (!host) return fail("uavtrack_get_pmi_blob: host is null");
+    if (!env->pmi.blob) return fail("uavtrack_get_pmi_blob: no weights installed (uavtrack_set_pmi_weights)");
+    const size_t n = PmiBlobLayout::make(env->pmi.hidden).total;
+    if (n_floats != (int64_t)n)
+        return fail("uavtrack_get_pmi_blob: %lld floats, the installed allocation has %zu", (long long)n_floats, n);
+    ON_DEVICE(env->cfg.device_id);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    HIP_TRY(hipMemcpyAsync(host, env->pmi.blob, n * 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
     return 0;
 }
 
@@ -1383,6 +1489,18 @@ int uavtrack_learner_publish_actor(uavtrack_learner *learner, uavtrack_env *env,
     const LearnerLayout &L = learner->d.L;
     const float *p = learner->d.params;
     return publish_actor(__func__, env, p + L.a_w1, p + L.a_b1, p + L.a_w2, p + L.a_b2, L.H, L.A, stream);
+}
+
+int uavtrack_pmi_trainer_publish(uavtrack_pmi_trainer *trainer, uavtrack_env *env, void *stream)
+{
+    if (!trainer || !env) return fail("uavtrack_pmi_trainer_publish: null handle");
+    if (trainer->cfg.device_id != env->cfg.device_id)
+        return fail("uavtrack_pmi_trainer_publish: the trainer is on device %d, the environment on device %d",
+                    trainer->cfg.device_id, env->cfg.device_id);
+    const PmiTrainLayout &L = trainer->d.L;
+    const float *p[kPmiStateTensors];
+    for (int k = 0; k < kPmiStateTensors; ++k) p[k] = trainer->d.state + L.soff[k];
+    return publish_pmi(__func__, env, p, L.H, stream);
 }
 
 int uavtrack_learner_set_optimizer_state(uavtrack_learner *learner, const float *exp_avg, const float *exp_avg_sq,

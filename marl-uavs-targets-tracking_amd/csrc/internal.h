@@ -122,9 +122,14 @@ struct PmiWeights {
     const void *l1 = nullptr; // -> into blob: the branch layers as f16 planes in MFMA A-operand order (pack_pmi_l1), with t3
     const void *t3 = nullptr; // -> into blob: fc1 block-scaled as two f16 planes (f16(T w), remainder) for pmi_score_t3_kernel,
                               //    or null when the network's weights / activation bounds do not fit f16's range
-    float t3_s1 = 1.0f, t3_t = 1.0f;   // the powers of two folded into the branch layers (S1) and fc1 (T) of the t3 planes
-    float rng_inv[3] = {0.0f, 0.0f, 0.0f};   // 1 / the largest |x| per branch input the f16 planes take (pmi_kernel.hip, PmiParams)
-    int32_t hidden = 0;
+    const float *scal = nullptr;   // -> into blob: the scalar block (pmi_pack.h): block scales, range-watch limits, f16 verdict
+    float *fold = nullptr;   // device scratch of a device publish (pmi_pack_kernel.hip): the folded network, n_floats floats
+    // a device publish (uavtrack_publish_pmi_weights) has written the allocation since the last uavtrack_set_pmi_weights:
+    // l1 / t3 are then set whatever the verdict, which only the device knows (the scalar block), and AUTO / F16X3 launch
+    // the t3 kernel with its gated stand-by
+    bool dev_published = false;
+    int32_t hidden = 0;      // padded to the scorer's granule
+    int32_t hidden_raw = 0;  // as given to uavtrack_set_pmi_weights
     size_t n_floats = 0;
 };
 
@@ -153,7 +158,8 @@ struct uavtrack_env {
     uavtrack::PmiWeights pmi;
     int32_t n_cus = 0;           // compute units of the device (grid of the persistent scorer)
     int32_t pmi_scheme = 0;      // uavtrack_set_pmi_scheme: UAVTRACK_PMI_AUTO or a pinned scorer
-    unsigned *pmi_flags = nullptr;   // device [2]: the f16 scorer's range flag, chunks re-scored by the wide-range kernel
+    unsigned *pmi_flags = nullptr;   // device [3]: the f16 scorer's range flag; chunks re-scored by the wide-range kernel because an
+                                     // input left f16's range at run time; chunks it scored because published weights do not fit f16
     float *actor_w = nullptr;    // device blob of uavtrack_set_actor_weights (actor.h layout)
     double *actor_scales = nullptr;   // device [2]: T1, T2 between the two launches of a device publish (actor_pack_kernel.hip)
     int32_t actor_hidden = 0;

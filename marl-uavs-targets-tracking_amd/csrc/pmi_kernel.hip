@@ -25,6 +25,7 @@
 // UAV min(i, j) emitted the pair, in the slot "its first slot + rank of max(i, j) among its later neighbours".
 
 #include "internal.h"
+#include "pmi_pack.h"
 
 #include <cstring>
 #include <utility>
@@ -60,18 +61,20 @@ struct PmiParams {
     const void *x6;          // fc1 as three bf16 planes in MFMA B-operand order (pack_pmi_x6)
     const void *l1;          // the three branch layers as f16 planes in MFMA A-operand order (pack_pmi_l1), with t3
     const void *t3;          // fc1 as two f16 planes of T * w (hi, unscaled remainder) for pmi_score_t3_kernel (pack_pmi_t3), or null
-    float t3_scale;          // S1 * T: the power-of-two scale the t3 kernel's layer-2 accumulators carry (b1 goes in times this)
-    float t3_inv_scale;      // ... and its reciprocal (folded into w2)
+    const float *scal;       // -> into blob: the scalar block (pmi_pack.h): S1 * T, the power-of-two scale the t3 kernel's layer-2
+                             //    accumulators carry (b1 goes in times this), its reciprocal (folded into w2), the range-watch limits
+                             //    and the f16 verdict -- in memory, not in the arguments, because a device publish
+                             //    (uavtrack_publish_pmi_weights) changes them behind the host's back
     const float *obs;        // [S][B][N][12] local states of the chunk's steps
     const uint2 *pairs;      // {flat [step][b][i] index of i within the chunk, that of j} (0xFFFFFFFF: a dummy of the slot pool)
     const unsigned *pair_count;
     float *scores;           // one per pair, in pair-list order
     unsigned long long *pair_total;
     int32_t N;
-    // f16 range watch of pmi_score_t3_kernel: 1 / (largest |x| each branch's inputs may reach before an f16 operand could
-    // saturate; uavtrack_set_pmi_weights); a tile that exceeds one raises *range_flag, and the wide-range kernel launched
-    // behind it (gate != null: it returns at once while *gate == 0) scores the chunk again
-    float rng_inv[3];
+    // f16 range watch of pmi_score_t3_kernel: scal holds 1 / (largest |x| each branch's inputs may reach before an f16 operand
+    // could saturate; uavtrack_set_pmi_weights); a tile that exceeds one raises *range_flag (to 1), and the wide-range kernel
+    // launched behind it (gate != null: it returns at once while *gate == 0) scores the chunk again.  Weights that do not
+    // fit f16 at all (scal's verdict 0, possible after a device publish only) raise it to 2 without scoring anything.
     unsigned *range_flag;
     const unsigned *gate;
 };
@@ -712,13 +715,21 @@ __global__ void __launch_bounds__(H * 2, 1) pmi_score_t3_kernel(const PmiParams 
 #pragma unroll
         for (int j = 0; j < 3; ++j) { asm volatile("" : "+a"(L1h[j])); asm volatile("" : "+a"(L1l[j])); asm volatile("" : "+a"(L1s[j])); }
     }
+    // the weight-dependent scalars: uniform loads into scalar registers, once per workgroup, issued behind the plane loads
+    // above so that their trip to memory runs beside those
+    const float t3_scale = q.scal[kPmiScalScale], t3_inv_scale = q.scal[kPmiScalInvScale];
+    const float rng_inv0 = q.scal[kPmiScalRng], rng_inv1 = q.scal[kPmiScalRng + 1], rng_inv2 = q.scal[kPmiScalRng + 2];
+    if (__float_as_uint(q.scal[kPmiScalFit]) == 0u) {            // (uniform over the grid) the planes are not to be used: the stand-by scores
+        if (blockIdx.x == 0 && tid == 0 && *q.pair_count != 0u) *q.range_flag = 2u;
+        return;
+    }
     // accumulator row r of a lane is column (unit) m(r) = (r & 3) + 8 (r >> 2) + 4 kh of the wavefront's 32
     f32x16 biasv, w2r;
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
         const int m = 32 * w + (r & 3) + 8 * (r >> 2) + 4 * kh;
-        biasv[r] = b1[m] * q.t3_scale;          // (powers of two: exact)
-        w2r[r] = w2[m] * q.t3_inv_scale;
+        biasv[r] = b1[m] * t3_scale;          // (powers of two: exact)
+        w2r[r] = w2[m] * t3_inv_scale;
     }
 
     // where this lane's units of layer-1 block j land in an activation row: byte (j H + 32 w + 16 kh + r) * 2
@@ -752,7 +763,7 @@ __global__ void __launch_bounds__(H * 2, 1) pmi_score_t3_kernel(const PmiParams 
     // f16 range watch (see PmiParams): the largest |x| of each branch's inputs -- comm x_0..4, obs x_5..8, boundary x_9..11
     auto max3a = [](float a, float b, float c) { return fmaxf(fmaxf(fabsf(a), fabsf(b)), fabsf(c)); };
     auto range_raise = [&](float rc, float ro, float rb) {
-        if (fmaxf(fmaxf(rc * q.rng_inv[0], ro * q.rng_inv[1]), rb * q.rng_inv[2]) > 1.0f) *q.range_flag = 1u;
+        if (fmaxf(fmaxf(rc * rng_inv0, ro * rng_inv1), rb * rng_inv2) > 1.0f) *q.range_flag = 1u;
     };
 
     // ---- the producer of one tile's activation planes, as a list of items of one or two instructions each that the main
@@ -1032,7 +1043,8 @@ __global__ void __launch_bounds__(kMaxWorkgroup) pmi_mix_kernel(const MixParams 
     float *rv = reinterpret_cast<float *>(mix_lds + (size_t)kMixBatch * EN * RS);      // the reward slots as the rollout kernel left them
     if (blockIdx.x == 0 && tid == 0) {
         *f.pair_count = 0;
-        if (f.flags[0]) { f.flags[0] = 0; f.flags[1] += 1; }
+        const unsigned raised = f.flags[0];      // 1: the run-time range watch, 2: weights outside f16's range (device publish)
+        if (raised) { f.flags[0] = 0; f.flags[raised == 2u ? 2 : 1] += 1; }
     }
     // A workgroup takes kMixBatch consecutive groups of E instances (a group of one or a few instances per pass over the
     // lanes): with one group per workgroup the launch was bound by workgroup turnover (270 000 single-wavefront groups of
@@ -1193,8 +1205,7 @@ void pack_pmi_blob(const float *abi_blob, float *device_order, int H)
         for (int t4 = 0; t4 < KH / 4; ++t4)
             for (int l = 0; l < 64; ++l)
                 for (int q = 0; q < 4; ++q)
-                    dst[(((size_t)w * (KH / 4) + t4) * 64 + l) * 4 + q] =
-                        W1[(size_t)(2 * (4 * t4 + q) + (l >> 5)) * H + w * 32 + (l & 31)];
+                    dst[(((size_t)w * (KH / 4) + t4) * 64 + l) * 4 + q] = W1[(size_t)pmi_blob_row(t4, l, q) * H + w * 32 + (l & 31)];
 }
 
 // fc1 as three bf16 planes (x = hi + mid + lo by truncation, exact) in the B-operand order of
@@ -1208,16 +1219,9 @@ void pack_pmi_x6(const float *abi_blob, uint16_t *planes, int H)
         for (int s = 0; s < KS; ++s)
             for (int l = 0; l < 64; ++l)
                 for (int j = 0; j < 8; ++j) {
-                    float v = W1[(size_t)(16 * s + 8 * (l >> 5) + j) * H + w * 32 + (l & 31)];
-                    for (int p = 0; p < 3; ++p) {
-                        uint32_t u;
-                        memcpy(&u, &v, 4);
-                        u &= 0xFFFF0000u;
-                        float hi;
-                        memcpy(&hi, &u, 4);
-                        planes[((((size_t)w * 3 + p) * KS + s) * 64 + l) * 8 + j] = (uint16_t)(u >> 16);
-                        v -= hi;                     // exact: the remainder has at most 16 significant bits left
-                    }
+                    uint16_t part[3];
+                    pmi_split_x6(W1[(size_t)pmi_x6_row(s, l, j) * H + w * 32 + (l & 31)], part);
+                    for (int p = 0; p < 3; ++p) planes[((((size_t)w * 3 + p) * KS + s) * 64 + l) * 8 + j] = part[p];
                 }
 }
 
@@ -1247,16 +1251,8 @@ void pack_pmi_t3(const float *abi_blob, uint16_t *planes, int H, float T)
         for (int s = 0; s < KS; ++s)
             for (int l = 0; l < 64; ++l)
                 for (int j = 0; j < 8; ++j) {
-                    // k-position -> fc1 input: inside a block of 32, position q = 16 kh + r holds unit (r & 3) + 8 (r >> 2) + 4 kh,
-                    // the order in which pmi_score_t3_kernel's lanes store their activations
-                    const int kp = 16 * s + 8 * (l >> 5) + j, q = kp & 31, r = q & 15;
-                    const int row = (kp & ~31) + (r & 3) + 8 * (r >> 2) + 4 * (q >> 4);
-                    const float v = T * W1[(size_t)row * H + w * 32 + (l & 31)];
-                    const _Float16 hi = (_Float16)v;
-                    const _Float16 lo = (_Float16)(v - (float)hi);
-                    uint16_t bh, bl;
-                    memcpy(&bh, &hi, 2);
-                    memcpy(&bl, &lo, 2);
+                    uint16_t bh, bl;      // (the rows follow the order in which pmi_score_t3_kernel's lanes store their activations: pmi_t3_row)
+                    pmi_split_t3(W1[(size_t)pmi_t3_row(s, l, j) * H + w * 32 + (l & 31)], T, bh, bl);
                     planes[((((size_t)w * 2 + 0) * KS + s) * 64 + l) * 8 + j] = bh;
                     planes[((((size_t)w * 2 + 1) * KS + s) * 64 + l) * 8 + j] = bl;
                 }
@@ -1270,24 +1266,12 @@ void pack_pmi_t3(const float *abi_blob, uint16_t *planes, int H, float T)
 void pack_pmi_l1(const float *abi_blob, uint16_t *planes, int H, float S1)
 {
     const int NW = H / 32;
-    const int k0[3] = {0, 5, 9}, fan[3] = {5, 4, 3};
-    const size_t woff[3] = {0, (size_t)6 * H, (size_t)11 * H};
     for (int w = 0; w < NW; ++w)
         for (int j = 0; j < 3; ++j)
             for (int l = 0; l < 64; ++l)
                 for (int jj = 0; jj < 8; ++jj) {
-                    const int unit = 32 * w + (l & 31), k = 8 * (l >> 5) + jj;
-                    float v = 0.0f;
-                    if (k >= k0[j] && k < k0[j] + fan[j]) v = abi_blob[woff[j] + (size_t)(k - k0[j]) * H + unit];
-                    else if (k == 12) v = abi_blob[woff[j] + (size_t)fan[j] * H + unit];
-                    v *= S1;
-                    const _Float16 hi = (_Float16)v;
-                    const _Float16 lo = (_Float16)(v - (float)hi);
-                    const _Float16 hs = (_Float16)((float)hi * (1.0f / 2048.0f));
                     uint16_t bh, bl, bs;
-                    memcpy(&bh, &hi, 2);
-                    memcpy(&bl, &lo, 2);
-                    memcpy(&bs, &hs, 2);
+                    pmi_split_l1(pmi_l1_value(abi_blob, H, w, j, l, jj), S1, bh, bl, bs);
                     planes[((((size_t)w * 3 + j) * 3 + 0) * 64 + l) * 8 + jj] = bh;
                     planes[((((size_t)w * 3 + j) * 3 + 1) * 64 + l) * 8 + jj] = bl;
                     planes[((((size_t)w * 3 + j) * 3 + 2) * 64 + l) * 8 + jj] = bs;
@@ -1298,7 +1282,8 @@ void pack_pmi_l1(const float *abi_blob, uint16_t *planes, int H, float S1)
 __global__ void pmi_counters_reset_kernel(unsigned *pair_count, unsigned *flags)
 {
     *pair_count = 0;
-    if (flags[0]) { flags[0] = 0; flags[1] += 1; }
+    const unsigned raised = flags[0];
+    if (raised) { flags[0] = 0; flags[raised == 2u ? 2 : 1] += 1; }
 }
 
 hipError_t launch_pmi_counters_reset(const uavtrack_env *env, hipStream_t stream)
@@ -1335,6 +1320,8 @@ bool pmi_scheme_fits(int hidden_padded, bool f16_range_ok, int scheme)
 
 bool pmi_scheme_available(const uavtrack_env *env, int scheme)
 {
+    // (after a device publish the planes are always there and the verdict lives on the device: F16X3 is then never refused
+    // here -- unfit weights are scored by its stand-by, uavtrack_pmi_publish_info counts the chunks)
     return pmi_scheme_fits(env->pmi.hidden, env->pmi.t3 != nullptr, scheme);
 }
 
@@ -1348,15 +1335,13 @@ hipError_t launch_pmi_score(const uavtrack_env *env, const float *obs, hipStream
     q.x6 = env->pmi.x6;
     q.l1 = env->pmi.l1;
     q.t3 = env->pmi.t3;
-    q.t3_scale = env->pmi.t3_s1 * env->pmi.t3_t;
-    q.t3_inv_scale = 1.0f / q.t3_scale;
+    q.scal = env->pmi.scal;
     q.obs = obs;
     q.pairs = pairs ? pairs : env->pairs;
     q.pair_count = env->pair_count;
     q.scores = scores ? scores : env->scores;
     q.pair_total = env->pair_total;
     q.N = n_uav > 0 ? n_uav : env->cfg.n_uav;
-    for (int k = 0; k < 3; ++k) q.rng_inv[k] = env->pmi.rng_inv[k];
     q.range_flag = env->pmi_flags;
     q.gate = nullptr;
     const int cus = env->n_cus > 0 ? env->n_cus : 256;

@@ -72,6 +72,16 @@ class ReplayRing(C.Structure):
         ("capacity", C.c_int64), ("pos", C.c_int64), ("count", C.c_int64)]
 
 
+class PmiTensors(C.Structure):
+    """Mirror of `struct uavtrack_pmi_tensors` (include/uavtrack.h): 26 device pointers in PMI_STATE_KEYS order."""
+    _fields_ = [("t", C.c_void_p * 26)]
+
+
+# the float entries of the reference PMINetwork's state_dict, its order (= struct uavtrack_pmi_tensors)
+PMI_STATE_KEYS = tuple(f"{m}.{k}" for lin, bn in (("fc_comm", "bn_comm"), ("fc_obs", "bn_obs"),
+                                                   ("fc_boundary_state", "bn_boundary_state"), ("fc1", "bn1"))
+                       for m, k in ((lin, "weight"), (lin, "bias"), (bn, "weight"), (bn, "bias"),
+                                    (bn, "running_mean"), (bn, "running_var"))) + ("fc2.weight", "fc2.bias")
 PMI_TRAIN_TENSORS = 18                                    # PMINetwork.parameters()
 PMI_BN_LAYERS = 4                                         # BatchNorm1d layers (num_batches_tracked entries)
 LOSS_FORMS = ("reference", "per_sample")                  # enum uavtrack_actor_loss
@@ -94,6 +104,10 @@ SIGNATURES = {
     "uavtrack_set_pmi_weights": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int32, C.c_void_p]),
     "uavtrack_set_pmi_scheme": (C.c_int, [C.c_void_p, C.c_int32]),
     "uavtrack_pmi_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64), C.c_void_p]),
+    "uavtrack_publish_pmi_weights": (C.c_int, [C.c_void_p, C.POINTER(PmiTensors), C.c_int32, C.c_void_p]),
+    "uavtrack_pmi_publish_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64), C.c_void_p]),
+    "uavtrack_pmi_blob_floats": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]),
+    "uavtrack_get_pmi_blob": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     "uavtrack_pmi_inference": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
     "uavtrack_step": (C.c_int, [C.c_void_p] + [C.c_void_p] * 6 + [C.c_void_p]),
     "uavtrack_step_accumulate": (C.c_int, [C.c_void_p] + [C.c_void_p] * 7 + [C.c_void_p]),
@@ -135,6 +149,7 @@ SIGNATURES = {
     "uavtrack_pmi_trainer_get_optimizer_state": (C.c_int, [C.c_void_p] + [C.c_void_p] * 3 + [C.c_int64, C.c_void_p]),
     "uavtrack_pmi_trainer_train": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p,
                                               C.c_int64, C.c_int64] + [C.c_void_p] * 4),
+    "uavtrack_pmi_trainer_publish": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "uavtrack_pmi_trainer_check": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64), C.c_void_p]),
     "uavtrack_replay_create": (C.c_int, [C.POINTER(ReplayConfig), C.POINTER(C.c_void_p)]),
     "uavtrack_replay_destroy": (C.c_int, [C.c_void_p]),

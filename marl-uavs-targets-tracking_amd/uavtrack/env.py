@@ -339,6 +339,58 @@ class BatchedUavEnv(Handle):
         _lib.check(self._lib.uavtrack_set_pmi_weights(self._h, C.c_void_p(blob.ctypes.data), blob.size, hidden,
                                                       self._stream()), "uavtrack_set_pmi_weights")
 
+    @staticmethod
+    def _pmi_publish_tensors(source, device_index: int):
+        """The 26 tensors of publish_pmi's source, validated (ValueError) and contiguous -> (tensors, hidden)."""
+        sd = source.state_dict() if isinstance(source, torch.nn.Module) else source
+        keys = _lib.PMI_STATE_KEYS
+        missing = [k for k in keys if k not in sd]
+        if missing:
+            raise ValueError(f"publish_pmi: the source lacks the tensors {missing}")
+        ts = [sd[k] for k in keys]
+        for k, t in zip(keys, ts):
+            if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.device.type != "cuda" \
+                    or t.device.index != device_index:
+                raise ValueError(f"publish_pmi: {k} must be a float32 tensor on cuda:{device_index}")
+        H = ts[0].shape[0] if ts[0].dim() == 2 else -1
+        for b, fan in enumerate((5, 4, 3, 3 * H)):
+            if tuple(ts[6 * b].shape) != (H, fan) or any(tuple(t.shape) != (H,) for t in ts[6 * b + 1:6 * b + 6]):
+                raise ValueError(f"publish_pmi: the tensors of {keys[6 * b]} and its BatchNorm1d do not have the shapes of "
+                                 f"Linear({fan}, H) + BatchNorm1d(H), H = {H}")
+        if tuple(ts[24].shape) != (1, H) or ts[25].numel() != 1:
+            raise ValueError(f"publish_pmi: fc2 must be Linear({H}, 1), got weight {tuple(ts[24].shape)}")
+        return [t.detach().contiguous() for t in ts], int(H)
+
+    def publish_pmi(self, source) -> None:
+        """set_pmi without the host: BatchNorm fold, bounds, scales and every packed layout are computed on the device
+        from device tensors, stream-ordered (no copy to the host, no synchronisation; capturable), bit for bit what
+        set_pmi installs from the same numbers.  source: a DevicePMINetwork (its own state), a module with make_pmi_net's
+        parameter names, or a state dict of fp32 tensors on this device.  Weights of the same hidden width must be
+        installed (set_pmi sizes the allocation).  A non-contiguous tensor is made contiguous on the device; a missing
+        key, a wrong device, dtype or shape raises ValueError before anything is enqueued."""
+        if isinstance(source, DevicePMINetwork):
+            source.publish_pmi(self)
+            return
+        ts, H = self._pmi_publish_tensors(source, self._device_index)
+        arg = _lib.PmiTensors()
+        for k, t in enumerate(ts):
+            arg.t[k] = t.data_ptr()
+        _lib.check(self._lib.uavtrack_publish_pmi_weights(self._h, C.byref(arg), C.c_int32(H), self._stream()),
+                   "uavtrack_publish_pmi_weights")
+        # the launches read the tensors when they run: keep the contiguous copies alive until the next publish
+        self._pmi_publish_keep = ts
+
+    def pmi_blob(self) -> np.ndarray:
+        """The installed PMI weights allocation (csrc/pmi_pack.h: the fp32 blob in scorer order, the bf16 / f16 planes,
+        the scalar block) as uint32 words, read back to the host (synchronises): an inspection aid, e.g. to compare
+        set_pmi and publish_pmi bit for bit."""
+        n = C.c_int64(0)
+        _lib.check(self._lib.uavtrack_pmi_blob_floats(self._h, C.byref(n)), "uavtrack_pmi_blob_floats")
+        out = np.empty(n.value, np.uint32)
+        _lib.check(self._lib.uavtrack_get_pmi_blob(self._h, _lib.host_ptr(out), out.size, self._stream()),
+                   "uavtrack_get_pmi_blob")
+        return out
+
     def set_pmi_scheme(self, scheme: str = "auto") -> None:
         """Pin the MAAC-R pair scorer: "auto" (default: the fastest the weights allow), "f16x3", "bf16x6" or "fp32"
         (uavtrack_set_pmi_scheme).  Raises if the loaded weights cannot run on it."""
@@ -349,11 +401,20 @@ class BatchedUavEnv(Handle):
     def pmi_info(self) -> Dict[str, object]:
         """{"scheme": the scorer the next MAAC-R step launches (None without weights), "hidden_padded", "f16_range_ok": the
         host-side range guard passed, "rescored_chunks": chunks the wide-range kernel scored again because an operand left
-        f16's range at run time}.  Synchronises the stream."""
+        f16's range at run time}.  After a publish_pmi, "scheme" and "f16_range_ok" follow the verdict the device reached
+        (pmi_publish_info has the counters of that path).  Synchronises the stream."""
         out = (C.c_int64 * 4)()
         _lib.check(self._lib.uavtrack_pmi_info(self._h, out, self._stream()), "uavtrack_pmi_info")
         return dict(scheme=_lib.PMI_SCHEMES[out[0]] if out[0] else None, hidden_padded=int(out[1]), f16_range_ok=bool(out[2]),
                     rescored_chunks=int(out[3]))
+
+    def pmi_publish_info(self) -> Dict[str, object]:
+        """{"device_published": the installed weights come from publish_pmi (False after set_pmi), "unfit_chunks": chunks
+        the wide-range kernel scored because device-published weights did not fit f16's range -- counted apart from
+        pmi_info's "rescored_chunks", which stays the run-time range watch's}.  Synchronises the stream."""
+        pub = (C.c_int64 * 2)()
+        _lib.check(self._lib.uavtrack_pmi_publish_info(self._h, pub, self._stream()), "uavtrack_pmi_publish_info")
+        return dict(device_published=bool(pub[0]), unfit_chunks=int(pub[1]))
 
     def launch_info(self) -> Dict[str, int]:
         """Geometry of the most recent rollout launch (uavtrack_launch_info)."""

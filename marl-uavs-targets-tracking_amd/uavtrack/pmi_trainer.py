@@ -106,6 +106,13 @@ class DevicePMINetwork(Handle):
                                  bs)
         return float(avg) if sync else avg
 
+    def publish_pmi(self, env) -> None:
+        """This trainer's current network into env's MAAC-R scorer, folded and packed on the device
+        (uavtrack_pmi_trainer_publish): stream-ordered, no host copy, no synchronisation, capturable; bit for bit what
+        `env.set_pmi(self)` installs.  env must hold weights of this hidden width (set_pmi once, before the loop)."""
+        _lib.check(self._lib.uavtrack_pmi_trainer_publish(self._h, env._h, self._stream()),
+                   "uavtrack_pmi_trainer_publish")
+
     # ---- state
     def _get(self):
         st = np.empty(self.num_state, np.float32)
