@@ -14,6 +14,7 @@ update is the same rule on a sampled batch, and the new actor weights are re-upl
     python examples/train_maac.py --replay prioritized --learner device --envs 4096 --n-uav 20   # prioritised ring, 32.8 M slots
     python examples/train_maac.py --replay prioritized --learner device --publish device --log-every 10   # no host sync per iteration
     python examples/train_maac.py --method maac-r --pmi-trainer device --learner device --replay prioritized --publish device --log-every 10
+    python examples/train_maac.py --shards 8 --envs 32768 --n-uav 20 --learner device --replay prioritized --publish device   # 8 shard handles, one learner
 
 --method maac-r is the paper's method (configs/MAAC-R.yaml): the reward of every step is mixed in-kernel with the
 neighbours' rewards, weighted by the PMI network's scores (uav.py:262-291); that network is trained alongside on
@@ -60,6 +61,82 @@ def update(actor, critic, opt_a, opt_c, batch, gamma):
     return float(actor_loss.detach()), float(critic_loss.detach())
 
 
+def train_sharded(args, timings=None):
+    """--shards K: K environment handles over disjoint global environment ids, K rollouts, K prioritised rings, ONE
+    device learner.  Every update takes one gradient row from each ring and applies them in shard order
+    (update_from_many), each ring gets its own priorities back, and the new actor is published to every handle."""
+    dev = "cuda:0"
+    K = args.shards
+    torch.manual_seed(args.seed)
+    coop = args.cooperative if args.cooperative is not None else (0.0 if args.method == "maac" else 0.3)
+    mode = {"maac": uavtrack.RewardMode.RAW, "maac-g": uavtrack.RewardMode.MEAN}[args.method]
+    envs = []
+    for k in range(K):
+        off, cnt = uavtrack.shard_range(args.envs, k, K)
+        envs.append(uavtrack.BatchedUavEnv(uavtrack.EnvConfig(
+            n_envs=cnt, n_uav=args.n_uav, m_targets=args.m_targets, cooperative=coop, reward_mode=mode,
+            horizon=args.steps, env_offset=off), dev))
+    na_total = envs[0].cfg.na_total
+    actor = uavtrack.ActorMLP(hidden_dim=args.hidden, action_dim=na_total).to(dev)
+    per_shard = -(-args.batch // K)                                   # rows each ring contributes to one update
+    learner = uavtrack.DeviceActorCritic(12, args.hidden, na_total, args.actor_lr, args.critic_lr, args.gamma, dev,
+                                         loss=args.actor_loss, max_batch=per_shard)
+    actor.load_state_dict(learner.actor_state_dict())
+    rollouts = [uavtrack.BatchedRollout(e, actor, device_actor=True, seed=args.seed) for e in envs]
+    rings = [uavtrack.PrioritizedReplayRing(2 * e.cfg.n_envs * args.n_uav * args.steps, dev, alpha=args.alpha,
+                                            seed=args.seed + 7919 * k, max_batch=per_shard) for k, e in enumerate(envs)]
+    per_iter = args.envs * args.n_uav * args.steps
+    history, stamps, outs = [], [], [None] * K
+    t_log = time.perf_counter()
+    for it in range(args.iters):
+        log = (it + 1) % args.log_every == 0 or it == args.iters - 1
+        t0 = time.perf_counter()
+        eps = []
+        for k, (ro, ring) in enumerate(zip(rollouts, rings)):
+            ro.seed = args.seed + it
+            ro.reset(seed=1000 + it)
+            obs_in = ro.obs.clone()
+            res = ro.run_fused(args.steps, out=outs[k])
+            outs[k] = {key: v for key, v in res.items() if key != "ep_sums"}
+            ring.add_rollout(obs_in, res)
+            eps.append(res["ep_sums"])
+        if log:
+            torch.cuda.synchronize()
+        t_roll = time.perf_counter() - t0
+        for _ in range(args.updates):
+            la_t, lc_t, _ = learner.update_from_many(rings, per_shard)
+        la, lc = (float(la_t), float(lc_t)) if log else (la_t, lc_t)
+        if args.publish == "host":
+            actor.load_state_dict(learner.actor_state_dict())
+            for ro in rollouts:
+                ro.sync_actor()
+        else:
+            for e in envs:
+                learner.publish_actor(e)                              # one device pack per handle
+        ep = torch.cat(eps)                                           # [envs, 5] in global environment order
+        history.append(ep[:, 0].mean())
+        if not log:
+            continue
+        ret, cov = float(ep[:, 0].mean()), float(ep[:, 4].mean()) / args.steps
+        torch.cuda.synchronize()
+        now = time.perf_counter()
+        n_iter = it + 1 - (stamps[-1][0] if stamps else 0)
+        stamps.append((it + 1, now))
+        print(f"iter {it:3d}  shards {K}  episode return {ret:8.3f}  covered targets/step {cov:5.2f}  actor loss {la:+.4f}  "
+              f"critic loss {lc:.4f}  rollout {t_roll * 1e3:6.1f} ms ({per_iter / t_roll / 1e9:.2f} G agent-steps/s)  "
+              f"iteration {((now - t0) if args.log_every == 1 else (now - t_log) / n_iter) * 1e3:6.1f} ms", flush=True)
+        t_log = now
+    for ring in rings:
+        ring.check()                                                  # no draw was refused on the device
+    learner.check()                                                   # no update was refused on the device
+    for e in envs:
+        e.close()
+    history = [float(r) for r in history]
+    if timings is not None:
+        timings.extend(stamps)
+    return history
+
+
 def main(argv=None, timings=None):
     """Returns the episode return of every iteration.  timings (a list, optional) receives (iterations done, perf_counter)
     at every printed line, each taken after a synchronisation."""
@@ -104,6 +181,11 @@ def main(argv=None, timings=None):
                     help="--pmi-trainer device only: where train_pmi draws its index triples: torch's CPU generator (the "
                          "reference's stream; copies them to the device) or a device generator seeded with --seed (no "
                          "host work); auto: cpu with --publish host, device with --publish device")
+    ap.add_argument("--shards", type=int, default=1,
+                    help="split --envs into K environment handles (uavtrack.shard_range: disjoint global environment "
+                         "ids), each with its own rollout and prioritised ring, and take every update of the ONE learner "
+                         "from all K rings (DeviceActorCritic.update_from_many: one gradient row per ring, one apply); "
+                         "needs --learner device --replay prioritized")
     ap.add_argument("--log-every", type=int, default=1,
                     help="print (and so synchronise) every N iterations and after the last; the iteration time printed is "
                          "the mean over the iterations since the previous line, and with N > 1 the rollout time of a "
@@ -111,6 +193,17 @@ def main(argv=None, timings=None):
     args = ap.parse_args(argv)
     if args.log_every < 1:
         ap.error("--log-every must be >= 1")
+
+    if args.shards < 1 or args.shards > args.envs:
+        ap.error("--shards must be in [1, --envs]")
+    if args.shards > 1:
+        if args.learner != "device" or args.replay != "prioritized":
+            ap.error("--shards K > 1 needs --learner device --replay prioritized (one device learner updated from K "
+                     "prioritised rings)")
+        if args.method == "maac-r":
+            ap.error("--shards K > 1 supports --method maac and maac-g (the PMI trainer's BatchNorm uses batch "
+                     "statistics: its batch cannot be split without changing the function)")
+        return train_sharded(args, timings)
 
     dev = "cuda:0"
     torch.manual_seed(args.seed)

@@ -460,8 +460,53 @@ int uavtrack_learner_update(uavtrack_learner *learner, int64_t n,
                             const float *next_states, int64_t capacity, const int64_t *indices,
                             float *actor_loss, float *critic_loss, float *td_delta, float *priorities, void *stream);
 
-/* Synchronises `stream`; fails if any update since the previous check was refused on the device (bad action or
- * index).  refused (nullable) receives their number; the count restarts at 0. */
+/* ---- the split update: gradient rows and an ordered apply ----
+ * uavtrack_learner_update cut between "sum" and "scale + Adam", so that one update can take its batch from several
+ * rings, several calls (gradient accumulation) or several processes (data parallelism) with DEFINED bits: every sum is
+ * taken in a fixed order, so every participant that applies the same rows in the same order ends with the same
+ * parameters, and one row applied alone gives uavtrack_learner_update's bits.
+ *
+ * A gradient row is uavtrack_learner_row_floats = P + 8 fp32 words on the DEVICE (P = uavtrack_learner_num_params):
+ *   [0, P)      the unscaled gradient sums in parameter order (the actor's are sums of onehot(a) - p, times delta for
+ *               UAVTRACK_LOSS_PER_SAMPLE; the critic's sums of V - target): what the update forms before it scales
+ *   [P, P+4)    the loss sums: sum -log p, sum delta, sum -log p * delta, sum (V - target)^2
+ *   P+4, P+5    n of this row, an int64 as its low and high 32 bits
+ *   P+6         int32 status bits of this row: bit 0 an action outside [0, A), bit 1 an index outside [0, capacity)
+ *   P+7         int32 P, the layout tag
+ * The reference's actor loss mean(-log p) * mean(delta) is linear in mean(delta), which is why the rows can be summed:
+ * the apply scales the actor's sums once by the GLOBAL -mean(delta) / N.  (Averaging per-row updates or per-row loss
+ * gradients is a different rule.)
+ * All four calls are stream-ordered: no synchronisation, no allocation, capturable.  Host-side errors (a null required
+ * pointer, n < 1 or above the reserved batch, count outside [1, UAVTRACK_LEARNER_MAX_ROWS]) enqueue nothing. */
+#define UAVTRACK_LEARNER_MAX_ROWS 64   /* rows one apply takes: ranks x micro-batches */
+
+/* Words of a gradient row (P + 8). */
+int uavtrack_learner_row_floats(uavtrack_learner *learner, int64_t *out);
+
+/* The forwards, the backwards and the sums of uavtrack_learner_update on one batch (same arguments), into `row`
+ * (DEVICE, row_floats words).  td_delta [n] is required.  Changes no learner state except scratch: parameters, moments,
+ * steps and the verdict of the last apply stay.  Bad actions or indices are recorded in the row. */
+int uavtrack_learner_grad(uavtrack_learner *learner, int64_t n,
+                          const float *states, const int32_t *actions, const float *rewards,
+                          const float *next_states, int64_t capacity, const int64_t *indices,
+                          float *td_delta, float *row, void *stream);
+
+/* One update from rows [count][row_floats] (DEVICE): gradient and loss sums added in row order in fp32, N = sum of the
+ * rows' n, losses and scales as uavtrack_learner_update forms them from N, then both Adam steps and the step counts.
+ * If any row carries a status bit or another layout tag, the apply changes nothing (parameters, moments, steps), its
+ * losses are NaN and the next uavtrack_learner_check counts it: exactly a refused update.  The verdict stays on the
+ * handle for uavtrack_learner_write_priorities. */
+int uavtrack_learner_apply(uavtrack_learner *learner, const float *rows, int64_t count,
+                           float *actor_loss, float *critic_loss, void *stream);
+
+/* The priority write of uavtrack_learner_update for one row's batch: |td_delta[i]| into priorities[indices[i]]
+ * (indices == NULL: slot i), the last occurrence of a repeated slot winning.  Writes nothing if the most recent apply
+ * (or update) on this handle was refused, so a refused update leaves every participant's priorities alone. */
+int uavtrack_learner_write_priorities(uavtrack_learner *learner, int64_t n, const int64_t *indices, int64_t capacity,
+                                      const float *td_delta, float *priorities, void *stream);
+
+/* Synchronises `stream`; fails if any update or apply since the previous check was refused on the device (bad action
+ * or index, or a row of another layout).  refused (nullable) receives their number; the count restarts at 0. */
 int uavtrack_learner_check(uavtrack_learner *learner, int64_t *refused, void *stream);
 
 /* ---- the PMI trainer: PMINetwork.train_pmi + its Adam steps on the device ----

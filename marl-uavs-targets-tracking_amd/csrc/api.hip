@@ -1269,7 +1269,7 @@ Bufs scratch_bufs(LearnerDevice &d, int64_t max_n) { return {buf(d.td, max_n), b
 Bufs device_bufs(LearnerDevice &d)
 {
     const size_t P = (size_t)d.L.P;
-    return adam_bufs(d.opt) + Bufs{buf(d.params, P, true), buf(d.partials, kLearnerMaxGroups * (P + 4)), buf(d.scal, 2)} +
+    return adam_bufs(d.opt) + Bufs{buf(d.params, P, true), buf(d.gstatus, 1, true), buf(d.partials, kLearnerMaxGroups * (P + 4)), buf(d.scal, 2)} +
            scratch_bufs(d, d.max_n);
 }
 
@@ -1540,13 +1540,78 @@ int uavtrack_learner_update(uavtrack_learner *learner, int64_t n, const float *s
     return 0;
 }
 
+int uavtrack_learner_row_floats(uavtrack_learner *learner, int64_t *out)
+{
+    if (!learner || !out) return fail("uavtrack_learner_row_floats: null argument");
+    *out = (int64_t)learner->d.L.P + kLearnerRowTail;
+    return 0;
+}
+
+int uavtrack_learner_grad(uavtrack_learner *learner, int64_t n, const float *states, const int32_t *actions,
+                          const float *rewards, const float *next_states, int64_t capacity, const int64_t *indices,
+                          float *td_delta, float *row, void *stream)
+{
+    if (!learner) return fail("uavtrack_learner_grad: null handle");
+    if (!states || !actions || !rewards || !next_states)
+        return fail("uavtrack_learner_grad: states, actions, rewards and next_states must not be null");
+    if (!td_delta || !row) return fail("uavtrack_learner_grad: td_delta and row must not be null");
+    if (n < 1) return fail("uavtrack_learner_grad: n = %lld < 1", (long long)n);
+    if (n > learner->d.max_n)
+        return fail("uavtrack_learner_grad: n = %lld rows, scratch is reserved for %lld (uavtrack_learner_reserve)",
+                    (long long)n, (long long)learner->d.max_n);
+    if (capacity < 1) return fail("uavtrack_learner_grad: capacity = %lld < 1", (long long)capacity);
+    if (!indices && n > capacity)
+        return fail("uavtrack_learner_grad: n = %lld rows without indices from a store of %lld", (long long)n,
+                    (long long)capacity);
+    ON_DEVICE(learner->cfg.device_id);
+    LearnerLaunch q;
+    q.n = n; q.capacity = capacity;
+    q.states = states; q.rewards = rewards; q.next_states = next_states; q.actions = actions; q.idx = indices;
+    q.actor_loss = nullptr; q.critic_loss = nullptr; q.td_delta = td_delta; q.priorities = nullptr;
+    HIP_TRY(launch_learner_grad(learner->d, q, row, static_cast<hipStream_t>(stream)));
+    return 0;
+}
+
+int uavtrack_learner_apply(uavtrack_learner *learner, const float *rows, int64_t count, float *actor_loss,
+                           float *critic_loss, void *stream)
+{
+    if (!learner) return fail("uavtrack_learner_apply: null handle");
+    if (!rows) return fail("uavtrack_learner_apply: rows must not be null");
+    if (!actor_loss || !critic_loss) return fail("uavtrack_learner_apply: actor_loss and critic_loss must not be null");
+    if (count < 1 || count > UAVTRACK_LEARNER_MAX_ROWS)
+        return fail("uavtrack_learner_apply: count = %lld out of range [1, %d]", (long long)count, UAVTRACK_LEARNER_MAX_ROWS);
+    ON_DEVICE(learner->cfg.device_id);
+    HIP_TRY(launch_learner_apply(learner->d, rows, (int)count, actor_loss, critic_loss, static_cast<hipStream_t>(stream)));
+    return 0;
+}
+
+int uavtrack_learner_write_priorities(uavtrack_learner *learner, int64_t n, const int64_t *indices, int64_t capacity,
+                                      const float *td_delta, float *priorities, void *stream)
+{
+    if (!learner) return fail("uavtrack_learner_write_priorities: null handle");
+    if (!td_delta || !priorities) return fail("uavtrack_learner_write_priorities: td_delta and priorities must not be null");
+    if (n < 1) return fail("uavtrack_learner_write_priorities: n = %lld < 1", (long long)n);
+    if (n > learner->d.max_n)
+        return fail("uavtrack_learner_write_priorities: n = %lld rows, scratch is reserved for %lld "
+                    "(uavtrack_learner_reserve)", (long long)n, (long long)learner->d.max_n);
+    if (capacity < 1) return fail("uavtrack_learner_write_priorities: capacity = %lld < 1", (long long)capacity);
+    if (!indices && n > capacity)
+        return fail("uavtrack_learner_write_priorities: n = %lld rows without indices into a store of %lld", (long long)n,
+                    (long long)capacity);
+    ON_DEVICE(learner->cfg.device_id);
+    HIP_TRY(launch_learner_priorities(learner->d, indices, n, capacity, td_delta, priorities,
+                                      static_cast<hipStream_t>(stream)));
+    return 0;
+}
+
 int uavtrack_learner_check(uavtrack_learner *learner, int64_t *refused, void *stream)
 {
     int count = 0;
     if (take_refusals(__func__, learner, refused, stream, &count)) return 1;
     if (count)
         return fail("uavtrack_learner_check: %d update(s) refused: an action outside [0, %d) or an index outside "
-                    "[0, capacity); they changed nothing", count, learner->d.L.A);
+                    "[0, capacity), or (uavtrack_learner_apply) a gradient row of another layout; they changed nothing",
+                    count, learner->d.L.A);
     return 0;
 }
 

@@ -284,6 +284,7 @@ constexpr int kLearnerTensors = 8;
 constexpr int kLearnerMaxHidden = 256;
 constexpr int kLearnerMaxActions = 48;
 constexpr int kLearnerMaxGroups = 256;        // workgroups of the gradient kernel (= gradient partial rows)
+constexpr int kLearnerRowTail = 8;            // words behind the P gradient sums of a gradient row: 4 loss sums, n (2), status, P
 struct LearnerLayout {
     int H, A, P;
     int a_w1, a_b1, a_w2, a_b2, c_w1, c_b1, c_w2, c_b2;
@@ -314,7 +315,8 @@ struct LearnerDevice {
     float gamma, actor_lr, critic_lr;
     int per_sample;
     float *params;                  // [P]
-    AdamState opt;                  // kLearnerTensors tensors over [P]
+    AdamState opt;                  // kLearnerTensors tensors over [P]; opt.status: the last update's / apply's verdict
+    int *gstatus;                   // [1] input errors of the last uavtrack_learner_grad (they travel in its row)
     float *partials;                // [kLearnerMaxGroups][P + 4]
     float *scal;                    // [2] gradient scales of the current update
     float *td;                      // [max_n] td_delta when the caller passes none
@@ -333,6 +335,13 @@ size_t learner_lds_bytes(const LearnerLayout &L, int rows);
 int learner_groups(const LearnerLayout &L, int64_t n);
 hipError_t learner_prepare_kernels(const LearnerLayout &L);
 hipError_t launch_learner_update(const LearnerDevice &d, const LearnerLaunch &q, hipStream_t stream);
+// the split update: gradient row [P + kLearnerRowTail] <- one batch; rows [count][P + kLearnerRowTail] -> both Adam steps;
+// the priority write gated on the last apply's verdict
+hipError_t launch_learner_grad(const LearnerDevice &d, const LearnerLaunch &q, float *row, hipStream_t stream);
+hipError_t launch_learner_apply(const LearnerDevice &d, const float *rows, int count, float *actor_loss,
+                                float *critic_loss, hipStream_t stream);
+hipError_t launch_learner_priorities(const LearnerDevice &d, const int64_t *idx, int64_t n, int64_t capacity,
+                                     const float *td, float *prio, hipStream_t stream);
 
 // pmi_train_kernel.hip -- the device PMI trainer (uavtrack_pmi_trainer_*).  `state` holds the float entries of the
 // reference PMINetwork's state_dict in its order (26 tensors: per Linear+BatchNorm1d block weight, bias, bn weight, bn

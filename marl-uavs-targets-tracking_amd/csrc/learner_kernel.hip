@@ -12,6 +12,7 @@
 //   learner_prio_*           |delta| into the priorities at the sampled slots, the last occurrence of a slot in the
 //                            batch winning (a claim / max-row / mark / write chain: no float atomics anywhere).
 // Nothing depends on timing, so two identical calls give bitwise identical results.
+// The split form (learner_reduce_kernel, learner_apply_*) cuts the same chain after the sums: see below.
 //
 // The sums are arranged so the reference's broadcast actor loss costs nothing extra: with
 // actor_loss = mean_i(-log p_i) * mean_j(delta_j), dL/dz_i = -mean(delta) (onehot(a_i) - p_i) / n, so the grad kernel
@@ -259,6 +260,77 @@ __global__ void learner_adam_kernel(float *params, float *m, float *v, const flo
     adam_element(params[p], m[p], v[p], g, steps[L.tensor_of(p)], actor ? actor_lr : critic_lr);
 }
 
+// ---- the split update (uavtrack_learner_grad / _apply / _write_priorities): the update cut between "sum" and "scale +
+// Adam".  A gradient row is [P + kLearnerRowTail] words: the P unscaled gradient sums exactly as learner_adam_kernel
+// forms g before it scales, the four loss sums as learner_finalize_kernel forms them, then n (int64 as two words), the
+// row's status bits and P as a layout tag.  Every sum keeps a fixed order (workgroups ascending inside a row, rows
+// ascending in the apply), so whoever applies the same rows in the same order gets the same bits, and one row gives the
+// bits of the closed update (0.0f + x == x bitwise: a sum that starts from +0 is never -0).
+
+// One thread per word of the row: the workgroup partials summed in workgroup order.
+__global__ void learner_reduce_kernel(const float *partials, int groups, int P, int64_t n, const int *status, float *row)
+{
+    const int p = blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= P + kLearnerRowTail) return;
+    if (p < P + 4) {
+        float g = 0.0f;
+        for (int w = 0; w < groups; ++w) g += partials[(size_t)w * (P + 4) + p];
+        row[p] = g;
+        return;
+    }
+    int32_t *tail = reinterpret_cast<int32_t *>(row);
+    const uint64_t un = (uint64_t)n;
+    const int q = p - (P + 4);
+    tail[p] = q == 0 ? (int32_t)(uint32_t)(un & 0xFFFFFFFFu) : q == 1 ? (int32_t)(uint32_t)(un >> 32) : q == 2 ? *status : P;
+}
+
+// One thread: the rows' verdict into the status word, the loss sums added in row order, N = sum of the rows' n; then
+// losses, scales, refusal count and step counters by learner_finalize_kernel's formulas.
+__global__ void learner_apply_begin_kernel(const float *rows, int count, int P, int per_sample, int *status, int *errors,
+                                           int64_t *steps, float *scal, float *actor_loss, float *critic_loss)
+{
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    const size_t stride = (size_t)P + kLearnerRowTail;
+    float sum[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+    int64_t N = 0;
+    int bad = 0;
+    for (int r = 0; r < count; ++r) {
+        const float *row = rows + r * stride;
+        const int32_t *tail = reinterpret_cast<const int32_t *>(row);
+        for (int q = 0; q < 4; ++q) sum[q] += row[P + q];
+        const int64_t nr = (int64_t)((uint64_t)(uint32_t)tail[P + 4] | ((uint64_t)(uint32_t)tail[P + 5] << 32));
+        bad |= tail[P + 6] & 3;
+        if (tail[P + 7] != P || nr < 1) bad |= 4;               // a row of another layout (or not a row at all)
+        else N += nr;
+    }
+    *status = bad;
+    const float inv_n = 1.0f / (float)N;
+    const float mean_nlp = sum[0] * inv_n, mean_delta = sum[1] * inv_n;
+    const float al = per_sample ? sum[2] * inv_n : mean_nlp * mean_delta;
+    const float cl = sum[3] * inv_n;
+    if (actor_loss) *actor_loss = bad ? NAN : al;
+    if (critic_loss) *critic_loss = bad ? NAN : cl;
+    scal[0] = per_sample ? -inv_n : -mean_delta * inv_n;
+    scal[1] = 2.0f * inv_n;
+    if (bad) { *errors += 1; return; }
+    for (int q = 0; q < kLearnerTensors; ++q) steps[q] += 1;
+}
+
+// Both Adam steps on the rows' gradient sums, added in row order and scaled once.
+__global__ void learner_apply_adam_kernel(float *params, float *m, float *v, const float *rows, int count, LearnerLayout L,
+                                          const int *status, const int64_t *steps, const float *scal, float actor_lr,
+                                          float critic_lr)
+{
+    const int p = blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= L.P || *status) return;
+    const size_t stride = (size_t)L.P + kLearnerRowTail;
+    float g = 0.0f;
+    for (int r = 0; r < count; ++r) g += rows[r * stride + p];
+    const bool actor = p < L.c_w1;
+    g *= actor ? scal[0] : scal[1];
+    adam_element(params[p], m[p], v[p], g, steps[L.tensor_of(p)], actor ? actor_lr : critic_lr);
+}
+
 // the priorities: claim every sampled slot, keep the largest batch row per slot, mark it, write |delta| from it
 __global__ void learner_prio_claim_kernel(const int64_t *idx, int64_t n, int64_t capacity, float *prio, const int *status)
 {
@@ -320,22 +392,49 @@ hipError_t learner_prepare_kernels(const LearnerLayout &L)
                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
 }
 
-hipError_t launch_learner_update(const LearnerDevice &d, const LearnerLaunch &q, hipStream_t st)
+namespace {
+
+hipError_t launch_grad(const LearnerDevice &d, const LearnerLaunch &q, float *td, int *status, hipStream_t st)
 {
     const LearnerLayout &L = d.L;
     const int R = learner_rows_per_tile(L.H);
-    const int groups = learner_groups(L, q.n);
-    hipLaunchKernelGGL(learner_begin_kernel, dim3(1), dim3(64), 0, st, d.opt.status);
+    hipLaunchKernelGGL(learner_begin_kernel, dim3(1), dim3(64), 0, st, status);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
 
     GradArgs a;
     a.params = d.params; a.states = q.states; a.rewards = q.rewards; a.next_states = q.next_states;
     a.actions = q.actions; a.idx = q.idx; a.n = q.n; a.capacity = q.capacity;
-    a.partials = d.partials; a.td_delta = q.td_delta ? q.td_delta : d.td; a.status = d.opt.status;
+    a.partials = d.partials; a.td_delta = td; a.status = status;
     a.L = L; a.rows = R; a.gamma = d.gamma; a.per_sample = d.per_sample;
-    hipLaunchKernelGGL(learner_grad_kernel, dim3(groups), dim3(kLW), learner_lds_bytes(L, R), st, a);
+    hipLaunchKernelGGL(learner_grad_kernel, dim3(learner_groups(L, q.n)), dim3(kLW), learner_lds_bytes(L, R), st, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_prio(const LearnerDevice &d, const int64_t *idx, int64_t n, int64_t capacity, const float *td,
+                       float *prio, hipStream_t st)
+{
+    const dim3 grid((unsigned)((n + 255) / 256)), blk(256);
+    hipError_t e;
+    hipLaunchKernelGGL(learner_prio_claim_kernel, grid, blk, 0, st, idx, n, capacity, prio, d.opt.status);
     if ((e = hipGetLastError()) != hipSuccess) return e;
+    hipLaunchKernelGGL(learner_prio_max_kernel, grid, blk, 0, st, idx, n, capacity, prio, d.opt.status);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    hipLaunchKernelGGL(learner_prio_mark_kernel, grid, blk, 0, st, idx, n, capacity, prio, d.last, d.opt.status);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    hipLaunchKernelGGL(learner_prio_write_kernel, grid, blk, 0, st, idx, n, td, prio, d.last, d.opt.status);
+    return hipGetLastError();
+}
+
+}  // namespace
+
+hipError_t launch_learner_update(const LearnerDevice &d, const LearnerLaunch &q, hipStream_t st)
+{
+    const LearnerLayout &L = d.L;
+    const int groups = learner_groups(L, q.n);
+    float *td = q.td_delta ? q.td_delta : d.td;
+    hipError_t e = launch_grad(d, q, td, d.opt.status, st);
+    if (e != hipSuccess) return e;
 
     hipLaunchKernelGGL(learner_finalize_kernel, dim3(1), dim3(64), 0, st, d.partials, groups, L, q.n, d.per_sample,
                        d.opt.status, d.opt.errors, d.opt.steps, d.scal, q.actor_loss, q.critic_loss);
@@ -345,20 +444,39 @@ hipError_t launch_learner_update(const LearnerDevice &d, const LearnerLaunch &q,
                        d.partials, groups, L, d.opt.status, d.opt.steps, d.scal, d.actor_lr, d.critic_lr);
     if ((e = hipGetLastError()) != hipSuccess) return e;
 
-    if (q.priorities) {
-        const dim3 grid((unsigned)((q.n + 255) / 256)), blk(256);
-        const float *td = q.td_delta ? q.td_delta : d.td;
-        hipLaunchKernelGGL(learner_prio_claim_kernel, grid, blk, 0, st, q.idx, q.n, q.capacity, q.priorities, d.opt.status);
-        if ((e = hipGetLastError()) != hipSuccess) return e;
-        hipLaunchKernelGGL(learner_prio_max_kernel, grid, blk, 0, st, q.idx, q.n, q.capacity, q.priorities, d.opt.status);
-        if ((e = hipGetLastError()) != hipSuccess) return e;
-        hipLaunchKernelGGL(learner_prio_mark_kernel, grid, blk, 0, st, q.idx, q.n, q.capacity, q.priorities, d.last,
-                           d.opt.status);
-        if ((e = hipGetLastError()) != hipSuccess) return e;
-        hipLaunchKernelGGL(learner_prio_write_kernel, grid, blk, 0, st, q.idx, q.n, td, q.priorities, d.last, d.opt.status);
-        if ((e = hipGetLastError()) != hipSuccess) return e;
-    }
+    if (q.priorities) return launch_prio(d, q.idx, q.n, q.capacity, td, q.priorities, st);
     return hipSuccess;
+}
+
+// The gradient half of the split update: q.td_delta is required, q.actor_loss / critic_loss / priorities are not used.
+// The bad-input bits go to the handle's grad status word, so the verdict of the last apply stays in opt.status.
+hipError_t launch_learner_grad(const LearnerDevice &d, const LearnerLaunch &q, float *row, hipStream_t st)
+{
+    const int P = d.L.P;
+    hipError_t e = launch_grad(d, q, q.td_delta, d.gstatus, st);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(learner_reduce_kernel, dim3((P + kLearnerRowTail + 255) / 256), dim3(256), 0, st, d.partials,
+                       learner_groups(d.L, q.n), P, q.n, d.gstatus, row);
+    return hipGetLastError();
+}
+
+hipError_t launch_learner_apply(const LearnerDevice &d, const float *rows, int count, float *actor_loss,
+                                float *critic_loss, hipStream_t st)
+{
+    const LearnerLayout &L = d.L;
+    hipLaunchKernelGGL(learner_apply_begin_kernel, dim3(1), dim3(64), 0, st, rows, count, L.P, d.per_sample, d.opt.status,
+                       d.opt.errors, d.opt.steps, d.scal, actor_loss, critic_loss);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(learner_apply_adam_kernel, dim3((L.P + 255) / 256), dim3(256), 0, st, d.params, d.opt.m, d.opt.v,
+                       rows, count, L, d.opt.status, d.opt.steps, d.scal, d.actor_lr, d.critic_lr);
+    return hipGetLastError();
+}
+
+hipError_t launch_learner_priorities(const LearnerDevice &d, const int64_t *idx, int64_t n, int64_t capacity,
+                                     const float *td, float *prio, hipStream_t st)
+{
+    return launch_prio(d, idx, n, capacity, td, prio, st);
 }
 
 }  // namespace uavtrack

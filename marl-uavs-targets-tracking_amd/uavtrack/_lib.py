@@ -85,6 +85,8 @@ PMI_STATE_KEYS = tuple(f"{m}.{k}" for lin, bn in (("fc_comm", "bn_comm"), ("fc_o
 PMI_TRAIN_TENSORS = 18                                    # PMINetwork.parameters()
 PMI_BN_LAYERS = 4                                         # BatchNorm1d layers (num_batches_tracked entries)
 LOSS_FORMS = ("reference", "per_sample")                  # enum uavtrack_actor_loss
+LEARNER_ROW_TAIL = 8                                      # words behind the P gradient sums of a gradient row
+LEARNER_MAX_ROWS = 64                                     # UAVTRACK_LEARNER_MAX_ROWS
 LEARNER_TENSORS = 8                                       # parameter tensors: actor fc1.w fc1.b fc2.w fc2.b, critic likewise
 ACTOR_SAMPLE, ACTOR_ARGMAX = 0, 1   # enum in include/uavtrack.h
 PROF_CLASSES = ("rollout", "scorer", "mix", "ep_sums")   # UAVTRACK_PROF_* in include/uavtrack.h
@@ -138,6 +140,10 @@ SIGNATURES = {
     "uavtrack_learner_set_optimizer_state": (C.c_int, [C.c_void_p] + [C.c_void_p] * 3 + [C.c_int64, C.c_void_p]),
     "uavtrack_learner_get_optimizer_state": (C.c_int, [C.c_void_p] + [C.c_void_p] * 3 + [C.c_int64, C.c_void_p]),
     "uavtrack_learner_update": (C.c_int, [C.c_void_p, C.c_int64] + [C.c_void_p] * 4 + [C.c_int64] + [C.c_void_p] * 6),
+    "uavtrack_learner_row_floats": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]),
+    "uavtrack_learner_grad": (C.c_int, [C.c_void_p, C.c_int64] + [C.c_void_p] * 4 + [C.c_int64] + [C.c_void_p] * 4),
+    "uavtrack_learner_apply": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "uavtrack_learner_write_priorities": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64] + [C.c_void_p] * 3),
     "uavtrack_learner_check": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64), C.c_void_p]),
     "uavtrack_pmi_trainer_create": (C.c_int, [C.POINTER(PmiTrainerConfig), C.POINTER(C.c_void_p)]),
     "uavtrack_pmi_trainer_destroy": (C.c_int, [C.c_void_p]),

@@ -6,6 +6,11 @@ train.py:262 written back -- stream-ordered, with no synchronisation and no allo
 The actor loss of the reference broadcasts: log_probs is [n, 1], td_delta is [n], so `-log_probs * td_delta` is
 [n, n] and actor_loss = mean_i(-log p_i) * mean_j(delta_j).  That is the default here (loss="reference");
 loss="per_sample" is mean_i(-log p_i * delta_i), the form examples/train_maac.py's PyTorch learner trains with.
+
+The same update also comes in pieces (uavtrack_learner_grad / _apply / _write_priorities): grad_from leaves a batch's
+unscaled sums in a device gradient row, apply adds rows in row order, scales once and steps Adam.  update_from_many
+(several rings, one GPU) and update_from(..., group=...) (one ring per rank) are built on them; every participant that
+applies the same rows in the same order ends with the same bits, and one row is bit for bit `update`.
 """
 from __future__ import annotations
 
@@ -25,6 +30,18 @@ from .adam import flat, from_state_dict, split, to_state_dict
 from .replay import DeviceReplayBuffer, PrioritizedDeviceReplayBuffer
 from .replay_ring import PrioritizedReplayRing
 from .rollout import ActorMLP
+
+
+def num_params(hidden_dim: int, action_dim: int) -> int:
+    """Floats of the learner's parameter blob: actor fc1 (12 H + H), fc2 (A H + A), critic fc1 (12 H + H), fc2 (H + 1)."""
+    H, A = int(hidden_dim), int(action_dim)
+    return 27 * H + A * H + A + 1
+
+
+def row_floats(hidden_dim: int, action_dim: int) -> int:
+    """Words of one gradient row of the split update (include/uavtrack.h): the P gradient sums, four loss sums, n as
+    two words, the row's status bits and the layout tag P."""
+    return num_params(hidden_dim, action_dim) + _lib.LEARNER_ROW_TAIL
 
 
 class ValueMLP(torch.nn.Module):
@@ -64,6 +81,7 @@ class DeviceActorCritic(Handle):
         n = C.c_int64()
         _lib.check(self._lib.uavtrack_learner_num_params(self._h, C.byref(n)), "uavtrack_learner_num_params")
         self.num_params = n.value
+        self.row_floats = row_floats(self.hidden_dim, self.action_dim)     # = uavtrack_learner_row_floats
         self._set_params(flat(self._params()))
 
     def _params(self):
@@ -114,13 +132,21 @@ class DeviceActorCritic(Handle):
         return self._run(n, store, n, None, None)
 
     def update_from(self, buffer, batch_size: int, beta: float = 0.4,
-                    generator: Optional[torch.Generator] = None):
+                    generator: Optional[torch.Generator] = None, group=None):
         """buffer.sample(batch_size) + update + (prioritised buffer) update_priorities(indices, |td_delta|)
         (train.py:253-262), the gather and the priority write inside the library call.  The indices are drawn as
         the buffer's own sample() draws them.  beta only weights the importance weights, which the reference's
         update does not use.  For a PrioritizedReplayRing the draw is one library call of its own (the ring's seed
         and device call counter; `generator` does not apply), so the whole update is two library calls with no torch
-        kernel between them, and can be captured into a graph."""
+        kernel between them, and can be captured into a graph.
+
+        With a torch.distributed `group`, every rank of it takes ONE common update from all ranks' batches: the
+        gradient row of this rank's batch (grad_from), an all-gather of the rows in rank order
+        (sharding.gather_learner_rows), the apply of all of them, and the priority write into this rank's buffer.
+        Ranks that start equal (sharding.broadcast_learner) stay bitwise equal; batch sizes may differ between ranks.
+        The returned losses are the global ones, td_delta this rank's."""
+        if group is not None:
+            return self._update_from_group(buffer, batch_size, generator, group)
         k = min(int(batch_size), buffer.count)
         if k < 1:
             raise ValueError("update_from: the buffer is empty")
@@ -135,6 +161,97 @@ class DeviceActorCritic(Handle):
             idx = torch.randperm(buffer.count, device=buffer.device, generator=generator)[:k]
             prio = None
         return self._run(k, buffer.store, buffer.capacity, idx, prio)
+
+    # ---- the split update: gradient rows and an ordered apply
+    def _draw_from(self, buffer, k: int, generator: Optional[torch.Generator]):
+        """(indices, priorities or None) of one batch of k rows, drawn as the buffer's own sample() draws them."""
+        if isinstance(buffer, PrioritizedReplayRing):
+            return buffer._draw_into(k), buffer.priorities
+        if isinstance(buffer, PrioritizedDeviceReplayBuffer):
+            prob = buffer.priorities[:buffer.count] ** buffer.alpha
+            prob = prob / prob.sum()
+            return torch.multinomial(prob, k, replacement=True, generator=generator), buffer.priorities
+        return torch.randperm(buffer.count, device=buffer.device, generator=generator)[:k], None
+
+    def new_rows(self, count: int) -> torch.Tensor:
+        """A [count, row_floats] device tensor for `count` gradient rows (pass rows[k] to grad_from as `row`)."""
+        return torch.empty(int(count), self.row_floats, device=self.device)
+
+    def _grad(self, n: int, store: Dict[str, torch.Tensor], capacity: int, idx: Optional[torch.Tensor],
+              row: Optional[torch.Tensor] = None, td: Optional[torch.Tensor] = None):
+        if row is None:
+            row = torch.empty(self.row_floats, device=self.device)
+        elif row.numel() != self.row_floats or row.dtype != torch.float32 or not row.is_contiguous() \
+                or row.device != self.device:
+            raise ValueError(f"row must be a contiguous float32 tensor of {self.row_floats} words on {self.device}")
+        if td is None:
+            td = torch.empty(n, device=self.device)
+        _lib.check(self._lib.uavtrack_learner_grad(
+            self._h, n, _ptr(store["states"]), _ptr(store["actions"]), _ptr(store["rewards"]),
+            _ptr(store["next_states"]), capacity, _ptr(idx), _ptr(td), _ptr(row), self._stream()),
+            "uavtrack_learner_grad")
+        return row, td
+
+    def grad_from(self, buffer, batch_size: int, row: Optional[torch.Tensor] = None,
+                  generator: Optional[torch.Generator] = None):
+        """The gradient half of update_from: draws min(batch_size, buffer.count) rows as update_from does (for a
+        PrioritizedReplayRing the ring's own library call) and leaves their unscaled gradient and loss sums in `row`
+        (a new tensor if None).  Returns (row, td_delta, indices); changes nothing in the learner.  The indices of a
+        PrioritizedReplayRing live in the ring's own draw tensor until its next draw: call write_priorities (or clone
+        them) before drawing from the same ring again."""
+        k = min(int(batch_size), buffer.count)
+        if k < 1:
+            raise ValueError("grad_from: the buffer is empty")
+        idx, _ = self._draw_from(buffer, k, generator)
+        row, td = self._grad(k, buffer.store, buffer.capacity, idx, row)
+        return row, td, idx
+
+    def apply(self, rows):
+        """One update from gradient rows ([count, row_floats], or a sequence of rows): the sums added in row order, one
+        global scale, both Adam steps.  Returns (actor_loss, critic_loss) as device tensors, without synchronising.  A
+        row that carries a refusal (or another learner's layout) refuses the whole update, on every participant."""
+        if not torch.is_tensor(rows):
+            rows = torch.stack([r.reshape(-1) for r in rows])
+        rows = rows.reshape(-1, rows.shape[-1])
+        if rows.shape[1] != self.row_floats or rows.dtype != torch.float32 or rows.device != self.device:
+            raise ValueError(f"rows must be float32 [count, {self.row_floats}] on {self.device}, got "
+                             f"{tuple(rows.shape)} {rows.dtype} on {rows.device}")
+        rows = rows.contiguous()
+        losses = torch.empty(2, device=self.device)
+        _lib.check(self._lib.uavtrack_learner_apply(self._h, _ptr(rows), rows.shape[0], _ptr(losses[0:1]),
+                                                    _ptr(losses[1:2]), self._stream()), "uavtrack_learner_apply")
+        return losses[0], losses[1]
+
+    def write_priorities(self, buffer, idx: Optional[torch.Tensor], td: torch.Tensor) -> None:
+        """|td| into a prioritised buffer's priorities at idx (the last occurrence of a repeated slot winning), unless
+        the most recent apply on this learner was refused.  A buffer without priorities is left alone."""
+        prio = getattr(buffer, "priorities", None)
+        if prio is None:
+            return
+        _lib.check(self._lib.uavtrack_learner_write_priorities(self._h, td.numel(), _ptr(idx), buffer.capacity,
+                                                               _ptr(td), _ptr(prio), self._stream()),
+                   "uavtrack_learner_write_priorities")
+
+    def update_from_many(self, buffers, batch_size: int, generator: Optional[torch.Generator] = None):
+        """ONE update from several buffers on this device (the shards of one GPU): one gradient row per buffer from
+        min(batch_size, its count) of its rows, the rows applied in list order, each prioritised buffer's priorities
+        written back from its own draw.  Returns (actor_loss, critic_loss, [td_delta per buffer])."""
+        buffers = list(buffers)
+        if not 1 <= len(buffers) <= _lib.LEARNER_MAX_ROWS:
+            raise ValueError(f"update_from_many: {len(buffers)} buffers, one apply takes 1 to {_lib.LEARNER_MAX_ROWS} rows")
+        rows = self.new_rows(len(buffers))
+        drawn = [self.grad_from(b, batch_size, rows[k], generator) for k, b in enumerate(buffers)]
+        al, cl = self.apply(rows)
+        for b, (_, td, idx) in zip(buffers, drawn):
+            self.write_priorities(b, idx, td)
+        return al, cl, [td for _, td, _ in drawn]
+
+    def _update_from_group(self, buffer, batch_size: int, generator, group):
+        from .sharding import gather_learner_rows
+        row, td, idx = self.grad_from(buffer, batch_size, None, generator)
+        al, cl = self.apply(gather_learner_rows(row, group))
+        self.write_priorities(buffer, idx, td)
+        return al, cl, td
 
     def publish_actor(self, env) -> None:
         """The actor's current parameters into env's rollout actor, packed on the device (uavtrack_learner_publish_actor):
@@ -162,6 +279,11 @@ class DeviceActorCritic(Handle):
         """(exp_avg [P], exp_avg_sq [P], step [8]) as numpy arrays: the actor's parameters, then the critic's."""
         return adam.read(self._lib.uavtrack_learner_get_optimizer_state, self._h, self.num_params,
                          _lib.LEARNER_TENSORS, self._stream())
+
+    def _set_optim_state(self, exp_avg: np.ndarray, exp_avg_sq: np.ndarray, step: np.ndarray) -> None:
+        """_optim_state's inverse."""
+        adam.write(self._lib.uavtrack_learner_set_optimizer_state, self._h, np.ascontiguousarray(exp_avg, np.float32),
+                   np.ascontiguousarray(exp_avg_sq, np.float32), np.ascontiguousarray(step, np.int64), self._stream())
 
     def _optimizers(self):
         """(parameters, lr, float span, tensor span) of the actor's and the critic's Adam in the flat state."""

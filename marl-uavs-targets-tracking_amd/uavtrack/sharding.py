@@ -174,3 +174,51 @@ def gather_transitions_async(sample, group=None) -> TransitionGather:
 def gather_transitions(sample, group=None):
     """Blocking form: {"states" [R K, 12], "actions", "rewards", "next_states", "index"} on every rank."""
     return gather_transitions_async(sample, group).wait()
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Data-parallel learners.  Each rank holds a shard, its own replay ring and a DeviceActorCritic; one update is the
+# gradient row of every rank's batch (DeviceActorCritic.grad_from), ONE all-gather of the rows in rank order, and the
+# same ordered apply on every rank (DeviceActorCritic.update_from(..., group=...)).  The rows travel as int32 bit views
+# (their tail words are integers), so no backend touches a bit.
+
+
+def gather_learner_rows(row, group=None):
+    """All-gather of one gradient row per rank into [world, row_floats], rank-major, on the row's device.  Without a
+    process group, or with one rank, the row itself as [1, row_floats]."""
+    import torch
+    import torch.distributed as dist
+    row = row.reshape(1, -1)
+    if not (dist.is_available() and dist.is_initialized()) or dist.get_world_size(group) == 1:
+        return row
+    world = dist.get_world_size(group)
+    dev = row.device
+    send = row.contiguous().view(torch.int32)
+    if dev.type == "cuda" and dist.get_backend(group) == "gloo":
+        send = send.cpu()          # rehearsal on gloo: stage through the host
+    out = torch.empty((world, send.shape[1]), dtype=torch.int32, device=send.device)
+    dist.all_gather_into_tensor(out, send, group=group)
+    return out.to(dev).view(torch.float32)
+
+
+def broadcast_learner(learner, group=None, src: int = 0) -> None:
+    """Rank `src`'s parameters, Adam moments and step counts to every rank of `group` (src is a global rank), so that
+    the ranks' learners start equal.  Synchronises; meant for start-up and checkpoint loads, not the training loop."""
+    import numpy as np
+    import torch
+    import torch.distributed as dist
+    if not (dist.is_available() and dist.is_initialized()) or dist.get_world_size(group) == 1:
+        return
+    m, v, steps = learner._optim_state()
+    # one int32 block: the three float blobs as bit views, then the step counts
+    blk = torch.from_numpy(np.concatenate([learner._get_params().view(np.int32), m.view(np.int32), v.view(np.int32),
+                                           np.ascontiguousarray(steps, np.int64).view(np.int32)]))
+    if dist.get_backend(group) != "gloo":
+        blk = blk.to(learner.device)
+    dist.broadcast(blk, src=src, group=group)
+    blk = blk.cpu().numpy()
+    P = learner.num_params
+    learner._set_params(np.ascontiguousarray(blk[:P]).view(np.float32))
+    learner._set_optim_state(np.ascontiguousarray(blk[P:2 * P]).view(np.float32),
+                              np.ascontiguousarray(blk[2 * P:3 * P]).view(np.float32),
+                              np.ascontiguousarray(blk[3 * P:]).view(np.int64))
