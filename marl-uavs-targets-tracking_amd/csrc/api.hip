@@ -1356,6 +1356,31 @@ int reserve_scratch(const char *fn, H *h, int64_t max_batch, int64_t limit, int6
     return 0;
 }
 
+// The batch tests of uavtrack_learner_update / _grad / _write_priorities, after their null tests: n, the reserved
+// scratch, the store's capacity, and n against it when no indices choose the rows (`dir`: "from" or "into" the store).
+int accept_batch(const char *fn, const uavtrack_learner *l, int64_t n, int64_t capacity, const int64_t *indices,
+                 const char *dir)
+{
+    if (n < 1) return fail("%s: n = %lld < 1", fn, (long long)n);
+    if (n > l->d.max_n)
+        return fail("%s: n = %lld rows, scratch is reserved for %lld (uavtrack_learner_reserve)", fn, (long long)n,
+                    (long long)l->d.max_n);
+    if (capacity < 1) return fail("%s: capacity = %lld < 1", fn, (long long)capacity);
+    if (!indices && n > capacity)
+        return fail("%s: n = %lld rows without indices %s a store of %lld", fn, (long long)n, dir, (long long)capacity);
+    return 0;
+}
+
+// the fields uavtrack_learner_update and _grad fill alike; the others are null
+LearnerLaunch learner_batch(int64_t n, const float *states, const int32_t *actions, const float *rewards,
+                            const float *next_states, int64_t capacity, const int64_t *indices, float *td_delta)
+{
+    LearnerLaunch q = {};
+    q.n = n; q.capacity = capacity; q.td_delta = td_delta;
+    q.states = states; q.rewards = rewards; q.next_states = next_states; q.actions = actions; q.idx = indices;
+    return q;
+}
+
 // *_set/get_optimizer_state of a trainer: exp_avg, exp_avg_sq [P] and step [tensors] in from the host (const
 // pointers; everything is validated before the first copy, so a refused load leaves the previous state in place) or
 // out to it.  `has` completes the size message: "<n> floats, <has % P>".
@@ -1523,19 +1548,10 @@ int uavtrack_learner_update(uavtrack_learner *learner, int64_t n, const float *s
     if (!states || !actions || !rewards || !next_states)
         return fail("uavtrack_learner_update: states, actions, rewards and next_states must not be null");
     if (!actor_loss || !critic_loss) return fail("uavtrack_learner_update: actor_loss and critic_loss must not be null");
-    if (n < 1) return fail("uavtrack_learner_update: n = %lld < 1", (long long)n);
-    if (n > learner->d.max_n)
-        return fail("uavtrack_learner_update: n = %lld rows, scratch is reserved for %lld (uavtrack_learner_reserve)",
-                    (long long)n, (long long)learner->d.max_n);
-    if (capacity < 1) return fail("uavtrack_learner_update: capacity = %lld < 1", (long long)capacity);
-    if (!indices && n > capacity)
-        return fail("uavtrack_learner_update: n = %lld rows without indices from a store of %lld", (long long)n,
-                    (long long)capacity);
+    if (accept_batch(__func__, learner, n, capacity, indices, "from")) return 1;
     ON_DEVICE(learner->cfg.device_id);
-    LearnerLaunch q;
-    q.n = n; q.capacity = capacity;
-    q.states = states; q.rewards = rewards; q.next_states = next_states; q.actions = actions; q.idx = indices;
-    q.actor_loss = actor_loss; q.critic_loss = critic_loss; q.td_delta = td_delta; q.priorities = priorities;
+    LearnerLaunch q = learner_batch(n, states, actions, rewards, next_states, capacity, indices, td_delta);
+    q.actor_loss = actor_loss; q.critic_loss = critic_loss; q.priorities = priorities;
     HIP_TRY(launch_learner_update(learner->d, q, static_cast<hipStream_t>(stream)));
     return 0;
 }
@@ -1555,19 +1571,9 @@ int uavtrack_learner_grad(uavtrack_learner *learner, int64_t n, const float *sta
     if (!states || !actions || !rewards || !next_states)
         return fail("uavtrack_learner_grad: states, actions, rewards and next_states must not be null");
     if (!td_delta || !row) return fail("uavtrack_learner_grad: td_delta and row must not be null");
-    if (n < 1) return fail("uavtrack_learner_grad: n = %lld < 1", (long long)n);
-    if (n > learner->d.max_n)
-        return fail("uavtrack_learner_grad: n = %lld rows, scratch is reserved for %lld (uavtrack_learner_reserve)",
-                    (long long)n, (long long)learner->d.max_n);
-    if (capacity < 1) return fail("uavtrack_learner_grad: capacity = %lld < 1", (long long)capacity);
-    if (!indices && n > capacity)
-        return fail("uavtrack_learner_grad: n = %lld rows without indices from a store of %lld", (long long)n,
-                    (long long)capacity);
+    if (accept_batch(__func__, learner, n, capacity, indices, "from")) return 1;
     ON_DEVICE(learner->cfg.device_id);
-    LearnerLaunch q;
-    q.n = n; q.capacity = capacity;
-    q.states = states; q.rewards = rewards; q.next_states = next_states; q.actions = actions; q.idx = indices;
-    q.actor_loss = nullptr; q.critic_loss = nullptr; q.td_delta = td_delta; q.priorities = nullptr;
+    const LearnerLaunch q = learner_batch(n, states, actions, rewards, next_states, capacity, indices, td_delta);
     HIP_TRY(launch_learner_grad(learner->d, q, row, static_cast<hipStream_t>(stream)));
     return 0;
 }
@@ -1590,14 +1596,7 @@ int uavtrack_learner_write_priorities(uavtrack_learner *learner, int64_t n, cons
 {
     if (!learner) return fail("uavtrack_learner_write_priorities: null handle");
     if (!td_delta || !priorities) return fail("uavtrack_learner_write_priorities: td_delta and priorities must not be null");
-    if (n < 1) return fail("uavtrack_learner_write_priorities: n = %lld < 1", (long long)n);
-    if (n > learner->d.max_n)
-        return fail("uavtrack_learner_write_priorities: n = %lld rows, scratch is reserved for %lld "
-                    "(uavtrack_learner_reserve)", (long long)n, (long long)learner->d.max_n);
-    if (capacity < 1) return fail("uavtrack_learner_write_priorities: capacity = %lld < 1", (long long)capacity);
-    if (!indices && n > capacity)
-        return fail("uavtrack_learner_write_priorities: n = %lld rows without indices into a store of %lld", (long long)n,
-                    (long long)capacity);
+    if (accept_batch(__func__, learner, n, capacity, indices, "into")) return 1;
     ON_DEVICE(learner->cfg.device_id);
     HIP_TRY(launch_learner_priorities(learner->d, indices, n, capacity, td_delta, priorities,
                                       static_cast<hipStream_t>(stream)));

@@ -7,12 +7,13 @@
 //                            gradient sum of the tile is added into the workgroup's LDS accumulators (each
 //                            parameter owned by one thread, so the order of the adds is fixed), and the workgroup
 //                            writes one partial row [P + 4] (gradients, then the four loss sums) at the end;
-//   learner_finalize_kernel  the loss partials summed in workgroup order -> losses, mean(delta), step counters;
+//   learner_finalize_kernel  the loss partials summed in workgroup order -> losses, gradient scales, step counters;
 //   learner_adam_kernel      per parameter: the gradient partials summed in workgroup order, scaled, Adam;
 //   learner_prio_*           |delta| into the priorities at the sampled slots, the last occurrence of a slot in the
 //                            batch winning (a claim / max-row / mark / write chain: no float atomics anywhere).
 // Nothing depends on timing, so two identical calls give bitwise identical results.
-// The split form (learner_reduce_kernel, learner_apply_*) cuts the same chain after the sums: see below.
+// The split form cuts the same chain after the sums: learner_reduce_kernel leaves them in a gradient row, and the apply
+// runs the same finalize and Adam kernels over rows instead of workgroup partials (see below).
 //
 // The sums are arranged so the reference's broadcast actor loss costs nothing extra: with
 // actor_loss = mean_i(-log p_i) * mean_j(delta_j), dL/dz_i = -mean(delta) (onehot(a_i) - p_i) / n, so the grad kernel
@@ -224,20 +225,42 @@ __global__ void learner_begin_kernel(int *status)
     if (threadIdx.x == 0 && blockIdx.x == 0) *status = 0;
 }
 
-// One thread: losses, mean(delta), the per-call status into the sticky error count, the step counters.
-__global__ void learner_finalize_kernel(const float *partials, int groups, LearnerLayout L, int64_t n, int per_sample,
-                                        const int *status, int *errors, int64_t *steps, float *scal,
-                                        float *actor_loss, float *critic_loss)
+// The ordered sum every reduction over partial rows or gradient rows uses: word p of `count` rows, rows ascending.
+__device__ __forceinline__ float ordered_sum(const float *src, int count, size_t stride, int p)
+{
+    float g = 0.0f;
+    for (int r = 0; r < count; ++r) g += src[r * stride + p];
+    return g;
+}
+
+// One thread: the four loss sums added in row order, then losses, mean(delta) and the gradient scales from N, the call's
+// verdict into the sticky refusal count, the step counters.  The closed update (n_given >= 1) passes the workgroup
+// partials with N = n_given and reads the verdict the gradient kernel left in the status word; the apply (n_given == 0)
+// passes gradient rows, takes N and the verdict from their tails and writes the verdict to the status word.
+__global__ void learner_finalize_kernel(const float *src, int count, size_t stride, int P, int64_t n_given, int per_sample,
+                                        int *status, int *errors, int64_t *steps, float *scal, float *actor_loss,
+                                        float *critic_loss)
 {
     if (threadIdx.x != 0 || blockIdx.x != 0) return;
     float sum[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-    for (int g = 0; g < groups; ++g)
-        for (int q = 0; q < 4; ++q) sum[q] += partials[(size_t)g * (L.P + 4) + L.P + q];
-    const float inv_n = 1.0f / (float)n;
+    int64_t N = n_given;
+    int bad = 0;
+    for (int r = 0; r < count; ++r) {
+        const float *row = src + r * stride;
+        for (int q = 0; q < 4; ++q) sum[q] += row[P + q];
+        if (n_given) continue;                                      // a workgroup partial ends here
+        const int32_t *tail = reinterpret_cast<const int32_t *>(row) + P + 4;
+        const int64_t nr = (int64_t)((uint64_t)(uint32_t)tail[0] | ((uint64_t)(uint32_t)tail[1] << 32));
+        bad |= tail[2] & 3;
+        if (tail[3] != P || nr < 1) bad |= 4;                       // a row of another layout (or not a row at all)
+        else N += nr;
+    }
+    if (n_given) bad = *status;
+    else *status = bad;
+    const float inv_n = 1.0f / (float)N;
     const float mean_nlp = sum[0] * inv_n, mean_delta = sum[1] * inv_n;
     const float al = per_sample ? sum[2] * inv_n : mean_nlp * mean_delta;
     const float cl = sum[3] * inv_n;
-    const int bad = *status;
     if (actor_loss) *actor_loss = bad ? NAN : al;
     if (critic_loss) *critic_loss = bad ? NAN : cl;
     // gradient scales of the Adam kernel: actor, critic
@@ -247,88 +270,40 @@ __global__ void learner_finalize_kernel(const float *partials, int groups, Learn
     for (int q = 0; q < kLearnerTensors; ++q) steps[q] += 1;
 }
 
-// Both torch.optim.Adam steps (adam_element, internal.h) on the summed and scaled gradient partials.
-__global__ void learner_adam_kernel(float *params, float *m, float *v, const float *partials, int groups, LearnerLayout L,
-                                    const int *status, const int64_t *steps, const float *scal, float actor_lr, float critic_lr)
+// Both torch.optim.Adam steps (adam_element, internal.h) on the gradient sums of `count` rows, added in row order and
+// scaled once.
+__global__ void learner_adam_kernel(float *params, float *m, float *v, const float *src, int count, size_t stride,
+                                    LearnerLayout L, const int *status, const int64_t *steps, const float *scal,
+                                    float actor_lr, float critic_lr)
 {
     const int p = blockIdx.x * blockDim.x + threadIdx.x;
     if (p >= L.P || *status) return;
-    float g = 0.0f;
-    for (int w = 0; w < groups; ++w) g += partials[(size_t)w * (L.P + 4) + p];
     const bool actor = p < L.c_w1;
-    g *= actor ? scal[0] : scal[1];
+    const float g = ordered_sum(src, count, stride, p) * (actor ? scal[0] : scal[1]);
     adam_element(params[p], m[p], v[p], g, steps[L.tensor_of(p)], actor ? actor_lr : critic_lr);
 }
 
 // ---- the split update (uavtrack_learner_grad / _apply / _write_priorities): the update cut between "sum" and "scale +
-// Adam".  A gradient row is [P + kLearnerRowTail] words: the P unscaled gradient sums exactly as learner_adam_kernel
-// forms g before it scales, the four loss sums as learner_finalize_kernel forms them, then n (int64 as two words), the
-// row's status bits and P as a layout tag.  Every sum keeps a fixed order (workgroups ascending inside a row, rows
+// Adam".  A gradient row is [P + kLearnerRowTail] words: the P gradient sums and the four loss sums, each the
+// ordered_sum of the workgroup partials (what the closed update's Adam and finalize kernels form before they scale),
+// then n (int64 as two words), the row's status bits and P as a layout tag.  The apply launches the same finalize and
+// Adam kernels over rows instead of partials.  Every sum keeps a fixed order (workgroups ascending inside a row, rows
 // ascending in the apply), so whoever applies the same rows in the same order gets the same bits, and one row gives the
 // bits of the closed update (0.0f + x == x bitwise: a sum that starts from +0 is never -0).
 
-// One thread per word of the row: the workgroup partials summed in workgroup order.
+// One thread per word of the row: the workgroup partials summed in workgroup order, then the tail.
 __global__ void learner_reduce_kernel(const float *partials, int groups, int P, int64_t n, const int *status, float *row)
 {
     const int p = blockIdx.x * blockDim.x + threadIdx.x;
     if (p >= P + kLearnerRowTail) return;
     if (p < P + 4) {
-        float g = 0.0f;
-        for (int w = 0; w < groups; ++w) g += partials[(size_t)w * (P + 4) + p];
-        row[p] = g;
+        row[p] = ordered_sum(partials, groups, (size_t)P + 4, p);
         return;
     }
     int32_t *tail = reinterpret_cast<int32_t *>(row);
     const uint64_t un = (uint64_t)n;
     const int q = p - (P + 4);
     tail[p] = q == 0 ? (int32_t)(uint32_t)(un & 0xFFFFFFFFu) : q == 1 ? (int32_t)(uint32_t)(un >> 32) : q == 2 ? *status : P;
-}
-
-// One thread: the rows' verdict into the status word, the loss sums added in row order, N = sum of the rows' n; then
-// losses, scales, refusal count and step counters by learner_finalize_kernel's formulas.
-__global__ void learner_apply_begin_kernel(const float *rows, int count, int P, int per_sample, int *status, int *errors,
-                                           int64_t *steps, float *scal, float *actor_loss, float *critic_loss)
-{
-    if (threadIdx.x != 0 || blockIdx.x != 0) return;
-    const size_t stride = (size_t)P + kLearnerRowTail;
-    float sum[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-    int64_t N = 0;
-    int bad = 0;
-    for (int r = 0; r < count; ++r) {
-        const float *row = rows + r * stride;
-        const int32_t *tail = reinterpret_cast<const int32_t *>(row);
-        for (int q = 0; q < 4; ++q) sum[q] += row[P + q];
-        const int64_t nr = (int64_t)((uint64_t)(uint32_t)tail[P + 4] | ((uint64_t)(uint32_t)tail[P + 5] << 32));
-        bad |= tail[P + 6] & 3;
-        if (tail[P + 7] != P || nr < 1) bad |= 4;               // a row of another layout (or not a row at all)
-        else N += nr;
-    }
-    *status = bad;
-    const float inv_n = 1.0f / (float)N;
-    const float mean_nlp = sum[0] * inv_n, mean_delta = sum[1] * inv_n;
-    const float al = per_sample ? sum[2] * inv_n : mean_nlp * mean_delta;
-    const float cl = sum[3] * inv_n;
-    if (actor_loss) *actor_loss = bad ? NAN : al;
-    if (critic_loss) *critic_loss = bad ? NAN : cl;
-    scal[0] = per_sample ? -inv_n : -mean_delta * inv_n;
-    scal[1] = 2.0f * inv_n;
-    if (bad) { *errors += 1; return; }
-    for (int q = 0; q < kLearnerTensors; ++q) steps[q] += 1;
-}
-
-// Both Adam steps on the rows' gradient sums, added in row order and scaled once.
-__global__ void learner_apply_adam_kernel(float *params, float *m, float *v, const float *rows, int count, LearnerLayout L,
-                                          const int *status, const int64_t *steps, const float *scal, float actor_lr,
-                                          float critic_lr)
-{
-    const int p = blockIdx.x * blockDim.x + threadIdx.x;
-    if (p >= L.P || *status) return;
-    const size_t stride = (size_t)L.P + kLearnerRowTail;
-    float g = 0.0f;
-    for (int r = 0; r < count; ++r) g += rows[r * stride + p];
-    const bool actor = p < L.c_w1;
-    g *= actor ? scal[0] : scal[1];
-    adam_element(params[p], m[p], v[p], g, steps[L.tensor_of(p)], actor ? actor_lr : critic_lr);
 }
 
 // the priorities: claim every sampled slot, keep the largest batch row per slot, mark it, write |delta| from it
@@ -411,8 +386,25 @@ hipError_t launch_grad(const LearnerDevice &d, const LearnerLaunch &q, float *td
     return hipGetLastError();
 }
 
-hipError_t launch_prio(const LearnerDevice &d, const int64_t *idx, int64_t n, int64_t capacity, const float *td,
-                       float *prio, hipStream_t st)
+// The tail both forms share: finalize over `count` rows of `stride` words (n_given as learner_finalize_kernel takes
+// it), then Adam over the same rows.
+hipError_t launch_scale_adam(const LearnerDevice &d, const float *src, int count, size_t stride, int64_t n_given,
+                             float *actor_loss, float *critic_loss, hipStream_t st)
+{
+    const LearnerLayout &L = d.L;
+    hipLaunchKernelGGL(learner_finalize_kernel, dim3(1), dim3(64), 0, st, src, count, stride, L.P, n_given, d.per_sample,
+                       d.opt.status, d.opt.errors, d.opt.steps, d.scal, actor_loss, critic_loss);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(learner_adam_kernel, dim3((L.P + 255) / 256), dim3(256), 0, st, d.params, d.opt.m, d.opt.v, src,
+                       count, stride, L, d.opt.status, d.opt.steps, d.scal, d.actor_lr, d.critic_lr);
+    return hipGetLastError();
+}
+
+}  // namespace
+
+hipError_t launch_learner_priorities(const LearnerDevice &d, const int64_t *idx, int64_t n, int64_t capacity,
+                                     const float *td, float *prio, hipStream_t st)
 {
     const dim3 grid((unsigned)((n + 255) / 256)), blk(256);
     hipError_t e;
@@ -426,25 +418,14 @@ hipError_t launch_prio(const LearnerDevice &d, const int64_t *idx, int64_t n, in
     return hipGetLastError();
 }
 
-}  // namespace
-
 hipError_t launch_learner_update(const LearnerDevice &d, const LearnerLaunch &q, hipStream_t st)
 {
-    const LearnerLayout &L = d.L;
-    const int groups = learner_groups(L, q.n);
     float *td = q.td_delta ? q.td_delta : d.td;
     hipError_t e = launch_grad(d, q, td, d.opt.status, st);
     if (e != hipSuccess) return e;
-
-    hipLaunchKernelGGL(learner_finalize_kernel, dim3(1), dim3(64), 0, st, d.partials, groups, L, q.n, d.per_sample,
-                       d.opt.status, d.opt.errors, d.opt.steps, d.scal, q.actor_loss, q.critic_loss);
-    if ((e = hipGetLastError()) != hipSuccess) return e;
-
-    hipLaunchKernelGGL(learner_adam_kernel, dim3((L.P + 255) / 256), dim3(256), 0, st, d.params, d.opt.m, d.opt.v,
-                       d.partials, groups, L, d.opt.status, d.opt.steps, d.scal, d.actor_lr, d.critic_lr);
-    if ((e = hipGetLastError()) != hipSuccess) return e;
-
-    if (q.priorities) return launch_prio(d, q.idx, q.n, q.capacity, td, q.priorities, st);
+    e = launch_scale_adam(d, d.partials, learner_groups(d.L, q.n), (size_t)d.L.P + 4, q.n, q.actor_loss, q.critic_loss, st);
+    if (e != hipSuccess) return e;
+    if (q.priorities) return launch_learner_priorities(d, q.idx, q.n, q.capacity, td, q.priorities, st);
     return hipSuccess;
 }
 
@@ -463,20 +444,7 @@ hipError_t launch_learner_grad(const LearnerDevice &d, const LearnerLaunch &q, f
 hipError_t launch_learner_apply(const LearnerDevice &d, const float *rows, int count, float *actor_loss,
                                 float *critic_loss, hipStream_t st)
 {
-    const LearnerLayout &L = d.L;
-    hipLaunchKernelGGL(learner_apply_begin_kernel, dim3(1), dim3(64), 0, st, rows, count, L.P, d.per_sample, d.opt.status,
-                       d.opt.errors, d.opt.steps, d.scal, actor_loss, critic_loss);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(learner_apply_adam_kernel, dim3((L.P + 255) / 256), dim3(256), 0, st, d.params, d.opt.m, d.opt.v,
-                       rows, count, L, d.opt.status, d.opt.steps, d.scal, d.actor_lr, d.critic_lr);
-    return hipGetLastError();
-}
-
-hipError_t launch_learner_priorities(const LearnerDevice &d, const int64_t *idx, int64_t n, int64_t capacity,
-                                     const float *td, float *prio, hipStream_t st)
-{
-    return launch_prio(d, idx, n, capacity, td, prio, st);
+    return launch_scale_adam(d, rows, count, (size_t)d.L.P + kLearnerRowTail, 0, actor_loss, critic_loss, st);
 }
 
 }  // namespace uavtrack

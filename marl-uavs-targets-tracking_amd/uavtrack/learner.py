@@ -107,14 +107,28 @@ class DeviceActorCritic(Handle):
         self._check()
 
     # ---- the update
+    @staticmethod
+    def _batch_args(store: Dict[str, torch.Tensor], capacity: int, idx: Optional[torch.Tensor]):
+        """A batch as uavtrack_learner_update and _grad take it: the store's four arrays, its capacity, the indices."""
+        return (*(_ptr(store[k]) for k in ("states", "actions", "rewards", "next_states")), capacity, _ptr(idx))
+
+    def _draw_from(self, buffer, k: int, generator: Optional[torch.Generator]):
+        """(indices, priorities or None) of one batch of k rows, drawn as the buffer's own sample() draws them."""
+        if isinstance(buffer, PrioritizedReplayRing):
+            return buffer._draw_into(k), buffer.priorities
+        if isinstance(buffer, PrioritizedDeviceReplayBuffer):
+            prob = buffer.priorities[:buffer.count] ** buffer.alpha
+            prob = prob / prob.sum()
+            return torch.multinomial(prob, k, replacement=True, generator=generator), buffer.priorities
+        return torch.randperm(buffer.count, device=buffer.device, generator=generator)[:k], None
+
     def _run(self, n: int, store: Dict[str, torch.Tensor], capacity: int, idx: Optional[torch.Tensor],
              priorities: Optional[torch.Tensor]):
         dev = self.device
         losses = torch.empty(2, device=dev)
         td = torch.empty(n, device=dev)
         _lib.check(self._lib.uavtrack_learner_update(
-            self._h, n, _ptr(store["states"]), _ptr(store["actions"]), _ptr(store["rewards"]),
-            _ptr(store["next_states"]), capacity, _ptr(idx), _ptr(losses[0:1]), _ptr(losses[1:2]), _ptr(td),
+            self._h, n, *self._batch_args(store, capacity, idx), _ptr(losses[0:1]), _ptr(losses[1:2]), _ptr(td),
             _ptr(priorities), self._stream()), "uavtrack_learner_update")
         return losses[0], losses[1], td
 
@@ -150,29 +164,10 @@ class DeviceActorCritic(Handle):
         k = min(int(batch_size), buffer.count)
         if k < 1:
             raise ValueError("update_from: the buffer is empty")
-        if isinstance(buffer, PrioritizedReplayRing):
-            return self._run(k, buffer.store, buffer.capacity, buffer._draw_into(k), buffer.priorities)
-        if isinstance(buffer, PrioritizedDeviceReplayBuffer):
-            prob = buffer.priorities[:buffer.count] ** buffer.alpha
-            prob = prob / prob.sum()
-            idx = torch.multinomial(prob, k, replacement=True, generator=generator)
-            prio = buffer.priorities
-        else:
-            idx = torch.randperm(buffer.count, device=buffer.device, generator=generator)[:k]
-            prio = None
+        idx, prio = self._draw_from(buffer, k, generator)
         return self._run(k, buffer.store, buffer.capacity, idx, prio)
 
     # ---- the split update: gradient rows and an ordered apply
-    def _draw_from(self, buffer, k: int, generator: Optional[torch.Generator]):
-        """(indices, priorities or None) of one batch of k rows, drawn as the buffer's own sample() draws them."""
-        if isinstance(buffer, PrioritizedReplayRing):
-            return buffer._draw_into(k), buffer.priorities
-        if isinstance(buffer, PrioritizedDeviceReplayBuffer):
-            prob = buffer.priorities[:buffer.count] ** buffer.alpha
-            prob = prob / prob.sum()
-            return torch.multinomial(prob, k, replacement=True, generator=generator), buffer.priorities
-        return torch.randperm(buffer.count, device=buffer.device, generator=generator)[:k], None
-
     def new_rows(self, count: int) -> torch.Tensor:
         """A [count, row_floats] device tensor for `count` gradient rows (pass rows[k] to grad_from as `row`)."""
         return torch.empty(int(count), self.row_floats, device=self.device)
@@ -187,8 +182,7 @@ class DeviceActorCritic(Handle):
         if td is None:
             td = torch.empty(n, device=self.device)
         _lib.check(self._lib.uavtrack_learner_grad(
-            self._h, n, _ptr(store["states"]), _ptr(store["actions"]), _ptr(store["rewards"]),
-            _ptr(store["next_states"]), capacity, _ptr(idx), _ptr(td), _ptr(row), self._stream()),
+            self._h, n, *self._batch_args(store, capacity, idx), _ptr(td), _ptr(row), self._stream()),
             "uavtrack_learner_grad")
         return row, td
 
