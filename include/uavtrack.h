@@ -384,6 +384,16 @@ int uavtrack_kernel_info(uavtrack_env *env, int64_t out[5]);
  * All zero before the first launch. */
 int uavtrack_launch_info(uavtrack_env *env, int64_t out[4]);
 
+/* Which rollout kernel instantiation the most recent rollout launch ran, as its template arguments: out[0], out[1] = the
+ * compile-time (N, M) of a specialised shape (0, 0: the generic kernel), out[2] = the reward mode AS INSTANTIATED (the
+ * greedy baseline's PMI slot is the RAW kernel), out[3] = 1 for the 3-D kernel, out[4] = the policy (0 the caller's
+ * actions, 1 the greedy baseline, 2 the actor), out[5] = 1 for the every-output variant, out[6] = 1 for the variant with
+ * the optional extras (automatic reset, target trace, raw rewards, state copy), out[7] = 1 for the single-wavefront
+ * variant.  The tuple is written down where the kernel's address is taken, so it names the kernel that ran, not the one
+ * that was asked for.  Before the first launch every entry is -1 ("none yet": all zeros is a real kernel, the generic
+ * planar RAW one with an output left out). */
+int uavtrack_variant_info(uavtrack_env *env, int64_t out[8]);
+
 /* ---- the learner: ActorCritic.update + both Adam steps on the device ----
  * A handle of its own, independent of any environment (one learner may serve sharded environments).  It holds the
  * shared actor FnnPolicyNet (actor_critic.py:85-98: Linear(12,H) - ReLU - Linear(H,A) - softmax), the critic

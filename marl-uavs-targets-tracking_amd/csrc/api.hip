@@ -1218,6 +1218,13 @@ int uavtrack_launch_info(uavtrack_env *env, int64_t out[4])
     return 0;
 }
 
+int uavtrack_variant_info(uavtrack_env *env, int64_t out[8])
+{
+    if (!env || !out) return fail("uavtrack_variant_info: null argument");
+    for (int k = 0; k < 8; ++k) out[k] = env->last_variant.v[k];
+    return 0;
+}
+
 int uavtrack_kernel_info(uavtrack_env *env, int64_t out[5])
 {
     if (!env || !out) return fail("uavtrack_kernel_info: null argument");

@@ -142,6 +142,12 @@ struct Geometry {
     int lone = 0;         // single-wave groups on a grid of at most two waves per SIMD: the LONE kernel variant
 };
 
+// The template arguments of one rollout_kernel instantiation, in the kernel's own order: N_, M_ (0, 0: the generic
+// kernel), MODE as instantiated, Z3, POLICY, ALLOUT, EXTRAS, LONE.  Written where the function pointer is taken
+// (step_kernel.hip, pick_reward), nowhere else; all -1 until a launch has happened (uavtrack_variant_info: all zeros is a
+// real kernel).
+struct VariantInfo { int64_t v[8] = {-1, -1, -1, -1, -1, -1, -1, -1}; };
+
 }  // namespace uavtrack
 
 struct uavtrack_env {
@@ -155,6 +161,7 @@ struct uavtrack_env {
     // block reservations pay off over many steps, and a launch that starts with an empty pool waits for its first one)
     uavtrack::Geometry geo_short;
     uavtrack::Geometry last_launch;   // geometry of the most recent rollout launch (uavtrack_launch_info)
+    uavtrack::VariantInfo last_variant;   // ... and the kernel instantiation it ran (uavtrack_variant_info)
     uavtrack::PmiWeights pmi;
     int32_t n_cus = 0;           // compute units of the device (grid of the persistent scorer)
     int32_t pmi_scheme = 0;      // uavtrack_set_pmi_scheme: UAVTRACK_PMI_AUTO or a pinned scorer
@@ -200,7 +207,7 @@ namespace uavtrack {
 Geometry plan_geometry(const uavtrack_config &cfg, int n_simd, bool allow_small_grid = true);
 enum { kPolicyGiven = 0, kPolicyGreedy = 1, kPolicyActor = 2 };   // where a rollout's actions come from
 // one rollout launch of p.T steps: the kernel variant and the geometry (env->geo or env->geo_short) are chosen by
-// select_rollout; the choice is kept in env->last_launch
+// select_rollout; the choice is kept in env->last_launch and env->last_variant
 hipError_t launch_rollout(uavtrack_env *env, const StepParams &p, hipStream_t stream, int policy = kPolicyGiven);
 
 // pmi_kernel.hip

@@ -1534,20 +1534,30 @@ const SpecShape *spec_shape(int N, int M)
 // What selects a launch's template arguments beyond its shape (select_rollout): MODE, Z3, POLICY, ALLOUT, EXTRAS, LONE
 struct Variant { int mode; bool z3; int policy; bool allout, extras, lone; };
 
+// A rollout_kernel instantiation and its template arguments, taken together in one expression (uavtrack_variant_info
+// reports `info`: it cannot say one kernel while another runs)
+struct Picked { KernelFn fn; VariantInfo info; };
+
+template <int N_, int M_, int MODE, bool Z3, int POLICY, bool ALLOUT, bool EXTRAS, bool LONE>
+Picked instance()
+{
+    return {rollout_kernel<N_, M_, MODE, Z3, POLICY, ALLOUT, EXTRAS, LONE>, {{N_, M_, MODE, Z3, POLICY, ALLOUT, EXTRAS, LONE}}};
+}
+
 template <int N_, int M_, bool Z3, int POLICY, bool ALLOUT, bool EXTRAS, bool LONE = false>
-KernelFn pick_reward(int mode)
+Picked pick_reward(int mode)
 {
     // (the greedy baseline never runs MAAC-R -- uavtrack_run_greedy refuses it -- so its PMI slot is the RAW kernel)
     constexpr int kPmi = POLICY == kPolicyGreedy ? UAVTRACK_REWARD_RAW : UAVTRACK_REWARD_PMI;
     switch (mode) {
-    case UAVTRACK_REWARD_MEAN: return rollout_kernel<N_, M_, UAVTRACK_REWARD_MEAN, Z3, POLICY, ALLOUT, EXTRAS, LONE>;
-    case UAVTRACK_REWARD_PMI:  return rollout_kernel<N_, M_, kPmi, Z3, POLICY, ALLOUT, EXTRAS, LONE>;
-    default:                   return rollout_kernel<N_, M_, UAVTRACK_REWARD_RAW, Z3, POLICY, ALLOUT, EXTRAS, LONE>;
+    case UAVTRACK_REWARD_MEAN: return instance<N_, M_, UAVTRACK_REWARD_MEAN, Z3, POLICY, ALLOUT, EXTRAS, LONE>();
+    case UAVTRACK_REWARD_PMI:  return instance<N_, M_, kPmi, Z3, POLICY, ALLOUT, EXTRAS, LONE>();
+    default:                   return instance<N_, M_, UAVTRACK_REWARD_RAW, Z3, POLICY, ALLOUT, EXTRAS, LONE>();
     }
 }
 
 template <int N_, int M_, int POLICY, bool ALLOUT, bool EXTRAS>
-KernelFn pick_dim(const Variant &v)
+Picked pick_dim(const Variant &v)
 {
     return v.z3 ? pick_reward<N_, M_, true, POLICY, ALLOUT, EXTRAS>(v.mode) : pick_reward<N_, M_, false, POLICY, ALLOUT, EXTRAS>(v.mode);
 }
@@ -1556,7 +1566,7 @@ KernelFn pick_dim(const Variant &v)
 // learner's rollout, the benchmark -- or the fused actor rollout: wave fences for barriers and, under MAAC-R, pair-list
 // slots from the pool); the planar greedy baseline with and without extras; any other policy without extras, with them.
 template <int N_, int M_, bool LONE_SHAPE>
-KernelFn pick_policy(const Variant &v)
+Picked pick_policy(const Variant &v)
 {
     if constexpr (LONE_SHAPE) {
         if (v.lone)
@@ -1573,7 +1583,7 @@ KernelFn pick_policy(const Variant &v)
 
 // kSpecShapes[I..] in order, then the generic kernel
 template <int I = 0>
-KernelFn pick_kernel(int N, int M, const Variant &v)
+Picked pick_kernel(int N, int M, const Variant &v)
 {
     if constexpr (I == kSpecShapeCount) {
         return pick_policy<0, 0, false>(v);
@@ -1656,8 +1666,9 @@ Geometry plan_geometry(const uavtrack_config &cfg, int n_simd, bool allow_small_
     return g;
 }
 
-// The one place that decides what a rollout launch runs: the kernel and its geometry (geo.lone: the LONE variant runs)
-struct RolloutChoice { KernelFn fn; Geometry geo; };
+// The one place that decides what a rollout launch runs: the kernel, its template arguments as pick_reward wrote them down,
+// and its geometry (geo.lone: the LONE variant runs)
+struct RolloutChoice { KernelFn fn; VariantInfo info; Geometry geo; };
 
 static RolloutChoice select_rollout(const uavtrack_env *env, const StepParams &p, int policy)
 {
@@ -1681,7 +1692,9 @@ static RolloutChoice select_rollout(const uavtrack_env *env, const StepParams &p
     r.geo = short_geo ? env->geo_short : env->geo;
     r.geo.lone = r.geo.lone && lone_exists;
     v.lone = r.geo.lone;
-    r.fn = pick_kernel(p.N, p.M, v);
+    const Picked k = pick_kernel(p.N, p.M, v);
+    r.fn = k.fn;
+    r.info = k.info;
     return r;
 }
 
@@ -1689,6 +1702,7 @@ hipError_t launch_rollout(uavtrack_env *env, const StepParams &p, hipStream_t st
 {
     const RolloutChoice r = select_rollout(env, p, policy);
     env->last_launch = r.geo;
+    env->last_variant = r.info;
     StepParams q = p;
     q.E = r.geo.envs_per_wg;
     const size_t lds = r.geo.lds_bytes;   // (the in-kernel actor needs no LDS: its operands move by lane swaps)

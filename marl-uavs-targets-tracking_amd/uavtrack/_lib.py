@@ -130,6 +130,7 @@ SIGNATURES = {
     "uavtrack_get_profile": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int64), C.c_void_p]),
     "uavtrack_kernel_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]),
     "uavtrack_launch_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]),
+    "uavtrack_variant_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]),
     "uavtrack_learner_create": (C.c_int, [C.POINTER(LearnerConfig), C.POINTER(C.c_void_p)]),
     "uavtrack_learner_destroy": (C.c_int, [C.c_void_p]),
     "uavtrack_learner_num_params": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]),

@@ -422,6 +422,14 @@ class BatchedUavEnv(Handle):
         _lib.check(self._lib.uavtrack_launch_info(self._h, out), "uavtrack_launch_info")
         return dict(workgroup=int(out[0]), envs_per_workgroup=int(out[1]), workgroups=int(out[2]), single_wavefront_variant=int(out[3]))
 
+    def variant_info(self) -> tuple:
+        """Template arguments of the rollout kernel the most recent launch ran (uavtrack_variant_info): (N_, M_, MODE as
+        instantiated, Z3, POLICY, ALLOUT, EXTRAS, LONE); N_ = M_ = 0 is the generic kernel.  All -1 before the first
+        launch (all zeros is a real kernel)."""
+        out = (C.c_int64 * 8)()
+        _lib.check(self._lib.uavtrack_variant_info(self._h, out), "uavtrack_variant_info")
+        return tuple(int(x) for x in out)
+
     def pmi_inference(self, x: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
         """PMINetwork.inference (PMINet.py:64-72) on a batch of pair inputs x [n, 12] (= la_i * la_j, uav.py:281) with the
         uploaded weights, on the MAAC-R scorer kernels -> scores [n]."""

@@ -76,6 +76,7 @@ def case(c, rng):
     acts = torch.from_numpy(rng.randint(0, na, size=(T, B, N)).astype(np.int32)).cuda()
     # 1. fused == single steps
     fused = a.step_many(acts)
+    tag += f" kernel{a.variant_info()}@{a.launch_info()['workgroup']}"      # (a failure names the kernel of the fused launch)
     ep = torch.zeros(B, 5, device="cuda")
     for t in range(T):
         obs, rew, done = b.step(acts[t], ep_sums=ep)

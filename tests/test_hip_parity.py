@@ -71,11 +71,9 @@ class Tally:
                 f"{what}: {self.env_excluded} of {self.env_total} env-steps on a knife edge"
 
 
-def compare_step(env, orc, act, what, margin=MARGIN, min_ok_frac=0.9, tally=None):
-    """One teacher-forced step: oracle starts from the device's fp32 state.  Returns the per-environment mask."""
-    inject(orc, host(env.get_state()))
-    obs, rew, _ = env.step(torch.from_numpy(act))
-    ref = orc.step(act)
+def knife_masks(ref, what, margin=MARGIN, min_ok_frac=0.9, tally=None):
+    """The knife-edge masks of one oracle step `ref` -> (ok [B], okr [B, N]): results whose fp64 margin is below `margin`
+    are set aside, counted in `tally`, and bounded per step (at least `min_ok_frac` of a batch of 30 or more compared)."""
     ok = ref["margin"] > margin               # [B]    every range / wall test of the environment
     okr = ref["margin_row"] > margin          # [B, N] the tests one UAV's own row depends on
     if os.environ.get("UAVTRACK_TEST_REPORT"):
@@ -86,21 +84,44 @@ def compare_step(env, orc, act, what, margin=MARGIN, min_ok_frac=0.9, tally=None
     if len(ok) >= 30:
         assert ok.mean() >= min_ok_frac, f"{what}: too many knife-edge envs ({ok.mean():.3f})"
     assert ok.any(), what
-    terms, cov = env.info["terms"].cpu().numpy(), env.info["covered"].cpu().numpy()
-    obs, rew = obs.cpu().numpy(), rew.cpu().numpy()
-    np.testing.assert_allclose(obs[okr], ref["obs"][okr], rtol=0, atol=ATOL, err_msg=f"{what} obs")
-    np.testing.assert_allclose(terms[:, okr], ref["terms"][:, okr], rtol=0, atol=ATOL, err_msg=f"{what} terms")
-    if orc.cfg.cooperative == 0:              # MAAC: the reward is the UAV's own raw reward (uav.py:270)
-        np.testing.assert_allclose(rew[okr], ref["reward"][okr], rtol=0, atol=ATOL, err_msg=f"{what} reward")
-    else:                                     # MAAC-G / MAAC-R: neighbours' raw rewards and the neighbour test enter
-        np.testing.assert_allclose(rew[ok], ref["reward"][ok], rtol=0, atol=ATOL, err_msg=f"{what} reward")
-    np.testing.assert_array_equal(cov[ok], ref["covered"][ok], err_msg=f"{what} covered")
-    st, rs = host(env.get_state()), orc.get_state()
+    return ok, okr
+
+
+def check_outputs(ref, ok, okr, cooperative, what, obs=None, rew=None, terms=None, cov=None):
+    """The outputs of one step (host arrays; None: not requested by the launch, not compared) against the oracle's `ref`
+    outside the knife edges: observations, terms and rewards within ATOL, the coverage count exactly."""
+    if obs is not None:
+        np.testing.assert_allclose(obs[okr], ref["obs"][okr], rtol=0, atol=ATOL, err_msg=f"{what} obs")
+    if terms is not None:
+        np.testing.assert_allclose(terms[:, okr], ref["terms"][:, okr], rtol=0, atol=ATOL, err_msg=f"{what} terms")
+    if rew is not None:
+        if cooperative == 0:                  # MAAC: the reward is the UAV's own raw reward (uav.py:270)
+            np.testing.assert_allclose(rew[okr], ref["reward"][okr], rtol=0, atol=ATOL, err_msg=f"{what} reward")
+        else:                                 # MAAC-G / MAAC-R: neighbours' raw rewards and the neighbour test enter
+            np.testing.assert_allclose(rew[ok], ref["reward"][ok], rtol=0, atol=ATOL, err_msg=f"{what} reward")
+    if cov is not None:
+        np.testing.assert_array_equal(cov[ok], ref["covered"][ok], err_msg=f"{what} covered")
+
+
+def check_state(st, rs, ok, what):
+    """The state behind a step (host arrays `st`) against the oracle's `rs`: poses within RTOL_POSE, headings within 1e-5
+    (the targets' outside wall knife edges), actions exactly."""
     for k in ("ux", "uy", "tx", "ty") + (("uz",) if "uz" in st else ()):
         np.testing.assert_allclose(st[k], rs[k], rtol=RTOL_POSE, atol=1e-4, err_msg=f"{what} {k}")
     assert ang_diff(st["uh"], rs["uh"]).max() < 1e-5, what
     assert ang_diff(st["th"][ok], rs["th"][ok]).max() < 1e-5, what
     np.testing.assert_array_equal(st["ua"], rs["ua"])
+
+
+def compare_step(env, orc, act, what, margin=MARGIN, min_ok_frac=0.9, tally=None):
+    """One teacher-forced step: oracle starts from the device's fp32 state.  Returns the per-environment mask."""
+    inject(orc, host(env.get_state()))
+    obs, rew, _ = env.step(torch.from_numpy(act))
+    ref = orc.step(act)
+    ok, okr = knife_masks(ref, what, margin, min_ok_frac, tally)
+    check_outputs(ref, ok, okr, orc.cfg.cooperative, what, obs=obs.cpu().numpy(), rew=rew.cpu().numpy(),
+                  terms=env.info["terms"].cpu().numpy(), cov=env.info["covered"].cpu().numpy())
+    check_state(host(env.get_state()), orc.get_state(), ok, what)
     return ok
 
 
