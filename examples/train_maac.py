@@ -15,6 +15,13 @@ update is the same rule on a sampled batch, and the new actor weights are re-upl
     python examples/train_maac.py --replay prioritized --learner device --publish device --log-every 10   # no host sync per iteration
     python examples/train_maac.py --method maac-r --pmi-trainer device --learner device --replay prioritized --publish device --log-every 10
     python examples/train_maac.py --shards 8 --envs 32768 --n-uav 20 --learner device --replay prioritized --publish device   # 8 shard handles, one learner
+    python examples/train_maac.py --phase evaluate --envs 256 --eval-episodes 4 --save-dir out   # train.evaluate, batched; csv files
+    python examples/train_maac.py --phase run --envs 256                                         # train.run, the C-METHOD baseline
+
+Every phase reports the reference's six per-episode results (train.py:181-196: return, the three reward terms, mean and
+maximum of the covered targets) from a uavtrack.EpisodeStats, which folds each rollout's outputs on the device; in
+`train` it is fed behind every rollout and read only on printed lines, so --log-every N still means no host
+synchronisation in between.  --save-dir writes the lists as data_util.save_csv does (plus the two covered lists).
 
 --method maac-r is the paper's method (configs/MAAC-R.yaml): the reward of every step is mixed in-kernel with the
 neighbours' rewards, weighted by the PMI network's scores (uav.py:262-291); that network is trained alongside on
@@ -61,6 +68,45 @@ def update(actor, critic, opt_a, opt_c, batch, gamma):
     return float(actor_loss.detach()), float(critic_loss.detach())
 
 
+SIX = ("return_list", "target_tracking_return_list", "boundary_punishment_return_list",
+       "duplicate_tracking_punishment_return_list", "average_covered_targets_list", "max_covered_targets_list")
+
+
+def drain(stats_list, kept):
+    """Read and clear every EpisodeStats (a synchronisation each: printed lines only); the records join `kept` (the
+    lists --save-dir writes) and their means over the episodes since the previous line come back as a string."""
+    reads = []
+    for st in stats_list:
+        reads.append(st.read())
+        st.clear()
+    got = {k: [v for r in reads for v in r[k].tolist()] for k in SIX}
+    for k in SIX:
+        kept[k].extend(got[k])
+    n = max(1, len(got[SIX[0]]))
+    tt, bp, dp, avg, mx = (sum(got[k]) / n for k in SIX[1:])
+    lost = sum(r["dropped"] for r in reads)
+    return (f"tracking {tt:+.4f}  boundary {bp:+.4f}  duplicate {dp:+.4f}  covered avg {avg:5.2f} max {mx:5.2f}  "
+            f"episodes {len(got[SIX[0]])}" + (f" (+{lost} not logged)" if lost else ""))
+
+
+def save_results(args, kept):
+    if args.save_dir:
+        os.makedirs(args.save_dir, exist_ok=True)
+        uavtrack.episode_stats.save_csv(kept, args.save_dir, extra=True)
+
+
+def evaluate_phase(args, env, policy):
+    """--phase evaluate (train.evaluate, train.py:298-324) and --phase run (train.run, train.py:372-396), batched: every
+    environment plays --eval-episodes episodes; prints the means of the six results, returns the per-episode returns."""
+    res = uavtrack.evaluate(env, policy, args.steps, episodes=args.eval_episodes, seed=args.seed)
+    n = len(res[SIX[0]])
+    print(f"{args.phase}: {n} episodes of {args.steps} steps ({res['path']} path)  " +
+          "  ".join(f"{k[:-5]} {res[k].mean():+.4f}" for k in SIX), flush=True)
+    save_results(args, res)
+    env.close()
+    return res["return_list"].tolist()
+
+
 def train_sharded(args, timings=None):
     """--shards K: K environment handles over disjoint global environment ids, K rollouts, K prioritised rings, ONE
     device learner.  Every update takes one gradient row from each ring and applies them in shard order
@@ -86,6 +132,8 @@ def train_sharded(args, timings=None):
     rings = [uavtrack.PrioritizedReplayRing(2 * e.cfg.n_envs * args.n_uav * args.steps, dev, alpha=args.alpha,
                                             seed=args.seed + 7919 * k, max_batch=per_shard) for k, e in enumerate(envs)]
     per_iter = args.envs * args.n_uav * args.steps
+    stats = [uavtrack.EpisodeStats(e, log_capacity=e.cfg.n_envs * args.log_every, max_steps=args.steps) for e in envs]
+    kept = {k: [] for k in SIX}
     history, stamps, outs = [], [], [None] * K
     t_log = time.perf_counter()
     for it in range(args.iters):
@@ -96,7 +144,7 @@ def train_sharded(args, timings=None):
             ro.seed = args.seed + it
             ro.reset(seed=1000 + it)
             obs_in = ro.obs.clone()
-            res = ro.run_fused(args.steps, out=outs[k])
+            res = ro.run_fused(args.steps, out=outs[k], stats=stats[k])    # done fires at the horizon: one record per episode
             outs[k] = {key: v for key, v in res.items() if key != "ep_sums"}
             ring.add_rollout(obs_in, res)
             eps.append(res["ep_sums"])
@@ -118,14 +166,16 @@ def train_sharded(args, timings=None):
         if not log:
             continue
         ret, cov = float(ep[:, 0].mean()), float(ep[:, 4].mean()) / args.steps
+        six = drain(stats, kept)
         torch.cuda.synchronize()
         now = time.perf_counter()
         n_iter = it + 1 - (stamps[-1][0] if stamps else 0)
         stamps.append((it + 1, now))
         print(f"iter {it:3d}  shards {K}  episode return {ret:8.3f}  covered targets/step {cov:5.2f}  actor loss {la:+.4f}  "
               f"critic loss {lc:.4f}  rollout {t_roll * 1e3:6.1f} ms ({per_iter / t_roll / 1e9:.2f} G agent-steps/s)  "
-              f"iteration {((now - t0) if args.log_every == 1 else (now - t_log) / n_iter) * 1e3:6.1f} ms", flush=True)
+              f"iteration {((now - t0) if args.log_every == 1 else (now - t_log) / n_iter) * 1e3:6.1f} ms  {six}", flush=True)
         t_log = now
+    save_results(args, kept)
     for ring in rings:
         ring.check()                                                  # no draw was refused on the device
     learner.check()                                                   # no update was refused on the device
@@ -190,9 +240,24 @@ def main(argv=None, timings=None):
                     help="print (and so synchronise) every N iterations and after the last; the iteration time printed is "
                          "the mean over the iterations since the previous line, and with N > 1 the rollout time of a "
                          "line includes the work still queued from the iterations before it")
+    ap.add_argument("--phase", choices=["train", "evaluate", "run"], default="train",
+                    help="main.py's three phases: train; evaluate (train.evaluate: the actor, sampled, --eval-episodes "
+                         "episodes per environment); run (train.run: the C-METHOD greedy baseline)")
+    ap.add_argument("--eval-episodes", type=int, default=1, help="--phase evaluate / run: episodes per environment")
+    ap.add_argument("--actor-path", default=None,
+                    help="--phase evaluate: a saved FnnPolicyNet / ActorMLP state dict (default: fresh weights)")
+    ap.add_argument("--save-dir", default=None,
+                    help="write the per-episode result lists there as data_util.save_csv does (return_list.csv, ...), "
+                         "plus average_covered_targets_list.csv and max_covered_targets_list.csv; default: nothing is written")
     args = ap.parse_args(argv)
     if args.log_every < 1:
         ap.error("--log-every must be >= 1")
+    if args.eval_episodes < 1:
+        ap.error("--eval-episodes must be >= 1")
+    if args.phase == "run" and args.method == "maac-r":
+        ap.error("--phase run is the C-METHOD baseline: it runs with the maac / maac-g rewards")
+    if args.phase != "train":
+        args.shards = 1
 
     if args.shards < 1 or args.shards > args.envs:
         ap.error("--shards must be in [1, --envs]")
@@ -225,6 +290,10 @@ def main(argv=None, timings=None):
         pmi_gen = torch.Generator(device=dev)
         pmi_gen.manual_seed(args.seed)
     actor = uavtrack.ActorMLP(hidden_dim=args.hidden, action_dim=cfg.na_total).to(dev)
+    if args.phase != "train":
+        if args.actor_path:
+            actor.load_state_dict(torch.load(args.actor_path, map_location=dev))
+        return evaluate_phase(args, env, actor if args.phase == "evaluate" else "greedy")
     critic = ValueNet(hidden_dim=args.hidden).to(dev)
     opt_a = torch.optim.Adam(actor.parameters(), lr=args.actor_lr)
     opt_c = torch.optim.Adam(critic.parameters(), lr=args.critic_lr)
@@ -240,6 +309,8 @@ def main(argv=None, timings=None):
                                                 max_batch=args.batch)
     else:
         replay = uavtrack.DeviceReplayBuffer(capacity=2 * per_iter, device=dev)
+    stats = uavtrack.EpisodeStats(env, log_capacity=args.envs * args.log_every, max_steps=args.steps)
+    kept = {k: [] for k in SIX}
     history = []
     out = None
     t_log = time.perf_counter()
@@ -250,7 +321,7 @@ def main(argv=None, timings=None):
         rollout.seed = args.seed + it
         rollout.reset(seed=1000 + it)
         obs_in = rollout.obs.clone()
-        res = rollout.run_fused(args.steps, out=out)                  # B episodes, one launch
+        res = rollout.run_fused(args.steps, out=out, stats=stats)     # B episodes, one launch; done at the horizon closes them
         out = {k: v for k, v in res.items() if k != "ep_sums"}        # reuse the output buffers next time
         if args.replay == "prioritized":
             replay.add_rollout(obs_in, res)                           # one library call, straight from the outputs
@@ -307,14 +378,16 @@ def main(argv=None, timings=None):
         if not log:
             continue
         ret, cov = float(ep[:, 0].mean()), float(ep[:, 4].mean()) / args.steps
+        six = drain([stats], kept)
         torch.cuda.synchronize()
         now = time.perf_counter()
         n_iter = it + 1 - (stamps[-1][0] if stamps else 0)           # iterations since the previous line
         stamps.append((it + 1, now))
         print(f"iter {it:3d}  episode return {ret:8.3f}  covered targets/step {cov:5.2f}  actor loss {la:+.4f}  "
               f"critic loss {lc:.4f}  pmi loss {lp:.4f}  rollout {t_roll * 1e3:6.1f} ms ({per_iter / t_roll / 1e9:.2f} G agent-steps/s)  "
-              f"iteration {((now - t0) if args.log_every == 1 else (now - t_log) / n_iter) * 1e3:6.1f} ms", flush=True)
+              f"iteration {((now - t0) if args.log_every == 1 else (now - t_log) / n_iter) * 1e3:6.1f} ms  {six}", flush=True)
         t_log = now
+    save_results(args, kept)
     if args.replay == "prioritized":
         replay.check()                                                # no draw was refused on the device
     env.close()

@@ -671,6 +671,75 @@ int uavtrack_replay_sample(uavtrack_replay *replay, const uavtrack_replay_ring *
  * priorities).  refused (nullable) receives their number; the count restarts at 0. */
 int uavtrack_replay_check(uavtrack_replay *replay, int64_t *refused, void *stream);
 
+/* ---- per-episode results: ReturnValueOfTrain on the device, across automatic resets ----
+ * The reference reports six results per episode (train.py:181-196, appended by train, evaluate and run through
+ * ReturnValueOfTrain, train.py:12-38).  This handle, independent of any environment, folds the outputs a stepping
+ * launch has already written -- reward [T][B][N], terms [T][3][B][N], covered [T][B], done [T][B] -- into per-environment
+ * open-episode accumulators that live on the device and carry over from call to call, and appends one record per
+ * finished episode to a device log.  It reads the FINAL reward array, so it is the same for MAAC, MAAC-G and MAAC-R.
+ *
+ * Arithmetic.  Every sum is fp64 in one fixed order: the N values of a step are added in ascending UAV index i,
+ * starting from +0.0 (Python's sum(reward_list[...]), train.py:181-184), and the step sums are added to the episode's
+ * accumulator in ascending t (train.py:181 `+=`).  The covered sum (int64) and maximum (int32) are integers.  The
+ * division happens once, when the record is written: sum / (double)(steps * N), (double)covered_sum / (double)steps.
+ * An episode is limited to 2^31 - 1 steps.
+ *
+ * Order of the log.  The records of one add appear in ascending (t, b) of their closing step: the order of a scan over
+ * the done matrix, not of arrival.  The records of one close appear in ascending b.  Two identical call sequences give
+ * byte-identical logs.
+ *
+ * Overflow.  Once the log holds log_capacity records, further records are counted, not written; their episodes'
+ * accumulators restart all the same.  The read call returns that count in `dropped`. */
+typedef struct uavtrack_episode_stats_config {
+    uint32_t struct_size;       /* = sizeof(uavtrack_episode_stats_config), ABI check */
+    int32_t  device_id;         /* HIP device ordinal */
+    int64_t  n_envs;            /* B >= 1 */
+    int32_t  n_uav;             /* N in [1, 2048] */
+    int32_t  pad_;              /* 0 */
+    int64_t  env_offset;        /* global id of env 0 (shards): record.env = env_offset + b */
+    int64_t  max_steps;         /* largest T of one add; sizes the step-sum scratch (max_steps * n_envs < 2^31) */
+    int64_t  log_capacity;      /* records the device log holds, >= 1 */
+} uavtrack_episode_stats_config;
+
+typedef struct uavtrack_episode_record {   /* 64 bytes, no padding */
+    double  ret, tracking, boundary, duplicate;   /* each episode sum / (steps * N)                 (train.py:187-190) */
+    double  average_covered, max_covered;         /* np.mean / np.max of covered over the episode's steps (train.py:191-192) */
+    int64_t env;                                  /* env_offset + b */
+    int32_t steps;                                /* steps in this episode */
+    int32_t ordinal;                              /* episodes this environment had closed before this one */
+} uavtrack_episode_record;
+
+typedef struct uavtrack_episode_stats uavtrack_episode_stats;   /* opaque handle */
+
+/* Allocates the accumulators (all zero: every environment starts with an open episode of no steps, ordinal 0), the
+ * step-sum scratch and the log; synchronises the device. */
+int uavtrack_episode_stats_create(const uavtrack_episode_stats_config *cfg, uavtrack_episode_stats **out);
+int uavtrack_episode_stats_destroy(uavtrack_episode_stats *stats);
+
+/* Folds the T steps of one launch (DEVICE pointers, the layouts above; done nullable) into the open episodes.  Step t of
+ * environment b first joins the open episode; if done[t][b] != 0 the episode closes with that step included: its record
+ * goes to the log, the accumulators restart and the environment's ordinal advances.  With done == NULL nothing closes.
+ * Stream-ordered: no synchronisation, no allocation, capturable into a graph; the arrays are read when the launches
+ * execute on `stream`.  Under MAAC-R it belongs behind the stepping call, whose last stage writes the final rewards.
+ * Returns an error, enqueuing nothing, for a null handle, reward, terms or covered, T < 1 or T > max_steps.  A
+ * negative covered count, or one above 2^31 - 1, is not checked. */
+int uavtrack_episode_stats_add(uavtrack_episode_stats *stats, int64_t T, const float *reward, const float *terms,
+                               const int32_t *covered, const uint8_t *done, void *stream);
+
+/* Ends every open episode that holds at least one step, as a done flag behind its last step would have: for
+ * fixed-length rollouts whose caller resets by hand and never sees done (train.py:160 with num_steps).  Stream-ordered
+ * like the add. */
+int uavtrack_episode_stats_close(uavtrack_episode_stats *stats, void *stream);
+
+/* Synchronises `stream`.  *count = the records the log holds; the first min(*count, capacity) of them are copied, in
+ * log order, to records_host (a HOST array of `capacity` records; may be NULL when capacity is 0).  *dropped = the
+ * records that found the log full since the last clear. */
+int uavtrack_episode_stats_read(uavtrack_episode_stats *stats, uavtrack_episode_record *records_host, int64_t capacity,
+                                int64_t *count, int64_t *dropped, void *stream);
+
+/* Empties the log and zeroes `dropped`, stream-ordered.  The open episodes and the ordinals stay as they are. */
+int uavtrack_episode_stats_clear(uavtrack_episode_stats *stats, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -19,6 +19,7 @@ from .replay import DeviceReplayBuffer, PrioritizedDeviceReplayBuffer, transitio
 from .replay_ring import PrioritizedReplayRing  # noqa: F401
 from .learner import DeviceActorCritic, ValueMLP  # noqa: F401
 from .pmi_trainer import DevicePMINetwork  # noqa: F401
+from .episode_stats import EpisodeStats, evaluate  # noqa: F401
 from .pmi_data import sample_pmi_pairs, pmi_contrastive_loss, pmi_batches, train_pmi_epoch  # noqa: F401
 from . import _lib  # noqa: F401
 
@@ -26,5 +27,5 @@ __all__ = ["EnvConfig", "RewardMode", "BatchedUavEnv", "Environment", "fold_pmi_
            "shard_range", "gather_rollout_summary", "gather_rollout_summary_async", "sample_local_transitions", "gather_transitions",
            "gather_transitions_async", "gather_learner_rows", "broadcast_learner", "ActorMLP", "BatchedRollout", "sample_actions",
            "DeviceReplayBuffer", "PrioritizedDeviceReplayBuffer", "transitions_from_rollout", "PrioritizedReplayRing", "DeviceActorCritic", "ValueMLP",
-           "DevicePMINetwork",
+           "DevicePMINetwork", "EpisodeStats", "evaluate",
            "sample_pmi_pairs", "pmi_contrastive_loss", "pmi_batches", "train_pmi_epoch", "make_pmi_net"]

@@ -72,6 +72,23 @@ class ReplayRing(C.Structure):
         ("capacity", C.c_int64), ("pos", C.c_int64), ("count", C.c_int64)]
 
 
+class EpisodeStatsConfig(C.Structure):
+    """Mirror of `struct uavtrack_episode_stats_config` (include/uavtrack.h)."""
+    _fields_ = [
+        ("struct_size", C.c_uint32), ("device_id", C.c_int32), ("n_envs", C.c_int64), ("n_uav", C.c_int32),
+        ("pad_", C.c_int32), ("env_offset", C.c_int64), ("max_steps", C.c_int64), ("log_capacity", C.c_int64),
+    ]
+
+
+class EpisodeRecord(C.Structure):
+    """Mirror of `struct uavtrack_episode_record` (include/uavtrack.h): 64 bytes."""
+    _fields_ = [
+        ("ret", C.c_double), ("tracking", C.c_double), ("boundary", C.c_double), ("duplicate", C.c_double),
+        ("average_covered", C.c_double), ("max_covered", C.c_double), ("env", C.c_int64), ("steps", C.c_int32),
+        ("ordinal", C.c_int32),
+    ]
+
+
 class PmiTensors(C.Structure):
     """Mirror of `struct uavtrack_pmi_tensors` (include/uavtrack.h): 26 device pointers in PMI_STATE_KEYS order."""
     _fields_ = [("t", C.c_void_p * 26)]
@@ -165,6 +182,13 @@ SIGNATURES = {
     "uavtrack_replay_sample": (C.c_int, [C.c_void_p, C.POINTER(ReplayRing), C.c_int64, C.c_double, C.c_double,
                                          C.c_void_p, C.c_void_p, C.c_void_p]),
     "uavtrack_replay_check": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64), C.c_void_p]),
+    "uavtrack_episode_stats_create": (C.c_int, [C.POINTER(EpisodeStatsConfig), C.POINTER(C.c_void_p)]),
+    "uavtrack_episode_stats_destroy": (C.c_int, [C.c_void_p]),
+    "uavtrack_episode_stats_add": (C.c_int, [C.c_void_p, C.c_int64] + [C.c_void_p] * 4 + [C.c_void_p]),
+    "uavtrack_episode_stats_close": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "uavtrack_episode_stats_read": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_int64),
+                                              C.POINTER(C.c_int64), C.c_void_p]),
+    "uavtrack_episode_stats_clear": (C.c_int, [C.c_void_p, C.c_void_p]),
 }
 
 _lib = None

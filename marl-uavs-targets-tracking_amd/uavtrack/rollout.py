@@ -74,6 +74,7 @@ class BatchedRollout:
         self._bound_key = None                                         # (stream handle, seed) the bound calls were built under
         self._graph_seed = None
         self._chunk_ready = False
+        self._stats = None                                             # run(stats=...): the EpisodeStats the chunks of this run feed
 
     # one closed-loop step on the current stream; everything stays on the device
     def _one_step(self):
@@ -115,8 +116,13 @@ class BatchedRollout:
         self.obs.copy_(self.env.reset(seed=seed))
         self.ep.zero_()
 
-    def run(self, steps: int) -> Dict[str, torch.Tensor]:
-        """Advance `steps` closed-loop steps; returns the episode accumulators so far."""
+    def run(self, steps: int, stats=None) -> Dict[str, torch.Tensor]:
+        """Advance `steps` closed-loop steps; returns the episode accumulators so far.  stats (an EpisodeStats; fuse_chunks
+        only, where every chunk's [k, ...] outputs exist): each chunk is added to it behind its launch, on the same
+        stream, so episodes that end inside or between chunks get their records (EpisodeStats.add)."""
+        if stats is not None and not self.fuse_chunks:
+            raise ValueError("run(stats=...) needs fuse_chunks=True: the per-step path keeps no per-step outputs to fold")
+        self._stats = stats
         done = 0
         if self.fuse_chunks:
             # a bound call froze the stream current when it was built and the seed: another stream or seed rebuilds them
@@ -169,6 +175,8 @@ class BatchedRollout:
                 call = self._bound[self._ep_used - 1] = self.env.bind_run(
                     k, dict(out, ep_sums=ep_row), "actor" if self.device_actor else "greedy", obs_in=self.obs, seed=self.seed)
             call()
+            if self._stats is not None:
+                self._stats.add(out)
             return
         if out is not None:
             out = dict(out, ep_sums=ep_row)
@@ -180,6 +188,8 @@ class BatchedRollout:
             ep_row.copy_(res["ep_sums"])
             if k == self.k:
                 self._chunk_out = res
+        if self._stats is not None:
+            self._stats.add(res)
         self.obs = res["obs"][-1]
         self.last_reward = res["reward"][-1]
         self._chunk_ready = out is not None        # from now on obs / last_reward are the views the bound calls were built on
@@ -194,13 +204,17 @@ class BatchedRollout:
         also be a DeviceActorCritic or a state dict of device tensors."""
         self.env.publish_actor(self.policy if source is None else source)
 
-    def run_fused(self, steps: int, want_terms: bool = False, out: Optional[Dict[str, torch.Tensor]] = None
-                  ) -> Dict[str, torch.Tensor]:
+    def run_fused(self, steps: int, want_terms: bool = False, out: Optional[Dict[str, torch.Tensor]] = None,
+                  stats=None) -> Dict[str, torch.Tensor]:
         """The same `steps` closed-loop steps as run(), as ONE launch (device_actor mode, MAAC / MAAC-G).  Returns
         the launch's outputs -- obs/actions/reward [T, ...] are the transitions of train.py:176-180 (state[t] is
-        obs[t-1], or the observation held before the call for t = 0) -- plus the running episode sums."""
+        obs[t-1], or the observation held before the call for t = 0) -- plus the running episode sums.  stats (an
+        EpisodeStats) receives the launch's outputs on the same stream; the terms are then written whatever want_terms
+        says."""
         assert self.device_actor, "run_fused needs device_actor=True"
-        res = self.env.run_actor(steps, self.obs, seed=self.seed, want_terms=want_terms, out=out)
+        res = self.env.run_actor(steps, self.obs, seed=self.seed, want_terms=want_terms or stats is not None, out=out)
+        if stats is not None:
+            stats.add(res)
         self.obs.copy_(res["obs"][-1])
         self.last_reward.copy_(res["reward"][-1])
         self.ep += res["ep_sums"]
