@@ -98,7 +98,8 @@ def save_results(args, kept):
 def evaluate_phase(args, env, policy):
     """--phase evaluate (train.evaluate, train.py:298-324) and --phase run (train.run, train.py:372-396), batched: every
     environment plays --eval-episodes episodes; prints the means of the six results, returns the per-episode returns."""
-    res = uavtrack.evaluate(env, policy, args.steps, episodes=args.eval_episodes, seed=args.seed)
+    res = uavtrack.evaluate(env, policy, args.steps, episodes=args.eval_episodes, seed=args.seed,
+                            auto_reset=args.rollout_episodes > 1)       # then all the episodes in ONE launch
     n = len(res[SIX[0]])
     print(f"{args.phase}: {n} episodes of {args.steps} steps ({res['path']} path)  " +
           "  ".join(f"{k[:-5]} {res[k].mean():+.4f}" for k in SIX), flush=True)
@@ -244,6 +245,11 @@ def main(argv=None, timings=None):
                     help="main.py's three phases: train; evaluate (train.evaluate: the actor, sampled, --eval-episodes "
                          "episodes per environment); run (train.run: the C-METHOD greedy baseline)")
     ap.add_argument("--eval-episodes", type=int, default=1, help="--phase evaluate / run: episodes per environment")
+    ap.add_argument("--rollout-episodes", type=int, default=1,
+                    help="K > 1: every iteration is ONE launch of K * --steps steps that resets each environment inside the "
+                         "kernel at its horizon (BatchedRollout(auto_reset_seed=...)): K episodes per environment without a "
+                         "reset launch or an observation copy in between; --phase evaluate / run then play their "
+                         "--eval-episodes in one launch too (evaluate(auto_reset=True)).  Not with --shards")
     ap.add_argument("--actor-path", default=None,
                     help="--phase evaluate: a saved FnnPolicyNet / ActorMLP state dict (default: fresh weights)")
     ap.add_argument("--save-dir", default=None,
@@ -254,6 +260,10 @@ def main(argv=None, timings=None):
         ap.error("--log-every must be >= 1")
     if args.eval_episodes < 1:
         ap.error("--eval-episodes must be >= 1")
+    if args.rollout_episodes < 1:
+        ap.error("--rollout-episodes must be >= 1")
+    if args.rollout_episodes > 1 and args.shards > 1:
+        ap.error("--rollout-episodes K > 1 runs on one environment handle (no --shards)")
     if args.phase == "run" and args.method == "maac-r":
         ap.error("--phase run is the C-METHOD baseline: it runs with the maac / maac-g rewards")
     if args.phase != "train":
@@ -303,13 +313,15 @@ def main(argv=None, timings=None):
                                              dev, loss=args.actor_loss, max_batch=args.batch)
         actor.load_state_dict(learner.actor_state_dict())
     rollout = uavtrack.BatchedRollout(env, actor, device_actor=True, seed=args.seed)
-    per_iter = args.envs * args.n_uav * args.steps
+    K = args.rollout_episodes
+    T = K * args.steps                                                # steps of one launch
+    per_iter = args.envs * args.n_uav * T
     if args.replay == "prioritized":
         replay = uavtrack.PrioritizedReplayRing(2 * per_iter, dev, alpha=args.alpha, seed=args.seed,
                                                 max_batch=args.batch)
     else:
         replay = uavtrack.DeviceReplayBuffer(capacity=2 * per_iter, device=dev)
-    stats = uavtrack.EpisodeStats(env, log_capacity=args.envs * args.log_every, max_steps=args.steps)
+    stats = uavtrack.EpisodeStats(env, log_capacity=args.envs * K * args.log_every, max_steps=T)
     kept = {k: [] for k in SIX}
     history = []
     out = None
@@ -320,8 +332,10 @@ def main(argv=None, timings=None):
         t0 = time.perf_counter()
         rollout.seed = args.seed + it
         rollout.reset(seed=1000 + it)
+        if K > 1:
+            rollout.auto_reset_seed = 1000 + it                       # the in-launch resets continue this iteration's reset stream
         obs_in = rollout.obs.clone()
-        res = rollout.run_fused(args.steps, out=out, stats=stats)     # B episodes, one launch; done at the horizon closes them
+        res = rollout.run_fused(T, out=out, stats=stats)              # K * B episodes, one launch; done at the horizon closes them
         out = {k: v for k, v in res.items() if k != "ep_sums"}        # reuse the output buffers next time
         if args.replay == "prioritized":
             replay.add_rollout(obs_in, res)                           # one library call, straight from the outputs
@@ -374,10 +388,10 @@ def main(argv=None, timings=None):
         else:
             rollout.publish_actor()                                   # the CUDA ActorMLP, packed on the device
         ep = res["ep_sums"]                                           # [B, 5]: sum_t mean_i reward, 3 terms, covered
-        history.append(ep[:, 0].mean())                               # (a device scalar: read once, at the end)
+        history.append(ep[:, 0].mean() / K)                           # (a device scalar: read once, at the end)
         if not log:
             continue
-        ret, cov = float(ep[:, 0].mean()), float(ep[:, 4].mean()) / args.steps
+        ret, cov = float(ep[:, 0].mean()) / K, float(ep[:, 4].mean()) / T
         six = drain([stats], kept)
         torch.cuda.synchronize()
         now = time.perf_counter()

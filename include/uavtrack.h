@@ -314,6 +314,40 @@ int uavtrack_run_actor(uavtrack_env *env, int32_t T, uint64_t seed, int32_t mode
                        int32_t *actions_out, float *obs, float *reward, float *terms,
                        int32_t *covered, uint8_t *done, float *ep_sums, void *stream);
 
+/* uavtrack_run_actor with the automatic episode turnover of uavtrack_step_many_autoreset: one launch of the fused
+ * policy rollout may span any number of episodes.  An environment whose done flag fires at step t is reset right behind
+ * that step -- exactly uavtrack_reset(reset_seed, e + 1), e the episode number of its previous reset -- and the actor's
+ * input at step t + 1 is the fresh state's observation ([-1]*9 + [x/dc, y/dc, a/Na], uavtrack_reset's obs output).
+ * The draw stream: while an environment is in episode e (what uavtrack_reset stored, plus the resets of this launch so
+ * far), its draws use the Philox key of seed + e (mod 2^64); a cached Philox block never crosses a reset.
+ * The equivalence the tests hold the call to -- bitwise, per environment: uavtrack_run_actor with seed + e up to each
+ * done step, then uavtrack_reset(reset_seed, e + 1), then uavtrack_run_actor with seed + e + 1 from the reset's
+ * observation, and so on; ep_sums runs over the whole call.  Everything else is uavtrack_run_actor's contract plus
+ * uavtrack_step_many_autoreset's: needs cfg.horizon >= 1; stream-ordered, no allocation, no synchronisation, capturable;
+ * with reward_mode PMI the launch is chunked as uavtrack_run_actor is.  Every reward mode, 2-D and 3-D.  Returns an
+ * error, enqueuing nothing, for what uavtrack_run_actor refuses, for cfg.horizon < 1, and for a start-observation buffer
+ * (below) that holds fewer than T steps. */
+int uavtrack_run_actor_autoreset(uavtrack_env *env, int32_t T, uint64_t seed, uint64_t reset_seed, int32_t mode,
+                                 const float *obs_in, int32_t *actions_out, float *obs, float *reward, float *terms,
+                                 int32_t *covered, uint8_t *done, float *ep_sums, void *stream);
+
+/* uavtrack_run_greedy with the same turnover and the same draw-stream rule (key of seed + e in episode e).  Bitwise
+ * identical, per environment, to: uavtrack_run_greedy with seed + e up to each done step, uavtrack_reset(reset_seed,
+ * e + 1), continue.  uavtrack_run_greedy's own limits stay: a 3-D configuration or reward_mode PMI is refused with an
+ * error that names the combination (there is no rollout kernel for it). */
+int uavtrack_run_greedy_autoreset(uavtrack_env *env, int32_t T, uint64_t seed, uint64_t reset_seed, int32_t *actions_out,
+                                  float *obs, float *reward, float *terms,
+                                  int32_t *covered, uint8_t *done, float *ep_sums, void *stream);
+
+/* Optional extra output of the automatic-reset entry points (uavtrack_step_many_autoreset, _run_actor_autoreset,
+ * _run_greedy_autoreset), installed like the raw rewards below: start_obs [T][B][N][12].  Row (t, b) is written only
+ * where done[t][b] fired, and holds the observation of the fresh state the environment was reset to -- the policy's
+ * input at step t + 1, the `state` of the transition at t + 1 (uavtrack_replay_add_rollout_episodes); every other row
+ * is left untouched.  Launches without the automatic reset never see the buffer.  A device pointer, 16-byte aligned;
+ * capacity_steps >= the largest T passed to an automatic-reset call while the buffer is set (checked);
+ * start_obs = NULL switches the output off (the default). */
+int uavtrack_set_start_obs_output(uavtrack_env *env, float *start_obs, int32_t capacity_steps);
+
 /* Optional extra output of every stepping entry point (uavtrack_step, _step_accumulate, _step_many, _run_greedy,
  * _run_actor): the target positions after each step, tpos [T][B][M][2] = (x, y) -- what Environment.step appends to
  * position['all_target_xs'/'all_target_ys'] (environment.py:150-153) and Environment.save_position writes to
@@ -654,6 +688,18 @@ int uavtrack_replay_add(uavtrack_replay *replay, const uavtrack_replay_ring *rin
 int uavtrack_replay_add_rollout(uavtrack_replay *replay, const uavtrack_replay_ring *ring, int64_t steps, int64_t agents,
                                 const float *obs_in, const float *obs, const int32_t *actions, const float *reward,
                                 void *stream);
+
+/* uavtrack_replay_add_rollout for a rollout that crossed episode ends (uavtrack_run_actor_autoreset): envs * n_uav
+ * agents per step, done [steps][envs] (uint8) and start_obs [steps][envs][n_uav][12] as that launch wrote them.  The
+ * state of transition (t, b, i) is obs_in[b][i] at t == 0, start_obs[t - 1][b][i] where done[t - 1][b] != 0 (the
+ * episode of step t - 1 ended there: its last observation is not the state step t acted on), else obs[t - 1][b][i].
+ * Everything else -- order, the window when n exceeds the capacity, the wrap, priorities, errors -- is
+ * uavtrack_replay_add_rollout's; each obs row is still read once, a start_obs row only where done fired.  With done all
+ * zero the ring ends byte-identical to uavtrack_replay_add_rollout's (start_obs is then never read). */
+int uavtrack_replay_add_rollout_episodes(uavtrack_replay *replay, const uavtrack_replay_ring *ring, int64_t steps,
+                                         int64_t envs, int64_t n_uav, const float *obs_in, const float *obs,
+                                         const int32_t *actions, const float *reward, const uint8_t *done,
+                                         const float *start_obs, void *stream);
 
 /* PrioritizedReplayBuffer.sample's draw (train.py:98-112) without the gather: n slots with replacement from
  * P(i) = p_i^alpha / sum_j p_j^alpha over [0, count) (the draw stream above) into indices [n] (DEVICE int64), and,

@@ -869,9 +869,13 @@ static int run_steps(uavtrack_env *env, int32_t T, const int32_t *actions, float
         return fail("%s: T = %d exceeds the %d steps the target-trace buffer holds (uavtrack_set_target_trace)", who, T, env->tpos_steps);
     if (env->raw_out && T > env->raw_steps)
         return fail("%s: T = %d exceeds the %d steps the raw-reward buffer holds (uavtrack_set_raw_reward_output)", who, T, env->raw_steps);
+    // (the fresh-state observations exist only in an automatic-reset launch: no other launch sees the buffer)
+    if (pol.auto_reset && env->start_obs_out && T > env->start_obs_steps)
+        return fail("%s: T = %d exceeds the %d steps the start-observation buffer holds (uavtrack_set_start_obs_output)", who, T, env->start_obs_steps);
     StepParams p = env->base;
     p.actions = actions;
     p.tpos = env->tpos;
+    p.start_obs = pol.auto_reset ? env->start_obs_out : nullptr;
     p.raw = env->raw_out;
     p.state_copy = env->state_copy_out;
     p.obs = obs; p.reward = reward; p.terms = terms; p.nbrec = nullptr;
@@ -880,7 +884,7 @@ static int run_steps(uavtrack_env *env, int32_t T, const int32_t *actions, float
     p.ep_accumulate = accumulate ? 1 : 0;
     p.actions_out = pol.actions_out;
     p.env_offset = env->cfg.env_offset;
-    p.auto_reset = pol.auto_reset ? 1 : 0;
+    p.auto_reset = pol.auto_reset ? kAutoResetOn : 0;
     p.reset_k0 = (uint32_t)pol.reset_seed; p.reset_k1 = (uint32_t)(pol.reset_seed >> 32);
     p.greedy_k0 = (uint32_t)pol.seed; p.greedy_k1 = (uint32_t)(pol.seed >> 32);
     if (pol.policy == kPolicyActor) {
@@ -923,6 +927,8 @@ static int run_steps(uavtrack_env *env, int32_t T, const int32_t *actions, float
         p.done = done ? done + (size_t)t0 * c.n_envs : nullptr;
         p.tpos = env->tpos ? env->tpos + (size_t)t0 * c.n_envs * c.m_targets : nullptr;
         p.raw = env->raw_out ? env->raw_out + (size_t)t0 * BN : nullptr;
+        p.start_obs = (pol.auto_reset && env->start_obs_out) ? env->start_obs_out + (size_t)t0 * BN * UAVTRACK_OBS_DIM : nullptr;
+        if (pol.auto_reset && t0 > 0) p.auto_reset = kAutoResetContinued;   // (an actor's first input after a reset at the chunk's edge)
         HIP_TRY(timed_launch(env, UAVTRACK_PROF_ROLLOUT, st, [&] { return launch_rollout(env, p, st, pol.policy); }));
         // the actor of the next chunk starts from this chunk's last observation (a lane reads its own row
         // once, at launch start, before it writes anything: the scratch buffer may be reused in place)
@@ -1099,6 +1105,58 @@ int uavtrack_run_actor(uavtrack_env *env, int32_t T, uint64_t seed, int32_t mode
     PolicyArgs pol;
     pol.policy = kPolicyActor; pol.obs_in = obs_in; pol.actions_out = actions_out; pol.seed = seed; pol.mode = mode;
     return run_steps(env, T, nullptr, obs, reward, terms, covered, done, ep_sums, stream, "uavtrack_run_actor", false, pol);
+}
+
+// The fused policy rollouts with the automatic episode turnover: the checks of the parent call, then those of
+// uavtrack_step_many_autoreset.  Every (policy, mode, dim) the parents accept has a kernel variant with the turnover; what
+// they refuse (the greedy baseline in 3-D or under MAAC-R) is refused here by name.
+int uavtrack_run_actor_autoreset(uavtrack_env *env, int32_t T, uint64_t seed, uint64_t reset_seed, int32_t mode,
+                                 const float *obs_in, int32_t *actions_out, float *obs, float *reward, float *terms,
+                                 int32_t *covered, uint8_t *done, float *ep_sums, void *stream)
+{
+    const char *who = "uavtrack_run_actor_autoreset";
+    if (!env) return fail("%s: null handle", who);
+    if (env->cfg.horizon < 1) return fail("%s: the configuration has no horizon (done never fires)", who);
+    if (T < 1) return fail("%s: T must be >= 1 (got %d)", who, T);
+    if (!reward) return fail("%s: reward is null", who);
+    if (!obs_in) return fail("%s: obs_in is null (the observation the policy sees at the first step)", who);
+    if (!env->actor_w) return fail("%s: needs uavtrack_set_actor_weights first", who);
+    if (mode != UAVTRACK_ACTOR_SAMPLE && mode != UAVTRACK_ACTOR_ARGMAX)
+        return fail("%s: mode %d is neither UAVTRACK_ACTOR_SAMPLE nor UAVTRACK_ACTOR_ARGMAX", who, mode);
+    if (obs_in == obs && T > 1)
+        return fail("%s: obs_in must not alias obs when T > 1 (pass the previous launch's last rows, or a copy)", who);
+    PolicyArgs pol;
+    pol.policy = kPolicyActor; pol.obs_in = obs_in; pol.actions_out = actions_out; pol.seed = seed; pol.mode = mode;
+    pol.auto_reset = true; pol.reset_seed = reset_seed;
+    return run_steps(env, T, nullptr, obs, reward, terms, covered, done, ep_sums, stream, who, false, pol);
+}
+
+int uavtrack_run_greedy_autoreset(uavtrack_env *env, int32_t T, uint64_t seed, uint64_t reset_seed, int32_t *actions_out,
+                                  float *obs, float *reward, float *terms, int32_t *covered, uint8_t *done, float *ep_sums,
+                                  void *stream)
+{
+    const char *who = "uavtrack_run_greedy_autoreset";
+    if (!env) return fail("%s: null handle", who);
+    if (env->cfg.dim != 2 || env->cfg.reward_mode == UAVTRACK_REWARD_PMI)
+        return fail("%s: no rollout kernel for the combination (policy greedy, reward mode %s, %d-D): the C-METHOD baseline "
+                    "is planar and runs with the MAAC / MAAC-G rewards", who,
+                    env->cfg.reward_mode == UAVTRACK_REWARD_PMI ? "MAAC-R" : env->cfg.reward_mode == UAVTRACK_REWARD_MEAN ? "MAAC-G" : "MAAC",
+                    env->cfg.dim);
+    if (env->cfg.horizon < 1) return fail("%s: the configuration has no horizon (done never fires)", who);
+    PolicyArgs pol;
+    pol.policy = kPolicyGreedy; pol.actions_out = actions_out; pol.seed = seed;
+    pol.auto_reset = true; pol.reset_seed = reset_seed;
+    return run_steps(env, T, nullptr, obs, reward, terms, covered, done, ep_sums, stream, who, false, pol);
+}
+
+int uavtrack_set_start_obs_output(uavtrack_env *env, float *start_obs, int32_t capacity_steps)
+{
+    if (!env) return fail("uavtrack_set_start_obs_output: null handle");
+    if (start_obs && capacity_steps < 1) return fail("uavtrack_set_start_obs_output: capacity_steps must be >= 1 (got %d)", capacity_steps);
+    if ((uintptr_t)start_obs & 15) return fail("uavtrack_set_start_obs_output: start_obs must be 16-byte aligned (rows are written as float4)");
+    env->start_obs_out = start_obs;
+    env->start_obs_steps = start_obs ? capacity_steps : 0;
+    return 0;
 }
 
 int uavtrack_set_target_trace(uavtrack_env *env, float *tpos, int32_t capacity_steps)
@@ -1851,6 +1909,27 @@ int uavtrack_replay_add_rollout(uavtrack_replay *replay, const uavtrack_replay_r
     ON_DEVICE(replay->cfg.device_id);
     HIP_TRY(launch_replay_add(replay->d, ring_view(ring), steps * agents, agents, obs_in, nullptr, obs, actions, reward,
                               static_cast<hipStream_t>(stream)));
+    return 0;
+}
+
+int uavtrack_replay_add_rollout_episodes(uavtrack_replay *replay, const uavtrack_replay_ring *ring, int64_t steps,
+                                         int64_t envs, int64_t n_uav, const float *obs_in, const float *obs,
+                                         const int32_t *actions, const float *reward, const uint8_t *done,
+                                         const float *start_obs, void *stream)
+{
+    const char *fn = "uavtrack_replay_add_rollout_episodes";
+    if (!replay) return fail("%s: null handle", fn);
+    if (accept_ring(replay, fn, ring, true)) return 1;
+    if (!obs_in || !obs || !actions || !reward || !done || !start_obs)
+        return fail("%s: obs_in, obs, actions, reward, done and start_obs must not be null", fn);
+    if (!aligned16(obs_in) || !aligned16(obs) || !aligned16(start_obs))
+        return fail("%s: obs_in, obs and start_obs must be 16-byte aligned", fn);
+    if (steps < 1 || envs < 1 || n_uav < 1) return fail("%s: steps, envs and n_uav must be >= 1", fn);
+    if (envs > INT64_MAX / n_uav || steps > INT64_MAX / (envs * n_uav) / 12) return fail("%s: steps * envs * n_uav overflows", fn);
+    const int64_t agents = envs * n_uav;
+    ON_DEVICE(replay->cfg.device_id);
+    HIP_TRY(launch_replay_add(replay->d, ring_view(ring), steps * agents, agents, obs_in, nullptr, obs, actions, reward,
+                              static_cast<hipStream_t>(stream), done, start_obs, n_uav));
     return 0;
 }
 

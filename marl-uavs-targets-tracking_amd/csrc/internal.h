@@ -78,7 +78,7 @@ struct StepParams {
     int32_t B, N, M, E, T, na, na_total, horizon;
     int32_t ep_accumulate;   // 1: ep_sums += (uavtrack_step_accumulate), 0: ep_sums = sums of this launch
     // automatic episode turnover (uavtrack_step_many_autoreset): an environment whose done flag fires is reset in place
-    int32_t auto_reset;
+    int32_t auto_reset;      // 0, kAutoResetOn, or kAutoResetContinued for the later chunks of a chunked launch (MAAC-R)
     uint32_t reset_k0, reset_k1;     // reset seed (Philox key), as uavtrack_reset
     double x_max_d, y_max_d, z_max_d;
     // fused greedy rollout (uavtrack_run_greedy): actions come from the in-kernel baseline policy
@@ -106,7 +106,11 @@ struct StepParams {
     float dup_k, sym_dup_k;      // the duplicate term's clip and normalisation folded (environment.py:210,217): dup = clamp(k * sum g, -1, 0)
                                  // with k = -0.5 / (e/2 * n_uav) for a float sum of g, times 2^-kSymBits for sym_dup's fixed-point sum
     float alpha, beta, gamma, coop;
+    // automatic reset: optional [T][B][N][12] observation of the fresh state, written at the steps whose done flag fired
+    // (uavtrack_set_start_obs_output).  Last member: the kernel-argument offsets of everything above stay where they were.
+    float *start_obs;
 };
+constexpr int32_t kAutoResetOn = 1, kAutoResetContinued = 2;
 
 // MAAC-R neighbour record of one agent-step, 32-bit words: [0 .. W) neighbour bit mask (d <= dp on post-move poses,
 // uav.py:278; bit j = UAV j, self excluded), [W] index of the first pair this UAV emitted (its neighbours j > i, in
@@ -184,6 +188,8 @@ struct uavtrack_env {
     int32_t tpos_steps = 0;
     float *raw_out = nullptr;         // caller's raw-reward buffer (not owned), capacity in steps (uavtrack_set_raw_reward_output)
     int32_t raw_steps = 0;
+    float *start_obs_out = nullptr;   // caller's fresh-state observation buffer (not owned), capacity in steps (uavtrack_set_start_obs_output)
+    int32_t start_obs_steps = 0;
     float *state_copy_out = nullptr;  // (during uavtrack_step_host) where the launch leaves a second copy of the state slab
     // uavtrack_step_host: one pinned, device-mapped host block (actions in, every output and a copy of the state out)
     void *host_blk = nullptr;         // host address (hipHostMalloc)
@@ -438,7 +444,9 @@ hipError_t launch_replay_sample(const ReplayDevice &d, const float *priorities, 
 // min(n, capacity) land in the ring, from ring.pos on
 hipError_t launch_replay_add(const ReplayDevice &d, const ReplayRingView &ring, int64_t n, int64_t agents,
                              const float *obs_in, const float *states, const float *next_states, const int32_t *actions,
-                             const float *rewards, hipStream_t stream);
+                             const float *rewards, hipStream_t stream,
+                             // (the rollout crossed episode ends: done [n / agents][agents / n_uav], start_obs [n][12])
+                             const uint8_t *done = nullptr, const float *start_obs = nullptr, int64_t n_uav = 1);
 
 // episode_kernel.hip -- per-episode results (uavtrack_episode_stats_*).  The open episodes are struct-of-arrays over the
 // environments; a closing step's log slot comes from a scan over the done matrix in groups of kEpisodeGroup environments

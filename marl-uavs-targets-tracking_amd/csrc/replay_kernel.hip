@@ -25,6 +25,8 @@
 //
 // Adding is two reductions (the maximum of the whole priorities array, train.py:87-88) and one write kernel: each thread
 // owns one source transition f, reads obs[f] once and writes it as the next state of f and the state of f + agents.
+// The episodes form (a rollout that crossed episode ends, uavtrack_replay_add_rollout_episodes) writes the fresh state's
+// observation, start_obs[f], as the state of f + agents instead wherever the done flag of f's environment-step fired.
 
 #include "internal.h"
 #include "philox.h"
@@ -309,6 +311,9 @@ struct AddArgs {
     const float *src_rewards;
     const float *top;
     int64_t n, agents, skip, start;
+    const uint8_t *done;                       // episodes form: [steps][envs], with n_uav agents per environment
+    const float *start_obs;                    //                [n][12], read only where done fired
+    int64_t n_uav;
 };
 
 __device__ __forceinline__ void copy_row(float *dst, const float *src)
@@ -319,8 +324,14 @@ __device__ __forceinline__ void copy_row(float *dst, const float *src)
     d[0] = a; d[1] = b; d[2] = c;
 }
 
+template <bool EPISODES>
 __global__ void __launch_bounds__(kSW) replay_write_kernel(AddArgs a)
 {
+    // what transition g + agents acted on: obs[g], or the fresh state's observation where g's episode ended at g
+    auto state_after = [&](int64_t g, const float *obs_row) {
+        if (EPISODES && a.done[g / a.n_uav]) return a.start_obs + g * 12;
+        return obs_row;
+    };
     const int64_t cap = a.ring.capacity;
     const float top = *a.top;
     for (int64_t f = a.skip + (int64_t)blockIdx.x * kSW + threadIdx.x; f < a.n; f += (int64_t)gridDim.x * kSW) {
@@ -332,10 +343,10 @@ __global__ void __launch_bounds__(kSW) replay_write_kernel(AddArgs a)
             const int64_t M = a.agents;
             if (f + M < a.n) {                   // obs[f] is also the state of transition f + M
                 const int64_t s2 = (a.start + (f + M - a.skip)) % cap;
-                copy_row(a.ring.states + s2 * 12, row);
+                copy_row(a.ring.states + s2 * 12, state_after(f, row));
             }
             if (f < M) copy_row(a.ring.states + slot * 12, a.obs_in + f * 12);
-            else if (f - M < a.skip) copy_row(a.ring.states + slot * 12, a.src_next + (f - M) * 12);
+            else if (f - M < a.skip) copy_row(a.ring.states + slot * 12, state_after(f - M, a.src_next + (f - M) * 12));
         } else {
             copy_row(a.ring.states + slot * 12, a.src_states + f * 12);
         }
@@ -380,7 +391,7 @@ hipError_t launch_replay_sample(const ReplayDevice &d, const float *priorities, 
 
 hipError_t launch_replay_add(const ReplayDevice &d, const ReplayRingView &ring, int64_t n, int64_t agents,
                              const float *obs_in, const float *states, const float *next_states, const int32_t *actions,
-                             const float *rewards, hipStream_t st)
+                             const float *rewards, hipStream_t st, const uint8_t *done, const float *start_obs, int64_t n_uav)
 {
     const int64_t cap = ring.capacity;
     int64_t groups = (cap + (int64_t)kSW * 16 - 1) / ((int64_t)kSW * 16);
@@ -393,12 +404,14 @@ hipError_t launch_replay_add(const ReplayDevice &d, const ReplayRingView &ring, 
     AddArgs a;
     a.ring = ring; a.obs_in = obs_in; a.src_states = states; a.src_next = next_states; a.src_actions = actions;
     a.src_rewards = rewards; a.top = d.parts + kReplayMaxParts; a.n = n; a.agents = agents;
+    a.done = done; a.start_obs = start_obs; a.n_uav = n_uav;
     a.skip = n > cap ? n - cap : 0;
     a.start = (ring.pos + a.skip) % cap;
     const int64_t m = n - a.skip;
     int64_t blocks = (m + kSW - 1) / kSW;
     if (blocks > 65536) blocks = 65536;
-    hipLaunchKernelGGL(replay_write_kernel, dim3((unsigned)blocks), dim3(kSW), 0, st, a);
+    if (done) hipLaunchKernelGGL(replay_write_kernel<true>, dim3((unsigned)blocks), dim3(kSW), 0, st, a);
+    else hipLaunchKernelGGL(replay_write_kernel<false>, dim3((unsigned)blocks), dim3(kSW), 0, st, a);
     return hipGetLastError();
 }
 

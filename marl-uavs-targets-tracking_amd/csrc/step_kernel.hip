@@ -729,6 +729,12 @@ __global__ void __launch_bounds__(kMaxWorkgroup) rollout_kernel(const StepParams
         const float4 q0 = ip[0], q1 = ip[1], q2 = ip[2];
         o[0] = q0.x; o[1] = q0.y; o[2] = q0.z; o[3] = q0.w; o[4] = q1.x; o[5] = q1.y;
         o[6] = q1.z; o[7] = q1.w; o[8] = q2.x; o[9] = q2.y; o[10] = q2.z; o[11] = q2.w;
+        // (a later chunk of a chunked automatic-reset launch, MAAC-R: an environment the previous chunk reset behind its
+        //  last step starts from the fresh state's observation, not from that chunk's last row -- see the turnover below)
+        if (EXTRAS && p.auto_reset == kAutoResetContinued && count == 0) {
+            o[0] = o[1] = o[2] = o[3] = o[4] = o[5] = o[6] = o[7] = o[8] = -1.0f;
+            o[9] = x * p.inv_dc; o[10] = y * p.inv_dc; o[11] = (float)a_prev * p.inv_na_total;
+        }
     }
     // Per-lane constants of the step loop: this lane's own slots in both table copies, and (when the
     // workgroup has at least one lane per target, as in every benchmark shape) its target's slot.
@@ -827,6 +833,14 @@ __global__ void __launch_bounds__(kMaxWorkgroup) rollout_kernel(const StepParams
         if (kStepsPerIter > 1 && t >= p.T) break;
         const unsigned tg_off = (unsigned)t * (unsigned)BN + g32;   // flat [t][b][i] (MAAC-R pair records; < 2^32 by ensure_pmi_scratch)
         const int cbuf = (t & 1) * E * CW;
+        // The policy's Philox key.  An automatic-reset launch draws episode e of an environment with the key of seed + e
+        // (64-bit wrap): segment by segment it is the plain policy rollout called with that seed, and no episode repeats
+        // another's draws.  Every other launch keeps the seed as its key.
+        uint32_t pk0 = p.greedy_k0, pk1 = p.greedy_k1;
+        if (EXTRAS && !GIVEN && p.auto_reset) {
+            const uint64_t key = (((uint64_t)p.greedy_k1 << 32) | (uint64_t)p.greedy_k0) + (uint64_t)(uint32_t)epi;
+            pk0 = (uint32_t)key; pk1 = (uint32_t)(key >> 32);
+        }
 
         // ---- P0 (fused greedy rollout only): the C-METHOD baseline policy (uav.py:324-369) on the state as it
         //      stands before this step -- UAV poses are the previous step's post-move copy, targets not yet moved
@@ -850,7 +864,7 @@ __global__ void __launch_bounds__(kMaxWorkgroup) rollout_kernel(const StepParams
             if (active) {
                 const float4 *rows = uenv + pc * 3;
                 act = greedy_pick(x, y, h, i, N, M, p.na, p.dc2, p.turn_unit, (uint64_t)(p.env_offset + b),
-                                  (uint32_t)count, p.greedy_k0, p.greedy_k1,
+                                  (uint32_t)count, pk0, pk1,
                                   [&](int j) { return upos_of(rows, j); },
                                   [&](int k) { return tpos_of(tenv, k); },
                                   [&](int k) { return ncnt[e * M + k]; });
@@ -867,10 +881,10 @@ __global__ void __launch_bounds__(kMaxWorkgroup) rollout_kernel(const StepParams
             //  widths to the general variants -- both layouts in one kernel spilled)
             if constexpr (LONE)
                 act = actor_pick<false, actor_tiles(Z3), kLoneActorTiles>(o, p.actor_w, kLoneActorTiles, p.na_total, (uint64_t)(p.env_offset + b),
-                                        (uint32_t)count, i, p.greedy_k0, p.greedy_k1, p.actor_mode, nullptr, arng);
+                                        (uint32_t)count, i, pk0, pk1, p.actor_mode, nullptr, arng);
             else
                 act = actor_pick<false, actor_tiles(Z3)>(o, p.actor_w, p.actor_hblocks, p.na_total, (uint64_t)(p.env_offset + b),
-                                        (uint32_t)count, i, p.greedy_k0, p.greedy_k1, p.actor_mode, nullptr, arng);
+                                        (uint32_t)count, i, pk0, pk1, p.actor_mode, nullptr, arng);
             if (active && p.actions_out) out_store(at(p.actions_out + row, g32 * 4u), act);
         }
 
@@ -1379,6 +1393,13 @@ __global__ void __launch_bounds__(kMaxWorkgroup) rollout_kernel(const StepParams
                     uav_store(uenv + pn * 3, i, x, y, c, s, (float)a_prev + abias, z);   // this step's copy: the next step's "previous" one
                     o[0] = o[1] = o[2] = o[3] = o[4] = o[5] = o[6] = o[7] = o[8] = -1.0f;   // get_states() of a fresh state (uav.py:174,186)
                     o[9] = x * p.inv_dc; o[10] = y * p.inv_dc; o[11] = (float)a_prev * p.inv_na_total;
+                    arng.valid = false;      // the cached Philox block belongs to the finished episode's key
+                    if (p.start_obs) {       // what the policy sees at step t + 1 (uavtrack_set_start_obs_output); rows of other steps stay untouched
+                        float4 *so4 = reinterpret_cast<float4 *>(p.start_obs + (row + g) * UAVTRACK_OBS_DIM);
+                        so4[0] = make_float4(o[0], o[1], o[2], o[3]);
+                        so4[1] = make_float4(o[4], o[5], o[6], o[7]);
+                        so4[2] = make_float4(o[8], o[9], o[10], o[11]);
+                    }
                 }
                 auto reset_target = [&](int q, float &tx, float &ty, float &th, float &tc, float &ts) {
                     const int te = q / M, k = q - te * M;

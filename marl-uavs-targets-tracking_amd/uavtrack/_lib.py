@@ -139,6 +139,10 @@ SIGNATURES = {
     "uavtrack_get_actor_blob": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     "uavtrack_actor_actions": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "uavtrack_run_actor": (C.c_int, [C.c_void_p, C.c_int32, C.c_uint64, C.c_int32] + [C.c_void_p] * 8 + [C.c_void_p]),
+    "uavtrack_run_actor_autoreset": (C.c_int, [C.c_void_p, C.c_int32, C.c_uint64, C.c_uint64, C.c_int32] + [C.c_void_p] * 8
+                                     + [C.c_void_p]),
+    "uavtrack_run_greedy_autoreset": (C.c_int, [C.c_void_p, C.c_int32, C.c_uint64, C.c_uint64] + [C.c_void_p] * 7 + [C.c_void_p]),
+    "uavtrack_set_start_obs_output": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32]),
     "uavtrack_set_target_trace": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32]),
     "uavtrack_set_raw_reward_output": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32]),
     "uavtrack_step_host": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(HostStep), C.c_void_p]),
@@ -179,6 +183,8 @@ SIGNATURES = {
     "uavtrack_replay_destroy": (C.c_int, [C.c_void_p]),
     "uavtrack_replay_add": (C.c_int, [C.c_void_p, C.POINTER(ReplayRing), C.c_int64] + [C.c_void_p] * 5),
     "uavtrack_replay_add_rollout": (C.c_int, [C.c_void_p, C.POINTER(ReplayRing), C.c_int64, C.c_int64] + [C.c_void_p] * 5),
+    "uavtrack_replay_add_rollout_episodes": (C.c_int, [C.c_void_p, C.POINTER(ReplayRing), C.c_int64, C.c_int64, C.c_int64]
+                                             + [C.c_void_p] * 7),
     "uavtrack_replay_sample": (C.c_int, [C.c_void_p, C.POINTER(ReplayRing), C.c_int64, C.c_double, C.c_double,
                                          C.c_void_p, C.c_void_p, C.c_void_p]),
     "uavtrack_replay_check": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64), C.c_void_p]),

@@ -40,6 +40,7 @@ class BatchedUavEnv(Handle):
         self._episode = 0
         self._trace: Optional[torch.Tensor] = None    # the installed target-trace buffer (kept alive: the library holds its raw pointer)
         self._raw: Optional[torch.Tensor] = None      # ... and the raw-reward buffer (set_raw_output)
+        self._start_obs: Optional[torch.Tensor] = None   # ... and the fresh-state observations of automatic resets (set_start_obs_output)
         self._host_step = _lib.HostStep()             # step_host: the library's host result block and numpy views of it
         self._host_views: Optional[Dict[str, np.ndarray]] = None
 
@@ -169,6 +170,38 @@ class BatchedUavEnv(Handle):
         finally:
             self.set_raw_output(installed)
 
+    def set_start_obs_output(self, buf: Optional[torch.Tensor]) -> None:
+        """Observation of the fresh state behind every in-launch reset, [T, B, N, 12]: row (t, b) is written where
+        done[t, b] fired in an automatic-reset launch (what the policy sees at step t + 1) and left untouched elsewhere;
+        launches without the automatic reset never write it.  None switches the output off."""
+        if buf is None:
+            _lib.check(self._lib.uavtrack_set_start_obs_output(self._h, None, 0), "uavtrack_set_start_obs_output")
+            self._start_obs = None
+            return
+        if buf.dim() != 4 or not self._fits(buf, (buf.shape[0], self.B, self.N, _lib.OBS_DIM), torch.float32):
+            raise ValueError(f"start-observation buffer must be a contiguous float32 [T, {self.B}, {self.N}, {_lib.OBS_DIM}] "
+                             f"tensor on {self.device}")
+        _lib.check(self._lib.uavtrack_set_start_obs_output(self._h, _ptr(buf), C.c_int32(buf.shape[0])),
+                   "uavtrack_set_start_obs_output")
+        self._start_obs = buf       # (kept alive: the library holds its raw pointer)
+
+    def _with_start_obs(self, T: int, want: bool, o, launch):
+        """Run `launch()` with a [T, B, N, 12] start-observation buffer attached when asked; returns (launch's result,
+        the buffer or None).  A buffer the caller installed earlier comes back afterwards."""
+        if not want:
+            return launch(), None
+        so = self._reuse(o, "start_obs", (T, self.B, self.N, _lib.OBS_DIM), torch.float32)
+        installed = self._start_obs
+        self.set_start_obs_output(so)
+        try:
+            return launch(), so
+        finally:
+            self.set_start_obs_output(installed)
+
+    def _count_episodes(self, T: int, auto_reset_seed) -> None:
+        if auto_reset_seed is not None and self.cfg.horizon > 0:
+            self._episode += T // self.cfg.horizon + 1      # stay ahead of the episode numbers the device has used
+
     def step_host(self, actions: np.ndarray, stream=None) -> Dict[str, np.ndarray]:
         """Environment.step for a host caller (uavtrack_step_host): `actions` is a C-contiguous int32 numpy array [B, N];
         returns numpy VIEWS of the library's page-locked result block -- obs [B, N, 12], reward [B, N], terms [3, B, N],
@@ -243,8 +276,7 @@ class BatchedUavEnv(Handle):
                                                        _ptr(obs), _ptr(reward), _ptr(terms), _ptr(covered), _ptr(done), _ptr(ep),
                                                        self._stream()), "uavtrack_step_many_autoreset")
         tp, rb = self._with_raw(T, want_raw, o, lambda: self._with_targets(T, want_targets, o, launch))
-        if auto_reset_seed is not None and self.cfg.horizon > 0:
-            self._episode += T // self.cfg.horizon + 1      # stay ahead of the episode numbers the device has used
+        self._count_episodes(T, auto_reset_seed)
         res = dict(obs=obs, reward=reward, terms=terms, covered=covered, done=done, ep_sums=ep)
         if tp is not None:
             res["targets"] = tp
@@ -450,10 +482,12 @@ class BatchedUavEnv(Handle):
 
     def run_greedy(self, T: int, seed: int = 0, want_obs: bool = True, want_terms: bool = True,
                    want_actions: bool = True, want_targets: bool = False,
-                   out: Optional[Dict[str, torch.Tensor]] = None) -> Dict[str, torch.Tensor]:
+                   out: Optional[Dict[str, torch.Tensor]] = None, auto_reset_seed: Optional[int] = None,
+                   want_start_obs: bool = False) -> Dict[str, torch.Tensor]:
         """T closed-loop steps of the C-METHOD baseline (train.py:326-370) in one launch.  Pass a previous result as
-        `out` to reuse its buffers."""
+        `out` to reuse its buffers.  auto_reset_seed / want_start_obs: as run_actor."""
         o = out or {}
+        s64 = C.c_uint64(seed & (2 ** 64 - 1))
 
         def buf(key, shape, dtype, want=True):
             return self._reuse(o, key, shape, dtype, want)
@@ -464,11 +498,17 @@ class BatchedUavEnv(Handle):
         covered = buf("covered", (T, self.B), torch.int32)
         done = buf("done", (T, self.B), torch.uint8)
         ep = buf("ep_sums", (self.B, 5), torch.float32)
-        tp = self._with_targets(T, want_targets, o, lambda: _lib.check(
-            self._lib.uavtrack_run_greedy(self._h, C.c_int32(T), C.c_uint64(seed & (2 ** 64 - 1)), _ptr(acts), _ptr(obs),
-                                          _ptr(reward), _ptr(terms), _ptr(covered), _ptr(done), _ptr(ep), self._stream()),
-            "uavtrack_run_greedy"))
+        tail = (_ptr(acts), _ptr(obs), _ptr(reward), _ptr(terms), _ptr(covered), _ptr(done), _ptr(ep), self._stream())
+        if auto_reset_seed is None:
+            launch = lambda: _lib.check(self._lib.uavtrack_run_greedy(self._h, C.c_int32(T), s64, *tail), "uavtrack_run_greedy")
+        else:
+            launch = lambda: _lib.check(self._lib.uavtrack_run_greedy_autoreset(
+                self._h, C.c_int32(T), s64, C.c_uint64(auto_reset_seed & (2 ** 64 - 1)), *tail), "uavtrack_run_greedy_autoreset")
+        tp, so = self._with_start_obs(T, want_start_obs, o, lambda: self._with_targets(T, want_targets, o, launch))
+        self._count_episodes(T, auto_reset_seed)
         res = dict(actions=acts, obs=obs, reward=reward, terms=terms, covered=covered, done=done, ep_sums=ep)
+        if so is not None:
+            res["start_obs"] = so
         if tp is not None:
             res["targets"] = tp
         return res
@@ -547,9 +587,15 @@ class BatchedUavEnv(Handle):
 
     def run_actor(self, T: int, obs_in: torch.Tensor, seed: int = 0, mode: int = _lib.ACTOR_SAMPLE,
                   want_terms: bool = True, out: Optional[Dict[str, torch.Tensor]] = None,
-                  want_targets: bool = False) -> Dict[str, torch.Tensor]:
+                  want_targets: bool = False, auto_reset_seed: Optional[int] = None,
+                  want_start_obs: bool = False) -> Dict[str, torch.Tensor]:
         """T closed-loop steps of actor + environment (the rollout of train.operate_epoch, train.py:160-192) in
-        one launch.  obs_in [B, N, 12] is what the policy sees first (reset()'s return or the last obs)."""
+        one launch.  obs_in [B, N, 12] is what the policy sees first (reset()'s return or the last obs).
+        auto_reset_seed: environments whose done flag fires are reset inside the launch (reset(auto_reset_seed, next
+        episode)), so the launch may span episodes; episode e of an environment draws with seed + e
+        (uavtrack_run_actor_autoreset).  want_start_obs adds "start_obs" [T, B, N, 12]: where done[t, b] fired, the fresh
+        state's observation -- the policy's input at step t + 1; other rows are never written (and without
+        auto_reset_seed none is)."""
         if obs_in.shape != (self.B, self.N, _lib.OBS_DIM) or obs_in.dtype != torch.float32 \
                 or not obs_in.is_contiguous() or obs_in.device != self.device:
             raise ValueError(f"obs_in must be a contiguous float32 [{self.B}, {self.N}, {_lib.OBS_DIM}] tensor on {self.device}")
@@ -564,20 +610,32 @@ class BatchedUavEnv(Handle):
         covered = buf("covered", (T, self.B), torch.int32)
         done = buf("done", (T, self.B), torch.uint8)
         ep = buf("ep_sums", (self.B, 5), torch.float32)
-        tp = self._with_targets(T, want_targets, o, lambda: _lib.check(
-            self._lib.uavtrack_run_actor(self._h, C.c_int32(T), C.c_uint64(seed & (2 ** 64 - 1)), C.c_int32(mode), _ptr(obs_in),
-                                         _ptr(acts), _ptr(obs), _ptr(reward), _ptr(terms), _ptr(covered), _ptr(done), _ptr(ep),
-                                         self._stream()), "uavtrack_run_actor"))
+        s64 = C.c_uint64(seed & (2 ** 64 - 1))
+        tail = (C.c_int32(mode), _ptr(obs_in), _ptr(acts), _ptr(obs), _ptr(reward), _ptr(terms), _ptr(covered), _ptr(done),
+                _ptr(ep), self._stream())
+        if auto_reset_seed is None:
+            launch = lambda: _lib.check(self._lib.uavtrack_run_actor(self._h, C.c_int32(T), s64, *tail), "uavtrack_run_actor")
+        else:
+            launch = lambda: _lib.check(self._lib.uavtrack_run_actor_autoreset(
+                self._h, C.c_int32(T), s64, C.c_uint64(auto_reset_seed & (2 ** 64 - 1)), *tail), "uavtrack_run_actor_autoreset")
+        tp, so = self._with_start_obs(T, want_start_obs, o, lambda: self._with_targets(T, want_targets, o, launch))
+        self._count_episodes(T, auto_reset_seed)
         res = dict(actions=acts, obs=obs, reward=reward, terms=terms, covered=covered, done=done, ep_sums=ep)
+        if so is not None:
+            res["start_obs"] = so
         if tp is not None:
             res["targets"] = tp
         return res
 
     def bind_run(self, T: int, out: Dict[str, torch.Tensor], policy: str = "actor", obs_in: Optional[torch.Tensor] = None,
-                 seed: int = 0, mode: int = _lib.ACTOR_SAMPLE):
+                 seed: int = 0, mode: int = _lib.ACTOR_SAMPLE, auto_reset_seed: Optional[int] = None,
+                 want_start_obs: bool = False):
         """A zero-argument callable that issues `uavtrack_run_actor` / `uavtrack_run_greedy` (T steps, policy inside the
         kernel) into `out` on the stream current NOW, with every ctypes argument built once -- what a driver that issues
-        short fused chunks replays (the per-call Python of run_actor is a visible share of a 10-step launch)."""
+        short fused chunks replays (the per-call Python of run_actor is a visible share of a 10-step launch).
+        auto_reset_seed: the automatic-reset forms of the two calls (the host episode counter advances per call, as in
+        run_actor).  want_start_obs: out["start_obs"] [T, B, N, 12] (allocated when missing) is installed as the
+        start-observation buffer now and stays installed."""
         shapes = dict(actions=((T, self.B, self.N), torch.int32), obs=((T, self.B, self.N, _lib.OBS_DIM), torch.float32),
                       reward=((T, self.B, self.N), torch.float32), terms=((T, 3, self.B, self.N), torch.float32),
                       covered=((T, self.B), torch.int32), done=((T, self.B), torch.uint8), ep_sums=((self.B, 5), torch.float32))
@@ -589,21 +647,26 @@ class BatchedUavEnv(Handle):
         tail = (_ptr(out.get("actions")), _ptr(out.get("obs")), _ptr(out["reward"]), _ptr(out.get("terms")), _ptr(out.get("covered")),
                 _ptr(out.get("done")), _ptr(out.get("ep_sums")), self._stream())
         s64 = C.c_uint64(seed & (2 ** 64 - 1))
+        if policy not in ("actor", "greedy"):
+            raise ValueError("policy must be 'actor' or 'greedy'")
+        if want_start_obs:
+            out["start_obs"] = self._reuse(out, "start_obs", (T, self.B, self.N, _lib.OBS_DIM), torch.float32)
+            self.set_start_obs_output(out["start_obs"])
+        name = f"uavtrack_run_{policy}" + ("_autoreset" if auto_reset_seed is not None else "")
+        fn = getattr(self._lib, name)
+        head = (self._h, C.c_int32(T), s64) + ((C.c_uint64(auto_reset_seed & (2 ** 64 - 1)),) if auto_reset_seed is not None else ())
         if policy == "actor":
             if not self._fits(obs_in, (self.B, self.N, _lib.OBS_DIM), torch.float32):
                 raise ValueError("obs_in must be a contiguous float32 [B, N, 12] tensor on this device")
-            fn, name = self._lib.uavtrack_run_actor, "uavtrack_run_actor"
-            args = (self._h, C.c_int32(T), s64, C.c_int32(mode), _ptr(obs_in)) + tail
-        elif policy == "greedy":
-            fn, name = self._lib.uavtrack_run_greedy, "uavtrack_run_greedy"
-            args = (self._h, C.c_int32(T), s64) + tail
+            args = head + (C.c_int32(mode), _ptr(obs_in)) + tail
         else:
-            raise ValueError("policy must be 'actor' or 'greedy'")
+            args = head + tail
         keep = (out, obs_in)
 
         def call():
             if fn(*args) != 0:
                 _lib.check(1, name)
+            self._count_episodes(T, auto_reset_seed)
             return keep[0]
         return call
 

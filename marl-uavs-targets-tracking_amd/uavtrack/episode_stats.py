@@ -147,7 +147,8 @@ class EpisodeStats(Handle):
         save_csv(self.read(), save_dir, extra)
 
 
-def evaluate(env, policy, num_steps: int, episodes: int = 1, seed: int = 0, mode: str = "sample") -> Dict[str, np.ndarray]:
+def evaluate(env, policy, num_steps: int, episodes: int = 1, seed: int = 0, mode: str = "sample",
+             auto_reset: bool = False) -> Dict[str, np.ndarray]:
     """train.evaluate (train.py:298-324) for every environment of `env`, `episodes` times: reset, one fused launch of
     `num_steps` closed-loop steps, the six results per episode -> EpisodeStats.read() with episodes * B records (episode
     e of all environments, in ascending environment, before episode e + 1).
@@ -158,7 +159,14 @@ def evaluate(env, policy, num_steps: int, episodes: int = 1, seed: int = 0, mode
             "greedy": train.run (train.py:326-396), the C-METHOD baseline inside the step kernel (uavtrack_run_greedy).
             The reference's run_epoch leaves its four sums undivided; here they are divided by num_steps * n_uav like
             every other record.
-    Episode e is reset by hand with reset seed `seed + e` (the fused policy launches have no in-kernel reset).  How its
+    auto_reset=True: all `episodes` run in ONE launch of episodes * num_steps steps that resets each environment inside
+    the kernel (uavtrack_run_actor_autoreset / _run_greedy_autoreset; the handle's horizon must equal num_steps): one
+    reset(seed, episode 0) by hand, then episode e is the in-launch reset(seed, e) and draws with policy seed
+    `seed + e`.  The records come from the launch's own done flags ("path" is "auto_reset"), in EpisodeStats' order for
+    one add, ascending (t, b) of the closing step: episode e of all environments before episode e + 1, as below.  "ep_sums" is then [1, B, 5], the sums over
+    the whole launch.  (The reset seed is `seed` for every episode here, `seed + e` below: the two forms play different
+    episodes.)
+    Otherwise episode e is reset by hand with reset seed `seed + e`.  How its
     record is closed depends on the handle: where the environment was created with horizon == num_steps, the launch's
     own done flags close it (the "done" path); otherwise done never fires inside the episode and
     EpisodeStats.close() ends it (the "close" path).  The returned dict says which ran under "path"; the records are
@@ -175,10 +183,23 @@ def evaluate(env, policy, num_steps: int, episodes: int = 1, seed: int = 0, mode
     if not greedy:
         env.set_actor(policy.actor_state_dict() if isinstance(policy, DeviceActorCritic) else policy)
     by_done = env.cfg.horizon == num_steps
-    stats = EpisodeStats(env, log_capacity=episodes * env.B, max_steps=num_steps)
+    if auto_reset and not by_done:
+        raise ValueError(f"evaluate(auto_reset=True) needs an environment whose horizon ({env.cfg.horizon}) equals num_steps "
+                         f"({num_steps}): the in-launch reset fires on the handle's own done flag")
+    stats = EpisodeStats(env, log_capacity=episodes * env.B, max_steps=num_steps * (episodes if auto_reset else 1))
     out, ep = None, []
     try:
-        for e in range(episodes):
+        if auto_reset:
+            obs = env.reset(seed=seed, episode=0)
+            kw = dict(seed=seed, auto_reset_seed=seed)
+            if greedy:
+                out = env.run_greedy(episodes * num_steps, want_actions=False, **kw)
+            else:
+                out = env.run_actor(episodes * num_steps, obs, want_terms=True,
+                                    mode=_lib.ACTOR_ARGMAX if mode == "argmax" else _lib.ACTOR_SAMPLE, **kw)
+            ep.append(out["ep_sums"].clone())
+            stats.add(out)
+        for e in range(0 if auto_reset else episodes):
             obs = env.reset(seed=seed + e, episode=e)
             if greedy:
                 out = env.run_greedy(num_steps, seed=seed + e, want_actions=False, out=out)
@@ -192,6 +213,6 @@ def evaluate(env, policy, num_steps: int, episodes: int = 1, seed: int = 0, mode
         res = stats.read()
     finally:
         stats.destroy()
-    res["path"] = "done" if by_done else "close"
+    res["path"] = "auto_reset" if auto_reset else "done" if by_done else "close"
     res["ep_sums"] = torch.stack(ep)
     return res

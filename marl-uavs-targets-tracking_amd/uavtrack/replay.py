@@ -19,9 +19,15 @@ KEYS = ("states", "actions", "rewards", "next_states")
 
 def transitions_from_rollout(obs_in: torch.Tensor, out: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
     """The (state, action, reward, next_state) tuples of train.py:176-180 from one rollout's outputs:
-    obs_in [B,N,12] is what the policy saw first; out = {obs [T,B,N,12], actions [T,B,N], reward [T,B,N]}."""
+    obs_in [B,N,12] is what the policy saw first; out = {obs [T,B,N,12], actions [T,B,N], reward [T,B,N]}.
+    A rollout that crossed episode ends (run_actor(auto_reset_seed=..., want_start_obs=True)) also carries done [T,B]
+    and start_obs [T,B,N,12]: where done[t-1, b] fired, the state of step t is start_obs[t-1, b] -- the observation of
+    the fresh state the environment was reset to -- not the finished episode's last observation obs[t-1, b]."""
     obs = out["obs"]
     states = torch.cat([obs_in.unsqueeze(0), obs[:-1]], dim=0)
+    if out.get("done") is not None and out.get("start_obs") is not None and obs.shape[0] > 1:
+        fired = out["done"][:-1].bool()[:, :, None, None]
+        states[1:] = torch.where(fired, out["start_obs"][:-1], states[1:])
     D = obs.shape[-1]
     return {"states": states.reshape(-1, D), "actions": out["actions"].reshape(-1),
             "rewards": out["reward"].reshape(-1), "next_states": obs.reshape(-1, D)}

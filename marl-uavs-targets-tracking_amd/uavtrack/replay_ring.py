@@ -84,8 +84,11 @@ class PrioritizedReplayRing(Handle):
 
     def add_rollout(self, obs_in: torch.Tensor, out: Dict[str, torch.Tensor]) -> None:
         """add(transitions_from_rollout(obs_in, out)) in one library call: obs_in [B,N,12] is what the policy saw
-        first, out = {obs [T,B,N,12], actions [T,B,N] int32, reward [T,B,N]} (BatchedRollout.run_fused's outputs)."""
+        first, out = {obs [T,B,N,12], actions [T,B,N] int32, reward [T,B,N]} (BatchedRollout.run_fused's outputs).  When
+        `out` carries start_obs (a rollout across episode ends, with its done [T,B] uint8), the state behind a fired done
+        is the fresh state's observation (uavtrack_replay_add_rollout_episodes)."""
         obs, act, rew = out["obs"], out["actions"], out["reward"]
+        so = out.get("start_obs")
         T = obs.shape[0]
         M = obs_in.numel() // _lib.OBS_DIM
         if obs.numel() != T * M * _lib.OBS_DIM or act.numel() != T * M or rew.numel() != T * M:
@@ -98,6 +101,20 @@ class PrioritizedReplayRing(Handle):
             if t.device != self.device or not t.is_contiguous():
                 raise ValueError("add_rollout: every input must be contiguous on the ring's device")
         ring = self._ring()
+        if so is not None:
+            done = out.get("done")
+            if obs.dim() != 4 or done is None or tuple(done.shape) != tuple(obs.shape[:2]) or done.dtype != torch.uint8 \
+                    or tuple(so.shape) != tuple(obs.shape) or so.dtype != torch.float32:
+                raise ValueError("add_rollout: with start_obs, obs must be [T,B,N,12], done uint8 [T,B] and start_obs "
+                                 "float32 of obs's shape")
+            for t in (done, so):
+                if t.device != self.device or not t.is_contiguous():
+                    raise ValueError("add_rollout: every input must be contiguous on the ring's device")
+            _lib.check(self._lib.uavtrack_replay_add_rollout_episodes(
+                self._h, C.byref(ring), T, int(obs.shape[1]), int(obs.shape[2]), _ptr(obs_in), _ptr(obs), _ptr(act), _ptr(rew),
+                _ptr(done), _ptr(so), self._stream()), "uavtrack_replay_add_rollout_episodes")
+            self._advance(T * M)
+            return
         _lib.check(self._lib.uavtrack_replay_add_rollout(self._h, C.byref(ring), T, M, _ptr(obs_in), _ptr(obs),
                                                          _ptr(act), _ptr(rew), self._stream()),
                    "uavtrack_replay_add_rollout")

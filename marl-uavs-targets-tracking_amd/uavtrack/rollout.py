@@ -49,14 +49,18 @@ class BatchedRollout:
 
     def __init__(self, env: BatchedUavEnv, policy, select: Callable[[torch.Tensor], torch.Tensor] = sample_actions,
                  steps_per_graph: int = 8, use_graph: bool = True, seed: int = 0, device_actor: bool = False,
-                 fuse_chunks: bool = False):
-        """fuse_chunks (library policies only: device_actor or "greedy"): run() issues every `steps_per_graph` steps as
+                 fuse_chunks: bool = False, auto_reset_seed: Optional[int] = None):
+        """auto_reset_seed (library policies only): run_fused and the fuse_chunks path of run() cross episode ends -- an
+        environment whose done flag fires is reset inside the launch (reset(auto_reset_seed, next episode)) and goes on
+        from the fresh state's observation; the results of run_fused then carry "start_obs" (see BatchedUavEnv.run_actor).
+        fuse_chunks (library policies only: device_actor or "greedy"): run() issues every `steps_per_graph` steps as
         ONE launch with the policy inside the step kernel (uavtrack_run_actor / uavtrack_run_greedy with T = k -- the
         same bits as k x (policy kernel, step), see tests) instead of replaying a graph of 2 k kernels: a kernel boundary
         costs this path more than the step itself (a T = 1 launch is ~7 us of GPU time for a 2.6 us step)."""
         self.env, self.policy, self.select, self.seed = env, policy, select, seed
         self.device_actor = device_actor
         self.fuse_chunks = bool(fuse_chunks) and (device_actor or isinstance(policy, str))
+        self.auto_reset_seed = auto_reset_seed
         self._chunk_out: Optional[Dict[str, torch.Tensor]] = None
         if device_actor:
             env.set_actor(policy)
@@ -71,7 +75,7 @@ class BatchedRollout:
         self._ep_ring: Optional[torch.Tensor] = None                   # fuse_chunks: one row of episode sums per chunk of a run()
         self._ep_used = 0
         self._bound: Dict[int, Callable] = {}
-        self._bound_key = None                                         # (stream handle, seed) the bound calls were built under
+        self._bound_key = None                                         # (stream handle, seed, reset seed) the bound calls were built under
         self._graph_seed = None
         self._chunk_ready = False
         self._stats = None                                             # run(stats=...): the EpisodeStats the chunks of this run feed
@@ -126,7 +130,7 @@ class BatchedRollout:
         done = 0
         if self.fuse_chunks:
             # a bound call froze the stream current when it was built and the seed: another stream or seed rebuilds them
-            key = (self.env._stream().value, self.seed)
+            key = (self.env._stream().value, self.seed, self.auto_reset_seed)
             if key != self._bound_key:
                 self._bound.clear()
                 self._bound_key = key
@@ -151,6 +155,11 @@ class BatchedRollout:
             self._one_step()
         return {"ep_sums": self.ep, "obs": self.obs, "reward": self.last_reward}
 
+    def _carry(self, res) -> None:
+        """(auto_reset_seed) What the policy sees next, into the driver's own `obs` buffer: the launch's last observation,
+        or, for an environment reset behind the launch's last step, the fresh state's."""
+        torch.where(res["done"][-1].bool()[:, None, None], res["start_obs"][-1], res["obs"][-1], out=self.obs)
+
     def _fused_chunk(self, k: int):
         """k closed-loop steps of the library policy + environment in one launch; state of the driver as after k _one_step().
         Nothing but the launch is issued per chunk: `obs` / `last_reward` become VIEWS of the chunk's last rows (the next
@@ -166,6 +175,7 @@ class BatchedRollout:
             self._ep_used = 0
         ep_row = ring[self._ep_used]
         self._ep_used += 1
+        ar = self.auto_reset_seed is not None      # then `obs` stays the driver's own buffer (_carry), never a view of a chunk
         out = self._chunk_out if self._chunk_out is not None and self._chunk_out["reward"].shape[0] == k else None
         if out is not None and k == self.k and self._chunk_ready:
             # steady state: a pre-built library call per ring row (the chunk's buffers, its first observation = the previous
@@ -173,24 +183,32 @@ class BatchedRollout:
             call = self._bound.get(self._ep_used - 1)
             if call is None:
                 call = self._bound[self._ep_used - 1] = self.env.bind_run(
-                    k, dict(out, ep_sums=ep_row), "actor" if self.device_actor else "greedy", obs_in=self.obs, seed=self.seed)
+                    k, dict(out, ep_sums=ep_row), "actor" if self.device_actor else "greedy", obs_in=self.obs, seed=self.seed,
+                    auto_reset_seed=self.auto_reset_seed, want_start_obs=ar)
             call()
+            if ar:
+                self._carry(out)
             if self._stats is not None:
                 self._stats.add(out)
             return
         if out is not None:
             out = dict(out, ep_sums=ep_row)
         if self.device_actor:
-            res = self.env.run_actor(k, self.obs, seed=self.seed, want_terms=True, out=out)
+            res = self.env.run_actor(k, self.obs, seed=self.seed, want_terms=True, out=out, auto_reset_seed=self.auto_reset_seed,
+                                     want_start_obs=ar)
         else:
-            res = self.env.run_greedy(k, seed=self.seed, want_actions=False, out=out)
+            res = self.env.run_greedy(k, seed=self.seed, want_actions=False, out=out, auto_reset_seed=self.auto_reset_seed,
+                                      want_start_obs=ar)
         if out is None:
             ep_row.copy_(res["ep_sums"])
             if k == self.k:
                 self._chunk_out = res
         if self._stats is not None:
             self._stats.add(res)
-        self.obs = res["obs"][-1]
+        if ar:
+            self._carry(res)
+        else:
+            self.obs = res["obs"][-1]
         self.last_reward = res["reward"][-1]
         self._chunk_ready = out is not None        # from now on obs / last_reward are the views the bound calls were built on
 
@@ -212,10 +230,15 @@ class BatchedRollout:
         EpisodeStats) receives the launch's outputs on the same stream; the terms are then written whatever want_terms
         says."""
         assert self.device_actor, "run_fused needs device_actor=True"
-        res = self.env.run_actor(steps, self.obs, seed=self.seed, want_terms=want_terms or stats is not None, out=out)
+        ar = self.auto_reset_seed
+        res = self.env.run_actor(steps, self.obs, seed=self.seed, want_terms=want_terms or stats is not None, out=out,
+                                 auto_reset_seed=ar, want_start_obs=ar is not None)
         if stats is not None:
             stats.add(res)
-        self.obs.copy_(res["obs"][-1])
+        if ar is not None:
+            self._carry(res)
+        else:
+            self.obs.copy_(res["obs"][-1])
         self.last_reward.copy_(res["reward"][-1])
         self.ep += res["ep_sums"]
         res = dict(res)
