@@ -514,16 +514,36 @@ int orc_reset_philox(const orc_config *cfg, uint64_t seed, uint32_t episode,
 }
 
 /* ---- greedy baseline policy, uav.py:324-369 -------------------------------------------------- */
+/* What an fp32 evaluation may move a score, an angle, a distance by: the thresholds of the robustness verdict */
+#define GREEDY_TOL_SCORE 2e-5
+#define GREEDY_TOL_ANGLE 1e-4
+#define GREEDY_TOL_DIST  1e-2
+
+/* d^2 of a UAV-target pair as an fp32 evaluation forms it from the fp32-rounded inputs: fma(dy, dy, dx * dx) */
+static float greedy_d2_f32(double x, double y, double gx, double gy)
+{
+    const float dx = (float)gx - (float)x, dy = (float)gy - (float)y;
+    return fmaf(dy, dy, dx * dx);
+}
+
 int orc_greedy_actions(const orc_config *cfg, uint64_t seed, int64_t env_offset, const int32_t *step_count,
                        const double *ux, const double *uy, const double *uh,
                        const double *tx, const double *ty,
                        int32_t *actions, double *mg_score, double *mg_angle, double *mg_dist,
-                       int force_argmax, double *best_angle_out, int32_t *branch_out)
+                       int force_argmax, double *best_angle_out, int32_t *branch_out, uint8_t *robust)
 {
     const int B = cfg->n_envs, N = cfg->n_uav, M = cfg->m_targets, na = cfg->na;
     const uint32_t key[2] = {(uint32_t)seed, (uint32_t)(seed >> 32)};
+    /* per target of the UAV at hand: the interval [lo, hi] its score lies in whichever way the uncertain penalty tests
+     * fall, and its distance */
+    double *lo = NULL, *hi = NULL, *dk = NULL;
     long b;
     if (cfg->dim != 2) return -1;
+    if (robust) {
+        lo = (double *)malloc(sizeof(double) * 3 * (size_t)M);
+        if (!lo) return -2;
+        hi = lo + M; dk = lo + 2 * (size_t)M;
+    }
     for (b = 0; b < B; ++b) {
         const double *x = ux + (size_t)b * N, *y = uy + (size_t)b * N, *h = uh + (size_t)b * N;
         const double *gx = tx + (size_t)b * M, *gy = ty + (size_t)b * M;
@@ -535,11 +555,13 @@ int orc_greedy_actions(const orc_config *cfg, uint64_t seed, int64_t env_offset,
             uint32_t r[4];
             double best = -INFINITY, second = -INFINITY, best_angle = 0.0;
             double ms = INFINITY, ma = INFINITY;                    /* this UAV's margins */
+            int best_k = 0;
             orc_philox4x32_10(ctr, key, r);
             if (mg_score) mg_score[(size_t)b * N + i] = INFINITY;
             if (mg_angle) mg_angle[(size_t)b * N + i] = INFINITY;
             if (best_angle_out) best_angle_out[(size_t)b * N + i] = NAN;
             if (branch_out) branch_out[(size_t)b * N + i] = 0;
+            if (robust) robust[(size_t)b * N + i] = 1;              /* the draws are bit-exact: a random action always is */
             if (!force_argmax && u01f(r[0]) < 0.25f) {              /* uav.py:338-339 */
                 actions[(size_t)b * N + i] = (int32_t)(((uint64_t)r[1] * (uint32_t)na) >> 32);
                 continue;
@@ -547,17 +569,26 @@ int orc_greedy_actions(const orc_config *cfg, uint64_t seed, int64_t env_offset,
             for (k = 0; k < M; ++k) {                               /* uav.py:341-362 */
                 const double d_t = dist2(x[i], y[i], gx[k], gy[k]);
                 double pen = 0.0, score;
+                int sure = 0, unsure = 0;                           /* others certainly inside dc / within the tolerance of dc */
                 for (j = 0; j < N; ++j) {
                     if (x[j] != x[i] || y[j] != y[i]) {             /* `(uav_x, uav_y) != (self.x, self.y)` */
                         const double d = dist2(x[j], y[j], gx[k], gy[k]);
                         note_margin(&md, d, cfg->dc);
                         if (d < cfg->dc) pen += 0.8;
+                        if (fabs(d - cfg->dc) <= GREEDY_TOL_DIST) ++unsure;
+                        else if (d < cfg->dc) ++sure;
                     }
                 }
                 score = 1.0 / d_t - pen;
+                if (robust) {
+                    hi[k] = 1.0 / d_t - 0.8 * sure;
+                    lo[k] = 1.0 / d_t - 0.8 * (sure + unsure);
+                    dk[k] = d_t;
+                }
                 if (score > best) {
                     second = best;
                     best = score;
+                    best_k = k;
                     best_angle = atan2(gy[k] - y[i], gx[k] - x[i]) - h[i];
                 } else if (score > second) {
                     second = score;
@@ -567,6 +598,40 @@ int orc_greedy_actions(const orc_config *cfg, uint64_t seed, int64_t env_offset,
             if (best_angle_out) best_angle_out[(size_t)b * N + i] = best_angle;   /* what uav.py:362 leaves behind */
             const int straight = !force_argmax && u01f(r[2]) < 0.3f; /* uav.py:365-366 */
             if (branch_out) branch_out[(size_t)b * N + i] = straight ? 1 : 2;
+            if (robust && !straight) {
+                /* The scoring branch.  The choice stands iff the chosen target's score beats every other target's by more
+                 * than the score tolerance whichever way the uncertain penalty tests fall, or ties it EXACTLY: an exact tie
+                 * is decided by index (first best wins), here and in fp32 alike, provided fp32 sees a tie too.  The condition
+                 * for that, on the fp32-rounded inputs: the two d^2 are bitwise equal as fp32 forms them (then 1/d is, from
+                 * whatever instruction), the fp64 distances are equal, and either both are zero (score +inf, no penalty
+                 * matters) or neither target has an uncertain penalty test and both carry the same count (lo == hi, equal).
+                 * Mirror-image and coincident targets are the simple cases.  The angle must keep the angle tolerance from the
+                 * nearest action boundary and from the seam of the wrap at +-pi (index na - 1 on one side, 0 on the other). */
+                const float d2c = greedy_d2_f32(x[i], y[i], gx[best_k], gy[best_k]);
+                int ok = 1;
+                for (k = 0; k < M && ok; ++k) {
+                    if (k == best_k) continue;
+                    if (lo[best_k] - hi[k] > GREEDY_TOL_SCORE) continue;      /* (inf - finite = inf; inf - inf = NaN: falls through) */
+                    {
+                        const float d2k = greedy_d2_f32(x[i], y[i], gx[k], gy[k]);
+                        const int same_bits = memcmp(&d2k, &d2c, sizeof d2k) == 0;
+                        const int exact = dk[k] == dk[best_k] &&
+                                          (dk[k] == 0.0 || (lo[k] == hi[k] && lo[best_k] == hi[best_k] && hi[k] == hi[best_k]));
+                        ok = same_bits && exact && k > best_k;
+                    }
+                }
+                if (ok) {
+                    const double ang = py_fmod_pos(best_angle + ORC_PI, 2.0 * ORC_PI) - ORC_PI;
+                    double bestd = INFINITY, secondd = INFINITY;
+                    for (a = 0; a < na; ++a) {
+                        const double dd = fabs(ang - cfg->dt * (2.0 * (a + 1) - na - 1) * cfg->u_h_max / (na - 1));
+                        if (dd < bestd) { secondd = bestd; bestd = dd; }
+                        else if (dd < secondd) secondd = dd;
+                    }
+                    ok = (secondd - bestd) * 0.5 > GREEDY_TOL_ANGLE && ORC_PI - fabs(ang) > GREEDY_TOL_ANGLE;
+                }
+                robust[(size_t)b * N + i] = (uint8_t)ok;
+            }
             if (straight) best_angle = 0.0;
             {   /* find_closest_a_idx, defined here: nearest turn rate of uav.py:73-81 to the wrapped angle */
                 const double ang = py_fmod_pos(best_angle + ORC_PI, 2.0 * ORC_PI) - ORC_PI;
@@ -587,6 +652,7 @@ int orc_greedy_actions(const orc_config *cfg, uint64_t seed, int64_t env_offset,
         }
         if (mg_dist) mg_dist[b] = md;
     }
+    free(lo);
     return 0;
 }
 

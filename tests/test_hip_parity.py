@@ -796,7 +796,9 @@ def test_closed_loop_rollout_graph_equals_eager(uavtrack):
 def test_greedy_baseline_policy_vs_oracle(uavtrack):
     """UAV.get_action_by_direction (uav.py:324-369) on device vs the fp64 oracle.  Actions are
     indices: exact wherever the oracle's margins (score gap between the two best targets, distance of the
-    angle to an action boundary, |d - dc| of the penalty tests) leave fp32 no room to flip."""
+    angle to an action boundary, |d - dc| of the penalty tests THIS UAV's choice depends on) leave fp32 no room to
+    flip; tests/test_hip_greedy.py runs the kernel's own geometry and the hand-made edge scenes."""
+    from greedy_scenes import CAP
     from oracle import greedy_actions
     for N, M, B, box in ((20, 10, 512, 2000.0), (5, 3, 300, 2000.0), (50, 25, 64, 2000.0), (20, 10, 256, 600.0)):
         kw = dict(n_envs=B, n_uav=N, m_targets=M, x_max=box, y_max=box)
@@ -811,8 +813,13 @@ def test_greedy_baseline_policy_vs_oracle(uavtrack):
             got = env.greedy_actions(seed=99).cpu().numpy()
             want, mg = greedy_actions(orc, 99, st["step_count"], env_offset=77)
             # (the score 1/d - 0.8 * #others reaches tens in a crowded box, where an fp32 ulp is ~4e-6)
-            ok = (mg["score"] > 2e-5) & (mg["angle"] > 1e-4) & (mg["dist"][:, None] > 1e-2)
-            assert ok.mean() > 0.5, (N, M, t, ok.mean())
+            # Compared: every UAV the oracle's per-UAV verdict calls robust (uav_oracle.h; a pair near dc sets aside only the
+            # UAVs whose choice it can change) and every UAV the margins this test used before accepted; at most 10 % of the
+            # scoring-branch decisions may be left out (greedy_scenes.CAP).
+            ok = mg["robust"] | ((mg["score"] > 2e-5) & (mg["angle"] > 1e-4) & (mg["dist"][:, None] > 1e-2))
+            steer = mg["branch"] == 2
+            assert (steer & ~ok).sum() <= CAP * steer.sum(), (N, M, t, int((steer & ~ok).sum()), int(steer.sum()))
+            assert ok[~steer].all()
             np.testing.assert_array_equal(got[ok], want[ok], err_msg=f"N{N} M{M} t{t}")
             assert got.min() >= 0 and got.max() <= 11
             total += int(ok.sum())

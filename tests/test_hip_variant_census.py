@@ -22,6 +22,7 @@ import pytest
 import torch
 
 import variant_census as vc
+from greedy_scenes import CAP
 from oracle import OracleConfig, OracleEnv, OraclePmi, actor_actions, greedy_actions
 from test_hip_parity import (ATOL, MARGIN, RTOL_POSE, Tally, check_outputs, check_state, host, inject, knife_masks,
                              random_pmi_state_dict)
@@ -114,8 +115,12 @@ def _check_policy(e, orc, kw, out, obs_in, seed, step_count, actor, pre, what):
     """The launch's own actions against the oracle's policy, outside its margins (tests/fuzz_api.py steps 2 and 3)."""
     if e.key[4] == vc.GREEDY:
         want, mg = greedy_actions(orc, seed, step_count)
-        okg = (mg["score"] > 2e-5) & (mg["angle"] > 1e-4) & (mg["dist"][:, None] > 1e-2)
+        # the oracle's per-UAV verdict and whatever the per-environment margins used here before accepted; at most 10 % of
+        # the scoring-branch decisions left out (greedy_scenes.CAP; the census scene leaves out about 1 %)
+        okg = mg["robust"] | ((mg["score"] > 2e-5) & (mg["angle"] > 1e-4) & (mg["dist"][:, None] > 1e-2))
+        steer = mg["branch"] == 2
         assert okg.any(), what
+        assert (steer & ~okg).sum() <= CAP * steer.sum() and okg[~steer].all(), (what, int((steer & ~okg).sum()), int(steer.sum()))
         np.testing.assert_array_equal(out["actions"][okg], want[okg], err_msg=f"{what} greedy actions")
     elif e.key[4] == vc.ACTOR:
         aa, probs = pre           # actor_actions on the same observation and step count, taken before the launch
