@@ -13,6 +13,7 @@ update is the same rule on a sampled batch, and the new actor weights are re-upl
     python examples/train_maac.py --method maac-r --envs 1024 --iters 40     # reciprocal (PMI) reward, PMI net trained too
     python examples/train_maac.py --replay prioritized --learner device --envs 4096 --n-uav 20   # prioritised ring, 32.8 M slots
     python examples/train_maac.py --replay prioritized --learner device --publish device --log-every 10   # no host sync per iteration
+    python examples/train_maac.py --replay prioritized --learner device --importance --beta-final 1.0     # train on the importance weights, beta annealed on the device
     python examples/train_maac.py --method maac-r --pmi-trainer device --learner device --replay prioritized --publish device --log-every 10
     python examples/train_maac.py --shards 8 --envs 32768 --n-uav 20 --learner device --replay prioritized --publish device   # 8 shard handles, one learner
     python examples/train_maac.py --phase evaluate --envs 256 --eval-episodes 4 --save-dir out   # train.evaluate, batched; csv files
@@ -54,14 +55,19 @@ class ValueNet(torch.nn.Module):
         return self.fc2(torch.relu(self.fc1(x))).squeeze(-1)
 
 
-def update(actor, critic, opt_a, opt_c, batch, gamma):
-    """One ActorCritic.update step (actor_critic.py:150-178) on a batch of transitions."""
+def update(actor, critic, opt_a, opt_c, batch, gamma, weights=None):
+    """One ActorCritic.update step (actor_critic.py:150-178) on a batch of transitions.  weights (--importance): the
+    draw's importance weights, one per row, multiplied into the per-sample losses before the mean."""
     s, a, r, s2 = batch["states"], batch["actions"].long().unsqueeze(1), batch["rewards"], batch["next_states"]
     td_target = r + gamma * critic(s2)
     td_delta = td_target - critic(s)
     log_probs = torch.log(actor(s).gather(1, a).squeeze(1).clamp_min(1e-12))
-    actor_loss = torch.mean(-log_probs * td_delta.detach())
-    critic_loss = torch.nn.functional.mse_loss(critic(s), td_target.detach())
+    if weights is None:
+        actor_loss = torch.mean(-log_probs * td_delta.detach())
+        critic_loss = torch.nn.functional.mse_loss(critic(s), td_target.detach())
+    else:
+        actor_loss = torch.mean(weights * (-log_probs * td_delta.detach()))
+        critic_loss = torch.mean(weights * (critic(s) - td_target.detach()) ** 2)
     opt_a.zero_grad(); opt_c.zero_grad()
     actor_loss.backward(); critic_loss.backward()
     opt_a.step(); opt_c.step()
@@ -106,6 +112,18 @@ def evaluate_phase(args, env, policy):
     save_results(args, res)
     env.close()
     return res["return_list"].tolist()
+
+
+def importance_kwargs(args):
+    """What --importance / --beta / --beta-final mean to update_from, update_from_many and the ring's sample(): nothing
+    without --importance (the reference's update drops the weights), else beta and, with --beta-final, the linear
+    schedule over every draw of the run (iters x updates), counted on the device."""
+    if not args.importance:
+        return {}
+    kw = {"importance": True, "beta": args.beta}
+    if args.beta_final is not None:
+        kw.update(beta_final=args.beta_final, anneal_calls=max(1, args.iters * args.updates))
+    return kw
 
 
 def train_sharded(args, timings=None):
@@ -153,7 +171,7 @@ def train_sharded(args, timings=None):
             torch.cuda.synchronize()
         t_roll = time.perf_counter() - t0
         for _ in range(args.updates):
-            la_t, lc_t, _ = learner.update_from_many(rings, per_shard)
+            la_t, lc_t, _ = learner.update_from_many(rings, per_shard, **importance_kwargs(args))
         la, lc = (float(la_t), float(lc_t)) if log else (la_t, lc_t)
         if args.publish == "host":
             actor.load_state_dict(learner.actor_state_dict())
@@ -224,6 +242,13 @@ def main(argv=None, timings=None):
                          "from the rollout and drawn from in HIP, |td_delta| written back as the new priorities")
     ap.add_argument("--alpha", type=float, default=0.6, help="--replay prioritized: priority exponent (train.py:74)")
     ap.add_argument("--beta", type=float, default=0.4, help="--replay prioritized: importance exponent (train.py:100)")
+    ap.add_argument("--importance", action="store_true",
+                    help="--replay prioritized only: train on the draw's importance weights (count * P(i))^-beta / max "
+                         "(weighted critic and actor losses: DeviceActorCritic.update_from(importance=True), or the torch "
+                         "learner's per-sample losses times the weights); default: drop them, as the reference does")
+    ap.add_argument("--beta-final", type=float, default=None,
+                    help="--importance only: anneal beta linearly from --beta to this value over the run's iters x updates "
+                         "draws, on the ring's device call counter (no host value to freeze in a captured update)")
     ap.add_argument("--publish", choices=["host", "device"], default="host",
                     help="host: the learner's actor weights reach the rollout through the host pack (sync_actor); device: "
                          "packed on the device from the learner's parameters (publish_actor), no copy, no synchronisation; "
@@ -266,6 +291,10 @@ def main(argv=None, timings=None):
         ap.error("--rollout-episodes K > 1 runs on one environment handle (no --shards)")
     if args.phase == "run" and args.method == "maac-r":
         ap.error("--phase run is the C-METHOD baseline: it runs with the maac / maac-g rewards")
+    if args.importance and args.replay != "prioritized":
+        ap.error("--importance needs --replay prioritized (a uniform draw has no importance weights)")
+    if args.beta_final is not None and not args.importance:
+        ap.error("--beta-final anneals the importance exponent: it needs --importance")
     if args.phase != "train":
         args.shards = 1
 
@@ -345,9 +374,10 @@ def main(argv=None, timings=None):
             torch.cuda.synchronize()
         t_roll = time.perf_counter() - t0
         if learner is None and args.replay == "prioritized":          # train.py:250-262
+            ikw = importance_kwargs(args)
             for _ in range(args.updates):
-                batch, idx, _w = replay.sample(args.batch, args.beta)
-                la, lc = update(actor, critic, opt_a, opt_c, batch, args.gamma)
+                batch, idx, w = replay.sample(args.batch, args.beta, ikw.get("beta_final"), ikw.get("anneal_calls", 0))
+                la, lc = update(actor, critic, opt_a, opt_c, batch, args.gamma, w if args.importance else None)
                 with torch.no_grad():
                     s, r, s2 = batch["states"], batch["rewards"], batch["next_states"]
                     replay.update_priorities(idx, (r + args.gamma * critic(s2) - critic(s)).abs())
@@ -356,7 +386,7 @@ def main(argv=None, timings=None):
                 la, lc = update(actor, critic, opt_a, opt_c, replay.sample(args.batch), args.gamma)
         else:
             for _ in range(args.updates):
-                la_t, lc_t, _ = learner.update_from(replay, args.batch)
+                la_t, lc_t, _ = learner.update_from(replay, args.batch, **importance_kwargs(args))
             la, lc = (float(la_t), float(lc_t)) if log else (la_t, lc_t)
             if args.publish == "host":
                 actor.load_state_dict(learner.actor_state_dict())     # the rollout's actor: host pack, as sync_actor

@@ -504,6 +504,29 @@ int uavtrack_learner_update(uavtrack_learner *learner, int64_t n,
                             const float *next_states, int64_t capacity, const int64_t *indices,
                             float *actor_loss, float *critic_loss, float *td_delta, float *priorities, void *stream);
 
+/* ---- importance-weighted updates ----
+ * uavtrack_learner_update with one weight per batch row: weights (DEVICE fp32 [n], in BATCH order: weights[i] belongs
+ * to row i of the batch, not to slot indices[i]), w_i >= 0 -- the importance-sampling weights a prioritised draw hands
+ * out with its indices (uavtrack_replay_sample, uavtrack_replay_sample_annealed).  The losses become
+ *   critic_loss                            = mean_i( w_i * (V(s_i) - y_i)^2 ),  y_i = r_i + gamma * V(s'_i) detached
+ *   actor_loss, UAVTRACK_LOSS_PER_SAMPLE   = mean_i( -w_i * log p_i * delta_i )
+ *   actor_loss, UAVTRACK_LOSS_REFERENCE    = mean_i( -w_i * log p_i ) * mean_j( w_j * delta_j )
+ * The reference's broadcast loss is a double sum over pairs, (1/n^2) sum_i sum_j (-log p_i) delta_j; the importance
+ * weight of the pair (i, j) is w_i * w_j, which gives the product of the two weighted means (and stays linear in the
+ * weighted mean of delta, so gradient rows still add).  Every mean divides by n, the row count, as torch's
+ * (w * l).mean() does -- not by sum w.  td_delta and the priorities written back stay the unweighted delta_i and
+ * |delta_i|.  With every w_i = 1 each formula is uavtrack_learner_update's, and weights == NULL makes the call exactly
+ * uavtrack_learner_update: a vector of ones gives the same bits.
+ * A weight that is NaN, infinite or negative is found on the device like a bad action (status bit 2): the update then
+ * changes nothing, its losses are NaN and the next uavtrack_learner_check counts it.  A refused draw writes NaN weights,
+ * so the update behind a refused draw is refused too, with no host involvement. */
+int uavtrack_learner_update_weighted(uavtrack_learner *learner, int64_t n,
+                                     const float *states, const int32_t *actions, const float *rewards,
+                                     const float *next_states, int64_t capacity, const int64_t *indices,
+                                     const float *weights,
+                                     float *actor_loss, float *critic_loss, float *td_delta, float *priorities,
+                                     void *stream);
+
 /* ---- the split update: gradient rows and an ordered apply ----
  * uavtrack_learner_update cut between "sum" and "scale + Adam", so that one update can take its batch from several
  * rings, several calls (gradient accumulation) or several processes (data parallelism) with DEFINED bits: every sum is
@@ -515,11 +538,15 @@ int uavtrack_learner_update(uavtrack_learner *learner, int64_t n,
  *               UAVTRACK_LOSS_PER_SAMPLE; the critic's sums of V - target): what the update forms before it scales
  *   [P, P+4)    the loss sums: sum -log p, sum delta, sum -log p * delta, sum (V - target)^2
  *   P+4, P+5    n of this row, an int64 as its low and high 32 bits
- *   P+6         int32 status bits of this row: bit 0 an action outside [0, A), bit 1 an index outside [0, capacity)
+ *   P+6         int32 status bits of this row: bit 0 an action outside [0, A), bit 1 an index outside [0, capacity),
+ *               bit 2 an importance weight that is NaN, infinite or negative
  *   P+7         int32 P, the layout tag
  * The reference's actor loss mean(-log p) * mean(delta) is linear in mean(delta), which is why the rows can be summed:
  * the apply scales the actor's sums once by the GLOBAL -mean(delta) / N.  (Averaging per-row updates or per-row loss
  * gradients is a different rule.)
+ * A row of uavtrack_learner_grad_weighted has the same layout and tag; every term of its sums carries its batch row's
+ * w_i (sum -w log p, sum w delta, sum -w log p delta, sum w (V - target)^2), its n is still the row count, and weighted
+ * and unweighted rows may meet in one apply.
  * All four calls are stream-ordered: no synchronisation, no allocation, capturable.  Host-side errors (a null required
  * pointer, n < 1 or above the reserved batch, count outside [1, UAVTRACK_LEARNER_MAX_ROWS]) enqueue nothing. */
 #define UAVTRACK_LEARNER_MAX_ROWS 64   /* rows one apply takes: ranks x micro-batches */
@@ -535,6 +562,13 @@ int uavtrack_learner_grad(uavtrack_learner *learner, int64_t n,
                           const float *next_states, int64_t capacity, const int64_t *indices,
                           float *td_delta, float *row, void *stream);
 
+/* uavtrack_learner_grad with importance weights (DEVICE fp32 [n], batch order; see "importance-weighted updates"):
+ * weights == NULL makes it exactly uavtrack_learner_grad.  td_delta stays the unweighted delta. */
+int uavtrack_learner_grad_weighted(uavtrack_learner *learner, int64_t n,
+                                   const float *states, const int32_t *actions, const float *rewards,
+                                   const float *next_states, int64_t capacity, const int64_t *indices,
+                                   const float *weights, float *td_delta, float *row, void *stream);
+
 /* One update from rows [count][row_floats] (DEVICE): gradient and loss sums added in row order in fp32, N = sum of the
  * rows' n, losses and scales as uavtrack_learner_update forms them from N, then both Adam steps and the step counts.
  * If any row carries a status bit or another layout tag, the apply changes nothing (parameters, moments, steps), its
@@ -549,8 +583,8 @@ int uavtrack_learner_apply(uavtrack_learner *learner, const float *rows, int64_t
 int uavtrack_learner_write_priorities(uavtrack_learner *learner, int64_t n, const int64_t *indices, int64_t capacity,
                                       const float *td_delta, float *priorities, void *stream);
 
-/* Synchronises `stream`; fails if any update or apply since the previous check was refused on the device (bad action
- * or index, or a row of another layout).  refused (nullable) receives their number; the count restarts at 0. */
+/* Synchronises `stream`; fails if any update or apply since the previous check was refused on the device (bad action,
+ * index or importance weight, or a row of another layout).  refused (nullable) receives their number; the count restarts at 0. */
 int uavtrack_learner_check(uavtrack_learner *learner, int64_t *refused, void *stream);
 
 /* ---- the PMI trainer: PMINetwork.train_pmi + its Adam steps on the device ----
@@ -712,6 +746,18 @@ int uavtrack_replay_add_rollout_episodes(uavtrack_replay *replay, const uavtrack
  * and NaN weights, and the next uavtrack_replay_check reports it. */
 int uavtrack_replay_sample(uavtrack_replay *replay, const uavtrack_replay_ring *ring, int64_t n, double alpha,
                            double beta, int64_t *indices, float *weights, void *stream);
+
+/* uavtrack_replay_sample with beta read off a linear schedule on the device, so that a captured draw anneals when its
+ * graph is replayed.  Call number c is the device call counter uavtrack_replay_sample uses and advances (both calls
+ * share it), read before it advances; call c uses
+ *   beta_c = beta0 + (beta1 - beta0) * min(1, c / anneal_calls)
+ * formed in fp64 on the device, each operation rounded on its own (no fused multiply-add), so the same expression in
+ * host doubles gives the same beta_c and uavtrack_replay_sample at beta_c the same bits.  anneal_calls >= 1; beta0 and
+ * beta1 finite and >= 0.  Everything else -- the draw stream, the refusals, the errors, capturability -- is
+ * uavtrack_replay_sample's contract. */
+int uavtrack_replay_sample_annealed(uavtrack_replay *replay, const uavtrack_replay_ring *ring, int64_t n, double alpha,
+                                    double beta0, double beta1, int64_t anneal_calls, int64_t *indices, float *weights,
+                                    void *stream);
 
 /* Synchronises `stream`; fails if any sample call since the previous check was refused on the device (bad or all-zero
  * priorities).  refused (nullable) receives their number; the count restarts at 0. */

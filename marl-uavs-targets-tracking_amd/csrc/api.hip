@@ -1450,12 +1450,13 @@ int accept_batch(const char *fn, const uavtrack_learner *l, int64_t n, int64_t c
     return 0;
 }
 
-// the fields uavtrack_learner_update and _grad fill alike; the others are null
+// the fields uavtrack_learner_update and _grad (and their weighted forms) fill alike; the others are null
 LearnerLaunch learner_batch(int64_t n, const float *states, const int32_t *actions, const float *rewards,
-                            const float *next_states, int64_t capacity, const int64_t *indices, float *td_delta)
+                            const float *next_states, int64_t capacity, const int64_t *indices, const float *weights,
+                            float *td_delta)
 {
     LearnerLaunch q = {};
-    q.n = n; q.capacity = capacity; q.td_delta = td_delta;
+    q.n = n; q.capacity = capacity; q.td_delta = td_delta; q.weights = weights;
     q.states = states; q.rewards = rewards; q.next_states = next_states; q.actions = actions; q.idx = indices;
     return q;
 }
@@ -1619,20 +1620,63 @@ int uavtrack_learner_get_optimizer_state(uavtrack_learner *learner, float *exp_a
     return optimizer_state(__func__, learner, exp_avg, exp_avg_sq, step, n_floats, stream, "the networks have %d");
 }
 
+}  // extern "C"
+
+namespace {
+
+// uavtrack_learner_update and _update_weighted (`fn`: the caller's name; weights nullable)
+int learner_update(const char *fn, uavtrack_learner *learner, int64_t n, const float *states, const int32_t *actions,
+                   const float *rewards, const float *next_states, int64_t capacity, const int64_t *indices,
+                   const float *weights, float *actor_loss, float *critic_loss, float *td_delta, float *priorities,
+                   void *stream)
+{
+    if (!learner) return fail("%s: null handle", fn);
+    if (!states || !actions || !rewards || !next_states)
+        return fail("%s: states, actions, rewards and next_states must not be null", fn);
+    if (!actor_loss || !critic_loss) return fail("%s: actor_loss and critic_loss must not be null", fn);
+    if (accept_batch(fn, learner, n, capacity, indices, "from")) return 1;
+    ON_DEVICE(learner->cfg.device_id);
+    LearnerLaunch q = learner_batch(n, states, actions, rewards, next_states, capacity, indices, weights, td_delta);
+    q.actor_loss = actor_loss; q.critic_loss = critic_loss; q.priorities = priorities;
+    HIP_TRY(launch_learner_update(learner->d, q, static_cast<hipStream_t>(stream)));
+    return 0;
+}
+
+// uavtrack_learner_grad and _grad_weighted
+int learner_grad(const char *fn, uavtrack_learner *learner, int64_t n, const float *states, const int32_t *actions,
+                 const float *rewards, const float *next_states, int64_t capacity, const int64_t *indices,
+                 const float *weights, float *td_delta, float *row, void *stream)
+{
+    if (!learner) return fail("%s: null handle", fn);
+    if (!states || !actions || !rewards || !next_states)
+        return fail("%s: states, actions, rewards and next_states must not be null", fn);
+    if (!td_delta || !row) return fail("%s: td_delta and row must not be null", fn);
+    if (accept_batch(fn, learner, n, capacity, indices, "from")) return 1;
+    ON_DEVICE(learner->cfg.device_id);
+    const LearnerLaunch q = learner_batch(n, states, actions, rewards, next_states, capacity, indices, weights, td_delta);
+    HIP_TRY(launch_learner_grad(learner->d, q, row, static_cast<hipStream_t>(stream)));
+    return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
 int uavtrack_learner_update(uavtrack_learner *learner, int64_t n, const float *states, const int32_t *actions,
                             const float *rewards, const float *next_states, int64_t capacity, const int64_t *indices,
                             float *actor_loss, float *critic_loss, float *td_delta, float *priorities, void *stream)
 {
-    if (!learner) return fail("uavtrack_learner_update: null handle");
-    if (!states || !actions || !rewards || !next_states)
-        return fail("uavtrack_learner_update: states, actions, rewards and next_states must not be null");
-    if (!actor_loss || !critic_loss) return fail("uavtrack_learner_update: actor_loss and critic_loss must not be null");
-    if (accept_batch(__func__, learner, n, capacity, indices, "from")) return 1;
-    ON_DEVICE(learner->cfg.device_id);
-    LearnerLaunch q = learner_batch(n, states, actions, rewards, next_states, capacity, indices, td_delta);
-    q.actor_loss = actor_loss; q.critic_loss = critic_loss; q.priorities = priorities;
-    HIP_TRY(launch_learner_update(learner->d, q, static_cast<hipStream_t>(stream)));
-    return 0;
+    return learner_update(__func__, learner, n, states, actions, rewards, next_states, capacity, indices, nullptr,
+                          actor_loss, critic_loss, td_delta, priorities, stream);
+}
+
+int uavtrack_learner_update_weighted(uavtrack_learner *learner, int64_t n, const float *states, const int32_t *actions,
+                                     const float *rewards, const float *next_states, int64_t capacity,
+                                     const int64_t *indices, const float *weights, float *actor_loss, float *critic_loss,
+                                     float *td_delta, float *priorities, void *stream)
+{
+    return learner_update(__func__, learner, n, states, actions, rewards, next_states, capacity, indices, weights,
+                          actor_loss, critic_loss, td_delta, priorities, stream);
 }
 
 int uavtrack_learner_row_floats(uavtrack_learner *learner, int64_t *out)
@@ -1646,15 +1690,16 @@ int uavtrack_learner_grad(uavtrack_learner *learner, int64_t n, const float *sta
                           const float *rewards, const float *next_states, int64_t capacity, const int64_t *indices,
                           float *td_delta, float *row, void *stream)
 {
-    if (!learner) return fail("uavtrack_learner_grad: null handle");
-    if (!states || !actions || !rewards || !next_states)
-        return fail("uavtrack_learner_grad: states, actions, rewards and next_states must not be null");
-    if (!td_delta || !row) return fail("uavtrack_learner_grad: td_delta and row must not be null");
-    if (accept_batch(__func__, learner, n, capacity, indices, "from")) return 1;
-    ON_DEVICE(learner->cfg.device_id);
-    const LearnerLaunch q = learner_batch(n, states, actions, rewards, next_states, capacity, indices, td_delta);
-    HIP_TRY(launch_learner_grad(learner->d, q, row, static_cast<hipStream_t>(stream)));
-    return 0;
+    return learner_grad(__func__, learner, n, states, actions, rewards, next_states, capacity, indices, nullptr,
+                        td_delta, row, stream);
+}
+
+int uavtrack_learner_grad_weighted(uavtrack_learner *learner, int64_t n, const float *states, const int32_t *actions,
+                                   const float *rewards, const float *next_states, int64_t capacity,
+                                   const int64_t *indices, const float *weights, float *td_delta, float *row, void *stream)
+{
+    return learner_grad(__func__, learner, n, states, actions, rewards, next_states, capacity, indices, weights,
+                        td_delta, row, stream);
 }
 
 int uavtrack_learner_apply(uavtrack_learner *learner, const float *rows, int64_t count, float *actor_loss,
@@ -1687,9 +1732,9 @@ int uavtrack_learner_check(uavtrack_learner *learner, int64_t *refused, void *st
     int count = 0;
     if (take_refusals(__func__, learner, refused, stream, &count)) return 1;
     if (count)
-        return fail("uavtrack_learner_check: %d update(s) refused: an action outside [0, %d) or an index outside "
-                    "[0, capacity), or (uavtrack_learner_apply) a gradient row of another layout; they changed nothing",
-                    count, learner->d.L.A);
+        return fail("uavtrack_learner_check: %d update(s) refused: an action outside [0, %d), an index outside "
+                    "[0, capacity) or an importance weight that is NaN, infinite or negative, or (uavtrack_learner_apply) "
+                    "a gradient row of another layout; they changed nothing", count, learner->d.L.A);
     return 0;
 }
 
@@ -1933,23 +1978,48 @@ int uavtrack_replay_add_rollout_episodes(uavtrack_replay *replay, const uavtrack
     return 0;
 }
 
+}  // extern "C"
+
+namespace {
+
+// uavtrack_replay_sample (anneal_calls == 0: beta0 is the call's beta) and _sample_annealed (anneal_calls >= 1)
+int replay_sample(const char *fn, uavtrack_replay *replay, const uavtrack_replay_ring *ring, int64_t n, double alpha,
+                  double beta0, double beta1, int64_t anneal_calls, int64_t *indices, float *weights, void *stream)
+{
+    if (!replay) return fail("%s: null handle", fn);
+    if (accept_ring(replay, fn, ring, false)) return 1;
+    if (!indices) return fail("%s: indices must not be null", fn);
+    if (n < 1 || n > replay->cfg.max_batch)
+        return fail("%s: n = %lld outside [1, max_batch = %lld]", fn, (long long)n, (long long)replay->cfg.max_batch);
+    if (ring->count < 1) return fail("%s: the ring is empty (count = 0)", fn);
+    if (!std::isfinite(alpha) || !(alpha > 0) || (float)alpha <= 0.0f)
+        return fail("%s: alpha = %g must be finite and > 0", fn, alpha);
+    const char *first = anneal_calls ? "beta0" : "beta";
+    if (!std::isfinite(beta0) || !(beta0 >= 0)) return fail("%s: %s = %g must be finite and >= 0", fn, first, beta0);
+    if (!std::isfinite(beta1) || !(beta1 >= 0)) return fail("%s: beta1 = %g must be finite and >= 0", fn, beta1);
+    ON_DEVICE(replay->cfg.device_id);
+    HIP_TRY(launch_replay_sample(replay->d, ring->priorities, ring->count, n, (float)alpha, beta0, beta1, anneal_calls,
+                                 indices, weights, static_cast<hipStream_t>(stream)));
+    return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
 int uavtrack_replay_sample(uavtrack_replay *replay, const uavtrack_replay_ring *ring, int64_t n, double alpha,
                            double beta, int64_t *indices, float *weights, void *stream)
 {
-    if (!replay) return fail("uavtrack_replay_sample: null handle");
-    if (accept_ring(replay, "uavtrack_replay_sample", ring, false)) return 1;
-    if (!indices) return fail("uavtrack_replay_sample: indices must not be null");
-    if (n < 1 || n > replay->cfg.max_batch)
-        return fail("uavtrack_replay_sample: n = %lld outside [1, max_batch = %lld]", (long long)n,
-                    (long long)replay->cfg.max_batch);
-    if (ring->count < 1) return fail("uavtrack_replay_sample: the ring is empty (count = 0)");
-    if (!std::isfinite(alpha) || !(alpha > 0) || (float)alpha <= 0.0f)
-        return fail("uavtrack_replay_sample: alpha = %g must be finite and > 0", alpha);
-    if (!std::isfinite(beta) || !(beta >= 0)) return fail("uavtrack_replay_sample: beta = %g must be finite and >= 0", beta);
-    ON_DEVICE(replay->cfg.device_id);
-    HIP_TRY(launch_replay_sample(replay->d, ring->priorities, ring->count, n, (float)alpha, beta, indices, weights,
-                                 static_cast<hipStream_t>(stream)));
-    return 0;
+    return replay_sample(__func__, replay, ring, n, alpha, beta, beta, 0, indices, weights, stream);
+}
+
+int uavtrack_replay_sample_annealed(uavtrack_replay *replay, const uavtrack_replay_ring *ring, int64_t n, double alpha,
+                                    double beta0, double beta1, int64_t anneal_calls, int64_t *indices, float *weights,
+                                    void *stream)
+{
+    if (!replay) return fail("uavtrack_replay_sample_annealed: null handle");
+    if (anneal_calls < 1) return fail("uavtrack_replay_sample_annealed: anneal_calls = %lld < 1", (long long)anneal_calls);
+    return replay_sample(__func__, replay, ring, n, alpha, beta0, beta1, anneal_calls, indices, weights, stream);
 }
 
 int uavtrack_replay_check(uavtrack_replay *replay, int64_t *refused, void *stream)

@@ -341,6 +341,7 @@ struct LearnerLaunch {
     const float *states, *rewards, *next_states;
     const int32_t *actions;
     const int64_t *idx;
+    const float *weights;           // nullable [n]: importance weights in batch order
     float *actor_loss, *critic_loss, *td_delta, *priorities;
 };
 int learner_rows_per_tile(int hidden);
@@ -437,8 +438,11 @@ struct ReplayRingView {
     int32_t *actions;
     int64_t capacity, pos, count;
 };
+// beta of call c (the device counter before it advances): beta0 when anneal_calls == 0, else
+// beta0 + (beta1 - beta0) * min(1, c / anneal_calls), formed in fp64 on the device
 hipError_t launch_replay_sample(const ReplayDevice &d, const float *priorities, int64_t count, int64_t k, float alpha,
-                                double beta, int64_t *indices, float *weights, hipStream_t stream);
+                                double beta0, double beta1, int64_t anneal_calls, int64_t *indices, float *weights,
+                                hipStream_t stream);
 // n transitions: flat (obs_in == nullptr: states / next_states [n][12], actions / rewards [n]) or one rollout
 // (obs_in [agents][12], obs [n / agents][agents][12], actions / rewards [n / agents][agents]); only the last
 // min(n, capacity) land in the ring, from ring.pos on

@@ -19,6 +19,13 @@
 // actor_loss = mean_i(-log p_i) * mean_j(delta_j), dL/dz_i = -mean(delta) (onehot(a_i) - p_i) / n, so the grad kernel
 // accumulates (onehot - p) and the Adam kernel multiplies by -mean(delta) / n once.  Per-sample: delta_i (onehot - p)
 // is accumulated and scaled by -1 / n.  The critic accumulates (V - target) and is scaled by 2 / n.
+//
+// Importance weights (uavtrack_learner_update_weighted / _grad_weighted): row i carries w_i >= 0 and the losses become
+// critic mean_i(w_i (V - y)^2), per-sample actor mean_i(-w_i log p_i delta_i), reference actor
+// mean_i(-w_i log p_i) * mean_j(w_j delta_j) -- the pair (i, j) of the broadcast loss weighted by w_i w_j.  Every sum
+// above takes its row's w_i as one more factor (the logit weight, the value weight, the four loss terms) and nothing
+// after the sums changes: the means still divide by n, and -(sum w delta / N) / N falls out of the same words.  No
+// weights is the factor 1.0f, an exact multiply, so the unweighted update keeps its bits.
 
 #include "internal.h"
 
@@ -38,10 +45,11 @@ struct GradArgs {
     const float *states, *rewards, *next_states;
     const int32_t *actions;
     const int64_t *idx;             // nullable: rows 0..n-1
+    const float *weights;           // nullable [n], batch order: importance weights (null: every row 1.0f)
     int64_t n, capacity;
     float *partials;                // [groups][P + 4]
     float *td_delta;                // nullable [n]
-    int *status;                    // bit 0: action out of range, bit 1: index out of range
+    int *status;                    // bit 0: action out of range, bit 1: index out of range, bit 2: weight NaN, inf or < 0
     LearnerLayout L;
     int rows;                       // R rows per tile
     float gamma;
@@ -64,6 +72,7 @@ __global__ void __launch_bounds__(kLW) learner_grad_kernel(GradArgs a)
     float *vn  = gv + R;                    // [R]     V'
     float *lt  = vn + R;                    // [R][4]  per-row loss terms
     int *act   = reinterpret_cast<int *>(lt + R * 4);   // [R] action, -1 = row not used
+    float *wt  = reinterpret_cast<float *>(act + R);    // [R] importance weight of the row
 
     const int tid = threadIdx.x;
     const float *W1a = a.params + L.a_w1, *b1a = a.params + L.a_b1, *W2a = a.params + L.a_w2, *b2a = a.params + L.a_b2;
@@ -75,10 +84,11 @@ __global__ void __launch_bounds__(kLW) learner_grad_kernel(GradArgs a)
     const int64_t tiles = (a.n + R - 1) / R;
     for (int64_t t = blockIdx.x; t < tiles; t += gridDim.x) {
         const int64_t row0 = t * R;
-        // ---- gather the tile: states, next states, action, reward
+        // ---- gather the tile: states, next states, action, reward, importance weight
         for (int r = tid; r < R; r += kLW) {
             const int64_t i = row0 + r;
             int av = -1;
+            float wi = 1.0f;
             if (i < a.n) {
                 const int64_t src = a.idx ? a.idx[i] : i;
                 if (src < 0 || src >= a.capacity) {
@@ -87,6 +97,10 @@ __global__ void __launch_bounds__(kLW) learner_grad_kernel(GradArgs a)
                     av = a.actions[src];
                     if (av < 0 || av >= A) { atomicOr(a.status, 1); av = -1; }
                     vn[r] = a.rewards[src];               // the reward waits in vn until V' overwrites it
+                }
+                if (a.weights) {
+                    wi = a.weights[i];
+                    if (!(wi >= 0.0f) || isinf(wi)) { atomicOr(a.status, 4); av = -1; }
                 }
                 for (int k = 0; k < 12; ++k) {
                     s[r * 12 + k]  = av >= 0 ? a.states[src * 12 + k] : 0.0f;
@@ -97,6 +111,7 @@ __global__ void __launch_bounds__(kLW) learner_grad_kernel(GradArgs a)
             }
             if (av < 0) vn[r] = 0.0f;
             act[r] = av;
+            wt[r] = wi;
         }
         __syncthreads();
         // ---- layer 1 of the three forwards
@@ -148,13 +163,14 @@ __global__ void __launch_bounds__(kLW) learner_grad_kernel(GradArgs a)
             const float v = gv[r];
             const float delta = target - v;
             const float nlp = -logf(z[av] * inv);
-            const float w = a.per_sample ? delta : 1.0f;
+            const float wi = wt[r];
+            const float w = (a.per_sample ? delta : 1.0f) * wi;
             for (int o = 0; o < A; ++o) z[o] = w * ((o == av ? 1.0f : 0.0f) - z[o] * inv);
-            gv[r] = v - target;
-            lt[r * 4 + 0] = nlp;
-            lt[r * 4 + 1] = delta;
-            lt[r * 4 + 2] = nlp * delta;
-            lt[r * 4 + 3] = (v - target) * (v - target);
+            gv[r] = (v - target) * wi;
+            lt[r * 4 + 0] = nlp * wi;
+            lt[r * 4 + 1] = delta * wi;
+            lt[r * 4 + 2] = (nlp * delta) * wi;
+            lt[r * 4 + 3] = ((v - target) * (v - target)) * wi;
             if (a.td_delta) a.td_delta[row0 + r] = delta;
         }
         __syncthreads();
@@ -251,8 +267,8 @@ __global__ void learner_finalize_kernel(const float *src, int count, size_t stri
         if (n_given) continue;                                      // a workgroup partial ends here
         const int32_t *tail = reinterpret_cast<const int32_t *>(row) + P + 4;
         const int64_t nr = (int64_t)((uint64_t)(uint32_t)tail[0] | ((uint64_t)(uint32_t)tail[1] << 32));
-        bad |= tail[2] & 3;
-        if (tail[3] != P || nr < 1) bad |= 4;                       // a row of another layout (or not a row at all)
+        bad |= tail[2] & 7;
+        if (tail[3] != P || nr < 1) bad |= 8;                       // a row of another layout (or not a row at all)
         else N += nr;
     }
     if (n_given) bad = *status;
@@ -350,7 +366,7 @@ int learner_rows_per_tile(int hidden)
 
 size_t learner_lds_bytes(const LearnerLayout &L, int rows)
 {
-    return sizeof(float) * ((size_t)L.P + (size_t)rows * (24 + 3 * L.H + L.A + 2 + 4)) + sizeof(int) * (size_t)rows;
+    return sizeof(float) * ((size_t)L.P + (size_t)rows * (24 + 3 * L.H + L.A + 2 + 4 + 1)) + sizeof(int) * (size_t)rows;
 }
 
 int learner_groups(const LearnerLayout &L, int64_t n)
@@ -379,7 +395,7 @@ hipError_t launch_grad(const LearnerDevice &d, const LearnerLaunch &q, float *td
 
     GradArgs a;
     a.params = d.params; a.states = q.states; a.rewards = q.rewards; a.next_states = q.next_states;
-    a.actions = q.actions; a.idx = q.idx; a.n = q.n; a.capacity = q.capacity;
+    a.actions = q.actions; a.idx = q.idx; a.weights = q.weights; a.n = q.n; a.capacity = q.capacity;
     a.partials = d.partials; a.td_delta = td; a.status = status;
     a.L = L; a.rows = R; a.gamma = d.gamma; a.per_sample = d.per_sample;
     hipLaunchKernelGGL(learner_grad_kernel, dim3(learner_groups(L, q.n)), dim3(kLW), learner_lds_bytes(L, R), st, a);

@@ -15,7 +15,8 @@
 //                           running sum exceeds x: searchsorted(cdf, x, side='right'), as np.random.choice;
 //   replay_min_kernel,      (only when weights are asked for) (count * P(i))^-beta / max over the batch, the maximum
 //   replay_weight_kernel    taken from the smallest P(i) of the batch (a workgroup reduction, then one order-independent
-//                           atomic min per workgroup).
+//                           atomic min per workgroup).  beta is the caller's, or (uavtrack_replay_sample_annealed) read
+//                           off a linear schedule at this call's number, so a replayed graph anneals.
 // The sums are fp64 in a fixed order, but not one order: the scans associate a prefix differently from its predecessor,
 // so where the rescan and the coarse prefix disagree in the last bit, or a lane or tile holding no w > 0 gets a prefix
 // an ulp above its predecessor's and x falls in between, the rule is: the draw takes the last slot with w > 0 at or
@@ -266,12 +267,24 @@ __global__ void __launch_bounds__(kSW) replay_min_kernel(const double *pdraw, in
     }
 }
 
-__global__ void replay_weight_kernel(const double *pdraw, int64_t k, int64_t count, double beta,
-                                     const unsigned long long *pmin, const int *status, float *weights)
+// beta of call number c: beta0 + (beta1 - beta0) * min(1, c / anneal_calls), every operation rounded on its own (no
+// fused multiply-add), so the host forms the same double from the same expression
+__device__ __forceinline__ double annealed_beta(double beta0, double beta1, int64_t anneal_calls, uint64_t c)
+{
+#pragma clang fp contract(off)
+    const double frac = fmin(1.0, (double)c / (double)anneal_calls);
+    const double step = (beta1 - beta0) * frac;
+    return beta0 + step;
+}
+
+__global__ void replay_weight_kernel(const double *pdraw, int64_t k, int64_t count, double beta0, double beta1,
+                                     int64_t anneal_calls, const uint64_t *counter, const unsigned long long *pmin,
+                                     const int *status, float *weights)
 {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= k) return;
     if (*status) { weights[i] = NAN; return; }
+    const double beta = anneal_calls > 0 ? annealed_beta(beta0, beta1, anneal_calls, counter[1]) : beta0;
     const double n = (double)count;
     const double wmax = pow(n * __longlong_as_double((long long)*pmin), -beta);
     weights[i] = (float)(pow(n * pdraw[i], -beta) / wmax);
@@ -359,7 +372,8 @@ __global__ void __launch_bounds__(kSW) replay_write_kernel(AddArgs a)
 }  // namespace
 
 hipError_t launch_replay_sample(const ReplayDevice &d, const float *priorities, int64_t count, int64_t k, float alpha,
-                                double beta, int64_t *indices, float *weights, hipStream_t st)
+                                double beta0, double beta1, int64_t anneal_calls, int64_t *indices, float *weights,
+                                hipStream_t st)
 {
     const int ntiles = (int)((count + kReplayTile - 1) / kReplayTile);
     hipLaunchKernelGGL(replay_begin_kernel, dim3(1), dim3(64), 0, st, d.counter, d.status, d.pmin);
@@ -383,7 +397,7 @@ hipError_t launch_replay_sample(const ReplayDevice &d, const float *priorities, 
         hipLaunchKernelGGL(replay_min_kernel, dim3((unsigned)mg), dim3(kSW), 0, st, d.pdraw, k, d.pmin);
         if ((e = hipGetLastError()) != hipSuccess) return e;
         hipLaunchKernelGGL(replay_weight_kernel, dim3((unsigned)((k + 255) / 256)), dim3(256), 0, st, d.pdraw, k, count,
-                           beta, d.pmin, d.status, weights);
+                           beta0, beta1, anneal_calls, d.counter, d.pmin, d.status, weights);
         if ((e = hipGetLastError()) != hipSuccess) return e;
     }
     return hipSuccess;

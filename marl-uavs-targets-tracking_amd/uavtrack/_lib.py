@@ -162,8 +162,12 @@ SIGNATURES = {
     "uavtrack_learner_set_optimizer_state": (C.c_int, [C.c_void_p] + [C.c_void_p] * 3 + [C.c_int64, C.c_void_p]),
     "uavtrack_learner_get_optimizer_state": (C.c_int, [C.c_void_p] + [C.c_void_p] * 3 + [C.c_int64, C.c_void_p]),
     "uavtrack_learner_update": (C.c_int, [C.c_void_p, C.c_int64] + [C.c_void_p] * 4 + [C.c_int64] + [C.c_void_p] * 6),
+    "uavtrack_learner_update_weighted": (C.c_int, [C.c_void_p, C.c_int64] + [C.c_void_p] * 4 + [C.c_int64]
+                                         + [C.c_void_p] * 7),
     "uavtrack_learner_row_floats": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]),
     "uavtrack_learner_grad": (C.c_int, [C.c_void_p, C.c_int64] + [C.c_void_p] * 4 + [C.c_int64] + [C.c_void_p] * 4),
+    "uavtrack_learner_grad_weighted": (C.c_int, [C.c_void_p, C.c_int64] + [C.c_void_p] * 4 + [C.c_int64]
+                                       + [C.c_void_p] * 5),
     "uavtrack_learner_apply": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
     "uavtrack_learner_write_priorities": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64] + [C.c_void_p] * 3),
     "uavtrack_learner_check": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64), C.c_void_p]),
@@ -187,6 +191,8 @@ SIGNATURES = {
                                              + [C.c_void_p] * 7),
     "uavtrack_replay_sample": (C.c_int, [C.c_void_p, C.POINTER(ReplayRing), C.c_int64, C.c_double, C.c_double,
                                          C.c_void_p, C.c_void_p, C.c_void_p]),
+    "uavtrack_replay_sample_annealed": (C.c_int, [C.c_void_p, C.POINTER(ReplayRing), C.c_int64, C.c_double, C.c_double,
+                                                  C.c_double, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
     "uavtrack_replay_check": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64), C.c_void_p]),
     "uavtrack_episode_stats_create": (C.c_int, [C.POINTER(EpisodeStatsConfig), C.POINTER(C.c_void_p)]),
     "uavtrack_episode_stats_destroy": (C.c_int, [C.c_void_p]),

@@ -11,6 +11,17 @@ The same update also comes in pieces (uavtrack_learner_grad / _apply / _write_pr
 unscaled sums in a device gradient row, apply adds rows in row order, scales once and steps Adam.  update_from_many
 (several rings, one GPU) and update_from(..., group=...) (one ring per rank) are built on them; every participant that
 applies the same rows in the same order ends with the same bits, and one row is bit for bit `update`.
+
+Importance weights (update(weights=...), update_from(importance=True) and the same on grad_from, update_from_many and
+the group path) put a prioritised draw's importance-sampling weights w_i >= 0, one per batch row in batch order, into
+the losses:
+    critic_loss                = mean_i(w_i (V(s_i) - y_i)^2)
+    actor_loss, "per_sample"   = mean_i(-w_i log p_i delta_i)
+    actor_loss, "reference"    = mean_i(-w_i log p_i) * mean_j(w_j delta_j)    (the pair (i, j) of the broadcast weighs w_i w_j)
+Means divide by n, not by sum w; td_delta and the priorities written back stay the unweighted delta and |delta|.  With
+several rings or ranks in one update, each row's weights are normalised by that draw's own maximum, as K independent
+sample() calls would do.  Without them (the default) every call is bit for bit what it was: the reference's update does
+not use the weights its sample() returns.
 """
 from __future__ import annotations
 
@@ -103,7 +114,8 @@ class DeviceActorCritic(Handle):
 
     def check(self) -> None:
         """Synchronises; raises if an update since the last check was refused on the device (an action outside
-        [0, action_dim) or an index outside the ring), which then changed nothing."""
+        [0, action_dim), an index outside the ring, or an importance weight that is NaN, infinite or negative -- what a
+        refused ring draw hands out), which then changed nothing."""
         self._check()
 
     # ---- the update
@@ -112,29 +124,58 @@ class DeviceActorCritic(Handle):
         """A batch as uavtrack_learner_update and _grad take it: the store's four arrays, its capacity, the indices."""
         return (*(_ptr(store[k]) for k in ("states", "actions", "rewards", "next_states")), capacity, _ptr(idx))
 
-    def _draw_from(self, buffer, k: int, generator: Optional[torch.Generator]):
-        """(indices, priorities or None) of one batch of k rows, drawn as the buffer's own sample() draws them."""
+    def _draw_from(self, buffer, k: int, generator: Optional[torch.Generator], importance: bool = False,
+                   beta: float = 0.4, beta_final: Optional[float] = None, anneal_calls: int = 0):
+        """(indices, priorities or None, importance weights or None) of one batch of k rows, drawn as the buffer's own
+        sample() draws them.  Weights only with `importance` and a prioritised buffer, normalised by this draw's maximum."""
         if isinstance(buffer, PrioritizedReplayRing):
-            return buffer._draw_into(k), buffer.priorities
+            if importance:
+                idx, w = buffer._draw_into(k, True, beta, beta_final, anneal_calls)
+                return idx, buffer.priorities, w
+            return buffer._draw_into(k), buffer.priorities, None
         if isinstance(buffer, PrioritizedDeviceReplayBuffer):
             prob = buffer.priorities[:buffer.count] ** buffer.alpha
             prob = prob / prob.sum()
-            return torch.multinomial(prob, k, replacement=True, generator=generator), buffer.priorities
-        return torch.randperm(buffer.count, device=buffer.device, generator=generator)[:k], None
+            idx = torch.multinomial(prob, k, replacement=True, generator=generator)
+            if not importance:
+                return idx, buffer.priorities, None
+            if beta_final is not None:
+                raise ValueError("beta_final anneals over a PrioritizedReplayRing's device call counter; a "
+                                 "PrioritizedDeviceReplayBuffer has none: pass this call's beta")
+            w = (buffer.count * prob[idx]) ** (-beta)                 # as its own sample() forms them
+            return idx, buffer.priorities, (w / w.max()).to(torch.float32).contiguous()
+        return torch.randperm(buffer.count, device=buffer.device, generator=generator)[:k], None, None
+
+    def _weights_arg(self, weights: Optional[torch.Tensor], n: int):
+        if weights is None:
+            return None
+        if weights.numel() != n or weights.dtype != torch.float32 or not weights.is_contiguous() \
+                or weights.device != self.device:
+            raise ValueError(f"weights must be a contiguous float32 tensor of {n} elements (one per batch row, in batch "
+                             f"order) on {self.device}")
+        return weights
 
     def _run(self, n: int, store: Dict[str, torch.Tensor], capacity: int, idx: Optional[torch.Tensor],
-             priorities: Optional[torch.Tensor]):
+             priorities: Optional[torch.Tensor], weights: Optional[torch.Tensor] = None):
         dev = self.device
         losses = torch.empty(2, device=dev)
         td = torch.empty(n, device=dev)
-        _lib.check(self._lib.uavtrack_learner_update(
-            self._h, n, *self._batch_args(store, capacity, idx), _ptr(losses[0:1]), _ptr(losses[1:2]), _ptr(td),
-            _ptr(priorities), self._stream()), "uavtrack_learner_update")
+        if weights is None:
+            _lib.check(self._lib.uavtrack_learner_update(
+                self._h, n, *self._batch_args(store, capacity, idx), _ptr(losses[0:1]), _ptr(losses[1:2]), _ptr(td),
+                _ptr(priorities), self._stream()), "uavtrack_learner_update")
+        else:
+            _lib.check(self._lib.uavtrack_learner_update_weighted(
+                self._h, n, *self._batch_args(store, capacity, idx), _ptr(self._weights_arg(weights, n)),
+                _ptr(losses[0:1]), _ptr(losses[1:2]), _ptr(td), _ptr(priorities), self._stream()),
+                "uavtrack_learner_update_weighted")
         return losses[0], losses[1], td
 
-    def update(self, transition_dict: Dict[str, torch.Tensor]):
+    def update(self, transition_dict: Dict[str, torch.Tensor], weights: Optional[torch.Tensor] = None):
         """ActorCritic.update (actor_critic.py:150-179) on a batch {states [n,12], actions [n], rewards [n],
-        next_states [n,12]}: returns (actor_loss, critic_loss, td_delta) as device tensors, without synchronising."""
+        next_states [n,12]}: returns (actor_loss, critic_loss, td_delta) as device tensors, without synchronising.
+        weights [n] (optional): importance weights w_i >= 0, one per row (the module docstring has the weighted losses);
+        None is the reference's unweighted update, and a vector of ones gives its bits."""
         dev = self.device
         s = torch.as_tensor(transition_dict["states"], device=dev, dtype=torch.float32).reshape(-1, _lib.OBS_DIM).contiguous()
         n = s.shape[0]
@@ -143,29 +184,41 @@ class DeviceActorCritic(Handle):
                  "rewards": torch.as_tensor(transition_dict["rewards"], device=dev, dtype=torch.float32).reshape(n).contiguous(),
                  "next_states": torch.as_tensor(transition_dict["next_states"], device=dev,
                                                 dtype=torch.float32).reshape(n, _lib.OBS_DIM).contiguous()}
-        return self._run(n, store, n, None, None)
+        if weights is not None:
+            weights = torch.as_tensor(weights, device=dev, dtype=torch.float32).reshape(-1).contiguous()
+        return self._run(n, store, n, None, None, weights)
 
     def update_from(self, buffer, batch_size: int, beta: float = 0.4,
-                    generator: Optional[torch.Generator] = None, group=None):
+                    generator: Optional[torch.Generator] = None, group=None, importance: bool = False,
+                    beta_final: Optional[float] = None, anneal_calls: int = 0):
         """buffer.sample(batch_size) + update + (prioritised buffer) update_priorities(indices, |td_delta|)
         (train.py:253-262), the gather and the priority write inside the library call.  The indices are drawn as
-        the buffer's own sample() draws them.  beta only weights the importance weights, which the reference's
-        update does not use.  For a PrioritizedReplayRing the draw is one library call of its own (the ring's seed
-        and device call counter; `generator` does not apply), so the whole update is two library calls with no torch
-        kernel between them, and can be captured into a graph.
+        the buffer's own sample() draws them.  For a PrioritizedReplayRing the draw is one library call of its own
+        (the ring's seed and device call counter; `generator` does not apply), so the whole update is two library
+        calls with no torch kernel between them, and can be captured into a graph.
+
+        importance=False (the default) is the reference's update: it drops the importance weights its sample()
+        returns, and beta then has no effect.  importance=True trains on them (the weighted losses of the module
+        docstring): (count * P(i))^-beta / max over this draw, one per batch row.  A PrioritizedReplayRing writes them
+        beside its indices in the same library call (still two calls, still capturable); with beta_final, beta runs
+        linearly from beta to beta_final over the ring's first anneal_calls draws on the device, so a replayed graph
+        anneals.  A PrioritizedDeviceReplayBuffer forms them in torch as its sample() does (no beta_final).  A uniform
+        buffer has no weights: importance changes nothing there.  A refused ring draw hands out NaN weights, which
+        refuse this update on the device as well.
 
         With a torch.distributed `group`, every rank of it takes ONE common update from all ranks' batches: the
         gradient row of this rank's batch (grad_from), an all-gather of the rows in rank order
         (sharding.gather_learner_rows), the apply of all of them, and the priority write into this rank's buffer.
         Ranks that start equal (sharding.broadcast_learner) stay bitwise equal; batch sizes may differ between ranks.
-        The returned losses are the global ones, td_delta this rank's."""
+        The returned losses are the global ones, td_delta this rank's.  With importance=True every rank's weights are
+        normalised by its own draw's maximum, as independent sample() calls would do."""
         if group is not None:
-            return self._update_from_group(buffer, batch_size, generator, group)
+            return self._update_from_group(buffer, batch_size, generator, group, importance, beta, beta_final, anneal_calls)
         k = min(int(batch_size), buffer.count)
         if k < 1:
             raise ValueError("update_from: the buffer is empty")
-        idx, prio = self._draw_from(buffer, k, generator)
-        return self._run(k, buffer.store, buffer.capacity, idx, prio)
+        idx, prio, w = self._draw_from(buffer, k, generator, importance, beta, beta_final, anneal_calls)
+        return self._run(k, buffer.store, buffer.capacity, idx, prio, w)
 
     # ---- the split update: gradient rows and an ordered apply
     def new_rows(self, count: int) -> torch.Tensor:
@@ -173,7 +226,8 @@ class DeviceActorCritic(Handle):
         return torch.empty(int(count), self.row_floats, device=self.device)
 
     def _grad(self, n: int, store: Dict[str, torch.Tensor], capacity: int, idx: Optional[torch.Tensor],
-              row: Optional[torch.Tensor] = None, td: Optional[torch.Tensor] = None):
+              row: Optional[torch.Tensor] = None, td: Optional[torch.Tensor] = None,
+              weights: Optional[torch.Tensor] = None):
         if row is None:
             row = torch.empty(self.row_floats, device=self.device)
         elif row.numel() != self.row_floats or row.dtype != torch.float32 or not row.is_contiguous() \
@@ -181,23 +235,30 @@ class DeviceActorCritic(Handle):
             raise ValueError(f"row must be a contiguous float32 tensor of {self.row_floats} words on {self.device}")
         if td is None:
             td = torch.empty(n, device=self.device)
-        _lib.check(self._lib.uavtrack_learner_grad(
-            self._h, n, *self._batch_args(store, capacity, idx), _ptr(td), _ptr(row), self._stream()),
-            "uavtrack_learner_grad")
+        if weights is None:
+            _lib.check(self._lib.uavtrack_learner_grad(
+                self._h, n, *self._batch_args(store, capacity, idx), _ptr(td), _ptr(row), self._stream()),
+                "uavtrack_learner_grad")
+        else:
+            _lib.check(self._lib.uavtrack_learner_grad_weighted(
+                self._h, n, *self._batch_args(store, capacity, idx), _ptr(self._weights_arg(weights, n)), _ptr(td),
+                _ptr(row), self._stream()), "uavtrack_learner_grad_weighted")
         return row, td
 
     def grad_from(self, buffer, batch_size: int, row: Optional[torch.Tensor] = None,
-                  generator: Optional[torch.Generator] = None):
+                  generator: Optional[torch.Generator] = None, importance: bool = False, beta: float = 0.4,
+                  beta_final: Optional[float] = None, anneal_calls: int = 0):
         """The gradient half of update_from: draws min(batch_size, buffer.count) rows as update_from does (for a
         PrioritizedReplayRing the ring's own library call) and leaves their unscaled gradient and loss sums in `row`
         (a new tensor if None).  Returns (row, td_delta, indices); changes nothing in the learner.  The indices of a
         PrioritizedReplayRing live in the ring's own draw tensor until its next draw: call write_priorities (or clone
-        them) before drawing from the same ring again."""
+        them) before drawing from the same ring again.  importance, beta, beta_final, anneal_calls: as update_from; the
+        row's sums then carry this draw's weights, normalised by this draw's own maximum."""
         k = min(int(batch_size), buffer.count)
         if k < 1:
             raise ValueError("grad_from: the buffer is empty")
-        idx, _ = self._draw_from(buffer, k, generator)
-        row, td = self._grad(k, buffer.store, buffer.capacity, idx, row)
+        idx, _, w = self._draw_from(buffer, k, generator, importance, beta, beta_final, anneal_calls)
+        row, td = self._grad(k, buffer.store, buffer.capacity, idx, row, None, w)
         return row, td, idx
 
     def apply(self, rows):
@@ -226,23 +287,30 @@ class DeviceActorCritic(Handle):
                                                                _ptr(td), _ptr(prio), self._stream()),
                    "uavtrack_learner_write_priorities")
 
-    def update_from_many(self, buffers, batch_size: int, generator: Optional[torch.Generator] = None):
+    def update_from_many(self, buffers, batch_size: int, generator: Optional[torch.Generator] = None,
+                         importance: bool = False, beta: float = 0.4, beta_final: Optional[float] = None,
+                         anneal_calls: int = 0):
         """ONE update from several buffers on this device (the shards of one GPU): one gradient row per buffer from
         min(batch_size, its count) of its rows, the rows applied in list order, each prioritised buffer's priorities
-        written back from its own draw.  Returns (actor_loss, critic_loss, [td_delta per buffer])."""
+        written back from its own draw.  Returns (actor_loss, critic_loss, [td_delta per buffer]).  With
+        importance=True each buffer's row carries its own draw's importance weights, normalised by that draw's own
+        maximum (not a maximum across the buffers), as independent sample() calls would do; every ring anneals over
+        its own call counter."""
         buffers = list(buffers)
         if not 1 <= len(buffers) <= _lib.LEARNER_MAX_ROWS:
             raise ValueError(f"update_from_many: {len(buffers)} buffers, one apply takes 1 to {_lib.LEARNER_MAX_ROWS} rows")
         rows = self.new_rows(len(buffers))
-        drawn = [self.grad_from(b, batch_size, rows[k], generator) for k, b in enumerate(buffers)]
+        drawn = [self.grad_from(b, batch_size, rows[k], generator, importance, beta, beta_final, anneal_calls)
+                 for k, b in enumerate(buffers)]
         al, cl = self.apply(rows)
         for b, (_, td, idx) in zip(buffers, drawn):
             self.write_priorities(b, idx, td)
         return al, cl, [td for _, td, _ in drawn]
 
-    def _update_from_group(self, buffer, batch_size: int, generator, group):
+    def _update_from_group(self, buffer, batch_size: int, generator, group, importance: bool = False,
+                           beta: float = 0.4, beta_final: Optional[float] = None, anneal_calls: int = 0):
         from .sharding import gather_learner_rows
-        row, td, idx = self.grad_from(buffer, batch_size, None, generator)
+        row, td, idx = self.grad_from(buffer, batch_size, None, generator, importance, beta, beta_final, anneal_calls)
         al, cl = self.apply(gather_learner_rows(row, group))
         self.write_priorities(buffer, idx, td)
         return al, cl, td

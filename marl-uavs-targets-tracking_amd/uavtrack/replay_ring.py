@@ -7,7 +7,9 @@ Against PrioritizedDeviceReplayBuffer (uavtrack/replay.py, which stays the plain
     `capacity` transitions written), new transitions entering at the device-side maximum priority;
   - the draw has no 2^24-slot limit (torch.multinomial's), keeps its CDF in fp64 as np.random.choice does, and is
     keyed by (seed, device call counter), so every replay of a captured graph draws afresh.  The stream is documented
-    in include/uavtrack.h.
+    in include/uavtrack.h;
+  - beta can follow a linear schedule over that same call counter (draw(..., beta_final=, anneal_calls=):
+    uavtrack_replay_sample_annealed), formed on the device, so a replayed graph anneals too.
 """
 from __future__ import annotations
 
@@ -45,6 +47,7 @@ class PrioritizedReplayRing(Handle):
         self._create(_lib.ReplayConfig(device_id=self.device.index, max_capacity=self.capacity, max_batch=self.max_batch,
                                        seed=self.seed & (2**64 - 1)))
         self._idx = torch.empty(self.max_batch, dtype=torch.int64, device=self.device)   # update_from's draws
+        self._w = torch.empty(self.max_batch, dtype=torch.float32, device=self.device)   # and their importance weights
 
     def _ring(self) -> _lib.ReplayRing:
         s = self.store
@@ -121,34 +124,51 @@ class PrioritizedReplayRing(Handle):
         self._advance(T * M)
 
     # ---- sample (train.py:98-112)
-    def _draw(self, k: int, beta: float, idx: torch.Tensor, weights: Optional[torch.Tensor]) -> None:
+    def _draw(self, k: int, beta: float, idx: torch.Tensor, weights: Optional[torch.Tensor],
+              beta_final: Optional[float] = None, anneal_calls: int = 0) -> None:
         ring = self._ring()
-        _lib.check(self._lib.uavtrack_replay_sample(self._h, C.byref(ring), k, self.alpha, float(beta), _ptr(idx),
-                                                    _ptr(weights), self._stream()), "uavtrack_replay_sample")
+        if beta_final is None:
+            _lib.check(self._lib.uavtrack_replay_sample(self._h, C.byref(ring), k, self.alpha, float(beta), _ptr(idx),
+                                                        _ptr(weights), self._stream()), "uavtrack_replay_sample")
+            return
+        if int(anneal_calls) < 1:
+            raise ValueError(f"beta_final needs anneal_calls >= 1 (the draws the schedule runs over), got {anneal_calls}")
+        _lib.check(self._lib.uavtrack_replay_sample_annealed(
+            self._h, C.byref(ring), k, self.alpha, float(beta), float(beta_final), int(anneal_calls), _ptr(idx),
+            _ptr(weights), self._stream()), "uavtrack_replay_sample_annealed")
 
-    def _draw_into(self, k: int) -> torch.Tensor:
-        """k indices into the preallocated index tensor (no weights): what DeviceActorCritic.update_from uses."""
+    def _draw_into(self, k: int, importance: bool = False, beta: float = 0.0, beta_final: Optional[float] = None,
+                   anneal_calls: int = 0):
+        """k indices into the preallocated index tensor: what DeviceActorCritic.update_from uses.  Without `importance`
+        no weights are formed and the indices come back alone; with it, (indices, weights) in the preallocated pair."""
         idx = self._idx[:k]
-        self._draw(k, 0.0, idx, None)
-        return idx
+        if not importance:
+            self._draw(k, 0.0, idx, None)
+            return idx
+        w = self._w[:k]
+        self._draw(k, beta, idx, w, beta_final, anneal_calls)
+        return idx, w
 
-    def draw(self, batch_size: int, beta: float = 0.4) -> Tuple[Optional[torch.Tensor], Optional[torch.Tensor]]:
+    def draw(self, batch_size: int, beta: float = 0.4, beta_final: Optional[float] = None,
+             anneal_calls: int = 0) -> Tuple[Optional[torch.Tensor], Optional[torch.Tensor]]:
         """(indices int64 [k], importance weights fp32 [k]) with k = min(batch_size, count), drawn with replacement
-        from P(i) = p_i^alpha / sum_j p_j^alpha; (None, None) for an empty ring.  No synchronisation."""
+        from P(i) = p_i^alpha / sum_j p_j^alpha; (None, None) for an empty ring.  No synchronisation.  With beta_final,
+        draw number c of this ring (its device call counter, which every draw advances) uses
+        beta + (beta_final - beta) * min(1, c / anneal_calls), formed on the device."""
         if self.count == 0:
             return None, None
         k = min(int(batch_size), self.count)
         idx = torch.empty(k, dtype=torch.int64, device=self.device)
         w = torch.empty(k, dtype=torch.float32, device=self.device)
-        self._draw(k, beta, idx, w)
+        self._draw(k, beta, idx, w, beta_final, anneal_calls)
         return idx, w
 
-    def sample(self, batch_size: int, beta: float = 0.4):
+    def sample(self, batch_size: int, beta: float = 0.4, beta_final: Optional[float] = None, anneal_calls: int = 0):
         """PrioritizedReplayBuffer.sample: (transitions dict, indices int64, weights), or (empty dict, None, None)
-        for an empty ring."""
+        for an empty ring.  beta_final, anneal_calls: as draw."""
         if self.count == 0:
             return {k: self.store[k][:0] for k in KEYS}, None, None
-        idx, w = self.draw(batch_size, beta)
+        idx, w = self.draw(batch_size, beta, beta_final, anneal_calls)
         return {key: self.store[key][idx] for key in KEYS}, idx, w
 
     def update_priorities(self, batch_indices: torch.Tensor, batch_priorities: torch.Tensor) -> None:
