@@ -16,6 +16,7 @@ update is the same rule on a sampled batch, and the new actor weights are re-upl
     python examples/train_maac.py --replay prioritized --learner device --importance --beta-final 1.0     # train on the importance weights, beta annealed on the device
     python examples/train_maac.py --method maac-r --pmi-trainer device --learner device --replay prioritized --publish device --log-every 10
     python examples/train_maac.py --shards 8 --envs 32768 --n-uav 20 --learner device --replay prioritized --publish device   # 8 shard handles, one learner
+    python examples/train_maac.py --shards 4 --method maac-r --pmi-trainer device --learner device --replay prioritized --publish device   # ... and one PMI trainer
     python examples/train_maac.py --phase evaluate --envs 256 --eval-episodes 4 --save-dir out   # train.evaluate, batched; csv files
     python examples/train_maac.py --phase run --envs 256                                         # train.run, the C-METHOD baseline
 
@@ -129,18 +130,28 @@ def importance_kwargs(args):
 def train_sharded(args, timings=None):
     """--shards K: K environment handles over disjoint global environment ids, K rollouts, K prioritised rings, ONE
     device learner.  Every update takes one gradient row from each ring and applies them in shard order
-    (update_from_many), each ring gets its own priorities back, and the new actor is published to every handle."""
+    (update_from_many), each ring gets its own priorities back, and the new actor is published to every handle.
+    --method maac-r: ONE device PMI trainer too, trained after the K rollouts on triples drawn over the K observation
+    histories (train_pmi_many) and published to every handle's scorer."""
     dev = "cuda:0"
     K = args.shards
     torch.manual_seed(args.seed)
     coop = args.cooperative if args.cooperative is not None else (0.0 if args.method == "maac" else 0.3)
-    mode = {"maac": uavtrack.RewardMode.RAW, "maac-g": uavtrack.RewardMode.MEAN}[args.method]
+    mode = {"maac": uavtrack.RewardMode.RAW, "maac-g": uavtrack.RewardMode.MEAN, "maac-r": uavtrack.RewardMode.PMI}[args.method]
     envs = []
     for k in range(K):
         off, cnt = uavtrack.shard_range(args.envs, k, K)
         envs.append(uavtrack.BatchedUavEnv(uavtrack.EnvConfig(
             n_envs=cnt, n_uav=args.n_uav, m_targets=args.m_targets, cooperative=coop, reward_mode=mode,
             horizon=args.steps, env_offset=off), dev))
+    pmi_dev = pmi_gen = None
+    if args.method == "maac-r":                                       # ONE PMI trainer; every handle scores with its network
+        pmi_dev = uavtrack.DevicePMINetwork(args.pmi_hidden, args.pmi_b2, dev, max_batch=max(args.pmi_batch, 4096))
+        for e in envs:
+            e.set_pmi(pmi_dev)
+        if args.pmi_draw == "device" or (args.pmi_draw == "auto" and args.publish == "device"):
+            pmi_gen = torch.Generator(device=dev)
+            pmi_gen.manual_seed(args.seed)
     na_total = envs[0].cfg.na_total
     actor = uavtrack.ActorMLP(hidden_dim=args.hidden, action_dim=na_total).to(dev)
     per_shard = -(-args.batch // K)                                   # rows each ring contributes to one update
@@ -180,6 +191,17 @@ def train_sharded(args, timings=None):
         else:
             for e in envs:
                 learner.publish_actor(e)                              # one device pack per handle
+        pmi_field = ""
+        if pmi_dev is not None:                                       # train_pmi over the K histories, never concatenated
+            lp = pmi_dev.train_pmi_many({"pmi": {"batch_size": args.pmi_batch}}, [o["obs"] for o in outs], args.n_uav,
+                                        generator=pmi_gen, sync=False)
+            for e in envs:
+                if args.publish == "device":
+                    pmi_dev.publish_pmi(e)                            # no copy to the host, no synchronisation
+                else:
+                    e.set_pmi(pmi_dev)
+            if log:
+                pmi_field = f"pmi loss {float(lp):.4f}  "
         ep = torch.cat(eps)                                           # [envs, 5] in global environment order
         history.append(ep[:, 0].mean())
         if not log:
@@ -191,13 +213,15 @@ def train_sharded(args, timings=None):
         n_iter = it + 1 - (stamps[-1][0] if stamps else 0)
         stamps.append((it + 1, now))
         print(f"iter {it:3d}  shards {K}  episode return {ret:8.3f}  covered targets/step {cov:5.2f}  actor loss {la:+.4f}  "
-              f"critic loss {lc:.4f}  rollout {t_roll * 1e3:6.1f} ms ({per_iter / t_roll / 1e9:.2f} G agent-steps/s)  "
+              f"critic loss {lc:.4f}  {pmi_field}rollout {t_roll * 1e3:6.1f} ms ({per_iter / t_roll / 1e9:.2f} G agent-steps/s)  "
               f"iteration {((now - t0) if args.log_every == 1 else (now - t_log) / n_iter) * 1e3:6.1f} ms  {six}", flush=True)
         t_log = now
     save_results(args, kept)
     for ring in rings:
         ring.check()                                                  # no draw was refused on the device
     learner.check()                                                   # no update was refused on the device
+    if pmi_dev is not None:
+        pmi_dev.check()                                               # no train_pmi call was refused on the device
     for e in envs:
         e.close()
     history = [float(r) for r in history]
@@ -261,7 +285,9 @@ def main(argv=None, timings=None):
                     help="split --envs into K environment handles (uavtrack.shard_range: disjoint global environment "
                          "ids), each with its own rollout and prioritised ring, and take every update of the ONE learner "
                          "from all K rings (DeviceActorCritic.update_from_many: one gradient row per ring, one apply); "
-                         "needs --learner device --replay prioritized")
+                         "needs --learner device --replay prioritized; --method maac-r also needs --pmi-trainer device "
+                         "(DevicePMINetwork.train_pmi_many over the K observation histories, un-concatenated), and each "
+                         "MAAC-R handle sizes its own scorer scratch")
     ap.add_argument("--log-every", type=int, default=1,
                     help="print (and so synchronise) every N iterations and after the last; the iteration time printed is "
                          "the mean over the iterations since the previous line, and with N > 1 the rollout time of a "
@@ -304,9 +330,9 @@ def main(argv=None, timings=None):
         if args.learner != "device" or args.replay != "prioritized":
             ap.error("--shards K > 1 needs --learner device --replay prioritized (one device learner updated from K "
                      "prioritised rings)")
-        if args.method == "maac-r":
-            ap.error("--shards K > 1 supports --method maac and maac-g (the PMI trainer's BatchNorm uses batch "
-                     "statistics: its batch cannot be split without changing the function)")
+        if args.method == "maac-r" and args.pmi_trainer != "device":
+            ap.error("--shards K > 1 with --method maac-r needs --pmi-trainer device (one uavtrack.DevicePMINetwork "
+                     "trained over the K observation histories: train_pmi_many)")
         return train_sharded(args, timings)
 
     dev = "cuda:0"

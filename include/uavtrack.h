@@ -660,6 +660,42 @@ int uavtrack_pmi_trainer_check(uavtrack_pmi_trainer *trainer, int64_t *refused, 
  * or the trainer's hidden differs from the installed width. */
 int uavtrack_pmi_trainer_publish(uavtrack_pmi_trainer *trainer, uavtrack_env *env, void *stream);
 
+/* One observation history among several (K shard handles on one device, or the part of a timeline one rank holds).  A
+ * *group* is n_uav consecutive rows: one "timestep" of train_pmi.  The *timeline* of sources[0..count) is the
+ * concatenation of their groups in list order: group t lives in source k when base_k <= t < base_k + n_rows_k / n_uav,
+ * base_k being the number of groups in the sources before k. */
+typedef struct uavtrack_pmi_source {
+    const float *rows;      /* DEVICE: [n_rows][12], timestep-major */
+    int64_t n_rows;         /* a positive multiple of n_uav */
+} uavtrack_pmi_source;
+
+#define UAVTRACK_PMI_MAX_SOURCES 64
+
+/* uavtrack_pmi_trainer_train on the timeline of sources[0..count), bit for bit (state, running statistics,
+ * num_batches_tracked, both moments, step counts, avg_loss, losses, outputs); count == 1 is that call.  The rows are
+ * never concatenated: one gather launch per scratch fill copies the 2 selected rows of each draw into the trainer's
+ * scratch (as many draws as the reserve holds rows: one fill per call while b2 <= max_batch), and the step kernels run
+ * on them.  Stream-ordered: no synchronisation, no allocation, capturable into a graph.  `sources` is a HOST array read
+ * during the call and captured by value (the pointers and row counts, not the rows).
+ * Returns an error, enqueuing nothing, for a count outside [1, UAVTRACK_PMI_MAX_SOURCES], a null rows, an n_rows that
+ * is not a positive multiple of n_uav, and whatever uavtrack_pmi_trainer_train refuses.  A t_idx outside [0, total
+ * groups) or a u_idx outside [0, n_uav) is found on the device, as there: the call changes nothing, its losses are NaN,
+ * and the next uavtrack_pmi_trainer_check reports it. */
+int uavtrack_pmi_trainer_train_many(uavtrack_pmi_trainer *trainer, const uavtrack_pmi_source *sources, int32_t count,
+                                    int64_t n_uav, const int64_t *t_idx, const int64_t *u_idx, int64_t b2,
+                                    int64_t batch_size, float *avg_loss, float *losses, float *outputs, void *stream);
+
+/* The gather alone, for a participant that holds part of a timeline: sources[0..count) are the groups [group_base,
+ * group_base + local groups) of a timeline of total_groups groups.  For every draw i whose t_idx[i] falls inside that
+ * span, selected[i] ([b2][2][12], DEVICE) receives rows (t_idx[i], u_idx[i][0]) and (t_idx[i], u_idx[i][1]); the rows
+ * of every other draw are left as they were.  Every draw is checked against total_groups and n_uav on the device: one
+ * out of range makes the call write nothing, and the next uavtrack_pmi_trainer_check reports it.  Stream-ordered,
+ * no synchronisation, no allocation, capturable; `sources` as above.  Returns an error, enqueuing nothing, for a bad
+ * source list (as above), b2 outside [1, 2^31 - 1], group_base < 0 or a span that ends behind total_groups. */
+int uavtrack_pmi_trainer_select(uavtrack_pmi_trainer *trainer, const uavtrack_pmi_source *sources, int32_t count,
+                                int64_t group_base, int64_t total_groups, int64_t n_uav, const int64_t *t_idx,
+                                const int64_t *u_idx, int64_t b2, float *selected, void *stream);
+
 /* ---- the prioritised replay ring: PrioritizedReplayBuffer.add / sample on the device ----
  * The reference's PrioritizedReplayBuffer (train.py:73-139) as a ring of caller-owned DEVICE tensors: states and
  * next_states [capacity][12] fp32, actions [capacity] int32, rewards and priorities [capacity] fp32.  pos (next slot to

@@ -1347,7 +1347,8 @@ Bufs scratch_bufs(PmiTrainDevice &d, int64_t max_b)
 {
     const size_t H = (size_t)d.L.H, nb = (size_t)max_b;
     return {buf(d.xh0, 2 * 3 * H * nb), buf(d.a0, 2 * 3 * H * nb), buf(d.da0, 2 * 3 * H * nb), buf(d.xh1, 2 * H * nb),
-            buf(d.a1, 2 * H * nb), buf(d.dz1, 2 * H * nb), buf(d.go, 2 * nb)};
+            buf(d.a1, 2 * H * nb), buf(d.dz1, 2 * H * nb), buf(d.go, 2 * nb), buf(d.sel, 2 * 12 * nb), buf(d.sel_t, nb),
+            buf(d.sel_u, 2 * nb)};
 }
 
 Bufs device_bufs(PmiTrainDevice &d)
@@ -1849,6 +1850,93 @@ int uavtrack_pmi_trainer_train(uavtrack_pmi_trainer *trainer, const float *rows,
     q.rows = rows; q.n_rows = n_rows; q.n_uav = n_uav; q.b2 = b2; q.batch = batch_size;
     q.t_idx = t_idx; q.u_idx = u_idx; q.avg_loss = avg_loss; q.losses = losses; q.outputs = outputs;
     HIP_TRY(launch_pmi_train(trainer->d, q, static_cast<hipStream_t>(stream)));
+    return 0;
+}
+
+}  // extern "C"
+
+namespace {
+
+// The source list of uavtrack_pmi_trainer_train_many / _select into the table the select kernel takes by value; the
+// span starts at group_base.  Returns nonzero after fail().
+int accept_sources(const char *fn, const uavtrack_pmi_source *sources, int32_t count, int64_t n_uav, int64_t group_base,
+                   PmiSourceTable *out)
+{
+    if (!sources) return fail("%s: sources must not be null", fn);
+    if (count < 1 || count > UAVTRACK_PMI_MAX_SOURCES)
+        return fail("%s: count = %d out of range [1, %d]", fn, count, UAVTRACK_PMI_MAX_SOURCES);
+    if (n_uav < 1) return fail("%s: n_uav = %lld < 1", fn, (long long)n_uav);
+    out->count = count;
+    out->base[0] = group_base;
+    for (int k = 0; k < count; ++k) {
+        if (!sources[k].rows) return fail("%s: sources[%d].rows is null", fn, k);
+        if (sources[k].n_rows < n_uav || sources[k].n_rows % n_uav != 0)
+            return fail("%s: sources[%d].n_rows = %lld is not a positive multiple of n_uav = %lld", fn, k,
+                        (long long)sources[k].n_rows, (long long)n_uav);
+        const int64_t groups = sources[k].n_rows / n_uav;
+        if (groups > INT64_MAX / 2 - out->base[k]) return fail("%s: the sources hold too many groups", fn);
+        out->rows[k] = sources[k].rows;
+        out->base[k + 1] = out->base[k] + groups;
+    }
+    for (int k = count; k < kPmiMaxSources; ++k) {
+        out->rows[k] = nullptr;
+        out->base[k + 1] = out->base[count];
+    }
+    return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int uavtrack_pmi_trainer_train_many(uavtrack_pmi_trainer *trainer, const uavtrack_pmi_source *sources, int32_t count,
+                                    int64_t n_uav, const int64_t *t_idx, const int64_t *u_idx, int64_t b2,
+                                    int64_t batch_size, float *avg_loss, float *losses, float *outputs, void *stream)
+{
+    if (!trainer) return fail("uavtrack_pmi_trainer_train_many: null handle");
+    if (!t_idx || !u_idx || !avg_loss)
+        return fail("uavtrack_pmi_trainer_train_many: t_idx, u_idx and avg_loss must not be null");
+    PmiSourceTable table;
+    if (accept_sources(__func__, sources, count, n_uav, 0, &table)) return 1;
+    if (batch_size < 2)
+        return fail("uavtrack_pmi_trainer_train_many: batch_size = %lld < 2 (train-mode BatchNorm1d needs two rows)",
+                    (long long)batch_size);
+    if (batch_size > trainer->d.max_b)
+        return fail("uavtrack_pmi_trainer_train_many: batch_size = %lld, scratch is reserved for %lld "
+                    "(uavtrack_pmi_trainer_reserve)", (long long)batch_size, (long long)trainer->d.max_b);
+    if (b2 < batch_size)
+        return fail("uavtrack_pmi_trainer_train_many: b2 = %lld < batch_size = %lld (no mini-batch)", (long long)b2,
+                    (long long)batch_size);
+    if (b2 / batch_size > (int64_t)1 << 30)
+        return fail("uavtrack_pmi_trainer_train_many: b2 = %lld too large", (long long)b2);
+    ON_DEVICE(trainer->cfg.device_id);
+    PmiTrainLaunch q;
+    q.rows = nullptr; q.n_rows = table.base[count] * n_uav; q.n_uav = n_uav; q.b2 = b2; q.batch = batch_size;
+    q.t_idx = t_idx; q.u_idx = u_idx; q.avg_loss = avg_loss; q.losses = losses; q.outputs = outputs;
+    HIP_TRY(launch_pmi_train_many(trainer->d, table, q, static_cast<hipStream_t>(stream)));
+    return 0;
+}
+
+int uavtrack_pmi_trainer_select(uavtrack_pmi_trainer *trainer, const uavtrack_pmi_source *sources, int32_t count,
+                                int64_t group_base, int64_t total_groups, int64_t n_uav, const int64_t *t_idx,
+                                const int64_t *u_idx, int64_t b2, float *selected, void *stream)
+{
+    if (!trainer) return fail("uavtrack_pmi_trainer_select: null handle");
+    if (!t_idx || !u_idx || !selected)
+        return fail("uavtrack_pmi_trainer_select: t_idx, u_idx and selected must not be null");
+    if (b2 < 1 || b2 > INT32_MAX)   // 24 lanes per draw at most: the grid stays below 2^31 workgroups
+        return fail("uavtrack_pmi_trainer_select: b2 = %lld out of range [1, %d]", (long long)b2, INT32_MAX);
+    if (group_base < 0 || total_groups < 1 || group_base >= total_groups)
+        return fail("uavtrack_pmi_trainer_select: group_base = %lld outside a timeline of %lld groups", (long long)group_base,
+                    (long long)total_groups);
+    PmiSourceTable table;
+    if (accept_sources(__func__, sources, count, n_uav, group_base, &table)) return 1;
+    if (table.base[count] > total_groups)
+        return fail("uavtrack_pmi_trainer_select: the sources end at group %lld of a timeline of %lld", (long long)table.base[count],
+                    (long long)total_groups);
+    ON_DEVICE(trainer->cfg.device_id);
+    HIP_TRY(launch_pmi_select(trainer->d, table, total_groups, n_uav, t_idx, u_idx, b2, selected,
+                              static_cast<hipStream_t>(stream)));
     return 0;
 }
 

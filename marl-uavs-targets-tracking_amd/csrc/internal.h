@@ -405,6 +405,9 @@ struct PmiTrainDevice {
     float *inv0, *inv1;             // [2][3H], [2][H] 1 / sqrt(var + eps) of the current step
     float *go;                      // [2][max_b] dL/d(output_1_2), dL/d(output_1_3)
     float *acc;                     // [1] sum of |loss| over the call
+    // uavtrack_pmi_trainer_train_many: the selected rows of up to max_b draws and the identity triples that address them
+    float *sel;                     // [max_b][2][12]
+    int64_t *sel_t, *sel_u;         // [max_b] = i, [max_b][2] = (0, 1)
     int64_t max_b;
 };
 struct PmiTrainLaunch {
@@ -414,6 +417,19 @@ struct PmiTrainLaunch {
     float *avg_loss, *losses, *outputs;
 };
 hipError_t launch_pmi_train(const PmiTrainDevice &d, const PmiTrainLaunch &q, hipStream_t stream);
+// A source list as the select kernel takes it, by value: source k holds the timeline's groups [base[k], base[k + 1])
+constexpr int kPmiMaxSources = 64;            // UAVTRACK_PMI_MAX_SOURCES
+struct PmiSourceTable {
+    const float *rows[kPmiMaxSources];
+    int64_t base[kPmiMaxSources + 1];         // base[0]: the span's first group in the timeline
+    int count;
+};
+// uavtrack_pmi_trainer_train_many: q.rows is unused, q.n_rows = total groups * n_uav
+hipError_t launch_pmi_train_many(const PmiTrainDevice &d, const PmiSourceTable &src, const PmiTrainLaunch &q,
+                                 hipStream_t stream);
+// uavtrack_pmi_trainer_select: the draws of the table's span into selected [b2][2][12]
+hipError_t launch_pmi_select(const PmiTrainDevice &d, const PmiSourceTable &src, int64_t total_groups, int64_t n_uav,
+                             const int64_t *t_idx, const int64_t *u_idx, int64_t b2, float *selected, hipStream_t stream);
 
 // replay_kernel.hip -- the prioritised replay ring (uavtrack_replay_*).  The ring's stores and priorities belong to the
 // caller; the handle owns the scratch below.  Sampling works on tiles of kReplayTile slots: per-tile fp64 sums, one

@@ -18,6 +18,9 @@
 //   pmi_adam_kernel           per trainable element: Adam on the gradient the kernels above wrote (zero_grad
 //                             semantics: every gradient is rewritten each step);
 // and pmi_finalize_kernel: avg_loss, the refusal count.
+// uavtrack_pmi_trainer_train_many runs the same chain on rows that pmi_select_kernel first gathers from a list of
+// histories into the trainer's scratch (the step kernels' arithmetic does not depend on where a row came from);
+// uavtrack_pmi_trainer_select is that gather alone, for one participant's span of a timeline.
 // Every sum over the batch is owned by one wavefront (lanes over rows, a fixed xor-butterfly reduction) or one thread,
 // so there are no float atomics and two identical calls give bitwise identical results.  Both forwards of a step live
 // in the same wavefront, which applies their running-statistics updates in the reference's order.
@@ -452,24 +455,24 @@ __global__ void pmi_finalize_kernel(const int *status, int *errors, const float 
     *avg_loss = *acc / (float)nb;
 }
 
-}  // namespace
-
-hipError_t launch_pmi_train(const PmiTrainDevice &d, const PmiTrainLaunch &q, hipStream_t st)
+// The step kernels' arguments that do not change within a call; rows, the triples and n_uav are the caller's
+StepArgs step_args(const PmiTrainDevice &d, const PmiTrainLaunch &q)
 {
-    const PmiTrainLayout &L = d.L;
-    const int H = L.H, B = (int)q.batch;
-    const int64_t nb = q.b2 / q.batch;
-    hipLaunchKernelGGL(pmi_begin_kernel, dim3(1), dim3(kWG), 0, st, q.t_idx, q.u_idx, q.b2, q.n_rows / q.n_uav, q.n_uav,
-                       d.opt.status, d.acc);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
-
     StepArgs a;
-    a.L = L; a.rows = q.rows; a.t_idx = q.t_idx; a.u_idx = q.u_idx; a.n_uav = q.n_uav; a.B = B;
+    a.L = d.L; a.rows = q.rows; a.t_idx = q.t_idx; a.u_idx = q.u_idx; a.n_uav = q.n_uav; a.B = (int)q.batch;
+    a.row0 = 0; a.step = 0;
     a.state = d.state; a.grad = d.grad; a.nbt = d.nbt; a.steps = d.opt.steps;
     a.xh0 = d.xh0; a.a0 = d.a0; a.da0 = d.da0; a.xh1 = d.xh1; a.a1 = d.a1; a.dz1 = d.dz1;
     a.inv0 = d.inv0; a.inv1 = d.inv1; a.go = d.go; a.acc = d.acc;
     a.losses = q.losses; a.outputs = q.outputs; a.status = d.opt.status;
+    return a;
+}
+
+// Mini-batch steps [b0, b1) of a call, step b taking the triples from first + (b - b0) * B on
+hipError_t launch_pmi_steps(const PmiTrainDevice &d, StepArgs a, int64_t b0, int64_t b1, int64_t first, hipStream_t st)
+{
+    const PmiTrainLayout &L = d.L;
+    const int H = L.H, B = a.B;
     const dim3 blk(kWG);
     const dim3 g_branch((3 * H + kWavesPerWG - 1) / kWavesPerWG), g_fc1((H + kWavesPerWG - 1) / kWavesPerWG);
     const dim3 g_adam((L.P + kWG - 1) / kWG);
@@ -491,8 +494,8 @@ hipError_t launch_pmi_train(const PmiTrainDevice &d, const PmiTrainLaunch &q, hi
     const Opnd x_b = {d.dz1, B, 1, 0, B, 0, (int64_t)H * B};
     const Opnd x_c = {d.da0, B, 1, 0, B, 0, (int64_t)K * B};
     const Opnd x_m = {d.a0, B, 1, 0, B, 0, (int64_t)K * B};
-    for (int64_t b = 0; b < nb; ++b) {
-        a.row0 = b * q.batch;
+    for (int64_t b = b0; b < b1; ++b) {
+        a.row0 = first + (b - b0) * B;
         a.step = (int)b;
         hipLaunchKernelGGL(pmi_branch_fwd_kernel, g_branch, blk, 0, st, a);
         hipLaunchKernelGGL(pmi_gemm_kernel, tiles(H, N2), blk, 0, st, f_a, f_b, f_c, H, N2, K, (int)kAddBias,
@@ -507,9 +510,123 @@ hipError_t launch_pmi_train(const PmiTrainDevice &d, const PmiTrainLaunch &q, hi
         hipLaunchKernelGGL(pmi_branch_bwd_kernel, g_branch, blk, 0, st, a);
         hipLaunchKernelGGL(pmi_adam_kernel, g_adam, blk, 0, st, L, d.state, d.opt.m, d.opt.v, d.grad, d.opt.steps,
                            d.opt.status, d.lr);
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
+}
+
+// The gather of uavtrack_pmi_trainer_train_many and _select: draws [d0, d0 + n) of the triples, the two rows of draw
+// d0 + j to dst[j][2][12].  One lane per (draw, side, V floats); the draw's source is found by a binary search over the
+// table's group prefix, and a draw whose group lies outside the table's span [base[0], base[count]) is skipped (its
+// rows of dst stay as they were).  Row offsets are 64-bit.  The call's verdict (pmi_begin_kernel, which has tested every
+// triple against the whole timeline) is read first: a refused call loads nothing through its indices and stores nothing.
+struct SelectArgs {
+    PmiSourceTable src;
+    const int64_t *t_idx, *u_idx;
+    int64_t n_uav, d0, n;
+    float *dst;
+    int64_t *id_t, *id_u;                // nullable: identity triples (t' = j, u' = (0, 1)) that address dst as a history
+    const int *status;
+    int *errors;                         // nullable: the refusal count, for a call that ends with this kernel
+};
+
+template <int V>
+__global__ void __launch_bounds__(kWG) pmi_select_kernel(SelectArgs a)
+{
+    constexpr int kPerRow = 12 / V, kPerDraw = 2 * kPerRow;
+    const int64_t gid = (int64_t)blockIdx.x * kWG + threadIdx.x;
+    if (*a.status) {
+        if (gid == 0 && a.errors) *a.errors += 1;
+        return;
+    }
+    const int64_t j = gid / kPerDraw;
+    if (j >= a.n) return;
+    const int r = (int)(gid - j * kPerDraw), side = r / kPerRow, c = r - side * kPerRow;
+    if (r == 0 && a.id_t) {
+        a.id_t[j] = j;
+        a.id_u[2 * j] = 0;
+        a.id_u[2 * j + 1] = 1;
+    }
+    const int64_t g = a.d0 + j, t = a.t_idx[g];
+    if (t < a.src.base[0] || t >= a.src.base[a.src.count]) return;
+    int lo = 0, hi = a.src.count;        // base[lo] <= t < base[hi]
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (t >= a.src.base[mid]) lo = mid; else hi = mid;
+    }
+    const float *from = a.src.rows[lo] + ((t - a.src.base[lo]) * a.n_uav + a.u_idx[2 * g + side]) * 12 + c * V;
+    float *to = a.dst + (j * 2 + side) * 12 + c * V;
+    if (V == 4) *reinterpret_cast<float4 *>(to) = *reinterpret_cast<const float4 *>(from);
+    else *to = *from;
+}
+
+bool aligned16(const void *p) { return ((uintptr_t)p & 15) == 0; }
+
+void launch_select(SelectArgs a, hipStream_t st)
+{
+    bool vec = aligned16(a.dst);
+    for (int k = 0; k < a.src.count; ++k) vec = vec && aligned16(a.src.rows[k]);
+    const int64_t lanes = a.n * (vec ? 6 : 24);
+    const dim3 grid((unsigned)((lanes + kWG - 1) / kWG));
+    if (vec) hipLaunchKernelGGL(pmi_select_kernel<4>, grid, dim3(kWG), 0, st, a);
+    else hipLaunchKernelGGL(pmi_select_kernel<1>, grid, dim3(kWG), 0, st, a);
+}
+
+}  // namespace
+
+hipError_t launch_pmi_train(const PmiTrainDevice &d, const PmiTrainLaunch &q, hipStream_t st)
+{
+    const int64_t nb = q.b2 / q.batch;
+    hipLaunchKernelGGL(pmi_begin_kernel, dim3(1), dim3(kWG), 0, st, q.t_idx, q.u_idx, q.b2, q.n_rows / q.n_uav, q.n_uav,
+                       d.opt.status, d.acc);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    if ((e = launch_pmi_steps(d, step_args(d, q), 0, nb, 0, st)) != hipSuccess) return e;
+    hipLaunchKernelGGL(pmi_finalize_kernel, dim3(1), dim3(64), 0, st, d.opt.status, d.opt.errors, d.acc, nb, q.avg_loss);
+    return hipGetLastError();
+}
+
+// launch_pmi_train with the rows of each mini-batch gathered from the source list first: the scratch holds the rows of
+// max_b draws, so the steps run in fills of max_b / batch mini-batches (one fill while b2 <= max_b), each a select
+// launch and then the unchanged step kernels on the scratch through identity triples.  The range check stays
+// pmi_begin_kernel's, on the caller's triples against the whole timeline.
+hipError_t launch_pmi_train_many(const PmiTrainDevice &d, const PmiSourceTable &src, const PmiTrainLaunch &q,
+                                 hipStream_t st)
+{
+    const int64_t nb = q.b2 / q.batch, per_fill = d.max_b / q.batch;
+    hipLaunchKernelGGL(pmi_begin_kernel, dim3(1), dim3(kWG), 0, st, q.t_idx, q.u_idx, q.b2, q.n_rows / q.n_uav, q.n_uav,
+                       d.opt.status, d.acc);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    StepArgs a = step_args(d, q);
+    a.rows = d.sel; a.t_idx = d.sel_t; a.u_idx = d.sel_u; a.n_uav = 2;
+    SelectArgs s;
+    s.src = src; s.t_idx = q.t_idx; s.u_idx = q.u_idx; s.n_uav = q.n_uav;
+    s.dst = d.sel; s.id_t = d.sel_t; s.id_u = d.sel_u; s.status = d.opt.status; s.errors = nullptr;
+    for (int64_t b0 = 0; b0 < nb; b0 += per_fill) {
+        const int64_t b1 = b0 + per_fill < nb ? b0 + per_fill : nb;
+        s.d0 = b0 * q.batch;
+        s.n = (b1 - b0) * q.batch;
+        launch_select(s, st);
         if ((e = hipGetLastError()) != hipSuccess) return e;
+        if ((e = launch_pmi_steps(d, a, b0, b1, 0, st)) != hipSuccess) return e;
     }
     hipLaunchKernelGGL(pmi_finalize_kernel, dim3(1), dim3(64), 0, st, d.opt.status, d.opt.errors, d.acc, nb, q.avg_loss);
+    return hipGetLastError();
+}
+
+hipError_t launch_pmi_select(const PmiTrainDevice &d, const PmiSourceTable &src, int64_t total_groups, int64_t n_uav,
+                             const int64_t *t_idx, const int64_t *u_idx, int64_t b2, float *selected, hipStream_t st)
+{
+    hipLaunchKernelGGL(pmi_begin_kernel, dim3(1), dim3(kWG), 0, st, t_idx, u_idx, b2, total_groups, n_uav, d.opt.status,
+                       d.acc);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    SelectArgs s;
+    s.src = src; s.t_idx = t_idx; s.u_idx = u_idx; s.n_uav = n_uav; s.d0 = 0; s.n = b2;
+    s.dst = selected; s.id_t = nullptr; s.id_u = nullptr; s.status = d.opt.status; s.errors = d.opt.errors;
+    launch_select(s, st);
     return hipGetLastError();
 }
 

@@ -94,12 +94,18 @@ class PmiTensors(C.Structure):
     _fields_ = [("t", C.c_void_p * 26)]
 
 
+class PmiSource(C.Structure):
+    """Mirror of `struct uavtrack_pmi_source` (include/uavtrack.h)."""
+    _fields_ = [("rows", C.c_void_p), ("n_rows", C.c_int64)]
+
+
 # the float entries of the reference PMINetwork's state_dict, its order (= struct uavtrack_pmi_tensors)
 PMI_STATE_KEYS = tuple(f"{m}.{k}" for lin, bn in (("fc_comm", "bn_comm"), ("fc_obs", "bn_obs"),
                                                    ("fc_boundary_state", "bn_boundary_state"), ("fc1", "bn1"))
                        for m, k in ((lin, "weight"), (lin, "bias"), (bn, "weight"), (bn, "bias"),
                                     (bn, "running_mean"), (bn, "running_var"))) + ("fc2.weight", "fc2.bias")
 PMI_TRAIN_TENSORS = 18                                    # PMINetwork.parameters()
+PMI_MAX_SOURCES = 64                                      # UAVTRACK_PMI_MAX_SOURCES
 PMI_BN_LAYERS = 4                                         # BatchNorm1d layers (num_batches_tracked entries)
 LOSS_FORMS = ("reference", "per_sample")                  # enum uavtrack_actor_loss
 LEARNER_ROW_TAIL = 8                                      # words behind the P gradient sums of a gradient row
@@ -182,6 +188,10 @@ SIGNATURES = {
     "uavtrack_pmi_trainer_train": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p,
                                               C.c_int64, C.c_int64] + [C.c_void_p] * 4),
     "uavtrack_pmi_trainer_publish": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "uavtrack_pmi_trainer_train_many": (C.c_int, [C.c_void_p, C.POINTER(PmiSource), C.c_int32, C.c_int64, C.c_void_p,
+                                                   C.c_void_p, C.c_int64, C.c_int64] + [C.c_void_p] * 4),
+    "uavtrack_pmi_trainer_select": (C.c_int, [C.c_void_p, C.POINTER(PmiSource), C.c_int32, C.c_int64, C.c_int64, C.c_int64,
+                                               C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
     "uavtrack_pmi_trainer_check": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64), C.c_void_p]),
     "uavtrack_replay_create": (C.c_int, [C.POINTER(ReplayConfig), C.POINTER(C.c_void_p)]),
     "uavtrack_replay_destroy": (C.c_int, [C.c_void_p]),

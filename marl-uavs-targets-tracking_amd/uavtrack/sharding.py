@@ -222,3 +222,76 @@ def broadcast_learner(learner, group=None, src: int = 0) -> None:
     learner._set_optim_state(np.ascontiguousarray(blk[P:2 * P]).view(np.float32),
                               np.ascontiguousarray(blk[2 * P:3 * P]).view(np.float32),
                               np.ascontiguousarray(blk[3 * P:]).view(np.int64))
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# MAAC-R over ranks.  PMINetwork.train_pmi trains on b2 selected (timestep, uav-pair) row pairs; only the selection
+# touches the observation history.  So the ranks exchange the 2 b2 selected rows (288 KB at b2 = 3000), never a
+# history, and every rank runs the whole, unsplit training step on them (DevicePMINetwork.train_pmi(group=...)): the
+# BatchNorm statistics stay those of the full mini-batch and no synchronised BatchNorm is needed.
+
+
+def gather_pmi_selected(selected, group=None):
+    """All-gather of each rank's [b2, 2, 12] selected block (uavtrack_pmi_trainer_select into a zeroed buffer) into
+    [world * b2, 2, 12], rank-major, on the block's device.  The rows travel as int32 bit views, so no backend
+    touches a bit (NaN payloads, -0.0).  Without a process group, or with one rank, the block itself."""
+    import torch
+    import torch.distributed as dist
+    if not (dist.is_available() and dist.is_initialized()) or dist.get_world_size(group) == 1:
+        return selected
+    world = dist.get_world_size(group)
+    dev = selected.device
+    send = selected.contiguous().view(torch.int32)
+    if dev.type == "cuda" and dist.get_backend(group) == "gloo":
+        send = send.cpu()          # rehearsal on gloo: stage through the host
+    out = torch.empty((world * send.shape[0],) + tuple(send.shape[1:]), dtype=torch.int32, device=send.device)
+    dist.all_gather_into_tensor(out, send, group=group)
+    return out.to(dev).view(torch.float32)
+
+
+def _pmi_owner_triples(t_idx, u_idx, group_counts, n_uav: int):
+    """The triples that read draw i's rows out of the rank-major gathered block: rank r owns the timeline's timesteps
+    [base_r, base_r + group_counts[r]), draw i belongs to owner(i), the rank whose span holds t_idx[i], and its two
+    rows are "timestep" owner(i) * b2 + i of the block taken as world * b2 timesteps of 2 rows: t' = owner(i) * b2 + i,
+    u' = (0, 1).  If any draw lies outside the timeline or [0, n_uav) (every rank's select then wrote nothing), every
+    t' is -1, so that the training call on the block is refused on the device as the same draws would be on one
+    process.  Device arithmetic only: no synchronisation.  Returns (t' [b2], u' [b2, 2]) int64 on t_idx's device."""
+    import torch
+    b2 = t_idx.numel()
+    ends = torch.cumsum(torch.as_tensor(list(group_counts), dtype=torch.int64), 0).to(t_idx.device)
+    owner = torch.bucketize(t_idx, ends, right=True).clamp_(max=len(group_counts) - 1)
+    t2 = owner * b2 + torch.arange(b2, dtype=torch.int64, device=t_idx.device)
+    bad = ((t_idx < 0) | (t_idx >= ends[-1])).any() | ((u_idx < 0) | (u_idx >= int(n_uav))).any()
+    t2 = torch.where(bad, torch.full_like(t2, -1), t2)
+    u2 = torch.tensor([0, 1], dtype=torch.int64, device=t_idx.device).repeat(b2, 1)
+    return t2.contiguous(), u2.contiguous()
+
+
+def broadcast_pmi_trainer(trainer, group=None, src: int = 0) -> None:
+    """Rank `src`'s PMI network state (the state blob and num_batches_tracked), Adam moments and step counts to every
+    rank of `group` (src is a global rank), so that the ranks' trainers start equal.  Synchronises; meant for start-up
+    and checkpoint loads, not the training loop."""
+    import numpy as np
+    import torch
+    import torch.distributed as dist
+    from . import _lib, adam
+    if not (dist.is_available() and dist.is_initialized()) or dist.get_world_size(group) == 1:
+        return
+    st, nbt = trainer._get()
+    m, v, steps = trainer.optimizer_state()
+    # one int32 block: the three float blobs as bit views, then the two int64 count arrays
+    blk = torch.from_numpy(np.concatenate([st.view(np.int32), m.view(np.int32), v.view(np.int32),
+                                           np.ascontiguousarray(nbt, np.int64).view(np.int32),
+                                           np.ascontiguousarray(steps, np.int64).view(np.int32)]))
+    if dist.get_backend(group) != "gloo":
+        blk = blk.to(trainer.device)
+    dist.broadcast(blk, src=src, group=group)
+    blk = blk.cpu().numpy()
+    S, P, nb = trainer.num_state, trainer.num_params, 2 * _lib.PMI_BN_LAYERS
+    st = np.ascontiguousarray(blk[:S]).view(np.float32)
+    nbt = np.ascontiguousarray(blk[S + 2 * P:S + 2 * P + nb]).view(np.int64)
+    _lib.check(trainer._lib.uavtrack_pmi_trainer_set_params(trainer._h, _lib.host_ptr(st), _lib.host_ptr(nbt), st.size,
+                                                            trainer._stream()), "uavtrack_pmi_trainer_set_params")
+    adam.write(trainer._lib.uavtrack_pmi_trainer_set_optimizer_state, trainer._h,
+               np.ascontiguousarray(blk[S:S + P]).view(np.float32), np.ascontiguousarray(blk[S + P:S + 2 * P]).view(np.float32),
+               np.ascontiguousarray(blk[S + 2 * P + nb:]).view(np.int64), trainer._stream())
