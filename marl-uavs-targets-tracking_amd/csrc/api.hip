@@ -155,6 +155,10 @@ hipError_t timed_launch(uavtrack_env *env, int cls, hipStream_t st, F &&launch)
     return e;
 }
 
+// Step t0 of an array with a leading [T] axis and `stride` elements per step; a null array stays null.
+template <typename P>
+P *at_step(P *base, int32_t t0, size_t stride) { return base ? base + (size_t)t0 * stride : nullptr; }
+
 // ---- the environment's device buffers, by set (the arguments size the sets that are replaced later) -----------------
 Bufs slab_bufs(uavtrack_env *env)
 {
@@ -843,100 +847,144 @@ int uavtrack_get_pmi_blob(uavtrack_env *env, float *host, int64_t n_floats, void
     return 0;
 }
 
-// Where a rollout's actions come from: the caller's tensor, the in-kernel greedy baseline (uavtrack_run_greedy) or the
-// in-kernel actor (uavtrack_run_actor).
-struct PolicyArgs {
-    bool auto_reset = false;           // uavtrack_step_many_autoreset: reset seed
-    uint64_t reset_seed = 0;
-    int policy = kPolicyGiven;
+// One request to the rollout kernel, as each of the nine stepping entry points states it.  The optional outputs start
+// out as what the handle has installed (uavtrack_set_target_trace and its kin).
+struct RolloutCall {
+    const char *who;                   // the entry point, as the error messages name it
+    int32_t T;
+    const int32_t *actions = nullptr;  // given actions [T][B][N] (kPolicyGiven)
+    // per-step outputs, leading [T] axis; all but reward nullable
+    float *obs, *reward, *terms;
+    int32_t *covered;
+    uint8_t *done;
+    int32_t *actions_out = nullptr;    // greedy / actor: chosen actions
+    float *ep_sums;                    // [B][5]
+    bool accumulate = false;           // ep_sums += (uavtrack_step_accumulate: ep_sums is then required)
+    int policy = kPolicyGiven;         // where the actions come from: the caller, the in-kernel greedy baseline or actor
     const float *obs_in = nullptr;     // actor: observation seen at the first step
-    int32_t *actions_out = nullptr;    // greedy / actor: chosen actions [T][B][N], nullable
     uint64_t seed = 0;                 // greedy / actor: policy seed
-    int32_t mode = 0;
+    int32_t mode = 0;                  // actor: UAVTRACK_ACTOR_SAMPLE / _ARGMAX
+    bool auto_reset = false;           // the _autoreset forms
+    uint64_t reset_seed = 0;
+    // optional outputs with their capacities in steps
+    float2 *tpos = nullptr;
+    float *raw = nullptr, *start_obs = nullptr;
+    int32_t tpos_steps = 0, raw_steps = 0, start_obs_steps = 0;
+    float *state_copy = nullptr;       // uavtrack_step_host: second copy of the state slab behind the launch
+
+    RolloutCall(const char *who_, const uavtrack_env *env, int32_t T_, float *obs_, float *reward_, float *terms_,
+                int32_t *covered_, uint8_t *done_, float *ep_sums_)
+        : who(who_), T(T_), obs(obs_), reward(reward_), terms(terms_), covered(covered_), done(done_), ep_sums(ep_sums_)
+    {
+        if (!env) return;              // (refused by accept_rollout)
+        tpos = env->tpos; tpos_steps = env->tpos_steps;
+        raw = env->raw_out; raw_steps = env->raw_steps;
+        start_obs = env->start_obs_out; start_obs_steps = env->start_obs_steps;
+    }
 };
 
-static int run_steps(uavtrack_env *env, int32_t T, const int32_t *actions, float *obs, float *reward, float *terms,
-                     int32_t *covered, uint8_t *done, float *ep_sums, void *stream, const char *who,
-                     bool accumulate = false, const PolicyArgs &pol = PolicyArgs())
+// Every refusal of the stepping entry points, in one order.  Nothing has been enqueued when one of them fires.
+static int accept_rollout(const uavtrack_env *env, const RolloutCall &q)
 {
+    const char *who = q.who;
     if (!env) return fail("%s: null handle", who);
-    if (T < 1) return fail("%s: T must be >= 1 (got %d)", who, T);
-    if (pol.policy == kPolicyGiven && !actions) return fail("%s: actions is null", who);
-    if (!reward) return fail("%s: reward is null", who);
+    const uavtrack_config &c = env->cfg;
+    if (q.accumulate && !q.ep_sums) return fail("%s: ep_sums is null", who);
+    if (q.policy == kPolicyGreedy && (c.dim != 2 || c.reward_mode == UAVTRACK_REWARD_PMI))
+        return fail("%s: no rollout kernel for the combination (policy greedy, reward mode %s, %d-D): the C-METHOD baseline "
+                    "is planar and runs with the MAAC / MAAC-G rewards", who,
+                    c.reward_mode == UAVTRACK_REWARD_PMI ? "MAAC-R" : c.reward_mode == UAVTRACK_REWARD_MEAN ? "MAAC-G" : "MAAC", c.dim);
+    if (q.auto_reset && c.horizon < 1) return fail("%s: the configuration has no horizon (done never fires)", who);
+    if (q.T < 1) return fail("%s: T must be >= 1 (got %d)", who, q.T);
+    if (q.policy == kPolicyGiven && !q.actions) return fail("%s: actions is null", who);
+    if (!q.reward) return fail("%s: reward is null", who);
+    if (q.policy == kPolicyActor) {
+        if (!q.obs_in) return fail("%s: obs_in is null (the observation the policy sees at the first step)", who);
+        if (!env->actor_w) return fail("%s: needs uavtrack_set_actor_weights first", who);
+        if (q.mode != UAVTRACK_ACTOR_SAMPLE && q.mode != UAVTRACK_ACTOR_ARGMAX)
+            return fail("%s: mode %d is neither UAVTRACK_ACTOR_SAMPLE nor UAVTRACK_ACTOR_ARGMAX", who, q.mode);
+        if (q.obs_in == q.obs && q.T > 1)
+            return fail("%s: obs_in must not alias obs when T > 1 (pass the previous launch's last rows, or a copy)", who);
+    }
+    if (q.tpos && q.T > q.tpos_steps)
+        return fail("%s: T = %d exceeds the %d steps the target-trace buffer holds (uavtrack_set_target_trace)", who, q.T, q.tpos_steps);
+    if (q.raw && q.T > q.raw_steps)
+        return fail("%s: T = %d exceeds the %d steps the raw-reward buffer holds (uavtrack_set_raw_reward_output)", who, q.T, q.raw_steps);
+    // (the fresh-state observations exist only in an automatic-reset launch: no other launch sees the buffer)
+    if (q.auto_reset && q.start_obs && q.T > q.start_obs_steps)
+        return fail("%s: T = %d exceeds the %d steps the start-observation buffer holds (uavtrack_set_start_obs_output)", who, q.T, q.start_obs_steps);
+    if (c.reward_mode == UAVTRACK_REWARD_PMI && !env->pmi.blob) return fail("%s: reward_mode PMI needs uavtrack_set_pmi_weights first", who);
+    return 0;
+}
+
+// The kernel arguments of steps [t0, t0 + n) of a request.  obs_in: what an actor sees at step t0; add: ep_sums +=.
+static StepParams rollout_params(const uavtrack_env *env, const RolloutCall &q, int32_t t0, int32_t n, const float *obs_in, bool add)
+{
+    const uavtrack_config &c = env->cfg;
+    const size_t B = (size_t)c.n_envs, BN = B * c.n_uav, BM = B * c.m_targets;
+    const bool pmi = c.reward_mode == UAVTRACK_REWARD_PMI;
+    StepParams p = env->base;
+    p.T = n;
+    p.actions = at_step(q.actions, t0, BN);
+    p.actions_out = at_step(q.actions_out, t0, BN);
+    p.obs = at_step(q.obs, t0, BN * UAVTRACK_OBS_DIM);
+    if (pmi && !p.obs) p.obs = env->obs_tmp;       // (the scorer reads the chunk's observations)
+    p.reward = at_step(q.reward, t0, BN);
+    p.terms = at_step(q.terms, t0, 3 * BN);
+    p.covered = at_step(q.covered, t0, B);
+    p.done = at_step(q.done, t0, B);
+    p.tpos = at_step(q.tpos, t0, BM);
+    p.raw = at_step(q.raw, t0, BN);
+    p.start_obs = q.auto_reset ? at_step(q.start_obs, t0, BN * UAVTRACK_OBS_DIM) : nullptr;
+    p.state_copy = q.state_copy;
+    // episode sums: the three terms and the coverage are summed by the rollout kernel (registers) in every mode; MAAC-R's
+    // return by the mix stage (per-step means) and a one-lane-per-environment reduction over the chunk's steps
+    p.ep_sums = q.ep_sums;
+    p.ep_accumulate = add ? 1 : 0;
+    p.nbrec = pmi ? env->nbrec : nullptr;
+    p.pairs = pmi ? env->pairs : nullptr;
+    p.pair_count = pmi ? env->pair_count : nullptr;      // zero: set at allocation, re-zeroed by the mix kernel
+    p.pair_total = pmi ? env->pair_total : nullptr;
+    p.env_offset = c.env_offset;
+    // (kAutoResetContinued: an actor's first input after a reset at the chunk's edge)
+    p.auto_reset = !q.auto_reset ? 0 : t0 > 0 ? kAutoResetContinued : kAutoResetOn;
+    p.reset_k0 = (uint32_t)q.reset_seed; p.reset_k1 = (uint32_t)(q.reset_seed >> 32);
+    p.greedy_k0 = (uint32_t)q.seed; p.greedy_k1 = (uint32_t)(q.seed >> 32);
+    p.obs_in = obs_in;
+    if (q.policy == kPolicyActor) {
+        p.actor_w = env->actor_w; p.actor_hblocks = actor_blocks(env->actor_hidden);
+        p.actor_mode = q.mode;
+    }
+    return p;
+}
+
+static int run_rollout(uavtrack_env *env, const RolloutCall &q, void *stream)
+{
+    if (accept_rollout(env, q)) return 1;
     ON_DEVICE(env->cfg.device_id);
     hipStream_t st = static_cast<hipStream_t>(stream);
-    if (env->tpos && T > env->tpos_steps)
-        return fail("%s: T = %d exceeds the %d steps the target-trace buffer holds (uavtrack_set_target_trace)", who, T, env->tpos_steps);
-    if (env->raw_out && T > env->raw_steps)
-        return fail("%s: T = %d exceeds the %d steps the raw-reward buffer holds (uavtrack_set_raw_reward_output)", who, T, env->raw_steps);
-    // (the fresh-state observations exist only in an automatic-reset launch: no other launch sees the buffer)
-    if (pol.auto_reset && env->start_obs_out && T > env->start_obs_steps)
-        return fail("%s: T = %d exceeds the %d steps the start-observation buffer holds (uavtrack_set_start_obs_output)", who, T, env->start_obs_steps);
-    StepParams p = env->base;
-    p.actions = actions;
-    p.tpos = env->tpos;
-    p.start_obs = pol.auto_reset ? env->start_obs_out : nullptr;
-    p.raw = env->raw_out;
-    p.state_copy = env->state_copy_out;
-    p.obs = obs; p.reward = reward; p.terms = terms; p.nbrec = nullptr;
-    p.covered = covered; p.done = done; p.ep_sums = ep_sums;
-    p.pairs = nullptr; p.pair_count = nullptr; p.pair_total = nullptr;
-    p.ep_accumulate = accumulate ? 1 : 0;
-    p.actions_out = pol.actions_out;
-    p.env_offset = env->cfg.env_offset;
-    p.auto_reset = pol.auto_reset ? kAutoResetOn : 0;
-    p.reset_k0 = (uint32_t)pol.reset_seed; p.reset_k1 = (uint32_t)(pol.reset_seed >> 32);
-    p.greedy_k0 = (uint32_t)pol.seed; p.greedy_k1 = (uint32_t)(pol.seed >> 32);
-    if (pol.policy == kPolicyActor) {
-        p.obs_in = pol.obs_in; p.actor_w = env->actor_w; p.actor_hblocks = actor_blocks(env->actor_hidden);
-        p.actor_mode = pol.mode;
-    }
-    if (env->cfg.reward_mode != UAVTRACK_REWARD_PMI) {
-        p.T = T;
-        HIP_TRY(timed_launch(env, UAVTRACK_PROF_ROLLOUT, st, [&] { return launch_rollout(env, p, st, pol.policy); }));
-        return 0;
-    }
     // MAAC-R.  Rewards never feed back into the dynamics, so scoring is deferred: a chunk of steps is
     // simulated by ONE fused launch (observations, raw rewards, poses, and the neighbour pairs of every
     // step of the chunk), then ONE launch of the MFMA scorer over all those pairs, then ONE launch of the
     // softmax mix.  T = 1 (closed loop) is a chunk of one.  Everything is stream-ordered.
-    if (!env->pmi.blob) return fail("%s: reward_mode PMI needs uavtrack_set_pmi_weights first", who);
-    if (ensure_pmi_scratch(env, T, st)) return 1;
-    const uavtrack_config &c = env->cfg;
-    const size_t BN = (size_t)c.n_envs * c.n_uav;
-    // episode sums: the three terms and the coverage are summed by the rollout kernel (registers, as in the other modes),
-    // the return by the mix stage (per-step means) and a one-lane-per-environment reduction over the chunk's steps
-    p.ep_sums = ep_sums;
-    p.nbrec = env->nbrec;
-    p.pairs = env->pairs;
-    p.pair_count = env->pair_count;      // zero: set at allocation, re-zeroed by the mix kernel
-    p.pair_total = env->pair_total;
-    bool add = accumulate;
-    for (int32_t t0 = 0; t0 < T; t0 += env->pmi_steps_cap) {
-        const int32_t n = (T - t0 < env->pmi_steps_cap) ? T - t0 : env->pmi_steps_cap;
-        float *obs_t = obs ? obs + (size_t)t0 * BN * UAVTRACK_OBS_DIM : env->obs_tmp;
-        float *terms_t = terms ? terms + (size_t)t0 * 3 * BN : nullptr;
-        float *reward_t = reward + (size_t)t0 * BN;
-        int32_t *covered_t = covered ? covered + (size_t)t0 * c.n_envs : nullptr;
-        p.T = n;
-        p.ep_accumulate = add ? 1 : 0;
-        p.actions = actions ? actions + (size_t)t0 * BN : nullptr;
-        p.actions_out = pol.actions_out ? pol.actions_out + (size_t)t0 * BN : nullptr;
-        p.obs = obs_t; p.reward = reward_t; p.terms = terms_t;
-        p.covered = covered_t;
-        p.done = done ? done + (size_t)t0 * c.n_envs : nullptr;
-        p.tpos = env->tpos ? env->tpos + (size_t)t0 * c.n_envs * c.m_targets : nullptr;
-        p.raw = env->raw_out ? env->raw_out + (size_t)t0 * BN : nullptr;
-        p.start_obs = (pol.auto_reset && env->start_obs_out) ? env->start_obs_out + (size_t)t0 * BN * UAVTRACK_OBS_DIM : nullptr;
-        if (pol.auto_reset && t0 > 0) p.auto_reset = kAutoResetContinued;   // (an actor's first input after a reset at the chunk's edge)
-        HIP_TRY(timed_launch(env, UAVTRACK_PROF_ROLLOUT, st, [&] { return launch_rollout(env, p, st, pol.policy); }));
+    // The other reward modes are the single chunk (0, T) without the scoring stages.
+    const bool pmi = env->cfg.reward_mode == UAVTRACK_REWARD_PMI;
+    if (pmi && ensure_pmi_scratch(env, q.T, st)) return 1;
+    const int32_t cap = pmi ? env->pmi_steps_cap : q.T;
+    const float *obs_in = q.obs_in;
+    bool add = q.accumulate;
+    for (int32_t t0 = 0; t0 < q.T; t0 += cap) {
+        const int32_t n = (q.T - t0 < cap) ? q.T - t0 : cap;
+        const StepParams p = rollout_params(env, q, t0, n, obs_in, add);
+        HIP_TRY(timed_launch(env, UAVTRACK_PROF_ROLLOUT, st, [&] { return launch_rollout(env, p, st, q.policy); }));
+        if (!pmi) continue;
         // the actor of the next chunk starts from this chunk's last observation (a lane reads its own row
         // once, at launch start, before it writes anything: the scratch buffer may be reused in place)
-        p.obs_in = obs_t + (size_t)(n - 1) * BN * UAVTRACK_OBS_DIM;
-        HIP_TRY(timed_launch(env, UAVTRACK_PROF_SCORER, st, [&] { return launch_pmi_score(env, obs_t, st); }));
-        HIP_TRY(timed_launch(env, UAVTRACK_PROF_MIX, st, [&] { return launch_pmi_finalize(env, n, reward_t, ep_sums ? env->rsum : nullptr, st); }));
-        if (ep_sums) {
-            HIP_TRY(timed_launch(env, UAVTRACK_PROF_EPSUMS, st, [&] { return launch_ep_reward(env, n, env->rsum, ep_sums, add, st); }));
+        obs_in = p.obs + (size_t)(n - 1) * env->cfg.n_envs * env->cfg.n_uav * UAVTRACK_OBS_DIM;
+        HIP_TRY(timed_launch(env, UAVTRACK_PROF_SCORER, st, [&] { return launch_pmi_score(env, p.obs, st); }));
+        HIP_TRY(timed_launch(env, UAVTRACK_PROF_MIX, st, [&] { return launch_pmi_finalize(env, n, p.reward, q.ep_sums ? env->rsum : nullptr, st); }));
+        if (q.ep_sums) {
+            HIP_TRY(timed_launch(env, UAVTRACK_PROF_EPSUMS, st, [&] { return launch_ep_reward(env, n, env->rsum, q.ep_sums, add, st); }));
             add = true;
         }
     }
@@ -946,42 +994,41 @@ static int run_steps(uavtrack_env *env, int32_t T, const int32_t *actions, float
 int uavtrack_step(uavtrack_env *env, const int32_t *actions, float *obs, float *reward, float *terms,
                   int32_t *covered, uint8_t *done, void *stream)
 {
-    return run_steps(env, 1, actions, obs, reward, terms, covered, done, nullptr, stream, "uavtrack_step");
+    RolloutCall q(__func__, env, 1, obs, reward, terms, covered, done, nullptr);
+    q.actions = actions;
+    return run_rollout(env, q, stream);
 }
 
 int uavtrack_step_accumulate(uavtrack_env *env, const int32_t *actions, float *obs, float *reward, float *terms,
                              int32_t *covered, uint8_t *done, float *ep_sums, void *stream)
 {
-    if (!ep_sums) return fail("uavtrack_step_accumulate: ep_sums is null");
-    return run_steps(env, 1, actions, obs, reward, terms, covered, done, ep_sums, stream,
-                     "uavtrack_step_accumulate", true);
+    RolloutCall q(__func__, env, 1, obs, reward, terms, covered, done, ep_sums);
+    q.actions = actions; q.accumulate = true;
+    return run_rollout(env, q, stream);
 }
 
 int uavtrack_step_many(uavtrack_env *env, int32_t T, const int32_t *actions, float *obs, float *reward,
                        float *terms, int32_t *covered, uint8_t *done, float *ep_sums, void *stream)
 {
-    return run_steps(env, T, actions, obs, reward, terms, covered, done, ep_sums, stream, "uavtrack_step_many");
+    RolloutCall q(__func__, env, T, obs, reward, terms, covered, done, ep_sums);
+    q.actions = actions;
+    return run_rollout(env, q, stream);
 }
 
 int uavtrack_step_many_autoreset(uavtrack_env *env, int32_t T, uint64_t reset_seed, const int32_t *actions, float *obs,
                                  float *reward, float *terms, int32_t *covered, uint8_t *done, float *ep_sums, void *stream)
 {
-    if (env && env->cfg.horizon < 1) return fail("uavtrack_step_many_autoreset: the configuration has no horizon (done never fires)");
-    PolicyArgs pol;
-    pol.auto_reset = true; pol.reset_seed = reset_seed;
-    return run_steps(env, T, actions, obs, reward, terms, covered, done, ep_sums, stream, "uavtrack_step_many_autoreset", false, pol);
+    RolloutCall q(__func__, env, T, obs, reward, terms, covered, done, ep_sums);
+    q.actions = actions; q.auto_reset = true; q.reset_seed = reset_seed;
+    return run_rollout(env, q, stream);
 }
 
 int uavtrack_run_greedy(uavtrack_env *env, int32_t T, uint64_t seed, int32_t *actions_out, float *obs, float *reward,
                         float *terms, int32_t *covered, uint8_t *done, float *ep_sums, void *stream)
 {
-    if (!env) return fail("uavtrack_run_greedy: null handle");
-    if (env->cfg.dim != 2) return fail("uavtrack_run_greedy: the reference baseline is planar (dim must be 2)");
-    if (env->cfg.reward_mode == UAVTRACK_REWARD_PMI)
-        return fail("uavtrack_run_greedy: the C-METHOD baseline runs with the MAAC / MAAC-G rewards (C-METHOD.yaml: cooperative 0)");
-    PolicyArgs pol;
-    pol.policy = kPolicyGreedy; pol.actions_out = actions_out; pol.seed = seed;
-    return run_steps(env, T, nullptr, obs, reward, terms, covered, done, ep_sums, stream, "uavtrack_run_greedy", false, pol);
+    RolloutCall q(__func__, env, T, obs, reward, terms, covered, done, ep_sums);
+    q.policy = kPolicyGreedy; q.actions_out = actions_out; q.seed = seed;
+    return run_rollout(env, q, stream);
 }
 
 int uavtrack_greedy_actions(uavtrack_env *env, uint64_t seed, int32_t *actions, void *stream)
@@ -1092,88 +1139,64 @@ int uavtrack_run_actor(uavtrack_env *env, int32_t T, uint64_t seed, int32_t mode
                        int32_t *actions_out, float *obs, float *reward, float *terms, int32_t *covered,
                        uint8_t *done, float *ep_sums, void *stream)
 {
-    if (!env) return fail("uavtrack_run_actor: null handle");
-    if (T < 1) return fail("uavtrack_run_actor: T must be >= 1 (got %d)", T);
-    if (!reward) return fail("uavtrack_run_actor: reward is null");
-    if (!obs_in) return fail("uavtrack_run_actor: obs_in is null (the observation the policy sees at the first step)");
-    if (!env->actor_w) return fail("uavtrack_run_actor: needs uavtrack_set_actor_weights first");
-    if (mode != UAVTRACK_ACTOR_SAMPLE && mode != UAVTRACK_ACTOR_ARGMAX)
-        return fail("uavtrack_run_actor: mode %d is neither UAVTRACK_ACTOR_SAMPLE nor UAVTRACK_ACTOR_ARGMAX", mode);
-    if (obs_in == obs && T > 1)
-        return fail("uavtrack_run_actor: obs_in must not alias obs when T > 1 (pass the previous launch's last rows, "
-                    "or a copy)");
-    PolicyArgs pol;
-    pol.policy = kPolicyActor; pol.obs_in = obs_in; pol.actions_out = actions_out; pol.seed = seed; pol.mode = mode;
-    return run_steps(env, T, nullptr, obs, reward, terms, covered, done, ep_sums, stream, "uavtrack_run_actor", false, pol);
+    RolloutCall q(__func__, env, T, obs, reward, terms, covered, done, ep_sums);
+    q.policy = kPolicyActor; q.obs_in = obs_in; q.actions_out = actions_out; q.seed = seed; q.mode = mode;
+    return run_rollout(env, q, stream);
 }
 
-// The fused policy rollouts with the automatic episode turnover: the checks of the parent call, then those of
-// uavtrack_step_many_autoreset.  Every (policy, mode, dim) the parents accept has a kernel variant with the turnover; what
-// they refuse (the greedy baseline in 3-D or under MAAC-R) is refused here by name.
+// The fused policy rollouts with the automatic episode turnover.  Every (policy, mode, dim) the plain calls accept has a
+// kernel variant with the turnover; what they refuse (the greedy baseline in 3-D or under MAAC-R) is refused here too.
 int uavtrack_run_actor_autoreset(uavtrack_env *env, int32_t T, uint64_t seed, uint64_t reset_seed, int32_t mode,
                                  const float *obs_in, int32_t *actions_out, float *obs, float *reward, float *terms,
                                  int32_t *covered, uint8_t *done, float *ep_sums, void *stream)
 {
-    const char *who = "uavtrack_run_actor_autoreset";
-    if (!env) return fail("%s: null handle", who);
-    if (env->cfg.horizon < 1) return fail("%s: the configuration has no horizon (done never fires)", who);
-    if (T < 1) return fail("%s: T must be >= 1 (got %d)", who, T);
-    if (!reward) return fail("%s: reward is null", who);
-    if (!obs_in) return fail("%s: obs_in is null (the observation the policy sees at the first step)", who);
-    if (!env->actor_w) return fail("%s: needs uavtrack_set_actor_weights first", who);
-    if (mode != UAVTRACK_ACTOR_SAMPLE && mode != UAVTRACK_ACTOR_ARGMAX)
-        return fail("%s: mode %d is neither UAVTRACK_ACTOR_SAMPLE nor UAVTRACK_ACTOR_ARGMAX", who, mode);
-    if (obs_in == obs && T > 1)
-        return fail("%s: obs_in must not alias obs when T > 1 (pass the previous launch's last rows, or a copy)", who);
-    PolicyArgs pol;
-    pol.policy = kPolicyActor; pol.obs_in = obs_in; pol.actions_out = actions_out; pol.seed = seed; pol.mode = mode;
-    pol.auto_reset = true; pol.reset_seed = reset_seed;
-    return run_steps(env, T, nullptr, obs, reward, terms, covered, done, ep_sums, stream, who, false, pol);
+    RolloutCall q(__func__, env, T, obs, reward, terms, covered, done, ep_sums);
+    q.policy = kPolicyActor; q.obs_in = obs_in; q.actions_out = actions_out; q.seed = seed; q.mode = mode;
+    q.auto_reset = true; q.reset_seed = reset_seed;
+    return run_rollout(env, q, stream);
 }
 
 int uavtrack_run_greedy_autoreset(uavtrack_env *env, int32_t T, uint64_t seed, uint64_t reset_seed, int32_t *actions_out,
                                   float *obs, float *reward, float *terms, int32_t *covered, uint8_t *done, float *ep_sums,
                                   void *stream)
 {
-    const char *who = "uavtrack_run_greedy_autoreset";
-    if (!env) return fail("%s: null handle", who);
-    if (env->cfg.dim != 2 || env->cfg.reward_mode == UAVTRACK_REWARD_PMI)
-        return fail("%s: no rollout kernel for the combination (policy greedy, reward mode %s, %d-D): the C-METHOD baseline "
-                    "is planar and runs with the MAAC / MAAC-G rewards", who,
-                    env->cfg.reward_mode == UAVTRACK_REWARD_PMI ? "MAAC-R" : env->cfg.reward_mode == UAVTRACK_REWARD_MEAN ? "MAAC-G" : "MAAC",
-                    env->cfg.dim);
-    if (env->cfg.horizon < 1) return fail("%s: the configuration has no horizon (done never fires)", who);
-    PolicyArgs pol;
-    pol.policy = kPolicyGreedy; pol.actions_out = actions_out; pol.seed = seed;
-    pol.auto_reset = true; pol.reset_seed = reset_seed;
-    return run_steps(env, T, nullptr, obs, reward, terms, covered, done, ep_sums, stream, who, false, pol);
+    RolloutCall q(__func__, env, T, obs, reward, terms, covered, done, ep_sums);
+    q.policy = kPolicyGreedy; q.actions_out = actions_out; q.seed = seed;
+    q.auto_reset = true; q.reset_seed = reset_seed;
+    return run_rollout(env, q, stream);
+}
+
+// The checks of the three optional-output setters; a null buffer switches the output off (capacity 0).
+static int accept_output(const char *fn, const uavtrack_env *env, const float *buf, int32_t &capacity_steps)
+{
+    if (!env) return fail("%s: null handle", fn);
+    if (buf && capacity_steps < 1) return fail("%s: capacity_steps must be >= 1 (got %d)", fn, capacity_steps);
+    if (!buf) capacity_steps = 0;
+    return 0;
 }
 
 int uavtrack_set_start_obs_output(uavtrack_env *env, float *start_obs, int32_t capacity_steps)
 {
-    if (!env) return fail("uavtrack_set_start_obs_output: null handle");
-    if (start_obs && capacity_steps < 1) return fail("uavtrack_set_start_obs_output: capacity_steps must be >= 1 (got %d)", capacity_steps);
+    if (accept_output(__func__, env, start_obs, capacity_steps)) return 1;
     if ((uintptr_t)start_obs & 15) return fail("uavtrack_set_start_obs_output: start_obs must be 16-byte aligned (rows are written as float4)");
     env->start_obs_out = start_obs;
-    env->start_obs_steps = start_obs ? capacity_steps : 0;
+    env->start_obs_steps = capacity_steps;
     return 0;
 }
 
 int uavtrack_set_target_trace(uavtrack_env *env, float *tpos, int32_t capacity_steps)
 {
-    if (!env) return fail("uavtrack_set_target_trace: null handle");
-    if (tpos && capacity_steps < 1) return fail("uavtrack_set_target_trace: capacity_steps must be >= 1 (got %d)", capacity_steps);
+    if (accept_output(__func__, env, tpos, capacity_steps)) return 1;
     env->tpos = reinterpret_cast<float2 *>(tpos);
-    env->tpos_steps = tpos ? capacity_steps : 0;
+    env->tpos_steps = capacity_steps;
     return 0;
 }
 
 int uavtrack_set_raw_reward_output(uavtrack_env *env, float *raw, int32_t capacity_steps)
 {
-    if (!env) return fail("uavtrack_set_raw_reward_output: null handle");
-    if (raw && capacity_steps < 1) return fail("uavtrack_set_raw_reward_output: capacity_steps must be >= 1 (got %d)", capacity_steps);
+    if (accept_output(__func__, env, raw, capacity_steps)) return 1;
     env->raw_out = raw;
-    env->raw_steps = raw ? capacity_steps : 0;
+    env->raw_steps = capacity_steps;
     return 0;
 }
 
@@ -1199,18 +1222,15 @@ int uavtrack_step_host(uavtrack_env *env, const int32_t *actions_host, uavtrack_
     uint32_t *hb = static_cast<uint32_t *>(env->host_blk), *db = static_cast<uint32_t *>(env->host_blk_dev);
     const size_t BN = (size_t)c.n_envs * c.n_uav;
     memcpy(hb + L.actions, actions_host, BN * 4);          // the kernel reads them through the mapping: no copy call
-    // the raw rewards are this call's own extra output; a buffer the caller installed comes back afterwards
-    float *const raw_was = env->raw_out;
-    const int32_t raw_steps_was = env->raw_steps;
-    env->raw_out = reinterpret_cast<float *>(db + L.raw); env->raw_steps = 1;
-    env->state_copy_out = reinterpret_cast<float *>(db + L.state);      // the rollout kernel leaves the state there itself
-    const int rc = run_steps(env, 1, reinterpret_cast<const int32_t *>(db + L.actions), reinterpret_cast<float *>(db + L.obs),
-                             reinterpret_cast<float *>(db + L.reward), reinterpret_cast<float *>(db + L.terms),
-                             reinterpret_cast<int32_t *>(db + L.covered), reinterpret_cast<uint8_t *>(db + L.done), nullptr, stream,
-                             "uavtrack_step_host");
-    env->raw_out = raw_was; env->raw_steps = raw_steps_was;
-    env->state_copy_out = nullptr;
-    if (rc) return rc;
+    RolloutCall q(__func__, env, 1, reinterpret_cast<float *>(db + L.obs), reinterpret_cast<float *>(db + L.reward),
+                  reinterpret_cast<float *>(db + L.terms), reinterpret_cast<int32_t *>(db + L.covered),
+                  reinterpret_cast<uint8_t *>(db + L.done), nullptr);
+    q.actions = reinterpret_cast<const int32_t *>(db + L.actions);
+    // the raw rewards are this call's own extra output, whatever buffer the caller has installed; the rollout kernel
+    // leaves the state in the block itself
+    q.raw = reinterpret_cast<float *>(db + L.raw); q.raw_steps = 1;
+    q.state_copy = reinterpret_cast<float *>(db + L.state);
+    if (run_rollout(env, q, stream)) return 1;
     HIP_TRY(hipStreamSynchronize(st));
     const float *hf = reinterpret_cast<const float *>(hb);
     const StateBlock sv = state_view(const_cast<float *>(hf + L.state), c.n_envs, c.n_uav, c.m_targets, c.dim == 3);

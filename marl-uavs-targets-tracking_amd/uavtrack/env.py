@@ -4,6 +4,7 @@ write them in place on torch's current stream (no host sync, no copies)."""
 from __future__ import annotations
 
 import ctypes as C
+import functools
 from typing import Dict, Optional
 
 import numpy as np
@@ -17,6 +18,27 @@ from ._lib import ptr as _ptr
 from .pmi_trainer import DevicePMINetwork
 
 _STATE_KEYS = ("ux", "uy", "uz", "uh", "ua", "tx", "ty", "tz", "th")
+
+# every output of a rollout call: result key -> (shape of a T-step launch on B x N UAVs and M targets, dtype)
+_OUTPUTS = {
+    "actions": (lambda T, B, N, M: (T, B, N), torch.int32),
+    "obs": (lambda T, B, N, M: (T, B, N, _lib.OBS_DIM), torch.float32),
+    "reward": (lambda T, B, N, M: (T, B, N), torch.float32),
+    "terms": (lambda T, B, N, M: (T, 3, B, N), torch.float32),
+    "covered": (lambda T, B, N, M: (T, B), torch.int32),
+    "done": (lambda T, B, N, M: (T, B), torch.uint8),
+    "ep_sums": (lambda T, B, N, M: (B, 5), torch.float32),
+    "targets": (lambda T, B, N, M: (T, B, M, 2), torch.float32),
+    "raw": (lambda T, B, N, M: (T, B, N), torch.float32),
+    "start_obs": (lambda T, B, N, M: (T, B, N, _lib.OBS_DIM), torch.float32),
+}
+# the outputs a handle has installed rather than passed per call: result key -> (attribute that keeps the installed
+# tensor alive, the ABI setter, what error messages call the buffer)
+_INSTALLED = {
+    "targets": ("_trace", "uavtrack_set_target_trace", "target trace"),
+    "raw": ("_raw", "uavtrack_set_raw_reward_output", "raw-reward buffer"),
+    "start_obs": ("_start_obs", "uavtrack_set_start_obs_output", "start-observation buffer"),
+}
 
 
 class BatchedUavEnv(Handle):
@@ -60,13 +82,40 @@ class BatchedUavEnv(Handle):
         return (t is not None and tuple(t.shape) == tuple(shape) and t.dtype == dtype and t.device == self.device
                 and t.is_contiguous())
 
-    def _reuse(self, o, key, shape, dtype, want=True):
+    def _shape(self, key, T):
+        shape, dtype = _OUTPUTS[key]
+        return shape(T, self.B, self.N, self.M), dtype
+
+    def _reuse(self, o, key, T, want=True):
         """Output buffer `key` of a previous result `o` if it has exactly the shape this launch writes, else a
         fresh one (a kernel writing T2 rows into a T1-row buffer would corrupt device memory)."""
         if not want:
             return None
         t = o.get(key) if o else None
-        return t if self._fits(t, shape, dtype) else self._empty(shape, dtype)
+        return t if self._fits(t, *self._shape(key, T)) else self._empty(*self._shape(key, T))
+
+    def _check_out(self, out, keys, T):
+        """The caller's buffers of a bound call: each one present fits what the launch writes, and reward is there."""
+        for k in keys:
+            if out.get(k) is not None and not self._fits(out[k], *self._shape(k, T)):
+                shape, dtype = self._shape(k, T)
+                raise ValueError(f"out[{k!r}] must be a contiguous {dtype} {shape} tensor on {self.device}")
+        if out.get("reward") is None:
+            raise ValueError("out['reward'] is required")
+
+    def _rollout_call(self, entry, T, t, seed=0, mode=0, auto_reset_seed=None):
+        """(ctypes function, its argument tuple, its name in error messages) of uavtrack_<entry>[_autoreset] on the stream
+        current now.  entry: "step_many", "run_greedy" or "run_actor"; t: the tensors by result key ("actions" is the
+        input of step_many and an output of the other two; "obs_in" for the actor), None or missing for a null pointer."""
+        name = f"uavtrack_{entry}" + ("_autoreset" if auto_reset_seed is not None else "")
+        u64 = lambda v: C.c_uint64(v & (2 ** 64 - 1))
+        args = (self._h, C.c_int32(T)) + ((u64(seed),) if entry != "step_many" else ())
+        if auto_reset_seed is not None:
+            args += (u64(auto_reset_seed),)
+        if entry == "run_actor":
+            args += (C.c_int32(mode), _ptr(t["obs_in"]))
+        args += tuple(_ptr(t.get(k)) for k in ("actions", "obs", "reward", "terms", "covered", "done", "ep_sums"))
+        return getattr(self._lib, name), args + (self._stream(),), name
 
     def _out_arg(self, t, shape, dtype, name):
         if t is None:
@@ -106,15 +155,8 @@ class BatchedUavEnv(Handle):
         this step's contribution to (train.py:181-192).  `out_obs` / `out_reward`: caller-owned
         buffers the kernel writes instead of fresh tensors (static graph I/O)."""
         a = self._actions(actions, (self.B, self.N))
-
-        def take(buf, shape):
-            if buf is None:
-                return self._empty(shape, torch.float32)
-            if tuple(buf.shape) != shape or buf.dtype != torch.float32 or not buf.is_contiguous() or buf.device != self.device:
-                raise ValueError(f"output buffer must be a contiguous float32 {shape} tensor on {self.device}")
-            return buf
-        obs = take(out_obs, (self.B, self.N, _lib.OBS_DIM))
-        reward = take(out_reward, (self.B, self.N))
+        obs = self._out_arg(out_obs, (self.B, self.N, _lib.OBS_DIM), torch.float32, "out_obs")
+        reward = self._out_arg(out_reward, (self.B, self.N), torch.float32, "out_reward")
         terms = self._empty((3, self.B, self.N), torch.float32) if want_terms else None
         covered = self._empty((self.B,), torch.int32)
         done = self._empty((self.B,), torch.uint8)
@@ -132,71 +174,47 @@ class BatchedUavEnv(Handle):
             self.info["raw"] = self._raw[0]       # uav.raw_reward of this step (set_raw_output)
         return obs, reward, done.bool()
 
+    def _set_output(self, kind: str, buf: Optional[torch.Tensor]) -> None:
+        attr, setter, what = _INSTALLED[kind]
+        steps = 0
+        if buf is not None:
+            steps = buf.shape[0] if buf.dim() else 0
+            shape, dtype = self._shape(kind, steps)
+            if not self._fits(buf, shape, dtype):
+                raise ValueError(f"{what} must be a contiguous float32 [T, {', '.join(map(str, shape[1:]))}] tensor on {self.device}")
+        _lib.check(getattr(self._lib, setter)(self._h, _ptr(buf), C.c_int32(steps)), setter)
+        setattr(self, attr, buf)      # every later launch writes through the raw pointer: the tensor must outlive them
+
     def set_target_trace(self, buf: Optional[torch.Tensor]) -> None:
         """Target positions after each step, [T, B, M, 2] (environment.py:150-153), written by every later stepping
         call until replaced; None switches the output off."""
-        if buf is None:
-            _lib.check(self._lib.uavtrack_set_target_trace(self._h, None, 0), "uavtrack_set_target_trace")
-            self._trace = None
-            return
-        if buf.dim() != 4 or not self._fits(buf, (buf.shape[0], self.B, self.M, 2), torch.float32):
-            raise ValueError(f"target trace must be a contiguous float32 [T, {self.B}, {self.M}, 2] tensor on {self.device}")
-        _lib.check(self._lib.uavtrack_set_target_trace(self._h, _ptr(buf), C.c_int32(buf.shape[0])), "uavtrack_set_target_trace")
-        self._trace = buf     # every later launch writes through the raw pointer: the tensor must outlive them
+        self._set_output("targets", buf)
 
     def set_raw_output(self, buf: Optional[torch.Tensor]) -> None:
         """uav.raw_reward of every UAV after each step, [T, B, N] (environment.py:219: the weighted sum of the three
         normalised terms before any cooperative sharing), written by every later stepping call until replaced; None
         switches the output off."""
-        if buf is None:
-            _lib.check(self._lib.uavtrack_set_raw_reward_output(self._h, None, 0), "uavtrack_set_raw_reward_output")
-            self._raw = None
-            return
-        if buf.dim() != 3 or not self._fits(buf, (buf.shape[0], self.B, self.N), torch.float32):
-            raise ValueError(f"raw-reward buffer must be a contiguous float32 [T, {self.B}, {self.N}] tensor on {self.device}")
-        _lib.check(self._lib.uavtrack_set_raw_reward_output(self._h, _ptr(buf), C.c_int32(buf.shape[0])),
-                   "uavtrack_set_raw_reward_output")
-        self._raw = buf       # (kept alive: the library holds its raw pointer)
-
-    def _with_raw(self, T: int, want: bool, o, launch):
-        """Run `launch()` with a [T, B, N] raw-reward buffer attached when asked; returns it (or None)."""
-        if not want:
-            return launch(), None
-        rb = self._reuse(o, "raw", (T, self.B, self.N), torch.float32)
-        installed = self._raw
-        self.set_raw_output(rb)
-        try:
-            return launch(), rb
-        finally:
-            self.set_raw_output(installed)
+        self._set_output("raw", buf)
 
     def set_start_obs_output(self, buf: Optional[torch.Tensor]) -> None:
         """Observation of the fresh state behind every in-launch reset, [T, B, N, 12]: row (t, b) is written where
         done[t, b] fired in an automatic-reset launch (what the policy sees at step t + 1) and left untouched elsewhere;
         launches without the automatic reset never write it.  None switches the output off."""
-        if buf is None:
-            _lib.check(self._lib.uavtrack_set_start_obs_output(self._h, None, 0), "uavtrack_set_start_obs_output")
-            self._start_obs = None
-            return
-        if buf.dim() != 4 or not self._fits(buf, (buf.shape[0], self.B, self.N, _lib.OBS_DIM), torch.float32):
-            raise ValueError(f"start-observation buffer must be a contiguous float32 [T, {self.B}, {self.N}, {_lib.OBS_DIM}] "
-                             f"tensor on {self.device}")
-        _lib.check(self._lib.uavtrack_set_start_obs_output(self._h, _ptr(buf), C.c_int32(buf.shape[0])),
-                   "uavtrack_set_start_obs_output")
-        self._start_obs = buf       # (kept alive: the library holds its raw pointer)
+        self._set_output("start_obs", buf)
 
-    def _with_start_obs(self, T: int, want: bool, o, launch):
-        """Run `launch()` with a [T, B, N, 12] start-observation buffer attached when asked; returns (launch's result,
-        the buffer or None).  A buffer the caller installed earlier comes back afterwards."""
+    def _attached(self, kind: str, T: int, want: bool, o, launch) -> Dict[str, torch.Tensor]:
+        """Run `launch()` with a T-step buffer of `kind` installed when asked (reused from `o` if it fits); a buffer the
+        caller installed earlier comes back afterwards.  Returns the buffers attached to the launch by result key:
+        launch's own (a nested _attached) and this one."""
         if not want:
-            return launch(), None
-        so = self._reuse(o, "start_obs", (T, self.B, self.N, _lib.OBS_DIM), torch.float32)
-        installed = self._start_obs
-        self.set_start_obs_output(so)
+            return launch() or {}
+        buf = self._reuse(o, kind, T)
+        installed = getattr(self, _INSTALLED[kind][0])
+        self._set_output(kind, buf)
         try:
-            return launch(), so
+            return {**(launch() or {}), kind: buf}
         finally:
-            self.set_start_obs_output(installed)
+            self._set_output(kind, installed)
 
     def _count_episodes(self, T: int, auto_reset_seed) -> None:
         if auto_reset_seed is not None and self.cfg.horizon > 0:
@@ -230,20 +248,6 @@ class BatchedUavEnv(Handle):
             self._host_views = {k: view(getattr(hs, k), shape, ct, dt) for k, (shape, (ct, dt)) in spec.items()}
         return self._host_views
 
-    def _with_targets(self, T: int, want: bool, o, launch):
-        """Run `launch()` with a [T, B, M, 2] target trace attached when asked; returns the trace (or None)."""
-        if not want:
-            launch()
-            return None
-        tp = self._reuse(o, "targets", (T, self.B, self.M, 2), torch.float32)
-        installed = self._trace            # a trace the caller set up earlier comes back afterwards
-        self.set_target_trace(tp)
-        try:
-            launch()
-        finally:
-            self.set_target_trace(installed)
-        return tp
-
     def step_many(self, actions, want_obs: bool = True, want_terms: bool = True, want_ep_sums: bool = True,
                   out: Optional[Dict[str, torch.Tensor]] = None, want_targets: bool = False,
                   auto_reset_seed: Optional[int] = None, want_raw: bool = False) -> Dict[str, torch.Tensor]:
@@ -255,33 +259,21 @@ class BatchedUavEnv(Handle):
         a = torch.as_tensor(actions)
         T = int(a.shape[0])
         a = self._actions(a, (T, self.B, self.N))
+        return self._eager("step_many", T, out, dict(obs=want_obs, reward=True, terms=want_terms, covered=True, done=True,
+                                                     ep_sums=want_ep_sums), dict(targets=want_targets, raw=want_raw),
+                           dict(actions=a), auto_reset_seed=auto_reset_seed)
+
+    def _eager(self, entry, T, out, want, attach, given, seed=0, mode=0, auto_reset_seed=None) -> Dict[str, torch.Tensor]:
+        """step_many / run_greedy / run_actor: the wanted buffers (reused from `out` where they fit) and the `given`
+        inputs, one launch with the `attach`ed installed outputs around it, the result dictionary."""
         o = out or {}
-
-        def buf(key, shape, dtype, want=True):
-            return self._reuse(o, key, shape, dtype, want)
-
-        obs = buf("obs", (T, self.B, self.N, _lib.OBS_DIM), torch.float32, want_obs)
-        reward = buf("reward", (T, self.B, self.N), torch.float32)
-        terms = buf("terms", (T, 3, self.B, self.N), torch.float32, want_terms)
-        covered = buf("covered", (T, self.B), torch.int32)
-        done = buf("done", (T, self.B), torch.uint8)
-        ep = buf("ep_sums", (self.B, 5), torch.float32, want_ep_sums)
-        if auto_reset_seed is None:
-            launch = lambda: _lib.check(
-                self._lib.uavtrack_step_many(self._h, C.c_int32(T), _ptr(a), _ptr(obs), _ptr(reward), _ptr(terms), _ptr(covered),
-                                             _ptr(done), _ptr(ep), self._stream()), "uavtrack_step_many")
-        else:
-            launch = lambda: _lib.check(
-                self._lib.uavtrack_step_many_autoreset(self._h, C.c_int32(T), C.c_uint64(auto_reset_seed & (2 ** 64 - 1)), _ptr(a),
-                                                       _ptr(obs), _ptr(reward), _ptr(terms), _ptr(covered), _ptr(done), _ptr(ep),
-                                                       self._stream()), "uavtrack_step_many_autoreset")
-        tp, rb = self._with_raw(T, want_raw, o, lambda: self._with_targets(T, want_targets, o, launch))
+        res = {k: self._reuse(o, k, T, w) for k, w in want.items()}
+        fn, args, name = self._rollout_call(entry, T, {**res, **given}, seed, mode, auto_reset_seed)
+        launch = lambda: _lib.check(fn(*args), name)
+        for kind, w in attach.items():
+            launch = functools.partial(self._attached, kind, T, w, o, launch)
+        res.update(launch() or {})
         self._count_episodes(T, auto_reset_seed)
-        res = dict(obs=obs, reward=reward, terms=terms, covered=covered, done=done, ep_sums=ep)
-        if tp is not None:
-            res["targets"] = tp
-        if rb is not None:
-            res["raw"] = rb          # uav.raw_reward per step (environment.py:219)
         return res
 
     def bind_step_many(self, actions: torch.Tensor, out: Dict[str, torch.Tensor]):
@@ -290,21 +282,13 @@ class BatchedUavEnv(Handle):
         slicing, dict building: tens of microseconds) would be a visible share of a short launch."""
         T = int(actions.shape[0])
         a = self._actions(actions, (T, self.B, self.N))
-        shapes = dict(obs=((T, self.B, self.N, _lib.OBS_DIM), torch.float32), reward=((T, self.B, self.N), torch.float32),
-                      terms=((T, 3, self.B, self.N), torch.float32), covered=((T, self.B), torch.int32),
-                      done=((T, self.B), torch.uint8), ep_sums=((self.B, 5), torch.float32))
-        for k, (shape, dtype) in shapes.items():
-            if out.get(k) is not None and not self._fits(out[k], shape, dtype):
-                raise ValueError(f"out[{k!r}] must be a contiguous {dtype} {shape} tensor on {self.device}")
-        if out.get("reward") is None:
-            raise ValueError("out['reward'] is required")
-        args = (self._h, C.c_int32(T), _ptr(a), _ptr(out.get("obs")), _ptr(out["reward"]), _ptr(out.get("terms")),
-                _ptr(out.get("covered")), _ptr(out.get("done")), _ptr(out.get("ep_sums")), self._stream())
-        fn, keep = self._lib.uavtrack_step_many, (a, out)
+        self._check_out(out, ("obs", "reward", "terms", "covered", "done", "ep_sums"), T)
+        fn, args, name = self._rollout_call("step_many", T, dict(out, actions=a))
+        keep = (a, out)
 
         def call():
             if fn(*args) != 0:
-                _lib.check(1, "uavtrack_step_many")
+                _lib.check(1, name)
             return keep[1]
         return call
 
@@ -486,32 +470,9 @@ class BatchedUavEnv(Handle):
                    want_start_obs: bool = False) -> Dict[str, torch.Tensor]:
         """T closed-loop steps of the C-METHOD baseline (train.py:326-370) in one launch.  Pass a previous result as
         `out` to reuse its buffers.  auto_reset_seed / want_start_obs: as run_actor."""
-        o = out or {}
-        s64 = C.c_uint64(seed & (2 ** 64 - 1))
-
-        def buf(key, shape, dtype, want=True):
-            return self._reuse(o, key, shape, dtype, want)
-        acts = buf("actions", (T, self.B, self.N), torch.int32, want_actions)
-        obs = buf("obs", (T, self.B, self.N, _lib.OBS_DIM), torch.float32, want_obs)
-        reward = buf("reward", (T, self.B, self.N), torch.float32)
-        terms = buf("terms", (T, 3, self.B, self.N), torch.float32, want_terms)
-        covered = buf("covered", (T, self.B), torch.int32)
-        done = buf("done", (T, self.B), torch.uint8)
-        ep = buf("ep_sums", (self.B, 5), torch.float32)
-        tail = (_ptr(acts), _ptr(obs), _ptr(reward), _ptr(terms), _ptr(covered), _ptr(done), _ptr(ep), self._stream())
-        if auto_reset_seed is None:
-            launch = lambda: _lib.check(self._lib.uavtrack_run_greedy(self._h, C.c_int32(T), s64, *tail), "uavtrack_run_greedy")
-        else:
-            launch = lambda: _lib.check(self._lib.uavtrack_run_greedy_autoreset(
-                self._h, C.c_int32(T), s64, C.c_uint64(auto_reset_seed & (2 ** 64 - 1)), *tail), "uavtrack_run_greedy_autoreset")
-        tp, so = self._with_start_obs(T, want_start_obs, o, lambda: self._with_targets(T, want_targets, o, launch))
-        self._count_episodes(T, auto_reset_seed)
-        res = dict(actions=acts, obs=obs, reward=reward, terms=terms, covered=covered, done=done, ep_sums=ep)
-        if so is not None:
-            res["start_obs"] = so
-        if tp is not None:
-            res["targets"] = tp
-        return res
+        return self._eager("run_greedy", T, out, dict(actions=want_actions, obs=want_obs, reward=True, terms=want_terms,
+                                                      covered=True, done=True, ep_sums=True),
+                           dict(targets=want_targets, start_obs=want_start_obs), {}, seed, 0, auto_reset_seed)
 
     # ---- the learner's shared actor on the device (actor_critic.py:85-98, 138-148) ----
     def set_actor(self, actor) -> None:
@@ -599,33 +560,9 @@ class BatchedUavEnv(Handle):
         if obs_in.shape != (self.B, self.N, _lib.OBS_DIM) or obs_in.dtype != torch.float32 \
                 or not obs_in.is_contiguous() or obs_in.device != self.device:
             raise ValueError(f"obs_in must be a contiguous float32 [{self.B}, {self.N}, {_lib.OBS_DIM}] tensor on {self.device}")
-        o = out or {}
-
-        def buf(key, shape, dtype, want=True):
-            return self._reuse(o, key, shape, dtype, want)
-        acts = buf("actions", (T, self.B, self.N), torch.int32)
-        obs = buf("obs", (T, self.B, self.N, _lib.OBS_DIM), torch.float32)
-        reward = buf("reward", (T, self.B, self.N), torch.float32)
-        terms = buf("terms", (T, 3, self.B, self.N), torch.float32, want_terms)
-        covered = buf("covered", (T, self.B), torch.int32)
-        done = buf("done", (T, self.B), torch.uint8)
-        ep = buf("ep_sums", (self.B, 5), torch.float32)
-        s64 = C.c_uint64(seed & (2 ** 64 - 1))
-        tail = (C.c_int32(mode), _ptr(obs_in), _ptr(acts), _ptr(obs), _ptr(reward), _ptr(terms), _ptr(covered), _ptr(done),
-                _ptr(ep), self._stream())
-        if auto_reset_seed is None:
-            launch = lambda: _lib.check(self._lib.uavtrack_run_actor(self._h, C.c_int32(T), s64, *tail), "uavtrack_run_actor")
-        else:
-            launch = lambda: _lib.check(self._lib.uavtrack_run_actor_autoreset(
-                self._h, C.c_int32(T), s64, C.c_uint64(auto_reset_seed & (2 ** 64 - 1)), *tail), "uavtrack_run_actor_autoreset")
-        tp, so = self._with_start_obs(T, want_start_obs, o, lambda: self._with_targets(T, want_targets, o, launch))
-        self._count_episodes(T, auto_reset_seed)
-        res = dict(actions=acts, obs=obs, reward=reward, terms=terms, covered=covered, done=done, ep_sums=ep)
-        if so is not None:
-            res["start_obs"] = so
-        if tp is not None:
-            res["targets"] = tp
-        return res
+        return self._eager("run_actor", T, out, dict(actions=True, obs=True, reward=True, terms=want_terms, covered=True,
+                                                     done=True, ep_sums=True),
+                           dict(targets=want_targets, start_obs=want_start_obs), dict(obs_in=obs_in), seed, mode, auto_reset_seed)
 
     def bind_run(self, T: int, out: Dict[str, torch.Tensor], policy: str = "actor", obs_in: Optional[torch.Tensor] = None,
                  seed: int = 0, mode: int = _lib.ACTOR_SAMPLE, auto_reset_seed: Optional[int] = None,
@@ -636,31 +573,15 @@ class BatchedUavEnv(Handle):
         auto_reset_seed: the automatic-reset forms of the two calls (the host episode counter advances per call, as in
         run_actor).  want_start_obs: out["start_obs"] [T, B, N, 12] (allocated when missing) is installed as the
         start-observation buffer now and stays installed."""
-        shapes = dict(actions=((T, self.B, self.N), torch.int32), obs=((T, self.B, self.N, _lib.OBS_DIM), torch.float32),
-                      reward=((T, self.B, self.N), torch.float32), terms=((T, 3, self.B, self.N), torch.float32),
-                      covered=((T, self.B), torch.int32), done=((T, self.B), torch.uint8), ep_sums=((self.B, 5), torch.float32))
-        for k, (shape, dtype) in shapes.items():
-            if out.get(k) is not None and not self._fits(out[k], shape, dtype):
-                raise ValueError(f"out[{k!r}] must be a contiguous {dtype} {shape} tensor on {self.device}")
-        if out.get("reward") is None:
-            raise ValueError("out['reward'] is required")
-        tail = (_ptr(out.get("actions")), _ptr(out.get("obs")), _ptr(out["reward"]), _ptr(out.get("terms")), _ptr(out.get("covered")),
-                _ptr(out.get("done")), _ptr(out.get("ep_sums")), self._stream())
-        s64 = C.c_uint64(seed & (2 ** 64 - 1))
+        self._check_out(out, ("actions", "obs", "reward", "terms", "covered", "done", "ep_sums"), T)
         if policy not in ("actor", "greedy"):
             raise ValueError("policy must be 'actor' or 'greedy'")
+        if policy == "actor" and not self._fits(obs_in, (self.B, self.N, _lib.OBS_DIM), torch.float32):
+            raise ValueError("obs_in must be a contiguous float32 [B, N, 12] tensor on this device")
         if want_start_obs:
-            out["start_obs"] = self._reuse(out, "start_obs", (T, self.B, self.N, _lib.OBS_DIM), torch.float32)
+            out["start_obs"] = self._reuse(out, "start_obs", T)
             self.set_start_obs_output(out["start_obs"])
-        name = f"uavtrack_run_{policy}" + ("_autoreset" if auto_reset_seed is not None else "")
-        fn = getattr(self._lib, name)
-        head = (self._h, C.c_int32(T), s64) + ((C.c_uint64(auto_reset_seed & (2 ** 64 - 1)),) if auto_reset_seed is not None else ())
-        if policy == "actor":
-            if not self._fits(obs_in, (self.B, self.N, _lib.OBS_DIM), torch.float32):
-                raise ValueError("obs_in must be a contiguous float32 [B, N, 12] tensor on this device")
-            args = head + (C.c_int32(mode), _ptr(obs_in)) + tail
-        else:
-            args = head + tail
+        fn, args, name = self._rollout_call(f"run_{policy}", T, dict(out, obs_in=obs_in), seed, mode, auto_reset_seed)
         keep = (out, obs_in)
 
         def call():

@@ -67,11 +67,11 @@ def make_env(case, pmi_sd, **kw):
     return env
 
 
-def stagger(env):
-    """reset(3, episode 5), then step counts b % H; returns the reset's observation (what the policy sees first)."""
+def stagger(env, h=H):
+    """reset(3, episode 5), then step counts b % h; returns the reset's observation (what the policy sees first)."""
     obs = env.reset(seed=3, episode=EP0)
     st = env.get_state()
-    st["step_count"] = torch.arange(env.B, dtype=torch.int32, device=DEV) % H
+    st["step_count"] = torch.arange(env.B, dtype=torch.int32, device=DEV) % h
     env.set_state(**st)
     return obs
 
@@ -423,3 +423,55 @@ def test_refusals_enqueue_nothing(pmi_state_dict):
         env = make_env(("greedy", 5, 3, mode, dim, 0), pmi_state_dict)
         env.reset(seed=1)
         refused(env, match, lambda e, out: e.run_greedy(T, auto_reset_seed=RESET, out=out))
+
+
+def test_chunked_maacr_launch_equals_the_single_chunk(pmi_state_dict, monkeypatch):
+    """Test 8.  An automatic-reset MAAC-R launch split into several chunks (UAVTRACK_PMI_SCRATCH_MB=1: two to four steps
+    per chunk at 70 x 20 x 10) against the same launch in one chunk: run_actor with start_obs and the target trace,
+    step_many with the target trace and the raw rewards.  Horizon 5, T = 19, step counts b % 5: a done flag fires at every
+    step, chunk edges included.  Everything bitwise, the final state with it, but ep_sums: the chunks add their float
+    sums in another order (rtol = atol = 1e-6, as the chunked comparison of tests/test_hip_parity.py)."""
+    case, Hc, Tc = ("actor", 20, 10, "PMI", 2, 128), 5, 19
+    g = torch.Generator(DEV).manual_seed(4)
+    given = torch.randint(0, 12, (Tc, 70, 20), dtype=torch.int32, device=DEV, generator=g)
+
+    def play(scratch_mb):
+        # (the library reads the variable whenever it sizes the scratch: at set_pmi and at a launch longer than it holds)
+        if scratch_mb is None:
+            monkeypatch.delenv("UAVTRACK_PMI_SCRATCH_MB", raising=False)
+        else:
+            monkeypatch.setenv("UAVTRACK_PMI_SCRATCH_MB", str(scratch_mb))
+        env = make_env(case, pmi_state_dict, horizon=Hc, n_envs=70)
+        env.set_profiling(True)
+        res = []
+        for form in ("run_actor", "step_many"):
+            obs0 = stagger(env, Hc)
+            env.profile()
+            if form == "run_actor":
+                r = env.run_actor(Tc, obs0, seed=SEED, auto_reset_seed=RESET, want_start_obs=True, want_targets=True,
+                                  out=dict(start_obs=sentinel_start_obs(env, Tc)))
+            else:
+                r = env.step_many(given, auto_reset_seed=RESET, want_targets=True, want_raw=True)
+            launches = env.profile()["rollout"]["launches"]
+            res.append(({k: v.clone() for k, v in r.items()}, env.get_state(), launches))
+        env.close()
+        return res
+
+    chunked, whole = play(1), play(None)
+    keys = (("actions", "obs", "reward", "terms", "covered", "done", "start_obs", "targets", "ep_sums"),
+            ("obs", "reward", "terms", "covered", "done", "targets", "raw", "ep_sums"))
+    for form, (a, sa, la), (b, sb, lb), want_keys in zip(("run_actor", "step_many"), chunked, whole, keys):
+        assert la >= 3 and lb == 1, (form, la, lb)            # a chunk behind the second ran: kAutoResetContinued
+        assert set(a) == set(b) == set(want_keys), (form, sorted(a), sorted(b))
+        done = a["done"].bool()
+        assert bool(done.any(dim=1).all()), form               # a reset at every step of the launch
+        for k in want_keys:
+            if k == "ep_sums":
+                torch.testing.assert_close(a[k], b[k], rtol=1e-6, atol=1e-6, msg=lambda m: f"{form} ep_sums: {m}")
+            else:
+                assert torch.equal(a[k], b[k]), (form, k, (a[k] != b[k]).nonzero()[:4].tolist())
+        for k in sa:
+            assert torch.equal(sa[k], sb[k]), (form, k)
+        if form == "run_actor":
+            fired = done[:, :, None, None].expand_as(a["start_obs"])
+            assert bool((a["start_obs"][~fired] == SENTINEL).all()) and not bool((a["start_obs"][fired] == SENTINEL).any())
