@@ -159,8 +159,12 @@ def train_sharded(args, timings=None):
                                          loss=args.actor_loss, max_batch=per_shard)
     actor.load_state_dict(learner.actor_state_dict())
     rollouts = [uavtrack.BatchedRollout(e, actor, device_actor=True, seed=args.seed) for e in envs]
-    rings = [uavtrack.PrioritizedReplayRing(2 * e.cfg.n_envs * args.n_uav * args.steps, dev, alpha=args.alpha,
-                                            seed=args.seed + 7919 * k, max_batch=per_shard) for k, e in enumerate(envs)]
+    if args.replay == "prioritized":
+        rings = [uavtrack.PrioritizedReplayRing(2 * e.cfg.n_envs * args.n_uav * args.steps, dev, alpha=args.alpha,
+                                                seed=args.seed + 7919 * k, max_batch=per_shard) for k, e in enumerate(envs)]
+    else:                                                             # uniform-device
+        rings = [uavtrack.ReplayRing(2 * e.cfg.n_envs * args.n_uav * args.steps, dev, seed=args.seed + 7919 * k,
+                                     max_batch=per_shard) for k, e in enumerate(envs)]
     per_iter = args.envs * args.n_uav * args.steps
     stats = [uavtrack.EpisodeStats(e, log_capacity=e.cfg.n_envs * args.log_every, max_steps=args.steps) for e in envs]
     kept = {k: [] for k in SIX}
@@ -260,10 +264,12 @@ def main(argv=None, timings=None):
     ap.add_argument("--pmi-trainer", choices=["torch", "device"], default="torch",
                     help="--method maac-r only: torch: the PyTorch PMINetwork.train_pmi loop below; device: "
                          "uavtrack.DevicePMINetwork, the whole train_pmi call in one library call")
-    ap.add_argument("--replay", choices=["uniform", "prioritized"], default="uniform",
-                    help="uniform: DeviceReplayBuffer (random.sample, train.py:57); prioritized: uavtrack."
-                         "PrioritizedReplayRing (the reference's PrioritizedReplayBuffer, train.py:73-139), added to "
-                         "from the rollout and drawn from in HIP, |td_delta| written back as the new priorities")
+    ap.add_argument("--replay", choices=["uniform", "uniform-device", "prioritized"], default="uniform",
+                    help="uniform: DeviceReplayBuffer (random.sample, train.py:57); uniform-device: uavtrack.ReplayRing, "
+                         "the same buffer added to from the rollout and drawn from in HIP (distinct slots, O(batch)); "
+                         "prioritized: uavtrack.PrioritizedReplayRing (the reference's PrioritizedReplayBuffer, "
+                         "train.py:73-139), added to from the rollout and drawn from in HIP, |td_delta| written back as the "
+                         "new priorities")
     ap.add_argument("--alpha", type=float, default=0.6, help="--replay prioritized: priority exponent (train.py:74)")
     ap.add_argument("--beta", type=float, default=0.4, help="--replay prioritized: importance exponent (train.py:100)")
     ap.add_argument("--importance", action="store_true",
@@ -283,9 +289,9 @@ def main(argv=None, timings=None):
                          "host work); auto: cpu with --publish host, device with --publish device")
     ap.add_argument("--shards", type=int, default=1,
                     help="split --envs into K environment handles (uavtrack.shard_range: disjoint global environment "
-                         "ids), each with its own rollout and prioritised ring, and take every update of the ONE learner "
+                         "ids), each with its own rollout and device ring, and take every update of the ONE learner "
                          "from all K rings (DeviceActorCritic.update_from_many: one gradient row per ring, one apply); "
-                         "needs --learner device --replay prioritized; --method maac-r also needs --pmi-trainer device "
+                         "needs --learner device and --replay prioritized or uniform-device; --method maac-r also needs --pmi-trainer device "
                          "(DevicePMINetwork.train_pmi_many over the K observation histories, un-concatenated), and each "
                          "MAAC-R handle sizes its own scorer scratch")
     ap.add_argument("--log-every", type=int, default=1,
@@ -327,9 +333,9 @@ def main(argv=None, timings=None):
     if args.shards < 1 or args.shards > args.envs:
         ap.error("--shards must be in [1, --envs]")
     if args.shards > 1:
-        if args.learner != "device" or args.replay != "prioritized":
-            ap.error("--shards K > 1 needs --learner device --replay prioritized (one device learner updated from K "
-                     "prioritised rings)")
+        if args.learner != "device" or args.replay == "uniform":
+            ap.error("--shards K > 1 needs --learner device and --replay prioritized or uniform-device (one device "
+                     "learner updated from K device rings)")
         if args.method == "maac-r" and args.pmi_trainer != "device":
             ap.error("--shards K > 1 with --method maac-r needs --pmi-trainer device (one uavtrack.DevicePMINetwork "
                      "trained over the K observation histories: train_pmi_many)")
@@ -374,6 +380,8 @@ def main(argv=None, timings=None):
     if args.replay == "prioritized":
         replay = uavtrack.PrioritizedReplayRing(2 * per_iter, dev, alpha=args.alpha, seed=args.seed,
                                                 max_batch=args.batch)
+    elif args.replay == "uniform-device":
+        replay = uavtrack.ReplayRing(2 * per_iter, dev, seed=args.seed, max_batch=args.batch)
     else:
         replay = uavtrack.DeviceReplayBuffer(capacity=2 * per_iter, device=dev)
     stats = uavtrack.EpisodeStats(env, log_capacity=args.envs * K * args.log_every, max_steps=T)
@@ -392,7 +400,7 @@ def main(argv=None, timings=None):
         obs_in = rollout.obs.clone()
         res = rollout.run_fused(T, out=out, stats=stats)              # K * B episodes, one launch; done at the horizon closes them
         out = {k: v for k, v in res.items() if k != "ep_sums"}        # reuse the output buffers next time
-        if args.replay == "prioritized":
+        if args.replay != "uniform":
             replay.add_rollout(obs_in, res)                           # one library call, straight from the outputs
         else:
             replay.add(uavtrack.transitions_from_rollout(obs_in, res))

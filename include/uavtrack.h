@@ -714,7 +714,27 @@ int uavtrack_pmi_trainer_select(uavtrack_pmi_trainer *trainer, const uavtrack_pm
  * (train.py:106).  Sums are exact for integer weights below 2^53; otherwise a draw within rounding of a CDF boundary
  * may fall on either side of it.  The rule there: a draw that rounding sends to a lane (32 slots) or a tile (2048
  * slots) holding no w > 0, or past the last w > 0 of the lane or tile it was sent to, takes the last slot with w > 0
- * at or before that lane or tile.  So a draw never lands on a slot >= count or one with w = 0. */
+ * at or before that lane or tile.  So a draw never lands on a slot >= count or one with w = 0.
+ *
+ * A uniform ring.  The reference's other buffer, ReplayBuffer (train.py:41-70), is the same ring without priorities:
+ * ring->priorities == NULL.  The three adds then write the four stores alone, and the draw is
+ * uavtrack_replay_sample_uniform (random.sample, train.py:56-58: without replacement); the prioritised draws refuse such
+ * a ring.
+ *
+ * The uniform draw stream.  Draw j (0 <= j < n <= count) of call c -- the same device call counter as above: every
+ * sample call of either kind reads it and advances it by one -- is pi_c(j), pi_c applied again while the value is
+ * >= count.  pi_c is a bijection of [0, 2^b), b = the smallest even number >= 2 with 2^b >= count (so 2^b < 4 count from
+ * count = 2 on), h = b / 2: a balanced Feistel network of 16 rounds on x = L * 2^h + R,
+ *     (L, R) <- (R, L xor (fmix32((R + key_r) mod 2^32) mod 2^h))            for r = 0 .. 15, in this order
+ *     fmix32(x): x ^= x >> 16; x *= 0x85EBCA6B; x ^= x >> 13; x *= 0xC2B2AE35; x ^= x >> 16   (mod 2^32; murmur3's finaliser)
+ *     key_(4 i + w) = word w of Philox4x32-10(counter = (i, c mod 2^32, c >> 32, 0x554E4946 "UNIF"),
+ *                                             key = (seed mod 2^32, seed >> 32))                 for i = 0 .. 3
+ * and pi_c(x) = L * 2^h + R of the last round.  Word 3 differs from the three streams above.  The walk ends: it runs on
+ * the cycle of pi_c through j, which holds j < count itself.  No two draws meet: two walks that met would, pi_c being a
+ * bijection, have started from the same j.  So the n indices are distinct, and they are the first n entries, in order,
+ * of a permutation of [0, count) that depends on (seed, c, count) alone: n = count gives all of it, a smaller n its
+ * prefix.  Everything is integer arithmetic, so the indices are bitwise reproducible anywhere.  The expected number of
+ * applications of pi_c per draw is 2^b / count < 4. */
 typedef struct uavtrack_replay_config {
     uint32_t struct_size;       /* = sizeof(uavtrack_replay_config), ABI check */
     int32_t  device_id;         /* HIP device ordinal */
@@ -731,7 +751,7 @@ typedef struct uavtrack_replay_ring {
     int32_t *actions;           /* [capacity] */
     float   *rewards;           /* [capacity] */
     float   *next_states;       /* [capacity][12] */
-    float   *priorities;        /* [capacity] */
+    float   *priorities;        /* [capacity]; NULL: a uniform ring */
     int64_t  capacity;          /* in [1, max_capacity] */
     int64_t  pos;               /* in [0, capacity) */
     int64_t  count;             /* in [0, capacity] */
@@ -746,7 +766,9 @@ int uavtrack_replay_destroy(uavtrack_replay *replay);
  * rewards [n] (DEVICE).  Only the last min(n, capacity) are written, from slot (pos + max(0, n - capacity)) % capacity
  * on, wrapping; each gets the maximum of the whole priorities array as it stood before the call (1.0 when count == 0),
  * taken on the device.  Stream-ordered, no synchronisation, no allocation.  Returns an error, enqueuing nothing, for a
- * null pointer, n < 1, a ring outside the limits above, or a row array not 16-byte aligned. */
+ * null pointer, n < 1, a ring outside the limits above, or a row array not 16-byte aligned.  ring->priorities may be
+ * NULL (a uniform ring): the call then reads and writes no priority and writes the four stores exactly as otherwise;
+ * the same holds for the two rollout forms below. */
 int uavtrack_replay_add(uavtrack_replay *replay, const uavtrack_replay_ring *ring, int64_t n, const float *states,
                         const int32_t *actions, const float *rewards, const float *next_states, void *stream);
 
@@ -794,6 +816,16 @@ int uavtrack_replay_sample(uavtrack_replay *replay, const uavtrack_replay_ring *
 int uavtrack_replay_sample_annealed(uavtrack_replay *replay, const uavtrack_replay_ring *ring, int64_t n, double alpha,
                                     double beta0, double beta1, int64_t anneal_calls, int64_t *indices, float *weights,
                                     void *stream);
+
+/* ReplayBuffer.sample's draw (train.py:56-58, random.sample) without the gather: n DISTINCT slots of [0, count), in
+ * random order, into indices [n] (DEVICE int64) -- the uniform draw stream above.  Only ring->count (and the limits
+ * ring->capacity and ring->pos are checked against) is used; ring->priorities may be NULL.  The work is O(n) whatever
+ * the ring holds.  Stream-ordered, no synchronisation, no allocation, capturable; the call advances the handle's call
+ * counter as the prioritised draws do, so a replayed graph draws afresh.  Returns an error, enqueuing nothing and leaving
+ * the counter alone, for a null handle, ring or indices, n < 1 or n > max_batch, count < 1, n > count, count > capacity
+ * or capacity > max_capacity.  It reads no ring data, so nothing is refused on the device. */
+int uavtrack_replay_sample_uniform(uavtrack_replay *replay, const uavtrack_replay_ring *ring, int64_t n, int64_t *indices,
+                                   void *stream);
 
 /* Synchronises `stream`; fails if any sample call since the previous check was refused on the device (bad or all-zero
  * priorities).  refused (nullable) receives their number; the count restarts at 0. */

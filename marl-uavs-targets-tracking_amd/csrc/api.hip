@@ -1978,11 +1978,12 @@ namespace {
 
 bool aligned16(const void *p) { return ((uintptr_t)p & 15) == 0; }
 
-// The ring's pointers and host state against the handle's limits (`fn` names the ABI function in the message).
-int accept_ring(const uavtrack_replay *r, const char *fn, const uavtrack_replay_ring *ring, bool stores)
+// The ring's pointers and host state against the handle's limits (`fn` names the ABI function in the message).  The
+// adds need the stores and take a ring without priorities (a uniform ring); the prioritised draws need the priorities.
+int accept_ring(const uavtrack_replay *r, const char *fn, const uavtrack_replay_ring *ring, bool stores, bool priorities)
 {
     if (!ring) return fail("%s: ring is null", fn);
-    if (!ring->priorities) return fail("%s: ring->priorities is null", fn);
+    if (priorities && !ring->priorities) return fail("%s: ring->priorities is null", fn);
     if (stores && (!ring->states || !ring->actions || !ring->rewards || !ring->next_states))
         return fail("%s: the ring's states, actions, rewards and next_states must not be null", fn);
     if (stores && (!aligned16(ring->states) || !aligned16(ring->next_states)))
@@ -2035,7 +2036,7 @@ int uavtrack_replay_add(uavtrack_replay *replay, const uavtrack_replay_ring *rin
                         const int32_t *actions, const float *rewards, const float *next_states, void *stream)
 {
     if (!replay) return fail("uavtrack_replay_add: null handle");
-    if (accept_ring(replay, "uavtrack_replay_add", ring, true)) return 1;
+    if (accept_ring(replay, "uavtrack_replay_add", ring, true, false)) return 1;
     if (!states || !actions || !rewards || !next_states)
         return fail("uavtrack_replay_add: states, actions, rewards and next_states must not be null");
     if (!aligned16(states) || !aligned16(next_states))
@@ -2052,7 +2053,7 @@ int uavtrack_replay_add_rollout(uavtrack_replay *replay, const uavtrack_replay_r
                                 void *stream)
 {
     if (!replay) return fail("uavtrack_replay_add_rollout: null handle");
-    if (accept_ring(replay, "uavtrack_replay_add_rollout", ring, true)) return 1;
+    if (accept_ring(replay, "uavtrack_replay_add_rollout", ring, true, false)) return 1;
     if (!obs_in || !obs || !actions || !reward)
         return fail("uavtrack_replay_add_rollout: obs_in, obs, actions and reward must not be null");
     if (!aligned16(obs_in) || !aligned16(obs))
@@ -2072,7 +2073,7 @@ int uavtrack_replay_add_rollout_episodes(uavtrack_replay *replay, const uavtrack
 {
     const char *fn = "uavtrack_replay_add_rollout_episodes";
     if (!replay) return fail("%s: null handle", fn);
-    if (accept_ring(replay, fn, ring, true)) return 1;
+    if (accept_ring(replay, fn, ring, true, false)) return 1;
     if (!obs_in || !obs || !actions || !reward || !done || !start_obs)
         return fail("%s: obs_in, obs, actions, reward, done and start_obs must not be null", fn);
     if (!aligned16(obs_in) || !aligned16(obs) || !aligned16(start_obs))
@@ -2095,7 +2096,7 @@ int replay_sample(const char *fn, uavtrack_replay *replay, const uavtrack_replay
                   double beta0, double beta1, int64_t anneal_calls, int64_t *indices, float *weights, void *stream)
 {
     if (!replay) return fail("%s: null handle", fn);
-    if (accept_ring(replay, fn, ring, false)) return 1;
+    if (accept_ring(replay, fn, ring, false, true)) return 1;
     if (!indices) return fail("%s: indices must not be null", fn);
     if (n < 1 || n > replay->cfg.max_batch)
         return fail("%s: n = %lld outside [1, max_batch = %lld]", fn, (long long)n, (long long)replay->cfg.max_batch);
@@ -2128,6 +2129,24 @@ int uavtrack_replay_sample_annealed(uavtrack_replay *replay, const uavtrack_repl
     if (!replay) return fail("uavtrack_replay_sample_annealed: null handle");
     if (anneal_calls < 1) return fail("uavtrack_replay_sample_annealed: anneal_calls = %lld < 1", (long long)anneal_calls);
     return replay_sample(__func__, replay, ring, n, alpha, beta0, beta1, anneal_calls, indices, weights, stream);
+}
+
+int uavtrack_replay_sample_uniform(uavtrack_replay *replay, const uavtrack_replay_ring *ring, int64_t n, int64_t *indices,
+                                   void *stream)
+{
+    const char *fn = "uavtrack_replay_sample_uniform";
+    if (!replay) return fail("%s: null handle", fn);
+    if (accept_ring(replay, fn, ring, false, false)) return 1;
+    if (!indices) return fail("%s: indices must not be null", fn);
+    if (n < 1 || n > replay->cfg.max_batch)
+        return fail("%s: n = %lld outside [1, max_batch = %lld]", fn, (long long)n, (long long)replay->cfg.max_batch);
+    if (ring->count < 1) return fail("%s: the ring is empty (count = 0)", fn);
+    if (n > ring->count)
+        return fail("%s: n = %lld exceeds count = %lld (the draw is without replacement)", fn, (long long)n,
+                    (long long)ring->count);
+    ON_DEVICE(replay->cfg.device_id);
+    HIP_TRY(launch_replay_sample_uniform(replay->d, ring->count, n, indices, static_cast<hipStream_t>(stream)));
+    return 0;
 }
 
 int uavtrack_replay_check(uavtrack_replay *replay, int64_t *refused, void *stream)

@@ -437,6 +437,8 @@ hipError_t launch_pmi_select(const PmiTrainDevice &d, const PmiSourceTable &src,
 constexpr int kReplayTile = 2048;
 constexpr int kReplayMaxParts = 1024;         // workgroups of the priority-maximum reduction
 constexpr uint32_t kReplayDomain = 0x52504C59u;   // "RPLY": Philox counter word 3 of the draw stream
+constexpr uint32_t kUniformDomain = 0x554E4946u;  // "UNIF": Philox counter word 3 of the uniform draw's round keys
+constexpr int kUniformRounds = 16;            // Feistel rounds of the uniform draw's bijection (four Philox blocks of keys)
 struct ReplayDevice {
     int64_t max_capacity, max_batch;
     uint32_t k0, k1;                // Philox key: the ring's seed
@@ -459,9 +461,13 @@ struct ReplayRingView {
 hipError_t launch_replay_sample(const ReplayDevice &d, const float *priorities, int64_t count, int64_t k, float alpha,
                                 double beta0, double beta1, int64_t anneal_calls, int64_t *indices, float *weights,
                                 hipStream_t stream);
+// k distinct slots of [0, count), count <= 2^bits: the first k images of the call's keyed bijection, walked below count.
+// Shares the call counter with launch_replay_sample.
+hipError_t launch_replay_sample_uniform(const ReplayDevice &d, int64_t count, int64_t k, int64_t *indices,
+                                        hipStream_t stream);
 // n transitions: flat (obs_in == nullptr: states / next_states [n][12], actions / rewards [n]) or one rollout
 // (obs_in [agents][12], obs [n / agents][agents][12], actions / rewards [n / agents][agents]); only the last
-// min(n, capacity) land in the ring, from ring.pos on
+// min(n, capacity) land in the ring, from ring.pos on.  ring.priorities == nullptr (a uniform ring): the stores alone
 hipError_t launch_replay_add(const ReplayDevice &d, const ReplayRingView &ring, int64_t n, int64_t agents,
                              const float *obs_in, const float *states, const float *next_states, const int32_t *actions,
                              const float *rewards, hipStream_t stream,

@@ -24,10 +24,15 @@
 // x >= 0.  x >= total cannot happen: u <= 1 - 2^-53 and total >= 2^-149 is a normal double, so u * total rounds below
 // total.  So a draw lands only on a slot in [0, count) with w > 0.  A refused call writes slot 0 and NaN weights.
 //
+// The uniform draw (the reference's ReplayBuffer.sample, train.py:56-58: random.sample, without replacement) is
+// replay_begin_kernel and replay_uniform_kernel: one thread per draw, O(k) whatever the ring holds.  It reads nothing
+// of the ring, so it has no refusal.
+//
 // Adding is two reductions (the maximum of the whole priorities array, train.py:87-88) and one write kernel: each thread
 // owns one source transition f, reads obs[f] once and writes it as the next state of f and the state of f + agents.
 // The episodes form (a rollout that crossed episode ends, uavtrack_replay_add_rollout_episodes) writes the fresh state's
 // observation, start_obs[f], as the state of f + agents instead wherever the done flag of f's environment-step fired.
+// A ring without priorities (ring.priorities == nullptr, a uniform ring) skips the reductions and the priority write.
 
 #include "internal.h"
 #include "philox.h"
@@ -290,6 +295,49 @@ __global__ void replay_weight_kernel(const double *pdraw, int64_t k, int64_t cou
     weights[i] = (float)(pow(n * pdraw[i], -beta) / wmax);
 }
 
+// ---- the uniform draw: one thread per draw
+
+// murmur3's 32-bit finaliser (Appleby, MurmurHash3, public domain)
+__device__ __forceinline__ uint32_t fmix32(uint32_t x)
+{
+    x ^= x >> 16; x *= 0x85EBCA6Bu;
+    x ^= x >> 13; x *= 0xC2B2AE35u;
+    x ^= x >> 16;
+    return x;
+}
+
+// indices[j] = pi(j) walked below count: pi is a balanced Feistel network on 2 * half bits (count <= 4^half), round
+// r's function fmix32(R + key_r) mod 2^half, the keys Philox blocks of (seed, call number).  The walk stays on the
+// cycle of pi through j < count, so it ends, and no two draws meet: pi is a bijection and each draw stops at the first
+// value below count after its own start.
+__global__ void __launch_bounds__(kSW) replay_uniform_kernel(const uint64_t *counter, int64_t count, int64_t k, int half,
+                                                             uint32_t k0, uint32_t k1, int64_t *indices)
+{
+    const int64_t j = (int64_t)blockIdx.x * kSW + threadIdx.x;
+    if (j >= k) return;
+    const uint64_t call = counter[1];
+    uint32_t key[kUniformRounds];
+#pragma unroll
+    for (int i = 0; i < kUniformRounds / 4; ++i) {
+        const Philox4 r = philox4x32_10((uint32_t)i, (uint32_t)call, (uint32_t)(call >> 32), kUniformDomain, k0, k1);
+#pragma unroll
+        for (int w = 0; w < 4; ++w) key[4 * i + w] = r.v[w];
+    }
+    const uint32_t mask = (1u << half) - 1u;
+    uint64_t x = (uint64_t)j;
+    do {
+        uint32_t L = (uint32_t)(x >> half), R = (uint32_t)x & mask;
+#pragma unroll
+        for (int r = 0; r < kUniformRounds; ++r) {
+            const uint32_t t = L ^ (fmix32(R + key[r]) & mask);
+            L = R;
+            R = t;
+        }
+        x = ((uint64_t)L << half) | R;
+    } while (x >= (uint64_t)count);
+    indices[j] = (int64_t)x;
+}
+
 // ---- add
 
 __global__ void __launch_bounds__(kSW) replay_max_kernel(const float *prio, int64_t capacity, float *parts)
@@ -346,7 +394,7 @@ __global__ void __launch_bounds__(kSW) replay_write_kernel(AddArgs a)
         return obs_row;
     };
     const int64_t cap = a.ring.capacity;
-    const float top = *a.top;
+    const float top = a.ring.priorities ? *a.top : 0.0f;
     for (int64_t f = a.skip + (int64_t)blockIdx.x * kSW + threadIdx.x; f < a.n; f += (int64_t)gridDim.x * kSW) {
         int64_t slot = a.start + (f - a.skip);
         if (slot >= cap) slot -= cap;
@@ -365,7 +413,7 @@ __global__ void __launch_bounds__(kSW) replay_write_kernel(AddArgs a)
         }
         a.ring.actions[slot] = a.src_actions[f];
         a.ring.rewards[slot] = a.src_rewards[f];
-        a.ring.priorities[slot] = top;
+        if (a.ring.priorities) a.ring.priorities[slot] = top;
     }
 }
 
@@ -403,18 +451,33 @@ hipError_t launch_replay_sample(const ReplayDevice &d, const float *priorities, 
     return hipSuccess;
 }
 
+hipError_t launch_replay_sample_uniform(const ReplayDevice &d, int64_t count, int64_t k, int64_t *indices, hipStream_t st)
+{
+    static_assert(kUniformRounds % 4 == 0, "round keys come in Philox blocks of four");
+    int bits = 2;                              // even, >= 2, count <= 2^bits (< 4 * count from count 2 on)
+    while (((int64_t)1 << bits) < count) bits += 2;
+    hipLaunchKernelGGL(replay_begin_kernel, dim3(1), dim3(64), 0, st, d.counter, d.status, d.pmin);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(replay_uniform_kernel, dim3((unsigned)((k + kSW - 1) / kSW)), dim3(kSW), 0, st, d.counter, count,
+                       k, bits / 2, d.k0, d.k1, indices);
+    return hipGetLastError();
+}
+
 hipError_t launch_replay_add(const ReplayDevice &d, const ReplayRingView &ring, int64_t n, int64_t agents,
                              const float *obs_in, const float *states, const float *next_states, const int32_t *actions,
                              const float *rewards, hipStream_t st, const uint8_t *done, const float *start_obs, int64_t n_uav)
 {
     const int64_t cap = ring.capacity;
-    int64_t groups = (cap + (int64_t)kSW * 16 - 1) / ((int64_t)kSW * 16);
-    if (groups > kReplayMaxParts) groups = kReplayMaxParts;
-    hipLaunchKernelGGL(replay_max_kernel, dim3((unsigned)groups), dim3(kSW), 0, st, ring.priorities, cap, d.parts);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(replay_top_kernel, dim3(1), dim3(64), 0, st, d.parts, (int)groups, ring.count == 0 ? 1 : 0);
-    if ((e = hipGetLastError()) != hipSuccess) return e;
+    hipError_t e;
+    if (ring.priorities) {
+        int64_t groups = (cap + (int64_t)kSW * 16 - 1) / ((int64_t)kSW * 16);
+        if (groups > kReplayMaxParts) groups = kReplayMaxParts;
+        hipLaunchKernelGGL(replay_max_kernel, dim3((unsigned)groups), dim3(kSW), 0, st, ring.priorities, cap, d.parts);
+        if ((e = hipGetLastError()) != hipSuccess) return e;
+        hipLaunchKernelGGL(replay_top_kernel, dim3(1), dim3(64), 0, st, d.parts, (int)groups, ring.count == 0 ? 1 : 0);
+        if ((e = hipGetLastError()) != hipSuccess) return e;
+    }
     AddArgs a;
     a.ring = ring; a.obs_in = obs_in; a.src_states = states; a.src_next = next_states; a.src_actions = actions;
     a.src_rewards = rewards; a.top = d.parts + kReplayMaxParts; a.n = n; a.agents = agents;

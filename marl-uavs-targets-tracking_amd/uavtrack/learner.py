@@ -39,7 +39,7 @@ from ._handle import Handle, current_device
 from ._lib import host_ptr, ptr as _ptr
 from .adam import flat, from_state_dict, split, to_state_dict
 from .replay import DeviceReplayBuffer, PrioritizedDeviceReplayBuffer
-from .replay_ring import PrioritizedReplayRing
+from .replay_ring import PrioritizedReplayRing, ReplayRing
 from .rollout import ActorMLP
 
 
@@ -133,6 +133,8 @@ class DeviceActorCritic(Handle):
                 idx, w = buffer._draw_into(k, True, beta, beta_final, anneal_calls)
                 return idx, buffer.priorities, w
             return buffer._draw_into(k), buffer.priorities, None
+        if isinstance(buffer, ReplayRing):
+            return buffer._draw_into(k), None, None
         if isinstance(buffer, PrioritizedDeviceReplayBuffer):
             prob = buffer.priorities[:buffer.count] ** buffer.alpha
             prob = prob / prob.sum()
@@ -193,9 +195,9 @@ class DeviceActorCritic(Handle):
                     beta_final: Optional[float] = None, anneal_calls: int = 0):
         """buffer.sample(batch_size) + update + (prioritised buffer) update_priorities(indices, |td_delta|)
         (train.py:253-262), the gather and the priority write inside the library call.  The indices are drawn as
-        the buffer's own sample() draws them.  For a PrioritizedReplayRing the draw is one library call of its own
-        (the ring's seed and device call counter; `generator` does not apply), so the whole update is two library
-        calls with no torch kernel between them, and can be captured into a graph.
+        the buffer's own sample() draws them.  For a ReplayRing or a PrioritizedReplayRing the draw is one library call
+        of its own (the ring's seed and device call counter; `generator` does not apply), so the whole update is two
+        library calls with no torch kernel between them, and can be captured into a graph.
 
         importance=False (the default) is the reference's update: it drops the importance weights its sample()
         returns, and beta then has no effect.  importance=True trains on them (the weighted losses of the module
@@ -249,9 +251,9 @@ class DeviceActorCritic(Handle):
                   generator: Optional[torch.Generator] = None, importance: bool = False, beta: float = 0.4,
                   beta_final: Optional[float] = None, anneal_calls: int = 0):
         """The gradient half of update_from: draws min(batch_size, buffer.count) rows as update_from does (for a
-        PrioritizedReplayRing the ring's own library call) and leaves their unscaled gradient and loss sums in `row`
-        (a new tensor if None).  Returns (row, td_delta, indices); changes nothing in the learner.  The indices of a
-        PrioritizedReplayRing live in the ring's own draw tensor until its next draw: call write_priorities (or clone
+        ReplayRing or PrioritizedReplayRing the ring's own library call) and leaves their unscaled gradient and loss sums
+        in `row` (a new tensor if None).  Returns (row, td_delta, indices); changes nothing in the learner.  The indices
+        of either ring live in the ring's own draw tensor until its next draw: call write_priorities (or clone
         them) before drawing from the same ring again.  importance, beta, beta_final, anneal_calls: as update_from; the
         row's sums then carry this draw's weights, normalised by this draw's own maximum."""
         k = min(int(batch_size), buffer.count)

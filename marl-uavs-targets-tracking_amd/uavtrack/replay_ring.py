@@ -1,6 +1,13 @@
-"""The reference's `PrioritizedReplayBuffer` (src/train.py:73-139) with its add and its draw in HIP (uavtrack_replay_*):
-the ring's stores and priorities are device tensors laid out as in DeviceReplayBuffer, owned here and passed to the
+"""The reference's two replay buffers (src/train.py:41-139) with their add and their draw in HIP (uavtrack_replay_*):
+`ReplayRing` is `ReplayBuffer` (uniform, without replacement), `PrioritizedReplayRing` is `PrioritizedReplayBuffer`.
+The ring's stores and priorities are device tensors laid out as in DeviceReplayBuffer, owned here and passed to the
 library as pointers; the library handle keeps only scratch and the device-side draw counter.
+
+Against DeviceReplayBuffer (uavtrack/replay.py, which stays the plain-PyTorch reference), ReplayRing:
+  - add_rollout writes a rollout's outputs straight into the ring, as below;
+  - the draw is O(batch) instead of a shuffle of the whole ring (torch.randperm(count)[:k]): draw j of call c is a keyed
+    bijection of j walked below count, keyed by (seed, device call counter), so it allocates nothing and every replay
+    of a captured graph draws afresh.  The stream is documented in include/uavtrack.h.
 
 Against PrioritizedDeviceReplayBuffer (uavtrack/replay.py, which stays the plain-PyTorch reference):
   - add_rollout writes a rollout's outputs straight into the ring (no [T*B*N, 12] concatenation, only the last
@@ -24,37 +31,34 @@ from ._lib import ptr as _ptr
 from .replay import KEYS
 
 
-class PrioritizedReplayRing(Handle):
-    """PrioritizedReplayBuffer(capacity, alpha) (train.py:73-139) as a device ring with HIP add and sampling."""
+class ReplayRing(Handle):
+    """ReplayBuffer(capacity) (train.py:41-70) as a device ring with HIP add and sampling: uniform draws without
+    replacement.  Also what PrioritizedReplayRing shares with it: the stores, the adds and the handle."""
     _prefix = "uavtrack_replay_"
+    priorities: Optional[torch.Tensor] = None
 
-    def __init__(self, capacity: int, device, alpha: float = 0.6, seed: int = 0, max_batch: int = 65536,
-                 obs_dim: int = _lib.OBS_DIM):
+    def __init__(self, capacity: int, device, seed: int = 0, max_batch: int = 65536, obs_dim: int = _lib.OBS_DIM):
         if obs_dim != _lib.OBS_DIM:
             raise ValueError(f"obs_dim must be {_lib.OBS_DIM}, got {obs_dim}")
-        if not alpha > 0:
-            raise ValueError(f"alpha must be > 0, got {alpha}")
         self.capacity = int(capacity)
         self.device = current_device(device)
-        self.alpha, self.seed, self.max_batch = float(alpha), int(seed), int(max_batch)
+        self.seed, self.max_batch = int(seed), int(max_batch)
         self.store = {"states": torch.empty(self.capacity, obs_dim, device=self.device),
                       "actions": torch.empty(self.capacity, dtype=torch.int32, device=self.device),
                       "rewards": torch.empty(self.capacity, device=self.device),
                       "next_states": torch.empty(self.capacity, obs_dim, device=self.device)}
-        self.priorities = torch.zeros(self.capacity, device=self.device)
         self.pos = 0          # next slot to write
         self.count = 0        # valid transitions
         self._create(_lib.ReplayConfig(device_id=self.device.index, max_capacity=self.capacity, max_batch=self.max_batch,
                                        seed=self.seed & (2**64 - 1)))
         self._idx = torch.empty(self.max_batch, dtype=torch.int64, device=self.device)   # update_from's draws
-        self._w = torch.empty(self.max_batch, dtype=torch.float32, device=self.device)   # and their importance weights
 
     def _ring(self) -> _lib.ReplayRing:
         s = self.store
         return _lib.ReplayRing(states=s["states"].data_ptr(), actions=s["actions"].data_ptr(),
                                rewards=s["rewards"].data_ptr(), next_states=s["next_states"].data_ptr(),
-                               priorities=self.priorities.data_ptr(), capacity=self.capacity, pos=self.pos,
-                               count=self.count)
+                               priorities=None if self.priorities is None else self.priorities.data_ptr(),
+                               capacity=self.capacity, pos=self.pos, count=self.count)
 
     def _advance(self, n: int) -> None:
         self.pos = (self.pos + n) % self.capacity
@@ -65,13 +69,15 @@ class PrioritizedReplayRing(Handle):
 
     def check(self) -> None:
         """Synchronises; raises if a draw since the last check was refused on the device (a NaN, infinite or negative
-        priority in [0, count), or all of them zero).  A refused draw returned slot 0 and NaN weights."""
+        priority in [0, count), or all of them zero).  A refused draw returned slot 0 and NaN weights.  A uniform draw
+        reads no ring data and is never refused."""
         self._check()
 
-    # ---- add (train.py:87-96)
+    # ---- add (train.py:47-54, 87-96)
     def add(self, transition_dict: Dict[str, torch.Tensor]) -> None:
         """transition_dict: states [n,12], actions [n], rewards [n], next_states [n,12] (any leading shape is
-        flattened).  One library call writes the last min(n, capacity) of them at the current maximum priority."""
+        flattened).  One library call writes the last min(n, capacity) of them (a prioritised ring: at the current
+        maximum priority)."""
         n = transition_dict["actions"].numel()
         if n < 1:
             return
@@ -122,6 +128,48 @@ class PrioritizedReplayRing(Handle):
                                                          _ptr(act), _ptr(rew), self._stream()),
                    "uavtrack_replay_add_rollout")
         self._advance(T * M)
+
+    # ---- sample (train.py:56-58)
+    def _draw_uniform(self, k: int, idx: torch.Tensor) -> None:
+        ring = self._ring()
+        _lib.check(self._lib.uavtrack_replay_sample_uniform(self._h, C.byref(ring), k, _ptr(idx), self._stream()),
+                   "uavtrack_replay_sample_uniform")
+
+    def _draw_into(self, k: int) -> torch.Tensor:
+        """k distinct indices into the preallocated index tensor: what DeviceActorCritic.update_from uses."""
+        idx = self._idx[:k]
+        self._draw_uniform(k, idx)
+        return idx
+
+    def draw(self, batch_size: int) -> Optional[torch.Tensor]:
+        """indices int64 [k], k = min(batch_size, count): distinct slots of [0, count) in random order, as
+        random.sample's; None for an empty ring.  No synchronisation."""
+        if self.count == 0:
+            return None
+        idx = torch.empty(min(int(batch_size), self.count), dtype=torch.int64, device=self.device)
+        self._draw_uniform(idx.numel(), idx)
+        return idx
+
+    def sample(self, batch_size: int) -> Dict[str, torch.Tensor]:
+        """ReplayBuffer.sample (as DeviceReplayBuffer.sample returns it): the transitions dict of min(batch_size, count)
+        distinct transitions."""
+        if self.count == 0:
+            return {k: self.store[k][:0] for k in KEYS}
+        idx = self.draw(batch_size)
+        return {key: self.store[key][idx] for key in KEYS}
+
+
+class PrioritizedReplayRing(ReplayRing):
+    """PrioritizedReplayBuffer(capacity, alpha) (train.py:73-139) as a device ring with HIP add and sampling."""
+
+    def __init__(self, capacity: int, device, alpha: float = 0.6, seed: int = 0, max_batch: int = 65536,
+                 obs_dim: int = _lib.OBS_DIM):
+        if not alpha > 0:
+            raise ValueError(f"alpha must be > 0, got {alpha}")
+        super().__init__(capacity, device, seed, max_batch, obs_dim)
+        self.alpha = float(alpha)
+        self.priorities = torch.zeros(self.capacity, device=self.device)
+        self._w = torch.empty(self.max_batch, dtype=torch.float32, device=self.device)   # update_from's importance weights
 
     # ---- sample (train.py:98-112)
     def _draw(self, k: int, beta: float, idx: torch.Tensor, weights: Optional[torch.Tensor],
