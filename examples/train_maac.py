@@ -56,23 +56,62 @@ class ValueNet(torch.nn.Module):
         return self.fc2(torch.relu(self.fc1(x))).squeeze(-1)
 
 
-def update(actor, critic, opt_a, opt_c, batch, gamma, weights=None):
+def update(actor, critic, opt_a, opt_c, batch, gamma, weights=None, entropy_coef=0.0, max_grad_norm=None, diag=None):
     """One ActorCritic.update step (actor_critic.py:150-178) on a batch of transitions.  weights (--importance): the
-    draw's importance weights, one per row, multiplied into the per-sample losses before the mean."""
+    draw's importance weights, one per row, multiplied into the per-sample losses before the mean.  entropy_coef and
+    max_grad_norm: the two terms of DeviceActorCritic.set_regularisation, so that --learner torch and --learner device
+    stay comparable; diag (a dict) receives the mean entropy and the two gradient norms before clipping."""
     s, a, r, s2 = batch["states"], batch["actions"].long().unsqueeze(1), batch["rewards"], batch["next_states"]
     td_target = r + gamma * critic(s2)
     td_delta = td_target - critic(s)
-    log_probs = torch.log(actor(s).gather(1, a).squeeze(1).clamp_min(1e-12))
+    probs = actor(s)
+    log_probs = torch.log(probs.gather(1, a).squeeze(1).clamp_min(1e-12))
+    per_row = -log_probs * td_delta.detach()
+    if entropy_coef or diag is not None:
+        entropy = -(probs * torch.log(probs.clamp_min(1e-12))).sum(dim=1)
+        if entropy_coef:
+            per_row = per_row - entropy_coef * entropy
     if weights is None:
-        actor_loss = torch.mean(-log_probs * td_delta.detach())
+        actor_loss = torch.mean(per_row)
         critic_loss = torch.nn.functional.mse_loss(critic(s), td_target.detach())
     else:
-        actor_loss = torch.mean(weights * (-log_probs * td_delta.detach()))
+        actor_loss = torch.mean(weights * per_row)
         critic_loss = torch.mean(weights * (critic(s) - td_target.detach()) ** 2)
     opt_a.zero_grad(); opt_c.zero_grad()
     actor_loss.backward(); critic_loss.backward()
+    if max_grad_norm is not None:
+        norms = [torch.nn.utils.clip_grad_norm_(net.parameters(), max_grad_norm) for net in (actor, critic)]
+        if diag is not None:
+            diag["norms"] = torch.stack(norms).detach()
+    if diag is not None:
+        diag["entropy"] = entropy.detach().mean()
     opt_a.step(); opt_c.step()
     return float(actor_loss.detach()), float(critic_loss.detach())
+
+
+def device_learner(args, uavtrack, na_total, dev, max_batch):
+    """The DeviceActorCritic of --learner device with --entropy-coef / --max-grad-norm; the diagnostics only when one of
+    them is on.  A refused setting (--entropy-coef with --actor-loss reference) exits with the library's message."""
+    try:
+        learner = uavtrack.DeviceActorCritic(12, args.hidden, na_total, args.actor_lr, args.critic_lr, args.gamma, dev,
+                                             loss=args.actor_loss, max_batch=max_batch,
+                                             entropy_coef=args.entropy_coef, max_grad_norm=args.max_grad_norm)
+    except RuntimeError as e:
+        raise SystemExit(f"train_maac.py: {e}")
+    if regularised(args):
+        learner.enable_diagnostics(max_batch)
+    return learner
+
+
+def regularised(args):
+    return bool(args.entropy_coef) or args.max_grad_norm is not None
+
+
+def regularisation_field(entropy, norms):
+    """The printed lines' extra field while --entropy-coef or --max-grad-norm is on: the mean policy entropy of the last
+    update's batch and the actor's and critic's gradient norms before clipping (nan without --max-grad-norm)."""
+    a, c = (float("nan"), float("nan")) if norms is None else (float(norms[0]), float(norms[1]))
+    return f"entropy {float(entropy):.4f}  grad norm {a:.4f} {c:.4f}  "
 
 
 SIX = ("return_list", "target_tracking_return_list", "boundary_punishment_return_list",
@@ -155,8 +194,7 @@ def train_sharded(args, timings=None):
     na_total = envs[0].cfg.na_total
     actor = uavtrack.ActorMLP(hidden_dim=args.hidden, action_dim=na_total).to(dev)
     per_shard = -(-args.batch // K)                                   # rows each ring contributes to one update
-    learner = uavtrack.DeviceActorCritic(12, args.hidden, na_total, args.actor_lr, args.critic_lr, args.gamma, dev,
-                                         loss=args.actor_loss, max_batch=per_shard)
+    learner = device_learner(args, uavtrack, na_total, dev, per_shard)
     actor.load_state_dict(learner.actor_state_dict())
     rollouts = [uavtrack.BatchedRollout(e, actor, device_actor=True, seed=args.seed) for e in envs]
     if args.replay == "prioritized":
@@ -186,8 +224,11 @@ def train_sharded(args, timings=None):
             torch.cuda.synchronize()
         t_roll = time.perf_counter() - t0
         for _ in range(args.updates):
-            la_t, lc_t, _ = learner.update_from_many(rings, per_shard, **importance_kwargs(args))
+            la_t, lc_t, tds = learner.update_from_many(rings, per_shard, **importance_kwargs(args))
         la, lc = (float(la_t), float(lc_t)) if log else (la_t, lc_t)
+        reg_field = ""
+        if log and regularised(args):                                 # the last ring's rows of the last update
+            reg_field = regularisation_field(learner.entropy(tds[-1].numel()).mean(), learner.grad_norm)
         if args.publish == "host":
             actor.load_state_dict(learner.actor_state_dict())
             for ro in rollouts:
@@ -217,7 +258,7 @@ def train_sharded(args, timings=None):
         n_iter = it + 1 - (stamps[-1][0] if stamps else 0)
         stamps.append((it + 1, now))
         print(f"iter {it:3d}  shards {K}  episode return {ret:8.3f}  covered targets/step {cov:5.2f}  actor loss {la:+.4f}  "
-              f"critic loss {lc:.4f}  {pmi_field}rollout {t_roll * 1e3:6.1f} ms ({per_iter / t_roll / 1e9:.2f} G agent-steps/s)  "
+              f"critic loss {lc:.4f}  {reg_field}{pmi_field}rollout {t_roll * 1e3:6.1f} ms ({per_iter / t_roll / 1e9:.2f} G agent-steps/s)  "
               f"iteration {((now - t0) if args.log_every == 1 else (now - t_log) / n_iter) * 1e3:6.1f} ms  {six}", flush=True)
         t_log = now
     save_results(args, kept)
@@ -261,6 +302,12 @@ def main(argv=None, timings=None):
     ap.add_argument("--actor-loss", choices=["reference", "per_sample"], default="reference",
                     help="--learner device only: the reference's broadcast loss mean(-log p) * mean(delta), or "
                          "mean(-log p * delta) (what the torch learner trains with)")
+    ap.add_argument("--entropy-coef", type=float, default=0.0,
+                    help="entropy bonus c: actor loss mean(w (-log p delta - c H)), in both learners (--learner device: "
+                         "DeviceActorCritic(entropy_coef=c), --actor-loss per_sample only)")
+    ap.add_argument("--max-grad-norm", type=float, default=None,
+                    help="clip_grad_norm_ of the actor's and of the critic's gradient to this norm before each Adam step, "
+                         "in both learners (--learner device: DeviceActorCritic(max_grad_norm=...)); default: no clipping")
     ap.add_argument("--pmi-trainer", choices=["torch", "device"], default="torch",
                     help="--method maac-r only: torch: the PyTorch PMINetwork.train_pmi loop below; device: "
                          "uavtrack.DevicePMINetwork, the whole train_pmi call in one library call")
@@ -370,8 +417,7 @@ def main(argv=None, timings=None):
     opt_c = torch.optim.Adam(critic.parameters(), lr=args.critic_lr)
     learner = None
     if args.learner == "device":
-        learner = uavtrack.DeviceActorCritic(12, args.hidden, cfg.na_total, args.actor_lr, args.critic_lr, args.gamma,
-                                             dev, loss=args.actor_loss, max_batch=args.batch)
+        learner = device_learner(args, uavtrack, cfg.na_total, dev, args.batch)
         actor.load_state_dict(learner.actor_state_dict())
     rollout = uavtrack.BatchedRollout(env, actor, device_actor=True, seed=args.seed)
     K = args.rollout_episodes
@@ -407,21 +453,25 @@ def main(argv=None, timings=None):
         if log:
             torch.cuda.synchronize()
         t_roll = time.perf_counter() - t0
+        diag = {} if log and regularised(args) else None              # the torch learner's entropy and norms
+        reg_kw = dict(entropy_coef=args.entropy_coef, max_grad_norm=args.max_grad_norm, diag=diag)
         if learner is None and args.replay == "prioritized":          # train.py:250-262
             ikw = importance_kwargs(args)
             for _ in range(args.updates):
                 batch, idx, w = replay.sample(args.batch, args.beta, ikw.get("beta_final"), ikw.get("anneal_calls", 0))
-                la, lc = update(actor, critic, opt_a, opt_c, batch, args.gamma, w if args.importance else None)
+                la, lc = update(actor, critic, opt_a, opt_c, batch, args.gamma, w if args.importance else None, **reg_kw)
                 with torch.no_grad():
                     s, r, s2 = batch["states"], batch["rewards"], batch["next_states"]
                     replay.update_priorities(idx, (r + args.gamma * critic(s2) - critic(s)).abs())
         elif learner is None:
             for _ in range(args.updates):
-                la, lc = update(actor, critic, opt_a, opt_c, replay.sample(args.batch), args.gamma)
+                la, lc = update(actor, critic, opt_a, opt_c, replay.sample(args.batch), args.gamma, **reg_kw)
         else:
             for _ in range(args.updates):
-                la_t, lc_t, _ = learner.update_from(replay, args.batch, **importance_kwargs(args))
+                la_t, lc_t, td_t = learner.update_from(replay, args.batch, **importance_kwargs(args))
             la, lc = (float(la_t), float(lc_t)) if log else (la_t, lc_t)
+            if diag is not None:
+                diag.update(entropy=learner.entropy(td_t.numel()).mean(), norms=learner.grad_norm)
             if args.publish == "host":
                 actor.load_state_dict(learner.actor_state_dict())     # the rollout's actor: host pack, as sync_actor
         lp = float("nan")
@@ -461,8 +511,9 @@ def main(argv=None, timings=None):
         now = time.perf_counter()
         n_iter = it + 1 - (stamps[-1][0] if stamps else 0)           # iterations since the previous line
         stamps.append((it + 1, now))
+        reg_field = regularisation_field(diag["entropy"], diag.get("norms")) if diag else ""
         print(f"iter {it:3d}  episode return {ret:8.3f}  covered targets/step {cov:5.2f}  actor loss {la:+.4f}  "
-              f"critic loss {lc:.4f}  pmi loss {lp:.4f}  rollout {t_roll * 1e3:6.1f} ms ({per_iter / t_roll / 1e9:.2f} G agent-steps/s)  "
+              f"critic loss {lc:.4f}  {reg_field}pmi loss {lp:.4f}  rollout {t_roll * 1e3:6.1f} ms ({per_iter / t_roll / 1e9:.2f} G agent-steps/s)  "
               f"iteration {((now - t0) if args.log_every == 1 else (now - t_log) / n_iter) * 1e3:6.1f} ms  {six}", flush=True)
         t_log = now
     save_results(args, kept)

@@ -583,6 +583,53 @@ int uavtrack_learner_apply(uavtrack_learner *learner, const float *rows, int64_t
 int uavtrack_learner_write_priorities(uavtrack_learner *learner, int64_t n, const int64_t *indices, int64_t capacity,
                                       const float *td_delta, float *priorities, void *stream);
 
+/* ---- regularisation: an entropy bonus and gradient-norm clipping (both off by default) ----
+ * Two optional settings of a learner handle.  With both at their defaults every call above enqueues exactly the kernels
+ * it enqueued without them, with the same arguments.
+ *
+ * Entropy bonus c >= 0 (entropy_coef), UAVTRACK_LOSS_PER_SAMPLE only.  With p_i = softmax(z_i) and
+ * H_i = -sum_o p_io log p_io the actor loss becomes
+ *   actor_loss = mean_i( w_i * ( -log p_i(a_i) * delta_i - c * H_i ) )       (w_i = 1 without weights; the mean divides by n)
+ * The accumulated logit weight of a batch row is w_i * ( delta_i * (onehot - p_i)_o - c * p_io * (log p_io + H_i) ),
+ * still scaled by -1 / N in the Adam step, so a gradient row keeps its P + 8 words and its tag, and regularised rows add
+ * up in an apply like any others: the entropy term is one more summand of the same per-row sums.  actor_loss is the whole
+ * loss above; loss word [P+2] of a row carries sum w_i (-log p_i delta_i - c H_i), words [P], [P+1], [P+3] are unchanged.
+ * Every log p of a regularised row comes from the logits, (z_o - max) - log sum exp(z - max), so H_i and its gradient are
+ * finite for every finite logit vector, also where a small probability underflows to 0 in fp32 (such an action adds 0).
+ * The reference form scales the actor's gradient sums ONCE by the global -mean(delta) / N after they are added; an
+ * entropy term would need a scale of its own (-1 / N), that is a second actor block in the row: c != 0 on a
+ * UAVTRACK_LOSS_REFERENCE learner is refused.  With c == 0 the row loop computes what it computed before, to the bit.
+ *
+ * Gradient-norm clipping, one max_norm per network (actor, critic), each > 0 or +inf for off:
+ * torch.nn.utils.clip_grad_norm_(net.parameters(), max_norm).  g is the scaled gradient the Adam step forms (the ordered
+ * sum over workgroup partials or rows, times the network's scale); norm = sqrt(sum_p g_p^2) over that network's
+ * parameters; coef = min(1, max_norm / (norm + 1e-6)); Adam sees coef * g.  The sum of squares is taken in fp64 in a
+ * fixed order, coef is formed in double and rounded to fp32 once, so every participant of a split or data-parallel
+ * update gets the same coef bits from the same rows; norm + 1e-6 <= max_norm gives coef == 1.0f exactly, and an update
+ * that does not clip is bit for bit the unclipped one.  A non-finite norm propagates as torch's default does (nothing
+ * new is refused); a refused update stays a no-op.  Clipping applies to update, update_weighted and apply alike, in both
+ * loss forms; in an apply the norm is that of the summed rows.  With both max norms +inf no additional kernel is launched;
+ * otherwise an update adds two small launches and one more pass over P floats.
+ *
+ * Gradient rows carry no settings: every learner that takes part in one update (ranks, shards) must be given the same. */
+
+/* Host-side settings, read when a later update / grad / apply is ENQUEUED (a captured graph keeps the values it was
+ * captured with, as it keeps beta).  entropy_coef >= 0 finite; max norms > 0 or +inf.  Refused, changing nothing:
+ * NaN / negative / zero-norm values; entropy_coef != 0 on a UAVTRACK_LOSS_REFERENCE learner (see above). */
+int uavtrack_learner_set_regularisation(uavtrack_learner *learner, double entropy_coef, double actor_max_norm,
+                                        double critic_max_norm);
+/* out = {entropy_coef, actor_max_norm, critic_max_norm} as they were last set ({0, +inf, +inf} at create). */
+int uavtrack_learner_get_regularisation(uavtrack_learner *learner, double out[3]);
+
+/* Optional diagnostics, caller-owned DEVICE buffers (not copied; NULL uninstalls either).  Installing them changes no
+ * other output bit.
+ *   entropy   fp32 [capacity_rows]: H_i of batch row i, written by every update or grad while installed, whatever c is;
+ *             0 for a batch row that was not used (bad action, index or weight).  An update or grad of more rows than
+ *             capacity_rows while entropy is installed is refused on the host, enqueuing nothing.
+ *   grad_norm fp32 [2]: the actor's and the critic's gradient norm before clipping, written by every update or apply
+ *             that clips (at least one finite max norm; a huge finite one observes without clipping), NaN for a refused one. */
+int uavtrack_learner_set_diagnostics(uavtrack_learner *learner, float *entropy, int64_t capacity_rows, float *grad_norm);
+
 /* Synchronises `stream`; fails if any update or apply since the previous check was refused on the device (bad action,
  * index or importance weight, or a row of another layout).  refused (nullable) receives their number; the count restarts at 0. */
 int uavtrack_learner_check(uavtrack_learner *learner, int64_t *refused, void *stream);

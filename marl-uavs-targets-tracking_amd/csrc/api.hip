@@ -1321,6 +1321,7 @@ int uavtrack_kernel_info(uavtrack_env *env, int64_t out[5])
 struct uavtrack_learner {
     uavtrack_learner_config cfg;
     LearnerDevice d;
+    double reg[3] = {0.0, INFINITY, INFINITY};   // uavtrack_learner_get_regularisation: the values as they were set
 };
 
 struct uavtrack_pmi_trainer {
@@ -1359,7 +1360,8 @@ Bufs scratch_bufs(LearnerDevice &d, int64_t max_n) { return {buf(d.td, max_n), b
 Bufs device_bufs(LearnerDevice &d)
 {
     const size_t P = (size_t)d.L.P;
-    return adam_bufs(d.opt) + Bufs{buf(d.params, P, true), buf(d.gstatus, 1, true), buf(d.partials, kLearnerMaxGroups * (P + 4)), buf(d.scal, 2)} +
+    return adam_bufs(d.opt) + Bufs{buf(d.params, P, true), buf(d.gstatus, 1, true), buf(d.partials, kLearnerMaxGroups * (P + 4)), buf(d.scal, 2),
+                                   buf(d.gsum, P), buf(d.sq, 2 * (size_t)learner_clip_groups(d.L)), buf(d.coef, 2)} +
            scratch_bufs(d, d.max_n);
 }
 
@@ -1471,6 +1473,15 @@ int accept_batch(const char *fn, const uavtrack_learner *l, int64_t n, int64_t c
     return 0;
 }
 
+// uavtrack_learner_update / _grad while an entropy buffer is installed: the batch must fit into it
+int accept_entropy_rows(const char *fn, const uavtrack_learner *l, int64_t n)
+{
+    if (l->d.entropy && n > l->d.entropy_rows)
+        return fail("%s: n = %lld rows, the installed entropy buffer holds %lld (uavtrack_learner_set_diagnostics)", fn,
+                    (long long)n, (long long)l->d.entropy_rows);
+    return 0;
+}
+
 // the fields uavtrack_learner_update and _grad (and their weighted forms) fill alike; the others are null
 LearnerLaunch learner_batch(int64_t n, const float *states, const int32_t *actions, const float *rewards,
                             const float *next_states, int64_t capacity, const int64_t *indices, const float *weights,
@@ -1562,6 +1573,7 @@ int uavtrack_learner_create(const uavtrack_learner_config *cfg, uavtrack_learner
         d.opt.tensors = kLearnerTensors;
         d.opt.P = d.L.P;
         d.max_n = c.max_batch ? c.max_batch : kLearnerDefaultBatch;
+        d.max_norm[0] = d.max_norm[1] = INFINITY;       // regularisation off: entropy_coef 0, no diagnostics
         return learner_prepare_kernels(d.L);
     };
     return create_handle(__func__, cfg, out, check, init);
@@ -1573,6 +1585,43 @@ int uavtrack_learner_num_params(uavtrack_learner *learner, int64_t *out)
 {
     if (!learner || !out) return fail("uavtrack_learner_num_params: null argument");
     *out = learner->d.L.P;
+    return 0;
+}
+
+int uavtrack_learner_set_regularisation(uavtrack_learner *learner, double entropy_coef, double actor_max_norm,
+                                        double critic_max_norm)
+{
+    if (!learner) return fail("%s: null handle", __func__);
+    if (!std::isfinite(entropy_coef) || entropy_coef < 0)
+        return fail("%s: entropy_coef = %g must be finite and >= 0", __func__, entropy_coef);
+    if (!(actor_max_norm > 0) || !(critic_max_norm > 0))
+        return fail("%s: max norms (%g, %g) must be > 0, or +inf for no clipping", __func__, actor_max_norm, critic_max_norm);
+    if (entropy_coef != 0 && !learner->d.per_sample)
+        return fail("%s: entropy_coef = %g on a UAVTRACK_LOSS_REFERENCE learner: that form scales the actor's gradient "
+                    "sums once by -mean(delta) / N, a factor an entropy term cannot share; use UAVTRACK_LOSS_PER_SAMPLE",
+                    __func__, entropy_coef);
+    learner->d.entropy_coef = (float)entropy_coef;
+    learner->d.max_norm[0] = actor_max_norm;
+    learner->d.max_norm[1] = critic_max_norm;
+    learner->reg[0] = entropy_coef; learner->reg[1] = actor_max_norm; learner->reg[2] = critic_max_norm;
+    return 0;
+}
+
+int uavtrack_learner_get_regularisation(uavtrack_learner *learner, double out[3])
+{
+    if (!learner || !out) return fail("%s: null argument", __func__);
+    for (int k = 0; k < 3; ++k) out[k] = learner->reg[k];
+    return 0;
+}
+
+int uavtrack_learner_set_diagnostics(uavtrack_learner *learner, float *entropy, int64_t capacity_rows, float *grad_norm)
+{
+    if (!learner) return fail("%s: null handle", __func__);
+    if (entropy && capacity_rows < 1)
+        return fail("%s: capacity_rows = %lld < 1 with an entropy buffer", __func__, (long long)capacity_rows);
+    learner->d.entropy = entropy;
+    learner->d.entropy_rows = entropy ? capacity_rows : 0;
+    learner->d.grad_norm = grad_norm;
     return 0;
 }
 
@@ -1655,7 +1704,7 @@ int learner_update(const char *fn, uavtrack_learner *learner, int64_t n, const f
     if (!states || !actions || !rewards || !next_states)
         return fail("%s: states, actions, rewards and next_states must not be null", fn);
     if (!actor_loss || !critic_loss) return fail("%s: actor_loss and critic_loss must not be null", fn);
-    if (accept_batch(fn, learner, n, capacity, indices, "from")) return 1;
+    if (accept_batch(fn, learner, n, capacity, indices, "from") || accept_entropy_rows(fn, learner, n)) return 1;
     ON_DEVICE(learner->cfg.device_id);
     LearnerLaunch q = learner_batch(n, states, actions, rewards, next_states, capacity, indices, weights, td_delta);
     q.actor_loss = actor_loss; q.critic_loss = critic_loss; q.priorities = priorities;
@@ -1672,7 +1721,7 @@ int learner_grad(const char *fn, uavtrack_learner *learner, int64_t n, const flo
     if (!states || !actions || !rewards || !next_states)
         return fail("%s: states, actions, rewards and next_states must not be null", fn);
     if (!td_delta || !row) return fail("%s: td_delta and row must not be null", fn);
-    if (accept_batch(fn, learner, n, capacity, indices, "from")) return 1;
+    if (accept_batch(fn, learner, n, capacity, indices, "from") || accept_entropy_rows(fn, learner, n)) return 1;
     ON_DEVICE(learner->cfg.device_id);
     const LearnerLaunch q = learner_batch(n, states, actions, rewards, next_states, capacity, indices, weights, td_delta);
     HIP_TRY(launch_learner_grad(learner->d, q, row, static_cast<hipStream_t>(stream)));

@@ -335,6 +335,15 @@ struct LearnerDevice {
     float *td;                      // [max_n] td_delta when the caller passes none
     uint8_t *last;                  // [max_n] last-occurrence marks of the priority write
     int64_t max_n;
+    // regularisation (uavtrack_learner_set_regularisation / _set_diagnostics): host-side settings, read at enqueue
+    float entropy_coef;             // c >= 0; != 0 only with per_sample
+    double max_norm[2];             // actor, critic: > 0, +inf = off
+    float *entropy;                 // caller's [entropy_rows] buffer (not owned) or null
+    int64_t entropy_rows;
+    float *grad_norm;               // caller's [2] buffer (not owned) or null
+    float *gsum;                    // [P] the scaled gradient of a clipped update
+    double *sq;                     // [learner_clip_groups][2] its workgroups' sums of squares: actor, critic
+    float *coef;                    // [2] the clip coefficients
 };
 struct LearnerLaunch {
     int64_t n, capacity;
@@ -347,6 +356,7 @@ struct LearnerLaunch {
 int learner_rows_per_tile(int hidden);
 size_t learner_lds_bytes(const LearnerLayout &L, int rows);
 int learner_groups(const LearnerLayout &L, int64_t n);
+int learner_clip_groups(const LearnerLayout &L);   // workgroups of the clip's gradient pass: ceil(P / 256)
 hipError_t learner_prepare_kernels(const LearnerLayout &L);
 hipError_t launch_learner_update(const LearnerDevice &d, const LearnerLaunch &q, hipStream_t stream);
 // the split update: gradient row [P + kLearnerRowTail] <- one batch; rows [count][P + kLearnerRowTail] -> both Adam steps;

@@ -26,6 +26,16 @@
 // above takes its row's w_i as one more factor (the logit weight, the value weight, the four loss terms) and nothing
 // after the sums changes: the means still divide by n, and -(sum w delta / N) / N falls out of the same words.  No
 // weights is the factor 1.0f, an exact multiply, so the unweighted update keeps its bits.
+//
+// Regularisation (uavtrack_learner_set_regularisation, off by default).  An entropy bonus c > 0 (per-sample form only)
+// makes the actor loss mean_i(w_i (-log p_i delta_i - c H_i)), H_i = -sum_o p_io log p_io: the accumulated logit weight
+// of a row becomes w_i (delta_i (onehot - p_i)_o - c p_io (log p_io + H_i)), still scaled by -1 / N afterwards, and loss
+// word 2 carries the whole term, so rows keep their layout and still add.  Every log p then comes from the logits,
+// (z_o - max) - log sum exp, never from logf(p): finite for every finite logit vector.  learner_grad_reg_kernel is the
+// same body compiled with that block; learner_grad_kernel stays what it was.  Gradient-norm clipping (one max_norm per
+// network) runs between "scale" and "Adam": learner_gradsum_kernel forms the scaled gradient once and leaves each
+// workgroup's sums of squares in fp64, learner_clip_kernel adds them in workgroup order and writes both coefficients,
+// and the same Adam kernel then runs over (the scaled gradient, count 1, the coefficients as its scales).
 
 #include "internal.h"
 
@@ -54,9 +64,13 @@ struct GradArgs {
     int rows;                       // R rows per tile
     float gamma;
     int per_sample;
+    float entropy_coef;             // c >= 0 (learner_grad_reg_kernel only; c != 0 only with per_sample)
+    float *entropy;                 // nullable [n]: H_i of batch row i, 0 for a row that was not used
 };
 
-__global__ void __launch_bounds__(kLW) learner_grad_kernel(GradArgs a)
+// kReg: the entropy term and the entropy[] store in the per-row block; everything else is one text.
+template <bool kReg>
+__device__ __forceinline__ void learner_grad_body(const GradArgs &a)
 {
     extern __shared__ float lds[];
     const LearnerLayout &L = a.L;
@@ -152,10 +166,54 @@ __global__ void __launch_bounds__(kLW) learner_grad_kernel(GradArgs a)
                 for (int o = 0; o < A; ++o) z[o] = 0.0f;
                 gv[r] = 0.0f;
                 lt[r * 4 + 0] = lt[r * 4 + 1] = lt[r * 4 + 2] = lt[r * 4 + 3] = 0.0f;
+                if (kReg && a.entropy && row0 + r < a.n) a.entropy[row0 + r] = 0.0f;
                 continue;
             }
             float m = z[0];
             for (int o = 1; o < A; ++o) m = fmaxf(m, z[o]);
+            if constexpr (kReg) {
+                // d_o = z_o - max stays in z; e_o = expf(d_o) is formed again where it is needed (the same bits).
+                // H = log sum e - (sum e_o d_o) / sum e: both terms >= 0, and e_o == 0 (an underflowed probability)
+                // contributes 0, not 0 * d_o.
+                float sum = 0.0f, sd = 0.0f;
+                for (int o = 0; o < A; ++o) {
+                    const float d = z[o] - m, e = expf(d);
+                    z[o] = d;
+                    sum += e;
+                    sd += e > 0.0f ? e * d : 0.0f;
+                }
+                const float inv = 1.0f / sum;
+                const float lse = logf(sum);
+                const float ent = lse - sd * inv;
+                const float target = rew + a.gamma * vn[r];
+                const float v = gv[r];
+                const float delta = target - v;
+                const float wi = wt[r];
+                const float c = a.entropy_coef;
+                float nlp, al;
+                if (c != 0.0f) {                                    // launch-uniform
+                    nlp = lse - z[av];
+                    for (int o = 0; o < A; ++o) {
+                        const float d = z[o], e = expf(d), p = e * inv;
+                        const float ge = e > 0.0f ? p * ((d - lse) + ent) : 0.0f;
+                        z[o] = wi * (delta * ((o == av ? 1.0f : 0.0f) - p) - c * ge);
+                    }
+                    al = wi * (nlp * delta - c * ent);
+                } else {                                            // today's values, to the bit
+                    nlp = -logf(expf(z[av]) * inv);
+                    const float w = (a.per_sample ? delta : 1.0f) * wi;
+                    for (int o = 0; o < A; ++o) z[o] = w * ((o == av ? 1.0f : 0.0f) - expf(z[o]) * inv);
+                    al = (nlp * delta) * wi;
+                }
+                gv[r] = (v - target) * wi;
+                lt[r * 4 + 0] = nlp * wi;
+                lt[r * 4 + 1] = delta * wi;
+                lt[r * 4 + 2] = al;
+                lt[r * 4 + 3] = ((v - target) * (v - target)) * wi;
+                if (a.td_delta) a.td_delta[row0 + r] = delta;
+                if (a.entropy) a.entropy[row0 + r] = ent;
+                continue;
+            }
             float sum = 0.0f;
             for (int o = 0; o < A; ++o) { z[o] = expf(z[o] - m); sum += z[o]; }
             const float inv = 1.0f / sum;
@@ -235,6 +293,11 @@ __global__ void __launch_bounds__(kLW) learner_grad_kernel(GradArgs a)
         for (int q = 0; q < 4; ++q) out[P + q] = loss_run[q];
 }
 
+__global__ void __launch_bounds__(kLW) learner_grad_kernel(GradArgs a) { learner_grad_body<false>(a); }
+
+// launched instead of learner_grad_kernel while entropy_coef != 0 or an entropy[] buffer is installed
+__global__ void __launch_bounds__(kLW) learner_grad_reg_kernel(GradArgs a) { learner_grad_body<true>(a); }
+
 // Clears the update's status word (a kernel node rather than a memset node, so a captured update is a chain of kernels)
 __global__ void learner_begin_kernel(int *status)
 {
@@ -297,6 +360,68 @@ __global__ void learner_adam_kernel(float *params, float *m, float *v, const flo
     const bool actor = p < L.c_w1;
     const float g = ordered_sum(src, count, stride, p) * (actor ? scal[0] : scal[1]);
     adam_element(params[p], m[p], v[p], g, steps[L.tensor_of(p)], actor ? actor_lr : critic_lr);
+}
+
+// ---- gradient-norm clipping (torch.nn.utils.clip_grad_norm_, one max_norm per network), between "scale" and "Adam".
+// Every sum has a fixed order -- ordered_sum per word, a fixed tree over the 256 words of a workgroup, workgroups
+// ascending -- and is carried in fp64, so whoever clips the same rows in the same order gets the same coefficient bits.
+
+constexpr int kClipThreads = 256;   // words per workgroup of learner_gradsum_kernel (= the Adam kernel's)
+
+// One thread per word: g_p = ordered_sum * scal[network], the gradient the Adam kernel would form, into gsum[p]; the
+// workgroup's two sums of g^2 (a workgroup may straddle the actor / critic boundary) into sq[workgroup][2].
+__global__ void __launch_bounds__(kClipThreads) learner_gradsum_kernel(const float *src, int count, size_t stride,
+                                                                       LearnerLayout L, const int *status,
+                                                                       const float *scal, float *gsum, double *sq)
+{
+    __shared__ double part[2][kClipThreads];
+    if (*status) return;                                            // uniform: a refused update forms no norm
+    const int tid = threadIdx.x, p = blockIdx.x * kClipThreads + tid;
+    double qa = 0.0, qc = 0.0;
+    if (p < L.P) {
+        const bool actor = p < L.c_w1;
+        const float g = ordered_sum(src, count, stride, p) * (actor ? scal[0] : scal[1]);
+        gsum[p] = g;
+        const double q = (double)g * (double)g;
+        if (actor) qa = q; else qc = q;
+    }
+    part[0][tid] = qa;
+    part[1][tid] = qc;
+    __syncthreads();
+    for (int h = kClipThreads / 2; h > 0; h >>= 1) {
+        if (tid < h) {
+            part[0][tid] += part[0][tid + h];
+            part[1][tid] += part[1][tid + h];
+        }
+        __syncthreads();
+    }
+    if (tid == 0) {
+        sq[2 * blockIdx.x + 0] = part[0][0];
+        sq[2 * blockIdx.x + 1] = part[1][0];
+    }
+}
+
+// One thread: the workgroups' sums of squares added in workgroup order, the two norms, and per network
+// coef = min(1, max_norm / (norm + 1e-6)) formed in double and rounded to fp32 once (norm + 1e-6 <= max_norm gives
+// exactly 1.0f; max_norm = +inf is "off": exactly 1.0f).  A NaN ratio stays NaN, as torch's clamp leaves it.
+// grad_norm (nullable [2]): the two norms before clipping, NaN for a refused update.
+__global__ void learner_clip_kernel(const double *sq, int groups, double actor_max, double critic_max, const int *status,
+                                    float *coef, float *grad_norm)
+{
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    if (*status) {
+        if (grad_norm) { grad_norm[0] = NAN; grad_norm[1] = NAN; }
+        return;
+    }
+    double s[2] = {0.0, 0.0};
+    for (int g = 0; g < groups; ++g) { s[0] += sq[2 * g]; s[1] += sq[2 * g + 1]; }
+    const double mx[2] = {actor_max, critic_max};
+    for (int k = 0; k < 2; ++k) {
+        const double norm = sqrt(s[k]);
+        const double r = mx[k] / (norm + 1e-6);
+        coef[k] = isinf(mx[k]) || r >= 1.0 ? 1.0f : (float)r;
+        if (grad_norm) grad_norm[k] = (float)norm;
+    }
 }
 
 // ---- the split update (uavtrack_learner_grad / _apply / _write_priorities): the update cut between "sum" and "scale +
@@ -376,10 +501,15 @@ int learner_groups(const LearnerLayout &L, int64_t n)
     return (int)(tiles < kLearnerMaxGroups ? tiles : kLearnerMaxGroups);
 }
 
+int learner_clip_groups(const LearnerLayout &L) { return (L.P + kClipThreads - 1) / kClipThreads; }
+
 hipError_t learner_prepare_kernels(const LearnerLayout &L)
 {
     const size_t lds = learner_lds_bytes(L, learner_rows_per_tile(L.H));
-    return hipFuncSetAttribute(reinterpret_cast<const void *>(learner_grad_kernel),
+    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(learner_grad_kernel),
+                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) return e;
+    return hipFuncSetAttribute(reinterpret_cast<const void *>(learner_grad_reg_kernel),
                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
 }
 
@@ -398,7 +528,11 @@ hipError_t launch_grad(const LearnerDevice &d, const LearnerLaunch &q, float *td
     a.actions = q.actions; a.idx = q.idx; a.weights = q.weights; a.n = q.n; a.capacity = q.capacity;
     a.partials = d.partials; a.td_delta = td; a.status = status;
     a.L = L; a.rows = R; a.gamma = d.gamma; a.per_sample = d.per_sample;
-    hipLaunchKernelGGL(learner_grad_kernel, dim3(learner_groups(L, q.n)), dim3(kLW), learner_lds_bytes(L, R), st, a);
+    a.entropy_coef = d.entropy_coef; a.entropy = d.entropy;
+    if (d.entropy_coef != 0.0f || d.entropy)
+        hipLaunchKernelGGL(learner_grad_reg_kernel, dim3(learner_groups(L, q.n)), dim3(kLW), learner_lds_bytes(L, R), st, a);
+    else
+        hipLaunchKernelGGL(learner_grad_kernel, dim3(learner_groups(L, q.n)), dim3(kLW), learner_lds_bytes(L, R), st, a);
     return hipGetLastError();
 }
 
@@ -412,8 +546,22 @@ hipError_t launch_scale_adam(const LearnerDevice &d, const float *src, int count
                        d.opt.status, d.opt.errors, d.opt.steps, d.scal, actor_loss, critic_loss);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
+    const float *scal = d.scal;
+    if (std::isfinite(d.max_norm[0]) || std::isfinite(d.max_norm[1])) {
+        // the clip: the scaled gradient once into gsum, its norms, then Adam over (gsum, one row, the coefficients).
+        // 0.0f + g == g for the moments and the parameters: where g is -0 the sum is +0, and adam_element gives the
+        // same m, v and w from either zero.
+        const int groups = learner_clip_groups(L);
+        hipLaunchKernelGGL(learner_gradsum_kernel, dim3(groups), dim3(kClipThreads), 0, st, src, count, stride, L,
+                           d.opt.status, d.scal, d.gsum, d.sq);
+        if ((e = hipGetLastError()) != hipSuccess) return e;
+        hipLaunchKernelGGL(learner_clip_kernel, dim3(1), dim3(64), 0, st, d.sq, groups, d.max_norm[0], d.max_norm[1],
+                           d.opt.status, d.coef, d.grad_norm);
+        if ((e = hipGetLastError()) != hipSuccess) return e;
+        src = d.gsum; count = 1; stride = (size_t)L.P; scal = d.coef;
+    }
     hipLaunchKernelGGL(learner_adam_kernel, dim3((L.P + 255) / 256), dim3(256), 0, st, d.params, d.opt.m, d.opt.v, src,
-                       count, stride, L, d.opt.status, d.opt.steps, d.scal, d.actor_lr, d.critic_lr);
+                       count, stride, L, d.opt.status, d.opt.steps, scal, d.actor_lr, d.critic_lr);
     return hipGetLastError();
 }
 

@@ -177,6 +177,9 @@ SIGNATURES = {
     "uavtrack_learner_apply": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
     "uavtrack_learner_write_priorities": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64] + [C.c_void_p] * 3),
     "uavtrack_learner_check": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64), C.c_void_p]),
+    "uavtrack_learner_set_regularisation": (C.c_int, [C.c_void_p, C.c_double, C.c_double, C.c_double]),
+    "uavtrack_learner_get_regularisation": (C.c_int, [C.c_void_p, C.POINTER(C.c_double)]),
+    "uavtrack_learner_set_diagnostics": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     "uavtrack_pmi_trainer_create": (C.c_int, [C.POINTER(PmiTrainerConfig), C.POINTER(C.c_void_p)]),
     "uavtrack_pmi_trainer_destroy": (C.c_int, [C.c_void_p]),
     "uavtrack_pmi_trainer_num_params": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),

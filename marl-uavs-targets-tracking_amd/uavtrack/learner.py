@@ -22,6 +22,17 @@ Means divide by n, not by sum w; td_delta and the priorities written back stay t
 several rings or ranks in one update, each row's weights are normalised by that draw's own maximum, as K independent
 sample() calls would do.  Without them (the default) every call is bit for bit what it was: the reference's update does
 not use the weights its sample() returns.
+
+Regularisation (entropy_coef, max_grad_norm; both off by default, and then every call is bit for bit what it was):
+    actor_loss, "per_sample"   = mean_i(w_i (-log p_i delta_i - c H_i)),  H_i = -sum_o p_io log p_io,  c = entropy_coef
+and, per network, torch.nn.utils.clip_grad_norm_(net.parameters(), max_norm) on the gradient Adam is about to see:
+coef = min(1, max_norm / (norm + 1e-6)), the norm taken in float64 in a fixed order, so a split or data-parallel update
+clips by the same bits everywhere and an update that does not clip is bit for bit the unclipped one.  The entropy bonus
+exists for loss="per_sample" only (the reference form scales the actor's sums once by -mean(delta) / N, which an entropy
+term cannot share); clipping works with both forms and with apply, where the norm is that of the summed rows.  Gradient
+rows carry no settings: learners that share an update (ranks, shards) must be given equal ones
+(sharding.broadcast_learner copies them).  enable_diagnostics() installs two device buffers, the per-row entropies and
+the two gradient norms before clipping; reading them is a torch reduction of the caller's.
 """
 from __future__ import annotations
 
@@ -75,7 +86,7 @@ class DeviceActorCritic(Handle):
 
     def __init__(self, state_dim: int = 12, hidden_dim: int = 128, action_dim: int = 12, actor_lr: float = 1e-4,
                  critic_lr: float = 5e-4, gamma: float = 0.95, device="cuda:0", loss: str = "reference",
-                 max_batch: int = 0):
+                 max_batch: int = 0, entropy_coef: float = 0.0, max_grad_norm=None):
         if state_dim != _lib.OBS_DIM:
             raise ValueError(f"state_dim must be {_lib.OBS_DIM} (the environment's observation), got {state_dim}")
         if loss not in _lib.LOSS_FORMS:
@@ -83,6 +94,7 @@ class DeviceActorCritic(Handle):
         self.device = current_device(device)
         self.hidden_dim, self.action_dim, self.gamma, self.loss = int(hidden_dim), int(action_dim), float(gamma), loss
         self.actor_lr, self.critic_lr = float(actor_lr), float(critic_lr)
+        self._max_batch = int(max_batch)
         # host-side modules: the reference's layouts, default initialisation, and the format of state dicts
         self._actor = ActorMLP(state_dim, self.hidden_dim, self.action_dim)
         self._critic = ValueMLP(state_dim, self.hidden_dim)
@@ -94,6 +106,51 @@ class DeviceActorCritic(Handle):
         self.num_params = n.value
         self.row_floats = row_floats(self.hidden_dim, self.action_dim)     # = uavtrack_learner_row_floats
         self._set_params(flat(self._params()))
+        self._entropy = self.grad_norm = None
+        if entropy_coef != 0.0 or max_grad_norm is not None:
+            self.set_regularisation(entropy_coef, max_grad_norm)
+
+    # ---- regularisation and its diagnostics
+    def set_regularisation(self, entropy_coef: float = 0.0, max_grad_norm=None) -> None:
+        """The entropy bonus c >= 0 (loss="per_sample" only) and the gradient-norm clip: max_grad_norm is one float for
+        both networks, an (actor, critic) pair, or None / inf for off (also inside the pair).  Host-side settings that
+        hold for every update, grad_from and apply enqueued afterwards; a captured graph keeps the ones it was captured
+        with.  A refused call (a NaN or negative value, a norm of 0, an entropy bonus on loss="reference") raises and
+        changes nothing."""
+        pair = max_grad_norm if isinstance(max_grad_norm, (tuple, list)) else (max_grad_norm, max_grad_norm)
+        if len(pair) != 2:
+            raise ValueError(f"max_grad_norm must be a float or an (actor, critic) pair, got {max_grad_norm!r}")
+        a, c = (float("inf") if x is None else float(x) for x in pair)
+        _lib.check(self._lib.uavtrack_learner_set_regularisation(self._h, float(entropy_coef), a, c),
+                   "uavtrack_learner_set_regularisation")
+
+    def get_regularisation(self):
+        """(entropy_coef, actor_max_norm, critic_max_norm) as last set; inf = no clipping."""
+        out = (C.c_double * 3)()
+        _lib.check(self._lib.uavtrack_learner_get_regularisation(self._h, out), "uavtrack_learner_get_regularisation")
+        return tuple(out)
+
+    def enable_diagnostics(self, max_batch: Optional[int] = None) -> None:
+        """Allocates and installs the two diagnostic buffers: per-row entropies for batches of up to max_batch rows
+        (default: the learner's max_batch, or 65536) and the two gradient norms.  Afterwards entropy(n) is H_i of the
+        last update's or grad_from's first n rows (whatever entropy_coef is) and grad_norm the [2] tensor of the actor's
+        and critic's norms before clipping, written by every update or apply that clips (NaN before the first one and
+        for a refused one).  Installing them changes no other result; no call synchronises."""
+        rows = int(max_batch) if max_batch else (self._max_batch or 65536)
+        self._entropy = torch.zeros(rows, device=self.device)
+        self.grad_norm = torch.full((2,), float("nan"), device=self.device)
+        _lib.check(self._lib.uavtrack_learner_set_diagnostics(self._h, _ptr(self._entropy), rows, _ptr(self.grad_norm)),
+                   "uavtrack_learner_set_diagnostics")
+
+    def disable_diagnostics(self) -> None:
+        _lib.check(self._lib.uavtrack_learner_set_diagnostics(self._h, None, 0, None), "uavtrack_learner_set_diagnostics")
+        self._entropy = self.grad_norm = None
+
+    def entropy(self, n: int) -> torch.Tensor:
+        """H_i of the first n rows of the last batch (enable_diagnostics first)."""
+        if self._entropy is None:
+            raise RuntimeError("entropy: call enable_diagnostics() first")
+        return self._entropy[:int(n)]
 
     def _params(self):
         return list(self._actor.parameters()) + list(self._critic.parameters())

@@ -202,8 +202,10 @@ def gather_learner_rows(row, group=None):
 
 
 def broadcast_learner(learner, group=None, src: int = 0) -> None:
-    """Rank `src`'s parameters, Adam moments and step counts to every rank of `group` (src is a global rank), so that
-    the ranks' learners start equal.  Synchronises; meant for start-up and checkpoint loads, not the training loop."""
+    """Rank `src`'s parameters, Adam moments, step counts and regularisation settings (entropy_coef and the two max
+    norms) to every rank of `group` (src is a global rank), so that the ranks' learners start equal.  Gradient rows carry
+    no settings, so ranks that share updates must hold equal ones: change them on every rank alike afterwards, or
+    broadcast again.  Synchronises; meant for start-up and checkpoint loads, not the training loop."""
     import numpy as np
     import torch
     import torch.distributed as dist
@@ -212,7 +214,8 @@ def broadcast_learner(learner, group=None, src: int = 0) -> None:
     m, v, steps = learner._optim_state()
     # one int32 block: the three float blobs as bit views, then the step counts
     blk = torch.from_numpy(np.concatenate([learner._get_params().view(np.int32), m.view(np.int32), v.view(np.int32),
-                                           np.ascontiguousarray(steps, np.int64).view(np.int32)]))
+                                           np.ascontiguousarray(steps, np.int64).view(np.int32),
+                                           np.array(learner.get_regularisation(), np.float64).view(np.int32)]))
     if dist.get_backend(group) != "gloo":
         blk = blk.to(learner.device)
     dist.broadcast(blk, src=src, group=group)
@@ -221,7 +224,9 @@ def broadcast_learner(learner, group=None, src: int = 0) -> None:
     learner._set_params(np.ascontiguousarray(blk[:P]).view(np.float32))
     learner._set_optim_state(np.ascontiguousarray(blk[P:2 * P]).view(np.float32),
                               np.ascontiguousarray(blk[2 * P:3 * P]).view(np.float32),
-                              np.ascontiguousarray(blk[3 * P:]).view(np.int64))
+                              np.ascontiguousarray(blk[3 * P:-6]).view(np.int64))
+    c, a_max, c_max = np.ascontiguousarray(blk[-6:]).view(np.float64)
+    learner.set_regularisation(float(c), (float(a_max), float(c_max)))
 
 
 # ---------------------------------------------------------------------------------------------------------------------

@@ -9,6 +9,11 @@ backwards: actor fc2 weight + input gradients 2 x 2n(H A), fc1 weight gradient 2
 softmax, losses and Adam are not counted.
 
     python tools/learner_rate.py [--quick]
+    python tools/learner_rate.py --regularised [--quick]
+
+--regularised times the device update alone (loss="per_sample") under four settings of
+DeviceActorCritic.set_regularisation: everything off, the entropy bonus on, clipping on, both.  "off" enqueues the
+launches of the plain update; the clip adds two small launches and one more pass over P floats.
 """
 import argparse
 import json
@@ -45,21 +50,60 @@ def timed(fn, reps, runs):
     return ts[len(ts) // 2], ts
 
 
+def make_batch(n, A, dev):
+    g = torch.Generator(device=dev); g.manual_seed(0)
+    return {"states": torch.rand(n, 12, device=dev, generator=g) * 2 - 1,
+            "actions": torch.randint(0, A, (n,), device=dev, generator=g, dtype=torch.int32),
+            "rewards": torch.rand(n, device=dev, generator=g) * 4 - 2,
+            "next_states": torch.rand(n, 12, device=dev, generator=g) * 2 - 1}
+
+
+# --regularised: (name, entropy_coef, max_grad_norm); 1e-3 is far below the gradient norms of this batch, so both
+# networks are clipped (the clip chain costs the same whether it clips or not)
+SETTINGS = (("off", 0.0, None), ("entropy", 0.01, None), ("clip", 0.0, 1e-3), ("both", 0.01, 1e-3))
+
+
+def regularised(args, grid, dev, A):
+    for n, H in grid:
+        store = {k: v.contiguous() for k, v in make_batch(n, A, dev).items()}
+        out = {"n": n, "H": H, "A": A, "loss": "per_sample"}
+        for name, c, mgn in SETTINGS:
+            L = uavtrack.DeviceActorCritic(12, H, A, 1e-4, 5e-4, 0.95, dev, loss="per_sample", max_batch=n)
+            if name != "off":                 # "off" makes no call an older build of the library lacks
+                L.set_regularisation(c, mgn)
+
+            def dstep():
+                L._run(n, store, n, None, None)
+            for _ in range(10):
+                dstep()
+            torch.cuda.synchronize()
+            t, runs = timed(dstep, args.reps, args.runs)
+            L.check()
+            out[name + "_us"] = round(t, 1)
+            out[name + "_runs_us"] = [round(x, 1) for x in runs]
+            L.close()
+        print(json.dumps(out), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--quick", action="store_true", help="n 65536, H 128 only")
+    ap.add_argument("--regularised", action="store_true",
+                    help="time the device update with the entropy bonus and the gradient-norm clip off / on")
+    ap.add_argument("--settings", default=None, help="--regularised: a comma-separated subset of off,entropy,clip,both")
     ap.add_argument("--reps", type=int, default=100)
     ap.add_argument("--runs", type=int, default=5)
     args = ap.parse_args()
     dev = "cuda:0"
     A = 12
     grid = [(65536, 128)] if args.quick else [(n, H) for H in (64, 128, 256) for n in (4096, 65536, 262144)]
+    if args.regularised:
+        if args.settings:
+            global SETTINGS
+            SETTINGS = tuple(x for x in SETTINGS if x[0] in args.settings.split(","))
+        return regularised(args, grid, dev, A)
     for n, H in grid:
-        g = torch.Generator(device=dev); g.manual_seed(0)
-        batch = {"states": torch.rand(n, 12, device=dev, generator=g) * 2 - 1,
-                 "actions": torch.randint(0, A, (n,), device=dev, generator=g, dtype=torch.int32),
-                 "rewards": torch.rand(n, device=dev, generator=g) * 4 - 2,
-                 "next_states": torch.rand(n, 12, device=dev, generator=g) * 2 - 1}
+        batch = make_batch(n, A, dev)
         actor, critic = uavtrack.ActorMLP(12, H, A).to(dev), ValueNet(12, H).to(dev)
         oa, oc = torch.optim.Adam(actor.parameters(), lr=1e-4), torch.optim.Adam(critic.parameters(), lr=5e-4)
 
