@@ -14,6 +14,7 @@ update is the same rule on a sampled batch, and the new actor weights are re-upl
     python examples/train_maac.py --replay prioritized --learner device --envs 4096 --n-uav 20   # prioritised ring, 32.8 M slots
     python examples/train_maac.py --replay prioritized --learner device --publish device --log-every 10   # no host sync per iteration
     python examples/train_maac.py --replay prioritized --learner device --importance --beta-final 1.0     # train on the importance weights, beta annealed on the device
+    python examples/train_maac.py --replay prioritized --learner device --n-step 3                        # 3-step returns folded by the ring's add
     python examples/train_maac.py --method maac-r --pmi-trainer device --learner device --replay prioritized --publish device --log-every 10
     python examples/train_maac.py --shards 8 --envs 32768 --n-uav 20 --learner device --replay prioritized --publish device   # 8 shard handles, one learner
     python examples/train_maac.py --shards 4 --method maac-r --pmi-trainer device --learner device --replay prioritized --publish device   # ... and one PMI trainer
@@ -60,9 +61,10 @@ def update(actor, critic, opt_a, opt_c, batch, gamma, weights=None, entropy_coef
     """One ActorCritic.update step (actor_critic.py:150-178) on a batch of transitions.  weights (--importance): the
     draw's importance weights, one per row, multiplied into the per-sample losses before the mean.  entropy_coef and
     max_grad_norm: the two terms of DeviceActorCritic.set_regularisation, so that --learner torch and --learner device
-    stay comparable; diag (a dict) receives the mean entropy and the two gradient norms before clipping."""
+    stay comparable; diag (a dict) receives the mean entropy and the two gradient norms before clipping.  A batch from an
+    n-step ring (--n-step) carries "discounts", gamma^m per row, which take gamma's place in the target."""
     s, a, r, s2 = batch["states"], batch["actions"].long().unsqueeze(1), batch["rewards"], batch["next_states"]
-    td_target = r + gamma * critic(s2)
+    td_target = r + batch.get("discounts", gamma) * critic(s2)
     td_delta = td_target - critic(s)
     probs = actor(s)
     log_probs = torch.log(probs.gather(1, a).squeeze(1).clamp_min(1e-12))
@@ -101,6 +103,11 @@ def device_learner(args, uavtrack, na_total, dev, max_batch):
     if regularised(args):
         learner.enable_diagnostics(max_batch)
     return learner
+
+
+def nstep_ring(args, ring):
+    """--n-step N > 1: the ring stores N-step returns and their discounts (with_nstep); N = 1 leaves it what it was."""
+    return ring.with_nstep(args.n_step, args.gamma) if args.n_step > 1 else ring
 
 
 def regularised(args):
@@ -203,6 +210,7 @@ def train_sharded(args, timings=None):
     else:                                                             # uniform-device
         rings = [uavtrack.ReplayRing(2 * e.cfg.n_envs * args.n_uav * args.steps, dev, seed=args.seed + 7919 * k,
                                      max_batch=per_shard) for k, e in enumerate(envs)]
+    rings = [nstep_ring(args, ring) for ring in rings]
     per_iter = args.envs * args.n_uav * args.steps
     stats = [uavtrack.EpisodeStats(e, log_capacity=e.cfg.n_envs * args.log_every, max_steps=args.steps) for e in envs]
     kept = {k: [] for k in SIX}
@@ -317,6 +325,11 @@ def main(argv=None, timings=None):
                          "prioritized: uavtrack.PrioritizedReplayRing (the reference's PrioritizedReplayBuffer, "
                          "train.py:73-139), added to from the rollout and drawn from in HIP, |td_delta| written back as the "
                          "new priorities")
+    ap.add_argument("--n-step", type=int, default=1,
+                    help="N > 1: train on N-step targets.  The ring's add folds each transition's next N rewards (never "
+                         "across an episode end or the rollout's last step) and keeps gamma^m per slot "
+                         "(ring.with_nstep(N, gamma)); both learners bootstrap with that discount.  Needs --replay "
+                         "prioritized or uniform-device")
     ap.add_argument("--alpha", type=float, default=0.6, help="--replay prioritized: priority exponent (train.py:74)")
     ap.add_argument("--beta", type=float, default=0.4, help="--replay prioritized: importance exponent (train.py:100)")
     ap.add_argument("--importance", action="store_true",
@@ -370,6 +383,11 @@ def main(argv=None, timings=None):
         ap.error("--rollout-episodes K > 1 runs on one environment handle (no --shards)")
     if args.phase == "run" and args.method == "maac-r":
         ap.error("--phase run is the C-METHOD baseline: it runs with the maac / maac-g rewards")
+    if not 1 <= args.n_step <= 64:
+        ap.error("--n-step must be in [1, 64]")
+    if args.n_step > 1 and args.replay == "uniform":
+        ap.error("--n-step N > 1 needs --replay prioritized or --replay uniform-device: the n-step returns are folded by "
+                 "the device rings' add (the PyTorch buffer of --replay uniform stores one-step transitions)")
     if args.importance and args.replay != "prioritized":
         ap.error("--importance needs --replay prioritized (a uniform draw has no importance weights)")
     if args.beta_final is not None and not args.importance:
@@ -428,6 +446,8 @@ def main(argv=None, timings=None):
                                                 max_batch=args.batch)
     elif args.replay == "uniform-device":
         replay = uavtrack.ReplayRing(2 * per_iter, dev, seed=args.seed, max_batch=args.batch)
+    if args.replay != "uniform":
+        replay = nstep_ring(args, replay)
     else:
         replay = uavtrack.DeviceReplayBuffer(capacity=2 * per_iter, device=dev)
     stats = uavtrack.EpisodeStats(env, log_capacity=args.envs * K * args.log_every, max_steps=T)
@@ -462,7 +482,7 @@ def main(argv=None, timings=None):
                 la, lc = update(actor, critic, opt_a, opt_c, batch, args.gamma, w if args.importance else None, **reg_kw)
                 with torch.no_grad():
                     s, r, s2 = batch["states"], batch["rewards"], batch["next_states"]
-                    replay.update_priorities(idx, (r + args.gamma * critic(s2) - critic(s)).abs())
+                    replay.update_priorities(idx, (r + batch.get("discounts", args.gamma) * critic(s2) - critic(s)).abs())
         elif learner is None:
             for _ in range(args.updates):
                 la, lc = update(actor, critic, opt_a, opt_c, replay.sample(args.batch), args.gamma, **reg_kw)

@@ -539,7 +539,8 @@ int uavtrack_learner_update_weighted(uavtrack_learner *learner, int64_t n,
  *   [P, P+4)    the loss sums: sum -log p, sum delta, sum -log p * delta, sum (V - target)^2
  *   P+4, P+5    n of this row, an int64 as its low and high 32 bits
  *   P+6         int32 status bits of this row: bit 0 an action outside [0, A), bit 1 an index outside [0, capacity),
- *               bit 2 an importance weight that is NaN, infinite or negative
+ *               bit 2 an importance weight that is NaN, infinite or negative, bit 3 (value 8) a discount that is NaN,
+ *               negative or above 1 (see "multi-step targets: per-row discounts")
  *   P+7         int32 P, the layout tag
  * The reference's actor loss mean(-log p) * mean(delta) is linear in mean(delta), which is why the rows can be summed:
  * the apply scales the actor's sums once by the GLOBAL -mean(delta) / N.  (Averaging per-row updates or per-row loss
@@ -630,8 +631,36 @@ int uavtrack_learner_get_regularisation(uavtrack_learner *learner, double out[3]
  *             that clips (at least one finite max norm; a huge finite one observes without clipping), NaN for a refused one. */
 int uavtrack_learner_set_diagnostics(uavtrack_learner *learner, float *entropy, int64_t capacity_rows, float *grad_norm);
 
+/* ---- multi-step targets: per-row discounts ----
+ * The target of batch row i becomes
+ *   y_i = r_i + d_i * V(s'_i),   d_i = discounts[slot of row i],   delta_i = y_i - V(s_i)
+ * discounts is a DEVICE fp32 [capacity] store, indexed by SLOT and gathered through the same index vector as the reward
+ * (slot indices[i], or slot i without indices) -- unlike the importance weights, which are in batch order.  It is the
+ * fifth store of an n-step ring (uavtrack_replay_add_rollout_nstep leaves gamma^m there, m the transition's horizon), but
+ * any per-slot factor in [0, 1] will do: d_i = 0 means "do not bootstrap", which a caller can use to mark a true terminal
+ * state.  Everything downstream of delta and y is unchanged: both loss forms, the weights, the entropy term, clipping,
+ * td_delta and the priorities.  discounts == NULL means d_i = (float)gamma of the learner's config, the expression of
+ * uavtrack_learner_update, and a store filled with (float)gamma gives the same bits.  weights and discounts are each
+ * nullable; with both NULL the two calls below are exactly uavtrack_learner_update and uavtrack_learner_grad.
+ * A d_i that is NaN, negative or above 1 is found on the device like a bad action: status bit 3 (value 8) in the status
+ * word and in word P + 6 of a gradient row; the update or apply then changes nothing, its losses are NaN, the next
+ * uavtrack_learner_check counts it, and uavtrack_learner_write_priorities stays gated on that verdict.  A gradient row
+ * keeps its P + 8 words and its tag, and rows with and without discounts may meet in one apply.  Host-side errors are
+ * those of uavtrack_learner_update_weighted / _grad_weighted. */
+int uavtrack_learner_update_discounted(uavtrack_learner *learner, int64_t n,
+                                       const float *states, const int32_t *actions, const float *rewards,
+                                       const float *next_states, int64_t capacity, const int64_t *indices,
+                                       const float *weights, const float *discounts,
+                                       float *actor_loss, float *critic_loss, float *td_delta, float *priorities,
+                                       void *stream);
+int uavtrack_learner_grad_discounted(uavtrack_learner *learner, int64_t n,
+                                     const float *states, const int32_t *actions, const float *rewards,
+                                     const float *next_states, int64_t capacity, const int64_t *indices,
+                                     const float *weights, const float *discounts, float *td_delta, float *row,
+                                     void *stream);
+
 /* Synchronises `stream`; fails if any update or apply since the previous check was refused on the device (bad action,
- * index or importance weight, or a row of another layout).  refused (nullable) receives their number; the count restarts at 0. */
+ * index, importance weight or discount, or a row of another layout).  refused (nullable) receives their number; the count restarts at 0. */
 int uavtrack_learner_check(uavtrack_learner *learner, int64_t *refused, void *stream);
 
 /* ---- the PMI trainer: PMINetwork.train_pmi + its Adam steps on the device ----
@@ -839,6 +868,39 @@ int uavtrack_replay_add_rollout_episodes(uavtrack_replay *replay, const uavtrack
                                          int64_t envs, int64_t n_uav, const float *obs_in, const float *obs,
                                          const int32_t *actions, const float *reward, const uint8_t *done,
                                          const float *start_obs, void *stream);
+
+/* ---- multi-step targets: n-step returns from one rollout ----
+ * uavtrack_replay_add_rollout_episodes with each transition's reward folded over the next n steps of its agent.
+ * A rollout has steps = T and envs * n_uav agents per step; transition (t, b, i) is flattened as
+ * f = t * agents + b * n_uav + i, the order of uavtrack_replay_add_rollout.  n = n_step in
+ * [1, UAVTRACK_REPLAY_MAX_NSTEP]; g = (float)gamma, gamma finite and in [0, 1].
+ *   Horizon.  m(t, b) is the smallest m >= 1 for which one of these holds: m == n, t + m == T, or
+ *     done[t + m - 1][b] != 0.  A window never crosses an episode end, and it is cut at the rollout's last step, so every
+ *     step still yields exactly one transition.  Without done only the first two conditions apply.  The horizon depends
+ *     on (t, b) alone.
+ *   Return.  fp32 Horner from the far end, every multiply and add rounded on its own (no fused multiply-add):
+ *     R = reward[t + m - 1][b][i]; for k = m - 2 ... 0: R = reward[t + k][b][i] + g * R.
+ *   Discount.  d = g; then d = d * g exactly m - 1 times, in fp32.
+ *   Stored transition.  state: exactly what uavtrack_replay_add_rollout_episodes stores for (t, b, i) -- obs_in at t == 0,
+ *     start_obs[t - 1] behind a fired done, obs[t - 1] otherwise; action = actions[t][b][i]; reward = R;
+ *     next_state = obs[t + m - 1][b][i] (at an episode end that episode's last observation, which is what the one-step
+ *     form bootstraps from); discount = d, written to discounts [capacity], a caller-owned DEVICE fp32 array passed
+ *     beside the ring (the ring struct keeps its size).  The slot is that of the other adds: only the last
+ *     min(T * agents, capacity) transitions are written (their windows still look ahead into rows that are themselves
+ *     not written), from slot (pos + max(0, T * agents - capacity)) % capacity on, wrapping, the priorities at the
+ *     device-side maximum.
+ * With n == 1: m == 1 everywhere, R is the reward's bits and d is g's bits; the four stores and the priorities end
+ * byte-identical to uavtrack_replay_add_rollout_episodes, and with done == NULL to uavtrack_replay_add_rollout.
+ * done and start_obs are either both given or both NULL.  One thread handles one transition: it reads at most n rewards
+ * and n - 1 done bytes, one next-state row and its state row.  Stream-ordered, no synchronisation, no allocation,
+ * capturable.  Returns an error, enqueuing nothing, for a null required pointer, n_step outside
+ * [1, UAVTRACK_REPLAY_MAX_NSTEP], gamma not finite or outside [0, 1], exactly one of done and start_obs given, a ring
+ * outside its limits, or a row array that is not 16-byte aligned. */
+#define UAVTRACK_REPLAY_MAX_NSTEP 64
+int uavtrack_replay_add_rollout_nstep(uavtrack_replay *replay, const uavtrack_replay_ring *ring, float *discounts,
+                                      int64_t steps, int64_t envs, int64_t n_uav, const float *obs_in, const float *obs,
+                                      const int32_t *actions, const float *reward, const uint8_t *done,
+                                      const float *start_obs, int32_t n_step, double gamma, void *stream);
 
 /* PrioritizedReplayBuffer.sample's draw (train.py:98-112) without the gather: n slots with replacement from
  * P(i) = p_i^alpha / sum_j p_j^alpha over [0, count) (the draw stream above) into indices [n] (DEVICE int64), and,

@@ -1485,10 +1485,10 @@ int accept_entropy_rows(const char *fn, const uavtrack_learner *l, int64_t n)
 // the fields uavtrack_learner_update and _grad (and their weighted forms) fill alike; the others are null
 LearnerLaunch learner_batch(int64_t n, const float *states, const int32_t *actions, const float *rewards,
                             const float *next_states, int64_t capacity, const int64_t *indices, const float *weights,
-                            float *td_delta)
+                            const float *discounts, float *td_delta)
 {
     LearnerLaunch q = {};
-    q.n = n; q.capacity = capacity; q.td_delta = td_delta; q.weights = weights;
+    q.n = n; q.capacity = capacity; q.td_delta = td_delta; q.weights = weights; q.discounts = discounts;
     q.states = states; q.rewards = rewards; q.next_states = next_states; q.actions = actions; q.idx = indices;
     return q;
 }
@@ -1694,10 +1694,10 @@ int uavtrack_learner_get_optimizer_state(uavtrack_learner *learner, float *exp_a
 
 namespace {
 
-// uavtrack_learner_update and _update_weighted (`fn`: the caller's name; weights nullable)
+// uavtrack_learner_update, _update_weighted and _update_discounted (`fn`: the caller's name; weights, discounts nullable)
 int learner_update(const char *fn, uavtrack_learner *learner, int64_t n, const float *states, const int32_t *actions,
                    const float *rewards, const float *next_states, int64_t capacity, const int64_t *indices,
-                   const float *weights, float *actor_loss, float *critic_loss, float *td_delta, float *priorities,
+                   const float *weights, const float *discounts, float *actor_loss, float *critic_loss, float *td_delta, float *priorities,
                    void *stream)
 {
     if (!learner) return fail("%s: null handle", fn);
@@ -1706,16 +1706,16 @@ int learner_update(const char *fn, uavtrack_learner *learner, int64_t n, const f
     if (!actor_loss || !critic_loss) return fail("%s: actor_loss and critic_loss must not be null", fn);
     if (accept_batch(fn, learner, n, capacity, indices, "from") || accept_entropy_rows(fn, learner, n)) return 1;
     ON_DEVICE(learner->cfg.device_id);
-    LearnerLaunch q = learner_batch(n, states, actions, rewards, next_states, capacity, indices, weights, td_delta);
+    LearnerLaunch q = learner_batch(n, states, actions, rewards, next_states, capacity, indices, weights, discounts, td_delta);
     q.actor_loss = actor_loss; q.critic_loss = critic_loss; q.priorities = priorities;
     HIP_TRY(launch_learner_update(learner->d, q, static_cast<hipStream_t>(stream)));
     return 0;
 }
 
-// uavtrack_learner_grad and _grad_weighted
+// uavtrack_learner_grad, _grad_weighted and _grad_discounted
 int learner_grad(const char *fn, uavtrack_learner *learner, int64_t n, const float *states, const int32_t *actions,
                  const float *rewards, const float *next_states, int64_t capacity, const int64_t *indices,
-                 const float *weights, float *td_delta, float *row, void *stream)
+                 const float *weights, const float *discounts, float *td_delta, float *row, void *stream)
 {
     if (!learner) return fail("%s: null handle", fn);
     if (!states || !actions || !rewards || !next_states)
@@ -1723,7 +1723,8 @@ int learner_grad(const char *fn, uavtrack_learner *learner, int64_t n, const flo
     if (!td_delta || !row) return fail("%s: td_delta and row must not be null", fn);
     if (accept_batch(fn, learner, n, capacity, indices, "from") || accept_entropy_rows(fn, learner, n)) return 1;
     ON_DEVICE(learner->cfg.device_id);
-    const LearnerLaunch q = learner_batch(n, states, actions, rewards, next_states, capacity, indices, weights, td_delta);
+    const LearnerLaunch q = learner_batch(n, states, actions, rewards, next_states, capacity, indices, weights, discounts,
+                                          td_delta);
     HIP_TRY(launch_learner_grad(learner->d, q, row, static_cast<hipStream_t>(stream)));
     return 0;
 }
@@ -1736,7 +1737,7 @@ int uavtrack_learner_update(uavtrack_learner *learner, int64_t n, const float *s
                             const float *rewards, const float *next_states, int64_t capacity, const int64_t *indices,
                             float *actor_loss, float *critic_loss, float *td_delta, float *priorities, void *stream)
 {
-    return learner_update(__func__, learner, n, states, actions, rewards, next_states, capacity, indices, nullptr,
+    return learner_update(__func__, learner, n, states, actions, rewards, next_states, capacity, indices, nullptr, nullptr,
                           actor_loss, critic_loss, td_delta, priorities, stream);
 }
 
@@ -1745,7 +1746,17 @@ int uavtrack_learner_update_weighted(uavtrack_learner *learner, int64_t n, const
                                      const int64_t *indices, const float *weights, float *actor_loss, float *critic_loss,
                                      float *td_delta, float *priorities, void *stream)
 {
-    return learner_update(__func__, learner, n, states, actions, rewards, next_states, capacity, indices, weights,
+    return learner_update(__func__, learner, n, states, actions, rewards, next_states, capacity, indices, weights, nullptr,
+                          actor_loss, critic_loss, td_delta, priorities, stream);
+}
+
+int uavtrack_learner_update_discounted(uavtrack_learner *learner, int64_t n, const float *states, const int32_t *actions,
+                                       const float *rewards, const float *next_states, int64_t capacity,
+                                       const int64_t *indices, const float *weights, const float *discounts,
+                                       float *actor_loss, float *critic_loss, float *td_delta, float *priorities,
+                                       void *stream)
+{
+    return learner_update(__func__, learner, n, states, actions, rewards, next_states, capacity, indices, weights, discounts,
                           actor_loss, critic_loss, td_delta, priorities, stream);
 }
 
@@ -1760,7 +1771,7 @@ int uavtrack_learner_grad(uavtrack_learner *learner, int64_t n, const float *sta
                           const float *rewards, const float *next_states, int64_t capacity, const int64_t *indices,
                           float *td_delta, float *row, void *stream)
 {
-    return learner_grad(__func__, learner, n, states, actions, rewards, next_states, capacity, indices, nullptr,
+    return learner_grad(__func__, learner, n, states, actions, rewards, next_states, capacity, indices, nullptr, nullptr,
                         td_delta, row, stream);
 }
 
@@ -1768,7 +1779,16 @@ int uavtrack_learner_grad_weighted(uavtrack_learner *learner, int64_t n, const f
                                    const float *rewards, const float *next_states, int64_t capacity,
                                    const int64_t *indices, const float *weights, float *td_delta, float *row, void *stream)
 {
-    return learner_grad(__func__, learner, n, states, actions, rewards, next_states, capacity, indices, weights,
+    return learner_grad(__func__, learner, n, states, actions, rewards, next_states, capacity, indices, weights, nullptr,
+                        td_delta, row, stream);
+}
+
+int uavtrack_learner_grad_discounted(uavtrack_learner *learner, int64_t n, const float *states, const int32_t *actions,
+                                     const float *rewards, const float *next_states, int64_t capacity,
+                                     const int64_t *indices, const float *weights, const float *discounts, float *td_delta,
+                                     float *row, void *stream)
+{
+    return learner_grad(__func__, learner, n, states, actions, rewards, next_states, capacity, indices, weights, discounts,
                         td_delta, row, stream);
 }
 
@@ -1803,8 +1823,9 @@ int uavtrack_learner_check(uavtrack_learner *learner, int64_t *refused, void *st
     if (take_refusals(__func__, learner, refused, stream, &count)) return 1;
     if (count)
         return fail("uavtrack_learner_check: %d update(s) refused: an action outside [0, %d), an index outside "
-                    "[0, capacity) or an importance weight that is NaN, infinite or negative, or (uavtrack_learner_apply) "
-                    "a gradient row of another layout; they changed nothing", count, learner->d.L.A);
+                    "[0, capacity), an importance weight that is NaN, infinite or negative or a discount that is NaN or "
+                    "outside [0, 1], or (uavtrack_learner_apply) a gradient row of another layout; they changed nothing",
+                    count, learner->d.L.A);
     return 0;
 }
 
@@ -2133,6 +2154,30 @@ int uavtrack_replay_add_rollout_episodes(uavtrack_replay *replay, const uavtrack
     ON_DEVICE(replay->cfg.device_id);
     HIP_TRY(launch_replay_add(replay->d, ring_view(ring), steps * agents, agents, obs_in, nullptr, obs, actions, reward,
                               static_cast<hipStream_t>(stream), done, start_obs, n_uav));
+    return 0;
+}
+
+int uavtrack_replay_add_rollout_nstep(uavtrack_replay *replay, const uavtrack_replay_ring *ring, float *discounts,
+                                      int64_t steps, int64_t envs, int64_t n_uav, const float *obs_in, const float *obs,
+                                      const int32_t *actions, const float *reward, const uint8_t *done,
+                                      const float *start_obs, int32_t n_step, double gamma, void *stream)
+{
+    const char *fn = "uavtrack_replay_add_rollout_nstep";
+    if (!replay) return fail("%s: null handle", fn);
+    if (accept_ring(replay, fn, ring, true, false)) return 1;
+    if (!discounts || !obs_in || !obs || !actions || !reward)
+        return fail("%s: discounts, obs_in, obs, actions and reward must not be null", fn);
+    if (!done != !start_obs) return fail("%s: done and start_obs must both be given or both be null", fn);
+    if (!aligned16(obs_in) || !aligned16(obs) || !aligned16(start_obs))
+        return fail("%s: obs_in, obs and start_obs must be 16-byte aligned", fn);
+    if (n_step < 1 || n_step > UAVTRACK_REPLAY_MAX_NSTEP)
+        return fail("%s: n_step = %d outside [1, %d]", fn, (int)n_step, UAVTRACK_REPLAY_MAX_NSTEP);
+    if (!(gamma >= 0.0 && gamma <= 1.0)) return fail("%s: gamma = %g is not a finite value in [0, 1]", fn, gamma);
+    if (steps < 1 || envs < 1 || n_uav < 1) return fail("%s: steps, envs and n_uav must be >= 1", fn);
+    if (envs > INT64_MAX / n_uav || steps > INT64_MAX / (envs * n_uav) / 12) return fail("%s: steps * envs * n_uav overflows", fn);
+    ON_DEVICE(replay->cfg.device_id);
+    HIP_TRY(launch_replay_add_nstep(replay->d, ring_view(ring), discounts, steps, envs, n_uav, obs_in, obs, actions, reward,
+                                    done, start_obs, (int)n_step, (float)gamma, static_cast<hipStream_t>(stream)));
     return 0;
 }
 

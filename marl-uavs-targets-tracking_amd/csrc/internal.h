@@ -351,6 +351,7 @@ struct LearnerLaunch {
     const int32_t *actions;
     const int64_t *idx;
     const float *weights;           // nullable [n]: importance weights in batch order
+    const float *discounts;         // nullable [capacity]: per-slot discounts (null: the handle's gamma for every row)
     float *actor_loss, *critic_loss, *td_delta, *priorities;
 };
 int learner_rows_per_tile(int hidden);
@@ -483,6 +484,12 @@ hipError_t launch_replay_add(const ReplayDevice &d, const ReplayRingView &ring, 
                              const float *rewards, hipStream_t stream,
                              // (the rollout crossed episode ends: done [n / agents][agents / n_uav], start_obs [n][12])
                              const uint8_t *done = nullptr, const float *start_obs = nullptr, int64_t n_uav = 1);
+// uavtrack_replay_add_rollout_nstep: one rollout of steps x envs x n_uav transitions with n_step-step returns; done and
+// start_obs both given or both nullptr; discounts [capacity] receives gamma^m per written slot
+hipError_t launch_replay_add_nstep(const ReplayDevice &d, const ReplayRingView &ring, float *discounts, int64_t steps,
+                                   int64_t envs, int64_t n_uav, const float *obs_in, const float *obs,
+                                   const int32_t *actions, const float *reward, const uint8_t *done, const float *start_obs,
+                                   int n_step, float gamma, hipStream_t stream);
 
 // episode_kernel.hip -- per-episode results (uavtrack_episode_stats_*).  The open episodes are struct-of-arrays over the
 // environments; a closing step's log slot comes from a scan over the done matrix in groups of kEpisodeGroup environments

@@ -27,6 +27,10 @@
 // after the sums changes: the means still divide by n, and -(sum w delta / N) / N falls out of the same words.  No
 // weights is the factor 1.0f, an exact multiply, so the unweighted update keeps its bits.
 //
+// Per-row discounts (uavtrack_learner_update_discounted / _grad_discounted): the target of row i is y_i = r_i + d_i V(s'_i)
+// with d_i read from a per-slot store through the row's index, beside the reward (an n-step ring keeps gamma^m there).
+// The tile gather leaves d_i in LDS; no store is d_i = gamma for every row, the same multiply as before.
+//
 // Regularisation (uavtrack_learner_set_regularisation, off by default).  An entropy bonus c > 0 (per-sample form only)
 // makes the actor loss mean_i(w_i (-log p_i delta_i - c H_i)), H_i = -sum_o p_io log p_io: the accumulated logit weight
 // of a row becomes w_i (delta_i (onehot - p_i)_o - c p_io (log p_io + H_i)), still scaled by -1 / N afterwards, and loss
@@ -66,6 +70,8 @@ struct GradArgs {
     int per_sample;
     float entropy_coef;             // c >= 0 (learner_grad_reg_kernel only; c != 0 only with per_sample)
     float *entropy;                 // nullable [n]: H_i of batch row i, 0 for a row that was not used
+    const float *discounts;         // nullable [capacity], slot order: the row's discount d in y = r + d V(s') (null: gamma);
+                                    // status bit 3: a discount that is NaN, negative or above 1
 };
 
 // kReg: the entropy term and the entropy[] store in the per-row block; everything else is one text.
@@ -87,6 +93,7 @@ __device__ __forceinline__ void learner_grad_body(const GradArgs &a)
     float *lt  = vn + R;                    // [R][4]  per-row loss terms
     int *act   = reinterpret_cast<int *>(lt + R * 4);   // [R] action, -1 = row not used
     float *wt  = reinterpret_cast<float *>(act + R);    // [R] importance weight of the row
+    float *dc  = wt + R;                                // [R] discount of the row
 
     const int tid = threadIdx.x;
     const float *W1a = a.params + L.a_w1, *b1a = a.params + L.a_b1, *W2a = a.params + L.a_w2, *b2a = a.params + L.a_b2;
@@ -98,11 +105,11 @@ __device__ __forceinline__ void learner_grad_body(const GradArgs &a)
     const int64_t tiles = (a.n + R - 1) / R;
     for (int64_t t = blockIdx.x; t < tiles; t += gridDim.x) {
         const int64_t row0 = t * R;
-        // ---- gather the tile: states, next states, action, reward, importance weight
+        // ---- gather the tile: states, next states, action, reward, discount, importance weight
         for (int r = tid; r < R; r += kLW) {
             const int64_t i = row0 + r;
             int av = -1;
-            float wi = 1.0f;
+            float wi = 1.0f, di = a.gamma;
             if (i < a.n) {
                 const int64_t src = a.idx ? a.idx[i] : i;
                 if (src < 0 || src >= a.capacity) {
@@ -111,6 +118,10 @@ __device__ __forceinline__ void learner_grad_body(const GradArgs &a)
                     av = a.actions[src];
                     if (av < 0 || av >= A) { atomicOr(a.status, 1); av = -1; }
                     vn[r] = a.rewards[src];               // the reward waits in vn until V' overwrites it
+                    if (a.discounts) {
+                        di = a.discounts[src];
+                        if (!(di >= 0.0f && di <= 1.0f)) { atomicOr(a.status, 8); av = -1; }
+                    }
                 }
                 if (a.weights) {
                     wi = a.weights[i];
@@ -126,6 +137,7 @@ __device__ __forceinline__ void learner_grad_body(const GradArgs &a)
             if (av < 0) vn[r] = 0.0f;
             act[r] = av;
             wt[r] = wi;
+            dc[r] = di;
         }
         __syncthreads();
         // ---- layer 1 of the three forwards
@@ -185,7 +197,7 @@ __device__ __forceinline__ void learner_grad_body(const GradArgs &a)
                 const float inv = 1.0f / sum;
                 const float lse = logf(sum);
                 const float ent = lse - sd * inv;
-                const float target = rew + a.gamma * vn[r];
+                const float target = rew + dc[r] * vn[r];
                 const float v = gv[r];
                 const float delta = target - v;
                 const float wi = wt[r];
@@ -217,7 +229,7 @@ __device__ __forceinline__ void learner_grad_body(const GradArgs &a)
             float sum = 0.0f;
             for (int o = 0; o < A; ++o) { z[o] = expf(z[o] - m); sum += z[o]; }
             const float inv = 1.0f / sum;
-            const float target = rew + a.gamma * vn[r];
+            const float target = rew + dc[r] * vn[r];
             const float v = gv[r];
             const float delta = target - v;
             const float nlp = -logf(z[av] * inv);
@@ -330,8 +342,8 @@ __global__ void learner_finalize_kernel(const float *src, int count, size_t stri
         if (n_given) continue;                                      // a workgroup partial ends here
         const int32_t *tail = reinterpret_cast<const int32_t *>(row) + P + 4;
         const int64_t nr = (int64_t)((uint64_t)(uint32_t)tail[0] | ((uint64_t)(uint32_t)tail[1] << 32));
-        bad |= tail[2] & 7;
-        if (tail[3] != P || nr < 1) bad |= 8;                       // a row of another layout (or not a row at all)
+        bad |= tail[2] & 15;
+        if (tail[3] != P || nr < 1) bad |= 16;                      // a row of another layout (or not a row at all)
         else N += nr;
     }
     if (n_given) bad = *status;
@@ -491,7 +503,7 @@ int learner_rows_per_tile(int hidden)
 
 size_t learner_lds_bytes(const LearnerLayout &L, int rows)
 {
-    return sizeof(float) * ((size_t)L.P + (size_t)rows * (24 + 3 * L.H + L.A + 2 + 4 + 1)) + sizeof(int) * (size_t)rows;
+    return sizeof(float) * ((size_t)L.P + (size_t)rows * (24 + 3 * L.H + L.A + 2 + 4 + 2)) + sizeof(int) * (size_t)rows;
 }
 
 int learner_groups(const LearnerLayout &L, int64_t n)
@@ -528,7 +540,7 @@ hipError_t launch_grad(const LearnerDevice &d, const LearnerLaunch &q, float *td
     a.actions = q.actions; a.idx = q.idx; a.weights = q.weights; a.n = q.n; a.capacity = q.capacity;
     a.partials = d.partials; a.td_delta = td; a.status = status;
     a.L = L; a.rows = R; a.gamma = d.gamma; a.per_sample = d.per_sample;
-    a.entropy_coef = d.entropy_coef; a.entropy = d.entropy;
+    a.entropy_coef = d.entropy_coef; a.entropy = d.entropy; a.discounts = q.discounts;
     if (d.entropy_coef != 0.0f || d.entropy)
         hipLaunchKernelGGL(learner_grad_reg_kernel, dim3(learner_groups(L, q.n)), dim3(kLW), learner_lds_bytes(L, R), st, a);
     else

@@ -33,6 +33,9 @@
 // The episodes form (a rollout that crossed episode ends, uavtrack_replay_add_rollout_episodes) writes the fresh state's
 // observation, start_obs[f], as the state of f + agents instead wherever the done flag of f's environment-step fired.
 // A ring without priorities (ring.priorities == nullptr, a uniform ring) skips the reductions and the priority write.
+// The n-step form (uavtrack_replay_add_rollout_nstep) has a write kernel of its own, replay_write_nstep_kernel: one thread
+// per transition, which folds up to n rewards of its agent into the stored reward, takes the next state from the end of
+// that window and leaves the window's discount in a fifth per-slot store.
 
 #include "internal.h"
 #include "philox.h"
@@ -417,7 +420,79 @@ __global__ void __launch_bounds__(kSW) replay_write_kernel(AddArgs a)
     }
 }
 
+// ---- the n-step add (uavtrack_replay_add_rollout_nstep; include/uavtrack.h has the definitions)
+
+struct NstepArgs {
+    ReplayRingView ring;
+    float *discounts;                          // [capacity]
+    const float *obs_in, *obs, *reward;        // [agents][12], [steps][agents][12], [steps][agents]
+    const int32_t *actions;
+    const uint8_t *done;                       // nullable [steps][envs]
+    const float *start_obs;                    // [steps][agents][12], read only where done fired
+    const float *top;
+    int64_t n, agents, envs, n_uav, steps, skip, start;
+    int n_step;
+    float g;
+};
+
+// One thread per transition f = t * agents + b * n_uav + i, lanes consecutive in (b, i): for a fixed k the wavefront's
+// reads of reward[t + k] are one line, and done[t + k][b] is shared by an environment's lanes.  A thread reads at most
+// n_step - 1 done bytes and n_step rewards, its state row and the one obs row at the end of its window, and writes one
+// transition.
+__global__ void __launch_bounds__(kSW) replay_write_nstep_kernel(NstepArgs a)
+{
+#pragma clang fp contract(off)
+    const int64_t cap = a.ring.capacity, M = a.agents;
+    const float top = a.ring.priorities ? *a.top : 0.0f;
+    for (int64_t f = a.skip + (int64_t)blockIdx.x * kSW + threadIdx.x; f < a.n; f += (int64_t)gridDim.x * kSW) {
+        int64_t slot = a.start + (f - a.skip);
+        if (slot >= cap) slot -= cap;
+        const int64_t t = f / M, r = f - t * M, b = r / a.n_uav;
+        // the horizon: the smallest m >= 1 with m == n_step, t + m == steps or done[t + m - 1][b]
+        const int64_t left = a.steps - t;
+        const int lim = left < (int64_t)a.n_step ? (int)left : a.n_step;
+        int m = 1;
+        if (a.done) {
+            const uint8_t *dn = a.done + t * a.envs + b;               // dn[k * envs] = done[t + k][b]
+            while (m < lim && !dn[(int64_t)(m - 1) * a.envs]) ++m;
+        } else {
+            m = lim;
+        }
+        // the return, Horner from the far end, and the discount, m - 1 products
+        const float *rw = a.reward + f;                                // rw[k * M] = reward[t + k][b][i]
+        float R = rw[(int64_t)(m - 1) * M], d = a.g;
+        for (int k = m - 2; k >= 0; --k) {
+            R = rw[(int64_t)k * M] + a.g * R;
+            d = d * a.g;
+        }
+        const float *srow = a.obs_in + r * 12;
+        if (t > 0) {
+            const int64_t p = f - M;                                   // (t - 1, b, i)
+            srow = (a.done && a.done[(t - 1) * a.envs + b]) ? a.start_obs + p * 12 : a.obs + p * 12;
+        }
+        copy_row(a.ring.states + slot * 12, srow);
+        copy_row(a.ring.next_states + slot * 12, a.obs + (f + (int64_t)(m - 1) * M) * 12);
+        a.ring.actions[slot] = a.actions[f];
+        a.ring.rewards[slot] = R;
+        a.discounts[slot] = d;
+        if (a.ring.priorities) a.ring.priorities[slot] = top;
+    }
+}
+
 }  // namespace
+
+// the maximum of the ring's priorities as they stand (1.0 for an empty ring) into d.parts[kReplayMaxParts]
+static hipError_t launch_priority_top(const ReplayDevice &d, const ReplayRingView &ring, hipStream_t st)
+{
+    const int64_t cap = ring.capacity;
+    int64_t groups = (cap + (int64_t)kSW * 16 - 1) / ((int64_t)kSW * 16);
+    if (groups > kReplayMaxParts) groups = kReplayMaxParts;
+    hipLaunchKernelGGL(replay_max_kernel, dim3((unsigned)groups), dim3(kSW), 0, st, ring.priorities, cap, d.parts);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(replay_top_kernel, dim3(1), dim3(64), 0, st, d.parts, (int)groups, ring.count == 0 ? 1 : 0);
+    return hipGetLastError();
+}
 
 hipError_t launch_replay_sample(const ReplayDevice &d, const float *priorities, int64_t count, int64_t k, float alpha,
                                 double beta0, double beta1, int64_t anneal_calls, int64_t *indices, float *weights,
@@ -470,14 +545,7 @@ hipError_t launch_replay_add(const ReplayDevice &d, const ReplayRingView &ring, 
 {
     const int64_t cap = ring.capacity;
     hipError_t e;
-    if (ring.priorities) {
-        int64_t groups = (cap + (int64_t)kSW * 16 - 1) / ((int64_t)kSW * 16);
-        if (groups > kReplayMaxParts) groups = kReplayMaxParts;
-        hipLaunchKernelGGL(replay_max_kernel, dim3((unsigned)groups), dim3(kSW), 0, st, ring.priorities, cap, d.parts);
-        if ((e = hipGetLastError()) != hipSuccess) return e;
-        hipLaunchKernelGGL(replay_top_kernel, dim3(1), dim3(64), 0, st, d.parts, (int)groups, ring.count == 0 ? 1 : 0);
-        if ((e = hipGetLastError()) != hipSuccess) return e;
-    }
+    if (ring.priorities && (e = launch_priority_top(d, ring, st)) != hipSuccess) return e;
     AddArgs a;
     a.ring = ring; a.obs_in = obs_in; a.src_states = states; a.src_next = next_states; a.src_actions = actions;
     a.src_rewards = rewards; a.top = d.parts + kReplayMaxParts; a.n = n; a.agents = agents;
@@ -489,6 +557,27 @@ hipError_t launch_replay_add(const ReplayDevice &d, const ReplayRingView &ring, 
     if (blocks > 65536) blocks = 65536;
     if (done) hipLaunchKernelGGL(replay_write_kernel<true>, dim3((unsigned)blocks), dim3(kSW), 0, st, a);
     else hipLaunchKernelGGL(replay_write_kernel<false>, dim3((unsigned)blocks), dim3(kSW), 0, st, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_replay_add_nstep(const ReplayDevice &d, const ReplayRingView &ring, float *discounts, int64_t steps,
+                                   int64_t envs, int64_t n_uav, const float *obs_in, const float *obs,
+                                   const int32_t *actions, const float *reward, const uint8_t *done, const float *start_obs,
+                                   int n_step, float gamma, hipStream_t st)
+{
+    const int64_t cap = ring.capacity;
+    hipError_t e;
+    if (ring.priorities && (e = launch_priority_top(d, ring, st)) != hipSuccess) return e;
+    NstepArgs a;
+    a.ring = ring; a.discounts = discounts; a.obs_in = obs_in; a.obs = obs; a.reward = reward; a.actions = actions;
+    a.done = done; a.start_obs = start_obs; a.top = d.parts + kReplayMaxParts;
+    a.envs = envs; a.n_uav = n_uav; a.steps = steps; a.agents = envs * n_uav; a.n = steps * a.agents;
+    a.n_step = n_step; a.g = gamma;
+    a.skip = a.n > cap ? a.n - cap : 0;
+    a.start = (ring.pos + a.skip) % cap;
+    int64_t blocks = (a.n - a.skip + kSW - 1) / kSW;
+    if (blocks > 65536) blocks = 65536;
+    hipLaunchKernelGGL(replay_write_nstep_kernel, dim3((unsigned)blocks), dim3(kSW), 0, st, a);
     return hipGetLastError();
 }
 

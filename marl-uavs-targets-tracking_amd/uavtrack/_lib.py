@@ -110,6 +110,7 @@ PMI_BN_LAYERS = 4                                         # BatchNorm1d layers (
 LOSS_FORMS = ("reference", "per_sample")                  # enum uavtrack_actor_loss
 LEARNER_ROW_TAIL = 8                                      # words behind the P gradient sums of a gradient row
 LEARNER_MAX_ROWS = 64                                     # UAVTRACK_LEARNER_MAX_ROWS
+REPLAY_MAX_NSTEP = 64                                     # UAVTRACK_REPLAY_MAX_NSTEP
 LEARNER_TENSORS = 8                                       # parameter tensors: actor fc1.w fc1.b fc2.w fc2.b, critic likewise
 ACTOR_SAMPLE, ACTOR_ARGMAX = 0, 1   # enum in include/uavtrack.h
 PROF_CLASSES = ("rollout", "scorer", "mix", "ep_sums")   # UAVTRACK_PROF_* in include/uavtrack.h
@@ -174,6 +175,10 @@ SIGNATURES = {
     "uavtrack_learner_grad": (C.c_int, [C.c_void_p, C.c_int64] + [C.c_void_p] * 4 + [C.c_int64] + [C.c_void_p] * 4),
     "uavtrack_learner_grad_weighted": (C.c_int, [C.c_void_p, C.c_int64] + [C.c_void_p] * 4 + [C.c_int64]
                                        + [C.c_void_p] * 5),
+    "uavtrack_learner_update_discounted": (C.c_int, [C.c_void_p, C.c_int64] + [C.c_void_p] * 4 + [C.c_int64]
+                                           + [C.c_void_p] * 8),
+    "uavtrack_learner_grad_discounted": (C.c_int, [C.c_void_p, C.c_int64] + [C.c_void_p] * 4 + [C.c_int64]
+                                         + [C.c_void_p] * 6),
     "uavtrack_learner_apply": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
     "uavtrack_learner_write_priorities": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64] + [C.c_void_p] * 3),
     "uavtrack_learner_check": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64), C.c_void_p]),
@@ -202,6 +207,8 @@ SIGNATURES = {
     "uavtrack_replay_add_rollout": (C.c_int, [C.c_void_p, C.POINTER(ReplayRing), C.c_int64, C.c_int64] + [C.c_void_p] * 5),
     "uavtrack_replay_add_rollout_episodes": (C.c_int, [C.c_void_p, C.POINTER(ReplayRing), C.c_int64, C.c_int64, C.c_int64]
                                              + [C.c_void_p] * 7),
+    "uavtrack_replay_add_rollout_nstep": (C.c_int, [C.c_void_p, C.POINTER(ReplayRing), C.c_void_p, C.c_int64, C.c_int64,
+                                                    C.c_int64] + [C.c_void_p] * 6 + [C.c_int32, C.c_double, C.c_void_p]),
     "uavtrack_replay_sample": (C.c_int, [C.c_void_p, C.POINTER(ReplayRing), C.c_int64, C.c_double, C.c_double,
                                          C.c_void_p, C.c_void_p, C.c_void_p]),
     "uavtrack_replay_sample_annealed": (C.c_int, [C.c_void_p, C.POINTER(ReplayRing), C.c_int64, C.c_double, C.c_double,

@@ -33,6 +33,13 @@ term cannot share); clipping works with both forms and with apply, where the nor
 rows carry no settings: learners that share an update (ranks, shards) must be given equal ones
 (sharding.broadcast_learner copies them).  enable_diagnostics() installs two device buffers, the per-row entropies and
 the two gradient norms before clipping; reading them is a torch reduction of the caller's.
+
+Multi-step targets (update(discounts=...), and update_from / grad_from / update_from_many / the group path on an
+n-step ring, ring.with_nstep(n_step, gamma)): the target of row i is y_i = r_i + d_i V(s'_i) with d_i the row's slot in the ring's `discounts`
+store (gamma^m of its n-step window), gathered in the kernel beside the reward (uavtrack_learner_update_discounted /
+_grad_discounted).  Everything behind the target is unchanged.  Without discounts every call is bit for bit what it
+was, and a store of float32(gamma) gives the same bits; d_i = 0 means "do not bootstrap".  A discount that is NaN,
+negative or above 1 refuses the update on the device like a bad action.
 """
 from __future__ import annotations
 
@@ -214,12 +221,35 @@ class DeviceActorCritic(Handle):
                              f"order) on {self.device}")
         return weights
 
+    def _discounts_arg(self, discounts: Optional[torch.Tensor], capacity: int):
+        if discounts is None:
+            return None
+        if discounts.numel() != capacity or discounts.dtype != torch.float32 or not discounts.is_contiguous() \
+                or discounts.device != self.device:
+            raise ValueError(f"discounts must be a contiguous float32 tensor of {capacity} elements (one per slot of the "
+                             f"store) on {self.device}")
+        return discounts
+
+    def _discounts_of(self, buffer) -> Optional[torch.Tensor]:
+        """The buffer's per-slot discount store, or None; an n-step ring must have been folded with this learner's gamma."""
+        d = getattr(buffer, "discounts", None)
+        if d is not None and np.float32(buffer.gamma) != np.float32(self.gamma):
+            raise ValueError(f"the buffer's returns were folded with gamma = {buffer.gamma}, the learner bootstraps with "
+                             f"gamma = {self.gamma}: both must be the same float32")
+        return d
+
     def _run(self, n: int, store: Dict[str, torch.Tensor], capacity: int, idx: Optional[torch.Tensor],
-             priorities: Optional[torch.Tensor], weights: Optional[torch.Tensor] = None):
+             priorities: Optional[torch.Tensor], weights: Optional[torch.Tensor] = None,
+             discounts: Optional[torch.Tensor] = None):
         dev = self.device
         losses = torch.empty(2, device=dev)
         td = torch.empty(n, device=dev)
-        if weights is None:
+        if discounts is not None:
+            _lib.check(self._lib.uavtrack_learner_update_discounted(
+                self._h, n, *self._batch_args(store, capacity, idx), _ptr(self._weights_arg(weights, n)),
+                _ptr(self._discounts_arg(discounts, capacity)), _ptr(losses[0:1]), _ptr(losses[1:2]), _ptr(td),
+                _ptr(priorities), self._stream()), "uavtrack_learner_update_discounted")
+        elif weights is None:
             _lib.check(self._lib.uavtrack_learner_update(
                 self._h, n, *self._batch_args(store, capacity, idx), _ptr(losses[0:1]), _ptr(losses[1:2]), _ptr(td),
                 _ptr(priorities), self._stream()), "uavtrack_learner_update")
@@ -230,11 +260,14 @@ class DeviceActorCritic(Handle):
                 "uavtrack_learner_update_weighted")
         return losses[0], losses[1], td
 
-    def update(self, transition_dict: Dict[str, torch.Tensor], weights: Optional[torch.Tensor] = None):
+    def update(self, transition_dict: Dict[str, torch.Tensor], weights: Optional[torch.Tensor] = None,
+               discounts: Optional[torch.Tensor] = None):
         """ActorCritic.update (actor_critic.py:150-179) on a batch {states [n,12], actions [n], rewards [n],
         next_states [n,12]}: returns (actor_loss, critic_loss, td_delta) as device tensors, without synchronising.
         weights [n] (optional): importance weights w_i >= 0, one per row (the module docstring has the weighted losses);
-        None is the reference's unweighted update, and a vector of ones gives its bits."""
+        None is the reference's unweighted update, and a vector of ones gives its bits.
+        discounts [n] (optional): d_i in [0, 1] of row i, in batch order (row i is slot i here): the target becomes
+        r_i + d_i V(s'_i); None is gamma for every row, and a vector of float32(gamma) gives its bits."""
         dev = self.device
         s = torch.as_tensor(transition_dict["states"], device=dev, dtype=torch.float32).reshape(-1, _lib.OBS_DIM).contiguous()
         n = s.shape[0]
@@ -245,7 +278,9 @@ class DeviceActorCritic(Handle):
                                                 dtype=torch.float32).reshape(n, _lib.OBS_DIM).contiguous()}
         if weights is not None:
             weights = torch.as_tensor(weights, device=dev, dtype=torch.float32).reshape(-1).contiguous()
-        return self._run(n, store, n, None, None, weights)
+        if discounts is not None:
+            discounts = torch.as_tensor(discounts, device=dev, dtype=torch.float32).reshape(-1).contiguous()
+        return self._run(n, store, n, None, None, weights, discounts)
 
     def update_from(self, buffer, batch_size: int, beta: float = 0.4,
                     generator: Optional[torch.Generator] = None, group=None, importance: bool = False,
@@ -265,6 +300,9 @@ class DeviceActorCritic(Handle):
         buffer has no weights: importance changes nothing there.  A refused ring draw hands out NaN weights, which
         refuse this update on the device as well.
 
+        An n-step ring (ring.with_nstep(n_step, gamma)) brings its per-slot discounts: the target is then
+        r + discounts[slot] * V(s'), gathered in the same library call.  Its gamma must be this learner's (as float32).
+
         With a torch.distributed `group`, every rank of it takes ONE common update from all ranks' batches: the
         gradient row of this rank's batch (grad_from), an all-gather of the rows in rank order
         (sharding.gather_learner_rows), the apply of all of them, and the priority write into this rank's buffer.
@@ -277,7 +315,7 @@ class DeviceActorCritic(Handle):
         if k < 1:
             raise ValueError("update_from: the buffer is empty")
         idx, prio, w = self._draw_from(buffer, k, generator, importance, beta, beta_final, anneal_calls)
-        return self._run(k, buffer.store, buffer.capacity, idx, prio, w)
+        return self._run(k, buffer.store, buffer.capacity, idx, prio, w, self._discounts_of(buffer))
 
     # ---- the split update: gradient rows and an ordered apply
     def new_rows(self, count: int) -> torch.Tensor:
@@ -286,7 +324,7 @@ class DeviceActorCritic(Handle):
 
     def _grad(self, n: int, store: Dict[str, torch.Tensor], capacity: int, idx: Optional[torch.Tensor],
               row: Optional[torch.Tensor] = None, td: Optional[torch.Tensor] = None,
-              weights: Optional[torch.Tensor] = None):
+              weights: Optional[torch.Tensor] = None, discounts: Optional[torch.Tensor] = None):
         if row is None:
             row = torch.empty(self.row_floats, device=self.device)
         elif row.numel() != self.row_floats or row.dtype != torch.float32 or not row.is_contiguous() \
@@ -294,7 +332,12 @@ class DeviceActorCritic(Handle):
             raise ValueError(f"row must be a contiguous float32 tensor of {self.row_floats} words on {self.device}")
         if td is None:
             td = torch.empty(n, device=self.device)
-        if weights is None:
+        if discounts is not None:
+            _lib.check(self._lib.uavtrack_learner_grad_discounted(
+                self._h, n, *self._batch_args(store, capacity, idx), _ptr(self._weights_arg(weights, n)),
+                _ptr(self._discounts_arg(discounts, capacity)), _ptr(td), _ptr(row), self._stream()),
+                "uavtrack_learner_grad_discounted")
+        elif weights is None:
             _lib.check(self._lib.uavtrack_learner_grad(
                 self._h, n, *self._batch_args(store, capacity, idx), _ptr(td), _ptr(row), self._stream()),
                 "uavtrack_learner_grad")
@@ -317,7 +360,7 @@ class DeviceActorCritic(Handle):
         if k < 1:
             raise ValueError("grad_from: the buffer is empty")
         idx, _, w = self._draw_from(buffer, k, generator, importance, beta, beta_final, anneal_calls)
-        row, td = self._grad(k, buffer.store, buffer.capacity, idx, row, None, w)
+        row, td = self._grad(k, buffer.store, buffer.capacity, idx, row, None, w, self._discounts_of(buffer))
         return row, td, idx
 
     def apply(self, rows):

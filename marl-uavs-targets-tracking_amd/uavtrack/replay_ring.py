@@ -17,6 +17,12 @@ Against PrioritizedDeviceReplayBuffer (uavtrack/replay.py, which stays the plain
     in include/uavtrack.h;
   - beta can follow a linear schedule over that same call counter (draw(..., beta_final=, anneal_calls=):
     uavtrack_replay_sample_annealed), formed on the device, so a replayed graph anneals too.
+
+Multi-step targets.  Either ring turned into an n-step ring, ring.with_nstep(n_step, gamma), owns a fifth per-slot store, `discounts`: add_rollout
+then folds each transition's next n_step rewards into its reward, takes the next state from the end of that window and
+leaves gamma^m in the slot's discount (uavtrack_replay_add_rollout_nstep; the horizon m never crosses an episode end and
+is cut at the rollout's last step).  DeviceActorCritic.update_from and its relatives pick the store up, so the target of
+a row is r + discount * V(s').  Without with_nstep a ring is exactly what it was.
 """
 from __future__ import annotations
 
@@ -37,6 +43,11 @@ class ReplayRing(Handle):
     _prefix = "uavtrack_replay_"
     priorities: Optional[torch.Tensor] = None
 
+    discounts: Optional[torch.Tensor] = None
+
+    n_step: int = 1
+    gamma: Optional[float] = None
+
     def __init__(self, capacity: int, device, seed: int = 0, max_batch: int = 65536, obs_dim: int = _lib.OBS_DIM):
         if obs_dim != _lib.OBS_DIM:
             raise ValueError(f"obs_dim must be {_lib.OBS_DIM}, got {obs_dim}")
@@ -52,6 +63,25 @@ class ReplayRing(Handle):
         self._create(_lib.ReplayConfig(device_id=self.device.index, max_capacity=self.capacity, max_batch=self.max_batch,
                                        seed=self.seed & (2**64 - 1)))
         self._idx = torch.empty(self.max_batch, dtype=torch.int64, device=self.device)   # update_from's draws
+
+    def with_nstep(self, n_step: int = 1, gamma: Optional[float] = None) -> "ReplayRing":
+        """Makes this ring an n-step ring and returns it: ReplayRing(capacity, device).with_nstep(3, gamma=0.95).  The ring
+        then owns `discounts` [capacity] (every slot float32(gamma) to begin with, which is what the one-step transitions
+        it may already hold bootstrap with), add_rollout stores n_step-step returns and add fills the discounts.  gamma
+        None (then n_step must be 1) leaves the ring exactly what it was: discounts is None."""
+        n_step = int(n_step)
+        if not 1 <= n_step <= _lib.REPLAY_MAX_NSTEP:
+            raise ValueError(f"n_step must be in [1, {_lib.REPLAY_MAX_NSTEP}], got {n_step}")
+        if gamma is None:
+            if n_step != 1:
+                raise ValueError(f"n_step = {n_step} needs gamma (the discount the n-step return is folded with)")
+            return self
+        gamma = float(gamma)
+        if not 0.0 <= gamma <= 1.0:
+            raise ValueError(f"gamma must be in [0, 1], got {gamma}")
+        self.n_step, self.gamma = n_step, gamma
+        self.discounts = torch.full((self.capacity,), gamma, dtype=torch.float32, device=self.device)
+        return self
 
     def _ring(self) -> _lib.ReplayRing:
         s = self.store
@@ -77,7 +107,8 @@ class ReplayRing(Handle):
     def add(self, transition_dict: Dict[str, torch.Tensor]) -> None:
         """transition_dict: states [n,12], actions [n], rewards [n], next_states [n,12] (any leading shape is
         flattened).  One library call writes the last min(n, capacity) of them (a prioritised ring: at the current
-        maximum priority)."""
+        maximum priority).  A ring with discounts then fills the same slots' discounts from an optional "discounts"
+        entry [n], or with float32(gamma) where it is absent (a torch slice copy: the flat add is not the hot path)."""
         n = transition_dict["actions"].numel()
         if n < 1:
             return
@@ -89,13 +120,24 @@ class ReplayRing(Handle):
         ring = self._ring()
         _lib.check(self._lib.uavtrack_replay_add(self._h, C.byref(ring), n, _ptr(s), _ptr(a), _ptr(r), _ptr(s2),
                                                  self._stream()), "uavtrack_replay_add")
+        if self.discounts is not None:
+            d = transition_dict.get("discounts")
+            d = torch.full((n,), self.gamma, dtype=torch.float32, device=dev) if d is None \
+                else d.to(dev, torch.float32).reshape(n)
+            k = min(n, self.capacity)
+            start = (self.pos + n - k) % self.capacity
+            head = min(k, self.capacity - start)
+            self.discounts[start:start + head] = d[n - k:n - k + head]
+            self.discounts[:k - head] = d[n - k + head:]
         self._advance(n)
 
     def add_rollout(self, obs_in: torch.Tensor, out: Dict[str, torch.Tensor]) -> None:
         """add(transitions_from_rollout(obs_in, out)) in one library call: obs_in [B,N,12] is what the policy saw
         first, out = {obs [T,B,N,12], actions [T,B,N] int32, reward [T,B,N]} (BatchedRollout.run_fused's outputs).  When
         `out` carries start_obs (a rollout across episode ends, with its done [T,B] uint8), the state behind a fired done
-        is the fresh state's observation (uavtrack_replay_add_rollout_episodes)."""
+        is the fresh state's observation (uavtrack_replay_add_rollout_episodes).  A ring with discounts (with_nstep)
+        stores n_step-step returns and their discounts instead (uavtrack_replay_add_rollout_nstep), with or without
+        done / start_obs as above; obs must then be [T,B,N,12]."""
         obs, act, rew = out["obs"], out["actions"], out["reward"]
         so = out.get("start_obs")
         T = obs.shape[0]
@@ -119,6 +161,18 @@ class ReplayRing(Handle):
             for t in (done, so):
                 if t.device != self.device or not t.is_contiguous():
                     raise ValueError("add_rollout: every input must be contiguous on the ring's device")
+        else:
+            done = None
+        if self.discounts is not None:
+            if obs.dim() != 4:
+                raise ValueError("add_rollout: an n-step ring needs obs as [T,B,N,12]")
+            _lib.check(self._lib.uavtrack_replay_add_rollout_nstep(
+                self._h, C.byref(ring), _ptr(self.discounts), T, int(obs.shape[1]), int(obs.shape[2]), _ptr(obs_in),
+                _ptr(obs), _ptr(act), _ptr(rew), _ptr(done), _ptr(so), self.n_step, self.gamma, self._stream()),
+                "uavtrack_replay_add_rollout_nstep")
+            self._advance(T * M)
+            return
+        if so is not None:
             _lib.check(self._lib.uavtrack_replay_add_rollout_episodes(
                 self._h, C.byref(ring), T, int(obs.shape[1]), int(obs.shape[2]), _ptr(obs_in), _ptr(obs), _ptr(act), _ptr(rew),
                 _ptr(done), _ptr(so), self._stream()), "uavtrack_replay_add_rollout_episodes")
@@ -154,9 +208,15 @@ class ReplayRing(Handle):
         """ReplayBuffer.sample (as DeviceReplayBuffer.sample returns it): the transitions dict of min(batch_size, count)
         distinct transitions."""
         if self.count == 0:
-            return {k: self.store[k][:0] for k in KEYS}
-        idx = self.draw(batch_size)
-        return {key: self.store[key][idx] for key in KEYS}
+            return self._gather(slice(0, 0))
+        return self._gather(self.draw(batch_size))
+
+    def _gather(self, idx) -> Dict[str, torch.Tensor]:
+        """The transitions dict at idx: KEYS, and "discounts" on a ring that has them."""
+        out = {key: self.store[key][idx] for key in KEYS}
+        if self.discounts is not None:
+            out["discounts"] = self.discounts[idx]
+        return out
 
 
 class PrioritizedReplayRing(ReplayRing):
@@ -215,9 +275,9 @@ class PrioritizedReplayRing(ReplayRing):
         """PrioritizedReplayBuffer.sample: (transitions dict, indices int64, weights), or (empty dict, None, None)
         for an empty ring.  beta_final, anneal_calls: as draw."""
         if self.count == 0:
-            return {k: self.store[k][:0] for k in KEYS}, None, None
+            return self._gather(slice(0, 0)), None, None
         idx, w = self.draw(batch_size, beta, beta_final, anneal_calls)
-        return {key: self.store[key][idx] for key in KEYS}, idx, w
+        return self._gather(idx), idx, w
 
     def update_priorities(self, batch_indices: torch.Tensor, batch_priorities: torch.Tensor) -> None:
         """PrioritizedReplayBuffer.update_priorities (train.py:136-138): a repeated index keeps its last value, as the

@@ -1,0 +1,806 @@
+"""Multi-step targets on the MI355X: the n-step ring add (uavtrack_replay_add_rollout_nstep) against the numpy mirror
+(tests/nstep_mirror.py), bitwise over all five stores and the priorities; n = 1 as today's adds; the learner's per-row
+discounts (uavtrack_learner_update_discounted / _grad_discounted) with a store of float32(gamma) and with NULL as the
+plain update to the bit, with random discounts against the float64 mirror at test_sweep_against_fp64_mirror's bounds;
+the split form; refused discounts and host-side errors; the Python surface; graph capture; a real rollout end to end."""
+import ctypes as C
+import types
+
+import numpy as np
+import pytest
+import torch
+
+import learner_dp_mirror as dp
+import learner_mirror as mirror
+import learner_weighted_mirror as wm
+import nstep_mirror as nm
+
+pytestmark = pytest.mark.gpu
+
+DEV = "cuda:0"
+LR = (1e-3, 5e-3)
+GAMMA = 0.95
+G32 = np.float32(GAMMA)
+INF = float("inf")
+STORES = ("states", "actions", "rewards", "next_states")
+
+
+def _uav():
+    import uavtrack
+    return uavtrack
+
+
+def _dev(x):
+    return torch.from_numpy(np.ascontiguousarray(x)).to(DEV)
+
+
+# ---- 1. the add against the mirror ---------------------------------------------------------------------------------------
+
+T, B, N = 7, 3, 2
+AG = B * N
+NTR = T * AG                                                           # 42 transitions
+
+
+def _done(kind):
+    d = np.zeros((T, B), np.uint8)
+    if kind == "mid":
+        d[3, 1] = 1
+    elif kind == "consecutive":
+        d[2, 0] = d[3, 0] = 1
+    elif kind == "first":
+        d[0, 2] = 1
+    elif kind == "last":
+        d[T - 1, 1] = 1
+    elif kind == "every":
+        d[:, 1] = 1
+    return None if kind == "null" else d
+
+
+DONES = ("zeros", "null", "mid", "consecutive", "first", "last", "every")
+# (capacity, pos, count): roomy; pos three slots before the end; a ring smaller than the rollout
+RINGS = {"roomy": (100, 10, 10), "wrap": (100, 97, 100), "small": (17, 5, 17)}
+_roll = {}
+
+
+def _rollout():
+    if not _roll:
+        rng = np.random.default_rng(5)
+        _roll.update(obs_in=rng.standard_normal((B, N, 12)).astype(np.float32),
+                     obs=rng.standard_normal((T, B, N, 12)).astype(np.float32),
+                     actions=rng.integers(0, 12, (T, B, N)).astype(np.int32),
+                     reward=(rng.standard_normal((T, B, N)) * 3).astype(np.float32),
+                     start_obs=rng.standard_normal((T, B, N, 12)).astype(np.float32))
+        _roll["dev"] = {k: _dev(v) for k, v in _roll.items()}
+    return _roll
+
+
+def _out(done):
+    """The result dict add_rollout takes; done None: no done / start_obs at all."""
+    d = _rollout()["dev"]
+    out = {k: d[k] for k in ("obs", "actions", "reward")}
+    if done is not None:
+        out.update(done=_dev(done), start_obs=d["start_obs"])
+    return out
+
+
+def _new_ring(kind, cap, **kw):
+    u = _uav()
+    ring = (u.PrioritizedReplayRing if kind == "prioritised" else u.ReplayRing)(cap, DEV, seed=1, max_batch=64)
+    return ring.with_nstep(**kw)
+
+
+def _prefill(ring, pos, count, seed=9):
+    """Sentinel stores, the ring's host state, and (prioritised) priorities whose maximum over the whole array is 2.5."""
+    rng = np.random.default_rng(seed)
+    cap = ring.capacity
+    ring.store["states"].copy_(_dev(rng.standard_normal((cap, 12)).astype(np.float32)))
+    ring.store["next_states"].copy_(_dev(rng.standard_normal((cap, 12)).astype(np.float32)))
+    ring.store["actions"].fill_(-3)
+    ring.store["rewards"].fill_(-777.25)
+    if ring.discounts is not None:
+        ring.discounts.fill_(7.0)
+    if ring.priorities is not None:
+        p = rng.uniform(0.1, 2.0, cap).astype(np.float32)
+        p[count:] = 0.0
+        p[count // 2] = 2.5
+        ring.priorities.copy_(_dev(p))
+    ring.pos, ring.count = pos, count
+
+
+def _image(ring):
+    img = {k: ring.store[k].cpu().numpy().copy() for k in STORES}
+    img["discounts"] = None if ring.discounts is None else ring.discounts.cpu().numpy().copy()
+    img["priorities"] = None if ring.priorities is None else ring.priorities.cpu().numpy().copy()
+    return img
+
+
+def _same_image(a, b, keys=STORES + ("discounts", "priorities")):
+    for k in keys:
+        if a[k] is None or b[k] is None:
+            assert a[k] is None and b[k] is None, k
+        else:
+            assert a[k].tobytes() == b[k].tobytes(), k
+
+
+@pytest.mark.parametrize("ringcase", sorted(RINGS))
+@pytest.mark.parametrize("done_kind", DONES)
+@pytest.mark.parametrize("kind", ["uniform", "prioritised"])
+def test_add_against_the_mirror_bitwise(kind, done_kind, ringcase):
+    r = _rollout()
+    done = _done(done_kind)
+    cap, pos, count = RINGS[ringcase]
+    longest = 0
+    for gamma in (0.95, 1.0, 0.0):
+        for n_step in (1, 2, 3, 5, 7, 9):
+            ring = _new_ring(kind, cap, n_step=n_step, gamma=gamma)
+            _prefill(ring, pos, count)
+            img = _image(ring)
+            ring.add_rollout(r["dev"]["obs_in"], _out(done))
+            tr, m = nm.transitions(r["obs_in"], r["obs"], r["actions"], r["reward"], n_step, gamma, done,
+                                   None if done is None else r["start_obs"])
+            longest = max(longest, int(m.max()))
+            p2, c2 = nm.ring_add(img, pos, count, tr)
+            assert (ring.pos, ring.count) == (p2, c2)
+            _same_image(_image(ring), img)
+            if kind == "prioritised":
+                assert (img["priorities"] == np.float32(2.5)).sum() >= min(NTR, cap)
+    assert longest == T                                                # the longest window ran the whole rollout
+
+
+# ---- 2. n = 1 is today's add ---------------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("ringcase", sorted(RINGS))
+@pytest.mark.parametrize("done_kind", ["null", "zeros", "mid", "every"])
+@pytest.mark.parametrize("kind", ["uniform", "prioritised"])
+def test_n1_is_todays_add(kind, done_kind, ringcase):
+    r = _rollout()
+    done = _done(done_kind)
+    cap, pos, count = RINGS[ringcase]
+    new, old = _new_ring(kind, cap, n_step=1, gamma=GAMMA), _new_ring(kind, cap)
+    assert old.discounts is None and new.discounts is not None
+    _prefill(new, pos, count); _prefill(old, pos, count)
+    new.add_rollout(r["dev"]["obs_in"], _out(done))
+    old.add_rollout(r["dev"]["obs_in"], _out(done))      # uavtrack_replay_add_rollout_episodes, or _add_rollout without done
+    a, b = _image(new), _image(old)
+    _same_image(a, b, STORES + ("priorities",))
+    assert (new.pos, new.count) == (old.pos, old.count)
+    k = min(NTR, cap)
+    written = np.zeros(cap, bool)
+    written[(new.pos - k + np.arange(k)) % cap] = True
+    d = a["discounts"].view(np.int32)
+    assert (d[written] == G32.view(np.int32)).all() and (d[~written] == np.float32(7.0).view(np.int32)).all()
+
+
+# ---- the learner ---------------------------------------------------------------------------------------------------------
+
+SHAPES = [(1, 9, 1), (33, 12, 2), (64, 48, 63), (128, 12, 65), (128, 12, 4096)]
+CASES = [(H, A, n, loss, gather) for H, A, n in SHAPES for loss in ("reference", "per_sample") for gather in (True, False)]
+
+
+def _learner(H, A, loss="reference", blob=None, max_batch=0, c=0.0, mgn=None, diag=False, gamma=GAMMA):
+    L = _uav().DeviceActorCritic(12, H, A, LR[0], LR[1], gamma, DEV, loss=loss, max_batch=max_batch, entropy_coef=c,
+                                 max_grad_norm=mgn)
+    if blob is not None:
+        L._set_params(np.ascontiguousarray(blob, np.float32))
+    if diag:
+        L.enable_diagnostics()
+    return L
+
+
+def _state(L):
+    m, v, st = L._optim_state()
+    return {"params": L._get_params(), "exp_avg": m, "exp_avg_sq": v, "step": st}
+
+
+def _same(a, b):
+    assert a.keys() == b.keys()
+    for k in a:
+        if a[k] is None or b[k] is None:
+            assert a[k] is None and b[k] is None, k
+        else:
+            assert np.array_equal(np.asarray(a[k]), np.asarray(b[k]), equal_nan=True), k
+
+
+_cache = {}
+
+
+def _case(H, A, n, gather):
+    """(blob, host batch over the store, device store, capacity, host indices, device indices or None), built once."""
+    key = (H, A, n, gather)
+    if key not in _cache:
+        rng = np.random.RandomState(H * 1000 + n + (7 if gather else 0))
+        cap = n + 7 if gather else n
+        b = dp.batch(rng, cap, A)
+        idx = rng.randint(0, cap, size=n).astype(np.int64) if gather else np.arange(n)
+        store = {k: _dev(x) for k, x in zip(STORES, b)}
+        _cache[key] = (dp.init_blob(H, A, H + n), b, store, cap, idx, _dev(idx) if gather else None)
+    return _cache[key]
+
+
+def _gathered(b, idx):
+    return tuple(x[idx] for x in b)
+
+
+def _discount_store(cap, seed):
+    """A per-slot store in [0, 1] with exact zeros and an exact one (cap 1: a single zero)."""
+    return wm.make_weights(np.random.RandomState(seed + 101), cap) if cap > 1 else np.zeros(1, np.float32)
+
+
+def _update(L, n, store, cap, it, prio, w=None, d=None, direct=False):
+    """One closed update.  direct: uavtrack_learner_update_discounted itself, whatever is NULL."""
+    from uavtrack import _lib
+    if direct:
+        losses, td = torch.empty(2, device=DEV), torch.empty(n, device=DEV)
+        _lib.check(L._lib.uavtrack_learner_update_discounted(
+            L._h, n, *L._batch_args(store, cap, it), _lib.ptr(w), _lib.ptr(d), _lib.ptr(losses[0:1]),
+            _lib.ptr(losses[1:2]), _lib.ptr(td), _lib.ptr(prio), L._stream()), "uavtrack_learner_update_discounted")
+        al, cl = losses[0], losses[1]
+    else:
+        al, cl, td = L._run(n, store, cap, it, prio, w, d)
+    out = dict(_state(L), actor_loss=al.cpu().numpy(), critic_loss=cl.cpu().numpy(), td=td.cpu().numpy(),
+               prio=None if prio is None else prio.cpu().numpy())
+    if L._entropy is not None:
+        out["entropy"] = L.entropy(n).cpu().numpy()
+        out["grad_norm"] = L.grad_norm.cpu().numpy()
+    return out
+
+
+def _row(L, n, store, cap, it, w=None, d=None, direct=False):
+    from uavtrack import _lib
+    if direct:
+        row, td = torch.empty(L.row_floats, device=DEV), torch.empty(n, device=DEV)
+        _lib.check(L._lib.uavtrack_learner_grad_discounted(
+            L._h, n, *L._batch_args(store, cap, it), _lib.ptr(w), _lib.ptr(d), _lib.ptr(td), _lib.ptr(row), L._stream()),
+            "uavtrack_learner_grad_discounted")
+    else:
+        row, td = L._grad(n, store, cap, it, None, None, w, d)
+    return row.cpu().numpy(), td.cpu().numpy()
+
+
+# ---- 3. gamma everywhere is nothing --------------------------------------------------------------------------------------
+
+VARIANTS = ("plain", "weighted", "regularised", "diagnostics")
+
+
+@pytest.mark.parametrize("variant", VARIANTS)
+@pytest.mark.parametrize("H,A,n,loss,gather", CASES)
+def test_a_store_of_gamma_and_null_are_the_plain_update_bitwise(H, A, n, loss, gather, variant):
+    blob, b, store, cap, idx, it = _case(H, A, n, gather)
+    prio0 = torch.rand(cap, device=DEV) + 0.1
+    w = _dev(wm.make_weights(np.random.RandomState(n + H), n)) if variant == "weighted" else None
+    kw = {}
+    if variant == "regularised":                                       # (the entropy bonus exists for per_sample only)
+        kw = dict(c=0.01 if loss == "per_sample" else 0.0, mgn=(0.05, 0.5))
+    if variant == "diagnostics":
+        kw = dict(diag=True, mgn=(1e30, 1e30))
+    full = torch.full((cap,), GAMMA, device=DEV)
+    assert full.cpu().numpy().view(np.int32)[0] == G32.view(np.int32)
+    modes = (dict(), dict(direct=True), dict(d=full), dict(d=full, direct=True))
+    outs = []
+    for mode in modes:
+        L = _learner(H, A, loss, blob, max_batch=n, **kw)
+        outs.append(_update(L, n, store, cap, it, prio0.clone(), w, **mode))
+        L.check()
+    assert np.isfinite(outs[0]["actor_loss"]) and np.array_equal(outs[0]["step"], np.ones(8))
+    assert not np.array_equal(outs[0]["prio"], prio0.cpu().numpy())
+    for other in outs[1:]:
+        _same(outs[0], other)
+    L = _learner(H, A, loss, blob, max_batch=n, **kw)
+    rows = [_row(L, n, store, cap, it, w, **mode) for mode in modes]
+    L.check()
+    for row, td in rows[1:]:
+        assert np.array_equal(row.view(np.int32), rows[0][0].view(np.int32)) and np.array_equal(td, rows[0][1])
+    assert np.array_equal(rows[0][1], outs[0]["td"])
+
+
+# ---- 4. random discounts against the fp64 mirror ---------------------------------------------------------------------------
+
+def _assert_losses_and_td(al, cl, td, ral, rcl, rtd):
+    """test_sweep_against_fp64_mirror's bounds as tests/test_hip_learner_weighted.py states them: td_delta and the losses
+    at 2e-5 of their scale."""
+    tds = np.abs(rtd).max() + 1e-6
+    print(f"td error {np.abs(td - rtd).max():.3e} of bound {2e-5 * tds:.3e}")
+    np.testing.assert_allclose(td, rtd, rtol=0, atol=2e-5 * tds)
+    assert abs(float(cl) - rcl) <= 2e-5 * (np.mean(rtd ** 2) + 1e-12) + 1e-12, (float(cl), rcl)
+    nlp_scale = abs(ral) + np.mean(np.abs(rtd)) * 30
+    assert abs(float(al) - ral) <= 2e-5 * nlp_scale, (float(al), ral)
+
+
+def _assert_step_from_zero(st, blob, g, n, H, A):
+    """The same test's bounds on the first Adam step: the gradient (exp_avg / 0.1) within 2e-6 (1 + log2 n) of its
+    largest element, the parameters within 1e-3 lr except where the fp64 gradient is within the gradient's rounding of 0
+    (Adam's first step may then take either sign: within 2 lr)."""
+    gd = st["exp_avg"] / 0.1
+    gmax = np.abs(g).max()
+    tol_g = 2e-6 * (1 + np.log2(n)) * gmax
+    print(f"gradient error {np.abs(gd - g).max():.3e} of bound {tol_g:.3e}")
+    assert np.abs(gd - g).max() <= tol_g + 1e-30, (np.abs(gd - g).max(), tol_g)
+    p64 = mirror.adam(blob.astype(np.float64), np.zeros(g.size), np.zeros(g.size), np.ones(8, np.int64), g, LR, H, A)[0]
+    lr_of = np.concatenate([np.full(k, LR[0] if t < 4 else LR[1]) for t, k in enumerate(mirror.layout(H, A)[0])])
+    near0 = np.abs(g) <= 4 * tol_g + 1e-8
+    err = np.abs(st["params"] - p64)
+    assert (err[~near0] <= 1e-3 * lr_of[~near0] + 1e-6 * np.abs(p64[~near0])).all(), err[~near0].max()
+    assert (err[near0] <= 2 * lr_of[near0] + 1e-6).all()
+
+
+PATHS = [(loss, path) for loss in ("reference", "per_sample") for path in ("plain", "weighted", "regularised")
+         if not (path == "regularised" and loss == "reference")]
+
+
+@pytest.mark.parametrize("loss,path", PATHS)
+@pytest.mark.parametrize("gather", [True, False])
+@pytest.mark.parametrize("H,A,n", SHAPES)
+def test_random_discounts_against_fp64_mirror(H, A, n, gather, loss, path):
+    blob, b, store, cap, idx, it = _case(H, A, n, gather)
+    ds = _discount_store(cap, n + H)
+    d = ds[idx]                                                         # the per-row discounts, through the index vector
+    w = wm.make_weights(np.random.RandomState(n + H + 5), n) if path != "plain" else None
+    c = 0.01 if path == "regularised" else None
+    L = _learner(H, A, loss, blob, max_batch=n, c=c or 0.0)
+    out = _update(L, n, store, cap, it, None, None if w is None else _dev(w), _dev(ds))
+    L.check()
+    ref = nm.learner(blob, H, A, *_gathered(b, idx), d, loss, w, None if c is None else np.float32(c))
+    ral, rcl, rtd, g = ref[:4]
+    _assert_losses_and_td(out["actor_loss"], out["critic_loss"], out["td"], ral, rcl, rtd)
+    _assert_step_from_zero(out, blob, g, n, H, A)
+    # rows with d = 0 do not bootstrap: td_delta = r - V(s), within the same bound
+    zero = d == 0
+    assert zero.any() or n < 63
+    if zero.any():
+        r0 = nm.learner(blob, H, A, *_gathered(b, idx), np.zeros(n), loss, w, None if c is None else np.float32(c))[2]
+        assert np.array_equal(r0[zero], rtd[zero])
+        np.testing.assert_allclose(out["td"][zero], r0[zero], rtol=0, atol=2e-5 * (np.abs(rtd).max() + 1e-6))
+    if n >= 63:       # the discounts are in the result: gamma for every row is far outside the bound
+        gu = nm.learner(blob, H, A, *_gathered(b, idx), np.full(n, GAMMA), loss, w, None if c is None else np.float32(c))[3]
+        assert np.abs(out["exp_avg"] / 0.1 - gu).max() > 100 * 2e-6 * (1 + np.log2(n)) * np.abs(g).max()
+
+
+def test_the_discount_is_per_slot_and_the_weight_per_batch_row():
+    """A gathered batch whose index vector is a reversal: the discounts follow the slots, the weights the batch rows."""
+    H, A, n = 64, 12, 63
+    blob, b, store, cap, _, _ = _case(H, A, n, False)
+    idx = np.arange(n)[::-1].copy()
+    ds, w = _discount_store(cap, 3), wm.make_weights(np.random.RandomState(4), n)
+    L = _learner(H, A, "per_sample", blob, max_batch=n)
+    out = _update(L, n, store, cap, _dev(idx), None, _dev(w), _dev(ds))
+    L.check()
+    ral, rcl, rtd, g = nm.learner(blob, H, A, *_gathered(b, idx), ds[idx], "per_sample", w)
+    _assert_losses_and_td(out["actor_loss"], out["critic_loss"], out["td"], ral, rcl, rtd)
+    _assert_step_from_zero(out, blob, g, n, H, A)
+
+
+# ---- 5. the split form ---------------------------------------------------------------------------------------------------
+
+SPLIT = [(64, 48, 63), (128, 12, 65), (128, 12, 4096)]
+
+
+@pytest.mark.parametrize("weighted", [False, True])
+@pytest.mark.parametrize("loss", ["reference", "per_sample"])
+@pytest.mark.parametrize("H,A,n", SPLIT)
+def test_grad_apply_write_is_the_discounted_update_bitwise(H, A, n, loss, weighted):
+    blob, b, store, cap, idx, it = _case(H, A, n, True)
+    ds = _dev(_discount_store(cap, n))
+    w = _dev(wm.make_weights(np.random.RandomState(n), n)) if weighted else None
+    prio0 = torch.rand(cap, device=DEV) + 0.1
+    closed = _learner(H, A, loss, blob, max_batch=n)
+    want = _update(closed, n, store, cap, it, prio0.clone(), w, ds)
+    split = _learner(H, A, loss, blob, max_batch=n)
+    prio = prio0.clone()
+    row, td = split._grad(n, store, cap, it, None, None, w, ds)
+    al, cl = split.apply(row)
+    split.write_priorities(types.SimpleNamespace(priorities=prio, capacity=cap), it, td)
+    split.check(); closed.check()
+    assert not np.array_equal(want["prio"], prio0.cpu().numpy())
+    _same(dict(_state(split), actor_loss=al.cpu().numpy(), critic_loss=cl.cpu().numpy(), td=td.cpu().numpy(),
+               prio=prio.cpu().numpy()), want)
+
+
+@pytest.mark.parametrize("loss", ["reference", "per_sample"])
+@pytest.mark.parametrize("H,A,n", SPLIT)
+def test_a_row_with_discounts_and_a_row_without_apply_together(H, A, n, loss):
+    """Two gradient rows over the two halves of a batch, the first with a discount store and the second through the
+    plain uavtrack_learner_grad (gamma in the mirror), against the mirror on the whole batch."""
+    blob, b, store, cap, idx, it = _case(H, A, n, True)
+    ds = _discount_store(cap, n + 1)
+    h = n // 2
+    L = _learner(H, A, loss, blob, max_batch=n)
+    rows = L.new_rows(2)
+    _, td0 = L._grad(h, store, cap, it[:h], rows[0], None, None, _dev(ds))
+    _, td1 = L._grad(n - h, store, cap, it[h:].contiguous(), rows[1])
+    al, cl = L.apply(rows)
+    L.check()
+    d = np.concatenate([ds[idx[:h]].astype(np.float64), np.full(n - h, float(G32))])
+    ral, rcl, rtd, g = nm.learner(blob, H, A, *_gathered(b, idx), d, loss)
+    _assert_losses_and_td(al.cpu().numpy(), cl.cpu().numpy(), torch.cat([td0, td1]).cpu().numpy(), ral, rcl, rtd)
+    _assert_step_from_zero(_state(L), blob, g, n, H, A)
+
+
+# ---- 6. refusals -----------------------------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("bad", [float("nan"), -0.1, 1.5], ids=["nan", "negative", "above-one"])
+def test_a_bad_discount_refuses_the_update(bad):
+    H, A, n = 128, 12, 65
+    blob, b, store, cap, idx, it = _case(H, A, n, True)
+    L = _learner(H, A, "reference", blob, max_batch=n)
+    good = _dev(_discount_store(cap, 3))
+    good[int(idx[0])], good[int(idx[1])] = 1.0, 0.0                     # both ends of the range are accepted
+    L._run(n, store, cap, it, None, None, good)
+    L.check()
+    before = _state(L)
+    prio = torch.rand(cap, device=DEV) + 0.1
+    prio0 = prio.clone()
+    d = good.clone()
+    d[int(idx[40])] = bad                                               # a slot the second tile of the batch gathers
+    al, cl, _ = L._run(n, store, cap, it, prio, None, d)
+    assert torch.isnan(al) and torch.isnan(cl)
+    _same(_state(L), before)
+    assert torch.equal(prio, prio0)
+    with pytest.raises(RuntimeError, match="1 update"):
+        L.check()
+    L.check()                                                          # the count restarts
+    # the split form: the row carries status 8, the apply of it changes nothing, the priority write is held back
+    row, td = L._grad(n, store, cap, it, None, None, None, d)
+    assert int(row.cpu().numpy().view(np.int32)[L.num_params + 6]) == 8
+    ok_row, _ = L._grad(n, store, cap, it)
+    al, cl = L.apply(torch.stack([ok_row, row]))
+    L.write_priorities(types.SimpleNamespace(priorities=prio, capacity=cap), it, td)
+    assert torch.isnan(al) and torch.isnan(cl)
+    _same(_state(L), before)
+    assert torch.equal(prio, prio0)
+    with pytest.raises(RuntimeError, match="1 update"):
+        L.check()
+    # a bad discount in a slot the batch does not gather is not read
+    unused = np.setdiff1d(np.arange(cap), idx)
+    d = good.clone()
+    d[int(unused[0])] = bad
+    al, cl, _ = L._run(n, store, cap, it, prio, None, d)
+    L.check()
+    assert torch.isfinite(al) and torch.isfinite(cl) and not torch.equal(prio, prio0)
+    assert np.array_equal(_state(L)["step"], before["step"] + 1)
+
+
+def test_a_row_with_the_wrong_tag_is_still_refused():
+    """The finalize kernel's "another layout" flag moved from 8 to 16: a row whose tag is not P refuses the apply, alone
+    and beside a good row, and so does a row whose n is 0."""
+    H, A, n = 64, 12, 63
+    blob, b, store, cap, idx, it = _case(H, A, n, True)
+    L = _learner(H, A, "reference", blob, max_batch=n)
+    before = _state(L)
+    good, _ = L._grad(n, store, cap, it, None, None, None, _dev(_discount_store(cap, 1)))
+    P = L.num_params
+    for word, value in ((P + 7, P + 1), (P + 4, 0)):
+        bad = good.clone()
+        bad.view(torch.int32)[word] = value
+        for rows in (bad, torch.stack([good, bad])):
+            al, cl = L.apply(rows)
+            assert torch.isnan(al) and torch.isnan(cl)
+            _same(_state(L), before)
+            with pytest.raises(RuntimeError, match="1 update"):
+                L.check()
+    al, cl = L.apply(good)
+    L.check()
+    assert torch.isfinite(al) and np.array_equal(_state(L)["step"], np.ones(8))
+
+
+def test_host_side_errors_of_the_add_enqueue_nothing():
+    from uavtrack import _lib
+    lib = _lib.load()
+    r = _rollout()["dev"]
+    done = _dev(_done("mid"))
+    ring = _new_ring("prioritised", 100, n_step=3, gamma=GAMMA)
+    _prefill(ring, 10, 10)
+    torch.cuda.synchronize()
+    img = _image(ring)
+    p = _lib.ptr
+    off = lambda t: C.c_void_p(t.data_ptr() + 4)                       # not 16-byte aligned
+
+    def call(ring_struct=None, discounts=p(ring.discounts), obs_in=p(r["obs_in"]), obs=p(r["obs"]), act=p(r["actions"]),
+             rew=p(r["reward"]), dn=p(done), so=p(r["start_obs"]), n_step=3, gamma=GAMMA, steps=T, envs=B, n_uav=N):
+        rs = ring._ring() if ring_struct is None else ring_struct
+        return lib.uavtrack_replay_add_rollout_nstep(ring._h, C.byref(rs), discounts, steps, envs, n_uav, obs_in, obs, act,
+                                                     rew, dn, so, n_step, gamma, ring._stream())
+
+    def ring_with(**kw):
+        rs = ring._ring()
+        for k, v in kw.items():
+            setattr(rs, k, v)
+        return rs
+
+    bad_calls = {
+        "discounts": dict(discounts=None), "obs_in, obs": dict(obs=None), "obs_in": dict(obs_in=None),
+        "actions": dict(act=None), "reward": dict(rew=None),
+        "n_step = 0": dict(n_step=0), "n_step = 65": dict(n_step=65),
+        "gamma": dict(gamma=float("nan")), "gamma = -0.1": dict(gamma=-0.1), "gamma = 1.5": dict(gamma=1.5),
+        "gamma = inf": dict(gamma=INF),
+        "both": dict(dn=None), "both be": dict(so=None),
+        "pos": dict(ring_struct=ring_with(pos=100)), "capacity": dict(ring_struct=ring_with(capacity=101)),
+        "count": dict(ring_struct=ring_with(count=101)), "ring's": dict(ring_struct=ring_with(states=None)),
+        "aligned": dict(obs=off(r["obs"])), "16-byte": dict(so=off(r["start_obs"])),
+        "16-byte aligned": dict(ring_struct=ring_with(next_states=ring.store["next_states"].data_ptr() + 4)),
+        "steps": dict(steps=0),
+    }
+    for word, kw in bad_calls.items():
+        assert call(**kw) != 0, word
+        msg = lib.uavtrack_last_error().decode()
+        assert msg.startswith("uavtrack_replay_add_rollout_nstep: ") and word.split(" =")[0] in msg, (word, msg)
+    torch.cuda.synchronize()
+    _same_image(_image(ring), img)
+    assert call() == 0                                                  # and the good call goes through
+    torch.cuda.synchronize()
+    assert _image(ring)["rewards"].tobytes() != img["rewards"].tobytes()
+
+
+@pytest.mark.parametrize("fn", ["update", "grad"])
+def test_host_side_errors_of_the_discounted_calls_enqueue_nothing(fn):
+    from uavtrack import _lib
+    H, A, n = 64, 12, 63
+    blob, b, store, cap, idx, it = _case(H, A, n, True)
+    L = _learner(H, A, "reference", blob, max_batch=n)
+    name = f"uavtrack_learner_{fn}_discounted"
+    ds = _dev(_discount_store(cap, 2))
+    losses, td, row = torch.empty(2, device=DEV), torch.zeros(n, device=DEV), torch.zeros(L.row_floats, device=DEV)
+    prio = torch.rand(cap, device=DEV) + 0.1
+    prio0 = prio.clone()
+    before = _state(L)
+    p = _lib.ptr
+
+    def call(n_=n, states=p(store["states"]), cap_=cap, idx_=p(it), out0=p(losses[0:1]), td_=p(td), row_=p(row)):
+        head = (L._h, n_, states, p(store["actions"]), p(store["rewards"]), p(store["next_states"]), cap_, idx_, None, p(ds))
+        if fn == "update":
+            return L._lib.uavtrack_learner_update_discounted(*head, out0, p(losses[1:2]), td_, p(prio), L._stream())
+        return L._lib.uavtrack_learner_grad_discounted(*head, td_, row_, L._stream())
+
+    bad_calls = [dict(states=None), dict(n_=0), dict(n_=n + 1), dict(cap_=0), dict(n_=n, idx_=None, cap_=n - 1)]
+    bad_calls += [dict(out0=None)] if fn == "update" else [dict(td_=None), dict(row_=None)]
+    for kw in bad_calls:
+        assert call(**kw) != 0, kw
+        assert L._lib.uavtrack_last_error().decode().startswith(name + ": "), kw
+    L.check()
+    _same(_state(L), before)
+    assert torch.equal(prio, prio0) and not td.any() and not row.any()
+    assert call() == 0
+    L.check()
+
+
+# ---- 7. the Python surface -------------------------------------------------------------------------------------------------
+
+def _filled_ring(kind, data, seed, k, n_step=3, gamma=GAMMA, dseed=1):
+    """An n-step ring holding `data` through add(), with a random discount store, and (prioritised) random priorities."""
+    n = len(data[1])
+    ring = (_uav().PrioritizedReplayRing if kind == "prioritised" else _uav().ReplayRing)(
+        n + 50, DEV, seed=seed, max_batch=k).with_nstep(n_step, gamma)
+    tr = {key: torch.from_numpy(x) for key, x in zip(STORES, data)}
+    tr["discounts"] = torch.from_numpy(_discount_store(n, dseed))
+    ring.add(tr)
+    if kind == "prioritised":
+        ring.priorities[:n] = _dev(np.random.RandomState(dseed).uniform(0.1, 2.0, n).astype(np.float32))
+    return ring
+
+
+def test_ring_arguments_and_the_gamma_check():
+    u = _uav()
+    for cls in (u.ReplayRing, u.PrioritizedReplayRing):
+        plain = cls(64, DEV)
+        with pytest.raises(ValueError, match="gamma"):
+            plain.with_nstep(3)
+        with pytest.raises(ValueError, match="n_step"):
+            plain.with_nstep(65, gamma=0.9)
+        with pytest.raises(ValueError, match="gamma"):
+            plain.with_nstep(1, gamma=1.5)
+        assert plain.with_nstep() is plain
+        assert plain.discounts is None and plain.n_step == 1 and plain.gamma is None
+        assert "discounts" not in (plain.sample(4) if cls is u.ReplayRing else plain.sample(4)[0])
+    data = dp.batch(np.random.RandomState(1), 300, 12)
+    ring = _filled_ring("uniform", data, 3, 100, gamma=0.9)
+    L = _learner(64, 12, "reference", dp.init_blob(64, 12, 1), max_batch=100)
+    before = _state(L)
+    for call in (lambda: L.update_from(ring, 100), lambda: L.grad_from(ring, 100), lambda: L.update_from_many([ring], 100)):
+        with pytest.raises(ValueError, match=r"0\.9\b.*0\.95\b"):
+            call()
+    _same(_state(L), before)
+    L9 = _learner(64, 12, "reference", dp.init_blob(64, 12, 1), max_batch=100, gamma=0.9)
+    L9.update_from(ring, 100)
+    L9.check()
+
+
+@pytest.mark.parametrize("kind", ["uniform", "prioritised"])
+def test_add_fills_the_discounts_and_sample_carries_them(kind):
+    n = 300
+    data = dp.batch(np.random.RandomState(2), n, 12)
+    ring = _filled_ring(kind, data, 3, 100)
+    ds = _discount_store(n, 1)
+    assert np.array_equal(ring.discounts[:n].cpu().numpy(), ds)
+    # without a "discounts" entry the slots get float32(gamma); a wrapping add fills both pieces
+    more = {key: torch.from_numpy(x[:80]) for key, x in zip(STORES, data)}
+    ring.add(more)
+    got = ring.discounts.cpu().numpy()
+    assert (got[n:n + 50] == G32).all() and (got[:30] == G32).all() and np.array_equal(got[30:n], ds[30:])
+    assert ring.pos == 30 and ring.count == n + 50
+    s = ring.sample(64)
+    tr, idx = (s, None) if kind == "uniform" else (s[0], s[1])
+    assert set(tr) == set(STORES) | {"discounts"} and tr["discounts"].shape == (64,)
+    if idx is not None:
+        assert torch.equal(tr["discounts"], ring.discounts[idx]) and torch.equal(tr["rewards"], ring.store["rewards"][idx])
+    empty = _uav().ReplayRing(8, DEV).with_nstep(1, GAMMA).sample(4)
+    assert empty["discounts"].numel() == 0
+
+
+@pytest.mark.parametrize("importance", [False, True])
+@pytest.mark.parametrize("kind", ["uniform", "prioritised"])
+def test_update_from_and_grad_from_are_draw_discounted_call_write(kind, importance):
+    H, A, n, k = 128, 12, 3000, 1000
+    data = dp.batch(np.random.RandomState(21), n, A)
+    blob = dp.init_blob(H, A, 21)
+    one, ring = _learner(H, A, "per_sample", blob, max_batch=k), _filled_ring(kind, data, 17, k)
+    two, twin = _learner(H, A, "per_sample", blob, max_batch=k), _filled_ring(kind, data, 17, k)
+    imp = importance and kind == "prioritised"
+    for u in range(3):
+        if u < 2:
+            al, cl, td = one.update_from(ring, k, beta=0.4, importance=importance)
+        else:                                                           # the split path through grad_from
+            row, td, gidx = one.grad_from(ring, k, importance=importance, beta=0.4)
+            al, cl = one.apply(row)
+            one.write_priorities(ring, gidx, td)
+        if kind == "prioritised":
+            idx, w = twin.draw(k, 0.4)
+        else:
+            idx, w = twin.draw(k), None
+        out = _update(two, k, twin.store, twin.capacity, idx, twin.priorities, w if imp else None, twin.discounts,
+                      direct=True)
+        assert np.array_equal(al.cpu().numpy(), out["actor_loss"]) and np.array_equal(cl.cpu().numpy(), out["critic_loss"])
+        assert np.array_equal(td.cpu().numpy(), out["td"]) and np.isfinite(out["actor_loss"]), u
+        assert torch.equal(ring._idx[:k], idx)
+        if kind == "prioritised":
+            assert torch.equal(ring.priorities, twin.priorities)
+    _same(_state(one), _state(two))
+    for x in (one, two, ring, twin):
+        x.check()
+    # the discounts are in the result: the same draws from a ring without them end elsewhere
+    three = _learner(H, A, "per_sample", blob, max_batch=k)
+    third = _filled_ring(kind, data, 17, k)
+    third.discounts = None
+    for u in range(3):
+        three.update_from(third, k, beta=0.4, importance=importance)
+    assert not np.array_equal(_state(three)["params"], _state(one)["params"])
+
+
+def test_update_from_many_over_two_nstep_rings():
+    H, A, k = 128, 12, 600
+    blob = dp.init_blob(H, A, 23)
+    datas = [dp.batch(np.random.RandomState(30 + j), 900 + 100 * j, A) for j in range(2)]
+    kinds = ("prioritised", "uniform")
+    rings = [_filled_ring(kd, d, 40 + j, k, dseed=j) for j, (kd, d) in enumerate(zip(kinds, datas))]
+    twins = [_filled_ring(kd, d, 40 + j, k, dseed=j) for j, (kd, d) in enumerate(zip(kinds, datas))]
+    L, M = _learner(H, A, "reference", blob, max_batch=k), _learner(H, A, "reference", blob, max_batch=k)
+    al, cl, tds = L.update_from_many(rings, k)
+    rows = M.new_rows(2)
+    drawn = []
+    for j, t in enumerate(twins):
+        idx = t.draw(k, 0.4)[0] if kinds[j] == "prioritised" else t.draw(k)
+        from uavtrack import _lib
+        td = torch.empty(k, device=DEV)
+        _lib.check(M._lib.uavtrack_learner_grad_discounted(
+            M._h, k, *M._batch_args(t.store, t.capacity, idx), None, _lib.ptr(t.discounts), _lib.ptr(td),
+            _lib.ptr(rows[j]), M._stream()), "uavtrack_learner_grad_discounted")
+        drawn.append((idx, td))
+    al2, cl2 = M.apply(rows)
+    for t, (idx, td) in zip(twins, drawn):
+        M.write_priorities(t, idx, td)
+    L.check(); M.check()
+    assert torch.equal(al, al2) and torch.equal(cl, cl2) and torch.isfinite(al)
+    for a, (_, td) in zip(tds, drawn):
+        assert torch.equal(a, td)
+    _same(_state(L), _state(M))
+    assert torch.equal(rings[0].priorities, twins[0].priorities)
+
+
+# ---- 8. graph --------------------------------------------------------------------------------------------------------------
+
+def test_add_and_update_captured_and_replayed_equal_eager():
+    """add_rollout (n_step = 3) + update_from on one linear stream, captured once and replayed three times == three eager
+    iterations, bitwise.  The ring's host-side pos and count are frozen into the capture, so every eager iteration
+    starts its add from the same pos and count as the captured one."""
+    H, A, k = 64, 12, 32
+    r = _rollout()
+    out = _out(_done("mid"))
+    blob = dp.init_blob(H, A, 42)
+
+    def fresh():
+        ring = _new_ring("prioritised", 100, n_step=3, gamma=GAMMA)      # empty: every drawn slot is one the add wrote
+        return _learner(H, A, "reference", blob, max_batch=k), ring
+
+    eager, re_ = fresh()
+    graphed, rg = fresh()
+
+    def iteration(L, ring):
+        ring.pos, ring.count = 0, 0                                     # every iteration enqueues the same add
+        ring.add_rollout(r["dev"]["obs_in"], out)
+        return L.update_from(ring, k, importance=True, beta=0.4)
+
+    torch.cuda.synchronize()
+    s = torch.cuda.Stream(DEV)
+    s.wait_stream(torch.cuda.current_stream())
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.stream(s):
+        with torch.cuda.graph(g, stream=s):
+            g_out = iteration(graphed, rg)
+    torch.cuda.current_stream().wait_stream(s)
+    torch.cuda.synchronize()
+    assert np.array_equal(_state(graphed)["step"], np.zeros(8))           # capture ran nothing
+    for c in range(3):
+        e_out = iteration(eager, re_)
+        g.replay()
+        torch.cuda.synchronize()
+        for x, y in zip(e_out, g_out):
+            assert torch.equal(x, y) and torch.isfinite(x).all(), c
+        assert np.array_equal(graphed._get_params(), eager._get_params()), c
+        a, b = _image(rg), _image(re_)
+        for key in a:                                                   # the written slots: the rest was never initialised
+            assert a[key][:NTR].tobytes() == b[key][:NTR].tobytes(), key
+    _same(_state(graphed), _state(eager))
+    assert np.array_equal(_state(graphed)["step"], np.full(8, 3))
+    for x in (graphed, eager, re_, rg):
+        x.check()
+
+
+# ---- 9. end to end -----------------------------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("kind", ["uniform", "prioritised"])
+def test_a_real_rollout_across_episode_ends(kind):
+    """3 envs x 5 UAVs x 3 targets, horizon 4, one fused launch of 10 steps with automatic reset: episode ends at t = 3 and
+    t = 7, and the rollout's tail cuts the third episode.  add_rollout with n_step = 3 equals the mirror on the launch's
+    own tensors, bitwise."""
+    u = _uav()
+    cfg = u.EnvConfig(n_envs=3, n_uav=5, m_targets=3, horizon=4)
+    env = u.BatchedUavEnv(cfg, DEV)
+    torch.manual_seed(3)
+    actor = u.ActorMLP(hidden_dim=32, action_dim=cfg.na_total)
+    ro = u.BatchedRollout(env, actor, device_actor=True, seed=3, auto_reset_seed=11)
+    ro.reset(seed=5)
+    obs_in = ro.obs.clone()
+    res = ro.run_fused(10)
+    host = {key: res[key].cpu().numpy() for key in ("obs", "actions", "reward", "done", "start_obs")}
+    assert host["done"][3].all() and host["done"][7].all() and host["done"].sum() == 6
+    ring = _new_ring(kind, 400, n_step=3, gamma=GAMMA)
+    _prefill(ring, 20, 20)
+    img = _image(ring)
+    ring.add_rollout(obs_in, res)
+    tr, m = nm.transitions(obs_in.cpu().numpy(), host["obs"], host["actions"], host["reward"], 3, GAMMA, host["done"],
+                           host["start_obs"])
+    assert m[:, 0].tolist() == [3, 3, 2, 1, 3, 3, 2, 1, 2, 1]
+    p2, c2 = nm.ring_add(img, 20, 20, tr)
+    assert (ring.pos, ring.count) == (p2, c2) == (170, 170)
+    _same_image(_image(ring), img)
+    # the learner trains from it (a ring of its own: the prefilled slots above hold sentinels, no transitions)
+    fresh = _new_ring(kind, 400, n_step=3, gamma=GAMMA)
+    fresh.add_rollout(obs_in, res)
+    assert fresh.count == 150 and torch.equal(fresh.discounts[:150], ring.discounts[20:170])
+    L = _learner(32, cfg.na_total, "reference", max_batch=64)
+    al, cl, _ = L.update_from(fresh, 64)
+    L.check()
+    assert torch.isfinite(al) and torch.isfinite(cl)
+    env.close()
+
+
+# ---- 10. the example -------------------------------------------------------------------------------------------------------
+
+def test_example_trains_on_n_step_targets(capsys):
+    """examples/train_maac.py --n-step 3: both learners, both device rings and --shards train; with the PyTorch buffer of
+    --replay uniform it exits with a message naming the two ring options."""
+    import os
+    import sys
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "examples"))
+    import train_maac
+    common = ["--envs", "64", "--steps", "20", "--iters", "2", "--batch", "4096", "--updates", "2", "--n-step", "3"]
+    for extra in (["--replay", "prioritized", "--learner", "device", "--publish", "device"],
+                  ["--replay", "uniform-device", "--learner", "torch"],
+                  ["--replay", "prioritized", "--learner", "torch", "--importance"],
+                  ["--replay", "uniform-device", "--learner", "device", "--shards", "2"]):
+        hist = train_maac.main(common + extra)
+        assert len(hist) == 2 and np.isfinite(hist).all(), extra
+        lines = [ln for ln in capsys.readouterr().out.splitlines() if ln.startswith("iter")]
+        assert len(lines) == 2 and all(np.isfinite(float(ln.split("critic loss")[1].split()[0])) for ln in lines), extra
+    with pytest.raises(SystemExit):
+        train_maac.main(common + ["--replay", "uniform"])
+    err = capsys.readouterr().err
+    assert "--replay prioritized" in err and "uniform-device" in err
