@@ -70,9 +70,9 @@ __device__ __forceinline__ float fast_exp2(float v) { return __builtin_amdgcn_ex
 __device__ __forceinline__ v2f pk_fma(v2f a, v2f b, v2f c) { return __builtin_elementwise_fma(a, b, c); }
 __device__ __forceinline__ v2f splat(float v) { return (v2f){v, v}; }
 // Range test of two squared distances in one instruction: 1.0 where d2 <= K else 0.0, as
-// clamp(fma(d2, -S, nextafter(K) * S)) with S a power of two >= 1 / ulp(K) (fold_constants).  The
-// FMA rounds the exact value once, so its sign is exact; the smallest positive value is
-// ulp(K) * S >= 1 and clamps to exactly 1; overflow gives -inf -> 0; NaN clamps to 0 (DX10 clamp),
+// clamp(fma(d2, -S, nextafter(K) * S)) with S = 2 / ulp(smallest K), a power of two (fold_constants).  The FMA rounds the
+// exact value once, so its sign is exact; the smallest positive value is ulp(K) * S >= 2 (strict form d2 < K, fma(d2, -S, K * S): ulp(K) / 2 * S
+// >= 1 below a power of two, where the spacing halves) and clamps to exactly 1; overflow gives -inf -> 0; NaN clamps to 0 (DX10 clamp),
 // the same as the compare it replaces.  There is no packed compare/select, so this replaces
 // 2 v_cmp + 2 v_cndmask.
 // a wave-uniform value parked in a vector register (opaque to the compiler: it stays there)

@@ -19,6 +19,8 @@ Scenarios:
   g6  reset-only layouts N in {5,10,20,50}
   g7  hand-placed edge cases (walls, wraps, inclusive/strict thresholds, ...)
   g9  range tests one fp32 ulp inside / outside their thresholds after the move
+  g10 the same knife edges (inside / on / outside) at ten constants sets, every role of tests/range_edge_scenes.py: MAAC-G,
+      and MAAC-R H64 at three of the sets
   g8  non-default constants (dt .5, v_max 13, h_max pi/5, dp 173.3, dc 411.7, alpha/beta/gamma .5/.3/.2, target v_max 7,
       na 9, 1500 x 1100 box, reward normalisation by config n_uav / m_targets != the environment's own): N20 M10 MAAC-G
       and MAAC-R H64, N7 M4 MAAC; 4 seeds x 25 steps each
@@ -266,6 +268,38 @@ def gen_ulp_edges():
     run_cases("g9_ulp_edges", cases, None)
 
 
+def gen_ulp_edges_constants():
+    """g10: g9's knife edges away from the yaml constants.  tests/range_edge_scenes.py builds the scenes (and asserts in
+    fp64 that every coordinate of every step is an fp32 number and that only the designated pair is near a threshold):
+    2-D, one move, N = 4 to 6, M = 2 to 3, every threshold / side / role of the shape, under MAAC-G for the ten constants
+    sets and under MAAC-R (H = 64, the weights of pmi_h64) for three of them.  One group of stacked scenes per (set, shape,
+    mode); the scenes of a group share one configuration."""
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "tests"))
+    import range_edge_scenes as res
+    groups = res.g10_groups()
+    pmi = make_pmi(64, 43)
+    arrays, meta = {}, {"cases": []}
+    for name, cs, N, M, use_pmi in groups:
+        scenes = res.all_scenes(cs, N, M, 2, moves=1)
+        kw = res.config(cs, N, M, 2, 1, 1, cooperative=0.3)
+        cfg = make_cfg(N, M, 0.3, x_max=kw["x_max"], y_max=kw["y_max"], na=kw["na"])
+        cfg["uav"].update(dp=kw["dp"], dc=kw["dc"], v_max=kw["u_v_max"])
+        cfg["target"]["v_max"] = kw["t_v_max"]
+        eps = []
+        for sc in scenes:
+            st = sc.state
+            eps.append(run_episode(cfg, pmi if use_pmi else None, 1, seed=1,
+                                   init=dict(uav=list(zip(st["ux"], st["uy"], st["uh"], st["ua"])),
+                                             target=list(zip(st["tx"], st["ty"], st["th"]))),
+                                   actions=[[int(a) for a in sc.actions[0]]]))
+        for k, v in stack_eps(eps).items():
+            if k != "obs0":
+                arrays[f"{name}__{k}"] = v
+        meta["cases"].append(dict(name=name, constants=cs, n_uav=N, m_targets=M, cooperative=0.3, pmi=use_pmi, steps=1,
+                                  cfg=cfg, norm_n_uav=N, norm_m_targets=M, scenes=[sc.name for sc in scenes]))
+    save("g10_ulp_edges_constants", arrays, meta)
+
+
 def gen_actor():
     """FnnPolicyNet.forward (actor_critic.py:85-98) on recorded observations: weights + obs -> probs (fp32)."""
     from models.actor_critic import FnnPolicyNet  # noqa: E402  (reference)
@@ -430,6 +464,9 @@ def main():
     if len(sys.argv) > 1 and sys.argv[1] == "--only-ulp":
         gen_ulp_edges()
         return
+    if len(sys.argv) > 1 and sys.argv[1] == "--only-ulp-constants":
+        gen_ulp_edges_constants()
+        return
     if len(sys.argv) > 1 and sys.argv[1] == "--only-h64":
         gen_h64()
         return
@@ -453,6 +490,7 @@ def main():
     gen_pmi_train()
     gen_export()
     gen_ulp_edges()
+    gen_ulp_edges_constants()
 
 
 if __name__ == "__main__":

@@ -18,6 +18,7 @@ sys.path[:0] = [ROOT, os.path.join(ROOT, "marl-uavs-targets-tracking_amd"), os.p
 import torch  # noqa: E402
 import uavtrack  # noqa: E402
 from oracle import OracleConfig, OracleEnv, OraclePmi, actor_actions, greedy_actions  # noqa: E402
+from range_edge_scenes import CONSTANTS  # noqa: E402
 from test_hip_parity import random_pmi_state_dict  # noqa: E402
 
 
@@ -49,8 +50,12 @@ def case(c, rng):
         os.environ.pop("UAVTRACK_WGS", None)
     na_turn = int(rng.choice([12, 12, 12, 4, 7, 9]))        # environment.na (reference: 12)
     na = na_turn * (3 if dim == 3 else 1)
-    tag = f"case {c}: N{N} M{M} B{B} box{box} mode{mode} H{H} T{T} off{off} dim{dim} wgs{wgs} na{na_turn}"
-    kw = dict(n_envs=B, n_uav=N, m_targets=M, x_max=box, y_max=box, cooperative=0.0 if mode == 0 else 0.3,
+    # dp and dc from the ten constants sets of tests/range_edge_scenes.py (fold_constants' scale and thresholds change with
+    # their binades); a generator of its own, so the other draws of a case do not move
+    cs = sorted(CONSTANTS)[np.random.RandomState(1000 + c).randint(len(CONSTANTS))]
+    dp, dc = CONSTANTS[cs]["dp"], CONSTANTS[cs]["dc"]
+    tag = f"case {c}: N{N} M{M} B{B} box{box} mode{mode} H{H} T{T} off{off} dim{dim} wgs{wgs} na{na_turn} {cs}(dp{dp} dc{dc})"
+    kw = dict(n_envs=B, n_uav=N, m_targets=M, x_max=box, y_max=box, cooperative=0.0 if mode == 0 else 0.3, dp=dp, dc=dc,
               reward_mode=uavtrack.RewardMode(mode), env_offset=off, dim=dim, nc=3 if dim == 3 else 1, z_max=300.0, na=na_turn)
     pmi_sd = random_pmi_state_dict(H, c)
     if mode == 2:
@@ -86,7 +91,7 @@ def case(c, rng):
     np.testing.assert_allclose(fused["ep_sums"].cpu().numpy(), ep.cpu().numpy(), rtol=1e-5, atol=1e-5, err_msg=tag)
     # 4. teacher-forced vs oracle (one more step from the current state)
     orc = OracleEnv(OracleConfig(n_envs=B, n_uav=N, m_targets=M, x_max=box, y_max=box, cooperative=kw["cooperative"],
-                                 dim=dim, nc=3 if dim == 3 else 1, z_max=300.0, na=na_turn), n_threads=8)
+                                 dim=dim, nc=3 if dim == 3 else 1, z_max=300.0, na=na_turn, dp=dp, dc=dc), n_threads=8)
     if mode == 2:
         orc.pmi = OraclePmi.from_state_dict(pmi_sd)
     st = host(a.get_state())
