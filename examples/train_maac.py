@@ -15,6 +15,7 @@ update is the same rule on a sampled batch, and the new actor weights are re-upl
     python examples/train_maac.py --replay prioritized --learner device --publish device --log-every 10   # no host sync per iteration
     python examples/train_maac.py --replay prioritized --learner device --importance --beta-final 1.0     # train on the importance weights, beta annealed on the device
     python examples/train_maac.py --replay prioritized --learner device --n-step 3                        # 3-step returns folded by the ring's add
+    python examples/train_maac.py --replay prioritized --learner device --td-lambda 0.9                   # lambda-returns: critic values + a backward scan in the ring's add
     python examples/train_maac.py --method maac-r --pmi-trainer device --learner device --replay prioritized --publish device --log-every 10
     python examples/train_maac.py --shards 8 --envs 32768 --n-uav 20 --learner device --replay prioritized --publish device   # 8 shard handles, one learner
     python examples/train_maac.py --shards 4 --method maac-r --pmi-trainer device --learner device --replay prioritized --publish device   # ... and one PMI trainer
@@ -62,7 +63,8 @@ def update(actor, critic, opt_a, opt_c, batch, gamma, weights=None, entropy_coef
     draw's importance weights, one per row, multiplied into the per-sample losses before the mean.  entropy_coef and
     max_grad_norm: the two terms of DeviceActorCritic.set_regularisation, so that --learner torch and --learner device
     stay comparable; diag (a dict) receives the mean entropy and the two gradient norms before clipping.  A batch from an
-    n-step ring (--n-step) carries "discounts", gamma^m per row, which take gamma's place in the target."""
+    n-step ring (--n-step) carries "discounts", gamma^m per row, which take gamma's place in the target; so does a batch
+    from a lambda ring (--td-lambda), whose rewards and discounts make that target the lambda-return."""
     s, a, r, s2 = batch["states"], batch["actions"].long().unsqueeze(1), batch["rewards"], batch["next_states"]
     td_target = r + batch.get("discounts", gamma) * critic(s2)
     td_delta = td_target - critic(s)
@@ -106,8 +108,16 @@ def device_learner(args, uavtrack, na_total, dev, max_batch):
 
 
 def nstep_ring(args, ring):
-    """--n-step N > 1: the ring stores N-step returns and their discounts (with_nstep); N = 1 leaves it what it was."""
+    """--n-step N > 1: the ring stores N-step returns and their discounts (with_nstep); N = 1 leaves it what it was.
+    --td-lambda L: the ring stores lambda-returns instead (with_lambda)."""
+    if args.td_lambda is not None:
+        return ring.with_lambda(args.td_lambda, args.gamma)
     return ring.with_nstep(args.n_step, args.gamma) if args.n_step > 1 else ring
+
+
+def critic_kwargs(args, critic):
+    """add_rollout's extra argument under --td-lambda: the critic whose values the lambda add folds the rewards with."""
+    return {} if args.td_lambda is None else {"critic": critic}
 
 
 def regularised(args):
@@ -226,7 +236,7 @@ def train_sharded(args, timings=None):
             obs_in = ro.obs.clone()
             res = ro.run_fused(args.steps, out=outs[k], stats=stats[k])    # done fires at the horizon: one record per episode
             outs[k] = {key: v for key, v in res.items() if key != "ep_sums"}
-            ring.add_rollout(obs_in, res)
+            ring.add_rollout(obs_in, res, **critic_kwargs(args, learner))   # (--td-lambda: every ring, the one learner's values)
             eps.append(res["ep_sums"])
         if log:
             torch.cuda.synchronize()
@@ -330,6 +340,12 @@ def main(argv=None, timings=None):
                          "across an episode end or the rollout's last step) and keeps gamma^m per slot "
                          "(ring.with_nstep(N, gamma)); both learners bootstrap with that discount.  Needs --replay "
                          "prioritized or uniform-device")
+    ap.add_argument("--td-lambda", type=float, default=None,
+                    help="L in [0, 1]: train on TD(lambda) targets.  The ring's add evaluates the critic on the rollout's "
+                         "observations and walks every agent's chain backwards (ring.with_lambda(L, gamma), "
+                         "add_rollout(critic=...)): each slot keeps r + gamma L G' as its reward and gamma (1 - L) as its "
+                         "discount, never across an episode end or the rollout's last step.  Needs --replay prioritized or "
+                         "uniform-device; not with --n-step > 1")
     ap.add_argument("--alpha", type=float, default=0.6, help="--replay prioritized: priority exponent (train.py:74)")
     ap.add_argument("--beta", type=float, default=0.4, help="--replay prioritized: importance exponent (train.py:100)")
     ap.add_argument("--importance", action="store_true",
@@ -388,6 +404,14 @@ def main(argv=None, timings=None):
     if args.n_step > 1 and args.replay == "uniform":
         ap.error("--n-step N > 1 needs --replay prioritized or --replay uniform-device: the n-step returns are folded by "
                  "the device rings' add (the PyTorch buffer of --replay uniform stores one-step transitions)")
+    if args.td_lambda is not None:
+        if not 0.0 <= args.td_lambda <= 1.0:
+            ap.error("--td-lambda must be in [0, 1]")
+        if args.n_step > 1:
+            ap.error("--td-lambda and --n-step N > 1 exclude each other: a ring stores lambda-returns or n-step returns")
+        if args.replay == "uniform":
+            ap.error("--td-lambda needs --replay prioritized or --replay uniform-device: the lambda-returns are folded by "
+                     "the device rings' add (the PyTorch buffer of --replay uniform stores one-step transitions)")
     if args.importance and args.replay != "prioritized":
         ap.error("--importance needs --replay prioritized (a uniform draw has no importance weights)")
     if args.beta_final is not None and not args.importance:
@@ -467,7 +491,7 @@ def main(argv=None, timings=None):
         res = rollout.run_fused(T, out=out, stats=stats)              # K * B episodes, one launch; done at the horizon closes them
         out = {k: v for k, v in res.items() if k != "ep_sums"}        # reuse the output buffers next time
         if args.replay != "uniform":
-            replay.add_rollout(obs_in, res)                           # one library call, straight from the outputs
+            replay.add_rollout(obs_in, res, **critic_kwargs(args, critic if learner is None else learner))   # straight from the outputs
         else:
             replay.add(uavtrack.transitions_from_rollout(obs_in, res))
         if log:

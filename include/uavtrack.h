@@ -659,6 +659,17 @@ int uavtrack_learner_grad_discounted(uavtrack_learner *learner, int64_t n,
                                      const float *weights, const float *discounts, float *td_delta, float *row,
                                      void *stream);
 
+/* ---- the critic alone: V(x) outside an update ----
+ * values[i] = V(rows[i]) for n rows x[12] (DEVICE fp32 [n][12], 16-byte aligned; values DEVICE fp32 [n]) with the
+ * learner's critic parameters, by exactly the chain of the update's own V(s), H = hidden:
+ *   p_j = b1c[j]; for k = 0 .. 11: p_j = fmaf(W1c[j][k], x[k], p_j); h_j = fmaxf(p_j, 0);
+ *   z = b2c[0];   for j = 0 .. H - 1: z = fmaf(W2c[j], h_j, z);      V = z
+ * so a caller reads, bit for bit, the V(s) an update with the same parameters forms.  Stream-ordered, no
+ * synchronisation, no allocation, capturable; it needs no scratch, so n is not limited by the reserved batch, and it
+ * changes no learner state.  The parameters are read when the launch executes: a graph replayed after updates evaluates
+ * the critic of that moment.  Returns an error, enqueuing nothing, for a null pointer, n < 1 or misaligned rows. */
+int uavtrack_learner_values(uavtrack_learner *learner, int64_t n, const float *rows, float *values, void *stream);
+
 /* Synchronises `stream`; fails if any update or apply since the previous check was refused on the device (bad action,
  * index, importance weight or discount, or a row of another layout).  refused (nullable) receives their number; the count restarts at 0. */
 int uavtrack_learner_check(uavtrack_learner *learner, int64_t *refused, void *stream);
@@ -901,6 +912,41 @@ int uavtrack_replay_add_rollout_nstep(uavtrack_replay *replay, const uavtrack_re
                                       int64_t steps, int64_t envs, int64_t n_uav, const float *obs_in, const float *obs,
                                       const int32_t *actions, const float *reward, const uint8_t *done,
                                       const float *start_obs, int32_t n_step, double gamma, void *stream);
+
+/* ---- TD(lambda) targets: lambda-returns from one rollout ----
+ * uavtrack_replay_add_rollout_episodes with each transition stored as a (reward, discount) pair whose one-step target
+ * is the lambda-return.  T = steps, agents = envs * n_uav, f = t * agents + b * n_uav + i as above.
+ * values [T][envs][n_uav] is a caller-given DEVICE fp32 array meant to hold V(obs[t][b][i]), the value of the state step
+ * t ends in (at an episode end that episode's last observation, which is what the one-step form bootstraps from;
+ * uavtrack_learner_values over obs gives it).  g = (float)gamma and l = (float)lambda, both finite and in [0, 1];
+ * gl = g * l and c = g * (1.0f - l).  Every operation is rounded to fp32 on its own (no fused multiply-add).
+ * Per agent chain (b, i), walking t = T - 1 ... 0 and carrying G:
+ *     cut(t) = (t == T - 1) || (done != NULL && done[t][b] != 0) || (gl == 0)
+ *     cut:     R_t = reward[t][b][i]               d_t = g
+ *     else:    R_t = reward[t][b][i] + gl * G      d_t = c
+ *     G = R_t + d_t * values[t][b][i]
+ * Stored transition (t, b, i): state, action and priority exactly as uavtrack_replay_add_rollout_episodes stores them
+ * (without done and start_obs: as uavtrack_replay_add_rollout); next_state = obs[t][b][i]; reward = R_t; discount = d_t,
+ * written to discounts [capacity] as the n-step add writes its own.  Slots, the window for T * agents > capacity and the
+ * wrap are those of the other adds; the chain still walks rows that are themselves not written.
+ * The learner's target of such a slot (uavtrack_learner_update_discounted) is
+ *     R_t + d_t V_now(s'_t) = r_t + g l G_{t+1} + g (1 - l) V_now(s_{t+1}),
+ * the lambda-return with its tail G_{t+1} evaluated by the critic as it stood at add time and its first bootstrap term
+ * by the critic at update time.  Slots keep the tail they were added with (stale tails are accepted, as in caches of
+ * lambda-returns under replay).  A window never crosses an episode end and is cut at the rollout's last step, where the
+ * transition is the one-step one.  d_t is in [0, 1].  With lambda == 0 or gamma == 0 every step is a cut and all five
+ * stores and the priorities end byte-identical to uavtrack_replay_add_rollout_nstep at n_step == 1 (a reward of -0.0
+ * included: a cut copies the reward, it does not add zero to it).  With lambda == 1, d_t == 0 inside a segment:
+ * Monte-Carlo up to the cut, the bootstrap at the cut.  Non-finite values propagate into the stored rewards as non-finite
+ * rewards do; the add does not inspect them.
+ * The one-step write runs first; a scan kernel follows it, one thread per agent chain, the loads of eight steps issued
+ * ahead of the carried G.  The horizon is unbounded.  Stream-ordered, no synchronisation, no allocation, capturable.
+ * Errors: those of uavtrack_replay_add_rollout_nstep, with values required and lambda finite and in [0, 1]. */
+int uavtrack_replay_add_rollout_lambda(uavtrack_replay *replay, const uavtrack_replay_ring *ring, float *discounts,
+                                       int64_t steps, int64_t envs, int64_t n_uav, const float *obs_in, const float *obs,
+                                       const int32_t *actions, const float *reward, const uint8_t *done,
+                                       const float *start_obs, const float *values, double lambda, double gamma,
+                                       void *stream);
 
 /* PrioritizedReplayBuffer.sample's draw (train.py:98-112) without the gather: n slots with replacement from
  * P(i) = p_i^alpha / sum_j p_j^alpha over [0, count) (the draw stream above) into indices [n] (DEVICE int64), and,

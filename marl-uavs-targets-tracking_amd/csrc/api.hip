@@ -1817,6 +1817,18 @@ int uavtrack_learner_write_priorities(uavtrack_learner *learner, int64_t n, cons
     return 0;
 }
 
+int uavtrack_learner_values(uavtrack_learner *learner, int64_t n, const float *rows, float *values, void *stream)
+{
+    if (!learner) return fail("%s: null handle", __func__);
+    if (!rows || !values) return fail("%s: rows and values must not be null", __func__);
+    if (n < 1) return fail("%s: n = %lld < 1", __func__, (long long)n);
+    if (n > INT64_MAX / 48) return fail("%s: n = %lld rows overflow", __func__, (long long)n);
+    if (((uintptr_t)rows & 15) != 0) return fail("%s: rows must be 16-byte aligned", __func__);
+    ON_DEVICE(learner->cfg.device_id);
+    HIP_TRY(launch_learner_values(learner->d, n, rows, values, static_cast<hipStream_t>(stream)));
+    return 0;
+}
+
 int uavtrack_learner_check(uavtrack_learner *learner, int64_t *refused, void *stream)
 {
     int count = 0;
@@ -2178,6 +2190,30 @@ int uavtrack_replay_add_rollout_nstep(uavtrack_replay *replay, const uavtrack_re
     ON_DEVICE(replay->cfg.device_id);
     HIP_TRY(launch_replay_add_nstep(replay->d, ring_view(ring), discounts, steps, envs, n_uav, obs_in, obs, actions, reward,
                                     done, start_obs, (int)n_step, (float)gamma, static_cast<hipStream_t>(stream)));
+    return 0;
+}
+
+int uavtrack_replay_add_rollout_lambda(uavtrack_replay *replay, const uavtrack_replay_ring *ring, float *discounts,
+                                       int64_t steps, int64_t envs, int64_t n_uav, const float *obs_in, const float *obs,
+                                       const int32_t *actions, const float *reward, const uint8_t *done,
+                                       const float *start_obs, const float *values, double lambda, double gamma,
+                                       void *stream)
+{
+    const char *fn = "uavtrack_replay_add_rollout_lambda";
+    if (!replay) return fail("%s: null handle", fn);
+    if (accept_ring(replay, fn, ring, true, false)) return 1;
+    if (!discounts || !obs_in || !obs || !actions || !reward || !values)
+        return fail("%s: discounts, obs_in, obs, actions, reward and values must not be null", fn);
+    if (!done != !start_obs) return fail("%s: done and start_obs must both be given or both be null", fn);
+    if (!aligned16(obs_in) || !aligned16(obs) || !aligned16(start_obs))
+        return fail("%s: obs_in, obs and start_obs must be 16-byte aligned", fn);
+    if (!(lambda >= 0.0 && lambda <= 1.0)) return fail("%s: lambda = %g is not a finite value in [0, 1]", fn, lambda);
+    if (!(gamma >= 0.0 && gamma <= 1.0)) return fail("%s: gamma = %g is not a finite value in [0, 1]", fn, gamma);
+    if (steps < 1 || envs < 1 || n_uav < 1) return fail("%s: steps, envs and n_uav must be >= 1", fn);
+    if (envs > INT64_MAX / n_uav || steps > INT64_MAX / (envs * n_uav) / 12) return fail("%s: steps * envs * n_uav overflows", fn);
+    ON_DEVICE(replay->cfg.device_id);
+    HIP_TRY(launch_replay_add_lambda(replay->d, ring_view(ring), discounts, steps, envs, n_uav, obs_in, obs, actions, reward,
+                                     done, start_obs, values, (float)lambda, (float)gamma, static_cast<hipStream_t>(stream)));
     return 0;
 }
 

@@ -367,6 +367,9 @@ hipError_t launch_learner_apply(const LearnerDevice &d, const float *rows, int c
                                 float *critic_loss, hipStream_t stream);
 hipError_t launch_learner_priorities(const LearnerDevice &d, const int64_t *idx, int64_t n, int64_t capacity,
                                      const float *td, float *prio, hipStream_t stream);
+// uavtrack_learner_values: values[i] = V(rows[i]) with the critic as it stands when the launch executes, the chain of
+// the gradient kernel's V(s) to the bit; no scratch, any n >= 1
+hipError_t launch_learner_values(const LearnerDevice &d, int64_t n, const float *rows, float *values, hipStream_t stream);
 
 // pmi_train_kernel.hip -- the device PMI trainer (uavtrack_pmi_trainer_*).  `state` holds the float entries of the
 // reference PMINetwork's state_dict in its order (26 tensors: per Linear+BatchNorm1d block weight, bias, bn weight, bn
@@ -490,6 +493,13 @@ hipError_t launch_replay_add_nstep(const ReplayDevice &d, const ReplayRingView &
                                    int64_t envs, int64_t n_uav, const float *obs_in, const float *obs,
                                    const int32_t *actions, const float *reward, const uint8_t *done, const float *start_obs,
                                    int n_step, float gamma, hipStream_t stream);
+// uavtrack_replay_add_rollout_lambda: launch_replay_add's write (episodes form with done / start_obs, plain form without),
+// then the backward scan over each agent's chain that overwrites the written slots' rewards with R_t and leaves d_t in
+// discounts [capacity]; values [steps][envs][n_uav]
+hipError_t launch_replay_add_lambda(const ReplayDevice &d, const ReplayRingView &ring, float *discounts, int64_t steps,
+                                    int64_t envs, int64_t n_uav, const float *obs_in, const float *obs,
+                                    const int32_t *actions, const float *reward, const uint8_t *done, const float *start_obs,
+                                    const float *values, float lambda, float gamma, hipStream_t stream);
 
 // episode_kernel.hip -- per-episode results (uavtrack_episode_stats_*).  The open episodes are struct-of-arrays over the
 // environments; a closing step's log slot comes from a scan over the done matrix in groups of kEpisodeGroup environments

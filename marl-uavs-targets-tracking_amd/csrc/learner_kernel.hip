@@ -40,6 +40,9 @@
 // network) runs between "scale" and "Adam": learner_gradsum_kernel forms the scaled gradient once and leaves each
 // workgroup's sums of squares in fp64, learner_clip_kernel adds them in workgroup order and writes both coefficients,
 // and the same Adam kernel then runs over (the scaled gradient, count 1, the coefficients as its scales).
+//
+// The critic alone (uavtrack_learner_values): learner_values_kernel, at the end of the kernels below, evaluates V(x) of
+// any number of rows by the chain of the layer-1 and layer-2 loops above, to the bit, and touches no learner state.
 
 #include "internal.h"
 
@@ -493,7 +496,75 @@ __global__ void learner_prio_write_kernel(const int64_t *idx, int64_t n, const f
     if (last[i]) prio[idx ? idx[i] : i] = fabsf(td[i]);
 }
 
+// ---- the critic alone (uavtrack_learner_values): V(x) of n rows, the chain of learner_grad_kernel's V(s) to the bit.
+// One lane owns two rows (i and i + kVW of the workgroup's chunk of 2 kVW): 24 inputs in registers from six 16-byte
+// loads, consecutive lanes on consecutive 48-byte rows.  The critic's 14 H + 1 words are wavefront-uniform; the
+// workgroup copies them into LDS once, one 64-byte record per hidden unit {W1c[j][0..11], b1c[j], W2c[j], -, -}, and
+// every lane reads a record through the same address (four broadcast 16-byte LDS reads for 2 x 13 fused operations
+// and two max).  The chains are explicit fmaf in the gradient kernel's order; nothing is reassociated.
+
+constexpr int kVW = 256;          // threads per workgroup of the values kernel
+constexpr int kVRec = 16;         // words per hidden unit's LDS record
+
+__device__ __forceinline__ void load_row(float (&x)[12], const float *src)
+{
+    const float4 *s = reinterpret_cast<const float4 *>(src);
+    const float4 a = s[0], b = s[1], c = s[2];
+    x[0] = a.x; x[1] = a.y; x[2] = a.z; x[3] = a.w;
+    x[4] = b.x; x[5] = b.y; x[6] = b.z; x[7] = b.w;
+    x[8] = c.x; x[9] = c.y; x[10] = c.z; x[11] = c.w;
+}
+
+__global__ void __launch_bounds__(kVW) learner_values_kernel(const float *params, LearnerLayout L, int64_t n,
+                                                             const float *rows, float *values)
+{
+    __shared__ __attribute__((aligned(16))) float rec[kLearnerMaxHidden * kVRec];
+    const int tid = threadIdx.x, H = L.H;
+    const float *W1c = params + L.c_w1, *b1c = params + L.c_b1, *W2c = params + L.c_w2;
+    for (int e = tid; e < H * kVRec; e += kVW) {
+        const int j = e / kVRec, k = e - j * kVRec;
+        rec[e] = k < 12 ? W1c[j * 12 + k] : (k == 12 ? b1c[j] : (k == 13 ? W2c[j] : 0.0f));
+    }
+    const float b2 = params[L.c_b2];
+    __syncthreads();
+    const int64_t chunk = 2 * kVW;
+    for (int64_t base = (int64_t)blockIdx.x * chunk; base < n; base += (int64_t)gridDim.x * chunk) {
+        const int64_t i0 = base + tid, i1 = i0 + kVW;
+        float x0[12], x1[12];
+#pragma unroll
+        for (int k = 0; k < 12; ++k) { x0[k] = 0.0f; x1[k] = 0.0f; }
+        if (i0 < n) load_row(x0, rows + i0 * 12);
+        if (i1 < n) load_row(x1, rows + i1 * 12);
+        float z0 = b2, z1 = b2;
+#pragma unroll 2
+        for (int j = 0; j < H; ++j) {
+            const float4 *r = reinterpret_cast<const float4 *>(rec + j * kVRec);
+            const float4 wa = r[0], wb = r[1], wc = r[2], tail = r[3];
+            const float w[12] = {wa.x, wa.y, wa.z, wa.w, wb.x, wb.y, wb.z, wb.w, wc.x, wc.y, wc.z, wc.w};
+            float p0 = tail.x, p1 = tail.x;
+#pragma unroll
+            for (int k = 0; k < 12; ++k) {
+                p0 = fmaf(w[k], x0[k], p0);
+                p1 = fmaf(w[k], x1[k], p1);
+            }
+            z0 = fmaf(tail.y, fmaxf(p0, 0.0f), z0);
+            z1 = fmaf(tail.y, fmaxf(p1, 0.0f), z1);
+        }
+        if (i0 < n) values[i0] = z0;
+        if (i1 < n) values[i1] = z1;
+    }
+}
+
 }  // namespace
+
+hipError_t launch_learner_values(const LearnerDevice &d, int64_t n, const float *rows, float *values, hipStream_t st)
+{
+    static_assert(kLearnerMaxHidden * kVRec * sizeof(float) <= 64 * 1024, "the critic's records fit static LDS");
+    int64_t blocks = (n + 2 * kVW - 1) / (2 * kVW);
+    if (blocks > 2048) blocks = 2048;
+    hipLaunchKernelGGL(learner_values_kernel, dim3((unsigned)blocks), dim3(kVW), 0, st, d.params, d.L, n, rows, values);
+    return hipGetLastError();
+}
 
 int learner_rows_per_tile(int hidden)
 {

@@ -36,6 +36,9 @@
 // The n-step form (uavtrack_replay_add_rollout_nstep) has a write kernel of its own, replay_write_nstep_kernel: one thread
 // per transition, which folds up to n rewards of its agent into the stored reward, takes the next state from the end of
 // that window and leaves the window's discount in a fifth per-slot store.
+// The lambda form (uavtrack_replay_add_rollout_lambda) is the one-step write above followed by replay_lambda_scan_kernel:
+// one thread per agent chain walks the rollout backwards, carries the lambda-return G and overwrites the written slots'
+// rewards with R_t, leaving d_t in the discount store.
 
 #include "internal.h"
 #include "philox.h"
@@ -479,6 +482,93 @@ __global__ void __launch_bounds__(kSW) replay_write_nstep_kernel(NstepArgs a)
     }
 }
 
+// ---- the lambda add's scan (uavtrack_replay_add_rollout_lambda; include/uavtrack.h has the definitions)
+
+struct LambdaArgs {
+    float *rewards, *discounts;                // the ring's [capacity] stores
+    const float *reward, *values;              // [steps][agents]
+    const uint8_t *done;                       // nullable [steps][envs]
+    int64_t capacity, agents, envs, n_uav, steps, skip, start;
+    float g, gl, c;                            // (float)gamma, g * l, g * (1 - l)
+};
+
+constexpr int kLambdaAhead = 8;                // steps per group: its loads are in flight while the group before it folds
+constexpr int kLambdaW = 64;                   // threads per workgroup: a rollout has few chains (envs * n_uav), each a long
+                                               // walk, so single-wavefront workgroups spread them over the most CUs
+
+// One thread per agent chain r = b * n_uav + i, lanes consecutive in r: for a fixed t the wavefront's reads of reward[t]
+// and values[t] are whole lines and its two stores are contiguous slots.  The loads do not depend on the carried G, so the
+// walk is cut into groups of kLambdaAhead steps whose loads are unconditional and issued together, one group ahead of
+// the fold (the steps beyond a multiple of kLambdaAhead, the rollout's last ones, go first, one at a time): a chain
+// waits for memory once per group, not once per step.  The horizon is the whole rollout and nothing is kept per thread
+// beyond two groups of kLambdaAhead steps.  WINDOW (the rollout exceeds the ring): rows before `skip` are walked (the
+// walk has no other order) and not written; without it the fold is straight-line code.
+template <bool DONE, bool WINDOW>
+__global__ void __launch_bounds__(kLambdaW) replay_lambda_scan_kernel(LambdaArgs a)
+{
+#pragma clang fp contract(off)
+    const int64_t cap = a.capacity, M = a.agents, last = a.steps - 1;
+    const float g = a.g, gl = a.gl, c = a.c;                           // (values: a select between two struct members
+    const bool all_cut = gl == 0.0f;                                   //  would be a select of addresses and a load)
+    for (int64_t r = (int64_t)blockIdx.x * kLambdaW + threadIdx.x; r < M; r += (int64_t)gridDim.x * kLambdaW) {
+        const float *rw = a.reward + r, *vv = a.values + r;             // rw[u * M] = reward[u][b][i]
+        const uint8_t *dn = DONE ? a.done + r / a.n_uav : nullptr;      // dn[u * envs] = done[u][b]
+        float G = 0.0f;
+        auto fold = [&](int64_t u, float rew, float v, unsigned fired) {
+            const bool cut = (u == last) | all_cut | (fired != 0);
+            const float R = cut ? rew : rew + gl * G;
+            const float d = cut ? g : c;
+            G = R + d * v;
+            const int64_t f = u * M + r;
+            if (WINDOW && f < a.skip) return;
+            int64_t slot = a.start + (f - a.skip);
+            slot = slot >= cap ? slot - cap : slot;
+            a.rewards[slot] = R;
+            a.discounts[slot] = d;
+        };
+        // the three loads of step u, none of them conditional and nothing computed from them here
+        auto load = [&](int64_t u, float &rew, float &v, unsigned &fired) {
+            rew = rw[u * M];
+            v = vv[u * M];
+            fired = 0;
+            if constexpr (DONE) fired = dn[u * a.envs];
+        };
+        int64_t t = a.steps;                                           // steps [0, t) are still to fold, t - 1 next
+        for (int k = (int)(a.steps % kLambdaAhead); k > 0; --k) {
+            --t;
+            float rew, v;
+            unsigned fired;
+            load(t, rew, v, fired);
+            fold(t, rew, v, fired);
+        }
+        if (t == 0) continue;
+        // two groups in registers, A and B: while one folds, the loads of the group before it are in flight into the other
+        // (at the front of the chain: the same group again, unused).  No group is ever copied: a copy would wait for it.
+        struct Group { float rew[kLambdaAhead], v[kLambdaAhead]; unsigned fired[kLambdaAhead]; } A, B;
+        auto load_group = [&](int64_t end, Group &grp) {               // steps [end - kLambdaAhead, end), last step first
+#pragma unroll
+            for (int q = 0; q < kLambdaAhead; ++q) load(end - 1 - q, grp.rew[q], grp.v[q], grp.fired[q]);
+            __builtin_amdgcn_sched_barrier(0);                          // (the loads stay ahead of the fold behind them)
+        };
+        auto fold_group = [&](int64_t end, const Group &grp) {
+#pragma unroll
+            for (int q = 0; q < kLambdaAhead; ++q) fold(end - 1 - q, grp.rew[q], grp.v[q], grp.fired[q]);
+            __builtin_amdgcn_sched_barrier(0);
+        };
+        load_group(t, A);
+        while (true) {
+            load_group(t > kLambdaAhead ? t - kLambdaAhead : t, B);
+            fold_group(t, A);
+            t -= kLambdaAhead;
+            if (t == 0) break;
+            load_group(t > kLambdaAhead ? t - kLambdaAhead : t, A);
+            fold_group(t, B);
+            t -= kLambdaAhead;
+            if (t == 0) break;
+        }
+    }
+}
+
 }  // namespace
 
 // the maximum of the ring's priorities as they stand (1.0 for an empty ring) into d.parts[kReplayMaxParts]
@@ -578,6 +668,33 @@ hipError_t launch_replay_add_nstep(const ReplayDevice &d, const ReplayRingView &
     int64_t blocks = (a.n - a.skip + kSW - 1) / kSW;
     if (blocks > 65536) blocks = 65536;
     hipLaunchKernelGGL(replay_write_nstep_kernel, dim3((unsigned)blocks), dim3(kSW), 0, st, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_replay_add_lambda(const ReplayDevice &d, const ReplayRingView &ring, float *discounts, int64_t steps,
+                                    int64_t envs, int64_t n_uav, const float *obs_in, const float *obs,
+                                    const int32_t *actions, const float *reward, const uint8_t *done, const float *start_obs,
+                                    const float *values, float lambda, float gamma, hipStream_t st)
+{
+    const int64_t cap = ring.capacity, agents = envs * n_uav, n = steps * agents;
+    // states, actions, next states and priorities (and the raw rewards, which the scan overwrites) as the one-step add
+    hipError_t e = launch_replay_add(d, ring, n, agents, obs_in, nullptr, obs, actions, reward, st, done, start_obs, n_uav);
+    if (e != hipSuccess) return e;
+    LambdaArgs a;
+    a.rewards = ring.rewards; a.discounts = discounts; a.reward = reward; a.values = values; a.done = done;
+    a.capacity = cap; a.agents = agents; a.envs = envs; a.n_uav = n_uav; a.steps = steps;
+    a.skip = n > cap ? n - cap : 0;
+    a.start = (ring.pos + a.skip) % cap;
+    a.g = gamma;
+    a.gl = gamma * lambda;
+    a.c = gamma * (1.0f - lambda);
+    int64_t blocks = (agents + kLambdaW - 1) / kLambdaW;
+    if (blocks > 65536) blocks = 65536;
+    const dim3 grid((unsigned)blocks), blk(kLambdaW);
+    if (done && a.skip) hipLaunchKernelGGL((replay_lambda_scan_kernel<true, true>), grid, blk, 0, st, a);
+    else if (done) hipLaunchKernelGGL((replay_lambda_scan_kernel<true, false>), grid, blk, 0, st, a);
+    else if (a.skip) hipLaunchKernelGGL((replay_lambda_scan_kernel<false, true>), grid, blk, 0, st, a);
+    else hipLaunchKernelGGL((replay_lambda_scan_kernel<false, false>), grid, blk, 0, st, a);
     return hipGetLastError();
 }
 

@@ -179,6 +179,7 @@ SIGNATURES = {
                                            + [C.c_void_p] * 8),
     "uavtrack_learner_grad_discounted": (C.c_int, [C.c_void_p, C.c_int64] + [C.c_void_p] * 4 + [C.c_int64]
                                          + [C.c_void_p] * 6),
+    "uavtrack_learner_values": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
     "uavtrack_learner_apply": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
     "uavtrack_learner_write_priorities": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64] + [C.c_void_p] * 3),
     "uavtrack_learner_check": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64), C.c_void_p]),
@@ -209,6 +210,8 @@ SIGNATURES = {
                                              + [C.c_void_p] * 7),
     "uavtrack_replay_add_rollout_nstep": (C.c_int, [C.c_void_p, C.POINTER(ReplayRing), C.c_void_p, C.c_int64, C.c_int64,
                                                     C.c_int64] + [C.c_void_p] * 6 + [C.c_int32, C.c_double, C.c_void_p]),
+    "uavtrack_replay_add_rollout_lambda": (C.c_int, [C.c_void_p, C.POINTER(ReplayRing), C.c_void_p, C.c_int64, C.c_int64,
+                                                     C.c_int64] + [C.c_void_p] * 7 + [C.c_double, C.c_double, C.c_void_p]),
     "uavtrack_replay_sample": (C.c_int, [C.c_void_p, C.POINTER(ReplayRing), C.c_int64, C.c_double, C.c_double,
                                          C.c_void_p, C.c_void_p, C.c_void_p]),
     "uavtrack_replay_sample_annealed": (C.c_int, [C.c_void_p, C.POINTER(ReplayRing), C.c_int64, C.c_double, C.c_double,

@@ -40,6 +40,10 @@ store (gamma^m of its n-step window), gathered in the kernel beside the reward (
 _grad_discounted).  Everything behind the target is unchanged.  Without discounts every call is bit for bit what it
 was, and a store of float32(gamma) gives the same bits; d_i = 0 means "do not bootstrap".  A discount that is NaN,
 negative or above 1 refuses the update on the device like a bad action.
+
+The critic alone (values(states), uavtrack_learner_values): V(s) of any number of rows with the parameters as they stand
+when the launch runs, bit for bit the V(s) an update forms.  A lambda ring (ring.with_lambda(lam, gamma)) takes it as
+add_rollout(..., critic=learner) to fold a rollout's rewards with its values into lambda-returns.
 """
 from __future__ import annotations
 
@@ -181,6 +185,28 @@ class DeviceActorCritic(Handle):
         [0, action_dim), an index outside the ring, or an importance weight that is NaN, infinite or negative -- what a
         refused ring draw hands out), which then changed nothing."""
         self._check()
+
+    # ---- the critic alone
+    def values(self, states: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """V(s) of states [..., 12] (float32, contiguous, on the learner's device) with the critic's parameters as they
+        stand when the launch runs (uavtrack_learner_values): a float32 tensor of the leading shape, bit for bit the V(s)
+        an update with the same parameters forms.  `out` (float32, contiguous, that many elements, same device) is
+        written in place and returned.  No synchronisation, no limit from max_batch, no change to the learner."""
+        D = _lib.OBS_DIM
+        if states.dim() < 1 or states.shape[-1] != D or states.dtype != torch.float32 or not states.is_contiguous() \
+                or states.device != self.device:
+            raise ValueError(f"values: states must be a contiguous float32 tensor [..., {D}] on {self.device}, got "
+                             f"{tuple(states.shape)} {states.dtype} on {states.device}")
+        lead = tuple(states.shape[:-1])
+        n = states.numel() // D
+        if out is None:
+            out = torch.empty(lead, dtype=torch.float32, device=self.device)
+        elif out.numel() != n or out.dtype != torch.float32 or not out.is_contiguous() or out.device != self.device:
+            raise ValueError(f"values: out must be a contiguous float32 tensor of {n} elements on {self.device}")
+        if n:
+            _lib.check(self._lib.uavtrack_learner_values(self._h, n, _ptr(states), _ptr(out), self._stream()),
+                       "uavtrack_learner_values")
+        return out
 
     # ---- the update
     @staticmethod

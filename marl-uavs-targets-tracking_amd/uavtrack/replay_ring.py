@@ -23,6 +23,14 @@ then folds each transition's next n_step rewards into its reward, takes the next
 leaves gamma^m in the slot's discount (uavtrack_replay_add_rollout_nstep; the horizon m never crosses an episode end and
 is cut at the rollout's last step).  DeviceActorCritic.update_from and its relatives pick the store up, so the target of
 a row is r + discount * V(s').  Without with_nstep a ring is exactly what it was.
+
+TD(lambda) targets.  ring.with_lambda(lam, gamma) makes either ring a lambda ring instead: add_rollout(obs_in, out,
+critic=learner) (or values=V) walks each agent's chain backwards and stores every transition as the one-step transition
+with reward R_t = r_t + gamma lam G_{t+1} and discount gamma (1 - lam) (uavtrack_replay_add_rollout_lambda), so the same
+target r + discount * V(s') is the lambda-return: its tail evaluated by the critic at add time, its first bootstrap term
+by the critic at update time.  Windows never cross an episode end and are cut at the rollout's last step, where the
+transition is the plain one-step one; lam = 0 is with_nstep(1, gamma) to the byte.  Slots keep the tail they were added
+with.
 """
 from __future__ import annotations
 
@@ -47,6 +55,8 @@ class ReplayRing(Handle):
 
     n_step: int = 1
     gamma: Optional[float] = None
+    lam: Optional[float] = None                 # with_lambda: the ring stores lambda-returns
+    _values: Optional[torch.Tensor] = None      # add_rollout(critic=...)'s buffer, kept and only grown
 
     def __init__(self, capacity: int, device, seed: int = 0, max_batch: int = 65536, obs_dim: int = _lib.OBS_DIM):
         if obs_dim != _lib.OBS_DIM:
@@ -72,6 +82,8 @@ class ReplayRing(Handle):
         n_step = int(n_step)
         if not 1 <= n_step <= _lib.REPLAY_MAX_NSTEP:
             raise ValueError(f"n_step must be in [1, {_lib.REPLAY_MAX_NSTEP}], got {n_step}")
+        if self.lam is not None and n_step > 1:
+            raise ValueError(f"with_nstep({n_step}) on a lambda ring: a ring stores n-step returns or lambda-returns")
         if gamma is None:
             if n_step != 1:
                 raise ValueError(f"n_step = {n_step} needs gamma (the discount the n-step return is folded with)")
@@ -82,6 +94,44 @@ class ReplayRing(Handle):
         self.n_step, self.gamma = n_step, gamma
         self.discounts = torch.full((self.capacity,), gamma, dtype=torch.float32, device=self.device)
         return self
+
+    def with_lambda(self, lam: float, gamma: float) -> "ReplayRing":
+        """Makes this ring a lambda ring and returns it: ReplayRing(capacity, device).with_lambda(0.9, gamma=0.95).  The
+        ring then owns `discounts` [capacity] (every slot float32(gamma) to begin with, as with_nstep) and add_rollout
+        stores lambda-returns as (reward, discount) pairs, from `values=` or a `critic=`.  n_step stays 1; a ring is an
+        n-step ring (n_step > 1) or a lambda ring, not both."""
+        lam, gamma = float(lam), float(gamma)
+        if not 0.0 <= lam <= 1.0:
+            raise ValueError(f"lam must be in [0, 1], got {lam}")
+        if not 0.0 <= gamma <= 1.0:
+            raise ValueError(f"gamma must be in [0, 1], got {gamma}")
+        if self.n_step > 1:
+            raise ValueError(f"with_lambda on a ring with n_step = {self.n_step}: a ring stores n-step returns or "
+                             f"lambda-returns")
+        self.lam, self.gamma = lam, gamma
+        self.discounts = torch.full((self.capacity,), gamma, dtype=torch.float32, device=self.device)
+        return self
+
+    def _rollout_values(self, obs: torch.Tensor, critic, values: Optional[torch.Tensor]) -> torch.Tensor:
+        """The lambda add's values [T*B*N]: the caller's, or the critic's over obs into the ring's own buffer."""
+        n = obs.numel() // _lib.OBS_DIM
+        if (critic is None) == (values is None):
+            raise ValueError("add_rollout: a lambda ring needs exactly one of critic= and values=")
+        if values is not None:
+            if values.numel() != n or values.dtype != torch.float32 or not values.is_contiguous() \
+                    or values.device != self.device:
+                raise ValueError(f"add_rollout: values must be a contiguous float32 tensor of {n} elements (one per "
+                                 f"row of obs) on {self.device}")
+            return values
+        if self._values is None or self._values.numel() < n:
+            self._values = torch.empty(n, dtype=torch.float32, device=self.device)
+        buf = self._values[:n]
+        if isinstance(critic, torch.nn.Module):
+            with torch.no_grad():
+                buf.copy_(critic(obs.reshape(-1, _lib.OBS_DIM)).reshape(n))
+        else:
+            critic.values(obs, out=buf)
+        return buf
 
     def _ring(self) -> _lib.ReplayRing:
         s = self.store
@@ -131,13 +181,20 @@ class ReplayRing(Handle):
             self.discounts[:k - head] = d[n - k + head:]
         self._advance(n)
 
-    def add_rollout(self, obs_in: torch.Tensor, out: Dict[str, torch.Tensor]) -> None:
+    def add_rollout(self, obs_in: torch.Tensor, out: Dict[str, torch.Tensor], *, critic=None,
+                    values: Optional[torch.Tensor] = None) -> None:
         """add(transitions_from_rollout(obs_in, out)) in one library call: obs_in [B,N,12] is what the policy saw
         first, out = {obs [T,B,N,12], actions [T,B,N] int32, reward [T,B,N]} (BatchedRollout.run_fused's outputs).  When
         `out` carries start_obs (a rollout across episode ends, with its done [T,B] uint8), the state behind a fired done
         is the fresh state's observation (uavtrack_replay_add_rollout_episodes).  A ring with discounts (with_nstep)
         stores n_step-step returns and their discounts instead (uavtrack_replay_add_rollout_nstep), with or without
-        done / start_obs as above; obs must then be [T,B,N,12]."""
+        done / start_obs as above; obs must then be [T,B,N,12].  A lambda ring (with_lambda) stores lambda-returns
+        (uavtrack_replay_add_rollout_lambda) and needs exactly one of `values` (float32, contiguous, T*B*N elements:
+        V(obs[t][b][i])) and `critic` (an object with .values(states, out=), a DeviceActorCritic, or a torch module such
+        as ValueMLP, called under no_grad on obs.reshape(-1, 12)); the critic's values go into a buffer the ring keeps
+        and only grows.  Any other ring given either raises."""
+        if self.lam is None and (critic is not None or values is not None):
+            raise ValueError("add_rollout: critic= and values= are for a lambda ring (ring.with_lambda(lam, gamma))")
         obs, act, rew = out["obs"], out["actions"], out["reward"]
         so = out.get("start_obs")
         T = obs.shape[0]
@@ -163,6 +220,16 @@ class ReplayRing(Handle):
                     raise ValueError("add_rollout: every input must be contiguous on the ring's device")
         else:
             done = None
+        if self.lam is not None:
+            if obs.dim() != 4:
+                raise ValueError("add_rollout: a lambda ring needs obs as [T,B,N,12]")
+            v = self._rollout_values(obs, critic, values)
+            _lib.check(self._lib.uavtrack_replay_add_rollout_lambda(
+                self._h, C.byref(ring), _ptr(self.discounts), T, int(obs.shape[1]), int(obs.shape[2]), _ptr(obs_in),
+                _ptr(obs), _ptr(act), _ptr(rew), _ptr(done), _ptr(so), _ptr(v), self.lam, self.gamma, self._stream()),
+                "uavtrack_replay_add_rollout_lambda")
+            self._advance(T * M)
+            return
         if self.discounts is not None:
             if obs.dim() != 4:
                 raise ValueError("add_rollout: an n-step ring needs obs as [T,B,N,12]")
