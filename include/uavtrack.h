@@ -849,13 +849,21 @@ typedef struct uavtrack_replay_ring {
 int uavtrack_replay_create(const uavtrack_replay_config *cfg, uavtrack_replay **out);
 int uavtrack_replay_destroy(uavtrack_replay *replay);
 
-/* PrioritizedReplayBuffer.add (train.py:87-96) for n transitions: states / next_states [n][12], actions [n] int32,
- * rewards [n] (DEVICE).  Only the last min(n, capacity) are written, from slot (pos + max(0, n - capacity)) % capacity
- * on, wrapping; each gets the maximum of the whole priorities array as it stood before the call (1.0 when count == 0),
- * taken on the device.  Stream-ordered, no synchronisation, no allocation.  Returns an error, enqueuing nothing, for a
- * null pointer, n < 1, a ring outside the limits above, or a row array not 16-byte aligned.  ring->priorities may be
- * NULL (a uniform ring): the call then reads and writes no priority and writes the four stores exactly as otherwise;
- * the same holds for the two rollout forms below. */
+/* ---- the five adds: what they share ----
+ * An add writes n transitions into the caller's ring, in order f = 0 .. n - 1.  Only the last min(n, capacity) are
+ * written, from slot (pos + max(0, n - capacity)) % capacity on, wrapping; on a ring with priorities each gets the
+ * maximum of the whole priorities array as it stood before the call (1.0 when count == 0), taken on the device.
+ * ring->priorities may be NULL (a uniform ring): the call then reads and writes no priority and writes the stores
+ * exactly as otherwise.  The ring struct is the caller's and is not advanced: pos and count move on the caller's side.
+ * Every array is DEVICE memory.  Stream-ordered, no synchronisation, no allocation, capturable.
+ * Errors.  Each add returns an error, enqueuing nothing, for the first of these that applies: a null handle; a ring
+ * that is null, lacks a store, has its states or next_states off a 16-byte boundary, or is outside the limits above; a
+ * null pointer among those the form requires; exactly one of done and start_obs where both are optional; a source row
+ * array ([..][12]) off a 16-byte boundary; n_step, then lambda, then gamma out of range where the form has them; a size
+ * below 1; sizes whose product overflows.  Each entry point below states what it adds to this.
+ *
+ * uavtrack_replay_add: PrioritizedReplayBuffer.add (train.py:87-96) for n transitions given flat: states / next_states
+ * [n][12], actions [n] int32, rewards [n], all required. */
 int uavtrack_replay_add(uavtrack_replay *replay, const uavtrack_replay_ring *ring, int64_t n, const float *states,
                         const int32_t *actions, const float *rewards, const float *next_states, void *stream);
 
@@ -863,7 +871,7 @@ int uavtrack_replay_add(uavtrack_replay *replay, const uavtrack_replay_ring *rin
  * the policy saw first, obs [steps][agents][12], actions and reward [steps][agents] (agents = n_envs * n_uav).
  * Transition f = t * agents + i (t < steps) is (state = t ? obs[t - 1][i] : obs_in[i], actions[t][i], reward[t][i],
  * next_state = obs[t][i]), the [t][b][i] order of uavtrack.transitions_from_rollout; n = steps * agents.  Each obs row
- * is read once.  Errors as uavtrack_replay_add. */
+ * is read once.  All four arrays are required. */
 int uavtrack_replay_add_rollout(uavtrack_replay *replay, const uavtrack_replay_ring *ring, int64_t steps, int64_t agents,
                                 const float *obs_in, const float *obs, const int32_t *actions, const float *reward,
                                 void *stream);
@@ -872,9 +880,9 @@ int uavtrack_replay_add_rollout(uavtrack_replay *replay, const uavtrack_replay_r
  * agents per step, done [steps][envs] (uint8) and start_obs [steps][envs][n_uav][12] as that launch wrote them.  The
  * state of transition (t, b, i) is obs_in[b][i] at t == 0, start_obs[t - 1][b][i] where done[t - 1][b] != 0 (the
  * episode of step t - 1 ended there: its last observation is not the state step t acted on), else obs[t - 1][b][i].
- * Everything else -- order, the window when n exceeds the capacity, the wrap, priorities, errors -- is
- * uavtrack_replay_add_rollout's; each obs row is still read once, a start_obs row only where done fired.  With done all
- * zero the ring ends byte-identical to uavtrack_replay_add_rollout's (start_obs is then never read). */
+ * done and start_obs are required here.  Everything else is uavtrack_replay_add_rollout's; each obs row is still read
+ * once, a start_obs row only where done fired.  With done all zero the ring ends byte-identical to
+ * uavtrack_replay_add_rollout's (start_obs is then never read). */
 int uavtrack_replay_add_rollout_episodes(uavtrack_replay *replay, const uavtrack_replay_ring *ring, int64_t steps,
                                          int64_t envs, int64_t n_uav, const float *obs_in, const float *obs,
                                          const int32_t *actions, const float *reward, const uint8_t *done,
@@ -896,17 +904,12 @@ int uavtrack_replay_add_rollout_episodes(uavtrack_replay *replay, const uavtrack
  *     start_obs[t - 1] behind a fired done, obs[t - 1] otherwise; action = actions[t][b][i]; reward = R;
  *     next_state = obs[t + m - 1][b][i] (at an episode end that episode's last observation, which is what the one-step
  *     form bootstraps from); discount = d, written to discounts [capacity], a caller-owned DEVICE fp32 array passed
- *     beside the ring (the ring struct keeps its size).  The slot is that of the other adds: only the last
- *     min(T * agents, capacity) transitions are written (their windows still look ahead into rows that are themselves
- *     not written), from slot (pos + max(0, T * agents - capacity)) % capacity on, wrapping, the priorities at the
- *     device-side maximum.
+ *     beside the ring (the ring struct keeps its size).  Slot, window, wrap and priority are the shared ones; the
+ *     windows of the written transitions still look ahead into rows that are themselves not written.
  * With n == 1: m == 1 everywhere, R is the reward's bits and d is g's bits; the four stores and the priorities end
  * byte-identical to uavtrack_replay_add_rollout_episodes, and with done == NULL to uavtrack_replay_add_rollout.
- * done and start_obs are either both given or both NULL.  One thread handles one transition: it reads at most n rewards
- * and n - 1 done bytes, one next-state row and its state row.  Stream-ordered, no synchronisation, no allocation,
- * capturable.  Returns an error, enqueuing nothing, for a null required pointer, n_step outside
- * [1, UAVTRACK_REPLAY_MAX_NSTEP], gamma not finite or outside [0, 1], exactly one of done and start_obs given, a ring
- * outside its limits, or a row array that is not 16-byte aligned. */
+ * done and start_obs are either both given or both NULL; discounts and the four rollout arrays are required.  One thread
+ * handles one transition: it reads at most n rewards and n - 1 done bytes, one next-state row and its state row. */
 #define UAVTRACK_REPLAY_MAX_NSTEP 64
 int uavtrack_replay_add_rollout_nstep(uavtrack_replay *replay, const uavtrack_replay_ring *ring, float *discounts,
                                       int64_t steps, int64_t envs, int64_t n_uav, const float *obs_in, const float *obs,
@@ -940,8 +943,8 @@ int uavtrack_replay_add_rollout_nstep(uavtrack_replay *replay, const uavtrack_re
  * Monte-Carlo up to the cut, the bootstrap at the cut.  Non-finite values propagate into the stored rewards as non-finite
  * rewards do; the add does not inspect them.
  * The one-step write runs first; a scan kernel follows it, one thread per agent chain, the loads of eight steps issued
- * ahead of the carried G.  The horizon is unbounded.  Stream-ordered, no synchronisation, no allocation, capturable.
- * Errors: those of uavtrack_replay_add_rollout_nstep, with values required and lambda finite and in [0, 1]. */
+ * ahead of the carried G.  The horizon is unbounded.  Required and optional arrays are those of
+ * uavtrack_replay_add_rollout_nstep, with values required as well. */
 int uavtrack_replay_add_rollout_lambda(uavtrack_replay *replay, const uavtrack_replay_ring *ring, float *discounts,
                                        int64_t steps, int64_t envs, int64_t n_uav, const float *obs_in, const float *obs,
                                        const int32_t *actions, const float *reward, const uint8_t *done,

@@ -479,27 +479,29 @@ hipError_t launch_replay_sample(const ReplayDevice &d, const float *priorities, 
 // Shares the call counter with launch_replay_sample.
 hipError_t launch_replay_sample_uniform(const ReplayDevice &d, int64_t count, int64_t k, int64_t *indices,
                                         hipStream_t stream);
-// n transitions: flat (obs_in == nullptr: states / next_states [n][12], actions / rewards [n]) or one rollout
-// (obs_in [agents][12], obs [n / agents][agents][12], actions / rewards [n / agents][agents]); only the last
-// min(n, capacity) land in the ring, from ring.pos on.  ring.priorities == nullptr (a uniform ring): the stores alone
-hipError_t launch_replay_add(const ReplayDevice &d, const ReplayRingView &ring, int64_t n, int64_t agents,
-                             const float *obs_in, const float *states, const float *next_states, const int32_t *actions,
-                             const float *rewards, hipStream_t stream,
-                             // (the rollout crossed episode ends: done [n / agents][agents / n_uav], start_obs [n][12])
-                             const uint8_t *done = nullptr, const float *start_obs = nullptr, int64_t n_uav = 1);
-// uavtrack_replay_add_rollout_nstep: one rollout of steps x envs x n_uav transitions with n_step-step returns; done and
-// start_obs both given or both nullptr; discounts [capacity] receives gamma^m per written slot
-hipError_t launch_replay_add_nstep(const ReplayDevice &d, const ReplayRingView &ring, float *discounts, int64_t steps,
-                                   int64_t envs, int64_t n_uav, const float *obs_in, const float *obs,
-                                   const int32_t *actions, const float *reward, const uint8_t *done, const float *start_obs,
-                                   int n_step, float gamma, hipStream_t stream);
-// uavtrack_replay_add_rollout_lambda: launch_replay_add's write (episodes form with done / start_obs, plain form without),
-// then the backward scan over each agent's chain that overwrites the written slots' rewards with R_t and leaves d_t in
-// discounts [capacity]; values [steps][envs][n_uav]
-hipError_t launch_replay_add_lambda(const ReplayDevice &d, const ReplayRingView &ring, float *discounts, int64_t steps,
-                                    int64_t envs, int64_t n_uav, const float *obs_in, const float *obs,
-                                    const int32_t *actions, const float *reward, const uint8_t *done, const float *start_obs,
-                                    const float *values, float lambda, float gamma, hipStream_t stream);
+// One ring add of steps x envs x n_uav transitions, of which the last min(n, capacity) land in the ring from ring.pos on;
+// ring.priorities == nullptr (a uniform ring): the stores alone.
+//   Flat     states / next [n][12], actions / rewards [n], with steps = n and envs = n_uav = 1;
+//   Rollout  obs_in [agents][12], next = obs [steps][agents][12], actions / rewards [steps][agents]; with done [steps][envs]
+//            and start_obs (of obs's shape) the rollout crossed episode ends, without them envs * n_uav is just `agents`;
+//   Nstep    Rollout's source folded into n_step-step returns with gamma; discounts [capacity] receives gamma^m per slot;
+//   Lambda   Rollout's write, then the backward scan over each agent's chain that overwrites the written slots' rewards
+//            with R_t and leaves d_t in discounts; values [steps][agents].
+enum class ReplayForm { Flat, Rollout, Nstep, Lambda };
+struct ReplayAdd {
+    ReplayForm form;
+    ReplayRingView ring;
+    int64_t steps, envs, n_uav;
+    const float *obs_in, *states, *next, *rewards;
+    const int32_t *actions;
+    const uint8_t *done;            // both given or both nullptr
+    const float *start_obs;
+    float *discounts;
+    const float *values;
+    int n_step;                     // n-step form: in [1, UAVTRACK_REPLAY_MAX_NSTEP]
+    float lambda, gamma;
+};
+hipError_t launch_replay_add(const ReplayDevice &d, const ReplayAdd &q, hipStream_t stream);
 
 // episode_kernel.hip -- per-episode results (uavtrack_episode_stats_*).  The open episodes are struct-of-arrays over the
 // environments; a closing step's log slot comes from a scan over the done matrix in groups of kEpisodeGroup environments

@@ -28,17 +28,18 @@
 // replay_begin_kernel and replay_uniform_kernel: one thread per draw, O(k) whatever the ring holds.  It reads nothing
 // of the ring, so it has no refusal.
 //
-// Adding is two reductions (the maximum of the whole priorities array, train.py:87-88) and one write kernel: each thread
-// owns one source transition f, reads obs[f] once and writes it as the next state of f and the state of f + agents.
-// The episodes form (a rollout that crossed episode ends, uavtrack_replay_add_rollout_episodes) writes the fresh state's
-// observation, start_obs[f], as the state of f + agents instead wherever the done flag of f's environment-step fired.
-// A ring without priorities (ring.priorities == nullptr, a uniform ring) skips the reductions and the priority write.
-// The n-step form (uavtrack_replay_add_rollout_nstep) has a write kernel of its own, replay_write_nstep_kernel: one thread
-// per transition, which folds up to n rewards of its agent into the stored reward, takes the next state from the end of
-// that window and leaves the window's discount in a fifth per-slot store.
-// The lambda form (uavtrack_replay_add_rollout_lambda) is the one-step write above followed by replay_lambda_scan_kernel:
-// one thread per agent chain walks the rollout backwards, carries the lambda-return G and overwrites the written slots'
-// rewards with R_t, leaving d_t in the discount store.
+// Adding (launch_replay_add, one ReplayAdd request) is two reductions (the maximum of the whole priorities array,
+// train.py:87-88; skipped for a ring without priorities, a uniform ring) and one write kernel over the request's ring
+// window, the last min(n, capacity) transitions from ring.pos on:
+//   replay_write_kernel        flat and rollout forms: each thread owns one source transition f, reads obs[f] once and
+//                              writes it as the next state of f and the state of f + agents; <true> (done given) writes
+//                              start_obs[f] as that state instead wherever the done flag of f's environment-step fired;
+//   replay_write_nstep_kernel  the n-step form: a thread folds up to n rewards of its agent into the stored reward, takes
+//                              the next state from the end of that window and leaves the window's discount in a fifth
+//                              per-slot store;
+//   replay_lambda_scan_kernel  the lambda form, behind replay_write_kernel and over the same window: one thread per agent
+//                              chain walks the rollout backwards, carries the lambda-return G and overwrites the written
+//                              slots' rewards with R_t, leaving d_t in the discount store.
 
 #include "internal.h"
 #include "philox.h"
@@ -370,17 +371,45 @@ __global__ void replay_top_kernel(float *parts, int groups, int empty)
     parts[kReplayMaxParts] = empty ? 1.0f : m;
 }
 
+// The slots an add of n transitions writes: transitions [skip, n) into start, start + 1, ... (mod cap)
+struct RingWindow {
+    int64_t n, skip, start, cap;
+};
+
+RingWindow ring_window(const ReplayRingView &ring, int64_t n)
+{
+    RingWindow w;
+    w.n = n; w.cap = ring.capacity;
+    w.skip = n > w.cap ? n - w.cap : 0;
+    w.start = (ring.pos + w.skip) % w.cap;
+    return w;
+}
+
+// the slot of transition f in [skip, n): f - skip < cap and start < cap, so one subtraction wraps
+__device__ __forceinline__ int64_t window_slot(const RingWindow &w, int64_t f)
+{
+    const int64_t slot = w.start + (f - w.skip);
+    return slot >= w.cap ? slot - w.cap : slot;
+}
+
+// What every add kernel is given beside the ring: the source and the window.  n = steps * agents, agents = envs * n_uav.
+// The order matters only to how the kernel arguments are fetched: what the lambda scan reads (skip .. done) is the tail,
+// and its own arguments follow, so they stay the one span they were when the scan had a struct of its own.
+struct AddSource {
+    const float *obs_in;                       // rollout forms: [agents][12]; nullptr: the flat form
+    const float *states, *next;                // flat: states [n][12]; flat: next states, rollout forms: obs [n][12]
+    const int32_t *actions;                    // [n]
+    const float *start_obs;                    // [n][12], read only where done fired
+    const float *top;                          // the priority new transitions enter at
+    RingWindow w;
+    int64_t agents, envs, n_uav, steps;
+    const float *rewards;                      // [n]
+    const uint8_t *done;                       // nullable [steps][envs]
+};
+
 struct AddArgs {
     ReplayRingView ring;
-    const float *obs_in;                       // rollout form: [agents][12]; nullptr: flat form
-    const float *src_states, *src_next;        // flat: states [n][12]; both forms: next states [n][12]
-    const int32_t *src_actions;
-    const float *src_rewards;
-    const float *top;
-    int64_t n, agents, skip, start;
-    const uint8_t *done;                       // episodes form: [steps][envs], with n_uav agents per environment
-    const float *start_obs;                    //                [n][12], read only where done fired
-    int64_t n_uav;
+    AddSource s;
 };
 
 __device__ __forceinline__ void copy_row(float *dst, const float *src)
@@ -394,31 +423,28 @@ __device__ __forceinline__ void copy_row(float *dst, const float *src)
 template <bool EPISODES>
 __global__ void __launch_bounds__(kSW) replay_write_kernel(AddArgs a)
 {
+    const AddSource &s = a.s;
     // what transition g + agents acted on: obs[g], or the fresh state's observation where g's episode ended at g
     auto state_after = [&](int64_t g, const float *obs_row) {
-        if (EPISODES && a.done[g / a.n_uav]) return a.start_obs + g * 12;
+        if (EPISODES && s.done[g / s.n_uav]) return s.start_obs + g * 12;
         return obs_row;
     };
-    const int64_t cap = a.ring.capacity;
-    const float top = a.ring.priorities ? *a.top : 0.0f;
-    for (int64_t f = a.skip + (int64_t)blockIdx.x * kSW + threadIdx.x; f < a.n; f += (int64_t)gridDim.x * kSW) {
-        int64_t slot = a.start + (f - a.skip);
-        if (slot >= cap) slot -= cap;
-        const float *row = a.src_next + f * 12;
+    const float top = a.ring.priorities ? *s.top : 0.0f;
+    for (int64_t f = s.w.skip + (int64_t)blockIdx.x * kSW + threadIdx.x; f < s.w.n; f += (int64_t)gridDim.x * kSW) {
+        const int64_t slot = window_slot(s.w, f);
+        const float *row = s.next + f * 12;
         copy_row(a.ring.next_states + slot * 12, row);
-        if (a.obs_in) {
-            const int64_t M = a.agents;
-            if (f + M < a.n) {                   // obs[f] is also the state of transition f + M
-                const int64_t s2 = (a.start + (f + M - a.skip)) % cap;
-                copy_row(a.ring.states + s2 * 12, state_after(f, row));
-            }
-            if (f < M) copy_row(a.ring.states + slot * 12, a.obs_in + f * 12);
-            else if (f - M < a.skip) copy_row(a.ring.states + slot * 12, state_after(f - M, a.src_next + (f - M) * 12));
+        if (s.obs_in) {
+            const int64_t M = s.agents;
+            // obs[f] is also the state of transition f + M (f + M < n: in the window, one subtraction wraps there too)
+            if (f + M < s.w.n) copy_row(a.ring.states + window_slot(s.w, f + M) * 12, state_after(f, row));
+            if (f < M) copy_row(a.ring.states + slot * 12, s.obs_in + f * 12);
+            else if (f - M < s.w.skip) copy_row(a.ring.states + slot * 12, state_after(f - M, s.next + (f - M) * 12));
         } else {
-            copy_row(a.ring.states + slot * 12, a.src_states + f * 12);
+            copy_row(a.ring.states + slot * 12, s.states + f * 12);
         }
-        a.ring.actions[slot] = a.src_actions[f];
-        a.ring.rewards[slot] = a.src_rewards[f];
+        a.ring.actions[slot] = s.actions[f];
+        a.ring.rewards[slot] = s.rewards[f];
         if (a.ring.priorities) a.ring.priorities[slot] = top;
     }
 }
@@ -426,14 +452,8 @@ __global__ void __launch_bounds__(kSW) replay_write_kernel(AddArgs a)
 // ---- the n-step add (uavtrack_replay_add_rollout_nstep; include/uavtrack.h has the definitions)
 
 struct NstepArgs {
-    ReplayRingView ring;
+    AddArgs a;                                 // next: obs [steps][agents][12], rewards: reward [steps][agents]
     float *discounts;                          // [capacity]
-    const float *obs_in, *obs, *reward;        // [agents][12], [steps][agents][12], [steps][agents]
-    const int32_t *actions;
-    const uint8_t *done;                       // nullable [steps][envs]
-    const float *start_obs;                    // [steps][agents][12], read only where done fired
-    const float *top;
-    int64_t n, agents, envs, n_uav, steps, skip, start;
     int n_step;
     float g;
 };
@@ -442,18 +462,19 @@ struct NstepArgs {
 // reads of reward[t + k] are one line, and done[t + k][b] is shared by an environment's lanes.  A thread reads at most
 // n_step - 1 done bytes and n_step rewards, its state row and the one obs row at the end of its window, and writes one
 // transition.
-__global__ void __launch_bounds__(kSW) replay_write_nstep_kernel(NstepArgs a)
+__global__ void __launch_bounds__(kSW) replay_write_nstep_kernel(NstepArgs q)
 {
 #pragma clang fp contract(off)
-    const int64_t cap = a.ring.capacity, M = a.agents;
-    const float top = a.ring.priorities ? *a.top : 0.0f;
-    for (int64_t f = a.skip + (int64_t)blockIdx.x * kSW + threadIdx.x; f < a.n; f += (int64_t)gridDim.x * kSW) {
-        int64_t slot = a.start + (f - a.skip);
-        if (slot >= cap) slot -= cap;
+    const ReplayRingView &ring = q.a.ring;
+    const AddSource &a = q.a.s;
+    const int64_t M = a.agents;
+    const float top = ring.priorities ? *a.top : 0.0f;
+    for (int64_t f = a.w.skip + (int64_t)blockIdx.x * kSW + threadIdx.x; f < a.w.n; f += (int64_t)gridDim.x * kSW) {
+        const int64_t slot = window_slot(a.w, f);
         const int64_t t = f / M, r = f - t * M, b = r / a.n_uav;
         // the horizon: the smallest m >= 1 with m == n_step, t + m == steps or done[t + m - 1][b]
         const int64_t left = a.steps - t;
-        const int lim = left < (int64_t)a.n_step ? (int)left : a.n_step;
+        const int lim = left < (int64_t)q.n_step ? (int)left : q.n_step;
         int m = 1;
         if (a.done) {
             const uint8_t *dn = a.done + t * a.envs + b;               // dn[k * envs] = done[t + k][b]
@@ -462,33 +483,32 @@ __global__ void __launch_bounds__(kSW) replay_write_nstep_kernel(NstepArgs a)
             m = lim;
         }
         // the return, Horner from the far end, and the discount, m - 1 products
-        const float *rw = a.reward + f;                                // rw[k * M] = reward[t + k][b][i]
-        float R = rw[(int64_t)(m - 1) * M], d = a.g;
+        const float *rw = a.rewards + f;                                // rw[k * M] = reward[t + k][b][i]
+        float R = rw[(int64_t)(m - 1) * M], d = q.g;
         for (int k = m - 2; k >= 0; --k) {
-            R = rw[(int64_t)k * M] + a.g * R;
-            d = d * a.g;
+            R = rw[(int64_t)k * M] + q.g * R;
+            d = d * q.g;
         }
         const float *srow = a.obs_in + r * 12;
         if (t > 0) {
             const int64_t p = f - M;                                   // (t - 1, b, i)
-            srow = (a.done && a.done[(t - 1) * a.envs + b]) ? a.start_obs + p * 12 : a.obs + p * 12;
+            srow = (a.done && a.done[(t - 1) * a.envs + b]) ? a.start_obs + p * 12 : a.next + p * 12;
         }
-        copy_row(a.ring.states + slot * 12, srow);
-        copy_row(a.ring.next_states + slot * 12, a.obs + (f + (int64_t)(m - 1) * M) * 12);
-        a.ring.actions[slot] = a.actions[f];
-        a.ring.rewards[slot] = R;
-        a.discounts[slot] = d;
-        if (a.ring.priorities) a.ring.priorities[slot] = top;
+        copy_row(ring.states + slot * 12, srow);
+        copy_row(ring.next_states + slot * 12, a.next + (f + (int64_t)(m - 1) * M) * 12);
+        ring.actions[slot] = a.actions[f];
+        ring.rewards[slot] = R;
+        q.discounts[slot] = d;
+        if (ring.priorities) ring.priorities[slot] = top;
     }
 }
 
 // ---- the lambda add's scan (uavtrack_replay_add_rollout_lambda; include/uavtrack.h has the definitions)
 
 struct LambdaArgs {
+    AddSource s;                               // the write's own: the scan goes by the same window
     float *rewards, *discounts;                // the ring's [capacity] stores
-    const float *reward, *values;              // [steps][agents]
-    const uint8_t *done;                       // nullable [steps][envs]
-    int64_t capacity, agents, envs, n_uav, steps, skip, start;
+    const float *values;                       // [steps][agents]
     float g, gl, c;                            // (float)gamma, g * l, g * (1 - l)
 };
 
@@ -504,14 +524,15 @@ constexpr int kLambdaW = 64;                   // threads per workgroup: a rollo
 // beyond two groups of kLambdaAhead steps.  WINDOW (the rollout exceeds the ring): rows before `skip` are walked (the
 // walk has no other order) and not written; without it the fold is straight-line code.
 template <bool DONE, bool WINDOW>
-__global__ void __launch_bounds__(kLambdaW) replay_lambda_scan_kernel(LambdaArgs a)
+__global__ void __launch_bounds__(kLambdaW) replay_lambda_scan_kernel(LambdaArgs q)
 {
 #pragma clang fp contract(off)
-    const int64_t cap = a.capacity, M = a.agents, last = a.steps - 1;
-    const float g = a.g, gl = a.gl, c = a.c;                           // (values: a select between two struct members
+    const AddSource &a = q.s;
+    const int64_t M = a.agents, last = a.steps - 1;
+    const float g = q.g, gl = q.gl, c = q.c;                           // (values: a select between two struct members
     const bool all_cut = gl == 0.0f;                                   //  would be a select of addresses and a load)
     for (int64_t r = (int64_t)blockIdx.x * kLambdaW + threadIdx.x; r < M; r += (int64_t)gridDim.x * kLambdaW) {
-        const float *rw = a.reward + r, *vv = a.values + r;             // rw[u * M] = reward[u][b][i]
+        const float *rw = a.rewards + r, *vv = q.values + r;            // rw[u * M] = reward[u][b][i]
         const uint8_t *dn = DONE ? a.done + r / a.n_uav : nullptr;      // dn[u * envs] = done[u][b]
         float G = 0.0f;
         auto fold = [&](int64_t u, float rew, float v, unsigned fired) {
@@ -520,11 +541,10 @@ __global__ void __launch_bounds__(kLambdaW) replay_lambda_scan_kernel(LambdaArgs
             const float d = cut ? g : c;
             G = R + d * v;
             const int64_t f = u * M + r;
-            if (WINDOW && f < a.skip) return;
-            int64_t slot = a.start + (f - a.skip);
-            slot = slot >= cap ? slot - cap : slot;
-            a.rewards[slot] = R;
-            a.discounts[slot] = d;
+            if (WINDOW && f < a.w.skip) return;
+            const int64_t slot = window_slot(a.w, f);
+            q.rewards[slot] = R;
+            q.discounts[slot] = d;
         };
         // the three loads of step u, none of them conditional and nothing computed from them here
         auto load = [&](int64_t u, float &rew, float &v, unsigned &fired) {
@@ -629,73 +649,45 @@ hipError_t launch_replay_sample_uniform(const ReplayDevice &d, int64_t count, in
     return hipGetLastError();
 }
 
-hipError_t launch_replay_add(const ReplayDevice &d, const ReplayRingView &ring, int64_t n, int64_t agents,
-                             const float *obs_in, const float *states, const float *next_states, const int32_t *actions,
-                             const float *rewards, hipStream_t st, const uint8_t *done, const float *start_obs, int64_t n_uav)
+// `kernel` over `items` threads' worth of work in workgroups of `threads` (the kernels stride beyond 65536 workgroups)
+template <class Kernel, class Args>
+static hipError_t launch_over(Kernel kernel, int64_t items, int threads, hipStream_t st, const Args &a)
 {
-    const int64_t cap = ring.capacity;
+    int64_t blocks = (items + threads - 1) / threads;
+    if (blocks > 65536) blocks = 65536;
+    hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(threads), 0, st, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_replay_add(const ReplayDevice &d, const ReplayAdd &q, hipStream_t st)
+{
     hipError_t e;
-    if (ring.priorities && (e = launch_priority_top(d, ring, st)) != hipSuccess) return e;
+    if (q.ring.priorities && (e = launch_priority_top(d, q.ring, st)) != hipSuccess) return e;
     AddArgs a;
-    a.ring = ring; a.obs_in = obs_in; a.src_states = states; a.src_next = next_states; a.src_actions = actions;
-    a.src_rewards = rewards; a.top = d.parts + kReplayMaxParts; a.n = n; a.agents = agents;
-    a.done = done; a.start_obs = start_obs; a.n_uav = n_uav;
-    a.skip = n > cap ? n - cap : 0;
-    a.start = (ring.pos + a.skip) % cap;
-    const int64_t m = n - a.skip;
-    int64_t blocks = (m + kSW - 1) / kSW;
-    if (blocks > 65536) blocks = 65536;
-    if (done) hipLaunchKernelGGL(replay_write_kernel<true>, dim3((unsigned)blocks), dim3(kSW), 0, st, a);
-    else hipLaunchKernelGGL(replay_write_kernel<false>, dim3((unsigned)blocks), dim3(kSW), 0, st, a);
-    return hipGetLastError();
-}
-
-hipError_t launch_replay_add_nstep(const ReplayDevice &d, const ReplayRingView &ring, float *discounts, int64_t steps,
-                                   int64_t envs, int64_t n_uav, const float *obs_in, const float *obs,
-                                   const int32_t *actions, const float *reward, const uint8_t *done, const float *start_obs,
-                                   int n_step, float gamma, hipStream_t st)
-{
-    const int64_t cap = ring.capacity;
-    hipError_t e;
-    if (ring.priorities && (e = launch_priority_top(d, ring, st)) != hipSuccess) return e;
-    NstepArgs a;
-    a.ring = ring; a.discounts = discounts; a.obs_in = obs_in; a.obs = obs; a.reward = reward; a.actions = actions;
-    a.done = done; a.start_obs = start_obs; a.top = d.parts + kReplayMaxParts;
-    a.envs = envs; a.n_uav = n_uav; a.steps = steps; a.agents = envs * n_uav; a.n = steps * a.agents;
-    a.n_step = n_step; a.g = gamma;
-    a.skip = a.n > cap ? a.n - cap : 0;
-    a.start = (ring.pos + a.skip) % cap;
-    int64_t blocks = (a.n - a.skip + kSW - 1) / kSW;
-    if (blocks > 65536) blocks = 65536;
-    hipLaunchKernelGGL(replay_write_nstep_kernel, dim3((unsigned)blocks), dim3(kSW), 0, st, a);
-    return hipGetLastError();
-}
-
-hipError_t launch_replay_add_lambda(const ReplayDevice &d, const ReplayRingView &ring, float *discounts, int64_t steps,
-                                    int64_t envs, int64_t n_uav, const float *obs_in, const float *obs,
-                                    const int32_t *actions, const float *reward, const uint8_t *done, const float *start_obs,
-                                    const float *values, float lambda, float gamma, hipStream_t st)
-{
-    const int64_t cap = ring.capacity, agents = envs * n_uav, n = steps * agents;
-    // states, actions, next states and priorities (and the raw rewards, which the scan overwrites) as the one-step add
-    hipError_t e = launch_replay_add(d, ring, n, agents, obs_in, nullptr, obs, actions, reward, st, done, start_obs, n_uav);
-    if (e != hipSuccess) return e;
-    LambdaArgs a;
-    a.rewards = ring.rewards; a.discounts = discounts; a.reward = reward; a.values = values; a.done = done;
-    a.capacity = cap; a.agents = agents; a.envs = envs; a.n_uav = n_uav; a.steps = steps;
-    a.skip = n > cap ? n - cap : 0;
-    a.start = (ring.pos + a.skip) % cap;
-    a.g = gamma;
-    a.gl = gamma * lambda;
-    a.c = gamma * (1.0f - lambda);
-    int64_t blocks = (agents + kLambdaW - 1) / kLambdaW;
-    if (blocks > 65536) blocks = 65536;
-    const dim3 grid((unsigned)blocks), blk(kLambdaW);
-    if (done && a.skip) hipLaunchKernelGGL((replay_lambda_scan_kernel<true, true>), grid, blk, 0, st, a);
-    else if (done) hipLaunchKernelGGL((replay_lambda_scan_kernel<true, false>), grid, blk, 0, st, a);
-    else if (a.skip) hipLaunchKernelGGL((replay_lambda_scan_kernel<false, true>), grid, blk, 0, st, a);
-    else hipLaunchKernelGGL((replay_lambda_scan_kernel<false, false>), grid, blk, 0, st, a);
-    return hipGetLastError();
+    AddSource &s = a.s;
+    a.ring = q.ring; s.obs_in = q.obs_in; s.states = q.states; s.next = q.next; s.actions = q.actions;
+    s.rewards = q.rewards; s.done = q.done; s.start_obs = q.start_obs; s.top = d.parts + kReplayMaxParts;
+    s.envs = q.envs; s.n_uav = q.n_uav; s.steps = q.steps; s.agents = q.envs * q.n_uav;
+    s.w = ring_window(q.ring, q.steps * s.agents);             // what the write and the lambda scan both go by
+    const int64_t written = s.w.n - s.w.skip;
+    if (q.form == ReplayForm::Nstep) {
+        NstepArgs n;
+        n.a = a; n.discounts = q.discounts; n.n_step = q.n_step; n.g = q.gamma;
+        return launch_over(replay_write_nstep_kernel, written, kSW, st, n);
+    }
+    // lambda: states, actions, next states and priorities (and the raw rewards, which the scan overwrites) as the one-step add
+    e = q.done ? launch_over(replay_write_kernel<true>, written, kSW, st, a)
+               : launch_over(replay_write_kernel<false>, written, kSW, st, a);
+    if (q.form != ReplayForm::Lambda || e != hipSuccess) return e;
+    LambdaArgs l;
+    l.s = s; l.rewards = q.ring.rewards; l.discounts = q.discounts; l.values = q.values;
+    l.g = q.gamma;
+    l.gl = q.gamma * q.lambda;
+    l.c = q.gamma * (1.0f - q.lambda);
+    const bool window = s.w.skip != 0;
+    auto scan = q.done ? (window ? replay_lambda_scan_kernel<true, true> : replay_lambda_scan_kernel<true, false>)
+                       : (window ? replay_lambda_scan_kernel<false, true> : replay_lambda_scan_kernel<false, false>);
+    return launch_over(scan, s.agents, kLambdaW, st, l);
 }
 
 }  // namespace uavtrack

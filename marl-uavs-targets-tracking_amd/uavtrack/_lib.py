@@ -262,6 +262,14 @@ def ptr(t):
     return None if t is None else C.c_void_p(t.data_ptr())
 
 
+def tensor_arg(t, dtype, n: int, device, message: str):
+    """t as a pointer argument may take it: None, or a contiguous `dtype` tensor of n elements on `device`; else
+    ValueError(message).  Returns t."""
+    if t is not None and (t.numel() != n or t.dtype != dtype or not t.is_contiguous() or t.device != device):
+        raise ValueError(message)
+    return t
+
+
 def host_ptr(a):
     """A numpy array's address as a void * argument."""
     return a.ctypes.data_as(C.c_void_p)

@@ -201,8 +201,8 @@ class DeviceActorCritic(Handle):
         n = states.numel() // D
         if out is None:
             out = torch.empty(lead, dtype=torch.float32, device=self.device)
-        elif out.numel() != n or out.dtype != torch.float32 or not out.is_contiguous() or out.device != self.device:
-            raise ValueError(f"values: out must be a contiguous float32 tensor of {n} elements on {self.device}")
+        _lib.tensor_arg(out, torch.float32, n, self.device,
+                        f"values: out must be a contiguous float32 tensor of {n} elements on {self.device}")
         if n:
             _lib.check(self._lib.uavtrack_learner_values(self._h, n, _ptr(states), _ptr(out), self._stream()),
                        "uavtrack_learner_values")
@@ -238,23 +238,18 @@ class DeviceActorCritic(Handle):
             return idx, buffer.priorities, (w / w.max()).to(torch.float32).contiguous()
         return torch.randperm(buffer.count, device=buffer.device, generator=generator)[:k], None, None
 
-    def _weights_arg(self, weights: Optional[torch.Tensor], n: int):
-        if weights is None:
-            return None
-        if weights.numel() != n or weights.dtype != torch.float32 or not weights.is_contiguous() \
-                or weights.device != self.device:
-            raise ValueError(f"weights must be a contiguous float32 tensor of {n} elements (one per batch row, in batch "
-                             f"order) on {self.device}")
-        return weights
-
-    def _discounts_arg(self, discounts: Optional[torch.Tensor], capacity: int):
-        if discounts is None:
-            return None
-        if discounts.numel() != capacity or discounts.dtype != torch.float32 or not discounts.is_contiguous() \
-                or discounts.device != self.device:
-            raise ValueError(f"discounts must be a contiguous float32 tensor of {capacity} elements (one per slot of the "
-                             f"store) on {self.device}")
-        return discounts
+    def _form(self, n: int, weights: Optional[torch.Tensor], capacity: int, discounts: Optional[torch.Tensor]):
+        """(suffix, extra arguments) of the uavtrack_learner_update / _grad entry point a batch takes: plain, _weighted
+        (weights, one per batch row) or _discounted (weights or NULL, then discounts, one per slot of the store)."""
+        w = _lib.tensor_arg(weights, torch.float32, n, self.device,
+                            f"weights must be a contiguous float32 tensor of {n} elements (one per batch row, in batch "
+                            f"order) on {self.device}")
+        d = _lib.tensor_arg(discounts, torch.float32, capacity, self.device,
+                            f"discounts must be a contiguous float32 tensor of {capacity} elements (one per slot of the "
+                            f"store) on {self.device}")
+        if d is not None:
+            return "_discounted", (_ptr(w), _ptr(d))
+        return ("", ()) if w is None else ("_weighted", (_ptr(w),))
 
     def _discounts_of(self, buffer) -> Optional[torch.Tensor]:
         """The buffer's per-slot discount store, or None; an n-step ring must have been folded with this learner's gamma."""
@@ -270,20 +265,11 @@ class DeviceActorCritic(Handle):
         dev = self.device
         losses = torch.empty(2, device=dev)
         td = torch.empty(n, device=dev)
-        if discounts is not None:
-            _lib.check(self._lib.uavtrack_learner_update_discounted(
-                self._h, n, *self._batch_args(store, capacity, idx), _ptr(self._weights_arg(weights, n)),
-                _ptr(self._discounts_arg(discounts, capacity)), _ptr(losses[0:1]), _ptr(losses[1:2]), _ptr(td),
-                _ptr(priorities), self._stream()), "uavtrack_learner_update_discounted")
-        elif weights is None:
-            _lib.check(self._lib.uavtrack_learner_update(
-                self._h, n, *self._batch_args(store, capacity, idx), _ptr(losses[0:1]), _ptr(losses[1:2]), _ptr(td),
-                _ptr(priorities), self._stream()), "uavtrack_learner_update")
-        else:
-            _lib.check(self._lib.uavtrack_learner_update_weighted(
-                self._h, n, *self._batch_args(store, capacity, idx), _ptr(self._weights_arg(weights, n)),
-                _ptr(losses[0:1]), _ptr(losses[1:2]), _ptr(td), _ptr(priorities), self._stream()),
-                "uavtrack_learner_update_weighted")
+        suffix, extra = self._form(n, weights, capacity, discounts)
+        name = "uavtrack_learner_update" + suffix
+        _lib.check(getattr(self._lib, name)(
+            self._h, n, *self._batch_args(store, capacity, idx), *extra, _ptr(losses[0:1]), _ptr(losses[1:2]), _ptr(td),
+            _ptr(priorities), self._stream()), name)
         return losses[0], losses[1], td
 
     def update(self, transition_dict: Dict[str, torch.Tensor], weights: Optional[torch.Tensor] = None,
@@ -353,24 +339,14 @@ class DeviceActorCritic(Handle):
               weights: Optional[torch.Tensor] = None, discounts: Optional[torch.Tensor] = None):
         if row is None:
             row = torch.empty(self.row_floats, device=self.device)
-        elif row.numel() != self.row_floats or row.dtype != torch.float32 or not row.is_contiguous() \
-                or row.device != self.device:
-            raise ValueError(f"row must be a contiguous float32 tensor of {self.row_floats} words on {self.device}")
+        _lib.tensor_arg(row, torch.float32, self.row_floats, self.device,
+                        f"row must be a contiguous float32 tensor of {self.row_floats} words on {self.device}")
         if td is None:
             td = torch.empty(n, device=self.device)
-        if discounts is not None:
-            _lib.check(self._lib.uavtrack_learner_grad_discounted(
-                self._h, n, *self._batch_args(store, capacity, idx), _ptr(self._weights_arg(weights, n)),
-                _ptr(self._discounts_arg(discounts, capacity)), _ptr(td), _ptr(row), self._stream()),
-                "uavtrack_learner_grad_discounted")
-        elif weights is None:
-            _lib.check(self._lib.uavtrack_learner_grad(
-                self._h, n, *self._batch_args(store, capacity, idx), _ptr(td), _ptr(row), self._stream()),
-                "uavtrack_learner_grad")
-        else:
-            _lib.check(self._lib.uavtrack_learner_grad_weighted(
-                self._h, n, *self._batch_args(store, capacity, idx), _ptr(self._weights_arg(weights, n)), _ptr(td),
-                _ptr(row), self._stream()), "uavtrack_learner_grad_weighted")
+        suffix, extra = self._form(n, weights, capacity, discounts)
+        name = "uavtrack_learner_grad" + suffix
+        _lib.check(getattr(self._lib, name)(
+            self._h, n, *self._batch_args(store, capacity, idx), *extra, _ptr(td), _ptr(row), self._stream()), name)
         return row, td
 
     def grad_from(self, buffer, batch_size: int, row: Optional[torch.Tensor] = None,

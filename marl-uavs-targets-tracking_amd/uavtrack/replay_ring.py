@@ -118,11 +118,9 @@ class ReplayRing(Handle):
         if (critic is None) == (values is None):
             raise ValueError("add_rollout: a lambda ring needs exactly one of critic= and values=")
         if values is not None:
-            if values.numel() != n or values.dtype != torch.float32 or not values.is_contiguous() \
-                    or values.device != self.device:
-                raise ValueError(f"add_rollout: values must be a contiguous float32 tensor of {n} elements (one per "
-                                 f"row of obs) on {self.device}")
-            return values
+            return _lib.tensor_arg(values, torch.float32, n, self.device,
+                                   f"add_rollout: values must be a contiguous float32 tensor of {n} elements (one per "
+                                   f"row of obs) on {self.device}")
         if self._values is None or self._values.numel() < n:
             self._values = torch.empty(n, dtype=torch.float32, device=self.device)
         buf = self._values[:n]
@@ -205,50 +203,39 @@ class ReplayRing(Handle):
         if obs.dtype != torch.float32 or obs_in.dtype != torch.float32 or act.dtype != torch.int32 \
                 or rew.dtype != torch.float32:
             raise TypeError("add_rollout: obs_in, obs and reward must be float32, actions int32")
-        for t in (obs_in, obs, act, rew):
-            if t.device != self.device or not t.is_contiguous():
-                raise ValueError("add_rollout: every input must be contiguous on the ring's device")
-        ring = self._ring()
+        self._on_ring(obs_in, obs, act, rew)
+        episode_ends = (None, None)                  # done, start_obs as the library takes them
         if so is not None:
             done = out.get("done")
             if obs.dim() != 4 or done is None or tuple(done.shape) != tuple(obs.shape[:2]) or done.dtype != torch.uint8 \
                     or tuple(so.shape) != tuple(obs.shape) or so.dtype != torch.float32:
                 raise ValueError("add_rollout: with start_obs, obs must be [T,B,N,12], done uint8 [T,B] and start_obs "
                                  "float32 of obs's shape")
-            for t in (done, so):
-                if t.device != self.device or not t.is_contiguous():
-                    raise ValueError("add_rollout: every input must be contiguous on the ring's device")
+            self._on_ring(done, so)
+            episode_ends = (done.data_ptr(), so.data_ptr())
+        # the form and what its entry point takes behind (handle, ring): lambda, then n-step, then episodes, then plain
+        source = (obs_in.data_ptr(), obs.data_ptr(), act.data_ptr(), rew.data_ptr())     # (void * arguments take integers)
+        if self.lam is not None or self.discounts is not None:
+            if obs.dim() != 4:
+                raise ValueError(f"add_rollout: {'an n-step' if self.lam is None else 'a lambda'} ring needs obs as [T,B,N,12]")
+            args = (self.discounts.data_ptr(), T, obs.shape[1], obs.shape[2], *source, *episode_ends)
+            if self.lam is not None:
+                name = "uavtrack_replay_add_rollout_lambda"
+                args += (_ptr(self._rollout_values(obs, critic, values)), self.lam, self.gamma)
+            else:
+                name, args = "uavtrack_replay_add_rollout_nstep", args + (self.n_step, self.gamma)
+        elif so is not None:
+            name, args = "uavtrack_replay_add_rollout_episodes", (T, obs.shape[1], obs.shape[2], *source, *episode_ends)
         else:
-            done = None
-        if self.lam is not None:
-            if obs.dim() != 4:
-                raise ValueError("add_rollout: a lambda ring needs obs as [T,B,N,12]")
-            v = self._rollout_values(obs, critic, values)
-            _lib.check(self._lib.uavtrack_replay_add_rollout_lambda(
-                self._h, C.byref(ring), _ptr(self.discounts), T, int(obs.shape[1]), int(obs.shape[2]), _ptr(obs_in),
-                _ptr(obs), _ptr(act), _ptr(rew), _ptr(done), _ptr(so), _ptr(v), self.lam, self.gamma, self._stream()),
-                "uavtrack_replay_add_rollout_lambda")
-            self._advance(T * M)
-            return
-        if self.discounts is not None:
-            if obs.dim() != 4:
-                raise ValueError("add_rollout: an n-step ring needs obs as [T,B,N,12]")
-            _lib.check(self._lib.uavtrack_replay_add_rollout_nstep(
-                self._h, C.byref(ring), _ptr(self.discounts), T, int(obs.shape[1]), int(obs.shape[2]), _ptr(obs_in),
-                _ptr(obs), _ptr(act), _ptr(rew), _ptr(done), _ptr(so), self.n_step, self.gamma, self._stream()),
-                "uavtrack_replay_add_rollout_nstep")
-            self._advance(T * M)
-            return
-        if so is not None:
-            _lib.check(self._lib.uavtrack_replay_add_rollout_episodes(
-                self._h, C.byref(ring), T, int(obs.shape[1]), int(obs.shape[2]), _ptr(obs_in), _ptr(obs), _ptr(act), _ptr(rew),
-                _ptr(done), _ptr(so), self._stream()), "uavtrack_replay_add_rollout_episodes")
-            self._advance(T * M)
-            return
-        _lib.check(self._lib.uavtrack_replay_add_rollout(self._h, C.byref(ring), T, M, _ptr(obs_in), _ptr(obs),
-                                                         _ptr(act), _ptr(rew), self._stream()),
-                   "uavtrack_replay_add_rollout")
+            name, args = "uavtrack_replay_add_rollout", (T, M, *source)
+        ring = self._ring()
+        _lib.check(getattr(self._lib, name)(self._h, C.byref(ring), *args, self._stream()), name)
         self._advance(T * M)
+
+    def _on_ring(self, *tensors) -> None:
+        for t in tensors:
+            if t.device != self.device or not t.is_contiguous():
+                raise ValueError("add_rollout: every input must be contiguous on the ring's device")
 
     # ---- sample (train.py:56-58)
     def _draw_uniform(self, k: int, idx: torch.Tensor) -> None:
