@@ -826,7 +826,30 @@ __global__ void __launch_bounds__(kMaxWorkgroup) rollout_kernel(const StepParams
     // sequential view as a bit word: bit jp set = this lane sees pair jp BEFORE its move (2 jp >= i); the copy that holds it
     // is pn ^ bit (sweep_fast, copyw)
     const unsigned oldw = (i + 1) / 2 < 32 ? ~0u << ((i + 1) / 2) : 0u;
+    // Two waves on one SIMD are not served alike: at equal priority the SIMD issues for its OLDER wave first.  In the
+    // headline launch (1 366 single-wavefront groups: every SIMD holds a wave, 341 hold a second one, in wave slot 1) the
+    // older wave runs as if alone, 1.69 us per step, the younger takes 2.52 us and, left behind, ends the launch on a nearly
+    // empty CU (424 us for 200 steps).  The younger wave therefore starts at the higher priority and gives it
+    // up part of the way, after which age serves the older one: with s of T steps favoured both are through together when
+    // (T - s * 1.69 / 2.52) * 1.69 = (T - s) * 2.52, s = 0.6 T.  Priority decides who issues, never what: results are bitwise
+    // the same.  (Measured 0.431 -> 0.400 ms per 200-step launch, 0.060 -> 0.056 ms per 20 steps; the younger wave favoured
+    // throughout only swaps the roles: 0.431 ms.)  Only the plain single-wavefront 20 x 10 rollout: the rates, and with them
+    // the 0.6, were measured on its launches alone; the 10 x 10 and 5 x 3 variants stay as they were.
+    // What this rests on, and where it ends: that a SIMD serves its older wave first is OBSERVED on MI355X (the stamps of
+    // profiles/r06_relay_experiments.txt), not documented.  `favoured` is "wave slot != 0", which is "shares its SIMD with
+    // an older wave of this launch" only while this kernel has the GPU to itself and a SIMD holds at most two of its waves
+    // (up to 2 048 wavefronts, 6 144 environments; beyond, select_rollout takes a multi-wave variant).  With another
+    // kernel's wave in slot 0 (a learner or scorer on a second stream) the rollout wave beside it runs at priority 3 against
+    // it for 0.6 T steps, and of three waves on a SIMD two would be favoured: the 0.6 T models neither.  Results do not
+    // depend on any of it.
+    constexpr bool kAgeBalance = kStepsPerIter == 2 && N_ == 20 && M_ == 10;
+    constexpr unsigned kHwIdWaveSlot = 4u | 0u << 6 | 3u << 11;     // s_getreg operand: HW_ID (register 4), bits [3:0]
+    bool favoured = false;
+    if (kAgeBalance) favoured = __builtin_amdgcn_s_getreg(kHwIdWaveSlot) != 0;      // not in the first wave slot of its SIMD
+    const int favoured_steps = (p.T * 3 / 5) & ~1;
+    if (kAgeBalance && favoured) __builtin_amdgcn_s_setprio(3);
     for (int t0 = 0; t0 < p.T; t0 += kStepsPerIter) {
+        if (kAgeBalance && favoured && t0 == favoured_steps) __builtin_amdgcn_s_setprio(0);
 #pragma unroll
     for (int tpar = 0; tpar < kStepsPerIter; ++tpar) {
         const int t = t0 + tpar;

@@ -26,6 +26,7 @@ os.makedirs(out, exist_ok=True)
 flags = ("--offload-arch=gfx950 -O3 -std=c++17 -fPIC -fno-gpu-rdc -ffp-contract=off -I%s/include -I%s -Wno-unused-function -Wno-pass-failed "
          "-fno-convergent-functions -fno-slp-vectorize -mllvm -amdgpu-atomic-optimizer-strategy=None -mllvm -amdgpu-mfma-vgpr-form=1" % (ROOT, dst)).split()
 subprocess.run(["/opt/rocm/bin/hipcc"] + flags + ["-c", p, "-o", os.path.join(out, "step_kernel.o")], check=True)
-objs = [os.path.join(src, "build", f + ".o") for f in ("api", "reset_kernel", "pmi_kernel", "policy_kernel")] + [os.path.join(out, "step_kernel.o")]
+# (every object of the library's own build but the patched one: run `make -C csrc` first)
+objs = [os.path.join(src, "build", f) for f in sorted(os.listdir(os.path.join(src, "build"))) if f.endswith(".o") and f != "step_kernel.o"] + [os.path.join(out, "step_kernel.o")]
 subprocess.run(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-shared", "-fPIC", "-o", os.path.join(ROOT, "build_variants", name + ".so")] + objs, check=True)
 print("built build_variants/%s.so" % name)
