@@ -1,6 +1,6 @@
 """float64 mirror of the split update (uavtrack_learner_grad / _apply): a shard's UNSCALED gradient and loss sums, the
 ordered combine with its one global scale, and Adam through tests/learner_mirror.py.  Also the rule the split must NOT
-be mistaken for -- the average of the shards' own reference-loss gradients -- and the batch both test files share."""
+be mistaken for -- the average of the shards' own reference-loss gradients -- and the batches and initial parameters the learner tests draw."""
 import numpy as np
 
 import learner_mirror as mirror
@@ -77,7 +77,7 @@ def split(batch, pieces):
 
 
 def init_blob(H, A, seed):
-    """torch.nn.Linear's default initialisation of both networks as one fp32 blob (as tests/test_hip_learner.py)."""
+    """torch.nn.Linear's default initialisation of both networks as one fp32 blob."""
     import torch
     import uavtrack
     torch.manual_seed(seed)
@@ -86,7 +86,7 @@ def init_blob(H, A, seed):
 
 
 def batch(rng, n, A):
-    """The value ranges of tests/test_hip_learner.py's batches."""
+    """A batch of n transitions for the learner tests: (states, actions, rewards, next_states)."""
     s = rng.uniform(-1, 1, size=(n, 12)).astype(np.float32)
     s2 = rng.uniform(-1, 1, size=(n, 12)).astype(np.float32)
     s[:, 9:11] = rng.uniform(0, 5, size=(n, 2)); s2[:, 9:11] = rng.uniform(0, 5, size=(n, 2))
@@ -106,8 +106,3 @@ def teeth_batch():
     s, a, r, s2 = batch(np.random.RandomState(c["seed"]), c["n"], c["A"])
     r = (r + np.linspace(-3.0, 3.0, c["n"])).astype(np.float32)
     return init_blob(c["H"], c["A"], c["seed"]), (s, a, r, s2)
-
-
-def gpu_gradient_tolerance(n, gmax):
-    """The gradient bound tests/test_hip_learner.py::test_sweep_against_fp64_mirror applies to a single update."""
-    return 2e-6 * (1 + np.log2(n)) * gmax

@@ -2,7 +2,7 @@
 forms and against the float64 forward; the lambda ring add (uavtrack_replay_add_rollout_lambda) against the numpy mirror
 (tests/lambda_mirror.py), bitwise over all five stores and the priorities; lambda = 0 as with_nstep(1, gamma); values +
 add + update end to end; graph capture; host-side errors; the example.  The rollout, the done patterns and the ring
-cases are those of tests/test_hip_nstep.py."""
+cases are those of tests/test_hip_nstep.py (tests/ring_rollout_harness.py)."""
 import ctypes as C
 
 import numpy as np
@@ -11,13 +11,15 @@ import torch
 
 import lambda_mirror as lm
 import learner_dp_mirror as dp
+import learner_harness as lh
 import nstep_mirror as nm
-import test_hip_nstep as hn
+import ring_rollout_harness as rr
+from ring_rollout_harness import B, N, NTR, T
 
 pytestmark = pytest.mark.gpu
 
-DEV = hn.DEV
-GAMMA = hn.GAMMA
+DEV = lh.DEV
+GAMMA = lh.GAMMA
 LAMBDAS = (0.0, 0.5, 0.95, 1.0)
 GAMMAS = (0.0, 0.95, 1.0)
 U = 2.0 ** -24
@@ -26,10 +28,6 @@ U = 2.0 ** -24
 def _uav():
     import uavtrack
     return uavtrack
-
-
-def _dev(x):
-    return torch.from_numpy(np.ascontiguousarray(x)).to(DEV)
 
 
 # ---- 1. values: the update's own V(s), to the bit ------------------------------------------------------------------------
@@ -45,7 +43,7 @@ def _value_rows(n):
         x.flat[rng.randint(0, x.size)] = 1e3
         x.flat[rng.randint(0, x.size)] = -1e3
         x = x.astype(np.float32)
-        _rows[n] = (x, _dev(x), _dev(rng.randint(0, 5, n).astype(np.int32)))
+        _rows[n] = (x, lh.dev(x), lh.dev(rng.randint(0, 5, n).astype(np.int32)))
     return _rows[n]
 
 
@@ -56,8 +54,8 @@ def test_values_are_the_updates_own_v_bitwise_and_the_fp64_forward_within_the_ch
     blob = dp.init_blob(H, A, 100 + H)
     assert lm.critic_of(blob, H, A)[3] != 0                            # b2: V is never an exact zero by accident
     x, xd, act = _value_rows(n)
-    L = hn._learner(H, A, "reference", blob, max_batch=n)
-    before = hn._state(L)
+    L = lh.learner(H, A, "reference", blob, max_batch=n)
+    before = lh.state(L)
     v = L.values(xd)
     assert v.shape == (n,) and v.dtype == torch.float32
     # rewards = 0 and a discount store of 0: td_delta = (0 + 0 * V(s')) - V(s) = -V(s) exactly
@@ -66,7 +64,7 @@ def test_values_are_the_updates_own_v_bitwise_and_the_fp64_forward_within_the_ch
     L.check()
     got = v.cpu().numpy()
     assert got.tobytes() == (-td.cpu().numpy()).tobytes()
-    hn._same(hn._state(L), before)                                      # values changed nothing
+    lh.same(lh.state(L), before)                                      # values changed nothing
     # out= is written in place; any leading shape
     out = torch.full((n,), 7.0, device=DEV)
     assert L.values(xd.reshape(n, 1, 12), out=out) is out and torch.equal(out, v)
@@ -84,10 +82,10 @@ def test_values_read_the_parameters_of_the_moment_and_span_more_than_one_grid_pa
     load_state_dict the same call gives the new critic's values."""
     H, A, n = 16, 5, 2048 * 512 + 700
     blob = dp.init_blob(H, A, 7)
-    L = hn._learner(H, A, "reference", blob, max_batch=64)
+    L = lh.learner(H, A, "reference", blob, max_batch=64)
     rng = np.random.RandomState(3)
     x = rng.uniform(-2, 2, (n, 12)).astype(np.float32)
-    xd = _dev(x)
+    xd = lh.dev(x)
     got = L.values(xd).cpu().numpy()
     want = lm.critic_forward(blob, H, A, x)
     bound = (H + 14) * U * lm.critic_magnitude(blob, H, A, x) + np.spacing(np.abs(got)).astype(np.float64)
@@ -105,8 +103,6 @@ def test_values_read_the_parameters_of_the_moment_and_span_more_than_one_grid_pa
 
 # ---- 2. the add against the mirror ---------------------------------------------------------------------------------------
 
-T, B, N = hn.T, hn.B, hn.N
-NTR = hn.NTR
 _vals = {}
 
 
@@ -115,7 +111,7 @@ def _values(shape=(T, B, N), seed=11):
     key = (shape, seed)
     if key not in _vals:
         v = (np.random.default_rng(seed).standard_normal(shape) * 4).astype(np.float32)
-        _vals[key] = (v, _dev(v))
+        _vals[key] = (v, lh.dev(v))
     return _vals[key]
 
 
@@ -129,31 +125,31 @@ def _check_add(ring, pos, count, host, dev_obs_in, out, values, lam, gamma, done
     sentinels: the image starts from them)."""
     ring.with_lambda(lam, gamma)
     assert ring.n_step == 1 and ring.lam == lam and ring.gamma == gamma
-    hn._prefill(ring, pos, count)
-    img = hn._image(ring)
+    rr.prefill(ring, pos, count)
+    img = rr.image(ring)
     ring.add_rollout(dev_obs_in, out, values=values[1])
     tr = lm.transitions(host["obs_in"], host["obs"], host["actions"], host["reward"], values[0], lam, gamma, done,
                         None if done is None else host["start_obs"])
     p2, c2 = nm.ring_add(img, pos, count, tr)
     assert (ring.pos, ring.count) == (p2, c2)
-    hn._same_image(hn._image(ring), img)
+    rr.same_image(rr.image(ring), img)
     d = img["discounts"]
     assert ((d >= 0) & (d <= 1) | (d == np.float32(7.0))).all()        # status bit 3 never fires on a written slot
     return tr
 
 
-@pytest.mark.parametrize("ringcase", sorted(hn.RINGS))
-@pytest.mark.parametrize("done_kind", hn.DONES)
+@pytest.mark.parametrize("ringcase", sorted(rr.RINGS))
+@pytest.mark.parametrize("done_kind", rr.DONES)
 @pytest.mark.parametrize("kind", ["uniform", "prioritised"])
 def test_add_against_the_mirror_bitwise(kind, done_kind, ringcase):
-    r = hn._rollout()
-    done = hn._done(done_kind)
-    cap, pos, count = hn.RINGS[ringcase]
+    r = rr.rollout()
+    done = rr.done(done_kind)
+    cap, pos, count = rr.RINGS[ringcase]
     ring = _new_ring(kind, cap)
     folded = 0
     for lam in LAMBDAS:
         for gamma in GAMMAS:
-            tr = _check_add(ring, pos, count, r, r["dev"]["obs_in"], hn._out(done), _values(), lam, gamma, done)
+            tr = _check_add(ring, pos, count, r, r["dev"]["obs_in"], rr.out(done), _values(), lam, gamma, done)
             folded += int((tr["rewards"] != r["reward"].reshape(-1)).sum())
     assert folded > 0                                                  # some reward carried a tail
 
@@ -161,15 +157,15 @@ def test_add_against_the_mirror_bitwise(kind, done_kind, ringcase):
 @pytest.mark.parametrize("kind", ["uniform", "prioritised"])
 @pytest.mark.parametrize("steps", [1, 2])
 def test_add_of_one_and_two_steps(steps, kind):
-    r = hn._rollout()
+    r = rr.rollout()
     host = {k: (r[k] if k == "obs_in" else r[k][:steps]) for k in ("obs_in", "obs", "actions", "reward", "start_obs")}
-    dev = {k: _dev(v) for k, v in host.items()}
+    dev = {k: lh.dev(v) for k, v in host.items()}
     v = _values()
-    values = (v[0][:steps], _dev(v[0][:steps]))
+    values = (v[0][:steps], lh.dev(v[0][:steps]))
     for done in (None, np.zeros((steps, B), np.uint8), np.ones((steps, B), np.uint8)):
         out = {k: dev[k] for k in ("obs", "actions", "reward")}
         if done is not None:
-            out.update(done=_dev(done), start_obs=dev["start_obs"])
+            out.update(done=lh.dev(done), start_obs=dev["start_obs"])
         ring = _new_ring(kind, 50)
         for lam in LAMBDAS:
             for gamma in GAMMAS:
@@ -189,7 +185,7 @@ def _shaped_rollout(Tw, Bw, Nw):
                  actions=rng.integers(0, 12, (Tw, Bw, Nw)).astype(np.int32), reward=reward,
                  start_obs=rng.standard_normal((Tw, Bw, Nw, 12)).astype(np.float32),
                  done=(rng.random((Tw, Bw)) < 0.2).astype(np.uint8))
-        r["dev"] = {k: _dev(v) for k, v in r.items()}
+        r["dev"] = {k: lh.dev(v) for k, v in r.items()}
         _shaped[Tw, Bw, Nw] = r
     return _shaped[Tw, Bw, Nw]
 
@@ -219,24 +215,24 @@ def test_add_of_many_chains_and_of_long_chains(shape, kind, with_done, ringcase)
 
 # ---- 3. lambda = 0 is with_nstep(1, gamma) -------------------------------------------------------------------------------
 
-@pytest.mark.parametrize("ringcase", sorted(hn.RINGS))
+@pytest.mark.parametrize("ringcase", sorted(rr.RINGS))
 @pytest.mark.parametrize("done_kind", ["null", "mid", "every"])
 @pytest.mark.parametrize("kind", ["uniform", "prioritised"])
 def test_lambda_0_is_with_nstep_1_byte_for_byte(kind, done_kind, ringcase):
-    r = hn._rollout()
+    r = rr.rollout()
     reward = r["reward"].copy()
     reward[2, 1, 0] = -0.0                                             # a cut copies the reward: -0.0 stays -0.0
-    done = hn._done(done_kind)
-    out = dict(hn._out(done), reward=_dev(reward))
-    cap, pos, count = hn.RINGS[ringcase]
+    done = rr.done(done_kind)
+    out = dict(rr.out(done), reward=lh.dev(reward))
+    cap, pos, count = rr.RINGS[ringcase]
     for lam, gamma in ((0.0, GAMMA), (0.0, 1.0), (0.6, 0.0)):
         new = _new_ring(kind, cap).with_lambda(lam, gamma)
         old = _new_ring(kind, cap).with_nstep(1, gamma)
-        hn._prefill(new, pos, count); hn._prefill(old, pos, count)
+        rr.prefill(new, pos, count); rr.prefill(old, pos, count)
         new.add_rollout(r["dev"]["obs_in"], out, values=_values()[1])
         old.add_rollout(r["dev"]["obs_in"], out)
-        a, b = hn._image(new), hn._image(old)
-        hn._same_image(a, b)
+        a, b = rr.image(new), rr.image(old)
+        rr.same_image(a, b)
         assert (new.pos, new.count) == (old.pos, old.count)
         f = (2 * B + 1) * N                                             # the -0.0 reward's transition, where it was written
         if f >= NTR - min(NTR, cap):
@@ -249,11 +245,11 @@ def test_lambda_0_is_with_nstep_1_byte_for_byte(kind, done_kind, ringcase):
 @pytest.mark.parametrize("kind", ["uniform", "prioritised"])
 def test_values_add_and_update_end_to_end(kind):
     H, A, k, lam = 64, 12, 32, 0.9
-    r = hn._rollout()
-    done = hn._done("mid")
-    out = hn._out(done)
+    r = rr.rollout()
+    done = rr.done("mid")
+    out = rr.out(done)
     blob = dp.init_blob(H, A, 42)
-    L = hn._learner(H, A, "reference", blob, max_batch=k)
+    L = lh.learner(H, A, "reference", blob, max_batch=k)
     ring = _new_ring(kind, 100, max_batch=k).with_lambda(lam, GAMMA)
     ring.add_rollout(r["dev"]["obs_in"], out, critic=L)
     buf = ring._values
@@ -261,7 +257,7 @@ def test_values_add_and_update_end_to_end(kind):
     v = L.values(out["obs"])
     assert torch.equal(v.reshape(-1), buf[:NTR])
     tr = lm.transitions(r["obs_in"], r["obs"], r["actions"], r["reward"], v.cpu().numpy(), lam, GAMMA, done, r["start_obs"])
-    img = hn._image(ring)
+    img = rr.image(ring)
     for key in ("states", "actions", "rewards", "next_states", "discounts"):
         assert img[key][:NTR].tobytes() == tr[key].tobytes(), key
     assert (ring.pos, ring.count) == (NTR, NTR)
@@ -269,8 +265,8 @@ def test_values_add_and_update_end_to_end(kind):
     al, cl, td = L.update_from(ring, k)
     L.check(); ring.check()
     idx = ring._idx[:k].cpu().numpy()
-    ral, rcl, rtd, _ = nm.learner(blob, H, A, *(tr[key][idx] for key in hn.STORES), tr["discounts"][idx], "reference")
-    hn._assert_losses_and_td(al.cpu().numpy(), cl.cpu().numpy(), td.cpu().numpy(), ral, rcl, rtd)
+    ral, rcl, rtd, _ = nm.learner(blob, H, A, *(tr[key][idx] for key in lh.STORES), tr["discounts"][idx], "reference")
+    lh.assert_losses_and_td(al.cpu().numpy(), cl.cpu().numpy(), td.cpu().numpy(), ral, rcl, rtd)
     # a second add of the same shape allocates nothing
     ring.add_rollout(r["dev"]["obs_in"], out, critic=L)
     assert ring._values is buf
@@ -280,14 +276,14 @@ def test_values_add_and_update_end_to_end(kind):
     with pytest.raises(ValueError, match=r"0\.9\b.*0\.95\b"):
         L.update_from(other, k)
     # critic= a torch module with the same weights: rewards within the fold's bound of the device path
-    L2 = hn._learner(H, A, "reference", blob, max_batch=k)
+    L2 = lh.learner(H, A, "reference", blob, max_batch=k)
     net = _uav().ValueMLP(12, H).to(DEV)
     net.load_state_dict(L2.critic_state_dict())
     dev_ring = _new_ring(kind, 100, max_batch=k).with_lambda(lam, GAMMA)
     mod_ring = _new_ring(kind, 100, max_batch=k).with_lambda(lam, GAMMA)
     dev_ring.add_rollout(r["dev"]["obs_in"], out, critic=L2)
     mod_ring.add_rollout(r["dev"]["obs_in"], out, critic=net)
-    a, b = hn._image(dev_ring), hn._image(mod_ring)
+    a, b = rr.image(dev_ring), rr.image(mod_ring)
     for key in ("states", "actions", "next_states", "discounts", "priorities"):
         assert (a[key] is None and b[key] is None) or a[key][:NTR].tobytes() == b[key][:NTR].tobytes(), key
     V = L2.values(out["obs"]).cpu().numpy().astype(np.float64).reshape(T, B, N)
@@ -308,12 +304,12 @@ def test_values_add_and_update_captured_and_replayed_equal_eager():
     branches), captured once and replayed twice == the same three calls issued eagerly twice, bitwise.  The second
     iteration's values come from the critic the first one updated: parameters are read when the launch executes."""
     H, A, k = 64, 12, 32
-    r = hn._rollout()
-    out = hn._out(hn._done("mid"))
+    r = rr.rollout()
+    out = rr.out(rr.done("mid"))
     blob = dp.init_blob(H, A, 42)
 
     def fresh():
-        return hn._learner(H, A, "reference", blob, max_batch=k), \
+        return lh.learner(H, A, "reference", blob, max_batch=k), \
             _new_ring("prioritised", 100, max_batch=k).with_lambda(0.9, GAMMA)
 
     eager, re_ = fresh()
@@ -333,7 +329,7 @@ def test_values_add_and_update_captured_and_replayed_equal_eager():
             g_out = iteration(graphed, rg)
     torch.cuda.current_stream().wait_stream(s)
     torch.cuda.synchronize()
-    assert np.array_equal(hn._state(graphed)["step"], np.zeros(8))      # capture ran nothing
+    assert np.array_equal(lh.state(graphed)["step"], np.zeros(8))      # capture ran nothing
     rewards = []
     for c in range(2):
         e_out = iteration(eager, re_)
@@ -342,13 +338,13 @@ def test_values_add_and_update_captured_and_replayed_equal_eager():
         for x, y in zip(e_out, g_out):
             assert torch.equal(x, y) and torch.isfinite(x).all(), c
         assert np.array_equal(graphed._get_params(), eager._get_params()), c
-        a, b = hn._image(rg), hn._image(re_)
+        a, b = rr.image(rg), rr.image(re_)
         for key in a:                                                   # the written slots: the rest was never initialised
             assert a[key][:NTR].tobytes() == b[key][:NTR].tobytes(), key
         rewards.append(a["rewards"][:NTR].copy())
     assert not np.array_equal(rewards[0], rewards[1])                   # the replay evaluated the updated critic
-    hn._same(hn._state(graphed), hn._state(eager))
-    assert np.array_equal(hn._state(graphed)["step"], np.full(8, 2))
+    lh.same(lh.state(graphed), lh.state(eager))
+    assert np.array_equal(lh.state(graphed)["step"], np.full(8, 2))
     for x in (graphed, eager, re_, rg):
         x.check()
 
@@ -358,12 +354,12 @@ def test_values_add_and_update_captured_and_replayed_equal_eager():
 def test_host_side_errors_of_the_lambda_add_enqueue_nothing():
     from uavtrack import _lib
     lib = _lib.load()
-    r = hn._rollout()["dev"]
-    done = _dev(hn._done("mid"))
+    r = rr.rollout()["dev"]
+    done = lh.dev(rr.done("mid"))
     ring = _new_ring("prioritised", 100).with_lambda(0.9, GAMMA)
-    hn._prefill(ring, 10, 10)
+    rr.prefill(ring, 10, 10)
     torch.cuda.synchronize()
-    img = hn._image(ring)
+    img = rr.image(ring)
     p = _lib.ptr
     off = lambda t: C.c_void_p(t.data_ptr() + 4)                       # not 16-byte aligned
     vals = _values()[1]
@@ -399,19 +395,19 @@ def test_host_side_errors_of_the_lambda_add_enqueue_nothing():
         msg = lib.uavtrack_last_error().decode()
         assert msg.startswith("uavtrack_replay_add_rollout_lambda: ") and word.split(" =")[0] in msg, (word, msg)
     torch.cuda.synchronize()
-    hn._same_image(hn._image(ring), img)
+    rr.same_image(rr.image(ring), img)
     assert call() == 0                                                  # and the good call goes through
     torch.cuda.synchronize()
-    assert hn._image(ring)["rewards"].tobytes() != img["rewards"].tobytes()
+    assert rr.image(ring)["rewards"].tobytes() != img["rewards"].tobytes()
 
 
 def test_host_side_errors_of_values_enqueue_nothing():
     from uavtrack import _lib
     H, A, n = 64, 5, 63
-    L = hn._learner(H, A, "reference", dp.init_blob(H, A, 1), max_batch=n)
+    L = lh.learner(H, A, "reference", dp.init_blob(H, A, 1), max_batch=n)
     x, xd, _ = _value_rows(n)
     out = torch.full((n,), 7.0, device=DEV)
-    before = hn._state(L)
+    before = lh.state(L)
     p = _lib.ptr
 
     def call(h=L._h, n_=n, rows=p(xd), values=p(out)):
@@ -424,7 +420,7 @@ def test_host_side_errors_of_values_enqueue_nothing():
         msg = L._lib.uavtrack_last_error().decode()
         assert msg.startswith("uavtrack_learner_values: ") and word.split(" =")[0] in msg, (word, msg)
     L.check()
-    hn._same(hn._state(L), before)
+    lh.same(lh.state(L), before)
     assert (out == 7.0).all()
     assert call() == 0
     L.check()

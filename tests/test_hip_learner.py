@@ -1,30 +1,23 @@
 """The device learner (uavtrack_learner_*, uavtrack.DeviceActorCritic) on the MI355X: against the reference's recorded
 fp32 updates, against the float64 mirror (tests/learner_mirror.py) and a float64 torch.optim.Adam run; determinism,
 graph capture, interop with ActorMLP / BatchedUavEnv / the reference's checkpoint format, and refused inputs."""
-import os
-
 import numpy as np
 import pytest
 import torch
 
 from conftest import load_golden
+import learner_dp_mirror as dp
+import learner_harness as lh
 import learner_mirror as mirror
 
 pytestmark = pytest.mark.gpu
 
-DEV = "cuda:0"
+DEV = lh.DEV
 
 
 def _uav():
     import uavtrack
     return uavtrack
-
-
-def _learner(H, A, loss="reference", lr=(1e-3, 5e-3), gamma=0.95, blob=None, max_batch=0):
-    L = _uav().DeviceActorCritic(12, H, A, lr[0], lr[1], gamma, DEV, loss=loss, max_batch=max_batch)
-    if blob is not None:
-        L._set_params(np.ascontiguousarray(blob, np.float32))
-    return L
 
 
 def _store(z):
@@ -43,7 +36,7 @@ def _opt(L):
 def test_golden_reference_updates(case):
     z, meta = load_golden("f5_actor_critic_update")
     H, A, cap = meta["cases"][case]["hidden"], meta["A"], meta["capacity"]
-    L = _learner(H, A, lr=(meta["actor_lr"], meta["critic_lr"]), gamma=meta["gamma"], blob=z[f"{case}_w0"])
+    L = lh.learner(H, A, lr=(meta["actor_lr"], meta["critic_lr"]), gamma=meta["gamma"], blob=z[f"{case}_w0"])
     store = _store(z)
     prio = torch.from_numpy(z["prio_before"]).to(DEV) if case == "h128" else None
     for u in range(5):
@@ -62,66 +55,23 @@ def test_golden_reference_updates(case):
     L.check()
 
 
-def _batch(rng, cap, A):
-    s = rng.uniform(-1, 1, size=(cap, 12)).astype(np.float32)
-    s2 = rng.uniform(-1, 1, size=(cap, 12)).astype(np.float32)
-    s[:, 9:11] = rng.uniform(0, 5, size=(cap, 2)); s2[:, 9:11] = rng.uniform(0, 5, size=(cap, 2))
-    a = rng.randint(0, A, size=cap).astype(np.int32)
-    r = rng.uniform(-2, 2, size=cap).astype(np.float32)
-    return s, a, r, s2
-
-
-def _init_blob(H, A, seed):
-    torch.manual_seed(seed)
-    u = _uav()
-    return np.concatenate([p.detach().numpy().ravel() for p in
-                           list(u.ActorMLP(12, H, A).parameters()) + list(u.ValueMLP(12, H).parameters())]).astype(np.float32)
-
-
-SWEEP = [(H, A, n, loss, gather)
-         for k, (H, n) in enumerate([(1, 1), (33, 2), (64, 63), (128, 65), (200, 4096), (256, 65537),
-                                     (33, 65537), (128, 4096), (256, 63), (1, 65), (200, 2), (64, 1)])
-         for A in ([9, 12, 48][k % 3],)
-         for loss, gather in ((("reference", True),) if k % 2 == 0 else (("per_sample", False),)) +
-         ((("per_sample", True),) if k % 4 == 1 else ()) + ((("reference", False),) if k % 4 == 0 else ())]
-
-
-@pytest.mark.parametrize("H,A,n,loss,gather", SWEEP)
+@pytest.mark.parametrize("H,A,n,loss,gather", lh.SWEEP)
 def test_sweep_against_fp64_mirror(H, A, n, loss, gather):
-    """One update against the float64 mirror.  Tolerances: losses and td_delta 2e-5 relative to their magnitude
-    scale; the gradient (exp_avg / 0.1 after one step) within 2e-6 * (1 + log2 n) of its largest element; the
-    parameters within 1e-3 * lr, except where the fp64 gradient is within the gradient's rounding of 0 (then Adam's
-    first step, lr * g / (|g| + eps), may take either sign: within 2 lr)."""
+    """One update against the float64 mirror, at the bounds tests/learner_harness.py states and explains."""
     rng = np.random.RandomState(H * 1000 + n)
     cap = n + 7 if gather else n
-    s, a, r, s2 = _batch(rng, cap, A)
+    s, a, r, s2 = dp.batch(rng, cap, A)
     idx = rng.randint(0, cap, size=n).astype(np.int64) if gather else np.arange(n)
-    blob = _init_blob(H, A, H + n)
-    lr = (1e-3, 5e-3)
-    L = _learner(H, A, loss=loss, lr=lr, blob=blob, max_batch=max(n, 1))
+    blob = dp.init_blob(H, A, H + n)
+    L = lh.learner(H, A, loss=loss, blob=blob, max_batch=max(n, 1))
     store = {"states": torch.from_numpy(s).to(DEV), "actions": torch.from_numpy(a).to(DEV),
              "rewards": torch.from_numpy(r).to(DEV), "next_states": torch.from_numpy(s2).to(DEV)}
     it = torch.from_numpy(idx).to(DEV) if gather else None
     al, cl, td = L._run(n, store, cap, it, None)
     L.check()
     ral, rcl, rtd, g = mirror.losses_and_grads(blob, H, A, s[idx], a[idx], r[idx], s2[idx], 0.95, loss)
-    tds = np.abs(rtd).max() + 1e-6
-    np.testing.assert_allclose(td.cpu().numpy(), rtd, rtol=0, atol=2e-5 * tds)
-    assert abs(float(cl) - rcl) <= 2e-5 * (np.mean(rtd ** 2) + 1e-12) + 1e-12
-    nlp_scale = abs(ral) + np.mean(np.abs(rtd)) * 30
-    assert abs(float(al) - ral) <= 2e-5 * nlp_scale
-    m, v, st = _opt(L)
-    gd = m / 0.1
-    gmax = np.abs(g).max()
-    tol_g = 2e-6 * (1 + np.log2(n)) * gmax
-    assert np.abs(gd - g).max() <= tol_g + 1e-30, (np.abs(gd - g).max(), tol_g)
-    p = L._get_params()
-    p64 = mirror.adam(blob.astype(np.float64), np.zeros(g.size), np.zeros(g.size), np.ones(8, np.int64), g, lr, H, A)[0]
-    lr_of = np.concatenate([np.full(k, lr[0] if t < 4 else lr[1]) for t, k in enumerate(mirror.layout(H, A)[0])])
-    near0 = np.abs(g) <= 4 * tol_g + 1e-8
-    err = np.abs(p - p64)
-    assert (err[~near0] <= 1e-3 * lr_of[~near0] + 1e-6 * np.abs(p64[~near0])).all(), err[~near0].max()
-    assert (err[near0] <= 2 * lr_of[near0] + 1e-6).all()
+    lh.assert_losses_and_td(al.cpu().numpy(), cl.cpu().numpy(), td.cpu().numpy(), ral, rcl, rtd)
+    lh.assert_step_from_zero(lh.state(L), blob, g, n, H, A)
 
 
 def test_trajectory_tracks_fp64_torch_adam():
@@ -131,8 +81,8 @@ def test_trajectory_tracks_fp64_torch_adam():
     u = _uav()
     H, A, n, lr = 64, 12, 4096, (1e-3, 5e-3)
     rng = np.random.RandomState(3)
-    blob = _init_blob(H, A, 5)
-    L = _learner(H, A, lr=lr, blob=blob)
+    blob = dp.init_blob(H, A, 5)
+    L = lh.learner(H, A, lr=lr, blob=blob)
     actor, critic = u.ActorMLP(12, H, A).double(), u.ValueMLP(12, H).double()
     params = list(actor.parameters()) + list(critic.parameters())
     o = 0
@@ -141,7 +91,7 @@ def test_trajectory_tracks_fp64_torch_adam():
             p.copy_(torch.from_numpy(blob[o:o + p.numel()].astype(np.float64)).view_as(p)); o += p.numel()
     oa, oc = torch.optim.Adam(actor.parameters(), lr=lr[0]), torch.optim.Adam(critic.parameters(), lr=lr[1])
     for _ in range(50):
-        s, a, r, s2 = _batch(rng, n, A)
+        s, a, r, s2 = dp.batch(rng, n, A)
         L.update({"states": torch.from_numpy(s).to(DEV), "actions": torch.from_numpy(a).to(DEV),
                   "rewards": torch.from_numpy(r).to(DEV), "next_states": torch.from_numpy(s2).to(DEV)})
         S, S2, R = (torch.from_numpy(x.astype(np.float64)) for x in (s, s2, r))
@@ -162,18 +112,18 @@ def test_trajectory_tracks_fp64_torch_adam():
 def _setup_det(H=128, A=12, n=4096, seed=9):
     rng = np.random.RandomState(seed)
     cap = n + 100
-    s, a, r, s2 = _batch(rng, cap, A)
+    s, a, r, s2 = dp.batch(rng, cap, A)
     store = {"states": torch.from_numpy(s).to(DEV), "actions": torch.from_numpy(a).to(DEV),
              "rewards": torch.from_numpy(r).to(DEV), "next_states": torch.from_numpy(s2).to(DEV)}
     idx = torch.from_numpy(rng.randint(0, cap, size=(3, n)).astype(np.int64)).to(DEV)
-    return store, idx, cap, _init_blob(H, A, seed)
+    return store, idx, cap, dp.init_blob(H, A, seed)
 
 
 def test_determinism_bitwise():
     store, idx, cap, blob = _setup_det()
     outs = []
     for _ in range(2):
-        L = _learner(128, 12, blob=blob)
+        L = lh.learner(128, 12, blob=blob)
         res = [L._run(idx.shape[1], store, cap, idx[k], None) for k in range(3)]
         L.check()
         outs.append((L._get_params(), _opt(L), [tuple(t.cpu().numpy() for t in r) for r in res]))
@@ -189,9 +139,9 @@ def test_graph_capture_replay_matches_eager():
     store, idx, cap, blob = _setup_det(seed=10)
     prio_e = torch.rand(cap, device=DEV)
     prio_g = prio_e.clone()
-    eager = _learner(128, 12, blob=blob)
+    eager = lh.learner(128, 12, blob=blob)
     e_out = [eager._run(idx.shape[1], store, cap, idx[k], prio_e) for k in range(3)]
-    graphed = _learner(128, 12, blob=blob)
+    graphed = lh.learner(128, 12, blob=blob)
     torch.cuda.synchronize()
     s = torch.cuda.Stream(DEV)
     s.wait_stream(torch.cuda.current_stream())
@@ -219,7 +169,7 @@ def test_graph_capture_replay_matches_eager():
 def test_interop_actor_env_and_checkpoints(tmp_path):
     u = _uav()
     store, idx, cap, blob = _setup_det(H=128, A=12, seed=11)
-    L = _learner(128, 12, blob=blob)
+    L = lh.learner(128, 12, blob=blob)
     for k in range(3):
         L._run(idx.shape[1], store, cap, idx[k], None)
     L.check()
@@ -253,13 +203,13 @@ def test_interop_actor_env_and_checkpoints(tmp_path):
     ckc = torch.load(str(pc))
     critic.load_state_dict(ckc["model_state_dict"])
     torch.optim.Adam(critic.parameters(), lr=5e-3).load_state_dict(ckc["optimizer_state_dict"])
-    L2 = _learner(128, 12)
+    L2 = lh.learner(128, 12)
     L2.load(str(pa), str(pc))
     assert np.array_equal(L2._get_params(), L._get_params())
     for x1, x2 in zip(_opt(L2), _opt(L)):
         assert np.array_equal(x1, x2)
     sd_all = L.state_dict()
-    L3 = _learner(128, 12)
+    L3 = lh.learner(128, 12)
     L3.load_state_dict(sd_all)
     assert np.array_equal(L3._get_params(), L._get_params())
 
@@ -268,7 +218,7 @@ def test_refused_inputs_leave_the_learner_unchanged():
     import ctypes as C
     from uavtrack import _lib
     store, idx, cap, blob = _setup_det(H=64, A=12, n=1000, seed=12)
-    L = _learner(64, 12, blob=blob, max_batch=1000)
+    L = lh.learner(64, 12, blob=blob, max_batch=1000)
     L._run(1000, store, cap, idx[0], None)
     L.check()
     before = (L._get_params(), _opt(L))
@@ -306,9 +256,9 @@ def test_refused_inputs_leave_the_learner_unchanged():
     # hidden out of range: create refuses
     for H in (0, 257):
         with pytest.raises(RuntimeError, match="hidden"):
-            _learner(H, 12)
+            lh.learner(H, 12)
     with pytest.raises(RuntimeError, match="n_actions"):
-        _learner(64, 49)
+        lh.learner(64, 49)
     # a failing set leaves the previous state in place
     with pytest.raises(RuntimeError):
         L._set_params(np.zeros(5, np.float32))
@@ -335,11 +285,11 @@ def test_refused_inputs_leave_the_learner_unchanged():
 def test_update_from_prioritized_buffer_writes_priorities():
     u = _uav()
     rng = np.random.RandomState(13)
-    s, a, r, s2 = _batch(rng, 3000, 12)
+    s, a, r, s2 = dp.batch(rng, 3000, 12)
     buf = u.PrioritizedDeviceReplayBuffer(4000, DEV)
     buf.add({"states": torch.from_numpy(s), "actions": torch.from_numpy(a), "rewards": torch.from_numpy(r),
              "next_states": torch.from_numpy(s2)})
-    L = _learner(64, 12, blob=_init_blob(64, 12, 1))
+    L = lh.learner(64, 12, blob=dp.init_blob(64, 12, 1))
     gen = torch.Generator(device=DEV); gen.manual_seed(4)
     p0 = buf.priorities.clone()
     al, cl, td = L.update_from(buf, 2048, generator=gen)

@@ -17,12 +17,12 @@ import torch
 
 import learner_dp_mirror as dp
 import learner_dp_worker as worker
+import learner_harness as lh
 import learner_mirror as mirror
-from test_hip_learner import SWEEP
 
 pytestmark = pytest.mark.gpu
 
-DEV = "cuda:0"
+DEV = lh.DEV
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
@@ -31,27 +31,8 @@ def _uav():
     return uavtrack
 
 
-def _learner(H, A, loss="reference", lr=(1e-3, 5e-3), gamma=0.95, blob=None, max_batch=0):
-    L = _uav().DeviceActorCritic(12, H, A, lr[0], lr[1], gamma, DEV, loss=loss, max_batch=max_batch)
-    if blob is not None:
-        L._set_params(np.ascontiguousarray(blob, np.float32))
-    return L
-
-
-def _state(L):
-    m, v, st = L._optim_state()
-    return {"params": L._get_params(), "exp_avg": m, "exp_avg_sq": v, "step": st}
-
-
-def _same(x, y, what=""):
-    assert x.keys() == y.keys()
-    for k in x:
-        assert np.array_equal(x[k], y[k], equal_nan=True), (what, k)
-
-
 def _store(s, a, r, s2):
-    return {"states": torch.from_numpy(np.ascontiguousarray(s)).to(DEV), "actions": torch.from_numpy(np.ascontiguousarray(a)).to(DEV),
-            "rewards": torch.from_numpy(np.ascontiguousarray(r)).to(DEV), "next_states": torch.from_numpy(np.ascontiguousarray(s2)).to(DEV)}
+    return {k: lh.dev(x) for k, x in zip(lh.STORES, (s, a, r, s2))}
 
 
 def _prio_target(prio, cap):
@@ -64,7 +45,7 @@ def _prio_target(prio, cap):
 # test_sweep_against_fp64_mirror's grid at H 64 / 128 / 200 / 256: n = 1 and 63 below one tile (H 64: 64 rows), 65 and 63
 # not a multiple of it (H 128: 32, H 256: 16), 65537 rows at H 256 needing all 256 workgroups (4097 tiles), A 9 / 12 /
 # 48, both losses, with and without an index vector (drawn with replacement: repeated slots)
-GRID = [c for c in SWEEP if c[0] in (64, 128, 200, 256)]
+GRID = [c for c in lh.SWEEP if c[0] in (64, 128, 200, 256)]
 
 
 def test_grid_covers_what_it_must():
@@ -81,7 +62,7 @@ def test_one_row_is_the_closed_update(H, A, n, loss, gather):
     cap = n + 7 if gather else n
     store = _store(*dp.batch(rng, cap, A))
     blob = dp.init_blob(H, A, H + n)
-    closed, split = (_learner(H, A, loss=loss, blob=blob, max_batch=n) for _ in range(2))
+    closed, split = (lh.learner(H, A, loss=loss, blob=blob, max_batch=n) for _ in range(2))
     prio_c = torch.from_numpy(rng.uniform(0.1, 2, cap).astype(np.float32)).to(DEV)
     prio_s = prio_c.clone()
     for u in range(3):
@@ -97,8 +78,8 @@ def test_one_row_is_the_closed_update(H, A, n, loss, gather):
         tail = row[-8:].view(torch.int32).cpu().numpy()
         assert tail[4] == n and tail[5] == 0 and tail[6] == 0 and tail[7] == closed.num_params
     closed.check(); split.check()
-    _same(_state(closed), _state(split))
-    assert np.array_equal(_state(split)["step"], np.full(8, 3))
+    lh.same(lh.state(closed), lh.state(split))
+    assert np.array_equal(lh.state(split)["step"], np.full(8, 3))
 
 
 # ---- 2, 3. K rows: data parallelism and accumulation ---------------------------------------------------------------
@@ -113,7 +94,7 @@ def _k_handles(K):
     """The shared batch cut K ways, one grad per shard on K handles that start equal, every handle applies all rows."""
     c, blob, b = _teeth()
     shards = dp.split(b, dp.cuts(c["n"], K))
-    Ls = [_learner(c["H"], c["A"], lr=c["lrs"], gamma=c["gamma"], blob=blob, max_batch=c["n"]) for _ in range(K)]
+    Ls = [lh.learner(c["H"], c["A"], lr=c["lrs"], gamma=c["gamma"], blob=blob, max_batch=c["n"]) for _ in range(K)]
     rows = Ls[0].new_rows(K)
     tds = []
     for k, (L, sh) in enumerate(zip(Ls, shards)):
@@ -121,46 +102,25 @@ def _k_handles(K):
     losses = [L.apply(rows) for L in Ls]
     for L in Ls:
         L.check()
-    out = [dict(_state(L), actor_loss=al.cpu().numpy(), critic_loss=cl.cpu().numpy()) for L, (al, cl) in zip(Ls, losses)]
+    out = [dict(lh.state(L), actor_loss=al.cpu().numpy(), critic_loss=cl.cpu().numpy()) for L, (al, cl) in zip(Ls, losses)]
     return out, torch.cat(tds).cpu().numpy()
 
 
 @pytest.mark.parametrize("K", [2, 3, 8])
 def test_k_rows_same_bits_everywhere_and_inside_the_single_update_bounds(K):
     """All K handles bitwise equal; against the fp64 mirror on the WHOLE batch within the bounds
-    tests/test_hip_learner.py::test_sweep_against_fp64_mirror applies to a single update (copied, not widened)."""
+    tests/learner_harness.py applies to a single update."""
     c, blob, (s, a, r, s2) = _teeth()
     H, A, n, lr = c["H"], c["A"], c["n"], c["lrs"]
     out, td = _k_handles(K)
     for o in out[1:]:
-        _same(out[0], o)
+        lh.same(out[0], o)
     ral, rcl, rtd, g = mirror.losses_and_grads(blob, H, A, s, a, r, s2, c["gamma"], "reference")
-    al, cl = float(out[0]["actor_loss"]), float(out[0]["critic_loss"])
-    tds = np.abs(rtd).max() + 1e-6
-    print(f"K={K}: |td - td64| max {np.abs(td - rtd).max():.3e} (bound {2e-5 * tds:.3e})")
-    np.testing.assert_allclose(td, rtd, rtol=0, atol=2e-5 * tds)
-    print(f"K={K}: critic loss err {abs(cl - rcl):.3e} (bound {2e-5 * (np.mean(rtd ** 2) + 1e-12) + 1e-12:.3e})")
-    assert abs(cl - rcl) <= 2e-5 * (np.mean(rtd ** 2) + 1e-12) + 1e-12
-    nlp_scale = abs(ral) + np.mean(np.abs(rtd)) * 30
-    print(f"K={K}: actor loss err {abs(al - ral):.3e} (bound {2e-5 * nlp_scale:.3e})")
-    assert abs(al - ral) <= 2e-5 * nlp_scale
-    gd = out[0]["exp_avg"] / 0.1
-    gmax = np.abs(g).max()
-    tol_g = 2e-6 * (1 + np.log2(n)) * gmax
-    assert tol_g == dp.gpu_gradient_tolerance(n, gmax)
-    print(f"K={K}: gradient err {np.abs(gd - g).max():.3e} (bound {tol_g:.3e})")
-    assert np.abs(gd - g).max() <= tol_g + 1e-30, (np.abs(gd - g).max(), tol_g)
-    p = out[0]["params"]
-    p64 = mirror.adam(blob.astype(np.float64), np.zeros(g.size), np.zeros(g.size), np.ones(8, np.int64), g, lr, H, A)[0]
-    lr_of = np.concatenate([np.full(k, lr[0] if t < 4 else lr[1]) for t, k in enumerate(mirror.layout(H, A)[0])])
-    near0 = np.abs(g) <= 4 * tol_g + 1e-8
-    err = np.abs(p - p64)
-    print(f"K={K}: parameter err {err[~near0].max():.3e} away from g = 0, {err[near0].max() if near0.any() else 0:.3e} near it")
-    assert (err[~near0] <= 1e-3 * lr_of[~near0] + 1e-6 * np.abs(p64[~near0])).all(), err[~near0].max()
-    assert (err[near0] <= 2 * lr_of[near0] + 1e-6).all()
+    lh.assert_losses_and_td(out[0]["actor_loss"], out[0]["critic_loss"], td, ral, rcl, rtd)
+    lh.assert_step_from_zero(out[0], blob, g, n, H, A, lr=lr)
     # and the rule it must not be: the averaged per-shard gradients are far outside the same bound
     naive = dp.averaged_shard_gradients(blob, H, A, dp.split((s, a, r, s2), dp.cuts(n, K)), c["gamma"])
-    assert np.abs(gd - naive).max() > 50 * tol_g
+    assert np.abs(out[0]["exp_avg"] / 0.1 - naive).max() > 50 * lh.tol_g(n, g)
 
 
 @pytest.mark.parametrize("K", [2, 3, 8])
@@ -171,12 +131,12 @@ def test_accumulation_on_one_handle_and_update_from_many(K):
     c, blob, b = _teeth()
     shards = dp.split(b, dp.cuts(c["n"], K))
     want, want_td = _k_handles(K)
-    L = _learner(c["H"], c["A"], lr=c["lrs"], gamma=c["gamma"], blob=blob, max_batch=c["n"])
+    L = lh.learner(c["H"], c["A"], lr=c["lrs"], gamma=c["gamma"], blob=blob, max_batch=c["n"])
     rows = L.new_rows(K)
     tds = [L._grad(len(sh[1]), _store(*sh), len(sh[1]), None, rows[k])[1] for k, sh in enumerate(shards)]
     al, cl = L.apply(rows)
     L.check()
-    _same(dict(_state(L), actor_loss=al.cpu().numpy(), critic_loss=cl.cpu().numpy()), want[0])
+    lh.same(dict(lh.state(L), actor_loss=al.cpu().numpy(), critic_loss=cl.cpu().numpy()), want[0])
     assert np.array_equal(torch.cat(tds).cpu().numpy(), want_td)
 
     def rings():
@@ -188,7 +148,7 @@ def test_accumulation_on_one_handle_and_update_from_many(K):
                 np.random.RandomState(k).uniform(0.1, 2.0, len(sh[1])).astype(np.float32)).to(DEV)
             out.append(ring)
         return out
-    many, explicit = (_learner(c["H"], c["A"], lr=c["lrs"], gamma=c["gamma"], blob=blob, max_batch=4096) for _ in range(2))
+    many, explicit = (lh.learner(c["H"], c["A"], lr=c["lrs"], gamma=c["gamma"], blob=blob, max_batch=4096) for _ in range(2))
     ra, rb = rings(), rings()
     for u in range(2):
         before = [ring.priorities.cpu().numpy() for ring in ra]
@@ -207,7 +167,7 @@ def test_accumulation_on_one_handle_and_update_from_many(K):
     many.check(); explicit.check()
     for ring in ra + rb:
         ring.check()
-    _same(_state(many), _state(explicit))
+    lh.same(lh.state(many), lh.state(explicit))
 
 
 # ---- 4. refusal is global --------------------------------------------------------------------------------------------
@@ -219,11 +179,11 @@ def test_refusal_is_global():
     shards = dp.split(b, dp.cuts(c["n"], K))
     stores = [_store(*sh) for sh in shards]
     ns = [len(sh[1]) for sh in shards]
-    Ls = [_learner(H, A, blob=blob, max_batch=c["n"]) for _ in range(K)]
-    twins = [_learner(H, A, blob=blob, max_batch=c["n"]) for _ in range(K)]
+    Ls = [lh.learner(H, A, blob=blob, max_batch=c["n"]) for _ in range(K)]
+    twins = [lh.learner(H, A, blob=blob, max_batch=c["n"]) for _ in range(K)]
     prios = [torch.rand(n, device=DEV) + 0.1 for n in ns]
     prio0 = [p.clone() for p in prios]
-    before = [_state(L) for L in Ls]
+    before = [lh.state(L) for L in Ls]
 
     def round_(learners, sts, prio):
         rows = learners[0].new_rows(K)
@@ -244,7 +204,7 @@ def test_refusal_is_global():
         with pytest.raises(RuntimeError, match="1 update"):
             L.check()
         L.check()                                                         # the count restarts
-        _same(_state(L), before[k], "refused")
+        lh.same(lh.state(L), before[k], "refused")
         assert torch.equal(prios[k], prio0[k])
     # the next clean update succeeds and matches twins that never saw the bad one
     _, losses = round_(Ls, stores, prios)
@@ -252,24 +212,24 @@ def test_refusal_is_global():
     _, tlosses = round_(twins, stores, tprios)
     for k in range(K):
         Ls[k].check(); twins[k].check()
-        _same(_state(Ls[k]), _state(twins[k]), "after")
+        lh.same(lh.state(Ls[k]), lh.state(twins[k]), "after")
         assert torch.equal(losses[k][0], tlosses[k][0]) and torch.isfinite(losses[k][0])
         assert torch.equal(prios[k], tprios[k]) and not torch.equal(prios[k], prio0[k])
     # a row of a learner of another width: its words do not carry this layout's tag
-    other = _learner(64, A, blob=dp.init_blob(64, A, 1), max_batch=c["n"])
+    other = lh.learner(64, A, blob=dp.init_blob(64, A, 1), max_batch=c["n"])
     foreign, _ = other._grad(ns[0], stores[0], ns[0], None)
     other.check()
     L = Ls[0]
     rows = L.new_rows(2).zero_()
     good, td = L._grad(ns[0], stores[0], ns[0], None, rows[0])
     rows[1, :foreign.numel()] = foreign
-    state0, p0 = _state(L), prios[0].clone()
+    state0, p0 = lh.state(L), prios[0].clone()
     al, cl = L.apply(rows)
     L.write_priorities(_prio_target(prios[0], ns[0]), None, td)
     assert torch.isnan(al) and torch.isnan(cl)
     with pytest.raises(RuntimeError, match="1 update"):
         L.check()
-    _same(_state(L), state0, "foreign")
+    lh.same(lh.state(L), state0, "foreign")
     assert torch.equal(prios[0], p0)
     with pytest.raises(ValueError, match="rows must be"):
         L.apply(foreign)                                                  # the Python layer refuses the shape outright
@@ -283,11 +243,11 @@ def test_host_side_errors_enqueue_nothing():
     H, A, n = 64, 12, 500
     rng = np.random.RandomState(2)
     store = _store(*dp.batch(rng, n, A))
-    L = _learner(H, A, blob=dp.init_blob(H, A, 2), max_batch=n)
+    L = lh.learner(H, A, blob=dp.init_blob(H, A, 2), max_batch=n)
     row, td = L._grad(n, store, n, None)
     L.apply(row)
     L.check()
-    before = _state(L)
+    before = lh.state(L)
     p = lambda t: None if t is None else C.c_void_p(t.data_ptr())
     out = torch.full((2,), 7.0, device=DEV)
     row0, td0 = row.clone(), td.clone()
@@ -319,7 +279,7 @@ def test_host_side_errors_enqueue_nothing():
     with pytest.raises(ValueError, match="1 to 64"):
         L.update_from_many([], 10)
     L.check()                                                             # nothing ran, so nothing was refused either
-    _same(_state(L), before)
+    lh.same(lh.state(L), before)
     assert torch.equal(row, row0) and torch.equal(td, td0) and torch.equal(prio, prio0)
     assert torch.equal(out, torch.full((2,), 7.0, device=DEV))
     rf = C.c_int64()
@@ -348,9 +308,9 @@ def test_graph_capture_of_the_split_chain():
         al, cl = L.apply(row)
         L.write_priorities(r, idx, td)
         return al, cl, td
-    eager, re_ = _learner(H, A, blob=blob, max_batch=k), ring()
+    eager, re_ = lh.learner(H, A, blob=blob, max_batch=k), ring()
     e_out = [tuple(t.clone() for t in round_(eager, re_)) for _ in range(3)]
-    graphed, rg = _learner(H, A, blob=blob, max_batch=k), ring()
+    graphed, rg = lh.learner(H, A, blob=blob, max_batch=k), ring()
     torch.cuda.synchronize()
     s = torch.cuda.Stream(DEV)
     s.wait_stream(torch.cuda.current_stream())
@@ -360,15 +320,15 @@ def test_graph_capture_of_the_split_chain():
             g_out = round_(graphed, rg)
     torch.cuda.current_stream().wait_stream(s)
     torch.cuda.synchronize()
-    assert np.array_equal(_state(graphed)["step"], np.zeros(8))           # capture ran nothing
+    assert np.array_equal(lh.state(graphed)["step"], np.zeros(8))           # capture ran nothing
     for u in range(3):
         g.replay()
         torch.cuda.synchronize()
         for x, y in zip(e_out[u], g_out):
             assert torch.equal(x, y), u
-    assert np.array_equal(_state(graphed)["step"], np.full(8, 3))
+    assert np.array_equal(lh.state(graphed)["step"], np.full(8, 3))
     assert len({float(o[0]) for o in e_out}) == 3                         # three different draws
-    _same(_state(graphed), _state(eager))
+    lh.same(lh.state(graphed), lh.state(eager))
     assert torch.equal(re_.priorities, rg.priorities)
     graphed.check(); eager.check(); re_.check(); rg.check()
 

@@ -4,26 +4,25 @@ entropy bonus and the gradient-norm clip against the float64 mirror (tests/learn
 test_sweep_against_fp64_mirror's bounds; the edges of the softmax; weights; the split form and the shared tail;
 determinism and graph capture; refusals.
 
-Shapes are corners of test_hip_learner.SWEEP: H in {1, 33, 128, 256}, A in {2, 12, 48}, n in {1, 63, 65, 4096}, and
+Shapes are corners of learner_harness.SWEEP: H in {1, 33, 128, 256}, A in {2, 12, 48}, n in {1, 63, 65, 4096}, and
 n = 4113 at H = 256 (16 rows per tile: 258 tiles for 256 workgroups, so workgroups loop)."""
 import os
 import sys
-import types
 
 import numpy as np
 import pytest
 import torch
 
 import learner_dp_mirror as dp
+import learner_harness as lh
 import learner_mirror as mirror
 import learner_regularised_mirror as rm
 import learner_weighted_mirror as wm
 
 pytestmark = pytest.mark.gpu
 
-DEV = "cuda:0"
-LR = (1e-3, 5e-3)
-GAMMA = 0.95
+DEV = lh.DEV
+GAMMA = lh.GAMMA
 INF = float("inf")
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -38,53 +37,6 @@ def _uav():
     return uavtrack
 
 
-def _learner(H, A, loss, blob, max_batch, c=0.0, mgn=None, diag=False):
-    L = _uav().DeviceActorCritic(12, H, A, LR[0], LR[1], GAMMA, DEV, loss=loss, max_batch=max_batch, entropy_coef=c,
-                                 max_grad_norm=mgn)
-    L._set_params(np.ascontiguousarray(blob, np.float32))
-    if diag:
-        L.enable_diagnostics()
-    return L
-
-
-def _state(L):
-    m, v, st = L._optim_state()
-    return {"params": L._get_params(), "exp_avg": m, "exp_avg_sq": v, "step": st}
-
-
-def _same(a, b):
-    assert a.keys() == b.keys()
-    for k in a:
-        if a[k] is None or b[k] is None:
-            assert a[k] is None and b[k] is None, k
-        else:
-            assert np.array_equal(np.asarray(a[k]), np.asarray(b[k]), equal_nan=True), k
-
-
-def _dev(x):
-    return torch.from_numpy(np.ascontiguousarray(x)).to(DEV)
-
-
-_cache = {}
-
-
-def _case(H, A, n, gather):
-    """(blob, host batch over the store, device store, capacity, host indices, device indices or None), built once."""
-    key = (H, A, n, gather)
-    if key not in _cache:
-        rng = np.random.RandomState(H * 1000 + n + (7 if gather else 0))
-        cap = n + 7 if gather else n
-        b = dp.batch(rng, cap, A)
-        idx = rng.randint(0, cap, size=n).astype(np.int64) if gather else np.arange(n)
-        store = {k: _dev(x) for k, x in zip(("states", "actions", "rewards", "next_states"), b)}
-        _cache[key] = (dp.init_blob(H, A, H + n), b, store, cap, idx, _dev(idx) if gather else None)
-    return _cache[key]
-
-
-def _gathered(b, idx):
-    return tuple(x[idx] for x in b)
-
-
 def _weights(n, seed=0):
     return wm.make_weights(np.random.RandomState(n + 11 + seed), n)
 
@@ -96,64 +48,20 @@ def _mirror(H, A, n, gather, loss, c, weighted, blob=None):
     """The fp64 update of a case, computed once: (actor_loss, critic_loss, td, gradient, entropy)."""
     key = (H, A, n, gather, loss, c, weighted, None if blob is None else blob.tobytes())
     if key not in _mirror_cache:
-        blob0, b, _, _, idx, _ = _case(H, A, n, gather)
+        blob0, b, _, _, idx, _ = lh.case(H, A, n, gather)
         w = _weights(n) if weighted else None
-        _mirror_cache[key] = rm.losses_and_grads(blob0 if blob is None else blob, H, A, *_gathered(b, idx), GAMMA, loss,
+        _mirror_cache[key] = rm.losses_and_grads(blob0 if blob is None else blob, H, A, *lh.gathered(b, idx), GAMMA, loss,
                                                  w, np.float32(c))
     return _mirror_cache[key]
-
-
-def _tol_g(n, g):
-    """test_sweep_against_fp64_mirror's gradient bound."""
-    return 2e-6 * (1 + np.log2(n)) * np.abs(g).max()
-
-
-def _assert_losses_and_td(al, cl, td, ral, rcl, rtd, c, A):
-    """test_sweep_against_fp64_mirror's bounds; the actor-loss scale gains c log A, the size of the entropy term."""
-    tds = np.abs(rtd).max() + 1e-6
-    np.testing.assert_allclose(td, rtd, rtol=0, atol=2e-5 * tds)
-    assert abs(float(cl) - rcl) <= 2e-5 * (np.mean(rtd ** 2) + 1e-12) + 1e-12, (float(cl), rcl)
-    nlp_scale = abs(ral) + np.mean(np.abs(rtd)) * 30 + c * np.log(A)
-    print(f"actor loss error {abs(float(al) - ral):.3e} of bound {2e-5 * nlp_scale:.3e}")
-    assert abs(float(al) - ral) <= 2e-5 * nlp_scale, (float(al), ral)
-
-
-def _assert_step_from_zero(st, blob, g, n, H, A, coef=(1.0, 1.0)):
-    """test_sweep_against_fp64_mirror's bounds on the first Adam step from zero moments, g the fp64 gradient Adam should
-    have seen: exp_avg / 0.1 within the gradient bound (times the network's clip coefficient), the parameters within
-    1e-3 lr except where the gradient is within its rounding of 0 (then within 2 lr)."""
-    na = mirror.layout(H, A)[1][4]
-    cf = np.concatenate([np.full(na, coef[0]), np.full(g.size - na, coef[1])])
-    gd = st["exp_avg"] / 0.1
-    tol = _tol_g(n, g) * cf
-    err = np.abs(gd - g * cf)
-    print(f"gradient error {(err / np.maximum(tol, 1e-300)).max():.3f} of its bound")
-    assert (err <= tol + 1e-30).all(), (err / np.maximum(tol, 1e-300)).max()
-    p64 = mirror.adam(blob.astype(np.float64), np.zeros(g.size), np.zeros(g.size), np.ones(8, np.int64), g * cf, LR, H, A)[0]
-    lr_of = np.concatenate([np.full(k, LR[0] if t < 4 else LR[1]) for t, k in enumerate(mirror.layout(H, A)[0])])
-    near0 = np.abs(g * cf) <= 4 * tol + 1e-8
-    perr = np.abs(st["params"] - p64)
-    assert (perr[~near0] <= 1e-3 * lr_of[~near0] + 1e-6 * np.abs(p64[~near0])).all(), perr[~near0].max()
-    assert (perr[near0] <= 2 * lr_of[near0] + 1e-6).all()
 
 
 def _entropy_tol(A):
     return 1e-5 * max(1.0, np.log(A))
 
 
-def _update(L, n, store, cap, it, prio, w=None):
-    al, cl, td = L._run(n, store, cap, it, prio, w)
-    return dict(_state(L), actor_loss=al.cpu().numpy(), critic_loss=cl.cpu().numpy(), td=td.cpu().numpy(),
-                prio=None if prio is None else prio.cpu().numpy())
-
-
-def _split_update(L, n, store, cap, it, prio, w=None):
-    row, td = L._grad(n, store, cap, it, None, None, w)
-    al, cl = L.apply(row)
-    if prio is not None:
-        L.write_priorities(types.SimpleNamespace(priorities=prio, capacity=cap), it, td)
-    return dict(_state(L), actor_loss=al.cpu().numpy(), critic_loss=cl.cpu().numpy(), td=td.cpu().numpy(),
-                prio=None if prio is None else prio.cpu().numpy())
+def _bits(out):
+    """An update's result without the diagnostics: what a learner that has them installed shares with one that has not."""
+    return {k: v for k, v in out.items() if k not in ("entropy", "grad_norm")}
 
 
 # ---- 1. off is off -------------------------------------------------------------------------------------------------------
@@ -166,13 +74,13 @@ def test_off_is_off(H, A, n, gather, loss, weighted, diag):
     """set_regularisation(0, inf, inf), diagnostics installed or not: three consecutive updates, closed and as
     grad -> apply -> write_priorities, are an untouched learner's bit for bit (parameters, both moments, steps, losses,
     td_delta, priorities)."""
-    blob, b, store, cap, idx, it = _case(H, A, n, gather)
-    w = _dev(_weights(n)) if weighted else None
+    blob, b, store, cap, idx, it = lh.case(H, A, n, gather)
+    w = lh.dev(_weights(n)) if weighted else None
     prio0 = torch.rand(cap, device=DEV) + 0.1
-    for run in (_update, _split_update):
+    for run in (lh.update, lh.split_update):
         outs = []
         for touched in (False, True):
-            L = _learner(H, A, loss, blob, n, diag=diag and touched)
+            L = lh.learner(H, A, loss, blob, n, diag=diag and touched)
             if touched:
                 L.set_regularisation(0.0, (INF, INF))
                 assert L.get_regularisation() == (0.0, INF, INF)
@@ -180,13 +88,13 @@ def test_off_is_off(H, A, n, gather, loss, weighted, diag):
             outs.append([run(L, n, store, cap, it, prio, w) for _ in range(3)])
             L.check()
             if diag and touched:
-                ent = rm.policy(outs[-1][1]["params"], H, A, _gathered(b, idx)[0])[2]     # the policy of the third update
+                ent = rm.policy(outs[-1][1]["params"], H, A, lh.gathered(b, idx)[0])[2]     # the policy of the third update
                 assert np.abs(L.entropy(n).cpu().numpy() - ent).max() <= _entropy_tol(A)
                 assert torch.isnan(L.grad_norm).all()                                      # no clip, no norm
         assert np.isfinite(outs[0][2]["actor_loss"]) and np.array_equal(outs[0][2]["step"], np.full(8, 3))
         assert not np.array_equal(outs[0][2]["prio"], prio0.cpu().numpy())
         for x, y in zip(*outs):
-            _same(x, y)
+            lh.same(_bits(x), _bits(y))
 
 
 # ---- 2. the entropy gradient ---------------------------------------------------------------------------------------------
@@ -194,19 +102,19 @@ def test_off_is_off(H, A, n, gather, loss, weighted, diag):
 @pytest.mark.parametrize("c", [0.01, 1.0])
 @pytest.mark.parametrize("H,A,n,gather", SHAPES)
 def test_entropy_update_against_fp64_mirror(H, A, n, gather, c):
-    blob, b, store, cap, idx, it = _case(H, A, n, gather)
+    blob, b, store, cap, idx, it = lh.case(H, A, n, gather)
     weighted = (H + n) % 2 == 0
-    w = _dev(_weights(n)) if weighted else None
-    L = _learner(H, A, "per_sample", blob, n, c=c, diag=True)
-    out = _update(L, n, store, cap, it, None, w)
+    w = lh.dev(_weights(n)) if weighted else None
+    L = lh.learner(H, A, "per_sample", blob, n, c=c, diag=True)
+    out = lh.update(L, n, store, cap, it, None, w)
     L.check()
     ral, rcl, rtd, g, ent = _mirror(H, A, n, gather, "per_sample", c, weighted)
-    _assert_losses_and_td(out["actor_loss"], out["critic_loss"], out["td"], ral, rcl, rtd, c, A)
-    _assert_step_from_zero(out, blob, g, n, H, A)
+    lh.assert_losses_and_td(out["actor_loss"], out["critic_loss"], out["td"], ral, rcl, rtd, c, A)
+    lh.assert_step_from_zero(out, blob, g, n, H, A)
     assert np.abs(L.entropy(n).cpu().numpy() - ent).max() <= _entropy_tol(A)
     if c == 1.0 and A > 2 and n >= 63:       # the term is in the result: the plain gradient is far outside the bound
         g0 = _mirror(H, A, n, gather, "per_sample", 0.0, weighted)[3]
-        assert np.abs(out["exp_avg"] / 0.1 - g0).max() > 100 * _tol_g(n, g)
+        assert np.abs(out["exp_avg"] / 0.1 - g0).max() > 100 * lh.tol_g(n, g)
 
 
 # ---- 3. the edges of the softmax -----------------------------------------------------------------------------------------
@@ -225,21 +133,21 @@ def test_logits_spanning_more_than_250_stay_finite(H, A, n, gather):
     """fc2 with a ramp of 300 over its bias: every row's fp32 probabilities underflow to 0 somewhere, also at some rows'
     own action.  The row is finite and is the mirror's.  (The ramp sits in the bias, not in a scale on fc2.weight: a
     scale would also multiply the fp32 forward's rounding of the logits, which is not the softmax's doing.)"""
-    blob0, b, store, cap, idx, it = _case(H, A, n, gather)
+    blob0, b, store, cap, idx, it = lh.case(H, A, n, gather)
     blob = _with_fc2(blob0, H, A, 1.0, 300.0)
-    logp = rm.policy(blob, H, A, _gathered(b, idx)[0])[0]
+    logp = rm.policy(blob, H, A, lh.gathered(b, idx)[0])[0]
     assert (logp.max(axis=1) - logp.min(axis=1) > 250).all()
     assert (np.exp(logp.astype(np.float32)).min(axis=1) == 0).all()
-    assert (np.exp(logp[np.arange(n), _gathered(b, idx)[1]].astype(np.float32)) == 0).any()
+    assert (np.exp(logp[np.arange(n), lh.gathered(b, idx)[1]].astype(np.float32)) == 0).any()
     c = 1.0
-    L = _learner(H, A, "per_sample", blob, n, c=c, diag=True)
+    L = lh.learner(H, A, "per_sample", blob, n, c=c, diag=True)
     row, td = L._grad(n, store, cap, it)
     L.check()
     row = row.cpu().numpy()
     P = L.num_params
-    want = rm.shard_sums(blob, H, A, *_gathered(b, idx), GAMMA, "per_sample", None, np.float32(c))
+    want = rm.shard_sums(blob, H, A, *lh.gathered(b, idx), GAMMA, "per_sample", None, np.float32(c))
     assert np.isfinite(row[:P + 4]).all() and np.isfinite(want["g"]).all()
-    assert np.abs(row[:P] - want["g"]).max() <= _tol_g(n, want["g"])
+    assert np.abs(row[:P] - want["g"]).max() <= lh.tol_g(n, want["g"])
     for q in range(4):                                  # sums of n terms, each within 2e-5 of the loss scales above
         scale = [np.abs(want["loss"][0]), np.abs(want["td"]).sum(),
                  np.abs(want["loss"][2]) + np.abs(want["td"]).sum() * 30 + n * c * np.log(A), want["loss"][3]][q]
@@ -250,17 +158,17 @@ def test_logits_spanning_more_than_250_stay_finite(H, A, n, gather):
 
 @pytest.mark.parametrize("H,A,n,gather", [SHAPES[0], SHAPES[2], SHAPES[3]])
 def test_uniform_policy_has_entropy_log_a_and_no_entropy_gradient(H, A, n, gather):
-    blob0, b, store, cap, idx, it = _case(H, A, n, gather)
+    blob0, b, store, cap, idx, it = lh.case(H, A, n, gather)
     blob = _with_fc2(blob0, H, A, 0.0, 0.0)
     outs = []
     for c in (0.0, 1.0):
-        L = _learner(H, A, "per_sample", blob, n, c=c, diag=True)
-        outs.append(_update(L, n, store, cap, it, None))
+        L = lh.learner(H, A, "per_sample", blob, n, c=c, diag=True)
+        outs.append(lh.update(L, n, store, cap, it, None))
         L.check()
         assert np.abs(L.entropy(n).cpu().numpy() - np.log(A)).max() <= _entropy_tol(A)
     g = _mirror(H, A, n, gather, "per_sample", 1.0, False, blob)[3]
-    _assert_step_from_zero(outs[1], blob, g, n, H, A)
-    assert np.abs(outs[1]["exp_avg"] / 0.1 - outs[0]["exp_avg"] / 0.1).max() <= _tol_g(n, g)
+    lh.assert_step_from_zero(outs[1], blob, g, n, H, A)
+    assert np.abs(outs[1]["exp_avg"] / 0.1 - outs[0]["exp_avg"] / 0.1).max() <= lh.tol_g(n, g)
 
 
 # ---- 4. weights ----------------------------------------------------------------------------------------------------------
@@ -269,19 +177,19 @@ def test_uniform_policy_has_entropy_log_a_and_no_entropy_gradient(H, A, n, gathe
 def test_weights_with_settings_on(H, A, n, gather):
     """Entropy and clipping on: a vector of ones is no weights, bitwise; weights of 0.5 halve words [0, P + 4) of a row
     exactly; a NaN weight still refuses."""
-    blob, b, store, cap, idx, it = _case(H, A, n, gather)
+    blob, b, store, cap, idx, it = lh.case(H, A, n, gather)
     nr = rm.norms(_mirror(H, A, n, gather, "per_sample", 0.5, False)[3], H, A)
     mgn = (float(nr[0] / 4), float(nr[1] / 4))
     outs = []
     for w in (None, torch.ones(n, device=DEV)):
-        L = _learner(H, A, "per_sample", blob, n, c=0.5, mgn=mgn, diag=True)
-        outs.append(dict(_update(L, n, store, cap, it, None, w), ent=L.entropy(n).cpu().numpy(),
+        L = lh.learner(H, A, "per_sample", blob, n, c=0.5, mgn=mgn, diag=True)
+        outs.append(dict(lh.update(L, n, store, cap, it, None, w), ent=L.entropy(n).cpu().numpy(),
                          norm=L.grad_norm.cpu().numpy()))
         L.check()
-    _same(*outs)
+    lh.same(*outs)
     assert np.isfinite(outs[0]["norm"]).all() and np.array_equal(outs[0]["step"], np.ones(8))
     P = L.num_params
-    before = _state(L)
+    before = lh.state(L)
     row_u, td_u = L._grad(n, store, cap, it)
     row_h, td_h = L._grad(n, store, cap, it, None, None, torch.full((n,), 0.5, device=DEV))
     L.check()
@@ -294,7 +202,7 @@ def test_weights_with_settings_on(H, A, n, gather):
     w[n // 2] = float("nan")
     al, cl, _ = L._run(n, store, cap, it, None, w)
     assert torch.isnan(al) and torch.isnan(cl) and torch.isnan(L.grad_norm).all()
-    _same(_state(L), before)
+    lh.same(lh.state(L), before)
     with pytest.raises(RuntimeError, match="1 update"):
         L.check()
 
@@ -311,27 +219,27 @@ def _max_norms(nr, which):
 @pytest.mark.parametrize("loss", ["reference", "per_sample"])
 @pytest.mark.parametrize("H,A,n,gather", SMALL)
 def test_clip_against_fp64_mirror(H, A, n, gather, loss, which):
-    blob, b, store, cap, idx, it = _case(H, A, n, gather)
+    blob, b, store, cap, idx, it = lh.case(H, A, n, gather)
     c = 0.01 if loss == "per_sample" else 0.0
     weighted = loss == "reference"
-    w = _dev(_weights(n)) if weighted else None
+    w = lh.dev(_weights(n)) if weighted else None
     ral, rcl, rtd, g, ent = _mirror(H, A, n, gather, loss, c, weighted)
     nr = rm.norms(g, H, A)
     mgn = _max_norms(nr, which)
     assert all(max(m / x, x / m) >= 1.05 for m, x in zip(mgn, nr))          # the decision is far from its knife edge
     coef, _, _ = rm.clip(g, H, A, mgn)
     assert [x < 1 for x in coef] == [which in ("both", "actor"), which in ("both", "critic")]
-    L = _learner(H, A, loss, blob, n, c=c, mgn=tuple(float(x) for x in mgn), diag=True)
-    out = _update(L, n, store, cap, it, None, w)
+    L = lh.learner(H, A, loss, blob, n, c=c, mgn=tuple(float(x) for x in mgn), diag=True)
+    out = lh.update(L, n, store, cap, it, None, w)
     L.check()
-    _assert_losses_and_td(out["actor_loss"], out["critic_loss"], out["td"], ral, rcl, rtd, c, A)
-    _assert_step_from_zero(out, blob, g, n, H, A, coef)
+    lh.assert_losses_and_td(out["actor_loss"], out["critic_loss"], out["td"], ral, rcl, rtd, c, A)
+    lh.assert_step_from_zero(out, blob, g, n, H, A, coef)
     got = L.grad_norm.cpu().numpy()
     print("norms", got, nr)
-    assert (np.abs(got - nr) <= np.sqrt(g.size) * _tol_g(n, g)).all(), (got, nr)
+    assert (np.abs(got - nr) <= np.sqrt(g.size) * lh.tol_g(n, g)).all(), (got, nr)
     if which == "neither":                      # bit for bit the unclipped update, and the norms are still written
-        U = _learner(H, A, loss, blob, n, c=c)
-        _same(out, _update(U, n, store, cap, it, None, w))
+        U = lh.learner(H, A, loss, blob, n, c=c)
+        lh.same(_bits(out), lh.update(U, n, store, cap, it, None, w))
         U.check()
 
 
@@ -340,19 +248,19 @@ def test_clip_against_fp64_mirror(H, A, n, gather, loss, which):
 @pytest.mark.parametrize("loss", ["reference", "per_sample"])
 @pytest.mark.parametrize("H,A,n,gather", [SHAPES[1], SHAPES[3], SHAPES[4]])
 def test_one_row_applied_alone_is_the_closed_update(H, A, n, gather, loss):
-    blob, b, store, cap, idx, it = _case(H, A, n, gather)
+    blob, b, store, cap, idx, it = lh.case(H, A, n, gather)
     c = 0.5 if loss == "per_sample" else 0.0
     nr = rm.norms(_mirror(H, A, n, gather, loss, c, False)[3], H, A)
     mgn = (float(nr[0] / 4), float(nr[1] / 4))
     prio0 = torch.rand(cap, device=DEV) + 0.1
     outs = []
-    for run in (_update, _split_update):
-        L = _learner(H, A, loss, blob, n, c=c, mgn=mgn, diag=True)
+    for run in (lh.update, lh.split_update):
+        L = lh.learner(H, A, loss, blob, n, c=c, mgn=mgn, diag=True)
         prio = prio0.clone()
         outs.append(dict(run(L, n, store, cap, it, prio), ent=L.entropy(n).cpu().numpy(), norm=L.grad_norm.cpu().numpy()))
         L.check()
     assert np.isfinite(outs[0]["norm"]).all() and not np.array_equal(outs[0]["prio"], prio0.cpu().numpy())
-    _same(*outs)
+    lh.same(*outs)
 
 
 @pytest.mark.parametrize("loss", ["reference", "per_sample"])
@@ -361,13 +269,13 @@ def test_three_rows_match_the_mirror_and_two_learners_stay_equal(H, A, n, gather
     """K = 3 rows of different n, applied together with entropy and clipping on, against the closed update of the
     concatenated batch in the mirror; the same rows applied on two learners that started equal leave them bitwise
     equal."""
-    blob, b, store, cap, idx, it = _case(H, A, n, gather)
+    blob, b, store, cap, idx, it = lh.case(H, A, n, gather)
     c = 0.5 if loss == "per_sample" else 0.0
     ral, rcl, rtd, g, ent = _mirror(H, A, n, gather, loss, c, False)
     nr = rm.norms(g, H, A)
     mgn = (nr[0] / 4, nr[1] / 4)
     coef = rm.clip(g, H, A, mgn)[0]
-    one, two = (_learner(H, A, loss, blob, n, c=c, mgn=tuple(float(x) for x in mgn), diag=True) for _ in range(2))
+    one, two = (lh.learner(H, A, loss, blob, n, c=c, mgn=tuple(float(x) for x in mgn), diag=True) for _ in range(2))
     rows = one.new_rows(3)
     tds = []
     for k, (lo, hi) in enumerate(dp.cuts(n, 3, seed=n)):
@@ -375,41 +283,41 @@ def test_three_rows_match_the_mirror_and_two_learners_stay_equal(H, A, n, gather
         tds.append(td)
     res = [L.apply(rows) for L in (one, two)]
     one.check(); two.check()
-    _same(_state(one), _state(two))
+    lh.same(lh.state(one), lh.state(two))
     assert torch.equal(one.grad_norm, two.grad_norm)
     for x, y in zip(*res):
         assert torch.equal(x, y)
-    _assert_losses_and_td(res[0][0].cpu().numpy(), res[0][1].cpu().numpy(), torch.cat(tds).cpu().numpy(), ral, rcl, rtd, c, A)
-    _assert_step_from_zero(_state(one), blob, g, n, H, A, coef)
-    assert (np.abs(one.grad_norm.cpu().numpy() - nr) <= np.sqrt(g.size) * _tol_g(n, g)).all()
+    lh.assert_losses_and_td(res[0][0].cpu().numpy(), res[0][1].cpu().numpy(), torch.cat(tds).cpu().numpy(), ral, rcl, rtd, c, A)
+    lh.assert_step_from_zero(lh.state(one), blob, g, n, H, A, coef)
+    assert (np.abs(one.grad_norm.cpu().numpy() - nr) <= np.sqrt(g.size) * lh.tol_g(n, g)).all()
 
 
 # ---- 7. determinism and capture ------------------------------------------------------------------------------------------
 
 def test_identical_calls_give_identical_bits():
     H, A, n, gather = SHAPES[3]
-    blob, b, store, cap, idx, it = _case(H, A, n, gather)
+    blob, b, store, cap, idx, it = lh.case(H, A, n, gather)
     nr = rm.norms(_mirror(H, A, n, gather, "per_sample", 0.3, False)[3], H, A)
     outs = []
     for _ in range(2):
-        L = _learner(H, A, "per_sample", blob, n, c=0.3, mgn=(float(nr[0] / 4), float(nr[1] / 4)), diag=True)
-        res = [_update(L, n, store, cap, it, None) for _ in range(3)]
+        L = lh.learner(H, A, "per_sample", blob, n, c=0.3, mgn=(float(nr[0] / 4), float(nr[1] / 4)), diag=True)
+        res = [lh.update(L, n, store, cap, it, None) for _ in range(3)]
         L.check()
         outs.append(res + [{"ent": L.entropy(n).cpu().numpy(), "norm": L.grad_norm.cpu().numpy()}])
     for x, y in zip(*outs):
-        _same(x, y)
+        lh.same(x, y)
 
 
 def test_graph_replay_matches_eager():
     """One update with entropy and clipping captured in a graph and replayed three times == three eager updates."""
     H, A, n, gather = SHAPES[3]
-    blob, b, store, cap, idx, it = _case(H, A, n, gather)
+    blob, b, store, cap, idx, it = lh.case(H, A, n, gather)
     nr = rm.norms(_mirror(H, A, n, gather, "per_sample", 0.3, False)[3], H, A)
     kw = dict(c=0.3, mgn=(float(nr[0] / 4), float(nr[1] / 4)), diag=True)
     prio_e = torch.rand(cap, device=DEV) + 0.1
     prio_g = prio_e.clone()
-    eager = _learner(H, A, "per_sample", blob, n, **kw)
-    graphed = _learner(H, A, "per_sample", blob, n, **kw)
+    eager = lh.learner(H, A, "per_sample", blob, n, **kw)
+    graphed = lh.learner(H, A, "per_sample", blob, n, **kw)
     torch.cuda.synchronize()
     s = torch.cuda.Stream(DEV)
     s.wait_stream(torch.cuda.current_stream())
@@ -419,17 +327,17 @@ def test_graph_replay_matches_eager():
             g_out = graphed._run(n, store, cap, it, prio_g)
     torch.cuda.current_stream().wait_stream(s)
     torch.cuda.synchronize()
-    assert np.array_equal(_state(graphed)["step"], np.zeros(8))           # capture ran nothing
+    assert np.array_equal(lh.state(graphed)["step"], np.zeros(8))           # capture ran nothing
     for k in range(3):
         e_out = eager._run(n, store, cap, it, prio_e)
         g.replay()
         torch.cuda.synchronize()
         for x, y in zip(e_out, g_out):
             assert torch.equal(x, y), k
-        _same(_state(graphed), _state(eager))
+        lh.same(lh.state(graphed), lh.state(eager))
         assert torch.equal(prio_e, prio_g) and torch.equal(eager.grad_norm, graphed.grad_norm)
         assert torch.equal(eager.entropy(n), graphed.entropy(n))
-    assert np.array_equal(_state(graphed)["step"], np.full(8, 3)) and torch.isfinite(graphed.grad_norm).all()
+    assert np.array_equal(lh.state(graphed)["step"], np.full(8, 3)) and torch.isfinite(graphed.grad_norm).all()
     assert float(graphed.grad_norm[0]) > kw["mgn"][0] and float(graphed.grad_norm[1]) > kw["mgn"][1]   # both clipped
     graphed.check(); eager.check()
 
@@ -438,15 +346,15 @@ def test_graph_replay_matches_eager():
 
 def test_the_setter_refuses_bad_values_and_changes_nothing():
     H, A, n, gather = SHAPES[1]
-    blob = _case(H, A, n, gather)[0]
-    L = _learner(H, A, "per_sample", blob, n, c=0.25, mgn=(1.5, None))
+    blob = lh.case(H, A, n, gather)[0]
+    L = lh.learner(H, A, "per_sample", blob, n, c=0.25, mgn=(1.5, None))
     assert L.get_regularisation() == (0.25, 1.5, INF)
     for c, mgn in ((float("nan"), None), (-0.1, None), (INF, None), (0.1, 0.0), (0.1, (1.0, 0.0)), (0.1, float("nan")),
                    (0.1, (-1.0, 1.0))):
         with pytest.raises(RuntimeError, match="uavtrack_learner_set_regularisation: "):
             L.set_regularisation(c, mgn)
         assert L.get_regularisation() == (0.25, 1.5, INF)
-    R = _learner(H, A, "reference", blob, n, mgn=2.0)
+    R = lh.learner(H, A, "reference", blob, n, mgn=2.0)
     assert R.get_regularisation() == (0.0, 2.0, 2.0)
     with pytest.raises(RuntimeError, match="UAVTRACK_LOSS_REFERENCE.*cannot share"):
         R.set_regularisation(0.1, 2.0)
@@ -459,12 +367,12 @@ def test_the_setter_refuses_bad_values_and_changes_nothing():
 
 def test_a_bad_action_with_clipping_on_changes_nothing():
     H, A, n, gather = SHAPES[2]
-    blob, b, store, cap, idx, it = _case(H, A, n, gather)
-    L = _learner(H, A, "per_sample", blob, n, c=0.1, mgn=(0.01, 0.01), diag=True)
+    blob, b, store, cap, idx, it = lh.case(H, A, n, gather)
+    L = lh.learner(H, A, "per_sample", blob, n, c=0.1, mgn=(0.01, 0.01), diag=True)
     al, cl, _ = L._run(n, store, cap, it, None)
     L.check()
     assert torch.isfinite(L.grad_norm).all()
-    before = _state(L)
+    before = lh.state(L)
     prio = torch.rand(cap, device=DEV) + 0.1
     prio0 = prio.clone()
     bad = {k: v.clone() for k, v in store.items()}
@@ -472,7 +380,7 @@ def test_a_bad_action_with_clipping_on_changes_nothing():
     al, cl, _ = L._run(n, bad, cap, it, prio)
     assert torch.isnan(al) and torch.isnan(cl) and torch.isnan(L.grad_norm).all()
     assert float(L.entropy(n)[40]) == 0.0 and float(L.entropy(n)[39]) > 0.0
-    _same(_state(L), before)
+    lh.same(lh.state(L), before)
     assert torch.equal(prio, prio0)
     with pytest.raises(RuntimeError, match="1 update"):
         L.check()
@@ -483,20 +391,20 @@ def test_a_bad_action_with_clipping_on_changes_nothing():
 
 def test_an_update_larger_than_the_entropy_buffer_is_refused_on_the_host():
     H, A, n, gather = SHAPES[1]
-    blob, b, store, cap, idx, it = _case(H, A, n, gather)
-    L = _learner(H, A, "per_sample", blob, n)
+    blob, b, store, cap, idx, it = lh.case(H, A, n, gather)
+    L = lh.learner(H, A, "per_sample", blob, n)
     L.enable_diagnostics(n - 1)
-    before = _state(L)
+    before = lh.state(L)
     with pytest.raises(RuntimeError, match="entropy buffer holds 62"):
         L._run(n, store, cap, it, None)
     with pytest.raises(RuntimeError, match="entropy buffer holds 62"):
         L._grad(n, store, cap, it)
-    _same(_state(L), before)
+    lh.same(lh.state(L), before)
     L._run(n - 1, store, cap, it[:n - 1].contiguous(), None)
     L.disable_diagnostics()
     L._run(n, store, cap, it, None)
     L.check()
-    assert np.array_equal(_state(L)["step"], np.full(8, 2))
+    assert np.array_equal(lh.state(L)["step"], np.full(8, 2))
 
 
 # ---- 9. the example ------------------------------------------------------------------------------------------------------

@@ -11,18 +11,19 @@ import pytest
 import torch
 
 import learner_dp_mirror as dp
-import learner_mirror as mirror
+import learner_harness as lh
 import learner_weighted_mirror as wm
 import nstep_mirror as nm
+import ring_rollout_harness as rr
+from ring_rollout_harness import B, DONES, N, NTR, RINGS, T
 
 pytestmark = pytest.mark.gpu
 
-DEV = "cuda:0"
-LR = (1e-3, 5e-3)
-GAMMA = 0.95
+DEV = lh.DEV
+GAMMA = lh.GAMMA
 G32 = np.float32(GAMMA)
 INF = float("inf")
-STORES = ("states", "actions", "rewards", "next_states")
+STORES = lh.STORES
 
 
 def _uav():
@@ -30,58 +31,7 @@ def _uav():
     return uavtrack
 
 
-def _dev(x):
-    return torch.from_numpy(np.ascontiguousarray(x)).to(DEV)
-
-
 # ---- 1. the add against the mirror ---------------------------------------------------------------------------------------
-
-T, B, N = 7, 3, 2
-AG = B * N
-NTR = T * AG                                                           # 42 transitions
-
-
-def _done(kind):
-    d = np.zeros((T, B), np.uint8)
-    if kind == "mid":
-        d[3, 1] = 1
-    elif kind == "consecutive":
-        d[2, 0] = d[3, 0] = 1
-    elif kind == "first":
-        d[0, 2] = 1
-    elif kind == "last":
-        d[T - 1, 1] = 1
-    elif kind == "every":
-        d[:, 1] = 1
-    return None if kind == "null" else d
-
-
-DONES = ("zeros", "null", "mid", "consecutive", "first", "last", "every")
-# (capacity, pos, count): roomy; pos three slots before the end; a ring smaller than the rollout
-RINGS = {"roomy": (100, 10, 10), "wrap": (100, 97, 100), "small": (17, 5, 17)}
-_roll = {}
-
-
-def _rollout():
-    if not _roll:
-        rng = np.random.default_rng(5)
-        _roll.update(obs_in=rng.standard_normal((B, N, 12)).astype(np.float32),
-                     obs=rng.standard_normal((T, B, N, 12)).astype(np.float32),
-                     actions=rng.integers(0, 12, (T, B, N)).astype(np.int32),
-                     reward=(rng.standard_normal((T, B, N)) * 3).astype(np.float32),
-                     start_obs=rng.standard_normal((T, B, N, 12)).astype(np.float32))
-        _roll["dev"] = {k: _dev(v) for k, v in _roll.items()}
-    return _roll
-
-
-def _out(done):
-    """The result dict add_rollout takes; done None: no done / start_obs at all."""
-    d = _rollout()["dev"]
-    out = {k: d[k] for k in ("obs", "actions", "reward")}
-    if done is not None:
-        out.update(done=_dev(done), start_obs=d["start_obs"])
-    return out
-
 
 def _new_ring(kind, cap, **kw):
     u = _uav()
@@ -89,59 +39,26 @@ def _new_ring(kind, cap, **kw):
     return ring.with_nstep(**kw)
 
 
-def _prefill(ring, pos, count, seed=9):
-    """Sentinel stores, the ring's host state, and (prioritised) priorities whose maximum over the whole array is 2.5."""
-    rng = np.random.default_rng(seed)
-    cap = ring.capacity
-    ring.store["states"].copy_(_dev(rng.standard_normal((cap, 12)).astype(np.float32)))
-    ring.store["next_states"].copy_(_dev(rng.standard_normal((cap, 12)).astype(np.float32)))
-    ring.store["actions"].fill_(-3)
-    ring.store["rewards"].fill_(-777.25)
-    if ring.discounts is not None:
-        ring.discounts.fill_(7.0)
-    if ring.priorities is not None:
-        p = rng.uniform(0.1, 2.0, cap).astype(np.float32)
-        p[count:] = 0.0
-        p[count // 2] = 2.5
-        ring.priorities.copy_(_dev(p))
-    ring.pos, ring.count = pos, count
-
-
-def _image(ring):
-    img = {k: ring.store[k].cpu().numpy().copy() for k in STORES}
-    img["discounts"] = None if ring.discounts is None else ring.discounts.cpu().numpy().copy()
-    img["priorities"] = None if ring.priorities is None else ring.priorities.cpu().numpy().copy()
-    return img
-
-
-def _same_image(a, b, keys=STORES + ("discounts", "priorities")):
-    for k in keys:
-        if a[k] is None or b[k] is None:
-            assert a[k] is None and b[k] is None, k
-        else:
-            assert a[k].tobytes() == b[k].tobytes(), k
-
-
 @pytest.mark.parametrize("ringcase", sorted(RINGS))
 @pytest.mark.parametrize("done_kind", DONES)
 @pytest.mark.parametrize("kind", ["uniform", "prioritised"])
 def test_add_against_the_mirror_bitwise(kind, done_kind, ringcase):
-    r = _rollout()
-    done = _done(done_kind)
+    r = rr.rollout()
+    done = rr.done(done_kind)
     cap, pos, count = RINGS[ringcase]
     longest = 0
     for gamma in (0.95, 1.0, 0.0):
         for n_step in (1, 2, 3, 5, 7, 9):
             ring = _new_ring(kind, cap, n_step=n_step, gamma=gamma)
-            _prefill(ring, pos, count)
-            img = _image(ring)
-            ring.add_rollout(r["dev"]["obs_in"], _out(done))
+            rr.prefill(ring, pos, count)
+            img = rr.image(ring)
+            ring.add_rollout(r["dev"]["obs_in"], rr.out(done))
             tr, m = nm.transitions(r["obs_in"], r["obs"], r["actions"], r["reward"], n_step, gamma, done,
                                    None if done is None else r["start_obs"])
             longest = max(longest, int(m.max()))
             p2, c2 = nm.ring_add(img, pos, count, tr)
             assert (ring.pos, ring.count) == (p2, c2)
-            _same_image(_image(ring), img)
+            rr.same_image(rr.image(ring), img)
             if kind == "prioritised":
                 assert (img["priorities"] == np.float32(2.5)).sum() >= min(NTR, cap)
     assert longest == T                                                # the longest window ran the whole rollout
@@ -153,16 +70,16 @@ def test_add_against_the_mirror_bitwise(kind, done_kind, ringcase):
 @pytest.mark.parametrize("done_kind", ["null", "zeros", "mid", "every"])
 @pytest.mark.parametrize("kind", ["uniform", "prioritised"])
 def test_n1_is_todays_add(kind, done_kind, ringcase):
-    r = _rollout()
-    done = _done(done_kind)
+    r = rr.rollout()
+    done = rr.done(done_kind)
     cap, pos, count = RINGS[ringcase]
     new, old = _new_ring(kind, cap, n_step=1, gamma=GAMMA), _new_ring(kind, cap)
     assert old.discounts is None and new.discounts is not None
-    _prefill(new, pos, count); _prefill(old, pos, count)
-    new.add_rollout(r["dev"]["obs_in"], _out(done))
-    old.add_rollout(r["dev"]["obs_in"], _out(done))      # uavtrack_replay_add_rollout_episodes, or _add_rollout without done
-    a, b = _image(new), _image(old)
-    _same_image(a, b, STORES + ("priorities",))
+    rr.prefill(new, pos, count); rr.prefill(old, pos, count)
+    new.add_rollout(r["dev"]["obs_in"], rr.out(done))
+    old.add_rollout(r["dev"]["obs_in"], rr.out(done))      # uavtrack_replay_add_rollout_episodes, or _add_rollout without done
+    a, b = rr.image(new), rr.image(old)
+    rr.same_image(a, b, STORES + ("priorities",))
     assert (new.pos, new.count) == (old.pos, old.count)
     k = min(NTR, cap)
     written = np.zeros(cap, bool)
@@ -177,84 +94,9 @@ SHAPES = [(1, 9, 1), (33, 12, 2), (64, 48, 63), (128, 12, 65), (128, 12, 4096)]
 CASES = [(H, A, n, loss, gather) for H, A, n in SHAPES for loss in ("reference", "per_sample") for gather in (True, False)]
 
 
-def _learner(H, A, loss="reference", blob=None, max_batch=0, c=0.0, mgn=None, diag=False, gamma=GAMMA):
-    L = _uav().DeviceActorCritic(12, H, A, LR[0], LR[1], gamma, DEV, loss=loss, max_batch=max_batch, entropy_coef=c,
-                                 max_grad_norm=mgn)
-    if blob is not None:
-        L._set_params(np.ascontiguousarray(blob, np.float32))
-    if diag:
-        L.enable_diagnostics()
-    return L
-
-
-def _state(L):
-    m, v, st = L._optim_state()
-    return {"params": L._get_params(), "exp_avg": m, "exp_avg_sq": v, "step": st}
-
-
-def _same(a, b):
-    assert a.keys() == b.keys()
-    for k in a:
-        if a[k] is None or b[k] is None:
-            assert a[k] is None and b[k] is None, k
-        else:
-            assert np.array_equal(np.asarray(a[k]), np.asarray(b[k]), equal_nan=True), k
-
-
-_cache = {}
-
-
-def _case(H, A, n, gather):
-    """(blob, host batch over the store, device store, capacity, host indices, device indices or None), built once."""
-    key = (H, A, n, gather)
-    if key not in _cache:
-        rng = np.random.RandomState(H * 1000 + n + (7 if gather else 0))
-        cap = n + 7 if gather else n
-        b = dp.batch(rng, cap, A)
-        idx = rng.randint(0, cap, size=n).astype(np.int64) if gather else np.arange(n)
-        store = {k: _dev(x) for k, x in zip(STORES, b)}
-        _cache[key] = (dp.init_blob(H, A, H + n), b, store, cap, idx, _dev(idx) if gather else None)
-    return _cache[key]
-
-
-def _gathered(b, idx):
-    return tuple(x[idx] for x in b)
-
-
 def _discount_store(cap, seed):
     """A per-slot store in [0, 1] with exact zeros and an exact one (cap 1: a single zero)."""
     return wm.make_weights(np.random.RandomState(seed + 101), cap) if cap > 1 else np.zeros(1, np.float32)
-
-
-def _update(L, n, store, cap, it, prio, w=None, d=None, direct=False):
-    """One closed update.  direct: uavtrack_learner_update_discounted itself, whatever is NULL."""
-    from uavtrack import _lib
-    if direct:
-        losses, td = torch.empty(2, device=DEV), torch.empty(n, device=DEV)
-        _lib.check(L._lib.uavtrack_learner_update_discounted(
-            L._h, n, *L._batch_args(store, cap, it), _lib.ptr(w), _lib.ptr(d), _lib.ptr(losses[0:1]),
-            _lib.ptr(losses[1:2]), _lib.ptr(td), _lib.ptr(prio), L._stream()), "uavtrack_learner_update_discounted")
-        al, cl = losses[0], losses[1]
-    else:
-        al, cl, td = L._run(n, store, cap, it, prio, w, d)
-    out = dict(_state(L), actor_loss=al.cpu().numpy(), critic_loss=cl.cpu().numpy(), td=td.cpu().numpy(),
-               prio=None if prio is None else prio.cpu().numpy())
-    if L._entropy is not None:
-        out["entropy"] = L.entropy(n).cpu().numpy()
-        out["grad_norm"] = L.grad_norm.cpu().numpy()
-    return out
-
-
-def _row(L, n, store, cap, it, w=None, d=None, direct=False):
-    from uavtrack import _lib
-    if direct:
-        row, td = torch.empty(L.row_floats, device=DEV), torch.empty(n, device=DEV)
-        _lib.check(L._lib.uavtrack_learner_grad_discounted(
-            L._h, n, *L._batch_args(store, cap, it), _lib.ptr(w), _lib.ptr(d), _lib.ptr(td), _lib.ptr(row), L._stream()),
-            "uavtrack_learner_grad_discounted")
-    else:
-        row, td = L._grad(n, store, cap, it, None, None, w, d)
-    return row.cpu().numpy(), td.cpu().numpy()
 
 
 # ---- 3. gamma everywhere is nothing --------------------------------------------------------------------------------------
@@ -265,9 +107,9 @@ VARIANTS = ("plain", "weighted", "regularised", "diagnostics")
 @pytest.mark.parametrize("variant", VARIANTS)
 @pytest.mark.parametrize("H,A,n,loss,gather", CASES)
 def test_a_store_of_gamma_and_null_are_the_plain_update_bitwise(H, A, n, loss, gather, variant):
-    blob, b, store, cap, idx, it = _case(H, A, n, gather)
+    blob, b, store, cap, idx, it = lh.case(H, A, n, gather)
     prio0 = torch.rand(cap, device=DEV) + 0.1
-    w = _dev(wm.make_weights(np.random.RandomState(n + H), n)) if variant == "weighted" else None
+    w = lh.dev(wm.make_weights(np.random.RandomState(n + H), n)) if variant == "weighted" else None
     kw = {}
     if variant == "regularised":                                       # (the entropy bonus exists for per_sample only)
         kw = dict(c=0.01 if loss == "per_sample" else 0.0, mgn=(0.05, 0.5))
@@ -275,18 +117,18 @@ def test_a_store_of_gamma_and_null_are_the_plain_update_bitwise(H, A, n, loss, g
         kw = dict(diag=True, mgn=(1e30, 1e30))
     full = torch.full((cap,), GAMMA, device=DEV)
     assert full.cpu().numpy().view(np.int32)[0] == G32.view(np.int32)
-    modes = (dict(), dict(direct=True), dict(d=full), dict(d=full, direct=True))
+    modes = (dict(), dict(entry="discounted"), dict(d=full), dict(d=full, entry="discounted"))
     outs = []
     for mode in modes:
-        L = _learner(H, A, loss, blob, max_batch=n, **kw)
-        outs.append(_update(L, n, store, cap, it, prio0.clone(), w, **mode))
+        L = lh.learner(H, A, loss, blob, max_batch=n, **kw)
+        outs.append(lh.update(L, n, store, cap, it, prio0.clone(), w, **mode))
         L.check()
     assert np.isfinite(outs[0]["actor_loss"]) and np.array_equal(outs[0]["step"], np.ones(8))
     assert not np.array_equal(outs[0]["prio"], prio0.cpu().numpy())
     for other in outs[1:]:
-        _same(outs[0], other)
-    L = _learner(H, A, loss, blob, max_batch=n, **kw)
-    rows = [_row(L, n, store, cap, it, w, **mode) for mode in modes]
+        lh.same(outs[0], other)
+    L = lh.learner(H, A, loss, blob, max_batch=n, **kw)
+    rows = [lh.row(L, n, store, cap, it, w, **mode) for mode in modes]
     L.check()
     for row, td in rows[1:]:
         assert np.array_equal(row.view(np.int32), rows[0][0].view(np.int32)) and np.array_equal(td, rows[0][1])
@@ -294,34 +136,6 @@ def test_a_store_of_gamma_and_null_are_the_plain_update_bitwise(H, A, n, loss, g
 
 
 # ---- 4. random discounts against the fp64 mirror ---------------------------------------------------------------------------
-
-def _assert_losses_and_td(al, cl, td, ral, rcl, rtd):
-    """test_sweep_against_fp64_mirror's bounds as tests/test_hip_learner_weighted.py states them: td_delta and the losses
-    at 2e-5 of their scale."""
-    tds = np.abs(rtd).max() + 1e-6
-    print(f"td error {np.abs(td - rtd).max():.3e} of bound {2e-5 * tds:.3e}")
-    np.testing.assert_allclose(td, rtd, rtol=0, atol=2e-5 * tds)
-    assert abs(float(cl) - rcl) <= 2e-5 * (np.mean(rtd ** 2) + 1e-12) + 1e-12, (float(cl), rcl)
-    nlp_scale = abs(ral) + np.mean(np.abs(rtd)) * 30
-    assert abs(float(al) - ral) <= 2e-5 * nlp_scale, (float(al), ral)
-
-
-def _assert_step_from_zero(st, blob, g, n, H, A):
-    """The same test's bounds on the first Adam step: the gradient (exp_avg / 0.1) within 2e-6 (1 + log2 n) of its
-    largest element, the parameters within 1e-3 lr except where the fp64 gradient is within the gradient's rounding of 0
-    (Adam's first step may then take either sign: within 2 lr)."""
-    gd = st["exp_avg"] / 0.1
-    gmax = np.abs(g).max()
-    tol_g = 2e-6 * (1 + np.log2(n)) * gmax
-    print(f"gradient error {np.abs(gd - g).max():.3e} of bound {tol_g:.3e}")
-    assert np.abs(gd - g).max() <= tol_g + 1e-30, (np.abs(gd - g).max(), tol_g)
-    p64 = mirror.adam(blob.astype(np.float64), np.zeros(g.size), np.zeros(g.size), np.ones(8, np.int64), g, LR, H, A)[0]
-    lr_of = np.concatenate([np.full(k, LR[0] if t < 4 else LR[1]) for t, k in enumerate(mirror.layout(H, A)[0])])
-    near0 = np.abs(g) <= 4 * tol_g + 1e-8
-    err = np.abs(st["params"] - p64)
-    assert (err[~near0] <= 1e-3 * lr_of[~near0] + 1e-6 * np.abs(p64[~near0])).all(), err[~near0].max()
-    assert (err[near0] <= 2 * lr_of[near0] + 1e-6).all()
-
 
 PATHS = [(loss, path) for loss in ("reference", "per_sample") for path in ("plain", "weighted", "regularised")
          if not (path == "regularised" and loss == "reference")]
@@ -331,42 +145,42 @@ PATHS = [(loss, path) for loss in ("reference", "per_sample") for path in ("plai
 @pytest.mark.parametrize("gather", [True, False])
 @pytest.mark.parametrize("H,A,n", SHAPES)
 def test_random_discounts_against_fp64_mirror(H, A, n, gather, loss, path):
-    blob, b, store, cap, idx, it = _case(H, A, n, gather)
+    blob, b, store, cap, idx, it = lh.case(H, A, n, gather)
     ds = _discount_store(cap, n + H)
     d = ds[idx]                                                         # the per-row discounts, through the index vector
     w = wm.make_weights(np.random.RandomState(n + H + 5), n) if path != "plain" else None
     c = 0.01 if path == "regularised" else None
-    L = _learner(H, A, loss, blob, max_batch=n, c=c or 0.0)
-    out = _update(L, n, store, cap, it, None, None if w is None else _dev(w), _dev(ds))
+    L = lh.learner(H, A, loss, blob, max_batch=n, c=c or 0.0)
+    out = lh.update(L, n, store, cap, it, None, None if w is None else lh.dev(w), lh.dev(ds))
     L.check()
-    ref = nm.learner(blob, H, A, *_gathered(b, idx), d, loss, w, None if c is None else np.float32(c))
+    ref = nm.learner(blob, H, A, *lh.gathered(b, idx), d, loss, w, None if c is None else np.float32(c))
     ral, rcl, rtd, g = ref[:4]
-    _assert_losses_and_td(out["actor_loss"], out["critic_loss"], out["td"], ral, rcl, rtd)
-    _assert_step_from_zero(out, blob, g, n, H, A)
+    lh.assert_losses_and_td(out["actor_loss"], out["critic_loss"], out["td"], ral, rcl, rtd)
+    lh.assert_step_from_zero(out, blob, g, n, H, A)
     # rows with d = 0 do not bootstrap: td_delta = r - V(s), within the same bound
     zero = d == 0
     assert zero.any() or n < 63
     if zero.any():
-        r0 = nm.learner(blob, H, A, *_gathered(b, idx), np.zeros(n), loss, w, None if c is None else np.float32(c))[2]
+        r0 = nm.learner(blob, H, A, *lh.gathered(b, idx), np.zeros(n), loss, w, None if c is None else np.float32(c))[2]
         assert np.array_equal(r0[zero], rtd[zero])
         np.testing.assert_allclose(out["td"][zero], r0[zero], rtol=0, atol=2e-5 * (np.abs(rtd).max() + 1e-6))
     if n >= 63:       # the discounts are in the result: gamma for every row is far outside the bound
-        gu = nm.learner(blob, H, A, *_gathered(b, idx), np.full(n, GAMMA), loss, w, None if c is None else np.float32(c))[3]
-        assert np.abs(out["exp_avg"] / 0.1 - gu).max() > 100 * 2e-6 * (1 + np.log2(n)) * np.abs(g).max()
+        gu = nm.learner(blob, H, A, *lh.gathered(b, idx), np.full(n, GAMMA), loss, w, None if c is None else np.float32(c))[3]
+        assert np.abs(out["exp_avg"] / 0.1 - gu).max() > 100 * lh.tol_g(n, g)
 
 
 def test_the_discount_is_per_slot_and_the_weight_per_batch_row():
     """A gathered batch whose index vector is a reversal: the discounts follow the slots, the weights the batch rows."""
     H, A, n = 64, 12, 63
-    blob, b, store, cap, _, _ = _case(H, A, n, False)
+    blob, b, store, cap, _, _ = lh.case(H, A, n, False)
     idx = np.arange(n)[::-1].copy()
     ds, w = _discount_store(cap, 3), wm.make_weights(np.random.RandomState(4), n)
-    L = _learner(H, A, "per_sample", blob, max_batch=n)
-    out = _update(L, n, store, cap, _dev(idx), None, _dev(w), _dev(ds))
+    L = lh.learner(H, A, "per_sample", blob, max_batch=n)
+    out = lh.update(L, n, store, cap, lh.dev(idx), None, lh.dev(w), lh.dev(ds))
     L.check()
-    ral, rcl, rtd, g = nm.learner(blob, H, A, *_gathered(b, idx), ds[idx], "per_sample", w)
-    _assert_losses_and_td(out["actor_loss"], out["critic_loss"], out["td"], ral, rcl, rtd)
-    _assert_step_from_zero(out, blob, g, n, H, A)
+    ral, rcl, rtd, g = nm.learner(blob, H, A, *lh.gathered(b, idx), ds[idx], "per_sample", w)
+    lh.assert_losses_and_td(out["actor_loss"], out["critic_loss"], out["td"], ral, rcl, rtd)
+    lh.assert_step_from_zero(out, blob, g, n, H, A)
 
 
 # ---- 5. the split form ---------------------------------------------------------------------------------------------------
@@ -378,20 +192,20 @@ SPLIT = [(64, 48, 63), (128, 12, 65), (128, 12, 4096)]
 @pytest.mark.parametrize("loss", ["reference", "per_sample"])
 @pytest.mark.parametrize("H,A,n", SPLIT)
 def test_grad_apply_write_is_the_discounted_update_bitwise(H, A, n, loss, weighted):
-    blob, b, store, cap, idx, it = _case(H, A, n, True)
-    ds = _dev(_discount_store(cap, n))
-    w = _dev(wm.make_weights(np.random.RandomState(n), n)) if weighted else None
+    blob, b, store, cap, idx, it = lh.case(H, A, n, True)
+    ds = lh.dev(_discount_store(cap, n))
+    w = lh.dev(wm.make_weights(np.random.RandomState(n), n)) if weighted else None
     prio0 = torch.rand(cap, device=DEV) + 0.1
-    closed = _learner(H, A, loss, blob, max_batch=n)
-    want = _update(closed, n, store, cap, it, prio0.clone(), w, ds)
-    split = _learner(H, A, loss, blob, max_batch=n)
+    closed = lh.learner(H, A, loss, blob, max_batch=n)
+    want = lh.update(closed, n, store, cap, it, prio0.clone(), w, ds)
+    split = lh.learner(H, A, loss, blob, max_batch=n)
     prio = prio0.clone()
     row, td = split._grad(n, store, cap, it, None, None, w, ds)
     al, cl = split.apply(row)
     split.write_priorities(types.SimpleNamespace(priorities=prio, capacity=cap), it, td)
     split.check(); closed.check()
     assert not np.array_equal(want["prio"], prio0.cpu().numpy())
-    _same(dict(_state(split), actor_loss=al.cpu().numpy(), critic_loss=cl.cpu().numpy(), td=td.cpu().numpy(),
+    lh.same(dict(lh.state(split), actor_loss=al.cpu().numpy(), critic_loss=cl.cpu().numpy(), td=td.cpu().numpy(),
                prio=prio.cpu().numpy()), want)
 
 
@@ -400,19 +214,19 @@ def test_grad_apply_write_is_the_discounted_update_bitwise(H, A, n, loss, weight
 def test_a_row_with_discounts_and_a_row_without_apply_together(H, A, n, loss):
     """Two gradient rows over the two halves of a batch, the first with a discount store and the second through the
     plain uavtrack_learner_grad (gamma in the mirror), against the mirror on the whole batch."""
-    blob, b, store, cap, idx, it = _case(H, A, n, True)
+    blob, b, store, cap, idx, it = lh.case(H, A, n, True)
     ds = _discount_store(cap, n + 1)
     h = n // 2
-    L = _learner(H, A, loss, blob, max_batch=n)
+    L = lh.learner(H, A, loss, blob, max_batch=n)
     rows = L.new_rows(2)
-    _, td0 = L._grad(h, store, cap, it[:h], rows[0], None, None, _dev(ds))
+    _, td0 = L._grad(h, store, cap, it[:h], rows[0], None, None, lh.dev(ds))
     _, td1 = L._grad(n - h, store, cap, it[h:].contiguous(), rows[1])
     al, cl = L.apply(rows)
     L.check()
     d = np.concatenate([ds[idx[:h]].astype(np.float64), np.full(n - h, float(G32))])
-    ral, rcl, rtd, g = nm.learner(blob, H, A, *_gathered(b, idx), d, loss)
-    _assert_losses_and_td(al.cpu().numpy(), cl.cpu().numpy(), torch.cat([td0, td1]).cpu().numpy(), ral, rcl, rtd)
-    _assert_step_from_zero(_state(L), blob, g, n, H, A)
+    ral, rcl, rtd, g = nm.learner(blob, H, A, *lh.gathered(b, idx), d, loss)
+    lh.assert_losses_and_td(al.cpu().numpy(), cl.cpu().numpy(), torch.cat([td0, td1]).cpu().numpy(), ral, rcl, rtd)
+    lh.assert_step_from_zero(lh.state(L), blob, g, n, H, A)
 
 
 # ---- 6. refusals -----------------------------------------------------------------------------------------------------------
@@ -420,20 +234,20 @@ def test_a_row_with_discounts_and_a_row_without_apply_together(H, A, n, loss):
 @pytest.mark.parametrize("bad", [float("nan"), -0.1, 1.5], ids=["nan", "negative", "above-one"])
 def test_a_bad_discount_refuses_the_update(bad):
     H, A, n = 128, 12, 65
-    blob, b, store, cap, idx, it = _case(H, A, n, True)
-    L = _learner(H, A, "reference", blob, max_batch=n)
-    good = _dev(_discount_store(cap, 3))
+    blob, b, store, cap, idx, it = lh.case(H, A, n, True)
+    L = lh.learner(H, A, "reference", blob, max_batch=n)
+    good = lh.dev(_discount_store(cap, 3))
     good[int(idx[0])], good[int(idx[1])] = 1.0, 0.0                     # both ends of the range are accepted
     L._run(n, store, cap, it, None, None, good)
     L.check()
-    before = _state(L)
+    before = lh.state(L)
     prio = torch.rand(cap, device=DEV) + 0.1
     prio0 = prio.clone()
     d = good.clone()
     d[int(idx[40])] = bad                                               # a slot the second tile of the batch gathers
     al, cl, _ = L._run(n, store, cap, it, prio, None, d)
     assert torch.isnan(al) and torch.isnan(cl)
-    _same(_state(L), before)
+    lh.same(lh.state(L), before)
     assert torch.equal(prio, prio0)
     with pytest.raises(RuntimeError, match="1 update"):
         L.check()
@@ -445,7 +259,7 @@ def test_a_bad_discount_refuses_the_update(bad):
     al, cl = L.apply(torch.stack([ok_row, row]))
     L.write_priorities(types.SimpleNamespace(priorities=prio, capacity=cap), it, td)
     assert torch.isnan(al) and torch.isnan(cl)
-    _same(_state(L), before)
+    lh.same(lh.state(L), before)
     assert torch.equal(prio, prio0)
     with pytest.raises(RuntimeError, match="1 update"):
         L.check()
@@ -456,17 +270,17 @@ def test_a_bad_discount_refuses_the_update(bad):
     al, cl, _ = L._run(n, store, cap, it, prio, None, d)
     L.check()
     assert torch.isfinite(al) and torch.isfinite(cl) and not torch.equal(prio, prio0)
-    assert np.array_equal(_state(L)["step"], before["step"] + 1)
+    assert np.array_equal(lh.state(L)["step"], before["step"] + 1)
 
 
 def test_a_row_with_the_wrong_tag_is_still_refused():
     """The finalize kernel's "another layout" flag moved from 8 to 16: a row whose tag is not P refuses the apply, alone
     and beside a good row, and so does a row whose n is 0."""
     H, A, n = 64, 12, 63
-    blob, b, store, cap, idx, it = _case(H, A, n, True)
-    L = _learner(H, A, "reference", blob, max_batch=n)
-    before = _state(L)
-    good, _ = L._grad(n, store, cap, it, None, None, None, _dev(_discount_store(cap, 1)))
+    blob, b, store, cap, idx, it = lh.case(H, A, n, True)
+    L = lh.learner(H, A, "reference", blob, max_batch=n)
+    before = lh.state(L)
+    good, _ = L._grad(n, store, cap, it, None, None, None, lh.dev(_discount_store(cap, 1)))
     P = L.num_params
     for word, value in ((P + 7, P + 1), (P + 4, 0)):
         bad = good.clone()
@@ -474,23 +288,23 @@ def test_a_row_with_the_wrong_tag_is_still_refused():
         for rows in (bad, torch.stack([good, bad])):
             al, cl = L.apply(rows)
             assert torch.isnan(al) and torch.isnan(cl)
-            _same(_state(L), before)
+            lh.same(lh.state(L), before)
             with pytest.raises(RuntimeError, match="1 update"):
                 L.check()
     al, cl = L.apply(good)
     L.check()
-    assert torch.isfinite(al) and np.array_equal(_state(L)["step"], np.ones(8))
+    assert torch.isfinite(al) and np.array_equal(lh.state(L)["step"], np.ones(8))
 
 
 def test_host_side_errors_of_the_add_enqueue_nothing():
     from uavtrack import _lib
     lib = _lib.load()
-    r = _rollout()["dev"]
-    done = _dev(_done("mid"))
+    r = rr.rollout()["dev"]
+    done = lh.dev(rr.done("mid"))
     ring = _new_ring("prioritised", 100, n_step=3, gamma=GAMMA)
-    _prefill(ring, 10, 10)
+    rr.prefill(ring, 10, 10)
     torch.cuda.synchronize()
-    img = _image(ring)
+    img = rr.image(ring)
     p = _lib.ptr
     off = lambda t: C.c_void_p(t.data_ptr() + 4)                       # not 16-byte aligned
 
@@ -524,24 +338,24 @@ def test_host_side_errors_of_the_add_enqueue_nothing():
         msg = lib.uavtrack_last_error().decode()
         assert msg.startswith("uavtrack_replay_add_rollout_nstep: ") and word.split(" =")[0] in msg, (word, msg)
     torch.cuda.synchronize()
-    _same_image(_image(ring), img)
+    rr.same_image(rr.image(ring), img)
     assert call() == 0                                                  # and the good call goes through
     torch.cuda.synchronize()
-    assert _image(ring)["rewards"].tobytes() != img["rewards"].tobytes()
+    assert rr.image(ring)["rewards"].tobytes() != img["rewards"].tobytes()
 
 
 @pytest.mark.parametrize("fn", ["update", "grad"])
 def test_host_side_errors_of_the_discounted_calls_enqueue_nothing(fn):
     from uavtrack import _lib
     H, A, n = 64, 12, 63
-    blob, b, store, cap, idx, it = _case(H, A, n, True)
-    L = _learner(H, A, "reference", blob, max_batch=n)
+    blob, b, store, cap, idx, it = lh.case(H, A, n, True)
+    L = lh.learner(H, A, "reference", blob, max_batch=n)
     name = f"uavtrack_learner_{fn}_discounted"
-    ds = _dev(_discount_store(cap, 2))
+    ds = lh.dev(_discount_store(cap, 2))
     losses, td, row = torch.empty(2, device=DEV), torch.zeros(n, device=DEV), torch.zeros(L.row_floats, device=DEV)
     prio = torch.rand(cap, device=DEV) + 0.1
     prio0 = prio.clone()
-    before = _state(L)
+    before = lh.state(L)
     p = _lib.ptr
 
     def call(n_=n, states=p(store["states"]), cap_=cap, idx_=p(it), out0=p(losses[0:1]), td_=p(td), row_=p(row)):
@@ -556,7 +370,7 @@ def test_host_side_errors_of_the_discounted_calls_enqueue_nothing(fn):
         assert call(**kw) != 0, kw
         assert L._lib.uavtrack_last_error().decode().startswith(name + ": "), kw
     L.check()
-    _same(_state(L), before)
+    lh.same(lh.state(L), before)
     assert torch.equal(prio, prio0) and not td.any() and not row.any()
     assert call() == 0
     L.check()
@@ -573,7 +387,7 @@ def _filled_ring(kind, data, seed, k, n_step=3, gamma=GAMMA, dseed=1):
     tr["discounts"] = torch.from_numpy(_discount_store(n, dseed))
     ring.add(tr)
     if kind == "prioritised":
-        ring.priorities[:n] = _dev(np.random.RandomState(dseed).uniform(0.1, 2.0, n).astype(np.float32))
+        ring.priorities[:n] = lh.dev(np.random.RandomState(dseed).uniform(0.1, 2.0, n).astype(np.float32))
     return ring
 
 
@@ -592,13 +406,13 @@ def test_ring_arguments_and_the_gamma_check():
         assert "discounts" not in (plain.sample(4) if cls is u.ReplayRing else plain.sample(4)[0])
     data = dp.batch(np.random.RandomState(1), 300, 12)
     ring = _filled_ring("uniform", data, 3, 100, gamma=0.9)
-    L = _learner(64, 12, "reference", dp.init_blob(64, 12, 1), max_batch=100)
-    before = _state(L)
+    L = lh.learner(64, 12, "reference", dp.init_blob(64, 12, 1), max_batch=100)
+    before = lh.state(L)
     for call in (lambda: L.update_from(ring, 100), lambda: L.grad_from(ring, 100), lambda: L.update_from_many([ring], 100)):
         with pytest.raises(ValueError, match=r"0\.9\b.*0\.95\b"):
             call()
-    _same(_state(L), before)
-    L9 = _learner(64, 12, "reference", dp.init_blob(64, 12, 1), max_batch=100, gamma=0.9)
+    lh.same(lh.state(L), before)
+    L9 = lh.learner(64, 12, "reference", dp.init_blob(64, 12, 1), max_batch=100, gamma=0.9)
     L9.update_from(ring, 100)
     L9.check()
 
@@ -631,8 +445,8 @@ def test_update_from_and_grad_from_are_draw_discounted_call_write(kind, importan
     H, A, n, k = 128, 12, 3000, 1000
     data = dp.batch(np.random.RandomState(21), n, A)
     blob = dp.init_blob(H, A, 21)
-    one, ring = _learner(H, A, "per_sample", blob, max_batch=k), _filled_ring(kind, data, 17, k)
-    two, twin = _learner(H, A, "per_sample", blob, max_batch=k), _filled_ring(kind, data, 17, k)
+    one, ring = lh.learner(H, A, "per_sample", blob, max_batch=k), _filled_ring(kind, data, 17, k)
+    two, twin = lh.learner(H, A, "per_sample", blob, max_batch=k), _filled_ring(kind, data, 17, k)
     imp = importance and kind == "prioritised"
     for u in range(3):
         if u < 2:
@@ -645,23 +459,23 @@ def test_update_from_and_grad_from_are_draw_discounted_call_write(kind, importan
             idx, w = twin.draw(k, 0.4)
         else:
             idx, w = twin.draw(k), None
-        out = _update(two, k, twin.store, twin.capacity, idx, twin.priorities, w if imp else None, twin.discounts,
-                      direct=True)
+        out = lh.update(two, k, twin.store, twin.capacity, idx, twin.priorities, w if imp else None, twin.discounts,
+                      entry="discounted")
         assert np.array_equal(al.cpu().numpy(), out["actor_loss"]) and np.array_equal(cl.cpu().numpy(), out["critic_loss"])
         assert np.array_equal(td.cpu().numpy(), out["td"]) and np.isfinite(out["actor_loss"]), u
         assert torch.equal(ring._idx[:k], idx)
         if kind == "prioritised":
             assert torch.equal(ring.priorities, twin.priorities)
-    _same(_state(one), _state(two))
+    lh.same(lh.state(one), lh.state(two))
     for x in (one, two, ring, twin):
         x.check()
     # the discounts are in the result: the same draws from a ring without them end elsewhere
-    three = _learner(H, A, "per_sample", blob, max_batch=k)
+    three = lh.learner(H, A, "per_sample", blob, max_batch=k)
     third = _filled_ring(kind, data, 17, k)
     third.discounts = None
     for u in range(3):
         three.update_from(third, k, beta=0.4, importance=importance)
-    assert not np.array_equal(_state(three)["params"], _state(one)["params"])
+    assert not np.array_equal(lh.state(three)["params"], lh.state(one)["params"])
 
 
 def test_update_from_many_over_two_nstep_rings():
@@ -671,7 +485,7 @@ def test_update_from_many_over_two_nstep_rings():
     kinds = ("prioritised", "uniform")
     rings = [_filled_ring(kd, d, 40 + j, k, dseed=j) for j, (kd, d) in enumerate(zip(kinds, datas))]
     twins = [_filled_ring(kd, d, 40 + j, k, dseed=j) for j, (kd, d) in enumerate(zip(kinds, datas))]
-    L, M = _learner(H, A, "reference", blob, max_batch=k), _learner(H, A, "reference", blob, max_batch=k)
+    L, M = lh.learner(H, A, "reference", blob, max_batch=k), lh.learner(H, A, "reference", blob, max_batch=k)
     al, cl, tds = L.update_from_many(rings, k)
     rows = M.new_rows(2)
     drawn = []
@@ -690,7 +504,7 @@ def test_update_from_many_over_two_nstep_rings():
     assert torch.equal(al, al2) and torch.equal(cl, cl2) and torch.isfinite(al)
     for a, (_, td) in zip(tds, drawn):
         assert torch.equal(a, td)
-    _same(_state(L), _state(M))
+    lh.same(lh.state(L), lh.state(M))
     assert torch.equal(rings[0].priorities, twins[0].priorities)
 
 
@@ -701,13 +515,13 @@ def test_add_and_update_captured_and_replayed_equal_eager():
     iterations, bitwise.  The ring's host-side pos and count are frozen into the capture, so every eager iteration
     starts its add from the same pos and count as the captured one."""
     H, A, k = 64, 12, 32
-    r = _rollout()
-    out = _out(_done("mid"))
+    r = rr.rollout()
+    out = rr.out(rr.done("mid"))
     blob = dp.init_blob(H, A, 42)
 
     def fresh():
         ring = _new_ring("prioritised", 100, n_step=3, gamma=GAMMA)      # empty: every drawn slot is one the add wrote
-        return _learner(H, A, "reference", blob, max_batch=k), ring
+        return lh.learner(H, A, "reference", blob, max_batch=k), ring
 
     eager, re_ = fresh()
     graphed, rg = fresh()
@@ -726,7 +540,7 @@ def test_add_and_update_captured_and_replayed_equal_eager():
             g_out = iteration(graphed, rg)
     torch.cuda.current_stream().wait_stream(s)
     torch.cuda.synchronize()
-    assert np.array_equal(_state(graphed)["step"], np.zeros(8))           # capture ran nothing
+    assert np.array_equal(lh.state(graphed)["step"], np.zeros(8))           # capture ran nothing
     for c in range(3):
         e_out = iteration(eager, re_)
         g.replay()
@@ -734,11 +548,11 @@ def test_add_and_update_captured_and_replayed_equal_eager():
         for x, y in zip(e_out, g_out):
             assert torch.equal(x, y) and torch.isfinite(x).all(), c
         assert np.array_equal(graphed._get_params(), eager._get_params()), c
-        a, b = _image(rg), _image(re_)
+        a, b = rr.image(rg), rr.image(re_)
         for key in a:                                                   # the written slots: the rest was never initialised
             assert a[key][:NTR].tobytes() == b[key][:NTR].tobytes(), key
-    _same(_state(graphed), _state(eager))
-    assert np.array_equal(_state(graphed)["step"], np.full(8, 3))
+    lh.same(lh.state(graphed), lh.state(eager))
+    assert np.array_equal(lh.state(graphed)["step"], np.full(8, 3))
     for x in (graphed, eager, re_, rg):
         x.check()
 
@@ -762,20 +576,20 @@ def test_a_real_rollout_across_episode_ends(kind):
     host = {key: res[key].cpu().numpy() for key in ("obs", "actions", "reward", "done", "start_obs")}
     assert host["done"][3].all() and host["done"][7].all() and host["done"].sum() == 6
     ring = _new_ring(kind, 400, n_step=3, gamma=GAMMA)
-    _prefill(ring, 20, 20)
-    img = _image(ring)
+    rr.prefill(ring, 20, 20)
+    img = rr.image(ring)
     ring.add_rollout(obs_in, res)
     tr, m = nm.transitions(obs_in.cpu().numpy(), host["obs"], host["actions"], host["reward"], 3, GAMMA, host["done"],
                            host["start_obs"])
     assert m[:, 0].tolist() == [3, 3, 2, 1, 3, 3, 2, 1, 2, 1]
     p2, c2 = nm.ring_add(img, 20, 20, tr)
     assert (ring.pos, ring.count) == (p2, c2) == (170, 170)
-    _same_image(_image(ring), img)
+    rr.same_image(rr.image(ring), img)
     # the learner trains from it (a ring of its own: the prefilled slots above hold sentinels, no transitions)
     fresh = _new_ring(kind, 400, n_step=3, gamma=GAMMA)
     fresh.add_rollout(obs_in, res)
     assert fresh.count == 150 and torch.equal(fresh.discounts[:150], ring.discounts[20:170])
-    L = _learner(32, cfg.na_total, "reference", max_batch=64)
+    L = lh.learner(32, cfg.na_total, "reference", max_batch=64)
     al, cl, _ = L.update_from(fresh, 64)
     L.check()
     assert torch.isfinite(al) and torch.isfinite(cl)

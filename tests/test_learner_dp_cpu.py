@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 import learner_dp_mirror as dp
+import learner_harness as lh
 import learner_mirror as mirror
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -56,7 +57,7 @@ def test_averaging_shard_gradients_is_a_different_rule(K):
     assert _rel(g, mirror.losses_and_grads(blob, c["H"], c["A"], *b, c["gamma"])[3]) <= 1e-12
     naive = dp.averaged_shard_gradients(blob, c["H"], c["A"], shards, c["gamma"])
     na = sum(mirror.layout(c["H"], c["A"])[0][:4])                       # the actor's part: where mean(delta) acts
-    tol = dp.gpu_gradient_tolerance(c["n"], np.abs(g).max())
+    tol = lh.tol_g(c["n"], g)
     assert np.abs(naive[:na] - g[:na]).max() > 100 * tol, (np.abs(naive[:na] - g[:na]).max(), tol)
 
 
