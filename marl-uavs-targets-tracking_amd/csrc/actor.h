@@ -42,7 +42,7 @@
 // here the draw is the inverse CDF of the same probabilities at a Philox uniform keyed by
 // (seed, global env, step_count, uav) -- reproducible, shard-independent, restated by the oracle.
 #pragma once
-#include "internal.h"
+#include "env.h"
 #include "philox.h"
 
 #include <cmath>

@@ -1,132 +1,20 @@
-// api.hip -- the C ABI of libuavtrack.so (include/uavtrack.h): handle lifetime,
+// api_env.hip -- the C ABI of the environment handle (include/uavtrack.h, uavtrack_env): handle lifetime,
 // argument validation, constant folding, and stream-ordered launches.  No compute
 // happens on the host and there is no CPU fallback.
 
-#include "internal.h"
+#include "api_env.h"
 #include "actor.h"
 #include "pmi_pack.h"
 
 #include <cmath>
-#include <cstdarg>
-#include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <new>
-#include <string>
-#include <type_traits>
 #include <vector>
 
 using namespace uavtrack;
 
 namespace {
-
-thread_local std::string g_err;
-
-int fail(const char *fmt, ...)
-{
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    g_err = buf;
-    return 1;
-}
-
-#define HIP_TRY(expr)                                                                  \
-    do {                                                                               \
-        hipError_t e__ = (expr);                                                       \
-        if (e__ != hipSuccess) return fail("%s: %s", #expr, hipGetErrorString(e__));   \
-    } while (0)
-
-// Makes the handle's device current for the duration of one ABI call and gives the caller's device back on
-// return: a process that drives several shards, or keeps PyTorch on another GPU, must not find its current
-// device changed behind its back.
-struct DeviceGuard {
-    int prev = -1;
-    bool changed = false;
-    hipError_t err = hipSuccess;
-    explicit DeviceGuard(int dev)
-    {
-        err = hipGetDevice(&prev);
-        if (err == hipSuccess && prev != dev) {
-            err = hipSetDevice(dev);
-            changed = (err == hipSuccess);
-        }
-    }
-    ~DeviceGuard()
-    {
-        if (changed) (void)hipSetDevice(prev);
-    }
-    DeviceGuard(const DeviceGuard &) = delete;
-    DeviceGuard &operator=(const DeviceGuard &) = delete;
-};
-#define ON_DEVICE(dev)            \
-    DeviceGuard guard__(dev);     \
-    HIP_TRY(guard__.err)
-
-// ---- device buffers: each one is named once, in the list of the set it belongs to, for allocation and release alike
-struct Buf {
-    void **slot;     // the pointer that owns it
-    size_t bytes;    // (read by replace() only: release() takes the same lists)
-    bool zero;       // starts zeroed
-};
-using Bufs = std::vector<Buf>;
-
-template <typename T>
-Buf buf(T *&p, size_t n = 0, bool zero = false)
-{
-    return {reinterpret_cast<void **>(&p), (n ? n : 1) * sizeof(T), zero};
-}
-
-Bufs operator+(Bufs a, const Bufs &b)
-{
-    a.insert(a.end(), b.begin(), b.end());
-    return a;
-}
-
-void release(const Bufs &set)
-{
-    for (const Buf &b : set) {
-        if (*b.slot) (void)hipFree(*b.slot);
-        *b.slot = nullptr;
-    }
-}
-
-// All or nothing: a new buffer for every slot of `set`, zeroed on `st` where marked, before any slot changes; only then
-// are the old buffers freed.  On failure the new ones are freed, every slot keeps what it held, and the error comes back
-// (grown scratch: the handle stays good at its old size).
-hipError_t replace(const Bufs &set, hipStream_t st = nullptr)
-{
-    std::vector<void *> fresh(set.size(), nullptr);
-    hipError_t e = hipSuccess;
-    for (size_t i = 0; i < set.size() && e == hipSuccess; ++i) e = hipMalloc(&fresh[i], set[i].bytes);
-    for (size_t i = 0; i < set.size() && e == hipSuccess; ++i)
-        if (set[i].zero) e = hipMemsetAsync(fresh[i], 0, set[i].bytes, st);
-    if (e != hipSuccess) {
-        for (void *p : fresh)
-            if (p) (void)hipFree(p);
-        return e;
-    }
-    release(set);
-    for (size_t i = 0; i < set.size(); ++i) *set[i].slot = fresh[i];
-    return hipSuccess;
-}
-
-// The device a handle is created on (`fn` names the creating ABI function in the error): visible, and a gfx950.
-int accept_device(const char *fn, int device_id, hipDeviceProp_t *prop)
-{
-    int ndev = 0;
-    hipError_t e = hipGetDeviceCount(&ndev);
-    if (e != hipSuccess || ndev < 1)
-        return fail("%s: no HIP device visible (%s); libuavtrack has no CPU fallback", fn,
-                    e != hipSuccess ? hipGetErrorString(e) : "device count 0");
-    if (device_id < 0 || device_id >= ndev) return fail("%s: device_id %d out of range [0, %d)", fn, device_id, ndev);
-    HIP_TRY(hipGetDeviceProperties(prop, device_id));
-    if (strncmp(prop->gcnArchName, "gfx950", 6) != 0)
-        return fail("%s: device %d is %s; this library is built for gfx950 only", fn, device_id, prop->gcnArchName);
-    return 0;
-}
 
 void drop_profile(uavtrack_env *env)
 {
@@ -387,10 +275,6 @@ HostLayout host_layout(const uavtrack_config &c)
 }  // namespace
 
 extern "C" {
-
-int uavtrack_version(void) { return UAVTRACK_ABI_VERSION; }
-
-const char *uavtrack_last_error(void) { return g_err.c_str(); }
 
 int uavtrack_create(const uavtrack_config *cfg, uavtrack_env **out)
 {
@@ -744,7 +628,7 @@ int uavtrack_pmi_info(uavtrack_env *env, int64_t out[4], void *stream)
     out[0] = pmi_effective_scheme(env);
     out[1] = env->pmi.hidden;
     out[2] = env->pmi.t3 ? 1 : 0;
-    if (env->pmi.dev_published && pmi_t3_floats(env->pmi.hidden)) {
+    if (env->pmi.dev_published && PmiBlobLayout::make(env->pmi.hidden).t3_len) {
         // the verdict of the last device publish is the device's: read it (this call synchronises anyway)
         ON_DEVICE(env->cfg.device_id);
         hipStream_t st = static_cast<hipStream_t>(stream);
@@ -781,10 +665,12 @@ int uavtrack_pmi_publish_info(uavtrack_env *env, int64_t out[2], void *stream)
     return 0;
 }
 
+}  // extern "C"
+
 // The device pack behind uavtrack_publish_pmi_weights and uavtrack_pmi_trainer_publish (the caller has tested the handle
 // and the pointers): refused, with nothing enqueued, unless weights of the same width are installed.
-static int publish_pmi(const char *fn, uavtrack_env *env, const float *const tensors[kPmiStateTensors], int32_t hidden,
-                       void *stream)
+int uavtrack::publish_pmi(const char *fn, uavtrack_env *env, const float *const tensors[kPmiStateTensors], int32_t hidden,
+                          void *stream)
 {
     if (!env->pmi.blob) return fail("%s: no weights installed: uavtrack_set_pmi_weights sizes the allocation first", fn);
     if (hidden != env->pmi.hidden_raw)
@@ -807,6 +693,8 @@ static int publish_pmi(const char *fn, uavtrack_env *env, const float *const ten
     env->pmi.dev_published = true;
     return 0;
 }
+
+extern "C" {
 
 int uavtrack_publish_pmi_weights(uavtrack_env *env, const uavtrack_pmi_tensors *t, int32_t hidden, void *stream)
 {
@@ -1076,10 +964,12 @@ int uavtrack_set_actor_weights(uavtrack_env *env, const float *w1, const float *
     return 0;
 }
 
+}  // extern "C"
+
 // The device pack behind uavtrack_publish_actor_weights and uavtrack_learner_publish_actor (the caller has tested the
 // handle and the pointers): refused, with nothing enqueued, unless an actor of the same width is installed.
-static int publish_actor(const char *fn, uavtrack_env *env, const float *w1, const float *b1, const float *w2,
-                         const float *b2, int32_t hidden, int32_t n_actions, void *stream)
+int uavtrack::publish_actor(const char *fn, uavtrack_env *env, const float *w1, const float *b1, const float *w2,
+                            const float *b2, int32_t hidden, int32_t n_actions, void *stream)
 {
     if (!env->actor_w) return fail("%s: no actor installed: uavtrack_set_actor_weights sizes the blob first", fn);
     if (hidden != env->actor_hidden)
@@ -1098,6 +988,8 @@ static int publish_actor(const char *fn, uavtrack_env *env, const float *w1, con
     HIP_TRY(launch_actor_pack(a, static_cast<hipStream_t>(stream)));
     return 0;
 }
+
+extern "C" {
 
 int uavtrack_publish_actor_weights(uavtrack_env *env, const float *w1, const float *b1, const float *w2, const float *b2,
                                    int32_t hidden, void *stream)
@@ -1311,1064 +1203,6 @@ int uavtrack_kernel_info(uavtrack_env *env, int64_t out[5])
     out[2] = env->geo.groups;
     out[3] = (int64_t)env->geo.lds_bytes;
     out[4] = env->geo.specialised;
-    return 0;
-}
-
-}  // extern "C"
-
-// ---- the device-side handles: learner, PMI trainer, replay ring, episode results ---------------------------------------------------
-
-struct uavtrack_learner {
-    uavtrack_learner_config cfg;
-    LearnerDevice d;
-    double reg[3] = {0.0, INFINITY, INFINITY};   // uavtrack_learner_get_regularisation: the values as they were set
-};
-
-struct uavtrack_pmi_trainer {
-    uavtrack_pmi_trainer_config cfg;
-    PmiTrainDevice d;
-};
-
-struct uavtrack_replay {
-    uavtrack_replay_config cfg;
-    ReplayDevice d;
-};
-
-struct uavtrack_episode_stats {
-    uavtrack_episode_stats_config cfg;
-    EpisodeDevice d;
-};
-
-namespace {
-
-constexpr int64_t kLearnerDefaultBatch = 65536;
-constexpr int64_t kLearnerMaxBatch = ((int64_t)1 << 31) - 1;   // row numbers are int32 in the priority write
-constexpr int64_t kPmiTrainDefaultBatch = 4096;
-constexpr int64_t kReplayMaxBatch = ((int64_t)1 << 31) - 1;   // draw numbers are Philox counter word 0
-constexpr int64_t kReplayMaxCapacity = (int64_t)kReplayTile * ((int64_t)1 << 30);   // tile numbers are int32
-
-// Each handle's device buffers (device_bufs: all of them, sized from the handle's fields) and the word through which
-// its calls are refused on the device.  The two trainers share the torch.optim.Adam state (AdamState, internal.h).
-Bufs adam_bufs(AdamState &o)
-{
-    return {buf(o.m, o.P, true), buf(o.v, o.P, true), buf(o.steps, o.tensors, true), buf(o.status, 1, true),
-            buf(o.errors, 1, true)};
-}
-
-Bufs scratch_bufs(LearnerDevice &d, int64_t max_n) { return {buf(d.td, max_n), buf(d.last, max_n)}; }
-
-Bufs device_bufs(LearnerDevice &d)
-{
-    const size_t P = (size_t)d.L.P;
-    return adam_bufs(d.opt) + Bufs{buf(d.params, P, true), buf(d.gstatus, 1, true), buf(d.partials, kLearnerMaxGroups * (P + 4)), buf(d.scal, 2),
-                                   buf(d.gsum, P), buf(d.sq, 2 * (size_t)learner_clip_groups(d.L)), buf(d.coef, 2)} +
-           scratch_bufs(d, d.max_n);
-}
-
-Bufs scratch_bufs(PmiTrainDevice &d, int64_t max_b)
-{
-    const size_t H = (size_t)d.L.H, nb = (size_t)max_b;
-    return {buf(d.xh0, 2 * 3 * H * nb), buf(d.a0, 2 * 3 * H * nb), buf(d.da0, 2 * 3 * H * nb), buf(d.xh1, 2 * H * nb),
-            buf(d.a1, 2 * H * nb), buf(d.dz1, 2 * H * nb), buf(d.go, 2 * nb), buf(d.sel, 2 * 12 * nb), buf(d.sel_t, nb),
-            buf(d.sel_u, 2 * nb)};
-}
-
-Bufs device_bufs(PmiTrainDevice &d)
-{
-    const size_t S = (size_t)d.L.S, P = (size_t)d.L.P, H = (size_t)d.L.H;
-    return adam_bufs(d.opt) + Bufs{buf(d.state, S, true), buf(d.nbt, kPmiBlocks, true), buf(d.grad, P, true),
-                                   buf(d.inv0, 2 * 3 * H), buf(d.inv1, 2 * H), buf(d.acc, 1)} +
-           scratch_bufs(d, d.max_b);
-}
-
-Bufs device_bufs(ReplayDevice &d)
-{
-    const size_t tiles = (size_t)((d.max_capacity + kReplayTile - 1) / kReplayTile);
-    return {buf(d.prefix, tiles), buf(d.tile_last, tiles), buf(d.counter, 2, true), buf(d.pmin, 1),
-            buf(d.pdraw, (size_t)d.max_batch), buf(d.parts, kReplayMaxParts + 1), buf(d.status, 1, true),
-            buf(d.errors, 1, true)};
-}
-
-Bufs device_bufs(EpisodeDevice &d)
-{
-    const size_t B = (size_t)d.B;
-    return {buf(d.step_sums, (size_t)d.max_steps * 4 * B), buf(d.acc, 4 * B, true), buf(d.cov_sum, B, true),
-            buf(d.cov_max, B, true), buf(d.steps, B, true), buf(d.ordinal, B, true),
-            buf(d.slots, (size_t)d.max_steps * (size_t)episode_groups(d.B)), buf(d.head, 3, true),
-            buf(d.log, (size_t)d.log_capacity)};
-}
-
-int *refusal_word(const LearnerDevice &d) { return d.opt.errors; }
-int *refusal_word(const PmiTrainDevice &d) { return d.opt.errors; }
-int *refusal_word(const ReplayDevice &d) { return d.errors; }
-
-// *_create: the null and struct_size tests, the config's ranges (`check`), the device, then the handle with the fields
-// `init` derives from the config (it may return an error of its own), every buffer of device_bufs() at once, and a
-// device synchronisation.  A failure leaves nothing behind.
-template <typename H, typename Cfg, typename Check, typename Init>
-int create_handle(const char *fn, const Cfg *cfg, H **out, Check check, Init init)
-{
-    if (!cfg || !out) return fail("%s: null argument", fn);
-    *out = nullptr;
-    if (cfg->struct_size != sizeof(Cfg))
-        return fail("%s: struct_size %u != %zu (header / library mismatch)", fn, cfg->struct_size, sizeof(Cfg));
-    if (check(fn, *cfg)) return 1;
-    hipDeviceProp_t prop;
-    if (accept_device(fn, cfg->device_id, &prop)) return 1;
-    ON_DEVICE(cfg->device_id);
-    H *h = new (std::nothrow) H();
-    if (!h) return fail("%s: out of host memory", fn);
-    h->cfg = *cfg;
-    hipError_t e = init(h->d, *cfg);
-    if (e == hipSuccess) e = replace(device_bufs(h->d));
-    if (e == hipSuccess) e = hipDeviceSynchronize();
-    if (e != hipSuccess) {
-        release(device_bufs(h->d));
-        delete h;
-        return fail("%s: %s", fn, hipGetErrorString(e));
-    }
-    *out = h;
-    return 0;
-}
-
-template <typename H>
-int destroy_handle(H *h)
-{
-    if (!h) return 0;
-    DeviceGuard guard(h->cfg.device_id);
-    (void)hipDeviceSynchronize();
-    release(device_bufs(h->d));
-    delete h;
-    return 0;
-}
-
-// *_reserve: scratch for `max_batch` rows (grow-only; `rows` holds what is reserved), the new set allocated before the
-// old one goes.
-template <typename H, typename D>
-int reserve_scratch(const char *fn, H *h, int64_t max_batch, int64_t limit, int64_t D::*rows)
-{
-    if (!h) return fail("%s: null handle", fn);
-    if (max_batch < 1 || max_batch > limit)
-        return fail("%s: max_batch %lld out of range [1, %lld]", fn, (long long)max_batch, (long long)limit);
-    if (max_batch <= h->d.*rows) return 0;
-    ON_DEVICE(h->cfg.device_id);
-    HIP_TRY(hipDeviceSynchronize());          // in-flight calls may still use the old scratch
-    HIP_TRY(replace(scratch_bufs(h->d, max_batch)));
-    h->d.*rows = max_batch;
-    return 0;
-}
-
-// The batch tests of uavtrack_learner_update / _grad / _write_priorities, after their null tests: n, the reserved
-// scratch, the store's capacity, and n against it when no indices choose the rows (`dir`: "from" or "into" the store).
-int accept_batch(const char *fn, const uavtrack_learner *l, int64_t n, int64_t capacity, const int64_t *indices,
-                 const char *dir)
-{
-    if (n < 1) return fail("%s: n = %lld < 1", fn, (long long)n);
-    if (n > l->d.max_n)
-        return fail("%s: n = %lld rows, scratch is reserved for %lld (uavtrack_learner_reserve)", fn, (long long)n,
-                    (long long)l->d.max_n);
-    if (capacity < 1) return fail("%s: capacity = %lld < 1", fn, (long long)capacity);
-    if (!indices && n > capacity)
-        return fail("%s: n = %lld rows without indices %s a store of %lld", fn, (long long)n, dir, (long long)capacity);
-    return 0;
-}
-
-// uavtrack_learner_update / _grad while an entropy buffer is installed: the batch must fit into it
-int accept_entropy_rows(const char *fn, const uavtrack_learner *l, int64_t n)
-{
-    if (l->d.entropy && n > l->d.entropy_rows)
-        return fail("%s: n = %lld rows, the installed entropy buffer holds %lld (uavtrack_learner_set_diagnostics)", fn,
-                    (long long)n, (long long)l->d.entropy_rows);
-    return 0;
-}
-
-// the fields uavtrack_learner_update and _grad (and their weighted forms) fill alike; the others are null
-LearnerLaunch learner_batch(int64_t n, const float *states, const int32_t *actions, const float *rewards,
-                            const float *next_states, int64_t capacity, const int64_t *indices, const float *weights,
-                            const float *discounts, float *td_delta)
-{
-    LearnerLaunch q = {};
-    q.n = n; q.capacity = capacity; q.td_delta = td_delta; q.weights = weights; q.discounts = discounts;
-    q.states = states; q.rewards = rewards; q.next_states = next_states; q.actions = actions; q.idx = indices;
-    return q;
-}
-
-// *_set/get_optimizer_state of a trainer: exp_avg, exp_avg_sq [P] and step [tensors] in from the host (const
-// pointers; everything is validated before the first copy, so a refused load leaves the previous state in place) or
-// out to it.  `has` completes the size message: "<n> floats, <has % P>".
-template <typename H, typename F, typename S>
-int optimizer_state(const char *fn, H *h, F *exp_avg, F *exp_avg_sq, S *step, int64_t n_floats, void *stream,
-                    const char *has)
-{
-    if (!h || !exp_avg || !exp_avg_sq || !step) return fail("%s: null argument", fn);
-    const AdamState &o = h->d.opt;
-    if (n_floats != h->d.L.P) {
-        char what[96];
-        snprintf(what, sizeof what, has, h->d.L.P);
-        return fail("%s: %lld floats, %s", fn, (long long)n_floats, what);
-    }
-    ON_DEVICE(h->cfg.device_id);
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    if constexpr (std::is_const<F>::value) {
-        for (int t = 0; t < o.tensors; ++t)
-            if (step[t] < 0) return fail("%s: step[%d] = %lld < 0", fn, t, (long long)step[t]);
-        for (int64_t p = 0; p < o.P; ++p)
-            if (!(exp_avg_sq[p] >= 0.0f)) return fail("%s: exp_avg_sq[%lld] is not >= 0", fn, (long long)p);
-        HIP_TRY(hipStreamSynchronize(st));
-        HIP_TRY(hipMemcpyAsync(o.m, exp_avg, (size_t)o.P * 4, hipMemcpyHostToDevice, st));
-        HIP_TRY(hipMemcpyAsync(o.v, exp_avg_sq, (size_t)o.P * 4, hipMemcpyHostToDevice, st));
-        HIP_TRY(hipMemcpyAsync(o.steps, step, (size_t)o.tensors * 8, hipMemcpyHostToDevice, st));
-    } else {
-        HIP_TRY(hipMemcpyAsync(exp_avg, o.m, (size_t)o.P * 4, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipMemcpyAsync(exp_avg_sq, o.v, (size_t)o.P * 4, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipMemcpyAsync(step, o.steps, (size_t)o.tensors * 8, hipMemcpyDeviceToHost, st));
-    }
-    HIP_TRY(hipStreamSynchronize(st));
-    return 0;
-}
-
-// *_check: the calls refused on the device since the last check (`count`, and `refused` when given), the count
-// cleared; synchronises the stream.
-template <typename H>
-int take_refusals(const char *fn, H *h, int64_t *refused, void *stream, int *count)
-{
-    if (!h) return fail("%s: null handle", fn);
-    ON_DEVICE(h->cfg.device_id);
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    HIP_TRY(hipMemcpyAsync(count, refusal_word(h->d), 4, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemsetAsync(refusal_word(h->d), 0, 4, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    if (refused) *refused = *count;
-    return 0;
-}
-
-}  // namespace
-
-// ---- the device learner -------------------------------------------------------------------------------------------
-
-extern "C" {
-
-int uavtrack_learner_create(const uavtrack_learner_config *cfg, uavtrack_learner **out)
-{
-    auto check = [](const char *fn, const uavtrack_learner_config &c) {
-        if (c.hidden < 1 || c.hidden > kLearnerMaxHidden)
-            return fail("%s: hidden %d out of range [1, %d]", fn, c.hidden, kLearnerMaxHidden);
-        if (c.n_actions < 1 || c.n_actions > kLearnerMaxActions)
-            return fail("%s: n_actions %d out of range [1, %d]", fn, c.n_actions, kLearnerMaxActions);
-        if (c.loss != UAVTRACK_LOSS_REFERENCE && c.loss != UAVTRACK_LOSS_PER_SAMPLE)
-            return fail("%s: unknown loss form %d", fn, c.loss);
-        if (c.max_batch < 0 || c.max_batch > kLearnerMaxBatch)
-            return fail("%s: max_batch %lld out of range [0, %lld]", fn, (long long)c.max_batch, (long long)kLearnerMaxBatch);
-        if (!std::isfinite(c.gamma) || !std::isfinite(c.actor_lr) || !std::isfinite(c.critic_lr) || c.actor_lr < 0 ||
-            c.critic_lr < 0)
-            return fail("%s: gamma and the learning rates must be finite, the rates >= 0", fn);
-        return 0;
-    };
-    auto init = [](LearnerDevice &d, const uavtrack_learner_config &c) {
-        d.L = LearnerLayout::make(c.hidden, c.n_actions);
-        d.gamma = (float)c.gamma;
-        d.actor_lr = (float)c.actor_lr;
-        d.critic_lr = (float)c.critic_lr;
-        d.per_sample = c.loss == UAVTRACK_LOSS_PER_SAMPLE;
-        d.opt.tensors = kLearnerTensors;
-        d.opt.P = d.L.P;
-        d.max_n = c.max_batch ? c.max_batch : kLearnerDefaultBatch;
-        d.max_norm[0] = d.max_norm[1] = INFINITY;       // regularisation off: entropy_coef 0, no diagnostics
-        return learner_prepare_kernels(d.L);
-    };
-    return create_handle(__func__, cfg, out, check, init);
-}
-
-int uavtrack_learner_destroy(uavtrack_learner *learner) { return destroy_handle(learner); }
-
-int uavtrack_learner_num_params(uavtrack_learner *learner, int64_t *out)
-{
-    if (!learner || !out) return fail("uavtrack_learner_num_params: null argument");
-    *out = learner->d.L.P;
-    return 0;
-}
-
-int uavtrack_learner_set_regularisation(uavtrack_learner *learner, double entropy_coef, double actor_max_norm,
-                                        double critic_max_norm)
-{
-    if (!learner) return fail("%s: null handle", __func__);
-    if (!std::isfinite(entropy_coef) || entropy_coef < 0)
-        return fail("%s: entropy_coef = %g must be finite and >= 0", __func__, entropy_coef);
-    if (!(actor_max_norm > 0) || !(critic_max_norm > 0))
-        return fail("%s: max norms (%g, %g) must be > 0, or +inf for no clipping", __func__, actor_max_norm, critic_max_norm);
-    if (entropy_coef != 0 && !learner->d.per_sample)
-        return fail("%s: entropy_coef = %g on a UAVTRACK_LOSS_REFERENCE learner: that form scales the actor's gradient "
-                    "sums once by -mean(delta) / N, a factor an entropy term cannot share; use UAVTRACK_LOSS_PER_SAMPLE",
-                    __func__, entropy_coef);
-    learner->d.entropy_coef = (float)entropy_coef;
-    learner->d.max_norm[0] = actor_max_norm;
-    learner->d.max_norm[1] = critic_max_norm;
-    learner->reg[0] = entropy_coef; learner->reg[1] = actor_max_norm; learner->reg[2] = critic_max_norm;
-    return 0;
-}
-
-int uavtrack_learner_get_regularisation(uavtrack_learner *learner, double out[3])
-{
-    if (!learner || !out) return fail("%s: null argument", __func__);
-    for (int k = 0; k < 3; ++k) out[k] = learner->reg[k];
-    return 0;
-}
-
-int uavtrack_learner_set_diagnostics(uavtrack_learner *learner, float *entropy, int64_t capacity_rows, float *grad_norm)
-{
-    if (!learner) return fail("%s: null handle", __func__);
-    if (entropy && capacity_rows < 1)
-        return fail("%s: capacity_rows = %lld < 1 with an entropy buffer", __func__, (long long)capacity_rows);
-    learner->d.entropy = entropy;
-    learner->d.entropy_rows = entropy ? capacity_rows : 0;
-    learner->d.grad_norm = grad_norm;
-    return 0;
-}
-
-int uavtrack_learner_reserve(uavtrack_learner *learner, int64_t max_batch)
-{
-    return reserve_scratch(__func__, learner, max_batch, kLearnerMaxBatch, &LearnerDevice::max_n);
-}
-
-int uavtrack_learner_set_params(uavtrack_learner *learner, const float *params, int64_t n_floats, void *stream)
-{
-    if (!learner || !params) return fail("uavtrack_learner_set_params: null argument");
-    if (n_floats != learner->d.L.P)
-        return fail("uavtrack_learner_set_params: %lld floats, the networks have %d", (long long)n_floats, learner->d.L.P);
-    ON_DEVICE(learner->cfg.device_id);
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    HIP_TRY(hipStreamSynchronize(st));
-    HIP_TRY(hipMemcpyAsync(learner->d.params, params, (size_t)n_floats * 4, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    return 0;
-}
-
-int uavtrack_learner_get_params(uavtrack_learner *learner, float *params, int64_t n_floats, void *stream)
-{
-    if (!learner || !params) return fail("uavtrack_learner_get_params: null argument");
-    if (n_floats != learner->d.L.P)
-        return fail("uavtrack_learner_get_params: %lld floats, the networks have %d", (long long)n_floats, learner->d.L.P);
-    ON_DEVICE(learner->cfg.device_id);
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    HIP_TRY(hipMemcpyAsync(params, learner->d.params, (size_t)n_floats * 4, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    return 0;
-}
-
-int uavtrack_learner_publish_actor(uavtrack_learner *learner, uavtrack_env *env, void *stream)
-{
-    if (!learner || !env) return fail("uavtrack_learner_publish_actor: null handle");
-    if (learner->cfg.device_id != env->cfg.device_id)
-        return fail("uavtrack_learner_publish_actor: the learner is on device %d, the environment on device %d",
-                    learner->cfg.device_id, env->cfg.device_id);
-    const LearnerLayout &L = learner->d.L;
-    const float *p = learner->d.params;
-    return publish_actor(__func__, env, p + L.a_w1, p + L.a_b1, p + L.a_w2, p + L.a_b2, L.H, L.A, stream);
-}
-
-int uavtrack_pmi_trainer_publish(uavtrack_pmi_trainer *trainer, uavtrack_env *env, void *stream)
-{
-    if (!trainer || !env) return fail("uavtrack_pmi_trainer_publish: null handle");
-    if (trainer->cfg.device_id != env->cfg.device_id)
-        return fail("uavtrack_pmi_trainer_publish: the trainer is on device %d, the environment on device %d",
-                    trainer->cfg.device_id, env->cfg.device_id);
-    const PmiTrainLayout &L = trainer->d.L;
-    const float *p[kPmiStateTensors];
-    for (int k = 0; k < kPmiStateTensors; ++k) p[k] = trainer->d.state + L.soff[k];
-    return publish_pmi(__func__, env, p, L.H, stream);
-}
-
-int uavtrack_learner_set_optimizer_state(uavtrack_learner *learner, const float *exp_avg, const float *exp_avg_sq,
-                                         const int64_t *step, int64_t n_floats, void *stream)
-{
-    return optimizer_state(__func__, learner, exp_avg, exp_avg_sq, step, n_floats, stream, "the networks have %d");
-}
-
-int uavtrack_learner_get_optimizer_state(uavtrack_learner *learner, float *exp_avg, float *exp_avg_sq, int64_t *step,
-                                         int64_t n_floats, void *stream)
-{
-    return optimizer_state(__func__, learner, exp_avg, exp_avg_sq, step, n_floats, stream, "the networks have %d");
-}
-
-}  // extern "C"
-
-namespace {
-
-// uavtrack_learner_update, _update_weighted and _update_discounted (`fn`: the caller's name; weights, discounts nullable)
-int learner_update(const char *fn, uavtrack_learner *learner, int64_t n, const float *states, const int32_t *actions,
-                   const float *rewards, const float *next_states, int64_t capacity, const int64_t *indices,
-                   const float *weights, const float *discounts, float *actor_loss, float *critic_loss, float *td_delta, float *priorities,
-                   void *stream)
-{
-    if (!learner) return fail("%s: null handle", fn);
-    if (!states || !actions || !rewards || !next_states)
-        return fail("%s: states, actions, rewards and next_states must not be null", fn);
-    if (!actor_loss || !critic_loss) return fail("%s: actor_loss and critic_loss must not be null", fn);
-    if (accept_batch(fn, learner, n, capacity, indices, "from") || accept_entropy_rows(fn, learner, n)) return 1;
-    ON_DEVICE(learner->cfg.device_id);
-    LearnerLaunch q = learner_batch(n, states, actions, rewards, next_states, capacity, indices, weights, discounts, td_delta);
-    q.actor_loss = actor_loss; q.critic_loss = critic_loss; q.priorities = priorities;
-    HIP_TRY(launch_learner_update(learner->d, q, static_cast<hipStream_t>(stream)));
-    return 0;
-}
-
-// uavtrack_learner_grad, _grad_weighted and _grad_discounted
-int learner_grad(const char *fn, uavtrack_learner *learner, int64_t n, const float *states, const int32_t *actions,
-                 const float *rewards, const float *next_states, int64_t capacity, const int64_t *indices,
-                 const float *weights, const float *discounts, float *td_delta, float *row, void *stream)
-{
-    if (!learner) return fail("%s: null handle", fn);
-    if (!states || !actions || !rewards || !next_states)
-        return fail("%s: states, actions, rewards and next_states must not be null", fn);
-    if (!td_delta || !row) return fail("%s: td_delta and row must not be null", fn);
-    if (accept_batch(fn, learner, n, capacity, indices, "from") || accept_entropy_rows(fn, learner, n)) return 1;
-    ON_DEVICE(learner->cfg.device_id);
-    const LearnerLaunch q = learner_batch(n, states, actions, rewards, next_states, capacity, indices, weights, discounts,
-                                          td_delta);
-    HIP_TRY(launch_learner_grad(learner->d, q, row, static_cast<hipStream_t>(stream)));
-    return 0;
-}
-
-}  // namespace
-
-extern "C" {
-
-int uavtrack_learner_update(uavtrack_learner *learner, int64_t n, const float *states, const int32_t *actions,
-                            const float *rewards, const float *next_states, int64_t capacity, const int64_t *indices,
-                            float *actor_loss, float *critic_loss, float *td_delta, float *priorities, void *stream)
-{
-    return learner_update(__func__, learner, n, states, actions, rewards, next_states, capacity, indices, nullptr, nullptr,
-                          actor_loss, critic_loss, td_delta, priorities, stream);
-}
-
-int uavtrack_learner_update_weighted(uavtrack_learner *learner, int64_t n, const float *states, const int32_t *actions,
-                                     const float *rewards, const float *next_states, int64_t capacity,
-                                     const int64_t *indices, const float *weights, float *actor_loss, float *critic_loss,
-                                     float *td_delta, float *priorities, void *stream)
-{
-    return learner_update(__func__, learner, n, states, actions, rewards, next_states, capacity, indices, weights, nullptr,
-                          actor_loss, critic_loss, td_delta, priorities, stream);
-}
-
-int uavtrack_learner_update_discounted(uavtrack_learner *learner, int64_t n, const float *states, const int32_t *actions,
-                                       const float *rewards, const float *next_states, int64_t capacity,
-                                       const int64_t *indices, const float *weights, const float *discounts,
-                                       float *actor_loss, float *critic_loss, float *td_delta, float *priorities,
-                                       void *stream)
-{
-    return learner_update(__func__, learner, n, states, actions, rewards, next_states, capacity, indices, weights, discounts,
-                          actor_loss, critic_loss, td_delta, priorities, stream);
-}
-
-int uavtrack_learner_row_floats(uavtrack_learner *learner, int64_t *out)
-{
-    if (!learner || !out) return fail("uavtrack_learner_row_floats: null argument");
-    *out = (int64_t)learner->d.L.P + kLearnerRowTail;
-    return 0;
-}
-
-int uavtrack_learner_grad(uavtrack_learner *learner, int64_t n, const float *states, const int32_t *actions,
-                          const float *rewards, const float *next_states, int64_t capacity, const int64_t *indices,
-                          float *td_delta, float *row, void *stream)
-{
-    return learner_grad(__func__, learner, n, states, actions, rewards, next_states, capacity, indices, nullptr, nullptr,
-                        td_delta, row, stream);
-}
-
-int uavtrack_learner_grad_weighted(uavtrack_learner *learner, int64_t n, const float *states, const int32_t *actions,
-                                   const float *rewards, const float *next_states, int64_t capacity,
-                                   const int64_t *indices, const float *weights, float *td_delta, float *row, void *stream)
-{
-    return learner_grad(__func__, learner, n, states, actions, rewards, next_states, capacity, indices, weights, nullptr,
-                        td_delta, row, stream);
-}
-
-int uavtrack_learner_grad_discounted(uavtrack_learner *learner, int64_t n, const float *states, const int32_t *actions,
-                                     const float *rewards, const float *next_states, int64_t capacity,
-                                     const int64_t *indices, const float *weights, const float *discounts, float *td_delta,
-                                     float *row, void *stream)
-{
-    return learner_grad(__func__, learner, n, states, actions, rewards, next_states, capacity, indices, weights, discounts,
-                        td_delta, row, stream);
-}
-
-int uavtrack_learner_apply(uavtrack_learner *learner, const float *rows, int64_t count, float *actor_loss,
-                           float *critic_loss, void *stream)
-{
-    if (!learner) return fail("uavtrack_learner_apply: null handle");
-    if (!rows) return fail("uavtrack_learner_apply: rows must not be null");
-    if (!actor_loss || !critic_loss) return fail("uavtrack_learner_apply: actor_loss and critic_loss must not be null");
-    if (count < 1 || count > UAVTRACK_LEARNER_MAX_ROWS)
-        return fail("uavtrack_learner_apply: count = %lld out of range [1, %d]", (long long)count, UAVTRACK_LEARNER_MAX_ROWS);
-    ON_DEVICE(learner->cfg.device_id);
-    HIP_TRY(launch_learner_apply(learner->d, rows, (int)count, actor_loss, critic_loss, static_cast<hipStream_t>(stream)));
-    return 0;
-}
-
-int uavtrack_learner_write_priorities(uavtrack_learner *learner, int64_t n, const int64_t *indices, int64_t capacity,
-                                      const float *td_delta, float *priorities, void *stream)
-{
-    if (!learner) return fail("uavtrack_learner_write_priorities: null handle");
-    if (!td_delta || !priorities) return fail("uavtrack_learner_write_priorities: td_delta and priorities must not be null");
-    if (accept_batch(__func__, learner, n, capacity, indices, "into")) return 1;
-    ON_DEVICE(learner->cfg.device_id);
-    HIP_TRY(launch_learner_priorities(learner->d, indices, n, capacity, td_delta, priorities,
-                                      static_cast<hipStream_t>(stream)));
-    return 0;
-}
-
-int uavtrack_learner_values(uavtrack_learner *learner, int64_t n, const float *rows, float *values, void *stream)
-{
-    if (!learner) return fail("%s: null handle", __func__);
-    if (!rows || !values) return fail("%s: rows and values must not be null", __func__);
-    if (n < 1) return fail("%s: n = %lld < 1", __func__, (long long)n);
-    if (n > INT64_MAX / 48) return fail("%s: n = %lld rows overflow", __func__, (long long)n);
-    if (((uintptr_t)rows & 15) != 0) return fail("%s: rows must be 16-byte aligned", __func__);
-    ON_DEVICE(learner->cfg.device_id);
-    HIP_TRY(launch_learner_values(learner->d, n, rows, values, static_cast<hipStream_t>(stream)));
-    return 0;
-}
-
-int uavtrack_learner_check(uavtrack_learner *learner, int64_t *refused, void *stream)
-{
-    int count = 0;
-    if (take_refusals(__func__, learner, refused, stream, &count)) return 1;
-    if (count)
-        return fail("uavtrack_learner_check: %d update(s) refused: an action outside [0, %d), an index outside "
-                    "[0, capacity), an importance weight that is NaN, infinite or negative or a discount that is NaN or "
-                    "outside [0, 1], or (uavtrack_learner_apply) a gradient row of another layout; they changed nothing",
-                    count, learner->d.L.A);
-    return 0;
-}
-
-// ---- the device PMI trainer ---------------------------------------------------------------------------------------
-
-int uavtrack_pmi_trainer_create(const uavtrack_pmi_trainer_config *cfg, uavtrack_pmi_trainer **out)
-{
-    auto check = [](const char *fn, const uavtrack_pmi_trainer_config &c) {
-        if (c.hidden < 1 || c.hidden > kPmiMaxHidden)
-            return fail("%s: hidden %d out of range [1, %d]", fn, c.hidden, kPmiMaxHidden);
-        if (c.max_batch < 0 || c.max_batch > kPmiTrainMaxBatch)
-            return fail("%s: max_batch %lld out of range [0, %lld]", fn, (long long)c.max_batch, (long long)kPmiTrainMaxBatch);
-        if (!std::isfinite(c.lr) || c.lr < 0) return fail("%s: lr must be finite and >= 0", fn);
-        return 0;
-    };
-    auto init = [](PmiTrainDevice &d, const uavtrack_pmi_trainer_config &c) {
-        d.L = PmiTrainLayout::make(c.hidden);
-        d.lr = (float)c.lr;
-        d.opt.tensors = kPmiTrainTensors;
-        d.opt.P = d.L.P;
-        d.max_b = c.max_batch ? c.max_batch : kPmiTrainDefaultBatch;
-        return hipSuccess;
-    };
-    return create_handle(__func__, cfg, out, check, init);
-}
-
-int uavtrack_pmi_trainer_destroy(uavtrack_pmi_trainer *trainer) { return destroy_handle(trainer); }
-
-int uavtrack_pmi_trainer_num_params(uavtrack_pmi_trainer *trainer, int64_t *n_state, int64_t *n_train)
-{
-    if (!trainer || !n_state || !n_train) return fail("uavtrack_pmi_trainer_num_params: null argument");
-    *n_state = trainer->d.L.S;
-    *n_train = trainer->d.L.P;
-    return 0;
-}
-
-int uavtrack_pmi_trainer_reserve(uavtrack_pmi_trainer *trainer, int64_t max_batch)
-{
-    return reserve_scratch(__func__, trainer, max_batch, kPmiTrainMaxBatch, &PmiTrainDevice::max_b);
-}
-
-int uavtrack_pmi_trainer_set_params(uavtrack_pmi_trainer *trainer, const float *state, const int64_t *num_batches_tracked,
-                                    int64_t n_state, void *stream)
-{
-    if (!trainer || !state || !num_batches_tracked) return fail("uavtrack_pmi_trainer_set_params: null argument");
-    PmiTrainDevice &d = trainer->d;
-    if (n_state != d.L.S)
-        return fail("uavtrack_pmi_trainer_set_params: %lld floats, the network's state has %d", (long long)n_state, d.L.S);
-    for (int b = 0; b < kPmiBlocks; ++b)
-        if (num_batches_tracked[b] < 0)
-            return fail("uavtrack_pmi_trainer_set_params: num_batches_tracked[%d] = %lld < 0", b,
-                        (long long)num_batches_tracked[b]);
-    ON_DEVICE(trainer->cfg.device_id);
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    HIP_TRY(hipStreamSynchronize(st));
-    HIP_TRY(hipMemcpyAsync(d.state, state, (size_t)n_state * 4, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(d.nbt, num_batches_tracked, kPmiBlocks * 8, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    return 0;
-}
-
-int uavtrack_pmi_trainer_get_params(uavtrack_pmi_trainer *trainer, float *state, int64_t *num_batches_tracked,
-                                    int64_t n_state, void *stream)
-{
-    if (!trainer || !state || !num_batches_tracked) return fail("uavtrack_pmi_trainer_get_params: null argument");
-    PmiTrainDevice &d = trainer->d;
-    if (n_state != d.L.S)
-        return fail("uavtrack_pmi_trainer_get_params: %lld floats, the network's state has %d", (long long)n_state, d.L.S);
-    ON_DEVICE(trainer->cfg.device_id);
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    HIP_TRY(hipMemcpyAsync(state, d.state, (size_t)n_state * 4, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(num_batches_tracked, d.nbt, kPmiBlocks * 8, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    return 0;
-}
-
-int uavtrack_pmi_trainer_set_optimizer_state(uavtrack_pmi_trainer *trainer, const float *exp_avg, const float *exp_avg_sq,
-                                             const int64_t *step, int64_t n_train, void *stream)
-{
-    return optimizer_state(__func__, trainer, exp_avg, exp_avg_sq, step, n_train, stream, "the network has %d trainable");
-}
-
-int uavtrack_pmi_trainer_get_optimizer_state(uavtrack_pmi_trainer *trainer, float *exp_avg, float *exp_avg_sq,
-                                             int64_t *step, int64_t n_train, void *stream)
-{
-    return optimizer_state(__func__, trainer, exp_avg, exp_avg_sq, step, n_train, stream, "the network has %d trainable");
-}
-
-int uavtrack_pmi_trainer_train(uavtrack_pmi_trainer *trainer, const float *rows, int64_t n_rows, int64_t n_uav,
-                               const int64_t *t_idx, const int64_t *u_idx, int64_t b2, int64_t batch_size,
-                               float *avg_loss, float *losses, float *outputs, void *stream)
-{
-    if (!trainer) return fail("uavtrack_pmi_trainer_train: null handle");
-    if (!rows || !t_idx || !u_idx || !avg_loss)
-        return fail("uavtrack_pmi_trainer_train: rows, t_idx, u_idx and avg_loss must not be null");
-    if (n_uav < 1) return fail("uavtrack_pmi_trainer_train: n_uav = %lld < 1", (long long)n_uav);
-    if (n_rows < n_uav || n_rows % n_uav != 0)
-        return fail("uavtrack_pmi_trainer_train: n_rows = %lld is not a positive multiple of n_uav = %lld", (long long)n_rows,
-                    (long long)n_uav);
-    if (batch_size < 2)
-        return fail("uavtrack_pmi_trainer_train: batch_size = %lld < 2 (train-mode BatchNorm1d needs two rows)",
-                    (long long)batch_size);
-    if (batch_size > trainer->d.max_b)
-        return fail("uavtrack_pmi_trainer_train: batch_size = %lld, scratch is reserved for %lld (uavtrack_pmi_trainer_reserve)",
-                    (long long)batch_size, (long long)trainer->d.max_b);
-    if (b2 < batch_size)
-        return fail("uavtrack_pmi_trainer_train: b2 = %lld < batch_size = %lld (no mini-batch)", (long long)b2,
-                    (long long)batch_size);
-    if (b2 / batch_size > (int64_t)1 << 30) return fail("uavtrack_pmi_trainer_train: b2 = %lld too large", (long long)b2);
-    ON_DEVICE(trainer->cfg.device_id);
-    PmiTrainLaunch q;
-    q.rows = rows; q.n_rows = n_rows; q.n_uav = n_uav; q.b2 = b2; q.batch = batch_size;
-    q.t_idx = t_idx; q.u_idx = u_idx; q.avg_loss = avg_loss; q.losses = losses; q.outputs = outputs;
-    HIP_TRY(launch_pmi_train(trainer->d, q, static_cast<hipStream_t>(stream)));
-    return 0;
-}
-
-}  // extern "C"
-
-namespace {
-
-// The source list of uavtrack_pmi_trainer_train_many / _select into the table the select kernel takes by value; the
-// span starts at group_base.  Returns nonzero after fail().
-int accept_sources(const char *fn, const uavtrack_pmi_source *sources, int32_t count, int64_t n_uav, int64_t group_base,
-                   PmiSourceTable *out)
-{
-    if (!sources) return fail("%s: sources must not be null", fn);
-    if (count < 1 || count > UAVTRACK_PMI_MAX_SOURCES)
-        return fail("%s: count = %d out of range [1, %d]", fn, count, UAVTRACK_PMI_MAX_SOURCES);
-    if (n_uav < 1) return fail("%s: n_uav = %lld < 1", fn, (long long)n_uav);
-    out->count = count;
-    out->base[0] = group_base;
-    for (int k = 0; k < count; ++k) {
-        if (!sources[k].rows) return fail("%s: sources[%d].rows is null", fn, k);
-        if (sources[k].n_rows < n_uav || sources[k].n_rows % n_uav != 0)
-            return fail("%s: sources[%d].n_rows = %lld is not a positive multiple of n_uav = %lld", fn, k,
-                        (long long)sources[k].n_rows, (long long)n_uav);
-        const int64_t groups = sources[k].n_rows / n_uav;
-        if (groups > INT64_MAX / 2 - out->base[k]) return fail("%s: the sources hold too many groups", fn);
-        out->rows[k] = sources[k].rows;
-        out->base[k + 1] = out->base[k] + groups;
-    }
-    for (int k = count; k < kPmiMaxSources; ++k) {
-        out->rows[k] = nullptr;
-        out->base[k + 1] = out->base[count];
-    }
-    return 0;
-}
-
-}  // namespace
-
-extern "C" {
-
-int uavtrack_pmi_trainer_train_many(uavtrack_pmi_trainer *trainer, const uavtrack_pmi_source *sources, int32_t count,
-                                    int64_t n_uav, const int64_t *t_idx, const int64_t *u_idx, int64_t b2,
-                                    int64_t batch_size, float *avg_loss, float *losses, float *outputs, void *stream)
-{
-    if (!trainer) return fail("uavtrack_pmi_trainer_train_many: null handle");
-    if (!t_idx || !u_idx || !avg_loss)
-        return fail("uavtrack_pmi_trainer_train_many: t_idx, u_idx and avg_loss must not be null");
-    PmiSourceTable table;
-    if (accept_sources(__func__, sources, count, n_uav, 0, &table)) return 1;
-    if (batch_size < 2)
-        return fail("uavtrack_pmi_trainer_train_many: batch_size = %lld < 2 (train-mode BatchNorm1d needs two rows)",
-                    (long long)batch_size);
-    if (batch_size > trainer->d.max_b)
-        return fail("uavtrack_pmi_trainer_train_many: batch_size = %lld, scratch is reserved for %lld "
-                    "(uavtrack_pmi_trainer_reserve)", (long long)batch_size, (long long)trainer->d.max_b);
-    if (b2 < batch_size)
-        return fail("uavtrack_pmi_trainer_train_many: b2 = %lld < batch_size = %lld (no mini-batch)", (long long)b2,
-                    (long long)batch_size);
-    if (b2 / batch_size > (int64_t)1 << 30)
-        return fail("uavtrack_pmi_trainer_train_many: b2 = %lld too large", (long long)b2);
-    ON_DEVICE(trainer->cfg.device_id);
-    PmiTrainLaunch q;
-    q.rows = nullptr; q.n_rows = table.base[count] * n_uav; q.n_uav = n_uav; q.b2 = b2; q.batch = batch_size;
-    q.t_idx = t_idx; q.u_idx = u_idx; q.avg_loss = avg_loss; q.losses = losses; q.outputs = outputs;
-    HIP_TRY(launch_pmi_train_many(trainer->d, table, q, static_cast<hipStream_t>(stream)));
-    return 0;
-}
-
-int uavtrack_pmi_trainer_select(uavtrack_pmi_trainer *trainer, const uavtrack_pmi_source *sources, int32_t count,
-                                int64_t group_base, int64_t total_groups, int64_t n_uav, const int64_t *t_idx,
-                                const int64_t *u_idx, int64_t b2, float *selected, void *stream)
-{
-    if (!trainer) return fail("uavtrack_pmi_trainer_select: null handle");
-    if (!t_idx || !u_idx || !selected)
-        return fail("uavtrack_pmi_trainer_select: t_idx, u_idx and selected must not be null");
-    if (b2 < 1 || b2 > INT32_MAX)   // 24 lanes per draw at most: the grid stays below 2^31 workgroups
-        return fail("uavtrack_pmi_trainer_select: b2 = %lld out of range [1, %d]", (long long)b2, INT32_MAX);
-    if (group_base < 0 || total_groups < 1 || group_base >= total_groups)
-        return fail("uavtrack_pmi_trainer_select: group_base = %lld outside a timeline of %lld groups", (long long)group_base,
-                    (long long)total_groups);
-    PmiSourceTable table;
-    if (accept_sources(__func__, sources, count, n_uav, group_base, &table)) return 1;
-    if (table.base[count] > total_groups)
-        return fail("uavtrack_pmi_trainer_select: the sources end at group %lld of a timeline of %lld", (long long)table.base[count],
-                    (long long)total_groups);
-    ON_DEVICE(trainer->cfg.device_id);
-    HIP_TRY(launch_pmi_select(trainer->d, table, total_groups, n_uav, t_idx, u_idx, b2, selected,
-                              static_cast<hipStream_t>(stream)));
-    return 0;
-}
-
-int uavtrack_pmi_trainer_check(uavtrack_pmi_trainer *trainer, int64_t *refused, void *stream)
-{
-    int count = 0;
-    if (take_refusals(__func__, trainer, refused, stream, &count)) return 1;
-    if (count)
-        return fail("uavtrack_pmi_trainer_check: %d train call(s) refused: a timestep index outside [0, T) or a uav index "
-                    "outside [0, n_uav); they changed nothing", count);
-    return 0;
-}
-
-}  // extern "C"
-
-// ---- the prioritised replay ring ----------------------------------------------------------------------------------
-
-namespace {
-
-bool aligned16(const void *p) { return ((uintptr_t)p & 15) == 0; }
-
-// The ring's pointers and host state against the handle's limits (`fn` names the ABI function in the message).  The
-// adds need the stores and take a ring without priorities (a uniform ring); the prioritised draws need the priorities.
-int accept_ring(const uavtrack_replay *r, const char *fn, const uavtrack_replay_ring *ring, bool stores, bool priorities)
-{
-    if (!ring) return fail("%s: ring is null", fn);
-    if (priorities && !ring->priorities) return fail("%s: ring->priorities is null", fn);
-    if (stores && (!ring->states || !ring->actions || !ring->rewards || !ring->next_states))
-        return fail("%s: the ring's states, actions, rewards and next_states must not be null", fn);
-    if (stores && (!aligned16(ring->states) || !aligned16(ring->next_states)))
-        return fail("%s: the ring's states and next_states must be 16-byte aligned", fn);
-    if (ring->capacity < 1 || ring->capacity > r->cfg.max_capacity)
-        return fail("%s: capacity %lld outside [1, max_capacity = %lld]", fn, (long long)ring->capacity,
-                    (long long)r->cfg.max_capacity);
-    if (ring->count < 0 || ring->count > ring->capacity)
-        return fail("%s: count %lld outside [0, capacity = %lld]", fn, (long long)ring->count, (long long)ring->capacity);
-    if (ring->pos < 0 || ring->pos >= ring->capacity)
-        return fail("%s: pos %lld outside [0, capacity = %lld)", fn, (long long)ring->pos, (long long)ring->capacity);
-    return 0;
-}
-
-ReplayRingView ring_view(const uavtrack_replay_ring *ring)
-{
-    ReplayRingView v;
-    v.states = ring->states; v.actions = ring->actions; v.rewards = ring->rewards; v.next_states = ring->next_states;
-    v.priorities = ring->priorities; v.capacity = ring->capacity; v.pos = ring->pos; v.count = ring->count;
-    return v;
-}
-
-// One request to add to a ring, as each of the five add entry points states it: the launcher's own request plus what
-// only the acceptor needs.  The flat form is one step of n "environments"; uavtrack_replay_add_rollout knows only
-// agents = envs * n_uav, and passes it as envs.
-struct ReplayAddCall {
-    const char *who;                   // the entry point, as the error messages name it
-    const uavtrack_replay_ring *ring;  // (a.ring is filled once this one is accepted)
-    bool episodes = false;             // the entry point has done / start_obs: _episodes requires them, the n-step and
-                                       // lambda forms take both or neither
-    double lambda = 0.0, gamma = 0.0;  // as given: checked as doubles, launched as floats
-    ReplayAdd a{};
-
-    ReplayAddCall(const char *who_, const uavtrack_replay_ring *ring_, ReplayForm form, int64_t steps, int64_t envs,
-                  int64_t n_uav, const float *obs_in, const float *next, const int32_t *actions, const float *rewards)
-        : who(who_), ring(ring_)
-    {
-        a.form = form; a.steps = steps; a.envs = envs; a.n_uav = n_uav; a.n_step = 1;
-        a.obs_in = obs_in; a.next = next; a.actions = actions; a.rewards = rewards;
-    }
-};
-
-// Every refusal of the add entry points, in one order.  Nothing has been enqueued when one of them fires.
-int accept_replay_add(const uavtrack_replay *replay, const ReplayAddCall &q)
-{
-    const char *who = q.who;
-    const ReplayAdd &a = q.a;
-    if (!replay) return fail("%s: null handle", who);
-    if (accept_ring(replay, who, q.ring, true, false)) return 1;
-    const bool flat = a.form == ReplayForm::Flat, plain = a.form == ReplayForm::Rollout, lambda = a.form == ReplayForm::Lambda;
-    const bool given = (flat ? a.states : a.obs_in) && a.next && a.actions && a.rewards;
-    if (!given || (!flat && !plain && !a.discounts) || (plain && q.episodes && (!a.done || !a.start_obs)) || (lambda && !a.values))
-        return fail("%s: %s must not be null", who,
-                    flat ? "states, actions, rewards and next_states"
-                    : lambda ? "discounts, obs_in, obs, actions, reward and values"
-                    : !plain ? "discounts, obs_in, obs, actions and reward"
-                    : q.episodes ? "obs_in, obs, actions, reward, done and start_obs" : "obs_in, obs, actions and reward");
-    if (!a.done != !a.start_obs) return fail("%s: done and start_obs must both be given or both be null", who);
-    if (!aligned16(flat ? a.states : a.obs_in) || !aligned16(a.next) || !aligned16(a.start_obs))
-        return fail("%s: %s must be 16-byte aligned", who,
-                    flat ? "states and next_states" : q.episodes ? "obs_in, obs and start_obs" : "obs_in and obs");
-    if (a.n_step < 1 || a.n_step > UAVTRACK_REPLAY_MAX_NSTEP)
-        return fail("%s: n_step = %d outside [1, %d]", who, a.n_step, UAVTRACK_REPLAY_MAX_NSTEP);
-    if (!(q.lambda >= 0.0 && q.lambda <= 1.0)) return fail("%s: lambda = %g is not a finite value in [0, 1]", who, q.lambda);
-    if (!(q.gamma >= 0.0 && q.gamma <= 1.0)) return fail("%s: gamma = %g is not a finite value in [0, 1]", who, q.gamma);
-    if (flat) return a.steps < 1 ? fail("%s: n = %lld < 1", who, (long long)a.steps) : 0;   // (no product is taken of n)
-    if (a.steps < 1 || a.envs < 1 || a.n_uav < 1)
-        return fail("%s: %s must be >= 1", who, q.episodes ? "steps, envs and n_uav" : "steps and agents");
-    if (a.envs > INT64_MAX / a.n_uav || a.steps > INT64_MAX / (a.envs * a.n_uav) / 12)
-        return fail("%s: %s overflows", who, q.episodes ? "steps * envs * n_uav" : "steps * agents");
-    return 0;
-}
-
-int run_replay_add(uavtrack_replay *replay, const ReplayAddCall &q, void *stream)
-{
-    if (accept_replay_add(replay, q)) return 1;
-    ReplayAdd a = q.a;
-    a.ring = ring_view(q.ring); a.lambda = (float)q.lambda; a.gamma = (float)q.gamma;
-    ON_DEVICE(replay->cfg.device_id);
-    HIP_TRY(launch_replay_add(replay->d, a, static_cast<hipStream_t>(stream)));
-    return 0;
-}
-
-// What the three draws refuse alike: the handle, the ring (with its priorities for the prioritised draws), indices, n
-// and an empty ring.
-int accept_draw(const uavtrack_replay *replay, const char *fn, const uavtrack_replay_ring *ring, bool priorities, int64_t n,
-                const int64_t *indices)
-{
-    if (!replay) return fail("%s: null handle", fn);
-    if (accept_ring(replay, fn, ring, false, priorities)) return 1;
-    if (!indices) return fail("%s: indices must not be null", fn);
-    if (n < 1 || n > replay->cfg.max_batch)
-        return fail("%s: n = %lld outside [1, max_batch = %lld]", fn, (long long)n, (long long)replay->cfg.max_batch);
-    if (ring->count < 1) return fail("%s: the ring is empty (count = 0)", fn);
-    return 0;
-}
-
-// uavtrack_replay_sample (anneal_calls == 0: beta0 is the call's beta) and _sample_annealed (anneal_calls >= 1)
-int replay_sample(const char *fn, uavtrack_replay *replay, const uavtrack_replay_ring *ring, int64_t n, double alpha,
-                  double beta0, double beta1, int64_t anneal_calls, int64_t *indices, float *weights, void *stream)
-{
-    if (accept_draw(replay, fn, ring, true, n, indices)) return 1;
-    if (!std::isfinite(alpha) || !(alpha > 0) || (float)alpha <= 0.0f)
-        return fail("%s: alpha = %g must be finite and > 0", fn, alpha);
-    const char *first = anneal_calls ? "beta0" : "beta";
-    if (!std::isfinite(beta0) || !(beta0 >= 0)) return fail("%s: %s = %g must be finite and >= 0", fn, first, beta0);
-    if (!std::isfinite(beta1) || !(beta1 >= 0)) return fail("%s: beta1 = %g must be finite and >= 0", fn, beta1);
-    ON_DEVICE(replay->cfg.device_id);
-    HIP_TRY(launch_replay_sample(replay->d, ring->priorities, ring->count, n, (float)alpha, beta0, beta1, anneal_calls,
-                                 indices, weights, static_cast<hipStream_t>(stream)));
-    return 0;
-}
-
-}  // namespace
-
-extern "C" {
-
-int uavtrack_replay_create(const uavtrack_replay_config *cfg, uavtrack_replay **out)
-{
-    auto check = [](const char *fn, const uavtrack_replay_config &c) {
-        if (c.max_capacity < 1 || c.max_capacity > kReplayMaxCapacity)
-            return fail("%s: max_capacity %lld out of range [1, %lld]", fn, (long long)c.max_capacity,
-                        (long long)kReplayMaxCapacity);
-        if (c.max_batch < 1 || c.max_batch > kReplayMaxBatch)
-            return fail("%s: max_batch %lld out of range [1, %lld]", fn, (long long)c.max_batch, (long long)kReplayMaxBatch);
-        return 0;
-    };
-    auto init = [](ReplayDevice &d, const uavtrack_replay_config &c) {
-        d.max_capacity = c.max_capacity;
-        d.max_batch = c.max_batch;
-        d.k0 = (uint32_t)c.seed;
-        d.k1 = (uint32_t)(c.seed >> 32);
-        return hipSuccess;
-    };
-    return create_handle(__func__, cfg, out, check, init);
-}
-
-int uavtrack_replay_destroy(uavtrack_replay *replay) { return destroy_handle(replay); }
-
-int uavtrack_replay_add(uavtrack_replay *replay, const uavtrack_replay_ring *ring, int64_t n, const float *states,
-                        const int32_t *actions, const float *rewards, const float *next_states, void *stream)
-{
-    ReplayAddCall q(__func__, ring, ReplayForm::Flat, n, 1, 1, nullptr, next_states, actions, rewards);
-    q.a.states = states;
-    return run_replay_add(replay, q, stream);
-}
-
-int uavtrack_replay_add_rollout(uavtrack_replay *replay, const uavtrack_replay_ring *ring, int64_t steps, int64_t agents,
-                                const float *obs_in, const float *obs, const int32_t *actions, const float *reward,
-                                void *stream)
-{
-    ReplayAddCall q(__func__, ring, ReplayForm::Rollout, steps, agents, 1, obs_in, obs, actions, reward);
-    return run_replay_add(replay, q, stream);
-}
-
-int uavtrack_replay_add_rollout_episodes(uavtrack_replay *replay, const uavtrack_replay_ring *ring, int64_t steps,
-                                         int64_t envs, int64_t n_uav, const float *obs_in, const float *obs,
-                                         const int32_t *actions, const float *reward, const uint8_t *done,
-                                         const float *start_obs, void *stream)
-{
-    ReplayAddCall q(__func__, ring, ReplayForm::Rollout, steps, envs, n_uav, obs_in, obs, actions, reward);
-    q.episodes = true; q.a.done = done; q.a.start_obs = start_obs;
-    return run_replay_add(replay, q, stream);
-}
-
-int uavtrack_replay_add_rollout_nstep(uavtrack_replay *replay, const uavtrack_replay_ring *ring, float *discounts,
-                                      int64_t steps, int64_t envs, int64_t n_uav, const float *obs_in, const float *obs,
-                                      const int32_t *actions, const float *reward, const uint8_t *done,
-                                      const float *start_obs, int32_t n_step, double gamma, void *stream)
-{
-    ReplayAddCall q(__func__, ring, ReplayForm::Nstep, steps, envs, n_uav, obs_in, obs, actions, reward);
-    q.episodes = true; q.a.done = done; q.a.start_obs = start_obs;
-    q.a.discounts = discounts; q.a.n_step = n_step; q.gamma = gamma;
-    return run_replay_add(replay, q, stream);
-}
-
-int uavtrack_replay_add_rollout_lambda(uavtrack_replay *replay, const uavtrack_replay_ring *ring, float *discounts,
-                                       int64_t steps, int64_t envs, int64_t n_uav, const float *obs_in, const float *obs,
-                                       const int32_t *actions, const float *reward, const uint8_t *done,
-                                       const float *start_obs, const float *values, double lambda, double gamma,
-                                       void *stream)
-{
-    ReplayAddCall q(__func__, ring, ReplayForm::Lambda, steps, envs, n_uav, obs_in, obs, actions, reward);
-    q.episodes = true; q.a.done = done; q.a.start_obs = start_obs;
-    q.a.discounts = discounts; q.a.values = values; q.lambda = lambda; q.gamma = gamma;
-    return run_replay_add(replay, q, stream);
-}
-
-int uavtrack_replay_sample(uavtrack_replay *replay, const uavtrack_replay_ring *ring, int64_t n, double alpha,
-                           double beta, int64_t *indices, float *weights, void *stream)
-{
-    return replay_sample(__func__, replay, ring, n, alpha, beta, beta, 0, indices, weights, stream);
-}
-
-int uavtrack_replay_sample_annealed(uavtrack_replay *replay, const uavtrack_replay_ring *ring, int64_t n, double alpha,
-                                    double beta0, double beta1, int64_t anneal_calls, int64_t *indices, float *weights,
-                                    void *stream)
-{
-    if (!replay) return fail("uavtrack_replay_sample_annealed: null handle");
-    if (anneal_calls < 1) return fail("uavtrack_replay_sample_annealed: anneal_calls = %lld < 1", (long long)anneal_calls);
-    return replay_sample(__func__, replay, ring, n, alpha, beta0, beta1, anneal_calls, indices, weights, stream);
-}
-
-int uavtrack_replay_sample_uniform(uavtrack_replay *replay, const uavtrack_replay_ring *ring, int64_t n, int64_t *indices,
-                                   void *stream)
-{
-    if (accept_draw(replay, __func__, ring, false, n, indices)) return 1;
-    if (n > ring->count)
-        return fail("%s: n = %lld exceeds count = %lld (the draw is without replacement)", __func__, (long long)n,
-                    (long long)ring->count);
-    ON_DEVICE(replay->cfg.device_id);
-    HIP_TRY(launch_replay_sample_uniform(replay->d, ring->count, n, indices, static_cast<hipStream_t>(stream)));
-    return 0;
-}
-
-int uavtrack_replay_check(uavtrack_replay *replay, int64_t *refused, void *stream)
-{
-    int count = 0;
-    if (take_refusals(__func__, replay, refused, stream, &count)) return 1;
-    if (count)
-        return fail("uavtrack_replay_check: %d sample call(s) refused: a priority in [0, count) is NaN, infinite or "
-                    "negative, or all of them are zero; their indices are slot 0", count);
-    return 0;
-}
-
-}  // extern "C"
-
-// ---- per-episode results ------------------------------------------------------------------------------------------
-
-extern "C" {
-
-int uavtrack_episode_stats_create(const uavtrack_episode_stats_config *cfg, uavtrack_episode_stats **out)
-{
-    auto check = [](const char *fn, const uavtrack_episode_stats_config &c) {
-        if (c.n_envs < 1) return fail("%s: n_envs %lld < 1", fn, (long long)c.n_envs);
-        if (c.n_uav < 1 || c.n_uav > kEpisodeMaxUav) return fail("%s: n_uav %d out of range [1, %d]", fn, c.n_uav, kEpisodeMaxUav);
-        if (c.max_steps < 1) return fail("%s: max_steps %lld < 1", fn, (long long)c.max_steps);
-        if (c.max_steps > INT32_MAX / c.n_envs)
-            return fail("%s: max_steps %lld * n_envs %lld must stay below 2^31", fn, (long long)c.max_steps, (long long)c.n_envs);
-        if (c.log_capacity < 1 || c.log_capacity > INT32_MAX)
-            return fail("%s: log_capacity %lld out of range [1, 2^31)", fn, (long long)c.log_capacity);
-        return 0;
-    };
-    auto init = [](EpisodeDevice &d, const uavtrack_episode_stats_config &c) {
-        d.B = c.n_envs;
-        d.N = c.n_uav;
-        d.env_offset = c.env_offset;
-        d.max_steps = c.max_steps;
-        d.log_capacity = c.log_capacity;
-        return hipSuccess;
-    };
-    return create_handle(__func__, cfg, out, check, init);
-}
-
-int uavtrack_episode_stats_destroy(uavtrack_episode_stats *stats) { return destroy_handle(stats); }
-
-int uavtrack_episode_stats_add(uavtrack_episode_stats *stats, int64_t T, const float *reward, const float *terms,
-                               const int32_t *covered, const uint8_t *done, void *stream)
-{
-    if (!stats) return fail("uavtrack_episode_stats_add: null handle");
-    if (!reward || !terms || !covered) return fail("uavtrack_episode_stats_add: reward, terms and covered must not be null");
-    if (T < 1 || T > stats->cfg.max_steps)
-        return fail("uavtrack_episode_stats_add: T = %lld outside [1, max_steps = %lld]", (long long)T,
-                    (long long)stats->cfg.max_steps);
-    ON_DEVICE(stats->cfg.device_id);
-    HIP_TRY(launch_episode_add(stats->d, T, reward, terms, covered, done, static_cast<hipStream_t>(stream)));
-    return 0;
-}
-
-int uavtrack_episode_stats_close(uavtrack_episode_stats *stats, void *stream)
-{
-    if (!stats) return fail("uavtrack_episode_stats_close: null handle");
-    ON_DEVICE(stats->cfg.device_id);
-    HIP_TRY(launch_episode_close(stats->d, static_cast<hipStream_t>(stream)));
-    return 0;
-}
-
-int uavtrack_episode_stats_read(uavtrack_episode_stats *stats, uavtrack_episode_record *records_host, int64_t capacity,
-                                int64_t *count, int64_t *dropped, void *stream)
-{
-    if (!stats || !count || !dropped) return fail("uavtrack_episode_stats_read: null argument");
-    if (capacity < 0 || (capacity > 0 && !records_host))
-        return fail("uavtrack_episode_stats_read: capacity %lld without a record array", (long long)capacity);
-    ON_DEVICE(stats->cfg.device_id);
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    int64_t head[2] = {0, 0};
-    HIP_TRY(hipMemcpyAsync(head, stats->d.head, sizeof head, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    const int64_t n = head[0] < capacity ? head[0] : capacity;
-    if (n > 0) {
-        HIP_TRY(hipMemcpyAsync(records_host, stats->d.log, (size_t)n * sizeof(uavtrack_episode_record), hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-    }
-    *count = head[0];
-    *dropped = head[1];
-    return 0;
-}
-
-int uavtrack_episode_stats_clear(uavtrack_episode_stats *stats, void *stream)
-{
-    if (!stats) return fail("uavtrack_episode_stats_clear: null handle");
-    ON_DEVICE(stats->cfg.device_id);
-    HIP_TRY(hipMemsetAsync(stats->d.head, 0, 2 * sizeof(int64_t), static_cast<hipStream_t>(stream)));
     return 0;
 }
 

@@ -1,0 +1,358 @@
+// api_learner.hip -- the C ABI of the device learner (include/uavtrack.h, uavtrack_learner_*).
+
+#include "api_env.h"
+#include "api_handle.h"
+#include "learner.h"
+
+#include <cmath>
+
+using namespace uavtrack;
+
+struct uavtrack_learner {
+    uavtrack_learner_config cfg;
+    LearnerDevice d;
+    double reg[3] = {0.0, INFINITY, INFINITY};   // uavtrack_learner_get_regularisation: the values as they were set
+};
+
+namespace uavtrack {
+
+static Bufs scratch_bufs(LearnerDevice &d, int64_t max_n) { return {buf(d.td, max_n), buf(d.last, max_n)}; }
+
+static Bufs device_bufs(LearnerDevice &d)
+{
+    const size_t P = (size_t)d.L.P;
+    return adam_bufs(d.opt) + Bufs{buf(d.params, P, true), buf(d.gstatus, 1, true), buf(d.partials, kLearnerMaxGroups * (P + 4)), buf(d.scal, 2),
+                                   buf(d.gsum, P), buf(d.sq, 2 * (size_t)learner_clip_groups(d.L)), buf(d.coef, 2)} +
+           scratch_bufs(d, d.max_n);
+}
+
+static int *refusal_word(const LearnerDevice &d) { return d.opt.errors; }
+
+}  // namespace uavtrack
+
+namespace {
+
+constexpr int64_t kLearnerDefaultBatch = 65536;
+constexpr int64_t kLearnerMaxBatch = ((int64_t)1 << 31) - 1;   // row numbers are int32 in the priority write
+
+// The batch tests of uavtrack_learner_update / _grad / _write_priorities, after their null tests: n, the reserved
+// scratch, the store's capacity, and n against it when no indices choose the rows (`dir`: "from" or "into" the store).
+int accept_batch(const char *fn, const uavtrack_learner *l, int64_t n, int64_t capacity, const int64_t *indices,
+                 const char *dir)
+{
+    if (n < 1) return fail("%s: n = %lld < 1", fn, (long long)n);
+    if (n > l->d.max_n)
+        return fail("%s: n = %lld rows, scratch is reserved for %lld (uavtrack_learner_reserve)", fn, (long long)n,
+                    (long long)l->d.max_n);
+    if (capacity < 1) return fail("%s: capacity = %lld < 1", fn, (long long)capacity);
+    if (!indices && n > capacity)
+        return fail("%s: n = %lld rows without indices %s a store of %lld", fn, (long long)n, dir, (long long)capacity);
+    return 0;
+}
+
+// uavtrack_learner_update / _grad while an entropy buffer is installed: the batch must fit into it
+int accept_entropy_rows(const char *fn, const uavtrack_learner *l, int64_t n)
+{
+    if (l->d.entropy && n > l->d.entropy_rows)
+        return fail("%s: n = %lld rows, the installed entropy buffer holds %lld (uavtrack_learner_set_diagnostics)", fn,
+                    (long long)n, (long long)l->d.entropy_rows);
+    return 0;
+}
+
+// the fields uavtrack_learner_update and _grad (and their weighted forms) fill alike; the others are null
+LearnerLaunch learner_batch(int64_t n, const float *states, const int32_t *actions, const float *rewards,
+                            const float *next_states, int64_t capacity, const int64_t *indices, const float *weights,
+                            const float *discounts, float *td_delta)
+{
+    LearnerLaunch q = {};
+    q.n = n; q.capacity = capacity; q.td_delta = td_delta; q.weights = weights; q.discounts = discounts;
+    q.states = states; q.rewards = rewards; q.next_states = next_states; q.actions = actions; q.idx = indices;
+    return q;
+}
+
+}  // namespace
+
+extern "C" {
+
+int uavtrack_learner_create(const uavtrack_learner_config *cfg, uavtrack_learner **out)
+{
+    auto check = [](const char *fn, const uavtrack_learner_config &c) {
+        if (c.hidden < 1 || c.hidden > kLearnerMaxHidden)
+            return fail("%s: hidden %d out of range [1, %d]", fn, c.hidden, kLearnerMaxHidden);
+        if (c.n_actions < 1 || c.n_actions > kLearnerMaxActions)
+            return fail("%s: n_actions %d out of range [1, %d]", fn, c.n_actions, kLearnerMaxActions);
+        if (c.loss != UAVTRACK_LOSS_REFERENCE && c.loss != UAVTRACK_LOSS_PER_SAMPLE)
+            return fail("%s: unknown loss form %d", fn, c.loss);
+        if (c.max_batch < 0 || c.max_batch > kLearnerMaxBatch)
+            return fail("%s: max_batch %lld out of range [0, %lld]", fn, (long long)c.max_batch, (long long)kLearnerMaxBatch);
+        if (!std::isfinite(c.gamma) || !std::isfinite(c.actor_lr) || !std::isfinite(c.critic_lr) || c.actor_lr < 0 ||
+            c.critic_lr < 0)
+            return fail("%s: gamma and the learning rates must be finite, the rates >= 0", fn);
+        return 0;
+    };
+    auto init = [](LearnerDevice &d, const uavtrack_learner_config &c) {
+        d.L = LearnerLayout::make(c.hidden, c.n_actions);
+        d.gamma = (float)c.gamma;
+        d.actor_lr = (float)c.actor_lr;
+        d.critic_lr = (float)c.critic_lr;
+        d.per_sample = c.loss == UAVTRACK_LOSS_PER_SAMPLE;
+        d.opt.tensors = kLearnerTensors;
+        d.opt.P = d.L.P;
+        d.max_n = c.max_batch ? c.max_batch : kLearnerDefaultBatch;
+        d.max_norm[0] = d.max_norm[1] = INFINITY;       // regularisation off: entropy_coef 0, no diagnostics
+        return learner_prepare_kernels(d.L);
+    };
+    return create_handle(__func__, cfg, out, check, init);
+}
+
+int uavtrack_learner_destroy(uavtrack_learner *learner) { return destroy_handle(learner); }
+
+int uavtrack_learner_num_params(uavtrack_learner *learner, int64_t *out)
+{
+    if (!learner || !out) return fail("uavtrack_learner_num_params: null argument");
+    *out = learner->d.L.P;
+    return 0;
+}
+
+int uavtrack_learner_set_regularisation(uavtrack_learner *learner, double entropy_coef, double actor_max_norm,
+                                        double critic_max_norm)
+{
+    if (!learner) return fail("%s: null handle", __func__);
+    if (!std::isfinite(entropy_coef) || entropy_coef < 0)
+        return fail("%s: entropy_coef = %g must be finite and >= 0", __func__, entropy_coef);
+    if (!(actor_max_norm > 0) || !(critic_max_norm > 0))
+        return fail("%s: max norms (%g, %g) must be > 0, or +inf for no clipping", __func__, actor_max_norm, critic_max_norm);
+    if (entropy_coef != 0 && !learner->d.per_sample)
+        return fail("%s: entropy_coef = %g on a UAVTRACK_LOSS_REFERENCE learner: that form scales the actor's gradient "
+                    "sums once by -mean(delta) / N, a factor an entropy term cannot share; use UAVTRACK_LOSS_PER_SAMPLE",
+                    __func__, entropy_coef);
+    learner->d.entropy_coef = (float)entropy_coef;
+    learner->d.max_norm[0] = actor_max_norm;
+    learner->d.max_norm[1] = critic_max_norm;
+    learner->reg[0] = entropy_coef; learner->reg[1] = actor_max_norm; learner->reg[2] = critic_max_norm;
+    return 0;
+}
+
+int uavtrack_learner_get_regularisation(uavtrack_learner *learner, double out[3])
+{
+    if (!learner || !out) return fail("%s: null argument", __func__);
+    for (int k = 0; k < 3; ++k) out[k] = learner->reg[k];
+    return 0;
+}
+
+int uavtrack_learner_set_diagnostics(uavtrack_learner *learner, float *entropy, int64_t capacity_rows, float *grad_norm)
+{
+    if (!learner) return fail("%s: null handle", __func__);
+    if (entropy && capacity_rows < 1)
+        return fail("%s: capacity_rows = %lld < 1 with an entropy buffer", __func__, (long long)capacity_rows);
+    learner->d.entropy = entropy;
+    learner->d.entropy_rows = entropy ? capacity_rows : 0;
+    learner->d.grad_norm = grad_norm;
+    return 0;
+}
+
+int uavtrack_learner_reserve(uavtrack_learner *learner, int64_t max_batch)
+{
+    return reserve_scratch(__func__, learner, max_batch, kLearnerMaxBatch, &LearnerDevice::max_n);
+}
+
+int uavtrack_learner_set_params(uavtrack_learner *learner, const float *params, int64_t n_floats, void *stream)
+{
+    if (!learner || !params) return fail("uavtrack_learner_set_params: null argument");
+    if (n_floats != learner->d.L.P)
+        return fail("uavtrack_learner_set_params: %lld floats, the networks have %d", (long long)n_floats, learner->d.L.P);
+    ON_DEVICE(learner->cfg.device_id);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    HIP_TRY(hipStreamSynchronize(st));
+    HIP_TRY(hipMemcpyAsync(learner->d.params, params, (size_t)n_floats * 4, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return 0;
+}
+
+int uavtrack_learner_get_params(uavtrack_learner *learner, float *params, int64_t n_floats, void *stream)
+{
+    if (!learner || !params) return fail("uavtrack_learner_get_params: null argument");
+    if (n_floats != learner->d.L.P)
+        return fail("uavtrack_learner_get_params: %lld floats, the networks have %d", (long long)n_floats, learner->d.L.P);
+    ON_DEVICE(learner->cfg.device_id);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    HIP_TRY(hipMemcpyAsync(params, learner->d.params, (size_t)n_floats * 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return 0;
+}
+
+int uavtrack_learner_publish_actor(uavtrack_learner *learner, uavtrack_env *env, void *stream)
+{
+    if (!learner || !env) return fail("uavtrack_learner_publish_actor: null handle");
+    if (learner->cfg.device_id != env->cfg.device_id)
+        return fail("uavtrack_learner_publish_actor: the learner is on device %d, the environment on device %d",
+                    learner->cfg.device_id, env->cfg.device_id);
+    const LearnerLayout &L = learner->d.L;
+    const float *p = learner->d.params;
+    return publish_actor(__func__, env, p + L.a_w1, p + L.a_b1, p + L.a_w2, p + L.a_b2, L.H, L.A, stream);
+}
+
+int uavtrack_learner_set_optimizer_state(uavtrack_learner *learner, const float *exp_avg, const float *exp_avg_sq,
+                                         const int64_t *step, int64_t n_floats, void *stream)
+{
+    return optimizer_state(__func__, learner, exp_avg, exp_avg_sq, step, n_floats, stream, "the networks have %d");
+}
+
+int uavtrack_learner_get_optimizer_state(uavtrack_learner *learner, float *exp_avg, float *exp_avg_sq, int64_t *step,
+                                         int64_t n_floats, void *stream)
+{
+    return optimizer_state(__func__, learner, exp_avg, exp_avg_sq, step, n_floats, stream, "the networks have %d");
+}
+
+}  // extern "C"
+
+namespace {
+
+// uavtrack_learner_update, _update_weighted and _update_discounted (`fn`: the caller's name; weights, discounts nullable)
+int learner_update(const char *fn, uavtrack_learner *learner, int64_t n, const float *states, const int32_t *actions,
+                   const float *rewards, const float *next_states, int64_t capacity, const int64_t *indices,
+                   const float *weights, const float *discounts, float *actor_loss, float *critic_loss, float *td_delta, float *priorities,
+                   void *stream)
+{
+    if (!learner) return fail("%s: null handle", fn);
+    if (!states || !actions || !rewards || !next_states)
+        return fail("%s: states, actions, rewards and next_states must not be null", fn);
+    if (!actor_loss || !critic_loss) return fail("%s: actor_loss and critic_loss must not be null", fn);
+    if (accept_batch(fn, learner, n, capacity, indices, "from") || accept_entropy_rows(fn, learner, n)) return 1;
+    ON_DEVICE(learner->cfg.device_id);
+    LearnerLaunch q = learner_batch(n, states, actions, rewards, next_states, capacity, indices, weights, discounts, td_delta);
+    q.actor_loss = actor_loss; q.critic_loss = critic_loss; q.priorities = priorities;
+    HIP_TRY(launch_learner_update(learner->d, q, static_cast<hipStream_t>(stream)));
+    return 0;
+}
+
+// uavtrack_learner_grad, _grad_weighted and _grad_discounted
+int learner_grad(const char *fn, uavtrack_learner *learner, int64_t n, const float *states, const int32_t *actions,
+                 const float *rewards, const float *next_states, int64_t capacity, const int64_t *indices,
+                 const float *weights, const float *discounts, float *td_delta, float *row, void *stream)
+{
+    if (!learner) return fail("%s: null handle", fn);
+    if (!states || !actions || !rewards || !next_states)
+        return fail("%s: states, actions, rewards and next_states must not be null", fn);
+    if (!td_delta || !row) return fail("%s: td_delta and row must not be null", fn);
+    if (accept_batch(fn, learner, n, capacity, indices, "from") || accept_entropy_rows(fn, learner, n)) return 1;
+    ON_DEVICE(learner->cfg.device_id);
+    const LearnerLaunch q = learner_batch(n, states, actions, rewards, next_states, capacity, indices, weights, discounts,
+                                          td_delta);
+    HIP_TRY(launch_learner_grad(learner->d, q, row, static_cast<hipStream_t>(stream)));
+    return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int uavtrack_learner_update(uavtrack_learner *learner, int64_t n, const float *states, const int32_t *actions,
+                            const float *rewards, const float *next_states, int64_t capacity, const int64_t *indices,
+                            float *actor_loss, float *critic_loss, float *td_delta, float *priorities, void *stream)
+{
+    return learner_update(__func__, learner, n, states, actions, rewards, next_states, capacity, indices, nullptr, nullptr,
+                          actor_loss, critic_loss, td_delta, priorities, stream);
+}
+
+int uavtrack_learner_update_weighted(uavtrack_learner *learner, int64_t n, const float *states, const int32_t *actions,
+                                     const float *rewards, const float *next_states, int64_t capacity,
+                                     const int64_t *indices, const float *weights, float *actor_loss, float *critic_loss,
+                                     float *td_delta, float *priorities, void *stream)
+{
+    return learner_update(__func__, learner, n, states, actions, rewards, next_states, capacity, indices, weights, nullptr,
+                          actor_loss, critic_loss, td_delta, priorities, stream);
+}
+
+int uavtrack_learner_update_discounted(uavtrack_learner *learner, int64_t n, const float *states, const int32_t *actions,
+                                       const float *rewards, const float *next_states, int64_t capacity,
+                                       const int64_t *indices, const float *weights, const float *discounts,
+                                       float *actor_loss, float *critic_loss, float *td_delta, float *priorities,
+                                       void *stream)
+{
+    return learner_update(__func__, learner, n, states, actions, rewards, next_states, capacity, indices, weights, discounts,
+                          actor_loss, critic_loss, td_delta, priorities, stream);
+}
+
+int uavtrack_learner_row_floats(uavtrack_learner *learner, int64_t *out)
+{
+    if (!learner || !out) return fail("uavtrack_learner_row_floats: null argument");
+    *out = (int64_t)learner->d.L.P + kLearnerRowTail;
+    return 0;
+}
+
+int uavtrack_learner_grad(uavtrack_learner *learner, int64_t n, const float *states, const int32_t *actions,
+                          const float *rewards, const float *next_states, int64_t capacity, const int64_t *indices,
+                          float *td_delta, float *row, void *stream)
+{
+    return learner_grad(__func__, learner, n, states, actions, rewards, next_states, capacity, indices, nullptr, nullptr,
+                        td_delta, row, stream);
+}
+
+int uavtrack_learner_grad_weighted(uavtrack_learner *learner, int64_t n, const float *states, const int32_t *actions,
+                                   const float *rewards, const float *next_states, int64_t capacity,
+                                   const int64_t *indices, const float *weights, float *td_delta, float *row, void *stream)
+{
+    return learner_grad(__func__, learner, n, states, actions, rewards, next_states, capacity, indices, weights, nullptr,
+                        td_delta, row, stream);
+}
+
+int uavtrack_learner_grad_discounted(uavtrack_learner *learner, int64_t n, const float *states, const int32_t *actions,
+                                     const float *rewards, const float *next_states, int64_t capacity,
+                                     const int64_t *indices, const float *weights, const float *discounts, float *td_delta,
+                                     float *row, void *stream)
+{
+    return learner_grad(__func__, learner, n, states, actions, rewards, next_states, capacity, indices, weights, discounts,
+                        td_delta, row, stream);
+}
+
+int uavtrack_learner_apply(uavtrack_learner *learner, const float *rows, int64_t count, float *actor_loss,
+                           float *critic_loss, void *stream)
+{
+    if (!learner) return fail("uavtrack_learner_apply: null handle");
+    if (!rows) return fail("uavtrack_learner_apply: rows must not be null");
+    if (!actor_loss || !critic_loss) return fail("uavtrack_learner_apply: actor_loss and critic_loss must not be null");
+    if (count < 1 || count > UAVTRACK_LEARNER_MAX_ROWS)
+        return fail("uavtrack_learner_apply: count = %lld out of range [1, %d]", (long long)count, UAVTRACK_LEARNER_MAX_ROWS);
+    ON_DEVICE(learner->cfg.device_id);
+    HIP_TRY(launch_learner_apply(learner->d, rows, (int)count, actor_loss, critic_loss, static_cast<hipStream_t>(stream)));
+    return 0;
+}
+
+int uavtrack_learner_write_priorities(uavtrack_learner *learner, int64_t n, const int64_t *indices, int64_t capacity,
+                                      const float *td_delta, float *priorities, void *stream)
+{
+    if (!learner) return fail("uavtrack_learner_write_priorities: null handle");
+    if (!td_delta || !priorities) return fail("uavtrack_learner_write_priorities: td_delta and priorities must not be null");
+    if (accept_batch(__func__, learner, n, capacity, indices, "into")) return 1;
+    ON_DEVICE(learner->cfg.device_id);
+    HIP_TRY(launch_learner_priorities(learner->d, indices, n, capacity, td_delta, priorities,
+                                      static_cast<hipStream_t>(stream)));
+    return 0;
+}
+
+int uavtrack_learner_values(uavtrack_learner *learner, int64_t n, const float *rows, float *values, void *stream)
+{
+    if (!learner) return fail("%s: null handle", __func__);
+    if (!rows || !values) return fail("%s: rows and values must not be null", __func__);
+    if (n < 1) return fail("%s: n = %lld < 1", __func__, (long long)n);
+    if (n > INT64_MAX / 48) return fail("%s: n = %lld rows overflow", __func__, (long long)n);
+    if (((uintptr_t)rows & 15) != 0) return fail("%s: rows must be 16-byte aligned", __func__);
+    ON_DEVICE(learner->cfg.device_id);
+    HIP_TRY(launch_learner_values(learner->d, n, rows, values, static_cast<hipStream_t>(stream)));
+    return 0;
+}
+
+int uavtrack_learner_check(uavtrack_learner *learner, int64_t *refused, void *stream)
+{
+    int count = 0;
+    if (take_refusals(__func__, learner, refused, stream, &count)) return 1;
+    if (count)
+        return fail("uavtrack_learner_check: %d update(s) refused: an action outside [0, %d), an index outside "
+                    "[0, capacity), an importance weight that is NaN, infinite or negative or a discount that is NaN or "
+                    "outside [0, 1], or (uavtrack_learner_apply) a gradient row of another layout; they changed nothing",
+                    count, learner->d.L.A);
+    return 0;
+}
+
+}  // extern "C"

@@ -18,7 +18,7 @@
 // close is the same chain with "holds at least one step" in place of the done flag.  No atomics anywhere: the log's
 // order is the scan's, and every sum has one order (include/uavtrack.h states it).
 
-#include "internal.h"
+#include "episode.h"
 
 #include <hip/hip_runtime.h>
 #include <cstdint>

@@ -3,7 +3,7 @@
 // bits.  `upos(j)` / `tpos(k)` return the (x, y) of UAV j / target k of this UAV's environment,
 // `near(k)` the number of UAVs within dc of target k (computed once per target).
 #pragma once
-#include "internal.h"
+#include "env.h"
 #include "philox.h"
 
 namespace uavtrack {

@@ -44,7 +44,7 @@
 // The critic alone (uavtrack_learner_values): learner_values_kernel, at the end of the kernels below, evaluates V(x) of
 // any number of rows by the chain of the layer-1 and layer-2 loops above, to the bit, and touches no learner state.
 
-#include "internal.h"
+#include "learner.h"
 
 #include <hip/hip_runtime.h>
 #include <cmath>
@@ -364,7 +364,7 @@ __global__ void learner_finalize_kernel(const float *src, int count, size_t stri
     for (int q = 0; q < kLearnerTensors; ++q) steps[q] += 1;
 }
 
-// Both torch.optim.Adam steps (adam_element, internal.h) on the gradient sums of `count` rows, added in row order and
+// Both torch.optim.Adam steps (adam_element, adam.h) on the gradient sums of `count` rows, added in row order and
 // scaled once.
 __global__ void learner_adam_kernel(float *params, float *m, float *v, const float *src, int count, size_t stride,
                                     LearnerLayout L, const int *status, const int64_t *steps, const float *scal,

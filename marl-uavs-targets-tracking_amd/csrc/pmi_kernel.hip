@@ -21,10 +21,10 @@
 // pmi_mix_kernel: one thread per UAV-step: neighbours in index order, max-shifted softmax of
 // their scores (scipy.special.softmax, uav.py:287), reward = (1-a) raw_i + a sum_j w_j raw_j,
 // (1-a) raw_i without neighbours (uav.py:290), final clip (environment.py:225).  It finds the
-// score of (i, j) through the neighbour records the rollout kernel wrote (internal.h: nbrec_words):
+// score of (i, j) through the neighbour records the rollout kernel wrote (env.h: nbrec_words):
 // UAV min(i, j) emitted the pair, in the slot "its first slot + rank of max(i, j) among its later neighbours".
 
-#include "internal.h"
+#include "env.h"
 #include "pmi_pack.h"
 
 #include <cstring>
@@ -1016,7 +1016,7 @@ __global__ void __launch_bounds__(H * 2, 1) pmi_score_t3_kernel(const PmiParams 
 }
 
 struct MixParams {
-    const uint32_t *nbrec;       // [S][B][N][W + 1] neighbour records of the chunk's S steps (internal.h, nbrec_words)
+    const uint32_t *nbrec;       // [S][B][N][W + 1] neighbour records of the chunk's S steps (env.h, nbrec_words)
     const float *scores;         // one per emitted pair
     float *reward;               // [S][B][N]: in, what the rollout kernel left (raw reward of a UAV with neighbours, final reward of one without); out, final
     float *rsum;                 // [S][B] mean over the UAVs of the final reward (nullable): what the episode sum adds up
@@ -1301,14 +1301,14 @@ hipError_t launch_pmi_inference_prep(const float *x, float *obs2, uint2 *pairs, 
 
 int pmi_effective_scheme(const uavtrack_env *env)
 {
-    const bool split = pmi_x6_floats(env->pmi.hidden) != 0;       // widths whose planes stay register-resident: 64, 96, 128
+    const bool split = PmiBlobLayout::make(env->pmi.hidden).x6_len != 0;       // widths whose planes stay register-resident: 64, 96, 128
     if (env->pmi_scheme != UAVTRACK_PMI_AUTO) return env->pmi_scheme;
     return split && env->pmi.t3 ? UAVTRACK_PMI_F16X3 : split ? UAVTRACK_PMI_BF16X6 : UAVTRACK_PMI_FP32;
 }
 
 bool pmi_scheme_fits(int hidden_padded, bool f16_range_ok, int scheme)
 {
-    const bool split = pmi_x6_floats(hidden_padded) != 0;
+    const bool split = PmiBlobLayout::make(hidden_padded).x6_len != 0;
     switch (scheme) {
     case UAVTRACK_PMI_AUTO:   return true;
     case UAVTRACK_PMI_F16X3:  return split && f16_range_ok;     // (not ok: a weight or an activation bound beyond f16's range)

@@ -8,9 +8,17 @@
 // not agree on.
 #pragma once
 
-#include "internal.h"
+#include <hip/hip_runtime.h>
+#include <stddef.h>
+#include <stdint.h>
+
+#include "pmi_net.h"
+#include "uavtrack.h"
 
 namespace uavtrack {
+
+constexpr int kPmiX6MaxHidden = 128;                // widest layer whose three bf16 planes stay register-resident (4 waves, one per SIMD)
+constexpr int kPmiX6MinHidden = 64;                 // (narrower layers have fewer k-steps than the producer has pairs to hide)
 
 // The weights allocation, in floats: the fp32 blob in scorer order (pack_pmi_blob), padded to 16 bytes; for the widths
 // with split kernels (64 / 96 / 128) the bf16 planes of fc1 (pack_pmi_x6), the f16 planes of the branch layers
@@ -21,14 +29,14 @@ struct PmiBlobLayout {
     {
         PmiBlobLayout L;
         const size_t HP = (size_t)hp;
-        const bool split = hp >= kPmiX6MinHidden && hp <= kPmiX6MaxHidden;      // (pmi_x6_floats / pmi_l1_floats / pmi_t3_floats, internal.h)
+        const bool split = hp >= kPmiX6MinHidden && hp <= kPmiX6MaxHidden;
         L.n_dev = 12 * HP + 3 * HP + 3 * HP * HP + HP + HP + 1;
         L.x6_off = (L.n_dev + 3) & ~(size_t)3;
-        L.x6_len = split ? 3 * HP * HP * 3 / 2 : 0;
+        L.x6_len = split ? 3 * HP * HP * 3 / 2 : 0;                 // 3 planes x 2 B
         L.l1_off = L.x6_off + L.x6_len;
-        L.l1_len = split ? (HP / 32) * 3 * 3 * 64 * 8 / 2 : 0;
+        L.l1_len = split ? (HP / 32) * 3 * 3 * 64 * 8 / 2 : 0;      // [w][branch][3 planes][lane][8] x 2 B
         L.t3_off = L.l1_off + L.l1_len;
-        L.t3_len = split ? 3 * HP * HP : 0;
+        L.t3_len = split ? 3 * HP * HP : 0;                         // 2 planes x 2 B
         L.scal_off = L.t3_off + L.t3_len;
         L.total = L.scal_off + 8;
         return L;
@@ -166,5 +174,11 @@ struct PmiPackArgs {
     float *blob;                           // the weights allocation (PmiBlobLayout::make(HP))
 };
 hipError_t launch_pmi_pack(const PmiPackArgs &a, hipStream_t stream);
+
+// pmi_kernel.hip -- the host packers of uavtrack_set_pmi_weights
+void pack_pmi_blob(const float *abi_blob, float *device_order, int hidden);
+void pack_pmi_x6(const float *abi_blob, uint16_t *planes, int hidden);
+void pack_pmi_t3(const float *abi_blob, uint16_t *planes, int hidden, float T);
+void pack_pmi_l1(const float *abi_blob, uint16_t *planes, int hidden, float S1);
 
 }  // namespace uavtrack

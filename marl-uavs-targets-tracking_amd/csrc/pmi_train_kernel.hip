@@ -26,7 +26,7 @@
 // in the same wavefront, which applies their running-statistics updates in the reference's order.
 // Intermediates are stored feature-major ([side][feature][row]) so the lanes of a wavefront read consecutive rows.
 
-#include "internal.h"
+#include "pmi_train.h"
 
 #include <hip/hip_runtime.h>
 #include <cmath>
@@ -436,7 +436,7 @@ __global__ void __launch_bounds__(kWG) pmi_branch_bwd_kernel(StepArgs a)
     }
 }
 
-// The torch.optim.Adam step (adam_element, internal.h) of every trainable element, in place in the state; the step
+// The torch.optim.Adam step (adam_element, adam.h) of every trainable element, in place in the state; the step
 // counts were advanced by this step's pmi_head_kernel
 __global__ void pmi_adam_kernel(PmiTrainLayout L, float *state, float *m, float *v, const float *grad,
                                 const int64_t *steps, const int *status, float lr)

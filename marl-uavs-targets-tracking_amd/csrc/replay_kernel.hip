@@ -41,7 +41,7 @@
 //                              chain walks the rollout backwards, carries the lambda-return G and overwrites the written
 //                              slots' rewards with R_t, leaving d_t in the discount store.
 
-#include "internal.h"
+#include "replay.h"
 #include "philox.h"
 
 #include <hip/hip_runtime.h>

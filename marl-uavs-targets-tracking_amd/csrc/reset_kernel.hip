@@ -5,7 +5,7 @@
 // (seed, global env id, episode, agent index), so any sharding of the batch over GPUs
 // reproduces the same environments.
 
-#include "internal.h"
+#include "env.h"
 #include "philox.h"
 
 namespace uavtrack {

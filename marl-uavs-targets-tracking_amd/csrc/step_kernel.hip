@@ -777,7 +777,7 @@ __global__ void __launch_bounds__(kMaxWorkgroup) rollout_kernel(const StepParams
     auto pmi_reward_slot = [&](bool has_neighbours, float raw_i) {
         return has_neighbours ? raw_i : fminf(fmaxf((1.0f - p.coop) * raw_i, -1.0f), 1.0f);
     };
-    auto store_record = [&](unsigned tg, unsigned long long nball, unsigned first) {      // N <= 64 (internal.h, nbrec_words)
+    auto store_record = [&](unsigned tg, unsigned long long nball, unsigned first) {      // N <= 64 (env.h, nbrec_words)
         if (N <= 32) out_store(reinterpret_cast<uint2 *>(p.nbrec + (size_t)tg * 2), (unsigned)nball, first);
         else {
             uint32_t *rec = p.nbrec + (size_t)tg * 3;
@@ -1335,7 +1335,7 @@ __global__ void __launch_bounds__(kMaxWorkgroup) rollout_kernel(const StepParams
         if (MODE == UAVTRACK_REWARD_PMI) {
             unsigned *wg_cnt = covw + 2 * E * CW;          // two extra words behind the coverage masks
             if (tid == 0) wg_cnt[0] = 0;
-            // One record per agent-step for the mix kernel (internal.h, nbrec_words): the neighbour mask, where this
+            // One record per agent-step for the mix kernel (env.h, nbrec_words): the neighbour mask, where this
             // UAV's pairs start in the pair list (their scores land in the same slots), and the raw reward.
             const int W = nbrec_mask_words(N);
             int mine = 0, slot = 0;

@@ -21,7 +21,7 @@ SCALE_EXP = 60                 # kActorScaleExp: T1, T2 in [2^-60, 2^60]
 
 
 def actor_xb(x_max=2000.0, y_max=2000.0, dc=500.0, u_v_max=20.0, t_v_max=5.0) -> np.ndarray:
-    """The nominal observation bounds uavtrack_set_actor_weights builds (csrc/api.hip)."""
+    """The nominal observation bounds uavtrack_set_actor_weights builds (csrc/api_env.hip)."""
     vr = 1.0 + t_v_max / u_v_max
     pos = 4.0 * max(x_max, y_max) / dc
     return np.array([1, 1, 2, 2, 1, 1, 1, vr, vr, pos, pos, 1], np.float64)

@@ -27,7 +27,7 @@ POLICY_SEED = 99
 # oracle's pair evaluations, stays below 2e8 (the largest here: 203 * 3 * 4096 * 3 = 7.5e6).
 Shape = namedtuple("Shape", "name N M B box seed na env_offset steps")
 
-# na_max: validate() (csrc/api.hip) puts no upper bound of its own on na with nc = 1; the bound a handle meets is
+# na_max: validate() (csrc/api_env.hip) puts no upper bound of its own on na with nc = 1; the bound a handle meets is
 # uavtrack_create's on the specialised shapes of up to 64 UAVs, n_uav^2 * na * nc * 4 < 2^24.  At 50 x 25 that is
 # na <= 1677 (2500 * 1677 * 4 = 16 770 000 < 16 777 216 <= 2500 * 1678 * 4).  The turn rates are then pi / (6 * 1676) =
 # 3.1e-4 apart in halves, three times the angle tolerance, so steering decisions can still be compared.  (At 20 x 10 the

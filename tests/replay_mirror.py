@@ -8,7 +8,7 @@ import numpy as np
 from oracle import philox4x32_10
 
 DOMAIN = 0x52504C59          # "RPLY": Philox counter word 3 of the draw stream
-TILE = 2048                  # kReplayTile (csrc/internal.h)
+TILE = 2048                  # kReplayTile (csrc/replay.h)
 M32 = 0xFFFFFFFF
 
 

@@ -16,7 +16,7 @@ tests/test_hip_variant_census.py runs every entry against the fp64 oracle.
 from collections import namedtuple
 
 RAW, MEAN, PMI = 0, 1, 2                  # UAVTRACK_REWARD_* (include/uavtrack.h), uavtrack.RewardMode
-GIVEN, GREEDY, ACTOR = 0, 1, 2            # kPolicy* (csrc/internal.h)
+GIVEN, GREEDY, ACTOR = 0, 1, 2            # kPolicy* (csrc/env.h)
 MODE_NAMES = {RAW: "raw", MEAN: "mean", PMI: "pmi"}
 POLICY_NAMES = {GIVEN: "given", GREEDY: "greedy", ACTOR: "actor"}
 
