@@ -16,6 +16,7 @@ update is the same rule on a sampled batch, and the new actor weights are re-upl
     python examples/train_maac.py --replay prioritized --learner device --importance --beta-final 1.0     # train on the importance weights, beta annealed on the device
     python examples/train_maac.py --replay prioritized --learner device --n-step 3                        # 3-step returns folded by the ring's add
     python examples/train_maac.py --replay prioritized --learner device --td-lambda 0.9                   # lambda-returns: critic values + a backward scan in the ring's add
+    python examples/train_maac.py --replay prioritized --learner device --rho-bar 1.0 --publish device --log-every 10   # truncated importance ratios: who acted
     python examples/train_maac.py --method maac-r --pmi-trainer device --learner device --replay prioritized --publish device --log-every 10
     python examples/train_maac.py --shards 8 --envs 32768 --n-uav 20 --learner device --replay prioritized --publish device   # 8 shard handles, one learner
     python examples/train_maac.py --shards 4 --method maac-r --pmi-trainer device --learner device --replay prioritized --publish device   # ... and one PMI trainer
@@ -58,19 +59,27 @@ class ValueNet(torch.nn.Module):
         return self.fc2(torch.relu(self.fc1(x))).squeeze(-1)
 
 
-def update(actor, critic, opt_a, opt_c, batch, gamma, weights=None, entropy_coef=0.0, max_grad_norm=None, diag=None):
+def update(actor, critic, opt_a, opt_c, batch, gamma, weights=None, entropy_coef=0.0, max_grad_norm=None, diag=None,
+           rho_bar=None, rho_stats=None):
     """One ActorCritic.update step (actor_critic.py:150-178) on a batch of transitions.  weights (--importance): the
     draw's importance weights, one per row, multiplied into the per-sample losses before the mean.  entropy_coef and
     max_grad_norm: the two terms of DeviceActorCritic.set_regularisation, so that --learner torch and --learner device
     stay comparable; diag (a dict) receives the mean entropy and the two gradient norms before clipping.  A batch from an
     n-step ring (--n-step) carries "discounts", gamma^m per row, which take gamma's place in the target; so does a batch
-    from a lambda ring (--td-lambda), whose rewards and discounts make that target the lambda-return."""
+    from a lambda ring (--td-lambda), whose rewards and discounts make that target the lambda-return.  rho_bar (--rho-bar):
+    the batch carries "log_mu" and every row's losses are multiplied by min(rho_bar, pi / mu), a constant of the
+    differentiation, as DeviceActorCritic.update_from(rho_bar=) does; rho_stats (a dict) receives the ratios."""
     s, a, r, s2 = batch["states"], batch["actions"].long().unsqueeze(1), batch["rewards"], batch["next_states"]
     td_target = r + batch.get("discounts", gamma) * critic(s2)
     td_delta = td_target - critic(s)
     probs = actor(s)
     log_probs = torch.log(probs.gather(1, a).squeeze(1).clamp_min(1e-12))
     per_row = -log_probs * td_delta.detach()
+    if rho_bar is not None:
+        rho = torch.exp(log_probs.detach() - batch["log_mu"]).clamp(max=rho_bar)
+        weights = rho if weights is None else weights * rho
+        if rho_stats is not None:
+            rho_stats["rho"] = rho
     if entropy_coef or diag is not None:
         entropy = -(probs * torch.log(probs.clamp_min(1e-12))).sum(dim=1)
         if entropy_coef:
@@ -113,6 +122,26 @@ def nstep_ring(args, ring):
     if args.td_lambda is not None:
         return ring.with_lambda(args.td_lambda, args.gamma)
     return ring.with_nstep(args.n_step, args.gamma) if args.n_step > 1 else ring
+
+
+def behaviour_ring(args, ring):
+    """--rho-bar: the ring keeps the behaviour log-probability of every slot (with_behaviour)."""
+    return ring if args.rho_bar is None else ring.with_behaviour()
+
+
+def add_rollout(args, ring, obs_in, res, acted, critic):
+    """The rollout's outputs into the ring, before the iteration's updates.  --rho-bar: with the log-probabilities of
+    `acted` -- the device learner, or the PyTorch actor -- whose actor at this moment is the one the rollout ran."""
+    if args.rho_bar is None:
+        ring.add_rollout(obs_in, res, **critic_kwargs(args, critic))
+    else:
+        ring.add_rollout_behaviour(obs_in, res, behaviour=acted, **critic_kwargs(args, critic))
+
+
+def rho_field(rho, rho_bar):
+    """The printed lines' extra field under --rho-bar: the mean ratio of the last update's batch and the share of its rows
+    at the cap (a read of the device buffer rho_out filled: printed lines only)."""
+    return f"rho mean {float(rho.mean()):.4f} at cap {float((rho >= rho_bar).float().mean()):.3f}  "
 
 
 def critic_kwargs(args, critic):
@@ -220,7 +249,8 @@ def train_sharded(args, timings=None):
     else:                                                             # uniform-device
         rings = [uavtrack.ReplayRing(2 * e.cfg.n_envs * args.n_uav * args.steps, dev, seed=args.seed + 7919 * k,
                                      max_batch=per_shard) for k, e in enumerate(envs)]
-    rings = [nstep_ring(args, ring) for ring in rings]
+    rings = [behaviour_ring(args, nstep_ring(args, ring)) for ring in rings]
+    rho_bufs = [torch.empty(per_shard, device=dev) for _ in rings] if args.rho_bar is not None else None
     per_iter = args.envs * args.n_uav * args.steps
     stats = [uavtrack.EpisodeStats(e, log_capacity=e.cfg.n_envs * args.log_every, max_steps=args.steps) for e in envs]
     kept = {k: [] for k in SIX}
@@ -236,17 +266,23 @@ def train_sharded(args, timings=None):
             obs_in = ro.obs.clone()
             res = ro.run_fused(args.steps, out=outs[k], stats=stats[k])    # done fires at the horizon: one record per episode
             outs[k] = {key: v for key, v in res.items() if key != "ep_sums"}
-            ring.add_rollout(obs_in, res, **critic_kwargs(args, learner))   # (--td-lambda: every ring, the one learner's values)
+            add_rollout(args, ring, obs_in, res, learner, learner)   # (--td-lambda: every ring, the one learner's values)
             eps.append(res["ep_sums"])
         if log:
             torch.cuda.synchronize()
         t_roll = time.perf_counter() - t0
+        rho_kw = {}
+        if rho_bufs is not None:                                      # every ring's ratios, read on printed lines only
+            rhos = [b[:min(per_shard, ring.count)] for b, ring in zip(rho_bufs, rings)]
+            rho_kw = {"rho_bar": args.rho_bar, "rho_out": rhos}
         for _ in range(args.updates):
-            la_t, lc_t, tds = learner.update_from_many(rings, per_shard, **importance_kwargs(args))
+            la_t, lc_t, tds = learner.update_from_many(rings, per_shard, **importance_kwargs(args), **rho_kw)
         la, lc = (float(la_t), float(lc_t)) if log else (la_t, lc_t)
         reg_field = ""
         if log and regularised(args):                                 # the last ring's rows of the last update
             reg_field = regularisation_field(learner.entropy(tds[-1].numel()).mean(), learner.grad_norm)
+        if log and rho_kw:
+            reg_field += rho_field(torch.cat(rhos), args.rho_bar)
         if args.publish == "host":
             actor.load_state_dict(learner.actor_state_dict())
             for ro in rollouts:
@@ -346,6 +382,14 @@ def main(argv=None, timings=None):
                          "add_rollout(critic=...)): each slot keeps r + gamma L G' as its reward and gamma (1 - L) as its "
                          "discount, never across an episode end or the rollout's last step.  Needs --replay prioritized or "
                          "uniform-device; not with --n-step > 1")
+    ap.add_argument("--rho-bar", type=float, default=None,
+                    help="R > 0: correct for who acted.  The ring keeps log mu(a|s) of every slot, evaluated by the learner's "
+                         "actor over the window each add writes (ring.with_behaviour(), add_rollout_behaviour), and every "
+                         "update weighs its rows by the truncated importance ratio min(R, pi / mu) "
+                         "(DeviceActorCritic.update_from(rho_bar=R); the torch learner multiplies its per-sample losses by "
+                         "the same ratios); the printed lines show the mean ratio and the share of rows at the cap.  With "
+                         "--n-step or --td-lambda the ratio corrects the first action only.  Needs --replay prioritized or "
+                         "uniform-device")
     ap.add_argument("--alpha", type=float, default=0.6, help="--replay prioritized: priority exponent (train.py:74)")
     ap.add_argument("--beta", type=float, default=0.4, help="--replay prioritized: importance exponent (train.py:100)")
     ap.add_argument("--importance", action="store_true",
@@ -412,6 +456,9 @@ def main(argv=None, timings=None):
         if args.replay == "uniform":
             ap.error("--td-lambda needs --replay prioritized or --replay uniform-device: the lambda-returns are folded by "
                      "the device rings' add (the PyTorch buffer of --replay uniform stores one-step transitions)")
+    if args.rho_bar is not None and (not args.rho_bar > 0 or args.replay == "uniform"):
+        ap.error("--rho-bar must be > 0 and needs --replay prioritized or --replay uniform-device (the device rings keep "
+                 "the behaviour log-probabilities)")
     if args.importance and args.replay != "prioritized":
         ap.error("--importance needs --replay prioritized (a uniform draw has no importance weights)")
     if args.beta_final is not None and not args.importance:
@@ -471,9 +518,10 @@ def main(argv=None, timings=None):
     elif args.replay == "uniform-device":
         replay = uavtrack.ReplayRing(2 * per_iter, dev, seed=args.seed, max_batch=args.batch)
     if args.replay != "uniform":
-        replay = nstep_ring(args, replay)
+        replay = behaviour_ring(args, nstep_ring(args, replay))
     else:
         replay = uavtrack.DeviceReplayBuffer(capacity=2 * per_iter, device=dev)
+    rho_buf = torch.empty(args.batch, device=dev) if args.rho_bar is not None and learner is not None else None
     stats = uavtrack.EpisodeStats(env, log_capacity=args.envs * K * args.log_every, max_steps=T)
     kept = {k: [] for k in SIX}
     history = []
@@ -491,14 +539,17 @@ def main(argv=None, timings=None):
         res = rollout.run_fused(T, out=out, stats=stats)              # K * B episodes, one launch; done at the horizon closes them
         out = {k: v for k, v in res.items() if k != "ep_sums"}        # reuse the output buffers next time
         if args.replay != "uniform":
-            replay.add_rollout(obs_in, res, **critic_kwargs(args, critic if learner is None else learner))   # straight from the outputs
+            add_rollout(args, replay, obs_in, res, actor if learner is None else learner,
+                        critic if learner is None else learner)      # straight from the outputs
         else:
             replay.add(uavtrack.transitions_from_rollout(obs_in, res))
         if log:
             torch.cuda.synchronize()
         t_roll = time.perf_counter() - t0
         diag = {} if log and regularised(args) else None              # the torch learner's entropy and norms
-        reg_kw = dict(entropy_coef=args.entropy_coef, max_grad_norm=args.max_grad_norm, diag=diag)
+        rho_stats = {}                                                # --rho-bar: the last update's ratios, a device tensor
+        reg_kw = dict(entropy_coef=args.entropy_coef, max_grad_norm=args.max_grad_norm, diag=diag, rho_bar=args.rho_bar,
+                      rho_stats=rho_stats)
         if learner is None and args.replay == "prioritized":          # train.py:250-262
             ikw = importance_kwargs(args)
             for _ in range(args.updates):
@@ -511,8 +562,12 @@ def main(argv=None, timings=None):
             for _ in range(args.updates):
                 la, lc = update(actor, critic, opt_a, opt_c, replay.sample(args.batch), args.gamma, **reg_kw)
         else:
+            rho_kw = {}
+            if args.rho_bar is not None:
+                rho_stats["rho"] = rho_buf[:min(args.batch, replay.count)]
+                rho_kw = {"rho_bar": args.rho_bar, "rho_out": rho_stats["rho"]}
             for _ in range(args.updates):
-                la_t, lc_t, td_t = learner.update_from(replay, args.batch, **importance_kwargs(args))
+                la_t, lc_t, td_t = learner.update_from(replay, args.batch, **importance_kwargs(args), **rho_kw)
             la, lc = (float(la_t), float(lc_t)) if log else (la_t, lc_t)
             if diag is not None:
                 diag.update(entropy=learner.entropy(td_t.numel()).mean(), norms=learner.grad_norm)
@@ -556,6 +611,8 @@ def main(argv=None, timings=None):
         n_iter = it + 1 - (stamps[-1][0] if stamps else 0)           # iterations since the previous line
         stamps.append((it + 1, now))
         reg_field = regularisation_field(diag["entropy"], diag.get("norms")) if diag else ""
+        if args.rho_bar is not None:
+            reg_field += rho_field(rho_stats["rho"], args.rho_bar)
         print(f"iter {it:3d}  episode return {ret:8.3f}  covered targets/step {cov:5.2f}  actor loss {la:+.4f}  "
               f"critic loss {lc:.4f}  {reg_field}pmi loss {lp:.4f}  rollout {t_roll * 1e3:6.1f} ms ({per_iter / t_roll / 1e9:.2f} G agent-steps/s)  "
               f"iteration {((now - t0) if args.log_every == 1 else (now - t_log) / n_iter) * 1e3:6.1f} ms  {six}", flush=True)
@@ -563,6 +620,8 @@ def main(argv=None, timings=None):
     save_results(args, kept)
     if args.replay == "prioritized":
         replay.check()                                                # no draw was refused on the device
+    if learner is not None and args.rho_bar is not None:
+        learner.check()                                               # no update met a slot whose behaviour is unknown
     env.close()
     history = [float(r) for r in history]
     if timings is not None:

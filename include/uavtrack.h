@@ -670,6 +670,59 @@ int uavtrack_learner_grad_discounted(uavtrack_learner *learner, int64_t n,
  * the critic of that moment.  Returns an error, enqueuing nothing, for a null pointer, n < 1 or misaligned rows. */
 int uavtrack_learner_values(uavtrack_learner *learner, int64_t n, const float *rows, float *values, void *stream);
 
+/* ---- the actor alone, and off-policy correction: truncated importance ratios as update weights ----
+ * Rows of a replay ring were acted by the actor of the moment they were added (the behaviour policy mu), not by the one
+ * an update differentiates (pi).  The truncated ratio rho_i = min(rho_bar, pi(a_i|s_i) / mu(a_i|s_i)) is one weight per
+ * batch row, and the weighted entry points above take one weight per batch row: with w_i = rho_i,
+ * UAVTRACK_LOSS_PER_SAMPLE trains mean_i(-rho_i log p_i delta_i) and mean_i(rho_i (V(s_i) - y_i)^2), rho a constant of
+ * the differentiation -- the truncated-importance-sampling policy gradient and the rho-weighted TD(0) critic, the
+ * one-step case of V-trace.  The ratio corrects the FIRST action of a transition only: on an n-step or lambda ring the
+ * later actions of the window stay uncorrected (no traces; Retrace and full V-trace are not built).
+ *
+ * log pi(a|s) of a row, with the learner's actor parameters as they stand when the launch executes, H = hidden:
+ *   p_j = b1a[j]; for k = 0 .. 11: p_j = fmaf(W1a[j][k], s[k], p_j); h_j = fmaxf(p_j, 0);
+ *   z_o = b2a[o]; for j = 0 .. H - 1: z_o = fmaf(W2a[o][j], h_j, z_o);
+ *   log p_a = (z_a - max_o z_o) - logf(sum_o expf(z_o - max)),   the sum in ascending o
+ * the chains of the update's own actor forward and the logits form of its regularised rows: finite for every finite
+ * logit vector, also where a probability underflows.  The bits of a row depend on the row and the parameters alone, not
+ * on n, on the addressing mode or on where in a launch the row falls.  A slot outside [0, capacity) or an action outside
+ * [0, A) gives NaN for that row; no status word is involved.
+ * All three calls are stream-ordered: no synchronisation, no allocation, no scratch (n is not limited by the reserved
+ * batch), capturable, and they change no learner state.  states (DEVICE fp32 [capacity][12], 16-byte aligned) and
+ * actions (DEVICE int32 [capacity]) are a ring's stores.  Returns an error, enqueuing nothing, for a null required
+ * pointer, n < 1, n > capacity where no indices choose the rows, misaligned states, and what each call names below. */
+
+/* batch order: row i reads slot indices[i] (indices NULL: slot i, capacity >= n); log_probs[i] (DEVICE fp32 [n]) */
+int uavtrack_learner_log_probs(uavtrack_learner *learner, int64_t n, const float *states, const int32_t *actions,
+                               int64_t capacity, const int64_t *indices, float *log_probs, void *stream);
+
+/* ring window: slots (first + k) % capacity, k < n <= capacity, 0 <= first < capacity; writes log_mu[slot] (DEVICE fp32
+ * [capacity], a ring's sixth store).  Run behind a ring add over the window the add has just written, it leaves the
+ * behaviour log-probabilities of the new transitions -- provided the learner's actor is, at that moment, the one that
+ * acted: the add has to come before the updates of the iteration.  (A rollout whose actor runs on the f16 matrix cores
+ * "at fp32 accuracy" sampled from this distribution to that accuracy, not to the bit.) */
+int uavtrack_learner_log_probs_window(uavtrack_learner *learner, const float *states, const int32_t *actions,
+                                      int64_t capacity, int64_t first, int64_t n, float *log_mu, void *stream);
+
+/* The weights of a batch, fused with the forward.  With src_i = indices[i] (indices NULL: i):
+ *   rho_i          = fminf((float)rho_bar, expf(log p_i - log_mu[src_i]))
+ *   weights_out[i] = (weights_in ? weights_in[i] : 1.0f) * rho_i       (DEVICE fp32 [n]; weights_out may alias weights_in)
+ *   rho_out[i]     = rho_i                                              (DEVICE fp32 [n], nullable)
+ * log_mu is DEVICE fp32 [capacity], indexed by slot.  rho_bar > 0; +inf means untruncated (rho_bar <= 0 or NaN is
+ * refused on the host).  A log_mu that is NaN ("unknown") or > 0 gives rho_i = NaN, and so do a bad slot and a bad
+ * action; an overflowing untruncated ratio is +inf.  The update behind the call refuses a NaN, infinite or negative
+ * weight on the device (status bit 2), so an unknown behaviour policy refuses the update with no host involvement.
+ * expf(0.0f) == 1.0f: a row whose log_mu holds the bits this kernel would form now has rho_i == 1 exactly, so an
+ * on-policy batch at rho_bar >= 1 trains with the bits of the unweighted update.  weights_in carries a prioritised
+ * draw's importance weights; the product is not normalised again.
+ * Measured on one MI355X, H = 128, A = 12: uavtrack_learner_log_probs_window over 2 048 000 slots
+ * 212 us and over 16 384 000 slots 1.60 ms (2.3 x uavtrack_learner_values on the same rows; bound by the LDS reads of the
+ * actor's records); this call at n = 65 536 28 us; an update of 65 536 rows behind a draw 863 us with it against 829 us
+ * without (uniform ring), 1 737 us against 1 707 us (prioritised ring with importance weights). */
+int uavtrack_learner_ratio_weights(uavtrack_learner *learner, int64_t n, const float *states, const int32_t *actions,
+                                   const float *log_mu, int64_t capacity, const int64_t *indices, double rho_bar,
+                                   const float *weights_in, float *weights_out, float *rho_out, void *stream);
+
 /* Synchronises `stream`; fails if any update or apply since the previous check was refused on the device (bad action,
  * index, importance weight or discount, or a row of another layout).  refused (nullable) receives their number; the count restarts at 0. */
 int uavtrack_learner_check(uavtrack_learner *learner, int64_t *refused, void *stream);

@@ -3,6 +3,7 @@
 #include "api_env.h"
 #include "api_handle.h"
 #include "learner.h"
+#include "learner_policy.h"
 
 #include <cmath>
 
@@ -340,6 +341,81 @@ int uavtrack_learner_values(uavtrack_learner *learner, int64_t n, const float *r
     if (((uintptr_t)rows & 15) != 0) return fail("%s: rows must be 16-byte aligned", __func__);
     ON_DEVICE(learner->cfg.device_id);
     HIP_TRY(launch_learner_values(learner->d, n, rows, values, static_cast<hipStream_t>(stream)));
+    return 0;
+}
+
+}  // extern "C"
+
+namespace {
+
+// what uavtrack_learner_log_probs, _log_probs_window and _ratio_weights test alike, after their null tests
+int accept_policy_rows(const char *fn, int64_t n, const float *states, int64_t capacity)
+{
+    if (n < 1) return fail("%s: n = %lld < 1", fn, (long long)n);
+    if (capacity < 1) return fail("%s: capacity = %lld < 1", fn, (long long)capacity);
+    if (capacity > INT64_MAX / 48) return fail("%s: capacity = %lld slots overflow", fn, (long long)capacity);
+    if (((uintptr_t)states & 15) != 0) return fail("%s: states must be 16-byte aligned", fn);
+    return 0;
+}
+
+PolicyLaunch policy_rows(int64_t n, const float *states, const int32_t *actions, int64_t capacity, const int64_t *indices)
+{
+    PolicyLaunch q = {};
+    q.n = n; q.capacity = capacity; q.first = -1; q.states = states; q.actions = actions; q.idx = indices;
+    return q;
+}
+
+}  // namespace
+
+extern "C" {
+
+int uavtrack_learner_log_probs(uavtrack_learner *learner, int64_t n, const float *states, const int32_t *actions,
+                               int64_t capacity, const int64_t *indices, float *log_probs, void *stream)
+{
+    if (!learner) return fail("%s: null handle", __func__);
+    if (!states || !actions || !log_probs) return fail("%s: states, actions and log_probs must not be null", __func__);
+    if (accept_policy_rows(__func__, n, states, capacity)) return 1;
+    if (!indices && n > capacity)
+        return fail("%s: n = %lld rows without indices from a store of %lld", __func__, (long long)n, (long long)capacity);
+    ON_DEVICE(learner->cfg.device_id);
+    PolicyLaunch q = policy_rows(n, states, actions, capacity, indices);
+    q.log_probs = log_probs;
+    HIP_TRY(launch_learner_policy(learner->d, q, static_cast<hipStream_t>(stream)));
+    return 0;
+}
+
+int uavtrack_learner_log_probs_window(uavtrack_learner *learner, const float *states, const int32_t *actions,
+                                      int64_t capacity, int64_t first, int64_t n, float *log_mu, void *stream)
+{
+    if (!learner) return fail("%s: null handle", __func__);
+    if (!states || !actions || !log_mu) return fail("%s: states, actions and log_mu must not be null", __func__);
+    if (accept_policy_rows(__func__, n, states, capacity)) return 1;
+    if (n > capacity) return fail("%s: a window of n = %lld slots in a ring of %lld", __func__, (long long)n, (long long)capacity);
+    if (first < 0 || first >= capacity)
+        return fail("%s: first = %lld outside [0, %lld)", __func__, (long long)first, (long long)capacity);
+    ON_DEVICE(learner->cfg.device_id);
+    PolicyLaunch q = policy_rows(n, states, actions, capacity, nullptr);
+    q.first = first;
+    q.log_probs = log_mu;
+    HIP_TRY(launch_learner_policy(learner->d, q, static_cast<hipStream_t>(stream)));
+    return 0;
+}
+
+int uavtrack_learner_ratio_weights(uavtrack_learner *learner, int64_t n, const float *states, const int32_t *actions,
+                                   const float *log_mu, int64_t capacity, const int64_t *indices, double rho_bar,
+                                   const float *weights_in, float *weights_out, float *rho_out, void *stream)
+{
+    if (!learner) return fail("%s: null handle", __func__);
+    if (!states || !actions || !log_mu || !weights_out)
+        return fail("%s: states, actions, log_mu and weights_out must not be null", __func__);
+    if (accept_policy_rows(__func__, n, states, capacity)) return 1;
+    if (!indices && n > capacity)
+        return fail("%s: n = %lld rows without indices from a store of %lld", __func__, (long long)n, (long long)capacity);
+    if (!(rho_bar > 0)) return fail("%s: rho_bar = %g must be > 0 (+inf: untruncated)", __func__, rho_bar);
+    ON_DEVICE(learner->cfg.device_id);
+    PolicyLaunch q = policy_rows(n, states, actions, capacity, indices);
+    q.log_mu = log_mu; q.rho_bar = (float)rho_bar; q.weights_in = weights_in; q.weights_out = weights_out; q.rho_out = rho_out;
+    HIP_TRY(launch_learner_policy(learner->d, q, static_cast<hipStream_t>(stream)));
     return 0;
 }
 

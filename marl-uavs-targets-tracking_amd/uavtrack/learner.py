@@ -41,6 +41,16 @@ _grad_discounted).  Everything behind the target is unchanged.  Without discount
 was, and a store of float32(gamma) gives the same bits; d_i = 0 means "do not bootstrap".  A discount that is NaN,
 negative or above 1 refuses the update on the device like a bad action.
 
+Off-policy correction (update(log_mu=, rho_bar=), update_from(ring, k, rho_bar=R) and the same on grad_from,
+update_from_many and the group path, on a ring made with_behaviour()): the truncated importance ratio
+rho_i = min(R, pi(a_i|s_i) / mu(a_i|s_i)) is one more weight per batch row, formed by uavtrack_learner_ratio_weights from
+the ring's per-slot log mu and the actor as it stands, and multiplied into the draw's importance weights (or 1).  With
+loss="per_sample" the losses above are then the truncated-importance-sampling policy gradient and the rho-weighted TD(0)
+critic, rho a constant of the differentiation: the one-step case of V-trace.  Only the first action of a transition is
+corrected; n-step and lambda windows carry no traces.  A row whose log mu holds the bits the actor forms now has rho = 1
+exactly, so an on-policy batch at R >= 1 trains with the unweighted update's bits; an unknown log mu (NaN) refuses the
+update on the device.  log_probs(states, actions) is the actor alone (uavtrack_learner_log_probs).
+
 The critic alone (values(states), uavtrack_learner_values): V(s) of any number of rows with the parameters as they stand
 when the launch runs, bit for bit the V(s) an update forms.  A lambda ring (ring.with_lambda(lam, gamma)) takes it as
 add_rollout(..., critic=learner) to fold a rollout's rewards with its values into lambda-returns.
@@ -208,6 +218,77 @@ class DeviceActorCritic(Handle):
                        "uavtrack_learner_values")
         return out
 
+    # ---- the actor alone, and the truncated importance ratios of a batch
+    def _rows_arg(self, what: str, states: torch.Tensor, actions: torch.Tensor) -> int:
+        """The row count of states [..., 12] float32 and actions [...] int32, both contiguous on the learner's device."""
+        D = _lib.OBS_DIM
+        if states.dim() < 1 or states.shape[-1] != D or states.dtype != torch.float32 or not states.is_contiguous() \
+                or states.device != self.device:
+            raise ValueError(f"{what}: states must be a contiguous float32 tensor [..., {D}] on {self.device}, got "
+                             f"{tuple(states.shape)} {states.dtype} on {states.device}")
+        n = states.numel() // D
+        _lib.tensor_arg(actions, torch.int32, n, self.device,
+                        f"{what}: actions must be a contiguous int32 tensor of {n} elements on {self.device}")
+        return n
+
+    def log_probs(self, states: torch.Tensor, actions: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """log pi(a | s) of states [..., 12] (float32) and actions [...] (int32), both contiguous on the learner's
+        device, with the actor's parameters as they stand when the launch runs (uavtrack_learner_log_probs): a float32
+        tensor of the leading shape, NaN where an action lies outside [0, action_dim).  The bits of a row do not depend
+        on how many rows travel with it.  `out` (float32, contiguous, that many elements, same device) is written in
+        place and returned.  No synchronisation, no limit from max_batch, no change to the learner."""
+        n = self._rows_arg("log_probs", states, actions)
+        if out is None:
+            out = torch.empty(tuple(states.shape[:-1]), dtype=torch.float32, device=self.device)
+        _lib.tensor_arg(out, torch.float32, n, self.device,
+                        f"log_probs: out must be a contiguous float32 tensor of {n} elements on {self.device}")
+        if n:
+            _lib.check(self._lib.uavtrack_learner_log_probs(self._h, n, _ptr(states), _ptr(actions), n, None, _ptr(out),
+                                                            self._stream()), "uavtrack_learner_log_probs")
+        return out
+
+    def log_probs_window(self, states: torch.Tensor, actions: torch.Tensor, first: int, n: int,
+                         log_mu: torch.Tensor) -> None:
+        """log pi(actions[slot] | states[slot]) into log_mu[slot] for the n slots (first + k) % capacity of a ring's
+        stores (uavtrack_learner_log_probs_window): what a behaviour ring runs behind an add."""
+        capacity = self._rows_arg("log_probs_window", states, actions)
+        _lib.tensor_arg(log_mu, torch.float32, capacity, self.device,
+                        f"log_probs_window: log_mu must be a contiguous float32 tensor of {capacity} elements on {self.device}")
+        _lib.check(self._lib.uavtrack_learner_log_probs_window(self._h, _ptr(states), _ptr(actions), capacity, int(first),
+                                                               int(n), _ptr(log_mu), self._stream()),
+                   "uavtrack_learner_log_probs_window")
+
+    def _ratio_weights(self, n: int, store: Dict[str, torch.Tensor], log_mu: torch.Tensor, capacity: int,
+                       idx: Optional[torch.Tensor], rho_bar: float, w_in: Optional[torch.Tensor], w_out: torch.Tensor,
+                       rho_out: Optional[torch.Tensor]) -> torch.Tensor:
+        """uavtrack_learner_ratio_weights: w_out[i] = (w_in[i] or 1) * min(rho_bar, pi / mu of batch row i)."""
+        _lib.tensor_arg(log_mu, torch.float32, capacity, self.device,
+                        f"log_mu must be a contiguous float32 tensor of {capacity} elements (one per slot of the store) on "
+                        f"{self.device}")
+        _lib.tensor_arg(rho_out, torch.float32, n, self.device,
+                        f"rho_out must be a contiguous float32 tensor of {n} elements (one per batch row) on {self.device}")
+        _lib.check(self._lib.uavtrack_learner_ratio_weights(
+            self._h, n, _ptr(store["states"]), _ptr(store["actions"]), _ptr(log_mu), capacity, _ptr(idx), float(rho_bar),
+            _ptr(w_in), _ptr(w_out), _ptr(rho_out), self._stream()), "uavtrack_learner_ratio_weights")
+        return w_out
+
+    def _ratios_from(self, buffer, k: int, idx: Optional[torch.Tensor], w: Optional[torch.Tensor],
+                     rho_bar: Optional[float], rho_out: Optional[torch.Tensor]) -> Optional[torch.Tensor]:
+        """The weights a draw of k rows trains with: w as drawn when rho_bar is None, else w (or 1) times the truncated
+        ratios of the buffer's behaviour store, in the ring's own weight buffer (a prioritised ring's importance weights
+        are multiplied in place)."""
+        if rho_bar is None:
+            if rho_out is not None:
+                raise ValueError("rho_out needs rho_bar")
+            return w
+        log_mu = getattr(buffer, "log_mu", None)
+        if log_mu is None:
+            raise ValueError("rho_bar needs the buffer's behaviour log-probabilities: a ReplayRing or PrioritizedReplayRing "
+                             "made ring.with_behaviour()")
+        own = getattr(buffer, "_w", None)
+        w_out = (buffer._rho_w if own is None else own)[:k]
+        return self._ratio_weights(k, buffer.store, log_mu, buffer.capacity, idx, rho_bar, w, w_out, rho_out)
+
     # ---- the update
     @staticmethod
     def _batch_args(store: Dict[str, torch.Tensor], capacity: int, idx: Optional[torch.Tensor]):
@@ -273,13 +354,19 @@ class DeviceActorCritic(Handle):
         return losses[0], losses[1], td
 
     def update(self, transition_dict: Dict[str, torch.Tensor], weights: Optional[torch.Tensor] = None,
-               discounts: Optional[torch.Tensor] = None):
+               discounts: Optional[torch.Tensor] = None, log_mu: Optional[torch.Tensor] = None,
+               rho_bar: Optional[float] = None):
         """ActorCritic.update (actor_critic.py:150-179) on a batch {states [n,12], actions [n], rewards [n],
         next_states [n,12]}: returns (actor_loss, critic_loss, td_delta) as device tensors, without synchronising.
         weights [n] (optional): importance weights w_i >= 0, one per row (the module docstring has the weighted losses);
         None is the reference's unweighted update, and a vector of ones gives its bits.
         discounts [n] (optional): d_i in [0, 1] of row i, in batch order (row i is slot i here): the target becomes
-        r_i + d_i V(s'_i); None is gamma for every row, and a vector of float32(gamma) gives its bits."""
+        r_i + d_i V(s'_i); None is gamma for every row, and a vector of float32(gamma) gives its bits.
+        log_mu [n] with rho_bar > 0 (both or neither): the behaviour log-probability of each row's action; the row's
+        weight becomes w_i min(rho_bar, pi / mu) (uavtrack_learner_ratio_weights, then the weighted update); a NaN or
+        positive log_mu refuses the update on the device."""
+        if (log_mu is None) != (rho_bar is None):
+            raise ValueError("update: log_mu and rho_bar come together")
         dev = self.device
         s = torch.as_tensor(transition_dict["states"], device=dev, dtype=torch.float32).reshape(-1, _lib.OBS_DIM).contiguous()
         n = s.shape[0]
@@ -292,11 +379,15 @@ class DeviceActorCritic(Handle):
             weights = torch.as_tensor(weights, device=dev, dtype=torch.float32).reshape(-1).contiguous()
         if discounts is not None:
             discounts = torch.as_tensor(discounts, device=dev, dtype=torch.float32).reshape(-1).contiguous()
+        if rho_bar is not None:
+            log_mu = torch.as_tensor(log_mu, device=dev, dtype=torch.float32).reshape(-1).contiguous()
+            weights = self._ratio_weights(n, store, log_mu, n, None, rho_bar, weights, torch.empty(n, device=dev), None)
         return self._run(n, store, n, None, None, weights, discounts)
 
     def update_from(self, buffer, batch_size: int, beta: float = 0.4,
                     generator: Optional[torch.Generator] = None, group=None, importance: bool = False,
-                    beta_final: Optional[float] = None, anneal_calls: int = 0):
+                    beta_final: Optional[float] = None, anneal_calls: int = 0, rho_bar: Optional[float] = None,
+                    rho_out: Optional[torch.Tensor] = None):
         """buffer.sample(batch_size) + update + (prioritised buffer) update_priorities(indices, |td_delta|)
         (train.py:253-262), the gather and the priority write inside the library call.  The indices are drawn as
         the buffer's own sample() draws them.  For a ReplayRing or a PrioritizedReplayRing the draw is one library call
@@ -320,13 +411,25 @@ class DeviceActorCritic(Handle):
         (sharding.gather_learner_rows), the apply of all of them, and the priority write into this rank's buffer.
         Ranks that start equal (sharding.broadcast_learner) stay bitwise equal; batch sizes may differ between ranks.
         The returned losses are the global ones, td_delta this rank's.  With importance=True every rank's weights are
-        normalised by its own draw's maximum, as independent sample() calls would do."""
+        normalised by its own draw's maximum, as independent sample() calls would do.
+
+        rho_bar > 0 (a ring made with_behaviour(); any other buffer raises) corrects for who acted: between the draw and
+        the update, uavtrack_learner_ratio_weights forms rho_i = min(rho_bar, pi(a_i|s_i) / mu(a_i|s_i)) from the ring's
+        log_mu store and the actor as it stands, and the update trains on w_i rho_i (w_i the importance weight, or 1;
+        no second normalisation) through the weighted or discounted entry point: three library calls with no torch
+        kernel between them, capturable.  rho_out (float32 [k], optional) receives the ratios.  rho_bar = inf does not
+        truncate.  A drawn slot whose log_mu is NaN (unknown) or positive refuses the update on the device.  td_delta and
+        the priorities stay the unweighted delta and |delta|.  On an n-step or lambda ring the ratio corrects the first
+        action only.  Participants of one update (ranks, shards) must pass equal rho_bar.  None (the default) enqueues
+        exactly what was enqueued without it."""
         if group is not None:
-            return self._update_from_group(buffer, batch_size, generator, group, importance, beta, beta_final, anneal_calls)
+            return self._update_from_group(buffer, batch_size, generator, group, importance, beta, beta_final, anneal_calls,
+                                           rho_bar, rho_out)
         k = min(int(batch_size), buffer.count)
         if k < 1:
             raise ValueError("update_from: the buffer is empty")
         idx, prio, w = self._draw_from(buffer, k, generator, importance, beta, beta_final, anneal_calls)
+        w = self._ratios_from(buffer, k, idx, w, rho_bar, rho_out)
         return self._run(k, buffer.store, buffer.capacity, idx, prio, w, self._discounts_of(buffer))
 
     # ---- the split update: gradient rows and an ordered apply
@@ -351,17 +454,20 @@ class DeviceActorCritic(Handle):
 
     def grad_from(self, buffer, batch_size: int, row: Optional[torch.Tensor] = None,
                   generator: Optional[torch.Generator] = None, importance: bool = False, beta: float = 0.4,
-                  beta_final: Optional[float] = None, anneal_calls: int = 0):
+                  beta_final: Optional[float] = None, anneal_calls: int = 0, rho_bar: Optional[float] = None,
+                  rho_out: Optional[torch.Tensor] = None):
         """The gradient half of update_from: draws min(batch_size, buffer.count) rows as update_from does (for a
         ReplayRing or PrioritizedReplayRing the ring's own library call) and leaves their unscaled gradient and loss sums
         in `row` (a new tensor if None).  Returns (row, td_delta, indices); changes nothing in the learner.  The indices
         of either ring live in the ring's own draw tensor until its next draw: call write_priorities (or clone
         them) before drawing from the same ring again.  importance, beta, beta_final, anneal_calls: as update_from; the
-        row's sums then carry this draw's weights, normalised by this draw's own maximum."""
+        row's sums then carry this draw's weights, normalised by this draw's own maximum.  rho_bar, rho_out: as
+        update_from; the row's sums then carry w_i rho_i."""
         k = min(int(batch_size), buffer.count)
         if k < 1:
             raise ValueError("grad_from: the buffer is empty")
         idx, _, w = self._draw_from(buffer, k, generator, importance, beta, beta_final, anneal_calls)
+        w = self._ratios_from(buffer, k, idx, w, rho_bar, rho_out)
         row, td = self._grad(k, buffer.store, buffer.capacity, idx, row, None, w, self._discounts_of(buffer))
         return row, td, idx
 
@@ -393,18 +499,23 @@ class DeviceActorCritic(Handle):
 
     def update_from_many(self, buffers, batch_size: int, generator: Optional[torch.Generator] = None,
                          importance: bool = False, beta: float = 0.4, beta_final: Optional[float] = None,
-                         anneal_calls: int = 0):
+                         anneal_calls: int = 0, rho_bar: Optional[float] = None, rho_out=None):
         """ONE update from several buffers on this device (the shards of one GPU): one gradient row per buffer from
         min(batch_size, its count) of its rows, the rows applied in list order, each prioritised buffer's priorities
         written back from its own draw.  Returns (actor_loss, critic_loss, [td_delta per buffer]).  With
         importance=True each buffer's row carries its own draw's importance weights, normalised by that draw's own
         maximum (not a maximum across the buffers), as independent sample() calls would do; every ring anneals over
-        its own call counter."""
+        its own call counter.  rho_bar: as update_from, every buffer a behaviour ring; rho_out: a sequence of one
+        float32 [k] tensor (or None) per buffer."""
         buffers = list(buffers)
         if not 1 <= len(buffers) <= _lib.LEARNER_MAX_ROWS:
             raise ValueError(f"update_from_many: {len(buffers)} buffers, one apply takes 1 to {_lib.LEARNER_MAX_ROWS} rows")
         rows = self.new_rows(len(buffers))
-        drawn = [self.grad_from(b, batch_size, rows[k], generator, importance, beta, beta_final, anneal_calls)
+        rho_outs = [None] * len(buffers) if rho_out is None else list(rho_out)
+        if len(rho_outs) != len(buffers):
+            raise ValueError(f"update_from_many: rho_out holds {len(rho_outs)} entries for {len(buffers)} buffers")
+        drawn = [self.grad_from(b, batch_size, rows[k], generator, importance, beta, beta_final, anneal_calls, rho_bar,
+                                rho_outs[k])
                  for k, b in enumerate(buffers)]
         al, cl = self.apply(rows)
         for b, (_, td, idx) in zip(buffers, drawn):
@@ -412,9 +523,11 @@ class DeviceActorCritic(Handle):
         return al, cl, [td for _, td, _ in drawn]
 
     def _update_from_group(self, buffer, batch_size: int, generator, group, importance: bool = False,
-                           beta: float = 0.4, beta_final: Optional[float] = None, anneal_calls: int = 0):
+                           beta: float = 0.4, beta_final: Optional[float] = None, anneal_calls: int = 0,
+                           rho_bar: Optional[float] = None, rho_out: Optional[torch.Tensor] = None):
         from .sharding import gather_learner_rows
-        row, td, idx = self.grad_from(buffer, batch_size, None, generator, importance, beta, beta_final, anneal_calls)
+        row, td, idx = self.grad_from(buffer, batch_size, None, generator, importance, beta, beta_final, anneal_calls,
+                                      rho_bar, rho_out)
         al, cl = self.apply(gather_learner_rows(row, group))
         self.write_priorities(buffer, idx, td)
         return al, cl, td

@@ -31,6 +31,17 @@ target r + discount * V(s') is the lambda-return: its tail evaluated by the crit
 by the critic at update time.  Windows never cross an episode end and are cut at the rollout's last step, where the
 transition is the plain one-step one; lam = 0 is with_nstep(1, gamma) to the byte.  Slots keep the tail they were added
 with.
+
+Behaviour log-probabilities.  ring.with_behaviour() gives either ring (n-step and lambda rings included) a sixth per-slot
+store, `log_mu`: log mu(action[slot] | state[slot]) of the policy that acted, NaN where it is not known.
+add_rollout_behaviour(obs_in, out, behaviour=learner) is add_rollout followed, on the same stream, by the learner's actor
+over the ring window the add has just written (uavtrack_learner_log_probs_window: it reads the ring's own states and
+actions, so one path serves every add form and no add kernel changes).  That is right when the learner's actor at add
+time is the one that acted: add before the iteration's updates.  The rollout's actor runs on the f16 matrix cores "at
+fp32 accuracy", so mu is the acting distribution to that accuracy, not to the bit.  DeviceActorCritic.update_from(ring,
+k, rho_bar=R) turns the store into truncated importance ratios min(R, pi / mu), one weight per batch row; they correct
+the first action of a transition only (on an n-step or lambda ring the rest of the window stays uncorrected).  Without
+with_behaviour a ring is exactly what it was.
 """
 from __future__ import annotations
 
@@ -57,6 +68,8 @@ class ReplayRing(Handle):
     gamma: Optional[float] = None
     lam: Optional[float] = None                 # with_lambda: the ring stores lambda-returns
     _values: Optional[torch.Tensor] = None      # add_rollout(critic=...)'s buffer, kept and only grown
+    log_mu: Optional[torch.Tensor] = None       # with_behaviour: per-slot behaviour log-probabilities
+    _rho_w: Optional[torch.Tensor] = None       # with_behaviour: update_from's ratio weights (a prioritised ring: its _w)
 
     def __init__(self, capacity: int, device, seed: int = 0, max_batch: int = 65536, obs_dim: int = _lib.OBS_DIM):
         if obs_dim != _lib.OBS_DIM:
@@ -112,6 +125,26 @@ class ReplayRing(Handle):
         self.discounts = torch.full((self.capacity,), gamma, dtype=torch.float32, device=self.device)
         return self
 
+    def with_behaviour(self) -> "ReplayRing":
+        """Gives this ring the behaviour store and returns it: ReplayRing(capacity, device).with_lambda(0.9, 0.95)
+        .with_behaviour().  The ring then owns `log_mu` [capacity] float32, every slot NaN ("unknown") to begin with, and
+        a [max_batch] float32 buffer for the ratio weights of update_from(..., rho_bar=) (a prioritised ring multiplies
+        into its importance-weight buffer instead); add_rollout_behaviour and add fill the store, sample() returns it.
+        Composes with with_nstep and with_lambda in either order."""
+        if self.log_mu is None:
+            self.log_mu = torch.full((self.capacity,), float("nan"), dtype=torch.float32, device=self.device)
+            if getattr(self, "_w", None) is None:          # a prioritised ring's own importance-weight buffer serves
+                self._rho_w = torch.empty(self.max_batch, dtype=torch.float32, device=self.device)
+        return self
+
+    def _copy_last(self, dst: torch.Tensor, src: torch.Tensor, n: int) -> None:
+        """The last min(n, capacity) of src's n elements into dst's slots from pos on, as an add of n rows places them."""
+        k = min(n, self.capacity)
+        start = (self.pos + n - k) % self.capacity
+        head = min(k, self.capacity - start)
+        dst[start:start + head] = src[n - k:n - k + head]
+        dst[:k - head] = src[n - k + head:]
+
     def _rollout_values(self, obs: torch.Tensor, critic, values: Optional[torch.Tensor]) -> torch.Tensor:
         """The lambda add's values [T*B*N]: the caller's, or the critic's over obs into the ring's own buffer."""
         n = obs.numel() // _lib.OBS_DIM
@@ -156,7 +189,8 @@ class ReplayRing(Handle):
         """transition_dict: states [n,12], actions [n], rewards [n], next_states [n,12] (any leading shape is
         flattened).  One library call writes the last min(n, capacity) of them (a prioritised ring: at the current
         maximum priority).  A ring with discounts then fills the same slots' discounts from an optional "discounts"
-        entry [n], or with float32(gamma) where it is absent (a torch slice copy: the flat add is not the hot path)."""
+        entry [n], or with float32(gamma) where it is absent (a torch slice copy: the flat add is not the hot path).  A
+        behaviour ring fills their log_mu likewise from an optional "log_mu" entry [n], or with NaN ("unknown")."""
         n = transition_dict["actions"].numel()
         if n < 1:
             return
@@ -172,11 +206,12 @@ class ReplayRing(Handle):
             d = transition_dict.get("discounts")
             d = torch.full((n,), self.gamma, dtype=torch.float32, device=dev) if d is None \
                 else d.to(dev, torch.float32).reshape(n)
-            k = min(n, self.capacity)
-            start = (self.pos + n - k) % self.capacity
-            head = min(k, self.capacity - start)
-            self.discounts[start:start + head] = d[n - k:n - k + head]
-            self.discounts[:k - head] = d[n - k + head:]
+            self._copy_last(self.discounts, d, n)
+        if self.log_mu is not None:
+            m = transition_dict.get("log_mu")
+            m = torch.full((n,), float("nan"), dtype=torch.float32, device=dev) if m is None \
+                else m.to(dev, torch.float32).reshape(n)
+            self._copy_last(self.log_mu, m, n)
         self._advance(n)
 
     def add_rollout(self, obs_in: torch.Tensor, out: Dict[str, torch.Tensor], *, critic=None,
@@ -190,7 +225,32 @@ class ReplayRing(Handle):
         (uavtrack_replay_add_rollout_lambda) and needs exactly one of `values` (float32, contiguous, T*B*N elements:
         V(obs[t][b][i])) and `critic` (an object with .values(states, out=), a DeviceActorCritic, or a torch module such
         as ValueMLP, called under no_grad on obs.reshape(-1, 12)); the critic's values go into a buffer the ring keeps
-        and only grows.  Any other ring given either raises."""
+        and only grows.  Any other ring given either raises.  A behaviour ring (with_behaviour) is added to through
+        add_rollout_behaviour, which says who acted; this call refuses it."""
+        self._add_rollout(obs_in, out, critic, values, None, None)
+
+    def add_rollout_behaviour(self, obs_in: torch.Tensor, out: Dict[str, torch.Tensor], *, behaviour=None,
+                              log_mu: Optional[torch.Tensor] = None, critic=None,
+                              values: Optional[torch.Tensor] = None) -> None:
+        """add_rollout on a behaviour ring (with_behaviour; any other ring raises): the same add, then the behaviour
+        log-probabilities of the slots it wrote, from exactly one of
+          behaviour=  a DeviceActorCritic (an object with .log_probs_window): after the add's own library call, on the
+                      same stream, its actor over the window the add has just written -- the last min(T*B*N, capacity)
+                      rows (uavtrack_learner_log_probs_window; the hot path: no torch kernel, capturable).  Right when
+                      that actor is the one that acted: add before the iteration's updates.  Or a torch module that
+                      returns action probabilities, such as ActorMLP: called under no_grad on the window's states, the
+                      logarithm of the taken action's probability gathered in torch (not the hot path);
+          log_mu=     float32, contiguous, T*B*N elements in add order, on the ring's device: slice-copied as add copies
+                      discounts.
+        critic=, values=: as add_rollout."""
+        if self.log_mu is None:
+            raise ValueError("add_rollout_behaviour: behaviour= and log_mu= are for a behaviour ring (ring.with_behaviour())")
+        self._add_rollout(obs_in, out, critic, values, behaviour, log_mu)
+
+    def _add_rollout(self, obs_in, out, critic, values, behaviour, log_mu) -> None:
+        if self.log_mu is not None and (behaviour is None) == (log_mu is None):
+            raise ValueError("add_rollout: a behaviour ring needs exactly one of behaviour= and log_mu= "
+                             "(add_rollout_behaviour)")
         if self.lam is None and (critic is not None or values is not None):
             raise ValueError("add_rollout: critic= and values= are for a lambda ring (ring.with_lambda(lam, gamma))")
         obs, act, rew = out["obs"], out["actions"], out["reward"]
@@ -228,9 +288,30 @@ class ReplayRing(Handle):
             name, args = "uavtrack_replay_add_rollout_episodes", (T, obs.shape[1], obs.shape[2], *source, *episode_ends)
         else:
             name, args = "uavtrack_replay_add_rollout", (T, M, *source)
+        n = T * M
+        if log_mu is not None:
+            _lib.tensor_arg(log_mu, torch.float32, n, self.device,
+                            f"add_rollout: log_mu must be a contiguous float32 tensor of {n} elements (one per row of "
+                            f"obs, in add order) on {self.device}")
         ring = self._ring()
         _lib.check(getattr(self._lib, name)(self._h, C.byref(ring), *args, self._stream()), name)
-        self._advance(T * M)
+        if log_mu is not None:
+            self._copy_last(self.log_mu, log_mu.reshape(n), n)
+        elif behaviour is not None:
+            k = min(n, self.capacity)
+            self._window_log_mu(behaviour, (self.pos + n - k) % self.capacity, k)
+        self._advance(n)
+
+    def _window_log_mu(self, behaviour, first: int, k: int) -> None:
+        """log_mu of the k slots from `first` on (wrapping) from the ring's own states and actions."""
+        if not isinstance(behaviour, torch.nn.Module):
+            behaviour.log_probs_window(self.store["states"], self.store["actions"], first, k, self.log_mu)
+            return
+        slots = (first + torch.arange(k, device=self.device)) % self.capacity
+        with torch.no_grad():
+            p = behaviour(self.store["states"][slots])
+            a = self.store["actions"][slots].to(torch.int64).unsqueeze(1)
+            self.log_mu[slots] = torch.log(p.gather(1, a).squeeze(1)).clamp_(max=0.0).to(torch.float32)
 
     def _on_ring(self, *tensors) -> None:
         for t in tensors:
@@ -266,10 +347,12 @@ class ReplayRing(Handle):
         return self._gather(self.draw(batch_size))
 
     def _gather(self, idx) -> Dict[str, torch.Tensor]:
-        """The transitions dict at idx: KEYS, and "discounts" on a ring that has them."""
+        """The transitions dict at idx: KEYS, "discounts" on a ring that has them and "log_mu" on a behaviour ring."""
         out = {key: self.store[key][idx] for key in KEYS}
         if self.discounts is not None:
             out["discounts"] = self.discounts[idx]
+        if self.log_mu is not None:
+            out["log_mu"] = self.log_mu[idx]
         return out
 
 

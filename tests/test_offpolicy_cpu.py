@@ -1,0 +1,231 @@
+"""Off-policy correction without a GPU: the weighted update with w = rho IS the truncated-importance-sampling actor and
+the rho-weighted TD(0) critic (torch autograd in float64 against tests/learner_weighted_mirror.py), the ratio's special
+values, the window an add writes, the three new symbols declared in include/uavtrack.h, exported by the library and
+bound in uavtrack/_lib.py with the header's argument lists, and the Python surface."""
+import ctypes as C
+import inspect
+import os
+import re
+
+import numpy as np
+import pytest
+import torch
+
+import learner_dp_mirror as dp
+import learner_weighted_mirror as wm
+import offpolicy_mirror as om
+import uavtrack
+from uavtrack import _lib
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CSRC = os.path.join(ROOT, "marl-uavs-targets-tracking_amd", "csrc")
+GAMMA = 0.95
+
+
+def _case(H, A, n):
+    rng = np.random.RandomState(100 * H + n)
+    blob = dp.init_blob(H, A, H + n).astype(np.float64)
+    blob[13 * H:13 * H + A * H] *= 5                                        # a policy with opinions
+    s, a, r, s2 = dp.batch(rng, n, A)
+    lp = om.log_probs(blob, H, A, s, a)
+    log_mu = np.minimum(lp + rng.uniform(-1.5, 1.5, size=n), 0.0)          # stale behaviour: ratios on both sides of 1
+    return blob, (s, a, r, s2), log_mu
+
+
+@pytest.mark.parametrize("H,A,n", [(33, 12, 65), (1, 9, 2)])
+def test_the_weighted_update_with_rho_is_the_truncated_is_actor_and_the_rho_weighted_critic(H, A, n):
+    blob, (s, a, r, s2), log_mu = _case(H, A, n)
+    w, rho = om.weights(blob, H, A, s, a, log_mu, 2.0)
+    assert (rho == 2.0).any() or n < 10
+    assert (w == rho).all() and (rho > 0).all()
+    _, _, _, want = wm.losses_and_grads(blob, H, A, s, a, r, s2, GAMMA, "per_sample", weights=rho)
+
+    p = torch.tensor(blob, dtype=torch.float64, requires_grad=True)
+    o = np.cumsum([0, 12 * H, H, A * H, A, 12 * H, H, H, 1])
+    w1a, b1a, w2a, b2a = p[o[0]:o[1]].view(H, 12), p[o[1]:o[2]], p[o[2]:o[3]].view(A, H), p[o[3]:o[4]]
+    w1c, b1c, w2c, b2c = p[o[4]:o[5]].view(H, 12), p[o[5]:o[6]], p[o[6]:o[7]].view(1, H), p[o[7]:o[8]]
+    ts, ts2, tr = (torch.tensor(np.asarray(x, np.float64)) for x in (s, s2, r))
+    ta = torch.tensor(np.asarray(a, np.int64))
+
+    def critic(x):
+        return (torch.relu(x @ w1c.T + b1c) @ w2c.T + b2c).squeeze(1)
+
+    logp = torch.log_softmax(torch.relu(ts @ w1a.T + b1a) @ w2a.T + b2a, dim=1).gather(1, ta[:, None]).squeeze(1)
+    v = critic(ts)
+    y = (tr + GAMMA * critic(ts2)).detach()
+    delta = (y - v).detach()
+    trho = torch.exp(logp - torch.tensor(log_mu)).clamp(max=2.0).detach()
+    np.testing.assert_allclose(trho.numpy(), rho, rtol=1e-12)
+    actor_loss = torch.mean(-trho * logp * delta)
+    critic_loss = torch.mean(trho * (v - y) ** 2)
+    (actor_loss + critic_loss).backward()              # the two losses share no parameter
+    got = p.grad.numpy()
+    err = np.abs(got - want).max() / np.abs(want).max()
+    print(f"H = {H}, A = {A}, n = {n}: autograd against the weighted mirror at weights = rho, relative {err:.2e}")
+    assert err <= 1e-10
+
+
+def test_the_ratios_special_values():
+    H, A, n = 33, 12, 65
+    blob, (s, a, _, _), _ = _case(H, A, n)
+    lp = om.log_probs(blob, H, A, s, a)
+    assert np.isfinite(lp).all() and (lp <= 0).all()
+    for rho_bar in (1.0, 2.5, np.inf):
+        w, rho = om.weights(blob, H, A, s, a, lp, rho_bar)
+        assert (rho == 1.0).all() and (w == 1.0).all()                     # on-policy: rho = 1 for every rho_bar >= 1
+    for rho_bar in (1.0, 2.5):
+        w, rho = om.weights(blob, H, A, s, a, np.full(n, -80.0), rho_bar)
+        assert (rho == np.float32(rho_bar)).all()
+    w_in = np.linspace(0, 1, n)
+    w, rho = om.weights(blob, H, A, s, a, np.full(n, -80.0), 2.5, w_in)
+    assert (w == w_in * 2.5).all()
+    bad = lp.copy()
+    bad[3], bad[7] = np.nan, 1e-3
+    w, rho = om.weights(blob, H, A, s, a, bad, 1.0)
+    assert np.isnan(rho[[3, 7]]).all() and np.isnan(w[[3, 7]]).all() and np.isfinite(np.delete(rho, [3, 7])).all()
+    a2 = np.array(a)
+    a2[0], a2[1] = -1, A
+    assert np.isnan(om.weights(blob, H, A, s, a2, lp, 1.0)[1][:2]).all()
+    _, rho = om.weights(blob, H, A, s, a, np.full(n, -2000.0), np.inf)      # the untruncated ratio overflows: +inf
+    assert np.isinf(rho).all()
+
+
+def test_window_slots():
+    slots, rows = om.window_slots(5, 4, 7)                                  # a wrap
+    assert slots.tolist() == [5, 6, 0, 1] and rows.tolist() == [0, 1, 2, 3]
+    slots, rows = om.window_slots(3, 7, 7)                                  # n == capacity
+    assert slots.tolist() == [3, 4, 5, 6, 0, 1, 2] and rows.tolist() == list(range(7))
+    slots, rows = om.window_slots(3, 17, 7)                                 # n > capacity: the last 7 rows are kept
+    assert rows.tolist() == list(range(10, 17)) and slots.tolist() == [(3 + r) % 7 for r in range(10, 17)]
+    assert sorted(slots.tolist()) == list(range(7))
+    # the ring's own arithmetic: first = (pos + n - k) % capacity, k = min(n, capacity)
+    for pos, n, cap in ((5, 4, 7), (3, 7, 7), (3, 17, 7), (0, 1, 1), (6, 60, 257)):
+        slots, _ = om.window_slots(pos, n, cap)
+        k = min(n, cap)
+        assert slots.tolist() == [((pos + n - k) % cap + j) % cap for j in range(k)]
+
+
+ARGS = {
+    "uavtrack_learner_log_probs": "learner n states actions capacity indices log_probs stream",
+    "uavtrack_learner_log_probs_window": "learner states actions capacity first n log_mu stream",
+    "uavtrack_learner_ratio_weights": "learner n states actions log_mu capacity indices rho_bar weights_in weights_out "
+                                      "rho_out stream",
+}
+CTYPE = {"uavtrack_learner *": C.c_void_p, "int64_t": C.c_int64, "double": C.c_double, "const int64_t *": C.c_void_p,
+         "const int32_t *": C.c_void_p, "const float *": C.c_void_p, "float *": C.c_void_p, "void *": C.c_void_p}
+
+
+@pytest.mark.parametrize("name", sorted(ARGS))
+def test_symbols_are_declared_exported_and_bound_with_the_headers_argument_lists(name):
+    hdr = open(os.path.join(ROOT, "include", "uavtrack.h")).read()
+    m = re.search(r"\bint\s+" + name + r"\s*\(([^;]*)\)\s*;", hdr)
+    assert m, f"{name} is not declared in include/uavtrack.h"
+    decl = [" ".join(a.split()) for a in m.group(1).split(",")]
+    names = [re.search(r"(\w+)$", a).group(1) for a in decl]
+    assert names == ARGS[name].split()
+    types = [a[:-len(n)].strip() for a, n in zip(decl, names)]
+    assert name in _lib.SIGNATURES, f"{name} is not bound in uavtrack/_lib.py"
+    res, args = _lib.SIGNATURES[name]
+    assert res is C.c_int and args == [CTYPE[t] for t in types]
+    assert hasattr(_lib.load(), name), f"{name} is not exported by the built library"
+    assert re.search(r"#define UAVTRACK_ABI_VERSION\s+1\b", hdr) and _lib.ABI_VERSION == 1
+
+
+class _Bare(uavtrack.ReplayRing):
+    """The host-side state of a ring without its device handle."""
+
+    def __init__(self, capacity=8):
+        self.capacity, self.device, self.max_batch, self.pos, self.count = capacity, torch.device("cpu"), 16, 0, 0
+
+
+class _BarePrioritized(uavtrack.PrioritizedReplayRing):
+    def __init__(self, capacity=8):
+        self.capacity, self.device, self.max_batch = capacity, torch.device("cpu"), 16
+        self._w = torch.empty(16)
+
+
+def test_with_behaviour_composes_with_nstep_and_lambda():
+    R = uavtrack.ReplayRing
+    assert R.log_mu is None and uavtrack.PrioritizedReplayRing.with_behaviour is R.with_behaviour
+    assert list(inspect.signature(R.with_behaviour).parameters) == ["self"]
+    for make in (lambda: _Bare().with_behaviour(), lambda: _Bare().with_nstep(3, 0.95).with_behaviour(),
+                 lambda: _Bare().with_behaviour().with_nstep(3, 0.95), lambda: _Bare().with_lambda(0.9, 0.95).with_behaviour(),
+                 lambda: _Bare().with_behaviour().with_lambda(0.9, 0.95)):
+        ring = make()
+        assert ring.log_mu.dtype == torch.float32 and ring.log_mu.shape == (8,) and torch.isnan(ring.log_mu).all()
+        assert ring._rho_w.shape == (16,) and ring._rho_w.dtype == torch.float32
+    ring = _Bare().with_lambda(0.9, 0.95).with_behaviour()
+    assert ring.lam == 0.9 and ring.discounts is not None
+    ring = _Bare().with_behaviour()
+    store = ring.log_mu
+    assert ring.with_behaviour() is ring and ring.log_mu is store           # a second call keeps the store
+    pr = _BarePrioritized().with_behaviour()
+    assert pr.log_mu is not None and pr._rho_w is None                      # its own importance-weight buffer serves
+    assert _Bare().log_mu is None and _Bare().with_nstep(3, 0.95).log_mu is None
+
+
+def _rollout(T=3, B=2, N=2):
+    rng = np.random.default_rng(5)
+    return (torch.from_numpy(rng.standard_normal((B, N, 12)).astype(np.float32)),
+            {"obs": torch.from_numpy(rng.standard_normal((T, B, N, 12)).astype(np.float32)),
+             "actions": torch.from_numpy(rng.integers(0, 12, (T, B, N)).astype(np.int32)),
+             "reward": torch.from_numpy(rng.standard_normal((T, B, N)).astype(np.float32))})
+
+
+def test_add_rollout_refuses_both_or_neither_of_behaviour_and_log_mu():
+    obs_in, out = _rollout()
+    lm = torch.zeros(12)
+    ring = _Bare().with_behaviour()
+    with pytest.raises(ValueError, match="exactly one of behaviour= and log_mu="):
+        ring.add_rollout(obs_in, out)                                       # neither: the plain add does not say who acted
+    with pytest.raises(ValueError, match="exactly one of behaviour= and log_mu="):
+        ring.add_rollout_behaviour(obs_in, out)
+    with pytest.raises(ValueError, match="exactly one of behaviour= and log_mu="):
+        ring.add_rollout_behaviour(obs_in, out, behaviour=object(), log_mu=lm)
+    for plain in (_Bare(), _Bare().with_nstep(3, 0.95), _Bare().with_lambda(0.9, 0.95)):
+        for kw in (dict(behaviour=object()), dict(log_mu=lm)):             # nothing is silently ignored
+            with pytest.raises(ValueError, match="behaviour ring"):
+                plain.add_rollout_behaviour(obs_in, out, **kw)
+    ring.store = {}
+    ring._ring = lambda: None
+    for bad in (lm.double(), lm[:-1], torch.zeros(24)[::2]):
+        with pytest.raises(ValueError, match="log_mu must be"):
+            ring.add_rollout_behaviour(obs_in, out, log_mu=bad)
+    assert torch.isnan(ring.log_mu).all() and ring.pos == 0
+    ps = inspect.signature(uavtrack.ReplayRing.add_rollout_behaviour).parameters
+    assert list(ps) == ["self", "obs_in", "out", "behaviour", "log_mu", "critic", "values"]
+    assert all(ps[k].kind is inspect.Parameter.KEYWORD_ONLY and ps[k].default is None for k in list(ps)[3:])
+
+
+def test_the_learners_surface_and_rho_bar_without_the_store():
+    L = uavtrack.DeviceActorCritic
+    assert list(inspect.signature(L.log_probs).parameters) == ["self", "states", "actions", "out"]
+    ps = inspect.signature(L.update).parameters
+    assert ps["log_mu"].default is None and ps["rho_bar"].default is None
+    for fn in (L.update_from, L.grad_from, L.update_from_many):
+        ps = inspect.signature(fn).parameters
+        assert ps["rho_bar"].default is None and ps["rho_out"].default is None
+    bare = object.__new__(L)                                                # the host-side check needs no handle
+    for ring in (_Bare(), _Bare().with_nstep(3, 0.95), object()):
+        with pytest.raises(ValueError, match="with_behaviour"):
+            bare._ratios_from(ring, 4, None, None, 1.0, None)
+    w = torch.ones(4)
+    assert bare._ratios_from(_Bare(), 4, None, w, None, None) is w          # rho_bar None: the draw's weights, untouched
+    assert bare._ratios_from(_Bare(), 4, None, None, None, None) is None
+    with pytest.raises(ValueError, match="rho_out needs rho_bar"):
+        bare._ratios_from(_Bare().with_behaviour(), 4, None, None, None, torch.empty(4))
+
+
+def _closure(path, seen):
+    for inc in re.findall(r'#include\s+"([^"]+)"', open(path).read()):
+        if inc not in seen:
+            seen.add(inc)
+            _closure(os.path.join(CSRC, inc), seen)
+    return seen
+
+
+def test_the_new_unit_reaches_the_learner_and_nothing_of_the_environment():
+    seen = _closure(os.path.join(CSRC, "learner_policy_kernel.hip"), set())
+    assert "learner.h" in seen and "learner_policy.h" in seen
+    assert not seen & {"env.h", "actor.h", "greedy.h", "pmi_pack.h", "api_env.h"}, seen
+    assert "learner_policy_kernel.hip" in open(os.path.join(CSRC, "Makefile")).read()
