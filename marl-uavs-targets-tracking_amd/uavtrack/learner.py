@@ -12,16 +12,17 @@ unscaled sums in a device gradient row, apply adds rows in row order, scales onc
 (several rings, one GPU) and update_from(..., group=...) (one ring per rank) are built on them; every participant that
 applies the same rows in the same order ends with the same bits, and one row is bit for bit `update`.
 
-Importance weights (update(weights=...), update_from(importance=True) and the same on grad_from, update_from_many and
-the group path) put a prioritised draw's importance-sampling weights w_i >= 0, one per batch row in batch order, into
-the losses:
+What update_from, grad_from, update_from_many and the group path draw and weigh a batch by (importance, beta, beta_final,
+anneal_calls, rho_bar, rho_out, generator) is one replay.DrawSpec, documented there; the losses they reach are these.
+
+Importance weights (update(weights=...), DrawSpec.importance) put a prioritised draw's importance-sampling weights
+w_i >= 0, one per batch row in batch order, into the losses:
     critic_loss                = mean_i(w_i (V(s_i) - y_i)^2)
     actor_loss, "per_sample"   = mean_i(-w_i log p_i delta_i)
     actor_loss, "reference"    = mean_i(-w_i log p_i) * mean_j(w_j delta_j)    (the pair (i, j) of the broadcast weighs w_i w_j)
-Means divide by n, not by sum w; td_delta and the priorities written back stay the unweighted delta and |delta|.  With
-several rings or ranks in one update, each row's weights are normalised by that draw's own maximum, as K independent
-sample() calls would do.  Without them (the default) every call is bit for bit what it was: the reference's update does
-not use the weights its sample() returns.
+Means divide by n, not by sum w; td_delta and the priorities written back stay the unweighted delta and |delta|.  Without
+them (the default) every call is bit for bit what it was: the reference's update does not use the weights its sample()
+returns.
 
 Regularisation (entropy_coef, max_grad_norm; both off by default, and then every call is bit for bit what it was):
     actor_loss, "per_sample"   = mean_i(w_i (-log p_i delta_i - c H_i)),  H_i = -sum_o p_io log p_io,  c = entropy_coef
@@ -41,15 +42,14 @@ _grad_discounted).  Everything behind the target is unchanged.  Without discount
 was, and a store of float32(gamma) gives the same bits; d_i = 0 means "do not bootstrap".  A discount that is NaN,
 negative or above 1 refuses the update on the device like a bad action.
 
-Off-policy correction (update(log_mu=, rho_bar=), update_from(ring, k, rho_bar=R) and the same on grad_from,
-update_from_many and the group path, on a ring made with_behaviour()): the truncated importance ratio
-rho_i = min(R, pi(a_i|s_i) / mu(a_i|s_i)) is one more weight per batch row, formed by uavtrack_learner_ratio_weights from
-the ring's per-slot log mu and the actor as it stands, and multiplied into the draw's importance weights (or 1).  With
-loss="per_sample" the losses above are then the truncated-importance-sampling policy gradient and the rho-weighted TD(0)
-critic, rho a constant of the differentiation: the one-step case of V-trace.  Only the first action of a transition is
-corrected; n-step and lambda windows carry no traces.  A row whose log mu holds the bits the actor forms now has rho = 1
-exactly, so an on-policy batch at R >= 1 trains with the unweighted update's bits; an unknown log mu (NaN) refuses the
-update on the device.  log_probs(states, actions) is the actor alone (uavtrack_learner_log_probs).
+Off-policy correction (update(log_mu=, rho_bar=), DrawSpec.rho_bar on a ring made with_behaviour()): the truncated
+importance ratio rho_i = min(R, pi(a_i|s_i) / mu(a_i|s_i)) is one more weight per batch row, formed by
+uavtrack_learner_ratio_weights from the ring's per-slot log mu and the actor as it stands, and multiplied into the draw's
+importance weights (or 1).  With loss="per_sample" the losses above are then the truncated-importance-sampling policy
+gradient and the rho-weighted TD(0) critic, rho a constant of the differentiation: the one-step case of V-trace; n-step and
+lambda windows carry no traces.  A row whose log mu holds the bits the actor forms now has rho = 1 exactly, so an on-policy
+batch at R >= 1 trains with the unweighted update's bits.  log_probs(states, actions) is the actor alone
+(uavtrack_learner_log_probs).
 
 The critic alone (values(states), uavtrack_learner_values): V(s) of any number of rows with the parameters as they stand
 when the launch runs, bit for bit the V(s) an update forms.  A lambda ring (ring.with_lambda(lam, gamma)) takes it as
@@ -59,7 +59,7 @@ from __future__ import annotations
 
 import ctypes as C
 import os
-from collections import OrderedDict
+from collections import OrderedDict, namedtuple
 from typing import Dict, Optional
 
 import numpy as np
@@ -70,9 +70,11 @@ from . import adam
 from ._handle import Handle, current_device
 from ._lib import host_ptr, ptr as _ptr
 from .adam import flat, from_state_dict, split, to_state_dict
-from .replay import DeviceReplayBuffer, PrioritizedDeviceReplayBuffer
-from .replay_ring import PrioritizedReplayRing, ReplayRing
+from .replay import DrawSpec
 from .rollout import ActorMLP
+
+
+_Drawn = namedtuple("_Drawn", "n store capacity idx priorities weights discounts")   # one drawn batch, as _run takes it
 
 
 def num_params(hidden_dim: int, action_dim: int) -> int:
@@ -196,40 +198,38 @@ class DeviceActorCritic(Handle):
         refused ring draw hands out), which then changed nothing."""
         self._check()
 
-    # ---- the critic alone
-    def values(self, states: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
-        """V(s) of states [..., 12] (float32, contiguous, on the learner's device) with the critic's parameters as they
-        stand when the launch runs (uavtrack_learner_values): a float32 tensor of the leading shape, bit for bit the V(s)
-        an update with the same parameters forms.  `out` (float32, contiguous, that many elements, same device) is
-        written in place and returned.  No synchronisation, no limit from max_batch, no change to the learner."""
-        D = _lib.OBS_DIM
-        if states.dim() < 1 or states.shape[-1] != D or states.dtype != torch.float32 or not states.is_contiguous() \
-                or states.device != self.device:
-            raise ValueError(f"values: states must be a contiguous float32 tensor [..., {D}] on {self.device}, got "
-                             f"{tuple(states.shape)} {states.dtype} on {states.device}")
-        lead = tuple(states.shape[:-1])
-        n = states.numel() // D
-        if out is None:
-            out = torch.empty(lead, dtype=torch.float32, device=self.device)
-        _lib.tensor_arg(out, torch.float32, n, self.device,
-                        f"values: out must be a contiguous float32 tensor of {n} elements on {self.device}")
-        if n:
-            _lib.check(self._lib.uavtrack_learner_values(self._h, n, _ptr(states), _ptr(out), self._stream()),
-                       "uavtrack_learner_values")
-        return out
-
-    # ---- the actor alone, and the truncated importance ratios of a batch
-    def _rows_arg(self, what: str, states: torch.Tensor, actions: torch.Tensor) -> int:
-        """The row count of states [..., 12] float32 and actions [...] int32, both contiguous on the learner's device."""
+    # ---- the critic alone, the actor alone, and the argument checks they share
+    def _rows_arg(self, what: str, states: torch.Tensor) -> int:
+        """The row count of states [..., 12]: float32, contiguous, on the learner's device."""
         D = _lib.OBS_DIM
         if states.dim() < 1 or states.shape[-1] != D or states.dtype != torch.float32 or not states.is_contiguous() \
                 or states.device != self.device:
             raise ValueError(f"{what}: states must be a contiguous float32 tensor [..., {D}] on {self.device}, got "
                              f"{tuple(states.shape)} {states.dtype} on {states.device}")
-        n = states.numel() // D
+        return states.numel() // D
+
+    def _actions_arg(self, what: str, actions: torch.Tensor, n: int) -> None:
         _lib.tensor_arg(actions, torch.int32, n, self.device,
                         f"{what}: actions must be a contiguous int32 tensor of {n} elements on {self.device}")
-        return n
+
+    def _out_arg(self, what: str, out: Optional[torch.Tensor], states: torch.Tensor, n: int) -> torch.Tensor:
+        """`out`, or a new float32 tensor of states' leading shape."""
+        if out is None:
+            out = torch.empty(tuple(states.shape[:-1]), dtype=torch.float32, device=self.device)
+        return _lib.tensor_arg(out, torch.float32, n, self.device,
+                               f"{what}: out must be a contiguous float32 tensor of {n} elements on {self.device}")
+
+    def values(self, states: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """V(s) of states [..., 12] (float32, contiguous, on the learner's device) with the critic's parameters as they
+        stand when the launch runs (uavtrack_learner_values): a float32 tensor of the leading shape, bit for bit the V(s)
+        an update with the same parameters forms.  `out` (float32, contiguous, that many elements, same device) is
+        written in place and returned.  No synchronisation, no limit from max_batch, no change to the learner."""
+        n = self._rows_arg("values", states)
+        out = self._out_arg("values", out, states, n)
+        if n:
+            _lib.check(self._lib.uavtrack_learner_values(self._h, n, _ptr(states), _ptr(out), self._stream()),
+                       "uavtrack_learner_values")
+        return out
 
     def log_probs(self, states: torch.Tensor, actions: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
         """log pi(a | s) of states [..., 12] (float32) and actions [...] (int32), both contiguous on the learner's
@@ -237,11 +237,9 @@ class DeviceActorCritic(Handle):
         tensor of the leading shape, NaN where an action lies outside [0, action_dim).  The bits of a row do not depend
         on how many rows travel with it.  `out` (float32, contiguous, that many elements, same device) is written in
         place and returned.  No synchronisation, no limit from max_batch, no change to the learner."""
-        n = self._rows_arg("log_probs", states, actions)
-        if out is None:
-            out = torch.empty(tuple(states.shape[:-1]), dtype=torch.float32, device=self.device)
-        _lib.tensor_arg(out, torch.float32, n, self.device,
-                        f"log_probs: out must be a contiguous float32 tensor of {n} elements on {self.device}")
+        n = self._rows_arg("log_probs", states)
+        self._actions_arg("log_probs", actions, n)
+        out = self._out_arg("log_probs", out, states, n)
         if n:
             _lib.check(self._lib.uavtrack_learner_log_probs(self._h, n, _ptr(states), _ptr(actions), n, None, _ptr(out),
                                                             self._stream()), "uavtrack_learner_log_probs")
@@ -251,7 +249,8 @@ class DeviceActorCritic(Handle):
                          log_mu: torch.Tensor) -> None:
         """log pi(actions[slot] | states[slot]) into log_mu[slot] for the n slots (first + k) % capacity of a ring's
         stores (uavtrack_learner_log_probs_window): what a behaviour ring runs behind an add."""
-        capacity = self._rows_arg("log_probs_window", states, actions)
+        capacity = self._rows_arg("log_probs_window", states)
+        self._actions_arg("log_probs_window", actions, capacity)
         _lib.tensor_arg(log_mu, torch.float32, capacity, self.device,
                         f"log_probs_window: log_mu must be a contiguous float32 tensor of {capacity} elements on {self.device}")
         _lib.check(self._lib.uavtrack_learner_log_probs_window(self._h, _ptr(states), _ptr(actions), capacity, int(first),
@@ -273,21 +272,19 @@ class DeviceActorCritic(Handle):
         return w_out
 
     def _ratios_from(self, buffer, k: int, idx: Optional[torch.Tensor], w: Optional[torch.Tensor],
-                     rho_bar: Optional[float], rho_out: Optional[torch.Tensor]) -> Optional[torch.Tensor]:
-        """The weights a draw of k rows trains with: w as drawn when rho_bar is None, else w (or 1) times the truncated
-        ratios of the buffer's behaviour store, in the ring's own weight buffer (a prioritised ring's importance weights
-        are multiplied in place)."""
-        if rho_bar is None:
-            if rho_out is not None:
+                     spec: DrawSpec) -> Optional[torch.Tensor]:
+        """The weights a draw of k rows trains with: w as drawn when spec.rho_bar is None, else w (or 1) times the
+        truncated ratios of the buffer's behaviour store, where the ring keeps them (_ratio_out)."""
+        if spec.rho_bar is None:
+            if spec.rho_out is not None:
                 raise ValueError("rho_out needs rho_bar")
             return w
-        log_mu = getattr(buffer, "log_mu", None)
+        log_mu = getattr(buffer, "log_mu", None)          # an object that is no buffer gets the same answer
         if log_mu is None:
             raise ValueError("rho_bar needs the buffer's behaviour log-probabilities: a ReplayRing or PrioritizedReplayRing "
                              "made ring.with_behaviour()")
-        own = getattr(buffer, "_w", None)
-        w_out = (buffer._rho_w if own is None else own)[:k]
-        return self._ratio_weights(k, buffer.store, log_mu, buffer.capacity, idx, rho_bar, w, w_out, rho_out)
+        return self._ratio_weights(k, buffer.store, log_mu, buffer.capacity, idx, spec.rho_bar, w, buffer._ratio_out(k),
+                                   spec.rho_out)
 
     # ---- the update
     @staticmethod
@@ -295,62 +292,42 @@ class DeviceActorCritic(Handle):
         """A batch as uavtrack_learner_update and _grad take it: the store's four arrays, its capacity, the indices."""
         return (*(_ptr(store[k]) for k in ("states", "actions", "rewards", "next_states")), capacity, _ptr(idx))
 
-    def _draw_from(self, buffer, k: int, generator: Optional[torch.Generator], importance: bool = False,
-                   beta: float = 0.4, beta_final: Optional[float] = None, anneal_calls: int = 0):
-        """(indices, priorities or None, importance weights or None) of one batch of k rows, drawn as the buffer's own
-        sample() draws them.  Weights only with `importance` and a prioritised buffer, normalised by this draw's maximum."""
-        if isinstance(buffer, PrioritizedReplayRing):
-            if importance:
-                idx, w = buffer._draw_into(k, True, beta, beta_final, anneal_calls)
-                return idx, buffer.priorities, w
-            return buffer._draw_into(k), buffer.priorities, None
-        if isinstance(buffer, ReplayRing):
-            return buffer._draw_into(k), None, None
-        if isinstance(buffer, PrioritizedDeviceReplayBuffer):
-            prob = buffer.priorities[:buffer.count] ** buffer.alpha
-            prob = prob / prob.sum()
-            idx = torch.multinomial(prob, k, replacement=True, generator=generator)
-            if not importance:
-                return idx, buffer.priorities, None
-            if beta_final is not None:
-                raise ValueError("beta_final anneals over a PrioritizedReplayRing's device call counter; a "
-                                 "PrioritizedDeviceReplayBuffer has none: pass this call's beta")
-            w = (buffer.count * prob[idx]) ** (-beta)                 # as its own sample() forms them
-            return idx, buffer.priorities, (w / w.max()).to(torch.float32).contiguous()
-        return torch.randperm(buffer.count, device=buffer.device, generator=generator)[:k], None, None
+    def _drawn_batch(self, buffer, batch_size: int, spec: DrawSpec, caller: str) -> _Drawn:
+        """min(batch_size, buffer.count) rows drawn as the buffer's own sample() draws them (_draw_batch), the weights
+        they train with, and the buffer's per-slot discounts, which must have been folded with this learner's gamma."""
+        k = min(int(batch_size), buffer.count)
+        if k < 1:
+            raise ValueError(f"{caller}: the buffer is empty")
+        idx, w = buffer._draw_batch(k, spec)
+        w = self._ratios_from(buffer, k, idx, w, spec)
+        d = buffer.discounts
+        if d is not None and np.float32(buffer.gamma) != np.float32(self.gamma):
+            raise ValueError(f"the buffer's returns were folded with gamma = {buffer.gamma}, the learner bootstraps with "
+                             f"gamma = {self.gamma}: both must be the same float32")
+        return _Drawn(k, buffer.store, buffer.capacity, idx, buffer.priorities, w, d)
 
-    def _form(self, n: int, weights: Optional[torch.Tensor], capacity: int, discounts: Optional[torch.Tensor]):
-        """(suffix, extra arguments) of the uavtrack_learner_update / _grad entry point a batch takes: plain, _weighted
-        (weights, one per batch row) or _discounted (weights or NULL, then discounts, one per slot of the store)."""
+    def _launch(self, kind: str, n: int, store: Dict[str, torch.Tensor], capacity: int, idx: Optional[torch.Tensor],
+                weights: Optional[torch.Tensor], discounts: Optional[torch.Tensor], *outputs) -> None:
+        """uavtrack_learner_<kind> ("update" or "grad") in the form the batch takes: plain, _weighted (weights, one per
+        batch row) or _discounted (weights or NULL, then discounts, one per slot of the store); then the outputs."""
         w = _lib.tensor_arg(weights, torch.float32, n, self.device,
                             f"weights must be a contiguous float32 tensor of {n} elements (one per batch row, in batch "
                             f"order) on {self.device}")
         d = _lib.tensor_arg(discounts, torch.float32, capacity, self.device,
                             f"discounts must be a contiguous float32 tensor of {capacity} elements (one per slot of the "
                             f"store) on {self.device}")
-        if d is not None:
-            return "_discounted", (_ptr(w), _ptr(d))
-        return ("", ()) if w is None else ("_weighted", (_ptr(w),))
-
-    def _discounts_of(self, buffer) -> Optional[torch.Tensor]:
-        """The buffer's per-slot discount store, or None; an n-step ring must have been folded with this learner's gamma."""
-        d = getattr(buffer, "discounts", None)
-        if d is not None and np.float32(buffer.gamma) != np.float32(self.gamma):
-            raise ValueError(f"the buffer's returns were folded with gamma = {buffer.gamma}, the learner bootstraps with "
-                             f"gamma = {self.gamma}: both must be the same float32")
-        return d
+        suffix, extra = ("_discounted", (_ptr(w), _ptr(d))) if d is not None else \
+            ("", ()) if w is None else ("_weighted", (_ptr(w),))
+        name = f"uavtrack_learner_{kind}{suffix}"
+        _lib.check(getattr(self._lib, name)(self._h, n, *self._batch_args(store, capacity, idx), *extra,
+                                            *map(_ptr, outputs), self._stream()), name)
 
     def _run(self, n: int, store: Dict[str, torch.Tensor], capacity: int, idx: Optional[torch.Tensor],
              priorities: Optional[torch.Tensor], weights: Optional[torch.Tensor] = None,
              discounts: Optional[torch.Tensor] = None):
-        dev = self.device
-        losses = torch.empty(2, device=dev)
-        td = torch.empty(n, device=dev)
-        suffix, extra = self._form(n, weights, capacity, discounts)
-        name = "uavtrack_learner_update" + suffix
-        _lib.check(getattr(self._lib, name)(
-            self._h, n, *self._batch_args(store, capacity, idx), *extra, _ptr(losses[0:1]), _ptr(losses[1:2]), _ptr(td),
-            _ptr(priorities), self._stream()), name)
+        losses = torch.empty(2, device=self.device)
+        td = torch.empty(n, device=self.device)
+        self._launch("update", n, store, capacity, idx, weights, discounts, losses[0:1], losses[1:2], td, priorities)
         return losses[0], losses[1], td
 
     def update(self, transition_dict: Dict[str, torch.Tensor], weights: Optional[torch.Tensor] = None,
@@ -391,17 +368,9 @@ class DeviceActorCritic(Handle):
         """buffer.sample(batch_size) + update + (prioritised buffer) update_priorities(indices, |td_delta|)
         (train.py:253-262), the gather and the priority write inside the library call.  The indices are drawn as
         the buffer's own sample() draws them.  For a ReplayRing or a PrioritizedReplayRing the draw is one library call
-        of its own (the ring's seed and device call counter; `generator` does not apply), so the whole update is two
-        library calls with no torch kernel between them, and can be captured into a graph.
-
-        importance=False (the default) is the reference's update: it drops the importance weights its sample()
-        returns, and beta then has no effect.  importance=True trains on them (the weighted losses of the module
-        docstring): (count * P(i))^-beta / max over this draw, one per batch row.  A PrioritizedReplayRing writes them
-        beside its indices in the same library call (still two calls, still capturable); with beta_final, beta runs
-        linearly from beta to beta_final over the ring's first anneal_calls draws on the device, so a replayed graph
-        anneals.  A PrioritizedDeviceReplayBuffer forms them in torch as its sample() does (no beta_final).  A uniform
-        buffer has no weights: importance changes nothing there.  A refused ring draw hands out NaN weights, which
-        refuse this update on the device as well.
+        of its own, so the whole update is two library calls (three with rho_bar) with no torch kernel between them,
+        and can be captured into a graph.  beta, generator, importance, beta_final, anneal_calls, rho_bar, rho_out: the
+        fields of replay.DrawSpec, documented there; the defaults are the reference's update.
 
         An n-step ring (ring.with_nstep(n_step, gamma)) brings its per-slot discounts: the target is then
         r + discounts[slot] * V(s'), gathered in the same library call.  Its gamma must be this learner's (as float32).
@@ -410,27 +379,14 @@ class DeviceActorCritic(Handle):
         gradient row of this rank's batch (grad_from), an all-gather of the rows in rank order
         (sharding.gather_learner_rows), the apply of all of them, and the priority write into this rank's buffer.
         Ranks that start equal (sharding.broadcast_learner) stay bitwise equal; batch sizes may differ between ranks.
-        The returned losses are the global ones, td_delta this rank's.  With importance=True every rank's weights are
-        normalised by its own draw's maximum, as independent sample() calls would do.
-
-        rho_bar > 0 (a ring made with_behaviour(); any other buffer raises) corrects for who acted: between the draw and
-        the update, uavtrack_learner_ratio_weights forms rho_i = min(rho_bar, pi(a_i|s_i) / mu(a_i|s_i)) from the ring's
-        log_mu store and the actor as it stands, and the update trains on w_i rho_i (w_i the importance weight, or 1;
-        no second normalisation) through the weighted or discounted entry point: three library calls with no torch
-        kernel between them, capturable.  rho_out (float32 [k], optional) receives the ratios.  rho_bar = inf does not
-        truncate.  A drawn slot whose log_mu is NaN (unknown) or positive refuses the update on the device.  td_delta and
-        the priorities stay the unweighted delta and |delta|.  On an n-step or lambda ring the ratio corrects the first
-        action only.  Participants of one update (ranks, shards) must pass equal rho_bar.  None (the default) enqueues
-        exactly what was enqueued without it."""
-        if group is not None:
-            return self._update_from_group(buffer, batch_size, generator, group, importance, beta, beta_final, anneal_calls,
-                                           rho_bar, rho_out)
-        k = min(int(batch_size), buffer.count)
-        if k < 1:
-            raise ValueError("update_from: the buffer is empty")
-        idx, prio, w = self._draw_from(buffer, k, generator, importance, beta, beta_final, anneal_calls)
-        w = self._ratios_from(buffer, k, idx, w, rho_bar, rho_out)
-        return self._run(k, buffer.store, buffer.capacity, idx, prio, w, self._discounts_of(buffer))
+        The returned losses are the global ones, td_delta this rank's."""
+        spec = DrawSpec(importance=importance, beta=beta, beta_final=beta_final, anneal_calls=anneal_calls,
+                        rho_bar=rho_bar, rho_out=rho_out, generator=generator)
+        if group is None:
+            return self._run(*self._drawn_batch(buffer, batch_size, spec, "update_from"))
+        from .sharding import gather_learner_rows
+        al, cl, (td,) = self._update_split([buffer], batch_size, [spec], lambda rows: gather_learner_rows(rows, group))
+        return al, cl, td
 
     # ---- the split update: gradient rows and an ordered apply
     def new_rows(self, count: int) -> torch.Tensor:
@@ -446,10 +402,7 @@ class DeviceActorCritic(Handle):
                         f"row must be a contiguous float32 tensor of {self.row_floats} words on {self.device}")
         if td is None:
             td = torch.empty(n, device=self.device)
-        suffix, extra = self._form(n, weights, capacity, discounts)
-        name = "uavtrack_learner_grad" + suffix
-        _lib.check(getattr(self._lib, name)(
-            self._h, n, *self._batch_args(store, capacity, idx), *extra, _ptr(td), _ptr(row), self._stream()), name)
+        self._launch("grad", n, store, capacity, idx, weights, discounts, td, row)
         return row, td
 
     def grad_from(self, buffer, batch_size: int, row: Optional[torch.Tensor] = None,
@@ -460,16 +413,16 @@ class DeviceActorCritic(Handle):
         ReplayRing or PrioritizedReplayRing the ring's own library call) and leaves their unscaled gradient and loss sums
         in `row` (a new tensor if None).  Returns (row, td_delta, indices); changes nothing in the learner.  The indices
         of either ring live in the ring's own draw tensor until its next draw: call write_priorities (or clone
-        them) before drawing from the same ring again.  importance, beta, beta_final, anneal_calls: as update_from; the
-        row's sums then carry this draw's weights, normalised by this draw's own maximum.  rho_bar, rho_out: as
-        update_from; the row's sums then carry w_i rho_i."""
-        k = min(int(batch_size), buffer.count)
-        if k < 1:
-            raise ValueError("grad_from: the buffer is empty")
-        idx, _, w = self._draw_from(buffer, k, generator, importance, beta, beta_final, anneal_calls)
-        w = self._ratios_from(buffer, k, idx, w, rho_bar, rho_out)
-        row, td = self._grad(k, buffer.store, buffer.capacity, idx, row, None, w, self._discounts_of(buffer))
-        return row, td, idx
+        them) before drawing from the same ring again.  The other arguments are the fields of replay.DrawSpec; the
+        row's sums carry the weights it describes."""
+        return self._grad_drawn(buffer, batch_size, DrawSpec(
+            importance=importance, beta=beta, beta_final=beta_final, anneal_calls=anneal_calls, rho_bar=rho_bar,
+            rho_out=rho_out, generator=generator), row)
+
+    def _grad_drawn(self, buffer, batch_size: int, spec: DrawSpec, row: Optional[torch.Tensor]):
+        b = self._drawn_batch(buffer, batch_size, spec, "grad_from")
+        row, td = self._grad(b.n, b.store, b.capacity, b.idx, row, None, b.weights, b.discounts)
+        return row, td, b.idx
 
     def apply(self, rows):
         """One update from gradient rows ([count, row_floats], or a sequence of rows): the sums added in row order, one
@@ -490,47 +443,39 @@ class DeviceActorCritic(Handle):
     def write_priorities(self, buffer, idx: Optional[torch.Tensor], td: torch.Tensor) -> None:
         """|td| into a prioritised buffer's priorities at idx (the last occurrence of a repeated slot winning), unless
         the most recent apply on this learner was refused.  A buffer without priorities is left alone."""
-        prio = getattr(buffer, "priorities", None)
-        if prio is None:
-            return
-        _lib.check(self._lib.uavtrack_learner_write_priorities(self._h, td.numel(), _ptr(idx), buffer.capacity,
-                                                               _ptr(td), _ptr(prio), self._stream()),
-                   "uavtrack_learner_write_priorities")
+        if buffer.priorities is not None:
+            _lib.check(self._lib.uavtrack_learner_write_priorities(self._h, td.numel(), _ptr(idx), buffer.capacity,
+                                                                   _ptr(td), _ptr(buffer.priorities), self._stream()),
+                       "uavtrack_learner_write_priorities")
 
     def update_from_many(self, buffers, batch_size: int, generator: Optional[torch.Generator] = None,
                          importance: bool = False, beta: float = 0.4, beta_final: Optional[float] = None,
                          anneal_calls: int = 0, rho_bar: Optional[float] = None, rho_out=None):
         """ONE update from several buffers on this device (the shards of one GPU): one gradient row per buffer from
         min(batch_size, its count) of its rows, the rows applied in list order, each prioritised buffer's priorities
-        written back from its own draw.  Returns (actor_loss, critic_loss, [td_delta per buffer]).  With
-        importance=True each buffer's row carries its own draw's importance weights, normalised by that draw's own
-        maximum (not a maximum across the buffers), as independent sample() calls would do; every ring anneals over
-        its own call counter.  rho_bar: as update_from, every buffer a behaviour ring; rho_out: a sequence of one
-        float32 [k] tensor (or None) per buffer."""
+        written back from its own draw.  Returns (actor_loss, critic_loss, [td_delta per buffer]).  The other arguments
+        are the fields of replay.DrawSpec, one spec for every buffer (each draw's weights normalised by its own maximum,
+        with rho_bar every buffer a behaviour ring), except rho_out: a sequence of one float32 [k] tensor (or None) per
+        buffer."""
         buffers = list(buffers)
         if not 1 <= len(buffers) <= _lib.LEARNER_MAX_ROWS:
             raise ValueError(f"update_from_many: {len(buffers)} buffers, one apply takes 1 to {_lib.LEARNER_MAX_ROWS} rows")
-        rows = self.new_rows(len(buffers))
+        spec = DrawSpec(importance=importance, beta=beta, beta_final=beta_final, anneal_calls=anneal_calls,
+                        rho_bar=rho_bar, generator=generator)
         rho_outs = [None] * len(buffers) if rho_out is None else list(rho_out)
         if len(rho_outs) != len(buffers):
             raise ValueError(f"update_from_many: rho_out holds {len(rho_outs)} entries for {len(buffers)} buffers")
-        drawn = [self.grad_from(b, batch_size, rows[k], generator, importance, beta, beta_final, anneal_calls, rho_bar,
-                                rho_outs[k])
-                 for k, b in enumerate(buffers)]
-        al, cl = self.apply(rows)
+        return self._update_split(buffers, batch_size, [spec._replace(rho_out=r) for r in rho_outs])
+
+    def _update_split(self, buffers, batch_size: int, specs, gather=None):
+        """The split update behind update_from_many and update_from(group=): a gradient row per buffer, the rows as
+        `gather` completes them (the other ranks' rows), one apply, each buffer's priorities from its own draw."""
+        rows = self.new_rows(len(buffers))
+        drawn = [self._grad_drawn(b, batch_size, s, r) for b, s, r in zip(buffers, specs, rows)]
+        al, cl = self.apply(rows if gather is None else gather(rows))
         for b, (_, td, idx) in zip(buffers, drawn):
             self.write_priorities(b, idx, td)
         return al, cl, [td for _, td, _ in drawn]
-
-    def _update_from_group(self, buffer, batch_size: int, generator, group, importance: bool = False,
-                           beta: float = 0.4, beta_final: Optional[float] = None, anneal_calls: int = 0,
-                           rho_bar: Optional[float] = None, rho_out: Optional[torch.Tensor] = None):
-        from .sharding import gather_learner_rows
-        row, td, idx = self.grad_from(buffer, batch_size, None, generator, importance, beta, beta_final, anneal_calls,
-                                      rho_bar, rho_out)
-        al, cl = self.apply(gather_learner_rows(row, group))
-        self.write_priorities(buffer, idx, td)
-        return al, cl, td
 
     def publish_actor(self, env) -> None:
         """The actor's current parameters into env's rollout actor, packed on the device (uavtrack_learner_publish_actor):

@@ -10,11 +10,44 @@ maximum priority (train.py:87-96), importance weights (size * P(i))^-beta / max 
 """
 from __future__ import annotations
 
-from typing import Dict, Optional, Tuple
+from typing import Dict, NamedTuple, Optional, Tuple
 
 import torch
 
 KEYS = ("states", "actions", "rewards", "next_states")
+
+
+class DrawSpec(NamedTuple):
+    """How DeviceActorCritic.update_from, grad_from, update_from_many and the group path draw a batch from a buffer and
+    weigh its rows: each builds one of these from its arguments and hands it to the buffer's _draw_batch(k, spec), which
+    returns (indices, weights or None).  The defaults enqueue exactly the reference's update: sample(), the unweighted
+    update, |td_delta| into a prioritised buffer's priorities.
+
+    importance    train on the prioritised draw's importance weights (count * P(i))^-beta / max over this draw, one per
+                  batch row (the weighted losses of uavtrack/learner.py); False drops them as the reference's update
+                  does, and beta then has no effect.  A PrioritizedReplayRing writes them beside its indices in the same
+                  library call, a PrioritizedDeviceReplayBuffer forms them in torch as its sample() does; a uniform
+                  buffer has none.  A refused ring draw hands out NaN weights, which refuse the update on the device as
+                  well.  Several buffers or ranks in one update: each draw is normalised by its own maximum.
+    beta_final, anneal_calls
+                  PrioritizedReplayRing only: beta runs linearly from beta to beta_final over the ring's first
+                  anneal_calls draws, counted on the device, so a replayed graph anneals (every ring over its own counter).
+    rho_bar       > 0, a ring made with_behaviour() (any other buffer raises): between the draw and the update,
+                  uavtrack_learner_ratio_weights forms rho_i = min(rho_bar, pi(a_i|s_i) / mu(a_i|s_i)) from the ring's
+                  log_mu store and the actor as it stands, and the update trains on w_i rho_i (w_i the importance weight,
+                  or 1; no second normalisation), capturable like the rest.  inf does not truncate.  A drawn slot whose
+                  log_mu is NaN (unknown) or positive refuses the update on the device.  td_delta and the priorities stay
+                  the unweighted delta and |delta|; on an n-step or lambda ring the ratio corrects the first action only.
+                  Participants of one update (ranks, shards) must pass equal rho_bar.
+    rho_out       float32 [k], optional, needs rho_bar: receives the ratios.
+    generator     the torch.Generator of a torch buffer's draw; a ring draws from its own seed and device call counter."""
+    importance: bool = False
+    beta: float = 0.4
+    beta_final: Optional[float] = None
+    anneal_calls: int = 0
+    rho_bar: Optional[float] = None
+    rho_out: Optional[torch.Tensor] = None
+    generator: Optional[torch.Generator] = None
 
 
 def transitions_from_rollout(obs_in: torch.Tensor, out: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
@@ -35,6 +68,7 @@ def transitions_from_rollout(obs_in: torch.Tensor, out: Dict[str, torch.Tensor])
 
 class DeviceReplayBuffer:
     """ReplayBuffer (train.py:41-70) as a device ring."""
+    priorities = discounts = log_mu = gamma = None     # what a prioritised, an n-step or a behaviour buffer would hold
 
     def __init__(self, capacity: int, device, obs_dim: int = 12):
         self.capacity = int(capacity)
@@ -70,9 +104,12 @@ class DeviceReplayBuffer:
         self.count = min(self.capacity, self.count + n)
         return idx
 
+    def _draw_batch(self, k: int, spec: DrawSpec = DrawSpec()):
+        """(k distinct indices, None): the draw of sample() and of the learner's update_from."""
+        return torch.randperm(self.count, device=self.device, generator=spec.generator)[:k], None
+
     def sample(self, batch_size: int, generator: Optional[torch.Generator] = None) -> Dict[str, torch.Tensor]:
-        k = min(int(batch_size), self.count)
-        idx = torch.randperm(self.count, device=self.device, generator=generator)[:k]
+        idx, _ = self._draw_batch(min(int(batch_size), self.count), DrawSpec(generator=generator))
         return {key: self.store[key][idx] for key in KEYS}
 
 
@@ -93,15 +130,24 @@ class PrioritizedDeviceReplayBuffer(DeviceReplayBuffer):
         self.priorities.index_add_(0, idx, top.expand(idx.numel()))
         return idx
 
+    def _draw_batch(self, k: int, spec: DrawSpec = DrawSpec()):
+        """(k indices drawn with replacement from p_i^alpha / sum, their importance weights or None)."""
+        prob = self.priorities[:self.count] ** self.alpha
+        prob = prob / prob.sum()
+        idx = torch.multinomial(prob, k, replacement=True, generator=spec.generator)
+        if not spec.importance:
+            return idx, None
+        if spec.beta_final is not None:
+            raise ValueError("beta_final anneals over a PrioritizedReplayRing's device call counter; a "
+                             "PrioritizedDeviceReplayBuffer has none: pass this call's beta")
+        weights = (self.count * prob[idx]) ** (-spec.beta)
+        return idx, weights / weights.max()
+
     def sample(self, batch_size: int, beta: float = 0.4, generator: Optional[torch.Generator] = None):
         if self.count == 0:
             return {k: self.store[k][:0] for k in KEYS}, None, None
-        prob = self.priorities[:self.count] ** self.alpha
-        prob = prob / prob.sum()
-        k = min(int(batch_size), self.count)
-        idx = torch.multinomial(prob, k, replacement=True, generator=generator)
-        weights = (self.count * prob[idx]) ** (-beta)
-        weights = weights / weights.max()
+        idx, weights = self._draw_batch(min(int(batch_size), self.count),
+                                        DrawSpec(importance=True, beta=beta, generator=generator))
         return {key: self.store[key][idx] for key in KEYS}, idx, weights
 
     def update_priorities(self, batch_indices: torch.Tensor, batch_priorities: torch.Tensor) -> None:

@@ -53,7 +53,7 @@ import torch
 from . import _lib
 from ._handle import Handle, current_device
 from ._lib import ptr as _ptr
-from .replay import KEYS
+from .replay import KEYS, DrawSpec
 
 
 class ReplayRing(Handle):
@@ -61,14 +61,13 @@ class ReplayRing(Handle):
     replacement.  Also what PrioritizedReplayRing shares with it: the stores, the adds and the handle."""
     _prefix = "uavtrack_replay_"
     priorities: Optional[torch.Tensor] = None
-
     discounts: Optional[torch.Tensor] = None
-
     n_step: int = 1
     gamma: Optional[float] = None
     lam: Optional[float] = None                 # with_lambda: the ring stores lambda-returns
     _values: Optional[torch.Tensor] = None      # add_rollout(critic=...)'s buffer, kept and only grown
     log_mu: Optional[torch.Tensor] = None       # with_behaviour: per-slot behaviour log-probabilities
+    _w: Optional[torch.Tensor] = None           # a prioritised ring's importance weights of update_from's draws
     _rho_w: Optional[torch.Tensor] = None       # with_behaviour: update_from's ratio weights (a prioritised ring: its _w)
 
     def __init__(self, capacity: int, device, seed: int = 0, max_batch: int = 65536, obs_dim: int = _lib.OBS_DIM):
@@ -133,7 +132,7 @@ class ReplayRing(Handle):
         Composes with with_nstep and with_lambda in either order."""
         if self.log_mu is None:
             self.log_mu = torch.full((self.capacity,), float("nan"), dtype=torch.float32, device=self.device)
-            if getattr(self, "_w", None) is None:          # a prioritised ring's own importance-weight buffer serves
+            if self._w is None:                            # a prioritised ring's own importance-weight buffer serves
                 self._rho_w = torch.empty(self.max_batch, dtype=torch.float32, device=self.device)
         return self
 
@@ -324,11 +323,16 @@ class ReplayRing(Handle):
         _lib.check(self._lib.uavtrack_replay_sample_uniform(self._h, C.byref(ring), k, _ptr(idx), self._stream()),
                    "uavtrack_replay_sample_uniform")
 
-    def _draw_into(self, k: int) -> torch.Tensor:
-        """k distinct indices into the preallocated index tensor: what DeviceActorCritic.update_from uses."""
+    def _draw_batch(self, k: int, spec: DrawSpec = DrawSpec()):
+        """(k distinct indices in the preallocated index tensor, None): what DeviceActorCritic.update_from uses."""
         idx = self._idx[:k]
         self._draw_uniform(k, idx)
-        return idx
+        return idx, None
+
+    def _ratio_out(self, k: int) -> torch.Tensor:
+        """Where update_from(..., rho_bar=) leaves the k weights it trains with: a prioritised ring's importance weights
+        are multiplied in place, a uniform behaviour ring has the buffer with_behaviour made."""
+        return (self._rho_w if self._w is None else self._w)[:k]
 
     def draw(self, batch_size: int) -> Optional[torch.Tensor]:
         """indices int64 [k], k = min(batch_size, count): distinct slots of [0, count) in random order, as
@@ -382,16 +386,15 @@ class PrioritizedReplayRing(ReplayRing):
             self._h, C.byref(ring), k, self.alpha, float(beta), float(beta_final), int(anneal_calls), _ptr(idx),
             _ptr(weights), self._stream()), "uavtrack_replay_sample_annealed")
 
-    def _draw_into(self, k: int, importance: bool = False, beta: float = 0.0, beta_final: Optional[float] = None,
-                   anneal_calls: int = 0):
-        """k indices into the preallocated index tensor: what DeviceActorCritic.update_from uses.  Without `importance`
-        no weights are formed and the indices come back alone; with it, (indices, weights) in the preallocated pair."""
+    def _draw_batch(self, k: int, spec: DrawSpec = DrawSpec()):
+        """(k indices, their importance weights) in the preallocated pair: what DeviceActorCritic.update_from uses.
+        Without spec.importance no weights are formed: (indices, None)."""
         idx = self._idx[:k]
-        if not importance:
+        if not spec.importance:
             self._draw(k, 0.0, idx, None)
-            return idx
+            return idx, None
         w = self._w[:k]
-        self._draw(k, beta, idx, w, beta_final, anneal_calls)
+        self._draw(k, spec.beta, idx, w, spec.beta_final, spec.anneal_calls)
         return idx, w
 
     def draw(self, batch_size: int, beta: float = 0.4, beta_final: Optional[float] = None,

@@ -11,6 +11,7 @@ import torch
 import learner_dp_mirror as dp
 import learner_harness as lh
 import offpolicy_mirror as om
+from uavtrack.replay import DrawSpec
 
 pytestmark = pytest.mark.gpu
 
@@ -282,10 +283,7 @@ def test_off_policy_update_from_is_draw_then_ratio_weights_then_the_weighted_upd
     blob = L1._get_params()
     r = torch.empty(63, device=DEV)
     got = _outcome(L1, r1, L1.update_from(r1, 63, importance=importance, rho_bar=2.0, rho_out=r))
-    if importance:
-        idx, w = r2._draw_into(63, True, 0.4)
-    else:
-        idx, w = r2._draw_into(63), None
+    idx, w = r2._draw_batch(63, DrawSpec(importance=importance, beta=0.4))
     w_out, rho = torch.empty(63, device=DEV), torch.empty(63, device=DEV)
     _ratio(L2, 63, r2.store, r2.log_mu, CAP, idx, 2.0, w, w_out, rho)
     want = lh.update(L2, 63, r2.store, CAP, idx, r2.priorities, w_out)
@@ -439,10 +437,7 @@ def test_update_from_many_is_the_apply_of_the_explicit_weighted_rows():
     rows = L2.new_rows(2)
     want_td = []
     for k, ring in enumerate(rings2):
-        if ring.priorities is not None:
-            i, w = ring._draw_into(40, True, 0.4)
-        else:
-            i, w = ring._draw_into(40), None
+        i, w = ring._draw_batch(40, DrawSpec(importance=True, beta=0.4))    # a uniform ring: no weights
         w_out = torch.empty(40, device=DEV)
         _ratio(L2, 40, ring.store, ring.log_mu, CAP, i, 2.0, w, w_out, None)
         _, t = L2._grad(40, ring.store, CAP, i, rows[k], None, w_out)

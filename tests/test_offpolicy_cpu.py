@@ -16,6 +16,7 @@ import learner_weighted_mirror as wm
 import offpolicy_mirror as om
 import uavtrack
 from uavtrack import _lib
+from uavtrack.replay import DrawSpec
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "marl-uavs-targets-tracking_amd", "csrc")
@@ -208,12 +209,12 @@ def test_the_learners_surface_and_rho_bar_without_the_store():
     bare = object.__new__(L)                                                # the host-side check needs no handle
     for ring in (_Bare(), _Bare().with_nstep(3, 0.95), object()):
         with pytest.raises(ValueError, match="with_behaviour"):
-            bare._ratios_from(ring, 4, None, None, 1.0, None)
+            bare._ratios_from(ring, 4, None, None, DrawSpec(rho_bar=1.0))
     w = torch.ones(4)
-    assert bare._ratios_from(_Bare(), 4, None, w, None, None) is w          # rho_bar None: the draw's weights, untouched
-    assert bare._ratios_from(_Bare(), 4, None, None, None, None) is None
+    assert bare._ratios_from(_Bare(), 4, None, w, DrawSpec()) is w           # rho_bar None: the draw's weights, untouched
+    assert bare._ratios_from(_Bare(), 4, None, None, DrawSpec()) is None
     with pytest.raises(ValueError, match="rho_out needs rho_bar"):
-        bare._ratios_from(_Bare().with_behaviour(), 4, None, None, None, torch.empty(4))
+        bare._ratios_from(_Bare().with_behaviour(), 4, None, None, DrawSpec(rho_out=torch.empty(4)))
 
 
 def _closure(path, seen):

@@ -59,7 +59,7 @@ def test_python_interface():
     assert list(inspect.signature(R.sample).parameters) == ["self", "batch_size"]
     for name in ("add", "add_rollout", "size", "check"):
         assert getattr(P, name) is getattr(R, name), name                     # shared, not copied
-    assert P.draw is not R.draw and P.sample is not R.sample and P._draw_into is not R._draw_into
+    assert P.draw is not R.draw and P.sample is not R.sample and P._draw_batch is not R._draw_batch
 
 
 def test_uniform_draw_refuses_without_a_gpu_handle():

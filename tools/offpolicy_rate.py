@@ -70,7 +70,7 @@ def update_rows(n, H, slots):
                     for k in ("plain", "rho_bar")}
         ring = filled(cls(slots, DEV, seed=1, max_batch=n).with_behaviour(), learners["rho_bar"])
         if kind == "uniform":
-            idx = ring._draw_into(n)
+            idx, _ = ring._draw_batch(n)
             w = torch.empty(n, device=DEV)
             res = alternating({"ratio_weights": lambda: learners["rho_bar"]._ratio_weights(
                 n, ring.store, ring.log_mu, slots, idx, 1.0, None, w, None)}, reps=50)

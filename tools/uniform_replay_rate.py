@@ -67,7 +67,7 @@ def update_rows(count, k, reps):
     torch.manual_seed(0)
     learner = uavtrack.DeviceActorCritic(12, 128, 12, 1e-4, 5e-4, 0.95, DEV, max_batch=k)
     rows = []
-    for what, hip, tor in (("draw", lambda: ring._draw_into(k), lambda: torch.randperm(count, device=DEV)[:k]),
+    for what, hip, tor in (("draw", lambda: ring._draw_batch(k), lambda: torch.randperm(count, device=DEV)[:k]),
                            ("draw + update_from", lambda: learner.update_from(ring, k),
                             lambda: learner.update_from(ref, k))):
         rows.append({"what": what, "count": count, "k": k, "reps": reps, "runs": RUNS, **compare(hip, tor, reps)})
