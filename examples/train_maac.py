@@ -17,6 +17,8 @@ update is the same rule on a sampled batch, and the new actor weights are re-upl
     python examples/train_maac.py --replay prioritized --learner device --n-step 3                        # 3-step returns folded by the ring's add
     python examples/train_maac.py --replay prioritized --learner device --td-lambda 0.9                   # lambda-returns: critic values + a backward scan in the ring's add
     python examples/train_maac.py --replay prioritized --learner device --rho-bar 1.0 --publish device --log-every 10   # truncated importance ratios: who acted
+    python examples/train_maac.py --replay prioritized --learner device --target-tau 0.005                # bootstrap from a Polyak-averaged target critic
+    python examples/train_maac.py --replay prioritized --learner device --target-period 100 --td-lambda 0.9   # ... or a periodic copy; the lambda add folds with it too
     python examples/train_maac.py --method maac-r --pmi-trainer device --learner device --replay prioritized --publish device --log-every 10
     python examples/train_maac.py --shards 8 --envs 32768 --n-uav 20 --learner device --replay prioritized --publish device   # 8 shard handles, one learner
     python examples/train_maac.py --shards 4 --method maac-r --pmi-trainer device --learner device --replay prioritized --publish device   # ... and one PMI trainer
@@ -36,6 +38,7 @@ pmi_contrastive_loss on the device history) and its BatchNorm-folded weights are
 generator and the PMI loss read on printed lines only, so that a MAAC-R iteration too issues no host synchronisation.
 """
 import argparse
+import copy
 import os
 import sys
 import time
@@ -60,7 +63,7 @@ class ValueNet(torch.nn.Module):
 
 
 def update(actor, critic, opt_a, opt_c, batch, gamma, weights=None, entropy_coef=0.0, max_grad_norm=None, diag=None,
-           rho_bar=None, rho_stats=None):
+           rho_bar=None, rho_stats=None, target_critic=None):
     """One ActorCritic.update step (actor_critic.py:150-178) on a batch of transitions.  weights (--importance): the
     draw's importance weights, one per row, multiplied into the per-sample losses before the mean.  entropy_coef and
     max_grad_norm: the two terms of DeviceActorCritic.set_regularisation, so that --learner torch and --learner device
@@ -68,9 +71,16 @@ def update(actor, critic, opt_a, opt_c, batch, gamma, weights=None, entropy_coef
     n-step ring (--n-step) carries "discounts", gamma^m per row, which take gamma's place in the target; so does a batch
     from a lambda ring (--td-lambda), whose rewards and discounts make that target the lambda-return.  rho_bar (--rho-bar):
     the batch carries "log_mu" and every row's losses are multiplied by min(rho_bar, pi / mu), a constant of the
-    differentiation, as DeviceActorCritic.update_from(rho_bar=) does; rho_stats (a dict) receives the ratios."""
+    differentiation, as DeviceActorCritic.update_from(rho_bar=) does; rho_stats (a dict) receives the ratios.
+    target_critic (--target-tau / --target-period): the copy of the critic that V(s') comes from; keeping it in step
+    is the caller's (sync_target_critic)."""
     s, a, r, s2 = batch["states"], batch["actions"].long().unsqueeze(1), batch["rewards"], batch["next_states"]
-    td_target = r + batch.get("discounts", gamma) * critic(s2)
+    if target_critic is None:
+        v_next = critic(s2)
+    else:
+        with torch.no_grad():
+            v_next = target_critic(s2)
+    td_target = r + batch.get("discounts", gamma) * v_next
     td_delta = td_target - critic(s)
     probs = actor(s)
     log_probs = torch.log(probs.gather(1, a).squeeze(1).clamp_min(1e-12))
@@ -102,9 +112,36 @@ def update(actor, critic, opt_a, opt_c, batch, gamma, weights=None, entropy_coef
     return float(actor_loss.detach()), float(critic_loss.detach())
 
 
+def targeted(args):
+    return args.target_tau is not None or args.target_period is not None
+
+
+def sync_target_critic(args, target_critic, critic, updates_done):
+    """The torch learner's side of --target-tau / --target-period, behind each update: DeviceActorCritic.set_target's two
+    rules on a copy.deepcopy of the critic -- t <- (1 - tau) t + tau w with two float32 multiplies and one add, or a copy
+    after every --target-period updates."""
+    if args.target_tau is not None:
+        tau32 = torch.tensor(args.target_tau, dtype=torch.float32)
+        omt, tau = float(1.0 - tau32), float(tau32)                    # both float32 values: formed once, as the library's
+    with torch.no_grad():
+        for t, w in zip(target_critic.parameters(), critic.parameters()):
+            if args.target_tau is not None:
+                t.mul_(omt).add_(w * tau)
+            elif updates_done % args.target_period == 0:
+                t.copy_(w)
+
+
+def lambda_critic(args, online, target):
+    """Whose values the lambda add folds the rewards with (--lambda-critic): the target critic's while one is kept
+    (the default then: the tail of a lambda-return bootstraps from the same slowly moving critic as its head, which
+    every update takes from the target), else the online critic's."""
+    return target if targeted(args) and args.lambda_critic != "online" else online
+
+
 def device_learner(args, uavtrack, na_total, dev, max_batch):
     """The DeviceActorCritic of --learner device with --entropy-coef / --max-grad-norm; the diagnostics only when one of
-    them is on.  A refused setting (--entropy-coef with --actor-loss reference) exits with the library's message."""
+    them is on.  A refused setting (--entropy-coef with --actor-loss reference) exits with the library's message.
+    --target-tau / --target-period: its target critic (set_target)."""
     try:
         learner = uavtrack.DeviceActorCritic(12, args.hidden, na_total, args.actor_lr, args.critic_lr, args.gamma, dev,
                                              loss=args.actor_loss, max_batch=max_batch,
@@ -113,6 +150,8 @@ def device_learner(args, uavtrack, na_total, dev, max_batch):
         raise SystemExit(f"train_maac.py: {e}")
     if regularised(args):
         learner.enable_diagnostics(max_batch)
+    if targeted(args):
+        learner.set_target(tau=args.target_tau, period=args.target_period)
     return learner
 
 
@@ -266,7 +305,8 @@ def train_sharded(args, timings=None):
             obs_in = ro.obs.clone()
             res = ro.run_fused(args.steps, out=outs[k], stats=stats[k])    # done fires at the horizon: one record per episode
             outs[k] = {key: v for key, v in res.items() if key != "ep_sums"}
-            add_rollout(args, ring, obs_in, res, learner, learner)   # (--td-lambda: every ring, the one learner's values)
+            add_rollout(args, ring, obs_in, res, learner,
+                        lambda_critic(args, learner, learner.target))   # (--td-lambda: every ring, the one learner's values)
             eps.append(res["ep_sums"])
         if log:
             torch.cuda.synchronize()
@@ -390,6 +430,19 @@ def main(argv=None, timings=None):
                          "the same ratios); the printed lines show the mean ratio and the share of rows at the cap.  With "
                          "--n-step or --td-lambda the ratio corrects the first action only.  Needs --replay prioritized or "
                          "uniform-device")
+    tgt = ap.add_mutually_exclusive_group()
+    tgt.add_argument("--target-tau", type=float, default=None,
+                     help="tau in (0, 1]: bootstrap V(s') from a target critic kept by Polyak averaging, "
+                          "t <- (1 - tau) t + tau w after every update (DeviceActorCritic.set_target(tau=...); the torch "
+                          "learner keeps a copy.deepcopy of its critic under the same rule)")
+    tgt.add_argument("--target-period", type=int, default=None,
+                     help="K >= 1: bootstrap V(s') from a target critic that is copied from the critic after every K "
+                          "updates (DeviceActorCritic.set_target(period=K), counted on the device; the torch learner "
+                          "likewise)")
+    ap.add_argument("--lambda-critic", choices=["target", "online"], default=None,
+                    help="--td-lambda with a target critic: whose values the ring's add folds the rewards with.  Default "
+                         "target: the whole lambda-return then bootstraps from the one slowly moving critic, as the "
+                         "update's own V(s') does; online: the critic being trained, as without a target")
     ap.add_argument("--alpha", type=float, default=0.6, help="--replay prioritized: priority exponent (train.py:74)")
     ap.add_argument("--beta", type=float, default=0.4, help="--replay prioritized: importance exponent (train.py:100)")
     ap.add_argument("--importance", action="store_true",
@@ -459,6 +512,12 @@ def main(argv=None, timings=None):
     if args.rho_bar is not None and (not args.rho_bar > 0 or args.replay == "uniform"):
         ap.error("--rho-bar must be > 0 and needs --replay prioritized or --replay uniform-device (the device rings keep "
                  "the behaviour log-probabilities)")
+    if args.target_tau is not None and not 0.0 < args.target_tau <= 1.0:
+        ap.error("--target-tau must lie in (0, 1]")
+    if args.target_period is not None and args.target_period < 1:
+        ap.error("--target-period must be >= 1")
+    if args.lambda_critic is not None and (args.td_lambda is None or not targeted(args)):
+        ap.error("--lambda-critic chooses between two critics: it needs --td-lambda and --target-tau or --target-period")
     if args.importance and args.replay != "prioritized":
         ap.error("--importance needs --replay prioritized (a uniform draw has no importance weights)")
     if args.beta_final is not None and not args.importance:
@@ -504,10 +563,14 @@ def main(argv=None, timings=None):
     critic = ValueNet(hidden_dim=args.hidden).to(dev)
     opt_a = torch.optim.Adam(actor.parameters(), lr=args.actor_lr)
     opt_c = torch.optim.Adam(critic.parameters(), lr=args.critic_lr)
+    target_critic = None                                              # the torch learner's target (--learner torch)
     learner = None
     if args.learner == "device":
         learner = device_learner(args, uavtrack, cfg.na_total, dev, args.batch)
         actor.load_state_dict(learner.actor_state_dict())
+    elif targeted(args):
+        target_critic = copy.deepcopy(critic).requires_grad_(False)
+    updates_done = 0
     rollout = uavtrack.BatchedRollout(env, actor, device_actor=True, seed=args.seed)
     K = args.rollout_episodes
     T = K * args.steps                                                # steps of one launch
@@ -540,7 +603,8 @@ def main(argv=None, timings=None):
         out = {k: v for k, v in res.items() if k != "ep_sums"}        # reuse the output buffers next time
         if args.replay != "uniform":
             add_rollout(args, replay, obs_in, res, actor if learner is None else learner,
-                        critic if learner is None else learner)      # straight from the outputs
+                        lambda_critic(args, critic, target_critic) if learner is None else
+                        lambda_critic(args, learner, learner.target))   # straight from the outputs
         else:
             replay.add(uavtrack.transitions_from_rollout(obs_in, res))
         if log:
@@ -549,7 +613,8 @@ def main(argv=None, timings=None):
         diag = {} if log and regularised(args) else None              # the torch learner's entropy and norms
         rho_stats = {}                                                # --rho-bar: the last update's ratios, a device tensor
         reg_kw = dict(entropy_coef=args.entropy_coef, max_grad_norm=args.max_grad_norm, diag=diag, rho_bar=args.rho_bar,
-                      rho_stats=rho_stats)
+                      rho_stats=rho_stats, target_critic=target_critic)
+        boot = critic if target_critic is None else target_critic     # whose V(s') the torch learner bootstraps from
         if learner is None and args.replay == "prioritized":          # train.py:250-262
             ikw = importance_kwargs(args)
             for _ in range(args.updates):
@@ -557,10 +622,16 @@ def main(argv=None, timings=None):
                 la, lc = update(actor, critic, opt_a, opt_c, batch, args.gamma, w if args.importance else None, **reg_kw)
                 with torch.no_grad():
                     s, r, s2 = batch["states"], batch["rewards"], batch["next_states"]
-                    replay.update_priorities(idx, (r + batch.get("discounts", args.gamma) * critic(s2) - critic(s)).abs())
+                    replay.update_priorities(idx, (r + batch.get("discounts", args.gamma) * boot(s2) - critic(s)).abs())
+                updates_done += 1
+                if target_critic is not None:
+                    sync_target_critic(args, target_critic, critic, updates_done)
         elif learner is None:
             for _ in range(args.updates):
                 la, lc = update(actor, critic, opt_a, opt_c, replay.sample(args.batch), args.gamma, **reg_kw)
+                updates_done += 1
+                if target_critic is not None:
+                    sync_target_critic(args, target_critic, critic, updates_done)
         else:
             rho_kw = {}
             if args.rho_bar is not None:

@@ -670,6 +670,61 @@ int uavtrack_learner_grad_discounted(uavtrack_learner *learner, int64_t n,
  * the critic of that moment.  Returns an error, enqueuing nothing, for a null pointer, n < 1 or misaligned rows. */
 int uavtrack_learner_values(uavtrack_learner *learner, int64_t n, const float *rows, float *values, void *stream);
 
+/* ---- the target critic: bootstrap from a second copy of the critic, synced softly or periodically (off by default) ----
+ * A learner may hold a second copy of the critic's parameters, the target theta-: 14 H + 1 fp32 words in the critic's own
+ * torch order, fc1.weight [H][12], fc1.bias [H], fc2.weight [1][H], fc2.bias [1].  With it off, every call above enqueues
+ * exactly the kernels it enqueued without it.  While a target is enabled:
+ *
+ * Bootstrap.  y_i = r_i + d_i * V_target(s'_i), with theta- as it stands when the gradient kernel executes;
+ * delta_i = y_i - V(s_i).  V(s_i), both backward passes, the losses, td_delta and the priorities are formed as before, in
+ * both loss forms, with weights, per-row discounts, truncated ratios, the entropy bonus and clipping: none of them
+ * touches V(s').  V_target(s') is the chain of uavtrack_learner_values (layer 1 in k order, layer 2 in j order, explicit
+ * fmaf) over theta-, so while theta- holds the critic's bits an update forms the bits of the update without a target.
+ * This holds for update, update_weighted, update_discounted and the three grad calls alike.
+ *
+ * Sync rule.  Once per SUCCESSFUL update or apply, behind its Adam step on the same stream and gated on the same status
+ * word: a refused update or apply leaves theta- untouched.  w is the critic just stepped, t the target, word by word:
+ *   UAVTRACK_TARGET_POLYAK, tau in (0, 1]:  tau32 = (float)tau and omt = 1.0f - tau32, both formed once on the host;
+ *       t <- fl( fl(omt * t) + fl(tau32 * w) )
+ *     two fp32 multiplies and one fp32 add, each rounded to nearest on its own, never contracted into an FMA: a float32
+ *     mirror that performs the three operations reproduces every bit.  At tau = 1, omt = 0 and t <- w: the critic's bits
+ *     (for finite t; a word w = -0.0f comes out as +0.0f where omt * t is +0).
+ *   UAVTRACK_TARGET_PERIODIC, period >= 1:  t <- w if step % period == 0, where step is the critic's fc1.weight Adam
+ *     step count on the device (step[4] of uavtrack_learner_get_optimizer_state) AFTER this update advanced it.  The
+ *     counter lives on the device: a replayed graph keeps the schedule, and so does a learner resumed from a checkpoint.
+ * The split update: uavtrack_learner_grad* bootstraps from theta-, uavtrack_learner_apply runs the sync rule behind its
+ * Adam step.  Gradient rows keep their P + 8 words and carry no settings: the participants of one update must hold
+ * equal settings and equal theta-; they then stay bitwise equal, each running the same rule on the same bits.
+ *
+ * What is promised bitwise: the arithmetic above; that an update whose theta- equals the critic's bits is the update
+ * without a target; that a learner that disabled its target again updates like one that never had one.  Nothing is
+ * claimed about learning curves.  Cost on one MI355X: DESIGN.md section 9. */
+enum uavtrack_target_mode {
+    UAVTRACK_TARGET_OFF      = 0,   /* bootstrap from the online critic (the default) */
+    UAVTRACK_TARGET_POLYAK   = 1,   /* soft sync by tau after every successful update */
+    UAVTRACK_TARGET_PERIODIC = 2    /* hard copy whenever the device step count is a multiple of period */
+};
+
+/* Host-side settings, read when a later update / grad / apply is ENQUEUED (a captured graph keeps the ones it was
+ * captured with).  mode: enum uavtrack_target_mode; tau is read for _POLYAK only, period for _PERIODIC only.
+ * OFF -> on allocates the block (once; it is kept for the handle's life, so this call is not for use inside a capture)
+ * and hard-copies the current critic into it, ordered on `stream`.  Changing tau, period or the mode while a target is
+ * enabled keeps theta-.  _OFF returns the bootstrap to the online critic; enabling again hard-copies again.
+ * Refused, changing nothing: an unknown mode, tau outside (0, 1] or NaN, period < 1. */
+int uavtrack_learner_set_target(uavtrack_learner *learner, int32_t mode, double tau, int64_t period, void *stream);
+/* out = {mode, tau as it was set (0 unless _POLYAK), period (0 unless _PERIODIC)}; {0, 0, 0} at create. */
+int uavtrack_learner_get_target(uavtrack_learner *learner, double out[3]);
+/* theta- <- the critic as it stands when the copy executes: stream-ordered, no synchronisation, no allocation,
+ * capturable.  An error while no target is enabled. */
+int uavtrack_learner_sync_target(uavtrack_learner *learner, void *stream);
+/* theta- as a HOST blob of n_floats = 14 H + 1 floats in the order above.  Synchronise `stream`, like
+ * uavtrack_learner_set_params.  An error while no target is enabled. */
+int uavtrack_learner_set_target_params(uavtrack_learner *learner, const float *params, int64_t n_floats, void *stream);
+int uavtrack_learner_get_target_params(uavtrack_learner *learner, float *params, int64_t n_floats, void *stream);
+/* uavtrack_learner_values with theta- in the critic's place: the same kernel, chain and argument rules, theta- read when
+ * the launch executes.  An error while no target is enabled. */
+int uavtrack_learner_values_target(uavtrack_learner *learner, int64_t n, const float *rows, float *values, void *stream);
+
 /* ---- the actor alone, and off-policy correction: truncated importance ratios as update weights ----
  * Rows of a replay ring were acted by the actor of the moment they were added (the behaviour policy mu), not by the one
  * an update differentiates (pi).  The truncated ratio rho_i = min(rho_bar, pi(a_i|s_i) / mu(a_i|s_i)) is one weight per

@@ -13,6 +13,7 @@ struct uavtrack_learner {
     uavtrack_learner_config cfg;
     LearnerDevice d;
     double reg[3] = {0.0, INFINITY, INFINITY};   // uavtrack_learner_get_regularisation: the values as they were set
+    double target_tau = 0.0;                     // uavtrack_learner_get_target: tau as it was set (0 unless Polyak)
 };
 
 namespace uavtrack {
@@ -26,6 +27,9 @@ static Bufs device_bufs(LearnerDevice &d)
                                    buf(d.gsum, P), buf(d.sq, 2 * (size_t)learner_clip_groups(d.L)), buf(d.coef, 2)} +
            scratch_bufs(d, d.max_n);
 }
+
+// the target critic's block: not part of device_bufs(), it is allocated when a target is first enabled
+static Bufs target_bufs(LearnerDevice &d) { return {buf(d.target, (size_t)learner_critic_words(d.L))}; }
 
 static int *refusal_word(const LearnerDevice &d) { return d.opt.errors; }
 
@@ -106,7 +110,15 @@ int uavtrack_learner_create(const uavtrack_learner_config *cfg, uavtrack_learner
     return create_handle(__func__, cfg, out, check, init);
 }
 
-int uavtrack_learner_destroy(uavtrack_learner *learner) { return destroy_handle(learner); }
+int uavtrack_learner_destroy(uavtrack_learner *learner)
+{
+    if (learner && learner->d.target) {
+        DeviceGuard guard(learner->cfg.device_id);
+        (void)hipDeviceSynchronize();
+        release(target_bufs(learner->d));
+    }
+    return destroy_handle(learner);
+}
 
 int uavtrack_learner_num_params(uavtrack_learner *learner, int64_t *out)
 {
@@ -340,7 +352,103 @@ int uavtrack_learner_values(uavtrack_learner *learner, int64_t n, const float *r
     if (n > INT64_MAX / 48) return fail("%s: n = %lld rows overflow", __func__, (long long)n);
     if (((uintptr_t)rows & 15) != 0) return fail("%s: rows must be 16-byte aligned", __func__);
     ON_DEVICE(learner->cfg.device_id);
-    HIP_TRY(launch_learner_values(learner->d, n, rows, values, static_cast<hipStream_t>(stream)));
+    HIP_TRY(launch_learner_values(learner->d, false, n, rows, values, static_cast<hipStream_t>(stream)));
+    return 0;
+}
+
+// ---- the target critic
+
+int uavtrack_learner_set_target(uavtrack_learner *learner, int32_t mode, double tau, int64_t period, void *stream)
+{
+    if (!learner) return fail("%s: null handle", __func__);
+    if (mode != UAVTRACK_TARGET_OFF && mode != UAVTRACK_TARGET_POLYAK && mode != UAVTRACK_TARGET_PERIODIC)
+        return fail("%s: unknown mode %d", __func__, mode);
+    if (mode == UAVTRACK_TARGET_POLYAK && !(tau > 0 && tau <= 1))
+        return fail("%s: tau = %g must lie in (0, 1]", __func__, tau);
+    if (mode == UAVTRACK_TARGET_PERIODIC && period < 1) return fail("%s: period = %lld < 1", __func__, (long long)period);
+    LearnerDevice &d = learner->d;
+    if (mode != UAVTRACK_TARGET_OFF && !d.target_mode) {
+        // off -> on: the block (once per handle), then a hard copy of the critic as it stands, stream-ordered
+        ON_DEVICE(learner->cfg.device_id);
+        if (!d.target) HIP_TRY(replace(target_bufs(d)));
+        HIP_TRY(hipMemcpyAsync(d.target, d.params + d.L.c_w1, sizeof(float) * (size_t)learner_critic_words(d.L),
+                               hipMemcpyDeviceToDevice, static_cast<hipStream_t>(stream)));
+    }
+    d.target_mode = mode;
+    d.target_tau = mode == UAVTRACK_TARGET_POLYAK ? (float)tau : 0.0f;
+    d.target_omt = 1.0f - d.target_tau;
+    d.target_period = mode == UAVTRACK_TARGET_PERIODIC ? period : 0;
+    learner->target_tau = mode == UAVTRACK_TARGET_POLYAK ? tau : 0.0;
+    return 0;
+}
+
+int uavtrack_learner_get_target(uavtrack_learner *learner, double out[3])
+{
+    if (!learner || !out) return fail("%s: null argument", __func__);
+    out[0] = learner->d.target_mode; out[1] = learner->target_tau; out[2] = (double)learner->d.target_period;
+    return 0;
+}
+
+int uavtrack_learner_sync_target(uavtrack_learner *learner, void *stream)
+{
+    if (!learner) return fail("%s: null handle", __func__);
+    const LearnerDevice &d = learner->d;
+    if (!d.target_mode) return fail("%s: no target critic is enabled (uavtrack_learner_set_target)", __func__);
+    ON_DEVICE(learner->cfg.device_id);
+    HIP_TRY(hipMemcpyAsync(d.target, d.params + d.L.c_w1, sizeof(float) * (size_t)learner_critic_words(d.L),
+                           hipMemcpyDeviceToDevice, static_cast<hipStream_t>(stream)));
+    return 0;
+}
+
+}  // extern "C"
+
+namespace {
+
+// uavtrack_learner_set_target_params / _get_target_params: P = const float (in from the host) or float (out to it)
+template <typename P>
+int target_params(const char *fn, uavtrack_learner *learner, P *params, int64_t n_floats, void *stream)
+{
+    if (!learner || !params) return fail("%s: null argument", fn);
+    const LearnerDevice &d = learner->d;
+    if (!d.target_mode) return fail("%s: no target critic is enabled (uavtrack_learner_set_target)", fn);
+    if (n_floats != learner_critic_words(d.L))
+        return fail("%s: %lld floats, the critic has %d", fn, (long long)n_floats, learner_critic_words(d.L));
+    ON_DEVICE(learner->cfg.device_id);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if constexpr (std::is_const<P>::value) {
+        HIP_TRY(hipStreamSynchronize(st));
+        HIP_TRY(hipMemcpyAsync(d.target, params, (size_t)n_floats * 4, hipMemcpyHostToDevice, st));
+    } else {
+        HIP_TRY(hipMemcpyAsync(params, d.target, (size_t)n_floats * 4, hipMemcpyDeviceToHost, st));
+    }
+    HIP_TRY(hipStreamSynchronize(st));
+    return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int uavtrack_learner_set_target_params(uavtrack_learner *learner, const float *params, int64_t n_floats, void *stream)
+{
+    return target_params(__func__, learner, params, n_floats, stream);
+}
+
+int uavtrack_learner_get_target_params(uavtrack_learner *learner, float *params, int64_t n_floats, void *stream)
+{
+    return target_params(__func__, learner, params, n_floats, stream);
+}
+
+int uavtrack_learner_values_target(uavtrack_learner *learner, int64_t n, const float *rows, float *values, void *stream)
+{
+    if (!learner) return fail("%s: null handle", __func__);
+    if (!rows || !values) return fail("%s: rows and values must not be null", __func__);
+    if (n < 1) return fail("%s: n = %lld < 1", __func__, (long long)n);
+    if (n > INT64_MAX / 48) return fail("%s: n = %lld rows overflow", __func__, (long long)n);
+    if (((uintptr_t)rows & 15) != 0) return fail("%s: rows must be 16-byte aligned", __func__);
+    if (!learner->d.target_mode) return fail("%s: no target critic is enabled (uavtrack_learner_set_target)", __func__);
+    ON_DEVICE(learner->cfg.device_id);
+    HIP_TRY(launch_learner_values(learner->d, true, n, rows, values, static_cast<hipStream_t>(stream)));
     return 0;
 }
 

@@ -63,6 +63,12 @@ struct LearnerDevice {
     float *gsum;                    // [P] the scaled gradient of a clipped update
     double *sq;                     // [learner_clip_groups][2] its workgroups' sums of squares: actor, critic
     float *coef;                    // [2] the clip coefficients
+    // the target critic (uavtrack_learner_set_target): host-side settings, read at enqueue
+    float *target;                  // [14 H + 1] the critic's block in torch order at offsets 0, 12 H, 13 H, 14 H; null
+                                    // until a target is first enabled, then kept for the handle's life
+    int target_mode;                // UAVTRACK_TARGET_OFF / _POLYAK / _PERIODIC
+    float target_tau, target_omt;   // Polyak: (float)tau and 1.0f - (float)tau
+    int64_t target_period;          // periodic: >= 1; 0 while Polyak
 };
 struct LearnerLaunch {
     int64_t n, capacity;
@@ -77,6 +83,7 @@ int learner_rows_per_tile(int hidden);
 size_t learner_lds_bytes(const LearnerLayout &L, int rows);
 int learner_groups(const LearnerLayout &L, int64_t n);
 int learner_clip_groups(const LearnerLayout &L);   // workgroups of the clip's gradient pass: ceil(P / 256)
+inline int learner_critic_words(const LearnerLayout &L) { return 14 * L.H + 1; }   // the critic's block, c_w1 .. P
 hipError_t learner_prepare_kernels(const LearnerLayout &L);
 hipError_t launch_learner_update(const LearnerDevice &d, const LearnerLaunch &q, hipStream_t stream);
 // the split update: gradient row [P + kLearnerRowTail] <- one batch; rows [count][P + kLearnerRowTail] -> both Adam steps;
@@ -87,7 +94,8 @@ hipError_t launch_learner_apply(const LearnerDevice &d, const float *rows, int c
 hipError_t launch_learner_priorities(const LearnerDevice &d, const int64_t *idx, int64_t n, int64_t capacity,
                                      const float *td, float *prio, hipStream_t stream);
 // uavtrack_learner_values: values[i] = V(rows[i]) with the critic as it stands when the launch executes, the chain of
-// the gradient kernel's V(s) to the bit; no scratch, any n >= 1
-hipError_t launch_learner_values(const LearnerDevice &d, int64_t n, const float *rows, float *values, hipStream_t stream);
+// the gradient kernel's V(s) to the bit; no scratch, any n >= 1.  target: with the target critic's block (d.target)
+hipError_t launch_learner_values(const LearnerDevice &d, bool target, int64_t n, const float *rows, float *values,
+                                 hipStream_t stream);
 
 }  // namespace uavtrack

@@ -41,6 +41,13 @@
 // workgroup's sums of squares in fp64, learner_clip_kernel adds them in workgroup order and writes both coefficients,
 // and the same Adam kernel then runs over (the scaled gradient, count 1, the coefficients as its scales).
 //
+// The target critic (uavtrack_learner_set_target, off by default): a second copy of the critic's 14 H + 1 words from which
+// V(s') alone is formed, y_i = r_i + d_i V_target(s'_i); V(s_i), both backward passes and everything behind delta are
+// unchanged.  learner_grad_target_kernel / learner_grad_reg_target_kernel are the same body with the layer-1 and layer-2
+// chains of V(s') over the other block (read from global memory, as the online weights are: no more LDS);
+// learner_target_kernel, behind the Adam kernel and gated on the same status word, moves the block towards the critic
+// (Polyak) or copies it every `period` steps of the device step counter.  While off, the launches are the ones above.
+//
 // The critic alone (uavtrack_learner_values): learner_values_kernel, at the end of the kernels below, evaluates V(x) of
 // any number of rows by the chain of the layer-1 and layer-2 loops above, to the bit, and touches no learner state.
 
@@ -75,10 +82,14 @@ struct GradArgs {
     float *entropy;                 // nullable [n]: H_i of batch row i, 0 for a row that was not used
     const float *discounts;         // nullable [capacity], slot order: the row's discount d in y = r + d V(s') (null: gamma);
                                     // status bit 3: a discount that is NaN, negative or above 1
+    const float *target;            // the target critic's block [14 H + 1] at its own offsets 0, 12 H, 13 H, 14 H
+                                    // (learner_grad_target_kernel / _reg_target_kernel only; null otherwise)
 };
 
 // kReg: the entropy term and the entropy[] store in the per-row block; everything else is one text.
-template <bool kReg>
+// kTgt: V(s') from the separate critic block a.target (the target critic) instead of the online critic; without it
+// W1t / b1t / W2t / b2t are the online critic's pointers at compile time.
+template <bool kReg, bool kTgt = false>
 __device__ __forceinline__ void learner_grad_body(const GradArgs &a)
 {
     extern __shared__ float lds[];
@@ -101,6 +112,8 @@ __device__ __forceinline__ void learner_grad_body(const GradArgs &a)
     const int tid = threadIdx.x;
     const float *W1a = a.params + L.a_w1, *b1a = a.params + L.a_b1, *W2a = a.params + L.a_w2, *b2a = a.params + L.a_b2;
     const float *W1c = a.params + L.c_w1, *b1c = a.params + L.c_b1, *W2c = a.params + L.c_w2, *b2c = a.params + L.c_b2;
+    const float *W1t = kTgt ? a.target : W1c, *b1t = kTgt ? a.target + 12 * H : b1c;
+    const float *W2t = kTgt ? a.target + 13 * H : W2c, *b2t = kTgt ? a.target + 14 * H : b2c;
 
     for (int p = tid; p < P; p += kLW) acc[p] = 0.0f;
     float loss_run[4] = {0.0f, 0.0f, 0.0f, 0.0f};   // thread 0's running sums, tile after tile
@@ -146,11 +159,11 @@ __device__ __forceinline__ void learner_grad_body(const GradArgs &a)
         // ---- layer 1 of the three forwards
         for (int e = tid; e < R * H; e += kLW) {
             const int r = e / H, j = e - r * H;
-            float pa = b1a[j], pc = b1c[j], pn = b1c[j];
+            float pa = b1a[j], pc = b1c[j], pn = b1t[j];
             for (int k = 0; k < 12; ++k) {
                 pa = fmaf(W1a[j * 12 + k], s[r * 12 + k], pa);
                 pc = fmaf(W1c[j * 12 + k], s[r * 12 + k], pc);
-                pn = fmaf(W1c[j * 12 + k], s2[r * 12 + k], pn);
+                pn = fmaf(W1t[j * 12 + k], s2[r * 12 + k], pn);
             }
             ha[e] = fmaxf(pa, 0.0f);
             hc[e] = fmaxf(pc, 0.0f);
@@ -164,8 +177,8 @@ __device__ __forceinline__ void learner_grad_body(const GradArgs &a)
         for (int e = tid; e < R * O; e += kLW) {
             const int r = e / O, o = e - r * O;
             const float *h = o < A ? ha + r * H : (o == A ? hc + r * H : hx + r * H);
-            const float *w = o < A ? W2a + o * H : W2c;
-            float z = o < A ? b2a[o] : b2c[0];
+            const float *w = o < A ? W2a + o * H : (o == A ? W2c : W2t);
+            float z = o < A ? b2a[o] : (o == A ? b2c[0] : b2t[0]);
             for (int j = 0; j < H; ++j) z = fmaf(w[j], h[j], z);
             if (o < A) gz[r * A + o] = z;
             else if (o == A) gv[r] = z;
@@ -313,6 +326,10 @@ __global__ void __launch_bounds__(kLW) learner_grad_kernel(GradArgs a) { learner
 // launched instead of learner_grad_kernel while entropy_coef != 0 or an entropy[] buffer is installed
 __global__ void __launch_bounds__(kLW) learner_grad_reg_kernel(GradArgs a) { learner_grad_body<true>(a); }
 
+// the same two while a target critic is enabled (uavtrack_learner_set_target): V(s') over a.target
+__global__ void __launch_bounds__(kLW) learner_grad_target_kernel(GradArgs a) { learner_grad_body<false, true>(a); }
+__global__ void __launch_bounds__(kLW) learner_grad_reg_target_kernel(GradArgs a) { learner_grad_body<true, true>(a); }
+
 // Clears the update's status word (a kernel node rather than a memset node, so a captured update is a chain of kernels)
 __global__ void learner_begin_kernel(int *status)
 {
@@ -375,6 +392,20 @@ __global__ void learner_adam_kernel(float *params, float *m, float *v, const flo
     const bool actor = p < L.c_w1;
     const float g = ordered_sum(src, count, stride, p) * (actor ? scal[0] : scal[1]);
     adam_element(params[p], m[p], v[p], g, steps[L.tensor_of(p)], actor ? actor_lr : critic_lr);
+}
+
+// The target critic's sync rule (uavtrack_learner_set_target), behind the Adam kernel of a closed update or an apply and
+// gated on the same status word: one thread per word of the critic's block.  Polyak (period == 0):
+// t <- fl(fl(omt * t) + fl(tau * w)), each operation rounded on its own (no contraction), tau and omt = 1.0f - tau formed
+// on the host.  Periodic (period >= 1): t <- w when the critic's fc1.weight step count, which the finalize kernel has
+// already advanced, is a multiple of period.  A refused update leaves the block alone.
+__global__ void learner_target_kernel(float *target, const float *critic, int words, const int *status,
+                                      const int64_t *steps, float tau, float omt, int64_t period)
+{
+    const int p = blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= words || *status) return;
+    if (period == 0) target[p] = __fadd_rn(__fmul_rn(omt, target[p]), __fmul_rn(tau, critic[p]));
+    else if (steps[4] % period == 0) target[p] = critic[p];
 }
 
 // ---- gradient-norm clipping (torch.nn.utils.clip_grad_norm_, one max_norm per network), between "scale" and "Adam".
@@ -515,17 +546,18 @@ __device__ __forceinline__ void load_row(float (&x)[12], const float *src)
     x[8] = c.x; x[9] = c.y; x[10] = c.z; x[11] = c.w;
 }
 
-__global__ void __launch_bounds__(kVW) learner_values_kernel(const float *params, LearnerLayout L, int64_t n,
+// `critic` is a critic block [14 H + 1] in torch order: the online critic inside the parameter blob, or the target critic.
+__global__ void __launch_bounds__(kVW) learner_values_kernel(const float *critic, int H, int64_t n,
                                                              const float *rows, float *values)
 {
     __shared__ __attribute__((aligned(16))) float rec[kLearnerMaxHidden * kVRec];
-    const int tid = threadIdx.x, H = L.H;
-    const float *W1c = params + L.c_w1, *b1c = params + L.c_b1, *W2c = params + L.c_w2;
+    const int tid = threadIdx.x;
+    const float *W1c = critic, *b1c = critic + 12 * H, *W2c = critic + 13 * H;
     for (int e = tid; e < H * kVRec; e += kVW) {
         const int j = e / kVRec, k = e - j * kVRec;
         rec[e] = k < 12 ? W1c[j * 12 + k] : (k == 12 ? b1c[j] : (k == 13 ? W2c[j] : 0.0f));
     }
-    const float b2 = params[L.c_b2];
+    const float b2 = critic[14 * H];
     __syncthreads();
     const int64_t chunk = 2 * kVW;
     for (int64_t base = (int64_t)blockIdx.x * chunk; base < n; base += (int64_t)gridDim.x * chunk) {
@@ -557,12 +589,14 @@ __global__ void __launch_bounds__(kVW) learner_values_kernel(const float *params
 
 }  // namespace
 
-hipError_t launch_learner_values(const LearnerDevice &d, int64_t n, const float *rows, float *values, hipStream_t st)
+hipError_t launch_learner_values(const LearnerDevice &d, bool target, int64_t n, const float *rows, float *values,
+                                 hipStream_t st)
 {
     static_assert(kLearnerMaxHidden * kVRec * sizeof(float) <= 64 * 1024, "the critic's records fit static LDS");
     int64_t blocks = (n + 2 * kVW - 1) / (2 * kVW);
     if (blocks > 2048) blocks = 2048;
-    hipLaunchKernelGGL(learner_values_kernel, dim3((unsigned)blocks), dim3(kVW), 0, st, d.params, d.L, n, rows, values);
+    hipLaunchKernelGGL(learner_values_kernel, dim3((unsigned)blocks), dim3(kVW), 0, st,
+                       target ? d.target : d.params + d.L.c_w1, d.L.H, n, rows, values);
     return hipGetLastError();
 }
 
@@ -588,12 +622,16 @@ int learner_clip_groups(const LearnerLayout &L) { return (L.P + kClipThreads - 1
 
 hipError_t learner_prepare_kernels(const LearnerLayout &L)
 {
+    // every instantiation of the gradient body needs the attribute of its own: up to about 131 KB at H = 256
     const size_t lds = learner_lds_bytes(L, learner_rows_per_tile(L.H));
-    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(learner_grad_kernel),
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-    return hipFuncSetAttribute(reinterpret_cast<const void *>(learner_grad_reg_kernel),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    for (const void *k : {reinterpret_cast<const void *>(learner_grad_kernel),
+                          reinterpret_cast<const void *>(learner_grad_reg_kernel),
+                          reinterpret_cast<const void *>(learner_grad_target_kernel),
+                          reinterpret_cast<const void *>(learner_grad_reg_target_kernel)}) {
+        const hipError_t e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
 }
 
 namespace {
@@ -612,10 +650,11 @@ hipError_t launch_grad(const LearnerDevice &d, const LearnerLaunch &q, float *td
     a.partials = d.partials; a.td_delta = td; a.status = status;
     a.L = L; a.rows = R; a.gamma = d.gamma; a.per_sample = d.per_sample;
     a.entropy_coef = d.entropy_coef; a.entropy = d.entropy; a.discounts = q.discounts;
-    if (d.entropy_coef != 0.0f || d.entropy)
-        hipLaunchKernelGGL(learner_grad_reg_kernel, dim3(learner_groups(L, q.n)), dim3(kLW), learner_lds_bytes(L, R), st, a);
-    else
-        hipLaunchKernelGGL(learner_grad_kernel, dim3(learner_groups(L, q.n)), dim3(kLW), learner_lds_bytes(L, R), st, a);
+    a.target = d.target_mode ? d.target : nullptr;
+    const bool reg = d.entropy_coef != 0.0f || d.entropy;
+    auto *kernel = a.target ? (reg ? learner_grad_reg_target_kernel : learner_grad_target_kernel)
+                            : (reg ? learner_grad_reg_kernel : learner_grad_kernel);
+    hipLaunchKernelGGL(kernel, dim3(learner_groups(L, q.n)), dim3(kLW), learner_lds_bytes(L, R), st, a);
     return hipGetLastError();
 }
 
@@ -645,6 +684,11 @@ hipError_t launch_scale_adam(const LearnerDevice &d, const float *src, int count
     }
     hipLaunchKernelGGL(learner_adam_kernel, dim3((L.P + 255) / 256), dim3(256), 0, st, d.params, d.opt.m, d.opt.v, src,
                        count, stride, L, d.opt.status, d.opt.steps, scal, d.actor_lr, d.critic_lr);
+    if ((e = hipGetLastError()) != hipSuccess || !d.target_mode) return e;
+    // the target critic's sync rule, once per successful update or apply (period 0: Polyak)
+    const int words = learner_critic_words(L);
+    hipLaunchKernelGGL(learner_target_kernel, dim3((words + 255) / 256), dim3(256), 0, st, d.target, d.params + L.c_w1,
+                       words, d.opt.status, d.opt.steps, d.target_tau, d.target_omt, d.target_period);
     return hipGetLastError();
 }
 

@@ -108,7 +108,8 @@ PMI_TRAIN_TENSORS = 18                                    # PMINetwork.parameter
 PMI_MAX_SOURCES = 64                                      # UAVTRACK_PMI_MAX_SOURCES
 PMI_BN_LAYERS = 4                                         # BatchNorm1d layers (num_batches_tracked entries)
 LOSS_FORMS = ("reference", "per_sample")                  # enum uavtrack_actor_loss
-LEARNER_ROW_TAIL = 8                                      # words behind the P gradient sums of a gradient row
+TARGET_OFF, TARGET_POLYAK, TARGET_PERIODIC = 0, 1, 2       # enum uavtrack_target_mode
+LEARNER_ROW_TAIL = 8                                     # words behind the P gradient sums of a gradient row
 LEARNER_MAX_ROWS = 64                                     # UAVTRACK_LEARNER_MAX_ROWS
 REPLAY_MAX_NSTEP = 64                                     # UAVTRACK_REPLAY_MAX_NSTEP
 LEARNER_TENSORS = 8                                       # parameter tensors: actor fc1.w fc1.b fc2.w fc2.b, critic likewise
@@ -180,6 +181,12 @@ SIGNATURES = {
     "uavtrack_learner_grad_discounted": (C.c_int, [C.c_void_p, C.c_int64] + [C.c_void_p] * 4 + [C.c_int64]
                                          + [C.c_void_p] * 6),
     "uavtrack_learner_values": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "uavtrack_learner_set_target": (C.c_int, [C.c_void_p, C.c_int32, C.c_double, C.c_int64, C.c_void_p]),
+    "uavtrack_learner_get_target": (C.c_int, [C.c_void_p, C.POINTER(C.c_double)]),
+    "uavtrack_learner_sync_target": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "uavtrack_learner_set_target_params": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
+    "uavtrack_learner_get_target_params": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
+    "uavtrack_learner_values_target": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
     "uavtrack_learner_log_probs": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64] + [C.c_void_p] * 3),
     "uavtrack_learner_log_probs_window": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64,
                                                     C.c_void_p, C.c_void_p]),

@@ -54,6 +54,15 @@ batch at R >= 1 trains with the unweighted update's bits.  log_probs(states, act
 The critic alone (values(states), uavtrack_learner_values): V(s) of any number of rows with the parameters as they stand
 when the launch runs, bit for bit the V(s) an update forms.  A lambda ring (ring.with_lambda(lam, gamma)) takes it as
 add_rollout(..., critic=learner) to fold a rollout's rewards with its values into lambda-returns.
+
+The target critic (set_target(tau=) or set_target(period=), uavtrack_learner_set_target; off by default, and then every
+call is bit for bit what it was): a second copy theta- of the critic's 14 H + 1 words from which V(s') alone is formed,
+y_i = r_i + d_i V_theta-(s'_i), inside the same gradient kernel.  After every successful update or apply theta- moves by
+t <- (1 - tau) t + tau w in float32 (two multiplies and an add, each rounded on its own), or is copied from the critic
+whenever the critic's device step count is a multiple of period; a refused update leaves it alone.  grad_from bootstraps
+from it and apply runs the sync rule; gradient rows carry no settings, so learners that share an update must hold equal
+settings and theta- (sharding.pack_learner_state / unpack_learner_state carry both).  learner.target.values(states) is
+V of theta-; state_dict / save carry theta- and the settings while a target is enabled.
 """
 from __future__ import annotations
 
@@ -175,6 +184,80 @@ class DeviceActorCritic(Handle):
             raise RuntimeError("entropy: call enable_diagnostics() first")
         return self._entropy[:int(n)]
 
+    # ---- the target critic
+    def set_target(self, tau: Optional[float] = None, period: Optional[int] = None) -> None:
+        """Bootstrap from a target critic theta-: tau in (0, 1] keeps it by Polyak averaging
+        (t <- (1 - tau) t + tau w in float32 after every successful update or apply), period >= 1 copies the critic
+        whenever its device step count is a multiple of period; exactly one of the two, or neither to turn it off.
+        Enabling hard-copies the current critic (stream-ordered; it allocates once, so not inside a graph capture);
+        changing tau, period or the rule while enabled keeps theta-.  Host-side settings like set_regularisation: they
+        hold for every update, grad_from and apply enqueued afterwards, and a captured graph keeps the ones it was
+        captured with.  Both arguments given, or a bad value, raise ValueError before any library call."""
+        if tau is not None and period is not None:
+            raise ValueError("set_target: tau (Polyak) or period (periodic copy), not both")
+        mode, t, k = _lib.TARGET_OFF, 0.0, 0
+        if tau is not None:
+            mode, t = _lib.TARGET_POLYAK, float(tau)
+            if not 0.0 < t <= 1.0:                                    # NaN fails both comparisons
+                raise ValueError(f"set_target: tau = {tau!r} must lie in (0, 1]")
+        elif period is not None:
+            if isinstance(period, bool) or int(period) != period or int(period) < 1:
+                raise ValueError(f"set_target: period = {period!r} must be an integer >= 1")
+            mode, k = _lib.TARGET_PERIODIC, int(period)
+        _lib.check(self._lib.uavtrack_learner_set_target(self._h, mode, t, k, self._stream()), "uavtrack_learner_set_target")
+
+    def get_target(self) -> dict:
+        """{"tau": float or None, "period": int or None} as last set (set_target(**get_target()) sets the same); both
+        None while no target is enabled."""
+        out = (C.c_double * 3)()
+        _lib.check(self._lib.uavtrack_learner_get_target(self._h, out), "uavtrack_learner_get_target")
+        mode = int(out[0])
+        return {"tau": float(out[1]) if mode == _lib.TARGET_POLYAK else None,
+                "period": int(out[2]) if mode == _lib.TARGET_PERIODIC else None}
+
+    def _target_on(self) -> bool:
+        return any(v is not None for v in self.get_target().values())
+
+    def sync_target(self) -> None:
+        """theta- <- the critic as it stands when the copy runs: stream-ordered, capturable; an error while off."""
+        _lib.check(self._lib.uavtrack_learner_sync_target(self._h, self._stream()), "uavtrack_learner_sync_target")
+
+    def _set_target_params(self, flat: np.ndarray) -> None:
+        """theta- from a float32 blob of 14 H + 1 words in the critic's torch order; an error while off."""
+        flat = np.ascontiguousarray(flat, np.float32)
+        _lib.check(self._lib.uavtrack_learner_set_target_params(self._h, host_ptr(flat), flat.size, self._stream()),
+                   "uavtrack_learner_set_target_params")
+
+    def _get_target_params(self) -> np.ndarray:
+        flat = np.empty(14 * self.hidden_dim + 1, np.float32)
+        _lib.check(self._lib.uavtrack_learner_get_target_params(self._h, host_ptr(flat), flat.size, self._stream()),
+                   "uavtrack_learner_get_target_params")
+        return flat
+
+    def target_state_dict(self) -> "OrderedDict[str, torch.Tensor]":
+        """theta- as FnnValueNet's state_dict (CPU fp32); an error while off."""
+        names, params = zip(*self._critic.named_parameters())
+        return OrderedDict(zip(names, split(self._get_target_params(), params)))
+
+    @property
+    def target(self) -> "_TargetCritic":
+        """The target critic as something with .values(states, out=None): what a lambda ring's
+        add_rollout(..., critic=learner.target) folds its returns with."""
+        return _TargetCritic(self)
+
+    def _restore_target(self, settings: Optional[dict], target_sd: Optional[dict]) -> None:
+        """Behind a checkpoint load: the checkpoint's settings where it has them, then theta- from the checkpoint's
+        copy, or -- while a target is enabled and the checkpoint has none -- a hard sync to the loaded critic."""
+        if settings is not None:
+            self.set_target(**settings)
+        if not self._target_on():
+            return
+        if target_sd is None:
+            return self.sync_target()
+        probe = ValueMLP(_lib.OBS_DIM, self.hidden_dim)
+        probe.load_state_dict(target_sd)                              # torch checks keys and shapes
+        self._set_target_params(flat(list(probe.parameters())))
+
     def _params(self):
         return list(self._actor.parameters()) + list(self._critic.parameters())
 
@@ -224,11 +307,14 @@ class DeviceActorCritic(Handle):
         stand when the launch runs (uavtrack_learner_values): a float32 tensor of the leading shape, bit for bit the V(s)
         an update with the same parameters forms.  `out` (float32, contiguous, that many elements, same device) is
         written in place and returned.  No synchronisation, no limit from max_batch, no change to the learner."""
+        return self._values("uavtrack_learner_values", states, out)
+
+    def _values(self, entry: str, states: torch.Tensor, out: Optional[torch.Tensor]) -> torch.Tensor:
+        """values() through uavtrack_learner_values or, for the target critic, uavtrack_learner_values_target."""
         n = self._rows_arg("values", states)
         out = self._out_arg("values", out, states, n)
         if n:
-            _lib.check(self._lib.uavtrack_learner_values(self._h, n, _ptr(states), _ptr(out), self._stream()),
-                       "uavtrack_learner_values")
+            _lib.check(getattr(self._lib, entry)(self._h, n, _ptr(states), _ptr(out), self._stream()), entry)
         return out
 
     def log_probs(self, states: torch.Tensor, actions: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -542,26 +628,39 @@ class DeviceActorCritic(Handle):
         self._set_params(flat(cur))
 
     def state_dict(self) -> dict:
+        """The four reference entries; while a target critic is enabled also "target_critic" (theta-, FnnValueNet's
+        format) and "target" (its settings, as get_target returns them)."""
         a_opt, c_opt = self._adam_state_dicts()
-        return {"actor": self.actor_state_dict(), "critic": self.critic_state_dict(),
-                "actor_optimizer": a_opt, "critic_optimizer": c_opt}
+        sd = {"actor": self.actor_state_dict(), "critic": self.critic_state_dict(),
+              "actor_optimizer": a_opt, "critic_optimizer": c_opt}
+        if self._target_on():
+            sd["target_critic"], sd["target"] = self.target_state_dict(), self.get_target()
+        return sd
 
     def load_state_dict(self, sd: dict) -> None:
+        """state_dict's inverse.  "target" enables the target critic as saved and "target_critic" restores theta-; a
+        learner with a target enabled that loads a checkpoint without one hard-syncs theta- to the loaded critic."""
         self._load_module(sd.get("actor"), sd.get("critic"))
         self._load_adam(sd.get("actor_optimizer"), sd.get("critic_optimizer"))
+        self._restore_target(sd.get("target"), sd.get("target_critic"))
 
     def save(self, save_dir: str, epoch_i) -> None:
         """ActorCritic.save (actor_critic.py:181-190): <save_dir>/actor/actor_weights_<epoch>.pth and
-        <save_dir>/critic/critic_weights_<epoch>.pth, each {'model_state_dict', 'optimizer_state_dict'}."""
+        <save_dir>/critic/critic_weights_<epoch>.pth, each {'model_state_dict', 'optimizer_state_dict'}; while a target
+        critic is enabled the critic file also holds 'target_state_dict' and 'target' (the settings)."""
         a_opt, c_opt = self._adam_state_dicts()
-        for sub, model, opt in (("actor", self.actor_state_dict(), a_opt), ("critic", self.critic_state_dict(), c_opt)):
+        extra = {"target_state_dict": self.target_state_dict(), "target": self.get_target()} if self._target_on() else {}
+        for sub, model, opt, more in (("actor", self.actor_state_dict(), a_opt, {}),
+                                      ("critic", self.critic_state_dict(), c_opt, extra)):
             os.makedirs(os.path.join(save_dir, sub), exist_ok=True)
-            torch.save({"model_state_dict": model, "optimizer_state_dict": opt},
+            torch.save({"model_state_dict": model, "optimizer_state_dict": opt, **more},
                        os.path.join(save_dir, sub, f"{sub}_weights_{epoch_i}.pth"))
 
     def load(self, actor_path: Optional[str], critic_path: Optional[str]) -> None:
         """ActorCritic.load (actor_critic.py:192-205): each checkpoint that exists replaces that network's weights
-        and Adam state.  (The learning rates stay the ones this learner was built with.)"""
+        and Adam state.  (The learning rates stay the ones this learner was built with.)  A critic file with a
+        'target_state_dict' restores the target critic as load_state_dict does; without one, an enabled target is
+        hard-synced to the loaded critic."""
         ck = {}
         for key, path in (("actor", actor_path), ("critic", critic_path)):
             if path and os.path.exists(path):
@@ -570,3 +669,16 @@ class DeviceActorCritic(Handle):
                           ck["critic"]["model_state_dict"] if "critic" in ck else None)
         self._load_adam(ck["actor"]["optimizer_state_dict"] if "actor" in ck else None,
                         ck["critic"]["optimizer_state_dict"] if "critic" in ck else None)
+        self._restore_target(ck.get("critic", {}).get("target"), ck.get("critic", {}).get("target_state_dict"))
+
+
+class _TargetCritic:
+    """DeviceActorCritic.target: the target critic's values, for whoever takes a `critic` with .values()."""
+
+    def __init__(self, learner: DeviceActorCritic):
+        self._learner = learner
+
+    def values(self, states: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """DeviceActorCritic.values with theta- in the critic's place (uavtrack_learner_values_target): bit for bit the
+        V(s') an update bootstraps from.  An error while no target is enabled."""
+        return self._learner._values("uavtrack_learner_values_target", states, out)

@@ -201,32 +201,60 @@ def gather_learner_rows(row, group=None):
     return out.to(dev).view(torch.float32)
 
 
-def broadcast_learner(learner, group=None, src: int = 0) -> None:
-    """Rank `src`'s parameters, Adam moments, step counts and regularisation settings (entropy_coef and the two max
-    norms) to every rank of `group` (src is a global rank), so that the ranks' learners start equal.  Gradient rows carry
-    no settings, so ranks that share updates must hold equal ones: change them on every rank alike afterwards, or
-    broadcast again.  Synchronises; meant for start-up and checkpoint loads, not the training loop."""
+def pack_learner_state(learner):
+    """Everything that makes two learners update alike, as one int32 numpy block of a length that depends on the shapes
+    alone: the parameters and both Adam moments as bit views [3 P], the step counts [8 int64], the regularisation
+    settings (entropy_coef and the two max norms) and the target settings (tau or NaN, period or 0) as float64 bit views,
+    then the target critic's 14 H + 1 words (zeros while no target is enabled)."""
     import numpy as np
+    m, v, steps = learner._optim_state()
+    tgt = learner.get_target()
+    on = tgt["tau"] is not None or tgt["period"] is not None
+    settings = np.array([float("nan") if tgt["tau"] is None else tgt["tau"], tgt["period"] or 0], np.float64)
+    theta = learner._get_target_params() if on else np.zeros(14 * learner.hidden_dim + 1, np.float32)
+    return np.concatenate([learner._get_params().view(np.int32), m.view(np.int32), v.view(np.int32),
+                           np.ascontiguousarray(steps, np.int64).view(np.int32),
+                           np.array(learner.get_regularisation(), np.float64).view(np.int32), settings.view(np.int32),
+                           np.ascontiguousarray(theta, np.float32).view(np.int32)])
+
+
+def unpack_learner_state(learner, blk) -> None:
+    """pack_learner_state's inverse into a learner of the same shapes: afterwards it updates bit for bit like the one
+    that was packed.  A block without a target turns this learner's target off."""
+    import numpy as np
+
+    def f32(a):
+        return np.ascontiguousarray(a).view(np.float32)
+    P, T = learner.num_params, 14 * learner.hidden_dim + 1
+    blk = np.ascontiguousarray(blk, np.int32)
+    if blk.size != 3 * P + 16 + 6 + 4 + T:
+        raise ValueError(f"unpack_learner_state: a block of {blk.size} words, this learner's has {3 * P + 26 + T}")
+    learner._set_params(f32(blk[:P]))
+    steps, rest = blk[3 * P:3 * P + 16], blk[3 * P + 16:]
+    learner._set_optim_state(f32(blk[P:2 * P]), f32(blk[2 * P:3 * P]), np.ascontiguousarray(steps).view(np.int64))
+    c, a_max, c_max, tau, period = np.ascontiguousarray(rest[:10]).view(np.float64)
+    learner.set_regularisation(float(c), (float(a_max), float(c_max)))
+    learner.set_target(tau=None if np.isnan(tau) else float(tau), period=int(period) or None)
+    if not np.isnan(tau) or period:
+        learner._set_target_params(f32(rest[10:]))
+
+
+def broadcast_learner(learner, group=None, src: int = 0) -> None:
+    """Rank `src`'s parameters, Adam moments, step counts, regularisation settings (entropy_coef and the two max norms)
+    and target critic (its settings and, where enabled, its parameters) to every rank of `group` (src is a global
+    rank), so that the ranks' learners start equal: pack_learner_state on every rank, one broadcast,
+    unpack_learner_state.  Gradient rows carry no settings, so ranks that share updates must hold equal ones: change
+    them on every rank alike afterwards, or broadcast again.  Synchronises; meant for start-up and checkpoint loads, not
+    the training loop."""
     import torch
     import torch.distributed as dist
     if not (dist.is_available() and dist.is_initialized()) or dist.get_world_size(group) == 1:
         return
-    m, v, steps = learner._optim_state()
-    # one int32 block: the three float blobs as bit views, then the step counts
-    blk = torch.from_numpy(np.concatenate([learner._get_params().view(np.int32), m.view(np.int32), v.view(np.int32),
-                                           np.ascontiguousarray(steps, np.int64).view(np.int32),
-                                           np.array(learner.get_regularisation(), np.float64).view(np.int32)]))
+    blk = torch.from_numpy(pack_learner_state(learner))
     if dist.get_backend(group) != "gloo":
         blk = blk.to(learner.device)
     dist.broadcast(blk, src=src, group=group)
-    blk = blk.cpu().numpy()
-    P = learner.num_params
-    learner._set_params(np.ascontiguousarray(blk[:P]).view(np.float32))
-    learner._set_optim_state(np.ascontiguousarray(blk[P:2 * P]).view(np.float32),
-                              np.ascontiguousarray(blk[2 * P:3 * P]).view(np.float32),
-                              np.ascontiguousarray(blk[3 * P:-6]).view(np.int64))
-    c, a_max, c_max = np.ascontiguousarray(blk[-6:]).view(np.float64)
-    learner.set_regularisation(float(c), (float(a_max), float(c_max)))
+    unpack_learner_state(learner, blk.cpu().numpy())
 
 
 # ---------------------------------------------------------------------------------------------------------------------

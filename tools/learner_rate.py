@@ -10,10 +10,16 @@ softmax, losses and Adam are not counted.
 
     python tools/learner_rate.py [--quick]
     python tools/learner_rate.py --regularised [--quick]
+    python tools/learner_rate.py --target [--quick]
 
 --regularised times the device update alone (loss="per_sample") under four settings of
 DeviceActorCritic.set_regularisation: everything off, the entropy bonus on, clipping on, both.  "off" enqueues the
 launches of the plain update; the clip adds two small launches and one more pass over P floats.
+
+--target times the device update alone (loss="per_sample") under three settings of DeviceActorCritic.set_target: no
+target, Polyak (tau = 0.005) and periodic (period = 100).  "off" enqueues the launches of the plain update; a target
+swaps the gradient kernel for the instantiation that forms V(s') over the second critic block and adds one small
+launch over 14 H + 1 words behind the Adam kernel.
 """
 import argparse
 import json
@@ -58,19 +64,25 @@ def make_batch(n, A, dev):
             "next_states": torch.rand(n, 12, device=dev, generator=g) * 2 - 1}
 
 
-# --regularised: (name, entropy_coef, max_grad_norm); 1e-3 is far below the gradient norms of this batch, so both
-# networks are clipped (the clip chain costs the same whether it clips or not)
-SETTINGS = (("off", 0.0, None), ("entropy", 0.01, None), ("clip", 0.0, 1e-3), ("both", 0.01, 1e-3))
+# The settings sweeps: name -> what it does to a fresh learner (None: nothing, so that "off" makes no call an older build of
+# the library lacks).  --regularised: 1e-3 is far below the gradient norms of this batch, so both networks are clipped (the
+# clip chain costs the same whether it clips or not).
+SWEEPS = {
+    "regularised": (("off", None), ("entropy", lambda L: L.set_regularisation(0.01, None)),
+                    ("clip", lambda L: L.set_regularisation(0.0, 1e-3)), ("both", lambda L: L.set_regularisation(0.01, 1e-3))),
+    "target": (("off", None), ("polyak", lambda L: L.set_target(tau=0.005)), ("periodic", lambda L: L.set_target(period=100))),
+}
 
 
-def regularised(args, grid, dev, A):
+def sweep(args, grid, dev, A, settings):
+    """The device update alone (loss="per_sample") under each setting: one JSON line per configuration."""
     for n, H in grid:
         store = {k: v.contiguous() for k, v in make_batch(n, A, dev).items()}
         out = {"n": n, "H": H, "A": A, "loss": "per_sample"}
-        for name, c, mgn in SETTINGS:
+        for name, apply in settings:
             L = uavtrack.DeviceActorCritic(12, H, A, 1e-4, 5e-4, 0.95, dev, loss="per_sample", max_batch=n)
-            if name != "off":                 # "off" makes no call an older build of the library lacks
-                L.set_regularisation(c, mgn)
+            if apply is not None:
+                apply(L)
 
             def dstep():
                 L._run(n, store, n, None, None)
@@ -90,18 +102,20 @@ def main():
     ap.add_argument("--quick", action="store_true", help="n 65536, H 128 only")
     ap.add_argument("--regularised", action="store_true",
                     help="time the device update with the entropy bonus and the gradient-norm clip off / on")
-    ap.add_argument("--settings", default=None, help="--regularised: a comma-separated subset of off,entropy,clip,both")
+    ap.add_argument("--target", action="store_true",
+                    help="time the device update without a target critic, with Polyak averaging and with a periodic copy")
+    ap.add_argument("--settings", default=None, help="--regularised: a comma-separated subset of off,entropy,clip,both; "
+                                                     "--target: of off,polyak,periodic")
     ap.add_argument("--reps", type=int, default=100)
     ap.add_argument("--runs", type=int, default=5)
     args = ap.parse_args()
     dev = "cuda:0"
     A = 12
     grid = [(65536, 128)] if args.quick else [(n, H) for H in (64, 128, 256) for n in (4096, 65536, 262144)]
-    if args.regularised:
-        if args.settings:
-            global SETTINGS
-            SETTINGS = tuple(x for x in SETTINGS if x[0] in args.settings.split(","))
-        return regularised(args, grid, dev, A)
+    for which in ("regularised", "target"):
+        if getattr(args, which):
+            names = args.settings.split(",") if args.settings else [name for name, _ in SWEEPS[which]]
+            return sweep(args, grid, dev, A, [x for x in SWEEPS[which] if x[0] in names])
     for n, H in grid:
         batch = make_batch(n, A, dev)
         actor, critic = uavtrack.ActorMLP(12, H, A).to(dev), ValueNet(12, H).to(dev)
