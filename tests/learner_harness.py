@@ -6,7 +6,9 @@ until a function that needs it is called.
 The bounds (a single update from zero moments against tests/learner_mirror.py): td_delta and the losses within 2e-5 of
 their magnitude scale; the gradient (exp_avg / 0.1 after one step) within tol_g, 2e-6 (1 + log2 n) of its largest element;
 the parameters within 1e-3 * lr, except where the fp64 gradient is within the gradient's rounding of 0 (then Adam's
-first step, lr * g / (|g| + eps), may take either sign: within 2 lr).  tests/test_learner_harness_cpu.py pins them."""
+first step, lr * g / (|g| + eps), may take either sign: within 2 lr).  tests/test_learner_harness_cpu.py pins them.
+tol_g is a whole-blob bound (one max |g| over the actor and the critic together); the element-wise one, every element
+against the sum of its own absolute terms, lives in tests/learner_gradient_cases.py and test_hip_learner_gradients.py."""
 import types
 
 import numpy as np
