@@ -17,6 +17,7 @@ update is the same rule on a sampled batch, and the new actor weights are re-upl
     python examples/train_maac.py --replay prioritized --learner device --n-step 3                        # 3-step returns folded by the ring's add
     python examples/train_maac.py --replay prioritized --learner device --td-lambda 0.9                   # lambda-returns: critic values + a backward scan in the ring's add
     python examples/train_maac.py --replay prioritized --learner device --rho-bar 1.0 --publish device --log-every 10   # truncated importance ratios: who acted
+    python examples/train_maac.py --replay prioritized --learner device --actor-loss per_sample --ppo-clip 0.2   # ... or PPO's clipped surrogate from the same store
     python examples/train_maac.py --replay prioritized --learner device --target-tau 0.005                # bootstrap from a Polyak-averaged target critic
     python examples/train_maac.py --replay prioritized --learner device --target-period 100 --td-lambda 0.9   # ... or a periodic copy; the lambda add folds with it too
     python examples/train_maac.py --method maac-r --pmi-trainer device --learner device --replay prioritized --publish device --log-every 10
@@ -63,7 +64,7 @@ class ValueNet(torch.nn.Module):
 
 
 def update(actor, critic, opt_a, opt_c, batch, gamma, weights=None, entropy_coef=0.0, max_grad_norm=None, diag=None,
-           rho_bar=None, rho_stats=None, target_critic=None):
+           rho_bar=None, rho_stats=None, target_critic=None, ppo_clip=None):
     """One ActorCritic.update step (actor_critic.py:150-178) on a batch of transitions.  weights (--importance): the
     draw's importance weights, one per row, multiplied into the per-sample losses before the mean.  entropy_coef and
     max_grad_norm: the two terms of DeviceActorCritic.set_regularisation, so that --learner torch and --learner device
@@ -72,6 +73,9 @@ def update(actor, critic, opt_a, opt_c, batch, gamma, weights=None, entropy_coef
     from a lambda ring (--td-lambda), whose rewards and discounts make that target the lambda-return.  rho_bar (--rho-bar):
     the batch carries "log_mu" and every row's losses are multiplied by min(rho_bar, pi / mu), a constant of the
     differentiation, as DeviceActorCritic.update_from(rho_bar=) does; rho_stats (a dict) receives the ratios.
+    ppo_clip (--ppo-clip EPS): the batch carries "log_mu" and the policy term of a row becomes
+    -min(r A, clamp(r, 1 - EPS, 1 + EPS) A) with r = pi / mu differentiated through and A = td_delta, as
+    DeviceActorCritic.update_from(clip_eps=) trains; rho_stats receives the ratios.
     target_critic (--target-tau / --target-period): the copy of the critic that V(s') comes from; keeping it in step
     is the caller's (sync_target_critic)."""
     s, a, r, s2 = batch["states"], batch["actions"].long().unsqueeze(1), batch["rewards"], batch["next_states"]
@@ -85,6 +89,11 @@ def update(actor, critic, opt_a, opt_c, batch, gamma, weights=None, entropy_coef
     probs = actor(s)
     log_probs = torch.log(probs.gather(1, a).squeeze(1).clamp_min(1e-12))
     per_row = -log_probs * td_delta.detach()
+    if ppo_clip is not None:
+        r, adv = torch.exp(log_probs - batch["log_mu"]), td_delta.detach()
+        per_row = -torch.min(r * adv, r.clamp(1 - ppo_clip, 1 + ppo_clip) * adv)
+        if rho_stats is not None:
+            rho_stats["rho"] = r.detach()
     if rho_bar is not None:
         rho = torch.exp(log_probs.detach() - batch["log_mu"]).clamp(max=rho_bar)
         weights = rho if weights is None else weights * rho
@@ -163,15 +172,21 @@ def nstep_ring(args, ring):
     return ring.with_nstep(args.n_step, args.gamma) if args.n_step > 1 else ring
 
 
+def behavioural(args):
+    """--rho-bar or --ppo-clip: the two corrections for who acted, which both read the behaviour log-probabilities."""
+    return args.rho_bar is not None or args.ppo_clip is not None
+
+
 def behaviour_ring(args, ring):
-    """--rho-bar: the ring keeps the behaviour log-probability of every slot (with_behaviour)."""
-    return ring if args.rho_bar is None else ring.with_behaviour()
+    """--rho-bar / --ppo-clip: the ring keeps the behaviour log-probability of every slot (with_behaviour)."""
+    return ring.with_behaviour() if behavioural(args) else ring
 
 
 def add_rollout(args, ring, obs_in, res, acted, critic):
-    """The rollout's outputs into the ring, before the iteration's updates.  --rho-bar: with the log-probabilities of
-    `acted` -- the device learner, or the PyTorch actor -- whose actor at this moment is the one the rollout ran."""
-    if args.rho_bar is None:
+    """The rollout's outputs into the ring, before the iteration's updates.  --rho-bar / --ppo-clip: with the
+    log-probabilities of `acted` -- the device learner, or the PyTorch actor -- whose actor at this moment is the one
+    the rollout ran."""
+    if not behavioural(args):
         ring.add_rollout(obs_in, res, **critic_kwargs(args, critic))
     else:
         ring.add_rollout_behaviour(obs_in, res, behaviour=acted, **critic_kwargs(args, critic))
@@ -181,6 +196,25 @@ def rho_field(rho, rho_bar):
     """The printed lines' extra field under --rho-bar: the mean ratio of the last update's batch and the share of its rows
     at the cap (a read of the device buffer rho_out filled: printed lines only)."""
     return f"rho mean {float(rho.mean()):.4f} at cap {float((rho >= rho_bar).float().mean()):.3f}  "
+
+
+def ratio_field(r, eps):
+    """The printed lines' extra field under --ppo-clip: the mean ratio of the last update's batch, the share of its rows
+    with |r - 1| > EPS and the approximate KL mean(-log r) (a read of the device buffer ratio_out filled: printed lines
+    only)."""
+    return (f"ratio mean {float(r.mean()):.4f} clipped {float(((r - 1).abs() > eps).float().mean()):.3f} "
+            f"kl {float(-torch.log(r).mean()):+.5f}  ")
+
+
+def ratio_kwargs(args, bufs, rings):
+    """update_from_many's arguments under --rho-bar or --ppo-clip, and the views of bufs (one per ring) the ratios land
+    in; update_from takes the one view itself."""
+    if not behavioural(args):
+        return {}, None
+    views = [b[:min(b.numel(), ring.count)] for b, ring in zip(bufs, rings)]
+    if args.ppo_clip is not None:
+        return {"clip_eps": args.ppo_clip, "ratio_out": views}, views
+    return {"rho_bar": args.rho_bar, "rho_out": views}, views
 
 
 def critic_kwargs(args, critic):
@@ -289,7 +323,7 @@ def train_sharded(args, timings=None):
         rings = [uavtrack.ReplayRing(2 * e.cfg.n_envs * args.n_uav * args.steps, dev, seed=args.seed + 7919 * k,
                                      max_batch=per_shard) for k, e in enumerate(envs)]
     rings = [behaviour_ring(args, nstep_ring(args, ring)) for ring in rings]
-    rho_bufs = [torch.empty(per_shard, device=dev) for _ in rings] if args.rho_bar is not None else None
+    rho_bufs = [torch.empty(per_shard, device=dev) for _ in rings] if behavioural(args) else None
     per_iter = args.envs * args.n_uav * args.steps
     stats = [uavtrack.EpisodeStats(e, log_capacity=e.cfg.n_envs * args.log_every, max_steps=args.steps) for e in envs]
     kept = {k: [] for k in SIX}
@@ -311,10 +345,7 @@ def train_sharded(args, timings=None):
         if log:
             torch.cuda.synchronize()
         t_roll = time.perf_counter() - t0
-        rho_kw = {}
-        if rho_bufs is not None:                                      # every ring's ratios, read on printed lines only
-            rhos = [b[:min(per_shard, ring.count)] for b, ring in zip(rho_bufs, rings)]
-            rho_kw = {"rho_bar": args.rho_bar, "rho_out": rhos}
+        rho_kw, rhos = ratio_kwargs(args, rho_bufs, rings)            # every ring's ratios, read on printed lines only
         for _ in range(args.updates):
             la_t, lc_t, tds = learner.update_from_many(rings, per_shard, **importance_kwargs(args), **rho_kw)
         la, lc = (float(la_t), float(lc_t)) if log else (la_t, lc_t)
@@ -322,7 +353,8 @@ def train_sharded(args, timings=None):
         if log and regularised(args):                                 # the last ring's rows of the last update
             reg_field = regularisation_field(learner.entropy(tds[-1].numel()).mean(), learner.grad_norm)
         if log and rho_kw:
-            reg_field += rho_field(torch.cat(rhos), args.rho_bar)
+            reg_field += rho_field(torch.cat(rhos), args.rho_bar) if args.ppo_clip is None else \
+                ratio_field(torch.cat(rhos), args.ppo_clip)
         if args.publish == "host":
             actor.load_state_dict(learner.actor_state_dict())
             for ro in rollouts:
@@ -422,6 +454,13 @@ def main(argv=None, timings=None):
                          "add_rollout(critic=...)): each slot keeps r + gamma L G' as its reward and gamma (1 - L) as its "
                          "discount, never across an episode end or the rollout's last step.  Needs --replay prioritized or "
                          "uniform-device; not with --n-step > 1")
+    ap.add_argument("--ppo-clip", type=float, default=None, metavar="EPS",
+                    help="EPS >= 0: PPO's clipped surrogate instead of --rho-bar.  The ring keeps log mu(a|s) as for "
+                         "--rho-bar, and every update trains -min(r A, clip(r, 1 - EPS, 1 + EPS) A) with r = pi / mu "
+                         "differentiated through and A the TD error (DeviceActorCritic.update_from(clip_eps=EPS), inside "
+                         "the gradient kernel; the torch learner trains the same expression); the printed lines show the "
+                         "mean ratio, the share of rows with |r - 1| > EPS and mean(-log r).  Needs --replay prioritized or "
+                         "uniform-device, and --actor-loss per_sample with --learner device; not with --rho-bar")
     ap.add_argument("--rho-bar", type=float, default=None,
                     help="R > 0: correct for who acted.  The ring keeps log mu(a|s) of every slot, evaluated by the learner's "
                          "actor over the window each add writes (ring.with_behaviour(), add_rollout_behaviour), and every "
@@ -512,6 +551,15 @@ def main(argv=None, timings=None):
     if args.rho_bar is not None and (not args.rho_bar > 0 or args.replay == "uniform"):
         ap.error("--rho-bar must be > 0 and needs --replay prioritized or --replay uniform-device (the device rings keep "
                  "the behaviour log-probabilities)")
+    if args.ppo_clip is not None:
+        if not args.ppo_clip >= 0 or args.replay == "uniform":
+            ap.error("--ppo-clip must be >= 0 and needs --replay prioritized or --replay uniform-device (the device rings "
+                     "keep the behaviour log-probabilities)")
+        if args.rho_bar is not None:
+            ap.error("--ppo-clip and --rho-bar exclude each other: one correction for who acted, not two")
+        if args.learner == "device" and args.actor_loss != "per_sample":
+            ap.error("--ppo-clip with --learner device needs --actor-loss per_sample: the reference form scales the actor's "
+                     "gradient sums once by -mean(delta) / N, a factor a per-row gate cannot share")
     if args.target_tau is not None and not 0.0 < args.target_tau <= 1.0:
         ap.error("--target-tau must lie in (0, 1]")
     if args.target_period is not None and args.target_period < 1:
@@ -584,7 +632,7 @@ def main(argv=None, timings=None):
         replay = behaviour_ring(args, nstep_ring(args, replay))
     else:
         replay = uavtrack.DeviceReplayBuffer(capacity=2 * per_iter, device=dev)
-    rho_buf = torch.empty(args.batch, device=dev) if args.rho_bar is not None and learner is not None else None
+    rho_buf = torch.empty(args.batch, device=dev) if behavioural(args) and learner is not None else None
     stats = uavtrack.EpisodeStats(env, log_capacity=args.envs * K * args.log_every, max_steps=T)
     kept = {k: [] for k in SIX}
     history = []
@@ -613,7 +661,7 @@ def main(argv=None, timings=None):
         diag = {} if log and regularised(args) else None              # the torch learner's entropy and norms
         rho_stats = {}                                                # --rho-bar: the last update's ratios, a device tensor
         reg_kw = dict(entropy_coef=args.entropy_coef, max_grad_norm=args.max_grad_norm, diag=diag, rho_bar=args.rho_bar,
-                      rho_stats=rho_stats, target_critic=target_critic)
+                      rho_stats=rho_stats, target_critic=target_critic, ppo_clip=args.ppo_clip)
         boot = critic if target_critic is None else target_critic     # whose V(s') the torch learner bootstraps from
         if learner is None and args.replay == "prioritized":          # train.py:250-262
             ikw = importance_kwargs(args)
@@ -633,10 +681,10 @@ def main(argv=None, timings=None):
                 if target_critic is not None:
                     sync_target_critic(args, target_critic, critic, updates_done)
         else:
-            rho_kw = {}
-            if args.rho_bar is not None:
-                rho_stats["rho"] = rho_buf[:min(args.batch, replay.count)]
-                rho_kw = {"rho_bar": args.rho_bar, "rho_out": rho_stats["rho"]}
+            rho_kw, views = ratio_kwargs(args, [rho_buf], [replay])
+            if views:                                                 # one ring: its view itself, not a list
+                rho_stats["rho"] = views[0]
+                rho_kw = {k: views[0] if k.endswith("_out") else v for k, v in rho_kw.items()}
             for _ in range(args.updates):
                 la_t, lc_t, td_t = learner.update_from(replay, args.batch, **importance_kwargs(args), **rho_kw)
             la, lc = (float(la_t), float(lc_t)) if log else (la_t, lc_t)
@@ -684,6 +732,8 @@ def main(argv=None, timings=None):
         reg_field = regularisation_field(diag["entropy"], diag.get("norms")) if diag else ""
         if args.rho_bar is not None:
             reg_field += rho_field(rho_stats["rho"], args.rho_bar)
+        if args.ppo_clip is not None:
+            reg_field += ratio_field(rho_stats["rho"], args.ppo_clip)
         print(f"iter {it:3d}  episode return {ret:8.3f}  covered targets/step {cov:5.2f}  actor loss {la:+.4f}  "
               f"critic loss {lc:.4f}  {reg_field}pmi loss {lp:.4f}  rollout {t_roll * 1e3:6.1f} ms ({per_iter / t_roll / 1e9:.2f} G agent-steps/s)  "
               f"iteration {((now - t0) if args.log_every == 1 else (now - t_log) / n_iter) * 1e3:6.1f} ms  {six}", flush=True)
@@ -691,7 +741,7 @@ def main(argv=None, timings=None):
     save_results(args, kept)
     if args.replay == "prioritized":
         replay.check()                                                # no draw was refused on the device
-    if learner is not None and args.rho_bar is not None:
+    if learner is not None and behavioural(args):
         learner.check()                                               # no update met a slot whose behaviour is unknown
     env.close()
     history = [float(r) for r in history]

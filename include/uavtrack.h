@@ -540,7 +540,8 @@ int uavtrack_learner_update_weighted(uavtrack_learner *learner, int64_t n,
  *   P+4, P+5    n of this row, an int64 as its low and high 32 bits
  *   P+6         int32 status bits of this row: bit 0 an action outside [0, A), bit 1 an index outside [0, capacity),
  *               bit 2 an importance weight that is NaN, infinite or negative, bit 3 (value 8) a discount that is NaN,
- *               negative or above 1 (see "multi-step targets: per-row discounts")
+ *               negative or above 1 (see "multi-step targets: per-row discounts"), bit 4 (value 16) a behaviour
+ *               log-probability that is NaN or positive, or a ratio that is not finite (see "the clipped surrogate")
  *   P+7         int32 P, the layout tag
  * The reference's actor loss mean(-log p) * mean(delta) is linear in mean(delta), which is why the rows can be summed:
  * the apply scales the actor's sums once by the GLOBAL -mean(delta) / N.  (Averaging per-row updates or per-row loss
@@ -778,8 +779,55 @@ int uavtrack_learner_ratio_weights(uavtrack_learner *learner, int64_t n, const f
                                    const float *log_mu, int64_t capacity, const int64_t *indices, double rho_bar,
                                    const float *weights_in, float *weights_out, float *rho_out, void *stream);
 
+/* ---- the clipped surrogate: PPO's actor loss from stored behaviour log-probabilities (UAVTRACK_LOSS_PER_SAMPLE only) ----
+ * The other standard answer to rows an older actor acted: differentiate THROUGH the ratio r = pi / mu and stop a row's
+ * policy gradient once r has left [1 - eps, 1 + eps] in the direction its advantage pushes.  Batch row i reads slot
+ * src_i (indices[i], or i); w_i is its weight (1 without weights), c the entropy coefficient, A_i = delta_i the TD error
+ * of the update (a constant of the differentiation).  eps32 = (float)clip_eps, lo = 1.0f - eps32, hi = 1.0f + eps32,
+ * both folded on the host (hi = +inf for clip_eps = +inf):
+ *   lp_i   = (z_a - max_o z_o) - logf(sum_o expf(z_o - max))      the bits uavtrack_learner_log_probs forms for the row
+ *   r_i    = expf(lp_i - log_mu[src_i])
+ *   pass_i = (A_i >= 0) ? (r_i <= hi) : (r_i >= lo)               inclusive: a ratio on the boundary still passes
+ *   surr_i = pass_i ? r_i * A_i : ((A_i >= 0) ? hi : lo) * A_i    = min(r A, clip(r, lo, hi) A)
+ *   actor_loss   = mean_i( w_i * ( -surr_i - c * H_i ) )
+ *   logit weight = w_i * ( (pass_i ? r_i * A_i : 0) * (onehot - p_i)_o - c * p_io * (log p_io + H_i) ),  scaled by -1 / N
+ * The critic, td_delta, the priorities, per-row discounts, the target critic, gradient-norm clipping and the entropy term
+ * are what they are without it.  Loss words [P], [P+1], [P+3] of a gradient row keep their meaning and word [P+2] carries
+ * sum w_i (-surr_i - c H_i); a row keeps its P + 8 words and its tag, so rows with and without the clipped loss may meet
+ * in one apply (rows carry no settings: participants of one update pass equal clip_eps).  log p, p and H of a clipped
+ * row always come from the logits.  The products are ordered (A_i * r_i) first, so r_i == 1.0f with pass_i true leaves
+ * the bits of the per-sample weight: a batch whose log_mu holds the bits uavtrack_learner_log_probs forms now
+ * (expf(0.0f) == 1.0f) trains, at any clip_eps >= 0, with the parameters, moments, td_delta, critic loss and priorities
+ * of the per-sample update; its actor_loss is mean(-w (A + c H)), not mean(w (-log p A - c H)).
+ * The reference form scales the actor's sums ONCE by the global -mean(delta) / N, and a per-row gate cannot share that
+ * scale: a UAVTRACK_LOSS_REFERENCE learner is refused on the host.
+ * log_mu is DEVICE fp32 [capacity], indexed by SLOT and gathered beside the reward (a behaviour ring's sixth store).
+ * ratio_out (DEVICE fp32 [n], nullable, batch order) receives r_i whatever clip_eps is, NaN for a row that set a status
+ * bit: the clip fraction mean(|r - 1| > eps) and the approximate KL mean(-log r) are one reduction over it.
+ * Refusals, found on the device like a bad action: a drawn slot whose log_mu is NaN ("unknown") or > 0, or whose r_i is
+ * not finite, sets status bit 4 (value 16) in the status word and in word P + 6 of a row, and that row is not used; the
+ * update or apply then changes nothing, its losses are NaN, the next uavtrack_learner_check counts it, and
+ * uavtrack_learner_write_priorities stays gated on that verdict.
+ * Both calls are stream-ordered: no synchronisation, no allocation, capturable.  Host-side errors, enqueuing nothing:
+ * those of uavtrack_learner_update_discounted / _grad_discounted, a null log_mu, clip_eps NaN or negative (+inf is
+ * allowed and never clips), a UAVTRACK_LOSS_REFERENCE learner.  weights and discounts are each nullable.
+ * No second actor forward runs: the gradient kernel has the logits already.  Cost on one MI355X: DESIGN.md section 9. */
+int uavtrack_learner_update_clipped(uavtrack_learner *learner, int64_t n,
+                                    const float *states, const int32_t *actions, const float *rewards,
+                                    const float *next_states, int64_t capacity, const int64_t *indices,
+                                    const float *weights, const float *discounts,
+                                    const float *log_mu, double clip_eps, float *ratio_out,
+                                    float *actor_loss, float *critic_loss, float *td_delta, float *priorities,
+                                    void *stream);
+int uavtrack_learner_grad_clipped(uavtrack_learner *learner, int64_t n,
+                                  const float *states, const int32_t *actions, const float *rewards,
+                                  const float *next_states, int64_t capacity, const int64_t *indices,
+                                  const float *weights, const float *discounts,
+                                  const float *log_mu, double clip_eps, float *ratio_out,
+                                  float *td_delta, float *row, void *stream);
+
 /* Synchronises `stream`; fails if any update or apply since the previous check was refused on the device (bad action,
- * index, importance weight or discount, or a row of another layout).  refused (nullable) receives their number; the count restarts at 0. */
+ * index, importance weight, discount, behaviour log-probability or ratio, or a row of another layout).  refused (nullable) receives their number; the count restarts at 0. */
 int uavtrack_learner_check(uavtrack_learner *learner, int64_t *refused, void *stream);
 
 /* ---- the PMI trainer: PMINetwork.train_pmi + its Adam steps on the device ----

@@ -75,6 +75,20 @@ LearnerLaunch learner_batch(int64_t n, const float *states, const int32_t *actio
     return q;
 }
 
+// The clipped surrogate's arguments of uavtrack_learner_update_clipped / _grad_clipped, into q
+int accept_clip(const char *fn, const uavtrack_learner *l, const float *log_mu, double clip_eps, float *ratio_out,
+                LearnerLaunch &q)
+{
+    if (!log_mu) return fail("%s: log_mu must not be null", fn);
+    if (!(clip_eps >= 0)) return fail("%s: clip_eps = %g must be >= 0 (+inf: never clips)", fn, clip_eps);
+    if (!l->d.per_sample)
+        return fail("%s: the clipped surrogate on a UAVTRACK_LOSS_REFERENCE learner: that form scales the actor's gradient "
+                    "sums once by -mean(delta) / N, a factor a per-row gate cannot share; use UAVTRACK_LOSS_PER_SAMPLE", fn);
+    const float eps32 = (float)clip_eps;
+    q.log_mu = log_mu; q.clip_lo = 1.0f - eps32; q.clip_hi = 1.0f + eps32; q.ratio = ratio_out;
+    return 0;
+}
+
 }  // namespace
 
 extern "C" {
@@ -221,11 +235,19 @@ int uavtrack_learner_get_optimizer_state(uavtrack_learner *learner, float *exp_a
 
 namespace {
 
-// uavtrack_learner_update, _update_weighted and _update_discounted (`fn`: the caller's name; weights, discounts nullable)
+// the clipped surrogate's arguments as the _clipped entry points pass them on; null for every other entry point
+struct ClipArgs {
+    const float *log_mu;
+    double clip_eps;
+    float *ratio_out;
+};
+
+// uavtrack_learner_update, _update_weighted, _update_discounted and _update_clipped (`fn`: the caller's name; weights,
+// discounts nullable; clip: _update_clipped only)
 int learner_update(const char *fn, uavtrack_learner *learner, int64_t n, const float *states, const int32_t *actions,
                    const float *rewards, const float *next_states, int64_t capacity, const int64_t *indices,
                    const float *weights, const float *discounts, float *actor_loss, float *critic_loss, float *td_delta, float *priorities,
-                   void *stream)
+                   void *stream, const ClipArgs *clip = nullptr)
 {
     if (!learner) return fail("%s: null handle", fn);
     if (!states || !actions || !rewards || !next_states)
@@ -235,14 +257,16 @@ int learner_update(const char *fn, uavtrack_learner *learner, int64_t n, const f
     ON_DEVICE(learner->cfg.device_id);
     LearnerLaunch q = learner_batch(n, states, actions, rewards, next_states, capacity, indices, weights, discounts, td_delta);
     q.actor_loss = actor_loss; q.critic_loss = critic_loss; q.priorities = priorities;
+    if (clip && accept_clip(fn, learner, clip->log_mu, clip->clip_eps, clip->ratio_out, q)) return 1;
     HIP_TRY(launch_learner_update(learner->d, q, static_cast<hipStream_t>(stream)));
     return 0;
 }
 
-// uavtrack_learner_grad, _grad_weighted and _grad_discounted
+// uavtrack_learner_grad, _grad_weighted, _grad_discounted and _grad_clipped
 int learner_grad(const char *fn, uavtrack_learner *learner, int64_t n, const float *states, const int32_t *actions,
                  const float *rewards, const float *next_states, int64_t capacity, const int64_t *indices,
-                 const float *weights, const float *discounts, float *td_delta, float *row, void *stream)
+                 const float *weights, const float *discounts, float *td_delta, float *row, void *stream,
+                 const ClipArgs *clip = nullptr)
 {
     if (!learner) return fail("%s: null handle", fn);
     if (!states || !actions || !rewards || !next_states)
@@ -250,8 +274,8 @@ int learner_grad(const char *fn, uavtrack_learner *learner, int64_t n, const flo
     if (!td_delta || !row) return fail("%s: td_delta and row must not be null", fn);
     if (accept_batch(fn, learner, n, capacity, indices, "from") || accept_entropy_rows(fn, learner, n)) return 1;
     ON_DEVICE(learner->cfg.device_id);
-    const LearnerLaunch q = learner_batch(n, states, actions, rewards, next_states, capacity, indices, weights, discounts,
-                                          td_delta);
+    LearnerLaunch q = learner_batch(n, states, actions, rewards, next_states, capacity, indices, weights, discounts, td_delta);
+    if (clip && accept_clip(fn, learner, clip->log_mu, clip->clip_eps, clip->ratio_out, q)) return 1;
     HIP_TRY(launch_learner_grad(learner->d, q, row, static_cast<hipStream_t>(stream)));
     return 0;
 }
@@ -287,6 +311,17 @@ int uavtrack_learner_update_discounted(uavtrack_learner *learner, int64_t n, con
                           actor_loss, critic_loss, td_delta, priorities, stream);
 }
 
+int uavtrack_learner_update_clipped(uavtrack_learner *learner, int64_t n, const float *states, const int32_t *actions,
+                                    const float *rewards, const float *next_states, int64_t capacity,
+                                    const int64_t *indices, const float *weights, const float *discounts,
+                                    const float *log_mu, double clip_eps, float *ratio_out, float *actor_loss,
+                                    float *critic_loss, float *td_delta, float *priorities, void *stream)
+{
+    const ClipArgs clip = {log_mu, clip_eps, ratio_out};
+    return learner_update(__func__, learner, n, states, actions, rewards, next_states, capacity, indices, weights, discounts,
+                          actor_loss, critic_loss, td_delta, priorities, stream, &clip);
+}
+
 int uavtrack_learner_row_floats(uavtrack_learner *learner, int64_t *out)
 {
     if (!learner || !out) return fail("uavtrack_learner_row_floats: null argument");
@@ -317,6 +352,16 @@ int uavtrack_learner_grad_discounted(uavtrack_learner *learner, int64_t n, const
 {
     return learner_grad(__func__, learner, n, states, actions, rewards, next_states, capacity, indices, weights, discounts,
                         td_delta, row, stream);
+}
+
+int uavtrack_learner_grad_clipped(uavtrack_learner *learner, int64_t n, const float *states, const int32_t *actions,
+                                  const float *rewards, const float *next_states, int64_t capacity, const int64_t *indices,
+                                  const float *weights, const float *discounts, const float *log_mu, double clip_eps,
+                                  float *ratio_out, float *td_delta, float *row, void *stream)
+{
+    const ClipArgs clip = {log_mu, clip_eps, ratio_out};
+    return learner_grad(__func__, learner, n, states, actions, rewards, next_states, capacity, indices, weights, discounts,
+                        td_delta, row, stream, &clip);
 }
 
 int uavtrack_learner_apply(uavtrack_learner *learner, const float *rows, int64_t count, float *actor_loss,
@@ -533,8 +578,10 @@ int uavtrack_learner_check(uavtrack_learner *learner, int64_t *refused, void *st
     if (take_refusals(__func__, learner, refused, stream, &count)) return 1;
     if (count)
         return fail("uavtrack_learner_check: %d update(s) refused: an action outside [0, %d), an index outside "
-                    "[0, capacity), an importance weight that is NaN, infinite or negative or a discount that is NaN or "
-                    "outside [0, 1], or (uavtrack_learner_apply) a gradient row of another layout; they changed nothing",
+                    "[0, capacity), an importance weight that is NaN, infinite or negative, a discount that is NaN or "
+                    "outside [0, 1], a behaviour log-probability that is NaN or positive or a ratio that is not finite "
+                    "(the clipped surrogate), or (uavtrack_learner_apply) a gradient row of another layout; they changed "
+                    "nothing",
                     count, learner->d.L.A);
     return 0;
 }

@@ -77,10 +77,13 @@ struct LearnerLaunch {
     const int64_t *idx;
     const float *weights;           // nullable [n]: importance weights in batch order
     const float *discounts;         // nullable [capacity]: per-slot discounts (null: the handle's gamma for every row)
+    const float *log_mu;            // nullable [capacity]: per-slot behaviour log-probabilities; non-null: the clipped surrogate
+    float clip_lo, clip_hi;         // its bounds 1 - eps and 1 + eps in fp32 (read only with log_mu)
+    float *ratio;                   // nullable [n]: its ratios in batch order (read only with log_mu)
     float *actor_loss, *critic_loss, *td_delta, *priorities;
 };
 int learner_rows_per_tile(int hidden);
-size_t learner_lds_bytes(const LearnerLayout &L, int rows);
+size_t learner_lds_bytes(const LearnerLayout &L, int rows, bool clipped = false);   // clipped: R more floats, behind the rest
 int learner_groups(const LearnerLayout &L, int64_t n);
 int learner_clip_groups(const LearnerLayout &L);   // workgroups of the clip's gradient pass: ceil(P / 256)
 inline int learner_critic_words(const LearnerLayout &L) { return 14 * L.H + 1; }   // the critic's block, c_w1 .. P

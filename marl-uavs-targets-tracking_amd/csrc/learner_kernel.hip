@@ -48,6 +48,17 @@
 // learner_target_kernel, behind the Adam kernel and gated on the same status word, moves the block towards the critic
 // (Polyak) or copies it every `period` steps of the device step counter.  While off, the launches are the ones above.
 //
+// The clipped surrogate (uavtrack_learner_update_clipped / _grad_clipped, per-sample form only): the ratio
+// r_i = expf(log p_i - log_mu[src_i]) against a per-slot store of behaviour log-probabilities is differentiated through,
+// and a row's policy gradient stops once r_i has left [lo, hi] in the direction its advantage delta_i pushes:
+// pass_i = delta_i >= 0 ? r_i <= hi : r_i >= lo, surr_i = min(r delta, clip(r, lo, hi) delta), logit weight
+// w_i ((pass_i ? delta_i r_i : 0) (onehot - p_i)_o - c p_io (log p_io + H_i)), loss word 2 sum w_i (-surr_i - c H_i).
+// learner_grad_clip_kernel / _clip_target_kernel are the same body with that block (kClip), always on the logits path;
+// the tile gather leaves log_mu[src] in R more floats of LDS behind dc, so only these two ask for the larger allocation.
+// log p_i is (z_a - max) - logf(sum expf(z - max)), the bits of learner_policy_kernel, and expf(0.0f) == 1.0f, so a row
+// whose log_mu holds those bits trains with the bits of the per-sample row.  A drawn slot whose log_mu is NaN or > 0, or
+// whose r_i is not finite, sets status bit 4 (value 16) and is not used.
+//
 // The critic alone (uavtrack_learner_values): learner_values_kernel, at the end of the kernels below, evaluates V(x) of
 // any number of rows by the chain of the layer-1 and layer-2 loops above, to the bit, and touches no learner state.
 
@@ -56,6 +67,7 @@
 #include <hip/hip_runtime.h>
 #include <cmath>
 #include <cstdint>
+#include <type_traits>
 
 namespace uavtrack {
 
@@ -74,6 +86,7 @@ struct GradArgs {
     float *partials;                // [groups][P + 4]
     float *td_delta;                // nullable [n]
     int *status;                    // bit 0: action out of range, bit 1: index out of range, bit 2: weight NaN, inf or < 0
+                                    // (bit 3: a bad discount, below; bit 4: a bad log_mu or ratio, GradClipArgs)
     LearnerLayout L;
     int rows;                       // R rows per tile
     float gamma;
@@ -86,11 +99,21 @@ struct GradArgs {
                                     // (learner_grad_target_kernel / _reg_target_kernel only; null otherwise)
 };
 
+// what the clipped surrogate's two kernels take on top (learner_grad_clip_kernel / _clip_target_kernel): a type of its
+// own, so that the other four keep their kernel arguments, and with them their code, word for word
+struct GradClipArgs : GradArgs {
+    const float *log_mu;            // [capacity], slot order: behaviour log-probabilities; status bit 4: a drawn slot whose
+                                    // log_mu is NaN or > 0, or whose ratio is not finite
+    float clip_lo, clip_hi;         // 1 - eps, 1 + eps in fp32, folded on the host
+    float *ratio;                   // nullable [n]: r_i of batch row i, NaN for a row that set a status bit
+};
+
 // kReg: the entropy term and the entropy[] store in the per-row block; everything else is one text.
 // kTgt: V(s') from the separate critic block a.target (the target critic) instead of the online critic; without it
 // W1t / b1t / W2t / b2t are the online critic's pointers at compile time.
-template <bool kReg, bool kTgt = false>
-__device__ __forceinline__ void learner_grad_body(const GradArgs &a)
+// kClip (with kReg): the clipped surrogate's gate on the row's policy gradient, log_mu gathered into lm, the ratio[] store.
+template <bool kReg, bool kTgt = false, bool kClip = false>
+__device__ __forceinline__ void learner_grad_body(const std::conditional_t<kClip, GradClipArgs, GradArgs> &a)
 {
     extern __shared__ float lds[];
     const LearnerLayout &L = a.L;
@@ -108,6 +131,7 @@ __device__ __forceinline__ void learner_grad_body(const GradArgs &a)
     int *act   = reinterpret_cast<int *>(lt + R * 4);   // [R] action, -1 = row not used
     float *wt  = reinterpret_cast<float *>(act + R);    // [R] importance weight of the row
     float *dc  = wt + R;                                // [R] discount of the row
+    float *lm  = dc + R;                                // [R] behaviour log-probability of the row (kClip only)
 
     const int tid = threadIdx.x;
     const float *W1a = a.params + L.a_w1, *b1a = a.params + L.a_b1, *W2a = a.params + L.a_w2, *b2a = a.params + L.a_b2;
@@ -137,6 +161,11 @@ __device__ __forceinline__ void learner_grad_body(const GradArgs &a)
                     if (a.discounts) {
                         di = a.discounts[src];
                         if (!(di >= 0.0f && di <= 1.0f)) { atomicOr(a.status, 8); av = -1; }
+                    }
+                    if constexpr (kClip) {
+                        const float mu = a.log_mu[src];
+                        if (!(mu <= 0.0f)) { atomicOr(a.status, 16); av = -1; }
+                        lm[r] = mu;
                     }
                 }
                 if (a.weights) {
@@ -195,6 +224,8 @@ __device__ __forceinline__ void learner_grad_body(const GradArgs &a)
                 gv[r] = 0.0f;
                 lt[r * 4 + 0] = lt[r * 4 + 1] = lt[r * 4 + 2] = lt[r * 4 + 3] = 0.0f;
                 if (kReg && a.entropy && row0 + r < a.n) a.entropy[row0 + r] = 0.0f;
+                if constexpr (kClip)
+                    if (a.ratio && row0 + r < a.n) a.ratio[row0 + r] = NAN;
                 continue;
             }
             float m = z[0];
@@ -219,7 +250,35 @@ __device__ __forceinline__ void learner_grad_body(const GradArgs &a)
                 const float wi = wt[r];
                 const float c = a.entropy_coef;
                 float nlp, al;
-                if (c != 0.0f) {                                    // launch-uniform
+                if constexpr (kClip) {
+                    nlp = lse - z[av];
+                    const float ratio = expf((z[av] - lse) - lm[r]);
+                    if (!(ratio <= 3.402823466e+38f)) {             // inf or NaN: the row is not used
+                        atomicOr(a.status, 16);
+                        for (int o = 0; o < A; ++o) z[o] = 0.0f;
+                        gv[r] = 0.0f;
+                        lt[r * 4 + 0] = lt[r * 4 + 1] = lt[r * 4 + 2] = lt[r * 4 + 3] = 0.0f;
+                        if (a.entropy) a.entropy[row0 + r] = 0.0f;
+                        if (a.ratio) a.ratio[row0 + r] = NAN;
+                        continue;
+                    }
+                    const bool pass = delta >= 0.0f ? ratio <= a.clip_hi : ratio >= a.clip_lo;
+                    const float dr = pass ? delta * ratio : 0.0f;   // ratio == 1: delta's bits
+                    const float surr = pass ? dr : (delta >= 0.0f ? a.clip_hi : a.clip_lo) * delta;
+                    if (c != 0.0f) {                                // launch-uniform
+                        for (int o = 0; o < A; ++o) {
+                            const float d = z[o], e = expf(d), p = e * inv;
+                            const float ge = e > 0.0f ? p * ((d - lse) + ent) : 0.0f;
+                            z[o] = wi * (dr * ((o == av ? 1.0f : 0.0f) - p) - c * ge);
+                        }
+                        al = wi * (-surr - c * ent);
+                    } else {
+                        const float w = dr * wi;
+                        for (int o = 0; o < A; ++o) z[o] = w * ((o == av ? 1.0f : 0.0f) - expf(z[o]) * inv);
+                        al = -surr * wi;
+                    }
+                    if (a.ratio) a.ratio[row0 + r] = ratio;
+                } else if (c != 0.0f) {                             // launch-uniform
                     nlp = lse - z[av];
                     for (int o = 0; o < A; ++o) {
                         const float d = z[o], e = expf(d), p = e * inv;
@@ -330,6 +389,10 @@ __global__ void __launch_bounds__(kLW) learner_grad_reg_kernel(GradArgs a) { lea
 __global__ void __launch_bounds__(kLW) learner_grad_target_kernel(GradArgs a) { learner_grad_body<false, true>(a); }
 __global__ void __launch_bounds__(kLW) learner_grad_reg_target_kernel(GradArgs a) { learner_grad_body<true, true>(a); }
 
+// the clipped surrogate (uavtrack_learner_update_clipped / _grad_clipped), without and with a target critic
+__global__ void __launch_bounds__(kLW) learner_grad_clip_kernel(GradClipArgs a) { learner_grad_body<true, false, true>(a); }
+__global__ void __launch_bounds__(kLW) learner_grad_clip_target_kernel(GradClipArgs a) { learner_grad_body<true, true, true>(a); }
+
 // Clears the update's status word (a kernel node rather than a memset node, so a captured update is a chain of kernels)
 __global__ void learner_begin_kernel(int *status)
 {
@@ -362,8 +425,8 @@ __global__ void learner_finalize_kernel(const float *src, int count, size_t stri
         if (n_given) continue;                                      // a workgroup partial ends here
         const int32_t *tail = reinterpret_cast<const int32_t *>(row) + P + 4;
         const int64_t nr = (int64_t)((uint64_t)(uint32_t)tail[0] | ((uint64_t)(uint32_t)tail[1] << 32));
-        bad |= tail[2] & 15;
-        if (tail[3] != P || nr < 1) bad |= 16;                      // a row of another layout (or not a row at all)
+        bad |= tail[2] & 31;
+        if (tail[3] != P || nr < 1) bad |= 32;                      // a row of another layout (or not a row at all)
         else N += nr;
     }
     if (n_given) bad = *status;
@@ -606,9 +669,10 @@ int learner_rows_per_tile(int hidden)
     return r > 256 ? 256 : r;
 }
 
-size_t learner_lds_bytes(const LearnerLayout &L, int rows)
+size_t learner_lds_bytes(const LearnerLayout &L, int rows, bool clipped)
 {
-    return sizeof(float) * ((size_t)L.P + (size_t)rows * (24 + 3 * L.H + L.A + 2 + 4 + 2)) + sizeof(int) * (size_t)rows;
+    return sizeof(float) * ((size_t)L.P + (size_t)rows * (24 + 3 * L.H + L.A + 2 + 4 + 2 + (clipped ? 1 : 0))) +
+           sizeof(int) * (size_t)rows;
 }
 
 int learner_groups(const LearnerLayout &L, int64_t n)
@@ -631,6 +695,13 @@ hipError_t learner_prepare_kernels(const LearnerLayout &L)
         const hipError_t e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (e != hipSuccess) return e;
     }
+    // the clipped surrogate's two keep log_mu of the tile in R more floats
+    const size_t clds = learner_lds_bytes(L, learner_rows_per_tile(L.H), true);
+    for (const void *k : {reinterpret_cast<const void *>(learner_grad_clip_kernel),
+                          reinterpret_cast<const void *>(learner_grad_clip_target_kernel)}) {
+        const hipError_t e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)clds);
+        if (e != hipSuccess) return e;
+    }
     return hipSuccess;
 }
 
@@ -644,17 +715,25 @@ hipError_t launch_grad(const LearnerDevice &d, const LearnerLaunch &q, float *td
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
 
-    GradArgs a;
+    GradClipArgs a;
     a.params = d.params; a.states = q.states; a.rewards = q.rewards; a.next_states = q.next_states;
     a.actions = q.actions; a.idx = q.idx; a.weights = q.weights; a.n = q.n; a.capacity = q.capacity;
     a.partials = d.partials; a.td_delta = td; a.status = status;
     a.L = L; a.rows = R; a.gamma = d.gamma; a.per_sample = d.per_sample;
     a.entropy_coef = d.entropy_coef; a.entropy = d.entropy; a.discounts = q.discounts;
     a.target = d.target_mode ? d.target : nullptr;
+    a.log_mu = q.log_mu; a.clip_lo = q.clip_lo; a.clip_hi = q.clip_hi; a.ratio = q.ratio;
     const bool reg = d.entropy_coef != 0.0f || d.entropy;
+    const bool clipped = q.log_mu != nullptr;
     auto *kernel = a.target ? (reg ? learner_grad_reg_target_kernel : learner_grad_target_kernel)
                             : (reg ? learner_grad_reg_kernel : learner_grad_kernel);
-    hipLaunchKernelGGL(kernel, dim3(learner_groups(L, q.n)), dim3(kLW), learner_lds_bytes(L, R), st, a);
+    const dim3 grid(learner_groups(L, q.n));
+    if (clipped) {
+        hipLaunchKernelGGL(a.target ? learner_grad_clip_target_kernel : learner_grad_clip_kernel, grid, dim3(kLW),
+                           learner_lds_bytes(L, R, true), st, a);
+        return hipGetLastError();
+    }
+    hipLaunchKernelGGL(kernel, grid, dim3(kLW), learner_lds_bytes(L, R), st, static_cast<const GradArgs &>(a));
     return hipGetLastError();
 }
 

@@ -180,6 +180,10 @@ SIGNATURES = {
                                            + [C.c_void_p] * 8),
     "uavtrack_learner_grad_discounted": (C.c_int, [C.c_void_p, C.c_int64] + [C.c_void_p] * 4 + [C.c_int64]
                                          + [C.c_void_p] * 6),
+    "uavtrack_learner_update_clipped": (C.c_int, [C.c_void_p, C.c_int64] + [C.c_void_p] * 4 + [C.c_int64]
+                                        + [C.c_void_p] * 4 + [C.c_double] + [C.c_void_p] * 6),
+    "uavtrack_learner_grad_clipped": (C.c_int, [C.c_void_p, C.c_int64] + [C.c_void_p] * 4 + [C.c_int64]
+                                      + [C.c_void_p] * 4 + [C.c_double] + [C.c_void_p] * 4),
     "uavtrack_learner_values": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
     "uavtrack_learner_set_target": (C.c_int, [C.c_void_p, C.c_int32, C.c_double, C.c_int64, C.c_void_p]),
     "uavtrack_learner_get_target": (C.c_int, [C.c_void_p, C.POINTER(C.c_double)]),

@@ -51,6 +51,18 @@ lambda windows carry no traces.  A row whose log mu holds the bits the actor for
 batch at R >= 1 trains with the unweighted update's bits.  log_probs(states, actions) is the actor alone
 (uavtrack_learner_log_probs).
 
+The clipped surrogate (update(log_mu=, clip_eps=), DrawSpec.clip_eps on a ring made with_behaviour(); loss="per_sample"
+only): PPO's answer to the same staleness, instead of rho_bar.  With r_i = pi(a_i|s_i) / mu(a_i|s_i), A_i = td_delta_i (a
+constant of the differentiation), lo = 1 - eps, hi = 1 + eps in float32:
+    actor_loss = mean_i(w_i (-min(r_i A_i, clip(r_i, lo, hi) A_i) - c H_i))
+so a row's policy gradient is r_i A_i grad log p_i while r_i <= hi (A_i >= 0) or r_i >= lo (A_i < 0), boundaries included,
+and 0 beyond; the critic, td_delta, the priorities, the entropy term and everything else are unchanged.  The ratio is
+formed inside the gradient kernel from the logits it already holds (uavtrack_learner_update_clipped / _grad_clipped): no
+second forward.  ratio_out receives r_i; the clip fraction and an approximate KL are one torch reduction over it.  A row
+whose log mu holds the bits log_probs forms now has r = 1 exactly and trains with the per-sample update's bits.  A drawn
+log mu that is NaN or positive, or a ratio that is not finite, refuses the update on the device.  The reference form
+scales the actor's sums once by -mean(delta) / N, which a per-row gate cannot share: loss="reference" raises.
+
 The critic alone (values(states), uavtrack_learner_values): V(s) of any number of rows with the parameters as they stand
 when the launch runs, bit for bit the V(s) an update forms.  A lambda ring (ring.with_lambda(lam, gamma)) takes it as
 add_rollout(..., critic=learner) to fold a rollout's rewards with its values into lambda-returns.
@@ -83,7 +95,9 @@ from .replay import DrawSpec
 from .rollout import ActorMLP
 
 
-_Drawn = namedtuple("_Drawn", "n store capacity idx priorities weights discounts")   # one drawn batch, as _run takes it
+# one drawn batch, as _run takes it
+_Drawn = namedtuple("_Drawn", "n store capacity idx priorities weights discounts log_mu clip_eps ratio_out",
+                    defaults=(None, None, None))
 
 
 def num_params(hidden_dim: int, action_dim: int) -> int:
@@ -277,8 +291,9 @@ class DeviceActorCritic(Handle):
 
     def check(self) -> None:
         """Synchronises; raises if an update since the last check was refused on the device (an action outside
-        [0, action_dim), an index outside the ring, or an importance weight that is NaN, infinite or negative -- what a
-        refused ring draw hands out), which then changed nothing."""
+        [0, action_dim), an index outside the ring, an importance weight that is NaN, infinite or negative -- what a
+        refused ring draw hands out --, a discount that is NaN or outside [0, 1], or, under the clipped surrogate, a
+        behaviour log-probability that is NaN or positive or a ratio that is not finite), which then changed nothing."""
         self._check()
 
     # ---- the critic alone, the actor alone, and the argument checks they share
@@ -365,6 +380,8 @@ class DeviceActorCritic(Handle):
             if spec.rho_out is not None:
                 raise ValueError("rho_out needs rho_bar")
             return w
+        if spec.clip_eps is not None:
+            raise ValueError("clip_eps together with rho_bar: one correction for who acted, not two")
         log_mu = getattr(buffer, "log_mu", None)          # an object that is no buffer gets the same answer
         if log_mu is None:
             raise ValueError("rho_bar needs the buffer's behaviour log-probabilities: a ReplayRing or PrioritizedReplayRing "
@@ -386,16 +403,42 @@ class DeviceActorCritic(Handle):
             raise ValueError(f"{caller}: the buffer is empty")
         idx, w = buffer._draw_batch(k, spec)
         w = self._ratios_from(buffer, k, idx, w, spec)
+        log_mu = self._clip_store(buffer, spec)
         d = buffer.discounts
         if d is not None and np.float32(buffer.gamma) != np.float32(self.gamma):
             raise ValueError(f"the buffer's returns were folded with gamma = {buffer.gamma}, the learner bootstraps with "
                              f"gamma = {self.gamma}: both must be the same float32")
-        return _Drawn(k, buffer.store, buffer.capacity, idx, buffer.priorities, w, d)
+        return _Drawn(k, buffer.store, buffer.capacity, idx, buffer.priorities, w, d, log_mu, spec.clip_eps, spec.ratio_out)
+
+    def _clip_eps_arg(self, clip_eps) -> float:
+        """clip_eps as the library takes it: >= 0, inf allowed, on a per-sample learner."""
+        if self.loss != "per_sample":
+            raise ValueError('clip_eps on a loss="reference" learner: that form scales the actor\'s gradient sums once by '
+                             '-mean(delta) / N, a factor a per-row gate cannot share; use loss="per_sample"')
+        eps = float(clip_eps)
+        if not eps >= 0.0:                                            # NaN fails the comparison
+            raise ValueError(f"clip_eps = {clip_eps!r} must be >= 0 (inf never clips)")
+        return eps
+
+    def _clip_store(self, buffer, spec: DrawSpec) -> Optional[torch.Tensor]:
+        """The buffer's behaviour store where spec asks for the clipped surrogate, else None."""
+        if spec.clip_eps is None:
+            if spec.ratio_out is not None:
+                raise ValueError("ratio_out needs clip_eps")
+            return None
+        self._clip_eps_arg(spec.clip_eps)
+        log_mu = getattr(buffer, "log_mu", None)
+        if log_mu is None:
+            raise ValueError("clip_eps needs the buffer's behaviour log-probabilities: a ReplayRing or PrioritizedReplayRing "
+                             "made ring.with_behaviour()")
+        return log_mu
 
     def _launch(self, kind: str, n: int, store: Dict[str, torch.Tensor], capacity: int, idx: Optional[torch.Tensor],
-                weights: Optional[torch.Tensor], discounts: Optional[torch.Tensor], *outputs) -> None:
+                weights: Optional[torch.Tensor], discounts: Optional[torch.Tensor], *outputs, clip=None) -> None:
         """uavtrack_learner_<kind> ("update" or "grad") in the form the batch takes: plain, _weighted (weights, one per
-        batch row) or _discounted (weights or NULL, then discounts, one per slot of the store); then the outputs."""
+        batch row), _discounted (weights or NULL, then discounts, one per slot of the store) or, with clip = (log_mu,
+        clip_eps, ratio_out), _clipped (weights or NULL, discounts or NULL, log_mu per slot, eps, ratios or NULL); then
+        the outputs."""
         w = _lib.tensor_arg(weights, torch.float32, n, self.device,
                             f"weights must be a contiguous float32 tensor of {n} elements (one per batch row, in batch "
                             f"order) on {self.device}")
@@ -404,32 +447,53 @@ class DeviceActorCritic(Handle):
                             f"store) on {self.device}")
         suffix, extra = ("_discounted", (_ptr(w), _ptr(d))) if d is not None else \
             ("", ()) if w is None else ("_weighted", (_ptr(w),))
+        if clip is not None:
+            log_mu, clip_eps, ratio_out = clip
+            _lib.tensor_arg(log_mu, torch.float32, capacity, self.device,
+                            f"log_mu must be a contiguous float32 tensor of {capacity} elements (one per slot of the "
+                            f"store) on {self.device}")
+            _lib.tensor_arg(ratio_out, torch.float32, n, self.device,
+                            f"ratio_out must be a contiguous float32 tensor of {n} elements (one per batch row) on "
+                            f"{self.device}")
+            suffix, extra = "_clipped", (_ptr(w), _ptr(d), _ptr(log_mu), self._clip_eps_arg(clip_eps), _ptr(ratio_out))
         name = f"uavtrack_learner_{kind}{suffix}"
         _lib.check(getattr(self._lib, name)(self._h, n, *self._batch_args(store, capacity, idx), *extra,
                                             *map(_ptr, outputs), self._stream()), name)
 
     def _run(self, n: int, store: Dict[str, torch.Tensor], capacity: int, idx: Optional[torch.Tensor],
              priorities: Optional[torch.Tensor], weights: Optional[torch.Tensor] = None,
-             discounts: Optional[torch.Tensor] = None):
+             discounts: Optional[torch.Tensor] = None, log_mu: Optional[torch.Tensor] = None,
+             clip_eps: Optional[float] = None, ratio_out: Optional[torch.Tensor] = None):
         losses = torch.empty(2, device=self.device)
         td = torch.empty(n, device=self.device)
-        self._launch("update", n, store, capacity, idx, weights, discounts, losses[0:1], losses[1:2], td, priorities)
+        self._launch("update", n, store, capacity, idx, weights, discounts, losses[0:1], losses[1:2], td, priorities,
+                     clip=None if clip_eps is None else (log_mu, clip_eps, ratio_out))
         return losses[0], losses[1], td
 
     def update(self, transition_dict: Dict[str, torch.Tensor], weights: Optional[torch.Tensor] = None,
                discounts: Optional[torch.Tensor] = None, log_mu: Optional[torch.Tensor] = None,
-               rho_bar: Optional[float] = None):
+               rho_bar: Optional[float] = None, clip_eps: Optional[float] = None,
+               ratio_out: Optional[torch.Tensor] = None):
         """ActorCritic.update (actor_critic.py:150-179) on a batch {states [n,12], actions [n], rewards [n],
         next_states [n,12]}: returns (actor_loss, critic_loss, td_delta) as device tensors, without synchronising.
         weights [n] (optional): importance weights w_i >= 0, one per row (the module docstring has the weighted losses);
         None is the reference's unweighted update, and a vector of ones gives its bits.
         discounts [n] (optional): d_i in [0, 1] of row i, in batch order (row i is slot i here): the target becomes
         r_i + d_i V(s'_i); None is gamma for every row, and a vector of float32(gamma) gives its bits.
-        log_mu [n] with rho_bar > 0 (both or neither): the behaviour log-probability of each row's action; the row's
-        weight becomes w_i min(rho_bar, pi / mu) (uavtrack_learner_ratio_weights, then the weighted update); a NaN or
-        positive log_mu refuses the update on the device."""
-        if (log_mu is None) != (rho_bar is None):
-            raise ValueError("update: log_mu and rho_bar come together")
+        log_mu [n], the behaviour log-probability of each row's action, comes with exactly one of rho_bar and clip_eps.
+        rho_bar > 0: the row's weight becomes w_i min(rho_bar, pi / mu) (uavtrack_learner_ratio_weights, then the
+        weighted update).  clip_eps >= 0 (loss="per_sample"): the clipped surrogate of the module docstring
+        (uavtrack_learner_update_clipped), ratio_out [n] (optional) receiving the ratios.  Either way a NaN or positive
+        log_mu refuses the update on the device."""
+        if rho_bar is not None and clip_eps is not None:
+            raise ValueError("update: clip_eps together with rho_bar: one correction for who acted, not two")
+        if (log_mu is None) != (rho_bar is None and clip_eps is None):
+            raise ValueError("update: log_mu and rho_bar come together (log_mu comes with exactly one of rho_bar and "
+                             "clip_eps)")
+        if ratio_out is not None and clip_eps is None:
+            raise ValueError("update: ratio_out needs clip_eps")
+        if clip_eps is not None:
+            self._clip_eps_arg(clip_eps)
         dev = self.device
         s = torch.as_tensor(transition_dict["states"], device=dev, dtype=torch.float32).reshape(-1, _lib.OBS_DIM).contiguous()
         n = s.shape[0]
@@ -442,21 +506,24 @@ class DeviceActorCritic(Handle):
             weights = torch.as_tensor(weights, device=dev, dtype=torch.float32).reshape(-1).contiguous()
         if discounts is not None:
             discounts = torch.as_tensor(discounts, device=dev, dtype=torch.float32).reshape(-1).contiguous()
-        if rho_bar is not None:
+        if log_mu is not None:
             log_mu = torch.as_tensor(log_mu, device=dev, dtype=torch.float32).reshape(-1).contiguous()
+        if rho_bar is not None:
             weights = self._ratio_weights(n, store, log_mu, n, None, rho_bar, weights, torch.empty(n, device=dev), None)
-        return self._run(n, store, n, None, None, weights, discounts)
+            return self._run(n, store, n, None, None, weights, discounts)
+        return self._run(n, store, n, None, None, weights, discounts, log_mu, clip_eps, ratio_out)
 
     def update_from(self, buffer, batch_size: int, beta: float = 0.4,
                     generator: Optional[torch.Generator] = None, group=None, importance: bool = False,
                     beta_final: Optional[float] = None, anneal_calls: int = 0, rho_bar: Optional[float] = None,
-                    rho_out: Optional[torch.Tensor] = None):
+                    rho_out: Optional[torch.Tensor] = None, clip_eps: Optional[float] = None,
+                    ratio_out: Optional[torch.Tensor] = None):
         """buffer.sample(batch_size) + update + (prioritised buffer) update_priorities(indices, |td_delta|)
         (train.py:253-262), the gather and the priority write inside the library call.  The indices are drawn as
         the buffer's own sample() draws them.  For a ReplayRing or a PrioritizedReplayRing the draw is one library call
         of its own, so the whole update is two library calls (three with rho_bar) with no torch kernel between them,
-        and can be captured into a graph.  beta, generator, importance, beta_final, anneal_calls, rho_bar, rho_out: the
-        fields of replay.DrawSpec, documented there; the defaults are the reference's update.
+        and can be captured into a graph.  beta, generator, importance, beta_final, anneal_calls, rho_bar, rho_out,
+        clip_eps, ratio_out: the fields of replay.DrawSpec, documented there; the defaults are the reference's update.
 
         An n-step ring (ring.with_nstep(n_step, gamma)) brings its per-slot discounts: the target is then
         r + discounts[slot] * V(s'), gathered in the same library call.  Its gamma must be this learner's (as float32).
@@ -467,7 +534,7 @@ class DeviceActorCritic(Handle):
         Ranks that start equal (sharding.broadcast_learner) stay bitwise equal; batch sizes may differ between ranks.
         The returned losses are the global ones, td_delta this rank's."""
         spec = DrawSpec(importance=importance, beta=beta, beta_final=beta_final, anneal_calls=anneal_calls,
-                        rho_bar=rho_bar, rho_out=rho_out, generator=generator)
+                        rho_bar=rho_bar, rho_out=rho_out, generator=generator, clip_eps=clip_eps, ratio_out=ratio_out)
         if group is None:
             return self._run(*self._drawn_batch(buffer, batch_size, spec, "update_from"))
         from .sharding import gather_learner_rows
@@ -481,20 +548,24 @@ class DeviceActorCritic(Handle):
 
     def _grad(self, n: int, store: Dict[str, torch.Tensor], capacity: int, idx: Optional[torch.Tensor],
               row: Optional[torch.Tensor] = None, td: Optional[torch.Tensor] = None,
-              weights: Optional[torch.Tensor] = None, discounts: Optional[torch.Tensor] = None):
+              weights: Optional[torch.Tensor] = None, discounts: Optional[torch.Tensor] = None,
+              log_mu: Optional[torch.Tensor] = None, clip_eps: Optional[float] = None,
+              ratio_out: Optional[torch.Tensor] = None):
         if row is None:
             row = torch.empty(self.row_floats, device=self.device)
         _lib.tensor_arg(row, torch.float32, self.row_floats, self.device,
                         f"row must be a contiguous float32 tensor of {self.row_floats} words on {self.device}")
         if td is None:
             td = torch.empty(n, device=self.device)
-        self._launch("grad", n, store, capacity, idx, weights, discounts, td, row)
+        self._launch("grad", n, store, capacity, idx, weights, discounts, td, row,
+                     clip=None if clip_eps is None else (log_mu, clip_eps, ratio_out))
         return row, td
 
     def grad_from(self, buffer, batch_size: int, row: Optional[torch.Tensor] = None,
                   generator: Optional[torch.Generator] = None, importance: bool = False, beta: float = 0.4,
                   beta_final: Optional[float] = None, anneal_calls: int = 0, rho_bar: Optional[float] = None,
-                  rho_out: Optional[torch.Tensor] = None):
+                  rho_out: Optional[torch.Tensor] = None, clip_eps: Optional[float] = None,
+                  ratio_out: Optional[torch.Tensor] = None):
         """The gradient half of update_from: draws min(batch_size, buffer.count) rows as update_from does (for a
         ReplayRing or PrioritizedReplayRing the ring's own library call) and leaves their unscaled gradient and loss sums
         in `row` (a new tensor if None).  Returns (row, td_delta, indices); changes nothing in the learner.  The indices
@@ -503,11 +574,12 @@ class DeviceActorCritic(Handle):
         row's sums carry the weights it describes."""
         return self._grad_drawn(buffer, batch_size, DrawSpec(
             importance=importance, beta=beta, beta_final=beta_final, anneal_calls=anneal_calls, rho_bar=rho_bar,
-            rho_out=rho_out, generator=generator), row)
+            rho_out=rho_out, generator=generator, clip_eps=clip_eps, ratio_out=ratio_out), row)
 
     def _grad_drawn(self, buffer, batch_size: int, spec: DrawSpec, row: Optional[torch.Tensor]):
         b = self._drawn_batch(buffer, batch_size, spec, "grad_from")
-        row, td = self._grad(b.n, b.store, b.capacity, b.idx, row, None, b.weights, b.discounts)
+        row, td = self._grad(b.n, b.store, b.capacity, b.idx, row, None, b.weights, b.discounts, b.log_mu, b.clip_eps,
+                             b.ratio_out)
         return row, td, b.idx
 
     def apply(self, rows):
@@ -536,22 +608,27 @@ class DeviceActorCritic(Handle):
 
     def update_from_many(self, buffers, batch_size: int, generator: Optional[torch.Generator] = None,
                          importance: bool = False, beta: float = 0.4, beta_final: Optional[float] = None,
-                         anneal_calls: int = 0, rho_bar: Optional[float] = None, rho_out=None):
+                         anneal_calls: int = 0, rho_bar: Optional[float] = None, rho_out=None,
+                         clip_eps: Optional[float] = None, ratio_out=None):
         """ONE update from several buffers on this device (the shards of one GPU): one gradient row per buffer from
         min(batch_size, its count) of its rows, the rows applied in list order, each prioritised buffer's priorities
         written back from its own draw.  Returns (actor_loss, critic_loss, [td_delta per buffer]).  The other arguments
         are the fields of replay.DrawSpec, one spec for every buffer (each draw's weights normalised by its own maximum,
-        with rho_bar every buffer a behaviour ring), except rho_out: a sequence of one float32 [k] tensor (or None) per
-        buffer."""
+        with rho_bar or clip_eps every buffer a behaviour ring), except rho_out and ratio_out: each a sequence of one
+        float32 [k] tensor (or None) per buffer."""
         buffers = list(buffers)
         if not 1 <= len(buffers) <= _lib.LEARNER_MAX_ROWS:
             raise ValueError(f"update_from_many: {len(buffers)} buffers, one apply takes 1 to {_lib.LEARNER_MAX_ROWS} rows")
         spec = DrawSpec(importance=importance, beta=beta, beta_final=beta_final, anneal_calls=anneal_calls,
-                        rho_bar=rho_bar, generator=generator)
+                        rho_bar=rho_bar, generator=generator, clip_eps=clip_eps)
         rho_outs = [None] * len(buffers) if rho_out is None else list(rho_out)
         if len(rho_outs) != len(buffers):
             raise ValueError(f"update_from_many: rho_out holds {len(rho_outs)} entries for {len(buffers)} buffers")
-        return self._update_split(buffers, batch_size, [spec._replace(rho_out=r) for r in rho_outs])
+        ratio_outs = [None] * len(buffers) if ratio_out is None else list(ratio_out)
+        if len(ratio_outs) != len(buffers):
+            raise ValueError(f"update_from_many: ratio_out holds {len(ratio_outs)} entries for {len(buffers)} buffers")
+        return self._update_split(buffers, batch_size,
+                                  [spec._replace(rho_out=r, ratio_out=q) for r, q in zip(rho_outs, ratio_outs)])
 
     def _update_split(self, buffers, batch_size: int, specs, gather=None):
         """The split update behind update_from_many and update_from(group=): a gradient row per buffer, the rows as

@@ -17,7 +17,18 @@ import torch
 KEYS = ("states", "actions", "rewards", "next_states")
 
 
-class DrawSpec(NamedTuple):
+class _DrawFields(NamedTuple):
+    """DrawSpec's seven tuple fields, in the order they have always had."""
+    importance: bool = False
+    beta: float = 0.4
+    beta_final: Optional[float] = None
+    anneal_calls: int = 0
+    rho_bar: Optional[float] = None
+    rho_out: Optional[torch.Tensor] = None
+    generator: Optional[torch.Generator] = None
+
+
+class DrawSpec(_DrawFields):
     """How DeviceActorCritic.update_from, grad_from, update_from_many and the group path draw a batch from a buffer and
     weigh its rows: each builds one of these from its arguments and hands it to the buffer's _draw_batch(k, spec), which
     returns (indices, weights or None).  The defaults enqueue exactly the reference's update: sample(), the unweighted
@@ -40,14 +51,31 @@ class DrawSpec(NamedTuple):
                   the unweighted delta and |delta|; on an n-step or lambda ring the ratio corrects the first action only.
                   Participants of one update (ranks, shards) must pass equal rho_bar.
     rho_out       float32 [k], optional, needs rho_bar: receives the ratios.
+    clip_eps      >= 0 (inf never clips), a ring made with_behaviour(), a loss="per_sample" learner, not together with
+                  rho_bar (one correction for who acted, not two): the update trains PPO's clipped surrogate
+                  min(r A, clip(r, 1 - eps, 1 + eps) A) with r = pi / mu from the ring's log_mu store and A = td_delta,
+                  formed inside the gradient kernel (uavtrack_learner_update_clipped / _grad_clipped; no further library
+                  call); the critic, td_delta and the priorities stay what they are.  importance composes: w_i is the
+                  draw's weight.  A drawn slot whose log_mu is NaN (unknown) or positive, or whose ratio is not finite,
+                  refuses the update on the device.  Participants of one update (ranks, shards) must pass equal clip_eps.
+    ratio_out     float32 [k], optional, needs clip_eps: receives the ratios r_i (NaN for a row that refused).
+    clip_eps and ratio_out are keyword-only attributes beside the seven tuple fields (which keep their order and their
+    number for whoever unpacks a spec); _replace takes them like fields.
     generator     the torch.Generator of a torch buffer's draw; a ring draws from its own seed and device call counter."""
-    importance: bool = False
-    beta: float = 0.4
-    beta_final: Optional[float] = None
-    anneal_calls: int = 0
-    rho_bar: Optional[float] = None
-    rho_out: Optional[torch.Tensor] = None
-    generator: Optional[torch.Generator] = None
+    clip_eps: Optional[float] = None
+    ratio_out: Optional[torch.Tensor] = None
+
+    def __new__(cls, *args, clip_eps: Optional[float] = None, ratio_out: Optional[torch.Tensor] = None, **kw):
+        self = super().__new__(cls, *args, **kw)
+        self.clip_eps, self.ratio_out = clip_eps, ratio_out
+        return self
+
+    def _replace(self, **kw):
+        clip = {k: kw.pop(k, getattr(self, k)) for k in ("clip_eps", "ratio_out")}
+        return type(self)(*super()._replace(**kw), **clip)
+
+    def __repr__(self):
+        return f"{super().__repr__()[:-1]}, clip_eps={self.clip_eps!r}, ratio_out={self.ratio_out!r})"
 
 
 def transitions_from_rollout(obs_in: torch.Tensor, out: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:

@@ -40,7 +40,9 @@ actions, so one path serves every add form and no add kernel changes).  That is 
 time is the one that acted: add before the iteration's updates.  The rollout's actor runs on the f16 matrix cores "at
 fp32 accuracy", so mu is the acting distribution to that accuracy, not to the bit.  DeviceActorCritic.update_from(ring,
 k, rho_bar=R) turns the store into truncated importance ratios min(R, pi / mu), one weight per batch row; they correct
-the first action of a transition only (on an n-step or lambda ring the rest of the window stays uncorrected).  Without
+the first action of a transition only (on an n-step or lambda ring the rest of the window stays uncorrected).
+update_from(ring, k, clip_eps=E) reads the same store inside the gradient kernel for PPO's clipped surrogate instead
+(uavtrack_learner_update_clipped); a drawn slot that is still NaN refuses that update on the device.  Without
 with_behaviour a ring is exactly what it was.
 """
 from __future__ import annotations

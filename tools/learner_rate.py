@@ -11,6 +11,7 @@ softmax, losses and Adam are not counted.
     python tools/learner_rate.py [--quick]
     python tools/learner_rate.py --regularised [--quick]
     python tools/learner_rate.py --target [--quick]
+    python tools/learner_rate.py --clipped
 
 --regularised times the device update alone (loss="per_sample") under four settings of
 DeviceActorCritic.set_regularisation: everything off, the entropy bonus on, clipping on, both.  "off" enqueues the
@@ -20,6 +21,14 @@ launches of the plain update; the clip adds two small launches and one more pass
 target, Polyak (tau = 0.005) and periodic (period = 100).  "off" enqueues the launches of the plain update; a target
 swaps the gradient kernel for the instantiation that forms V(s') over the second critic block and adds one small
 launch over 14 H + 1 words behind the Adam kernel.
+
+--clipped times DeviceActorCritic.update_from (loss="per_sample") at n = 65 536, H = 128, A = 12 from a uniform
+behaviour ring of 2 M slots, without and with clip_eps = 0.2 (the clipped surrogate: the gradient kernel's
+instantiation that gathers log_mu and gates each row; no further launch), the two alternating, medians of 7 runs of 20
+back-to-back calls.  A/B against another build of the library: run the tool once per library, alternating, three
+processes each, with UAVTRACK_LIB=<path> UAVTRACK_LIB_OLDER_OK=1; a library without the clipped symbols prints only its
+"plain" figure.  The plain figure of this build may not lie above the slowest of the other build's three (DESIGN.md
+section 4.11's rule); the clipped figure is reported, not a pass mark.
 """
 import argparse
 import json
@@ -97,6 +106,33 @@ def sweep(args, grid, dev, A, settings):
         print(json.dumps(out), flush=True)
 
 
+def clipped(n=65536, H=128, A=12, slots=1 << 21):
+    """update_from without and with clip_eps from one uniform behaviour ring: one JSON line."""
+    sys.path.insert(0, os.path.join(ROOT, "tools"))
+    from nstep_rate import alternating
+    from offpolicy_rate import filled
+    names = ["plain"] + (["clipped"] if hasattr(uavtrack._lib.load(), "uavtrack_learner_update_clipped") else [])
+    learners = {k: uavtrack.DeviceActorCritic(12, H, A, 1e-4, 5e-4, 0.95, "cuda:0", loss="per_sample", max_batch=n)
+                for k in names}
+    ring = filled(uavtrack.ReplayRing(slots, "cuda:0", seed=1, max_batch=n).with_behaviour(), learners["plain"])
+    ratio = torch.empty(n, device="cuda:0")
+    calls = {"plain": lambda: learners["plain"].update_from(ring, n)}
+    if "clipped" in names:
+        calls["clipped"] = lambda: learners["clipped"].update_from(ring, n, clip_eps=0.2, ratio_out=ratio)
+    res = alternating(calls, reps=20)
+    out = {"what": "update_from", "ring": "uniform", "n": n, "H": H, "A": A, "slots": slots,
+           "lib": os.environ.get("UAVTRACK_LIB", "this build")}
+    for name, (med, runs) in res.items():
+        out[name + "_us"] = round(med, 1)
+        out[name + "_runs_us"] = [round(x, 1) for x in runs]
+    if "clipped" in names:
+        out["clipped_share"] = round(float(((ratio - 1).abs() > 0.2).float().mean()), 4)
+    for x in list(learners.values()) + [ring]:
+        x.check()
+        x.close()
+    print(json.dumps(out), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--quick", action="store_true", help="n 65536, H 128 only")
@@ -104,11 +140,15 @@ def main():
                     help="time the device update with the entropy bonus and the gradient-norm clip off / on")
     ap.add_argument("--target", action="store_true",
                     help="time the device update without a target critic, with Polyak averaging and with a periodic copy")
+    ap.add_argument("--clipped", action="store_true",
+                    help="time update_from at n 65536, H 128 from a uniform behaviour ring without and with clip_eps = 0.2")
     ap.add_argument("--settings", default=None, help="--regularised: a comma-separated subset of off,entropy,clip,both; "
                                                      "--target: of off,polyak,periodic")
     ap.add_argument("--reps", type=int, default=100)
     ap.add_argument("--runs", type=int, default=5)
     args = ap.parse_args()
+    if args.clipped:
+        return clipped()
     dev = "cuda:0"
     A = 12
     grid = [(65536, 128)] if args.quick else [(n, H) for H in (64, 128, 256) for n in (4096, 65536, 262144)]
