@@ -2,7 +2,7 @@
 definitions of include/uavtrack.h.
 
 Critic values.  V(x) of a row x[12]: p_j = b1c[j]; p_j = fma(W1c[j][k], x[k], p_j) for k = 0 .. 11; h_j = max(p_j, 0);
-z = b2c[0]; z = fma(W2c[j], h_j, z) for j = 0 .. H - 1; V = z.  The mirror evaluates it in float64 (critic_forward) and
+z = b2c[0]; z = fma(W2c[j], h_j, z) for j = 0 .. H - 1; V = z.  The mirror evaluates it in float64 (critic_forward, learner_mirror.values64) and
 gives the magnitude bound m(x) = sum_j |W2_j| (sum_k |W1_jk| |x_k| + |b1_j|) + |b2| the fp32 chain's error scales with.
 
 Lambda-return transitions.  T steps, agents = envs * n_uav, f = t * agents + b * n_uav + i; values[t][b][i] is meant to
@@ -16,6 +16,7 @@ The stored transition is the one-step transition of uavtrack_replay_add_rollout_
 d_t; slots, window, wrap and priorities as the other adds (nstep_mirror.ring_add)."""
 import numpy as np
 
+import learner_mirror as mirror
 import nstep_mirror as nm
 
 f32 = np.float32
@@ -81,9 +82,7 @@ def critic_of(blob, H, A):
 
 def critic_forward(blob, H, A, x):
     """V(x) [n] in float64 for rows x [n][12]."""
-    W1, b1, W2, b2 = (np.asarray(a, np.float64) for a in critic_of(blob, H, A))
-    h = np.maximum(np.asarray(x, np.float64) @ W1.T + b1, 0.0)
-    return h @ W2 + b2
+    return mirror.values64(mirror.critic_block(np.asarray(blob, f32), H, A), H, x)
 
 
 def critic_magnitude(blob, H, A, x):

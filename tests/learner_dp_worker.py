@@ -21,8 +21,8 @@ COUNTS = (3000, 1777)            # transitions in each rank's ring: below BATCH,
 
 
 def rank_data(rank):
-    import learner_dp_mirror as dp
-    return dp.batch(np.random.RandomState(500 + rank), COUNTS[rank], A)
+    import learner_harness as lh
+    return lh.batch(np.random.RandomState(500 + rank), COUNTS[rank], A)
 
 
 def ring_for(rank, dev):
@@ -39,10 +39,10 @@ def ring_for(rank, dev):
 
 
 def learner_for(seed, dev):
-    import learner_dp_mirror as dp
+    import learner_harness as lh
     import uavtrack
     L = uavtrack.DeviceActorCritic(12, H, A, LRS[0], LRS[1], GAMMA, dev, max_batch=BATCH)
-    L._set_params(dp.init_blob(H, A, seed))
+    L._set_params(lh.init_blob(H, A, seed))
     return L
 
 

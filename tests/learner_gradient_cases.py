@@ -5,9 +5,8 @@ whole-blob bound learner_harness.tol_g stays what it is; this sits beside it.
 Two observables, one float64 result (`fp64`).  The gradient row of DeviceActorCritic._grad holds the P UNSCALED sums
 the gradient kernel accumulates and the four loss sums; a fresh learner's closed update leaves exp_avg = fl(0.1f g), g
 the SCALED (and, with a finite max_grad_norm, clipped) gradient, read back by pmi_gradient_cases.recovered_gradient.
-`fp64` is a wrapper over the existing mirrors: y_i = r_i + d_i V_target(s'_i) (learner_target_mirror.bootstrapped; the
-online critic's block while no target is enabled) handed with gamma = 0 to learner_regularised_mirror._terms, which
-carries weights and the entropy term, and learner_weighted_mirror._backward.
+`fp64` is tests/learner_mirror.py's forward (theta= the target block, None while no target is enabled; discount= the
+rows' discounts), terms (weights and the entropy term) and backward.
 
 The metric.  `gradient_scales` returns S per element: for an unscaled sum the float64 sum over the batch's rows of the
 absolute terms (sum_r |dh_rj| |s_rk| for a layer-1 weight with |dh_rj| = mask_rj sum_o |W2_oj| |gz_ro|, sum_r |gz_ro| ha_rj
@@ -28,13 +27,13 @@ float32 emulation of that chain reproduces to the bit, 5.5e-8 away: 1.6e-4 of S 
 The case's condition, asserted for every case (`margin`): the smallest |pre-activation| is at least MARGIN_FACTOR = 16
 times the largest |pre_fp32 - pre_fp64| of a numpy float32 forward.
 
-Parameters: learner_dp_mirror.init_blob ("default"); "peaked" scales the actor's fc2 so that the widest logit spread of
+Parameters: learner_harness.init_blob ("default"); "peaked" scales the actor's fc2 so that the widest logit spread of
 the batch is 40 (a trained, confident policy: probabilities down to e^-40, the spread below 60 so that logf(p) never
-sees a denormal); a target block is an independent draw.  Inputs: learner_dp_mirror.batch, rewards shifted by +1.5 in
+sees a denormal); a target block is an independent draw.  Inputs: learner_harness.batch, rewards shifted by +1.5 in
 every other reference-loss case (mean(delta) away from 0) and, where a row's delta would lie within MIN_DELTA = 0.25 of
 zero, moved by that much away from it (delta is a difference of two values; a unit that is on in a few rows only would
 make the relative error of one small delta most of an element, for whoever computes in fp32: torch's autograd on two
-CPUs differed by a factor of 3.4 there), weights from learner_weighted_mirror.make_weights (exact zeros, a maximum of
+CPUs differed by a factor of 3.4 there), weights from learner_harness.make_weights (exact zeros, a maximum of
 exactly 1), per-slot discounts from {g, g^2, g^3, 0, 1}, g = float32(0.95).  `dead` cases push one unit of each network
 below every row.
 
@@ -89,11 +88,8 @@ import zlib
 
 import numpy as np
 
-import learner_dp_mirror as dp
+import learner_harness as lh
 import learner_mirror as mirror
-import learner_regularised_mirror as rm
-import learner_target_mirror as tm
-import learner_weighted_mirror as wm
 import pmi_gradient_cases as pc
 
 F32 = np.float32
@@ -241,8 +237,7 @@ def margin(c, blob=None, theta=None, rows=None):
 
 def logit_spread(blob, H, A, s):
     """The widest max - min of a row's logits, in float64."""
-    w1a, b1a, w2a, b2a = mirror.unpack(blob, H, A)[:4]
-    z = np.maximum(np.asarray(s, np.float64) @ w1a.T + b1a, 0) @ w2a.T + b2a
+    z = mirror.logits(blob, H, A, s)
     return float((z.max(axis=1) - z.min(axis=1)).max())
 
 
@@ -252,17 +247,17 @@ def _build(sp, halves):
     seed = zlib.crc32(repr((tuple(sp), halves)).encode()) % (2 ** 31 - 1)
     rng = np.random.RandomState(seed)
     cap = halves * n + (7 if sp.gather else 0)
-    blob = dp.init_blob(H, A, seed)
+    blob = lh.init_blob(H, A, seed)
     has_target = sp.body in ("target", "all")
-    theta = tm.critic_block(dp.init_blob(H, A, seed + 5000), H, A) if has_target else None
-    s, a, r, s2 = dp.batch(rng, cap, A)
+    theta = mirror.critic_block(lh.init_blob(H, A, seed + 5000), H, A) if has_target else None
+    s, a, r, s2 = lh.batch(rng, cap, A)
     if sp.shift:
         r = (r + F32(1.5)).astype(F32)
     if sp.gather:
         idx = [rng.randint(0, cap, size=n).astype(np.int64) for _ in range(halves)]
     else:
         idx = [np.arange(h * n, (h + 1) * n) for h in range(halves)]
-    weights = [wm.make_weights(rng, n) for _ in range(halves)] if sp.body in ("weighted", "discounted", "all") else None
+    weights = [lh.make_weights(rng, n) for _ in range(halves)] if sp.body in ("weighted", "discounted", "all") else None
     g = F32(GAMMA)
     disc = rng.choice(np.array([g, g * g, g * g * g, 0.0, 1.0], F32), size=cap).astype(F32) \
         if sp.body in ("discounted", "all") else None
@@ -281,9 +276,8 @@ def _build(sp, halves):
         blob[o[2]:o[4]] = (blob[o[2]:o[4]].astype(np.float64) * f).astype(F32)
     # no row's delta within MIN_DELTA of zero: delta is a difference of two values, and a unit that is on in a few rows
     # only would make the relative error of one small delta most of an element
-    th = theta if theta is not None else tm.critic_block(blob, H, A)
     dslot = np.full(cap, F32(GAMMA), F32) if disc is None else disc
-    delta = tm.bootstrapped(th, H, r, s2, dslot) - tm.values64(tm.critic_block(blob, H, A), H, s)
+    delta = mirror.forward(blob, H, A, s, a, r, s2, dslot, theta).delta
     near = np.abs(delta) < MIN_DELTA
     r = np.where(near, r + np.where(delta >= 0, MIN_DELTA, -MIN_DELTA), r).astype(F32)
     c = types.SimpleNamespace(
@@ -324,7 +318,7 @@ def _scaled(c, sums, loss4, n, md=None, swap=False):
     na = mirror.layout(c.H, c.A)[1][4]
     sa, sc = (-md / n if c.loss == "reference" else -1.0 / n), 2.0 / n
     g = sums * np.concatenate([np.full(na, sa), np.full(sums.size - na, sc)])
-    coef = rm.clip(g, c.H, c.A, c.mgn)[0] if c.mgn else np.ones(2)
+    coef = mirror.clip_grad_norm(g, c.H, c.A, c.mgn)[0] if c.mgn else np.ones(2)
     if swap:
         coef = coef[::-1]
     g = g * np.concatenate([np.full(na, coef[0]), np.full(sums.size - na, coef[1])])
@@ -333,26 +327,22 @@ def _scaled(c, sums, loss4, n, md=None, swap=False):
 
 
 def pieces(c, h=0, blob=None, theta=None):
-    """The per-row pieces of batch h in float64 at `blob` / `theta` (default: the case's): the forward dict, the logit
-    weights gz [n][A], the value weights gv [n], the four loss terms lt [4][n], the entropies."""
-    blob = c.blob if blob is None else blob
-    theta = c.theta if theta is None else theta
+    """The per-row pieces of batch h in float64 at `blob` / `theta` (default: the case's): the forward record, the logit
+    weights gz [n][A], the value weights gv [n], the four loss terms lt [4][n]."""
     (s, a, r, s2), w, d = batch_of(c, h)
-    th = tm.critic_block(blob, c.H, c.A) if theta is None else theta
-    y = tm.bootstrapped(th, c.H, r, s2, d)
-    f, _, gz, gv, lt, ent = rm._terms(blob, c.H, c.A, s, a, y, s2, 0.0, c.loss, w, c.c)
-    return f, gz, gv, lt, ent
+    f = mirror.forward(c.blob if blob is None else blob, c.H, c.A, s, a, r, s2, d, c.theta if theta is None else theta)
+    return (f, *mirror.terms(f, c.loss, w, c.c)[:3])
 
 
 def fp64(c, h=0, blob=None, theta=None):
     """The float64 result of batch h: sums [P] (unscaled), loss4, grad [P] (scaled, clipped), td, the two losses, the
     clip coefficients, and S_row [P + 4], S_grad [P] from gradient_scales."""
-    f, gz, gv, lt, ent = pieces(c, h, blob, theta)
-    sums, loss4 = wm._backward(f, gz, gv), lt.sum(axis=1)
-    g, coef, sa, sc, al, cl = _scaled(c, sums, loss4, f["n"])
+    f, gz, gv, lt = pieces(c, h, blob, theta)
+    sums, loss4 = mirror.backward(f, gz, gv), lt.sum(axis=1)
+    g, coef, sa, sc, al, cl = _scaled(c, sums, loss4, f.n)
     S_row, S_grad = gradient_scales(c, f, gz, gv, lt, coef)
-    return types.SimpleNamespace(sums=sums, loss4=loss4, grad=g, td=f["delta"], actor_loss=al, critic_loss=cl, coef=coef,
-                                 entropy=ent, S_row=S_row, S_grad=S_grad)
+    return types.SimpleNamespace(sums=sums, loss4=loss4, grad=g, td=f.delta, actor_loss=al, critic_loss=cl, coef=coef,
+                                 entropy=f.entropy, S_row=S_row, S_grad=S_grad)
 
 
 def _network_factors(c, lt, n, coef, size):
@@ -364,12 +354,12 @@ def _network_factors(c, lt, n, coef, size):
 
 def gradient_scales(c, f, gz, gv, lt, coef=(1.0, 1.0)):
     """(S of the row's P + 4 words, S of the scaled gradient's P words): the float64 sums of the absolute terms."""
-    n = f["n"]
-    sa_, agz, agv = np.abs(f["s"]), np.abs(gz), np.abs(gv)
-    adh = (agz @ np.abs(f["w2a"])) * (f["pa"] > 0)
-    adc = agv[:, None] * np.abs(f["w2c"]) * (f["pc"] > 0)
-    S = np.concatenate([x.ravel() for x in (adh.T @ sa_, adh.sum(0), agz.T @ f["ha"], agz.sum(0), adc.T @ sa_, adc.sum(0),
-                                            (agv[:, None] * f["hc"]).sum(0), np.array([agv.sum()]))])
+    n = f.n
+    sa_, agz, agv = np.abs(f.s), np.abs(gz), np.abs(gv)
+    adh = (agz @ np.abs(f.w2a)) * (f.pa > 0)
+    adc = agv[:, None] * np.abs(f.w2c) * (f.pc > 0)
+    S = np.concatenate([x.ravel() for x in (adh.T @ sa_, adh.sum(0), agz.T @ f.ha, agz.sum(0), adc.T @ sa_, adc.sum(0),
+                                            (agv[:, None] * f.hc).sum(0), np.array([agv.sum()]))])
     return np.concatenate([S, np.abs(lt).sum(axis=1)]), S * _network_factors(c, lt, n, coef, S.size)
 
 
@@ -402,7 +392,7 @@ def torch_fp32(c):
     t = lambda x: torch.from_numpy(np.ascontiguousarray(x, F32))
     prm = [t(x).requires_grad_() for x in mirror.unpack(c.blob, H, A)]
     w1a, b1a, w2a, b2a, w1c, b1c, w2c, b2c = prm
-    th = c.theta if c.theta is not None else tm.critic_block(c.blob, H, A)
+    th = c.theta if c.theta is not None else mirror.critic_block(c.blob, H, A)
     w1t, b1t, w2t, b2t = t(th[:12 * H].reshape(H, 12)), t(th[12 * H:13 * H]), t(th[13 * H:14 * H]), t(th[14 * H:])
     s, s2, r, d = t(s), t(s2), t(r), t(d)
     iw = torch.ones(n) if w is None else t(w)
@@ -431,7 +421,7 @@ def _finish32(c, sums, loss4):
     g = sums * np.concatenate([np.full(na, sa, F32), np.full(sums.size - na, F32(2.0) * inv_n, F32)])
     assert g.dtype == F32
     if c.mgn:
-        coef = rm.clip(g.astype(np.float64), c.H, c.A, c.mgn)[0].astype(F32)
+        coef = mirror.clip_grad_norm(g.astype(np.float64), c.H, c.A, c.mgn)[0].astype(F32)
         g = g * np.concatenate([np.full(na, coef[0], F32), np.full(sums.size - na, coef[1], F32)])
     return np.concatenate([sums, loss4]).astype(np.float64), g.astype(np.float64)
 
@@ -442,7 +432,7 @@ def sequential_fp32(c):
     (s, a, r, s2), w, d = batch_of(c)
     H, A, n = c.H, c.A, c.n
     w1a, b1a, w2a, b2a, w1c, b1c, w2c, b2c = (x.astype(F32) for x in mirror.unpack(c.blob, H, A))
-    th = (c.theta if c.theta is not None else tm.critic_block(c.blob, H, A)).astype(F32)
+    th = (c.theta if c.theta is not None else mirror.critic_block(c.blob, H, A)).astype(F32)
     iw = np.ones(n, F32) if w is None else w.astype(F32)
     pa = s @ w1a.T + b1a; ha = np.maximum(pa, 0)
     z = ha @ w2a.T + b2a

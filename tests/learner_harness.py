@@ -1,7 +1,7 @@
 """What the device learner's GPU tests share (tests/test_hip_learner*.py, test_hip_nstep.py, test_hip_lambda.py): the
-learner and its cases, one update or gradient row through Python or straight through an entry point, and the bounds
-against the float64 mirror.  Imports without a GPU: uavtrack is imported inside functions, and nothing touches DEV
-until a function that needs it is called.
+learner and its cases (the host half of every case is drawn here, without a GPU), one update or gradient row through
+Python or straight through an entry point, and the bounds against the float64 mirror.  Imports without a GPU: uavtrack
+is imported inside functions, and nothing touches DEV until a function that needs it is called.
 
 The bounds (a single update from zero moments against tests/learner_mirror.py): td_delta and the losses within 2e-5 of
 their magnitude scale; the gradient (exp_avg / 0.1 after one step) within tol_g, 2e-6 (1 + log2 n) of its largest element;
@@ -14,7 +14,6 @@ import types
 import numpy as np
 import torch
 
-import learner_dp_mirror as dp
 import learner_mirror as mirror
 
 DEV = "cuda:0"
@@ -50,20 +49,91 @@ def dev(x):
     return torch.from_numpy(np.ascontiguousarray(x)).to(DEV)
 
 
+def init_blob(H, A, seed):
+    """torch.nn.Linear's default initialisation of both networks as one fp32 blob."""
+    import uavtrack
+    torch.manual_seed(seed)
+    return np.concatenate([p.detach().numpy().ravel() for p in list(uavtrack.ActorMLP(12, H, A).parameters()) +
+                           list(uavtrack.ValueMLP(12, H).parameters())]).astype(np.float32)
+
+
+def batch(rng, n, A):
+    """A batch of n transitions for the learner tests: (states, actions, rewards, next_states)."""
+    s = rng.uniform(-1, 1, size=(n, 12)).astype(np.float32)
+    s2 = rng.uniform(-1, 1, size=(n, 12)).astype(np.float32)
+    s[:, 9:11] = rng.uniform(0, 5, size=(n, 2)); s2[:, 9:11] = rng.uniform(0, 5, size=(n, 2))
+    a = rng.randint(0, A, size=n).astype(np.int32)
+    r = rng.uniform(-2, 2, size=n).astype(np.float32)
+    return s, a, r, s2
+
+
+def make_weights(rng, n):
+    """Weights in [0, 1] with some exact zeros and the maximum exactly 1 (what a prioritised draw's weights / max look
+    like, plus the zeros): n = 1 is [1], n = 2 is a zero and a one."""
+    w = rng.uniform(0.0, 1.0, size=n).astype(np.float32)
+    if n >= 2:
+        zeros = rng.choice(n, size=max(1, n // 10), replace=False)
+        w[zeros] = 0.0
+        free = np.setdiff1d(np.arange(n), zeros)
+        w[free[rng.randint(free.size)]] = 1.0
+    else:
+        w[:] = 1.0
+    return w
+
+
+def cuts(n, K, seed=0):
+    """K uneven contiguous pieces of range(n): K - 1 distinct interior boundaries, every piece non-empty."""
+    if K == 1:
+        return [(0, n)]
+    b = np.sort(np.random.RandomState(seed + K).choice(np.arange(1, n), size=K - 1, replace=False))
+    edges = [0] + [int(x) for x in b] + [n]
+    return list(zip(edges[:-1], edges[1:]))
+
+
+def split(batch, pieces):
+    return [tuple(x[lo:hi] for x in batch) for lo, hi in pieces]
+
+
+TEETH = dict(H=128, A=12, n=6007, gamma=0.95, lrs=(1e-3, 5e-3), seed=21)
+
+
+def teeth_batch():
+    """(blob, (s, a, r, s2)): a batch whose rewards ramp by 6 from the first row to the last, so that every contiguous
+    shard has its own mean(delta) and a rule that scales a shard by its own mean shows.  n is not a multiple of the
+    gradient kernel's tile."""
+    c = TEETH
+    s, a, r, s2 = batch(np.random.RandomState(c["seed"]), c["n"], c["A"])
+    r = (r + np.linspace(-3.0, 3.0, c["n"])).astype(np.float32)
+    return init_blob(c["H"], c["A"], c["seed"]), (s, a, r, s2)
+
+
 _cases = {}
 
 
-def case(H, A, n, gather):
-    """(blob, host batch over the store, device store, capacity, host indices, device indices or None), built once."""
+def host_case(H, A, n, gather):
+    """(blob, host batch over the store, capacity, host indices), built once."""
     key = (H, A, n, gather)
     if key not in _cases:
         rng = np.random.RandomState(H * 1000 + n + (7 if gather else 0))
         cap = n + 7 if gather else n
-        b = dp.batch(rng, cap, A)
+        b = batch(rng, cap, A)
         idx = rng.randint(0, cap, size=n).astype(np.int64) if gather else np.arange(n)
-        store = {k: dev(x) for k, x in zip(STORES, b)}
-        _cases[key] = (dp.init_blob(H, A, H + n), b, store, cap, idx, dev(idx) if gather else None)
+        _cases[key] = (init_blob(H, A, H + n), b, cap, idx)
     return _cases[key]
+
+
+_device = {}
+
+
+def case(H, A, n, gather):
+    """host_case and its device copies: (blob, host batch, device store, capacity, host indices, device indices or
+    None), built once."""
+    key = (H, A, n, gather)
+    blob, b, cap, idx = host_case(*key)
+    if key not in _device:
+        _device[key] = ({k: dev(x) for k, x in zip(STORES, b)}, dev(idx) if gather else None)
+    store, it = _device[key]
+    return blob, b, store, cap, idx, it
 
 
 def gathered(b, idx):

@@ -9,11 +9,9 @@ f = t * agents + b * n_uav + i.  n = n_step in [1, 64]; g = float32(gamma), gamm
   Stored    state as uavtrack_replay_add_rollout_episodes stores it (obs_in at t == 0, start_obs[t - 1] behind a fired
             done, obs[t - 1] otherwise), actions[t], R, next_state = obs[t + m - 1], discount d; the slot, the window
             for T * agents > capacity, the wrap and the priorities as the other adds.
-  Target    y_i = r_i + d_i V(s'_i), d_i = discounts[slot of row i]; everything behind it as before."""
+  Target    y_i = r_i + d_i V(s'_i), d_i = discounts[slot of row i]; everything behind it as before (tests/learner_mirror.py
+            takes the gathered per-row array as its discount)."""
 import numpy as np
-
-import learner_regularised_mirror as rm
-import learner_weighted_mirror as wm
 
 MAX_NSTEP = 64
 f32 = np.float32
@@ -110,12 +108,3 @@ def ring_add(image, pos, count, trans):
         prio[slots] = top
     return (pos + n) % cap, min(cap, count + n)
 
-
-def learner(blob, H, A, s, a, r, s2, discounts, loss="reference", weights=None, entropy_coef=None):
-    """The learner mirrors with gamma as the gathered per-row array (their target = r + gamma * vn broadcasts):
-    (actor_loss, critic_loss, td_delta, flat gradient[, entropy]) in float64; entropy_coef None: the weighted mirror."""
-    d = np.asarray(discounts, np.float64)
-    assert d.shape == (len(a),)
-    if entropy_coef is None:
-        return wm.losses_and_grads(blob, H, A, s, a, r, s2, d, loss, weights)
-    return rm.losses_and_grads(blob, H, A, s, a, r, s2, d, loss, weights, entropy_coef)

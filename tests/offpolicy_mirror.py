@@ -1,6 +1,6 @@
 """float64 numpy mirror of the actor alone and of the truncated importance ratios (uavtrack_learner_log_probs,
-_log_probs_window, _ratio_weights), the window an add of n rows writes, and the bounds the device is held to.  Imports
-no uavtrack.
+_log_probs_window, _ratio_weights), the window an add of n rows writes, and the bounds the device is held to.  The
+actor is tests/learner_mirror.py's; imports no uavtrack.
 
     log p_a = (z_a - max_o z_o) - log sum_o exp(z_o - max),   z = W2a relu(W1a s + b1a) + b2a
     rho_i   = min(float32(rho_bar), exp(log p_i - log_mu_i)),  NaN where log_mu_i is NaN or > 0, where the slot lies
@@ -9,32 +9,20 @@ no uavtrack.
 """
 import numpy as np
 
-
-def actor_of(blob, H, A):
-    """(W1a [H][12], b1a [H], W2a [A][H], b2a [A]) of the learner's parameter blob, in float64."""
-    b = np.asarray(blob, np.float64)
-    o = np.cumsum([0, 12 * H, H, A * H, A])
-    return b[o[0]:o[1]].reshape(H, 12), b[o[1]:o[2]], b[o[2]:o[3]].reshape(A, H), b[o[3]:o[4]]
-
-
-def logits(blob, H, A, s):
-    w1, b1, w2, b2 = actor_of(blob, H, A)
-    return np.maximum(np.asarray(s, np.float64).reshape(-1, 12) @ w1.T + b1, 0) @ w2.T + b2
+import learner_mirror as mirror
 
 
 def log_probs(blob, H, A, s, a):
     """log pi(a_i | s_i) in float64 [n]; NaN where a_i is outside [0, A)."""
-    z = logits(blob, H, A, s)
+    logp = mirror.policy(blob, H, A, s)[0]
     a = np.asarray(a, np.int64).reshape(-1)
     ok = (a >= 0) & (a < A)
-    d = z - z.max(axis=1, keepdims=True)
-    lp = d[np.arange(len(a)), np.where(ok, a, 0)] - np.log(np.exp(d).sum(axis=1))
-    return np.where(ok, lp, np.nan)
+    return np.where(ok, logp[np.arange(len(a)), np.where(ok, a, 0)], np.nan)
 
 
 def scale(blob, H, A, s):
     """max_o |z_o| + log A per row: the scale of the log-softmax's inputs, which the bound on log p is taken at."""
-    return np.abs(logits(blob, H, A, s)).max(axis=1) + np.log(A)
+    return np.abs(mirror.logits(blob, H, A, s)).max(axis=1) + np.log(A)
 
 
 def log_prob_bound(blob, H, A, s):

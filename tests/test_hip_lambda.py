@@ -10,8 +10,8 @@ import pytest
 import torch
 
 import lambda_mirror as lm
-import learner_dp_mirror as dp
 import learner_harness as lh
+import learner_mirror as mirror
 import nstep_mirror as nm
 import ring_rollout_harness as rr
 from ring_rollout_harness import B, N, NTR, T
@@ -51,7 +51,7 @@ def _value_rows(n):
 @pytest.mark.parametrize("H", [1, 7, 128, 256])
 def test_values_are_the_updates_own_v_bitwise_and_the_fp64_forward_within_the_chains_bound(H, n):
     A = 5
-    blob = dp.init_blob(H, A, 100 + H)
+    blob = lh.init_blob(H, A, 100 + H)
     assert lm.critic_of(blob, H, A)[3] != 0                            # b2: V is never an exact zero by accident
     x, xd, act = _value_rows(n)
     L = lh.learner(H, A, "reference", blob, max_batch=n)
@@ -81,7 +81,7 @@ def test_values_read_the_parameters_of_the_moment_and_span_more_than_one_grid_pa
     """n beyond 2048 workgroups x 512 rows (the grid-stride loop's second pass) and beyond max_batch; after
     load_state_dict the same call gives the new critic's values."""
     H, A, n = 16, 5, 2048 * 512 + 700
-    blob = dp.init_blob(H, A, 7)
+    blob = lh.init_blob(H, A, 7)
     L = lh.learner(H, A, "reference", blob, max_batch=64)
     rng = np.random.RandomState(3)
     x = rng.uniform(-2, 2, (n, 12)).astype(np.float32)
@@ -92,7 +92,7 @@ def test_values_read_the_parameters_of_the_moment_and_span_more_than_one_grid_pa
     assert (np.abs(got - want) <= bound).all()
     tail = L.values(xd[-700:].contiguous()).cpu().numpy()              # the same rows in the first pass: the same bits
     assert tail.tobytes() == got[-700:].tobytes()
-    blob2 = dp.init_blob(H, A, 8)
+    blob2 = lh.init_blob(H, A, 8)
     L._set_params(blob2)
     got2 = L.values(xd[:1000].contiguous()).cpu().numpy()
     want2 = lm.critic_forward(blob2, H, A, x[:1000])
@@ -248,7 +248,7 @@ def test_values_add_and_update_end_to_end(kind):
     r = rr.rollout()
     done = rr.done("mid")
     out = rr.out(done)
-    blob = dp.init_blob(H, A, 42)
+    blob = lh.init_blob(H, A, 42)
     L = lh.learner(H, A, "reference", blob, max_batch=k)
     ring = _new_ring(kind, 100, max_batch=k).with_lambda(lam, GAMMA)
     ring.add_rollout(r["dev"]["obs_in"], out, critic=L)
@@ -265,7 +265,7 @@ def test_values_add_and_update_end_to_end(kind):
     al, cl, td = L.update_from(ring, k)
     L.check(); ring.check()
     idx = ring._idx[:k].cpu().numpy()
-    ral, rcl, rtd, _ = nm.learner(blob, H, A, *(tr[key][idx] for key in lh.STORES), tr["discounts"][idx], "reference")
+    ral, rcl, rtd = mirror.losses_and_grads(blob, H, A, *(tr[key][idx] for key in lh.STORES), tr["discounts"][idx], "reference")[:3]
     lh.assert_losses_and_td(al.cpu().numpy(), cl.cpu().numpy(), td.cpu().numpy(), ral, rcl, rtd)
     # a second add of the same shape allocates nothing
     ring.add_rollout(r["dev"]["obs_in"], out, critic=L)
@@ -306,7 +306,7 @@ def test_values_add_and_update_captured_and_replayed_equal_eager():
     H, A, k = 64, 12, 32
     r = rr.rollout()
     out = rr.out(rr.done("mid"))
-    blob = dp.init_blob(H, A, 42)
+    blob = lh.init_blob(H, A, 42)
 
     def fresh():
         return lh.learner(H, A, "reference", blob, max_batch=k), \
@@ -404,7 +404,7 @@ def test_host_side_errors_of_the_lambda_add_enqueue_nothing():
 def test_host_side_errors_of_values_enqueue_nothing():
     from uavtrack import _lib
     H, A, n = 64, 5, 63
-    L = lh.learner(H, A, "reference", dp.init_blob(H, A, 1), max_batch=n)
+    L = lh.learner(H, A, "reference", lh.init_blob(H, A, 1), max_batch=n)
     x, xd, _ = _value_rows(n)
     out = torch.full((n,), 7.0, device=DEV)
     before = lh.state(L)

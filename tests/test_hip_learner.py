@@ -6,7 +6,6 @@ import pytest
 import torch
 
 from conftest import load_golden
-import learner_dp_mirror as dp
 import learner_harness as lh
 import learner_mirror as mirror
 
@@ -60,16 +59,16 @@ def test_sweep_against_fp64_mirror(H, A, n, loss, gather):
     """One update against the float64 mirror, at the bounds tests/learner_harness.py states and explains."""
     rng = np.random.RandomState(H * 1000 + n)
     cap = n + 7 if gather else n
-    s, a, r, s2 = dp.batch(rng, cap, A)
+    s, a, r, s2 = lh.batch(rng, cap, A)
     idx = rng.randint(0, cap, size=n).astype(np.int64) if gather else np.arange(n)
-    blob = dp.init_blob(H, A, H + n)
+    blob = lh.init_blob(H, A, H + n)
     L = lh.learner(H, A, loss=loss, blob=blob, max_batch=max(n, 1))
     store = {"states": torch.from_numpy(s).to(DEV), "actions": torch.from_numpy(a).to(DEV),
              "rewards": torch.from_numpy(r).to(DEV), "next_states": torch.from_numpy(s2).to(DEV)}
     it = torch.from_numpy(idx).to(DEV) if gather else None
     al, cl, td = L._run(n, store, cap, it, None)
     L.check()
-    ral, rcl, rtd, g = mirror.losses_and_grads(blob, H, A, s[idx], a[idx], r[idx], s2[idx], 0.95, loss)
+    ral, rcl, rtd, g = mirror.losses_and_grads(blob, H, A, s[idx], a[idx], r[idx], s2[idx], 0.95, loss)[:4]
     lh.assert_losses_and_td(al.cpu().numpy(), cl.cpu().numpy(), td.cpu().numpy(), ral, rcl, rtd)
     lh.assert_step_from_zero(lh.state(L), blob, g, n, H, A)
 
@@ -81,7 +80,7 @@ def test_trajectory_tracks_fp64_torch_adam():
     u = _uav()
     H, A, n, lr = 64, 12, 4096, (1e-3, 5e-3)
     rng = np.random.RandomState(3)
-    blob = dp.init_blob(H, A, 5)
+    blob = lh.init_blob(H, A, 5)
     L = lh.learner(H, A, lr=lr, blob=blob)
     actor, critic = u.ActorMLP(12, H, A).double(), u.ValueMLP(12, H).double()
     params = list(actor.parameters()) + list(critic.parameters())
@@ -91,7 +90,7 @@ def test_trajectory_tracks_fp64_torch_adam():
             p.copy_(torch.from_numpy(blob[o:o + p.numel()].astype(np.float64)).view_as(p)); o += p.numel()
     oa, oc = torch.optim.Adam(actor.parameters(), lr=lr[0]), torch.optim.Adam(critic.parameters(), lr=lr[1])
     for _ in range(50):
-        s, a, r, s2 = dp.batch(rng, n, A)
+        s, a, r, s2 = lh.batch(rng, n, A)
         L.update({"states": torch.from_numpy(s).to(DEV), "actions": torch.from_numpy(a).to(DEV),
                   "rewards": torch.from_numpy(r).to(DEV), "next_states": torch.from_numpy(s2).to(DEV)})
         S, S2, R = (torch.from_numpy(x.astype(np.float64)) for x in (s, s2, r))
@@ -112,11 +111,11 @@ def test_trajectory_tracks_fp64_torch_adam():
 def _setup_det(H=128, A=12, n=4096, seed=9):
     rng = np.random.RandomState(seed)
     cap = n + 100
-    s, a, r, s2 = dp.batch(rng, cap, A)
+    s, a, r, s2 = lh.batch(rng, cap, A)
     store = {"states": torch.from_numpy(s).to(DEV), "actions": torch.from_numpy(a).to(DEV),
              "rewards": torch.from_numpy(r).to(DEV), "next_states": torch.from_numpy(s2).to(DEV)}
     idx = torch.from_numpy(rng.randint(0, cap, size=(3, n)).astype(np.int64)).to(DEV)
-    return store, idx, cap, dp.init_blob(H, A, seed)
+    return store, idx, cap, lh.init_blob(H, A, seed)
 
 
 def test_determinism_bitwise():
@@ -285,11 +284,11 @@ def test_refused_inputs_leave_the_learner_unchanged():
 def test_update_from_prioritized_buffer_writes_priorities():
     u = _uav()
     rng = np.random.RandomState(13)
-    s, a, r, s2 = dp.batch(rng, 3000, 12)
+    s, a, r, s2 = lh.batch(rng, 3000, 12)
     buf = u.PrioritizedDeviceReplayBuffer(4000, DEV)
     buf.add({"states": torch.from_numpy(s), "actions": torch.from_numpy(a), "rewards": torch.from_numpy(r),
              "next_states": torch.from_numpy(s2)})
-    L = lh.learner(64, 12, blob=dp.init_blob(64, 12, 1))
+    L = lh.learner(64, 12, blob=lh.init_blob(64, 12, 1))
     gen = torch.Generator(device=DEV); gen.manual_seed(4)
     p0 = buf.priorities.clone()
     al, cl, td = L.update_from(buf, 2048, generator=gen)

@@ -1,6 +1,6 @@
 """The clipped-surrogate actor loss of the device learner (uavtrack_learner_update_clipped / _grad_clipped,
 DeviceActorCritic.update(log_mu=, clip_eps=), DrawSpec.clip_eps) on the MI355X: against the float64 mirror
-(tests/learner_clipped_mirror.py) at the harness's bounds; on-policy it is the per-sample update bit for bit; the split
+(tests/learner_mirror.py with clip=) at the harness's bounds; on-policy it is the per-sample update bit for bit; the split
 form; refusals on the device; determinism and graph capture; off is off.
 
 Shapes are corners of learner_harness.SWEEP (learner_clipped_mirror.SHAPES).  Every case's log_mu store comes from
@@ -13,11 +13,8 @@ import pytest
 import torch
 
 import learner_clipped_mirror as cm
-import learner_dp_mirror as dp
 import learner_harness as lh
-import learner_regularised_mirror as rm
-import learner_target_mirror as tm
-import learner_weighted_mirror as wm
+import learner_mirror as mirror
 
 pytestmark = pytest.mark.gpu
 
@@ -37,13 +34,11 @@ def _case(H, A, n, gather):
     """learner_harness.case plus the clipped case's per-slot log_mu, on the host and on the device."""
     blob, b, store, cap, idx, it = lh.case(H, A, n, gather)
     cb = cm.clip_batch(H, A, n, gather)
-    assert np.array_equal(cb["blob"], blob) and np.array_equal(cb["idx"], idx) and cb["cap"] == cap
-    assert all(np.array_equal(x, y) for x, y in zip(cb["b"], b))            # host_case drew the harness's case
     return blob, b, store, cap, idx, it, cb["log_mu"], lh.dev(cb["log_mu"])
 
 
 def _weights(n):
-    return wm.make_weights(np.random.RandomState(n + 11), n)
+    return lh.make_weights(np.random.RandomState(n + 11), n)
 
 
 def clipped(L, n, store, cap, it, prio, mu, eps, w=None):
@@ -72,8 +67,9 @@ def _mirror(H, A, n, gather, eps, c, weighted):
     if key not in _mirrors:
         cb = cm.clip_batch(H, A, n, gather)
         idx = cb["idx"]
-        _mirrors[key] = cm.losses_and_grads(cb["blob"], H, A, *lh.gathered(cb["b"], idx), GAMMA, cb["log_mu"][idx], eps,
-                                            _weights(n) if weighted else None, np.float32(c))
+        _mirrors[key] = mirror.losses_and_grads(cb["blob"], H, A, *lh.gathered(cb["b"], idx), GAMMA, "per_sample",
+                                                weights=_weights(n) if weighted else None, entropy_coef=np.float32(c),
+                                                clip=(cb["log_mu"][idx], eps))
     return _mirrors[key]
 
 
@@ -114,25 +110,26 @@ def test_clipped_update_against_fp64_mirror(H, A, n, gather, eps, c, weighted):
 
 @pytest.mark.parametrize("eps", [0.2, INF])
 def test_clipped_update_with_a_target_critic_against_fp64_mirror(eps):
-    """A target critic that differs from the critic: y = r + gamma V_target(s') in the mirror (the bootstrap folded into
-    the rewards, gamma = 0), log_mu built against those deltas."""
+    """A target critic that differs from the critic: y = r + gamma V_target(s') in the mirror (theta=), log_mu built
+    against those deltas."""
     H, A, n, gather = SHAPES[1]
     blob, b, store, cap, idx, it = lh.case(H, A, n, gather)
-    theta = tm.critic_block(dp.init_blob(H, A, 4242), H, A)
-    b_t = (b[0], b[1], tm.bootstrapped(theta, H, b[2], b[3], GAMMA), b[3])
-    cb = cm.clip_batch(H, A, n, gather, b_t, 0.0)
+    theta = mirror.critic_block(lh.init_blob(H, A, 4242), H, A)
+    cb = cm.clip_batch(H, A, n, gather, theta)
     c = 0.01
     L = lh.learner(H, A, "per_sample", blob, n, c=c)
     L.set_target(tau=0.5)
     L._set_target_params(theta)
     out = clipped(L, n, store, cap, it, None, lh.dev(cb["log_mu"]), eps)
     L.check()
-    ref = cm.losses_and_grads(blob, H, A, *lh.gathered(b_t, idx), 0.0, cb["log_mu"][idx], eps, None, np.float32(c))
+    ref = mirror.losses_and_grads(blob, H, A, *lh.gathered(b, idx), GAMMA, "per_sample", entropy_coef=np.float32(c),
+                                  clip=(cb["log_mu"][idx], eps), theta=theta)
     _assert_against(out, ref, blob, n, H, A, c)
     if eps == 0.2:
-        g_inf = cm.losses_and_grads(blob, H, A, *lh.gathered(b_t, idx), 0.0, cb["log_mu"][idx], INF, None, np.float32(c))[3]
+        g_inf = mirror.losses_and_grads(blob, H, A, *lh.gathered(b, idx), GAMMA, "per_sample", entropy_coef=np.float32(c),
+                                        clip=(cb["log_mu"][idx], INF), theta=theta).grad
         assert np.abs(out["exp_avg"] / 0.1 - g_inf).max() > 100 * lh.tol_g(n, ref[3])
-    want = tm.polyak(theta, tm.critic_block(out["params"], H, A), 0.5)       # and the sync rule ran behind the step
+    want = mirror.polyak(theta, mirror.critic_block(out["params"], H, A), 0.5)       # and the sync rule ran behind the step
     assert np.array_equal(L._get_target_params(), want)
 
 
@@ -189,10 +186,11 @@ def test_two_clipped_rows_and_a_mixed_pair_meet_the_mirrors_combine(H, A, n, gat
     accepted and are the mirror's combine of the same rows within tol_g."""
     blob, b, store, cap, idx, it, mu_h, mu = _case(H, A, n, gather)
     c, eps = 0.01, 0.2
-    (lo0, hi0), (lo1, hi1) = dp.cuts(n, 2, seed=n)
+    (lo0, hi0), (lo1, hi1) = lh.cuts(n, 2, seed=n)
     rows_of = lambda lo, hi: lh.gathered(b, idx[lo:hi])                                           # noqa: E731
-    clip_row = lambda lo, hi: cm.shard_sums(blob, H, A, *rows_of(lo, hi), GAMMA, mu_h[idx[lo:hi]], eps, None, np.float32(c))  # noqa: E731
-    plain_row = rm.shard_sums(blob, H, A, *rows_of(lo1, hi1), GAMMA, "per_sample", None, np.float32(c))
+    clip_row = lambda lo, hi: mirror.shard_sums(blob, H, A, *rows_of(lo, hi), GAMMA, "per_sample", None, np.float32(c),  # noqa: E731
+                                                (mu_h[idx[lo:hi]], eps))
+    plain_row = mirror.shard_sums(blob, H, A, *rows_of(lo1, hi1), GAMMA, "per_sample", None, np.float32(c))
     for second_clipped in (True, False):
         L = lh.learner(H, A, "per_sample", blob, n, c=c)
         rows = L.new_rows(2)
@@ -203,7 +201,7 @@ def test_two_clipped_rows_and_a_mixed_pair_meet_the_mirrors_combine(H, A, n, gat
             L._grad(hi1 - lo1, store, cap, it[lo1:hi1].contiguous(), rows[1])
         al, cl = L.apply(rows)
         L.check()
-        ral, rcl, g = dp.combine([clip_row(lo0, hi0), clip_row(lo1, hi1) if second_clipped else plain_row], H, A, "per_sample")
+        ral, rcl, g = mirror.combine([clip_row(lo0, hi0), clip_row(lo1, hi1) if second_clipped else plain_row], H, A, "per_sample")
         st = lh.state(L)
         assert np.array_equal(st["step"], np.ones(8))
         lh.assert_step_from_zero(st, blob, g, n, H, A)
@@ -227,7 +225,7 @@ def test_a_bad_behaviour_log_prob_refuses_on_the_device(what, value):
     bad slot where it is not drawn refuses nothing."""
     H, A, n, gather = SHAPES[1]
     blob, b, store, cap, idx, it, mu_h, mu = _case(H, A, n, gather)
-    logp = rm.policy(blob, H, A, b[0])[0][np.arange(cap), b[1].astype(np.int64)]
+    logp = mirror.policy(blob, H, A, b[0])[0][np.arange(cap), b[1].astype(np.int64)]
     k = 40
     slot = int(idx[k])
     undrawn = int(np.setdiff1d(np.arange(cap), idx)[0])
@@ -339,13 +337,13 @@ def _filled_ring(kind, L, seed=3):
 
 
 def _twins():
-    blob = dp.init_blob(64, 12, 77)
+    blob = lh.init_blob(64, 12, 77)
     return [lh.learner(64, 12, "per_sample", blob, max_batch=64, c=0.01) for _ in range(2)]
 
 
 def _move_on(L):
     """The actor moves on; the ring's log_mu stays."""
-    L._set_params(0.5 * (L._get_params() + dp.init_blob(64, 12, 78)))
+    L._set_params(0.5 * (L._get_params() + lh.init_blob(64, 12, 78)))
 
 
 def test_update_from_captures_into_one_graph():

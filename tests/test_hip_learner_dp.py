@@ -15,7 +15,6 @@ import numpy as np
 import pytest
 import torch
 
-import learner_dp_mirror as dp
 import learner_dp_worker as worker
 import learner_harness as lh
 import learner_mirror as mirror
@@ -60,8 +59,8 @@ def test_one_row_is_the_closed_update(H, A, n, loss, gather):
     """grad -> apply(count 1) -> write_priorities against update on a twin handle, three consecutive updates: bitwise."""
     rng = np.random.RandomState(H * 1000 + n)
     cap = n + 7 if gather else n
-    store = _store(*dp.batch(rng, cap, A))
-    blob = dp.init_blob(H, A, H + n)
+    store = _store(*lh.batch(rng, cap, A))
+    blob = lh.init_blob(H, A, H + n)
     closed, split = (lh.learner(H, A, loss=loss, blob=blob, max_batch=n) for _ in range(2))
     prio_c = torch.from_numpy(rng.uniform(0.1, 2, cap).astype(np.float32)).to(DEV)
     prio_s = prio_c.clone()
@@ -85,15 +84,15 @@ def test_one_row_is_the_closed_update(H, A, n, loss, gather):
 # ---- 2, 3. K rows: data parallelism and accumulation ---------------------------------------------------------------
 
 def _teeth():
-    c = dp.TEETH
-    blob, b = dp.teeth_batch()
+    c = lh.TEETH
+    blob, b = lh.teeth_batch()
     return c, blob, b
 
 
 def _k_handles(K):
     """The shared batch cut K ways, one grad per shard on K handles that start equal, every handle applies all rows."""
     c, blob, b = _teeth()
-    shards = dp.split(b, dp.cuts(c["n"], K))
+    shards = lh.split(b, lh.cuts(c["n"], K))
     Ls = [lh.learner(c["H"], c["A"], lr=c["lrs"], gamma=c["gamma"], blob=blob, max_batch=c["n"]) for _ in range(K)]
     rows = Ls[0].new_rows(K)
     tds = []
@@ -115,11 +114,11 @@ def test_k_rows_same_bits_everywhere_and_inside_the_single_update_bounds(K):
     out, td = _k_handles(K)
     for o in out[1:]:
         lh.same(out[0], o)
-    ral, rcl, rtd, g = mirror.losses_and_grads(blob, H, A, s, a, r, s2, c["gamma"], "reference")
+    ral, rcl, rtd, g = mirror.losses_and_grads(blob, H, A, s, a, r, s2, c["gamma"], "reference")[:4]
     lh.assert_losses_and_td(out[0]["actor_loss"], out[0]["critic_loss"], td, ral, rcl, rtd)
     lh.assert_step_from_zero(out[0], blob, g, n, H, A, lr=lr)
     # and the rule it must not be: the averaged per-shard gradients are far outside the same bound
-    naive = dp.averaged_shard_gradients(blob, H, A, dp.split((s, a, r, s2), dp.cuts(n, K)), c["gamma"])
+    naive = mirror.averaged_shard_gradients(blob, H, A, lh.split((s, a, r, s2), lh.cuts(n, K)), c["gamma"])
     assert np.abs(out[0]["exp_avg"] / 0.1 - naive).max() > 50 * lh.tol_g(n, g)
 
 
@@ -129,7 +128,7 @@ def test_accumulation_on_one_handle_and_update_from_many(K):
     K rings: bitwise the explicit grad_from / apply / write_priorities calls on twin rings, and each ring's priorities
     are learner_mirror.last_wins on that ring's own draw."""
     c, blob, b = _teeth()
-    shards = dp.split(b, dp.cuts(c["n"], K))
+    shards = lh.split(b, lh.cuts(c["n"], K))
     want, want_td = _k_handles(K)
     L = lh.learner(c["H"], c["A"], lr=c["lrs"], gamma=c["gamma"], blob=blob, max_batch=c["n"])
     rows = L.new_rows(K)
@@ -176,7 +175,7 @@ def test_refusal_is_global():
     c, blob, b = _teeth()
     K, j = 3, 1
     H, A = c["H"], c["A"]
-    shards = dp.split(b, dp.cuts(c["n"], K))
+    shards = lh.split(b, lh.cuts(c["n"], K))
     stores = [_store(*sh) for sh in shards]
     ns = [len(sh[1]) for sh in shards]
     Ls = [lh.learner(H, A, blob=blob, max_batch=c["n"]) for _ in range(K)]
@@ -216,7 +215,7 @@ def test_refusal_is_global():
         assert torch.equal(losses[k][0], tlosses[k][0]) and torch.isfinite(losses[k][0])
         assert torch.equal(prios[k], tprios[k]) and not torch.equal(prios[k], prio0[k])
     # a row of a learner of another width: its words do not carry this layout's tag
-    other = lh.learner(64, A, blob=dp.init_blob(64, A, 1), max_batch=c["n"])
+    other = lh.learner(64, A, blob=lh.init_blob(64, A, 1), max_batch=c["n"])
     foreign, _ = other._grad(ns[0], stores[0], ns[0], None)
     other.check()
     L = Ls[0]
@@ -242,8 +241,8 @@ def test_host_side_errors_enqueue_nothing():
     lib = _lib.load()
     H, A, n = 64, 12, 500
     rng = np.random.RandomState(2)
-    store = _store(*dp.batch(rng, n, A))
-    L = lh.learner(H, A, blob=dp.init_blob(H, A, 2), max_batch=n)
+    store = _store(*lh.batch(rng, n, A))
+    L = lh.learner(H, A, blob=lh.init_blob(H, A, 2), max_batch=n)
     row, td = L._grad(n, store, n, None)
     L.apply(row)
     L.check()
@@ -294,8 +293,8 @@ def test_graph_capture_of_the_split_chain():
     ring's device call counter and the Adam step counts advance under replay."""
     H, A, n, k = 128, 12, 5000, 2048
     rng = np.random.RandomState(31)
-    data = dp.batch(rng, n, A)
-    blob = dp.init_blob(H, A, 31)
+    data = lh.batch(rng, n, A)
+    blob = lh.init_blob(H, A, 31)
 
     def ring():
         r = _uav().PrioritizedReplayRing(n + 50, DEV, seed=5, max_batch=k)

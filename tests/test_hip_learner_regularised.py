@@ -1,6 +1,6 @@
 """The regularised device learner (uavtrack_learner_set_regularisation / _set_diagnostics, DeviceActorCritic's
 entropy_coef / max_grad_norm / enable_diagnostics) on the MI355X: with the settings off every call keeps its bits; the
-entropy bonus and the gradient-norm clip against the float64 mirror (tests/learner_regularised_mirror.py) at
+entropy bonus and the gradient-norm clip against the float64 mirror (tests/learner_mirror.py) at
 test_sweep_against_fp64_mirror's bounds; the edges of the softmax; weights; the split form and the shared tail;
 determinism and graph capture; refusals.
 
@@ -13,11 +13,8 @@ import numpy as np
 import pytest
 import torch
 
-import learner_dp_mirror as dp
 import learner_harness as lh
 import learner_mirror as mirror
-import learner_regularised_mirror as rm
-import learner_weighted_mirror as wm
 
 pytestmark = pytest.mark.gpu
 
@@ -38,20 +35,20 @@ def _uav():
 
 
 def _weights(n, seed=0):
-    return wm.make_weights(np.random.RandomState(n + 11 + seed), n)
+    return lh.make_weights(np.random.RandomState(n + 11 + seed), n)
 
 
 _mirror_cache = {}
 
 
 def _mirror(H, A, n, gather, loss, c, weighted, blob=None):
-    """The fp64 update of a case, computed once: (actor_loss, critic_loss, td, gradient, entropy)."""
+    """The fp64 update of a case, computed once: (actor_loss, critic_loss, td, gradient, entropy, None)."""
     key = (H, A, n, gather, loss, c, weighted, None if blob is None else blob.tobytes())
     if key not in _mirror_cache:
         blob0, b, _, _, idx, _ = lh.case(H, A, n, gather)
         w = _weights(n) if weighted else None
-        _mirror_cache[key] = rm.losses_and_grads(blob0 if blob is None else blob, H, A, *lh.gathered(b, idx), GAMMA, loss,
-                                                 w, np.float32(c))
+        _mirror_cache[key] = mirror.losses_and_grads(blob0 if blob is None else blob, H, A, *lh.gathered(b, idx), GAMMA, loss,
+                                                     weights=w, entropy_coef=np.float32(c))
     return _mirror_cache[key]
 
 
@@ -88,7 +85,7 @@ def test_off_is_off(H, A, n, gather, loss, weighted, diag):
             outs.append([run(L, n, store, cap, it, prio, w) for _ in range(3)])
             L.check()
             if diag and touched:
-                ent = rm.policy(outs[-1][1]["params"], H, A, lh.gathered(b, idx)[0])[2]     # the policy of the third update
+                ent = mirror.policy(outs[-1][1]["params"], H, A, lh.gathered(b, idx)[0])[2]     # the policy of the third update
                 assert np.abs(L.entropy(n).cpu().numpy() - ent).max() <= _entropy_tol(A)
                 assert torch.isnan(L.grad_norm).all()                                      # no clip, no norm
         assert np.isfinite(outs[0][2]["actor_loss"]) and np.array_equal(outs[0][2]["step"], np.full(8, 3))
@@ -108,7 +105,7 @@ def test_entropy_update_against_fp64_mirror(H, A, n, gather, c):
     L = lh.learner(H, A, "per_sample", blob, n, c=c, diag=True)
     out = lh.update(L, n, store, cap, it, None, w)
     L.check()
-    ral, rcl, rtd, g, ent = _mirror(H, A, n, gather, "per_sample", c, weighted)
+    ral, rcl, rtd, g, ent, _ = _mirror(H, A, n, gather, "per_sample", c, weighted)
     lh.assert_losses_and_td(out["actor_loss"], out["critic_loss"], out["td"], ral, rcl, rtd, c, A)
     lh.assert_step_from_zero(out, blob, g, n, H, A)
     assert np.abs(L.entropy(n).cpu().numpy() - ent).max() <= _entropy_tol(A)
@@ -135,7 +132,7 @@ def test_logits_spanning_more_than_250_stay_finite(H, A, n, gather):
     scale would also multiply the fp32 forward's rounding of the logits, which is not the softmax's doing.)"""
     blob0, b, store, cap, idx, it = lh.case(H, A, n, gather)
     blob = _with_fc2(blob0, H, A, 1.0, 300.0)
-    logp = rm.policy(blob, H, A, lh.gathered(b, idx)[0])[0]
+    logp = mirror.policy(blob, H, A, lh.gathered(b, idx)[0])[0]
     assert (logp.max(axis=1) - logp.min(axis=1) > 250).all()
     assert (np.exp(logp.astype(np.float32)).min(axis=1) == 0).all()
     assert (np.exp(logp[np.arange(n), lh.gathered(b, idx)[1]].astype(np.float32)) == 0).any()
@@ -145,7 +142,7 @@ def test_logits_spanning_more_than_250_stay_finite(H, A, n, gather):
     L.check()
     row = row.cpu().numpy()
     P = L.num_params
-    want = rm.shard_sums(blob, H, A, *lh.gathered(b, idx), GAMMA, "per_sample", None, np.float32(c))
+    want = mirror.shard_sums(blob, H, A, *lh.gathered(b, idx), GAMMA, "per_sample", None, np.float32(c))
     assert np.isfinite(row[:P + 4]).all() and np.isfinite(want["g"]).all()
     assert np.abs(row[:P] - want["g"]).max() <= lh.tol_g(n, want["g"])
     for q in range(4):                                  # sums of n terms, each within 2e-5 of the loss scales above
@@ -178,7 +175,7 @@ def test_weights_with_settings_on(H, A, n, gather):
     """Entropy and clipping on: a vector of ones is no weights, bitwise; weights of 0.5 halve words [0, P + 4) of a row
     exactly; a NaN weight still refuses."""
     blob, b, store, cap, idx, it = lh.case(H, A, n, gather)
-    nr = rm.norms(_mirror(H, A, n, gather, "per_sample", 0.5, False)[3], H, A)
+    nr = mirror.norms(_mirror(H, A, n, gather, "per_sample", 0.5, False)[3], H, A)
     mgn = (float(nr[0] / 4), float(nr[1] / 4))
     outs = []
     for w in (None, torch.ones(n, device=DEV)):
@@ -223,11 +220,11 @@ def test_clip_against_fp64_mirror(H, A, n, gather, loss, which):
     c = 0.01 if loss == "per_sample" else 0.0
     weighted = loss == "reference"
     w = lh.dev(_weights(n)) if weighted else None
-    ral, rcl, rtd, g, ent = _mirror(H, A, n, gather, loss, c, weighted)
-    nr = rm.norms(g, H, A)
+    ral, rcl, rtd, g, ent, _ = _mirror(H, A, n, gather, loss, c, weighted)
+    nr = mirror.norms(g, H, A)
     mgn = _max_norms(nr, which)
     assert all(max(m / x, x / m) >= 1.05 for m, x in zip(mgn, nr))          # the decision is far from its knife edge
-    coef, _, _ = rm.clip(g, H, A, mgn)
+    coef, _, _ = mirror.clip_grad_norm(g, H, A, mgn)
     assert [x < 1 for x in coef] == [which in ("both", "actor"), which in ("both", "critic")]
     L = lh.learner(H, A, loss, blob, n, c=c, mgn=tuple(float(x) for x in mgn), diag=True)
     out = lh.update(L, n, store, cap, it, None, w)
@@ -250,7 +247,7 @@ def test_clip_against_fp64_mirror(H, A, n, gather, loss, which):
 def test_one_row_applied_alone_is_the_closed_update(H, A, n, gather, loss):
     blob, b, store, cap, idx, it = lh.case(H, A, n, gather)
     c = 0.5 if loss == "per_sample" else 0.0
-    nr = rm.norms(_mirror(H, A, n, gather, loss, c, False)[3], H, A)
+    nr = mirror.norms(_mirror(H, A, n, gather, loss, c, False)[3], H, A)
     mgn = (float(nr[0] / 4), float(nr[1] / 4))
     prio0 = torch.rand(cap, device=DEV) + 0.1
     outs = []
@@ -271,14 +268,14 @@ def test_three_rows_match_the_mirror_and_two_learners_stay_equal(H, A, n, gather
     equal."""
     blob, b, store, cap, idx, it = lh.case(H, A, n, gather)
     c = 0.5 if loss == "per_sample" else 0.0
-    ral, rcl, rtd, g, ent = _mirror(H, A, n, gather, loss, c, False)
-    nr = rm.norms(g, H, A)
+    ral, rcl, rtd, g, ent, _ = _mirror(H, A, n, gather, loss, c, False)
+    nr = mirror.norms(g, H, A)
     mgn = (nr[0] / 4, nr[1] / 4)
-    coef = rm.clip(g, H, A, mgn)[0]
+    coef = mirror.clip_grad_norm(g, H, A, mgn)[0]
     one, two = (lh.learner(H, A, loss, blob, n, c=c, mgn=tuple(float(x) for x in mgn), diag=True) for _ in range(2))
     rows = one.new_rows(3)
     tds = []
-    for k, (lo, hi) in enumerate(dp.cuts(n, 3, seed=n)):
+    for k, (lo, hi) in enumerate(lh.cuts(n, 3, seed=n)):
         _, td = one._grad(hi - lo, store, cap, it[lo:hi].contiguous(), rows[k])
         tds.append(td)
     res = [L.apply(rows) for L in (one, two)]
@@ -297,7 +294,7 @@ def test_three_rows_match_the_mirror_and_two_learners_stay_equal(H, A, n, gather
 def test_identical_calls_give_identical_bits():
     H, A, n, gather = SHAPES[3]
     blob, b, store, cap, idx, it = lh.case(H, A, n, gather)
-    nr = rm.norms(_mirror(H, A, n, gather, "per_sample", 0.3, False)[3], H, A)
+    nr = mirror.norms(_mirror(H, A, n, gather, "per_sample", 0.3, False)[3], H, A)
     outs = []
     for _ in range(2):
         L = lh.learner(H, A, "per_sample", blob, n, c=0.3, mgn=(float(nr[0] / 4), float(nr[1] / 4)), diag=True)
@@ -312,7 +309,7 @@ def test_graph_replay_matches_eager():
     """One update with entropy and clipping captured in a graph and replayed three times == three eager updates."""
     H, A, n, gather = SHAPES[3]
     blob, b, store, cap, idx, it = lh.case(H, A, n, gather)
-    nr = rm.norms(_mirror(H, A, n, gather, "per_sample", 0.3, False)[3], H, A)
+    nr = mirror.norms(_mirror(H, A, n, gather, "per_sample", 0.3, False)[3], H, A)
     kw = dict(c=0.3, mgn=(float(nr[0] / 4), float(nr[1] / 4)), diag=True)
     prio_e = torch.rand(cap, device=DEV) + 0.1
     prio_g = prio_e.clone()

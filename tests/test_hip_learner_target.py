@@ -1,6 +1,6 @@
 """The device learner's target critic (uavtrack_learner_set_target, DeviceActorCritic.set_target) on the MI355X: off is
 off; the bootstrap substituted bit for bit against a plain learner that is handed V_target(s') as its rewards; the update
-against the float64 mirror (tests/learner_target_mirror.py) at the harness's bounds; the Polyak and the periodic rule
+against the float64 mirror (tests/learner_mirror.py with theta=) at the harness's bounds; the Polyak and the periodic rule
 against their float32 mirrors; the split update and several rings; the target's values and a lambda ring's add; graph
 capture; checkpoints and pack / unpack.
 
@@ -11,11 +11,8 @@ import numpy as np
 import pytest
 import torch
 
-import learner_dp_mirror as dp
 import learner_harness as lh
 import learner_mirror as mirror
-import learner_target_mirror as tm
-import learner_weighted_mirror as wm
 
 pytestmark = pytest.mark.gpu
 
@@ -34,11 +31,11 @@ def _uav():
 
 def _other(H, A, seed=0):
     """A critic block that is not the case's: theta- != theta."""
-    return tm.critic_block(dp.init_blob(H, A, 5000 + H + seed), H, A)
+    return mirror.critic_block(lh.init_blob(H, A, 5000 + H + seed), H, A)
 
 
 def _weights(n):
-    return wm.make_weights(np.random.RandomState(n + 11), n)
+    return lh.make_weights(np.random.RandomState(n + 11), n)
 
 
 def _prio(cap):
@@ -75,7 +72,7 @@ def test_off_is_off_and_a_fresh_target_is_the_critic(H, A, n, loss, gather):
     for kw in (dict(tau=0.3), dict(period=NEVER)):
         fresh = lh.learner(H, A, loss, blob, n)
         fresh.set_target(**kw)
-        assert fresh._get_target_params().tobytes() == tm.critic_block(blob, H, A).tobytes()
+        assert fresh._get_target_params().tobytes() == mirror.critic_block(blob, H, A).tobytes()
         lh.same(lh.update(fresh, n, store, cap, it, _prio(cap)), first, kw)
     for L in (plain, toggled, fresh):
         L.check()
@@ -98,7 +95,7 @@ def test_bootstrap_is_the_target_critics_value_bitwise(H, A, n, loss, weighted, 
     A_.set_target(period=NEVER)
     A_._set_target_params(theta)
     B_ = lh.learner(H, A, loss, blob, n)
-    C_ = lh.learner(H, A, loss, tm.with_critic(blob, H, A, theta), n)
+    C_ = lh.learner(H, A, loss, mirror.with_critic(blob, H, A, theta), n)
     v_next = C_.values(store["next_states"])
     assert v_next.shape == (cap,)
     assert torch.equal(A_.target.values(store["next_states"]), v_next)
@@ -129,13 +126,13 @@ def test_bootstrap_substitution_holds_under_the_entropy_bonus_and_clipping(H, A,
     A_.set_target(tau=0.5)
     A_._set_target_params(theta)
     B_ = lh.learner(H, A, "per_sample", blob, n, **kw)
-    v_next = lh.learner(H, A, "per_sample", tm.with_critic(blob, H, A, theta), n).values(store["next_states"])
+    v_next = lh.learner(H, A, "per_sample", mirror.with_critic(blob, H, A, theta), n).values(store["next_states"])
     ones, zeros = torch.ones(cap, device=DEV), torch.zeros(cap, device=DEV)
     got = lh.update(A_, n, dict(store, rewards=zeros), cap, it, _prio(cap), None, ones)
     want = lh.update(B_, n, dict(store, rewards=v_next), cap, it, _prio(cap), None, zeros)
     lh.same(got, want)
     assert np.isfinite(got["grad_norm"]).all() and (got["grad_norm"] > 0).all() and (got["entropy"] > 0).all()
-    assert A_._get_target_params().tobytes() == tm.polyak(theta, tm.critic_block(got["params"], H, A), 0.5).tobytes()
+    assert A_._get_target_params().tobytes() == mirror.polyak(theta, mirror.critic_block(got["params"], H, A), 0.5).tobytes()
     for L in (A_, B_):
         L.check()
 
@@ -171,11 +168,11 @@ def _clear_case(H, A, n, gather):
     if key not in _clear:
         rng = np.random.RandomState(H * 1000 + n + (7 if gather else 0))
         cap = n + 7 if gather else n
-        blob = dp.init_blob(H, A, H + n)
-        s, a, r, s2 = dp.batch(rng, cap, A)
+        blob = lh.init_blob(H, A, H + n)
+        s, a, r, s2 = lh.batch(rng, cap, A)
         bad = _on_a_kink(blob, H, A, s)
         while bad.any():
-            s[bad] = dp.batch(rng, int(bad.sum()), A)[0]
+            s[bad] = lh.batch(rng, int(bad.sum()), A)[0]
             bad = _on_a_kink(blob, H, A, s)
         b = (s, a, r, s2)
         idx = rng.randint(0, cap, size=n).astype(np.int64) if gather else np.arange(n)
@@ -196,11 +193,11 @@ def test_update_with_a_target_against_the_fp64_mirror(H, A, n, loss, gather):
     L._set_target_params(theta)
     out = lh.update(L, n, store, cap, it, None)
     L.check()
-    ral, rcl, rtd, g = tm.losses_and_grads(blob, theta, H, A, *lh.gathered(b, idx), GAMMA, loss)
+    ral, rcl, rtd, g = mirror.losses_and_grads(blob, H, A, *lh.gathered(b, idx), GAMMA, loss, theta=theta)[:4]
     lh.assert_losses_and_td(out["actor_loss"], out["critic_loss"], out["td"], ral, rcl, rtd)
     lh.assert_step_from_zero(out, blob, g, n, H, A)
     # the target moved the targets: the plain mirror's td_delta is another one
-    plain_td = tm.losses_and_grads(blob, tm.critic_block(blob, H, A), H, A, *lh.gathered(b, idx), GAMMA, loss)[2]
+    plain_td = mirror.losses_and_grads(blob, H, A, *lh.gathered(b, idx), GAMMA, loss).td
     assert np.abs(plain_td - rtd).max() > 1e-6
 
 
@@ -218,8 +215,8 @@ def test_polyak_chain_is_the_float32_mirror(H, A, n, gather, tau):
     L._set_target_params(t)
     for k in range(5):
         L._run(n, store, cap, it, None)
-        w = tm.critic_block(L._get_params(), H, A)
-        t = tm.polyak(t, w, tau)
+        w = mirror.critic_block(L._get_params(), H, A)
+        t = mirror.polyak(t, w, tau)
         got = L._get_target_params()
         assert got.tobytes() == t.tobytes(), (k, np.flatnonzero(got.view(np.int32) != t.view(np.int32))[:5])
         if tau == 1.0:
@@ -242,7 +239,7 @@ def test_periodic_copy_counts_successful_updates_on_the_device(H, A, n, gather):
     L = lh.learner(H, A, "reference", blob, n)
     L.set_target(period=3)
     assert L.get_target() == {"tau": None, "period": 3}
-    t = tm.critic_block(blob, H, A)
+    t = mirror.critic_block(blob, H, A)
     good = 0
     for k in range(1, 8):
         before = _full(L)
@@ -254,9 +251,9 @@ def test_periodic_copy_counts_successful_updates_on_the_device(H, A, n, gather):
         good += 1
         st = _full(L)
         assert np.array_equal(st["step"], np.full(8, good))
-        w = tm.critic_block(st["params"], H, A)
+        w = mirror.critic_block(st["params"], H, A)
         assert w.tobytes() != t.tobytes()
-        t = tm.periodic(t, w, st["step"][4], 3)
+        t = mirror.periodic(t, w, st["step"][4], 3)
         assert st["target"].tobytes() == t.tobytes(), k
         assert (t.tobytes() == w.tobytes()) == (good in (3, 6)), k
     with pytest.raises(RuntimeError, match="1 update"):
@@ -274,7 +271,7 @@ def test_period_one_is_tau_one():
     for k in range(3):
         lh.same(lh.update(a, n, store, cap, it, None), lh.update(c, n, store, cap, it, None), k)
         lh.same(_full(a), _full(c), k)
-        assert a._get_target_params().tobytes() == tm.critic_block(a._get_params(), H, A).tobytes()
+        assert a._get_target_params().tobytes() == mirror.critic_block(a._get_params(), H, A).tobytes()
 
 
 # ---- 6. the split update and several rings -------------------------------------------------------------------------------------
@@ -302,12 +299,12 @@ def test_grad_apply_write_priorities_is_the_closed_update(H, A, n, gather, kw):
 
 def test_update_from_many_is_the_rows_applied_by_hand():
     H, A, counts, k = 33, 12, (65, 40), 48
-    blob = dp.init_blob(H, A, 77)
+    blob = lh.init_blob(H, A, 77)
 
     def rings():
         out = []
         for r, cnt in enumerate(counts):
-            s, a, rew, s2 = dp.batch(np.random.RandomState(100 + r), cnt, A)
+            s, a, rew, s2 = lh.batch(np.random.RandomState(100 + r), cnt, A)
             ring = _uav().PrioritizedReplayRing(cnt + 5, DEV, seed=60 + r, max_batch=64)
             ring.add({"states": torch.from_numpy(s), "actions": torch.from_numpy(a), "rewards": torch.from_numpy(rew),
                       "next_states": torch.from_numpy(s2)})
@@ -330,7 +327,7 @@ def test_update_from_many_is_the_rows_applied_by_hand():
         for x, y in zip(ra, rb):
             assert torch.equal(x.priorities, y.priorities)
         lh.same(_full(many), _full(hand), u)
-    t = tm.critic_block(blob, H, A)
+    t = mirror.critic_block(blob, H, A)
     assert many._get_target_params().tobytes() not in (t.tobytes(), _other(H, A).tobytes())
     for x in (many, hand, *ra, *rb):
         x.check()
@@ -340,14 +337,14 @@ def test_update_from_many_is_the_rows_applied_by_hand():
 
 @pytest.mark.parametrize("H,A,n", SHAPES)
 def test_target_values_are_the_values_of_a_learner_whose_critic_is_theta(H, A, n):
-    blob = dp.init_blob(H, A, 9)
+    blob = lh.init_blob(H, A, 9)
     theta = _other(H, A)
     L = lh.learner(H, A, "reference", blob, 64)
     with pytest.raises(RuntimeError, match="uavtrack_learner_values_target: no target"):
         L.target.values(torch.zeros(1, 12, device=DEV))
     L.set_target(tau=0.5)
     L._set_target_params(theta)
-    ref = lh.learner(H, A, "reference", tm.with_critic(blob, H, A, theta), 64)
+    ref = lh.learner(H, A, "reference", mirror.with_critic(blob, H, A, theta), 64)
     x = lh.dev(np.random.RandomState(n).uniform(-3, 3, (n, 12)).astype(np.float32))
     want = ref.values(x)
     got = L.target.values(x)
@@ -355,7 +352,7 @@ def test_target_values_are_the_values_of_a_learner_whose_critic_is_theta(H, A, n
     out = torch.full((n,), 7.0, device=DEV)
     assert L.target.values(x.reshape(n, 1, 12), out=out) is out and torch.equal(out, want)
     assert torch.equal(L.values(x), lh.learner(H, A, "reference", blob, 64).values(x))     # the online critic's stay
-    want64 = tm.values64(theta, H, x.cpu().numpy())
+    want64 = mirror.values64(theta, H, x.cpu().numpy())
     assert np.abs(got.cpu().numpy() - want64).max() <= 1e-4 * (1 + np.abs(want64).max())
 
 
@@ -368,7 +365,7 @@ def test_lambda_ring_add_with_the_target_critic_stores_what_its_values_store(kin
     out = {"obs": lh.dev(rng.standard_normal((T, B, N, 12)).astype(np.float32)),
            "actions": lh.dev(rng.integers(0, A, (T, B, N)).astype(np.int32)),
            "reward": lh.dev(rng.standard_normal((T, B, N)).astype(np.float32))}
-    L = lh.learner(H, A, "reference", dp.init_blob(H, A, 10), 64)
+    L = lh.learner(H, A, "reference", lh.init_blob(H, A, 10), 64)
     L.set_target(period=NEVER)
     L._set_target_params(_other(H, A))
     u = _uav()
@@ -394,8 +391,8 @@ def test_captured_update_from_keeps_the_periodic_schedule_across_replays():
     """update_from with period = 2, captured once on one stream and replayed four times == the eager chain, bitwise; the
     target changed on replays 2 and 4 only: the schedule runs on the device step counter."""
     H, A, cnt, k = 128, 12, 90, 64
-    blob = dp.init_blob(H, A, 12)
-    s, a, rew, s2 = dp.batch(np.random.RandomState(4), cnt, A)
+    blob = lh.init_blob(H, A, 12)
+    s, a, rew, s2 = lh.batch(np.random.RandomState(4), cnt, A)
 
     def fresh():
         ring = _uav().PrioritizedReplayRing(100, DEV, seed=3, max_batch=k)
@@ -417,7 +414,7 @@ def test_captured_update_from_keeps_the_periodic_schedule_across_replays():
     torch.cuda.synchronize()
     assert np.array_equal(lh.state(graphed)["step"], np.zeros(8))              # capture ran nothing
     graphed.set_target(period=NEVER)                                            # the graph keeps period = 2
-    t = tm.critic_block(blob, H, A)
+    t = mirror.critic_block(blob, H, A)
     for c in range(1, 5):
         e_out = eager.update_from(re_, k, importance=True, beta=0.4)
         g.replay()
@@ -430,7 +427,7 @@ def test_captured_update_from_keeps_the_periodic_schedule_across_replays():
         assert got.tobytes() == eager._get_target_params().tobytes(), c
         assert (got.tobytes() != t.tobytes()) == (c % 2 == 0), c
         if c % 2 == 0:
-            assert got.tobytes() == tm.critic_block(graphed._get_params(), H, A).tobytes()
+            assert got.tobytes() == mirror.critic_block(graphed._get_params(), H, A).tobytes()
         t = got
     for x in (eager, graphed, re_, rg):
         x.check()
@@ -452,7 +449,7 @@ def _trained(H, A, n, kw, loss="per_sample"):
 def test_checkpoints_restore_the_target_and_its_settings(kw, tmp_path):
     H, A, n = 33, 12, 65
     src, batch = _trained(H, A, n, kw)
-    assert src._get_target_params().tobytes() != tm.critic_block(src._get_params(), H, A).tobytes()
+    assert src._get_target_params().tobytes() != mirror.critic_block(src._get_params(), H, A).tobytes()
     sd = src.state_dict()
     assert set(sd) == {"actor", "critic", "actor_optimizer", "critic_optimizer", "target_critic", "target"}
     assert list(sd["target_critic"]) == list(sd["critic"]) and sd["target"] == src.get_target() == {**dict(tau=None, period=None), **kw}
@@ -485,7 +482,7 @@ def test_checkpoint_without_a_target_hard_syncs_and_off_keeps_todays_keys(tmp_pa
     off.save(str(tmp_path), 1)
     paths = (str(tmp_path / "actor" / "actor_weights_1.pth"), str(tmp_path / "critic" / "critic_weights_1.pth"))
     assert set(torch.load(paths[1], map_location="cpu")) == {"model_state_dict", "optimizer_state_dict"}
-    critic = tm.critic_block(off._get_params(), H, A)
+    critic = mirror.critic_block(off._get_params(), H, A)
     for load in (lambda L: L.load_state_dict(sd), lambda L: L.load(*paths)):
         on = lh.learner(H, A, "reference", None, n)
         on.set_target(tau=0.1)
@@ -550,11 +547,11 @@ def test_settings_and_host_side_errors():
     assert np.concatenate([v.numpy().ravel() for v in sd.values()]).tobytes() == theta.tobytes()
     L.set_target()
     L.set_target(tau=0.2)
-    assert L._get_target_params().tobytes() == tm.critic_block(blob, H, A).tobytes()
+    assert L._get_target_params().tobytes() == mirror.critic_block(blob, H, A).tobytes()
     L._set_target_params(theta)
     L._run(n, store, cap, it, None)
     L.sync_target()
-    assert L._get_target_params().tobytes() == tm.critic_block(L._get_params(), H, A).tobytes()
+    assert L._get_target_params().tobytes() == mirror.critic_block(L._get_params(), H, A).tobytes()
     L.check()
 
 

@@ -1,7 +1,7 @@
 """The importance-weighted learner update (uavtrack_learner_update_weighted / _grad_weighted, DeviceActorCritic's
 `weights` / `importance` arguments) and the annealed ring draw (uavtrack_replay_sample_annealed) on the MI355X: ones
 and NULL against the unweighted update to the bit, exact scaling by a power of two, random weights against the float64
-weighted mirror (tests/learner_weighted_mirror.py) at test_sweep_against_fp64_mirror's tolerances, the split form,
+mirror (tests/learner_mirror.py with weights) at test_sweep_against_fp64_mirror's tolerances, the split form,
 refused weights, the ring end to end, and the device-side beta schedule, eager and under graph replay."""
 import types
 
@@ -9,10 +9,8 @@ import numpy as np
 import pytest
 import torch
 
-import learner_dp_mirror as dp
 import learner_harness as lh
 import learner_mirror as mirror
-import learner_weighted_mirror as wm
 
 pytestmark = pytest.mark.gpu
 
@@ -79,12 +77,12 @@ def test_half_weights_scale_the_row_exactly(H, A, n, loss, gather):
 @pytest.mark.parametrize("H,A,n,loss,gather", CASES)
 def test_random_weights_against_fp64_weighted_mirror(H, A, n, loss, gather):
     blob, b, store, cap, idx, it = lh.case(H, A, n, gather)
-    w = wm.make_weights(np.random.RandomState(n + H), n)
+    w = lh.make_weights(np.random.RandomState(n + H), n)
     assert w.max() == 1.0 and w.min() >= 0.0 and (n < 2 or (w == 0).any())
     L = lh.learner(H, A, loss, blob, max_batch=n)
     out = lh.update(L, n, store, cap, it, None, lh.dev(w))
     L.check()
-    ral, rcl, rtd, g = wm.losses_and_grads(blob, H, A, *lh.gathered(b, idx), GAMMA, loss, w)
+    ral, rcl, rtd, g = mirror.losses_and_grads(blob, H, A, *lh.gathered(b, idx), GAMMA, loss, weights=w)[:4]
     lh.assert_losses_and_td(out["actor_loss"], out["critic_loss"], out["td"], ral, rcl, rtd)
     lh.assert_step_from_zero(out, blob, g, n, H, A)
     if n >= 63:       # the weights are in the result: the unweighted gradient is far outside the bound
@@ -101,7 +99,7 @@ SPLIT = [(64, 48, 63), (128, 12, 65), (128, 12, 4096)]
 @pytest.mark.parametrize("H,A,n", SPLIT)
 def test_one_weighted_row_applied_alone_is_the_weighted_update(H, A, n, loss):
     blob, b, store, cap, idx, it = lh.case(H, A, n, True)
-    w = lh.dev(wm.make_weights(np.random.RandomState(n), n))
+    w = lh.dev(lh.make_weights(np.random.RandomState(n), n))
     closed = lh.learner(H, A, loss, blob, max_batch=n)
     want = lh.update(closed, n, store, cap, it, None, w)
     split = lh.learner(H, A, loss, blob, max_batch=n)
@@ -120,7 +118,7 @@ def test_two_rows_over_the_halves_match_the_mirror_on_the_whole_batch(H, A, n, l
     batch; `mixed`: the second half goes through the unweighted uavtrack_learner_grad (weights of 1 in the mirror) and
     the apply accepts the pair."""
     blob, b, store, cap, idx, it = lh.case(H, A, n, True)
-    w = wm.make_weights(np.random.RandomState(n + 1), n)
+    w = lh.make_weights(np.random.RandomState(n + 1), n)
     h = n // 2
     if mixed:
         w[h:] = 1.0
@@ -130,7 +128,7 @@ def test_two_rows_over_the_halves_match_the_mirror_on_the_whole_batch(H, A, n, l
     _, td1 = L._grad(n - h, store, cap, it[h:].contiguous(), rows[1], None, None if mixed else lh.dev(w[h:]))
     al, cl = L.apply(rows)
     L.check()
-    ral, rcl, rtd, g = wm.losses_and_grads(blob, H, A, *lh.gathered(b, idx), GAMMA, loss, w)
+    ral, rcl, rtd, g = mirror.losses_and_grads(blob, H, A, *lh.gathered(b, idx), GAMMA, loss, weights=w)[:4]
     lh.assert_losses_and_td(al.cpu().numpy(), cl.cpu().numpy(), torch.cat([td0, td1]).cpu().numpy(), ral, rcl, rtd)
     lh.assert_step_from_zero(lh.state(L), blob, g, n, H, A)
 
@@ -142,7 +140,7 @@ def test_a_bad_weight_refuses_the_update(bad):
     H, A, n = 128, 12, 65
     blob, b, store, cap, idx, it = lh.case(H, A, n, True)
     L = lh.learner(H, A, "reference", blob, max_batch=n)
-    good = lh.dev(wm.make_weights(np.random.RandomState(3), n))
+    good = lh.dev(lh.make_weights(np.random.RandomState(3), n))
     L._run(n, store, cap, it, None, good)
     L.check()
     before = lh.state(L)
@@ -187,9 +185,9 @@ def test_a_refused_draw_refuses_the_update_behind_it():
     """All priorities zero: the draw is refused on the device and writes NaN weights, which refuse the update behind it
     with no host involvement; both handles report it."""
     H, A, n, k = 64, 12, 500, 200
-    data = dp.batch(np.random.RandomState(8), n, A)
+    data = lh.batch(np.random.RandomState(8), n, A)
     ring = _ring(data, 3, k, prio_seed=None)
-    L = lh.learner(H, A, "reference", dp.init_blob(H, A, 8), max_batch=k)
+    L = lh.learner(H, A, "reference", lh.init_blob(H, A, 8), max_batch=k)
     before = lh.state(L)
     ring.priorities.zero_()
     al, cl, _ = L.update_from(ring, k, beta=0.4, importance=True)
@@ -211,8 +209,8 @@ def test_a_refused_draw_refuses_the_update_behind_it():
 @pytest.mark.parametrize("loss", ["reference", "per_sample"])
 def test_update_from_with_importance_is_draw_update_write(loss):
     H, A, n, k = 128, 12, 3000, 1000
-    data = dp.batch(np.random.RandomState(21), n, A)
-    blob = dp.init_blob(H, A, 21)
+    data = lh.batch(np.random.RandomState(21), n, A)
+    blob = lh.init_blob(H, A, 21)
     one, ring = lh.learner(H, A, loss, blob, max_batch=k), _ring(data, 17, k)
     two, twin = lh.learner(H, A, loss, blob, max_batch=k), _ring(data, 17, k)
     for u in range(3):
@@ -236,8 +234,8 @@ def test_update_from_with_importance_is_draw_update_write(loss):
 
 def test_beta_zero_with_importance_is_importance_off():
     H, A, n, k = 64, 12, 2000, 700
-    data = dp.batch(np.random.RandomState(22), n, A)
-    blob = dp.init_blob(H, A, 22)
+    data = lh.batch(np.random.RandomState(22), n, A)
+    blob = lh.init_blob(H, A, 22)
     outs = []
     for kw in (dict(beta=0.0, importance=True), dict(importance=False), dict()):
         L, ring = lh.learner(H, A, "reference", blob, max_batch=k), _ring(data, 4, k)
@@ -259,8 +257,8 @@ def test_update_from_many_uses_each_rings_own_weights(loss):
     """Two rings, importance on: the update is the mirror's over both draws, each with its own weights -- normalised by
     its own draw's maximum, so both rows hold a weight of exactly 1."""
     H, A, k = 128, 12, 600
-    blob = dp.init_blob(H, A, 23)
-    datas = [dp.batch(np.random.RandomState(30 + j), 900 + 100 * j, A) for j in range(2)]
+    blob = lh.init_blob(H, A, 23)
+    datas = [lh.batch(np.random.RandomState(30 + j), 900 + 100 * j, A) for j in range(2)]
     rings = [_ring(d, 40 + j, k, prio_seed=j) for j, d in enumerate(datas)]
     twins = [_ring(d, 40 + j, k, prio_seed=j) for j, d in enumerate(datas)]
     L = lh.learner(H, A, loss, blob, max_batch=k)
@@ -273,10 +271,10 @@ def test_update_from_many_uses_each_rings_own_weights(loss):
         assert float(w.max()) == 1.0
         i, wn = idx.cpu().numpy(), w.cpu().numpy()
         parts.append((lh.gathered(d, i), wn))
-        rows.append(wm.shard_sums(blob, H, A, *lh.gathered(d, i), GAMMA, loss, wn))
-    ral, rcl, g = dp.combine(rows, H, A, loss)
+        rows.append(mirror.shard_sums(blob, H, A, *lh.gathered(d, i), GAMMA, loss, wn))
+    ral, rcl, g = mirror.combine(rows, H, A, loss)
     whole = tuple(np.concatenate([p[0][q] for p in parts]) for q in range(4))
-    wal, wcl, rtd, wg = wm.losses_and_grads(blob, H, A, *whole, GAMMA, loss, np.concatenate([p[1] for p in parts]))
+    wal, wcl, rtd, wg = mirror.losses_and_grads(blob, H, A, *whole, GAMMA, loss, weights=np.concatenate([p[1] for p in parts]))[:4]
     assert abs(ral - wal) <= 1e-12 * abs(wal) and np.abs(g - wg).max() <= 1e-12 * np.abs(wg).max()
     lh.assert_losses_and_td(al.cpu().numpy(), cl.cpu().numpy(), torch.cat(tds).cpu().numpy(), ral, rcl, rtd)
     lh.assert_step_from_zero(lh.state(L), blob, g, 2 * k, H, A)
@@ -293,7 +291,7 @@ def _beta(c, beta0=0.4, beta1=1.0, calls=3):
 
 def test_annealed_draws_equal_draws_at_the_schedules_beta():
     n, k = 5000, 777
-    data = dp.batch(np.random.RandomState(41), n, 12)
+    data = lh.batch(np.random.RandomState(41), n, 12)
     ring, twin = _ring(data, 9, k), _ring(data, 9, k)
     seen = []
     for c in range(5):
@@ -319,8 +317,8 @@ def test_a_replayed_graph_anneals():
     """One update_from(..., importance=True, beta_final=1.0, anneal_calls=3) captured once and replayed five times ==
     five eager updates at the schedule's beta, bitwise: parameters and priorities after every replay."""
     H, A, n, k = 128, 12, 5000, 2048
-    data = dp.batch(np.random.RandomState(42), n, A)
-    blob = dp.init_blob(H, A, 42)
+    data = lh.batch(np.random.RandomState(42), n, A)
+    blob = lh.init_blob(H, A, 42)
     eager, re_ = lh.learner(H, A, "reference", blob, max_batch=k), _ring(data, 5, k)
     graphed, rg = lh.learner(H, A, "reference", blob, max_batch=k), _ring(data, 5, k)
     torch.cuda.synchronize()

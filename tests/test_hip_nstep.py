@@ -10,9 +10,8 @@ import numpy as np
 import pytest
 import torch
 
-import learner_dp_mirror as dp
 import learner_harness as lh
-import learner_weighted_mirror as wm
+import learner_mirror as mirror
 import nstep_mirror as nm
 import ring_rollout_harness as rr
 from ring_rollout_harness import B, DONES, N, NTR, RINGS, T
@@ -96,7 +95,7 @@ CASES = [(H, A, n, loss, gather) for H, A, n in SHAPES for loss in ("reference",
 
 def _discount_store(cap, seed):
     """A per-slot store in [0, 1] with exact zeros and an exact one (cap 1: a single zero)."""
-    return wm.make_weights(np.random.RandomState(seed + 101), cap) if cap > 1 else np.zeros(1, np.float32)
+    return lh.make_weights(np.random.RandomState(seed + 101), cap) if cap > 1 else np.zeros(1, np.float32)
 
 
 # ---- 3. gamma everywhere is nothing --------------------------------------------------------------------------------------
@@ -109,7 +108,7 @@ VARIANTS = ("plain", "weighted", "regularised", "diagnostics")
 def test_a_store_of_gamma_and_null_are_the_plain_update_bitwise(H, A, n, loss, gather, variant):
     blob, b, store, cap, idx, it = lh.case(H, A, n, gather)
     prio0 = torch.rand(cap, device=DEV) + 0.1
-    w = lh.dev(wm.make_weights(np.random.RandomState(n + H), n)) if variant == "weighted" else None
+    w = lh.dev(lh.make_weights(np.random.RandomState(n + H), n)) if variant == "weighted" else None
     kw = {}
     if variant == "regularised":                                       # (the entropy bonus exists for per_sample only)
         kw = dict(c=0.01 if loss == "per_sample" else 0.0, mgn=(0.05, 0.5))
@@ -148,12 +147,13 @@ def test_random_discounts_against_fp64_mirror(H, A, n, gather, loss, path):
     blob, b, store, cap, idx, it = lh.case(H, A, n, gather)
     ds = _discount_store(cap, n + H)
     d = ds[idx]                                                         # the per-row discounts, through the index vector
-    w = wm.make_weights(np.random.RandomState(n + H + 5), n) if path != "plain" else None
+    w = lh.make_weights(np.random.RandomState(n + H + 5), n) if path != "plain" else None
     c = 0.01 if path == "regularised" else None
     L = lh.learner(H, A, loss, blob, max_batch=n, c=c or 0.0)
     out = lh.update(L, n, store, cap, it, None, None if w is None else lh.dev(w), lh.dev(ds))
     L.check()
-    ref = nm.learner(blob, H, A, *lh.gathered(b, idx), d, loss, w, None if c is None else np.float32(c))
+    opts = dict(weights=w, entropy_coef=0.0 if c is None else np.float32(c))
+    ref = mirror.losses_and_grads(blob, H, A, *lh.gathered(b, idx), d, loss, **opts)
     ral, rcl, rtd, g = ref[:4]
     lh.assert_losses_and_td(out["actor_loss"], out["critic_loss"], out["td"], ral, rcl, rtd)
     lh.assert_step_from_zero(out, blob, g, n, H, A)
@@ -161,11 +161,11 @@ def test_random_discounts_against_fp64_mirror(H, A, n, gather, loss, path):
     zero = d == 0
     assert zero.any() or n < 63
     if zero.any():
-        r0 = nm.learner(blob, H, A, *lh.gathered(b, idx), np.zeros(n), loss, w, None if c is None else np.float32(c))[2]
+        r0 = mirror.losses_and_grads(blob, H, A, *lh.gathered(b, idx), np.zeros(n), loss, **opts).td
         assert np.array_equal(r0[zero], rtd[zero])
         np.testing.assert_allclose(out["td"][zero], r0[zero], rtol=0, atol=2e-5 * (np.abs(rtd).max() + 1e-6))
     if n >= 63:       # the discounts are in the result: gamma for every row is far outside the bound
-        gu = nm.learner(blob, H, A, *lh.gathered(b, idx), np.full(n, GAMMA), loss, w, None if c is None else np.float32(c))[3]
+        gu = mirror.losses_and_grads(blob, H, A, *lh.gathered(b, idx), np.full(n, GAMMA), loss, **opts).grad
         assert np.abs(out["exp_avg"] / 0.1 - gu).max() > 100 * lh.tol_g(n, g)
 
 
@@ -174,11 +174,11 @@ def test_the_discount_is_per_slot_and_the_weight_per_batch_row():
     H, A, n = 64, 12, 63
     blob, b, store, cap, _, _ = lh.case(H, A, n, False)
     idx = np.arange(n)[::-1].copy()
-    ds, w = _discount_store(cap, 3), wm.make_weights(np.random.RandomState(4), n)
+    ds, w = _discount_store(cap, 3), lh.make_weights(np.random.RandomState(4), n)
     L = lh.learner(H, A, "per_sample", blob, max_batch=n)
     out = lh.update(L, n, store, cap, lh.dev(idx), None, lh.dev(w), lh.dev(ds))
     L.check()
-    ral, rcl, rtd, g = nm.learner(blob, H, A, *lh.gathered(b, idx), ds[idx], "per_sample", w)
+    ral, rcl, rtd, g = mirror.losses_and_grads(blob, H, A, *lh.gathered(b, idx), ds[idx], "per_sample", weights=w)[:4]
     lh.assert_losses_and_td(out["actor_loss"], out["critic_loss"], out["td"], ral, rcl, rtd)
     lh.assert_step_from_zero(out, blob, g, n, H, A)
 
@@ -194,7 +194,7 @@ SPLIT = [(64, 48, 63), (128, 12, 65), (128, 12, 4096)]
 def test_grad_apply_write_is_the_discounted_update_bitwise(H, A, n, loss, weighted):
     blob, b, store, cap, idx, it = lh.case(H, A, n, True)
     ds = lh.dev(_discount_store(cap, n))
-    w = lh.dev(wm.make_weights(np.random.RandomState(n), n)) if weighted else None
+    w = lh.dev(lh.make_weights(np.random.RandomState(n), n)) if weighted else None
     prio0 = torch.rand(cap, device=DEV) + 0.1
     closed = lh.learner(H, A, loss, blob, max_batch=n)
     want = lh.update(closed, n, store, cap, it, prio0.clone(), w, ds)
@@ -224,7 +224,7 @@ def test_a_row_with_discounts_and_a_row_without_apply_together(H, A, n, loss):
     al, cl = L.apply(rows)
     L.check()
     d = np.concatenate([ds[idx[:h]].astype(np.float64), np.full(n - h, float(G32))])
-    ral, rcl, rtd, g = nm.learner(blob, H, A, *lh.gathered(b, idx), d, loss)
+    ral, rcl, rtd, g = mirror.losses_and_grads(blob, H, A, *lh.gathered(b, idx), d, loss)[:4]
     lh.assert_losses_and_td(al.cpu().numpy(), cl.cpu().numpy(), torch.cat([td0, td1]).cpu().numpy(), ral, rcl, rtd)
     lh.assert_step_from_zero(lh.state(L), blob, g, n, H, A)
 
@@ -404,15 +404,15 @@ def test_ring_arguments_and_the_gamma_check():
         assert plain.with_nstep() is plain
         assert plain.discounts is None and plain.n_step == 1 and plain.gamma is None
         assert "discounts" not in (plain.sample(4) if cls is u.ReplayRing else plain.sample(4)[0])
-    data = dp.batch(np.random.RandomState(1), 300, 12)
+    data = lh.batch(np.random.RandomState(1), 300, 12)
     ring = _filled_ring("uniform", data, 3, 100, gamma=0.9)
-    L = lh.learner(64, 12, "reference", dp.init_blob(64, 12, 1), max_batch=100)
+    L = lh.learner(64, 12, "reference", lh.init_blob(64, 12, 1), max_batch=100)
     before = lh.state(L)
     for call in (lambda: L.update_from(ring, 100), lambda: L.grad_from(ring, 100), lambda: L.update_from_many([ring], 100)):
         with pytest.raises(ValueError, match=r"0\.9\b.*0\.95\b"):
             call()
     lh.same(lh.state(L), before)
-    L9 = lh.learner(64, 12, "reference", dp.init_blob(64, 12, 1), max_batch=100, gamma=0.9)
+    L9 = lh.learner(64, 12, "reference", lh.init_blob(64, 12, 1), max_batch=100, gamma=0.9)
     L9.update_from(ring, 100)
     L9.check()
 
@@ -420,7 +420,7 @@ def test_ring_arguments_and_the_gamma_check():
 @pytest.mark.parametrize("kind", ["uniform", "prioritised"])
 def test_add_fills_the_discounts_and_sample_carries_them(kind):
     n = 300
-    data = dp.batch(np.random.RandomState(2), n, 12)
+    data = lh.batch(np.random.RandomState(2), n, 12)
     ring = _filled_ring(kind, data, 3, 100)
     ds = _discount_store(n, 1)
     assert np.array_equal(ring.discounts[:n].cpu().numpy(), ds)
@@ -443,8 +443,8 @@ def test_add_fills_the_discounts_and_sample_carries_them(kind):
 @pytest.mark.parametrize("kind", ["uniform", "prioritised"])
 def test_update_from_and_grad_from_are_draw_discounted_call_write(kind, importance):
     H, A, n, k = 128, 12, 3000, 1000
-    data = dp.batch(np.random.RandomState(21), n, A)
-    blob = dp.init_blob(H, A, 21)
+    data = lh.batch(np.random.RandomState(21), n, A)
+    blob = lh.init_blob(H, A, 21)
     one, ring = lh.learner(H, A, "per_sample", blob, max_batch=k), _filled_ring(kind, data, 17, k)
     two, twin = lh.learner(H, A, "per_sample", blob, max_batch=k), _filled_ring(kind, data, 17, k)
     imp = importance and kind == "prioritised"
@@ -480,8 +480,8 @@ def test_update_from_and_grad_from_are_draw_discounted_call_write(kind, importan
 
 def test_update_from_many_over_two_nstep_rings():
     H, A, k = 128, 12, 600
-    blob = dp.init_blob(H, A, 23)
-    datas = [dp.batch(np.random.RandomState(30 + j), 900 + 100 * j, A) for j in range(2)]
+    blob = lh.init_blob(H, A, 23)
+    datas = [lh.batch(np.random.RandomState(30 + j), 900 + 100 * j, A) for j in range(2)]
     kinds = ("prioritised", "uniform")
     rings = [_filled_ring(kd, d, 40 + j, k, dseed=j) for j, (kd, d) in enumerate(zip(kinds, datas))]
     twins = [_filled_ring(kd, d, 40 + j, k, dseed=j) for j, (kd, d) in enumerate(zip(kinds, datas))]
@@ -517,7 +517,7 @@ def test_add_and_update_captured_and_replayed_equal_eager():
     H, A, k = 64, 12, 32
     r = rr.rollout()
     out = rr.out(rr.done("mid"))
-    blob = dp.init_blob(H, A, 42)
+    blob = lh.init_blob(H, A, 42)
 
     def fresh():
         ring = _new_ring("prioritised", 100, n_step=3, gamma=GAMMA)      # empty: every drawn slot is one the add wrote

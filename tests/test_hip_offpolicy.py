@@ -8,7 +8,6 @@ import numpy as np
 import pytest
 import torch
 
-import learner_dp_mirror as dp
 import learner_harness as lh
 import offpolicy_mirror as om
 from uavtrack.replay import DrawSpec
@@ -43,10 +42,10 @@ def _store(H, A, n):
     if key not in _stores:
         rng = np.random.RandomState(31 * H + n)
         cap = n + 7
-        s, a, r, s2 = dp.batch(rng, cap, A)
+        s, a, r, s2 = lh.batch(rng, cap, A)
         idx = rng.randint(0, cap, size=n).astype(np.int64)
         store = {k: lh.dev(x) for k, x in zip(lh.STORES, (s, a, r, s2))}
-        _stores[key] = (dp.init_blob(H, A, H + n), s, a, store, cap, idx, lh.dev(idx))
+        _stores[key] = (lh.init_blob(H, A, H + n), s, a, store, cap, idx, lh.dev(idx))
     return _stores[key]
 
 
@@ -240,7 +239,7 @@ H0, A0 = 64, 12
 
 
 def _twins(loss="per_sample"):
-    blob = dp.init_blob(H0, A0, 77)
+    blob = lh.init_blob(H0, A0, 77)
     return lh.learner(H0, A0, loss, blob, max_batch=64), lh.learner(H0, A0, loss, blob, max_batch=64), blob
 
 
@@ -348,7 +347,7 @@ def test_every_add_form_leaves_the_actors_log_probs_in_the_slots_it_wrote(form):
 
 def _flat(n, seed, log_mu=None):
     rng = np.random.RandomState(seed)
-    s, a, r, s2 = dp.batch(rng, n, A0)
+    s, a, r, s2 = lh.batch(rng, n, A0)
     d = {"states": lh.dev(s), "actions": lh.dev(a), "rewards": lh.dev(r), "next_states": lh.dev(s2)}
     if log_mu is not None:
         d["log_mu"] = lh.dev(np.asarray(log_mu, np.float32))
@@ -425,7 +424,7 @@ def test_update_from_many_is_the_apply_of_the_explicit_weighted_rows():
     for r1, r2 in zip(rings1, rings2):
         _fill(r1, L1)
         _fill(r2, L2)
-    stale = dp.init_blob(H0, A0, 78)                                        # the actor moves on; the stores stay
+    stale = lh.init_blob(H0, A0, 78)                                        # the actor moves on; the stores stay
     L1._set_params(0.5 * (L1._get_params() + stale))
     L2._set_params(0.5 * (L2._get_params() + stale))
     before = lh.state(L1)
@@ -461,7 +460,7 @@ def test_draw_weights_and_update_capture_into_one_graph():
     r1, r2 = _ring("prioritised", True), _ring("prioritised", True)
     _fill(r1, L1)
     _fill(r2, L2)
-    stale = dp.init_blob(H0, A0, 78)
+    stale = lh.init_blob(H0, A0, 78)
     L1._set_params(0.5 * (L1._get_params() + stale))
     L2._set_params(0.5 * (L2._get_params() + stale))
     rho1, rho2 = torch.empty(63, device=DEV), torch.empty(63, device=DEV)

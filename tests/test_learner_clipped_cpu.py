@@ -1,4 +1,4 @@
-"""The clipped surrogate without a GPU: the float64 mirror (tests/learner_clipped_mirror.py) against torch autograd, the
+"""The clipped surrogate without a GPU: the float64 mirror (tests/learner_mirror.py with clip=) against torch autograd, the
 premises of the batches the GPU tests use, the host-side refusals of the Python layer, and the library calls the drawn
 paths enqueue with and without clip_eps (tests/learner_call_trace.py's recorder)."""
 import json
@@ -7,40 +7,17 @@ import numpy as np
 import pytest
 import torch
 
+import learner_autograd as ag
 import learner_call_trace as lt
 import learner_clipped_mirror as cm
-import learner_dp_mirror as dp
+import learner_harness as lh
 import learner_mirror as mirror
-import learner_weighted_mirror as wm
 
 INF = float("inf")
 GAMMA = cm.GAMMA
 
 
 # ---- 1. the mirror is torch's gradient -----------------------------------------------------------------------------------
-
-def _torch_update(blob, H, A, s, a, r, s2, gamma, log_mu, eps, w, c):
-    """(actor_loss, critic_loss, flat gradient) of -(min(r A, clamp(r, 1 - eps, 1 + eps) A) + c H) w and w (V - y)^2 by
-    autograd in float64, the bounds the float32 ones the library folds."""
-    params = [torch.tensor(np.asarray(x, np.float64), requires_grad=True) for x in mirror.unpack(blob, H, A)]
-    w1a, b1a, w2a, b2a, w1c, b1c, w2c, b2c = params
-    s, s2 = torch.tensor(np.asarray(s, np.float64)), torch.tensor(np.asarray(s2, np.float64))
-    a = torch.tensor(np.asarray(a, np.int64))
-    w = torch.tensor(np.asarray(w, np.float64))
-    logp = torch.log_softmax(torch.relu(s @ w1a.T + b1a) @ w2a.T + b2a, dim=1)
-    critic = lambda x: (torch.relu(x @ w1c.T + b1c) @ w2c.reshape(1, H).T)[:, 0] + b2c[0]               # noqa: E731
-    v = critic(s)
-    target = (torch.tensor(np.asarray(r, np.float64)) + gamma * critic(s2)).detach()
-    adv = (target - v).detach()
-    ratio = torch.exp(logp.gather(1, a[:, None])[:, 0] - torch.tensor(np.asarray(log_mu, np.float64)))
-    lo, hi = cm.bounds(eps)
-    ent = -(torch.exp(logp) * logp).sum(dim=1)
-    actor_loss = ((-torch.min(ratio * adv, ratio.clamp(lo, hi) * adv) - c * ent) * w).mean()
-    critic_loss = (w * (v - target) ** 2).mean()
-    ga = torch.autograd.grad(actor_loss, params[:4])
-    gc = torch.autograd.grad(critic_loss, params[4:])
-    return float(actor_loss.detach()), float(critic_loss.detach()), np.concatenate([g.numpy().ravel() for g in ga + gc])
-
 
 @pytest.mark.parametrize("eps", [0.2, INF])
 @pytest.mark.parametrize("H,A,n", [(33, 12, 63), (128, 48, 65)])
@@ -49,16 +26,18 @@ def test_the_mirror_is_torch_autograd_in_float64(H, A, n, eps):
     cb = cm.clip_batch(H, A, n, gather)
     rows = tuple(x[cb["idx"]] for x in cb["b"])
     mu = cb["log_mu"][cb["idx"]]
-    w = wm.make_weights(np.random.RandomState(n), n)
+    w = lh.make_weights(np.random.RandomState(n), n)
     c = 0.01
-    al, cl, td, g, ent, ratio = cm.losses_and_grads(cb["blob"], H, A, *rows, GAMMA, mu, eps, w, c)
-    tal, tcl, tg = _torch_update(cb["blob"], H, A, *rows, GAMMA, mu, eps, w, c)
+    al, cl, td, g, ent, ratio = mirror.losses_and_grads(cb["blob"], H, A, *rows, GAMMA, "per_sample", weights=w,
+                                                        entropy_coef=c, clip=(mu, eps))
+    t = ag.update(cb["blob"], H, A, *rows, GAMMA, "per_sample", w, c, clip=(mu, eps))
+    tal, tcl, tg = t.actor_loss, t.critic_loss, t.grad
     assert abs(al - tal) <= 1e-12 * abs(tal) and abs(cl - tcl) <= 1e-12 * abs(tcl)
     assert np.abs(g - tg).max() <= 1e-12 * np.abs(tg).max()
     # a row of the split form is the same gradient before its scale, and rows add
-    halves = [cm.shard_sums(cb["blob"], H, A, *(x[lo:hi] for x in rows), GAMMA, mu[lo:hi], eps, w[lo:hi], c)
-              for lo, hi in dp.cuts(n, 2)]
-    cal, ccl, cg = dp.combine(halves, H, A, "per_sample")
+    halves = [mirror.shard_sums(cb["blob"], H, A, *(x[lo:hi] for x in rows), GAMMA, "per_sample", w[lo:hi], c, (mu[lo:hi], eps))
+              for lo, hi in lh.cuts(n, 2)]
+    cal, ccl, cg = mirror.combine(halves, H, A, "per_sample")
     assert abs(cal - tal) <= 1e-12 * abs(tal) and np.abs(cg - tg).max() <= 1e-12 * np.abs(tg).max()
     if eps == 0.2:
         assert not cm.gate(ratio, td, eps).all() and cm.gate(ratio, td, INF).all()

@@ -1,21 +1,17 @@
 """The split learner update without a GPU: the float64 mirror of gradient rows and their ordered combine
-(tests/learner_dp_mirror.py) against the whole-batch mirror (tests/learner_mirror.py), the rule it must not be mistaken
-for, and the new entry points' declarations."""
+(tests/learner_mirror.py's shard_sums and combine) against the whole-batch update, the rule it must not be mistaken for,
+and the new entry points' declarations."""
 import os
 import re
 
 import numpy as np
 import pytest
 
-import learner_dp_mirror as dp
 import learner_harness as lh
 import learner_mirror as mirror
+from learner_autograd import rel as _rel
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def _rel(x, y):
-    return np.abs(np.asarray(x) - np.asarray(y)).max() / (np.abs(np.asarray(y)).max() + 1e-300)
 
 
 @pytest.mark.parametrize("loss", ["reference", "per_sample"])
@@ -25,17 +21,17 @@ def test_combined_shards_equal_the_whole_batch(K, loss):
     the whole batch to 1e-12 relative: losses, gradient, parameters and both moments."""
     H, A, n, gamma, lrs = 33, 9, 1000, 0.95, (1e-3, 5e-3)
     rng = np.random.RandomState(K)
-    b = dp.batch(rng, n, A)
-    blob = dp.init_blob(H, A, 3)
+    b = lh.batch(rng, n, A)
+    blob = lh.init_blob(H, A, 3)
     P = blob.size
     state = {"params": blob, "exp_avg": rng.randn(P) * 1e-3, "exp_avg_sq": rng.rand(P) * 1e-6, "step": np.full(8, 4)}
-    pieces = dp.cuts(n, K)
+    pieces = lh.cuts(n, K)
     assert len(pieces) == K and len({hi - lo for lo, hi in pieces}) > 1
-    rows = [dp.shard_sums(blob, H, A, *sh, gamma, loss) for sh in dp.split(b, pieces)]
-    got, al, cl = dp.update_from_rows(state, rows, H, A, lrs, loss)
+    rows = [mirror.shard_sums(blob, H, A, *sh, gamma, loss) for sh in lh.split(b, pieces)]
+    got, al, cl = mirror.update_from_rows(state, rows, H, A, lrs, loss)
     want, wal, wcl, wtd = mirror.update(state, H, A, *b, gamma, lrs, loss)
     assert abs(al - wal) <= 1e-12 * abs(wal) and abs(cl - wcl) <= 1e-12 * abs(wcl)
-    g = dp.combine(rows, H, A, loss)[2]
+    g = mirror.combine(rows, H, A, loss)[2]
     assert _rel(g, mirror.losses_and_grads(blob, H, A, *b, gamma, loss)[3]) <= 1e-12
     for k in ("params", "exp_avg", "exp_avg_sq"):
         assert _rel(got[k], want[k]) <= 1e-12, k
@@ -48,14 +44,14 @@ def test_averaging_shard_gradients_is_a_different_rule(K):
     """On the shared batch (rewards ramp across the rows) the average of the shards' own reference-loss gradients is
     further from the combined gradient than 100 x the bound the GPU test applies to the device's gradient, so a device
     path that averaged per-shard gradients could not pass it."""
-    c = dp.TEETH
-    blob, b = dp.teeth_batch()
-    shards = dp.split(b, dp.cuts(c["n"], K))
-    md = [dp.shard_sums(blob, c["H"], c["A"], *sh, c["gamma"])["loss"][1] / len(sh[1]) for sh in shards]
+    c = lh.TEETH
+    blob, b = lh.teeth_batch()
+    shards = lh.split(b, lh.cuts(c["n"], K))
+    md = [mirror.shard_sums(blob, c["H"], c["A"], *sh, c["gamma"])["loss"][1] / len(sh[1]) for sh in shards]
     assert max(md) - min(md) > 1.0                                       # the shards' mean(delta) clearly differ
-    g = dp.combine([dp.shard_sums(blob, c["H"], c["A"], *sh, c["gamma"]) for sh in shards], c["H"], c["A"])[2]
+    g = mirror.combine([mirror.shard_sums(blob, c["H"], c["A"], *sh, c["gamma"]) for sh in shards], c["H"], c["A"])[2]
     assert _rel(g, mirror.losses_and_grads(blob, c["H"], c["A"], *b, c["gamma"])[3]) <= 1e-12
-    naive = dp.averaged_shard_gradients(blob, c["H"], c["A"], shards, c["gamma"])
+    naive = mirror.averaged_shard_gradients(blob, c["H"], c["A"], shards, c["gamma"])
     na = sum(mirror.layout(c["H"], c["A"])[0][:4])                       # the actor's part: where mean(delta) acts
     tol = lh.tol_g(c["n"], g)
     assert np.abs(naive[:na] - g[:na]).max() > 100 * tol, (np.abs(naive[:na] - g[:na]).max(), tol)

@@ -1,17 +1,13 @@
 """The gradient comparison of tests/learner_gradient_cases.py without a GPU: every case meets its margin condition, both
 fp32 CPU references (torch autograd, the strictly sequential float32 sum) pass the comparator with a factor of two to
-spare, the wrapper's float64 sums are the four existing mirrors' wherever they overlap, the recovery of a gradient from
+spare, the wrapper's float64 sums are the mirror's one-call forms' wherever they overlap, the recovery of a gradient from
 Adam's first moments round-trips, and wrong backward passes (mutants: changed copies of the float64 backward, held here
 and never in the library) fail where they must and only there."""
 import numpy as np
 import pytest
 
-import learner_dp_mirror as dp
 import learner_gradient_cases as lg
 import learner_mirror as mirror
-import learner_regularised_mirror as rm
-import learner_target_mirror as tm
-import learner_weighted_mirror as wm
 import pmi_gradient_cases as pc
 
 IDS = [lg.spec_id(sp) for sp in lg.GRID]
@@ -105,7 +101,7 @@ def test_scales_bound_their_sums_and_zero_scales_are_exact_zeros(sp):
     assert not any(np.isinf(v) for v in lg.errors(row64, row64, ref.S_row, c.H, c.A).values())
 
 
-# ---- the wrapper against the four mirrors
+# ---- the wrapper against the mirror's one-call forms
 
 @pytest.mark.parametrize("sp", lg.GRID, ids=IDS)
 def test_wrapper_is_the_existing_mirrors_where_they_overlap(sp):
@@ -120,25 +116,26 @@ def test_wrapper_is_the_existing_mirrors_where_they_overlap(sp):
     def same(row, lag):
         close(ref.sums, row["g"]); close(ref.loss4, row["loss"]); close(ref.td, row["td"])
         close(ref.actor_loss, lag[0]); close(ref.critic_loss, lag[1]); close(ref.td, lag[2]); close(unclipped, lag[3])
+    args = (c.blob, H, A, s, a, r, s2)
     if sp.body == "plain":
-        same(dp.shard_sums(c.blob, H, A, s, a, r, s2, g, c.loss), mirror.losses_and_grads(c.blob, H, A, s, a, r, s2, g, c.loss))
-        comb = dp.combine([dp.shard_sums(c.blob, H, A, s, a, r, s2, g, c.loss)], H, A, c.loss)
+        same(mirror.shard_sums(*args, g, c.loss), mirror.losses_and_grads(*args, g, c.loss))
+        comb = mirror.combine([mirror.shard_sums(*args, g, c.loss)], H, A, c.loss)
         close(unclipped, comb[2])
     elif sp.body == "weighted":
-        same(wm.shard_sums(c.blob, H, A, s, a, r, s2, g, c.loss, w), wm.losses_and_grads(c.blob, H, A, s, a, r, s2, g, c.loss, w))
+        same(mirror.shard_sums(*args, g, c.loss, w), mirror.losses_and_grads(*args, g, c.loss, weights=w))
     elif sp.body in ("reg0", "regc"):
-        same(rm.shard_sums(c.blob, H, A, s, a, r, s2, g, c.loss, None, c.c),
-             rm.losses_and_grads(c.blob, H, A, s, a, r, s2, g, c.loss, None, c.c))
-        close(ref.entropy, rm.policy(c.blob, H, A, s)[2])
+        same(mirror.shard_sums(*args, g, c.loss, None, c.c), mirror.losses_and_grads(*args, g, c.loss, entropy_coef=c.c))
+        close(ref.entropy, mirror.policy(c.blob, H, A, s)[2])
     elif sp.body == "target":
-        lag = tm.losses_and_grads(c.blob, c.theta, H, A, s, a, r, s2, g, c.loss)
+        lag = mirror.losses_and_grads(*args, g, c.loss, theta=c.theta)
         close(ref.actor_loss, lag[0]); close(ref.critic_loss, lag[1]); close(ref.td, lag[2]); close(unclipped, lag[3])
-    else:                                                       # discounts: the weighted mirror on y folded by hand
-        y = tm.bootstrapped(c.theta if c.theta is not None else tm.critic_block(c.blob, H, A), H, r, s2, d)
-        same(rm.shard_sums(c.blob, H, A, s, a, y, s2, 0.0, c.loss, w, c.c),
-             rm.losses_and_grads(c.blob, H, A, s, a, y, s2, 0.0, c.loss, w, c.c))
+    else:                                                       # discounts: the mirror on y folded by hand
+        th = c.theta if c.theta is not None else mirror.critic_block(c.blob, H, A)
+        y = np.asarray(r, np.float64) + np.asarray(d, np.float64) * mirror.values64(th, H, s2)
+        same(mirror.shard_sums(c.blob, H, A, s, a, y, s2, 0.0, c.loss, w, c.c),
+             mirror.losses_and_grads(c.blob, H, A, s, a, y, s2, 0.0, c.loss, weights=w, entropy_coef=c.c))
     if c.mgn:
-        coef, _, clipped = rm.clip(unclipped, H, A, c.mgn)
+        coef, _, clipped = mirror.clip_grad_norm(unclipped, H, A, c.mgn)
         close(ref.grad, clipped)
         assert (coef < 1).all() and abs(coef[0] - coef[1]) > 0.1 * coef.max()
 
@@ -167,9 +164,8 @@ G32 = float(np.float32(lg.GAMMA))
 
 
 def _backward(f, gz, gv, keep=slice(None), mask_c=None, no_unit=False, no_logit=False):
-    """learner_weighted_mirror._backward with the rows of the sums, the critic's mask and the actor's dL/dh open to
-    change."""
-    s, ha, hc, pa, pc_, w2a, w2c = f["s"], f["ha"], f["hc"], f["pa"], f["pc"], f["w2a"], f["w2c"]
+    """learner_mirror.backward with the rows of the sums, the critic's mask and the actor's dL/dh open to change."""
+    s, ha, hc, pa, pc_, w2a, w2c = f.s, f.ha, f.hc, f.pa, f.pc, f.w2a, f.w2c
     A, H = w2a.shape
     g_w2a = gz[keep].T @ ha[keep]; g_b2a = gz[keep].sum(0)
     dha = (gz[:, :A - 1] @ w2a[:A - 1] if no_logit else gz @ w2a) * (pa > 0)
@@ -186,19 +182,18 @@ def _mutant(c, kind):
     """(row words, scaled gradient) of the float64 update with one thing wrong."""
     H, A, n, R = c.H, c.A, c.n, lg.rows_per_tile(c.H)
     (s, a, r, s2), w, d = lg.batch_of(c)
-    online = tm.critic_block(c.blob, H, A)
-    th = online if c.theta is None else c.theta
+    th = c.theta
     blob, cc = c.blob, c.c
     if kind == "gamma_for_discount":
         d = np.full(n, G32)
     if kind == "online_in_next":
-        th = online
+        th = None
     if kind == "target_in_v":
-        blob = tm.with_critic(c.blob, H, A, c.theta)
+        blob = mirror.with_critic(c.blob, H, A, c.theta)
     if kind == "entropy_sign":
         cc = -cc
-    y = tm.bootstrapped(th, H, r, s2, d)
-    f, _, gz, gv, lt, _ = rm._terms(blob, H, A, s, a, y, s2, 0.0, c.loss, w, cc)
+    f = mirror.forward(blob, H, A, s, a, r, s2, d, th)
+    gz, gv, lt, _ = mirror.terms(f, c.loss, w, cc)
     kw = {}
     keep = np.ones(n, bool)
     if kind in ("last_row", "row_R"):
@@ -208,14 +203,14 @@ def _mutant(c, kind):
     if kind in ("last_row", "row_R", "revisited_tile"):
         kw["keep"] = keep
     if kind == "critic_mask_next":
-        t64 = np.asarray(th, np.float64)
+        t64 = np.asarray(mirror.critic_block(c.blob, H, A) if th is None else th, np.float64)
         kw["mask_c"] = (np.asarray(s2, np.float64) @ t64[:12 * H].reshape(H, 12).T + t64[12 * H:13 * H]) > 0
     if kind == "no_unit":
         kw["no_unit"] = True
     if kind == "no_logit":
         kw["no_logit"] = True
     if kind == "unweighted_value":
-        gv = f["v"] - f["target"]
+        gv = f.v - f.target
     sums, loss4 = _backward(f, gz, gv, **kw), lt.sum(axis=1)
     md = lt[1][:R].sum() / R if kind == "first_tile_mean" else None
     return np.concatenate([sums, loss4]), lg._scaled(c, sums, loss4, n, md=md, swap=kind == "other_clip")[0]

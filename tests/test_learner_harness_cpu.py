@@ -4,7 +4,6 @@ tests apply sits within 10 % of the figure written here.  The factors bracket; t
 import numpy as np
 import pytest
 
-import learner_dp_mirror as dp
 import learner_harness as lh
 import learner_mirror as mirror
 
@@ -20,8 +19,8 @@ def _adam(blob, g):
 def synthetic(request):
     """The mirror's update and a device result that is the mirror's: td_delta and the losses cast to fp32, exp_avg
     0.1 g, the parameters mirror.adam's."""
-    blob = dp.init_blob(H, A, H + N)
-    ral, rcl, rtd, g = mirror.losses_and_grads(blob, H, A, *dp.batch(np.random.RandomState(1), N, A), lh.GAMMA, request.param)
+    blob = lh.init_blob(H, A, H + N)
+    ral, rcl, rtd, g = mirror.losses_and_grads(blob, H, A, *lh.batch(np.random.RandomState(1), N, A), lh.GAMMA, request.param)[:4]
     res = dict(al=float(np.float32(ral)), cl=float(np.float32(rcl)), td=rtd.astype(np.float32).astype(np.float64))
     return blob, (ral, rcl, rtd), g, res, {"exp_avg": 0.1 * g, "params": _adam(blob, g)}
 

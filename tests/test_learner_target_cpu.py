@@ -1,4 +1,4 @@
-"""The target critic without a GPU: the float64 mirror with theta- = the critic is learner_mirror.update; the float32
+"""The target critic without a GPU: the float64 mirror with theta- = the critic is the mirror without a target; the float32
 Polyak rule at tau = 1 returns the critic's bits; DeviceActorCritic.set_target refuses bad arguments before any library
 call (on tests/learner_call_trace.py's handle-less learner, whose library is a recorder); and
 sharding.pack_learner_state / unpack_learner_state round-trip on a stub learner."""
@@ -6,9 +6,8 @@ import numpy as np
 import pytest
 
 import learner_call_trace as lt
-import learner_dp_mirror as dp
+import learner_harness as lh
 import learner_mirror as mirror
-import learner_target_mirror as tm
 from uavtrack import sharding
 
 
@@ -16,21 +15,21 @@ from uavtrack import sharding
 @pytest.mark.parametrize("H,A,n", [(1, 9, 1), (33, 12, 65)])
 def test_mirror_with_the_critic_as_target_is_the_plain_mirror(H, A, n, loss):
     rng = np.random.RandomState(H + n)
-    blob = dp.init_blob(H, A, 3).astype(np.float64)
-    s, a, r, s2 = dp.batch(rng, n, A)
+    blob = lh.init_blob(H, A, 3).astype(np.float64)
+    s, a, r, s2 = lh.batch(rng, n, A)
     P = blob.size
     state = {"params": blob, "exp_avg": rng.standard_normal(P) * 1e-3, "exp_avg_sq": rng.uniform(0, 1e-4, P),
              "step": np.arange(8, dtype=np.int64)}
     want, wal, wcl, wtd = mirror.update(state, H, A, s, a, r, s2, 0.95, (1e-3, 5e-3), loss)
-    got, al, cl, td = tm.update(state, tm.critic_block(blob, H, A), H, A, s, a, r, s2, 0.95, (1e-3, 5e-3), loss)
+    got, al, cl, td = mirror.update(state, H, A, s, a, r, s2, 0.95, (1e-3, 5e-3), loss, theta=mirror.critic_block(blob, H, A))
     for k in ("params", "exp_avg", "exp_avg_sq"):
         np.testing.assert_allclose(got[k], want[k], rtol=0, atol=1e-12)
     assert np.array_equal(got["step"], want["step"])
     np.testing.assert_allclose(td, wtd, rtol=0, atol=1e-12)
     assert abs(al - wal) <= 1e-12 and abs(cl - wcl) <= 1e-12
     # and another target gives another update
-    other = tm.critic_block(dp.init_blob(H, A, 4), H, A)
-    assert np.abs(tm.update(state, other, H, A, s, a, r, s2, 0.95, (1e-3, 5e-3), loss)[3] - wtd).max() > 1e-6
+    other = mirror.critic_block(lh.init_blob(H, A, 4), H, A)
+    assert np.abs(mirror.update(state, H, A, s, a, r, s2, 0.95, (1e-3, 5e-3), loss, theta=other)[3] - wtd).max() > 1e-6
 
 
 def test_polyak_at_tau_one_returns_the_critics_bits_and_each_operation_rounds_on_its_own():
@@ -38,16 +37,16 @@ def test_polyak_at_tau_one_returns_the_critics_bits_and_each_operation_rounds_on
     w = np.concatenate([rng.standard_normal(64), [1e-45, -1e-45, 1e-39, -3e-41, 3.4e38, -3.4e38, 1.0, 0.0]]).astype(np.float32)
     for t in (np.zeros_like(w), -np.zeros_like(w), np.full_like(w, 1e-45), np.full_like(w, -7e-40),
               rng.standard_normal(w.size).astype(np.float32)):
-        got = tm.polyak(t, w, 1.0)
+        got = mirror.polyak(t, w, 1.0)
         assert got.dtype == np.float32 and got.tobytes() == w.tobytes()
-    assert tm.periodic(np.zeros_like(w), w, 6, 3).tobytes() == w.tobytes()
-    assert tm.periodic(np.zeros_like(w), w, 7, 3).tobytes() == np.zeros_like(w).tobytes()
+    assert mirror.periodic(np.zeros_like(w), w, 6, 3).tobytes() == w.tobytes()
+    assert mirror.periodic(np.zeros_like(w), w, 7, 3).tobytes() == np.zeros_like(w).tobytes()
     # tau = 0.3: the separately rounded form, which the fused and the float64 forms both miss somewhere
     t = rng.standard_normal(4096).astype(np.float32)
     w = rng.standard_normal(4096).astype(np.float32)
     tau32 = np.float32(0.3)
     omt = np.float32(1.0) - tau32
-    got = tm.polyak(t, w, 0.3)
+    got = mirror.polyak(t, w, 0.3)
     assert got.tobytes() == ((omt * t).astype(np.float32) + (tau32 * w).astype(np.float32)).astype(np.float32).tobytes()
     wide = (np.float64(omt) * t + np.float64(tau32) * w).astype(np.float32)
     assert (got != wide).any()

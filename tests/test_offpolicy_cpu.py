@@ -1,5 +1,5 @@
 """Off-policy correction without a GPU: the weighted update with w = rho IS the truncated-importance-sampling actor and
-the rho-weighted TD(0) critic (torch autograd in float64 against tests/learner_weighted_mirror.py), the ratio's special
+the rho-weighted TD(0) critic (torch autograd in float64 against tests/learner_mirror.py), the ratio's special
 values, the window an add writes, the three new symbols declared in include/uavtrack.h, exported by the library and
 bound in uavtrack/_lib.py with the header's argument lists, and the Python surface."""
 import ctypes as C
@@ -11,8 +11,8 @@ import numpy as np
 import pytest
 import torch
 
-import learner_dp_mirror as dp
-import learner_weighted_mirror as wm
+import learner_harness as lh
+import learner_mirror as mirror
 import offpolicy_mirror as om
 import uavtrack
 from uavtrack import _lib
@@ -25,9 +25,9 @@ GAMMA = 0.95
 
 def _case(H, A, n):
     rng = np.random.RandomState(100 * H + n)
-    blob = dp.init_blob(H, A, H + n).astype(np.float64)
+    blob = lh.init_blob(H, A, H + n).astype(np.float64)
     blob[13 * H:13 * H + A * H] *= 5                                        # a policy with opinions
-    s, a, r, s2 = dp.batch(rng, n, A)
+    s, a, r, s2 = lh.batch(rng, n, A)
     lp = om.log_probs(blob, H, A, s, a)
     log_mu = np.minimum(lp + rng.uniform(-1.5, 1.5, size=n), 0.0)          # stale behaviour: ratios on both sides of 1
     return blob, (s, a, r, s2), log_mu
@@ -39,7 +39,7 @@ def test_the_weighted_update_with_rho_is_the_truncated_is_actor_and_the_rho_weig
     w, rho = om.weights(blob, H, A, s, a, log_mu, 2.0)
     assert (rho == 2.0).any() or n < 10
     assert (w == rho).all() and (rho > 0).all()
-    _, _, _, want = wm.losses_and_grads(blob, H, A, s, a, r, s2, GAMMA, "per_sample", weights=rho)
+    want = mirror.losses_and_grads(blob, H, A, s, a, r, s2, GAMMA, "per_sample", weights=rho).grad
 
     p = torch.tensor(blob, dtype=torch.float64, requires_grad=True)
     o = np.cumsum([0, 12 * H, H, A * H, A, 12 * H, H, H, 1])
