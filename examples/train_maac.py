@@ -18,6 +18,7 @@ update is the same rule on a sampled batch, and the new actor weights are re-upl
     python examples/train_maac.py --replay prioritized --learner device --td-lambda 0.9                   # lambda-returns: critic values + a backward scan in the ring's add
     python examples/train_maac.py --replay prioritized --learner device --rho-bar 1.0 --publish device --log-every 10   # truncated importance ratios: who acted
     python examples/train_maac.py --replay prioritized --learner device --actor-loss per_sample --ppo-clip 0.2   # ... or PPO's clipped surrogate from the same store
+    python examples/train_maac.py --replay prioritized --learner device --actor-loss per_sample --ppo-clip 0.2 --normalise-advantage   # ... on batch-standardised advantages
     python examples/train_maac.py --replay prioritized --learner device --target-tau 0.005                # bootstrap from a Polyak-averaged target critic
     python examples/train_maac.py --replay prioritized --learner device --target-period 100 --td-lambda 0.9   # ... or a periodic copy; the lambda add folds with it too
     python examples/train_maac.py --method maac-r --pmi-trainer device --learner device --replay prioritized --publish device --log-every 10
@@ -64,7 +65,7 @@ class ValueNet(torch.nn.Module):
 
 
 def update(actor, critic, opt_a, opt_c, batch, gamma, weights=None, entropy_coef=0.0, max_grad_norm=None, diag=None,
-           rho_bar=None, rho_stats=None, target_critic=None, ppo_clip=None):
+           rho_bar=None, rho_stats=None, target_critic=None, ppo_clip=None, normalise=False, adv_stats=None):
     """One ActorCritic.update step (actor_critic.py:150-178) on a batch of transitions.  weights (--importance): the
     draw's importance weights, one per row, multiplied into the per-sample losses before the mean.  entropy_coef and
     max_grad_norm: the two terms of DeviceActorCritic.set_regularisation, so that --learner torch and --learner device
@@ -76,6 +77,9 @@ def update(actor, critic, opt_a, opt_c, batch, gamma, weights=None, entropy_coef
     ppo_clip (--ppo-clip EPS): the batch carries "log_mu" and the policy term of a row becomes
     -min(r A, clamp(r, 1 - EPS, 1 + EPS) A) with r = pi / mu differentiated through and A = td_delta, as
     DeviceActorCritic.update_from(clip_eps=) trains; rho_stats receives the ratios.
+    normalise (--normalise-advantage): the advantage of the policy term, plain or clipped, is the batch's standardised
+    TD error (td - td.mean()) / (td.std() + 1e-8), as DeviceActorCritic.set_advantage("batch") trains; the critic keeps
+    the raw TD error.  adv_stats (a dict) receives the mean and std of td_delta.
     target_critic (--target-tau / --target-period): the copy of the critic that V(s') comes from; keeping it in step
     is the caller's (sync_target_critic)."""
     s, a, r, s2 = batch["states"], batch["actions"].long().unsqueeze(1), batch["rewards"], batch["next_states"]
@@ -88,9 +92,14 @@ def update(actor, critic, opt_a, opt_c, batch, gamma, weights=None, entropy_coef
     td_delta = td_target - critic(s)
     probs = actor(s)
     log_probs = torch.log(probs.gather(1, a).squeeze(1).clamp_min(1e-12))
-    per_row = -log_probs * td_delta.detach()
+    adv = td_delta.detach()
+    if adv_stats is not None:
+        adv_stats["mean"], adv_stats["std"] = adv.mean(), adv.std()
+    if normalise:
+        adv = (adv - adv.mean()) / (adv.std() + 1e-8)
+    per_row = -log_probs * adv
     if ppo_clip is not None:
-        r, adv = torch.exp(log_probs - batch["log_mu"]), td_delta.detach()
+        r = torch.exp(log_probs - batch["log_mu"])
         per_row = -torch.min(r * adv, r.clamp(1 - ppo_clip, 1 + ppo_clip) * adv)
         if rho_stats is not None:
             rho_stats["rho"] = r.detach()
@@ -161,7 +170,15 @@ def device_learner(args, uavtrack, na_total, dev, max_batch):
         learner.enable_diagnostics(max_batch)
     if targeted(args):
         learner.set_target(tau=args.target_tau, period=args.target_period)
+    if args.normalise_advantage:
+        learner.set_advantage("batch")                                # each draw standardised by its own statistics
     return learner
+
+
+def advantage_field(mean, std):
+    """The printed lines' extra field under --normalise-advantage: the mean and the standard deviation of the last
+    update's TD errors (with --shards, of its last ring's draw)."""
+    return f"td mean {float(mean):+.3f} std {float(std):.3f}  "
 
 
 def nstep_ring(args, ring):
@@ -355,6 +372,8 @@ def train_sharded(args, timings=None):
         if log and rho_kw:
             reg_field += rho_field(torch.cat(rhos), args.rho_bar) if args.ppo_clip is None else \
                 ratio_field(torch.cat(rhos), args.ppo_clip)
+        if log and args.normalise_advantage:
+            reg_field += advantage_field(learner.advantage_stats[0], learner.advantage_stats[2])
         if args.publish == "host":
             actor.load_state_dict(learner.actor_state_dict())
             for ro in rollouts:
@@ -461,6 +480,11 @@ def main(argv=None, timings=None):
                          "the gradient kernel; the torch learner trains the same expression); the printed lines show the "
                          "mean ratio, the share of rows with |r - 1| > EPS and mean(-log r).  Needs --replay prioritized or "
                          "uniform-device, and --actor-loss per_sample with --learner device; not with --rho-bar")
+    ap.add_argument("--normalise-advantage", action="store_true",
+                    help="standardise each batch's TD errors before they multiply grad log p (and gate --ppo-clip): "
+                         "A = (td - mean) / (std + 1e-8), in both learners (--learner device: "
+                         "DeviceActorCritic.set_advantage(\"batch\"), --actor-loss per_sample only; with --shards each "
+                         "ring's draw by its own statistics); the printed lines gain the mean and std of td")
     ap.add_argument("--rho-bar", type=float, default=None,
                     help="R > 0: correct for who acted.  The ring keeps log mu(a|s) of every slot, evaluated by the learner's "
                          "actor over the window each add writes (ring.with_behaviour(), add_rollout_behaviour), and every "
@@ -551,6 +575,9 @@ def main(argv=None, timings=None):
     if args.rho_bar is not None and (not args.rho_bar > 0 or args.replay == "uniform"):
         ap.error("--rho-bar must be > 0 and needs --replay prioritized or --replay uniform-device (the device rings keep "
                  "the behaviour log-probabilities)")
+    if args.normalise_advantage and args.learner == "device" and args.actor_loss != "per_sample":
+        ap.error("--normalise-advantage with --learner device needs --actor-loss per_sample: the reference form scales the "
+                 "actor's gradient sums once by -mean(delta) / N, and a standardised advantage has mean 0")
     if args.ppo_clip is not None:
         if not args.ppo_clip >= 0 or args.replay == "uniform":
             ap.error("--ppo-clip must be >= 0 and needs --replay prioritized or --replay uniform-device (the device rings "
@@ -660,8 +687,10 @@ def main(argv=None, timings=None):
         t_roll = time.perf_counter() - t0
         diag = {} if log and regularised(args) else None              # the torch learner's entropy and norms
         rho_stats = {}                                                # --rho-bar: the last update's ratios, a device tensor
+        adv_stats = {} if args.normalise_advantage else None          # the last update's mean and std of td_delta
         reg_kw = dict(entropy_coef=args.entropy_coef, max_grad_norm=args.max_grad_norm, diag=diag, rho_bar=args.rho_bar,
-                      rho_stats=rho_stats, target_critic=target_critic, ppo_clip=args.ppo_clip)
+                      rho_stats=rho_stats, target_critic=target_critic, ppo_clip=args.ppo_clip,
+                      normalise=args.normalise_advantage, adv_stats=adv_stats)
         boot = critic if target_critic is None else target_critic     # whose V(s') the torch learner bootstraps from
         if learner is None and args.replay == "prioritized":          # train.py:250-262
             ikw = importance_kwargs(args)
@@ -734,6 +763,9 @@ def main(argv=None, timings=None):
             reg_field += rho_field(rho_stats["rho"], args.rho_bar)
         if args.ppo_clip is not None:
             reg_field += ratio_field(rho_stats["rho"], args.ppo_clip)
+        if args.normalise_advantage:
+            reg_field += advantage_field(*((adv_stats["mean"], adv_stats["std"]) if learner is None else
+                                           (learner.advantage_stats[0], learner.advantage_stats[2])))
         print(f"iter {it:3d}  episode return {ret:8.3f}  covered targets/step {cov:5.2f}  actor loss {la:+.4f}  "
               f"critic loss {lc:.4f}  {reg_field}pmi loss {lp:.4f}  rollout {t_roll * 1e3:6.1f} ms ({per_iter / t_roll / 1e9:.2f} G agent-steps/s)  "
               f"iteration {((now - t0) if args.log_every == 1 else (now - t_log) / n_iter) * 1e3:6.1f} ms  {six}", flush=True)

@@ -826,8 +826,78 @@ int uavtrack_learner_grad_clipped(uavtrack_learner *learner, int64_t n,
                                   const float *log_mu, double clip_eps, float *ratio_out,
                                   float *td_delta, float *row, void *stream);
 
+/* ---- batch-normalised advantages for the per-sample losses (UAVTRACK_LOSS_PER_SAMPLE only; off by default) ----
+ * Without it the advantage that multiplies grad log p is the raw TD error delta_i.  This setting standardises it,
+ *   A_i = fl( fl(delta_i - mean32) * inv32 )        two fp32 operations, each rounded to nearest on its own,
+ * with (mean32, inv32) the mean and the reciprocal standard deviation of the batch's own delta (UAVTRACK_ADVANTAGE_BATCH)
+ * or a pair the caller keeps in device memory (UAVTRACK_ADVANTAGE_GIVEN).  A_i replaces delta_i wherever delta_i is the
+ * actor's ADVANTAGE: the logit weight, the actor-loss term -log p_i A_i, and under the clipped surrogate the gate
+ * (pass_i = A_i >= 0 ? r_i <= hi : r_i >= lo), r_i A_i and surr_i.  Everything else keeps the raw delta_i: the critic's
+ * value weight and loss, td_delta, loss word [P+1] (sum w delta) and the priorities.  Importance weights and truncated
+ * ratios multiply afterwards, as before (the statistics are unweighted, over the rows of the batch); the entropy term is
+ * additive and unchanged.  A gradient row keeps its P + 8 words and its tag; normalised and raw rows may meet in one
+ * apply.  Rows carry no settings, and every row is standardised by the statistics of ITS OWN batch: a split update is K
+ * independently standardised draws (as each draw's importance weights are normalised by its own maximum), and its
+ * participants must hold equal settings.  The setting acts on every update and grad entry point (plain, _weighted,
+ * _discounted, _clipped), whose signatures are unchanged.  With the mode RAW every call enqueues exactly what it enqueued
+ * before, with the same arguments.
+ *
+ * UAVTRACK_ADVANTAGE_BATCH, for a batch of n >= 2 rows, three steps ahead of the gradient kernel on the same stream:
+ *  1. TD pass.  delta_i = (r_i + d_i V'(s'_i)) - V(s_i) of every row into library scratch: V' the target critic while one
+ *     is enabled, d_i the discount store's or (float)gamma; the chains of uavtrack_learner_values and the target as one
+ *     multiply and one add, each rounded on its own.  These are the bits the gradient kernel forms for the row (and
+ *     leaves in td_delta).  A row whose index is out of range counts as 0 (the update is refused anyway).
+ *  2. Statistics in fp64 from the fp32 delta_i, in a fixed order that does not depend on the launch geometry: rows in
+ *     chunks of 256 consecutive rows (chunk c = rows [256 c, 256 c + 256), the last chunk padded with zeros that are not
+ *     counted in n); inside a chunk the halving tree x[k] += x[k + h] for h = 128, 64 .. 1 (k < h) over the 256 terms in
+ *     row order; the chunk sums added in ascending chunk order, starting from 0.
+ *       S = sum delta_i,  mean64 = S / n;   Q = sum (delta_i - mean64)^2, the difference, the product and the adds as
+ *       separate fp64 operations;   std64 = sqrt(Q / (n - 1))  (the unbiased form of torch.Tensor.std());
+ *       inv64 = 1 / (std64 + eps),  eps a double, 1e-8 by default.
+ *     stats = {(float)mean64, (float)inv64, (float)std64}: three floats of DEVICE memory, the handle's own or a buffer
+ *     the caller installed (uavtrack_learner_set_advantage_stats), written by every batch-mode update or grad.
+ *  3. The gradient kernel reads mean32 = stats[0], inv32 = stats[1] and forms A_i as above.
+ * Every delta_i equal gives std64 = 0, inv32 = (float)(1 / eps) and A_i = 0 exactly: the actor does not move.
+ * The scratch (n floats and two doubles per chunk) is allocated when the mode BATCH is first set, at the reserved batch
+ * size, and grown by uavtrack_learner_reserve; no update, grad or apply allocates or synchronises, and all of them stay
+ * capturable.  Batch mode adds four small launches to an update or grad (TD pass, squares, statistics, and one behind the
+ * gradient kernel that turns stats into NaN where the call was refused).
+ *
+ * UAVTRACK_ADVANTAGE_GIVEN: no TD pass; the gradient kernel reads {mean32, inv32} from `given`, a caller-owned DEVICE
+ * fp32 [2] that is not copied and is read when the launch executes (like the entropy buffer): running statistics, or
+ * statistics a caller has reduced over shards or ranks.  {0.0f, 1.0f} leaves every bit of the RAW update of a learner
+ * whose entropy diagnostics are installed or entropy_coef != 0 (x - 0 and x * 1 are exact; the kernel is the regularised
+ * body), and the parameters, moments, losses, td_delta and priorities of any RAW update.
+ *
+ * Refusals.  On the host, enqueuing nothing: (set) an unknown mode, eps NaN or negative, GIVEN with given == NULL, a mode
+ * other than RAW on a UAVTRACK_LOSS_REFERENCE learner -- that form scales the actor's gradient sums once by the global
+ * -mean(delta) / N, and a standardised advantage has mean 0; (update / grad) n < 2 in BATCH mode.  On the device, like a
+ * bad action: a mean32 that is not finite or an inv32 that is NaN, infinite or negative sets status bit 6 (value 64) in
+ * the status word and in word P + 6 of a row; the update or apply changes nothing, its losses are NaN and the next
+ * uavtrack_learner_check counts it.  (In BATCH mode that is a batch whose delta is not finite.)  An update refused on the
+ * device for any reason behaves as before and leaves NaN in all three stats words.
+ * Not part of checkpoints, and not carried by sharding's learner state, like the regularisation settings.
+ * Cost on one MI355X: DESIGN.md section 9. */
+enum uavtrack_advantage_mode {
+    UAVTRACK_ADVANTAGE_RAW   = 0,   /* A_i = delta_i (the default) */
+    UAVTRACK_ADVANTAGE_BATCH = 1,   /* standardised by the batch's own mean and standard deviation */
+    UAVTRACK_ADVANTAGE_GIVEN = 2    /* standardised by the caller's {mean, inv_std} in device memory */
+};
+
+/* Host-side settings, read when a later update / grad is ENQUEUED (a captured graph keeps what it was captured with).
+ * eps is read in BATCH mode, given in GIVEN mode (ignored otherwise; eps must still be >= 0).  The first BATCH allocates
+ * the TD scratch (not for use inside a capture).  A refused call changes nothing. */
+int uavtrack_learner_set_advantage(uavtrack_learner *learner, int32_t mode, double eps, const float *given);
+/* mode, eps and given as they were last set ({RAW, 1e-8, NULL} at create). */
+int uavtrack_learner_get_advantage(uavtrack_learner *learner, int32_t *mode, double *eps, const float **given);
+/* Where BATCH mode leaves {mean, inv_std, std}: a caller-owned DEVICE fp32 [3] (not copied, in the style of
+ * uavtrack_learner_set_diagnostics; it must outlive the updates enqueued while it is installed), or NULL for three
+ * floats inside the handle, the default.  Host-side, read at enqueue; the gradient kernel reads the pair from there. */
+int uavtrack_learner_set_advantage_stats(uavtrack_learner *learner, float *stats);
+
 /* Synchronises `stream`; fails if any update or apply since the previous check was refused on the device (bad action,
- * index, importance weight, discount, behaviour log-probability or ratio, or a row of another layout).  refused (nullable) receives their number; the count restarts at 0. */
+ * index, importance weight, discount, behaviour log-probability or ratio, a bad given advantage pair, or a row of another
+ * layout).  refused (nullable) receives their number; the count restarts at 0. */
 int uavtrack_learner_check(uavtrack_learner *learner, int64_t *refused, void *stream);
 
 /* ---- the PMI trainer: PMINetwork.train_pmi + its Adam steps on the device ----

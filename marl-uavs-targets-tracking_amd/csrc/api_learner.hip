@@ -18,13 +18,24 @@ struct uavtrack_learner {
 
 namespace uavtrack {
 
-static Bufs scratch_bufs(LearnerDevice &d, int64_t max_n) { return {buf(d.td, max_n), buf(d.last, max_n)}; }
+// the TD pass of a batch-normalised advantage: not part of a handle until a mode other than raw is first set
+static Bufs advantage_bufs(LearnerDevice &d, int64_t max_n)
+{
+    return {buf(d.adv_td, max_n), buf(d.adv_part, 2 * (size_t)learner_adv_chunks(max_n))};
+}
+
+static Bufs scratch_bufs(LearnerDevice &d, int64_t max_n)
+{
+    Bufs set = {buf(d.td, max_n), buf(d.last, max_n)};
+    return d.adv_td ? set + advantage_bufs(d, max_n) : set;
+}
 
 static Bufs device_bufs(LearnerDevice &d)
 {
     const size_t P = (size_t)d.L.P;
     return adam_bufs(d.opt) + Bufs{buf(d.params, P, true), buf(d.gstatus, 1, true), buf(d.partials, kLearnerMaxGroups * (P + 4)), buf(d.scal, 2),
-                                   buf(d.gsum, P), buf(d.sq, 2 * (size_t)learner_clip_groups(d.L)), buf(d.coef, 2)} +
+                                   buf(d.gsum, P), buf(d.sq, 2 * (size_t)learner_clip_groups(d.L)), buf(d.coef, 2),
+                                   buf(d.adv_stats, 3, true)} +
            scratch_bufs(d, d.max_n);
 }
 
@@ -61,6 +72,15 @@ int accept_entropy_rows(const char *fn, const uavtrack_learner *l, int64_t n)
     if (l->d.entropy && n > l->d.entropy_rows)
         return fail("%s: n = %lld rows, the installed entropy buffer holds %lld (uavtrack_learner_set_diagnostics)", fn,
                     (long long)n, (long long)l->d.entropy_rows);
+    return 0;
+}
+
+// uavtrack_learner_update / _grad under a batch-normalised advantage: a standard deviation needs two rows
+int accept_advantage_rows(const char *fn, const uavtrack_learner *l, int64_t n)
+{
+    if (l->d.adv_mode == UAVTRACK_ADVANTAGE_BATCH && n < 2)
+        return fail("%s: n = %lld row under UAVTRACK_ADVANTAGE_BATCH: the standard deviation of a batch needs n >= 2 "
+                    "(uavtrack_learner_set_advantage)", fn, (long long)n);
     return 0;
 }
 
@@ -119,6 +139,7 @@ int uavtrack_learner_create(const uavtrack_learner_config *cfg, uavtrack_learner
         d.opt.P = d.L.P;
         d.max_n = c.max_batch ? c.max_batch : kLearnerDefaultBatch;
         d.max_norm[0] = d.max_norm[1] = INFINITY;       // regularisation off: entropy_coef 0, no diagnostics
+        d.adv_eps = 1e-8;                               // the advantage raw
         return learner_prepare_kernels(d.L);
     };
     return create_handle(__func__, cfg, out, check, init);
@@ -131,7 +152,7 @@ int uavtrack_learner_destroy(uavtrack_learner *learner)
         (void)hipDeviceSynchronize();
         release(target_bufs(learner->d));
     }
-    return destroy_handle(learner);
+    return destroy_handle(learner);                 // (the TD pass's scratch is in scratch_bufs() once it exists)
 }
 
 int uavtrack_learner_num_params(uavtrack_learner *learner, int64_t *out)
@@ -253,7 +274,9 @@ int learner_update(const char *fn, uavtrack_learner *learner, int64_t n, const f
     if (!states || !actions || !rewards || !next_states)
         return fail("%s: states, actions, rewards and next_states must not be null", fn);
     if (!actor_loss || !critic_loss) return fail("%s: actor_loss and critic_loss must not be null", fn);
-    if (accept_batch(fn, learner, n, capacity, indices, "from") || accept_entropy_rows(fn, learner, n)) return 1;
+    if (accept_batch(fn, learner, n, capacity, indices, "from") || accept_entropy_rows(fn, learner, n) ||
+        accept_advantage_rows(fn, learner, n))
+        return 1;
     ON_DEVICE(learner->cfg.device_id);
     LearnerLaunch q = learner_batch(n, states, actions, rewards, next_states, capacity, indices, weights, discounts, td_delta);
     q.actor_loss = actor_loss; q.critic_loss = critic_loss; q.priorities = priorities;
@@ -272,7 +295,9 @@ int learner_grad(const char *fn, uavtrack_learner *learner, int64_t n, const flo
     if (!states || !actions || !rewards || !next_states)
         return fail("%s: states, actions, rewards and next_states must not be null", fn);
     if (!td_delta || !row) return fail("%s: td_delta and row must not be null", fn);
-    if (accept_batch(fn, learner, n, capacity, indices, "from") || accept_entropy_rows(fn, learner, n)) return 1;
+    if (accept_batch(fn, learner, n, capacity, indices, "from") || accept_entropy_rows(fn, learner, n) ||
+        accept_advantage_rows(fn, learner, n))
+        return 1;
     ON_DEVICE(learner->cfg.device_id);
     LearnerLaunch q = learner_batch(n, states, actions, rewards, next_states, capacity, indices, weights, discounts, td_delta);
     if (clip && accept_clip(fn, learner, clip->log_mu, clip->clip_eps, clip->ratio_out, q)) return 1;
@@ -398,6 +423,48 @@ int uavtrack_learner_values(uavtrack_learner *learner, int64_t n, const float *r
     if (((uintptr_t)rows & 15) != 0) return fail("%s: rows must be 16-byte aligned", __func__);
     ON_DEVICE(learner->cfg.device_id);
     HIP_TRY(launch_learner_values(learner->d, false, n, rows, values, static_cast<hipStream_t>(stream)));
+    return 0;
+}
+
+// ---- the normalised advantage
+
+int uavtrack_learner_set_advantage(uavtrack_learner *learner, int32_t mode, double eps, const float *given)
+{
+    static_assert(UAVTRACK_ADVANTAGE_RAW == kAdvantageRaw && UAVTRACK_ADVANTAGE_BATCH == kAdvantageBatch &&
+                  UAVTRACK_ADVANTAGE_GIVEN == kAdvantageGiven, "learner.h restates enum uavtrack_advantage_mode");
+    if (!learner) return fail("%s: null handle", __func__);
+    if (mode != UAVTRACK_ADVANTAGE_RAW && mode != UAVTRACK_ADVANTAGE_BATCH && mode != UAVTRACK_ADVANTAGE_GIVEN)
+        return fail("%s: unknown mode %d", __func__, mode);
+    if (!(eps >= 0)) return fail("%s: eps = %g must be >= 0", __func__, eps);
+    if (mode == UAVTRACK_ADVANTAGE_GIVEN && !given)
+        return fail("%s: UAVTRACK_ADVANTAGE_GIVEN needs the {mean, inv_std} pair: given must not be null", __func__);
+    LearnerDevice &d = learner->d;
+    if (mode != UAVTRACK_ADVANTAGE_RAW && !d.per_sample)
+        return fail("%s: a normalised advantage on a UAVTRACK_LOSS_REFERENCE learner: that form scales the actor's gradient "
+                    "sums once by -mean(delta) / N, and a standardised advantage has mean 0; use UAVTRACK_LOSS_PER_SAMPLE",
+                    __func__);
+    if (mode == UAVTRACK_ADVANTAGE_BATCH && !d.adv_td) {
+        // the TD pass's scratch, once per handle at the reserved size (uavtrack_learner_reserve grows it with the rest)
+        ON_DEVICE(learner->cfg.device_id);
+        HIP_TRY(replace(advantage_bufs(d, d.max_n)));
+    }
+    d.adv_mode = mode;
+    d.adv_eps = eps;
+    d.adv_given = mode == UAVTRACK_ADVANTAGE_GIVEN ? given : nullptr;
+    return 0;
+}
+
+int uavtrack_learner_get_advantage(uavtrack_learner *learner, int32_t *mode, double *eps, const float **given)
+{
+    if (!learner || !mode || !eps || !given) return fail("%s: null argument", __func__);
+    *mode = learner->d.adv_mode; *eps = learner->d.adv_eps; *given = learner->d.adv_given;
+    return 0;
+}
+
+int uavtrack_learner_set_advantage_stats(uavtrack_learner *learner, float *stats)
+{
+    if (!learner) return fail("%s: null handle", __func__);
+    learner->d.adv_user = stats;
     return 0;
 }
 
@@ -580,8 +647,8 @@ int uavtrack_learner_check(uavtrack_learner *learner, int64_t *refused, void *st
         return fail("uavtrack_learner_check: %d update(s) refused: an action outside [0, %d), an index outside "
                     "[0, capacity), an importance weight that is NaN, infinite or negative, a discount that is NaN or "
                     "outside [0, 1], a behaviour log-probability that is NaN or positive or a ratio that is not finite "
-                    "(the clipped surrogate), or (uavtrack_learner_apply) a gradient row of another layout; they changed "
-                    "nothing",
+                    "(the clipped surrogate), a given advantage mean that is not finite or inv_std that is NaN, infinite or "
+                    "negative, or (uavtrack_learner_apply) a gradient row of another layout; they changed nothing",
                     count, learner->d.L.A);
     return 0;
 }

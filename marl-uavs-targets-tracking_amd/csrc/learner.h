@@ -69,7 +69,17 @@ struct LearnerDevice {
     int target_mode;                // UAVTRACK_TARGET_OFF / _POLYAK / _PERIODIC
     float target_tau, target_omt;   // Polyak: (float)tau and 1.0f - (float)tau
     int64_t target_period;          // periodic: >= 1; 0 while Polyak
+    // the normalised advantage (uavtrack_learner_set_advantage): host-side settings, read at enqueue
+    int adv_mode;                   // kAdvantageRaw / _Batch / _Given (= enum uavtrack_advantage_mode); != raw only with per_sample
+    double adv_eps;                 // batch: inv_std = 1 / (std + eps)
+    const float *adv_given;         // given: the caller's [2] {mean, inv_std} (not owned), read when the launch executes
+    float *adv_stats;               // [3] {mean, inv_std, std} of the last batch-mode update or grad ...
+    float *adv_user;                // ... unless the caller installed a [3] buffer of its own (not owned), else null
+    float *stats() const { return adv_user ? adv_user : adv_stats; }
+    float *adv_td;                  // [max_n] the TD pass's delta; null until a mode other than raw is first set
+    double *adv_part;               // [2][learner_adv_chunks(max_n)] the chunks' sums of delta, then of squared deviations
 };
+enum { kAdvantageRaw = 0, kAdvantageBatch = 1, kAdvantageGiven = 2 };
 struct LearnerLaunch {
     int64_t n, capacity;
     const float *states, *rewards, *next_states;
@@ -86,6 +96,7 @@ int learner_rows_per_tile(int hidden);
 size_t learner_lds_bytes(const LearnerLayout &L, int rows, bool clipped = false);   // clipped: R more floats, behind the rest
 int learner_groups(const LearnerLayout &L, int64_t n);
 int learner_clip_groups(const LearnerLayout &L);   // workgroups of the clip's gradient pass: ceil(P / 256)
+int64_t learner_adv_chunks(int64_t n);             // 256-row chunks of the advantage statistics: ceil(n / 256)
 inline int learner_critic_words(const LearnerLayout &L) { return 14 * L.H + 1; }   // the critic's block, c_w1 .. P
 hipError_t learner_prepare_kernels(const LearnerLayout &L);
 hipError_t launch_learner_update(const LearnerDevice &d, const LearnerLaunch &q, hipStream_t stream);

@@ -59,6 +59,15 @@
 // whose log_mu holds those bits trains with the bits of the per-sample row.  A drawn slot whose log_mu is NaN or > 0, or
 // whose r_i is not finite, sets status bit 4 (value 16) and is not used.
 //
+// Batch-normalised advantages (uavtrack_learner_set_advantage, per-sample form only, off by default): the advantage that
+// multiplies grad log p, gates the clip and enters the actor loss becomes A_i = fl(fl(delta_i - mean) * inv_std), mean and
+// inv_std read from three floats of device memory; the critic, td_delta, loss word 1 and the priorities keep delta_i.
+// learner_grad_adv_kernel and its three siblings are the same body with that line (kAdv), over an argument struct of
+// their own; the other six keep their arguments and their code.  In batch mode three small kernels run in front:
+// learner_td_kernel forms delta_i of every row by the gradient kernel's own chains (the bits it will form) and each
+// 256-row chunk's fp64 sum, learner_adv_sq_kernel each chunk's sum of squared deviations, learner_adv_stats_kernel the
+// three floats; learner_adv_seal_kernel, behind the gradient kernel, turns them into NaN where the update was refused.
+//
 // The critic alone (uavtrack_learner_values): learner_values_kernel, at the end of the kernels below, evaluates V(x) of
 // any number of rows by the chain of the layer-1 and layer-2 loops above, to the bit, and touches no learner state.
 
@@ -108,13 +117,22 @@ struct GradClipArgs : GradArgs {
     float *ratio;                   // nullable [n]: r_i of batch row i, NaN for a row that set a status bit
 };
 
+// what the four kernels of a normalised advantage take on top (learner_grad_adv_kernel and its siblings)
+struct GradAdvArgs : GradClipArgs {
+    const float *stats;             // [2] {mean, inv_std}, read when the launch executes; status bit 6 (value 64): a mean
+                                    // that is not finite, or an inv_std that is NaN, infinite or negative
+};
+
 // kReg: the entropy term and the entropy[] store in the per-row block; everything else is one text.
 // kTgt: V(s') from the separate critic block a.target (the target critic) instead of the online critic; without it
 // W1t / b1t / W2t / b2t are the online critic's pointers at compile time.
 // kClip (with kReg): the clipped surrogate's gate on the row's policy gradient, log_mu gathered into lm, the ratio[] store.
-template <bool kReg, bool kTgt = false, bool kClip = false>
-__device__ __forceinline__ void learner_grad_body(const std::conditional_t<kClip, GradClipArgs, GradArgs> &a)
+// kAdv (with kReg): the row's advantage is fl(fl(delta - mean) * inv_std) wherever the actor uses one.
+template <bool kReg, bool kTgt = false, bool kClip = false, bool kAdv = false>
+__device__ __forceinline__ void learner_grad_body(
+    const std::conditional_t<kAdv, GradAdvArgs, std::conditional_t<kClip, GradClipArgs, GradArgs>> &a)
 {
+    static_assert(kReg || !kAdv, "the normalised advantage lives in the kReg block");
     extern __shared__ float lds[];
     const LearnerLayout &L = a.L;
     const int H = L.H, A = L.A, R = a.rows, P = L.P;
@@ -138,6 +156,13 @@ __device__ __forceinline__ void learner_grad_body(const std::conditional_t<kClip
     const float *W1c = a.params + L.c_w1, *b1c = a.params + L.c_b1, *W2c = a.params + L.c_w2, *b2c = a.params + L.c_b2;
     const float *W1t = kTgt ? a.target : W1c, *b1t = kTgt ? a.target + 12 * H : b1c;
     const float *W2t = kTgt ? a.target + 13 * H : W2c, *b2t = kTgt ? a.target + 14 * H : b2c;
+
+    float adv_mean = 0.0f, adv_inv = 1.0f;
+    bool adv_bad = false;
+    if constexpr (kAdv) {
+        adv_mean = a.stats[0]; adv_inv = a.stats[1];
+        adv_bad = !(fabsf(adv_mean) <= 3.402823466e+38f) || !(adv_inv >= 0.0f && adv_inv <= 3.402823466e+38f);
+    }
 
     for (int p = tid; p < P; p += kLW) acc[p] = 0.0f;
     float loss_run[4] = {0.0f, 0.0f, 0.0f, 0.0f};   // thread 0's running sums, tile after tile
@@ -172,6 +197,8 @@ __device__ __forceinline__ void learner_grad_body(const std::conditional_t<kClip
                     wi = a.weights[i];
                     if (!(wi >= 0.0f) || isinf(wi)) { atomicOr(a.status, 4); av = -1; }
                 }
+                if constexpr (kAdv)
+                    if (adv_bad) { atomicOr(a.status, 64); av = -1; }
                 for (int k = 0; k < 12; ++k) {
                     s[r * 12 + k]  = av >= 0 ? a.states[src * 12 + k] : 0.0f;
                     s2[r * 12 + k] = av >= 0 ? a.next_states[src * 12 + k] : 0.0f;
@@ -247,6 +274,8 @@ __device__ __forceinline__ void learner_grad_body(const std::conditional_t<kClip
                 const float target = rew + dc[r] * vn[r];
                 const float v = gv[r];
                 const float delta = target - v;
+                float adv = delta;                                  // the actor's advantage; delta stays the critic's
+                if constexpr (kAdv) adv = __fmul_rn(__fsub_rn(delta, adv_mean), adv_inv);
                 const float wi = wt[r];
                 const float c = a.entropy_coef;
                 float nlp, al;
@@ -262,9 +291,9 @@ __device__ __forceinline__ void learner_grad_body(const std::conditional_t<kClip
                         if (a.ratio) a.ratio[row0 + r] = NAN;
                         continue;
                     }
-                    const bool pass = delta >= 0.0f ? ratio <= a.clip_hi : ratio >= a.clip_lo;
-                    const float dr = pass ? delta * ratio : 0.0f;   // ratio == 1: delta's bits
-                    const float surr = pass ? dr : (delta >= 0.0f ? a.clip_hi : a.clip_lo) * delta;
+                    const bool pass = adv >= 0.0f ? ratio <= a.clip_hi : ratio >= a.clip_lo;
+                    const float dr = pass ? adv * ratio : 0.0f;     // ratio == 1: the advantage's bits
+                    const float surr = pass ? dr : (adv >= 0.0f ? a.clip_hi : a.clip_lo) * adv;
                     if (c != 0.0f) {                                // launch-uniform
                         for (int o = 0; o < A; ++o) {
                             const float d = z[o], e = expf(d), p = e * inv;
@@ -283,14 +312,14 @@ __device__ __forceinline__ void learner_grad_body(const std::conditional_t<kClip
                     for (int o = 0; o < A; ++o) {
                         const float d = z[o], e = expf(d), p = e * inv;
                         const float ge = e > 0.0f ? p * ((d - lse) + ent) : 0.0f;
-                        z[o] = wi * (delta * ((o == av ? 1.0f : 0.0f) - p) - c * ge);
+                        z[o] = wi * (adv * ((o == av ? 1.0f : 0.0f) - p) - c * ge);
                     }
-                    al = wi * (nlp * delta - c * ent);
+                    al = wi * (nlp * adv - c * ent);
                 } else {                                            // today's values, to the bit
                     nlp = -logf(expf(z[av]) * inv);
-                    const float w = (a.per_sample ? delta : 1.0f) * wi;
+                    const float w = (a.per_sample ? adv : 1.0f) * wi;
                     for (int o = 0; o < A; ++o) z[o] = w * ((o == av ? 1.0f : 0.0f) - expf(z[o]) * inv);
-                    al = (nlp * delta) * wi;
+                    al = (nlp * adv) * wi;
                 }
                 gv[r] = (v - target) * wi;
                 lt[r * 4 + 0] = nlp * wi;
@@ -393,6 +422,12 @@ __global__ void __launch_bounds__(kLW) learner_grad_reg_target_kernel(GradArgs a
 __global__ void __launch_bounds__(kLW) learner_grad_clip_kernel(GradClipArgs a) { learner_grad_body<true, false, true>(a); }
 __global__ void __launch_bounds__(kLW) learner_grad_clip_target_kernel(GradClipArgs a) { learner_grad_body<true, true, true>(a); }
 
+// the normalised advantage (uavtrack_learner_set_advantage), without and with the clipped surrogate and a target critic
+__global__ void __launch_bounds__(kLW) learner_grad_adv_kernel(GradAdvArgs a) { learner_grad_body<true, false, false, true>(a); }
+__global__ void __launch_bounds__(kLW) learner_grad_adv_target_kernel(GradAdvArgs a) { learner_grad_body<true, true, false, true>(a); }
+__global__ void __launch_bounds__(kLW) learner_grad_adv_clip_kernel(GradAdvArgs a) { learner_grad_body<true, false, true, true>(a); }
+__global__ void __launch_bounds__(kLW) learner_grad_adv_clip_target_kernel(GradAdvArgs a) { learner_grad_body<true, true, true, true>(a); }
+
 // Clears the update's status word (a kernel node rather than a memset node, so a captured update is a chain of kernels)
 __global__ void learner_begin_kernel(int *status)
 {
@@ -425,7 +460,7 @@ __global__ void learner_finalize_kernel(const float *src, int count, size_t stri
         if (n_given) continue;                                      // a workgroup partial ends here
         const int32_t *tail = reinterpret_cast<const int32_t *>(row) + P + 4;
         const int64_t nr = (int64_t)((uint64_t)(uint32_t)tail[0] | ((uint64_t)(uint32_t)tail[1] << 32));
-        bad |= tail[2] & 31;
+        bad |= tail[2] & (31 | 64);
         if (tail[3] != P || nr < 1) bad |= 32;                      // a row of another layout (or not a row at all)
         else N += nr;
     }
@@ -650,7 +685,150 @@ __global__ void __launch_bounds__(kVW) learner_values_kernel(const float *critic
     }
 }
 
+// ---- batch-normalised advantages (uavtrack_learner_set_advantage, UAVTRACK_ADVANTAGE_BATCH): delta of every row and its
+// mean and standard deviation, ahead of the gradient kernel.  Rows are taken in chunks of kAdvChunk = 256 consecutive rows
+// (chunk c is rows [256 c, 256 c + 256) whatever the grid is; rows past n count as 0.0 and are not counted in n).  A chunk's
+// 256 fp64 terms are added by the fixed halving tree x[k] += x[k + h], h = 128 .. 1, and the chunk sums in ascending chunk
+// order by one thread, so no sum depends on the launch geometry.
+
+constexpr int kAdvChunk = 256;    // rows per chunk = threads per workgroup of the two kernels below
+
+struct TdArgs {
+    const float *critic;            // [14 H + 1] the online critic's block: V(s)
+    const float *target;            // [14 H + 1] the block V(s') is formed from (the same pointer while no target critic is on)
+    const float *states, *rewards, *next_states;
+    const int64_t *idx;             // nullable: rows 0..n-1
+    const float *discounts;         // nullable [capacity], slot order
+    int64_t n, capacity;
+    int H;
+    float gamma;
+    float *td;                      // [n] delta_i, 0 for a row whose index is out of range (the gradient kernel refuses it)
+    double *psum;                   // [chunks] the chunks' sums of delta
+};
+
+__device__ __forceinline__ double chunk_tree(double *part, int tid, double x)
+{
+    part[tid] = x;
+    __syncthreads();
+    for (int h = kAdvChunk / 2; h > 0; h >>= 1) {
+        if (tid < h) part[tid] += part[tid + h];
+        __syncthreads();
+    }
+    const double s = part[0];
+    __syncthreads();
+    return s;
+}
+
+// delta_i = (r_i + d_i V'(s'_i)) - V(s_i), one lane per row: the layer-1 and layer-2 chains of the gradient kernel
+// (explicit fmaf in k and j order, as learner_values_kernel has them) and the target as one multiply and one add, each
+// rounded on its own, so td[i] holds the bits the gradient kernel forms for the row.  Both critic blocks wait in LDS as
+// learner_values_kernel's records.
+__global__ void __launch_bounds__(kAdvChunk) learner_td_kernel(TdArgs a)
+{
+    __shared__ __attribute__((aligned(16))) float rec[2][kLearnerMaxHidden * kVRec];
+    __shared__ double part[kAdvChunk];
+    const int tid = threadIdx.x, H = a.H;
+    for (int b = 0; b < 2; ++b) {
+        const float *blk = b ? a.target : a.critic;
+        for (int e = tid; e < H * kVRec; e += kAdvChunk) {
+            const int j = e / kVRec, k = e - j * kVRec;
+            rec[b][e] = k < 12 ? blk[j * 12 + k] : (k == 12 ? blk[12 * H + j] : (k == 13 ? blk[13 * H + j] : 0.0f));
+        }
+    }
+    const float b2 = a.critic[14 * H], b2t = a.target[14 * H];
+    __syncthreads();
+    const int64_t chunks = (a.n + kAdvChunk - 1) / kAdvChunk;
+    for (int64_t c = blockIdx.x; c < chunks; c += gridDim.x) {
+        const int64_t i = c * kAdvChunk + tid;
+        float delta = 0.0f;
+        if (i < a.n) {
+            const int64_t src = a.idx ? a.idx[i] : i;
+            if (src >= 0 && src < a.capacity) {
+                float x[12], y[12];
+#pragma unroll
+                for (int k = 0; k < 12; ++k) { x[k] = a.states[src * 12 + k]; y[k] = a.next_states[src * 12 + k]; }
+                float v = b2, vn = b2t;
+                for (int j = 0; j < H; ++j) {
+                    const float4 *r = reinterpret_cast<const float4 *>(rec[0] + j * kVRec);
+                    const float4 *t = reinterpret_cast<const float4 *>(rec[1] + j * kVRec);
+                    const float4 wa = r[0], wb = r[1], wc = r[2], wd = r[3];
+                    const float4 ta = t[0], tb = t[1], tc = t[2], tdl = t[3];
+                    const float w[12] = {wa.x, wa.y, wa.z, wa.w, wb.x, wb.y, wb.z, wb.w, wc.x, wc.y, wc.z, wc.w};
+                    const float u[12] = {ta.x, ta.y, ta.z, ta.w, tb.x, tb.y, tb.z, tb.w, tc.x, tc.y, tc.z, tc.w};
+                    float p = wd.x, q = tdl.x;
+#pragma unroll
+                    for (int k = 0; k < 12; ++k) {
+                        p = fmaf(w[k], x[k], p);
+                        q = fmaf(u[k], y[k], q);
+                    }
+                    v = fmaf(wd.y, fmaxf(p, 0.0f), v);
+                    vn = fmaf(tdl.y, fmaxf(q, 0.0f), vn);
+                }
+                const float d = a.discounts ? a.discounts[src] : a.gamma;
+                const float target = __fadd_rn(a.rewards[src], __fmul_rn(d, vn));
+                delta = __fsub_rn(target, v);
+            }
+            a.td[i] = delta;
+        }
+        const double s = chunk_tree(part, tid, (double)delta);
+        if (tid == 0) a.psum[c] = s;
+    }
+}
+
+// the chunk sums in ascending chunk order
+__device__ __forceinline__ double ordered_sum64(const double *src, int64_t count)
+{
+    double s = 0.0;
+    for (int64_t c = 0; c < count; ++c) s += src[c];
+    return s;
+}
+
+// Q's chunk sums: (delta_i - mean64)^2 with the difference, the product and the adds as separate fp64 operations;
+// mean64 = S / n, S formed by thread 0 of every workgroup in the one order
+__global__ void __launch_bounds__(kAdvChunk) learner_adv_sq_kernel(const float *td, int64_t n, const double *psum, double *psq)
+{
+    __shared__ double part[kAdvChunk];
+    __shared__ double mean_s;
+    const int tid = threadIdx.x;
+    const int64_t chunks = (n + kAdvChunk - 1) / kAdvChunk;
+    if (tid == 0) mean_s = __ddiv_rn(ordered_sum64(psum, chunks), (double)n);
+    __syncthreads();
+    const double mean = mean_s;
+    for (int64_t c = blockIdx.x; c < chunks; c += gridDim.x) {
+        const int64_t i = c * kAdvChunk + tid;
+        double q = 0.0;
+        if (i < n) {
+            const double d = __dsub_rn((double)td[i], mean);
+            q = __dmul_rn(d, d);
+        }
+        const double s = chunk_tree(part, tid, q);
+        if (tid == 0) psq[c] = s;
+    }
+}
+
+// One thread: stats = {(float)mean64, (float)inv64, (float)std64}, std64 = sqrt(Q / (n - 1)) (the unbiased form, n >= 2),
+// inv64 = 1 / (std64 + eps)
+__global__ void learner_adv_stats_kernel(const double *psum, const double *psq, int64_t n, double eps, float *stats)
+{
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    const int64_t chunks = (n + kAdvChunk - 1) / kAdvChunk;
+    const double mean = __ddiv_rn(ordered_sum64(psum, chunks), (double)n);
+    const double var = __ddiv_rn(ordered_sum64(psq, chunks), (double)(n - 1));
+    const double sd = __dsqrt_rn(var);
+    const double inv = __ddiv_rn(1.0, __dadd_rn(sd, eps));
+    stats[0] = (float)mean; stats[1] = (float)inv; stats[2] = (float)sd;
+}
+
+// behind the gradient kernel: the statistics of a refused update are NaN
+__global__ void learner_adv_seal_kernel(const int *status, float *stats)
+{
+    if (threadIdx.x != 0 || blockIdx.x != 0 || !*status) return;
+    stats[0] = NAN; stats[1] = NAN; stats[2] = NAN;
+}
+
 }  // namespace
+
+int64_t learner_adv_chunks(int64_t n) { return (n + kAdvChunk - 1) / kAdvChunk; }
 
 hipError_t launch_learner_values(const LearnerDevice &d, bool target, int64_t n, const float *rows, float *values,
                                  hipStream_t st)
@@ -702,6 +880,17 @@ hipError_t learner_prepare_kernels(const LearnerLayout &L)
         const hipError_t e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)clds);
         if (e != hipSuccess) return e;
     }
+    // the normalised advantage's four: what their siblings ask for
+    for (const void *k : {reinterpret_cast<const void *>(learner_grad_adv_kernel),
+                          reinterpret_cast<const void *>(learner_grad_adv_target_kernel)}) {
+        const hipError_t e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (e != hipSuccess) return e;
+    }
+    for (const void *k : {reinterpret_cast<const void *>(learner_grad_adv_clip_kernel),
+                          reinterpret_cast<const void *>(learner_grad_adv_clip_target_kernel)}) {
+        const hipError_t e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)clds);
+        if (e != hipSuccess) return e;
+    }
     return hipSuccess;
 }
 
@@ -728,6 +917,35 @@ hipError_t launch_grad(const LearnerDevice &d, const LearnerLaunch &q, float *td
     auto *kernel = a.target ? (reg ? learner_grad_reg_target_kernel : learner_grad_target_kernel)
                             : (reg ? learner_grad_reg_kernel : learner_grad_kernel);
     const dim3 grid(learner_groups(L, q.n));
+    if (d.adv_mode != kAdvantageRaw) {
+        // the normalised advantage: in batch mode the TD pass and the statistics first, the seal behind
+        const bool batch = d.adv_mode == kAdvantageBatch;
+        GradAdvArgs v;
+        static_cast<GradClipArgs &>(v) = a;
+        v.stats = batch ? d.stats() : d.adv_given;
+        if (batch) {
+            const int64_t chunks = learner_adv_chunks(q.n);
+            const dim3 cgrid((unsigned)(chunks < 1024 ? chunks : 1024));
+            double *psum = d.adv_part, *psq = d.adv_part + learner_adv_chunks(d.max_n);
+            TdArgs t;
+            t.critic = d.params + L.c_w1; t.target = a.target ? a.target : t.critic;
+            t.states = q.states; t.rewards = q.rewards; t.next_states = q.next_states; t.idx = q.idx;
+            t.discounts = q.discounts; t.n = q.n; t.capacity = q.capacity; t.H = L.H; t.gamma = d.gamma;
+            t.td = d.adv_td; t.psum = psum;
+            hipLaunchKernelGGL(learner_td_kernel, cgrid, dim3(kAdvChunk), 0, st, t);
+            if ((e = hipGetLastError()) != hipSuccess) return e;
+            hipLaunchKernelGGL(learner_adv_sq_kernel, cgrid, dim3(kAdvChunk), 0, st, d.adv_td, q.n, psum, psq);
+            if ((e = hipGetLastError()) != hipSuccess) return e;
+            hipLaunchKernelGGL(learner_adv_stats_kernel, dim3(1), dim3(64), 0, st, psum, psq, q.n, d.adv_eps, d.stats());
+            if ((e = hipGetLastError()) != hipSuccess) return e;
+        }
+        auto *adv = clipped ? (a.target ? learner_grad_adv_clip_target_kernel : learner_grad_adv_clip_kernel)
+                            : (a.target ? learner_grad_adv_target_kernel : learner_grad_adv_kernel);
+        hipLaunchKernelGGL(adv, grid, dim3(kLW), learner_lds_bytes(L, R, clipped), st, v);
+        if ((e = hipGetLastError()) != hipSuccess || !batch) return e;
+        hipLaunchKernelGGL(learner_adv_seal_kernel, dim3(1), dim3(64), 0, st, status, d.stats());
+        return hipGetLastError();
+    }
     if (clipped) {
         hipLaunchKernelGGL(a.target ? learner_grad_clip_target_kernel : learner_grad_clip_kernel, grid, dim3(kLW),
                            learner_lds_bytes(L, R, true), st, a);

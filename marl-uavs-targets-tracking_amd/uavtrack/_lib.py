@@ -109,6 +109,7 @@ PMI_MAX_SOURCES = 64                                      # UAVTRACK_PMI_MAX_SOU
 PMI_BN_LAYERS = 4                                         # BatchNorm1d layers (num_batches_tracked entries)
 LOSS_FORMS = ("reference", "per_sample")                  # enum uavtrack_actor_loss
 TARGET_OFF, TARGET_POLYAK, TARGET_PERIODIC = 0, 1, 2       # enum uavtrack_target_mode
+ADVANTAGE_RAW, ADVANTAGE_BATCH, ADVANTAGE_GIVEN = 0, 1, 2   # enum uavtrack_advantage_mode
 LEARNER_ROW_TAIL = 8                                     # words behind the P gradient sums of a gradient row
 LEARNER_MAX_ROWS = 64                                     # UAVTRACK_LEARNER_MAX_ROWS
 REPLAY_MAX_NSTEP = 64                                     # UAVTRACK_REPLAY_MAX_NSTEP
@@ -202,6 +203,10 @@ SIGNATURES = {
     "uavtrack_learner_set_regularisation": (C.c_int, [C.c_void_p, C.c_double, C.c_double, C.c_double]),
     "uavtrack_learner_get_regularisation": (C.c_int, [C.c_void_p, C.POINTER(C.c_double)]),
     "uavtrack_learner_set_diagnostics": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
+    "uavtrack_learner_set_advantage": (C.c_int, [C.c_void_p, C.c_int32, C.c_double, C.c_void_p]),
+    "uavtrack_learner_get_advantage": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_double),
+                                                 C.POINTER(C.c_void_p)]),
+    "uavtrack_learner_set_advantage_stats": (C.c_int, [C.c_void_p, C.c_void_p]),
     "uavtrack_pmi_trainer_create": (C.c_int, [C.POINTER(PmiTrainerConfig), C.POINTER(C.c_void_p)]),
     "uavtrack_pmi_trainer_destroy": (C.c_int, [C.c_void_p]),
     "uavtrack_pmi_trainer_num_params": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),

@@ -75,6 +75,15 @@ whenever the critic's device step count is a multiple of period; a refused updat
 from it and apply runs the sync rule; gradient rows carry no settings, so learners that share an update must hold equal
 settings and theta- (sharding.pack_learner_state / unpack_learner_state carry both).  learner.target.values(states) is
 V of theta-; state_dict / save carry theta- and the settings while a target is enabled.
+
+Batch-normalised advantages (set_advantage("batch"), or a (mean, inv_std) device tensor; loss="per_sample" only; off by
+default, and then every call is bit for bit what it was and enqueues what it enqueued): the advantage of the actor's
+terms above becomes A_i = (delta_i - mean) / (std + eps) with the batch's own mean and unbiased standard deviation, found
+by a pass of its own ahead of the gradient kernel (float64 sums in a fixed order, include/uavtrack.h); it also chooses
+the side of the clip gate.  The critic, td_delta, the priorities and the entropy term are unchanged; importance weights
+and truncated ratios multiply afterwards.  Each gradient row of a split update is standardised by its own draw's
+statistics, as K independent learners would (the choice importance weights made: each draw is normalised by its own
+maximum); learner.advantage_stats holds (mean, inv_std, std) of the last batch.
 """
 from __future__ import annotations
 
@@ -272,6 +281,53 @@ class DeviceActorCritic(Handle):
         probe.load_state_dict(target_sd)                              # torch checks keys and shapes
         self._set_target_params(flat(list(probe.parameters())))
 
+    # ---- the normalised advantage
+    _advantage = "raw"                                                # "raw", "batch" or the installed [2] tensor
+    advantage_stats = None                                            # the [3] tensor, from the first "batch" on
+
+    def set_advantage(self, mode="raw", eps: float = 1e-8) -> None:
+        """What multiplies grad log p, gates the clip and enters the actor loss (loss="per_sample" only): "raw", the TD
+        error delta_i (the default); "batch", A_i = (delta_i - mean) / (std + eps) over the rows of each batch, formed in
+        the library ahead of the gradient kernel (uavtrack_learner_set_advantage; std is torch's unbiased one, so a batch
+        needs two rows); or a float32 [2] device tensor (mean, inv_std) that is read when an update runs, for running
+        statistics or ones reduced over shards or ranks.  The critic, td_delta and the priorities keep delta_i.  After
+        the first "batch", advantage_stats is the float32 [3] device tensor (mean, inv_std, std) of the last batch-mode
+        update or grad_from (NaN for a refused one).  A host-side setting like set_regularisation: it holds for every
+        update, update_from, grad_from, update_from_many and group update enqueued afterwards, a captured graph keeps
+        what it was captured with, each gradient row of a split update is standardised by its own draw's statistics,
+        and learners that share an update must hold equal settings (checkpoints and sharding.broadcast_learner do not
+        carry it).  The first "batch" allocates, so not inside a graph capture.  The reference loss, a bad eps or a
+        tensor of the wrong shape, dtype or device raise ValueError before any library call."""
+        if torch.is_tensor(mode):
+            if mode.shape != (2,) or mode.dtype != torch.float32 or mode.device != self.device or not mode.is_contiguous():
+                raise ValueError(f"set_advantage: a given (mean, inv_std) must be a contiguous float32 tensor [2] on "
+                                 f"{self.device}, got {tuple(mode.shape)} {mode.dtype} on {mode.device}")
+        elif mode not in ("raw", "batch"):
+            raise ValueError(f'set_advantage: mode must be "raw", "batch" or a float32 [2] device tensor, got {mode!r}')
+        e = float(eps)
+        if not e >= 0.0:                                              # NaN fails the comparison
+            raise ValueError(f"set_advantage: eps = {eps!r} must be >= 0")
+        if self.loss != "per_sample" and not (isinstance(mode, str) and mode == "raw"):
+            raise ValueError('set_advantage: a normalised advantage on a loss="reference" learner: that form scales the '
+                             "actor's gradient sums once by -mean(delta) / N, and a standardised advantage has mean 0; "
+                             'use loss="per_sample"')
+        given = mode if torch.is_tensor(mode) else None
+        if given is None and mode == "batch" and self.advantage_stats is None:
+            stats = torch.full((3,), float("nan"), device=self.device)
+            _lib.check(self._lib.uavtrack_learner_set_advantage_stats(self._h, _ptr(stats)),
+                       "uavtrack_learner_set_advantage_stats")
+            self.advantage_stats = stats
+        code = _lib.ADVANTAGE_GIVEN if given is not None else (_lib.ADVANTAGE_BATCH if mode == "batch" else _lib.ADVANTAGE_RAW)
+        _lib.check(self._lib.uavtrack_learner_set_advantage(self._h, code, e, _ptr(given)), "uavtrack_learner_set_advantage")
+        self._advantage = mode
+
+    def get_advantage(self):
+        """(mode, eps) as last set: mode "raw", "batch" or the installed tensor."""
+        mode, eps, given = C.c_int32(), C.c_double(), C.c_void_p()
+        _lib.check(self._lib.uavtrack_learner_get_advantage(self._h, C.byref(mode), C.byref(eps), C.byref(given)),
+                   "uavtrack_learner_get_advantage")
+        return ("raw", "batch", self._advantage)[mode.value], eps.value
+
     def _params(self):
         return list(self._actor.parameters()) + list(self._critic.parameters())
 
@@ -293,7 +349,8 @@ class DeviceActorCritic(Handle):
         """Synchronises; raises if an update since the last check was refused on the device (an action outside
         [0, action_dim), an index outside the ring, an importance weight that is NaN, infinite or negative -- what a
         refused ring draw hands out --, a discount that is NaN or outside [0, 1], or, under the clipped surrogate, a
-        behaviour log-probability that is NaN or positive or a ratio that is not finite), which then changed nothing."""
+        behaviour log-probability that is NaN or positive or a ratio that is not finite, or, under a normalised
+        advantage, a mean that is not finite or an inv_std that is NaN, infinite or negative), which then changed nothing."""
         self._check()
 
     # ---- the critic alone, the actor alone, and the argument checks they share
@@ -439,6 +496,8 @@ class DeviceActorCritic(Handle):
         batch row), _discounted (weights or NULL, then discounts, one per slot of the store) or, with clip = (log_mu,
         clip_eps, ratio_out), _clipped (weights or NULL, discounts or NULL, log_mu per slot, eps, ratios or NULL); then
         the outputs."""
+        if isinstance(self._advantage, str) and self._advantage == "batch" and n < 2:
+            raise ValueError(f'n = {n} row under set_advantage("batch"): the standard deviation of a batch needs two rows')
         w = _lib.tensor_arg(weights, torch.float32, n, self.device,
                             f"weights must be a contiguous float32 tensor of {n} elements (one per batch row, in batch "
                             f"order) on {self.device}")

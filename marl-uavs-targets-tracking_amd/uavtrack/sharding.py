@@ -244,8 +244,8 @@ def broadcast_learner(learner, group=None, src: int = 0) -> None:
     and target critic (its settings and, where enabled, its parameters) to every rank of `group` (src is a global
     rank), so that the ranks' learners start equal: pack_learner_state on every rank, one broadcast,
     unpack_learner_state.  Gradient rows carry no settings, so ranks that share updates must hold equal ones: change
-    them on every rank alike afterwards, or broadcast again.  Synchronises; meant for start-up and checkpoint loads, not
-    the training loop."""
+    them on every rank alike afterwards, or broadcast again.  The advantage setting (learner.set_advantage) is NOT carried:
+    call it on every rank alike.  Synchronises; meant for start-up and checkpoint loads, not the training loop."""
     import torch
     import torch.distributed as dist
     if not (dist.is_available() and dist.is_initialized()) or dist.get_world_size(group) == 1:

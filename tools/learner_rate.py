@@ -12,6 +12,7 @@ softmax, losses and Adam are not counted.
     python tools/learner_rate.py --regularised [--quick]
     python tools/learner_rate.py --target [--quick]
     python tools/learner_rate.py --clipped
+    python tools/learner_rate.py --normalised
 
 --regularised times the device update alone (loss="per_sample") under four settings of
 DeviceActorCritic.set_regularisation: everything off, the entropy bonus on, clipping on, both.  "off" enqueues the
@@ -29,6 +30,12 @@ back-to-back calls.  A/B against another build of the library: run the tool once
 processes each, with UAVTRACK_LIB=<path> UAVTRACK_LIB_OLDER_OK=1; a library without the clipped symbols prints only its
 "plain" figure.  The plain figure of this build may not lie above the slowest of the other build's three (DESIGN.md
 section 4.11's rule); the clipped figure is reported, not a pass mark.
+
+--normalised times the same update_from under the three modes of DeviceActorCritic.set_advantage -- "raw", a given
+(mean, inv_std) pair (the gradient kernel's normalising instantiation alone) and "batch" (the TD pass, the statistics and
+one sealing launch on top) --, each without and with clip_eps = 0.2, the six alternating.  A/B against another build as
+for --clipped; a library without the advantage symbols prints only its "raw" figures, and "raw" is the figure the rule
+above holds to.
 """
 import argparse
 import json
@@ -133,6 +140,37 @@ def clipped(n=65536, H=128, A=12, slots=1 << 21):
     print(json.dumps(out), flush=True)
 
 
+def normalised(n=65536, H=128, A=12, slots=1 << 21):
+    """update_from under set_advantage "raw", a given pair and "batch", without and with clip_eps: one JSON line."""
+    sys.path.insert(0, os.path.join(ROOT, "tools"))
+    from nstep_rate import alternating
+    from offpolicy_rate import filled
+    modes = ["raw"] + (["given", "batch"] if hasattr(uavtrack._lib.load(), "uavtrack_learner_set_advantage") else [])
+    pair = torch.tensor([3.0, 0.8], device="cuda:0")
+    learners, calls = {}, {}
+    for mode in modes:
+        for clip in (None, 0.2):
+            L = uavtrack.DeviceActorCritic(12, H, A, 1e-4, 5e-4, 0.95, "cuda:0", loss="per_sample", max_batch=n)
+            if mode != "raw":
+                L.set_advantage(pair if mode == "given" else "batch")
+            learners[mode + ("_clip" if clip else "")] = (L, clip)
+    ring = filled(uavtrack.ReplayRing(slots, "cuda:0", seed=1, max_batch=n).with_behaviour(), learners["raw"][0])
+    for name, (L, clip) in learners.items():
+        calls[name] = (lambda L=L: L.update_from(ring, n)) if clip is None else (lambda L=L, c=clip: L.update_from(ring, n, clip_eps=c))
+    res = alternating(calls, reps=20)
+    out = {"what": "update_from", "ring": "uniform", "n": n, "H": H, "A": A, "slots": slots,
+           "lib": os.environ.get("UAVTRACK_LIB", "this build")}
+    for name, (med, runs) in res.items():
+        out[name + "_us"] = round(med, 1)
+        out[name + "_runs_us"] = [round(x, 1) for x in runs]
+    if "batch" in modes:
+        out["batch_stats"] = [round(float(x), 4) for x in learners["batch"][0].advantage_stats]
+    for x in [L for L, _ in learners.values()] + [ring]:
+        x.check()
+        x.close()
+    print(json.dumps(out), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--quick", action="store_true", help="n 65536, H 128 only")
@@ -142,6 +180,8 @@ def main():
                     help="time the device update without a target critic, with Polyak averaging and with a periodic copy")
     ap.add_argument("--clipped", action="store_true",
                     help="time update_from at n 65536, H 128 from a uniform behaviour ring without and with clip_eps = 0.2")
+    ap.add_argument("--normalised", action="store_true",
+                    help="time update_from at n 65536, H 128 under set_advantage raw / given / batch, without and with clip_eps")
     ap.add_argument("--settings", default=None, help="--regularised: a comma-separated subset of off,entropy,clip,both; "
                                                      "--target: of off,polyak,periodic")
     ap.add_argument("--reps", type=int, default=100)
@@ -149,6 +189,8 @@ def main():
     args = ap.parse_args()
     if args.clipped:
         return clipped()
+    if args.normalised:
+        return normalised()
     dev = "cuda:0"
     A = 12
     grid = [(65536, 128)] if args.quick else [(n, H) for H in (64, 128, 256) for n in (4096, 65536, 262144)]
