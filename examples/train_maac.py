@@ -19,6 +19,7 @@ update is the same rule on a sampled batch, and the new actor weights are re-upl
     python examples/train_maac.py --replay prioritized --learner device --rho-bar 1.0 --publish device --log-every 10   # truncated importance ratios: who acted
     python examples/train_maac.py --replay prioritized --learner device --actor-loss per_sample --ppo-clip 0.2   # ... or PPO's clipped surrogate from the same store
     python examples/train_maac.py --replay prioritized --learner device --actor-loss per_sample --ppo-clip 0.2 --normalise-advantage   # ... on batch-standardised advantages
+    python examples/train_maac.py --replay uniform-device --learner device --actor-loss per_sample --ppo-clip 0.2 --ppo-epochs 4 --minibatch 65536   # ... over 4 epochs of disjoint minibatches of the new rollout
     python examples/train_maac.py --replay prioritized --learner device --target-tau 0.005                # bootstrap from a Polyak-averaged target critic
     python examples/train_maac.py --replay prioritized --learner device --target-period 100 --td-lambda 0.9   # ... or a periodic copy; the lambda add folds with it too
     python examples/train_maac.py --method maac-r --pmi-trainer device --learner device --replay prioritized --publish device --log-every 10
@@ -223,6 +224,40 @@ def ratio_field(r, eps):
             f"kl {float(-torch.log(r).mean()):+.5f}  ")
 
 
+class RatioMeans:
+    """--ppo-epochs with --ppo-clip or --rho-bar: the printed lines' ratio statistics as a mean over the iteration's
+    minibatches instead of the last update's alone, summed on the device (read on printed lines only)."""
+
+    def __init__(self, args):
+        self.args, self.sum, self.n = args, None, 0
+
+    def add(self, r):
+        a = self.args
+        if a.ppo_clip is not None:
+            v = torch.stack([r.mean(), ((r - 1).abs() > a.ppo_clip).float().mean(), -torch.log(r).mean()])
+        else:
+            v = torch.stack([r.mean(), (r >= a.rho_bar).float().mean()])
+        self.sum, self.n = (v if self.sum is None else self.sum + v), self.n + 1
+
+    def field(self):
+        m = (self.sum / self.n).tolist()
+        if self.args.ppo_clip is not None:
+            return f"ratio mean {m[0]:.4f} clipped {m[1]:.3f} kl {m[2]:+.5f} (over {self.n} minibatches)  "
+        return f"rho mean {m[0]:.4f} at cap {m[1]:.3f} (over {self.n} minibatches)  "
+
+
+def epoch_sweeps(args, rings, rows, sweeps):
+    """--ppo-epochs E, behind the iteration's adds: one sweep of minibatches of `rows` per ring, made on the first
+    iteration and rebound to what the add has just written on every later one (ring.sweep, sweep.rebind: the cursor back
+    at call 0), and the E * M update calls the iteration then takes -- M the minibatches of the smallest window, so that no
+    ring goes beyond its E epochs."""
+    try:
+        sweeps = [ring.sweep(rows) for ring in rings] if sweeps is None else [s.rebind() for s in sweeps]
+    except ValueError as e:
+        raise SystemExit(f"train_maac.py: --minibatch: {e}")
+    return sweeps, args.ppo_epochs * min(s.minibatches for s in sweeps)
+
+
 def ratio_kwargs(args, bufs, rings):
     """update_from_many's arguments under --rho-bar or --ppo-clip, and the views of bufs (one per ring) the ratios land
     in; update_from takes the one view itself."""
@@ -345,6 +380,7 @@ def train_sharded(args, timings=None):
     stats = [uavtrack.EpisodeStats(e, log_capacity=e.cfg.n_envs * args.log_every, max_steps=args.steps) for e in envs]
     kept = {k: [] for k in SIX}
     history, stamps, outs = [], [], [None] * K
+    sweeps = None                                                     # --ppo-epochs: one sweep per ring, made at the first add
     t_log = time.perf_counter()
     for it in range(args.iters):
         log = (it + 1) % args.log_every == 0 or it == args.iters - 1
@@ -362,14 +398,23 @@ def train_sharded(args, timings=None):
         if log:
             torch.cuda.synchronize()
         t_roll = time.perf_counter() - t0
-        rho_kw, rhos = ratio_kwargs(args, rho_bufs, rings)            # every ring's ratios, read on printed lines only
-        for _ in range(args.updates):
-            la_t, lc_t, tds = learner.update_from_many(rings, per_shard, **importance_kwargs(args), **rho_kw)
+        sources, n_updates = rings, args.updates
+        if args.ppo_epochs:                                           # E epochs over what the adds above wrote
+            sweeps, n_updates = epoch_sweeps(args, rings, per_shard, sweeps)
+            sources = sweeps
+        rho_kw, rhos = ratio_kwargs(args, rho_bufs, sources)          # every ring's ratios, read on printed lines only
+        means = RatioMeans(args) if log and rho_kw and args.ppo_epochs else None
+        for _ in range(n_updates):
+            la_t, lc_t, tds = learner.update_from_many(sources, per_shard, **importance_kwargs(args), **rho_kw)
+            if means is not None:
+                means.add(torch.cat(rhos))
         la, lc = (float(la_t), float(lc_t)) if log else (la_t, lc_t)
         reg_field = ""
         if log and regularised(args):                                 # the last ring's rows of the last update
             reg_field = regularisation_field(learner.entropy(tds[-1].numel()).mean(), learner.grad_norm)
-        if log and rho_kw:
+        if means is not None:
+            reg_field += means.field()
+        elif log and rho_kw:
             reg_field += rho_field(torch.cat(rhos), args.rho_bar) if args.ppo_clip is None else \
                 ratio_field(torch.cat(rhos), args.ppo_clip)
         if log and args.normalise_advantage:
@@ -480,6 +525,18 @@ def main(argv=None, timings=None):
                          "the gradient kernel; the torch learner trains the same expression); the printed lines show the "
                          "mean ratio, the share of rows with |r - 1| > EPS and mean(-log r).  Needs --replay prioritized or "
                          "uniform-device, and --actor-loss per_sample with --learner device; not with --rho-bar")
+    ap.add_argument("--ppo-epochs", type=int, default=None, metavar="E",
+                    help="E >= 1: on-policy epochs in place of --updates.  After each iteration's add the ring's sweep is "
+                         "rebound to the slots that add wrote (ring.sweep(K), sweep.rebind()) and the iteration takes E * M "
+                         "updates from it, M = window // K: E passes over the new rollout in disjoint minibatches, every "
+                         "transition once per pass, in another order each pass (DeviceActorCritic.update_from(sweep, K); the "
+                         "torch learner trains on sweep.sample(), and leaves a prioritised ring's priorities alone).  "
+                         "--ppo-clip, --rho-bar, --normalise-advantage, --entropy-coef, --n-step, --td-lambda and --shards "
+                         "apply as before, and the printed ratio statistics become means over the iteration's minibatches.  "
+                         "Needs --replay prioritized or uniform-device; not with --importance (a sweep is uniform)")
+    ap.add_argument("--minibatch", type=int, default=None, metavar="K",
+                    help="--ppo-epochs only: rows per minibatch (default: --batch; with --shards, split over the rings as "
+                         "--batch is); at most what one iteration adds")
     ap.add_argument("--normalise-advantage", action="store_true",
                     help="standardise each batch's TD errors before they multiply grad log p (and gate --ppo-clip): "
                          "A = (td - mean) / (std + 1e-8), in both learners (--learner device: "
@@ -587,6 +644,20 @@ def main(argv=None, timings=None):
         if args.learner == "device" and args.actor_loss != "per_sample":
             ap.error("--ppo-clip with --learner device needs --actor-loss per_sample: the reference form scales the actor's "
                      "gradient sums once by -mean(delta) / N, a factor a per-row gate cannot share")
+    if args.minibatch is not None and args.ppo_epochs is None:
+        ap.error("--minibatch is the minibatch of --ppo-epochs")
+    if args.ppo_epochs is not None:
+        if args.ppo_epochs < 1 or args.replay == "uniform":
+            ap.error("--ppo-epochs must be >= 1 and needs --replay prioritized or --replay uniform-device (the sweep is "
+                     "the device rings' draw)")
+        if args.importance:
+            ap.error("--ppo-epochs and --importance exclude each other: a sweep is a uniform pass and has no importance "
+                     "weights")
+        if args.minibatch is not None:
+            args.batch = args.minibatch                               # what the rings and the learner are sized by
+        if not 1 <= args.batch <= args.envs * args.n_uav * args.steps * args.rollout_episodes:
+            ap.error("--minibatch (default --batch) must be in [1, envs * n_uav * steps * rollout-episodes]: a minibatch is "
+                     "part of what one iteration adds")
     if args.target_tau is not None and not 0.0 < args.target_tau <= 1.0:
         ap.error("--target-tau must lie in (0, 1]")
     if args.target_period is not None and args.target_period < 1:
@@ -664,6 +735,7 @@ def main(argv=None, timings=None):
     kept = {k: [] for k in SIX}
     history = []
     out = None
+    sweeps = None                                                     # --ppo-epochs: the ring's sweep, made at the first add
     t_log = time.perf_counter()
     stamps = []
     for it in range(args.iters):
@@ -692,7 +764,20 @@ def main(argv=None, timings=None):
                       rho_stats=rho_stats, target_critic=target_critic, ppo_clip=args.ppo_clip,
                       normalise=args.normalise_advantage, adv_stats=adv_stats)
         boot = critic if target_critic is None else target_critic     # whose V(s') the torch learner bootstraps from
-        if learner is None and args.replay == "prioritized":          # train.py:250-262
+        source, n_updates = replay, args.updates
+        if args.ppo_epochs:                                           # E epochs over what the add above wrote
+            sweeps, n_updates = epoch_sweeps(args, [replay], args.batch, sweeps)
+            source = sweeps[0]
+        means = RatioMeans(args) if log and behavioural(args) and args.ppo_epochs else None
+        if learner is None and args.ppo_epochs:                       # the torch learner on the sweep's minibatches
+            for _ in range(n_updates):
+                la, lc = update(actor, critic, opt_a, opt_c, source.sample(), args.gamma, **reg_kw)
+                if means is not None:
+                    means.add(rho_stats["rho"])
+                updates_done += 1
+                if target_critic is not None:
+                    sync_target_critic(args, target_critic, critic, updates_done)
+        elif learner is None and args.replay == "prioritized":        # train.py:250-262
             ikw = importance_kwargs(args)
             for _ in range(args.updates):
                 batch, idx, w = replay.sample(args.batch, args.beta, ikw.get("beta_final"), ikw.get("anneal_calls", 0))
@@ -710,12 +795,14 @@ def main(argv=None, timings=None):
                 if target_critic is not None:
                     sync_target_critic(args, target_critic, critic, updates_done)
         else:
-            rho_kw, views = ratio_kwargs(args, [rho_buf], [replay])
+            rho_kw, views = ratio_kwargs(args, [rho_buf], [source])
             if views:                                                 # one ring: its view itself, not a list
                 rho_stats["rho"] = views[0]
                 rho_kw = {k: views[0] if k.endswith("_out") else v for k, v in rho_kw.items()}
-            for _ in range(args.updates):
-                la_t, lc_t, td_t = learner.update_from(replay, args.batch, **importance_kwargs(args), **rho_kw)
+            for _ in range(n_updates):
+                la_t, lc_t, td_t = learner.update_from(source, args.batch, **importance_kwargs(args), **rho_kw)
+                if means is not None:
+                    means.add(views[0])
             la, lc = (float(la_t), float(lc_t)) if log else (la_t, lc_t)
             if diag is not None:
                 diag.update(entropy=learner.entropy(td_t.numel()).mean(), norms=learner.grad_norm)
@@ -759,9 +846,11 @@ def main(argv=None, timings=None):
         n_iter = it + 1 - (stamps[-1][0] if stamps else 0)           # iterations since the previous line
         stamps.append((it + 1, now))
         reg_field = regularisation_field(diag["entropy"], diag.get("norms")) if diag else ""
-        if args.rho_bar is not None:
+        if means is not None:
+            reg_field += means.field()
+        elif args.rho_bar is not None:
             reg_field += rho_field(rho_stats["rho"], args.rho_bar)
-        if args.ppo_clip is not None:
+        elif args.ppo_clip is not None:
             reg_field += ratio_field(rho_stats["rho"], args.ppo_clip)
         if args.normalise_advantage:
             reg_field += advantage_field(*((adv_stats["mean"], adv_stats["std"]) if learner is None else

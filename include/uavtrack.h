@@ -1047,7 +1047,26 @@ int uavtrack_pmi_trainer_select(uavtrack_pmi_trainer *trainer, const uavtrack_pm
  * bijection, have started from the same j.  So the n indices are distinct, and they are the first n entries, in order,
  * of a permutation of [0, count) that depends on (seed, c, count) alone: n = count gives all of it, a smaller n its
  * prefix.  Everything is integer arithmetic, so the indices are bitwise reproducible anywhere.  The expected number of
- * applications of pi_c per draw is 2^b / count < 4. */
+ * applications of pi_c per draw is 2^b / count < 4.
+ *
+ * The sweep stream (on-policy epochs: uavtrack_replay_sample_sweep).  A sweep goes through a window of the ring -- the
+ * W = length slots first, first + 1, ... taken mod capacity -- in epochs of M = W / n (integer division) minibatches of
+ * n slots, every slot at most once per epoch.  It is numbered by a cursor the caller owns (two DEVICE words), not by the
+ * handle's call counter, which a sweep call neither reads nor advances: cursor[0] is the number q of the next call; a
+ * one-thread kernel in front of the draw copies it to cursor[1] and advances it, so every replay of a captured graph
+ * takes the next minibatch, and the draw reads q = cursor[1].  Call q is minibatch m = q mod M of epoch e = q / M, formed
+ * on the device, and its entry j (0 <= j < n) is
+ *     indices[j] = (first + sigma_e(m n + j)) mod capacity
+ * sigma_e(x) being pi(x), pi applied again while the value is >= W, with pi the Feistel network of the uniform draw
+ * stream above on b bits (b the smallest even number >= 2 with 2^b >= W): the same 16 rounds and fmix32, the round keys
+ *     key_(4 i + w) = word w of Philox4x32-10(counter = (i, e mod 2^32, e >> 32, 0x53574550 "SWEP"),
+ *                                             key = (seed mod 2^32, seed >> 32))                 for i = 0 .. 3
+ * -- the epoch in the place of the call number, and a word 3 that differs from the four streams above.  As there, the
+ * walks from the starts x < W end and never meet, so sigma_e is a permutation of [0, W): the M calls of an epoch return
+ * M n distinct slots of the window, all of it when n divides W; otherwise the last W mod n entries of that epoch's
+ * permutation are left out, other slots every epoch (a shuffled loader's drop_last).  Another epoch has other keys,
+ * hence another order.  Everything is integer arithmetic, so the indices are bitwise reproducible anywhere, and depend
+ * on (seed, q, first, W, n, capacity) alone: two cursors over the same window agree call for call. */
 typedef struct uavtrack_replay_config {
     uint32_t struct_size;       /* = sizeof(uavtrack_replay_config), ABI check */
     int32_t  device_id;         /* HIP device ordinal */
@@ -1210,6 +1229,21 @@ int uavtrack_replay_sample_annealed(uavtrack_replay *replay, const uavtrack_repl
  * or capacity > max_capacity.  It reads no ring data, so nothing is refused on the device. */
 int uavtrack_replay_sample_uniform(uavtrack_replay *replay, const uavtrack_replay_ring *ring, int64_t n, int64_t *indices,
                                    void *stream);
+
+/* The next minibatch of a sweep over a ring window (the sweep stream above): n distinct slots of the window of `length`
+ * slots from `first` on (wrapping at ring->capacity) into indices [n] (DEVICE int64), numbered by cursor (DEVICE, 2
+ * uint64 words, the caller's: word 0 the number of the next call, to be set -- 0 to begin, q to go to call q -- by the
+ * caller on the same stream; word 1 scratch).  length / n consecutive calls return every slot of the window exactly once
+ * when n divides length, and length / n * n distinct ones otherwise.  Only ring->capacity and ring->count (and
+ * ring->pos, checked against the limits) are used; it reads no ring data, so nothing is refused on the device, and
+ * ring->priorities may be NULL or not.  The work is O(n).  Stream-ordered, no synchronisation, no allocation,
+ * capturable; the handle's call counter is neither read nor advanced, so the other draws' streams are what they are
+ * without any sweep.  Returns an error, enqueuing nothing and leaving the cursor alone, for a null handle, ring, cursor
+ * or indices, n < 1 or n > max_batch, count < 1, count > capacity or capacity > max_capacity, length < 1, first outside
+ * [0, capacity), n > length, or a window that leaves the valid slots: length > count or, while count < capacity,
+ * first + length > count (a full ring's window may wrap). */
+int uavtrack_replay_sample_sweep(uavtrack_replay *replay, const uavtrack_replay_ring *ring, int64_t first, int64_t length,
+                                 int64_t n, uint64_t *cursor, int64_t *indices, void *stream);
 
 /* Synchronises `stream`; fails if any sample call since the previous check was refused on the device (bad or all-zero
  * priorities).  refused (nullable) receives their number; the count restarts at 0. */

@@ -254,6 +254,28 @@ int uavtrack_replay_sample_uniform(uavtrack_replay *replay, const uavtrack_repla
     return 0;
 }
 
+int uavtrack_replay_sample_sweep(uavtrack_replay *replay, const uavtrack_replay_ring *ring, int64_t first, int64_t length,
+                                 int64_t n, uint64_t *cursor, int64_t *indices, void *stream)
+{
+    if (accept_draw(replay, __func__, ring, false, n, indices)) return 1;
+    if (!cursor) return fail("%s: cursor must not be null", __func__);
+    if (length < 1) return fail("%s: length = %lld < 1", __func__, (long long)length);
+    if (first < 0 || first >= ring->capacity)
+        return fail("%s: first = %lld outside [0, capacity = %lld)", __func__, (long long)first, (long long)ring->capacity);
+    if (n > length)
+        return fail("%s: n = %lld exceeds length = %lld (a minibatch is part of the window)", __func__, (long long)n,
+                    (long long)length);
+    // the valid slots are [0, count), a circle once the ring is full (length > count, written so that nothing overflows)
+    if (length > ring->count || (ring->count < ring->capacity && first > ring->count - length))
+        return fail("%s: the window [%lld, %lld + %lld) leaves the ring's %lld valid slots (capacity %lld)", __func__,
+                    (long long)first, (long long)first, (long long)length, (long long)ring->count,
+                    (long long)ring->capacity);
+    ON_DEVICE(replay->cfg.device_id);
+    HIP_TRY(launch_replay_sample_sweep(replay->d, ring->capacity, first, length, n, cursor, indices,
+                                       static_cast<hipStream_t>(stream)));
+    return 0;
+}
+
 int uavtrack_replay_check(uavtrack_replay *replay, int64_t *refused, void *stream)
 {
     int count = 0;

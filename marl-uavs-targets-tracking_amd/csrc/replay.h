@@ -15,7 +15,9 @@ constexpr int kReplayTile = 2048;
 constexpr int kReplayMaxParts = 1024;         // workgroups of the priority-maximum reduction
 constexpr uint32_t kReplayDomain = 0x52504C59u;   // "RPLY": Philox counter word 3 of the draw stream
 constexpr uint32_t kUniformDomain = 0x554E4946u;  // "UNIF": Philox counter word 3 of the uniform draw's round keys
-constexpr int kUniformRounds = 16;            // Feistel rounds of the uniform draw's bijection (four Philox blocks of keys)
+constexpr uint32_t kSweepDomain = 0x53574550u;    // "SWEP": Philox counter word 3 of the sweep's round keys
+constexpr int kUniformRounds = 16;            // Feistel rounds of the uniform draw's and the sweep's bijection (four Philox
+                                              // blocks of keys)
 struct ReplayDevice {
     int64_t max_capacity, max_batch;
     uint32_t k0, k1;                // Philox key: the ring's seed
@@ -42,6 +44,11 @@ hipError_t launch_replay_sample(const ReplayDevice &d, const float *priorities, 
 // Shares the call counter with launch_replay_sample.
 hipError_t launch_replay_sample_uniform(const ReplayDevice &d, int64_t count, int64_t k, int64_t *indices,
                                         hipStream_t stream);
+// Minibatch cursor[0] % (length / n) of epoch cursor[0] / (length / n) of a sweep over the window first, first + 1, ...
+// (mod capacity) of `length` slots: n of them, no slot twice within an epoch.  cursor (DEVICE, 2 words, the caller's)
+// is advanced on the device; the handle's call counter is neither read nor advanced.
+hipError_t launch_replay_sample_sweep(const ReplayDevice &d, int64_t capacity, int64_t first, int64_t length, int64_t n,
+                                      uint64_t *cursor, int64_t *indices, hipStream_t stream);
 // One ring add of steps x envs x n_uav transitions, of which the last min(n, capacity) land in the ring from ring.pos on;
 // ring.priorities == nullptr (a uniform ring): the stores alone.
 //   Flat     states / next [n][12], actions / rewards [n], with steps = n and envs = n_uav = 1;

@@ -26,7 +26,9 @@
 //
 // The uniform draw (the reference's ReplayBuffer.sample, train.py:56-58: random.sample, without replacement) is
 // replay_begin_kernel and replay_uniform_kernel: one thread per draw, O(k) whatever the ring holds.  It reads nothing
-// of the ring, so it has no refusal.
+// of the ring, so it has no refusal.  The sweep (on-policy epochs: every slot of a ring window once per epoch, a
+// minibatch per call) is replay_cursor_kernel and replay_sweep_kernel: the same walk, keyed by the epoch and started at
+// the call's place in it, both read off a cursor the caller owns; the handle's counter is not touched.
 //
 // Adding (launch_replay_add, one ReplayAdd request) is two reductions (the maximum of the whole priorities array,
 // train.py:87-88; skipped for a ring without priorities, a uniform ring) and one write kernel over the request's ring
@@ -313,25 +315,22 @@ __device__ __forceinline__ uint32_t fmix32(uint32_t x)
     return x;
 }
 
-// indices[j] = pi(j) walked below count: pi is a balanced Feistel network on 2 * half bits (count <= 4^half), round
-// r's function fmix32(R + key_r) mod 2^half, the keys Philox blocks of (seed, call number).  The walk stays on the
-// cycle of pi through j < count, so it ends, and no two draws meet: pi is a bijection and each draw stops at the first
-// value below count after its own start.
-__global__ void __launch_bounds__(kSW) replay_uniform_kernel(const uint64_t *counter, int64_t count, int64_t k, int half,
-                                                             uint32_t k0, uint32_t k1, int64_t *indices)
+// pi(x) walked below count: pi is a balanced Feistel network on 2 * half bits (count <= 4^half), round r's function
+// fmix32(R + key_r) mod 2^half, the keys Philox blocks of (seed, number) in the stream DOMAIN names.  The walk stays on
+// the cycle of pi through x < count, so it ends, and no two starts below count meet: pi is a bijection and each walk
+// stops at the first value below count after its own start.  So the starts [0, count) map onto a permutation of
+// [0, count).  What the uniform draw (number = the call) and the sweep (number = the epoch) share.
+template <uint32_t DOMAIN>
+__device__ __forceinline__ uint64_t keyed_walk(uint64_t x, uint64_t number, int64_t count, int half, uint32_t k0, uint32_t k1)
 {
-    const int64_t j = (int64_t)blockIdx.x * kSW + threadIdx.x;
-    if (j >= k) return;
-    const uint64_t call = counter[1];
     uint32_t key[kUniformRounds];
 #pragma unroll
     for (int i = 0; i < kUniformRounds / 4; ++i) {
-        const Philox4 r = philox4x32_10((uint32_t)i, (uint32_t)call, (uint32_t)(call >> 32), kUniformDomain, k0, k1);
+        const Philox4 r = philox4x32_10((uint32_t)i, (uint32_t)number, (uint32_t)(number >> 32), DOMAIN, k0, k1);
 #pragma unroll
         for (int w = 0; w < 4; ++w) key[4 * i + w] = r.v[w];
     }
     const uint32_t mask = (1u << half) - 1u;
-    uint64_t x = (uint64_t)j;
     do {
         uint32_t L = (uint32_t)(x >> half), R = (uint32_t)x & mask;
 #pragma unroll
@@ -342,7 +341,48 @@ __global__ void __launch_bounds__(kSW) replay_uniform_kernel(const uint64_t *cou
         }
         x = ((uint64_t)L << half) | R;
     } while (x >= (uint64_t)count);
-    indices[j] = (int64_t)x;
+    return x;
+}
+
+// indices[j] = pi_call(j) walked below count
+__global__ void __launch_bounds__(kSW) replay_uniform_kernel(const uint64_t *counter, int64_t count, int64_t k, int half,
+                                                             uint32_t k0, uint32_t k1, int64_t *indices)
+{
+    const int64_t j = (int64_t)blockIdx.x * kSW + threadIdx.x;
+    if (j >= k) return;
+    indices[j] = (int64_t)keyed_walk<kUniformDomain>((uint64_t)j, counter[1], count, half, k0, k1);
+}
+
+// ---- the sweep: the whole of an epoch's permutation of a ring window, one minibatch of n per call
+
+// the caller's cursor as replay_begin_kernel treats the handle's counter: this call's number, then advanced
+__global__ void replay_cursor_kernel(uint64_t *cursor)
+{
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    cursor[1] = cursor[0];
+    cursor[0] += 1;
+}
+
+struct SweepArgs {
+    const uint64_t *cursor;
+    int64_t *indices;
+    int64_t first, length, n, cap;             // the window's first slot and its length W; n <= W <= cap, first < cap
+    int half;
+    uint32_t k0, k1;
+};
+
+// Call q = cursor[1] is minibatch m = q % M of epoch e = q / M, M = W / n: indices[j] = first + sigma_e(m n + j) wrapped
+// at cap, sigma_e the walk keyed by (seed, e).  m n + j < M n <= W is a start inside the window; first + x < 2 cap, so
+// one subtraction wraps.
+__global__ void __launch_bounds__(kSW) replay_sweep_kernel(SweepArgs a)
+{
+    const int64_t j = (int64_t)blockIdx.x * kSW + threadIdx.x;
+    if (j >= a.n) return;
+    const uint64_t q = a.cursor[1], M = (uint64_t)(a.length / a.n);
+    const uint64_t e = q / M, m = q - e * M;
+    const uint64_t x = keyed_walk<kSweepDomain>(m * (uint64_t)a.n + (uint64_t)j, e, a.length, a.half, a.k0, a.k1);
+    const int64_t slot = a.first + (int64_t)x;
+    a.indices[j] = slot >= a.cap ? slot - a.cap : slot;
 }
 
 // ---- add
@@ -636,16 +676,35 @@ hipError_t launch_replay_sample(const ReplayDevice &d, const float *priorities, 
     return hipSuccess;
 }
 
-hipError_t launch_replay_sample_uniform(const ReplayDevice &d, int64_t count, int64_t k, int64_t *indices, hipStream_t st)
+// half the width of the walk's domain: the width even, >= 2, count <= 2^width (< 4 * count from count 2 on)
+static int walk_half_bits(int64_t count)
 {
     static_assert(kUniformRounds % 4 == 0, "round keys come in Philox blocks of four");
-    int bits = 2;                              // even, >= 2, count <= 2^bits (< 4 * count from count 2 on)
+    int bits = 2;
     while (((int64_t)1 << bits) < count) bits += 2;
+    return bits / 2;
+}
+
+hipError_t launch_replay_sample_uniform(const ReplayDevice &d, int64_t count, int64_t k, int64_t *indices, hipStream_t st)
+{
     hipLaunchKernelGGL(replay_begin_kernel, dim3(1), dim3(64), 0, st, d.counter, d.status, d.pmin);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(replay_uniform_kernel, dim3((unsigned)((k + kSW - 1) / kSW)), dim3(kSW), 0, st, d.counter, count,
-                       k, bits / 2, d.k0, d.k1, indices);
+                       k, walk_half_bits(count), d.k0, d.k1, indices);
+    return hipGetLastError();
+}
+
+hipError_t launch_replay_sample_sweep(const ReplayDevice &d, int64_t capacity, int64_t first, int64_t length, int64_t n,
+                                      uint64_t *cursor, int64_t *indices, hipStream_t st)
+{
+    hipLaunchKernelGGL(replay_cursor_kernel, dim3(1), dim3(64), 0, st, cursor);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    SweepArgs a;
+    a.cursor = cursor; a.indices = indices; a.first = first; a.length = length; a.n = n; a.cap = capacity;
+    a.half = walk_half_bits(length); a.k0 = d.k0; a.k1 = d.k1;
+    hipLaunchKernelGGL(replay_sweep_kernel, dim3((unsigned)((n + kSW - 1) / kSW)), dim3(kSW), 0, st, a);
     return hipGetLastError();
 }
 

@@ -16,7 +16,7 @@ from .rollout import ActorMLP, BatchedRollout, sample_actions  # noqa: F401
 from .export import (uav_tracks_from_obs, save_uav_positions, save_covered_num, target_tracks,  # noqa: F401
                      save_target_positions, save_rollout)
 from .replay import DeviceReplayBuffer, PrioritizedDeviceReplayBuffer, transitions_from_rollout  # noqa: F401
-from .replay_ring import PrioritizedReplayRing, ReplayRing  # noqa: F401
+from .replay_ring import PrioritizedReplayRing, ReplayRing, RingSweep  # noqa: F401
 from .learner import DeviceActorCritic, ValueMLP  # noqa: F401
 from .pmi_trainer import DevicePMINetwork  # noqa: F401
 from .episode_stats import EpisodeStats, evaluate  # noqa: F401
@@ -26,6 +26,6 @@ from . import _lib  # noqa: F401
 __all__ = ["EnvConfig", "RewardMode", "BatchedUavEnv", "Environment", "fold_pmi_state_dict",
            "shard_range", "gather_rollout_summary", "gather_rollout_summary_async", "sample_local_transitions", "gather_transitions",
            "gather_transitions_async", "gather_learner_rows", "broadcast_learner", "gather_pmi_selected", "broadcast_pmi_trainer", "ActorMLP", "BatchedRollout", "sample_actions",
-           "DeviceReplayBuffer", "PrioritizedDeviceReplayBuffer", "transitions_from_rollout", "PrioritizedReplayRing", "ReplayRing", "DeviceActorCritic", "ValueMLP",
+           "DeviceReplayBuffer", "PrioritizedDeviceReplayBuffer", "transitions_from_rollout", "PrioritizedReplayRing", "ReplayRing", "RingSweep", "DeviceActorCritic", "ValueMLP",
            "DevicePMINetwork", "EpisodeStats", "evaluate",
            "sample_pmi_pairs", "pmi_contrastive_loss", "pmi_batches", "train_pmi_epoch", "make_pmi_net"]

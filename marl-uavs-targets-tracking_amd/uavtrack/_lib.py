@@ -238,6 +238,8 @@ SIGNATURES = {
     "uavtrack_replay_sample_annealed": (C.c_int, [C.c_void_p, C.POINTER(ReplayRing), C.c_int64, C.c_double, C.c_double,
                                                   C.c_double, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
     "uavtrack_replay_sample_uniform": (C.c_int, [C.c_void_p, C.POINTER(ReplayRing), C.c_int64, C.c_void_p, C.c_void_p]),
+    "uavtrack_replay_sample_sweep": (C.c_int, [C.c_void_p, C.POINTER(ReplayRing), C.c_int64, C.c_int64, C.c_int64,
+                                               C.c_void_p, C.c_void_p, C.c_void_p]),
     "uavtrack_replay_check": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64), C.c_void_p]),
     "uavtrack_episode_stats_create": (C.c_int, [C.POINTER(EpisodeStatsConfig), C.POINTER(C.c_void_p)]),
     "uavtrack_episode_stats_destroy": (C.c_int, [C.c_void_p]),

@@ -44,6 +44,12 @@ the first action of a transition only (on an n-step or lambda ring the rest of t
 update_from(ring, k, clip_eps=E) reads the same store inside the gradient kernel for PPO's clipped surrogate instead
 (uavtrack_learner_update_clipped); a drawn slot that is still NaN refuses that update on the device.  Without
 with_behaviour a ring is exactly what it was.
+
+On-policy epochs.  ring.sweep(batch_size, window="last") returns a RingSweep over a window of either ring -- by default
+the slots the most recent add wrote -- whose consecutive draws are the disjoint minibatches of an epoch, every slot of the
+window once per epoch, epoch after epoch in another order (uavtrack_replay_sample_sweep, numbered by a device cursor the
+sweep owns; the ring's own call counter is not touched).  The learner's update_from and its relatives take a sweep where
+they take a ring.
 """
 from __future__ import annotations
 
@@ -71,6 +77,7 @@ class ReplayRing(Handle):
     log_mu: Optional[torch.Tensor] = None       # with_behaviour: per-slot behaviour log-probabilities
     _w: Optional[torch.Tensor] = None           # a prioritised ring's importance weights of update_from's draws
     _rho_w: Optional[torch.Tensor] = None       # with_behaviour: update_from's ratio weights (a prioritised ring: its _w)
+    _last: Optional[Tuple[int, int]] = None     # (first slot, length) of what the most recent add wrote
 
     def __init__(self, capacity: int, device, seed: int = 0, max_batch: int = 65536, obs_dim: int = _lib.OBS_DIM):
         if obs_dim != _lib.OBS_DIM:
@@ -173,6 +180,8 @@ class ReplayRing(Handle):
                                capacity=self.capacity, pos=self.pos, count=self.count)
 
     def _advance(self, n: int) -> None:
+        k = min(n, self.capacity)
+        self._last = ((self.pos + n - k) % self.capacity, k)      # what every add path has just written: sweep("last")
         self.pos = (self.pos + n) % self.capacity
         self.count = min(self.capacity, self.count + n)
 
@@ -352,6 +361,14 @@ class ReplayRing(Handle):
             return self._gather(slice(0, 0))
         return self._gather(self.draw(batch_size))
 
+    def sweep(self, batch_size: int, window="last") -> "RingSweep":
+        """A RingSweep over a window of this ring (either ring): epochs of disjoint minibatches of batch_size slots, every
+        slot of the window once per epoch.  window: "last", the slots the most recent add, add_rollout or
+        add_rollout_behaviour wrote (the last min(n, capacity) of its n transitions); "all", the valid slots; or a
+        (first, length) pair, the slots first, first + 1, ... taken mod capacity.  The sweep stays on the window it was
+        made on; a later add does not move it (sweep.rebind does)."""
+        return RingSweep(self, batch_size, window)
+
     def _gather(self, idx) -> Dict[str, torch.Tensor]:
         """The transitions dict at idx: KEYS, "discounts" on a ring that has them and "log_mu" on a behaviour ring."""
         out = {key: self.store[key][idx] for key in KEYS}
@@ -430,3 +447,128 @@ class PrioritizedReplayRing(ReplayRing):
         last = torch.ones_like(srt, dtype=torch.bool)
         last[:-1] = srt[1:] != srt[:-1]
         self.priorities.index_copy_(0, srt[last], val[perm[last]])
+
+
+class RingSweep:
+    """On-policy epochs over a window of a ring (ring.sweep(batch_size, window)): call q of the sweep is minibatch
+    q % M of epoch q // M, M = W // batch_size, and an epoch's M minibatches are disjoint -- together the whole window
+    when batch_size divides W, else all but W % batch_size slots of it, other slots every epoch (a shuffled loader's
+    drop_last).  Every epoch is another order.  One library call (uavtrack_replay_sample_sweep; the stream is documented
+    in include/uavtrack.h), numbered by a two-word device cursor the sweep owns, so a captured draw replayed E * M times
+    performs E epochs.  The ring's own call counter is not touched: its draws are what they are without any sweep.
+
+    Where DeviceActorCritic.update_from, grad_from, update_from_many (a list of sweeps, one per shard) and the group path
+    take a buffer they take a sweep: it presents the ring's stores, priorities, discounts and behaviour store, its count
+    is the window's length, and its _draw_batch is the next minibatch.  rho_bar, clip_eps, ratio_out and the n-step and
+    lambda discounts compose as on the ring, and a prioritised ring's priorities still receive |td_delta|.  A sweep is
+    uniform and has no weights: importance=True and beta_final raise, and so does a batch size other than the sweep's."""
+
+    def __init__(self, ring: ReplayRing, batch_size: int, window="last"):
+        self.ring = ring
+        self.batch_size = int(batch_size)
+        if not 1 <= self.batch_size <= ring.max_batch:
+            raise ValueError(f"sweep: batch_size = {batch_size} outside [1, max_batch = {ring.max_batch}]")
+        self._window = self._resolve(window)
+        self._cursor = torch.zeros(2, dtype=torch.int64, device=ring.device)     # [next call, this call]
+        self._idx = torch.empty(self.batch_size, dtype=torch.int64, device=ring.device)   # update_from's draws
+
+    def _resolve(self, window) -> Tuple[int, int]:
+        """(first, length) of `window` on the ring as it stands, checked as the library checks it."""
+        ring = self.ring
+        if isinstance(window, str):
+            if window == "last":
+                if ring._last is None:
+                    raise ValueError('sweep: window="last" before any add: nothing has been written yet')
+                first, length = ring._last
+            elif window == "all":
+                first, length = 0, ring.count
+            else:
+                raise ValueError(f'sweep: window must be "last", "all" or a (first, length) pair, got {window!r}')
+        else:
+            try:
+                first, length = (int(v) for v in window)
+            except (TypeError, ValueError):
+                raise ValueError(f'sweep: window must be "last", "all" or a (first, length) pair, got {window!r}') from None
+        if length < 1:
+            raise ValueError(f"sweep: the window holds {length} slots (an empty ring?)")
+        if not 0 <= first < ring.capacity:
+            raise ValueError(f"sweep: first = {first} outside [0, capacity = {ring.capacity})")
+        if self.batch_size > length:
+            raise ValueError(f"sweep: batch_size = {self.batch_size} exceeds the window's {length} slots")
+        if length > ring.count or (ring.count < ring.capacity and first + length > ring.count):
+            raise ValueError(f"sweep: the window ({first}, {length}) leaves the ring's {ring.count} valid slots "
+                             f"(capacity {ring.capacity}; only a full ring's window may wrap)")
+        return first, length
+
+    # ---- the window and the cursor
+    @property
+    def window(self) -> Tuple[int, int]:
+        """(first, length): the slots first, first + 1, ... (mod capacity), length of them."""
+        return self._window
+
+    @property
+    def minibatches(self) -> int:
+        """M: minibatches (calls) per epoch, length // batch_size."""
+        return self._window[1] // self.batch_size
+
+    def rebind(self, window="last") -> "RingSweep":
+        """Pins the sweep to `window` of the ring as it stands now (as ring.sweep takes it) and rewinds the cursor to call
+        0.  Stream-ordered and allocation-free: one sweep object serves a training run, rebound after each add.  A
+        captured graph keeps the window it was captured with."""
+        self._window = self._resolve(window)
+        self._cursor.zero_()
+        return self
+
+    def seek(self, q: int) -> None:
+        """The next call becomes call q (minibatch q % M of epoch q // M): a stream-ordered fill of the cursor."""
+        q = int(q)
+        if not 0 <= q < 2 ** 63:
+            raise ValueError(f"seek: q = {q} outside [0, 2^63)")
+        self._cursor[:1].fill_(q)
+
+    def position(self) -> int:
+        """The number of the next call.  Synchronises."""
+        return int(self._cursor[0].item())
+
+    # ---- drawing
+    def _draw_into(self, idx: torch.Tensor) -> None:
+        ring = self.ring
+        view = ring._ring()
+        first, length = self._window
+        _lib.check(ring._lib.uavtrack_replay_sample_sweep(ring._h, C.byref(view), first, length, idx.numel(),
+                                                          _ptr(self._cursor), _ptr(idx), ring._stream()),
+                   "uavtrack_replay_sample_sweep")
+
+    def draw(self) -> torch.Tensor:
+        """The next minibatch: indices int64 [batch_size], distinct slots of the window.  No synchronisation."""
+        idx = torch.empty(self.batch_size, dtype=torch.int64, device=self.ring.device)
+        self._draw_into(idx)
+        return idx
+
+    def sample(self) -> Dict[str, torch.Tensor]:
+        """The next minibatch's transitions dict, with the keys ring.sample()'s dict has ("discounts" and "log_mu" on a
+        ring that has them)."""
+        return self.ring._gather(self.draw())
+
+    # ---- what the learner's draw functions read from a buffer
+    count = property(lambda self: self._window[1])
+    store = property(lambda self: self.ring.store)
+    capacity = property(lambda self: self.ring.capacity)
+    priorities = property(lambda self: self.ring.priorities)
+    discounts = property(lambda self: self.ring.discounts)
+    gamma = property(lambda self: self.ring.gamma)
+    log_mu = property(lambda self: self.ring.log_mu)
+
+    def _ratio_out(self, k: int) -> torch.Tensor:
+        return self.ring._ratio_out(k)
+
+    def _draw_batch(self, k: int, spec: DrawSpec = DrawSpec()):
+        """(the next minibatch in the preallocated index tensor, None).  Raises, enqueuing nothing, for what a sweep
+        does not have."""
+        if spec.importance or spec.beta_final is not None:
+            raise ValueError("a sweep is a uniform pass over its window and has no importance weights: importance=True and "
+                             "beta_final are for a PrioritizedReplayRing's own draw")
+        if k != self.batch_size:
+            raise ValueError(f"batch_size = {k}: this sweep was made for minibatches of {self.batch_size}")
+        self._draw_into(self._idx)
+        return self._idx, None
