@@ -1,4 +1,6 @@
 // api_learner.hip -- the C ABI of the device learner (include/uavtrack.h, uavtrack_learner_*).
+// The eight batch entry points (update, grad and their _weighted, _discounted and _clipped forms) each fill a
+// LearnerLaunch as they were called and share one acceptor and one runner: accept_learner_batch, run_learner_batch.
 
 #include "api_env.h"
 #include "api_handle.h"
@@ -84,29 +86,65 @@ int accept_advantage_rows(const char *fn, const uavtrack_learner *l, int64_t n)
     return 0;
 }
 
-// the fields uavtrack_learner_update and _grad (and their weighted forms) fill alike; the others are null
-LearnerLaunch learner_batch(int64_t n, const float *states, const int32_t *actions, const float *rewards,
-                            const float *next_states, int64_t capacity, const int64_t *indices, const float *weights,
-                            const float *discounts, float *td_delta)
-{
-    LearnerLaunch q = {};
-    q.n = n; q.capacity = capacity; q.td_delta = td_delta; q.weights = weights; q.discounts = discounts;
-    q.states = states; q.rewards = rewards; q.next_states = next_states; q.actions = actions; q.idx = indices;
-    return q;
-}
+enum class Batch { Update, Grad };
 
-// The clipped surrogate's arguments of uavtrack_learner_update_clipped / _grad_clipped, into q
-int accept_clip(const char *fn, const uavtrack_learner *l, const float *log_mu, double clip_eps, float *ratio_out,
-                LearnerLaunch &q)
+// Every host-side refusal of the eight batch entry points (uavtrack_learner_update, _grad and their _weighted,
+// _discounted and _clipped forms), in one order.  Nothing has been enqueued when one of them fires.
+int accept_learner_batch(const char *fn, const uavtrack_learner *l, const LearnerLaunch &q, Batch kind, const float *row)
 {
-    if (!log_mu) return fail("%s: log_mu must not be null", fn);
-    if (!(clip_eps >= 0)) return fail("%s: clip_eps = %g must be >= 0 (+inf: never clips)", fn, clip_eps);
+    if (!l) return fail("%s: null handle", fn);
+    if (!q.states || !q.actions || !q.rewards || !q.next_states)
+        return fail("%s: states, actions, rewards and next_states must not be null", fn);
+    if (kind == Batch::Update && (!q.actor_loss || !q.critic_loss))
+        return fail("%s: actor_loss and critic_loss must not be null", fn);
+    if (kind == Batch::Grad && (!q.td_delta || !row)) return fail("%s: td_delta and row must not be null", fn);
+    if (accept_batch(fn, l, q.n, q.capacity, q.idx, "from") || accept_entropy_rows(fn, l, q.n) ||
+        accept_advantage_rows(fn, l, q.n))
+        return 1;
+    if (!q.clipped) return 0;
+    if (!q.log_mu) return fail("%s: log_mu must not be null", fn);
+    if (!(q.clip_eps >= 0)) return fail("%s: clip_eps = %g must be >= 0 (+inf: never clips)", fn, q.clip_eps);
     if (!l->d.per_sample)
         return fail("%s: the clipped surrogate on a UAVTRACK_LOSS_REFERENCE learner: that form scales the actor's gradient "
                     "sums once by -mean(delta) / N, a factor a per-row gate cannot share; use UAVTRACK_LOSS_PER_SAMPLE", fn);
-    const float eps32 = (float)clip_eps;
-    q.log_mu = log_mu; q.clip_lo = 1.0f - eps32; q.clip_hi = 1.0f + eps32; q.ratio = ratio_out;
     return 0;
+}
+
+// The eight entry points behind their own names: accepted, the clip's bounds folded to fp32, then the closed update
+// (row null) or the gradient half into `row`.
+int run_learner_batch(const char *fn, uavtrack_learner *learner, LearnerLaunch q, Batch kind, float *row, void *stream)
+{
+    if (accept_learner_batch(fn, learner, q, kind, row)) return 1;
+    ON_DEVICE(learner->cfg.device_id);
+    if (q.clipped) {
+        const float eps32 = (float)q.clip_eps;
+        q.clip_lo = 1.0f - eps32; q.clip_hi = 1.0f + eps32;
+    }
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    HIP_TRY(kind == Batch::Update ? launch_learner_update(learner->d, q, st) : launch_learner_grad(learner->d, q, row, st));
+    return 0;
+}
+
+// uavtrack_learner_values (target false) and _values_target
+int learner_values(const char *fn, uavtrack_learner *learner, bool target, int64_t n, const float *rows, float *values,
+                   void *stream)
+{
+    if (!learner) return fail("%s: null handle", fn);
+    if (!rows || !values) return fail("%s: rows and values must not be null", fn);
+    if (n < 1) return fail("%s: n = %lld < 1", fn, (long long)n);
+    if (n > INT64_MAX / 48) return fail("%s: n = %lld rows overflow", fn, (long long)n);
+    if (((uintptr_t)rows & 15) != 0) return fail("%s: rows must be 16-byte aligned", fn);
+    if (target && !learner->d.target_mode) return fail("%s: no target critic is enabled (uavtrack_learner_set_target)", fn);
+    ON_DEVICE(learner->cfg.device_id);
+    HIP_TRY(launch_learner_values(learner->d, target, n, rows, values, static_cast<hipStream_t>(stream)));
+    return 0;
+}
+
+// theta- <- the critic as it stands when the copy runs: uavtrack_learner_set_target (off -> on) and _sync_target
+hipError_t copy_critic_to_target(const LearnerDevice &d, void *stream)
+{
+    return hipMemcpyAsync(d.target, d.params + d.L.c_w1, sizeof(float) * (size_t)learner_critic_words(d.L),
+                          hipMemcpyDeviceToDevice, static_cast<hipStream_t>(stream));
 }
 
 }  // namespace
@@ -252,69 +290,13 @@ int uavtrack_learner_get_optimizer_state(uavtrack_learner *learner, float *exp_a
     return optimizer_state(__func__, learner, exp_avg, exp_avg_sq, step, n_floats, stream, "the networks have %d");
 }
 
-}  // extern "C"
-
-namespace {
-
-// the clipped surrogate's arguments as the _clipped entry points pass them on; null for every other entry point
-struct ClipArgs {
-    const float *log_mu;
-    double clip_eps;
-    float *ratio_out;
-};
-
-// uavtrack_learner_update, _update_weighted, _update_discounted and _update_clipped (`fn`: the caller's name; weights,
-// discounts nullable; clip: _update_clipped only)
-int learner_update(const char *fn, uavtrack_learner *learner, int64_t n, const float *states, const int32_t *actions,
-                   const float *rewards, const float *next_states, int64_t capacity, const int64_t *indices,
-                   const float *weights, const float *discounts, float *actor_loss, float *critic_loss, float *td_delta, float *priorities,
-                   void *stream, const ClipArgs *clip = nullptr)
-{
-    if (!learner) return fail("%s: null handle", fn);
-    if (!states || !actions || !rewards || !next_states)
-        return fail("%s: states, actions, rewards and next_states must not be null", fn);
-    if (!actor_loss || !critic_loss) return fail("%s: actor_loss and critic_loss must not be null", fn);
-    if (accept_batch(fn, learner, n, capacity, indices, "from") || accept_entropy_rows(fn, learner, n) ||
-        accept_advantage_rows(fn, learner, n))
-        return 1;
-    ON_DEVICE(learner->cfg.device_id);
-    LearnerLaunch q = learner_batch(n, states, actions, rewards, next_states, capacity, indices, weights, discounts, td_delta);
-    q.actor_loss = actor_loss; q.critic_loss = critic_loss; q.priorities = priorities;
-    if (clip && accept_clip(fn, learner, clip->log_mu, clip->clip_eps, clip->ratio_out, q)) return 1;
-    HIP_TRY(launch_learner_update(learner->d, q, static_cast<hipStream_t>(stream)));
-    return 0;
-}
-
-// uavtrack_learner_grad, _grad_weighted, _grad_discounted and _grad_clipped
-int learner_grad(const char *fn, uavtrack_learner *learner, int64_t n, const float *states, const int32_t *actions,
-                 const float *rewards, const float *next_states, int64_t capacity, const int64_t *indices,
-                 const float *weights, const float *discounts, float *td_delta, float *row, void *stream,
-                 const ClipArgs *clip = nullptr)
-{
-    if (!learner) return fail("%s: null handle", fn);
-    if (!states || !actions || !rewards || !next_states)
-        return fail("%s: states, actions, rewards and next_states must not be null", fn);
-    if (!td_delta || !row) return fail("%s: td_delta and row must not be null", fn);
-    if (accept_batch(fn, learner, n, capacity, indices, "from") || accept_entropy_rows(fn, learner, n) ||
-        accept_advantage_rows(fn, learner, n))
-        return 1;
-    ON_DEVICE(learner->cfg.device_id);
-    LearnerLaunch q = learner_batch(n, states, actions, rewards, next_states, capacity, indices, weights, discounts, td_delta);
-    if (clip && accept_clip(fn, learner, clip->log_mu, clip->clip_eps, clip->ratio_out, q)) return 1;
-    HIP_TRY(launch_learner_grad(learner->d, q, row, static_cast<hipStream_t>(stream)));
-    return 0;
-}
-
-}  // namespace
-
-extern "C" {
-
 int uavtrack_learner_update(uavtrack_learner *learner, int64_t n, const float *states, const int32_t *actions,
                             const float *rewards, const float *next_states, int64_t capacity, const int64_t *indices,
                             float *actor_loss, float *critic_loss, float *td_delta, float *priorities, void *stream)
 {
-    return learner_update(__func__, learner, n, states, actions, rewards, next_states, capacity, indices, nullptr, nullptr,
-                          actor_loss, critic_loss, td_delta, priorities, stream);
+    LearnerLaunch q = {n, capacity, states, rewards, next_states, actions, indices};
+    q.actor_loss = actor_loss; q.critic_loss = critic_loss; q.td_delta = td_delta; q.priorities = priorities;
+    return run_learner_batch(__func__, learner, q, Batch::Update, nullptr, stream);
 }
 
 int uavtrack_learner_update_weighted(uavtrack_learner *learner, int64_t n, const float *states, const int32_t *actions,
@@ -322,8 +304,9 @@ int uavtrack_learner_update_weighted(uavtrack_learner *learner, int64_t n, const
                                      const int64_t *indices, const float *weights, float *actor_loss, float *critic_loss,
                                      float *td_delta, float *priorities, void *stream)
 {
-    return learner_update(__func__, learner, n, states, actions, rewards, next_states, capacity, indices, weights, nullptr,
-                          actor_loss, critic_loss, td_delta, priorities, stream);
+    LearnerLaunch q = {n, capacity, states, rewards, next_states, actions, indices, weights};
+    q.actor_loss = actor_loss; q.critic_loss = critic_loss; q.td_delta = td_delta; q.priorities = priorities;
+    return run_learner_batch(__func__, learner, q, Batch::Update, nullptr, stream);
 }
 
 int uavtrack_learner_update_discounted(uavtrack_learner *learner, int64_t n, const float *states, const int32_t *actions,
@@ -332,8 +315,9 @@ int uavtrack_learner_update_discounted(uavtrack_learner *learner, int64_t n, con
                                        float *actor_loss, float *critic_loss, float *td_delta, float *priorities,
                                        void *stream)
 {
-    return learner_update(__func__, learner, n, states, actions, rewards, next_states, capacity, indices, weights, discounts,
-                          actor_loss, critic_loss, td_delta, priorities, stream);
+    LearnerLaunch q = {n, capacity, states, rewards, next_states, actions, indices, weights, discounts};
+    q.actor_loss = actor_loss; q.critic_loss = critic_loss; q.td_delta = td_delta; q.priorities = priorities;
+    return run_learner_batch(__func__, learner, q, Batch::Update, nullptr, stream);
 }
 
 int uavtrack_learner_update_clipped(uavtrack_learner *learner, int64_t n, const float *states, const int32_t *actions,
@@ -342,9 +326,10 @@ int uavtrack_learner_update_clipped(uavtrack_learner *learner, int64_t n, const 
                                     const float *log_mu, double clip_eps, float *ratio_out, float *actor_loss,
                                     float *critic_loss, float *td_delta, float *priorities, void *stream)
 {
-    const ClipArgs clip = {log_mu, clip_eps, ratio_out};
-    return learner_update(__func__, learner, n, states, actions, rewards, next_states, capacity, indices, weights, discounts,
-                          actor_loss, critic_loss, td_delta, priorities, stream, &clip);
+    LearnerLaunch q = {n, capacity, states, rewards, next_states, actions, indices, weights, discounts};
+    q.clipped = true; q.log_mu = log_mu; q.clip_eps = clip_eps; q.ratio = ratio_out;
+    q.actor_loss = actor_loss; q.critic_loss = critic_loss; q.td_delta = td_delta; q.priorities = priorities;
+    return run_learner_batch(__func__, learner, q, Batch::Update, nullptr, stream);
 }
 
 int uavtrack_learner_row_floats(uavtrack_learner *learner, int64_t *out)
@@ -358,16 +343,18 @@ int uavtrack_learner_grad(uavtrack_learner *learner, int64_t n, const float *sta
                           const float *rewards, const float *next_states, int64_t capacity, const int64_t *indices,
                           float *td_delta, float *row, void *stream)
 {
-    return learner_grad(__func__, learner, n, states, actions, rewards, next_states, capacity, indices, nullptr, nullptr,
-                        td_delta, row, stream);
+    LearnerLaunch q = {n, capacity, states, rewards, next_states, actions, indices};
+    q.td_delta = td_delta;
+    return run_learner_batch(__func__, learner, q, Batch::Grad, row, stream);
 }
 
 int uavtrack_learner_grad_weighted(uavtrack_learner *learner, int64_t n, const float *states, const int32_t *actions,
                                    const float *rewards, const float *next_states, int64_t capacity,
                                    const int64_t *indices, const float *weights, float *td_delta, float *row, void *stream)
 {
-    return learner_grad(__func__, learner, n, states, actions, rewards, next_states, capacity, indices, weights, nullptr,
-                        td_delta, row, stream);
+    LearnerLaunch q = {n, capacity, states, rewards, next_states, actions, indices, weights};
+    q.td_delta = td_delta;
+    return run_learner_batch(__func__, learner, q, Batch::Grad, row, stream);
 }
 
 int uavtrack_learner_grad_discounted(uavtrack_learner *learner, int64_t n, const float *states, const int32_t *actions,
@@ -375,8 +362,9 @@ int uavtrack_learner_grad_discounted(uavtrack_learner *learner, int64_t n, const
                                      const int64_t *indices, const float *weights, const float *discounts, float *td_delta,
                                      float *row, void *stream)
 {
-    return learner_grad(__func__, learner, n, states, actions, rewards, next_states, capacity, indices, weights, discounts,
-                        td_delta, row, stream);
+    LearnerLaunch q = {n, capacity, states, rewards, next_states, actions, indices, weights, discounts};
+    q.td_delta = td_delta;
+    return run_learner_batch(__func__, learner, q, Batch::Grad, row, stream);
 }
 
 int uavtrack_learner_grad_clipped(uavtrack_learner *learner, int64_t n, const float *states, const int32_t *actions,
@@ -384,9 +372,10 @@ int uavtrack_learner_grad_clipped(uavtrack_learner *learner, int64_t n, const fl
                                   const float *weights, const float *discounts, const float *log_mu, double clip_eps,
                                   float *ratio_out, float *td_delta, float *row, void *stream)
 {
-    const ClipArgs clip = {log_mu, clip_eps, ratio_out};
-    return learner_grad(__func__, learner, n, states, actions, rewards, next_states, capacity, indices, weights, discounts,
-                        td_delta, row, stream, &clip);
+    LearnerLaunch q = {n, capacity, states, rewards, next_states, actions, indices, weights, discounts};
+    q.clipped = true; q.log_mu = log_mu; q.clip_eps = clip_eps; q.ratio = ratio_out;
+    q.td_delta = td_delta;
+    return run_learner_batch(__func__, learner, q, Batch::Grad, row, stream);
 }
 
 int uavtrack_learner_apply(uavtrack_learner *learner, const float *rows, int64_t count, float *actor_loss,
@@ -416,14 +405,7 @@ int uavtrack_learner_write_priorities(uavtrack_learner *learner, int64_t n, cons
 
 int uavtrack_learner_values(uavtrack_learner *learner, int64_t n, const float *rows, float *values, void *stream)
 {
-    if (!learner) return fail("%s: null handle", __func__);
-    if (!rows || !values) return fail("%s: rows and values must not be null", __func__);
-    if (n < 1) return fail("%s: n = %lld < 1", __func__, (long long)n);
-    if (n > INT64_MAX / 48) return fail("%s: n = %lld rows overflow", __func__, (long long)n);
-    if (((uintptr_t)rows & 15) != 0) return fail("%s: rows must be 16-byte aligned", __func__);
-    ON_DEVICE(learner->cfg.device_id);
-    HIP_TRY(launch_learner_values(learner->d, false, n, rows, values, static_cast<hipStream_t>(stream)));
-    return 0;
+    return learner_values(__func__, learner, false, n, rows, values, stream);
 }
 
 // ---- the normalised advantage
@@ -483,8 +465,7 @@ int uavtrack_learner_set_target(uavtrack_learner *learner, int32_t mode, double 
         // off -> on: the block (once per handle), then a hard copy of the critic as it stands, stream-ordered
         ON_DEVICE(learner->cfg.device_id);
         if (!d.target) HIP_TRY(replace(target_bufs(d)));
-        HIP_TRY(hipMemcpyAsync(d.target, d.params + d.L.c_w1, sizeof(float) * (size_t)learner_critic_words(d.L),
-                               hipMemcpyDeviceToDevice, static_cast<hipStream_t>(stream)));
+        HIP_TRY(copy_critic_to_target(d, stream));
     }
     d.target_mode = mode;
     d.target_tau = mode == UAVTRACK_TARGET_POLYAK ? (float)tau : 0.0f;
@@ -507,8 +488,7 @@ int uavtrack_learner_sync_target(uavtrack_learner *learner, void *stream)
     const LearnerDevice &d = learner->d;
     if (!d.target_mode) return fail("%s: no target critic is enabled (uavtrack_learner_set_target)", __func__);
     ON_DEVICE(learner->cfg.device_id);
-    HIP_TRY(hipMemcpyAsync(d.target, d.params + d.L.c_w1, sizeof(float) * (size_t)learner_critic_words(d.L),
-                           hipMemcpyDeviceToDevice, static_cast<hipStream_t>(stream)));
+    HIP_TRY(copy_critic_to_target(d, stream));
     return 0;
 }
 
@@ -553,15 +533,7 @@ int uavtrack_learner_get_target_params(uavtrack_learner *learner, float *params,
 
 int uavtrack_learner_values_target(uavtrack_learner *learner, int64_t n, const float *rows, float *values, void *stream)
 {
-    if (!learner) return fail("%s: null handle", __func__);
-    if (!rows || !values) return fail("%s: rows and values must not be null", __func__);
-    if (n < 1) return fail("%s: n = %lld < 1", __func__, (long long)n);
-    if (n > INT64_MAX / 48) return fail("%s: n = %lld rows overflow", __func__, (long long)n);
-    if (((uintptr_t)rows & 15) != 0) return fail("%s: rows must be 16-byte aligned", __func__);
-    if (!learner->d.target_mode) return fail("%s: no target critic is enabled (uavtrack_learner_set_target)", __func__);
-    ON_DEVICE(learner->cfg.device_id);
-    HIP_TRY(launch_learner_values(learner->d, true, n, rows, values, static_cast<hipStream_t>(stream)));
-    return 0;
+    return learner_values(__func__, learner, true, n, rows, values, stream);
 }
 
 }  // extern "C"

@@ -80,6 +80,8 @@ struct LearnerDevice {
     double *adv_part;               // [2][learner_adv_chunks(max_n)] the chunks' sums of delta, then of squared deviations
 };
 enum { kAdvantageRaw = 0, kAdvantageBatch = 1, kAdvantageGiven = 2 };
+// One batch of uavtrack_learner_update / _grad in any of their forms.  The eight entry points fill it as they were
+// called (the first nine fields in this order, by aggregate initialisation); what a form does not take stays zero.
 struct LearnerLaunch {
     int64_t n, capacity;
     const float *states, *rewards, *next_states;
@@ -87,6 +89,8 @@ struct LearnerLaunch {
     const int64_t *idx;
     const float *weights;           // nullable [n]: importance weights in batch order
     const float *discounts;         // nullable [capacity]: per-slot discounts (null: the handle's gamma for every row)
+    bool clipped;                   // a _clipped entry point: log_mu is required, clip_eps is tested
+    double clip_eps;                // as given; an accepted launch carries it folded into clip_lo / clip_hi
     const float *log_mu;            // nullable [capacity]: per-slot behaviour log-probabilities; non-null: the clipped surrogate
     float clip_lo, clip_hi;         // its bounds 1 - eps and 1 + eps in fp32 (read only with log_mu)
     float *ratio;                   // nullable [n]: its ratios in batch order (read only with log_mu)

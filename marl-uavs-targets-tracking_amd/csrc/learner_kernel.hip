@@ -68,10 +68,15 @@
 // 256-row chunk's fp64 sum, learner_adv_sq_kernel each chunk's sum of squared deviations, learner_adv_stats_kernel the
 // three floats; learner_adv_seal_kernel, behind the gradient kernel, turns them into NaN where the update was refused.
 //
+// Which of the ten instantiations of the gradient body a launch takes is learner_variants.h's table and its
+// learner_grad_variant; the host code below expands the same table over the kernels (kGradKernels), prepares every row's
+// LDS attribute from it and launches through it, each kernel receiving the filled GradAdvArgs cut down to its own type.
+//
 // The critic alone (uavtrack_learner_values): learner_values_kernel, at the end of the kernels below, evaluates V(x) of
 // any number of rows by the chain of the layer-1 and layer-2 loops above, to the bit, and touches no learner state.
 
 #include "learner.h"
+#include "learner_variants.h"
 
 #include <hip/hip_runtime.h>
 #include <cmath>
@@ -862,33 +867,32 @@ int learner_groups(const LearnerLayout &L, int64_t n)
 
 int learner_clip_groups(const LearnerLayout &L) { return (L.P + kClipThreads - 1) / kClipThreads; }
 
+namespace {
+
+// One launch of a gradient kernel: the fully filled arguments, cut down to the kernel's own parameter type.
+template <typename Args, void (*kKernel)(Args)>
+void launch_variant(dim3 grid, size_t lds, hipStream_t st, const GradAdvArgs &a)
+{
+    hipLaunchKernelGGL(kKernel, grid, dim3(kLW), lds, st, static_cast<const Args &>(a));
+}
+
+// learner_variants.h's table over the kernels themselves, in its order
+struct GradKernel {
+    const void *kernel;
+    void (*launch)(dim3 grid, size_t lds, hipStream_t st, const GradAdvArgs &a);
+};
+#define GRAD_KERNEL_ROW(k, Args, reg, tgt, clip, adv, lds) {reinterpret_cast<const void *>(k), launch_variant<Args, k>},
+const GradKernel kGradKernels[kLearnerGradVariantCount] = {UAVTRACK_LEARNER_GRAD_VARIANTS(GRAD_KERNEL_ROW)};
+#undef GRAD_KERNEL_ROW
+
+}  // namespace
+
 hipError_t learner_prepare_kernels(const LearnerLayout &L)
 {
     // every instantiation of the gradient body needs the attribute of its own: up to about 131 KB at H = 256
-    const size_t lds = learner_lds_bytes(L, learner_rows_per_tile(L.H));
-    for (const void *k : {reinterpret_cast<const void *>(learner_grad_kernel),
-                          reinterpret_cast<const void *>(learner_grad_reg_kernel),
-                          reinterpret_cast<const void *>(learner_grad_target_kernel),
-                          reinterpret_cast<const void *>(learner_grad_reg_target_kernel)}) {
-        const hipError_t e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-    }
-    // the clipped surrogate's two keep log_mu of the tile in R more floats
-    const size_t clds = learner_lds_bytes(L, learner_rows_per_tile(L.H), true);
-    for (const void *k : {reinterpret_cast<const void *>(learner_grad_clip_kernel),
-                          reinterpret_cast<const void *>(learner_grad_clip_target_kernel)}) {
-        const hipError_t e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)clds);
-        if (e != hipSuccess) return e;
-    }
-    // the normalised advantage's four: what their siblings ask for
-    for (const void *k : {reinterpret_cast<const void *>(learner_grad_adv_kernel),
-                          reinterpret_cast<const void *>(learner_grad_adv_target_kernel)}) {
-        const hipError_t e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-    }
-    for (const void *k : {reinterpret_cast<const void *>(learner_grad_adv_clip_kernel),
-                          reinterpret_cast<const void *>(learner_grad_adv_clip_target_kernel)}) {
-        const hipError_t e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)clds);
+    for (int i = 0; i < kLearnerGradVariantCount; ++i) {
+        const size_t lds = learner_lds_bytes(L, learner_rows_per_tile(L.H), kLearnerGradVariants[i].clipped_lds);
+        const hipError_t e = hipFuncSetAttribute(kGradKernels[i].kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (e != hipSuccess) return e;
     }
     return hipSuccess;
@@ -904,7 +908,8 @@ hipError_t launch_grad(const LearnerDevice &d, const LearnerLaunch &q, float *td
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
 
-    GradClipArgs a;
+    const bool batch = d.adv_mode == kAdvantageBatch;
+    GradAdvArgs a;
     a.params = d.params; a.states = q.states; a.rewards = q.rewards; a.next_states = q.next_states;
     a.actions = q.actions; a.idx = q.idx; a.weights = q.weights; a.n = q.n; a.capacity = q.capacity;
     a.partials = d.partials; a.td_delta = td; a.status = status;
@@ -912,46 +917,30 @@ hipError_t launch_grad(const LearnerDevice &d, const LearnerLaunch &q, float *td
     a.entropy_coef = d.entropy_coef; a.entropy = d.entropy; a.discounts = q.discounts;
     a.target = d.target_mode ? d.target : nullptr;
     a.log_mu = q.log_mu; a.clip_lo = q.clip_lo; a.clip_hi = q.clip_hi; a.ratio = q.ratio;
-    const bool reg = d.entropy_coef != 0.0f || d.entropy;
-    const bool clipped = q.log_mu != nullptr;
-    auto *kernel = a.target ? (reg ? learner_grad_reg_target_kernel : learner_grad_target_kernel)
-                            : (reg ? learner_grad_reg_kernel : learner_grad_kernel);
-    const dim3 grid(learner_groups(L, q.n));
-    if (d.adv_mode != kAdvantageRaw) {
-        // the normalised advantage: in batch mode the TD pass and the statistics first, the seal behind
-        const bool batch = d.adv_mode == kAdvantageBatch;
-        GradAdvArgs v;
-        static_cast<GradClipArgs &>(v) = a;
-        v.stats = batch ? d.stats() : d.adv_given;
-        if (batch) {
-            const int64_t chunks = learner_adv_chunks(q.n);
-            const dim3 cgrid((unsigned)(chunks < 1024 ? chunks : 1024));
-            double *psum = d.adv_part, *psq = d.adv_part + learner_adv_chunks(d.max_n);
-            TdArgs t;
-            t.critic = d.params + L.c_w1; t.target = a.target ? a.target : t.critic;
-            t.states = q.states; t.rewards = q.rewards; t.next_states = q.next_states; t.idx = q.idx;
-            t.discounts = q.discounts; t.n = q.n; t.capacity = q.capacity; t.H = L.H; t.gamma = d.gamma;
-            t.td = d.adv_td; t.psum = psum;
-            hipLaunchKernelGGL(learner_td_kernel, cgrid, dim3(kAdvChunk), 0, st, t);
-            if ((e = hipGetLastError()) != hipSuccess) return e;
-            hipLaunchKernelGGL(learner_adv_sq_kernel, cgrid, dim3(kAdvChunk), 0, st, d.adv_td, q.n, psum, psq);
-            if ((e = hipGetLastError()) != hipSuccess) return e;
-            hipLaunchKernelGGL(learner_adv_stats_kernel, dim3(1), dim3(64), 0, st, psum, psq, q.n, d.adv_eps, d.stats());
-            if ((e = hipGetLastError()) != hipSuccess) return e;
-        }
-        auto *adv = clipped ? (a.target ? learner_grad_adv_clip_target_kernel : learner_grad_adv_clip_kernel)
-                            : (a.target ? learner_grad_adv_target_kernel : learner_grad_adv_kernel);
-        hipLaunchKernelGGL(adv, grid, dim3(kLW), learner_lds_bytes(L, R, clipped), st, v);
-        if ((e = hipGetLastError()) != hipSuccess || !batch) return e;
-        hipLaunchKernelGGL(learner_adv_seal_kernel, dim3(1), dim3(64), 0, st, status, d.stats());
-        return hipGetLastError();
+    a.stats = batch ? d.stats() : d.adv_given;
+    const int variant = learner_grad_variant(d.entropy_coef != 0.0f || d.entropy, a.target != nullptr, q.log_mu != nullptr,
+                                             d.adv_mode != kAdvantageRaw);
+    if (batch) {
+        // the normalised advantage in batch mode: the TD pass and the statistics first, the seal behind
+        const int64_t chunks = learner_adv_chunks(q.n);
+        const dim3 cgrid((unsigned)(chunks < 1024 ? chunks : 1024));
+        double *psum = d.adv_part, *psq = d.adv_part + learner_adv_chunks(d.max_n);
+        TdArgs t;
+        t.critic = d.params + L.c_w1; t.target = a.target ? a.target : t.critic;
+        t.states = q.states; t.rewards = q.rewards; t.next_states = q.next_states; t.idx = q.idx;
+        t.discounts = q.discounts; t.n = q.n; t.capacity = q.capacity; t.H = L.H; t.gamma = d.gamma;
+        t.td = d.adv_td; t.psum = psum;
+        hipLaunchKernelGGL(learner_td_kernel, cgrid, dim3(kAdvChunk), 0, st, t);
+        if ((e = hipGetLastError()) != hipSuccess) return e;
+        hipLaunchKernelGGL(learner_adv_sq_kernel, cgrid, dim3(kAdvChunk), 0, st, d.adv_td, q.n, psum, psq);
+        if ((e = hipGetLastError()) != hipSuccess) return e;
+        hipLaunchKernelGGL(learner_adv_stats_kernel, dim3(1), dim3(64), 0, st, psum, psq, q.n, d.adv_eps, d.stats());
+        if ((e = hipGetLastError()) != hipSuccess) return e;
     }
-    if (clipped) {
-        hipLaunchKernelGGL(a.target ? learner_grad_clip_target_kernel : learner_grad_clip_kernel, grid, dim3(kLW),
-                           learner_lds_bytes(L, R, true), st, a);
-        return hipGetLastError();
-    }
-    hipLaunchKernelGGL(kernel, grid, dim3(kLW), learner_lds_bytes(L, R), st, static_cast<const GradArgs &>(a));
+    kGradKernels[variant].launch(dim3(learner_groups(L, q.n)), learner_lds_bytes(L, R, kLearnerGradVariants[variant].clipped_lds),
+                                 st, a);
+    if ((e = hipGetLastError()) != hipSuccess || !batch) return e;
+    hipLaunchKernelGGL(learner_adv_seal_kernel, dim3(1), dim3(64), 0, st, status, d.stats());
     return hipGetLastError();
 }
 

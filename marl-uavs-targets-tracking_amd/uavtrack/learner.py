@@ -104,9 +104,12 @@ from .replay import DrawSpec
 from .rollout import ActorMLP
 
 
-# one drawn batch, as _run takes it
-_Drawn = namedtuple("_Drawn", "n store capacity idx priorities weights discounts log_mu clip_eps ratio_out",
-                    defaults=(None, None, None))
+# One batch as _run_batch, _grad_batch and _launch take it: n rows of a store of `capacity` slots (its dict of states,
+# actions, rewards, next_states) through idx (None: rows 0..n-1), the priorities to write back, the weights per batch row, and
+# per slot of the store the discounts and the behaviour log-probabilities (read with clip_eps, and by _ratio_weights);
+# ratio_out per batch row.
+_Batch = namedtuple("_Batch", "n store capacity idx priorities weights discounts log_mu clip_eps ratio_out",
+                    defaults=(None,) * 6)
 
 
 def num_params(hidden_dim: int, action_dim: int) -> int:
@@ -138,6 +141,7 @@ class DeviceActorCritic(Handle):
     """ActorCritic(state_dim, hidden_dim, action_dim, actor_lr, critic_lr, gamma, device) with the update on the GPU.
     Initial weights are torch.nn.Linear's defaults drawn from torch's global generator, like the reference's."""
     _prefix = "uavtrack_learner_"
+    _Batch = _Batch                                                   # for a caller of _corrected / _ratio_weights
 
     def __init__(self, state_dim: int = 12, hidden_dim: int = 128, action_dim: int = 12, actor_lr: float = 1e-4,
                  critic_lr: float = 5e-4, gamma: float = 0.95, device="cuda:0", loss: str = "reference",
@@ -415,10 +419,10 @@ class DeviceActorCritic(Handle):
                                                                int(n), _ptr(log_mu), self._stream()),
                    "uavtrack_learner_log_probs_window")
 
-    def _ratio_weights(self, n: int, store: Dict[str, torch.Tensor], log_mu: torch.Tensor, capacity: int,
-                       idx: Optional[torch.Tensor], rho_bar: float, w_in: Optional[torch.Tensor], w_out: torch.Tensor,
+    def _ratio_weights(self, b: _Batch, rho_bar: float, w_out: torch.Tensor,
                        rho_out: Optional[torch.Tensor]) -> torch.Tensor:
-        """uavtrack_learner_ratio_weights: w_out[i] = (w_in[i] or 1) * min(rho_bar, pi / mu of batch row i)."""
+        """uavtrack_learner_ratio_weights: w_out[i] = (b.weights[i] or 1) * min(rho_bar, pi / mu of batch row i)."""
+        n, store, capacity, idx, _, w_in, _, log_mu = b[:8]
         _lib.tensor_arg(log_mu, torch.float32, capacity, self.device,
                         f"log_mu must be a contiguous float32 tensor of {capacity} elements (one per slot of the store) on "
                         f"{self.device}")
@@ -429,22 +433,35 @@ class DeviceActorCritic(Handle):
             _ptr(w_in), _ptr(w_out), _ptr(rho_out), self._stream()), "uavtrack_learner_ratio_weights")
         return w_out
 
-    def _ratios_from(self, buffer, k: int, idx: Optional[torch.Tensor], w: Optional[torch.Tensor],
-                     spec: DrawSpec) -> Optional[torch.Tensor]:
-        """The weights a draw of k rows trains with: w as drawn when spec.rho_bar is None, else w (or 1) times the
-        truncated ratios of the buffer's behaviour store, where the ring keeps them (_ratio_out)."""
-        if spec.rho_bar is None:
-            if spec.rho_out is not None:
-                raise ValueError("rho_out needs rho_bar")
-            return w
-        if spec.clip_eps is not None:
-            raise ValueError("clip_eps together with rho_bar: one correction for who acted, not two")
-        log_mu = getattr(buffer, "log_mu", None)          # an object that is no buffer gets the same answer
-        if log_mu is None:
-            raise ValueError("rho_bar needs the buffer's behaviour log-probabilities: a ReplayRing or PrioritizedReplayRing "
-                             "made ring.with_behaviour()")
-        return self._ratio_weights(k, buffer.store, log_mu, buffer.capacity, idx, spec.rho_bar, w, buffer._ratio_out(k),
-                                   spec.rho_out)
+    _NEEDS_BEHAVIOUR = "needs the buffer's behaviour log-probabilities: a ReplayRing or PrioritizedReplayRing made " \
+                       "ring.with_behaviour()"
+
+    def _corrected(self, b: _Batch, rho_bar: Optional[float], rho_out: Optional[torch.Tensor], w_out, who: str = "") -> _Batch:
+        """The batch as it trains under its correction for who acted.  b arrives with the behaviour log-probabilities at
+        hand (a ring's per-slot store, update()'s argument, or None) and the weights as drawn; it leaves with w (or 1)
+        times the truncated ratios into w_out(n) for weights under rho_bar (log_mu stays; _launch reads it under clip_eps
+        alone).  `who` is "update: " for update(), whose log_mu is an argument of its own and comes with exactly one of
+        the two."""
+        log_mu, clip_eps, ratio_out = b[7:]
+        if rho_bar is None and rho_out is not None:
+            raise ValueError("rho_out needs rho_bar")
+        if rho_bar is not None and clip_eps is not None:
+            raise ValueError(f"{who}clip_eps together with rho_bar: one correction for who acted, not two")
+        if who and (log_mu is None) != (rho_bar is None and clip_eps is None):
+            raise ValueError("update: log_mu and rho_bar come together (log_mu comes with exactly one of rho_bar and "
+                             "clip_eps)")
+        if rho_bar is not None and log_mu is None:
+            raise ValueError(f"rho_bar {self._NEEDS_BEHAVIOUR}")
+        if clip_eps is not None:
+            self._clip_eps_arg(clip_eps)
+            if log_mu is None:
+                raise ValueError(f"clip_eps {self._NEEDS_BEHAVIOUR}")
+            return b
+        if ratio_out is not None:
+            raise ValueError(f"{who}ratio_out needs clip_eps")
+        if rho_bar is None:
+            return b
+        return _Batch._make((*b[:5], self._ratio_weights(b, rho_bar, w_out(b.n), rho_out), *b[6:]))   # (_replace: 1 us)
 
     # ---- the update
     @staticmethod
@@ -452,20 +469,20 @@ class DeviceActorCritic(Handle):
         """A batch as uavtrack_learner_update and _grad take it: the store's four arrays, its capacity, the indices."""
         return (*(_ptr(store[k]) for k in ("states", "actions", "rewards", "next_states")), capacity, _ptr(idx))
 
-    def _drawn_batch(self, buffer, batch_size: int, spec: DrawSpec, caller: str) -> _Drawn:
+    def _drawn_batch(self, buffer, batch_size: int, spec: DrawSpec, caller: str) -> _Batch:
         """min(batch_size, buffer.count) rows drawn as the buffer's own sample() draws them (_draw_batch), the weights
         they train with, and the buffer's per-slot discounts, which must have been folded with this learner's gamma."""
         k = min(int(batch_size), buffer.count)
         if k < 1:
             raise ValueError(f"{caller}: the buffer is empty")
         idx, w = buffer._draw_batch(k, spec)
-        w = self._ratios_from(buffer, k, idx, w, spec)
-        log_mu = self._clip_store(buffer, spec)
-        d = buffer.discounts
-        if d is not None and np.float32(buffer.gamma) != np.float32(self.gamma):
+        b = self._corrected(_Batch(k, buffer.store, buffer.capacity, idx, buffer.priorities, w, buffer.discounts,
+                                   getattr(buffer, "log_mu", None),   # an object that is no buffer gets the same answer
+                                   spec.clip_eps, spec.ratio_out), spec.rho_bar, spec.rho_out, getattr(buffer, "_ratio_out", None))
+        if b.discounts is not None and np.float32(buffer.gamma) != np.float32(self.gamma):
             raise ValueError(f"the buffer's returns were folded with gamma = {buffer.gamma}, the learner bootstraps with "
                              f"gamma = {self.gamma}: both must be the same float32")
-        return _Drawn(k, buffer.store, buffer.capacity, idx, buffer.priorities, w, d, log_mu, spec.clip_eps, spec.ratio_out)
+        return b
 
     def _clip_eps_arg(self, clip_eps) -> float:
         """clip_eps as the library takes it: >= 0, inf allowed, on a per-sample learner."""
@@ -477,25 +494,11 @@ class DeviceActorCritic(Handle):
             raise ValueError(f"clip_eps = {clip_eps!r} must be >= 0 (inf never clips)")
         return eps
 
-    def _clip_store(self, buffer, spec: DrawSpec) -> Optional[torch.Tensor]:
-        """The buffer's behaviour store where spec asks for the clipped surrogate, else None."""
-        if spec.clip_eps is None:
-            if spec.ratio_out is not None:
-                raise ValueError("ratio_out needs clip_eps")
-            return None
-        self._clip_eps_arg(spec.clip_eps)
-        log_mu = getattr(buffer, "log_mu", None)
-        if log_mu is None:
-            raise ValueError("clip_eps needs the buffer's behaviour log-probabilities: a ReplayRing or PrioritizedReplayRing "
-                             "made ring.with_behaviour()")
-        return log_mu
-
-    def _launch(self, kind: str, n: int, store: Dict[str, torch.Tensor], capacity: int, idx: Optional[torch.Tensor],
-                weights: Optional[torch.Tensor], discounts: Optional[torch.Tensor], *outputs, clip=None) -> None:
+    def _launch(self, kind: str, b: _Batch, *outputs) -> None:
         """uavtrack_learner_<kind> ("update" or "grad") in the form the batch takes: plain, _weighted (weights, one per
-        batch row), _discounted (weights or NULL, then discounts, one per slot of the store) or, with clip = (log_mu,
-        clip_eps, ratio_out), _clipped (weights or NULL, discounts or NULL, log_mu per slot, eps, ratios or NULL); then
-        the outputs."""
+        batch row), _discounted (weights or NULL, then discounts, one per slot of the store) or, with clip_eps,
+        _clipped (weights or NULL, discounts or NULL, log_mu per slot, eps, ratios or NULL); then the outputs."""
+        n, store, capacity, idx, _, weights, discounts, log_mu, clip_eps, ratio_out = b
         if isinstance(self._advantage, str) and self._advantage == "batch" and n < 2:
             raise ValueError(f'n = {n} row under set_advantage("batch"): the standard deviation of a batch needs two rows')
         w = _lib.tensor_arg(weights, torch.float32, n, self.device,
@@ -506,8 +509,7 @@ class DeviceActorCritic(Handle):
                             f"store) on {self.device}")
         suffix, extra = ("_discounted", (_ptr(w), _ptr(d))) if d is not None else \
             ("", ()) if w is None else ("_weighted", (_ptr(w),))
-        if clip is not None:
-            log_mu, clip_eps, ratio_out = clip
+        if clip_eps is not None:
             _lib.tensor_arg(log_mu, torch.float32, capacity, self.device,
                             f"log_mu must be a contiguous float32 tensor of {capacity} elements (one per slot of the "
                             f"store) on {self.device}")
@@ -519,15 +521,15 @@ class DeviceActorCritic(Handle):
         _lib.check(getattr(self._lib, name)(self._h, n, *self._batch_args(store, capacity, idx), *extra,
                                             *map(_ptr, outputs), self._stream()), name)
 
-    def _run(self, n: int, store: Dict[str, torch.Tensor], capacity: int, idx: Optional[torch.Tensor],
-             priorities: Optional[torch.Tensor], weights: Optional[torch.Tensor] = None,
-             discounts: Optional[torch.Tensor] = None, log_mu: Optional[torch.Tensor] = None,
-             clip_eps: Optional[float] = None, ratio_out: Optional[torch.Tensor] = None):
+    def _run_batch(self, b: _Batch):
         losses = torch.empty(2, device=self.device)
-        td = torch.empty(n, device=self.device)
-        self._launch("update", n, store, capacity, idx, weights, discounts, losses[0:1], losses[1:2], td, priorities,
-                     clip=None if clip_eps is None else (log_mu, clip_eps, ratio_out))
+        td = torch.empty(b.n, device=self.device)
+        self._launch("update", b, losses[0:1], losses[1:2], td, b.priorities)
         return losses[0], losses[1], td
+
+    def _run(self, *batch):
+        """_run_batch of a batch spelled out in _Batch's order, for a caller that holds no record (tests, tools)."""
+        return self._run_batch(_Batch(*batch))
 
     def update(self, transition_dict: Dict[str, torch.Tensor], weights: Optional[torch.Tensor] = None,
                discounts: Optional[torch.Tensor] = None, log_mu: Optional[torch.Tensor] = None,
@@ -544,15 +546,6 @@ class DeviceActorCritic(Handle):
         weighted update).  clip_eps >= 0 (loss="per_sample"): the clipped surrogate of the module docstring
         (uavtrack_learner_update_clipped), ratio_out [n] (optional) receiving the ratios.  Either way a NaN or positive
         log_mu refuses the update on the device."""
-        if rho_bar is not None and clip_eps is not None:
-            raise ValueError("update: clip_eps together with rho_bar: one correction for who acted, not two")
-        if (log_mu is None) != (rho_bar is None and clip_eps is None):
-            raise ValueError("update: log_mu and rho_bar come together (log_mu comes with exactly one of rho_bar and "
-                             "clip_eps)")
-        if ratio_out is not None and clip_eps is None:
-            raise ValueError("update: ratio_out needs clip_eps")
-        if clip_eps is not None:
-            self._clip_eps_arg(clip_eps)
         dev = self.device
         s = torch.as_tensor(transition_dict["states"], device=dev, dtype=torch.float32).reshape(-1, _lib.OBS_DIM).contiguous()
         n = s.shape[0]
@@ -567,10 +560,8 @@ class DeviceActorCritic(Handle):
             discounts = torch.as_tensor(discounts, device=dev, dtype=torch.float32).reshape(-1).contiguous()
         if log_mu is not None:
             log_mu = torch.as_tensor(log_mu, device=dev, dtype=torch.float32).reshape(-1).contiguous()
-        if rho_bar is not None:
-            weights = self._ratio_weights(n, store, log_mu, n, None, rho_bar, weights, torch.empty(n, device=dev), None)
-            return self._run(n, store, n, None, None, weights, discounts)
-        return self._run(n, store, n, None, None, weights, discounts, log_mu, clip_eps, ratio_out)
+        return self._run_batch(self._corrected(_Batch(n, store, n, None, None, weights, discounts, log_mu, clip_eps, ratio_out),
+                                               rho_bar, None, lambda n: torch.empty(n, device=dev), "update: "))
 
     def update_from(self, buffer, batch_size: int, beta: float = 0.4,
                     generator: Optional[torch.Generator] = None, group=None, importance: bool = False,
@@ -595,7 +586,7 @@ class DeviceActorCritic(Handle):
         spec = DrawSpec(importance=importance, beta=beta, beta_final=beta_final, anneal_calls=anneal_calls,
                         rho_bar=rho_bar, rho_out=rho_out, generator=generator, clip_eps=clip_eps, ratio_out=ratio_out)
         if group is None:
-            return self._run(*self._drawn_batch(buffer, batch_size, spec, "update_from"))
+            return self._run_batch(self._drawn_batch(buffer, batch_size, spec, "update_from"))
         from .sharding import gather_learner_rows
         al, cl, (td,) = self._update_split([buffer], batch_size, [spec], lambda rows: gather_learner_rows(rows, group))
         return al, cl, td
@@ -605,20 +596,19 @@ class DeviceActorCritic(Handle):
         """A [count, row_floats] device tensor for `count` gradient rows (pass rows[k] to grad_from as `row`)."""
         return torch.empty(int(count), self.row_floats, device=self.device)
 
-    def _grad(self, n: int, store: Dict[str, torch.Tensor], capacity: int, idx: Optional[torch.Tensor],
-              row: Optional[torch.Tensor] = None, td: Optional[torch.Tensor] = None,
-              weights: Optional[torch.Tensor] = None, discounts: Optional[torch.Tensor] = None,
-              log_mu: Optional[torch.Tensor] = None, clip_eps: Optional[float] = None,
-              ratio_out: Optional[torch.Tensor] = None):
+    def _grad_batch(self, b: _Batch, row: Optional[torch.Tensor] = None, td: Optional[torch.Tensor] = None):
         if row is None:
             row = torch.empty(self.row_floats, device=self.device)
         _lib.tensor_arg(row, torch.float32, self.row_floats, self.device,
                         f"row must be a contiguous float32 tensor of {self.row_floats} words on {self.device}")
         if td is None:
-            td = torch.empty(n, device=self.device)
-        self._launch("grad", n, store, capacity, idx, weights, discounts, td, row,
-                     clip=None if clip_eps is None else (log_mu, clip_eps, ratio_out))
+            td = torch.empty(b.n, device=self.device)
+        self._launch("grad", b, td, row)
         return row, td
+
+    def _grad(self, n, store, capacity, idx, row=None, td=None, *rest):
+        """_grad_batch of a batch spelled out: rest is _Batch's fields from weights on."""
+        return self._grad_batch(_Batch(n, store, capacity, idx, None, *rest), row, td)
 
     def grad_from(self, buffer, batch_size: int, row: Optional[torch.Tensor] = None,
                   generator: Optional[torch.Generator] = None, importance: bool = False, beta: float = 0.4,
@@ -637,8 +627,7 @@ class DeviceActorCritic(Handle):
 
     def _grad_drawn(self, buffer, batch_size: int, spec: DrawSpec, row: Optional[torch.Tensor]):
         b = self._drawn_batch(buffer, batch_size, spec, "grad_from")
-        row, td = self._grad(b.n, b.store, b.capacity, b.idx, row, None, b.weights, b.discounts, b.log_mu, b.clip_eps,
-                             b.ratio_out)
+        row, td = self._grad_batch(b, row)
         return row, td, b.idx
 
     def apply(self, rows):

@@ -207,14 +207,18 @@ def test_the_learners_surface_and_rho_bar_without_the_store():
         ps = inspect.signature(fn).parameters
         assert ps["rho_bar"].default is None and ps["rho_out"].default is None
     bare = object.__new__(L)                                                # the host-side check needs no handle
+    def corrected(ring, w, spec):       # what _drawn_batch asks of a draw of 4 rows with weights w
+        return bare._corrected(L._Batch(4, None, None, None, weights=w, log_mu=getattr(ring, "log_mu", None)),
+                               spec.rho_bar, spec.rho_out, None).weights
+
     for ring in (_Bare(), _Bare().with_nstep(3, 0.95), object()):
         with pytest.raises(ValueError, match="with_behaviour"):
-            bare._ratios_from(ring, 4, None, None, DrawSpec(rho_bar=1.0))
+            corrected(ring, None, DrawSpec(rho_bar=1.0))
     w = torch.ones(4)
-    assert bare._ratios_from(_Bare(), 4, None, w, DrawSpec()) is w           # rho_bar None: the draw's weights, untouched
-    assert bare._ratios_from(_Bare(), 4, None, None, DrawSpec()) is None
+    assert corrected(_Bare(), w, DrawSpec()) is w                            # rho_bar None: the draw's weights, untouched
+    assert corrected(_Bare(), None, DrawSpec()) is None
     with pytest.raises(ValueError, match="rho_out needs rho_bar"):
-        bare._ratios_from(_Bare().with_behaviour(), 4, None, None, DrawSpec(rho_out=torch.empty(4)))
+        corrected(_Bare().with_behaviour(), None, DrawSpec(rho_out=torch.empty(4)))
 
 
 def _closure(path, seen):

@@ -72,8 +72,8 @@ def update_rows(n, H, slots):
         if kind == "uniform":
             idx, _ = ring._draw_batch(n)
             w = torch.empty(n, device=DEV)
-            res = alternating({"ratio_weights": lambda: learners["rho_bar"]._ratio_weights(
-                n, ring.store, ring.log_mu, slots, idx, 1.0, None, w, None)}, reps=50)
+            batch = learners["rho_bar"]._Batch(n, ring.store, slots, idx, log_mu=ring.log_mu)
+            res = alternating({"ratio_weights": lambda: learners["rho_bar"]._ratio_weights(batch, 1.0, w, None)}, reps=50)
             rows.append(put({"what": "ratio_weights", "n": n, "H": H, "A": A, "slots": slots}, res))
         imp = kind == "prioritised"
         res = alternating({"plain": lambda: learners["plain"].update_from(ring, n, importance=imp),
