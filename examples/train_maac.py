@@ -21,6 +21,7 @@ update is the same rule on a sampled batch, and the new actor weights are re-upl
     python examples/train_maac.py --replay prioritized --learner device --actor-loss per_sample --ppo-clip 0.2 --normalise-advantage   # ... on batch-standardised advantages
     python examples/train_maac.py --replay uniform-device --learner device --actor-loss per_sample --ppo-clip 0.2 --ppo-epochs 4 --minibatch 65536   # ... over 4 epochs of disjoint minibatches of the new rollout
     python examples/train_maac.py --replay prioritized --learner device --target-tau 0.005                # bootstrap from a Polyak-averaged target critic
+    python examples/train_maac.py --replay uniform-device --learner device --actor-loss per_sample --ppo-clip 0.2 --ppo-epochs 4 --minibatch 65536 --gae-lambda 0.95   # ... on fixed GAE advantages and value targets
     python examples/train_maac.py --replay prioritized --learner device --target-period 100 --td-lambda 0.9   # ... or a periodic copy; the lambda add folds with it too
     python examples/train_maac.py --method maac-r --pmi-trainer device --learner device --replay prioritized --publish device --log-every 10
     python examples/train_maac.py --shards 8 --envs 32768 --n-uav 20 --learner device --replay prioritized --publish device   # 8 shard handles, one learner
@@ -82,7 +83,9 @@ def update(actor, critic, opt_a, opt_c, batch, gamma, weights=None, entropy_coef
     TD error (td - td.mean()) / (td.std() + 1e-8), as DeviceActorCritic.set_advantage("batch") trains; the critic keeps
     the raw TD error.  adv_stats (a dict) receives the mean and std of td_delta.
     target_critic (--target-tau / --target-period): the copy of the critic that V(s') comes from; keeping it in step
-    is the caller's (sync_target_critic)."""
+    is the caller's (sync_target_critic).
+    A batch from a GAE ring (--gae-lambda) carries "advantages", which take td_delta's place as A (normalise applies on
+    top), and a reward that is the fixed value target G_t with a discount of 0: the critic regresses on it as it stands."""
     s, a, r, s2 = batch["states"], batch["actions"].long().unsqueeze(1), batch["rewards"], batch["next_states"]
     if target_critic is None:
         v_next = critic(s2)
@@ -93,7 +96,7 @@ def update(actor, critic, opt_a, opt_c, batch, gamma, weights=None, entropy_coef
     td_delta = td_target - critic(s)
     probs = actor(s)
     log_probs = torch.log(probs.gather(1, a).squeeze(1).clamp_min(1e-12))
-    adv = td_delta.detach()
+    adv = batch["advantages"] if "advantages" in batch else td_delta.detach()
     if adv_stats is not None:
         adv_stats["mean"], adv_stats["std"] = adv.mean(), adv.std()
     if normalise:
@@ -184,7 +187,10 @@ def advantage_field(mean, std):
 
 def nstep_ring(args, ring):
     """--n-step N > 1: the ring stores N-step returns and their discounts (with_nstep); N = 1 leaves it what it was.
-    --td-lambda L: the ring stores lambda-returns instead (with_lambda)."""
+    --td-lambda L: the ring stores lambda-returns instead (with_lambda).  --gae-lambda L: fixed GAE advantages and value
+    targets (with_gae)."""
+    if args.gae_lambda is not None:
+        return ring.with_gae(args.gae_lambda, args.gamma)
     if args.td_lambda is not None:
         return ring.with_lambda(args.td_lambda, args.gamma)
     return ring.with_nstep(args.n_step, args.gamma) if args.n_step > 1 else ring
@@ -270,8 +276,9 @@ def ratio_kwargs(args, bufs, rings):
 
 
 def critic_kwargs(args, critic):
-    """add_rollout's extra argument under --td-lambda: the critic whose values the lambda add folds the rewards with."""
-    return {} if args.td_lambda is None else {"critic": critic}
+    """add_rollout's extra argument under --td-lambda or --gae-lambda: the critic whose values the add folds the rewards
+    with (a GAE ring also takes its advantages' baseline from it)."""
+    return {} if args.td_lambda is None and args.gae_lambda is None else {"critic": critic}
 
 
 def regularised(args):
@@ -518,6 +525,17 @@ def main(argv=None, timings=None):
                          "add_rollout(critic=...)): each slot keeps r + gamma L G' as its reward and gamma (1 - L) as its "
                          "discount, never across an episode end or the rollout's last step.  Needs --replay prioritized or "
                          "uniform-device; not with --n-step > 1")
+    ap.add_argument("--gae-lambda", type=float, default=None, metavar="L",
+                    help="L in [0, 1], with --ppo-epochs: fixed GAE(L) advantages and value targets per slot.  The ring's add "
+                         "evaluates the critic on the rollout's observations and walks every agent's chain backwards "
+                         "(ring.with_gae(L, gamma), add_rollout(critic=...)): each slot keeps the lambda-return G as its "
+                         "reward, 0 as its discount and G - V(s) as its advantage, never across an episode end or the "
+                         "rollout's last step, and every minibatch of the iteration's epochs trains the actor on that "
+                         "advantage and the critic on that target (the device learner through "
+                         "uavtrack_learner_update_stored, the torch learner from sample()['advantages']).  "
+                         "--normalise-advantage, --ppo-clip, --shards and --lambda-critic apply.  Needs --replay prioritized "
+                         "or uniform-device, and --actor-loss per_sample with --learner device; not with --n-step > 1 or "
+                         "--td-lambda")
     ap.add_argument("--ppo-clip", type=float, default=None, metavar="EPS",
                     help="EPS >= 0: PPO's clipped surrogate instead of --rho-bar.  The ring keeps log mu(a|s) as for "
                          "--rho-bar, and every update trains -min(r A, clip(r, 1 - EPS, 1 + EPS) A) with r = pi / mu "
@@ -629,6 +647,18 @@ def main(argv=None, timings=None):
         if args.replay == "uniform":
             ap.error("--td-lambda needs --replay prioritized or --replay uniform-device: the lambda-returns are folded by "
                      "the device rings' add (the PyTorch buffer of --replay uniform stores one-step transitions)")
+    if args.gae_lambda is not None:
+        if not 0.0 <= args.gae_lambda <= 1.0:
+            ap.error("--gae-lambda must be in [0, 1]")
+        if args.n_step > 1 or args.td_lambda is not None:
+            ap.error("--gae-lambda excludes --n-step N > 1 and --td-lambda: a ring stores n-step returns, lambda-returns or "
+                     "GAE advantages, one of the three")
+        if args.ppo_epochs is None or args.replay == "uniform":
+            ap.error("--gae-lambda needs --ppo-epochs and --replay prioritized or --replay uniform-device: the advantages "
+                     "are fixed per slot by the device rings' add, for the epochs over what that add wrote")
+        if args.learner == "device" and args.actor_loss != "per_sample":
+            ap.error("--gae-lambda with --learner device needs --actor-loss per_sample: the reference form scales the actor's "
+                     "gradient sums once by -mean(delta) / N, a factor a per-row advantage cannot share")
     if args.rho_bar is not None and (not args.rho_bar > 0 or args.replay == "uniform"):
         ap.error("--rho-bar must be > 0 and needs --replay prioritized or --replay uniform-device (the device rings keep "
                  "the behaviour log-probabilities)")
@@ -662,7 +692,7 @@ def main(argv=None, timings=None):
         ap.error("--target-tau must lie in (0, 1]")
     if args.target_period is not None and args.target_period < 1:
         ap.error("--target-period must be >= 1")
-    if args.lambda_critic is not None and (args.td_lambda is None or not targeted(args)):
+    if args.lambda_critic is not None and ((args.td_lambda is None and args.gae_lambda is None) or not targeted(args)):
         ap.error("--lambda-critic chooses between two critics: it needs --td-lambda and --target-tau or --target-period")
     if args.importance and args.replay != "prioritized":
         ap.error("--importance needs --replay prioritized (a uniform draw has no importance weights)")

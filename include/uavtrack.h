@@ -895,9 +895,48 @@ int uavtrack_learner_get_advantage(uavtrack_learner *learner, int32_t *mode, dou
  * floats inside the handle, the default.  Host-side, read at enqueue; the gradient kernel reads the pair from there. */
 int uavtrack_learner_set_advantage_stats(uavtrack_learner *learner, float *stats);
 
+/* ---- stored advantages: the actor's advantage from a per-slot store (UAVTRACK_LOSS_PER_SAMPLE only) ----
+ * uavtrack_learner_update_clipped / _grad_clipped with one more array, advantages: DEVICE fp32 [capacity], indexed by SLOT
+ * and gathered beside the reward (a GAE ring's seventh store, uavtrack_replay_add_rollout_gae); log_mu is NULLABLE here
+ * (NULL: no clipped surrogate; clip_eps and ratio_out are then not read).
+ * Wherever the actor uses an advantage -- the logit weight, the actor-loss term, and under the clipped surrogate the gate,
+ * r_i A_i and surr_i -- x_i = advantages[src_i] takes the place of delta_i, with the advantage mode applied on top:
+ *     A_i = fl( fl(x_i - mean32) * inv32 )
+ *   RAW    the same kernels with the handle's constant pair {0.0f, 1.0f}: x - 0 and x * 1 are exact, A_i = x_i;
+ *   GIVEN  the caller's pair;
+ *   BATCH  a small gather kernel writes x_i (0 for an index out of range) into the TD scratch in the TD pass's place;
+ *          steps 2 and 3 above then run unchanged over it, so the order stated there describes these statistics too.
+ * Everything else keeps delta_i = (r_i + d_i V'(s'_i)) - V(s_i) as it is: the critic's value weight and loss, td_delta,
+ * loss word [P+1] and the priorities.  With the GAE ring's reward = G_t and discount = +0 the critic regresses on the fixed
+ * value target and the actor follows the fixed advantage: both constants of the iteration.  A store that holds the bits of
+ * td_delta of the plain per-sample update of the same batch leaves that update's parameters, moments, td_delta, critic
+ * loss and priorities.
+ * The four kernels are further instantiations of the gradient body (always with the entropy and advantage blocks), chosen
+ * by (target critic on, log_mu given) from a table of their own; the other entry points launch what they launched.
+ * A gradient row keeps its P + 8 words and its tag, so stored and plain rows may meet in one apply.
+ * Refusals.  On the host, enqueuing nothing: those of the _clipped forms (log_mu == NULL is allowed), a null advantages, a
+ * UAVTRACK_LOSS_REFERENCE learner (that form scales the actor's sums once by -mean(delta) / N, a factor a per-row
+ * advantage cannot share).  On the device, like a bad action: a drawn slot whose advantage is NaN ("unknown") or infinite
+ * sets status bit 7 (value 128) in the status word and in word P + 6 of a row, and that row is not used; the update or
+ * apply then changes nothing, its losses are NaN and the next uavtrack_learner_check counts it.
+ * Stream-ordered: no synchronisation, no allocation, capturable.  Cost on one MI355X: DESIGN.md section 9. */
+int uavtrack_learner_update_stored(uavtrack_learner *learner, int64_t n,
+                                   const float *states, const int32_t *actions, const float *rewards,
+                                   const float *next_states, int64_t capacity, const int64_t *indices,
+                                   const float *weights, const float *discounts, const float *advantages,
+                                   const float *log_mu, double clip_eps, float *ratio_out,
+                                   float *actor_loss, float *critic_loss, float *td_delta, float *priorities,
+                                   void *stream);
+int uavtrack_learner_grad_stored(uavtrack_learner *learner, int64_t n,
+                                 const float *states, const int32_t *actions, const float *rewards,
+                                 const float *next_states, int64_t capacity, const int64_t *indices,
+                                 const float *weights, const float *discounts, const float *advantages,
+                                 const float *log_mu, double clip_eps, float *ratio_out,
+                                 float *td_delta, float *row, void *stream);
+
 /* Synchronises `stream`; fails if any update or apply since the previous check was refused on the device (bad action,
- * index, importance weight, discount, behaviour log-probability or ratio, a bad given advantage pair, or a row of another
- * layout).  refused (nullable) receives their number; the count restarts at 0. */
+ * index, importance weight, discount, behaviour log-probability or ratio, a bad given advantage pair, a stored advantage
+ * that is not finite, or a row of another layout).  refused (nullable) receives their number; the count restarts at 0. */
 int uavtrack_learner_check(uavtrack_learner *learner, int64_t *refused, void *stream);
 
 /* ---- the PMI trainer: PMINetwork.train_pmi + its Adam steps on the device ----
@@ -1094,7 +1133,7 @@ typedef struct uavtrack_replay_ring {
 int uavtrack_replay_create(const uavtrack_replay_config *cfg, uavtrack_replay **out);
 int uavtrack_replay_destroy(uavtrack_replay *replay);
 
-/* ---- the five adds: what they share ----
+/* ---- the adds (five, and the GAE add further down): what they share ----
  * An add writes n transitions into the caller's ring, in order f = 0 .. n - 1.  Only the last min(n, capacity) are
  * written, from slot (pos + max(0, n - capacity)) % capacity on, wrapping; on a ring with priorities each gets the
  * maximum of the whole priorities array as it stood before the call (1.0 when count == 0), taken on the device.
@@ -1195,6 +1234,37 @@ int uavtrack_replay_add_rollout_lambda(uavtrack_replay *replay, const uavtrack_r
                                        const int32_t *actions, const float *reward, const uint8_t *done,
                                        const float *start_obs, const float *values, double lambda, double gamma,
                                        void *stream);
+
+/* ---- fixed GAE(lambda) advantages and value targets per slot: what PPO epochs train on ----
+ * uavtrack_replay_add_rollout_lambda with three more arrays and one more store.  Beyond values (as above):
+ *   values_in    [envs][n_uav]     DEVICE fp32, V(obs_in);
+ *   values_start [T][envs][n_uav]  DEVICE fp32, V(start_obs[t]); NULL together with done and start_obs, and read only
+ *                                  where done[t][b] fired;
+ *   advantages   [capacity]        DEVICE fp32, caller-owned, passed beside the ring like discounts (the ring struct keeps
+ *                                  its size): the seventh per-slot store.
+ * The fold is the lambda add's, operation for operation: the same g, l, gl, c, the same cut(t), R_t and d_t, and
+ *     G = R_t + d_t * values[t][b][i]            (every operation rounded to fp32 on its own)
+ * Stored transition (t, b, i): state, action, next_state and priority exactly what the lambda add stores;
+ *   reward    = G_t, the bits the fold forms for G at step t: the lambda-return with EVERY term evaluated at add time;
+ *   discount  = +0.0f, so the learner's target r + d V(s') of the slot is the fixed value target G_t (PPO's
+ *               returns = advantages + values; d == 0 is "do not bootstrap", which the learner already handles);
+ *   advantage = fl(G_t - Vs_t), Vs_t the value of the state the step began in: values_in[b][i] at t == 0,
+ *               values_start[t - 1][b][i] where done[t - 1][b] fired, values[t - 1][b][i] otherwise.
+ * Since sum_k (g l)^k delta_{t+k} = G^lambda_t - V(s_t) with delta_t = r_t + g V(s_{t+1}) - V(s_t), the advantage is
+ * GAE(lambda).  It bootstraps at the rollout's last step and at a fired done: done is the horizon, a truncation, as the
+ * lambda add treats it.  On the same inputs the states, actions, next_states and priorities end byte-identical to the
+ * lambda add's and reward == fl(R_t + fl(d_t * values[t])) of its (R_t, d_t).
+ * Slots, the window for T * agents > capacity and the wrap are those of the other adds.  The one-step write runs first; a
+ * scan kernel of its own follows, one thread per agent chain, the loads of eight steps issued ahead of the carried G
+ * (the lambda add's kernels are not touched).  Non-finite values propagate; the add does not inspect them (the learner
+ * refuses a drawn advantage that is not finite, uavtrack_learner_update_stored).
+ * Required: discounts, advantages, the four rollout arrays, values, values_in.  done, start_obs and values_start are all
+ * given or all NULL.  lambda, gamma, sizes and alignment as uavtrack_replay_add_rollout_lambda. */
+int uavtrack_replay_add_rollout_gae(uavtrack_replay *replay, const uavtrack_replay_ring *ring, float *discounts,
+                                    float *advantages, int64_t steps, int64_t envs, int64_t n_uav, const float *obs_in,
+                                    const float *obs, const int32_t *actions, const float *reward, const uint8_t *done,
+                                    const float *start_obs, const float *values, const float *values_in,
+                                    const float *values_start, double lambda, double gamma, void *stream);
 
 /* PrioritizedReplayBuffer.sample's draw (train.py:98-112) without the gather: n slots with replacement from
  * P(i) = p_i^alpha / sum_j p_j^alpha over [0, count) (the draw stream above) into indices [n] (DEVICE int64), and,

@@ -1,5 +1,5 @@
 // api_learner.hip -- the C ABI of the device learner (include/uavtrack.h, uavtrack_learner_*).
-// The eight batch entry points (update, grad and their _weighted, _discounted and _clipped forms) each fill a
+// The ten batch entry points (update, grad and their _weighted, _discounted, _clipped and _stored forms) each fill a
 // LearnerLaunch as they were called and share one acceptor and one runner: accept_learner_batch, run_learner_batch.
 
 #include "api_env.h"
@@ -37,7 +37,7 @@ static Bufs device_bufs(LearnerDevice &d)
     const size_t P = (size_t)d.L.P;
     return adam_bufs(d.opt) + Bufs{buf(d.params, P, true), buf(d.gstatus, 1, true), buf(d.partials, kLearnerMaxGroups * (P + 4)), buf(d.scal, 2),
                                    buf(d.gsum, P), buf(d.sq, 2 * (size_t)learner_clip_groups(d.L)), buf(d.coef, 2),
-                                   buf(d.adv_stats, 3, true)} +
+                                   buf(d.adv_stats, 3, true), buf(d.adv_unit, 2)} +
            scratch_bufs(d, d.max_n);
 }
 
@@ -88,8 +88,8 @@ int accept_advantage_rows(const char *fn, const uavtrack_learner *l, int64_t n)
 
 enum class Batch { Update, Grad };
 
-// Every host-side refusal of the eight batch entry points (uavtrack_learner_update, _grad and their _weighted,
-// _discounted and _clipped forms), in one order.  Nothing has been enqueued when one of them fires.
+// Every host-side refusal of the ten batch entry points (uavtrack_learner_update, _grad and their _weighted,
+// _discounted, _clipped and _stored forms), in one order.  Nothing has been enqueued when one of them fires.
 int accept_learner_batch(const char *fn, const uavtrack_learner *l, const LearnerLaunch &q, Batch kind, const float *row)
 {
     if (!l) return fail("%s: null handle", fn);
@@ -101,6 +101,14 @@ int accept_learner_batch(const char *fn, const uavtrack_learner *l, const Learne
     if (accept_batch(fn, l, q.n, q.capacity, q.idx, "from") || accept_entropy_rows(fn, l, q.n) ||
         accept_advantage_rows(fn, l, q.n))
         return 1;
+    if (q.stored) {
+        if (!q.advantages) return fail("%s: advantages must not be null", fn);
+        if (!l->d.per_sample)
+            return fail("%s: stored advantages on a UAVTRACK_LOSS_REFERENCE learner: that form scales the actor's gradient "
+                        "sums once by -mean(delta) / N, a factor a per-row advantage cannot share; use "
+                        "UAVTRACK_LOSS_PER_SAMPLE", fn);
+        if (!q.log_mu) return 0;                                    // (clip_eps is read with log_mu alone)
+    }
     if (!q.clipped) return 0;
     if (!q.log_mu) return fail("%s: log_mu must not be null", fn);
     if (!(q.clip_eps >= 0)) return fail("%s: clip_eps = %g must be >= 0 (+inf: never clips)", fn, q.clip_eps);
@@ -110,13 +118,13 @@ int accept_learner_batch(const char *fn, const uavtrack_learner *l, const Learne
     return 0;
 }
 
-// The eight entry points behind their own names: accepted, the clip's bounds folded to fp32, then the closed update
+// The ten entry points behind their own names: accepted, the clip's bounds folded to fp32, then the closed update
 // (row null) or the gradient half into `row`.
 int run_learner_batch(const char *fn, uavtrack_learner *learner, LearnerLaunch q, Batch kind, float *row, void *stream)
 {
     if (accept_learner_batch(fn, learner, q, kind, row)) return 1;
     ON_DEVICE(learner->cfg.device_id);
-    if (q.clipped) {
+    if (q.clipped && q.log_mu) {
         const float eps32 = (float)q.clip_eps;
         q.clip_lo = 1.0f - eps32; q.clip_hi = 1.0f + eps32;
     }
@@ -180,7 +188,17 @@ int uavtrack_learner_create(const uavtrack_learner_config *cfg, uavtrack_learner
         d.adv_eps = 1e-8;                               // the advantage raw
         return learner_prepare_kernels(d.L);
     };
-    return create_handle(__func__, cfg, out, check, init);
+    if (create_handle(__func__, cfg, out, check, init)) return 1;
+    // the constant pair a stored advantage in raw mode goes through: x - 0 and x * 1 are exact
+    const float unit[2] = {0.0f, 1.0f};
+    DeviceGuard guard((*out)->cfg.device_id);
+    const hipError_t e = hipMemcpy((*out)->d.adv_unit, unit, sizeof unit, hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        (void)uavtrack_learner_destroy(*out);
+        *out = nullptr;
+        return fail("%s: %s", __func__, hipGetErrorString(e));
+    }
+    return 0;
 }
 
 int uavtrack_learner_destroy(uavtrack_learner *learner)
@@ -374,6 +392,32 @@ int uavtrack_learner_grad_clipped(uavtrack_learner *learner, int64_t n, const fl
 {
     LearnerLaunch q = {n, capacity, states, rewards, next_states, actions, indices, weights, discounts};
     q.clipped = true; q.log_mu = log_mu; q.clip_eps = clip_eps; q.ratio = ratio_out;
+    q.td_delta = td_delta;
+    return run_learner_batch(__func__, learner, q, Batch::Grad, row, stream);
+}
+
+int uavtrack_learner_update_stored(uavtrack_learner *learner, int64_t n, const float *states, const int32_t *actions,
+                                   const float *rewards, const float *next_states, int64_t capacity,
+                                   const int64_t *indices, const float *weights, const float *discounts,
+                                   const float *advantages, const float *log_mu, double clip_eps, float *ratio_out,
+                                   float *actor_loss, float *critic_loss, float *td_delta, float *priorities, void *stream)
+{
+    LearnerLaunch q = {n, capacity, states, rewards, next_states, actions, indices, weights, discounts};
+    q.stored = true; q.advantages = advantages;
+    q.clipped = true; q.log_mu = log_mu; q.clip_eps = clip_eps; q.ratio = log_mu ? ratio_out : nullptr;
+    q.actor_loss = actor_loss; q.critic_loss = critic_loss; q.td_delta = td_delta; q.priorities = priorities;
+    return run_learner_batch(__func__, learner, q, Batch::Update, nullptr, stream);
+}
+
+int uavtrack_learner_grad_stored(uavtrack_learner *learner, int64_t n, const float *states, const int32_t *actions,
+                                 const float *rewards, const float *next_states, int64_t capacity, const int64_t *indices,
+                                 const float *weights, const float *discounts, const float *advantages,
+                                 const float *log_mu, double clip_eps, float *ratio_out, float *td_delta, float *row,
+                                 void *stream)
+{
+    LearnerLaunch q = {n, capacity, states, rewards, next_states, actions, indices, weights, discounts};
+    q.stored = true; q.advantages = advantages;
+    q.clipped = true; q.log_mu = log_mu; q.clip_eps = clip_eps; q.ratio = log_mu ? ratio_out : nullptr;
     q.td_delta = td_delta;
     return run_learner_batch(__func__, learner, q, Batch::Grad, row, stream);
 }
@@ -620,7 +664,8 @@ int uavtrack_learner_check(uavtrack_learner *learner, int64_t *refused, void *st
                     "[0, capacity), an importance weight that is NaN, infinite or negative, a discount that is NaN or "
                     "outside [0, 1], a behaviour log-probability that is NaN or positive or a ratio that is not finite "
                     "(the clipped surrogate), a given advantage mean that is not finite or inv_std that is NaN, infinite or "
-                    "negative, or (uavtrack_learner_apply) a gradient row of another layout; they changed nothing",
+                    "negative, a stored advantage that is NaN or infinite, or (uavtrack_learner_apply) a gradient row of another "
+                    "layout; they changed nothing",
                     count, learner->d.L.A);
     return 0;
 }

@@ -61,14 +61,14 @@ ReplayRingView ring_view(const uavtrack_replay_ring *ring)
     return v;
 }
 
-// One request to add to a ring, as each of the five add entry points states it: the launcher's own request plus what
+// One request to add to a ring, as each of the six add entry points states it: the launcher's own request plus what
 // only the acceptor needs.  The flat form is one step of n "environments"; uavtrack_replay_add_rollout knows only
 // agents = envs * n_uav, and passes it as envs.
 struct ReplayAddCall {
     const char *who;                   // the entry point, as the error messages name it
     const uavtrack_replay_ring *ring;  // (a.ring is filled once this one is accepted)
     bool episodes = false;             // the entry point has done / start_obs: _episodes requires them, the n-step and
-                                       // lambda forms take both or neither
+                                       // lambda forms and the GAE form take both or neither
     double lambda = 0.0, gamma = 0.0;  // as given: checked as doubles, launched as floats
     ReplayAdd a{};
 
@@ -96,7 +96,11 @@ int accept_replay_add(const uavtrack_replay *replay, const ReplayAddCall &q)
                     : lambda ? "discounts, obs_in, obs, actions, reward and values"
                     : !plain ? "discounts, obs_in, obs, actions and reward"
                     : q.episodes ? "obs_in, obs, actions, reward, done and start_obs" : "obs_in, obs, actions and reward");
+    if (a.form == ReplayForm::Gae && (!a.values || !a.values_in || !a.advantages))
+        return fail("%s: advantages, values and values_in must not be null", who);
     if (!a.done != !a.start_obs) return fail("%s: done and start_obs must both be given or both be null", who);
+    if (a.form == ReplayForm::Gae && !a.done != !a.values_start)
+        return fail("%s: values_start comes with done and start_obs: all three given or all three null", who);
     if (!aligned16(flat ? a.states : a.obs_in) || !aligned16(a.next) || !aligned16(a.start_obs))
         return fail("%s: %s must be 16-byte aligned", who,
                     flat ? "states and next_states" : q.episodes ? "obs_in, obs and start_obs" : "obs_in and obs");
@@ -224,6 +228,19 @@ int uavtrack_replay_add_rollout_lambda(uavtrack_replay *replay, const uavtrack_r
     ReplayAddCall q(__func__, ring, ReplayForm::Lambda, steps, envs, n_uav, obs_in, obs, actions, reward);
     q.episodes = true; q.a.done = done; q.a.start_obs = start_obs;
     q.a.discounts = discounts; q.a.values = values; q.lambda = lambda; q.gamma = gamma;
+    return run_replay_add(replay, q, stream);
+}
+
+int uavtrack_replay_add_rollout_gae(uavtrack_replay *replay, const uavtrack_replay_ring *ring, float *discounts,
+                                    float *advantages, int64_t steps, int64_t envs, int64_t n_uav, const float *obs_in,
+                                    const float *obs, const int32_t *actions, const float *reward, const uint8_t *done,
+                                    const float *start_obs, const float *values, const float *values_in,
+                                    const float *values_start, double lambda, double gamma, void *stream)
+{
+    ReplayAddCall q(__func__, ring, ReplayForm::Gae, steps, envs, n_uav, obs_in, obs, actions, reward);
+    q.episodes = true; q.a.done = done; q.a.start_obs = start_obs;
+    q.a.discounts = discounts; q.a.values = values; q.lambda = lambda; q.gamma = gamma;
+    q.a.advantages = advantages; q.a.values_in = values_in; q.a.values_start = values_start;
     return run_replay_add(replay, q, stream);
 }
 

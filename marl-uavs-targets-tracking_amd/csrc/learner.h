@@ -78,6 +78,7 @@ struct LearnerDevice {
     float *stats() const { return adv_user ? adv_user : adv_stats; }
     float *adv_td;                  // [max_n] the TD pass's delta; null until a mode other than raw is first set
     double *adv_part;               // [2][learner_adv_chunks(max_n)] the chunks' sums of delta, then of squared deviations
+    float *adv_unit;                // [2] {0.0f, 1.0f}: the pair a stored advantage in raw mode is "standardised" by
 };
 enum { kAdvantageRaw = 0, kAdvantageBatch = 1, kAdvantageGiven = 2 };
 // One batch of uavtrack_learner_update / _grad in any of their forms.  The eight entry points fill it as they were
@@ -94,10 +95,13 @@ struct LearnerLaunch {
     const float *log_mu;            // nullable [capacity]: per-slot behaviour log-probabilities; non-null: the clipped surrogate
     float clip_lo, clip_hi;         // its bounds 1 - eps and 1 + eps in fp32 (read only with log_mu)
     float *ratio;                   // nullable [n]: its ratios in batch order (read only with log_mu)
+    bool stored;                    // a _stored entry point: advantages is required, log_mu nullable, per-sample only
+    const float *advantages;        // nullable [capacity]: per-slot advantages of the actor; non-null: the stored kernels
     float *actor_loss, *critic_loss, *td_delta, *priorities;
 };
 int learner_rows_per_tile(int hidden);
-size_t learner_lds_bytes(const LearnerLayout &L, int rows, bool clipped = false);   // clipped: R more floats, behind the rest
+size_t learner_lds_bytes(const LearnerLayout &L, int rows, bool clipped = false,    // clipped: R more floats, behind the rest
+                         bool stored = false);                                      // stored: 2 R more (log_mu, the advantage)
 int learner_groups(const LearnerLayout &L, int64_t n);
 int learner_clip_groups(const LearnerLayout &L);   // workgroups of the clip's gradient pass: ceil(P / 256)
 int64_t learner_adv_chunks(int64_t n);             // 256-row chunks of the advantage statistics: ceil(n / 256)

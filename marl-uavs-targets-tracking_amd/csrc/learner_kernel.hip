@@ -70,7 +70,16 @@
 //
 // Which of the ten instantiations of the gradient body a launch takes is learner_variants.h's table and its
 // learner_grad_variant; the host code below expands the same table over the kernels (kGradKernels), prepares every row's
-// LDS attribute from it and launches through it, each kernel receiving the filled GradAdvArgs cut down to its own type.
+// LDS attribute from it and launches through it, each kernel receiving the filled GradStoredArgs cut down to its own type.
+//
+// Stored advantages (uavtrack_learner_update_stored / _grad_stored, per-sample form only): the advantage the actor starts
+// from is x_i = advantages[src_i], a per-slot store gathered beside the reward (a GAE ring's seventh store), in delta_i's
+// place wherever the actor uses an advantage; the advantage mode applies on top, A_i = fl(fl(x_i - mean) * inv_std), raw
+// being the handle's constant pair {0, 1}.  The critic, td_delta, loss word 1 and the priorities keep delta_i.  Four more
+// instantiations of the body (kStored; always kReg and kAdv, by kTgt and kClip) with a table and a picker of their own in
+// learner_variants.h; the ten above keep their arguments and their code.  In batch mode learner_adv_gather_kernel writes
+// x_i into the TD scratch in learner_td_kernel's place and the statistics kernels run over it unchanged.  A drawn
+// advantage that is NaN or infinite sets status bit 7 (value 128) and the row is not used.
 //
 // The critic alone (uavtrack_learner_values): learner_values_kernel, at the end of the kernels below, evaluates V(x) of
 // any number of rows by the chain of the layer-1 and layer-2 loops above, to the bit, and touches no learner state.
@@ -128,16 +137,25 @@ struct GradAdvArgs : GradClipArgs {
                                     // that is not finite, or an inv_std that is NaN, infinite or negative
 };
 
+// what the four kernels of a stored advantage take on top (learner_grad_stored_kernel and its siblings)
+struct GradStoredArgs : GradAdvArgs {
+    const float *advantages;        // [capacity], slot order: the actor's advantage x_i of a row, in delta_i's place; status
+                                    // bit 7 (value 128): a drawn slot whose advantage is NaN or infinite
+};
+
 // kReg: the entropy term and the entropy[] store in the per-row block; everything else is one text.
 // kTgt: V(s') from the separate critic block a.target (the target critic) instead of the online critic; without it
 // W1t / b1t / W2t / b2t are the online critic's pointers at compile time.
 // kClip (with kReg): the clipped surrogate's gate on the row's policy gradient, log_mu gathered into lm, the ratio[] store.
 // kAdv (with kReg): the row's advantage is fl(fl(delta - mean) * inv_std) wherever the actor uses one.
-template <bool kReg, bool kTgt = false, bool kClip = false, bool kAdv = false>
+// kStored (with kAdv): the advantage the line above starts from is advantages[src], gathered into xa, not delta.
+template <bool kReg, bool kTgt = false, bool kClip = false, bool kAdv = false, bool kStored = false>
 __device__ __forceinline__ void learner_grad_body(
-    const std::conditional_t<kAdv, GradAdvArgs, std::conditional_t<kClip, GradClipArgs, GradArgs>> &a)
+    const std::conditional_t<kStored, GradStoredArgs,
+                             std::conditional_t<kAdv, GradAdvArgs, std::conditional_t<kClip, GradClipArgs, GradArgs>>> &a)
 {
     static_assert(kReg || !kAdv, "the normalised advantage lives in the kReg block");
+    static_assert(kAdv || !kStored, "a stored advantage passes through the normalised advantage's line");
     extern __shared__ float lds[];
     const LearnerLayout &L = a.L;
     const int H = L.H, A = L.A, R = a.rows, P = L.P;
@@ -155,6 +173,7 @@ __device__ __forceinline__ void learner_grad_body(
     float *wt  = reinterpret_cast<float *>(act + R);    // [R] importance weight of the row
     float *dc  = wt + R;                                // [R] discount of the row
     float *lm  = dc + R;                                // [R] behaviour log-probability of the row (kClip only)
+    float *xa  = lm + R;                                // [R] stored advantage of the row (kStored only)
 
     const int tid = threadIdx.x;
     const float *W1a = a.params + L.a_w1, *b1a = a.params + L.a_b1, *W2a = a.params + L.a_w2, *b2a = a.params + L.a_b2;
@@ -196,6 +215,11 @@ __device__ __forceinline__ void learner_grad_body(
                         const float mu = a.log_mu[src];
                         if (!(mu <= 0.0f)) { atomicOr(a.status, 16); av = -1; }
                         lm[r] = mu;
+                    }
+                    if constexpr (kStored) {
+                        const float x = a.advantages[src];
+                        if (!(fabsf(x) <= 3.402823466e+38f)) { atomicOr(a.status, 128); av = -1; }
+                        xa[r] = x;
                     }
                 }
                 if (a.weights) {
@@ -280,7 +304,8 @@ __device__ __forceinline__ void learner_grad_body(
                 const float v = gv[r];
                 const float delta = target - v;
                 float adv = delta;                                  // the actor's advantage; delta stays the critic's
-                if constexpr (kAdv) adv = __fmul_rn(__fsub_rn(delta, adv_mean), adv_inv);
+                if constexpr (kStored) adv = xa[r];
+                if constexpr (kAdv) adv = __fmul_rn(__fsub_rn(adv, adv_mean), adv_inv);
                 const float wi = wt[r];
                 const float c = a.entropy_coef;
                 float nlp, al;
@@ -433,6 +458,12 @@ __global__ void __launch_bounds__(kLW) learner_grad_adv_target_kernel(GradAdvArg
 __global__ void __launch_bounds__(kLW) learner_grad_adv_clip_kernel(GradAdvArgs a) { learner_grad_body<true, false, true, true>(a); }
 __global__ void __launch_bounds__(kLW) learner_grad_adv_clip_target_kernel(GradAdvArgs a) { learner_grad_body<true, true, true, true>(a); }
 
+// a stored advantage (uavtrack_learner_update_stored / _grad_stored), without and with the clipped surrogate and a target critic
+__global__ void __launch_bounds__(kLW) learner_grad_stored_kernel(GradStoredArgs a) { learner_grad_body<true, false, false, true, true>(a); }
+__global__ void __launch_bounds__(kLW) learner_grad_stored_target_kernel(GradStoredArgs a) { learner_grad_body<true, true, false, true, true>(a); }
+__global__ void __launch_bounds__(kLW) learner_grad_stored_clip_kernel(GradStoredArgs a) { learner_grad_body<true, false, true, true, true>(a); }
+__global__ void __launch_bounds__(kLW) learner_grad_stored_clip_target_kernel(GradStoredArgs a) { learner_grad_body<true, true, true, true, true>(a); }
+
 // Clears the update's status word (a kernel node rather than a memset node, so a captured update is a chain of kernels)
 __global__ void learner_begin_kernel(int *status)
 {
@@ -465,7 +496,7 @@ __global__ void learner_finalize_kernel(const float *src, int count, size_t stri
         if (n_given) continue;                                      // a workgroup partial ends here
         const int32_t *tail = reinterpret_cast<const int32_t *>(row) + P + 4;
         const int64_t nr = (int64_t)((uint64_t)(uint32_t)tail[0] | ((uint64_t)(uint32_t)tail[1] << 32));
-        bad |= tail[2] & (31 | 64);
+        bad |= tail[2] & (31 | 64 | 128);
         if (tail[3] != P || nr < 1) bad |= 32;                      // a row of another layout (or not a row at all)
         else N += nr;
     }
@@ -780,6 +811,27 @@ __global__ void __launch_bounds__(kAdvChunk) learner_td_kernel(TdArgs a)
     }
 }
 
+// In learner_td_kernel's place when the batch brings stored advantages: td[i] = advantages[src_i], the value the
+// gradient kernel will standardise (0 for a row whose index is out of range), and each chunk's fp64 sum by the same tree.
+__global__ void __launch_bounds__(kAdvChunk) learner_adv_gather_kernel(const float *advantages, const int64_t *idx,
+                                                                       int64_t n, int64_t capacity, float *td, double *psum)
+{
+    __shared__ double part[kAdvChunk];
+    const int tid = threadIdx.x;
+    const int64_t chunks = (n + kAdvChunk - 1) / kAdvChunk;
+    for (int64_t c = blockIdx.x; c < chunks; c += gridDim.x) {
+        const int64_t i = c * kAdvChunk + tid;
+        float x = 0.0f;
+        if (i < n) {
+            const int64_t src = idx ? idx[i] : i;
+            if (src >= 0 && src < capacity) x = advantages[src];
+            td[i] = x;
+        }
+        const double s = chunk_tree(part, tid, (double)x);
+        if (tid == 0) psum[c] = s;
+    }
+}
+
 // the chunk sums in ascending chunk order
 __device__ __forceinline__ double ordered_sum64(const double *src, int64_t count)
 {
@@ -852,9 +904,9 @@ int learner_rows_per_tile(int hidden)
     return r > 256 ? 256 : r;
 }
 
-size_t learner_lds_bytes(const LearnerLayout &L, int rows, bool clipped)
+size_t learner_lds_bytes(const LearnerLayout &L, int rows, bool clipped, bool stored)
 {
-    return sizeof(float) * ((size_t)L.P + (size_t)rows * (24 + 3 * L.H + L.A + 2 + 4 + 2 + (clipped ? 1 : 0))) +
+    return sizeof(float) * ((size_t)L.P + (size_t)rows * (24 + 3 * L.H + L.A + 2 + 4 + 2 + (stored ? 2 : clipped ? 1 : 0))) +
            sizeof(int) * (size_t)rows;
 }
 
@@ -871,18 +923,19 @@ namespace {
 
 // One launch of a gradient kernel: the fully filled arguments, cut down to the kernel's own parameter type.
 template <typename Args, void (*kKernel)(Args)>
-void launch_variant(dim3 grid, size_t lds, hipStream_t st, const GradAdvArgs &a)
+void launch_variant(dim3 grid, size_t lds, hipStream_t st, const GradStoredArgs &a)
 {
     hipLaunchKernelGGL(kKernel, grid, dim3(kLW), lds, st, static_cast<const Args &>(a));
 }
 
-// learner_variants.h's table over the kernels themselves, in its order
+// learner_variants.h's two tables over the kernels themselves, each in its order
 struct GradKernel {
     const void *kernel;
-    void (*launch)(dim3 grid, size_t lds, hipStream_t st, const GradAdvArgs &a);
+    void (*launch)(dim3 grid, size_t lds, hipStream_t st, const GradStoredArgs &a);
 };
 #define GRAD_KERNEL_ROW(k, Args, reg, tgt, clip, adv, lds) {reinterpret_cast<const void *>(k), launch_variant<Args, k>},
 const GradKernel kGradKernels[kLearnerGradVariantCount] = {UAVTRACK_LEARNER_GRAD_VARIANTS(GRAD_KERNEL_ROW)};
+const GradKernel kStoredKernels[kLearnerStoredVariantCount] = {UAVTRACK_LEARNER_STORED_VARIANTS(GRAD_KERNEL_ROW)};
 #undef GRAD_KERNEL_ROW
 
 }  // namespace
@@ -890,9 +943,12 @@ const GradKernel kGradKernels[kLearnerGradVariantCount] = {UAVTRACK_LEARNER_GRAD
 hipError_t learner_prepare_kernels(const LearnerLayout &L)
 {
     // every instantiation of the gradient body needs the attribute of its own: up to about 131 KB at H = 256
-    for (int i = 0; i < kLearnerGradVariantCount; ++i) {
-        const size_t lds = learner_lds_bytes(L, learner_rows_per_tile(L.H), kLearnerGradVariants[i].clipped_lds);
-        const hipError_t e = hipFuncSetAttribute(kGradKernels[i].kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    const int R = learner_rows_per_tile(L.H);
+    for (int i = 0; i < kLearnerGradVariantCount + kLearnerStoredVariantCount; ++i) {
+        const bool stored = i >= kLearnerGradVariantCount;
+        const void *kernel = stored ? kStoredKernels[i - kLearnerGradVariantCount].kernel : kGradKernels[i].kernel;
+        const size_t lds = learner_lds_bytes(L, R, !stored && kLearnerGradVariants[i].clipped_lds, stored);
+        const hipError_t e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (e != hipSuccess) return e;
     }
     return hipSuccess;
@@ -908,8 +964,8 @@ hipError_t launch_grad(const LearnerDevice &d, const LearnerLaunch &q, float *td
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
 
-    const bool batch = d.adv_mode == kAdvantageBatch;
-    GradAdvArgs a;
+    const bool batch = d.adv_mode == kAdvantageBatch, stored = q.advantages != nullptr;
+    GradStoredArgs a;
     a.params = d.params; a.states = q.states; a.rewards = q.rewards; a.next_states = q.next_states;
     a.actions = q.actions; a.idx = q.idx; a.weights = q.weights; a.n = q.n; a.capacity = q.capacity;
     a.partials = d.partials; a.td_delta = td; a.status = status;
@@ -918,27 +974,38 @@ hipError_t launch_grad(const LearnerDevice &d, const LearnerLaunch &q, float *td
     a.target = d.target_mode ? d.target : nullptr;
     a.log_mu = q.log_mu; a.clip_lo = q.clip_lo; a.clip_hi = q.clip_hi; a.ratio = q.ratio;
     a.stats = batch ? d.stats() : d.adv_given;
-    const int variant = learner_grad_variant(d.entropy_coef != 0.0f || d.entropy, a.target != nullptr, q.log_mu != nullptr,
-                                             d.adv_mode != kAdvantageRaw);
+    a.advantages = q.advantages;
+    // a batch that brings advantages consults the stored table first; raw is then the constant pair {0, 1}
+    if (stored && d.adv_mode == kAdvantageRaw) a.stats = d.adv_unit;
+    const int variant = stored ? learner_stored_variant(a.target != nullptr, q.log_mu != nullptr)
+                               : learner_grad_variant(d.entropy_coef != 0.0f || d.entropy, a.target != nullptr,
+                                                      q.log_mu != nullptr, d.adv_mode != kAdvantageRaw);
     if (batch) {
-        // the normalised advantage in batch mode: the TD pass and the statistics first, the seal behind
+        // the normalised advantage in batch mode: the TD pass (stored advantages: their gather) and the statistics
+        // first, the seal behind
         const int64_t chunks = learner_adv_chunks(q.n);
         const dim3 cgrid((unsigned)(chunks < 1024 ? chunks : 1024));
         double *psum = d.adv_part, *psq = d.adv_part + learner_adv_chunks(d.max_n);
-        TdArgs t;
-        t.critic = d.params + L.c_w1; t.target = a.target ? a.target : t.critic;
-        t.states = q.states; t.rewards = q.rewards; t.next_states = q.next_states; t.idx = q.idx;
-        t.discounts = q.discounts; t.n = q.n; t.capacity = q.capacity; t.H = L.H; t.gamma = d.gamma;
-        t.td = d.adv_td; t.psum = psum;
-        hipLaunchKernelGGL(learner_td_kernel, cgrid, dim3(kAdvChunk), 0, st, t);
+        if (stored) {
+            hipLaunchKernelGGL(learner_adv_gather_kernel, cgrid, dim3(kAdvChunk), 0, st, q.advantages, q.idx, q.n,
+                               q.capacity, d.adv_td, psum);
+        } else {
+            TdArgs t;
+            t.critic = d.params + L.c_w1; t.target = a.target ? a.target : t.critic;
+            t.states = q.states; t.rewards = q.rewards; t.next_states = q.next_states; t.idx = q.idx;
+            t.discounts = q.discounts; t.n = q.n; t.capacity = q.capacity; t.H = L.H; t.gamma = d.gamma;
+            t.td = d.adv_td; t.psum = psum;
+            hipLaunchKernelGGL(learner_td_kernel, cgrid, dim3(kAdvChunk), 0, st, t);
+        }
         if ((e = hipGetLastError()) != hipSuccess) return e;
         hipLaunchKernelGGL(learner_adv_sq_kernel, cgrid, dim3(kAdvChunk), 0, st, d.adv_td, q.n, psum, psq);
         if ((e = hipGetLastError()) != hipSuccess) return e;
         hipLaunchKernelGGL(learner_adv_stats_kernel, dim3(1), dim3(64), 0, st, psum, psq, q.n, d.adv_eps, d.stats());
         if ((e = hipGetLastError()) != hipSuccess) return e;
     }
-    kGradKernels[variant].launch(dim3(learner_groups(L, q.n)), learner_lds_bytes(L, R, kLearnerGradVariants[variant].clipped_lds),
-                                 st, a);
+    const dim3 grid(learner_groups(L, q.n));
+    if (stored) kStoredKernels[variant].launch(grid, learner_lds_bytes(L, R, false, true), st, a);
+    else kGradKernels[variant].launch(grid, learner_lds_bytes(L, R, kLearnerGradVariants[variant].clipped_lds), st, a);
     if ((e = hipGetLastError()) != hipSuccess || !batch) return e;
     hipLaunchKernelGGL(learner_adv_seal_kernel, dim3(1), dim3(64), 0, st, status, d.stats());
     return hipGetLastError();

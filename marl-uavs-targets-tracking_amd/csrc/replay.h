@@ -56,8 +56,10 @@ hipError_t launch_replay_sample_sweep(const ReplayDevice &d, int64_t capacity, i
 //            and start_obs (of obs's shape) the rollout crossed episode ends, without them envs * n_uav is just `agents`;
 //   Nstep    Rollout's source folded into n_step-step returns with gamma; discounts [capacity] receives gamma^m per slot;
 //   Lambda   Rollout's write, then the backward scan over each agent's chain that overwrites the written slots' rewards
-//            with R_t and leaves d_t in discounts; values [steps][agents].
-enum class ReplayForm { Flat, Rollout, Nstep, Lambda };
+//            with R_t and leaves d_t in discounts; values [steps][agents];
+//   Gae      Lambda's write and fold, the scan storing G_t as the reward, +0 as the discount and G_t - V(s_t) in
+//            advantages [capacity]; values_in [agents], values_start [steps][agents] (with done, else nullptr).
+enum class ReplayForm { Flat, Rollout, Nstep, Lambda, Gae };
 struct ReplayAdd {
     ReplayForm form;
     ReplayRingView ring;
@@ -70,6 +72,8 @@ struct ReplayAdd {
     const float *values;
     int n_step;                     // n-step form: in [1, UAVTRACK_REPLAY_MAX_NSTEP]
     float lambda, gamma;
+    float *advantages;              // the GAE form's alone, as are the two below
+    const float *values_in, *values_start;
 };
 hipError_t launch_replay_add(const ReplayDevice &d, const ReplayAdd &q, hipStream_t stream);
 

@@ -41,7 +41,9 @@
 //                              per-slot store;
 //   replay_lambda_scan_kernel  the lambda form, behind replay_write_kernel and over the same window: one thread per agent
 //                              chain walks the rollout backwards, carries the lambda-return G and overwrites the written
-//                              slots' rewards with R_t, leaving d_t in the discount store.
+//                              slots' rewards with R_t, leaving d_t in the discount store;
+//   replay_gae_scan_kernel     the GAE form: the same walk and the same fold, storing the lambda-return G_t itself as the
+//                              reward, a discount of +0 and the advantage G_t - V(s_t) in a seventh per-slot store.
 
 #include "replay.h"
 #include "philox.h"
@@ -629,6 +631,99 @@ __global__ void __launch_bounds__(kLambdaW) replay_lambda_scan_kernel(LambdaArgs
     }
 }
 
+// ---- the GAE add's scan (uavtrack_replay_add_rollout_gae; include/uavtrack.h has the definitions)
+
+struct GaeArgs {
+    LambdaArgs l;                              // the lambda scan's own: the same fold over the same window
+    float *advantages;                         // [capacity], beside the ring
+    const float *values_in;                    // [agents] V(obs_in)
+    const float *values_start;                 // nullable with done: [steps][agents] V(start_obs), read where done fired
+};
+
+// The lambda scan's walk with one more load per step and three stores in place of two: the slot receives G_t itself
+// (reward), +0.0f (discount) and G_t - V(s_t) (advantage).  V(s_t) is the value of the state step t began in: values_in at
+// t == 0, else values[t - 1], a load that depends on nothing the fold carries and so travels in the step's group; where
+// done[t - 1] fired it is values_start[t - 1] instead, one dependent load on the rare path.  Grouping, window and order
+// of the fold are replay_lambda_scan_kernel's.
+template <bool DONE, bool WINDOW>
+__global__ void __launch_bounds__(kLambdaW) replay_gae_scan_kernel(GaeArgs p)
+{
+#pragma clang fp contract(off)
+    const LambdaArgs &q = p.l;
+    const AddSource &a = q.s;
+    const int64_t M = a.agents, last = a.steps - 1;
+    const float g = q.g, gl = q.gl, c = q.c;
+    const bool all_cut = gl == 0.0f;
+    for (int64_t r = (int64_t)blockIdx.x * kLambdaW + threadIdx.x; r < M; r += (int64_t)gridDim.x * kLambdaW) {
+        const float *rw = a.rewards + r, *vv = q.values + r, *vin = p.values_in + r;
+        const uint8_t *dn = DONE ? a.done + r / a.n_uav : nullptr;      // dn[u * envs] = done[u][b]
+        float G = 0.0f;
+        auto fold = [&](int64_t u, float rew, float v, unsigned fired, float vs, unsigned began) {
+            const bool cut = (u == last) | all_cut | (fired != 0);
+            const float R = cut ? rew : rew + gl * G;
+            const float d = cut ? g : c;
+            G = R + d * v;
+            const int64_t f = u * M + r;
+            if (WINDOW && f < a.w.skip) return;
+            if (DONE && began) vs = p.values_start[f - M];              // (began != 0 only for u >= 1)
+            const int64_t slot = window_slot(a.w, f);
+            q.rewards[slot] = G;
+            q.discounts[slot] = 0.0f;
+            p.advantages[slot] = G - vs;
+        };
+        // the loads of step u, none of them conditional: the lambda scan's three, the value of the state before the step
+        // and whether an episode ended there
+        auto load = [&](int64_t u, float &rew, float &v, unsigned &fired, float &vs, unsigned &began) {
+            rew = rw[u * M];
+            v = vv[u * M];
+            vs = *(u > 0 ? vv + (u - 1) * M : vin);
+            fired = 0;
+            began = 0;
+            if constexpr (DONE) {
+                fired = dn[u * a.envs];
+                began = dn[(u > 0 ? u - 1 : 0) * a.envs];
+                if (u == 0) began = 0;
+            }
+        };
+        int64_t t = a.steps;                                           // steps [0, t) are still to fold, t - 1 next
+        for (int k = (int)(a.steps % kLambdaAhead); k > 0; --k) {
+            --t;
+            float rew, v, vs;
+            unsigned fired, began;
+            load(t, rew, v, fired, vs, began);
+            fold(t, rew, v, fired, vs, began);
+        }
+        if (t == 0) continue;
+        struct Group {
+            float rew[kLambdaAhead], v[kLambdaAhead], vs[kLambdaAhead];
+            unsigned fired[kLambdaAhead], began[kLambdaAhead];
+        } A, B;
+        auto load_group = [&](int64_t end, Group &grp) {               // steps [end - kLambdaAhead, end), last step first
+#pragma unroll
+            for (int k = 0; k < kLambdaAhead; ++k)
+                load(end - 1 - k, grp.rew[k], grp.v[k], grp.fired[k], grp.vs[k], grp.began[k]);
+            __builtin_amdgcn_sched_barrier(0);                          // (the loads stay ahead of the fold behind them)
+        };
+        auto fold_group = [&](int64_t end, const Group &grp) {
+#pragma unroll
+            for (int k = 0; k < kLambdaAhead; ++k)
+                fold(end - 1 - k, grp.rew[k], grp.v[k], grp.fired[k], grp.vs[k], grp.began[k]);
+            __builtin_amdgcn_sched_barrier(0);
+        };
+        load_group(t, A);
+        while (true) {
+            load_group(t > kLambdaAhead ? t - kLambdaAhead : t, B);
+            fold_group(t, A);
+            t -= kLambdaAhead;
+            if (t == 0) break;
+            load_group(t > kLambdaAhead ? t - kLambdaAhead : t, A);
+            fold_group(t, B);
+            t -= kLambdaAhead;
+            if (t == 0) break;
+        }
+    }
+}
+
 }  // namespace
 
 // the maximum of the ring's priorities as they stand (1.0 for an empty ring) into d.parts[kReplayMaxParts]
@@ -737,13 +832,20 @@ hipError_t launch_replay_add(const ReplayDevice &d, const ReplayAdd &q, hipStrea
     // lambda: states, actions, next states and priorities (and the raw rewards, which the scan overwrites) as the one-step add
     e = q.done ? launch_over(replay_write_kernel<true>, written, kSW, st, a)
                : launch_over(replay_write_kernel<false>, written, kSW, st, a);
-    if (q.form != ReplayForm::Lambda || e != hipSuccess) return e;
+    if ((q.form != ReplayForm::Lambda && q.form != ReplayForm::Gae) || e != hipSuccess) return e;
     LambdaArgs l;
     l.s = s; l.rewards = q.ring.rewards; l.discounts = q.discounts; l.values = q.values;
     l.g = q.gamma;
     l.gl = q.gamma * q.lambda;
     l.c = q.gamma * (1.0f - q.lambda);
     const bool window = s.w.skip != 0;
+    if (q.form == ReplayForm::Gae) {
+        GaeArgs p;
+        p.l = l; p.advantages = q.advantages; p.values_in = q.values_in; p.values_start = q.values_start;
+        auto gae = q.done ? (window ? replay_gae_scan_kernel<true, true> : replay_gae_scan_kernel<true, false>)
+                          : (window ? replay_gae_scan_kernel<false, true> : replay_gae_scan_kernel<false, false>);
+        return launch_over(gae, s.agents, kLambdaW, st, p);
+    }
     auto scan = q.done ? (window ? replay_lambda_scan_kernel<true, true> : replay_lambda_scan_kernel<true, false>)
                        : (window ? replay_lambda_scan_kernel<false, true> : replay_lambda_scan_kernel<false, false>);
     return launch_over(scan, s.agents, kLambdaW, st, l);

@@ -185,6 +185,10 @@ SIGNATURES = {
                                         + [C.c_void_p] * 4 + [C.c_double] + [C.c_void_p] * 6),
     "uavtrack_learner_grad_clipped": (C.c_int, [C.c_void_p, C.c_int64] + [C.c_void_p] * 4 + [C.c_int64]
                                       + [C.c_void_p] * 4 + [C.c_double] + [C.c_void_p] * 4),
+    "uavtrack_learner_update_stored": (C.c_int, [C.c_void_p, C.c_int64] + [C.c_void_p] * 4 + [C.c_int64]
+                                       + [C.c_void_p] * 5 + [C.c_double] + [C.c_void_p] * 6),
+    "uavtrack_learner_grad_stored": (C.c_int, [C.c_void_p, C.c_int64] + [C.c_void_p] * 4 + [C.c_int64]
+                                     + [C.c_void_p] * 5 + [C.c_double] + [C.c_void_p] * 4),
     "uavtrack_learner_values": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
     "uavtrack_learner_set_target": (C.c_int, [C.c_void_p, C.c_int32, C.c_double, C.c_int64, C.c_void_p]),
     "uavtrack_learner_get_target": (C.c_int, [C.c_void_p, C.POINTER(C.c_double)]),
@@ -233,6 +237,9 @@ SIGNATURES = {
                                                     C.c_int64] + [C.c_void_p] * 6 + [C.c_int32, C.c_double, C.c_void_p]),
     "uavtrack_replay_add_rollout_lambda": (C.c_int, [C.c_void_p, C.POINTER(ReplayRing), C.c_void_p, C.c_int64, C.c_int64,
                                                      C.c_int64] + [C.c_void_p] * 7 + [C.c_double, C.c_double, C.c_void_p]),
+    "uavtrack_replay_add_rollout_gae": (C.c_int, [C.c_void_p, C.POINTER(ReplayRing), C.c_void_p, C.c_void_p, C.c_int64,
+                                                  C.c_int64, C.c_int64] + [C.c_void_p] * 9
+                                        + [C.c_double, C.c_double, C.c_void_p]),
     "uavtrack_replay_sample": (C.c_int, [C.c_void_p, C.POINTER(ReplayRing), C.c_int64, C.c_double, C.c_double,
                                          C.c_void_p, C.c_void_p, C.c_void_p]),
     "uavtrack_replay_sample_annealed": (C.c_int, [C.c_void_p, C.POINTER(ReplayRing), C.c_int64, C.c_double, C.c_double,

@@ -84,6 +84,14 @@ the side of the clip gate.  The critic, td_delta, the priorities and the entropy
 and truncated ratios multiply afterwards.  Each gradient row of a split update is standardised by its own draw's
 statistics, as K independent learners would (the choice importance weights made: each draw is normalised by its own
 maximum); learner.advantage_stats holds (mean, inv_std, std) of the last batch.
+
+Stored advantages (update(advantages=), and update_from / grad_from / update_from_many / the group path on a GAE ring,
+ring.with_gae(lam, gamma), or a sweep over one; loss="per_sample" only): the actor's advantage of row i is
+x_i = advantages[slot_i], gathered in the kernel beside the reward (uavtrack_learner_update_stored / _grad_stored), in
+delta_i's place in the logit weight, the actor-loss term and the clip gate; set_advantage applies on top ("batch"
+standardises the gathered x_i).  The critic, td_delta and the priorities keep delta_i, and on a GAE ring (reward G_t,
+discount 0) delta_i = G_t - V_now(s_i): a fixed value target.  An advantage that is NaN (unknown) or infinite refuses the
+update on the device.  Without advantages every call enqueues exactly what it enqueued.
 """
 from __future__ import annotations
 
@@ -107,9 +115,9 @@ from .rollout import ActorMLP
 # One batch as _run_batch, _grad_batch and _launch take it: n rows of a store of `capacity` slots (its dict of states,
 # actions, rewards, next_states) through idx (None: rows 0..n-1), the priorities to write back, the weights per batch row, and
 # per slot of the store the discounts and the behaviour log-probabilities (read with clip_eps, and by _ratio_weights);
-# ratio_out per batch row.
-_Batch = namedtuple("_Batch", "n store capacity idx priorities weights discounts log_mu clip_eps ratio_out",
-                    defaults=(None,) * 6)
+# ratio_out per batch row; per slot of the store again the actor's stored advantages (a GAE ring's).
+_Batch = namedtuple("_Batch", "n store capacity idx priorities weights discounts log_mu clip_eps ratio_out advantages",
+                    defaults=(None,) * 7)
 
 
 def num_params(hidden_dim: int, action_dim: int) -> int:
@@ -354,7 +362,8 @@ class DeviceActorCritic(Handle):
         [0, action_dim), an index outside the ring, an importance weight that is NaN, infinite or negative -- what a
         refused ring draw hands out --, a discount that is NaN or outside [0, 1], or, under the clipped surrogate, a
         behaviour log-probability that is NaN or positive or a ratio that is not finite, or, under a normalised
-        advantage, a mean that is not finite or an inv_std that is NaN, infinite or negative), which then changed nothing."""
+        advantage, a mean that is not finite or an inv_std that is NaN, infinite or negative, or a stored advantage that
+        is NaN or infinite), which then changed nothing."""
         self._check()
 
     # ---- the critic alone, the actor alone, and the argument checks they share
@@ -442,7 +451,7 @@ class DeviceActorCritic(Handle):
         times the truncated ratios into w_out(n) for weights under rho_bar (log_mu stays; _launch reads it under clip_eps
         alone).  `who` is "update: " for update(), whose log_mu is an argument of its own and comes with exactly one of
         the two."""
-        log_mu, clip_eps, ratio_out = b[7:]
+        log_mu, clip_eps, ratio_out = b[7:10]
         if rho_bar is None and rho_out is not None:
             raise ValueError("rho_out needs rho_bar")
         if rho_bar is not None and clip_eps is not None:
@@ -478,7 +487,8 @@ class DeviceActorCritic(Handle):
         idx, w = buffer._draw_batch(k, spec)
         b = self._corrected(_Batch(k, buffer.store, buffer.capacity, idx, buffer.priorities, w, buffer.discounts,
                                    getattr(buffer, "log_mu", None),   # an object that is no buffer gets the same answer
-                                   spec.clip_eps, spec.ratio_out), spec.rho_bar, spec.rho_out, getattr(buffer, "_ratio_out", None))
+                                   spec.clip_eps, spec.ratio_out, getattr(buffer, "advantages", None)),
+                            spec.rho_bar, spec.rho_out, getattr(buffer, "_ratio_out", None))
         if b.discounts is not None and np.float32(buffer.gamma) != np.float32(self.gamma):
             raise ValueError(f"the buffer's returns were folded with gamma = {buffer.gamma}, the learner bootstraps with "
                              f"gamma = {self.gamma}: both must be the same float32")
@@ -497,8 +507,10 @@ class DeviceActorCritic(Handle):
     def _launch(self, kind: str, b: _Batch, *outputs) -> None:
         """uavtrack_learner_<kind> ("update" or "grad") in the form the batch takes: plain, _weighted (weights, one per
         batch row), _discounted (weights or NULL, then discounts, one per slot of the store) or, with clip_eps,
-        _clipped (weights or NULL, discounts or NULL, log_mu per slot, eps, ratios or NULL); then the outputs."""
-        n, store, capacity, idx, _, weights, discounts, log_mu, clip_eps, ratio_out = b
+        _clipped (weights or NULL, discounts or NULL, log_mu per slot, eps, ratios or NULL) or, with advantages,
+        _stored (_clipped's with advantages per slot behind the discounts, log_mu NULL without clip_eps); then the
+        outputs."""
+        n, store, capacity, idx, _, weights, discounts, log_mu, clip_eps, ratio_out, advantages = b
         if isinstance(self._advantage, str) and self._advantage == "batch" and n < 2:
             raise ValueError(f'n = {n} row under set_advantage("batch"): the standard deviation of a batch needs two rows')
         w = _lib.tensor_arg(weights, torch.float32, n, self.device,
@@ -517,6 +529,15 @@ class DeviceActorCritic(Handle):
                             f"ratio_out must be a contiguous float32 tensor of {n} elements (one per batch row) on "
                             f"{self.device}")
             suffix, extra = "_clipped", (_ptr(w), _ptr(d), _ptr(log_mu), self._clip_eps_arg(clip_eps), _ptr(ratio_out))
+        if advantages is not None:
+            if self.loss != "per_sample":
+                raise ValueError('advantages on a loss="reference" learner: that form scales the actor\'s gradient sums once '
+                                 'by -mean(delta) / N, a factor a per-row advantage cannot share; use loss="per_sample"')
+            _lib.tensor_arg(advantages, torch.float32, capacity, self.device,
+                            f"advantages must be a contiguous float32 tensor of {capacity} elements (one per slot of the "
+                            f"store) on {self.device}")
+            clip = extra[2:] if clip_eps is not None else (None, 0.0, None)
+            suffix, extra = "_stored", (_ptr(w), _ptr(d), _ptr(advantages), *clip)
         name = f"uavtrack_learner_{kind}{suffix}"
         _lib.check(getattr(self._lib, name)(self._h, n, *self._batch_args(store, capacity, idx), *extra,
                                             *map(_ptr, outputs), self._stream()), name)
@@ -534,7 +555,7 @@ class DeviceActorCritic(Handle):
     def update(self, transition_dict: Dict[str, torch.Tensor], weights: Optional[torch.Tensor] = None,
                discounts: Optional[torch.Tensor] = None, log_mu: Optional[torch.Tensor] = None,
                rho_bar: Optional[float] = None, clip_eps: Optional[float] = None,
-               ratio_out: Optional[torch.Tensor] = None):
+               ratio_out: Optional[torch.Tensor] = None, advantages: Optional[torch.Tensor] = None):
         """ActorCritic.update (actor_critic.py:150-179) on a batch {states [n,12], actions [n], rewards [n],
         next_states [n,12]}: returns (actor_loss, critic_loss, td_delta) as device tensors, without synchronising.
         weights [n] (optional): importance weights w_i >= 0, one per row (the module docstring has the weighted losses);
@@ -545,7 +566,11 @@ class DeviceActorCritic(Handle):
         rho_bar > 0: the row's weight becomes w_i min(rho_bar, pi / mu) (uavtrack_learner_ratio_weights, then the
         weighted update).  clip_eps >= 0 (loss="per_sample"): the clipped surrogate of the module docstring
         (uavtrack_learner_update_clipped), ratio_out [n] (optional) receiving the ratios.  Either way a NaN or positive
-        log_mu refuses the update on the device."""
+        log_mu refuses the update on the device.
+        advantages [n] (optional, loss="per_sample"): the actor's advantage of each row, per slot of the store like
+        discounts (row i is slot i here), in td_delta's place wherever the actor uses one, the advantage mode applied on
+        top (uavtrack_learner_update_stored); the critic, td_delta and the priorities keep td_delta.  One that is NaN or
+        infinite refuses the update on the device."""
         dev = self.device
         s = torch.as_tensor(transition_dict["states"], device=dev, dtype=torch.float32).reshape(-1, _lib.OBS_DIM).contiguous()
         n = s.shape[0]
@@ -560,7 +585,10 @@ class DeviceActorCritic(Handle):
             discounts = torch.as_tensor(discounts, device=dev, dtype=torch.float32).reshape(-1).contiguous()
         if log_mu is not None:
             log_mu = torch.as_tensor(log_mu, device=dev, dtype=torch.float32).reshape(-1).contiguous()
-        return self._run_batch(self._corrected(_Batch(n, store, n, None, None, weights, discounts, log_mu, clip_eps, ratio_out),
+        if advantages is not None:
+            advantages = torch.as_tensor(advantages, device=dev, dtype=torch.float32).reshape(-1).contiguous()
+        return self._run_batch(self._corrected(_Batch(n, store, n, None, None, weights, discounts, log_mu, clip_eps, ratio_out,
+                                                      advantages),
                                                rho_bar, None, lambda n: torch.empty(n, device=dev), "update: "))
 
     def update_from(self, buffer, batch_size: int, beta: float = 0.4,
@@ -577,6 +605,10 @@ class DeviceActorCritic(Handle):
 
         An n-step ring (ring.with_nstep(n_step, gamma)) brings its per-slot discounts: the target is then
         r + discounts[slot] * V(s'), gathered in the same library call.  Its gamma must be this learner's (as float32).
+
+        A GAE ring (ring.with_gae(lam, gamma)), or a sweep over one, brings its per-slot advantages as well: the actor
+        then trains on advantages[slot] (uavtrack_learner_update_stored) and the critic on the ring's fixed value
+        targets, whatever earlier minibatches have done to the critic.  loss="per_sample" only.
 
         With a torch.distributed `group`, every rank of it takes ONE common update from all ranks' batches: the
         gradient row of this rank's batch (grad_from), an all-gather of the rows in rank order

@@ -45,6 +45,16 @@ update_from(ring, k, clip_eps=E) reads the same store inside the gradient kernel
 (uavtrack_learner_update_clipped); a drawn slot that is still NaN refuses that update on the device.  Without
 with_behaviour a ring is exactly what it was.
 
+Fixed GAE advantages.  ring.with_gae(lam, gamma) makes either ring a GAE ring instead of an n-step or lambda ring:
+add_rollout(obs_in, out, critic=learner) (or add_rollout_gae(values=, values_in=, values_start=)) runs the lambda add's fold and stores,
+per slot, the lambda-return G_t itself as the reward, a discount of +0 (so the learner's target r + discount * V(s') is
+the fixed value target G_t) and the advantage G_t - V(s_t) in a seventh per-slot store, `advantages`
+(uavtrack_replay_add_rollout_gae): GAE(lambda), bootstrapped at the rollout's last step and at a fired done.  NaN means
+unknown.  DeviceActorCritic.update_from and its relatives pick the store up from the ring or from a sweep over it
+(uavtrack_learner_update_stored): advantage and value target are then constants of the iteration, whatever the
+minibatches before have done to the critic.  Composes with with_behaviour().  Without with_gae a ring is exactly what it
+was.
+
 On-policy epochs.  ring.sweep(batch_size, window="last") returns a RingSweep over a window of either ring -- by default
 the slots the most recent add wrote -- whose consecutive draws are the disjoint minibatches of an epoch, every slot of the
 window once per epoch, epoch after epoch in another order (uavtrack_replay_sample_sweep, numbered by a device cursor the
@@ -74,6 +84,10 @@ class ReplayRing(Handle):
     gamma: Optional[float] = None
     lam: Optional[float] = None                 # with_lambda: the ring stores lambda-returns
     _values: Optional[torch.Tensor] = None      # add_rollout(critic=...)'s buffer, kept and only grown
+    advantages: Optional[torch.Tensor] = None   # with_gae: per-slot fixed advantages, NaN where not known
+    gae: bool = False                           # with_gae: lam and gamma are GAE's, the ring stores G_t, +0 and G_t - V(s_t)
+    _values_in: Optional[torch.Tensor] = None   # a GAE ring's add_rollout(critic=...): V(obs_in) and V(start_obs), likewise
+    _values_start: Optional[torch.Tensor] = None
     log_mu: Optional[torch.Tensor] = None       # with_behaviour: per-slot behaviour log-probabilities
     _w: Optional[torch.Tensor] = None           # a prioritised ring's importance weights of update_from's draws
     _rho_w: Optional[torch.Tensor] = None       # with_behaviour: update_from's ratio weights (a prioritised ring: its _w)
@@ -103,6 +117,9 @@ class ReplayRing(Handle):
         n_step = int(n_step)
         if not 1 <= n_step <= _lib.REPLAY_MAX_NSTEP:
             raise ValueError(f"n_step must be in [1, {_lib.REPLAY_MAX_NSTEP}], got {n_step}")
+        if self.gae and n_step > 1:
+            raise ValueError(f"with_nstep({n_step}) on a GAE ring: a ring stores n-step returns, lambda-returns or GAE "
+                             f"advantages, one of the three")
         if self.lam is not None and n_step > 1:
             raise ValueError(f"with_nstep({n_step}) on a lambda ring: a ring stores n-step returns or lambda-returns")
         if gamma is None:
@@ -126,11 +143,42 @@ class ReplayRing(Handle):
             raise ValueError(f"lam must be in [0, 1], got {lam}")
         if not 0.0 <= gamma <= 1.0:
             raise ValueError(f"gamma must be in [0, 1], got {gamma}")
+        if self.gae:
+            raise ValueError("with_lambda on a GAE ring: a ring stores n-step returns, lambda-returns or GAE advantages, "
+                             "one of the three")
         if self.n_step > 1:
             raise ValueError(f"with_lambda on a ring with n_step = {self.n_step}: a ring stores n-step returns or "
                              f"lambda-returns")
         self.lam, self.gamma = lam, gamma
         self.discounts = torch.full((self.capacity,), gamma, dtype=torch.float32, device=self.device)
+        return self
+
+    def with_gae(self, lam: float, gamma: float) -> "ReplayRing":
+        """Makes this ring a GAE ring and returns it: ReplayRing(capacity, device).with_gae(0.95, gamma=0.99).  The ring
+        then owns `advantages` [capacity] float32, every slot NaN ("unknown") to begin with, and `discounts` [capacity]
+        (kept if the ring has them already, else every slot float32(gamma), which is what one-step transitions it may
+        already hold bootstrap with); add_rollout stores the lambda-return as the reward, +0 as the discount and
+        G_t - V(s_t) as the advantage, from `critic=` or from add_rollout_gae's `values=, values_in=, values_start=`.  A ring is an n-step
+        ring (n_step > 1), a lambda ring or a GAE ring: with_gae raises after either, and they raise after it.
+        Composes with with_behaviour in either order."""
+        lam, gamma = float(lam), float(gamma)
+        if not 0.0 <= lam <= 1.0:
+            raise ValueError(f"lam must be in [0, 1], got {lam}")
+        if not 0.0 <= gamma <= 1.0:
+            raise ValueError(f"gamma must be in [0, 1], got {gamma}")
+        if self.n_step > 1:
+            raise ValueError(f"with_gae on a ring with n_step = {self.n_step}: a ring stores n-step returns, lambda-returns "
+                             f"or GAE advantages, one of the three")
+        if self.lam is not None and not self.gae:
+            raise ValueError("with_gae on a lambda ring: a ring stores n-step returns, lambda-returns or GAE advantages, "
+                             "one of the three")
+        if self.discounts is not None and not self.gae and self.gamma != gamma:
+            raise ValueError(f"with_gae(gamma = {gamma}) on a ring whose discounts were made with gamma = {self.gamma}")
+        self.gae, self.lam, self.gamma = True, lam, gamma
+        if self.discounts is None:
+            self.discounts = torch.full((self.capacity,), gamma, dtype=torch.float32, device=self.device)
+        if self.advantages is None:
+            self.advantages = torch.full((self.capacity,), float("nan"), dtype=torch.float32, device=self.device)
         return self
 
     def with_behaviour(self) -> "ReplayRing":
@@ -153,18 +201,23 @@ class ReplayRing(Handle):
         dst[start:start + head] = src[n - k:n - k + head]
         dst[:k - head] = src[n - k + head:]
 
-    def _rollout_values(self, obs: torch.Tensor, critic, values: Optional[torch.Tensor]) -> torch.Tensor:
-        """The lambda add's values [T*B*N]: the caller's, or the critic's over obs into the ring's own buffer."""
+    def _rollout_values(self, obs: torch.Tensor, critic, values: Optional[torch.Tensor], what: str = "values",
+                        of: str = "obs") -> torch.Tensor:
+        """The lambda add's values [T*B*N]: the caller's, or the critic's over obs into the ring's own buffer.  A GAE
+        ring's values_in (over obs_in) and values_start (over start_obs) likewise, each into a buffer of its own."""
         n = obs.numel() // _lib.OBS_DIM
         if (critic is None) == (values is None):
-            raise ValueError("add_rollout: a lambda ring needs exactly one of critic= and values=")
+            raise ValueError(f"add_rollout: a {'GAE' if self.gae else 'lambda'} ring needs exactly one of critic= and "
+                             f"{what}=")
         if values is not None:
             return _lib.tensor_arg(values, torch.float32, n, self.device,
-                                   f"add_rollout: values must be a contiguous float32 tensor of {n} elements (one per "
-                                   f"row of obs) on {self.device}")
-        if self._values is None or self._values.numel() < n:
-            self._values = torch.empty(n, dtype=torch.float32, device=self.device)
-        buf = self._values[:n]
+                                   f"add_rollout: {what} must be a contiguous float32 tensor of {n} elements (one per "
+                                   f"row of {of}) on {self.device}")
+        held = getattr(self, "_" + what)
+        if held is None or held.numel() < n:
+            held = torch.empty(n, dtype=torch.float32, device=self.device)
+            setattr(self, "_" + what, held)
+        buf = held[:n]
         if isinstance(critic, torch.nn.Module):
             with torch.no_grad():
                 buf.copy_(critic(obs.reshape(-1, _lib.OBS_DIM)).reshape(n))
@@ -200,10 +253,13 @@ class ReplayRing(Handle):
         flattened).  One library call writes the last min(n, capacity) of them (a prioritised ring: at the current
         maximum priority).  A ring with discounts then fills the same slots' discounts from an optional "discounts"
         entry [n], or with float32(gamma) where it is absent (a torch slice copy: the flat add is not the hot path).  A
-        behaviour ring fills their log_mu likewise from an optional "log_mu" entry [n], or with NaN ("unknown")."""
+        behaviour ring fills their log_mu likewise from an optional "log_mu" entry [n], or with NaN ("unknown"), and a GAE
+        ring their advantages from an optional "advantages" entry [n], or with NaN; on any other ring that entry raises."""
         n = transition_dict["actions"].numel()
         if n < 1:
             return
+        if self.advantages is None and transition_dict.get("advantages") is not None:
+            raise ValueError('add: "advantages" is for a GAE ring (ring.with_gae(lam, gamma))')
         dev, D = self.device, _lib.OBS_DIM
         s = transition_dict["states"].to(dev, torch.float32).reshape(n, D).contiguous()
         a = transition_dict["actions"].to(dev, torch.int32).reshape(n).contiguous()
@@ -222,6 +278,11 @@ class ReplayRing(Handle):
             m = torch.full((n,), float("nan"), dtype=torch.float32, device=dev) if m is None \
                 else m.to(dev, torch.float32).reshape(n)
             self._copy_last(self.log_mu, m, n)
+        x = transition_dict.get("advantages")
+        if self.advantages is not None:
+            x = torch.full((n,), float("nan"), dtype=torch.float32, device=dev) if x is None \
+                else x.to(dev, torch.float32).reshape(n)
+            self._copy_last(self.advantages, x, n)
         self._advance(n)
 
     def add_rollout(self, obs_in: torch.Tensor, out: Dict[str, torch.Tensor], *, critic=None,
@@ -235,9 +296,28 @@ class ReplayRing(Handle):
         (uavtrack_replay_add_rollout_lambda) and needs exactly one of `values` (float32, contiguous, T*B*N elements:
         V(obs[t][b][i])) and `critic` (an object with .values(states, out=), a DeviceActorCritic, or a torch module such
         as ValueMLP, called under no_grad on obs.reshape(-1, 12)); the critic's values go into a buffer the ring keeps
-        and only grows.  Any other ring given either raises.  A behaviour ring (with_behaviour) is added to through
-        add_rollout_behaviour, which says who acted; this call refuses it."""
+        and only grows.  Any other ring given either raises.  A GAE ring (with_gae) stores G_t, +0 and the advantage
+        (uavtrack_replay_add_rollout_gae) and takes `critic`, run over obs_in, over obs and, when the rollout carries it,
+        over start_obs, into three such buffers; its explicit form, three value arrays, is add_rollout_gae's.  A
+        behaviour ring (with_behaviour) is added to through add_rollout_behaviour, which says who acted; this call
+        refuses it."""
         self._add_rollout(obs_in, out, critic, values, None, None)
+
+    def add_rollout_gae(self, obs_in: torch.Tensor, out: Dict[str, torch.Tensor], *, critic=None,
+                        values: Optional[torch.Tensor] = None, values_in: Optional[torch.Tensor] = None,
+                        values_start: Optional[torch.Tensor] = None, behaviour=None,
+                        log_mu: Optional[torch.Tensor] = None) -> None:
+        """add_rollout on a GAE ring (with_gae; any other ring raises) with the explicit form spelled out: either
+        `critic` (as add_rollout: run over obs_in, obs and start_obs), or all of values= (float32, contiguous, T*B*N
+        elements: V(obs[t][b][i])), values_in= (B*N: V(obs_in[b][i])) and, exactly when `out` carries start_obs,
+        values_start= (T*B*N: V(start_obs[t][b][i]), read only where done fired).  add_rollout and
+        add_rollout_behaviour keep the parameter lists they had, so the three arrays travel through this call alone.
+        behaviour=, log_mu=: as add_rollout_behaviour, required on a behaviour ring and refused on any other."""
+        if not self.gae:
+            raise ValueError("add_rollout_gae: values_in= and values_start= are for a GAE ring (ring.with_gae(lam, gamma))")
+        if self.log_mu is None and (behaviour is not None or log_mu is not None):
+            raise ValueError("add_rollout_gae: behaviour= and log_mu= are for a behaviour ring (ring.with_behaviour())")
+        self._add_rollout(obs_in, out, critic, values, behaviour, log_mu, values_in, values_start, explicit=True)
 
     def add_rollout_behaviour(self, obs_in: torch.Tensor, out: Dict[str, torch.Tensor], *, behaviour=None,
                               log_mu: Optional[torch.Tensor] = None, critic=None,
@@ -257,12 +337,16 @@ class ReplayRing(Handle):
             raise ValueError("add_rollout_behaviour: behaviour= and log_mu= are for a behaviour ring (ring.with_behaviour())")
         self._add_rollout(obs_in, out, critic, values, behaviour, log_mu)
 
-    def _add_rollout(self, obs_in, out, critic, values, behaviour, log_mu) -> None:
+    def _add_rollout(self, obs_in, out, critic, values, behaviour, log_mu, values_in=None, values_start=None,
+                     explicit=False) -> None:
         if self.log_mu is not None and (behaviour is None) == (log_mu is None):
             raise ValueError("add_rollout: a behaviour ring needs exactly one of behaviour= and log_mu= "
                              "(add_rollout_behaviour)")
         if self.lam is None and (critic is not None or values is not None):
             raise ValueError("add_rollout: critic= and values= are for a lambda ring (ring.with_lambda(lam, gamma))")
+        if self.gae and values is not None and not explicit:
+            raise ValueError("add_rollout: a GAE ring takes critic= here; the explicit form values=, values_in=, "
+                             "values_start= is add_rollout_gae's")
         obs, act, rew = out["obs"], out["actions"], out["reward"]
         so = out.get("start_obs")
         T = obs.shape[0]
@@ -287,9 +371,18 @@ class ReplayRing(Handle):
         source = (obs_in.data_ptr(), obs.data_ptr(), act.data_ptr(), rew.data_ptr())     # (void * arguments take integers)
         if self.lam is not None or self.discounts is not None:
             if obs.dim() != 4:
-                raise ValueError(f"add_rollout: {'an n-step' if self.lam is None else 'a lambda'} ring needs obs as [T,B,N,12]")
+                raise ValueError(f"add_rollout: {'an n-step' if self.lam is None else 'a GAE' if self.gae else 'a lambda'} "
+                                 f"ring needs obs as [T,B,N,12]")
             args = (self.discounts.data_ptr(), T, obs.shape[1], obs.shape[2], *source, *episode_ends)
-            if self.lam is not None:
+            if self.gae:
+                name = "uavtrack_replay_add_rollout_gae"
+                if so is None and values_start is not None:
+                    raise ValueError("add_rollout: values_start= comes with a rollout that carries start_obs")
+                v = self._rollout_values(obs, critic, values)
+                v_in = self._rollout_values(obs_in, critic, values_in, "values_in", "obs_in")
+                v_so = None if so is None else self._rollout_values(so, critic, values_start, "values_start", "start_obs")
+                args = (args[0], self.advantages.data_ptr(), *args[1:], _ptr(v), _ptr(v_in), _ptr(v_so), self.lam, self.gamma)
+            elif self.lam is not None:
                 name = "uavtrack_replay_add_rollout_lambda"
                 args += (_ptr(self._rollout_values(obs, critic, values)), self.lam, self.gamma)
             else:
@@ -370,12 +463,15 @@ class ReplayRing(Handle):
         return RingSweep(self, batch_size, window)
 
     def _gather(self, idx) -> Dict[str, torch.Tensor]:
-        """The transitions dict at idx: KEYS, "discounts" on a ring that has them and "log_mu" on a behaviour ring."""
+        """The transitions dict at idx: KEYS, "discounts" on a ring that has them, "log_mu" on a behaviour ring and
+        "advantages" on a GAE ring."""
         out = {key: self.store[key][idx] for key in KEYS}
         if self.discounts is not None:
             out["discounts"] = self.discounts[idx]
         if self.log_mu is not None:
             out["log_mu"] = self.log_mu[idx]
+        if self.advantages is not None:
+            out["advantages"] = self.advantages[idx]
         return out
 
 
@@ -458,7 +554,7 @@ class RingSweep:
     performs E epochs.  The ring's own call counter is not touched: its draws are what they are without any sweep.
 
     Where DeviceActorCritic.update_from, grad_from, update_from_many (a list of sweeps, one per shard) and the group path
-    take a buffer they take a sweep: it presents the ring's stores, priorities, discounts and behaviour store, its count
+    take a buffer they take a sweep: it presents the ring's stores, priorities, discounts, behaviour store and advantages, its count
     is the window's length, and its _draw_batch is the next minibatch.  rho_bar, clip_eps, ratio_out and the n-step and
     lambda discounts compose as on the ring, and a prioritised ring's priorities still receive |td_delta|.  A sweep is
     uniform and has no weights: importance=True and beta_final raise, and so does a batch size other than the sweep's."""
@@ -558,6 +654,7 @@ class RingSweep:
     discounts = property(lambda self: self.ring.discounts)
     gamma = property(lambda self: self.ring.gamma)
     log_mu = property(lambda self: self.ring.log_mu)
+    advantages = property(lambda self: self.ring.advantages)
 
     def _ratio_out(self, k: int) -> torch.Tensor:
         return self.ring._ratio_out(k)
