@@ -86,10 +86,19 @@ int accept_advantage_rows(const char *fn, const uavtrack_learner *l, int64_t n)
     return 0;
 }
 
+// what a per-row factor of the actor's gradient (`what`, a per-row `factor`) meets on a reference-loss learner
+int refuse_on_reference(const char *fn, const char *what, const char *factor)
+{
+    return fail("%s: %s on a UAVTRACK_LOSS_REFERENCE learner: that form scales the actor's gradient sums once by "
+                "-mean(delta) / N, a factor a per-row %s cannot share; use UAVTRACK_LOSS_PER_SAMPLE", fn, what, factor);
+}
+
 enum class Batch { Update, Grad };
 
 // Every host-side refusal of the ten batch entry points (uavtrack_learner_update, _grad and their _weighted,
-// _discounted, _clipped and _stored forms), in one order.  Nothing has been enqueued when one of them fires.
+// _discounted, _clipped and _stored forms), in one order: the tests all forms share, a _stored call's own, then the
+// clip's wherever a log_mu is required (_clipped) or given (_stored; without one clip_eps is not read).  Nothing has
+// been enqueued when one of them fires.
 int accept_learner_batch(const char *fn, const uavtrack_learner *l, const LearnerLaunch &q, Batch kind, const float *row)
 {
     if (!l) return fail("%s: null handle", fn);
@@ -103,18 +112,13 @@ int accept_learner_batch(const char *fn, const uavtrack_learner *l, const Learne
         return 1;
     if (q.stored) {
         if (!q.advantages) return fail("%s: advantages must not be null", fn);
-        if (!l->d.per_sample)
-            return fail("%s: stored advantages on a UAVTRACK_LOSS_REFERENCE learner: that form scales the actor's gradient "
-                        "sums once by -mean(delta) / N, a factor a per-row advantage cannot share; use "
-                        "UAVTRACK_LOSS_PER_SAMPLE", fn);
-        if (!q.log_mu) return 0;                                    // (clip_eps is read with log_mu alone)
+        if (!l->d.per_sample) return refuse_on_reference(fn, "stored advantages", "advantage");
     }
-    if (!q.clipped) return 0;
-    if (!q.log_mu) return fail("%s: log_mu must not be null", fn);
-    if (!(q.clip_eps >= 0)) return fail("%s: clip_eps = %g must be >= 0 (+inf: never clips)", fn, q.clip_eps);
-    if (!l->d.per_sample)
-        return fail("%s: the clipped surrogate on a UAVTRACK_LOSS_REFERENCE learner: that form scales the actor's gradient "
-                    "sums once by -mean(delta) / N, a factor a per-row gate cannot share; use UAVTRACK_LOSS_PER_SAMPLE", fn);
+    if (q.clipped || q.log_mu) {
+        if (!q.log_mu) return fail("%s: log_mu must not be null", fn);
+        if (!(q.clip_eps >= 0)) return fail("%s: clip_eps = %g must be >= 0 (+inf: never clips)", fn, q.clip_eps);
+        if (!l->d.per_sample) return refuse_on_reference(fn, "the clipped surrogate", "gate");
+    }
     return 0;
 }
 
@@ -124,7 +128,7 @@ int run_learner_batch(const char *fn, uavtrack_learner *learner, LearnerLaunch q
 {
     if (accept_learner_batch(fn, learner, q, kind, row)) return 1;
     ON_DEVICE(learner->cfg.device_id);
-    if (q.clipped && q.log_mu) {
+    if (q.log_mu) {
         const float eps32 = (float)q.clip_eps;
         q.clip_lo = 1.0f - eps32; q.clip_hi = 1.0f + eps32;
     }
@@ -404,7 +408,7 @@ int uavtrack_learner_update_stored(uavtrack_learner *learner, int64_t n, const f
 {
     LearnerLaunch q = {n, capacity, states, rewards, next_states, actions, indices, weights, discounts};
     q.stored = true; q.advantages = advantages;
-    q.clipped = true; q.log_mu = log_mu; q.clip_eps = clip_eps; q.ratio = log_mu ? ratio_out : nullptr;
+    q.log_mu = log_mu; q.clip_eps = clip_eps; q.ratio = log_mu ? ratio_out : nullptr;
     q.actor_loss = actor_loss; q.critic_loss = critic_loss; q.td_delta = td_delta; q.priorities = priorities;
     return run_learner_batch(__func__, learner, q, Batch::Update, nullptr, stream);
 }
@@ -417,7 +421,7 @@ int uavtrack_learner_grad_stored(uavtrack_learner *learner, int64_t n, const flo
 {
     LearnerLaunch q = {n, capacity, states, rewards, next_states, actions, indices, weights, discounts};
     q.stored = true; q.advantages = advantages;
-    q.clipped = true; q.log_mu = log_mu; q.clip_eps = clip_eps; q.ratio = log_mu ? ratio_out : nullptr;
+    q.log_mu = log_mu; q.clip_eps = clip_eps; q.ratio = log_mu ? ratio_out : nullptr;
     q.td_delta = td_delta;
     return run_learner_batch(__func__, learner, q, Batch::Grad, row, stream);
 }

@@ -81,7 +81,7 @@ struct LearnerDevice {
     float *adv_unit;                // [2] {0.0f, 1.0f}: the pair a stored advantage in raw mode is "standardised" by
 };
 enum { kAdvantageRaw = 0, kAdvantageBatch = 1, kAdvantageGiven = 2 };
-// One batch of uavtrack_learner_update / _grad in any of their forms.  The eight entry points fill it as they were
+// One batch of uavtrack_learner_update / _grad in any of their forms.  The ten entry points fill it as they were
 // called (the first nine fields in this order, by aggregate initialisation); what a form does not take stays zero.
 struct LearnerLaunch {
     int64_t n, capacity;
@@ -100,8 +100,8 @@ struct LearnerLaunch {
     float *actor_loss, *critic_loss, *td_delta, *priorities;
 };
 int learner_rows_per_tile(int hidden);
-size_t learner_lds_bytes(const LearnerLayout &L, int rows, bool clipped = false,    // clipped: R more floats, behind the rest
-                         bool stored = false);                                      // stored: 2 R more (log_mu, the advantage)
+// extra_floats_per_row: a variant's lds_extra (learner_variants.h), behind the rest
+size_t learner_lds_bytes(const LearnerLayout &L, int rows, int extra_floats_per_row = 0);
 int learner_groups(const LearnerLayout &L, int64_t n);
 int learner_clip_groups(const LearnerLayout &L);   // workgroups of the clip's gradient pass: ceil(P / 256)
 int64_t learner_adv_chunks(int64_t n);             // 256-row chunks of the advantage statistics: ceil(n / 256)

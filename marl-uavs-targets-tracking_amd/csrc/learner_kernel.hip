@@ -62,22 +62,23 @@
 // Batch-normalised advantages (uavtrack_learner_set_advantage, per-sample form only, off by default): the advantage that
 // multiplies grad log p, gates the clip and enters the actor loss becomes A_i = fl(fl(delta_i - mean) * inv_std), mean and
 // inv_std read from three floats of device memory; the critic, td_delta, loss word 1 and the priorities keep delta_i.
-// learner_grad_adv_kernel and its three siblings are the same body with that line (kAdv), over an argument struct of
-// their own; the other six keep their arguments and their code.  In batch mode three small kernels run in front:
+// learner_grad_adv_kernel and its three siblings are the same body with that line (kAdv), reading the pair through
+// GradArgs::stats; the other six never read that field.  In batch mode three small kernels run in front:
 // learner_td_kernel forms delta_i of every row by the gradient kernel's own chains (the bits it will form) and each
 // 256-row chunk's fp64 sum, learner_adv_sq_kernel each chunk's sum of squared deviations, learner_adv_stats_kernel the
 // three floats; learner_adv_seal_kernel, behind the gradient kernel, turns them into NaN where the update was refused.
 //
-// Which of the ten instantiations of the gradient body a launch takes is learner_variants.h's table and its
+// Which of the fourteen instantiations of the gradient body a launch takes is learner_variants.h's table and its
 // learner_grad_variant; the host code below expands the same table over the kernels (kGradKernels), prepares every row's
-// LDS attribute from it and launches through it, each kernel receiving the filled GradStoredArgs cut down to its own type.
+// LDS attribute from it and launches through it.  Every kernel takes the one GradArgs, filled whole by launch_grad, and
+// reads of it what its flags compile in.
 //
 // Stored advantages (uavtrack_learner_update_stored / _grad_stored, per-sample form only): the advantage the actor starts
 // from is x_i = advantages[src_i], a per-slot store gathered beside the reward (a GAE ring's seventh store), in delta_i's
 // place wherever the actor uses an advantage; the advantage mode applies on top, A_i = fl(fl(x_i - mean) * inv_std), raw
 // being the handle's constant pair {0, 1}.  The critic, td_delta, loss word 1 and the priorities keep delta_i.  Four more
-// instantiations of the body (kStored; always kReg and kAdv, by kTgt and kClip) with a table and a picker of their own in
-// learner_variants.h; the ten above keep their arguments and their code.  In batch mode learner_adv_gather_kernel writes
+// instantiations of the body (kStored; always kReg and kAdv, by kTgt and kClip), the last four rows of the table in
+// learner_variants.h; the ten above never read GradArgs::advantages.  In batch mode learner_adv_gather_kernel writes
 // x_i into the TD scratch in learner_td_kernel's place and the statistics kernels run over it unchanged.  A drawn
 // advantage that is NaN or infinite sets status bit 7 (value 128) and the row is not used.
 //
@@ -90,7 +91,6 @@
 #include <hip/hip_runtime.h>
 #include <cmath>
 #include <cstdint>
-#include <type_traits>
 
 namespace uavtrack {
 
@@ -98,7 +98,9 @@ namespace {
 
 constexpr int kLW = 256;   // threads per workgroup of the grad kernel
 
-// the launch's shape, folded on the host
+// The launch's shape, folded on the host: one struct for all fourteen kernels.  Every kernel reads the fields down to
+// `target`; behind them a field is read only under the flag its comment names, and a kernel compiled without that flag
+// holds no load of it.
 struct GradArgs {
     const float *params;            // [P] both networks, LearnerLayout order
     const float *states, *rewards, *next_states;
@@ -109,7 +111,7 @@ struct GradArgs {
     float *partials;                // [groups][P + 4]
     float *td_delta;                // nullable [n]
     int *status;                    // bit 0: action out of range, bit 1: index out of range, bit 2: weight NaN, inf or < 0
-                                    // (bit 3: a bad discount, below; bit 4: a bad log_mu or ratio, GradClipArgs)
+                                    // (bit 3: a bad discount, below; bit 4: a bad log_mu or ratio, further below)
     LearnerLayout L;
     int rows;                       // R rows per tile
     float gamma;
@@ -119,26 +121,16 @@ struct GradArgs {
     const float *discounts;         // nullable [capacity], slot order: the row's discount d in y = r + d V(s') (null: gamma);
                                     // status bit 3: a discount that is NaN, negative or above 1
     const float *target;            // the target critic's block [14 H + 1] at its own offsets 0, 12 H, 13 H, 14 H
-                                    // (learner_grad_target_kernel / _reg_target_kernel only; null otherwise)
-};
-
-// what the clipped surrogate's two kernels take on top (learner_grad_clip_kernel / _clip_target_kernel): a type of its
-// own, so that the other four keep their kernel arguments, and with them their code, word for word
-struct GradClipArgs : GradArgs {
+                                    // (read under kTgt; null otherwise)
+    // read under kClip (the clipped surrogate):
     const float *log_mu;            // [capacity], slot order: behaviour log-probabilities; status bit 4: a drawn slot whose
                                     // log_mu is NaN or > 0, or whose ratio is not finite
     float clip_lo, clip_hi;         // 1 - eps, 1 + eps in fp32, folded on the host
     float *ratio;                   // nullable [n]: r_i of batch row i, NaN for a row that set a status bit
-};
-
-// what the four kernels of a normalised advantage take on top (learner_grad_adv_kernel and its siblings)
-struct GradAdvArgs : GradClipArgs {
+    // read under kAdv (a normalised advantage, and every stored one):
     const float *stats;             // [2] {mean, inv_std}, read when the launch executes; status bit 6 (value 64): a mean
                                     // that is not finite, or an inv_std that is NaN, infinite or negative
-};
-
-// what the four kernels of a stored advantage take on top (learner_grad_stored_kernel and its siblings)
-struct GradStoredArgs : GradAdvArgs {
+    // read under kStored:
     const float *advantages;        // [capacity], slot order: the actor's advantage x_i of a row, in delta_i's place; status
                                     // bit 7 (value 128): a drawn slot whose advantage is NaN or infinite
 };
@@ -150,9 +142,7 @@ struct GradStoredArgs : GradAdvArgs {
 // kAdv (with kReg): the row's advantage is fl(fl(delta - mean) * inv_std) wherever the actor uses one.
 // kStored (with kAdv): the advantage the line above starts from is advantages[src], gathered into xa, not delta.
 template <bool kReg, bool kTgt = false, bool kClip = false, bool kAdv = false, bool kStored = false>
-__device__ __forceinline__ void learner_grad_body(
-    const std::conditional_t<kStored, GradStoredArgs,
-                             std::conditional_t<kAdv, GradAdvArgs, std::conditional_t<kClip, GradClipArgs, GradArgs>>> &a)
+__device__ __forceinline__ void learner_grad_body(const GradArgs &a)
 {
     static_assert(kReg || !kAdv, "the normalised advantage lives in the kReg block");
     static_assert(kAdv || !kStored, "a stored advantage passes through the normalised advantage's line");
@@ -449,20 +439,20 @@ __global__ void __launch_bounds__(kLW) learner_grad_target_kernel(GradArgs a) { 
 __global__ void __launch_bounds__(kLW) learner_grad_reg_target_kernel(GradArgs a) { learner_grad_body<true, true>(a); }
 
 // the clipped surrogate (uavtrack_learner_update_clipped / _grad_clipped), without and with a target critic
-__global__ void __launch_bounds__(kLW) learner_grad_clip_kernel(GradClipArgs a) { learner_grad_body<true, false, true>(a); }
-__global__ void __launch_bounds__(kLW) learner_grad_clip_target_kernel(GradClipArgs a) { learner_grad_body<true, true, true>(a); }
+__global__ void __launch_bounds__(kLW) learner_grad_clip_kernel(GradArgs a) { learner_grad_body<true, false, true>(a); }
+__global__ void __launch_bounds__(kLW) learner_grad_clip_target_kernel(GradArgs a) { learner_grad_body<true, true, true>(a); }
 
 // the normalised advantage (uavtrack_learner_set_advantage), without and with the clipped surrogate and a target critic
-__global__ void __launch_bounds__(kLW) learner_grad_adv_kernel(GradAdvArgs a) { learner_grad_body<true, false, false, true>(a); }
-__global__ void __launch_bounds__(kLW) learner_grad_adv_target_kernel(GradAdvArgs a) { learner_grad_body<true, true, false, true>(a); }
-__global__ void __launch_bounds__(kLW) learner_grad_adv_clip_kernel(GradAdvArgs a) { learner_grad_body<true, false, true, true>(a); }
-__global__ void __launch_bounds__(kLW) learner_grad_adv_clip_target_kernel(GradAdvArgs a) { learner_grad_body<true, true, true, true>(a); }
+__global__ void __launch_bounds__(kLW) learner_grad_adv_kernel(GradArgs a) { learner_grad_body<true, false, false, true>(a); }
+__global__ void __launch_bounds__(kLW) learner_grad_adv_target_kernel(GradArgs a) { learner_grad_body<true, true, false, true>(a); }
+__global__ void __launch_bounds__(kLW) learner_grad_adv_clip_kernel(GradArgs a) { learner_grad_body<true, false, true, true>(a); }
+__global__ void __launch_bounds__(kLW) learner_grad_adv_clip_target_kernel(GradArgs a) { learner_grad_body<true, true, true, true>(a); }
 
 // a stored advantage (uavtrack_learner_update_stored / _grad_stored), without and with the clipped surrogate and a target critic
-__global__ void __launch_bounds__(kLW) learner_grad_stored_kernel(GradStoredArgs a) { learner_grad_body<true, false, false, true, true>(a); }
-__global__ void __launch_bounds__(kLW) learner_grad_stored_target_kernel(GradStoredArgs a) { learner_grad_body<true, true, false, true, true>(a); }
-__global__ void __launch_bounds__(kLW) learner_grad_stored_clip_kernel(GradStoredArgs a) { learner_grad_body<true, false, true, true, true>(a); }
-__global__ void __launch_bounds__(kLW) learner_grad_stored_clip_target_kernel(GradStoredArgs a) { learner_grad_body<true, true, true, true, true>(a); }
+__global__ void __launch_bounds__(kLW) learner_grad_stored_kernel(GradArgs a) { learner_grad_body<true, false, false, true, true>(a); }
+__global__ void __launch_bounds__(kLW) learner_grad_stored_target_kernel(GradArgs a) { learner_grad_body<true, true, false, true, true>(a); }
+__global__ void __launch_bounds__(kLW) learner_grad_stored_clip_kernel(GradArgs a) { learner_grad_body<true, false, true, true, true>(a); }
+__global__ void __launch_bounds__(kLW) learner_grad_stored_clip_target_kernel(GradArgs a) { learner_grad_body<true, true, true, true, true>(a); }
 
 // Clears the update's status word (a kernel node rather than a memset node, so a captured update is a chain of kernels)
 __global__ void learner_begin_kernel(int *status)
@@ -904,9 +894,9 @@ int learner_rows_per_tile(int hidden)
     return r > 256 ? 256 : r;
 }
 
-size_t learner_lds_bytes(const LearnerLayout &L, int rows, bool clipped, bool stored)
+size_t learner_lds_bytes(const LearnerLayout &L, int rows, int extra_floats_per_row)
 {
-    return sizeof(float) * ((size_t)L.P + (size_t)rows * (24 + 3 * L.H + L.A + 2 + 4 + 2 + (stored ? 2 : clipped ? 1 : 0))) +
+    return sizeof(float) * ((size_t)L.P + (size_t)rows * (24 + 3 * L.H + L.A + 2 + 4 + 2 + extra_floats_per_row)) +
            sizeof(int) * (size_t)rows;
 }
 
@@ -921,21 +911,9 @@ int learner_clip_groups(const LearnerLayout &L) { return (L.P + kClipThreads - 1
 
 namespace {
 
-// One launch of a gradient kernel: the fully filled arguments, cut down to the kernel's own parameter type.
-template <typename Args, void (*kKernel)(Args)>
-void launch_variant(dim3 grid, size_t lds, hipStream_t st, const GradStoredArgs &a)
-{
-    hipLaunchKernelGGL(kKernel, grid, dim3(kLW), lds, st, static_cast<const Args &>(a));
-}
-
-// learner_variants.h's two tables over the kernels themselves, each in its order
-struct GradKernel {
-    const void *kernel;
-    void (*launch)(dim3 grid, size_t lds, hipStream_t st, const GradStoredArgs &a);
-};
-#define GRAD_KERNEL_ROW(k, Args, reg, tgt, clip, adv, lds) {reinterpret_cast<const void *>(k), launch_variant<Args, k>},
-const GradKernel kGradKernels[kLearnerGradVariantCount] = {UAVTRACK_LEARNER_GRAD_VARIANTS(GRAD_KERNEL_ROW)};
-const GradKernel kStoredKernels[kLearnerStoredVariantCount] = {UAVTRACK_LEARNER_STORED_VARIANTS(GRAD_KERNEL_ROW)};
+// learner_variants.h's table over the kernels themselves, in its order
+#define GRAD_KERNEL_ROW(k, reg, tgt, clip, adv, stored, lds) k,
+void (*const kGradKernels[kLearnerGradVariantCount])(GradArgs) = {UAVTRACK_LEARNER_GRAD_VARIANTS(GRAD_KERNEL_ROW)};
 #undef GRAD_KERNEL_ROW
 
 }  // namespace
@@ -944,11 +922,10 @@ hipError_t learner_prepare_kernels(const LearnerLayout &L)
 {
     // every instantiation of the gradient body needs the attribute of its own: up to about 131 KB at H = 256
     const int R = learner_rows_per_tile(L.H);
-    for (int i = 0; i < kLearnerGradVariantCount + kLearnerStoredVariantCount; ++i) {
-        const bool stored = i >= kLearnerGradVariantCount;
-        const void *kernel = stored ? kStoredKernels[i - kLearnerGradVariantCount].kernel : kGradKernels[i].kernel;
-        const size_t lds = learner_lds_bytes(L, R, !stored && kLearnerGradVariants[i].clipped_lds, stored);
-        const hipError_t e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    for (int i = 0; i < kLearnerGradVariantCount; ++i) {
+        const size_t lds = learner_lds_bytes(L, R, kLearnerGradVariants[i].lds_extra);
+        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kGradKernels[i]),
+                                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (e != hipSuccess) return e;
     }
     return hipSuccess;
@@ -965,7 +942,7 @@ hipError_t launch_grad(const LearnerDevice &d, const LearnerLaunch &q, float *td
     if (e != hipSuccess) return e;
 
     const bool batch = d.adv_mode == kAdvantageBatch, stored = q.advantages != nullptr;
-    GradStoredArgs a;
+    GradArgs a;
     a.params = d.params; a.states = q.states; a.rewards = q.rewards; a.next_states = q.next_states;
     a.actions = q.actions; a.idx = q.idx; a.weights = q.weights; a.n = q.n; a.capacity = q.capacity;
     a.partials = d.partials; a.td_delta = td; a.status = status;
@@ -975,11 +952,10 @@ hipError_t launch_grad(const LearnerDevice &d, const LearnerLaunch &q, float *td
     a.log_mu = q.log_mu; a.clip_lo = q.clip_lo; a.clip_hi = q.clip_hi; a.ratio = q.ratio;
     a.stats = batch ? d.stats() : d.adv_given;
     a.advantages = q.advantages;
-    // a batch that brings advantages consults the stored table first; raw is then the constant pair {0, 1}
+    // a stored advantage passes through the normalised advantage's line in every mode: raw is the constant pair {0, 1}
     if (stored && d.adv_mode == kAdvantageRaw) a.stats = d.adv_unit;
-    const int variant = stored ? learner_stored_variant(a.target != nullptr, q.log_mu != nullptr)
-                               : learner_grad_variant(d.entropy_coef != 0.0f || d.entropy, a.target != nullptr,
-                                                      q.log_mu != nullptr, d.adv_mode != kAdvantageRaw);
+    const int variant = learner_grad_variant(d.entropy_coef != 0.0f || d.entropy, a.target != nullptr, q.log_mu != nullptr,
+                                             d.adv_mode != kAdvantageRaw, stored);
     if (batch) {
         // the normalised advantage in batch mode: the TD pass (stored advantages: their gather) and the statistics
         // first, the seal behind
@@ -1004,8 +980,8 @@ hipError_t launch_grad(const LearnerDevice &d, const LearnerLaunch &q, float *td
         if ((e = hipGetLastError()) != hipSuccess) return e;
     }
     const dim3 grid(learner_groups(L, q.n));
-    if (stored) kStoredKernels[variant].launch(grid, learner_lds_bytes(L, R, false, true), st, a);
-    else kGradKernels[variant].launch(grid, learner_lds_bytes(L, R, kLearnerGradVariants[variant].clipped_lds), st, a);
+    hipLaunchKernelGGL(kGradKernels[variant], grid, dim3(kLW), learner_lds_bytes(L, R, kLearnerGradVariants[variant].lds_extra),
+                       st, a);
     if ((e = hipGetLastError()) != hipSuccess || !batch) return e;
     hipLaunchKernelGGL(learner_adv_seal_kernel, dim3(1), dim3(64), 0, st, status, d.stats());
     return hipGetLastError();

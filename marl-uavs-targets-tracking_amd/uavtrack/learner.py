@@ -519,8 +519,7 @@ class DeviceActorCritic(Handle):
         d = _lib.tensor_arg(discounts, torch.float32, capacity, self.device,
                             f"discounts must be a contiguous float32 tensor of {capacity} elements (one per slot of the "
                             f"store) on {self.device}")
-        suffix, extra = ("_discounted", (_ptr(w), _ptr(d))) if d is not None else \
-            ("", ()) if w is None else ("_weighted", (_ptr(w),))
+        clip = (None, 0.0, None)                                      # what _stored takes where there is no clip_eps
         if clip_eps is not None:
             _lib.tensor_arg(log_mu, torch.float32, capacity, self.device,
                             f"log_mu must be a contiguous float32 tensor of {capacity} elements (one per slot of the "
@@ -528,7 +527,7 @@ class DeviceActorCritic(Handle):
             _lib.tensor_arg(ratio_out, torch.float32, n, self.device,
                             f"ratio_out must be a contiguous float32 tensor of {n} elements (one per batch row) on "
                             f"{self.device}")
-            suffix, extra = "_clipped", (_ptr(w), _ptr(d), _ptr(log_mu), self._clip_eps_arg(clip_eps), _ptr(ratio_out))
+            clip = (_ptr(log_mu), self._clip_eps_arg(clip_eps), _ptr(ratio_out))
         if advantages is not None:
             if self.loss != "per_sample":
                 raise ValueError('advantages on a loss="reference" learner: that form scales the actor\'s gradient sums once '
@@ -536,8 +535,10 @@ class DeviceActorCritic(Handle):
             _lib.tensor_arg(advantages, torch.float32, capacity, self.device,
                             f"advantages must be a contiguous float32 tensor of {capacity} elements (one per slot of the "
                             f"store) on {self.device}")
-            clip = extra[2:] if clip_eps is not None else (None, 0.0, None)
-            suffix, extra = "_stored", (_ptr(w), _ptr(d), _ptr(advantages), *clip)
+        suffix, extra = ("_stored", (_ptr(w), _ptr(d), _ptr(advantages), *clip)) if advantages is not None else \
+            ("_clipped", (_ptr(w), _ptr(d), *clip)) if clip_eps is not None else \
+            ("_discounted", (_ptr(w), _ptr(d))) if d is not None else \
+            ("_weighted", (_ptr(w),)) if w is not None else ("", ())
         name = f"uavtrack_learner_{kind}{suffix}"
         _lib.check(getattr(self._lib, name)(self._h, n, *self._batch_args(store, capacity, idx), *extra,
                                             *map(_ptr, outputs), self._stream()), name)

@@ -73,6 +73,17 @@ from ._handle import Handle, current_device
 from ._lib import ptr as _ptr
 from .replay import KEYS, DrawSpec
 
+# The per-slot side stores a ring may own: (the ring's attribute, which is also its key in a transitions dict, what add
+# fills in where the dict lacks the key; None: float32(the ring's gamma)).
+SIDE_STORES = (("discounts", None), ("log_mu", float("nan")), ("advantages", float("nan")))
+
+
+def _unit_range(name: str, value) -> float:
+    value = float(value)
+    if not 0.0 <= value <= 1.0:
+        raise ValueError(f"{name} must be in [0, 1], got {value}")
+    return value
+
 
 class ReplayRing(Handle):
     """ReplayBuffer(capacity) (train.py:41-70) as a device ring with HIP add and sampling: uniform draws without
@@ -126,11 +137,8 @@ class ReplayRing(Handle):
             if n_step != 1:
                 raise ValueError(f"n_step = {n_step} needs gamma (the discount the n-step return is folded with)")
             return self
-        gamma = float(gamma)
-        if not 0.0 <= gamma <= 1.0:
-            raise ValueError(f"gamma must be in [0, 1], got {gamma}")
-        self.n_step, self.gamma = n_step, gamma
-        self.discounts = torch.full((self.capacity,), gamma, dtype=torch.float32, device=self.device)
+        self.n_step, self.gamma = n_step, _unit_range("gamma", gamma)
+        self.discounts = torch.full((self.capacity,), self.gamma, dtype=torch.float32, device=self.device)
         return self
 
     def with_lambda(self, lam: float, gamma: float) -> "ReplayRing":
@@ -138,11 +146,7 @@ class ReplayRing(Handle):
         ring then owns `discounts` [capacity] (every slot float32(gamma) to begin with, as with_nstep) and add_rollout
         stores lambda-returns as (reward, discount) pairs, from `values=` or a `critic=`.  n_step stays 1; a ring is an
         n-step ring (n_step > 1) or a lambda ring, not both."""
-        lam, gamma = float(lam), float(gamma)
-        if not 0.0 <= lam <= 1.0:
-            raise ValueError(f"lam must be in [0, 1], got {lam}")
-        if not 0.0 <= gamma <= 1.0:
-            raise ValueError(f"gamma must be in [0, 1], got {gamma}")
+        lam, gamma = _unit_range("lam", lam), _unit_range("gamma", gamma)
         if self.gae:
             raise ValueError("with_lambda on a GAE ring: a ring stores n-step returns, lambda-returns or GAE advantages, "
                              "one of the three")
@@ -161,11 +165,7 @@ class ReplayRing(Handle):
         G_t - V(s_t) as the advantage, from `critic=` or from add_rollout_gae's `values=, values_in=, values_start=`.  A ring is an n-step
         ring (n_step > 1), a lambda ring or a GAE ring: with_gae raises after either, and they raise after it.
         Composes with with_behaviour in either order."""
-        lam, gamma = float(lam), float(gamma)
-        if not 0.0 <= lam <= 1.0:
-            raise ValueError(f"lam must be in [0, 1], got {lam}")
-        if not 0.0 <= gamma <= 1.0:
-            raise ValueError(f"gamma must be in [0, 1], got {gamma}")
+        lam, gamma = _unit_range("lam", lam), _unit_range("gamma", gamma)
         if self.n_step > 1:
             raise ValueError(f"with_gae on a ring with n_step = {self.n_step}: a ring stores n-step returns, lambda-returns "
                              f"or GAE advantages, one of the three")
@@ -268,21 +268,12 @@ class ReplayRing(Handle):
         ring = self._ring()
         _lib.check(self._lib.uavtrack_replay_add(self._h, C.byref(ring), n, _ptr(s), _ptr(a), _ptr(r), _ptr(s2),
                                                  self._stream()), "uavtrack_replay_add")
-        if self.discounts is not None:
-            d = transition_dict.get("discounts")
-            d = torch.full((n,), self.gamma, dtype=torch.float32, device=dev) if d is None \
-                else d.to(dev, torch.float32).reshape(n)
-            self._copy_last(self.discounts, d, n)
-        if self.log_mu is not None:
-            m = transition_dict.get("log_mu")
-            m = torch.full((n,), float("nan"), dtype=torch.float32, device=dev) if m is None \
-                else m.to(dev, torch.float32).reshape(n)
-            self._copy_last(self.log_mu, m, n)
-        x = transition_dict.get("advantages")
-        if self.advantages is not None:
-            x = torch.full((n,), float("nan"), dtype=torch.float32, device=dev) if x is None \
-                else x.to(dev, torch.float32).reshape(n)
-            self._copy_last(self.advantages, x, n)
+        for name, fill in SIDE_STORES:
+            held, v = getattr(self, name), transition_dict.get(name)
+            if held is not None:
+                v = torch.full((n,), self.gamma if fill is None else fill, dtype=torch.float32, device=dev) if v is None \
+                    else v.to(dev, torch.float32).reshape(n)
+                self._copy_last(held, v, n)
         self._advance(n)
 
     def add_rollout(self, obs_in: torch.Tensor, out: Dict[str, torch.Tensor], *, critic=None,
@@ -466,12 +457,7 @@ class ReplayRing(Handle):
         """The transitions dict at idx: KEYS, "discounts" on a ring that has them, "log_mu" on a behaviour ring and
         "advantages" on a GAE ring."""
         out = {key: self.store[key][idx] for key in KEYS}
-        if self.discounts is not None:
-            out["discounts"] = self.discounts[idx]
-        if self.log_mu is not None:
-            out["log_mu"] = self.log_mu[idx]
-        if self.advantages is not None:
-            out["advantages"] = self.advantages[idx]
+        out.update({name: getattr(self, name)[idx] for name, _ in SIDE_STORES if getattr(self, name) is not None})
         return out
 
 
@@ -651,10 +637,7 @@ class RingSweep:
     store = property(lambda self: self.ring.store)
     capacity = property(lambda self: self.ring.capacity)
     priorities = property(lambda self: self.ring.priorities)
-    discounts = property(lambda self: self.ring.discounts)
-    gamma = property(lambda self: self.ring.gamma)
-    log_mu = property(lambda self: self.ring.log_mu)
-    advantages = property(lambda self: self.ring.advantages)
+    gamma = property(lambda self: self.ring.gamma)      # (discounts, log_mu and advantages: behind the class)
 
     def _ratio_out(self, k: int) -> torch.Tensor:
         return self.ring._ratio_out(k)
@@ -669,3 +652,7 @@ class RingSweep:
             raise ValueError(f"batch_size = {k}: this sweep was made for minibatches of {self.batch_size}")
         self._draw_into(self._idx)
         return self._idx, None
+
+
+for _name, _ in SIDE_STORES:                            # a sweep presents its ring's side stores under their names
+    setattr(RingSweep, _name, property(lambda self, _name=_name: getattr(self.ring, _name)))

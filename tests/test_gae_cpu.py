@@ -1,14 +1,12 @@
 """Fixed GAE advantages without a GPU: the numpy mirror of the GAE add (tests/replay_gae_mirror.py) against an independent
-float64 GAE, the stored kernels' variant table (csrc/learner_variants.h), the host-side refusals of the ring and the
-learner, the bindings, and the library calls a learner enqueues with and without a GAE ring (the recorder of
-tests/learner_call_trace.py)."""
+float64 GAE, the host-side refusals of the ring and the learner, the bindings, and the library calls a learner enqueues
+with and without a GAE ring (the recorder of tests/learner_call_trace.py).  The stored kernels' rows of the variant table
+are pinned with the others, in tests/test_learner_variants_cpu.py."""
 import ctypes as C
 import inspect
 import json
 import os
 import re
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
@@ -21,7 +19,6 @@ import uavtrack
 from conftest import ROOT
 from uavtrack import _lib
 
-CSRC = os.path.join(ROOT, "marl-uavs-targets-tracking_amd", "csrc")
 U = 2.0 ** -24                                                          # the unit roundoff of float32
 
 
@@ -85,70 +82,6 @@ def test_the_mirrors_stores_are_the_lambda_mirrors_with_the_pair_folded_once_mor
     Vs = gm.state_values(val, vin, vso, done)
     assert np.array_equal(Vs[0], vin) and np.array_equal(Vs[1, 0], vso[0, 0]) and np.array_equal(Vs[1, 1], val[0, 1])
     assert np.array_equal(Vs[4, 1], vso[3, 1]) and np.array_equal(Vs[5, 1], vso[4, 1]) and np.array_equal(Vs[6, 1], val[5, 1])
-
-
-# ---- the stored kernels' table ---------------------------------------------------------------------------------------------
-
-# (target, log_mu) -> kernel, and kernel -> (kReg, kTgt, kClip, kAdv) of its instantiation (kStored throughout)
-EXPECTED = {
-    (0, 0): "learner_grad_stored_kernel",
-    (1, 0): "learner_grad_stored_target_kernel",
-    (0, 1): "learner_grad_stored_clip_kernel",
-    (1, 1): "learner_grad_stored_clip_target_kernel",
-}
-INSTANTIATIONS = {
-    "learner_grad_stored_kernel": (1, 0, 0, 1),
-    "learner_grad_stored_target_kernel": (1, 1, 0, 1),
-    "learner_grad_stored_clip_kernel": (1, 0, 1, 1),
-    "learner_grad_stored_clip_target_kernel": (1, 1, 1, 1),
-}
-PROGRAM = r"""
-#include <cstdio>
-#include "learner_variants.h"
-using namespace uavtrack;
-int main()
-{
-    std::printf("plain %d\n", kLearnerGradVariantCount);
-    for (int i = 0; i < kLearnerStoredVariantCount; ++i) {
-        const LearnerGradVariant &v = kLearnerStoredVariants[i];
-        std::printf("row %s %d %d %d %d %d\n", v.kernel, v.reg, v.target, v.clip, v.adv, v.clipped_lds);
-    }
-    for (int f = 0; f < 4; ++f) {
-        const int i = learner_stored_variant(f & 1, f & 2);
-        std::printf("pick %d %d %s\n", f & 1, (f >> 1) & 1, i < 0 ? "none" : kLearnerStoredVariants[i].kernel);
-    }
-    return 0;
-}
-"""
-
-
-@pytest.fixture(scope="module")
-def printed(tmp_path_factory):
-    cxx = os.environ.get("CXX") or shutil.which("c++") or shutil.which("g++") or shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    if not (shutil.which(cxx) or os.path.exists(cxx)):
-        pytest.skip("no C++ compiler on this machine")
-    d = tmp_path_factory.mktemp("stored_variants")
-    src, exe = str(d / "variants.cpp"), str(d / "variants")
-    with open(src, "w") as f:
-        f.write(PROGRAM)
-    r = subprocess.run([cxx, "-std=c++17", "-x", "c++", "-I" + CSRC, src, "-o", exe], stdout=subprocess.PIPE,
-                       stderr=subprocess.STDOUT, text=True)
-    assert r.returncode == 0, r.stdout
-    return [ln.split() for ln in subprocess.run([exe], stdout=subprocess.PIPE, text=True, check=True).stdout.splitlines()]
-
-
-def test_the_stored_table_is_four_instantiations_of_its_own_and_every_pair_takes_its_kernel(printed):
-    rows = {ln[1]: tuple(int(x) for x in ln[2:]) for ln in printed if ln[0] == "row"}
-    picks = {tuple(int(x) for x in ln[1:3]): ln[3] for ln in printed if ln[0] == "pick"}
-    assert [ln for ln in printed if ln[0] == "plain"] == [["plain", "10"]]      # the ten stay ten
-    assert len(rows) == sum(ln[0] == "row" for ln in printed) == 4
-    assert {k: v[:4] for k, v in rows.items()} == INSTANTIATIONS
-    assert all(v[4] == 1 for v in rows.values())                                # all ask for the stored LDS size
-    assert picks == EXPECTED and set(picks.values()) == set(rows)
-    text = open(os.path.join(CSRC, "learner_kernel.hip")).read()
-    for kernel, (reg, tgt, clip, adv) in INSTANTIATIONS.items():
-        flags = ", ".join("true" if x else "false" for x in (reg, tgt, clip, adv, 1))
-        assert re.search(rf"{kernel}\(GradStoredArgs a\) {{ learner_grad_body<{flags}>\(a\); }}", text), kernel
 
 
 # ---- the bindings ----------------------------------------------------------------------------------------------------------

@@ -1,13 +1,14 @@
-"""The contract the eight batch entry points of the learner share (uavtrack_learner_update, _update_weighted,
-_update_discounted, _update_clipped and the four _grad forms), called through ctypes: every host-side refusal returns
-non-zero with its whole message, in one order for all eight (of two faults the earlier one's message), and leaves the
+"""The contract the ten batch entry points of the learner share (uavtrack_learner_update, _update_weighted,
+_update_discounted, _update_clipped, _update_stored and the five _grad forms), called through ctypes: every host-side refusal
+returns non-zero with its whole message, in one order for all ten (of two faults the earlier one's message), and leaves the
 parameters, the Adam moments and step counts, theta-, the priorities and the caller's outputs byte for byte as they were,
 with nothing counted by uavtrack_learner_check; the good call lands; and the forms nest: null optional pointers give the
 bits of the shorter form.
 
 H = 8, A = 12, a store of 7 slots, n = 5 rows through indices with a repeated slot, learners reserved for 16 rows: one
-per_sample (target critic on) and one reference learner (which cannot arm a batch advantage and refuses the clipped
-forms, so those have no good call there)."""
+per_sample (target critic on) and one reference learner (which cannot arm a batch advantage and refuses the clipped and
+the stored forms, so those have no good call there).  The _stored pair runs twice, with log_mu and with log_mu null
+("_no_log_mu": clip_eps is then not read, so that call carries clip_eps = NaN throughout)."""
 import ctypes as C
 
 import numpy as np
@@ -23,12 +24,15 @@ H, A, CAP, N, MAX_BATCH = 8, 12, 7, 5, 16
 IDX = (3, 0, 6, 3, 5)                           # slot 3 twice: the later row's |delta| is its priority
 KINDS = ("update", "grad")
 SUFFIXES = ("", "_weighted", "_discounted", "_clipped")
-FORMS = tuple(k + s for k in KINDS for s in SUFFIXES)
+FORMS = tuple(k + s for k in KINDS for s in SUFFIXES) + \
+    tuple(k + s for k in KINDS for s in ("_stored", "_stored_no_log_mu"))
 SENTINEL = 7.5
 
 STORES_NULL = "states, actions, rewards and next_states must not be null"
 REFERENCE = ("the clipped surrogate on a UAVTRACK_LOSS_REFERENCE learner: that form scales the actor's gradient sums once "
              "by -mean(delta) / N, a factor a per-row gate cannot share; use UAVTRACK_LOSS_PER_SAMPLE")
+STORED_REFERENCE = ("stored advantages on a UAVTRACK_LOSS_REFERENCE learner: that form scales the actor's gradient sums "
+                    "once by -mean(delta) / N, a factor a per-row advantage cannot share; use UAVTRACK_LOSS_PER_SAMPLE")
 ADVANTAGE = ("n = 1 row under UAVTRACK_ADVANTAGE_BATCH: the standard deviation of a batch needs n >= 2 "
              "(uavtrack_learner_set_advantage)")
 ENTROPY = "n = 5 rows, the installed entropy buffer holds 4 (uavtrack_learner_set_diagnostics)"
@@ -45,7 +49,8 @@ def world():
          "indices": lh.dev(np.array(IDX, np.int64)),
          "weights": lh.dev(rng.uniform(0.25, 1.0, size=N).astype(np.float32)),
          "discounts": lh.dev(rng.uniform(0.5, 0.95, size=CAP).astype(np.float32)),
-         "log_mu": lh.dev(rng.uniform(-3.0, -1.0, size=CAP).astype(np.float32))}
+         "log_mu": lh.dev(rng.uniform(-3.0, -1.0, size=CAP).astype(np.float32)),
+         "advantages": lh.dev(rng.uniform(-1.0, 1.0, size=CAP).astype(np.float32))}
     torch.cuda.synchronize()
     return w
 
@@ -69,7 +74,7 @@ def _outputs(L):
 def _base(world, out):
     """The good call's arguments by name: addresses, sizes, scalars."""
     a = {k: v.data_ptr() for k, v in world["store"].items()}
-    a.update({k: world[k].data_ptr() for k in ("indices", "weights", "discounts", "log_mu")})
+    a.update({k: world[k].data_ptr() for k in ("indices", "weights", "discounts", "log_mu", "advantages")})
     a.update({k: v.data_ptr() for k, v in out.items()})
     a.update(n=N, capacity=CAP, clip_eps=0.2)
     return a
@@ -77,13 +82,16 @@ def _base(world, out):
 
 def _call(L, form, handle, a):
     """One direct library call; returns (rc, message)."""
+    form = form.replace("_no_log_mu", "")
     kind, suffix = form.split("_")[0], form[form.index("_"):] if "_" in form else ""
     args = [a["n"], a["states"], a["actions"], a["rewards"], a["next_states"], a["capacity"], a["indices"]]
     if suffix:
         args.append(a["weights"])
-    if suffix in ("_discounted", "_clipped"):
+    if suffix in ("_discounted", "_clipped", "_stored"):
         args.append(a["discounts"])
-    if suffix == "_clipped":
+    if suffix == "_stored":
+        args.append(a["advantages"])
+    if suffix in ("_clipped", "_stored"):
         args += [a["log_mu"], a["clip_eps"], a["ratio_out"]]
     args += [a["actor_loss"], a["critic_loss"], a["td_delta"], a["priorities"]] if kind == "update" else [a["td_delta"], a["row"]]
     rc = getattr(L._lib, "uavtrack_learner_" + form)(handle, *args, L._stream())
@@ -108,6 +116,7 @@ def _faults(form, loss):
     library tests them; then the pairs of two faults at once, whose message is the earlier one's.  Every text is the
     library's, written out."""
     update, clipped, per_sample = form.startswith("update"), form.endswith("_clipped"), loss == "per_sample"
+    stored, log_mu = "_stored" in form, form.endswith(("_clipped", "_stored"))
     out = [(f"{k} null", {k: None}, None, STORES_NULL) for k in lh.STORES]
     outs, outs_null = (("actor_loss", "critic_loss"), "actor_loss and critic_loss must not be null") if update else \
         (("td_delta", "row"), "td_delta and row must not be null")
@@ -120,12 +129,17 @@ def _faults(form, loss):
             ("entropy buffer of 4", {}, "entropy", ENTROPY)]
     if per_sample:
         out.append(("n = 1, batch advantage", {"n": 1}, "advantage", ADVANTAGE))
-    if clipped:
-        out += [("log_mu null", {"log_mu": None}, None, "log_mu must not be null"),
-                ("clip_eps = -1", {"clip_eps": -1.0}, None, "clip_eps = -1 must be >= 0 (+inf: never clips)"),
-                ("clip_eps = nan", {"clip_eps": float("nan")}, None, "clip_eps = nan must be >= 0 (+inf: never clips)")]
+    if stored:
+        out.append(("advantages null", {"advantages": None}, None, "advantages must not be null"))
         if not per_sample:
-            out.append(("reference learner", {}, None, REFERENCE))
+            out.append(("reference learner", {}, None, STORED_REFERENCE))
+    if clipped:
+        out.append(("log_mu null", {"log_mu": None}, None, "log_mu must not be null"))
+    if log_mu and (per_sample or clipped):                                  # (_stored on a reference learner never gets here)
+        out += [("clip_eps = -1", {"clip_eps": -1.0}, None, "clip_eps = -1 must be >= 0 (+inf: never clips)"),
+                ("clip_eps = nan", {"clip_eps": float("nan")}, None, "clip_eps = nan must be >= 0 (+inf: never clips)")]
+    if clipped and not per_sample:
+        out.append(("reference learner", {}, None, REFERENCE))
     # two at once, adjacent in the order wherever one call can hold both (the null handle's pair is the caller's)
     pairs = [("stores + outputs", {"rewards": None, outs[0]: None}, None, STORES_NULL),
              ("outputs + n = 0", {outs[1]: None, "n": 0}, None, outs_null),
@@ -142,6 +156,16 @@ def _faults(form, loss):
         else:
             pairs.append(("clip_eps = -1 + reference learner", {"clip_eps": -1.0}, None,
                           "clip_eps = -1 must be >= 0 (+inf: never clips)"))
+    if stored:
+        pairs.append(("entropy buffer + advantages null", {"advantages": None}, "entropy", ENTROPY))
+        if per_sample:
+            pairs.append(("batch advantage + advantages null", {"n": 1, "advantages": None}, "advantage", ADVANTAGE))
+        else:
+            pairs += [("advantages null + reference learner", {"advantages": None}, None, "advantages must not be null"),
+                      ("reference learner + clip_eps = -1", {"clip_eps": -1.0}, None, STORED_REFERENCE)]
+        if log_mu:
+            pairs.append(("advantages null + clip_eps = -1", {"advantages": None, "clip_eps": -1.0}, None,
+                          "advantages must not be null"))
     return out + pairs
 
 
@@ -156,9 +180,11 @@ def _arm(L, setting, on):
 @pytest.mark.parametrize("form", FORMS)
 def test_refusals_in_order_change_nothing_and_the_good_call_lands(form, loss, world):
     L = _learner(world, loss)
-    fn = "uavtrack_learner_" + form
+    fn = "uavtrack_learner_" + form.replace("_no_log_mu", "")
     out = _outputs(L)
     base = _base(world, out)
+    if form.endswith("_no_log_mu"):                                         # clip_eps is read with log_mu alone
+        base.update(log_mu=None, clip_eps=float("nan"))
     before = _image(L, out)
 
     def refused(label, handle, args, text):
@@ -175,7 +201,7 @@ def test_refusals_in_order_change_nothing_and_the_good_call_lands(form, loss, wo
         refused(label, L._h, dict(base, **over), text)
         _arm(L, setting, False)
 
-    if form.endswith("_clipped") and loss == "reference":
+    if ("_clipped" in form or "_stored" in form) and loss == "reference":
         L.close()
         return
     p0, (_, _, steps0) = L._get_params(), L._optim_state()
@@ -184,9 +210,11 @@ def test_refusals_in_order_change_nothing_and_the_good_call_lands(form, loss, wo
     assert _refused_count(L) == (0, 0)
     td = out["td_delta"].cpu().numpy()
     assert np.isfinite(td[:N]).all() and (td[N:] == SENTINEL).all()
-    if form.endswith("_clipped"):
-        ratio = out["ratio_out"].cpu().numpy()
+    ratio = out["ratio_out"].cpu().numpy()
+    if form.endswith(("_clipped", "_stored")):
         assert np.isfinite(ratio[:N]).all() and (ratio[N:] == SENTINEL).all()
+    else:
+        assert (ratio == SENTINEL).all()
     if form.startswith("update"):
         assert (L._optim_state()[2] == steps0 + 1).all() and not np.array_equal(L._get_params(), p0)
         assert np.isfinite(out["actor_loss"].item()) and np.isfinite(out["critic_loss"].item())

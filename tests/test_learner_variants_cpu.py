@@ -1,9 +1,11 @@
-"""Which of the ten gradient kernels a learner launch takes (csrc/learner_variants.h, learner_grad_variant): over all 16
-combinations of (entropy term or entropy buffer, target critic on, log_mu given, advantage mode not raw) the kernel the
-three nests of launch_grad chose before there was a table, written out below, and for every row of the table the larger
-LDS size exactly where the kernel keeps log_mu of its tile.  Host only: the header needs no HIP, a C++ compiler prints
-the table and the sixteen answers."""
+"""Which of the fourteen gradient kernels a learner launch takes (csrc/learner_variants.h, learner_grad_variant): over
+all 32 combinations of (entropy term or entropy buffer, target critic on, log_mu given, advantage mode not raw, stored
+advantages given) the kernel launch_grad chose before there was one table, written out below; for every row of the table
+the flags its kernel's one-line body instantiates learner_grad_body with (learner_kernel.hip) and the floats per tile row
+it asks for behind the common LDS block.  Host only: the header needs no HIP, a C++ compiler prints the table and the
+thirty-two answers."""
 import os
+import re
 import shutil
 import subprocess
 
@@ -13,9 +15,9 @@ from conftest import ROOT
 
 CSRC = os.path.join(ROOT, "marl-uavs-targets-tracking_amd", "csrc")
 
-# (reg, target, log_mu, adv) -> kernel.  The rule as launch_grad spelled it: a normalised advantage takes one of the four
-# adv kernels by (log_mu, target) whatever reg is; else log_mu takes one of the two clip kernels by target whatever reg
-# is; else one of the first four by (reg, target).
+# (reg, target, log_mu, adv) -> kernel without stored advantages.  The rule as launch_grad spelled it: a normalised
+# advantage takes one of the four adv kernels by (log_mu, target) whatever reg is; else log_mu takes one of the two clip
+# kernels by target whatever reg is; else one of the first four by (reg, target).
 EXPECTED = {
     (0, 0, 0, 0): "learner_grad_kernel",
     (1, 0, 0, 0): "learner_grad_reg_kernel",
@@ -34,7 +36,15 @@ EXPECTED = {
     (0, 1, 1, 1): "learner_grad_adv_clip_target_kernel",
     (1, 1, 1, 1): "learner_grad_adv_clip_target_kernel",
 }
-# kernel -> (kReg, kTgt, kClip, kAdv) of its instantiation of learner_grad_body (learner_kernel.hip)
+# (target, log_mu) -> kernel with stored advantages, whatever reg and adv are
+EXPECTED_STORED = {
+    (0, 0): "learner_grad_stored_kernel",
+    (1, 0): "learner_grad_stored_target_kernel",
+    (0, 1): "learner_grad_stored_clip_kernel",
+    (1, 1): "learner_grad_stored_clip_target_kernel",
+}
+# kernel -> (kReg, kTgt, kClip, kAdv) of its instantiation of learner_grad_body (learner_kernel.hip), in the table's order:
+# the ten without kStored, then the four with it
 INSTANTIATIONS = {
     "learner_grad_kernel": (0, 0, 0, 0),
     "learner_grad_reg_kernel": (1, 0, 0, 0),
@@ -47,6 +57,12 @@ INSTANTIATIONS = {
     "learner_grad_adv_clip_kernel": (1, 0, 1, 1),
     "learner_grad_adv_clip_target_kernel": (1, 1, 1, 1),
 }
+STORED_INSTANTIATIONS = {
+    "learner_grad_stored_kernel": (1, 0, 0, 1),
+    "learner_grad_stored_target_kernel": (1, 1, 0, 1),
+    "learner_grad_stored_clip_kernel": (1, 0, 1, 1),
+    "learner_grad_stored_clip_target_kernel": (1, 1, 1, 1),
+}
 
 PROGRAM = r"""
 #include <cstdio>
@@ -56,11 +72,11 @@ int main()
 {
     for (int i = 0; i < kLearnerGradVariantCount; ++i) {
         const LearnerGradVariant &v = kLearnerGradVariants[i];
-        std::printf("row %s %d %d %d %d %d\n", v.kernel, v.reg, v.target, v.clip, v.adv, v.clipped_lds);
+        std::printf("row %s %d %d %d %d %d %d\n", v.kernel, v.reg, v.target, v.clip, v.adv, v.stored, v.lds_extra);
     }
-    for (int f = 0; f < 16; ++f) {
-        const int i = learner_grad_variant(f & 1, f & 2, f & 4, f & 8);
-        std::printf("pick %d %d %d %d %s\n", f & 1, (f >> 1) & 1, (f >> 2) & 1, (f >> 3) & 1,
+    for (int f = 0; f < 32; ++f) {
+        const int i = learner_grad_variant(f & 1, f & 2, f & 4, f & 8, f & 16);
+        std::printf("pick %d %d %d %d %d %s\n", f & 1, (f >> 1) & 1, (f >> 2) & 1, (f >> 3) & 1, (f >> 4) & 1,
                     i < 0 ? "none" : kLearnerGradVariants[i].kernel);
     }
     return 0;
@@ -81,20 +97,36 @@ def printed(tmp_path_factory):
                        stderr=subprocess.STDOUT, text=True)
     assert r.returncode == 0, r.stdout
     lines = [ln.split() for ln in subprocess.run([exe], stdout=subprocess.PIPE, text=True, check=True).stdout.splitlines()]
-    rows = {ln[1]: tuple(int(x) for x in ln[2:]) for ln in lines if ln[0] == "row"}
-    picks = {tuple(int(x) for x in ln[1:5]): ln[5] for ln in lines if ln[0] == "pick"}
-    assert len(rows) == sum(ln[0] == "row" for ln in lines)                 # no kernel twice
+    rows = {ln[1]: tuple(int(x) for x in ln[2:]) for ln in lines if ln[0] == "row"}     # (insertion order: the table's)
+    picks = {tuple(int(x) for x in ln[1:6]): ln[6] for ln in lines if ln[0] == "pick"}
+    assert len(rows) == sum(ln[0] == "row" for ln in lines) == 14           # fourteen rows, no kernel twice
     return rows, picks
 
 
 def test_every_flag_combination_takes_the_kernel_the_nests_chose(printed):
     _, picks = printed
-    assert picks == EXPECTED
+    assert len(picks) == 32
+    assert {k[:4]: v for k, v in picks.items() if not k[4]} == EXPECTED
+    for (reg, target, log_mu, adv, stored), kernel in picks.items():
+        if stored:
+            assert kernel == EXPECTED_STORED[target, log_mu], (reg, target, log_mu, adv)
 
 
-def test_the_table_is_the_ten_instantiations_and_the_clip_kernels_alone_take_the_larger_lds(printed):
+def test_the_table_is_the_fourteen_instantiations_and_each_asks_for_the_lds_its_kernel_keeps(printed):
+    rows, picks = printed
+    assert list(rows)[:10] == list(INSTANTIATIONS)                          # the first ten rows are the ten, in this order
+    assert {k: v[:5] for k, v in rows.items()} == {**{k: (*v, 0) for k, v in INSTANTIATIONS.items()},
+                                                   **{k: (*v, 1) for k, v in STORED_INSTANTIATIONS.items()}}
+    for kernel, (reg, target, clip, adv, stored, lds_extra) in rows.items():
+        assert lds_extra == (2 if stored else clip), kernel                 # log_mu of the tile; log_mu and the advantage
+    assert set(picks.values()) == set(rows)                                 # every kernel is reachable
+
+
+def test_every_kernels_one_line_body_instantiates_the_gradient_body_with_its_rows_flags(printed):
     rows, _ = printed
-    assert {k: v[:4] for k, v in rows.items()} == INSTANTIATIONS
-    for kernel, (reg, target, clip, adv, clipped_lds) in rows.items():
-        assert clipped_lds == clip, kernel
-    assert set(EXPECTED.values()) == set(rows)                              # every kernel is reachable
+    text = open(os.path.join(CSRC, "learner_kernel.hip")).read()
+    for kernel, flags in rows.items():
+        args = ["true" if x else "false" for x in flags[:5]]
+        while len(args) > 1 and args[-1] == "false":                        # (trailing template defaults are left out)
+            args.pop()
+        assert re.search(rf"{kernel}\(GradArgs a\) {{ learner_grad_body<{', '.join(args)}>\(a\); }}", text), kernel
