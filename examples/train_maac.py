@@ -21,6 +21,7 @@ update is the same rule on a sampled batch, and the new actor weights are re-upl
     python examples/train_maac.py --replay prioritized --learner device --actor-loss per_sample --ppo-clip 0.2 --normalise-advantage   # ... on batch-standardised advantages
     python examples/train_maac.py --replay uniform-device --learner device --actor-loss per_sample --ppo-clip 0.2 --ppo-epochs 4 --minibatch 65536   # ... over 4 epochs of disjoint minibatches of the new rollout
     python examples/train_maac.py --replay prioritized --learner device --target-tau 0.005                # bootstrap from a Polyak-averaged target critic
+    python examples/train_maac.py --replay uniform-device --learner device --actor-loss per_sample --ppo-clip 0.2 --ppo-epochs 4 --minibatch 65536 --target-kl 0.01 --publish device --log-every 10   # ... stopped by a KL latch on the device
     python examples/train_maac.py --replay uniform-device --learner device --actor-loss per_sample --ppo-clip 0.2 --ppo-epochs 4 --minibatch 65536 --gae-lambda 0.95   # ... on fixed GAE advantages and value targets
     python examples/train_maac.py --replay prioritized --learner device --target-period 100 --td-lambda 0.9   # ... or a periodic copy; the lambda add folds with it too
     python examples/train_maac.py --method maac-r --pmi-trainer device --learner device --replay prioritized --publish device --log-every 10
@@ -67,7 +68,8 @@ class ValueNet(torch.nn.Module):
 
 
 def update(actor, critic, opt_a, opt_c, batch, gamma, weights=None, entropy_coef=0.0, max_grad_norm=None, diag=None,
-           rho_bar=None, rho_stats=None, target_critic=None, ppo_clip=None, normalise=False, adv_stats=None):
+           rho_bar=None, rho_stats=None, target_critic=None, ppo_clip=None, normalise=False, adv_stats=None, kl_limit=None,
+           kl_stats=None):
     """One ActorCritic.update step (actor_critic.py:150-178) on a batch of transitions.  weights (--importance): the
     draw's importance weights, one per row, multiplied into the per-sample losses before the mean.  entropy_coef and
     max_grad_norm: the two terms of DeviceActorCritic.set_regularisation, so that --learner torch and --learner device
@@ -85,7 +87,11 @@ def update(actor, critic, opt_a, opt_c, batch, gamma, weights=None, entropy_coef
     target_critic (--target-tau / --target-period): the copy of the critic that V(s') comes from; keeping it in step
     is the caller's (sync_target_critic).
     A batch from a GAE ring (--gae-lambda) carries "advantages", which take td_delta's place as A (normalise applies on
-    top), and a reward that is the fixed value target G_t with a discount of 0: the critic regresses on it as it stands."""
+    top), and a reward that is the fixed value target G_t with a discount of 0: the critic regresses on it as it stands.
+    kl_limit (--target-kl X: 1.5 X, with ppo_clip): the minibatch's own mean((r - 1) - log r), formed in float64 from the
+    float32 ratios before the step, goes to kl_stats["kl"]; where it exceeds kl_limit (compared in float32) nothing steps,
+    kl_stats["stopped"] is set and the losses returned are NaN -- the host's `break`, which
+    DeviceActorCritic.set_kl_stop latches on the device instead."""
     s, a, r, s2 = batch["states"], batch["actions"].long().unsqueeze(1), batch["rewards"], batch["next_states"]
     if target_critic is None:
         v_next = critic(s2)
@@ -107,6 +113,12 @@ def update(actor, critic, opt_a, opt_c, batch, gamma, weights=None, entropy_coef
         per_row = -torch.min(r * adv, r.clamp(1 - ppo_clip, 1 + ppo_clip) * adv)
         if rho_stats is not None:
             rho_stats["rho"] = r.detach()
+        if kl_limit is not None:
+            r64 = r.detach().double()
+            kl_stats["kl"] = ((r64 - 1.0) - torch.log(r64)).mean().float()
+            if bool(kl_stats["kl"] > torch.tensor(kl_limit, dtype=torch.float32)):      # the host's synchronisation
+                kl_stats["stopped"] = True
+                return float("nan"), float("nan")
     if rho_bar is not None:
         rho = torch.exp(log_probs.detach() - batch["log_mu"]).clamp(max=rho_bar)
         weights = rho if weights is None else weights * rho
@@ -176,7 +188,15 @@ def device_learner(args, uavtrack, na_total, dev, max_batch):
         learner.set_target(tau=args.target_tau, period=args.target_period)
     if args.normalise_advantage:
         learner.set_advantage("batch")                                # each draw standardised by its own statistics
+    if args.target_kl is not None:
+        learner.set_kl_stop(1.5 * args.target_kl)                     # the latch is cleared beside each sweep.rebind()
     return learner
+
+
+def kl_field(kl, skipped):
+    """The printed lines' extra field under --target-kl: the last evaluated minibatch's KL estimate and the updates that
+    were stopped since the previous line."""
+    return f"kl {float(kl):.5f} skipped {int(skipped)}  "
 
 
 def advantage_field(mean, std):
@@ -552,6 +572,14 @@ def main(argv=None, timings=None):
                          "--ppo-clip, --rho-bar, --normalise-advantage, --entropy-coef, --n-step, --td-lambda and --shards "
                          "apply as before, and the printed ratio statistics become means over the iteration's minibatches.  "
                          "Needs --replay prioritized or uniform-device; not with --importance (a sweep is uniform)")
+    ap.add_argument("--target-kl", type=float, default=None, metavar="X",
+                    help="X >= 0, with --ppo-clip and --ppo-epochs: KL early stopping.  Every minibatch's own estimate "
+                         "mean((r - 1) - log r) is formed before its step, and once one exceeds 1.5 X the rest of the "
+                         "iteration's updates are skipped.  --learner device: DeviceActorCritic.set_kl_stop(1.5 X), a latch on "
+                         "the device cleared beside each iteration's sweep.rebind() (kl_reset), so --log-every N still "
+                         "means no host synchronisation; --learner torch: the same estimator on the same rows and a host "
+                         "break.  Printed lines show the last KL and the updates skipped since the previous line (the "
+                         "losses of a line whose last update was stopped are NaN).  Not with --shards K > 1")
     ap.add_argument("--minibatch", type=int, default=None, metavar="K",
                     help="--ppo-epochs only: rows per minibatch (default: --batch; with --shards, split over the rings as "
                          "--batch is); at most what one iteration adds")
@@ -674,6 +702,15 @@ def main(argv=None, timings=None):
         if args.learner == "device" and args.actor_loss != "per_sample":
             ap.error("--ppo-clip with --learner device needs --actor-loss per_sample: the reference form scales the actor's "
                      "gradient sums once by -mean(delta) / N, a factor a per-row gate cannot share")
+    if args.target_kl is not None:
+        if not args.target_kl >= 0:
+            ap.error("--target-kl must be >= 0")
+        if args.ppo_clip is None or args.ppo_epochs is None:
+            ap.error("--target-kl needs --ppo-clip and --ppo-epochs: the estimate is formed from the clipped surrogate's "
+                     "ratios, and what it stops is the rest of an iteration's epochs")
+        if args.shards > 1:
+            ap.error("--target-kl is not for --shards K > 1: the shards' one update is a split update, and a gradient row "
+                     "has nowhere to carry a KL sum")
     if args.minibatch is not None and args.ppo_epochs is None:
         ap.error("--minibatch is the minibatch of --ppo-epochs")
     if args.ppo_epochs is not None:
@@ -766,6 +803,8 @@ def main(argv=None, timings=None):
     history = []
     out = None
     sweeps = None                                                     # --ppo-epochs: the ring's sweep, made at the first add
+    kl_stats = {}                                                     # --target-kl: the last evaluated KL ...
+    kl_skipped = torch.zeros((), dtype=torch.int64, device=dev)       # ... and the updates stopped since the last line
     t_log = time.perf_counter()
     stamps = []
     for it in range(args.iters):
@@ -793,17 +832,24 @@ def main(argv=None, timings=None):
         reg_kw = dict(entropy_coef=args.entropy_coef, max_grad_norm=args.max_grad_norm, diag=diag, rho_bar=args.rho_bar,
                       rho_stats=rho_stats, target_critic=target_critic, ppo_clip=args.ppo_clip,
                       normalise=args.normalise_advantage, adv_stats=adv_stats)
+        if args.target_kl is not None and learner is None:
+            reg_kw.update(kl_limit=1.5 * args.target_kl, kl_stats=kl_stats)
         boot = critic if target_critic is None else target_critic     # whose V(s') the torch learner bootstraps from
         source, n_updates = replay, args.updates
         if args.ppo_epochs:                                           # E epochs over what the add above wrote
             sweeps, n_updates = epoch_sweeps(args, [replay], args.batch, sweeps)
             source = sweeps[0]
         means = RatioMeans(args) if log and behavioural(args) and args.ppo_epochs else None
+        if args.target_kl is not None and learner is not None:
+            learner.kl_reset()                                        # beside the rebind: a new iteration, a clear latch
         if learner is None and args.ppo_epochs:                       # the torch learner on the sweep's minibatches
-            for _ in range(n_updates):
+            for q in range(n_updates):
                 la, lc = update(actor, critic, opt_a, opt_c, source.sample(), args.gamma, **reg_kw)
                 if means is not None:
                     means.add(rho_stats["rho"])
+                if kl_stats.pop("stopped", False):                    # --target-kl: the rest of the iteration is skipped
+                    kl_skipped += n_updates - q
+                    break
                 updates_done += 1
                 if target_critic is not None:
                     sync_target_critic(args, target_critic, critic, updates_done)
@@ -833,7 +879,10 @@ def main(argv=None, timings=None):
                 la_t, lc_t, td_t = learner.update_from(source, args.batch, **importance_kwargs(args), **rho_kw)
                 if means is not None:
                     means.add(views[0])
-            la, lc = (float(la_t), float(lc_t)) if log else (la_t, lc_t)
+            la, lc = (float(la_t), float(lc_t)) if log else (la_t, lc_t)   # (NaN where the last update was stopped)
+            if args.target_kl is not None:
+                kl_skipped += learner.kl_state[1]                     # device tensors: read on printed lines only
+                kl_stats["kl"] = learner.kl[0]
             if diag is not None:
                 diag.update(entropy=learner.entropy(td_t.numel()).mean(), norms=learner.grad_norm)
             if args.publish == "host":
@@ -882,6 +931,9 @@ def main(argv=None, timings=None):
             reg_field += rho_field(rho_stats["rho"], args.rho_bar)
         elif args.ppo_clip is not None:
             reg_field += ratio_field(rho_stats["rho"], args.ppo_clip)
+        if args.target_kl is not None:
+            reg_field += kl_field(kl_stats["kl"], kl_skipped)
+            kl_skipped.zero_()
         if args.normalise_advantage:
             reg_field += advantage_field(*((adv_stats["mean"], adv_stats["std"]) if learner is None else
                                            (learner.advantage_stats[0], learner.advantage_stats[2])))

@@ -934,6 +934,56 @@ int uavtrack_learner_grad_stored(uavtrack_learner *learner, int64_t n,
                                  const float *log_mu, double clip_eps, float *ratio_out,
                                  float *td_delta, float *row, void *stream);
 
+/* ---- KL early stopping for PPO epochs, latched on the device (UAVTRACK_LOSS_PER_SAMPLE only; off by default) ----
+ * PPO's usual safeguard, `if approx_kl > limit: break`, for a loop that issues no host synchronisation and for a captured
+ * graph that cannot break: a stop is a refusal that is not an error and that stays in force until it is reset.
+ * While the stop is on, every closed clipped update (uavtrack_learner_update_clipped, or _update_stored with a log_mu)
+ * evaluates the KL estimate of ITS OWN minibatch under the policy as it stands before that minibatch's step, and steps
+ * only where the estimate does not exceed the limit:
+ *   k_i = (r_i - 1) - log r_i    r_i the fp32 ratio the gradient kernel formed for batch row i (what ratio_out receives),
+ *                                widened to fp64; two fp64 subtractions and an fp64 log, as written.  k_i >= 0;
+ *                                r_i == 1.0f gives exactly 0; an underflowed r_i == 0 gives +inf, which stops.
+ *   kl  = (float)( S / n )       S = sum k_i in fp64 in the order of the advantage statistics above: rows in chunks of 256
+ *                                consecutive rows, the last padded with zeros; inside a chunk the halving tree
+ *                                x[k] += x[k + h], h = 128 .. 1; chunk sums added in ascending chunk order from 0.0.
+ * The statistic is unweighted: importance weights do not enter it.  kl_out[0] receives kl.  Where kl > (float)limit,
+ * compared in fp32, the latch state[0] is set and this update is STOPPED; while the latch is set every later update on
+ * this learner is stopped too, whatever its own KL would be, until uavtrack_learner_kl_reset.  limit = +inf observes and
+ * never stops.  state = {stopped (0 or 1), skipped}: skipped counts the stopped updates since the last reset, the one that
+ * tripped the latch included.
+ * A stopped update sets status bit 8 (value 256) in the status word and nothing else: both Adam steps and the step
+ * counters, the target critic's sync and the priority write are skipped as for a refused update, and its losses are NaN;
+ * but it is NOT a refusal, and uavtrack_learner_check does not count it.  The update that trips the latch has run its
+ * gradient kernel: td_delta, ratio_out and the entropy buffer hold its rows.  An update that meets the latch set returns
+ * from the gradient kernel before the first tile: it writes neither td_delta, ratio_out nor entropy, inspects no input
+ * (so it cannot be refused), and leaves kl_out at the last evaluated value.  After either, the advantage statistics of
+ * BATCH mode are NaN and grad_norm is NaN, as after a refused update: BATCH mode's statistics pass runs ahead of the
+ * gradient kernel as before (and still reads the rows), and while the stop is on its seal runs behind the KL pass's
+ * verdict.  An update refused on the device never sets the latch, and leaves kl_out NaN.
+ * A sweep's cursor and a ring's draw counter are advanced by the DRAW call, so they move under stopped updates too;
+ * rewind them as before (a new cursor value, uavtrack.RingSweep.rebind / seek).
+ * The KL pass is two small launches between the gradient kernel and the finalize kernel; the ratios come from ratio_out
+ * or, where the caller passes none, from [max_batch] floats of handle scratch.  That scratch is allocated when the stop is
+ * first turned on and grown by uavtrack_learner_reserve (neither for use inside a capture); no update allocates or
+ * synchronises.  While the stop is off every call enqueues exactly what it enqueued before.
+ * The setting is host-side and read when an update is ENQUEUED, so a captured graph keeps the one it was captured with;
+ * the latch is device state, so replays obey it.  Not part of checkpoints, and not carried by sharding's learner state.
+ * Refusals on the host, enqueuing nothing: (set) a limit that is NaN or negative, a null kl_out or state with on != 0, a
+ * UAVTRACK_LOSS_REFERENCE learner; (while on) an update that brings no log_mu (uavtrack_learner_update, _weighted,
+ * _discounted, _stored with log_mu == NULL), every uavtrack_learner_grad* entry point and uavtrack_learner_apply: a
+ * gradient row keeps its P + 8 words and has nowhere to carry a KL sum.
+ * Cost on one MI355X: DESIGN.md section 9. */
+
+/* on != 0: kl_out (DEVICE fp32 [1]) and state (DEVICE int32 [2]) are the caller's buffers, not copied and not owned, in
+ * the style of uavtrack_learner_set_diagnostics: they must outlive the updates enqueued while they are installed, and the
+ * caller zeroes state before the first update (or calls uavtrack_learner_kl_reset).  on == 0: off; the other arguments
+ * are not read.  A refused call changes nothing. */
+int uavtrack_learner_set_kl_stop(uavtrack_learner *learner, int32_t on, double limit, float *kl_out, int32_t *state);
+/* on, limit, kl_out and state as they were last set ({0, +inf, NULL, NULL} at create and while off). */
+int uavtrack_learner_get_kl_stop(uavtrack_learner *learner, int32_t *on, double *limit, float **kl_out, int32_t **state);
+/* state <- {0, 0}: a one-thread kernel on `stream`, stream-ordered and capturable.  An error while the stop is off. */
+int uavtrack_learner_kl_reset(uavtrack_learner *learner, void *stream);
+
 /* Synchronises `stream`; fails if any update or apply since the previous check was refused on the device (bad action,
  * index, importance weight, discount, behaviour log-probability or ratio, a bad given advantage pair, a stored advantage
  * that is not finite, or a row of another layout).  refused (nullable) receives their number; the count restarts at 0. */

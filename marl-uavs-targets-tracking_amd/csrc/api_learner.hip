@@ -16,6 +16,7 @@ struct uavtrack_learner {
     LearnerDevice d;
     double reg[3] = {0.0, INFINITY, INFINITY};   // uavtrack_learner_get_regularisation: the values as they were set
     double target_tau = 0.0;                     // uavtrack_learner_get_target: tau as it was set (0 unless Polyak)
+    double kl_limit = INFINITY;                  // uavtrack_learner_get_kl_stop: the limit as it was set
 };
 
 namespace uavtrack {
@@ -26,10 +27,17 @@ static Bufs advantage_bufs(LearnerDevice &d, int64_t max_n)
     return {buf(d.adv_td, max_n), buf(d.adv_part, 2 * (size_t)learner_adv_chunks(max_n))};
 }
 
+// the KL pass of the early stop: not part of a handle until the stop is first turned on
+static Bufs kl_bufs(LearnerDevice &d, int64_t max_n)
+{
+    return {buf(d.kl_ratio, max_n), buf(d.kl_part, (size_t)learner_adv_chunks(max_n))};
+}
+
 static Bufs scratch_bufs(LearnerDevice &d, int64_t max_n)
 {
     Bufs set = {buf(d.td, max_n), buf(d.last, max_n)};
-    return d.adv_td ? set + advantage_bufs(d, max_n) : set;
+    if (d.adv_td) set = set + advantage_bufs(d, max_n);
+    return d.kl_ratio ? set + kl_bufs(d, max_n) : set;
 }
 
 static Bufs device_bufs(LearnerDevice &d)
@@ -114,6 +122,13 @@ int accept_learner_batch(const char *fn, const uavtrack_learner *l, const Learne
         if (!q.advantages) return fail("%s: advantages must not be null", fn);
         if (!l->d.per_sample) return refuse_on_reference(fn, "stored advantages", "advantage");
     }
+    if (l->d.kl_on && kind == Batch::Grad)
+        return fail("%s: KL early stopping is on (uavtrack_learner_set_kl_stop): a gradient row has nowhere to carry a KL "
+                    "sum, so the split update is refused; use a closed clipped update, or turn the stop off", fn);
+    if (l->d.kl_on && !q.log_mu)
+        return fail("%s: KL early stopping is on (uavtrack_learner_set_kl_stop): the estimate is formed from the ratios "
+                    "against log_mu, and this form brings none; use uavtrack_learner_update_clipped, or _update_stored "
+                    "with a log_mu", fn);
     if (q.clipped || q.log_mu) {
         if (!q.log_mu) return fail("%s: log_mu must not be null", fn);
         if (!(q.clip_eps >= 0)) return fail("%s: clip_eps = %g must be >= 0 (+inf: never clips)", fn, q.clip_eps);
@@ -212,7 +227,7 @@ int uavtrack_learner_destroy(uavtrack_learner *learner)
         (void)hipDeviceSynchronize();
         release(target_bufs(learner->d));
     }
-    return destroy_handle(learner);                 // (the TD pass's scratch is in scratch_bufs() once it exists)
+    return destroy_handle(learner);                 // (the TD and KL passes' scratch is in scratch_bufs() once it exists)
 }
 
 int uavtrack_learner_num_params(uavtrack_learner *learner, int64_t *out)
@@ -434,6 +449,9 @@ int uavtrack_learner_apply(uavtrack_learner *learner, const float *rows, int64_t
     if (!actor_loss || !critic_loss) return fail("uavtrack_learner_apply: actor_loss and critic_loss must not be null");
     if (count < 1 || count > UAVTRACK_LEARNER_MAX_ROWS)
         return fail("uavtrack_learner_apply: count = %lld out of range [1, %d]", (long long)count, UAVTRACK_LEARNER_MAX_ROWS);
+    if (learner->d.kl_on)
+        return fail("uavtrack_learner_apply: KL early stopping is on (uavtrack_learner_set_kl_stop): gradient rows carry "
+                    "no KL sum, so the split update is refused; turn the stop off");
     ON_DEVICE(learner->cfg.device_id);
     HIP_TRY(launch_learner_apply(learner->d, rows, (int)count, actor_loss, critic_loss, static_cast<hipStream_t>(stream)));
     return 0;
@@ -495,6 +513,48 @@ int uavtrack_learner_set_advantage_stats(uavtrack_learner *learner, float *stats
 {
     if (!learner) return fail("%s: null handle", __func__);
     learner->d.adv_user = stats;
+    return 0;
+}
+
+// ---- KL early stopping
+
+int uavtrack_learner_set_kl_stop(uavtrack_learner *learner, int32_t on, double limit, float *kl_out, int32_t *state)
+{
+    if (!learner) return fail("%s: null handle", __func__);
+    LearnerDevice &d = learner->d;
+    if (!on) {
+        d.kl_on = 0; d.kl_limit = INFINITY; d.kl_out = nullptr; d.kl_state = nullptr;
+        learner->kl_limit = INFINITY;
+        return 0;
+    }
+    if (!(limit >= 0)) return fail("%s: limit = %g must be >= 0 (+inf: observe, never stop)", __func__, limit);
+    if (!kl_out || !state) return fail("%s: kl_out and state must not be null while on", __func__);
+    if (!d.per_sample)
+        return fail("%s: KL early stopping on a UAVTRACK_LOSS_REFERENCE learner: the estimate is formed from the clipped "
+                    "surrogate's ratios, which that form does not have; use UAVTRACK_LOSS_PER_SAMPLE", __func__);
+    if (!d.kl_ratio) {
+        // the KL pass's scratch, once per handle at the reserved size (uavtrack_learner_reserve grows it with the rest)
+        ON_DEVICE(learner->cfg.device_id);
+        HIP_TRY(replace(kl_bufs(d, d.max_n)));
+    }
+    d.kl_on = 1; d.kl_limit = (float)limit; d.kl_out = kl_out; d.kl_state = state;
+    learner->kl_limit = limit;
+    return 0;
+}
+
+int uavtrack_learner_get_kl_stop(uavtrack_learner *learner, int32_t *on, double *limit, float **kl_out, int32_t **state)
+{
+    if (!learner || !on || !limit || !kl_out || !state) return fail("%s: null argument", __func__);
+    *on = learner->d.kl_on; *limit = learner->kl_limit; *kl_out = learner->d.kl_out; *state = learner->d.kl_state;
+    return 0;
+}
+
+int uavtrack_learner_kl_reset(uavtrack_learner *learner, void *stream)
+{
+    if (!learner) return fail("%s: null handle", __func__);
+    if (!learner->d.kl_on) return fail("%s: KL early stopping is off (uavtrack_learner_set_kl_stop)", __func__);
+    ON_DEVICE(learner->cfg.device_id);
+    HIP_TRY(launch_learner_kl_reset(learner->d, static_cast<hipStream_t>(stream)));
     return 0;
 }
 

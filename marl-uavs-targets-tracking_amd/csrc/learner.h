@@ -79,7 +79,15 @@ struct LearnerDevice {
     float *adv_td;                  // [max_n] the TD pass's delta; null until a mode other than raw is first set
     double *adv_part;               // [2][learner_adv_chunks(max_n)] the chunks' sums of delta, then of squared deviations
     float *adv_unit;                // [2] {0.0f, 1.0f}: the pair a stored advantage in raw mode is "standardised" by
+    // KL early stopping (uavtrack_learner_set_kl_stop): host-side settings, read at enqueue; the latch is device state
+    int kl_on;
+    float kl_limit;                 // (float)limit: the update is stopped where kl > kl_limit in fp32 (+inf: never)
+    float *kl_out;                  // caller's [1] (not owned): the last evaluated batch's KL estimate
+    int32_t *kl_state;              // caller's [2] (not owned): {stopped (the latch), skipped}
+    float *kl_ratio;                // [max_n] the ratios when the caller passes no ratio_out; null until the stop is first on
+    double *kl_part;                // [learner_adv_chunks(max_n)] the chunks' sums of k_i
 };
+constexpr int kLearnerStopped = 256;   // status bit 8: the update was stopped by the KL latch (not an error)
 enum { kAdvantageRaw = 0, kAdvantageBatch = 1, kAdvantageGiven = 2 };
 // One batch of uavtrack_learner_update / _grad in any of their forms.  The ten entry points fill it as they were
 // called (the first nine fields in this order, by aggregate initialisation); what a form does not take stays zero.
@@ -113,6 +121,8 @@ hipError_t launch_learner_update(const LearnerDevice &d, const LearnerLaunch &q,
 hipError_t launch_learner_grad(const LearnerDevice &d, const LearnerLaunch &q, float *row, hipStream_t stream);
 hipError_t launch_learner_apply(const LearnerDevice &d, const float *rows, int count, float *actor_loss,
                                 float *critic_loss, hipStream_t stream);
+// uavtrack_learner_kl_reset: the latch and the skipped count back to 0, stream-ordered
+hipError_t launch_learner_kl_reset(const LearnerDevice &d, hipStream_t stream);
 hipError_t launch_learner_priorities(const LearnerDevice &d, const int64_t *idx, int64_t n, int64_t capacity,
                                      const float *td, float *prio, hipStream_t stream);
 // uavtrack_learner_values: values[i] = V(rows[i]) with the critic as it stands when the launch executes, the chain of

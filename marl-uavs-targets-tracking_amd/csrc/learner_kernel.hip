@@ -82,6 +82,14 @@
 // x_i into the TD scratch in learner_td_kernel's place and the statistics kernels run over it unchanged.  A drawn
 // advantage that is NaN or infinite sets status bit 7 (value 128) and the row is not used.
 //
+// KL early stopping (uavtrack_learner_set_kl_stop, closed clipped updates only, off by default): behind the gradient kernel
+// learner_kl_chunk_kernel sums k_i = (r_i - 1) - log r_i of the ratios in fp64 per 256-row chunk and learner_kl_kernel forms
+// kl = (float)(sum / n), and where kl > limit sets a latch in the caller's device memory and status bit 8 (value 256): the
+// update is stopped -- everything gated on the status word skips it, the finalize kernel counts no error -- and so is
+// every update behind it until the latch is reset: learner_begin_kl_kernel starts such an update's status word at 256, and
+// the kClip instantiations read the latch through GradArgs::latch and return before the first tile.  While off, the
+// launches and their arguments are the ones above (GradArgs::latch null).
+//
 // The critic alone (uavtrack_learner_values): learner_values_kernel, at the end of the kernels below, evaluates V(x) of
 // any number of rows by the chain of the layer-1 and layer-2 loops above, to the bit, and touches no learner state.
 
@@ -133,6 +141,8 @@ struct GradArgs {
     // read under kStored:
     const float *advantages;        // [capacity], slot order: the actor's advantage x_i of a row, in delta_i's place; status
                                     // bit 7 (value 128): a drawn slot whose advantage is NaN or infinite
+    // read under kClip, at the top of the body (KL early stopping):
+    const int32_t *latch;           // nullable [1]: the KL latch; non-zero when the launch executes: the launch does nothing
 };
 
 // kReg: the entropy term and the entropy[] store in the per-row block; everything else is one text.
@@ -146,6 +156,10 @@ __device__ __forceinline__ void learner_grad_body(const GradArgs &a)
 {
     static_assert(kReg || !kAdv, "the normalised advantage lives in the kReg block");
     static_assert(kAdv || !kStored, "a stored advantage passes through the normalised advantage's line");
+    // KL early stopping: a latched learner's update is thrown away, so it is not formed.  One word through a kernel
+    // argument: the same for every lane of every workgroup, ahead of the first barrier.
+    if constexpr (kClip)
+        if (a.latch && *a.latch) return;
     extern __shared__ float lds[];
     const LearnerLayout &L = a.L;
     const int H = L.H, A = L.A, R = a.rows, P = L.P;
@@ -460,6 +474,13 @@ __global__ void learner_begin_kernel(int *status)
     if (threadIdx.x == 0 && blockIdx.x == 0) *status = 0;
 }
 
+// In learner_begin_kernel's place while KL early stopping is on: a latched learner's update starts stopped, so every
+// kernel gated on the status word skips it.
+__global__ void learner_begin_kl_kernel(int *status, const int32_t *kl_state)
+{
+    if (threadIdx.x == 0 && blockIdx.x == 0) *status = kl_state[0] ? kLearnerStopped : 0;
+}
+
 // The ordered sum every reduction over partial rows or gradient rows uses: word p of `count` rows, rows ascending.
 __device__ __forceinline__ float ordered_sum(const float *src, int count, size_t stride, int p)
 {
@@ -469,7 +490,7 @@ __device__ __forceinline__ float ordered_sum(const float *src, int count, size_t
 }
 
 // One thread: the four loss sums added in row order, then losses, mean(delta) and the gradient scales from N, the call's
-// verdict into the sticky refusal count, the step counters.  The closed update (n_given >= 1) passes the workgroup
+// verdict into the sticky refusal count (a KL stop, bit 8 alone, is not a refusal and is not counted), the step counters.  The closed update (n_given >= 1) passes the workgroup
 // partials with N = n_given and reads the verdict the gradient kernel left in the status word; the apply (n_given == 0)
 // passes gradient rows, takes N and the verdict from their tails and writes the verdict to the status word.
 __global__ void learner_finalize_kernel(const float *src, int count, size_t stride, int P, int64_t n_given, int per_sample,
@@ -501,7 +522,8 @@ __global__ void learner_finalize_kernel(const float *src, int count, size_t stri
     // gradient scales of the Adam kernel: actor, critic
     scal[0] = per_sample ? -inv_n : -mean_delta * inv_n;
     scal[1] = 2.0f * inv_n;
-    if (bad) { *errors += 1; return; }
+    if (bad & ~kLearnerStopped) *errors += 1;                       // a stop alone is not a refusal
+    if (bad) return;
     for (int q = 0; q < kLearnerTensors; ++q) steps[q] += 1;
 }
 
@@ -873,6 +895,55 @@ __global__ void learner_adv_seal_kernel(const int *status, float *stats)
     stats[0] = NAN; stats[1] = NAN; stats[2] = NAN;
 }
 
+// ---- KL early stopping (uavtrack_learner_set_kl_stop): behind the gradient kernel of a closed clipped update, ahead of
+// the finalize kernel (batch mode's seal moves behind this pass, so a stopped update's statistics are NaN too).  k_i = (r_i - 1) - log r_i of the fp32 ratio the gradient kernel left for batch row
+// i, widened to fp64 (two subtractions and a log: r == 1 gives exactly 0, r == 0 gives +inf), summed in the order of the
+// advantage statistics: chunks of 256 rows, the halving tree, chunk sums ascending.  A refused update (its ratios hold
+// NaN) and a latched one (the gradient kernel wrote none) form no sum.
+
+__global__ void __launch_bounds__(kAdvChunk) learner_kl_chunk_kernel(const float *ratio, int64_t n, const int *status,
+                                                                     double *part)
+{
+    __shared__ double sh[kAdvChunk];
+    if (*status) return;                                            // uniform
+    const int tid = threadIdx.x;
+    const int64_t chunks = (n + kAdvChunk - 1) / kAdvChunk;
+    for (int64_t c = blockIdx.x; c < chunks; c += gridDim.x) {
+        const int64_t i = c * kAdvChunk + tid;
+        double k = 0.0;
+        if (i < n) {
+            const double r = (double)ratio[i];
+            k = __dsub_rn(__dsub_rn(r, 1.0), log(r));
+        }
+        const double s = chunk_tree(sh, tid, k);
+        if (tid == 0) part[c] = s;
+    }
+}
+
+// One thread: kl = (float)(sum / n); where kl > limit in fp32 the latch is set and the update stopped (status bit 8), so
+// everything behind this kernel that is gated on the status word skips it.  state = {stopped, skipped}: an update that
+// trips the latch or meets it set counts as skipped.  kl_out keeps the last evaluated batch's value under a latched
+// update and is NaN for a refused one, which never sets the latch.
+__global__ void learner_kl_kernel(const double *part, int64_t n, float limit, int *status, float *kl_out, int32_t *state)
+{
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    const int st = *status;
+    if (st & kLearnerStopped) { state[1] += 1; return; }
+    if (st) { *kl_out = NAN; return; }
+    const float kl = (float)__ddiv_rn(ordered_sum64(part, (n + kAdvChunk - 1) / kAdvChunk), (double)n);
+    *kl_out = kl;
+    if (kl > limit) {
+        state[0] = 1;
+        state[1] += 1;
+        *status = kLearnerStopped;
+    }
+}
+
+__global__ void learner_kl_reset_kernel(int32_t *state)
+{
+    if (threadIdx.x == 0 && blockIdx.x == 0) { state[0] = 0; state[1] = 0; }
+}
+
 }  // namespace
 
 int64_t learner_adv_chunks(int64_t n) { return (n + kAdvChunk - 1) / kAdvChunk; }
@@ -937,7 +1008,9 @@ hipError_t launch_grad(const LearnerDevice &d, const LearnerLaunch &q, float *td
 {
     const LearnerLayout &L = d.L;
     const int R = learner_rows_per_tile(L.H);
-    hipLaunchKernelGGL(learner_begin_kernel, dim3(1), dim3(64), 0, st, status);
+    // KL early stopping (closed clipped updates only; the host has refused every other form while it is on)
+    if (d.kl_on) hipLaunchKernelGGL(learner_begin_kl_kernel, dim3(1), dim3(64), 0, st, status, d.kl_state);
+    else hipLaunchKernelGGL(learner_begin_kernel, dim3(1), dim3(64), 0, st, status);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
 
@@ -952,6 +1025,8 @@ hipError_t launch_grad(const LearnerDevice &d, const LearnerLaunch &q, float *td
     a.log_mu = q.log_mu; a.clip_lo = q.clip_lo; a.clip_hi = q.clip_hi; a.ratio = q.ratio;
     a.stats = batch ? d.stats() : d.adv_given;
     a.advantages = q.advantages;
+    a.latch = d.kl_on ? d.kl_state : nullptr;
+    if (d.kl_on && !a.ratio) a.ratio = d.kl_ratio;                  // the KL pass reads the ratios: the handle's scratch
     // a stored advantage passes through the normalised advantage's line in every mode: raw is the constant pair {0, 1}
     if (stored && d.adv_mode == kAdvantageRaw) a.stats = d.adv_unit;
     const int variant = learner_grad_variant(d.entropy_coef != 0.0f || d.entropy, a.target != nullptr, q.log_mu != nullptr,
@@ -982,7 +1057,7 @@ hipError_t launch_grad(const LearnerDevice &d, const LearnerLaunch &q, float *td
     const dim3 grid(learner_groups(L, q.n));
     hipLaunchKernelGGL(kGradKernels[variant], grid, dim3(kLW), learner_lds_bytes(L, R, kLearnerGradVariants[variant].lds_extra),
                        st, a);
-    if ((e = hipGetLastError()) != hipSuccess || !batch) return e;
+    if ((e = hipGetLastError()) != hipSuccess || !batch || d.kl_on) return e;   // (the KL pass's verdict first: the seal follows it)
     hipLaunchKernelGGL(learner_adv_seal_kernel, dim3(1), dim3(64), 0, st, status, d.stats());
     return hipGetLastError();
 }
@@ -1038,11 +1113,32 @@ hipError_t launch_learner_priorities(const LearnerDevice &d, const int64_t *idx,
     return hipGetLastError();
 }
 
+hipError_t launch_learner_kl_reset(const LearnerDevice &d, hipStream_t st)
+{
+    hipLaunchKernelGGL(learner_kl_reset_kernel, dim3(1), dim3(64), 0, st, d.kl_state);
+    return hipGetLastError();
+}
+
 hipError_t launch_learner_update(const LearnerDevice &d, const LearnerLaunch &q, hipStream_t st)
 {
     float *td = q.td_delta ? q.td_delta : d.td;
     hipError_t e = launch_grad(d, q, td, d.opt.status, st);
     if (e != hipSuccess) return e;
+    if (d.kl_on) {
+        // the minibatch's own KL estimate from the ratios of the policy as it stands, and the verdict, ahead of the step
+        const int64_t chunks = learner_adv_chunks(q.n);
+        hipLaunchKernelGGL(learner_kl_chunk_kernel, dim3((unsigned)(chunks < 1024 ? chunks : 1024)), dim3(kAdvChunk), 0, st,
+                           q.ratio ? q.ratio : d.kl_ratio, q.n, d.opt.status, d.kl_part);
+        if ((e = hipGetLastError()) != hipSuccess) return e;
+        hipLaunchKernelGGL(learner_kl_kernel, dim3(1), dim3(64), 0, st, d.kl_part, q.n, d.kl_limit, d.opt.status, d.kl_out,
+                           d.kl_state);
+        if ((e = hipGetLastError()) != hipSuccess) return e;
+        if (d.adv_mode == kAdvantageBatch) {
+            // batch-mode statistics of a stopped update are NaN like a refused one's: the seal behind the verdict
+            hipLaunchKernelGGL(learner_adv_seal_kernel, dim3(1), dim3(64), 0, st, d.opt.status, d.stats());
+            if ((e = hipGetLastError()) != hipSuccess) return e;
+        }
+    }
     e = launch_scale_adam(d, d.partials, learner_groups(d.L, q.n), (size_t)d.L.P + 4, q.n, q.actor_loss, q.critic_loss, st);
     if (e != hipSuccess) return e;
     if (q.priorities) return launch_learner_priorities(d, q.idx, q.n, q.capacity, td, q.priorities, st);

@@ -211,6 +211,10 @@ SIGNATURES = {
     "uavtrack_learner_get_advantage": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_double),
                                                  C.POINTER(C.c_void_p)]),
     "uavtrack_learner_set_advantage_stats": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "uavtrack_learner_set_kl_stop": (C.c_int, [C.c_void_p, C.c_int32, C.c_double, C.c_void_p, C.c_void_p]),
+    "uavtrack_learner_get_kl_stop": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_double),
+                                               C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),
+    "uavtrack_learner_kl_reset": (C.c_int, [C.c_void_p, C.c_void_p]),
     "uavtrack_pmi_trainer_create": (C.c_int, [C.POINTER(PmiTrainerConfig), C.POINTER(C.c_void_p)]),
     "uavtrack_pmi_trainer_destroy": (C.c_int, [C.c_void_p]),
     "uavtrack_pmi_trainer_num_params": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),

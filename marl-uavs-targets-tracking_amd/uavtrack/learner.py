@@ -92,6 +92,13 @@ delta_i's place in the logit weight, the actor-loss term and the clip gate; set_
 standardises the gathered x_i).  The critic, td_delta and the priorities keep delta_i, and on a GAE ring (reward G_t,
 discount 0) delta_i = G_t - V_now(s_i): a fixed value target.  An advantage that is NaN (unknown) or infinite refuses the
 update on the device.  Without advantages every call enqueues exactly what it enqueued.
+
+KL early stopping (set_kl_stop(limit), uavtrack_learner_set_kl_stop; loss="per_sample" only; off by default, and then
+every call enqueues exactly what it enqueued): every clipped update forms kl = mean_i((r_i - 1) - log r_i) of its own
+minibatch from the ratios above, before its step, and steps only while kl <= limit; the first one beyond it sets a latch
+on the device and is stopped, with every update behind it, until kl_reset().  The host never reads the estimate, so E
+epochs of M minibatches stay E M replays of one captured update.  learner.kl and learner.kl_state are device tensors.
+Nothing is claimed about learning curves.
 """
 from __future__ import annotations
 
@@ -340,6 +347,71 @@ class DeviceActorCritic(Handle):
                    "uavtrack_learner_get_advantage")
         return ("raw", "batch", self._advantage)[mode.value], eps.value
 
+    # ---- KL early stopping
+    _kl_limit = None                                                  # None while off, else the limit as set
+    kl = None                                                         # float32 [1]: the last evaluated minibatch's KL
+    kl_state = None                                                   # int32 [2]: (stopped, skipped)
+
+    def set_kl_stop(self, limit: Optional[float]) -> None:
+        """PPO's `if approx_kl > limit: break` without the host (uavtrack_learner_set_kl_stop; loss="per_sample" only;
+        None turns it off).  While on, every update(..., clip_eps=) and update_from(ring | sweep, K, clip_eps=) forms the
+        KL estimate mean_i((r_i - 1) - log r_i) of its own minibatch from the ratios of the policy as it stands
+        (float64 sums in the fixed order of include/uavtrack.h, unweighted) into `kl`, and steps only where it does not
+        exceed `limit` (compared in float32; inf observes and never stops).  The first update beyond it sets a latch on
+        the device and is stopped, and so is every later one, whatever its own KL, until kl_reset(): nothing moves
+        (parameters, moments, step counts, the target critic, priorities), the losses are NaN, and check() does not count
+        it.  `kl` (float32 [1]) and `kl_state` (int32 [2]: stopped, skipped since the last reset) are device tensors;
+        reading them is the caller's own synchronisation, and no call here synchronises.  A ring's draw counter and a
+        sweep's cursor are advanced by the draw, so they move under stopped updates too (sweep.rebind() or seek rewind
+        as before).  A refused update never sets the latch and leaves kl NaN; an underflowed ratio of 0 gives inf.
+        A host-side setting like set_advantage: it holds for every update enqueued afterwards, a captured graph keeps
+        the one it was captured with (the latch is device state, so replays obey it), and checkpoints and
+        sharding.broadcast_learner do not carry it.  Turning it on allocates, so not inside a graph capture.  While on,
+        an update without clip_eps, grad_from, apply, update_from_many and the group path raise: the estimate needs the
+        clipped surrogate's ratios, and a gradient row has nowhere to carry a KL sum."""
+        if limit is None:
+            _lib.check(self._lib.uavtrack_learner_set_kl_stop(self._h, 0, float("inf"), None, None),
+                       "uavtrack_learner_set_kl_stop")
+            self._kl_limit = self.kl = self.kl_state = None
+            return
+        lim = float(limit)
+        if not lim >= 0.0:                                            # NaN fails the comparison
+            raise ValueError(f"set_kl_stop: limit = {limit!r} must be >= 0 (inf observes and never stops)")
+        if self.loss != "per_sample":
+            raise ValueError('set_kl_stop on a loss="reference" learner: the estimate is formed from the clipped '
+                             'surrogate\'s ratios, which that form does not have; use loss="per_sample"')
+        kl = torch.full((1,), float("nan"), device=self.device)
+        state = torch.zeros(2, dtype=torch.int32, device=self.device)
+        _lib.check(self._lib.uavtrack_learner_set_kl_stop(self._h, 1, lim, _ptr(kl), _ptr(state)),
+                   "uavtrack_learner_set_kl_stop")
+        self._kl_limit, self.kl, self.kl_state = lim, kl, state
+
+    def get_kl_stop(self) -> Optional[float]:
+        """The limit as last set, or None while off."""
+        on, limit, kl, state = C.c_int32(), C.c_double(), C.c_void_p(), C.c_void_p()
+        _lib.check(self._lib.uavtrack_learner_get_kl_stop(self._h, C.byref(on), C.byref(limit), C.byref(kl), C.byref(state)),
+                   "uavtrack_learner_get_kl_stop")
+        return limit.value if on.value else None
+
+    def kl_reset(self) -> None:
+        """kl_state <- (0, 0): stream-ordered, capturable (uavtrack_learner_kl_reset); an error while off."""
+        if self._kl_limit is None:
+            raise RuntimeError("kl_reset: KL early stopping is off (set_kl_stop)")
+        _lib.check(self._lib.uavtrack_learner_kl_reset(self._h, self._stream()), "uavtrack_learner_kl_reset")
+
+    def _kl_refuses_split(self, what: str) -> None:
+        """Raises while KL early stopping is on: `what` is a piece of the split update."""
+        if self._kl_limit is not None:
+            raise ValueError(f"{what} while KL early stopping is on (set_kl_stop): a gradient row has nowhere to carry a KL "
+                             f"sum, so the split update is refused; use update or update_from with clip_eps, or "
+                             f"set_kl_stop(None)")
+
+    def _kl_refuses_unclipped(self, what: str, clip_eps) -> None:
+        """Raises while KL early stopping is on and `what`, a closed update, comes without clip_eps."""
+        if self._kl_limit is not None and clip_eps is None:
+            raise ValueError(f"{what} without clip_eps while KL early stopping is on (set_kl_stop): the estimate is formed "
+                             f"from the clipped surrogate's ratios; pass clip_eps (inf never clips), or set_kl_stop(None)")
+
     def _params(self):
         return list(self._actor.parameters()) + list(self._critic.parameters())
 
@@ -511,6 +583,9 @@ class DeviceActorCritic(Handle):
         _stored (_clipped's with advantages per slot behind the discounts, log_mu NULL without clip_eps); then the
         outputs."""
         n, store, capacity, idx, _, weights, discounts, log_mu, clip_eps, ratio_out, advantages = b
+        if kind == "grad":
+            self._kl_refuses_split("uavtrack_learner_grad")
+        self._kl_refuses_unclipped("uavtrack_learner_update", clip_eps)
         if isinstance(self._advantage, str) and self._advantage == "batch" and n < 2:
             raise ValueError(f'n = {n} row under set_advantage("batch"): the standard deviation of a batch needs two rows')
         w = _lib.tensor_arg(weights, torch.float32, n, self.device,
@@ -572,6 +647,7 @@ class DeviceActorCritic(Handle):
         discounts (row i is slot i here), in td_delta's place wherever the actor uses one, the advantage mode applied on
         top (uavtrack_learner_update_stored); the critic, td_delta and the priorities keep td_delta.  One that is NaN or
         infinite refuses the update on the device."""
+        self._kl_refuses_unclipped("update", clip_eps)
         dev = self.device
         s = torch.as_tensor(transition_dict["states"], device=dev, dtype=torch.float32).reshape(-1, _lib.OBS_DIM).contiguous()
         n = s.shape[0]
@@ -616,6 +692,9 @@ class DeviceActorCritic(Handle):
         (sharding.gather_learner_rows), the apply of all of them, and the priority write into this rank's buffer.
         Ranks that start equal (sharding.broadcast_learner) stay bitwise equal; batch sizes may differ between ranks.
         The returned losses are the global ones, td_delta this rank's."""
+        if group is not None:
+            self._kl_refuses_split("update_from(group=)")
+        self._kl_refuses_unclipped("update_from", clip_eps)
         spec = DrawSpec(importance=importance, beta=beta, beta_final=beta_final, anneal_calls=anneal_calls,
                         rho_bar=rho_bar, rho_out=rho_out, generator=generator, clip_eps=clip_eps, ratio_out=ratio_out)
         if group is None:
@@ -654,6 +733,7 @@ class DeviceActorCritic(Handle):
         of either ring live in the ring's own draw tensor until its next draw: call write_priorities (or clone
         them) before drawing from the same ring again.  The other arguments are the fields of replay.DrawSpec; the
         row's sums carry the weights it describes."""
+        self._kl_refuses_split("grad_from")
         return self._grad_drawn(buffer, batch_size, DrawSpec(
             importance=importance, beta=beta, beta_final=beta_final, anneal_calls=anneal_calls, rho_bar=rho_bar,
             rho_out=rho_out, generator=generator, clip_eps=clip_eps, ratio_out=ratio_out), row)
@@ -667,6 +747,7 @@ class DeviceActorCritic(Handle):
         """One update from gradient rows ([count, row_floats], or a sequence of rows): the sums added in row order, one
         global scale, both Adam steps.  Returns (actor_loss, critic_loss) as device tensors, without synchronising.  A
         row that carries a refusal (or another learner's layout) refuses the whole update, on every participant."""
+        self._kl_refuses_split("apply")
         if not torch.is_tensor(rows):
             rows = torch.stack([r.reshape(-1) for r in rows])
         rows = rows.reshape(-1, rows.shape[-1])
@@ -697,6 +778,7 @@ class DeviceActorCritic(Handle):
         are the fields of replay.DrawSpec, one spec for every buffer (each draw's weights normalised by its own maximum,
         with rho_bar or clip_eps every buffer a behaviour ring), except rho_out and ratio_out: each a sequence of one
         float32 [k] tensor (or None) per buffer."""
+        self._kl_refuses_split("update_from_many")
         buffers = list(buffers)
         if not 1 <= len(buffers) <= _lib.LEARNER_MAX_ROWS:
             raise ValueError(f"update_from_many: {len(buffers)} buffers, one apply takes 1 to {_lib.LEARNER_MAX_ROWS} rows")

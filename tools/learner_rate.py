@@ -13,6 +13,7 @@ softmax, losses and Adam are not counted.
     python tools/learner_rate.py --target [--quick]
     python tools/learner_rate.py --clipped
     python tools/learner_rate.py --normalised
+    python tools/learner_rate.py --kl
 
 --regularised times the device update alone (loss="per_sample") under four settings of
 DeviceActorCritic.set_regularisation: everything off, the entropy bonus on, clipping on, both.  "off" enqueues the
@@ -35,6 +36,13 @@ section 4.11's rule); the clipped figure is reported, not a pass mark.
 (mean, inv_std) pair (the gradient kernel's normalising instantiation alone) and "batch" (the TD pass, the statistics and
 one sealing launch on top) --, each without and with clip_eps = 0.2, the six alternating.  A/B against another build as
 for --clipped; a library without the advantage symbols prints only its "raw" figures, and "raw" is the figure the rule
+above holds to.
+
+--kl times the same clipped update_from (clip_eps = 0.2) in three states of DeviceActorCritic.set_kl_stop -- off; on with
+limit = inf, which adds the KL pass (two small launches) and never trips; on and latched (the latch written by hand), where
+the gradient kernel returns before its first tile and everything behind it is gated off -- each as eager calls and as
+replays of a graph that holds the one update_from (draw and update), the six alternating.  A/B against another build as
+for --clipped; a library without the KL symbols prints only its "off" figures, and the eager "off" is the figure the rule
 above holds to.
 """
 import argparse
@@ -171,6 +179,44 @@ def normalised(n=65536, H=128, A=12, slots=1 << 21):
     print(json.dumps(out), flush=True)
 
 
+def kl(n=65536, H=128, A=12, slots=1 << 21):
+    """The clipped update_from with the KL stop off, on and latched, eager and as a one-call graph replay: one JSON line."""
+    sys.path.insert(0, os.path.join(ROOT, "tools"))
+    from nstep_rate import alternating
+    from offpolicy_rate import filled
+    names = ["off"] + (["on", "latched"] if hasattr(uavtrack._lib.load(), "uavtrack_learner_set_kl_stop") else [])
+    learners = {k: uavtrack.DeviceActorCritic(12, H, A, 1e-4, 5e-4, 0.95, "cuda:0", loss="per_sample", max_batch=n)
+                for k in names}
+    ring = filled(uavtrack.ReplayRing(slots, "cuda:0", seed=1, max_batch=n).with_behaviour(), learners["off"])
+    for name in names[1:]:
+        learners[name].set_kl_stop(float("inf") if name == "on" else 0.0)
+    calls, graphs, held = {}, {}, []
+    for name, L in learners.items():
+        calls[name] = lambda L=L: L.update_from(ring, n, clip_eps=0.2)
+        for _ in range(3):
+            calls[name]()
+        if name == "latched":
+            L.kl_state[:1].fill_(1)                                 # (an on-policy ring never trips it on its own)
+        torch.cuda.synchronize()
+        graphs[name] = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(graphs[name]):
+            held.append(calls[name]())
+        calls[name + "_graph"] = graphs[name].replay
+    res = alternating(calls, reps=20)
+    out = {"what": "update_from", "ring": "uniform", "n": n, "H": H, "A": A, "slots": slots, "clip_eps": 0.2,
+           "lib": os.environ.get("UAVTRACK_LIB", "this build")}
+    for name, (med, runs) in res.items():
+        out[name + "_us"] = round(med, 1)
+        out[name + "_runs_us"] = [round(x, 1) for x in runs]
+    if "on" in names:
+        out["on_kl"] = float(learners["on"].kl)
+        out["on_state"], out["latched_state"] = learners["on"].kl_state.tolist(), learners["latched"].kl_state.tolist()
+    for x in list(learners.values()) + [ring]:
+        x.check()
+        x.close()
+    print(json.dumps(out), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--quick", action="store_true", help="n 65536, H 128 only")
@@ -182,6 +228,8 @@ def main():
                     help="time update_from at n 65536, H 128 from a uniform behaviour ring without and with clip_eps = 0.2")
     ap.add_argument("--normalised", action="store_true",
                     help="time update_from at n 65536, H 128 under set_advantage raw / given / batch, without and with clip_eps")
+    ap.add_argument("--kl", action="store_true",
+                    help="time the clipped update_from at n 65536, H 128 with the KL stop off, on and latched, eager and replayed")
     ap.add_argument("--settings", default=None, help="--regularised: a comma-separated subset of off,entropy,clip,both; "
                                                      "--target: of off,polyak,periodic")
     ap.add_argument("--reps", type=int, default=100)
@@ -191,6 +239,8 @@ def main():
         return clipped()
     if args.normalised:
         return normalised()
+    if args.kl:
+        return kl()
     dev = "cuda:0"
     A = 12
     grid = [(65536, 128)] if args.quick else [(n, H) for H in (64, 128, 256) for n in (4096, 65536, 262144)]
