@@ -1,6 +1,8 @@
 """Cases, error scales and tolerances for the device learner's gradients, element by element against float64.  Plain
 numpy and torch on the CPU; used by test_learner_gradients_cpu.py (no GPU) and test_hip_learner_gradients.py.  The
-whole-blob bound learner_harness.tol_g stays what it is; this sits beside it.
+whole-blob bound learner_harness.tol_g stays what it is; this sits beside it.  The seven bodies below reach the first four
+gradient kernels; the clip, advantage and stored kernels have their cases, float64 side and tables in
+tests/learner_gradient_forms.py, on this module's metric, comparator and fp32 references (`--forms` prints its tables).
 
 Two observables, one float64 result (`fp64`).  The gradient row of DeviceActorCritic._grad holds the P UNSCALED sums
 the gradient kernel accumulates and the four loss sums; a fresh learner's closed update leaves exp_avg = fl(0.1f g), g
@@ -88,6 +90,7 @@ import zlib
 
 import numpy as np
 
+import learner_advantage_mirror as am
 import learner_harness as lh
 import learner_mirror as mirror
 import pmi_gradient_cases as pc
@@ -241,8 +244,9 @@ def logit_spread(blob, H, A, s):
     return float((z.max(axis=1) - z.min(axis=1)).max())
 
 
-def _build(sp, halves):
-    """The case of sp over `halves` batches of sp.n rows each (two for a second-step case)."""
+def _build(sp, halves, distinct=False):
+    """The case of sp over `halves` batches of sp.n rows each (two for a second-step case); distinct: an index vector
+    names no slot twice (the form cases, whose per-slot stores are dealt by batch row)."""
     H, A, n = sp.H, sp.A, sp.n
     seed = zlib.crc32(repr((tuple(sp), halves)).encode()) % (2 ** 31 - 1)
     rng = np.random.RandomState(seed)
@@ -253,7 +257,10 @@ def _build(sp, halves):
     s, a, r, s2 = lh.batch(rng, cap, A)
     if sp.shift:
         r = (r + F32(1.5)).astype(F32)
-    if sp.gather:
+    if sp.gather and distinct:
+        perm = rng.permutation(cap).astype(np.int64)
+        idx = [perm[h * n:(h + 1) * n] for h in range(halves)]
+    elif sp.gather:
         idx = [rng.randint(0, cap, size=n).astype(np.int64) for _ in range(halves)]
     else:
         idx = [np.arange(h * n, (h + 1) * n) for h in range(halves)]
@@ -352,10 +359,11 @@ def _network_factors(c, lt, n, coef, size):
     return np.concatenate([np.full(na, fa), np.full(size - na, 2.0 / n * coef[1])])
 
 
-def gradient_scales(c, f, gz, gv, lt, coef=(1.0, 1.0)):
-    """(S of the row's P + 4 words, S of the scaled gradient's P words): the float64 sums of the absolute terms."""
+def gradient_scales(c, f, gz, gv, lt, coef=(1.0, 1.0), agz=None):
+    """(S of the row's P + 4 words, S of the scaled gradient's P words): the float64 sums of the absolute terms.  agz:
+    the absolute parts of the logit weights where they are not |gz| (the form cases, below)."""
     n = f.n
-    sa_, agz, agv = np.abs(f.s), np.abs(gz), np.abs(gv)
+    sa_, agz, agv = np.abs(f.s), np.abs(gz) if agz is None else agz, np.abs(gv)
     adh = (agz @ np.abs(f.w2a)) * (f.pa > 0)
     adc = agv[:, None] * np.abs(f.w2c) * (f.pc > 0)
     S = np.concatenate([x.ravel() for x in (adh.T @ sa_, adh.sum(0), agz.T @ f.ha, agz.sum(0), adc.T @ sa_, adc.sum(0),
@@ -382,10 +390,13 @@ def errors(got, ref, S, H, A, slack=None):
 
 # ---- the two fp32 references
 
-def torch_fp32(c):
+def torch_fp32(c, stats=None, out=None):
     """(row words [P + 4], scaled gradient [P]) of batch 0 by torch's fp32 autograd on the CPU: the unscaled sums are
     the gradient of sum_i w_i (coef_i log p_i(a_i) + c H_i) + sum_i w_i (V_i - y_i)^2 / 2 with delta and y detached,
-    the scales are formed in fp32 from the loss sums as the finalize kernel forms them."""
+    the scales are formed in fp32 from the loss sums as the finalize kernel forms them.  A form case (c.form, below)
+    has its surrogate in coef_i log p_i(a_i)'s place: A_i log p_i(a_i), or r_i A_i where the row passes and bound A_i
+    where it does not, A_i a constant; stats = (mean, inv_std) of a "batch" form; out, a dict, receives "pass", "ratio"
+    and "adv" of the rows."""
     import torch
     (s, a, r, s2), w, d = batch_of(c)
     H, A, n = c.H, c.A, c.n
@@ -403,11 +414,29 @@ def torch_fp32(c):
     delta = (y - v).detach()
     lpa = logp[torch.arange(n), torch.from_numpy(np.asarray(a, np.int64))]
     ent = -(torch.exp(logp) * logp).sum(dim=1)
-    coef = delta if c.loss == "per_sample" else torch.ones(n)
-    ((iw * (coef * lpa + float(c.c) * ent)).sum() + (iw * (v - y) ** 2).sum() / 2).backward()
+    if getattr(c, "form", None) is None:
+        coef = delta if c.loss == "per_sample" else torch.ones(n)
+        gain, surr = coef * lpa, lpa * delta
+    else:
+        adv = t(_advantage32(c, delta.numpy(), stats))
+        if c.form.clip is None:
+            ok, ratio, gain = None, None, adv * lpa
+        else:
+            lo, hi = (float(x) for x in mirror.bounds(c.form.clip))
+            ratio = torch.exp(lpa - t(c.log_mu[c.idx[0]]))
+            with torch.no_grad():
+                ok = torch.where(adv >= 0, ratio <= hi, ratio >= lo)
+                edge = torch.where(adv >= 0, torch.tensor(hi), torch.tensor(lo))
+                flat = torch.where(ok, torch.zeros(n), edge * adv)      # (inf * 0 on a passing row is not selected)
+            gain = torch.where(ok, ratio * adv, flat)
+        surr = gain.detach()
+        if out is not None:
+            out.update({"pass": None if ok is None else ok.numpy(), "adv": adv.numpy(),
+                        "ratio": None if ratio is None else ratio.detach().numpy()})
+    ((iw * (gain + float(c.c) * ent)).sum() + (iw * (v - y) ** 2).sum() / 2).backward()
     sums = torch.cat([p.grad.reshape(-1) for p in prm])
     with torch.no_grad():
-        loss4 = torch.stack([(-lpa * iw).sum(), (delta * iw).sum(), (iw * (-lpa * delta - float(c.c) * ent)).sum(),
+        loss4 = torch.stack([(-lpa * iw).sum(), (delta * iw).sum(), (iw * (-surr - float(c.c) * ent)).sum(),
                              (iw * (v - y) ** 2).sum()])
     return _finish32(c, sums.numpy(), loss4.numpy())
 
@@ -426,9 +455,19 @@ def _finish32(c, sums, loss4):
     return np.concatenate([sums, loss4]).astype(np.float64), g.astype(np.float64)
 
 
-def sequential_fp32(c):
+def _advantage32(c, delta32, stats):
+    """The float32 advantage of a form case's batch 0 from a reference's own float32 delta: the stored value where there
+    is one, through fl(fl(x - mean) * inv_std) unless raw."""
+    x = c.advantages[c.idx[0]] if c.form.stored else np.asarray(delta32, F32)
+    if c.form.adv == "raw":
+        return x
+    mean, inv = c.given if c.form.adv == "given" else stats
+    return am.standardise(x, mean, inv)
+
+
+def sequential_fp32(c, stats=None, out=None):
     """(row words, scaled gradient) of batch 0 in numpy float32, every sum over rows taken one row after another in
-    ascending order."""
+    ascending order.  stats and out as torch_fp32's."""
     (s, a, r, s2), w, d = batch_of(c)
     H, A, n = c.H, c.A, c.n
     w1a, b1a, w2a, b2a, w1c, b1c, w2c, b2c = (x.astype(F32) for x in mirror.unpack(c.blob, H, A))
@@ -447,10 +486,25 @@ def sequential_fp32(c):
     ent = -np.where(p > 0, p * logp, F32(0)).sum(axis=1)
     onehot = np.zeros_like(p); onehot[np.arange(n), a] = 1
     nlp = -logp[np.arange(n), a]
-    coef = delta if c.loss == "per_sample" else np.ones(n, F32)
+    if getattr(c, "form", None) is None:
+        coef = delta if c.loss == "per_sample" else np.ones(n, F32)
+        actor = nlp * delta
+    else:
+        adv = _advantage32(c, delta, stats)
+        if c.form.clip is None:
+            ok, ratio, coef, actor = None, None, adv, nlp * adv
+        else:
+            with np.errstate(over="ignore", invalid="ignore"):
+                lo, hi = F32(1.0) - F32(c.form.clip), F32(1.0) + F32(c.form.clip)
+                ratio = np.exp(-nlp - c.log_mu[c.idx[0]])
+                ok = np.where(adv >= 0, ratio <= hi, ratio >= lo)
+                coef = np.where(ok, adv * ratio, F32(0))
+                actor = -np.where(ok, coef, np.where(adv >= 0, hi, lo) * adv)
+        if out is not None:
+            out.update({"pass": ok, "adv": adv, "ratio": ratio})
     gz = iw[:, None] * (coef[:, None] * (onehot - p) - F32(c.c) * np.where(p > 0, p * (logp + ent[:, None]), F32(0)))
     gv = (v - y) * iw
-    lt = np.stack([nlp * iw, delta * iw, iw * (nlp * delta - F32(c.c) * ent), (v - y) ** 2 * iw], axis=1)
+    lt = np.stack([nlp * iw, delta * iw, iw * (actor - F32(c.c) * ent), (v - y) ** 2 * iw], axis=1)
     dh = (gz @ w2a) * (pa > 0)
     dc = gv[:, None] * w2c * (pc_ > 0)
     for x in (gz, gv, lt, dh, dc, ha, hc):
@@ -653,8 +707,15 @@ if __name__ == "__main__":
     import os
     import sys
     sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "marl-uavs-targets-tracking_amd"))
-    row, grad = measure()
-    for title, table in (("WORST_ROW", row), ("WORST_GRAD", grad)):
+    forms = "--forms" in sys.argv                               # the form cases' tables (learner_gradient_forms.py)
+    if forms:
+        import learner_gradient_forms
+        row, grad, ratio = learner_gradient_forms.measure()
+        print("RATIO_WORST =", {k: float(f"{x:.2e}") for k, x in ratio.items()})
+    else:
+        row, grad = measure()
+    for title, table in (("FORM_WORST_ROW", row), ("FORM_WORST_GRAD", grad)) if forms else \
+            (("WORST_ROW", row), ("WORST_GRAD", grad)):
         print(f"{title} = {{")
         for k, t in table.items():
             print(f'    "{k}": {{')
@@ -665,7 +726,8 @@ if __name__ == "__main__":
     for title, table in (("row", row), ("scaled gradient", grad)):
         print(f"    {title:<18}" + "".join(f"{k:>16}" for k in table))
         for w in table["two"]:
-            print(f"    {w:<18}" + "".join(f"{table[k][w][0]:>11.2e} {table[k][w][1][:3]:<4}" for k in table))
+            print(f"    {w:<18}" + "".join(f"{table[k][w][0]:>11.2e} {table[k][w][1][:3]:<4}" if w in table[k] else
+                                           f"{'':>16}" for k in table))
     if "--who" in sys.argv:
         for table in (row, grad):
             for k, t in table.items():
